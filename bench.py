@@ -20,6 +20,10 @@ one CPython-exact stream and token draws are keyed by global chain id, so the ga
 N = 1 result: rank 0 re-runs the whole job on its own GPU after the timed region and asserts that (`verified_vs_single_gpu`).
 `--weak` keeps 256 chains per GPU instead.
 
+`--dump-outputs DIR` writes what the last timed step handed back -- the token buffer, and that step's logits and draws at the
+sampled positions -- as DIR/<name>.npy (float32) after the timed region.  Every input is seeded (seeds, weights, position stream,
+draws), so equal arguments give equal inputs and two builds can be compared array for array.
+
 Output: ONE JSON line (rank 0) with the driver's contract plus
   roofline     -- the GEMM kernel family (96.5 % of the FLOPs): executed FLOPs / HIP-event time on the engine's stream
   strict_mode  -- (N = 1) the same workload in the parity mode (PG_PREC_FP32: split-bf16 x3 GEMMs and attention): its
@@ -43,7 +47,8 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MFMA_BF16_PEAK_TFLOPS = 2500.0     # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_BF16_PEAK_TFLOPS = 2500.0     # dense bf16 MFMA peak of the MI355X (see roofline.peak_note)
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: all files together
 TOTAL_CHAINS = 256                 # BASELINE.json configs[1] / configs[2]
 SYNTH_KW = dict(std=0.025, embed_std=0.3, ln_jitter=0.1)     # seeded synthetic weights at a realistic logit scale (std ~ 10)
 
@@ -81,6 +86,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-shard-proxy", action="store_true",
                     help="N = 1: skip the shard_proxy leg (128 / 64 / 32 chains of the 256-chain job on this one GPU: what one GPU of "
                          "BASELINE config 3 runs at 2 / 4 / 8 GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last timed step handed back as DIR/<name>.npy (float32) -- tokens "
+                         "[chains, L + 2], the final token buffer of the timed job itself; last_step_logits [chains, P, vocab] and "
+                         "last_step_sampled_tokens [chains, P], the optional outputs of the same native call for that step (from an "
+                         "untimed replay of the job that must end in the same tokens).  Inputs are seeded: equal arguments give equal "
+                         "inputs, so two builds can be compared array for array.  Past 64 MB a fixed seeded subset of the chains")
     ap.add_argument("--force-dist", action="store_true",
                     help="N = 1: still create the torch.distributed process group (world_size 1) and run the final all-gather "
                          "through it, so that the RCCL path is executed on a single GPU")
@@ -404,7 +415,8 @@ def main():
             self.params = _lib.make_sample_params(True, cfg["mask_idx"], top_k, burnin, 1.0, valid_idx, rng_seed=0, rng_stream=0,
                                                   row_id_base=c_lo)
 
-        def run(self, n_iters):
+        def run(self, n_iters, logits=None, sampled=None):
+            """logits [n_iters, chains, P, vocab] fp32 / sampled [n_iters, chains, P] int32: the call's optional per-step outputs."""
             table = sharding.global_position_table(self.pos_rng, population, P, n_iters, B_total)
             mine = sharding.local_slice(table, self.c_lo, self.c_hi)
             self.params.iter_base = self.done
@@ -413,7 +425,9 @@ def main():
                 return mine
             d_idx = torch.from_numpy(mine).to(dev, non_blocking=True)
             _lib.check(L_.pg_esm_gibbs_run_device(self.engine.handle, ctypes.c_void_p(self.tok.data_ptr()), self.c_hi - self.c_lo, T,
-                                                  ctypes.c_void_p(d_idx.data_ptr()), n_iters, P, ctypes.byref(self.params), None, None))
+                                                  ctypes.c_void_p(d_idx.data_ptr()), n_iters, P, ctypes.byref(self.params),
+                                                  None if logits is None else ctypes.c_void_p(logits.data_ptr()),
+                                                  None if sampled is None else ctypes.c_void_p(sampled.data_ptr())))
             return d_idx                                     # caller keeps it alive until the stream is synchronised
 
     def barrier():
@@ -451,6 +465,33 @@ def main():
     if not dry:
         assert ((final[:, 1:-1] >= 4) & (final[:, 1:-1] <= 23)).all(), "chains left the 20-amino-acid alphabet"
 
+    # ---- --dump-outputs: what the last timed step handed back (rank 0, outside the timed region) ----------------------------
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {"tokens": final}
+        if not dry:
+            # The timed call passes NULL for the optional per-step outputs, as the drivers do.  The same job run again from the
+            # seeds -- W + K - 1 steps, then the last one with both output buffers -- gives that step's logits at the sampled
+            # positions and its draws; every draw is keyed by (seed, chain, iteration), so the replay must end in the timed job's tokens.
+            rj = Job(lm, 0, B_total)
+            if W + K > 1:
+                keep_r = rj.run(W + K - 1)
+            lg = torch.empty((1, B_total, P, cfg["vocab"]), dtype=torch.float32, device=dev)
+            st = torch.empty((1, B_total, P), dtype=torch.int32, device=dev)
+            keep_r = rj.run(1, lg, st)                                 # noqa: F841
+            torch.cuda.synchronize(dev)
+            assert (rj.tok.cpu().numpy() == final).all(), "the replay for --dump-outputs ended in other tokens than the timed job"
+            arrays["last_step_logits"] = lg[0].cpu().numpy()
+            arrays["last_step_sampled_tokens"] = st[0].cpu().numpy()
+        n_fit = (DUMP_MAX_BYTES - 4096) // (4 * sum(a[0].size for a in arrays.values()))      # 4096: the .npy headers
+        if n_fit < B_total:
+            rows = np.sort(np.random.default_rng(0).choice(B_total, n_fit, replace=False))
+            arrays = {name: a[rows] for name, a in arrays.items()}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float32))
+        dumped = {name: list(a.shape) for name, a in arrays.items()}
+
     mode = {"bf16": "bf16", "fp16": "fp16", "fp32": "bf16x3"}[args.precision]
     out = {"metric": "sampled positions/sec (whole node), ESM-1b L=256 B=256 Gibbs", "value": B_total * P * K / elapsed,
            "unit": "sampled positions/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K,
@@ -470,6 +511,8 @@ def main():
            "ranks_seen": 1, "backend": backend if dist is not None else None,
            "per_rank_elapsed_s": {"min": min(rank_elapsed), "max": max(rank_elapsed), "ranks": rank_elapsed,
                                   "chains_per_rank": counts}}
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "float32_arrays": dumped}
     if dist is not None:
         # counted, not assumed: every rank contributes a one to an all-reduce on the job's backend
         ones = torch.ones(1, dtype=torch.int64, device=dev if backend == "nccl" else "cpu")

@@ -59,3 +59,20 @@ def test_cpu_baseline_leg_and_traffic_file_selection():
     assert "2 of 256 chains x 2 Gibbs iterations" in out["sample"]
     assert out["logit_check"]["torch_baseline_vs_checker_max_abs"] < 1e-3
     assert out["config1"]["cpu_ms_per_iter"] > 0 and out["reference_style_position_loop"]["us_per_position_one_core"] > 0
+
+
+def test_dump_outputs_writes_the_final_tokens_once_and_reproducibly(tmp_path):
+    """`--dump-outputs DIR`: rank 0 alone writes DIR/tokens.npy (float32, [chains, L + 2]); the inputs are seeded, so a second run --
+    here with another number of ranks -- writes the same array.  (A dry run never touches the tokens: they are the seeds.)"""
+    import numpy as np
+    got = []
+    for n in (2, 1):
+        d = tmp_path / ("ranks%d" % n)
+        out = _run("--gpus", str(n), "--dump-outputs", str(d))
+        assert out["dumped_outputs"] == {"dir": str(d), "float32_arrays": {"tokens": [256, 258]}}
+        assert sorted(os.listdir(d)) == ["tokens.npy"]
+        a = np.load(d / "tokens.npy")
+        assert a.dtype == np.float32 and a.shape == (256, 258)
+        assert (a[:, 0] == 0).all() and (a[:, -1] == 2).all() and (a[:, 1:-1] >= 4).all() and (a[:, 1:-1] <= 23).all()
+        got.append(a)
+    assert (got[0] == got[1]).all()
