@@ -82,6 +82,19 @@ typedef struct pg_engine pg_engine;
                            attention key / value per layer (`layers.i.self_attn.bias_k` / `bias_v`, d_model values each), untied output
                            projection `embed_out.weight` [V][d] + `embed_out.bias` [V], no LM-head dense / LayerNorm, no token
                            dropout; vocabulary of 35 (<cls> = 32, <mask> = 33).  Runs through the ESM-1b entry points. */
+#define PG_ARCH_ESM2 4  /* fair-esm ESM2 (esm2_t33_650M_UR50D; any ESM-2 size with heads of 64 and d_model <= 2048).  The ESM-1b block
+                           stack, token dropout, emb_layer_norm_after and tied RoBERTa LM head, with three differences: no position
+                           table (`embed_positions.weight` is neither required nor read) -- positions enter through ROTARY embeddings
+                           applied to q and k of every attention layer ("rotate-half" pairs (i, i + 32) of each 64-wide head, angle
+                           float(t) * 10000^(-2i/64), t = the token's index along the sequence axis whether or not it is <pad>; one
+                           extra launch per layer between the QKV projection and the attention kernel, all three precision modes;
+                           the cos / sin table of max_positions + 2 rows is built when the engine is created); no
+                           emb_layer_norm_before (not required); vocabulary of 33 as ESM-1b.  Tensors read: `embed_tokens.weight`,
+                           `layers.i.*` as ESM-1b, `emb_layer_norm_after.*`, `lm_head.dense.*`, `lm_head.layer_norm.*`, `lm_head.bias`;
+                           `layers.i.self_attn.rot_emb.inv_freq` and `contact_head.*` are ignored when handed in.  Runs through the
+                           pg_esm_* entry points (the pg_msa_* ones answer PG_ERR_INVALID); max_positions bounds T as for ESM-1b
+                           (default 1024).  The persistent single-chain trunk is ESM-1b-only: ESM-2 chains of <= 32 token rows take
+                           the per-layer launches (weight-streaming GEMMs, hipGraph replay). */
 
 #define PG_PREC_BF16 0 /* bf16 MFMA operands, fp32 accumulate, fp32 residual stream (throughput mode) */
 #define PG_PREC_F16 2  /* the throughput mode with IEEE fp16 operands instead of bf16 (same kernels, same MFMA rate; 3 more mantissa
@@ -103,7 +116,7 @@ typedef struct {
   int32_t n_layers;      /* 33 / 12 */
   int32_t n_heads;       /* d_model / 64: head dim is 64 in both models */
   int32_t d_ffn;         /* 5120 / 3072; multiple of 128 */
-  int32_t max_positions; /* learned position table has max_positions + pad_idx + 1 rows */
+  int32_t max_positions; /* learned position table has max_positions + pad_idx + 1 rows (ESM-2: longest T; sizes the rotary table) */
   int32_t pad_idx, mask_idx, cls_idx, eos_idx;
   int32_t token_dropout; /* 1 for ESM-1b, 0 for MSA-1b */
   int32_t max_msa_rows;  /* rows of msa_position_embedding (1024), 0 for ESM-1b */
@@ -274,7 +287,8 @@ int pg_dbg_gather_plan(int rank, int world, int64_t rows, int width, const int64
 
 /* ---- measurement ---------------------------------------------------------------------------
  * HIP-event timing of kernel classes on the engine's stream (bench.py's roofline figure).
- * class names: "gemm", "attention", "layernorm", "embed", "head", "sample".  */
+ * class names: "gemm", "attention", "layernorm", "embed", "head", "sample", and "rope": ESM-2's rotation of q and k, timed under
+ * its own class (not under "attention"; no launch of the other architectures falls into it).  */
 int pg_prof_enable(pg_engine*, int on);
 int pg_prof_reset(pg_engine*);
 int pg_prof_get(pg_engine*, const char* kernel_class, double* total_ms, int64_t* launches);
@@ -309,6 +323,9 @@ int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float
 /* softmax(q k^T) v per (b, h); q already scaled; qkv[B][T][3*H*64] fp32 -> ctx[B][T][H*64]; PG_PREC_BF16 or PG_PREC_FP32
  * (split-bf16 MFMA kernel, output = hi + lo of the operand rows it writes) or PG_PREC_F16 (the bf16 kernel with fp16 operands) */
 int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, int B, int T, int H);
+/* ESM-2's rotary embedding: the q and k thirds of qkv_inout[B*T][3*H*64] (fp32 host buffer) rotated in place, row r at position
+ * r % T, in `precision` (16-bit modes: through a device buffer of that type, the result widened back); the v third is left alone */
+int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H);
 
 /* MSA attention blocks: qkv[B][R][C][3*H*64] fp32 -> ctx[B][R][C][H*64]; which = 0 tied row attention (scores * scale),
  * 1 column attention (q pre-scaled); 2 / 3 = the same two with the strict precision mode's kernels; 4 / 5 = 0 / 1 with fp16

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("PGIBBS_LIB_PATH") or os.path.join(_HERE, "lib", "libp
 
 PG_OK = 0
 PG_ERR_INVALID, PG_ERR_HIP, PG_ERR_NO_DEVICE, PG_ERR_WEIGHTS, PG_ERR_UNSUPPORTED, PG_ERR_RANGE = 1, 2, 3, 4, 5, 6
-PG_ARCH_ESM1B, PG_ARCH_MSA1B, PG_ARCH_ESM1 = 1, 2, 3
+PG_ARCH_ESM1B, PG_ARCH_MSA1B, PG_ARCH_ESM1, PG_ARCH_ESM2 = 1, 2, 3, 4
 PG_COMM_ID_BYTES = 128
 PG_PREC_BF16, PG_PREC_FP32, PG_PREC_F16 = 0, 1, 2
 INT32_MAX = 2**31 - 1
@@ -114,6 +114,7 @@ SIGNATURES = [
     ("pg_dbg_qkv_attention_bench", c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
     ("pg_dbg_layernorm", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),
     ("pg_dbg_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int]),
+    ("pg_dbg_rope", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int]),
     ("pg_dbg_msa_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float]),
 ]
 

@@ -138,7 +138,7 @@ int pg_engine_get_stat(pg_engine* h, const char* name, int64_t* value) {
 static int esm_forward_logits_once(pg_engine* h, const int32_t* tokens, int B, int T, float* logits_out) {
   if (!h || !tokens || !logits_out) return fail(PG_ERR_INVALID, "pg_esm_forward_logits: null argument");
   Engine& e = h->e;
-  if (e.cfg.arch != PG_ARCH_ESM1B && e.cfg.arch != PG_ARCH_ESM1) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 architecture");
+  if (!e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
   if (B < 0 || T < 1) return fail(PG_ERR_INVALID, "bad shape");
   if (T > e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
   if (B == 0) return PG_OK;
@@ -423,7 +423,7 @@ static int forward_logprobs(Engine& e, bool msa, const int32_t* tokens, int B, i
 int pg_esm_forward_logprobs(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
                             const int32_t* targets, int n_sel, int P, float* out) {
   if (!h || !tokens || !row_of || !idx || !targets || !out) return fail(PG_ERR_INVALID, "pg_esm_forward_logprobs: null argument");
-  if (h->e.cfg.arch != PG_ARCH_ESM1B && h->e.cfg.arch != PG_ARCH_ESM1) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 architecture");
+  if (!h->e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
   if (B < 0 || T < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
   if (T > h->e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
   PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprobs(h->e, false, tokens, B, 1, T, row_of, idx, targets, n_sel, P, out));
@@ -478,7 +478,7 @@ int pg_prof_reset(pg_engine* h) {
 }
 int pg_prof_get(pg_engine* h, const char* kernel_class, double* total_ms, int64_t* launches) {
   if (!h || !kernel_class || !total_ms || !launches) return fail(PG_ERR_INVALID, "pg_prof_get: null argument");
-  static const char* names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed", "head", "sample", "gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2"};
+  static const char* names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed", "head", "sample", "gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2", "rope"};
   int cls = -1;
   const bool all_gemm = !strcmp(kernel_class, "gemm");       // the whole family: the four per-layer projections + the rest
   for (int i = 0; i < PC_COUNT; ++i)
@@ -489,7 +489,7 @@ int pg_prof_get(pg_engine* h, const char* kernel_class, double* total_ms, int64_
   double ms = 0;
   int64_t n = 0;
   for (auto& r : h->e.prof.recs)
-    if (r.cls == cls || (all_gemm && (r.cls == PC_GEMM || r.cls >= PC_GEMM_QKV))) {
+    if (r.cls == cls || (all_gemm && (r.cls == PC_GEMM || (r.cls >= PC_GEMM_QKV && r.cls <= PC_GEMM_FC2)))) {
       float t = 0;
       PG_HIP(hipEventElapsedTime(&t, r.a, r.b));
       ms += t;
@@ -502,7 +502,7 @@ int pg_prof_get(pg_engine* h, const char* kernel_class, double* total_ms, int64_
 
 int pg_prof_get_kernels(pg_engine* h, const char* kernel_class, char* buf, int buf_bytes) {
   if (!h || !kernel_class || !buf || buf_bytes < 2) return fail(PG_ERR_INVALID, "pg_prof_get_kernels: null argument");
-  static const char* names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed", "head", "sample", "gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2"};
+  static const char* names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed", "head", "sample", "gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2", "rope"};
   int cls = -1;
   for (int i = 0; i < PC_COUNT; ++i)
     if (!strcmp(names[i], kernel_class)) cls = i;
@@ -860,6 +860,36 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
   if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(ctx, dc, (size_t)M * d * 4, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
+/* ESM-2's rotary embedding on a host fp32 buffer qkv[B*T][3*H*64]: the q and k thirds rotated in place (row r at position r % T),
+ * v left alone.  16-bit modes: through a device buffer of that type, the result widened back */
+int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
+  if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > 32) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  DeviceGuard g(-1);
+  int rc = dbg_device(device);
+  if (rc) return rc;
+  const int d = H * 64;
+  const int64_t M = (int64_t)B * T, n = M * 3 * d;
+  const std::vector<float> tab = rope_table(T);
+  Tmp t;
+  float* dq = (float*)t.get((size_t)n * 4);
+  float* dtab = (float*)t.get(tab.size() * 4);
+  bf16_t* bq = precision == PG_PREC_FP32 ? nullptr : (bf16_t*)t.get((size_t)n * 2);
+  if (!dq || !dtab || (precision != PG_PREC_FP32 && !bq)) return fail(PG_ERR_HIP, "hipMalloc failed");
+  PG_HIP(hipMemcpy(dq, qkv, (size_t)n * 4, hipMemcpyHostToDevice));
+  PG_HIP(hipMemcpy(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  if (precision == PG_PREC_FP32) {
+    if ((rc = launch_rope(nullptr, dq, true, dtab, T, M, T, H, 3 * d))) return rc;
+  } else {
+    if ((rc = DBG_OPS(launch_f32_to_bf16, nullptr, dq, bq, n, 1.f))) return rc;
+    if ((rc = DBG_OPS(launch_rope, nullptr, bq, false, dtab, T, M, T, H, 3 * d))) return rc;
+    if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bq, dq, n))) return rc;
+  }
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(qkv, dq, (size_t)n * 4, hipMemcpyDeviceToHost));
   return PG_OK;
 }
 

@@ -25,6 +25,7 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 
 // ---- embedding -------------------------------------------------------------------------------
 // tokens[n_seq][T] -> x[n_seq*T][d] fp32 = LN_before(embed[tok]*scale + pos[...] (+ msa_row_pos[r]))
+// pos == nullptr (ESM-2): nothing is added; gamma == nullptr (ESM-1, ESM-2): no LN_before.
 // token_dropout (ESM-1b): mask rows zeroed, all rows scaled by 0.88 / (1 - n_mask/src_len) per sequence.
 // rows_per_msa > 0 (MSA-1b): adds msa_pos[seq % rows_per_msa].
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ embed,
@@ -61,14 +62,14 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
   const int p = is_pad ? pad_idx : n_before + pad_idx;
   const int nch4 = d >> 2;
   const float4* e4 = (const float4*)(embed + (size_t)tok * d);
-  const float4* p4 = (const float4*)(pos + (size_t)p * d);
+  const float4* p4 = pos ? (const float4*)(pos + (size_t)p * d) : nullptr;      // pos == nullptr: no position table (ESM-2: rotary)
   const float4* r4 = rows_per_msa > 0 ? (const float4*)(msa_pos + (size_t)(seq % rows_per_msa) * d) : nullptr;
   float4 v[kMaxCh];
 #pragma unroll
   for (int i = 0; i < kMaxCh; ++i)
     if (lane + 64 * i < nch4) {
       const int c = lane + 64 * i;
-      const float4 e = e4[c], q = p4[c];
+      const float4 e = e4[c], q = p4 ? p4[c] : make_float4(0.f, 0.f, 0.f, 0.f);
       v[i] = make_float4(e.x * scale + q.x, e.y * scale + q.y, e.z * scale + q.z, e.w * scale + q.w);
       if (r4) {
         const float4 r = r4[c];

@@ -29,7 +29,8 @@ struct Prof {
 };
 
 // PC_GEMM_*: the four per-layer projections of a full-batch forward, timed apart (bench.py's per-kernel roofline); "gemm" = all five
-enum ProfClass { PC_GEMM = 0, PC_ATTN, PC_LN, PC_EMBED, PC_HEAD, PC_SAMPLE, PC_GEMM_QKV, PC_GEMM_OUT, PC_GEMM_FC1, PC_GEMM_FC2, PC_COUNT };
+enum ProfClass { PC_GEMM = 0, PC_ATTN, PC_LN, PC_EMBED, PC_HEAD, PC_SAMPLE, PC_GEMM_QKV, PC_GEMM_OUT, PC_GEMM_FC1, PC_GEMM_FC2,
+                 PC_ROPE /* ESM-2: the rotation of q and k, one launch per layer */, PC_COUNT };
 
 struct DenseW {   // y = x W^T + b ; W bf16 [N][K], b fp32 [N].  Strict precision mode: w is [N][3K], each row the
   bf16_t* w = nullptr;   // K-concatenated split-bf16 operand [hi | lo | hi] (hi = bf16(W), lo = bf16(W - hi))
@@ -122,6 +123,14 @@ struct Engine {
   DevBuf ffn_f32, scores;
   bool strict() const { return precision == PG_PREC_FP32; }
   bool esm1() const { return cfg.arch == PG_ARCH_ESM1; }      // ESM-1 differences: see pgibbs.h PG_ARCH_ESM1
+  bool esm2() const { return cfg.arch == PG_ARCH_ESM2; }      // ESM-2 differences: see pgibbs.h PG_ARCH_ESM2
+  bool esm_family() const { return cfg.arch == PG_ARCH_ESM1B || cfg.arch == PG_ARCH_ESM1 || cfg.arch == PG_ARCH_ESM2; }   // the pg_esm_* entry points
+  // ESM-2 rotary embedding: cos / sin table [rope_rows][64] fp32 built at init (rope.hip); rope() rotates the q and k thirds of a
+  // freshly projected qkv buffer (the engine's 16-bit type, fp32 in strict mode) of M token rows, T per sequence.  A no-op for
+  // every other architecture
+  float* rope_tab = nullptr;
+  int rope_rows = 0;
+  int rope(void* qkv_rows, int64_t M, int T);
   // out[Mp][N] fp32 (=|+=) X.W^T + b with X = xh + xl, W = wh + wl as ONE bf16 GEMM over K' = 3K:
   // [xl | xh | xh] . [wh | wl | wh]^T = xl.wh + xh.wl + xh.wh  (the dropped xl.wl term is ~2^-17 relative)
   int dense3(const bf16_t* x3, const DenseW& W, float* out, int Mp, bool accumulate);
@@ -157,6 +166,9 @@ struct Engine {
   // timing helper
   template <typename F> int timed(int cls, F&& f);
 };
+
+// host side of the ESM-2 rotary embedding: the cos / sin table the rotation kernel reads (engine.hip)
+std::vector<float> rope_table(int rows);
 
 // state-dict lookup used by init
 struct TensorMap {

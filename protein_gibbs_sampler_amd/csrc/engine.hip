@@ -219,7 +219,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   cfg = *c;
   precision = prec;
   device = -1;
-  if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_MSA1B && cfg.arch != PG_ARCH_ESM1) return fail(PG_ERR_INVALID, "unknown arch");
+  if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_MSA1B && cfg.arch != PG_ARCH_ESM1 && cfg.arch != PG_ARCH_ESM2) return fail(PG_ERR_INVALID, "unknown arch");
   if (prec != PG_PREC_BF16 && prec != PG_PREC_FP32 && prec != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
   if (cfg.d_model % 128 || cfg.d_ffn % 128 || cfg.n_heads * 64 != cfg.d_model)
     return fail(PG_ERR_INVALID, "d_model and d_ffn must be multiples of 128 and head dim must be 64");
@@ -241,13 +241,14 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   const float qs = 0.125f;  // head_dim^-0.5 = 64^-0.5, folded into W_q and b_q (exact in bf16)
   bool ok = true;
   ok = ok && (embed = up.f32("embed_tokens.weight", (int64_t)V * d));
-  ok = ok && (pos = up.f32("embed_positions.weight", (int64_t)(cfg.max_positions + cfg.pad_idx + 1) * d));
+  // ESM-2 has no position table (pos stays null: embed_ln_kernel adds nothing) -- positions enter through the rotation of q and k
+  if (!esm2()) ok = ok && (pos = up.f32("embed_positions.weight", (int64_t)(cfg.max_positions + cfg.pad_idx + 1) * d));
   if (esm1()) {
     // untied output projection straight from the residual stream: logits = x embed_out^T + embed_out_bias
     ok = ok && (embed_out = up.f32("embed_out.weight", (int64_t)V * d));
     ok = ok && (head_bias = up.f32("embed_out.bias", V));
   } else {
-    ok = ok && up.ln(ln_before, "emb_layer_norm_before", d);
+    if (!esm2()) ok = ok && up.ln(ln_before, "emb_layer_norm_before", d);      // ESM-2: none (ln_before.g stays null)
     ok = ok && up.ln(ln_after, "emb_layer_norm_after", d);
     ok = ok && up.dense(head_dense, {"lm_head.dense"}, {1.0f}, d, d);
     ok = ok && up.ln(head_ln, "lm_head.layer_norm", d);
@@ -286,6 +287,16 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
     }
   }
   if (!ok) return fail(PG_ERR_WEIGHTS, up.err.empty() ? std::string("weight upload failed") : up.err);
+  if (esm2()) {
+    if (cfg.max_positions < 1) return fail(PG_ERR_INVALID, "max_positions must be positive");
+    rope_rows = cfg.max_positions + 2;              // like the learned tables
+    const std::vector<float> tab = rope_table(rope_rows);
+    void* dt = nullptr;
+    PG_HIP(hipMalloc(&dt, tab.size() * 4));
+    owned.push_back(dt);
+    PG_HIP(hipMemcpy(dt, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    rope_tab = (float*)dt;
+  }
   if (cfg.arch == PG_ARCH_ESM1B && !strict() && OPS(chain_trunk_ok, 32, d, f, cfg.n_heads)) {
     // the persistent single-chain trunk reads its weights through one device table
     std::vector<PgChainLayerW> tab(cfg.n_layers);
@@ -436,6 +447,28 @@ float* Engine::splitk_ws(int rows, int n, int64_t batch_rows) {
   return splitk.as<float>();
 }
 
+// The rotary embedding's table [rows][64]: [t][i] = cos, [t][32 + i] = sin of ang[t][i] = float(t) * inv_freq[i] (an fp32 product),
+// inv_freq[i] = 1 / 10000^(2i / 64) in fp32 as fair-esm's RotaryEmbedding holds it (1.0 / (10000 ** (arange(0, 64, 2).float() / 64))).
+// The power is taken in double and rounded to fp32 -- the values torch's fp32 pow and glibc's powf give; a vectorised fp32 pow (numpy's)
+// is one ulp off at i = 5 and 27 --, the cosine and sine of the fp32 angle in double, rounded to fp32.
+std::vector<float> rope_table(int rows) {
+  std::vector<float> tab((size_t)rows * 64);
+  for (int i = 0; i < 32; ++i) {
+    const float inv_freq = 1.0f / (float)pow(10000.0, i / 32.0);
+    for (int t = 0; t < rows; ++t) {
+      const float ang = (float)t * inv_freq;
+      tab[(size_t)t * 64 + i] = (float)cos((double)ang);
+      tab[(size_t)t * 64 + 32 + i] = (float)sin((double)ang);
+    }
+  }
+  return tab;
+}
+
+int Engine::rope(void* qkv_rows, int64_t M, int T) {
+  if (!esm2()) return PG_OK;
+  return timed(PC_ROPE, [&] { return OPS(launch_rope, stream, qkv_rows, strict(), rope_tab, rope_rows, M, T, cfg.n_heads, 3 * cfg.d_model); });
+}
+
 int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx, int P, int64_t n_sel, const int32_t* d_iter_) {
   const int d = cfg.d_model, f = cfg.d_ffn;
   const int64_t M = (int64_t)B * T;
@@ -463,6 +496,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
       const EsmLayer& L = esm_layers[l];
       if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln1.g, L.ln1.b, h.as<bf16_t>(), M, d, eps, true, 0, 0, dense3_wants_dup(L.qkv, Mi)); }))) return rc;
       if ((rc = dense3(h.as<bf16_t>(), L.qkv, QKVf, Mi, false))) return rc;
+      if ((rc = rope(QKVf, M, T))) return rc;                                  // ESM-2 only
       if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), dense3_wants_dup(L.out, Mi) ? d : -d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32); }))) return rc;
       if ((rc = dense3(ctx.as<bf16_t>(), L.out, X, Mi, true))) return rc;
       if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln2.g, L.ln2.b, h.as<bf16_t>(), M, d, eps, true, 0, 0, dense3_wants_dup(L.fc1, Mi, true)); }))) return rc;
@@ -533,6 +567,7 @@ per_layer:
     } else {
       if ((rc = timed(PC_GEMM_QKV, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.qkv.w, L.qkv.b, QKV, Mi, 3 * d, d, d, d, 3 * d, EPI_BF16); }))) return rc;
     }
+    if (!attn_done && (rc = rope(QKV, M, T))) return rc;                       // ESM-2 only: q and k rotated by their positions
     if (!attn_done)
       if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16); }))) return rc;
     if (sel_idx && l == cfg.n_layers - 1) {
@@ -634,7 +669,7 @@ int Engine::head(const int32_t* d_idx_, const int32_t* d_row_map, int P, int wid
 
 int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_, int n_iters, int P,
                              const pg_sample_params* sp, float* d_samp_logits_, int32_t* d_samp_tok_) {
-  if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_ESM1) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 architecture");
+  if (!esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
   if (B < 0 || T < 1 || P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "gibbs: negative size");
   if (T > cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
   if (B == 0 || n_iters == 0) return PG_OK;

@@ -77,7 +77,12 @@ int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, co
                     const float* gamma, const float* beta, float* x, int64_t n_tok, int T, int d, int pad_idx,
                     int mask_idx, int token_dropout, int rows_per_msa, float eps,
                     const float* gamma2 = nullptr, const float* beta2 = nullptr, bf16_t* h2 = nullptr,   // h2: also the first layer's LayerNorm of x
-                    float embed_scale = 1.0f);   // gamma == nullptr: no emb_layer_norm_before; embed_scale = sqrt(d) (both: ESM-1)
+                    float embed_scale = 1.0f);   // gamma == nullptr: no emb_layer_norm_before; embed_scale = sqrt(d) (both: ESM-1);
+                                                 // pos == nullptr: no position table either (ESM-2)
+// ESM-2 rotary position embedding (rope.hip): the q and k thirds of qkv[M][ld] (rows [q | k | v], H heads of 64 each) rotated in place,
+// row r at position r % T; table = [table_rows][64] fp32 ([t][0..31] cos, [t][32..63] sin of float(t) * inv_freq[i]); f32: the buffer
+// is fp32 (strict mode), else the flavour's 16-bit type.  Rows >= M are not touched
+int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld);
 int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
                           int d, float eps, bool split3 = false,   // split3: h rows are [lo | hi | hi], 3 d wide
                           int colmajor_R = 0, int colmajor_C = 0,  // > 0: token row (b*R + r)*C + c is written as row (b*C + c)*R + r

@@ -1,0 +1,143 @@
+// Rotary position embedding (ESM-2): the q and k thirds of a [q | k | v] row buffer rotated in place, one launch per layer between
+// the QKV projection and the attention kernel.
+//
+// fair-esm's RotaryEmbedding, "rotate-half" form, head dimension 64: with ang[t][i] = float(t) * inv_freq[i] (i = 0..31, t = the
+// token's index along the sequence axis, padding or not) a head vector u[0..63] of q or k becomes
+//   u'[i]      = u[i]      * cos(ang[t][i]) - u[i + 32] * sin(ang[t][i])
+//   u'[i + 32] = u[i + 32] * cos(ang[t][i]) + u[i]      * sin(ang[t][i])
+// cos / sin come from a host-built table [positions][64] fp32 ([t][0..31] cos, [t][32..63] sin; 256 B per position, L2-resident):
+// no trigonometry on the device.  v is not touched.
+//
+// Arithmetic: the two products and the add / subtract of every output are separately rounded fp32 operations, in every precision
+// mode: contraction to FMA is OFF -- the Makefile compiles this file with -ffp-contract=off, as it does sample.hip (under hipcc's
+// default the __f*_rn intrinsics are ordinary operators and some of the pairs were fused, others not).  The 16-bit modes widen
+// their operands exactly, rotate in fp32 and round once (nearest-even) back to the buffer's type.  A host loop that
+// evaluates the formula in fp32 therefore reproduces the strict mode bit for bit and the 16-bit modes up to that one rounding.
+//
+// Layout rule (elementwise.hip): a pure HBM-bandwidth pass -- one 64-lane wave per token row, 16-byte accesses per lane, nothing
+// through LDS, no cross-lane traffic.  q and k are the first 2 d_model columns of a row, i.e. 2 H heads of 64 values side by side.
+// A lane owns 16 bytes of a head's low half AND the 16 bytes 32 values higher, so both members of every pair are lane-local:
+// 16-bit buffers 8 + 8 values, 4 lanes per head, 8 H lane-slots per row (160 at d = 1280); fp32 buffers 4 + 4 values, 8 lanes per
+// head, 16 H lane-slots.  Slot s = lane + 64 * pass: the lane's place inside the head (s mod 4 or 8) is the same in every pass, so
+// its cos / sin values are loaded once per row.  A row's loads are all issued before the first rotation.
+// Grid: at most one resident round of workgroups (the kernel's occupancy x CUs), every wave walking rows row, row + waves, ... -- a mid-size
+// batch has no nearly empty last round (the reason layernorm_bf16_stride_kernel exists), and stores retire behind the next row's
+// loads.  Rows >= M (the 256-row padding of the activation buffers) are not touched.
+#include "kernels.h"
+
+PG_OPS_BEGIN
+
+constexpr int kRopePass16 = 4;   // 8 H lane-slots / 64 lanes, H <= 32 (d_model <= 2048)
+constexpr int kRopePass32 = 8;   // 16 H lane-slots / 64 lanes
+
+__device__ __forceinline__ void rope_pair(float& lo, float& hi, float c, float s) {
+  const float a = lo, b = hi;
+  lo = __fsub_rn(__fmul_rn(a, c), __fmul_rn(b, s));
+  hi = __fadd_rn(__fmul_rn(b, c), __fmul_rn(a, s));
+}
+
+// two packed 16-bit values of the low half with their partners of the high half
+__device__ __forceinline__ void rope_word16(uint32_t& wl, uint32_t& wh, float c0, float s0, float c1, float s1) {
+  float l0 = op16_to_f32((bf16_t)(wl & 0xffff)), l1 = op16_to_f32((bf16_t)(wl >> 16));
+  float h0 = op16_to_f32((bf16_t)(wh & 0xffff)), h1 = op16_to_f32((bf16_t)(wh >> 16));
+  rope_pair(l0, h0, c0, s0);
+  rope_pair(l1, h1, c1, s1);
+  wl = pack_op2(l0, l1);
+  wh = pack_op2(h0, h1);
+}
+
+__global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, const float* __restrict__ tab, int M, int T, int H,
+                                                    int ld) {
+  const int lane = threadIdx.x & 63;
+  const int stride = (int)gridDim.x * 4;
+  const int slots = 8 * H;
+  const int c = lane & 3;                                       // values 8 c .. 8 c + 7 of the head's low half
+  for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
+    const float4* tr = (const float4*)(tab + (size_t)(row % T) * 64);
+    uint4* base = (uint4*)(qkv + (size_t)row * ld);             // 8 uint4 per head
+    uint4 lo[kRopePass16], hi[kRopePass16];
+#pragma unroll
+    for (int i = 0; i < kRopePass16; ++i) {
+      const int s = lane + 64 * i;
+      if (s < slots) {
+        const uint4* p = base + (s >> 2) * 8 + c;
+        lo[i] = p[0];
+        hi[i] = p[4];
+      }
+    }
+    const float4 ca = tr[2 * c], cb = tr[2 * c + 1], sa = tr[8 + 2 * c], sb = tr[8 + 2 * c + 1];
+#pragma unroll
+    for (int i = 0; i < kRopePass16; ++i) {
+      const int s = lane + 64 * i;
+      if (s < slots) {
+        rope_word16(lo[i].x, hi[i].x, ca.x, sa.x, ca.y, sa.y);
+        rope_word16(lo[i].y, hi[i].y, ca.z, sa.z, ca.w, sa.w);
+        rope_word16(lo[i].z, hi[i].z, cb.x, sb.x, cb.y, sb.y);
+        rope_word16(lo[i].w, hi[i].w, cb.z, sb.z, cb.w, sb.w);
+        uint4* p = base + (s >> 2) * 8 + c;
+        p[0] = lo[i];
+        p[4] = hi[i];
+      }
+    }
+  }
+}
+
+// strict precision mode: the same rotation on an fp32 buffer
+__global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, const float* __restrict__ tab, int M, int T, int H,
+                                                    int ld) {
+  const int lane = threadIdx.x & 63;
+  const int stride = (int)gridDim.x * 4;
+  const int slots = 16 * H;
+  const int c = lane & 7;                                       // values 4 c .. 4 c + 3 of the head's low half
+  for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
+    const float4* tr = (const float4*)(tab + (size_t)(row % T) * 64);
+    float4* base = (float4*)(qkv + (size_t)row * ld);           // 16 float4 per head
+    float4 lo[kRopePass32], hi[kRopePass32];
+#pragma unroll
+    for (int i = 0; i < kRopePass32; ++i) {
+      const int s = lane + 64 * i;
+      if (s < slots) {
+        const float4* p = base + (s >> 3) * 16 + c;
+        lo[i] = p[0];
+        hi[i] = p[8];
+      }
+    }
+    const float4 cs = tr[c], sn = tr[8 + c];
+#pragma unroll
+    for (int i = 0; i < kRopePass32; ++i) {
+      const int s = lane + 64 * i;
+      if (s < slots) {
+        rope_pair(lo[i].x, hi[i].x, cs.x, sn.x);
+        rope_pair(lo[i].y, hi[i].y, cs.y, sn.y);
+        rope_pair(lo[i].z, hi[i].z, cs.z, sn.z);
+        rope_pair(lo[i].w, hi[i].w, cs.w, sn.w);
+        float4* p = base + (s >> 3) * 16 + c;
+        p[0] = lo[i];
+        p[8] = hi[i];
+      }
+    }
+  }
+}
+
+int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld) {
+  if (H < 1 || H > 32) return fail(1, "rope: 1..32 heads of 64 (d_model <= 2048)");
+  if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
+  if (ld < 3 * H * 64 || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
+  if (M == 0) return 0;
+  if (M > 0x7fffffff - 4 * 8 * 1024) return fail(1, "rope: too many rows");     // 32-bit row arithmetic in the kernels
+  // the grid = what is resident at once (occupancy of the kernel x CUs, asked once), or fewer workgroups when the rows need fewer
+  static const int n_cu = [] {
+    hipDeviceProp_t p; int dv = 0; (void)hipGetDevice(&dv);
+    return hipGetDeviceProperties(&p, dv) == hipSuccess ? p.multiProcessorCount : 256;
+  }();
+  static const int occ16 = [] { int v = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, rope16_kernel, 256, 0) == hipSuccess && v > 0 ? v : 4; }();
+  static const int occ32 = [] { int v = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, rope32_kernel, 256, 0) == hipSuccess && v > 0 ? v : 4; }();
+  const int64_t need = (M + 3) / 4, resident = (int64_t)n_cu * (f32 ? occ32 : occ16);
+  const dim3 grid((unsigned)(need < resident ? need : resident));
+  if (f32) hipLaunchKernelGGL(rope32_kernel, grid, dim3(256), 0, s, (float*)qkv, table, (int)M, T, H, ld);
+  else hipLaunchKernelGGL(rope16_kernel, grid, dim3(256), 0, s, (bf16_t*)qkv, table, (int)M, T, H, ld);
+  PG_HIP(hipGetLastError());
+  return 0;
+}
+
+PG_OPS_END

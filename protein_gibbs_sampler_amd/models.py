@@ -55,6 +55,16 @@ class ESM1v(_Wrapper):
                          "esm1v_t33_650M_UR90S_1.pt", seed, precision, synthetic, config is not None)
 
 
+class ESM2(_Wrapper):
+    """esm2_t33_650M_UR50D: fair-esm's ESM-2 at 650M parameters (not a model of the original pgen package; the successor of ESM-1b
+    in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
+    layout (weights.load_fair_esm_checkpoint); other ESM-2 sizes load when their heads are 64 wide and d_model <= 2048."""
+
+    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
+        super().__init__(config or dict(_w.ESM2_T33_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
+                         "esm2_t33_650M_UR50D.pt", seed, precision, synthetic, config is not None)
+
+
 class ESM_MSA1(_Wrapper):
     """esm_msa1b_t12_100M_UR50S (models.py:84-88) with the reference's patched MSA batch converter."""
 

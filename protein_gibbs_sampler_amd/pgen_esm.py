@@ -11,7 +11,8 @@ from ._cli import RawAndDefaultsFormatter, add_engine_args, parse_line_args, see
 from .esm_sampler import ESM_sampler
 from .fasta_io import write_sequential_fasta
 
-model_map = {"esm1b": models.ESM1b, "esm1v": models.ESM1v, "esm6": models.ESM6, "esm12": models.ESM12, "esm34": models.ESM34}
+model_map = {"esm1b": models.ESM1b, "esm1v": models.ESM1v, "esm6": models.ESM6, "esm12": models.ESM12, "esm34": models.ESM34,
+             "esm2": models.ESM2}
 
 
 def main(input_h, output_p, args):

@@ -29,6 +29,22 @@ ESM1_T12_CONFIG = dict(ESM1_T6_CONFIG, n_layers=12)
 ESM1_T34_CONFIG = dict(ESM1_T6_CONFIG, n_layers=34, d_model=1280, n_heads=20, d_ffn=5120)
 
 
+# ESM-2 (fair-esm `ESM2`, esm2_t33_650M_UR50D -- models.ESM2): the ESM-1b block stack and LM head without a position table and without
+# emb_layer_norm_before; positions enter through rotary embeddings of q and k in every layer (include/pgibbs.h PG_ARCH_ESM2).  The
+# other released sizes have heads of 64 only at 650M (and 3B, whose d_model = 2560 exceeds the row kernels' 2048).
+ESM2_T33_CONFIG = dict(arch=_lib.PG_ARCH_ESM2, vocab=33, d_model=1280, n_layers=33, n_heads=20, d_ffn=5120, max_positions=1024,
+                       pad_idx=1, mask_idx=32, cls_idx=0, eos_idx=2, token_dropout=1, max_msa_rows=0, layer_norm_eps=1e-5)
+MAX_D_MODEL = 2048           # the row kernels hold at most kMaxCh * 256 features (csrc/ln_row.h)
+
+
+def rotary_inv_freq():
+    """fair-esm RotaryEmbedding's `inv_freq` for heads of 64, float32: 1.0 / (10000 ** (torch.arange(0, 64, 2).float() / 64)).  The
+    power is taken in double and rounded to float32 -- the values torch's float32 pow gives (numpy's vectorised float32 power is one
+    ulp off at i = 5 and 27), and what the engine builds its cos / sin table from (csrc/engine.hip rope_table)."""
+    p = (10000.0 ** (np.arange(32, dtype=np.float64) / 32.0)).astype(np.float32)
+    return (np.float32(1.0) / p).astype(np.float32)
+
+
 def sinusoidal_positions(n_rows, d, pad_idx):
     """fairseq / fair-esm SinusoidalPositionalEmbedding.get_embedding in float32 ([sin | cos] halves, inv_freq =
     exp(-i log(10000) / (d/2 - 1)), padding row zero): the engine reads it as its `embed_positions.weight` table."""
@@ -57,6 +73,11 @@ def tensor_shapes(cfg):
     if cfg["arch"] == _lib.PG_ARCH_ESM1:
         s = {"embed_tokens.weight": (V, d), "embed_positions.weight": (cfg["max_positions"] + cfg["pad_idx"] + 1, d),
              "embed_out.weight": (V, d), "embed_out.bias": (V,)}
+    elif cfg["arch"] == _lib.PG_ARCH_ESM2:        # no position table, no emb_layer_norm_before
+        s = {"embed_tokens.weight": (V, d),
+             "emb_layer_norm_after.weight": (d,), "emb_layer_norm_after.bias": (d,),
+             "lm_head.dense.weight": (d, d), "lm_head.dense.bias": (d,),
+             "lm_head.layer_norm.weight": (d,), "lm_head.layer_norm.bias": (d,), "lm_head.bias": (V,)}
     else:
         s = {"embed_tokens.weight": (V, d),
              "embed_positions.weight": (cfg["max_positions"] + cfg["pad_idx"] + 1, d),
@@ -75,7 +96,7 @@ def tensor_shapes(cfg):
 
     for i in range(cfg["n_layers"]):
         p = "layers.%d." % i
-        if cfg["arch"] in (_lib.PG_ARCH_ESM1B, _lib.PG_ARCH_ESM1):
+        if cfg["arch"] in (_lib.PG_ARCH_ESM1B, _lib.PG_ARCH_ESM1, _lib.PG_ARCH_ESM2):
             for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
                 lin(p + "self_attn." + n, d, d)
             if cfg["arch"] == _lib.PG_ARCH_ESM1:
@@ -155,6 +176,14 @@ def normalise_state_dict(sd, cfg, fair_esm_layout=True):
     named = {}
     for k, v in sd.items():
         name = k
+        if cfg["arch"] == _lib.PG_ARCH_ESM2 and name.endswith("rot_emb.inv_freq"):
+            # a buffer fair-esm recomputes when it builds the module; the engine computes it too -- a file that disagrees is not ESM-2's
+            got = (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, dtype=np.float32)).reshape(-1)
+            want_f = rotary_inv_freq()
+            if got.shape != want_f.shape or not np.allclose(got, want_f, rtol=1e-6, atol=0.0):
+                raise ValueError("tensor %r disagrees with rotary inv_freq = 1 / 10000^(2i/64) for heads of 64: the engine's rotary "
+                                 "embedding implements that formula only" % (k,))
+            continue
         if fair_esm_layout:
             name = _strip_fair_esm_prefixes(name)
             if is_msa:
@@ -175,7 +204,7 @@ def normalise_state_dict(sd, cfg, fair_esm_layout=True):
         if "embed_tokens.weight" not in named:
             named["embed_tokens.weight"] = named["lm_head.weight"]
         elif not np.array_equal(named["lm_head.weight"], named["embed_tokens.weight"]):
-            raise ValueError("checkpoint has an untied lm_head.weight: this engine implements the tied decoder of ESM-1b / MSA-1b")
+            raise ValueError("checkpoint has an untied lm_head.weight: this engine implements the tied decoder of ESM-1b / MSA-1b / ESM-2")
     out = {}
     for name, shape in want.items():
         if name not in named:
@@ -187,7 +216,9 @@ def normalise_state_dict(sd, cfg, fair_esm_layout=True):
     missing = [k for k in want if k not in out]
     if missing:
         raise KeyError("checkpoint is missing %d tensors, e.g. %s" % (len(missing), missing[:3]))
-    if fair_esm_layout and cfg.get("token_dropout"):
+    if fair_esm_layout and cfg.get("token_dropout") and cfg["arch"] != _lib.PG_ARCH_ESM2:
+        # (ESM-1b only: fair-esm's loader does this for `roberta_large` files and NOT for ESM-2 ones, whose <mask> row is used as
+        # stored by the tied decoder -- [recalled], no real checkpoint is available offline.)
         # fair-esm zeroes the <mask> embedding row when it loads an ESM-1b checkpoint ("For token drop", [recalled]); the
         # forward never reads that row as an input (masked positions are zeroed), but the tied decoder does: after loading,
         # logit[<mask>] = lm_head.bias[<mask>] only.  The samplers never draw <mask> (it is not in valid_aa_idx) and
@@ -199,7 +230,7 @@ def normalise_state_dict(sd, cfg, fair_esm_layout=True):
 
 
 _ARCH_OF = {"roberta_large": _lib.PG_ARCH_ESM1B, "protein_bert_base": _lib.PG_ARCH_ESM1, "msa_transformer": _lib.PG_ARCH_MSA1B}
-_ARCH_NAME = {_lib.PG_ARCH_ESM1B: "ESM-1b", _lib.PG_ARCH_ESM1: "ESM-1", _lib.PG_ARCH_MSA1B: "MSA-1b"}
+_ARCH_NAME = {_lib.PG_ARCH_ESM1B: "ESM-1b", _lib.PG_ARCH_ESM1: "ESM-1", _lib.PG_ARCH_MSA1B: "MSA-1b", _lib.PG_ARCH_ESM2: "ESM-2"}
 
 
 def checkpoint_args(blob):
@@ -295,16 +326,70 @@ def config_from_checkpoint(args, state_names, base_cfg, explicit=False):
     return cfg
 
 
+def checkpoint_cfg_v2(blob):
+    """The model hyper-parameters of a fair-esm v2 checkpoint ({"cfg": {"model": Namespace | mapping}, "model": state dict} -- the
+    ESM-2 files; fair-esm's `_load_model_and_alphabet_core_v2` reads `encoder_layers`, `encoder_embed_dim`, `encoder_attention_heads`
+    and `token_dropout` from it, [recalled]) as a dict; None when `blob` is not in that layout."""
+    c = blob.get("cfg") if isinstance(blob, dict) and "args" not in blob else None
+    m = (c.get("model") if isinstance(c, dict) else getattr(c, "model", None)) if c is not None else None
+    if m is None:
+        return None
+    return dict(m) if isinstance(m, dict) else dict(vars(m))
+
+
+def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
+    """The engine configuration an ESM-2 (v2) checkpoint asks for: `base_cfg` overridden by the file's encoder_layers /
+    encoder_embed_dim / encoder_attention_heads / token_dropout; d_ffn is 4 x embed_dim (fair-esm's ESM2 has no other).  Sizes the
+    engine cannot run raise ValueError naming the reason."""
+    cfg = dict(base_cfg)
+    take = {}
+    for key, name in (("encoder_embed_dim", "d_model"), ("encoder_layers", "n_layers"), ("encoder_attention_heads", "n_heads")):
+        if model_cfg.get(key) is not None:
+            take[name] = int(model_cfg[key])
+    if "d_model" in take:
+        take["d_ffn"] = 4 * take["d_model"]
+    if "token_dropout" in model_cfg:
+        take["token_dropout"] = 1 if model_cfg["token_dropout"] else 0
+    if explicit:
+        bad = {k: (cfg[k], v) for k, v in take.items() if cfg[k] != v}
+        if bad:
+            raise ValueError("config= disagrees with the checkpoint's own hyper-parameters: %s (given, in the file)" % bad)
+    cfg.update(take)
+    if cfg["n_heads"] * 64 != cfg["d_model"]:
+        raise ValueError("checkpoint has %d heads of dimension %g: the engine's attention kernels implement head dimension 64 "
+                         "(every model of pgen.models)" % (cfg["n_heads"], cfg["d_model"] / max(1, cfg["n_heads"])))
+    if cfg["d_model"] > MAX_D_MODEL:
+        raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head) hold at most %d "
+                         "features per row (esm2_t36_3B_UR50D is out of reach)" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL))
+    if any(n.startswith("emb_layer_norm_before") or n.startswith("embed_positions") for n in state_names):
+        raise ValueError("ESM-2 checkpoint with emb_layer_norm_before / embed_positions tensors: the ESM-2 engine has neither")
+    n_layers_seen = 1 + max([int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", n) for n in state_names) if m] or [-1])
+    if n_layers_seen and n_layers_seen != cfg["n_layers"]:
+        if "n_layers" in take or explicit:
+            raise ValueError("checkpoint holds %d layers but its hyper-parameters say %d" % (n_layers_seen, cfg["n_layers"]))
+        cfg["n_layers"] = n_layers_seen
+    return cfg
+
+
 def load_fair_esm_checkpoint(path, cfg, return_config=False, explicit_config=False):
-    """Read a fair-esm `.pt` file ({"args": ..., "model": state dict}) as the reference does through `esm.pretrained.*`
-    (/root/reference/src/pgen/models.py:61,86).  `cfg` gives the architecture (and the defaults of a file without `args`); sizes
-    and flags come from the checkpoint's own hyper-parameters (config_from_checkpoint).  return_config=True -> (state dict, cfg)."""
+    """Read a fair-esm `.pt` file ({"args": ..., "model": state dict}; for an ESM-2 `cfg` the v2 layout {"cfg": {"model": ...},
+    "model": state dict}) as the reference does through `esm.pretrained.*` (/root/reference/src/pgen/models.py:61,86).  `cfg` gives
+    the architecture (and the defaults of a file without `args`); sizes and flags come from the checkpoint's own hyper-parameters
+    (config_from_checkpoint, config_from_checkpoint_v2).  return_config=True -> (state dict, cfg)."""
     import torch
     blob = torch.load(path, map_location="cpu", weights_only=False)
     sd = blob["model"] if isinstance(blob, dict) and "model" in blob else blob
     args = checkpoint_args(blob)
-    if not args and isinstance(blob, dict) and isinstance(blob.get("cfg"), dict) and isinstance(blob["cfg"].get("model"), dict):
-        raise ValueError("checkpoint in fair-esm's v2 layout (ESM-2): not one of the models of pgen.models")
+    v2 = checkpoint_cfg_v2(blob) if not args else None
+    if cfg["arch"] == _lib.PG_ARCH_ESM2:
+        if args:
+            raise ValueError("checkpoint in fair-esm's v1 layout (arch %r): not an ESM-2 file" % (args.get("arch"),))
+        names = [_strip_fair_esm_prefixes(k) for k in sd]
+        cfg2 = config_from_checkpoint_v2(v2 or {}, names, cfg, explicit=explicit_config)
+        out = normalise_state_dict(sd, cfg2, fair_esm_layout=True)
+        return (out, cfg2) if return_config else out
+    if v2 is not None:
+        raise ValueError("checkpoint in fair-esm's v2 layout (ESM-2): not one of the models of pgen.models -- load it with models.ESM2")
     is_msa = cfg["arch"] == _lib.PG_ARCH_MSA1B
     names = [_swap_row_column(_strip_fair_esm_prefixes(k)) if is_msa else _strip_fair_esm_prefixes(k) for k in sd]
     cfg2 = config_from_checkpoint(args, names, cfg, explicit=explicit_config)
@@ -313,16 +398,33 @@ def load_fair_esm_checkpoint(path, cfg, return_config=False, explicit_config=Fal
 
 
 def to_fair_esm_checkpoint_layout(sd, cfg):
-    """Inverse of the key mapping above: engine/module names -> the on-disk fair-esm v1 key layout (used to write test
+    """Inverse of the key mapping above: engine/module names -> the on-disk fair-esm key layout (used to write test
     fixtures and to export weights): `encoder.sentence_encoder.` prefix on trunk tensors, `encoder.` on the LM head, and
-    row<->column exchanged for the MSA Transformer."""
+    row<->column exchanged for the MSA Transformer.  ESM-2 (v2 files): the same prefixes, the tied decoder also stored as
+    `encoder.lm_head.weight`, and every layer's `self_attn.rot_emb.inv_freq` buffer; `to_fair_esm_checkpoint_v2` adds the `cfg`."""
     is_msa = cfg["arch"] == _lib.PG_ARCH_MSA1B
     out = {}
     for name, v in sd.items():
         k = _swap_row_column(name) if is_msa else name
         k = ("encoder." + k) if k.startswith("lm_head.") else ("encoder.sentence_encoder." + k)
         out[k] = v
+    if cfg["arch"] == _lib.PG_ARCH_ESM2:
+        out["encoder.lm_head.weight"] = sd["embed_tokens.weight"]
+        for i in range(cfg["n_layers"]):
+            out["encoder.sentence_encoder.layers.%d.self_attn.rot_emb.inv_freq" % i] = rotary_inv_freq()
     return out
+
+
+def to_fair_esm_checkpoint_v2(sd, cfg, namespace=True):
+    """A whole ESM-2 checkpoint blob in fair-esm's v2 layout, ready for torch.save: {"cfg": {"model": Namespace (or a dict with
+    namespace=False)}, "model": state dict of tensors}."""
+    import argparse
+
+    import torch
+    m = dict(encoder_layers=cfg["n_layers"], encoder_embed_dim=cfg["d_model"], encoder_attention_heads=cfg["n_heads"],
+             token_dropout=bool(cfg["token_dropout"]))
+    model = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in to_fair_esm_checkpoint_layout(sd, cfg).items()}
+    return {"cfg": {"model": argparse.Namespace(**m) if namespace else m}, "model": model}
 
 
 def find_cached_checkpoint(filename):

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""ESM-2 next to ESM-1b on one MI355X: what the rotary embedding costs.
+
+For three shapes -- config 2 (256 chains x 258 tokens, 25 positions per iteration), a 32-chain shard of it, and one chain of 25
+residues (27 tokens, 2 positions) -- both full-size models (33 x 1280, synthetic weights, bf16 operands) run the same Gibbs job from
+device buffers (pg_esm_gibbs_run_device), alternating ESM-1b / ESM-2 for `--rounds` rounds in one process:
+
+  * ms per Gibbs iteration: host clock around `--iters` iterations ending in a stream synchronisation, after `--warmup` iterations of the
+    same shape; the median over the rounds is reported, every round is listed;
+  * the rotation kernel: a separate profiled run (HIP events through pg_prof_*, class "rope"): ms per launch and achieved GB/s =
+    (rows x 2 d_model x 2 B read + the same written) / time, next to the LayerNorm launches of the same run (class "layernorm":
+    rows x d_model x (4 B read + 2 B written)) as the bandwidth yardstick of the box.
+
+Prints one JSON line.  Needs a GPU: there is no CPU path.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+import warnings
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+SHAPES = [("config2_256x258_p25", 256, 256, 25), ("shard_32x258_p25", 32, 256, 25), ("chain_1x27_p2", 1, 25, 2)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--iters", type=int, default=20, help="timed Gibbs iterations per run")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3, help="alternations ESM-1b / ESM-2 per shape")
+    ap.add_argument("--prof-iters", type=int, default=3, help="iterations of the profiled run")
+    ap.add_argument("--layers", type=int, default=33, help="fewer layers for a rehearsal")
+    args = ap.parse_args(argv)
+
+    import torch
+    from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
+    if not torch.cuda.is_available():
+        raise SystemExit("esm2_bench: no GPU visible -- nothing is measured without one")
+    L_ = _lib.lib()
+
+    def build(cls, base):
+        cfg = weights.make_config(base, n_layers=args.layers)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            m = cls(state_dict=weights.synthetic_state_dict(cfg, seed=0), config=cfg, precision="bf16")
+        return esm_sampler.ESM_sampler(m, device="cuda:0")
+
+    samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), "esm2": build(models.ESM2, weights.ESM2_T33_CONFIG)}
+    d_model = weights.ESM2_T33_CONFIG["d_model"]
+
+    def job(s, B, L, P, iters):
+        """-> a closure that runs `iters` Gibbs iterations of B chains from fresh device buffers and synchronises"""
+        T = L + 2
+        rng = np.random.default_rng(1234)
+        tok = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, L)), np.full((B, 1), 2)], axis=1).astype(np.int32)
+        r = pyrandom.NativePyRandom()
+        r.seed(0)
+        table = sharding.global_position_table(r, list(range(1, L + 1)), P, iters, B)
+        params = _lib.make_sample_params(True, 32, 0, float("inf"), 1.0, s.valid_aa_idx, rng_seed=0)
+        d_tok = torch.from_numpy(tok).cuda()
+        d_idx = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).cuda()
+        lm = s.model.model
+
+        def run():
+            _lib.check(L_.pg_esm_gibbs_run_device(lm.handle, ctypes.c_void_p(d_tok.data_ptr()), B, T, ctypes.c_void_p(d_idx.data_ptr()),
+                                                  iters, P, ctypes.byref(params), None, None))
+            lm.synchronize()
+        return run
+
+    out = {"tool": "esm2_bench", "device": torch.cuda.get_device_name(0), "precision": "bf16", "layers": args.layers,
+           "iters": args.iters, "warmup": args.warmup, "rounds": args.rounds, "shapes": {}}
+    for name, B, L, P in SHAPES:
+        T = L + 2
+        rec = {"chains": B, "tokens": T, "positions": P}
+        timed = {k: job(s, B, L, P, args.iters) for k, s in samplers.items()}
+        warm = {k: job(s, B, L, P, max(args.warmup, 3)) for k, s in samplers.items()}
+        for k in samplers:
+            warm[k]()
+        ms = {k: [] for k in samplers}
+        for _ in range(args.rounds):
+            for k in samplers:                      # same order every round: ESM-1b, then ESM-2
+                t0 = time.perf_counter()
+                timed[k]()
+                ms[k].append((time.perf_counter() - t0) * 1e3 / args.iters)
+        for k in samplers:
+            rec[k + "_ms_per_iteration"] = round(statistics.median(ms[k]), 4)
+            rec[k + "_ms_per_iteration_rounds"] = [round(v, 4) for v in ms[k]]
+        rec["esm2_over_esm1b"] = round(rec["esm2_ms_per_iteration"] / rec["esm1b_ms_per_iteration"], 4)
+        # the rotation and the LayerNorm launches, by HIP events, in a run of their own
+        lm = samplers["esm2"].model.model
+        prof = job(samplers["esm2"], B, L, P, args.prof_iters)
+        lm.prof_enable(True)
+        lm.prof_reset()
+        prof()
+        rope_ms, rope_n = lm.prof_get("rope")
+        ln_ms, ln_n = lm.prof_get("layernorm")
+        lm.prof_enable(False)
+        rows = B * T
+        rec["rope_launches_per_iteration"] = rope_n // args.prof_iters
+        rec["rope_ms_per_launch"] = round(rope_ms / max(rope_n, 1), 5)
+        rec["rope_ms_per_iteration"] = round(rope_ms / args.prof_iters, 4)
+        rope_bytes = rows * 2 * d_model * 2 * 2
+        rec["rope_bytes_per_launch"] = rope_bytes
+        rec["rope_GBps"] = round(rope_bytes / (rope_ms / max(rope_n, 1) * 1e-3) / 1e9, 1) if rope_ms > 0 else None
+        if ln_n:
+            # the trunk's LayerNorm launches see all token rows except the pruned last layer's (the selected rows only): bytes by launch
+            # count would overstate them, so only full-row launches are priced -- 2 per layer, minus the pruned layer's second
+            rec["layernorm_ms_per_launch"] = round(ln_ms / ln_n, 5)
+            rec["layernorm_launches"] = ln_n
+            rec["layernorm_GBps_if_full_rows"] = round(rows * d_model * 6 / (ln_ms / ln_n * 1e-3) / 1e9, 1)
+        out["shapes"][name] = rec
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
