@@ -82,7 +82,8 @@ typedef struct pg_engine pg_engine;
                            attention key / value per layer (`layers.i.self_attn.bias_k` / `bias_v`, d_model values each), untied output
                            projection `embed_out.weight` [V][d] + `embed_out.bias` [V], no LM-head dense / LayerNorm, no token
                            dropout; vocabulary of 35 (<cls> = 32, <mask> = 33).  Runs through the ESM-1b entry points. */
-#define PG_ARCH_ESM2 4  /* fair-esm ESM2 (esm2_t33_650M_UR50D; any ESM-2 size with heads of 64 and d_model <= 2048).  The ESM-1b block
+#define PG_ARCH_ESM2 4  /* fair-esm ESM2 (esm2_t33_650M_UR50D, esm2_t36_3B_UR50D; any ESM-2 size with heads of 64 and d_model <= 2560 = 40 heads;
+                           pg_engine_create answers PG_ERR_INVALID for any other head width or a wider model).  The ESM-1b block
                            stack, token dropout, emb_layer_norm_after and tied RoBERTa LM head, with three differences: no position
                            table (`embed_positions.weight` is neither required nor read) -- positions enter through ROTARY embeddings
                            applied to q and k of every attention layer ("rotate-half" pairs (i, i + 32) of each 64-wide head, angle
@@ -94,7 +95,8 @@ typedef struct pg_engine pg_engine;
                            `layers.i.self_attn.rot_emb.inv_freq` and `contact_head.*` are ignored when handed in.  Runs through the
                            pg_esm_* entry points (the pg_msa_* ones answer PG_ERR_INVALID); max_positions bounds T as for ESM-1b
                            (default 1024).  The persistent single-chain trunk is ESM-1b-only: ESM-2 chains of <= 32 token rows take
-                           the per-layer launches (weight-streaming GEMMs, hipGraph replay). */
+                           the per-layer launches (weight-streaming GEMMs, hipGraph replay); at d_model > 1280 their LayerNorm is a
+                           launch of its own (the LayerNorm-folding GEMM takes K <= 1280). */
 
 #define PG_PREC_BF16 0 /* bf16 MFMA operands, fp32 accumulate, fp32 residual stream (throughput mode) */
 #define PG_PREC_F16 2  /* the throughput mode with IEEE fp16 operands instead of bf16 (same kernels, same MFMA rate; 3 more mantissa
@@ -320,12 +322,16 @@ int pg_dbg_qkv_attention_bench(int device, int B, int T, int H, int iters, doubl
 /* y = LayerNorm(x[M][d]) * gamma + beta */
 int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
                      float eps);
+/* the same LayerNorm as the GEMMs read it (d a multiple of 32, <= 2560): the operand rows written in `precision` and widened to fp32
+ * -- bf16 (PG_PREC_BF16) or fp16 (PG_PREC_F16) rows, or the strict mode's split rows (PG_PREC_FP32) returned as hi + lo */
+int pg_dbg_layernorm_operand(int device, int precision, const float* x, const float* gamma, const float* beta, float* y, int M,
+                             int d, float eps);
 /* softmax(q k^T) v per (b, h); q already scaled; qkv[B][T][3*H*64] fp32 -> ctx[B][T][H*64]; PG_PREC_BF16 or PG_PREC_FP32
  * (split-bf16 MFMA kernel, output = hi + lo of the operand rows it writes) or PG_PREC_F16 (the bf16 kernel with fp16 operands) */
 int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, int B, int T, int H);
 /* ESM-2's rotary embedding: the q and k thirds of qkv_inout[B*T][3*H*64] (fp32 host buffer) rotated in place, row r at position
  * r % T, in `precision` (16-bit modes: through a device buffer of that type, the result widened back); the v third is left alone */
-int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H);
+int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H);      /* H <= 40 */
 
 /* MSA attention blocks: qkv[B][R][C][3*H*64] fp32 -> ctx[B][R][C][H*64]; which = 0 tied row attention (scores * scale),
  * 1 column attention (q pre-scaled); 2 / 3 = the same two with the strict precision mode's kernels; 4 / 5 = 0 / 1 with fp16

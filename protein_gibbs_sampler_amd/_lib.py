@@ -113,6 +113,7 @@ SIGNATURES = [
     ("pg_dbg_rowln_bench", c_int, [c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
     ("pg_dbg_qkv_attention_bench", c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
     ("pg_dbg_layernorm", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),
+    ("pg_dbg_layernorm_operand", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),
     ("pg_dbg_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int]),
     ("pg_dbg_rope", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int]),
     ("pg_dbg_msa_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float]),

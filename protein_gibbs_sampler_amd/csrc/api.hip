@@ -603,7 +603,7 @@ int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const
     if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bout, dout, (int64_t)M * N))) return rc;
   } else {
     // the residual variant gets split-K scratch, as the engine gives its fc2 GEMMs (taken for deep K and few tiles)
-    const size_t ws_bytes = epi == 2 ? (size_t)5 * Mp * N * 4 : 0;
+    const size_t ws_bytes = epi == 2 ? DBG_OPS(gemm_splitk_ws_bytes, Mp, N, K) : 0;
     float* ws = ws_bytes && ws_bytes <= ((size_t)1 << 30) ? (float*)t.get(ws_bytes) : nullptr;
     if ((rc = DBG_OPS(launch_gemm_bf16, nullptr, bx, bw, db, dout, M <= 256 ? round_up(M, 16) : Mp, N, K, K, K, N,
                       epi == 2 ? EPI_F32_RESID : (epi ? EPI_F32_GELU : EPI_F32), ws, ws ? ws_bytes : 0, M))) return rc;
@@ -625,7 +625,7 @@ int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int
   float* db = (float*)t.get((size_t)N * 4);
   void* dout = t.get((size_t)round_up(M, kRowPad) * N * 4);
   if (!f || !bx || !bw || !db || !dout) return fail(PG_ERR_HIP, "hipMalloc failed");
-  const size_t ws_bytes = (epi == EPI_F32_RESID && M <= 8192) ? (size_t)5 * round_up(M, kRowPad) * N * 4 : 0;
+  const size_t ws_bytes = (epi == EPI_F32_RESID && M <= 8192) ? gemm_splitk_ws_bytes(M, N, K) : 0;
   float* ws = ws_bytes ? (float*)t.get(ws_bytes) : nullptr;
   std::vector<float> h((size_t)(M > N ? M : N) * K);
   uint32_t st = 12345u;
@@ -863,11 +863,39 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
   return PG_OK;
 }
 
+/* LayerNorm as the engine's GEMMs read it: the operand rows launch_layernorm_bf16 writes in `precision`, widened to fp32 --
+ * bf16 or fp16 rows, or (PG_PREC_FP32) the strict mode's split rows [lo | hi | hi] returned as hi + lo, the two hi copies checked */
+int pg_dbg_layernorm_operand(int device, int precision, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
+                             float eps) {
+  if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
+  if (!x || !gamma || !beta || !y || M < 1 || d < 32 || d % 32) return fail(PG_ERR_INVALID, "pg_dbg_layernorm_operand: bad argument");
+  DeviceGuard g(-1);
+  int rc = dbg_device(device);
+  if (rc) return rc;
+  const bool split = precision == PG_PREC_FP32;
+  Tmp t;
+  float* dx = (float*)t.get((size_t)M * d * 4);
+  float* dg = (float*)t.get((size_t)d * 4);
+  float* dbt = (float*)t.get((size_t)d * 4);
+  float* dy = (float*)t.get((size_t)M * d * 4);
+  bf16_t* h = (bf16_t*)t.get((size_t)M * d * 2 * (split ? 3 : 1));
+  if (!dx || !dg || !dbt || !dy || !h) return fail(PG_ERR_HIP, "hipMalloc failed");
+  PG_HIP(hipMemcpy(dx, x, (size_t)M * d * 4, hipMemcpyHostToDevice));
+  PG_HIP(hipMemcpy(dg, gamma, (size_t)d * 4, hipMemcpyHostToDevice));
+  PG_HIP(hipMemcpy(dbt, beta, (size_t)d * 4, hipMemcpyHostToDevice));
+  if ((rc = DBG_OPS(launch_layernorm_bf16, nullptr, dx, dg, dbt, h, M, d, eps, split, 0, 0, true))) return rc;
+  if (split) return split3_rows_to_host(h, y, M, d);
+  if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, h, dy, (int64_t)M * d))) return rc;
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(y, dy, (size_t)M * d * 4, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
 /* ESM-2's rotary embedding on a host fp32 buffer qkv[B*T][3*H*64]: the q and k thirds rotated in place (row r at position r % T),
  * v left alone.  16-bit modes: through a device buffer of that type, the result widened back */
 int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
   if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
-  if (!qkv || B < 1 || T < 1 || H < 1 || H > 32) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > 40) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
   DeviceGuard g(-1);
   int rc = dbg_device(device);
   if (rc) return rc;

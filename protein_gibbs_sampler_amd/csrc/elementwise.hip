@@ -28,6 +28,7 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 // pos == nullptr (ESM-2): nothing is added; gamma == nullptr (ESM-1, ESM-2): no LN_before.
 // token_dropout (ESM-1b): mask rows zeroed, all rows scaled by 0.88 / (1 - n_mask/src_len) per sequence.
 // rows_per_msa > 0 (MSA-1b): adds msa_pos[seq % rows_per_msa].
+template <int NCH>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ embed,
                                                       const float* __restrict__ pos, const float* __restrict__ msa_pos,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -64,9 +65,9 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
   const float4* e4 = (const float4*)(embed + (size_t)tok * d);
   const float4* p4 = pos ? (const float4*)(pos + (size_t)p * d) : nullptr;      // pos == nullptr: no position table (ESM-2: rotary)
   const float4* r4 = rows_per_msa > 0 ? (const float4*)(msa_pos + (size_t)(seq % rows_per_msa) * d) : nullptr;
-  float4 v[kMaxCh];
+  float4 v[NCH];
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) {
       const int c = lane + 64 * i;
       const float4 e = e4[c], q = p4 ? p4[c] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
   if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);      // gamma == nullptr: no emb_layer_norm_before (ESM-1)
   float4* o = (float4*)(x + (size_t)row * d);
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) {
       if (is_pad) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       o[lane + 64 * i] = v[i];
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
 }
 
 // ---- LayerNorm: x fp32 [M][d] -> h bf16 [M][d] ------------------------------------------------
+template <int NCH>
 __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, bf16_t* __restrict__ h,
                                                             int split3, int64_t M, int d, float eps) {
@@ -99,9 +101,9 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const float* __rest
   if (row >= M) return;
   const int nch4 = d >> 2;
   const float4* x4 = (const float4*)(x + (size_t)row * d);
-  float4 v[kMaxCh];
+  float4 v[NCH];
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
   ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   store_row_bf16(h + (size_t)row * d * (split3 ? 3 : 1), v, nch4, lane, split3, split3 != 2);       // split3 == 2: no duplicate hi block
@@ -171,6 +173,7 @@ __global__ __launch_bounds__(256) void layernorm_bf16_colmajor_kernel(const floa
 }
 
 // fp32 -> fp32 LayerNorm (debug entry / strict paths)
+template <int NCH>
 __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ y,
                                                            int64_t M, int d, float eps) {
@@ -179,20 +182,21 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
   if (row >= M) return;
   const int nch4 = d >> 2;
   const float4* x4 = (const float4*)(x + (size_t)row * d);
-  float4 v[kMaxCh];
+  float4 v[NCH];
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
   ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   float4* o = (float4*)(y + (size_t)row * d);
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) o[lane + 64 * i] = v[i];
 }
 
 // ---- gather the sampled rows + final LayerNorm -> bf16 (LM-head dense operand) ---------------
 // sel r -> token row row_of(r) * width + idx[r]; idx < 0 (ragged padding) -> row of zeros.
 // row_map == nullptr: selected row s = r / P maps to token row s.
+template <int NCH>
 __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __restrict__ x, const int32_t* __restrict__ idx,
                                                             const int32_t* __restrict__ row_map, int P, int width,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -202,10 +206,10 @@ __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __rest
   if (r >= n_sel) return;
   const int nch4 = d >> 2;
   int pos = idx ? idx[r] : 0;
-  float4 v[kMaxCh];
+  float4 v[NCH];
   if (pos < 0 || (idx && (pos & 0x3fffffff) >= width)) {
 #pragma unroll
-    for (int i = 0; i < kMaxCh; ++i) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = 0; i < NCH; ++i) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   } else {
     int64_t src;
     if (idx) {
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __rest
     }
     const float4* x4 = (const float4*)(x + (size_t)src * d);
 #pragma unroll
-    for (int i = 0; i < kMaxCh; ++i)
+    for (int i = 0; i < NCH; ++i)
       if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
     ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   }
@@ -243,6 +247,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restric
 
 // ---- LM-head tail: logits[r][V] = LN(g[r]) . embed^T + bias ----------------------------------
 // g = gelu(dense(x)) fp32 [n][d] (GEMM epilogue); the 33 x d tied decoder stays L2-resident.
+template <int NCH>
 __global__ __launch_bounds__(256) void lm_tail_kernel(const float* __restrict__ g, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, const float* __restrict__ embed,
                                                      const float* __restrict__ out_bias, float* __restrict__ logits,
@@ -252,9 +257,9 @@ __global__ __launch_bounds__(256) void lm_tail_kernel(const float* __restrict__ 
   if (r >= n) return;
   const int nch4 = d >> 2;
   const float4* x4 = (const float4*)(g + (size_t)r * d);
-  float4 v[kMaxCh];
+  float4 v[NCH];
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
   if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);      // gamma == nullptr: ESM-1's head has no LayerNorm
   float mine = 0.f;  // lane t keeps logit t (V <= 64)
@@ -268,7 +273,7 @@ __global__ __launch_bounds__(256) void lm_tail_kernel(const float* __restrict__ 
       const float4* e4 = (const float4*)(embed + (size_t)t * d);
       float a = 0.f;
 #pragma unroll
-      for (int i = 0; i < kMaxCh; ++i)
+      for (int i = 0; i < NCH; ++i)
         if (lane + 64 * i < nch4) {
           const float4 e = e4[lane + 64 * i];
           a += (v[i].x * e.x + v[i].y * e.y) + (v[i].z * e.z + v[i].w * e.w);
@@ -287,6 +292,7 @@ __global__ __launch_bounds__(256) void lm_tail_kernel(const float* __restrict__ 
 // Few rows (a single chain samples 2 positions per iteration; generate_single ~50): the row-per-wave kernel above walks the 33
 // decoder rows one trip after the other (84 us for 2 rows).  Here one workgroup per row, one wave per 4 decoder rows: every wave
 // normalises the row itself (1280 values) and all decoder rows are in flight at once.
+template <int NCH>
 __global__ __launch_bounds__(1024) void lm_tail_small_kernel(const float* __restrict__ g, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const float* __restrict__ embed,
                                                             const float* __restrict__ out_bias, float* __restrict__ logits,
@@ -295,9 +301,9 @@ __global__ __launch_bounds__(1024) void lm_tail_small_kernel(const float* __rest
   const int64_t r = blockIdx.x;
   const int nch4 = d >> 2;
   const float4* x4 = (const float4*)(g + (size_t)r * d);
-  float4 v[kMaxCh];
+  float4 v[NCH];
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
   if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   float s[4];
@@ -307,7 +313,7 @@ __global__ __launch_bounds__(1024) void lm_tail_small_kernel(const float* __rest
     const float4* e4 = (const float4*)(embed + (size_t)t * d);
     float a = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMaxCh; ++i)
+    for (int i = 0; i < NCH; ++i)
       if (lane + 64 * i < nch4) {
         const float4 e = e4[lane + 64 * i];
         a += (v[i].x * e.x + v[i].y * e.y) + (v[i].z * e.z + v[i].w * e.w);      // same per-lane order as lm_tail_kernel
@@ -373,24 +379,37 @@ __global__ void scale_f32_kernel(float* __restrict__ p, int64_t n, float scale) 
 
 // ---- launchers --------------------------------------------------------------------------------
 static inline unsigned rows_grid(int64_t rows) { return (unsigned)((rows + 3) / 4); }
+// rows_grid's result is a 32-bit workgroup count; past it the launch would cover the first rows only
+static inline bool rows_fit(int64_t rows) { return rows >= 0 && (rows + 3) / 4 <= 0x7fffffffLL; }
+// the row kernels hold a row as float4 v[NCH] per lane: the 8-chunk instantiation up to d = 2048 (every model before ESM-2 3B runs
+// it, unchanged), the 10-chunk one up to d = 2560
+static inline bool row_d_ok(int d) { return d >= 4 && d % 4 == 0 && d <= kMaxChWide * 256; }
+static inline bool row_wide(int d) { return d > kMaxCh * 256; }
 
 int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, const float* pos, const float* msa_pos,
                     const float* gamma, const float* beta, float* x, int64_t n_tok, int T, int d, int pad_idx,
                     int mask_idx, int token_dropout, int rows_per_msa, float eps, const float* gamma2, const float* beta2,
                     bf16_t* h2, float embed_scale) {
-  if (d % 4 || d > kMaxCh * 256) return fail(1, "embed: d must be a multiple of 4 and <= 2048");
+  if (!row_d_ok(d)) return fail(1, "embed: d must be a multiple of 4 and <= 2560");
   if (n_tok == 0) return 0;
-  hipLaunchKernelGGL(embed_ln_kernel, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta, x,
-                     n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
+  if (!rows_fit(n_tok)) return fail(1, "embed: too many rows");
+  if (row_wide(d))
+    hipLaunchKernelGGL(embed_ln_kernel<kMaxChWide>, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta, x,
+                       n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
+  else
+    hipLaunchKernelGGL(embed_ln_kernel<kMaxCh>, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta, x,
+                       n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
                           int d, float eps, bool split3, int colmajor_R, int colmajor_C, bool split3_dup) {
-  if (d % 4 || d > kMaxCh * 256) return fail(1, "layernorm: d must be a multiple of 4 and <= 2048");
+  if (!row_d_ok(d)) return fail(1, "layernorm: d must be a multiple of 4 and <= 2560");
   if (M == 0) return 0;
+  if (!rows_fit(M)) return fail(1, "layernorm: too many rows");
   if (colmajor_R > 0) {
+    if (row_wide(d)) return fail(1, "layernorm: column-major output needs d <= 2048");
     if (split3 || M % ((int64_t)colmajor_R * colmajor_C)) return fail(1, "layernorm: column-major output needs whole MSAs and plain bf16 rows");
     hipLaunchKernelGGL(layernorm_bf16_colmajor_kernel, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, M, d, eps, colmajor_R, colmajor_C);
     PG_HIP(hipGetLastError());
@@ -424,25 +443,35 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
       }
     }
   }
-  hipLaunchKernelGGL(layernorm_bf16_kernel, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, split3 ? (split3_dup ? 1 : 2) : 0, M, d, eps);
+  const int sp = split3 ? (split3_dup ? 1 : 2) : 0;
+  if (row_wide(d)) hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxChWide>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+  else hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxCh>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 int launch_layernorm_f32(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t M, int d,
                          float eps) {
-  if (d % 4 || d > kMaxCh * 256) return fail(1, "layernorm: d must be a multiple of 4 and <= 2048");
+  if (!row_d_ok(d)) return fail(1, "layernorm: d must be a multiple of 4 and <= 2560");
   if (M == 0) return 0;
-  hipLaunchKernelGGL(layernorm_f32_kernel, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
+  if (!rows_fit(M)) return fail(1, "layernorm: too many rows");
+  if (row_wide(d)) hipLaunchKernelGGL(layernorm_f32_kernel<kMaxChWide>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
+  else hipLaunchKernelGGL(layernorm_f32_kernel<kMaxCh>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 int launch_gather_ln_bf16(hipStream_t s, const float* x, const int32_t* idx, const int32_t* row_map, int P, int width,
                           const float* gamma, const float* beta, bf16_t* h, int64_t n_sel, int d, float eps, bool split3) {
+  if (!row_d_ok(d)) return fail(1, "gather_ln: d must be a multiple of 4 and <= 2560");
   if (n_sel == 0) return 0;
-  hipLaunchKernelGGL(gather_ln_bf16_kernel, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
-                     beta, h, split3 ? 1 : 0, n_sel, d, eps);
+  if (!rows_fit(n_sel)) return fail(1, "gather_ln: too many rows");
+  if (row_wide(d))
+    hipLaunchKernelGGL(gather_ln_bf16_kernel<kMaxChWide>, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
+                       beta, h, split3 ? 1 : 0, n_sel, d, eps);
+  else
+    hipLaunchKernelGGL(gather_ln_bf16_kernel<kMaxCh>, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
+                       beta, h, split3 ? 1 : 0, n_sel, d, eps);
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -459,20 +488,30 @@ int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t*
 
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
                    const float* out_bias, float* logits, int64_t n, int d, int V, float eps) {
-  if (V > 64) return fail(1, "lm_tail: vocab > 64 unsupported");
+  if (V < 1 || V > 64) return fail(1, "lm_tail: vocab must be in 1..64");      // lane t keeps logit t; 64 * ceil(V / 4) <= 1024 threads
+  if (!row_d_ok(d)) return fail(1, "lm_tail: d must be a multiple of 4 and <= 2560");
   if (n == 0) return 0;
+  if (!rows_fit(n)) return fail(1, "lm_tail: too many rows");
   // identical arithmetic per logit (same per-lane partial sums, same wave reduction): bit-equal results.  Up to 1024 rows (round 5;
   // it was 128): a 32-chain shard's 800 sampled rows took 81 us on the row-per-wave kernel -- 200 workgroups, each wave walking the
   // decoder rows in nine dependent trips -- PGIBBS_LM_TAIL_SMALL=n moves the switch
   static const int small_max = [] { const char* e = getenv("PGIBBS_LM_TAIL_SMALL"); return e ? atoi(e) : 1024; }();
   if (n <= small_max) {
-    hipLaunchKernelGGL(lm_tail_small_kernel, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias, logits,
-                       d, V, eps);
+    // no shared memory; every wave holds the row and four decoder rows' chunks (NCH + 4 float4 in flight at most: far below the
+    // 128 VGPRs a 1024-thread workgroup may use per lane)
+    if (row_wide(d))
+      hipLaunchKernelGGL(lm_tail_small_kernel<kMaxChWide>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
+                         logits, d, V, eps);
+    else
+      hipLaunchKernelGGL(lm_tail_small_kernel<kMaxCh>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
+                         logits, d, V, eps);
     PG_HIP(hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL(lm_tail_kernel, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V,
-                     eps);
+  if (row_wide(d))
+    hipLaunchKernelGGL(lm_tail_kernel<kMaxChWide>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
+  else
+    hipLaunchKernelGGL(lm_tail_kernel<kMaxCh>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
   PG_HIP(hipGetLastError());
   return 0;
 }

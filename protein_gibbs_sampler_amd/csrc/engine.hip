@@ -223,6 +223,9 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   if (prec != PG_PREC_BF16 && prec != PG_PREC_FP32 && prec != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
   if (cfg.d_model % 128 || cfg.d_ffn % 128 || cfg.n_heads * 64 != cfg.d_model)
     return fail(PG_ERR_INVALID, "d_model and d_ffn must be multiples of 128 and head dim must be 64");
+  // the row kernels (ln_row.h, rope.hip) hold a row of at most 2560 features per wave: 40 heads of 64, ESM-2 3B
+  if (cfg.d_model > 2560)
+    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " > 2560: the engine runs up to 40 heads of 64 (esm2_t36_3B_UR50D)");
   if (cfg.vocab < 1 || cfg.vocab > 64) return fail(PG_ERR_INVALID, "vocab must be in 1..64");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -440,9 +443,11 @@ int Engine::dense3_gelu(const bf16_t* x3, const DenseW& W, int Mp, const DenseW*
 // it is taken on the forward's token rows M (`batch_rows`), also for the pruned last layer whose GEMMs see only the B*P selected
 // rows -- a 32-chain shard of config 3 (8256 token rows, 800 selected) must give the same logits bit for bit as the whole
 // 256-chain batch (6400 selected), and did not while this looked at the selected rows.
-float* Engine::splitk_ws(int rows, int n, int64_t batch_rows) {
+// The scratch holds every K-split the launcher will run at this depth (gemm_splitk_ws_bytes: 4 at d_ffn 5120, 8 at 10240), so whether
+// fc2 is split never depends on what this engine's grow-only buffer was sized for by an earlier call.
+float* Engine::splitk_ws(int rows, int n, int K, int64_t batch_rows) {
   if (rows > 2048 || batch_rows > 2048) return nullptr;
-  const size_t need = (size_t)5 * round_up(rows, kRowPad) * n * 4;
+  const size_t need = OPS(gemm_splitk_ws_bytes, rows, n, K);
   if (splitk.bytes < need && splitk.ensure(need, stream)) return nullptr;
   return splitk.as<float>();
 }
@@ -590,21 +595,21 @@ per_layer:
         if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, XS, L.ln2.g, L.ln2.b, h_sel.as<bf16_t>(), n_sel, d, eps); }))) return rc;
         if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, h_sel.as<bf16_t>(), L.fc1.w, L.fc1.b, ffn_sel.as<bf16_t>(), Ni, f, d, d, d, f, EPI_BF16_GELU); }))) return rc;
       }
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ffn_sel.as<bf16_t>(), L.fc2.w, L.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, batch_rows), splitk.bytes); }))) return rc;
+      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ffn_sel.as<bf16_t>(), L.fc2.w, L.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, f, batch_rows), splitk.bytes); }))) return rc;
       break;
     }
     if (ln_in_gemm) {
       if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, CTX, L.out.w, L.out.b, X, Mi, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
       if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, X, d, L.ln2.g, L.ln2.b, eps, L.fc1.w, L.fc1.b, FFN, Mi, f, d, d, f, EPI_BF16_GELU); }))) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, batch_rows), splitk.bytes, (int)M); }))) return rc;
+      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
       continue;
     }
     if ((rc = resid_gemm_ln(CTX, L.out, X, Mi, M, d, L.ln2, Hh, nullptr, 0, PC_GEMM_OUT))) return rc;   // x += out_proj(ctx); h = LN2(x)
     if ((rc = timed(PC_GEMM_FC1, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.fc1.w, L.fc1.b, FFN, Mi, f, d, d, d, f, EPI_BF16_GELU, nullptr, 0, (int)M); }))) return rc;
     if (l + 1 < cfg.n_layers) {                                                                    // x += fc2(ffn); h = LN1 of the next layer
-      if ((rc = resid_gemm_ln(FFN, L.fc2, X, Mi, M, f, esm_layers[l + 1].ln1, Hh, splitk_ws(Mi, d, batch_rows), splitk.bytes, PC_GEMM_FC2))) return rc;
+      if ((rc = resid_gemm_ln(FFN, L.fc2, X, Mi, M, f, esm_layers[l + 1].ln1, Hh, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, PC_GEMM_FC2))) return rc;
     } else {
-      if ((rc = timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, batch_rows), splitk.bytes, (int)M); }))) return rc;
+      if ((rc = timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
     }
   }
   return PG_OK;
@@ -878,16 +883,16 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
       if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ctx_sel.as<bf16_t>(), L.col_out.w, L.col_out.b, XS, Ni, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
       if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, XS, L.ln_ffn.g, L.ln_ffn.b, h_sel.as<bf16_t>(), n_sel, d, eps); }))) return rc;
       if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, h_sel.as<bf16_t>(), L.fc1.w, L.fc1.b, ffn_sel.as<bf16_t>(), Ni, f, d, d, d, f, EPI_BF16_GELU); }))) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ffn_sel.as<bf16_t>(), L.fc2.w, L.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, batch_rows), splitk.bytes); }))) return rc;
+      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ffn_sel.as<bf16_t>(), L.fc2.w, L.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, f, batch_rows), splitk.bytes); }))) return rc;
       break;
     }
     if ((rc = resid_gemm_ln(CTX, L.col_out, X, Mi, M, d, L.ln_ffn, Hh, nullptr, 0, PC_GEMM_OUT))) return rc;                 // x += col_out(ctx); h = LN_ffn(x)
     // feed forward
     if ((rc = timed(PC_GEMM_FC1, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.fc1.w, L.fc1.b, FFN, Mi, f, d, d, d, f, EPI_BF16_GELU, nullptr, 0, (int)M); }))) return rc;
     if (l + 1 < cfg.n_layers) {                                                                      // x += fc2(ffn); h = LN_row of the next layer
-      if ((rc = resid_gemm_ln(FFN, L.fc2, X, Mi, M, f, msa_layers[l + 1].ln_row, Hh, splitk_ws(Mi, d, batch_rows), splitk.bytes, PC_GEMM_FC2))) return rc;
+      if ((rc = resid_gemm_ln(FFN, L.fc2, X, Mi, M, f, msa_layers[l + 1].ln_row, Hh, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, PC_GEMM_FC2))) return rc;
     } else {
-      if ((rc = timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, batch_rows), splitk.bytes, (int)M); }))) return rc;
+      if ((rc = timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
     }
   }
   return PG_OK;

@@ -1126,6 +1126,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   *o = r;
 }
 
+int gemm_splitk_splits(int K) { return K % 1280 == 0 ? K / 1280 : (K % 1024 == 0 ? K / 1024 : 1); }
+size_t gemm_splitk_ws_bytes(int M, int N, int K) {       // the kernels write whole tiles: at most M rounded up to the 256-row padding
+  return (size_t)gemm_splitk_splits(K) * ((M + 255) / 256 * 256) * N * 4;
+}
+
 int launch_gemm_bf16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K,
                      int ldx, int ldw, int ldo, int epi, float* ws, size_t ws_bytes, int m_live) {
   static const int variant = [] { const char* e = getenv("PGIBBS_GEMM"); return e ? atoi(e) : 2; }();
@@ -1164,7 +1169,7 @@ int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, co
   // Deep K with few tiles (fc2 of a few dozen chains: K = 5120, 80-320 tiles): K-splits run side by side into ws, then one
   // reduction adds them to the residual stream in fixed order.  M = 1024: 43 -> 21 us, M = 32: 15.6 -> 8 us.
   if (epi == EPI_F32_RESID && ws && K >= 2048 && M >= 16 && M % 16 == 0 && N % 64 == 0 && variant != 1 && variant < 6) {
-    const int splits = K % 1280 == 0 ? K / 1280 : (K % 1024 == 0 ? K / 1024 : 1);
+    const int splits = gemm_splitk_splits(K);
     const int Mr = M <= 16 ? 16 : (M <= 32 ? 32 : (M <= 256 ? (M + 63) / 64 * 64 : M));   // rows the kernels write (their tile heights)
     const long t64 = (long)(Mr / 64) * (N / 64);
     const bool pp_sized = M % 256 == 0 && N % 256 == 0 && (long)(M / 256) * (N / 256) >= 128;   // the 256^2 kernel fills the chip
@@ -1173,6 +1178,7 @@ int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, co
     // (round 4: ONE launch of N / 16 workgroups with 16 waves splitting K instead of the K-splits + reduction was measured slower,
     // config 1 1.73 -> 1.92 ms per iteration: every workgroup re-reads the whole [M][K] operand, 327 KB at K = 5120, and a CU's
     // L2 -> L1 path carries ~130 GB/s -- the K-splits spread those reads over four times as many CUs)
+    // ws_bytes >= gemm_splitk_ws_bytes(M, N, K) by the callers' sizing: the comparison guards the buffer, it is not the dispatch
     if (splits > 1 && small && (size_t)splits * stride * 4 <= ws_bytes && (K / splits) % 64 == 0) {
       int rc;
       const int Ks = K / splits;

@@ -7,6 +7,11 @@
 // height by the real row count (launch_gemm_big)
 int launch_gemm_bf16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K,
                      int ldx, int ldw, int ldo, int epi, float* ws = nullptr, size_t ws_bytes = 0, int m_live = 0);
+// The K-splits a residual GEMM of depth K runs as when it is given scratch and has few tiles (1: never split), and the scratch that
+// form needs for M token rows -- whoever hands `ws` to launch_gemm_bf16 sizes it with this, so that split or unsplit is decided by
+// the shape alone, never by how large a buffer happens to be
+int gemm_splitk_splits(int K);
+size_t gemm_splitk_ws_bytes(int M, int N, int K);
 // variant: 1 = lockstep tiles only, 2 = default dispatch, 6 / 7 = force 64^2 / 128^2 tiles, 21.. = ablations of the
 // ping-pong kernel (micro-benchmark entry)
 int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,

@@ -7,7 +7,12 @@
 
 PG_OPS_BEGIN
 
-constexpr int kMaxCh = 8;  // d <= 8 * 256 = 2048
+// A lane holds chunks lane, lane + 64, ... of the row as float4 v[NCH]: NCH is a template parameter of everything below, deduced
+// from the array.  kMaxCh = 8 (d <= 2048) is the form every model up to d_model 2048 runs, and the only one the residual GEMMs
+// (gemm_epilogue.h, gemm_rowln.hip) instantiate; kMaxChWide = 10 (d <= 2560: ESM-2 3B) costs 40 VGPRs per row instead of 32.
+// The arithmetic and its order -- per lane the chunks in ascending order, then wave_sum -- do not depend on NCH.
+constexpr int kMaxCh = 8;       // d <= 8 * 256 = 2048
+constexpr int kMaxChWide = 10;  // d <= 10 * 256 = 2560
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -16,23 +21,24 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // normalise the row held in v[] (chunk c = lane + 64*i) in place: (x-mean)/sqrt(var+eps)*g + b
-__device__ __forceinline__ void ln_inplace(float4 (&v)[kMaxCh], int nch4, int lane, int d, float eps,
+template <int NCH>
+__device__ __forceinline__ void ln_inplace(float4 (&v)[NCH], int nch4, int lane, int d, float eps,
                                            const float* __restrict__ gamma, const float* __restrict__ beta) {
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) s = __fadd_rn(s, __fadd_rn(__fadd_rn(v[i].x, v[i].y), __fadd_rn(v[i].z, v[i].w)));
   const float mean = __fdiv_rn(wave_sum(s), (float)d);
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) {
       v[i].x = __fsub_rn(v[i].x, mean); v[i].y = __fsub_rn(v[i].y, mean); v[i].z = __fsub_rn(v[i].z, mean); v[i].w = __fsub_rn(v[i].w, mean);
       q = __fadd_rn(q, __fadd_rn(__fmaf_rn(v[i].x, v[i].x, __fmul_rn(v[i].y, v[i].y)), __fmaf_rn(v[i].z, v[i].z, __fmul_rn(v[i].w, v[i].w))));
     }
   const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(__fdiv_rn(wave_sum(q), (float)d), eps)));
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) {
       const int c = lane + 64 * i;
       const float4 g = ((const float4*)gamma)[c], b = ((const float4*)beta)[c];
@@ -49,10 +55,11 @@ __device__ __forceinline__ void ln_inplace(float4 (&v)[kMaxCh], int nch4, int la
 // x_lo.w_hi + x_hi.w_lo + x_hi.w_hi in its fp32 accumulator -- whichever tile kernel runs it; the fused 16-wave kernel
 // (gemm_w16.hip) reads only the first two blocks of each group and issues the same three products from registers.
 // dup = false leaves the third block of every group unwritten (the consumer is the fused kernel: gemm_split3_fused).
-__device__ __forceinline__ void store_row_bf16(bf16_t* dst, const float4 (&v)[kMaxCh], int nch4, int lane, bool split3 = false,
+template <int NCH>
+__device__ __forceinline__ void store_row_bf16(bf16_t* dst, const float4 (&v)[NCH], int nch4, int lane, bool split3 = false,
                                                bool dup = true) {
 #pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
+  for (int i = 0; i < NCH; ++i)
     if (lane + 64 * i < nch4) {
       const int ci = lane + 64 * i;              // float4 index = columns 4 ci .. 4 ci + 3
       uint2 p;

@@ -27,8 +27,11 @@
 
 PG_OPS_BEGIN
 
-constexpr int kRopePass16 = 4;   // 8 H lane-slots / 64 lanes, H <= 32 (d_model <= 2048)
-constexpr int kRopePass32 = 8;   // 16 H lane-slots / 64 lanes
+// passes per row = lane-slots / 64, a template parameter of the kernels: H <= 32 (d_model <= 2048) keeps the 4- and 8-pass forms,
+// H <= 40 (d_model 2560: ESM-2 3B) runs 5 and 10 passes -- the same lane ownership and the same arithmetic, a wider row in registers
+constexpr int kRopePass16 = 4, kRopePass16Wide = 5;    // 8 H lane-slots / 64 lanes
+constexpr int kRopePass32 = 8, kRopePass32Wide = 10;   // 16 H lane-slots / 64 lanes
+constexpr int kRopeHeads = 32, kRopeHeadsWide = 40;
 
 __device__ __forceinline__ void rope_pair(float& lo, float& hi, float c, float s) {
   const float a = lo, b = hi;
@@ -46,6 +49,7 @@ __device__ __forceinline__ void rope_word16(uint32_t& wl, uint32_t& wh, float c0
   wh = pack_op2(h0, h1);
 }
 
+template <int NP>
 __global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, const float* __restrict__ tab, int M, int T, int H,
                                                     int ld) {
   const int lane = threadIdx.x & 63;
@@ -55,9 +59,9 @@ __global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, c
   for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
     const float4* tr = (const float4*)(tab + (size_t)(row % T) * 64);
     uint4* base = (uint4*)(qkv + (size_t)row * ld);             // 8 uint4 per head
-    uint4 lo[kRopePass16], hi[kRopePass16];
+    uint4 lo[NP], hi[NP];
 #pragma unroll
-    for (int i = 0; i < kRopePass16; ++i) {
+    for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
       if (s < slots) {
         const uint4* p = base + (s >> 2) * 8 + c;
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, c
     }
     const float4 ca = tr[2 * c], cb = tr[2 * c + 1], sa = tr[8 + 2 * c], sb = tr[8 + 2 * c + 1];
 #pragma unroll
-    for (int i = 0; i < kRopePass16; ++i) {
+    for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
       if (s < slots) {
         rope_word16(lo[i].x, hi[i].x, ca.x, sa.x, ca.y, sa.y);
@@ -83,6 +87,7 @@ __global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, c
 }
 
 // strict precision mode: the same rotation on an fp32 buffer
+template <int NP>
 __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, const float* __restrict__ tab, int M, int T, int H,
                                                     int ld) {
   const int lane = threadIdx.x & 63;
@@ -92,9 +97,9 @@ __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, co
   for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
     const float4* tr = (const float4*)(tab + (size_t)(row % T) * 64);
     float4* base = (float4*)(qkv + (size_t)row * ld);           // 16 float4 per head
-    float4 lo[kRopePass32], hi[kRopePass32];
+    float4 lo[NP], hi[NP];
 #pragma unroll
-    for (int i = 0; i < kRopePass32; ++i) {
+    for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
       if (s < slots) {
         const float4* p = base + (s >> 3) * 16 + c;
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, co
     }
     const float4 cs = tr[c], sn = tr[8 + c];
 #pragma unroll
-    for (int i = 0; i < kRopePass32; ++i) {
+    for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
       if (s < slots) {
         rope_pair(lo[i].x, hi[i].x, cs.x, sn.x);
@@ -119,25 +124,42 @@ __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, co
   }
 }
 
-int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld) {
-  if (H < 1 || H > 32) return fail(1, "rope: 1..32 heads of 64 (d_model <= 2048)");
-  if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
-  if (ld < 3 * H * 64 || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
-  if (M == 0) return 0;
-  if (M > 0x7fffffff - 4 * 8 * 1024) return fail(1, "rope: too many rows");     // 32-bit row arithmetic in the kernels
-  // the grid = what is resident at once (occupancy of the kernel x CUs, asked once), or fewer workgroups when the rows need fewer
+template <typename Kern>
+static int rope_occupancy(Kern kern) {
+  int v = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, 0) == hipSuccess && v > 0 ? v : 4;
+}
+
+// the grid = what is resident at once (occupancy of the kernel x CUs), or fewer workgroups when the rows need fewer
+template <typename Buf>
+static int rope_launch(void (*kern)(Buf*, const float*, int, int, int, int), int occ, hipStream_t s, Buf* qkv, const float* table, int64_t M,
+                       int T, int H, int ld) {
   static const int n_cu = [] {
     hipDeviceProp_t p; int dv = 0; (void)hipGetDevice(&dv);
     return hipGetDeviceProperties(&p, dv) == hipSuccess ? p.multiProcessorCount : 256;
   }();
-  static const int occ16 = [] { int v = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, rope16_kernel, 256, 0) == hipSuccess && v > 0 ? v : 4; }();
-  static const int occ32 = [] { int v = 0; return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, rope32_kernel, 256, 0) == hipSuccess && v > 0 ? v : 4; }();
-  const int64_t need = (M + 3) / 4, resident = (int64_t)n_cu * (f32 ? occ32 : occ16);
-  const dim3 grid((unsigned)(need < resident ? need : resident));
-  if (f32) hipLaunchKernelGGL(rope32_kernel, grid, dim3(256), 0, s, (float*)qkv, table, (int)M, T, H, ld);
-  else hipLaunchKernelGGL(rope16_kernel, grid, dim3(256), 0, s, (bf16_t*)qkv, table, (int)M, T, H, ld);
+  const int64_t need = (M + 3) / 4, resident = (int64_t)n_cu * occ;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(need < resident ? need : resident)), dim3(256), 0, s, qkv, table, (int)M, T, H, ld);
   PG_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld) {
+  if (H < 1 || H > kRopeHeadsWide) return fail(1, "rope: 1..40 heads of 64 (d_model <= 2560)");
+  if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
+  if (ld < 3 * H * 64 || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
+  if (M == 0) return 0;
+  if (M > 0x7fffffff - 4 * 8 * 1024) return fail(1, "rope: too many rows");     // 32-bit row arithmetic in the kernels
+  // asked once per instantiation (function-local statics: initialised thread-safely)
+  static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16>);
+  static const int occ32 = rope_occupancy(rope32_kernel<kRopePass32>);
+  static const int occ16w = rope_occupancy(rope16_kernel<kRopePass16Wide>);
+  static const int occ32w = rope_occupancy(rope32_kernel<kRopePass32Wide>);
+  const bool wide = H > kRopeHeads;
+  if (f32) return wide ? rope_launch(rope32_kernel<kRopePass32Wide>, occ32w, s, (float*)qkv, table, M, T, H, ld)
+                       : rope_launch(rope32_kernel<kRopePass32>, occ32, s, (float*)qkv, table, M, T, H, ld);
+  return wide ? rope_launch(rope16_kernel<kRopePass16Wide>, occ16w, s, (bf16_t*)qkv, table, M, T, H, ld)
+              : rope_launch(rope16_kernel<kRopePass16>, occ16, s, (bf16_t*)qkv, table, M, T, H, ld);
 }
 
 PG_OPS_END

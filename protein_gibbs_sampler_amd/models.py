@@ -58,11 +58,25 @@ class ESM1v(_Wrapper):
 class ESM2(_Wrapper):
     """esm2_t33_650M_UR50D: fair-esm's ESM-2 at 650M parameters (not a model of the original pgen package; the successor of ESM-1b
     in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
-    layout (weights.load_fair_esm_checkpoint); other ESM-2 sizes load when their heads are 64 wide and d_model <= 2048."""
+    layout (weights.load_fair_esm_checkpoint).  This wrapper promises the 650M model: a checkpoint wider than d_model 2048 (the 3B
+    file, 4.4 times the work per token) is refused with a message naming ESM2_3B.  The other released sizes have heads of 16 / 24 /
+    32 (8M / 35M / 150M) or 128 (15B) and are refused by head width: the engine's attention kernels implement heads of 64."""
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T33_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
                          "esm2_t33_650M_UR50D.pt", seed, precision, synthetic, config is not None)
+
+
+class ESM2_3B(_Wrapper):
+    """esm2_t36_3B_UR50D: ESM-2 at 3B parameters -- 36 layers, d_model 2560, 40 heads of 64, d_ffn 10240; about 5.7 GB of 16-bit
+    weights on the device (17 GB in precision="fp32").  The same wrapper as ESM2 (v2 checkpoint layout, ESM-1b alphabet and LM head)
+    with the wider configuration; the widest model the engine's row kernels hold (csrc/ln_row.h).  Sizes come from the file: a
+    narrower checkpoint with heads of 64 (the 650M file included) loads here without remark and runs as the model it is -- only the
+    opposite mismatch, a 3B file met by ESM2, is refused."""
+
+    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
+        super().__init__(config or dict(_w.ESM2_T36_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
+                         "esm2_t36_3B_UR50D.pt", seed, precision, synthetic, config is not None)
 
 
 class ESM_MSA1(_Wrapper):

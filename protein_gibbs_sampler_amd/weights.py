@@ -30,11 +30,14 @@ ESM1_T34_CONFIG = dict(ESM1_T6_CONFIG, n_layers=34, d_model=1280, n_heads=20, d_
 
 
 # ESM-2 (fair-esm `ESM2`, esm2_t33_650M_UR50D -- models.ESM2): the ESM-1b block stack and LM head without a position table and without
-# emb_layer_norm_before; positions enter through rotary embeddings of q and k in every layer (include/pgibbs.h PG_ARCH_ESM2).  The
-# other released sizes have heads of 64 only at 650M (and 3B, whose d_model = 2560 exceeds the row kernels' 2048).
+# emb_layer_norm_before; positions enter through rotary embeddings of q and k in every layer (include/pgibbs.h PG_ARCH_ESM2).  Of
+# the released sizes 650M and 3B have heads of 64 (8M / 35M / 150M: 16 / 24 / 32, 15B: 128 -- not engine models).
 ESM2_T33_CONFIG = dict(arch=_lib.PG_ARCH_ESM2, vocab=33, d_model=1280, n_layers=33, n_heads=20, d_ffn=5120, max_positions=1024,
                        pad_idx=1, mask_idx=32, cls_idx=0, eos_idx=2, token_dropout=1, max_msa_rows=0, layer_norm_eps=1e-5)
-MAX_D_MODEL = 2048           # the row kernels hold at most kMaxCh * 256 features (csrc/ln_row.h)
+# esm2_t36_3B_UR50D -- models.ESM2_3B: 36 layers of 40 heads, 4.4 times the arithmetic of the 650M model per token
+ESM2_T36_CONFIG = dict(ESM2_T33_CONFIG, d_model=2560, n_layers=36, n_heads=40, d_ffn=10240)
+MAX_D_MODEL = 2560           # the row kernels hold at most kMaxChWide * 256 features (csrc/ln_row.h)
+ESM2_650M_MAX_D_MODEL = 2048  # a wider file handed to a config of at most this width (models.ESM2) is refused: see below
 
 
 def rotary_inv_freq():
@@ -359,8 +362,13 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
         raise ValueError("checkpoint has %d heads of dimension %g: the engine's attention kernels implement head dimension 64 "
                          "(every model of pgen.models)" % (cfg["n_heads"], cfg["d_model"] / max(1, cfg["n_heads"])))
     if cfg["d_model"] > MAX_D_MODEL:
-        raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head) hold at most %d "
-                         "features per row (esm2_t36_3B_UR50D is out of reach)" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL))
+        raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head, rotation) hold at "
+                         "most %d features per row, 40 heads of 64 (esm2_t36_3B_UR50D)" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL))
+    # models.ESM2 / --model esm2 promise the 650M model: a 3B file is 4.4 times the work and is loaded on purpose, not by accident
+    if cfg["d_model"] > ESM2_650M_MAX_D_MODEL and base_cfg["d_model"] <= ESM2_650M_MAX_D_MODEL:
+        raise ValueError("checkpoint has d_model %d > %d, wider than the ESM-2 650M configuration it was loaded against: load "
+                         "esm2_t36_3B_UR50D with models.ESM2_3B / --model esm2_3b"
+                         % (cfg["d_model"], ESM2_650M_MAX_D_MODEL))
     if any(n.startswith("emb_layer_norm_before") or n.startswith("embed_positions") for n in state_names):
         raise ValueError("ESM-2 checkpoint with emb_layer_norm_before / embed_positions tensors: the ESM-2 engine has neither")
     n_layers_seen = 1 + max([int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", n) for n in state_names) if m] or [-1])

@@ -11,6 +11,11 @@ device buffers (pg_esm_gibbs_run_device), alternating ESM-1b / ESM-2 for `--roun
     (rows x 2 d_model x 2 B read + the same written) / time, next to the LayerNorm launches of the same run (class "layernorm":
     rows x d_model x (4 B read + 2 B written)) as the bandwidth yardstick of the box.
 
+`--size 3b` measures ESM-2 3B (36 x 2560, 40 heads; models.ESM2_3B) alone at the same three shapes: ms per iteration, the rotation
+and the LayerNorm launches at d_model 2560 with their GB/s.  Both sizes record the GEMM classes of the rotary model's profiled run
+("gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2": the launches that see every token row) as ms per launch and
+TFLOP/s = 2 rows N K / time.
+
 Prints one JSON line.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -35,8 +40,11 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3, help="alternations ESM-1b / ESM-2 per shape")
     ap.add_argument("--prof-iters", type=int, default=3, help="iterations of the profiled run")
-    ap.add_argument("--layers", type=int, default=33, help="fewer layers for a rehearsal")
+    ap.add_argument("--layers", type=int, default=None, help="fewer layers for a rehearsal (default: 33, or 36 with --size 3b)")
+    ap.add_argument("--size", choices=["650m", "3b"], default="650m", help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone")
     args = ap.parse_args(argv)
+    if args.layers is None:
+        args.layers = 36 if args.size == "3b" else 33
 
     import torch
     from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
@@ -51,8 +59,13 @@ def main(argv=None):
             m = cls(state_dict=weights.synthetic_state_dict(cfg, seed=0), config=cfg, precision="bf16")
         return esm_sampler.ESM_sampler(m, device="cuda:0")
 
-    samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), "esm2": build(models.ESM2, weights.ESM2_T33_CONFIG)}
-    d_model = weights.ESM2_T33_CONFIG["d_model"]
+    if args.size == "3b":
+        samplers = {"esm2_3b": build(models.ESM2_3B, weights.ESM2_T36_CONFIG)}
+        rotary, model_cfg = "esm2_3b", weights.ESM2_T36_CONFIG
+    else:
+        samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), "esm2": build(models.ESM2, weights.ESM2_T33_CONFIG)}
+        rotary, model_cfg = "esm2", weights.ESM2_T33_CONFIG
+    d_model, d_ffn = model_cfg["d_model"], model_cfg["d_ffn"]
 
     def job(s, B, L, P, iters):
         """-> a closure that runs `iters` Gibbs iterations of B chains from fresh device buffers and synchronises"""
@@ -73,7 +86,8 @@ def main(argv=None):
             lm.synchronize()
         return run
 
-    out = {"tool": "esm2_bench", "device": torch.cuda.get_device_name(0), "precision": "bf16", "layers": args.layers,
+    out = {"tool": "esm2_bench", "size": args.size, "d_model": d_model, "device": torch.cuda.get_device_name(0), "precision": "bf16",
+           "layers": args.layers,
            "iters": args.iters, "warmup": args.warmup, "rounds": args.rounds, "shapes": {}}
     for name, B, L, P in SHAPES:
         T = L + 2
@@ -91,15 +105,18 @@ def main(argv=None):
         for k in samplers:
             rec[k + "_ms_per_iteration"] = round(statistics.median(ms[k]), 4)
             rec[k + "_ms_per_iteration_rounds"] = [round(v, 4) for v in ms[k]]
-        rec["esm2_over_esm1b"] = round(rec["esm2_ms_per_iteration"] / rec["esm1b_ms_per_iteration"], 4)
+        if "esm1b" in samplers:
+            rec["esm2_over_esm1b"] = round(rec["esm2_ms_per_iteration"] / rec["esm1b_ms_per_iteration"], 4)
         # the rotation and the LayerNorm launches, by HIP events, in a run of their own
-        lm = samplers["esm2"].model.model
-        prof = job(samplers["esm2"], B, L, P, args.prof_iters)
+        lm = samplers[rotary].model.model
+        prof = job(samplers[rotary], B, L, P, args.prof_iters)
         lm.prof_enable(True)
         lm.prof_reset()
         prof()
         rope_ms, rope_n = lm.prof_get("rope")
         ln_ms, ln_n = lm.prof_get("layernorm")
+        gemm = {c: lm.prof_get(c) for c in ("gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2")}
+        gemm_kernels = {c: lm.prof_get_kernels(c) for c in gemm}
         lm.prof_enable(False)
         rows = B * T
         rec["rope_launches_per_iteration"] = rope_n // args.prof_iters
@@ -114,6 +131,13 @@ def main(argv=None):
             rec["layernorm_ms_per_launch"] = round(ln_ms / ln_n, 5)
             rec["layernorm_launches"] = ln_n
             rec["layernorm_GBps_if_full_rows"] = round(rows * d_model * 6 / (ln_ms / ln_n * 1e-3) / 1e9, 1)
+        # the classes whose launches see every token row (the pruned last layer's projections fall under "gemm_other")
+        nk = {"gemm_qkv": (3 * d_model, d_model), "gemm_out": (d_model, d_model), "gemm_fc1": (d_ffn, d_model), "gemm_fc2": (d_model, d_ffn)}
+        for c, (g_ms, g_n) in gemm.items():
+            if g_n:
+                n, k = nk[c]
+                rec[c] = {"launches": g_n, "ms_per_launch": round(g_ms / g_n, 5), "N": n, "K": k, "kernels": gemm_kernels[c],
+                          "TFLOPs": round(2.0 * rows * n * k / (g_ms / g_n * 1e-3) / 1e12, 1)}
         out["shapes"][name] = rec
     print(json.dumps(out))
 
