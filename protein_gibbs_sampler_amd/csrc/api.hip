@@ -10,8 +10,6 @@
 #include "gemm_epilogue.h"
 
 namespace pg {
-// debug entries: operand flavour by the `precision` argument (fp16 operands for PG_PREC_F16, else bf16)
-#define DBG_OPS(fn, ...) (precision == PG_PREC_F16 ? opf16::fn(__VA_ARGS__) : opbf16::fn(__VA_ARGS__))
 const char* last_error_cstr();
 }
 using namespace pg;
@@ -64,6 +62,61 @@ bool has_token(const int32_t* tokens, size_t n, int32_t id) {
   for (size_t i = 0; i < n; ++i)
     if (tokens[i] == id) return true;
   return false;
+}
+// A ragged batch (<pad> in some row; for the MSA model a ragged list of MSAs padded to one tensor, esm_msa_sampler.py:341): while
+// this lives the trunks mask keys at <pad> in attention, as fair-esm's key_padding_mask does
+struct PadFlag {
+  Engine& e;
+  PadFlag(Engine& e_, const int32_t* tokens, size_t n) : e(e_) { e.esm_pad_in_batch = has_token(tokens, n, e.cfg.pad_idx); }
+  ~PadFlag() { e.esm_pad_in_batch = false; }
+};
+
+// tokens[B][R][C] in (R = 1 for the ESM family), logits of every position out
+int forward_logits(Engine& e, const int32_t* tokens, int B, int R, int C, float* logits_out) {
+  DeviceGuard g(e.device);
+  const int64_t M = (int64_t)B * R * C;
+  int rc;
+  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
+  if ((rc = e.logits.ensure((size_t)M * e.cfg.vocab * 4, e.stream))) return rc;
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
+  {
+    PadFlag pad(e, tokens, (size_t)M);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
+  }
+  if (rc) return rc;
+  if ((rc = e.head(nullptr, nullptr, 1, C, M, e.logits.as<float>()))) return rc;
+  PG_HIP(hipMemcpyAsync(logits_out, e.logits.p, (size_t)M * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.chain_check())) return rc;
+  return check_finite(e, logits_out, (size_t)M * e.cfg.vocab);
+}
+
+// A Gibbs call on host buffers: tokens and the index table go to the device, run(d_tokens, d_idx, d_sampled_logits, d_sampled_tokens)
+// queues the loop (an output the caller did not ask for is null), and tokens and outputs come back.
+template <typename Run>
+int stage_gibbs(Engine& e, int32_t* tokens_inout, size_t n_tokens, const int32_t* idx, size_t n_draws, float* sampled_logits,
+                int32_t* sampled_tokens, Run&& run) {
+  const size_t tok_bytes = n_tokens * 4, n1 = n_draws ? n_draws : 1;
+  int rc;
+  if ((rc = e.d_tokens.ensure(tok_bytes, e.stream))) return rc;
+  if ((rc = e.d_idx.ensure(n1 * 4, e.stream))) return rc;
+  if (sampled_logits && (rc = e.d_samp_logits.ensure(n1 * e.cfg.vocab * 4, e.stream))) return rc;
+  if (sampled_tokens && (rc = e.d_samp_tok.ensure(n1 * 4, e.stream))) return rc;
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens_inout, tok_bytes, hipMemcpyHostToDevice, e.stream));
+  if (n_draws) PG_HIP(hipMemcpyAsync(e.d_idx.p, idx, n_draws * 4, hipMemcpyHostToDevice, e.stream));
+  if ((rc = run(e.d_tokens.as<int32_t>(), e.d_idx.as<int32_t>(), sampled_logits ? e.d_samp_logits.as<float>() : nullptr,
+                sampled_tokens ? e.d_samp_tok.as<int32_t>() : nullptr))) return rc;
+  // before the caller's token buffer (input AND output) is overwritten: a timed-out persistent launch is re-run by the caller
+  // macro, non-finite logits (PG_ERR_RANGE) leave the input intact for a caller that retries in another precision
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.finish_check())) return rc;
+  PG_HIP(hipMemcpyAsync(tokens_inout, e.d_tokens.p, tok_bytes, hipMemcpyDeviceToHost, e.stream));
+  if (sampled_logits && n_draws)
+    PG_HIP(hipMemcpyAsync(sampled_logits, e.d_samp_logits.p, n_draws * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
+  if (sampled_tokens && n_draws)
+    PG_HIP(hipMemcpyAsync(sampled_tokens, e.d_samp_tok.p, n_draws * 4, hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  return PG_OK;
 }
 }  // namespace
 
@@ -142,22 +195,7 @@ static int esm_forward_logits_once(pg_engine* h, const int32_t* tokens, int B, i
   if (B < 0 || T < 1) return fail(PG_ERR_INVALID, "bad shape");
   if (T > e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
   if (B == 0) return PG_OK;
-  DeviceGuard g(e.device);
-  const int64_t M = (int64_t)B * T;
-  int rc;
-  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
-  if ((rc = e.logits.ensure((size_t)M * e.cfg.vocab * 4, e.stream))) return rc;
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
-  e.esm_pad_in_batch = false;                       // ragged batch: <pad> keys are masked in attention (fair-esm key_padding_mask)
-  for (int64_t i = 0; i < M; ++i) e.esm_pad_in_batch |= tokens[i] == e.cfg.pad_idx;
-  rc = e.esm_trunk(e.d_tokens.as<int32_t>(), B, T);
-  e.esm_pad_in_batch = false;
-  if (rc) return rc;
-  if ((rc = e.head(nullptr, nullptr, 1, T, M, e.logits.as<float>()))) return rc;
-  PG_HIP(hipMemcpyAsync(logits_out, e.logits.p, (size_t)M * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  if ((rc = e.chain_check())) return rc;
-  return check_finite(e, logits_out, (size_t)M * e.cfg.vocab);
+  return forward_logits(e, tokens, B, 1, T, logits_out);
 }
 // The persistent single-chain trunk is an optimistic fast path: when one of its barriers timed out (Engine::chain_check) the
 // call's inputs are still intact in the caller's buffers, so it runs once more, now on the per-layer launches.
@@ -209,33 +247,13 @@ static int esm_gibbs_run_once(pg_engine* h, int32_t* tokens_inout, int B, int T,
   if (B == 0) return PG_OK;
   Engine& e = h->e;
   DeviceGuard g(e.device);
-  const size_t tok_bytes = (size_t)B * T * 4;
   const size_t n_draws = (size_t)B * P * n_iters;
   if (n_draws && (rc = check_idx_table(target_idx, n_draws, T, "pg_esm_gibbs_run"))) return rc;
-  // a ragged batch (<pad> in some row): keys at <pad> are masked in attention, as fair-esm's key_padding_mask does
-  struct PadFlag { Engine& e; ~PadFlag() { e.esm_pad_in_batch = false; } } pad_reset{e};
-  e.esm_pad_in_batch = has_token(tokens_inout, (size_t)B * T, e.cfg.pad_idx);
-  if ((rc = e.d_tokens.ensure(tok_bytes, e.stream))) return rc;
-  if ((rc = e.d_idx.ensure((n_draws ? n_draws : 1) * 4, e.stream))) return rc;
-  if (sampled_logits && (rc = e.d_samp_logits.ensure((n_draws ? n_draws : 1) * e.cfg.vocab * 4, e.stream))) return rc;
-  if (sampled_tokens && (rc = e.d_samp_tok.ensure((n_draws ? n_draws : 1) * 4, e.stream))) return rc;
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens_inout, tok_bytes, hipMemcpyHostToDevice, e.stream));
-  if (n_draws) PG_HIP(hipMemcpyAsync(e.d_idx.p, target_idx, n_draws * 4, hipMemcpyHostToDevice, e.stream));
-  rc = e.esm_gibbs_device(e.d_tokens.as<int32_t>(), B, T, e.d_idx.as<int32_t>(), n_iters, P, params,
-                          sampled_logits ? e.d_samp_logits.as<float>() : nullptr,
-                          sampled_tokens ? e.d_samp_tok.as<int32_t>() : nullptr);
-  if (rc) return rc;
-  // before the caller's token buffer (input AND output) is overwritten: a timed-out persistent launch is re-run by the caller
-  // macro, non-finite logits (PG_ERR_RANGE) leave the input intact for a caller that retries in another precision
-  PG_HIP(hipStreamSynchronize(e.stream));
-  if ((rc = e.finish_check())) return rc;
-  PG_HIP(hipMemcpyAsync(tokens_inout, e.d_tokens.p, tok_bytes, hipMemcpyDeviceToHost, e.stream));
-  if (sampled_logits && n_draws)
-    PG_HIP(hipMemcpyAsync(sampled_logits, e.d_samp_logits.p, n_draws * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
-  if (sampled_tokens && n_draws)
-    PG_HIP(hipMemcpyAsync(sampled_tokens, e.d_samp_tok.p, n_draws * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  return PG_OK;
+  PadFlag pad(e, tokens_inout, (size_t)B * T);
+  return stage_gibbs(e, tokens_inout, (size_t)B * T, target_idx, n_draws, sampled_logits, sampled_tokens,
+                     [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
+                       return e.esm_gibbs_device(d_tok, B, T, d_idx, n_iters, P, params, d_lg, d_st);
+                     });
 }
 int pg_esm_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int T, const int32_t* target_idx, int n_iters, int P,
                      const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
@@ -249,20 +267,7 @@ int pg_msa_forward_logits(pg_engine* h, const int32_t* tokens, int B, int R, int
   if (e.cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
   if (B < 0 || R < 1 || C < 1) return fail(PG_ERR_INVALID, "bad shape");
   if (B == 0) return PG_OK;
-  DeviceGuard g(e.device);
-  const int64_t M = (int64_t)B * R * C;
-  int rc;
-  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
-  if ((rc = e.logits.ensure((size_t)M * e.cfg.vocab * 4, e.stream))) return rc;
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
-  // a ragged list of MSAs padded to one tensor (esm_msa_sampler.py:341): fair-esm's padding semantics in both attention blocks
-  struct PadFlag { Engine& e; ~PadFlag() { e.esm_pad_in_batch = false; } } pad_reset{e};
-  e.esm_pad_in_batch = has_token(tokens, (size_t)M, e.cfg.pad_idx);
-  if ((rc = e.msa_trunk(e.d_tokens.as<int32_t>(), B, R, C))) return rc;
-  if ((rc = e.head(nullptr, nullptr, 1, C, M, e.logits.as<float>()))) return rc;
-  PG_HIP(hipMemcpyAsync(logits_out, e.logits.p, (size_t)M * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  return check_finite(e, logits_out, (size_t)M * e.cfg.vocab);
+  return forward_logits(e, tokens, B, R, C, logits_out);
 }
 
 int pg_msa_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, const int32_t* target_idx, int n_iters,
@@ -274,28 +279,12 @@ int pg_msa_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, c
   if (B == 0) return PG_OK;
   Engine& e = h->e;
   DeviceGuard g(e.device);
-  const size_t tok_bytes = (size_t)B * R * C * 4;
   const size_t n_draws = (size_t)B * R * P * n_iters;
   if (n_draws && (rc = check_idx_table(target_idx, n_draws, C, "pg_msa_gibbs_run"))) return rc;
-  if ((rc = e.d_tokens.ensure(tok_bytes, e.stream))) return rc;
-  if ((rc = e.d_idx.ensure((n_draws ? n_draws : 1) * 4, e.stream))) return rc;
-  if (sampled_logits && (rc = e.d_samp_logits.ensure((n_draws ? n_draws : 1) * e.cfg.vocab * 4, e.stream))) return rc;
-  if (sampled_tokens && (rc = e.d_samp_tok.ensure((n_draws ? n_draws : 1) * 4, e.stream))) return rc;
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens_inout, tok_bytes, hipMemcpyHostToDevice, e.stream));
-  if (n_draws) PG_HIP(hipMemcpyAsync(e.d_idx.p, target_idx, n_draws * 4, hipMemcpyHostToDevice, e.stream));
-  rc = e.msa_gibbs_device(e.d_tokens.as<int32_t>(), B, R, C, e.d_idx.as<int32_t>(), n_iters, P, params,
-                          sampled_logits ? e.d_samp_logits.as<float>() : nullptr,
-                          sampled_tokens ? e.d_samp_tok.as<int32_t>() : nullptr);
-  if (rc) return rc;
-  PG_HIP(hipStreamSynchronize(e.stream));
-  if ((rc = e.range_check())) return rc;             // before the caller's tokens are overwritten
-  PG_HIP(hipMemcpyAsync(tokens_inout, e.d_tokens.p, tok_bytes, hipMemcpyDeviceToHost, e.stream));
-  if (sampled_logits && n_draws)
-    PG_HIP(hipMemcpyAsync(sampled_logits, e.d_samp_logits.p, n_draws * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
-  if (sampled_tokens && n_draws)
-    PG_HIP(hipMemcpyAsync(sampled_tokens, e.d_samp_tok.p, n_draws * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  return PG_OK;
+  return stage_gibbs(e, tokens_inout, (size_t)B * R * C, target_idx, n_draws, sampled_logits, sampled_tokens,
+                     [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
+                       return e.msa_gibbs_device(d_tok, B, R, C, d_idx, n_iters, P, params, d_lg, d_st);
+                     });
 }
 
 int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
@@ -341,28 +330,12 @@ int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, in
       return PG_OK;
     }
   }
-  const size_t tok_bytes = (size_t)B * R * C * 4;
   const size_t n_draws = (size_t)B * P_max * n_steps;
   if (n_draws && (rc = check_idx_table(step_idx, n_draws, C, "pg_msa_gibbs_single_batch_run"))) return rc;
-  if ((rc = e.d_tokens.ensure(tok_bytes, e.stream))) return rc;
-  if ((rc = e.d_idx.ensure((n_draws ? n_draws : 1) * 4, e.stream))) return rc;
-  if (sampled_logits && (rc = e.d_samp_logits.ensure((n_draws ? n_draws : 1) * e.cfg.vocab * 4, e.stream))) return rc;
-  if (sampled_tokens && (rc = e.d_samp_tok.ensure((n_draws ? n_draws : 1) * 4, e.stream))) return rc;
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens_inout, tok_bytes, hipMemcpyHostToDevice, e.stream));
-  if (n_draws) PG_HIP(hipMemcpyAsync(e.d_idx.p, step_idx, n_draws * 4, hipMemcpyHostToDevice, e.stream));
-  rc = e.msa_single_device(e.d_tokens.as<int32_t>(), B, R, C, mask_row, target_row, e.d_idx.as<int32_t>(), step_sample_flag,
-                           n_steps, P_max, params, sampled_logits ? e.d_samp_logits.as<float>() : nullptr,
-                           sampled_tokens ? e.d_samp_tok.as<int32_t>() : nullptr);
-  if (rc) return rc;
-  PG_HIP(hipStreamSynchronize(e.stream));
-  if ((rc = e.range_check())) return rc;             // before the caller's tokens are overwritten
-  PG_HIP(hipMemcpyAsync(tokens_inout, e.d_tokens.p, tok_bytes, hipMemcpyDeviceToHost, e.stream));
-  if (sampled_logits && n_draws)
-    PG_HIP(hipMemcpyAsync(sampled_logits, e.d_samp_logits.p, n_draws * e.cfg.vocab * 4, hipMemcpyDeviceToHost, e.stream));
-  if (sampled_tokens && n_draws)
-    PG_HIP(hipMemcpyAsync(sampled_tokens, e.d_samp_tok.p, n_draws * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  return PG_OK;
+  return stage_gibbs(e, tokens_inout, (size_t)B * R * C, step_idx, n_draws, sampled_logits, sampled_tokens,
+                     [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
+                       return e.msa_single_device(d_tok, B, R, C, mask_row, target_row, d_idx, step_sample_flag, n_steps, P_max, params, d_lg, d_st);
+                     });
 }
 
 // generate_single == the batched form with one template
@@ -389,7 +362,7 @@ int pg_msa_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int R,
 // ---- masked log-likelihood scoring (next-tier path: log_likelihood_batch) ---------------------------
 // rows: tokens[n_rows][width]; sample s scores token row row_of[s] at positions idx[s][P] (entries < 0 skipped, out = 0)
 // against targets[s][P]; out[s][P] = log_softmax(logits)[target].
-static int forward_logprobs(Engine& e, bool msa, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+static int forward_logprobs(Engine& e, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
                             const int32_t* idx, const int32_t* targets, int n_sel, int P, float* out) {
   DeviceGuard g(e.device);
   const int64_t M = (int64_t)B * R * C;
@@ -408,9 +381,10 @@ static int forward_logprobs(Engine& e, bool msa, const int32_t* tokens, int B, i
   PG_HIP(hipMemcpyAsync(e.d_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
   PG_HIP(hipMemcpyAsync(e.d_samp_tok.p, targets, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
   PG_HIP(hipMemcpyAsync(e.d_rowmap.p, row_of, (size_t)n_sel * 4, hipMemcpyHostToDevice, e.stream));
-  e.esm_pad_in_batch = has_token(tokens, (size_t)M, e.cfg.pad_idx);      // ragged batch: <pad> keys masked (both architectures)
-  rc = msa ? e.msa_trunk(e.d_tokens.as<int32_t>(), B, R, C) : e.esm_trunk(e.d_tokens.as<int32_t>(), B, C);
-  e.esm_pad_in_batch = false;
+  {
+    PadFlag pad(e, tokens, (size_t)M);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
+  }
   if (rc) return rc;
   if ((rc = e.head(e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(), P, C, n, e.logits.as<float>()))) return rc;
   if ((rc = launch_logprob_gather(e.stream, e.logits.as<float>(), e.cfg.vocab, 1, C, e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(),
@@ -426,7 +400,7 @@ int pg_esm_forward_logprobs(pg_engine* h, const int32_t* tokens, int B, int T, c
   if (!h->e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
   if (B < 0 || T < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
   if (T > h->e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
-  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprobs(h->e, false, tokens, B, 1, T, row_of, idx, targets, n_sel, P, out));
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprobs(h->e, tokens, B, 1, T, row_of, idx, targets, n_sel, P, out));
 }
 
 int pg_msa_forward_logprobs(pg_engine* h, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
@@ -434,7 +408,7 @@ int pg_msa_forward_logprobs(pg_engine* h, const int32_t* tokens, int B, int R, i
   if (!h || !tokens || !row_of || !idx || !targets || !out) return fail(PG_ERR_INVALID, "pg_msa_forward_logprobs: null argument");
   if (h->e.cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
   if (B < 0 || R < 1 || C < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
-  return forward_logprobs(h->e, true, tokens, B, R, C, row_of, idx, targets, n_sel, P, out);
+  return forward_logprobs(h->e, tokens, B, R, C, row_of, idx, targets, n_sel, P, out);
 }
 
 int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
@@ -592,20 +566,20 @@ int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const
     PG_HIP(hipMemcpy(out, dout, (size_t)M * N * 4, hipMemcpyDeviceToHost));
     return PG_OK;
   }
-  if ((rc = DBG_OPS(launch_f32_to_bf16, nullptr, dx, bx, (int64_t)Mp * K, 1.f))) return rc;
-  if ((rc = DBG_OPS(launch_f32_to_bf16, nullptr, dw, bw, (int64_t)N * K, 1.f))) return rc;
+  if ((rc = OPS(launch_f32_to_bf16, nullptr, dx, bx, (int64_t)Mp * K, 1.f))) return rc;
+  if ((rc = OPS(launch_f32_to_bf16, nullptr, dw, bw, (int64_t)N * K, 1.f))) return rc;
   if (epi == 2) PG_HIP(hipMemcpy(dout, out, (size_t)M * N * 4, hipMemcpyHostToDevice));     // residual variant: out += x w^T + b
   if (epi == 3 || epi == 4) {                       // bf16 outputs (the QKV / fc1 epilogues), widened to fp32 for the caller
     bf16_t* bout = (bf16_t*)t.get((size_t)Mp * N * 2);
     if (!bout) return fail(PG_ERR_HIP, "hipMalloc failed");
-    if ((rc = DBG_OPS(launch_gemm_bf16, nullptr, bx, bw, db, bout, M <= 256 ? round_up(M, 16) : Mp, N, K, K, K, N,
+    if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, bout, M <= 256 ? round_up(M, 16) : Mp, N, K, K, K, N,
                       epi == 4 ? EPI_BF16_GELU : EPI_BF16, nullptr, 0, M))) return rc;
-    if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bout, dout, (int64_t)M * N))) return rc;
+    if ((rc = OPS(launch_bf16_to_f32, nullptr, bout, dout, (int64_t)M * N))) return rc;
   } else {
     // the residual variant gets split-K scratch, as the engine gives its fc2 GEMMs (taken for deep K and few tiles)
-    const size_t ws_bytes = epi == 2 ? DBG_OPS(gemm_splitk_ws_bytes, Mp, N, K) : 0;
+    const size_t ws_bytes = epi == 2 ? OPS(gemm_splitk_ws_bytes, Mp, N, K) : 0;
     float* ws = ws_bytes && ws_bytes <= ((size_t)1 << 30) ? (float*)t.get(ws_bytes) : nullptr;
-    if ((rc = DBG_OPS(launch_gemm_bf16, nullptr, bx, bw, db, dout, M <= 256 ? round_up(M, 16) : Mp, N, K, K, K, N,
+    if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, dout, M <= 256 ? round_up(M, 16) : Mp, N, K, K, K, N,
                       epi == 2 ? EPI_F32_RESID : (epi ? EPI_F32_GELU : EPI_F32), ws, ws ? ws_bytes : 0, M))) return rc;
   }
   PG_HIP(hipDeviceSynchronize());
@@ -855,9 +829,9 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
   float* dc = (float*)t.get((size_t)M * d * 4);
   if (!dq || !bq || !bc || !dc) return fail(PG_ERR_HIP, "hipMalloc failed");
   PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
-  if ((rc = DBG_OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
-  if ((rc = DBG_OPS(launch_attention_bf16, nullptr, bq, bc, B, T, H, 3 * d, d, d, 2 * d, nullptr, -1))) return rc;
-  if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
+  if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
+  if ((rc = OPS(launch_attention_bf16, nullptr, bq, bc, B, T, H, 3 * d, d, d, 2 * d, nullptr, -1))) return rc;
+  if ((rc = OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(ctx, dc, (size_t)M * d * 4, hipMemcpyDeviceToHost));
   return PG_OK;
@@ -883,9 +857,9 @@ int pg_dbg_layernorm_operand(int device, int precision, const float* x, const fl
   PG_HIP(hipMemcpy(dx, x, (size_t)M * d * 4, hipMemcpyHostToDevice));
   PG_HIP(hipMemcpy(dg, gamma, (size_t)d * 4, hipMemcpyHostToDevice));
   PG_HIP(hipMemcpy(dbt, beta, (size_t)d * 4, hipMemcpyHostToDevice));
-  if ((rc = DBG_OPS(launch_layernorm_bf16, nullptr, dx, dg, dbt, h, M, d, eps, split, 0, 0, true))) return rc;
+  if ((rc = OPS(launch_layernorm_bf16, nullptr, dx, dg, dbt, h, M, d, eps, split, 0, 0, true))) return rc;
   if (split) return split3_rows_to_host(h, y, M, d);
-  if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, h, dy, (int64_t)M * d))) return rc;
+  if ((rc = OPS(launch_bf16_to_f32, nullptr, h, dy, (int64_t)M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(y, dy, (size_t)M * d * 4, hipMemcpyDeviceToHost));
   return PG_OK;
@@ -912,9 +886,9 @@ int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
   if (precision == PG_PREC_FP32) {
     if ((rc = launch_rope(nullptr, dq, true, dtab, T, M, T, H, 3 * d))) return rc;
   } else {
-    if ((rc = DBG_OPS(launch_f32_to_bf16, nullptr, dq, bq, n, 1.f))) return rc;
-    if ((rc = DBG_OPS(launch_rope, nullptr, bq, false, dtab, T, M, T, H, 3 * d))) return rc;
-    if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bq, dq, n))) return rc;
+    if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, n, 1.f))) return rc;
+    if ((rc = OPS(launch_rope, nullptr, bq, false, dtab, T, M, T, H, 3 * d))) return rc;
+    if ((rc = OPS(launch_bf16_to_f32, nullptr, bq, dq, n))) return rc;
   }
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(qkv, dq, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -950,17 +924,17 @@ int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, in
   float* dc = (float*)t.get((size_t)M * d * 4);
   if (!dq || !bq || !bc || !dc) return fail(PG_ERR_HIP, "hipMalloc failed");
   PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
-  if ((rc = DBG_OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
+  if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
   if (which == 0) {
     // scratch for the split-R mode (taken when B*H*ceil(C/64) < 384 and R >= 8), so the tests exercise both modes
     const size_t pbytes = (size_t)B * H * 16 * C * 576 * 4 + (size_t)B * H * (C / 16 + 9) * 18 * 1024;
     float* part = pbytes <= ((size_t)1 << 30) ? (float*)t.get(pbytes) : nullptr;
-    if ((rc = DBG_OPS(launch_msa_row_attention_bf16, nullptr, bq, bc, B, R, C, H, 3 * d, d, d, 2 * d, scale, part, part ? pbytes : 0, 0))) return rc;
+    if ((rc = OPS(launch_msa_row_attention_bf16, nullptr, bq, bc, B, R, C, H, 3 * d, d, d, 2 * d, scale, part, part ? pbytes : 0, 0))) return rc;
   } else {
     SeqLayout col = {C, R * C, 1, C};
-    if ((rc = DBG_OPS(launch_attention_seq_bf16, nullptr, bq, bc, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, nullptr, -1))) return rc;
+    if ((rc = OPS(launch_attention_seq_bf16, nullptr, bq, bc, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, nullptr, -1))) return rc;
   }
-  if ((rc = DBG_OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
+  if ((rc = OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(ctx, dc, (size_t)M * d * 4, hipMemcpyDeviceToHost));
   return PG_OK;

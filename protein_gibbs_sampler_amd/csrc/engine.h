@@ -8,6 +8,10 @@
 
 namespace pg {
 
+// the operand-flavoured launchers (pg_common.h) by the `precision` in scope (an Engine's, the Uploader's, a debug entry's argument):
+// fp16 operands in PG_PREC_F16, bf16 otherwise (the strict mode's split operands are bf16 pairs)
+#define OPS(fn, ...) (precision == PG_PREC_F16 ? opf16::fn(__VA_ARGS__) : opbf16::fn(__VA_ARGS__))
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -39,15 +43,19 @@ struct DenseW {   // y = x W^T + b ; W bf16 [N][K], b fp32 [N].  Strict precisio
 };
 struct LnW { float* g = nullptr; float* b = nullptr; };
 
+struct FfnW { LnW ln; DenseW fc1, fc2; };   // x += fc2(gelu(fc1(LayerNorm(x))))
+
 struct EsmLayer {
-  LnW ln1, ln2;
-  DenseW qkv, out, fc1, fc2;
+  LnW ln1;
+  DenseW qkv, out;
+  FfnW ffn;
   bf16_t* bias_kv16 = nullptr;   // ESM-1 (add_bias_kv): [bias_k | bias_v] as 16-bit operands of the engine's flavour ...
   float* bias_kv32 = nullptr;    // ... and fp32 (strict mode)
 };
 struct MsaLayer {
-  LnW ln_row, ln_col, ln_ffn;
-  DenseW row_qkv, row_out, col_qkv, col_out, fc1, fc2;
+  LnW ln_row, ln_col;
+  DenseW row_qkv, row_out, col_qkv, col_out;
+  FfnW ffn;
   DenseW col_qkv_hm;      // col_qkv with its rows grouped per head ([q_h | k_h | v_h]): operand of the fused column kernel (gemm_colattn.hip)
 };
 
@@ -80,7 +88,8 @@ struct Engine {
   int64_t job_items = 0;                   // pg_engine_set_job_items: batch items of the whole (multi-GPU) job, 0 = this call
   int64_t order_items = 0;                 // > 0: order-changing kernel choices as for a job of this many items (batched generate_single: 1)
   int64_t job_batch(int64_t B) const { return order_items > 0 ? order_items : (job_items > B ? job_items : B); }
-  int64_t batch_rows = 0;                  // token rows of the JOB's forward (job_batch(B) x rows per item; set by the trunks)
+  int64_t batch_rows_for(int64_t B, int64_t rows_per_item) const { return job_batch(B) * rows_per_item; }
+  int64_t batch_rows = 0;                  // token rows of the JOB's forward (batch_rows_for; set by the trunks)
   int sel_gemm_rows(int64_t n_sel, int64_t Np) const;
   // launch-bound (small) Gibbs loops: one iteration captured as a hipGraph and replayed; the iteration number lives in
   // d_iter on the device, so the same graph serves every iteration
@@ -107,7 +116,6 @@ struct Engine {
   DevBuf chain_snap;
   static constexpr size_t kChainSnapBytes = 128, kChainLogMax = 64;
   bool chain_may_run(int B, int T) const;                    // would a forward of this shape take the persistent launch?
-  int64_t batch_rows_for(int B, int T) const { return job_batch(B) * T; }
   int chain_log_call(int32_t* d_tok, int B, int T, const int32_t* d_idx, int n_iters, int P, const pg_sample_params* sp, float* lg,
                      int32_t* st);
   // host-pinned word the draw / log-probability kernels set when a logit row is not finite (an fp16 operand that overflowed
@@ -142,19 +150,36 @@ struct Engine {
   int init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int precision);
 
   // ---- forward pieces (all on `stream`, device pointers) ----
+  int size_activations(int64_t Mp);   // x, h, qkv, ctx, ffn for Mp padded token rows
+  // the end of a layer on all Mi token rows (M real), both trunks.  ffn_block (bf16 / fp16): x += out(ctx); h = LN(x);
+  // x += fc2(gelu(fc1(h))); h = next_ln(x) when a layer follows.  ffn_strict: the FFN alone
+  int ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int Mi, int64_t M);
+  int ffn_strict(const FfnW& F, int Mi, int64_t M);
+  // finish the last layer on the n_draws selected rows only?  (PGIBBS_PRUNE_LAST=0: never) ... and that tail: the selected rows of
+  // x and ctx -> x_sel / ctx_sel, then ffn_block's steps on GEMMs of height Ni.  ln_in_gemm: the trunk folds LayerNorm into the
+  // weight-streaming GEMMs (fc1's too when Ni allows)
+  bool prune_last(int64_t n_draws, int64_t token_rows) const;
+  int pruned_tail(const DenseW& out, const FfnW& F, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int width, int64_t n_sel,
+                  const int32_t* d_iter, int Ni, bool ln_in_gemm);
   // tokens -> x (before ln_after).  With a selection (sel_idx != nullptr, bf16 mode) the LAST layer's out-proj, LN2 and
   // FFN run only on the selected rows and x_sel [n_sel][d] holds their residual stream (exact: nothing else reads
   // the last layer's output); head_compact() then consumes x_sel.
-  int esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx = nullptr, int P = 0, int64_t n_sel = 0,
-                const int32_t* d_iter = nullptr);
+  int esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx, int P, int64_t n_sel, const int32_t* d_iter);
   int head(const int32_t* d_idx, const int32_t* d_row_map, int P, int width, int64_t n_sel, float* d_logits,
            const float* x_src = nullptr);
+  // the trunk of this engine's architecture on tokens[B][R][C]; R = 1 for the ESM family (d_iter: its captured iteration only)
+  int trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx = nullptr, const int32_t* sel_row_map = nullptr, int P = 0,
+            int64_t n_sel = 0, const int32_t* d_iter = nullptr);
+  // One Gibbs iteration up to its logits: mask_idx scattered (if mask) to idx[n_rows][P] of the token rows mask_map, the trunk
+  // (pruned when prune_last says so), the LM head at idx[n_rows][P] of the token rows sel_map -> lg[n_rows * P][V].  A null map:
+  // row i is token row i.  dit: the device-side iteration counter of a captured iteration (pruned only)
+  int masked_logits(int32_t* d_tok, int B, int R, int C, const int32_t* idx, const int32_t* mask_map, const int32_t* sel_map,
+                    int64_t n_rows, int P, bool mask, int mask_idx, float* lg, const int32_t* dit = nullptr);
   int esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx, int n_iters, int P, const pg_sample_params* sp,
                        float* d_samp_logits, int32_t* d_samp_tok);
   // tokens[B][R][C] -> x; with a selection the LAST layer's column out-projection and FFN run on the selected rows only
   // (x_sel), as in esm_trunk
-  int msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx = nullptr, const int32_t* sel_row_map = nullptr,
-                int P = 0, int64_t n_sel = 0);
+  int msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int64_t n_sel);
   int msa_gibbs_device(int32_t* d_tok, int B, int R, int C, const int32_t* d_idx, int n_iters, int P,
                        const pg_sample_params* sp, float* d_samp_logits, int32_t* d_samp_tok);
   // generate_single on B templates of equal shape: step s masks row mask_row of every template and samples row target_row of

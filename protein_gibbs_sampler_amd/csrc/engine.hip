@@ -13,10 +13,6 @@
 
 namespace pg {
 
-// the operand-flavoured launchers (pg_common.h): fp16 operands in PG_PREC_F16, bf16 otherwise (the strict mode's split operands
-// are bf16 pairs)
-#define OPS(fn, ...) (precision == PG_PREC_F16 ? opf16::fn(__VA_ARGS__) : opbf16::fn(__VA_ARGS__))
-
 // ------------------------------------------------------------------------------------------------
 // error plumbing
 // ------------------------------------------------------------------------------------------------
@@ -127,6 +123,7 @@ namespace {
 struct Uploader {
   Engine* e;
   const TensorMap* tm;
+  const int precision;      // the engine's: OPS
   std::string err;
 
   float* f32(const std::string& name, int64_t numel) {
@@ -157,8 +154,7 @@ struct Uploader {
         ok = ok && launch_split3_bf16(e->stream, (const float*)tmp, (bf16_t*)dw + (size_t)p * n_each * Kw, n_each, K, scales[p],
                                       false, true) == 0;
       else
-        ok = ok && (e->precision == PG_PREC_F16 ? opf16::launch_f32_to_bf16(e->stream, (const float*)tmp, (bf16_t*)dw + (size_t)p * n_each * K, (int64_t)n_each * K, scales[p])
-                                              : opbf16::launch_f32_to_bf16(e->stream, (const float*)tmp, (bf16_t*)dw + (size_t)p * n_each * K, (int64_t)n_each * K, scales[p])) == 0;
+        ok = ok && OPS(launch_f32_to_bf16, e->stream, (const float*)tmp, (bf16_t*)dw + (size_t)p * n_each * K, (int64_t)n_each * K, scales[p]) == 0;
       ok = ok && hipStreamSynchronize(e->stream) == hipSuccess;
       ok = ok && hipMemcpy((float*)db + (size_t)p * n_each, b, (size_t)n_each * 4, hipMemcpyHostToDevice) == hipSuccess;
       if (ok && scales[p] != 1.0f) ok = launch_scale_f32(e->stream, (float*)db + (size_t)p * n_each, n_each, scales[p]) == 0 &&
@@ -183,8 +179,7 @@ struct Uploader {
     e->owned.push_back(d16);
     bool ok = hipMemcpy(d32, bk, (size_t)d * 4, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy((float*)d32 + d, bv, (size_t)d * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && (e->precision == PG_PREC_F16 ? opf16::launch_f32_to_bf16(e->stream, (const float*)d32, (bf16_t*)d16, 2 * d, 1.f)
-                                           : opbf16::launch_f32_to_bf16(e->stream, (const float*)d32, (bf16_t*)d16, 2 * d, 1.f)) == 0;
+    ok = ok && OPS(launch_f32_to_bf16, e->stream, (const float*)d32, (bf16_t*)d16, 2 * d, 1.f) == 0;
     ok = ok && hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) { err = "upload failed for " + kname; return false; }
     L.bias_kv32 = (float*)d32;
@@ -197,8 +192,7 @@ struct Uploader {
     if (hipMalloc(&dw, (size_t)in.N * in.K * 2) != hipSuccess || hipMalloc(&db, (size_t)in.N * 4) != hipSuccess) { err = "hipMalloc failed (head-major projection)"; return false; }
     e->owned.push_back(dw);
     e->owned.push_back(db);
-    const bool ok = (e->precision == PG_PREC_F16 ? opf16::launch_headmajor_qkv(e->stream, in.w, in.b, (bf16_t*)dw, (float*)db, H, in.K)
-                                                 : opbf16::launch_headmajor_qkv(e->stream, in.w, in.b, (bf16_t*)dw, (float*)db, H, in.K)) == 0 &&
+    const bool ok = OPS(launch_headmajor_qkv, e->stream, in.w, in.b, (bf16_t*)dw, (float*)db, H, in.K) == 0 &&
                     hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) { err = "head-major projection copy failed"; return false; }
     out.w = (bf16_t*)dw;
@@ -239,7 +233,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   TensorMap tm;
   for (int i = 0; i < n_tensors; ++i)
     if (tensors[i].name) tm.m[tensors[i].name] = &tensors[i];
-  Uploader up{this, &tm, ""};
+  Uploader up{this, &tm, prec, ""};
   const int d = cfg.d_model, f = cfg.d_ffn, V = cfg.vocab;
   const float qs = 0.125f;  // head_dim^-0.5 = 64^-0.5, folded into W_q and b_q (exact in bf16)
   bool ok = true;
@@ -265,9 +259,9 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
       ok = ok && up.ln(L.ln1, p + "self_attn_layer_norm", d);
       ok = ok && up.dense(L.qkv, {p + "self_attn.q_proj", p + "self_attn.k_proj", p + "self_attn.v_proj"}, {qs, 1.f, 1.f}, d, d);
       ok = ok && up.dense(L.out, {p + "self_attn.out_proj"}, {1.f}, d, d);
-      ok = ok && up.ln(L.ln2, p + "final_layer_norm", d);
-      ok = ok && up.dense(L.fc1, {p + "fc1"}, {1.f}, f, d);
-      ok = ok && up.dense(L.fc2, {p + "fc2"}, {1.f}, d, f);
+      ok = ok && up.ln(L.ffn.ln, p + "final_layer_norm", d);
+      ok = ok && up.dense(L.ffn.fc1, {p + "fc1"}, {1.f}, f, d);
+      ok = ok && up.dense(L.ffn.fc2, {p + "fc2"}, {1.f}, d, f);
       if (ok && esm1()) ok = up.bias_kv(L, p + "self_attn.bias_k", p + "self_attn.bias_v", d);
     }
   } else if (ok) {
@@ -284,9 +278,9 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
       ok = ok && up.dense(L.col_qkv, {cpre + "layer.q_proj", cpre + "layer.k_proj", cpre + "layer.v_proj"}, {qs, 1.f, 1.f}, d, d);
       if (ok && !strict()) ok = up.headmajor(L.col_qkv_hm, L.col_qkv, cfg.n_heads);
       ok = ok && up.dense(L.col_out, {cpre + "layer.out_proj"}, {1.f}, d, d);
-      ok = ok && up.ln(L.ln_ffn, ff + "layer_norm", d);
-      ok = ok && up.dense(L.fc1, {ff + "layer.fc1"}, {1.f}, f, d);
-      ok = ok && up.dense(L.fc2, {ff + "layer.fc2"}, {1.f}, d, f);
+      ok = ok && up.ln(L.ffn.ln, ff + "layer_norm", d);
+      ok = ok && up.dense(L.ffn.fc1, {ff + "layer.fc1"}, {1.f}, f, d);
+      ok = ok && up.dense(L.ffn.fc2, {ff + "layer.fc2"}, {1.f}, d, f);
     }
   }
   if (!ok) return fail(PG_ERR_WEIGHTS, up.err.empty() ? std::string("weight upload failed") : up.err);
@@ -305,7 +299,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
     std::vector<PgChainLayerW> tab(cfg.n_layers);
     for (int i = 0; i < cfg.n_layers; ++i) {
       const EsmLayer& L = esm_layers[i];
-      tab[i] = {L.ln1.g, L.ln1.b, L.qkv.w, L.qkv.b, L.out.w, L.out.b, L.ln2.g, L.ln2.b, L.fc1.w, L.fc1.b, L.fc2.w, L.fc2.b};
+      tab[i] = {L.ln1.g, L.ln1.b, L.qkv.w, L.qkv.b, L.out.w, L.out.b, L.ffn.ln.g, L.ffn.ln.b, L.ffn.fc1.w, L.ffn.fc1.b, L.ffn.fc2.w, L.ffn.fc2.b};
     }
     void* dt = nullptr;
     PG_HIP(hipMalloc(&dt, tab.size() * sizeof(PgChainLayerW)));
@@ -474,22 +468,86 @@ int Engine::rope(void* qkv_rows, int64_t M, int T) {
   return timed(PC_ROPE, [&] { return OPS(launch_rope, stream, qkv_rows, strict(), rope_tab, rope_rows, M, T, cfg.n_heads, 3 * cfg.d_model); });
 }
 
+int Engine::size_activations(int64_t Mp) {
+  if (Mp > 0x7fffffff / 4) return fail(PG_ERR_INVALID, "too many tokens in one call");
+  const size_t d = cfg.d_model, f = cfg.d_ffn;
+  const size_t w = strict() ? 3 : 1;                 // strict: h, ctx and ffn hold [lo | hi | hi] rows, qkv is fp32
+  int rc;
+  if ((rc = x.ensure((size_t)Mp * d * 4, stream))) return rc;
+  if ((rc = h.ensure((size_t)Mp * w * d * 2, stream))) return rc;
+  if ((rc = qkv.ensure((size_t)Mp * 3 * d * (strict() ? 4 : 2), stream))) return rc;
+  if ((rc = ctx.ensure((size_t)Mp * w * d * 2, stream))) return rc;
+  return ffn.ensure((size_t)Mp * w * f * 2, stream);
+}
+
+int Engine::ffn_strict(const FfnW& F, int Mi, int64_t M) {
+  float* X = x.as<float>();
+  bf16_t* H3 = h.as<bf16_t>();
+  int rc;
+  if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, F.ln.g, F.ln.b, H3, M, cfg.d_model, cfg.layer_norm_eps, true, 0, 0, dense3_wants_dup(F.fc1, Mi, true)); }))) return rc;
+  if ((rc = dense3_gelu(H3, F.fc1, Mi, &F.fc2))) return rc;
+  return dense3(ffn.as<bf16_t>(), F.fc2, X, Mi, true);
+}
+
+int Engine::ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int Mi, int64_t M) {
+  const int d = cfg.d_model, f = cfg.d_ffn;
+  float* X = x.as<float>();
+  bf16_t* Hh = h.as<bf16_t>();
+  bf16_t* FFN = ffn.as<bf16_t>();
+  int rc;
+  if ((rc = resid_gemm_ln(ctx.as<bf16_t>(), out, X, Mi, M, d, F.ln, Hh, nullptr, 0, PC_GEMM_OUT))) return rc;
+  if ((rc = timed(PC_GEMM_FC1, [&] { return OPS(launch_gemm_bf16, stream, Hh, F.fc1.w, F.fc1.b, FFN, Mi, f, d, d, d, f, EPI_BF16_GELU, nullptr, 0, (int)M); }))) return rc;
+  if (next_ln) return resid_gemm_ln(FFN, F.fc2, X, Mi, M, f, *next_ln, Hh, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, PC_GEMM_FC2);
+  return timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, F.fc2.w, F.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); });
+}
+
+bool Engine::prune_last(int64_t n_draws, int64_t token_rows) const {
+  static const int prune = [] { const char* e = getenv("PGIBBS_PRUNE_LAST"); return e ? atoi(e) : 1; }();
+  return prune && !strict() && n_draws > 0 && 2 * n_draws < token_rows;
+}
+
+int Engine::pruned_tail(const DenseW& out, const FfnW& F, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int width,
+                        int64_t n_sel, const int32_t* d_iter_, int Ni, bool ln_in_gemm) {
+  const int d = cfg.d_model, f = cfg.d_ffn;
+  const float eps = cfg.layer_norm_eps;
+  const int64_t Np = round_up64(n_sel, kRowPad);
+  int rc;
+  if ((rc = x_sel.ensure((size_t)Np * d * 4, stream)) || (rc = ctx_sel.ensure((size_t)Np * d * 2, stream)) ||
+      (rc = h_sel.ensure((size_t)Np * d * 2, stream)) || (rc = ffn_sel.ensure((size_t)Np * f * 2, stream))) return rc;
+  float* XS = x_sel.as<float>();
+  bf16_t* FS = ffn_sel.as<bf16_t>();
+  rc = timed(PC_HEAD, [&] {
+    int r2 = launch_gather_rows(stream, x.as<float>(), XS, sel_idx, sel_row_map, P, width, n_sel, d * 4, d_iter_);
+    if (r2) return r2;
+    return launch_gather_rows(stream, ctx.as<bf16_t>(), ctx_sel.as<bf16_t>(), sel_idx, sel_row_map, P, width, n_sel, d * 2, d_iter_);
+  });
+  if (rc) return rc;
+  if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ctx_sel.as<bf16_t>(), out.w, out.b, XS, Ni, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
+  if (ln_in_gemm && gemm_ln_skinny_ok(Ni, f, d)) {
+    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, XS, d, F.ln.g, F.ln.b, eps, F.fc1.w, F.fc1.b, FS, Ni, f, d, d, f, EPI_BF16_GELU); }))) return rc;
+  } else {
+    if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, XS, F.ln.g, F.ln.b, h_sel.as<bf16_t>(), n_sel, d, eps); }))) return rc;
+    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, h_sel.as<bf16_t>(), F.fc1.w, F.fc1.b, FS, Ni, f, d, d, d, f, EPI_BF16_GELU); }))) return rc;
+  }
+  return timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FS, F.fc2.w, F.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, f, batch_rows), splitk.bytes); });
+}
+
+int Engine::trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int64_t n_sel,
+                  const int32_t* d_iter_) {
+  return cfg.arch == PG_ARCH_MSA1B ? msa_trunk(d_tok, B, R, C, sel_idx, sel_row_map, P, n_sel) : esm_trunk(d_tok, B, C, sel_idx, P, n_sel, d_iter_);
+}
+
 int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx, int P, int64_t n_sel, const int32_t* d_iter_) {
   const int d = cfg.d_model, f = cfg.d_ffn;
   const int64_t M = (int64_t)B * T;
   const int64_t Mp = round_up64(M, kRowPad);
-  if (Mp > 0x7fffffff / 4) return fail(PG_ERR_INVALID, "too many tokens in one call");
-  batch_rows = job_batch(B) * T;
   int rc;
+  if ((rc = size_activations(Mp))) return rc;
+  batch_rows = batch_rows_for(B, T);
+  float* X = x.as<float>();
+  const float eps = cfg.layer_norm_eps;
   if (strict()) {
-    if ((rc = x.ensure((size_t)Mp * d * 4, stream))) return rc;
-    if ((rc = h.ensure((size_t)Mp * 3 * d * 2, stream))) return rc;        // [lo | hi | hi] rows
-    if ((rc = qkv.ensure((size_t)Mp * 3 * d * 4, stream))) return rc;
-    if ((rc = ctx.ensure((size_t)Mp * 3 * d * 2, stream))) return rc;
-    if ((rc = ffn.ensure((size_t)Mp * 3 * f * 2, stream))) return rc;
-    float* X = x.as<float>();
     float* QKVf = qkv.as<float>();
-    const float eps = cfg.layer_norm_eps;
     const int Mi = (int)Mp;
     rc = timed(PC_EMBED, [&] {
       return OPS(launch_embed_ln, stream, d_tok, embed, pos, nullptr, ln_before.g, ln_before.b, X, M, T, d, cfg.pad_idx,
@@ -504,23 +562,14 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
       if ((rc = rope(QKVf, M, T))) return rc;                                  // ESM-2 only
       if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), dense3_wants_dup(L.out, Mi) ? d : -d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32); }))) return rc;
       if ((rc = dense3(ctx.as<bf16_t>(), L.out, X, Mi, true))) return rc;
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln2.g, L.ln2.b, h.as<bf16_t>(), M, d, eps, true, 0, 0, dense3_wants_dup(L.fc1, Mi, true)); }))) return rc;
-      if ((rc = dense3_gelu(h.as<bf16_t>(), L.fc1, Mi, &L.fc2))) return rc;
-      if ((rc = dense3(ffn.as<bf16_t>(), L.fc2, X, Mi, true))) return rc;
+      if ((rc = ffn_strict(L.ffn, Mi, M))) return rc;
     }
     return PG_OK;
   }
-  if ((rc = x.ensure((size_t)Mp * d * 4, stream))) return rc;
-  if ((rc = h.ensure((size_t)Mp * d * 2, stream))) return rc;
-  if ((rc = qkv.ensure((size_t)Mp * 3 * d * 2, stream))) return rc;
-  if ((rc = ctx.ensure((size_t)Mp * d * 2, stream))) return rc;
-  if ((rc = ffn.ensure((size_t)Mp * f * 2, stream))) return rc;
-  float* X = x.as<float>();
   bf16_t* Hh = h.as<bf16_t>();
   bf16_t* QKV = qkv.as<bf16_t>();
   bf16_t* CTX = ctx.as<bf16_t>();
   bf16_t* FFN = ffn.as<bf16_t>();
-  const float eps = cfg.layer_norm_eps;
   // <= 256 rows: 64-row tiles, <= 48 rows the weight-streaming GEMM (buffers stay 256-padded) -- the latter not for a tiny shard
   // of a big job (sel_gemm_rows)
   const int Mi = sel_gemm_rows(M, Mp);
@@ -549,19 +598,18 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
     rc = timed(PC_GEMM, [&] { return OPS(launch_chain_trunk, stream, ca, Mi, d); });
     if (rc == kChainTrunkUnfit) {              // the grid cannot be co-resident on this device: per-layer launches, for good
       chain_disabled = true;
-      goto per_layer;
-    }
-    if (rc) return rc;
-    {   // test hook: PGIBBS_CHAIN_TRUNK_FAULT=n makes the n-th persistent launch of the process report a barrier timeout
+    } else if (rc) {
+      return rc;
+    } else {
+      // test hook: PGIBBS_CHAIN_TRUNK_FAULT=n makes the n-th persistent launch of the process report a barrier timeout
       static const int fault_at = [] { const char* e = getenv("PGIBBS_CHAIN_TRUNK_FAULT"); return e ? atoi(e) : 0; }();
       static int launches = 0;
       if (fault_at > 0 && ++launches == fault_at) *chain_err = 1;
+      if (!sel_idx) return PG_OK;
+      l_first = cfg.n_layers - 1;
+      attn_done = true;
     }
-    if (!sel_idx) return PG_OK;
-    l_first = cfg.n_layers - 1;
-    attn_done = true;
   }
-per_layer:
   for (int l = l_first; l < cfg.n_layers; ++l) {
     const EsmLayer& L = esm_layers[l];
     // Hh holds LN1(x): written by the previous layer's fc2 launch (or the LayerNorm kernel) -- see resid_gemm_ln
@@ -575,42 +623,17 @@ per_layer:
     if (!attn_done && (rc = rope(QKV, M, T))) return rc;                       // ESM-2 only: q and k rotated by their positions
     if (!attn_done)
       if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16); }))) return rc;
-    if (sel_idx && l == cfg.n_layers - 1) {
-      // last layer: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
-      const int64_t Np = round_up64(n_sel, kRowPad);
-      if ((rc = x_sel.ensure((size_t)Np * d * 4, stream)) || (rc = ctx_sel.ensure((size_t)Np * d * 2, stream)) ||
-          (rc = h_sel.ensure((size_t)Np * d * 2, stream)) || (rc = ffn_sel.ensure((size_t)Np * f * 2, stream))) return rc;
-      float* XS = x_sel.as<float>();
-      const int Ni = sel_gemm_rows(n_sel, Np);
-      rc = timed(PC_HEAD, [&] {
-        int r2 = launch_gather_rows(stream, X, XS, sel_idx, nullptr, P, T, n_sel, d * 4, d_iter_);
-        if (r2) return r2;
-        return launch_gather_rows(stream, CTX, ctx_sel.as<bf16_t>(), sel_idx, nullptr, P, T, n_sel, d * 2, d_iter_);
-      });
-      if (rc) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ctx_sel.as<bf16_t>(), L.out.w, L.out.b, XS, Ni, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
-      if (ln_in_gemm && gemm_ln_skinny_ok(Ni, f, d)) {
-        if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, XS, d, L.ln2.g, L.ln2.b, eps, L.fc1.w, L.fc1.b, ffn_sel.as<bf16_t>(), Ni, f, d, d, f, EPI_BF16_GELU); }))) return rc;
-      } else {
-        if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, XS, L.ln2.g, L.ln2.b, h_sel.as<bf16_t>(), n_sel, d, eps); }))) return rc;
-        if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, h_sel.as<bf16_t>(), L.fc1.w, L.fc1.b, ffn_sel.as<bf16_t>(), Ni, f, d, d, d, f, EPI_BF16_GELU); }))) return rc;
-      }
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ffn_sel.as<bf16_t>(), L.fc2.w, L.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, f, batch_rows), splitk.bytes); }))) return rc;
-      break;
-    }
-    if (ln_in_gemm) {
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, CTX, L.out.w, L.out.b, X, Mi, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, X, d, L.ln2.g, L.ln2.b, eps, L.fc1.w, L.fc1.b, FFN, Mi, f, d, d, f, EPI_BF16_GELU); }))) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
+    const bool last = l == cfg.n_layers - 1;
+    // last layer: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
+    if (sel_idx && last) return pruned_tail(L.out, L.ffn, sel_idx, nullptr, P, T, n_sel, d_iter_, sel_gemm_rows(n_sel, round_up64(n_sel, kRowPad)), ln_in_gemm);
+    if (!ln_in_gemm) {
+      if ((rc = ffn_block(L.out, L.ffn, last ? nullptr : &esm_layers[l + 1].ln1, Mi, M))) return rc;
       continue;
     }
-    if ((rc = resid_gemm_ln(CTX, L.out, X, Mi, M, d, L.ln2, Hh, nullptr, 0, PC_GEMM_OUT))) return rc;   // x += out_proj(ctx); h = LN2(x)
-    if ((rc = timed(PC_GEMM_FC1, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.fc1.w, L.fc1.b, FFN, Mi, f, d, d, d, f, EPI_BF16_GELU, nullptr, 0, (int)M); }))) return rc;
-    if (l + 1 < cfg.n_layers) {                                                                    // x += fc2(ffn); h = LN1 of the next layer
-      if ((rc = resid_gemm_ln(FFN, L.fc2, X, Mi, M, f, esm_layers[l + 1].ln1, Hh, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, PC_GEMM_FC2))) return rc;
-    } else {
-      if ((rc = timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
-    }
+    const FfnW& F = L.ffn;
+    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, CTX, L.out.w, L.out.b, X, Mi, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
+    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, X, d, F.ln.g, F.ln.b, eps, F.fc1.w, F.fc1.b, FFN, Mi, f, d, d, f, EPI_BF16_GELU); }))) return rc;
+    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FFN, F.fc2.w, F.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
   }
   return PG_OK;
 }
@@ -672,6 +695,18 @@ int Engine::head(const int32_t* d_idx_, const int32_t* d_row_map, int P, int wid
   });
 }
 
+int Engine::masked_logits(int32_t* d_tok, int B, int R, int C, const int32_t* idx, const int32_t* mask_map, const int32_t* sel_map,
+                          int64_t n_rows, int P, bool mask, int mask_idx, float* lg, const int32_t* dit) {
+  const int64_t n_draws = n_rows * P;
+  int rc;
+  if (mask && P > 0)
+    if ((rc = timed(PC_SAMPLE, [&] { return launch_mask_scatter(stream, d_tok, C, idx, mask_map, n_rows, P, mask_idx, dit); }))) return rc;
+  const bool pruned = prune_last(n_draws, (int64_t)B * R * C);
+  if ((rc = trunk(d_tok, B, R, C, pruned ? idx : nullptr, sel_map, P, n_draws, dit))) return rc;
+  if (P == 0) return PG_OK;
+  return pruned ? head(nullptr, nullptr, 1, 1, n_draws, lg, x_sel.as<float>()) : head(idx, sel_map, P, C, n_draws, lg);
+}
+
 int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_, int n_iters, int P,
                              const pg_sample_params* sp, float* d_samp_logits_, int32_t* d_samp_tok_) {
   if (!esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
@@ -683,20 +718,15 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
   const int64_t n_draws = (int64_t)B * P;
   int rc;
   if (!d_samp_logits_ && (rc = logits.ensure((size_t)(n_draws > 0 ? n_draws : 1) * V * 4, stream))) return rc;
-  static const int prune = [] { const char* e = getenv("PGIBBS_PRUNE_LAST"); return e ? atoi(e) : 1; }();
   static const int use_graph = [] { const char* e = getenv("PGIBBS_GRAPH"); return e ? atoi(e) : 1; }();
-  const bool pruned = prune && !strict() && P > 0 && n_draws * 2 < (int64_t)B * T;
+  const bool pruned = prune_last(n_draws, (int64_t)B * T);
 
   // one Gibbs iteration; with dit != nullptr every iteration-dependent quantity is derived on the device from *dit
   auto iteration = [&](int it, const int32_t* dit) -> int {
     const int32_t* idx_it = dit ? d_idx_ : d_idx_ + (size_t)it * n_draws;
-    int r;
-    if (sp->mask && P > 0)
-      if ((r = timed(PC_SAMPLE, [&] { return launch_mask_scatter(stream, d_tok, T, idx_it, nullptr, n_sel_rows, P, sp->mask_idx, dit); }))) return r;
-    if ((r = pruned ? esm_trunk(d_tok, B, T, idx_it, P, n_draws, dit) : esm_trunk(d_tok, B, T))) return r;
-    if (P == 0) return PG_OK;
     float* lg = d_samp_logits_ ? d_samp_logits_ + (size_t)it * n_draws * V : logits.as<float>();
-    if ((r = pruned ? head(nullptr, nullptr, 1, 1, n_draws, lg, x_sel.as<float>()) : head(idx_it, nullptr, P, T, n_draws, lg))) return r;
+    int r = masked_logits(d_tok, B, 1, T, idx_it, nullptr, nullptr, n_sel_rows, P, sp->mask, sp->mask_idx, lg, dit);
+    if (r || P == 0) return r;
     int32_t* st = d_samp_tok_ ? d_samp_tok_ + (size_t)it * n_draws : nullptr;
     return timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, T, lg, V, 1, idx_it, nullptr, n_sel_rows, P, sp, dit ? 0 : it, st, dit, range_err); });
   };
@@ -758,22 +788,16 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
 // ------------------------------------------------------------------------------------------------
 int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx, const int32_t* sel_row_map, int P,
                       int64_t n_sel) {
-  const int d = cfg.d_model, f = cfg.d_ffn, H = cfg.n_heads;
+  const int d = cfg.d_model, H = cfg.n_heads;
   const int64_t M = (int64_t)B * R * C;
   const int64_t Mp = round_up64(M, kRowPad);
-  if (Mp > 0x7fffffff / 4) return fail(PG_ERR_INVALID, "too many tokens in one call");
-  batch_rows = job_batch(B) * R * C;
   int rc;
-  if ((rc = x.ensure((size_t)Mp * d * 4, stream))) return rc;
-  if ((rc = h.ensure((size_t)Mp * d * 2, stream))) return rc;
-  if ((rc = qkv.ensure((size_t)Mp * 3 * d * 2, stream))) return rc;
-  if ((rc = ctx.ensure((size_t)Mp * d * 2, stream))) return rc;
-  if ((rc = ffn.ensure((size_t)Mp * f * 2, stream))) return rc;
+  if ((rc = size_activations(Mp))) return rc;
+  batch_rows = batch_rows_for(B, (int64_t)R * C);
   float* X = x.as<float>();
   bf16_t* Hh = h.as<bf16_t>();
   bf16_t* QKV = qkv.as<bf16_t>();
   bf16_t* CTX = ctx.as<bf16_t>();
-  bf16_t* FFN = ffn.as<bf16_t>();
   const float eps = cfg.layer_norm_eps;
   const int Mi = (int)Mp;
   const float row_scale = 0.125f / sqrtf((float)R);      // dh^-0.5 / sqrt(R): depends on R, applied to the scores
@@ -786,34 +810,25 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
     return fail(PG_ERR_UNSUPPORTED, "fp16 precision mode: batches with <pad> (ragged MSA lists) take the scores-through-scratch row "
                                     "attention, which exists for bf16 operands only -- use precision bf16 or fp32");
   if (strict()) {
-    if ((rc = h.ensure((size_t)Mp * 3 * d * 2, stream)) || (rc = ctx.ensure((size_t)Mp * 3 * d * 2, stream))) return rc;   // [lo | hi | hi] rows
-    if ((rc = qkv.ensure((size_t)Mp * 3 * d * 4, stream))) return rc;
-    if ((rc = ffn.ensure((size_t)Mp * 3 * f * 2, stream))) return rc;
     if ((rc = scores.ensure((size_t)B * H * C * msa_row_scores_ld(C) * 4, stream))) return rc;
-    float* Xs = x.as<float>();
     float* QKVf = qkv.as<float>();
-    bf16_t *H3 = h.as<bf16_t>(), *C3 = ctx.as<bf16_t>();
-    const float eps2 = cfg.layer_norm_eps;
-    const int Mi2 = (int)Mp;
     rc = timed(PC_EMBED, [&] {
-      return OPS(launch_embed_ln, stream, d_tok, embed, pos, msa_pos, ln_before.g, ln_before.b, Xs, M, C, d, cfg.pad_idx,
-                             cfg.mask_idx, 0, R, eps2);
+      return OPS(launch_embed_ln, stream, d_tok, embed, pos, msa_pos, ln_before.g, ln_before.b, X, M, C, d, cfg.pad_idx,
+                             cfg.mask_idx, 0, R, eps);
     });
     if (rc) return rc;
     const SeqLayout colS = {C, R * C, 1, C};
     for (int l = 0; l < cfg.n_layers; ++l) {
       const MsaLayer& L = msa_layers[l];
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, Xs, L.ln_row.g, L.ln_row.b, H3, M, d, eps2, true, 0, 0, dense3_wants_dup(L.row_qkv, Mi2)); }))) return rc;
-      if ((rc = dense3(H3, L.row_qkv, QKVf, Mi2, false))) return rc;
-      if ((rc = timed(PC_ATTN, [&] { return launch_msa_row_attention_f32(stream, QKVf, scores.as<float>(), C3, dense3_wants_dup(L.row_out, Mi2) ? d : -d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, row_scale, pad_tok, cfg.pad_idx); }))) return rc;
-      if ((rc = dense3(C3, L.row_out, Xs, Mi2, true))) return rc;
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, Xs, L.ln_col.g, L.ln_col.b, H3, M, d, eps2, true, 0, 0, dense3_wants_dup(L.col_qkv, Mi2)); }))) return rc;
-      if ((rc = dense3(H3, L.col_qkv, QKVf, Mi2, false))) return rc;
-      if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, C3, dense3_wants_dup(L.col_out, Mi2) ? d : -d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, colS, pad_tok, cfg.pad_idx); }))) return rc;
-      if ((rc = dense3(C3, L.col_out, Xs, Mi2, true))) return rc;
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, Xs, L.ln_ffn.g, L.ln_ffn.b, H3, M, d, eps2, true, 0, 0, dense3_wants_dup(L.fc1, Mi2, true)); }))) return rc;
-      if ((rc = dense3_gelu(H3, L.fc1, Mi2, &L.fc2))) return rc;
-      if ((rc = dense3(ffn.as<bf16_t>(), L.fc2, Xs, Mi2, true))) return rc;
+      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln_row.g, L.ln_row.b, Hh, M, d, eps, true, 0, 0, dense3_wants_dup(L.row_qkv, Mi)); }))) return rc;
+      if ((rc = dense3(Hh, L.row_qkv, QKVf, Mi, false))) return rc;
+      if ((rc = timed(PC_ATTN, [&] { return launch_msa_row_attention_f32(stream, QKVf, scores.as<float>(), CTX, dense3_wants_dup(L.row_out, Mi) ? d : -d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, row_scale, pad_tok, cfg.pad_idx); }))) return rc;
+      if ((rc = dense3(CTX, L.row_out, X, Mi, true))) return rc;
+      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln_col.g, L.ln_col.b, Hh, M, d, eps, true, 0, 0, dense3_wants_dup(L.col_qkv, Mi)); }))) return rc;
+      if ((rc = dense3(Hh, L.col_qkv, QKVf, Mi, false))) return rc;
+      if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, CTX, dense3_wants_dup(L.col_out, Mi) ? d : -d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, colS, pad_tok, cfg.pad_idx); }))) return rc;
+      if ((rc = dense3(CTX, L.col_out, X, Mi, true))) return rc;
+      if ((rc = ffn_strict(L.ffn, Mi, M))) return rc;
     }
     return PG_OK;
   }
@@ -867,33 +882,11 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
       if ((rc = timed(PC_GEMM_QKV, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.col_qkv.w, L.col_qkv.b, QKV, Mi, 3 * d, d, d, d, 3 * d, EPI_BF16); }))) return rc;
       if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_seq_bf16, stream, QKV, CTX, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, pad_tok, cfg.pad_idx, nullptr); }))) return rc;
     }
-    if (sel_idx && l == cfg.n_layers - 1) {
-      // last layer: nothing but the selected rows is read again -> finish column out-projection and FFN on n_sel rows
-      const int64_t Np = round_up64(n_sel, kRowPad);
-      if ((rc = x_sel.ensure((size_t)Np * d * 4, stream)) || (rc = ctx_sel.ensure((size_t)Np * d * 2, stream)) ||
-          (rc = h_sel.ensure((size_t)Np * d * 2, stream)) || (rc = ffn_sel.ensure((size_t)Np * f * 2, stream))) return rc;
-      float* XS = x_sel.as<float>();
-      const int Ni = (int)Np;
-      rc = timed(PC_HEAD, [&] {
-        int r2 = launch_gather_rows(stream, X, XS, sel_idx, sel_row_map, P, C, n_sel, d * 4);
-        if (r2) return r2;
-        return launch_gather_rows(stream, CTX, ctx_sel.as<bf16_t>(), sel_idx, sel_row_map, P, C, n_sel, d * 2);
-      });
-      if (rc) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ctx_sel.as<bf16_t>(), L.col_out.w, L.col_out.b, XS, Ni, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, XS, L.ln_ffn.g, L.ln_ffn.b, h_sel.as<bf16_t>(), n_sel, d, eps); }))) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, h_sel.as<bf16_t>(), L.fc1.w, L.fc1.b, ffn_sel.as<bf16_t>(), Ni, f, d, d, d, f, EPI_BF16_GELU); }))) return rc;
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ffn_sel.as<bf16_t>(), L.fc2.w, L.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, f, batch_rows), splitk.bytes); }))) return rc;
-      break;
-    }
-    if ((rc = resid_gemm_ln(CTX, L.col_out, X, Mi, M, d, L.ln_ffn, Hh, nullptr, 0, PC_GEMM_OUT))) return rc;                 // x += col_out(ctx); h = LN_ffn(x)
-    // feed forward
-    if ((rc = timed(PC_GEMM_FC1, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.fc1.w, L.fc1.b, FFN, Mi, f, d, d, d, f, EPI_BF16_GELU, nullptr, 0, (int)M); }))) return rc;
-    if (l + 1 < cfg.n_layers) {                                                                      // x += fc2(ffn); h = LN_row of the next layer
-      if ((rc = resid_gemm_ln(FFN, L.fc2, X, Mi, M, f, msa_layers[l + 1].ln_row, Hh, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, PC_GEMM_FC2))) return rc;
-    } else {
-      if ((rc = timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, L.fc2.w, L.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
-    }
+    const bool last = l == cfg.n_layers - 1;
+    // last layer: nothing but the selected rows is read again -> finish column out-projection and FFN on n_sel rows
+    if (sel_idx && last) return pruned_tail(L.col_out, L.ffn, sel_idx, sel_row_map, P, C, n_sel, nullptr, (int)round_up64(n_sel, kRowPad), false);
+    // x += col_out(ctx); h = LN_ffn(x); feed forward; h = LN_row of the next layer
+    if ((rc = ffn_block(L.col_out, L.ffn, last ? nullptr : &msa_layers[l + 1].ln_row, Mi, M))) return rc;
   }
   return PG_OK;
 }
@@ -918,14 +911,9 @@ int Engine::msa_gibbs_device(int32_t* d_tok, int B, int R, int C, const int32_t*
   if (!d_samp_logits_ && (rc = logits.ensure((size_t)(n_draws > 0 ? n_draws : 1) * V * 4, stream))) return rc;
   for (int it = 0; it < n_iters; ++it) {
     const int32_t* idx_it = d_idx_ + (size_t)it * n_draws;
-    if (sp->mask && P > 0)
-      if ((rc = timed(PC_SAMPLE, [&] { return launch_mask_scatter(stream, d_tok, C, idx_it, nullptr, n_sel_rows, P, sp->mask_idx); }))) return rc;
-    static const int prune = [] { const char* e = getenv("PGIBBS_PRUNE_LAST"); return e ? atoi(e) : 1; }();
-    const bool pruned = prune && !strict() && P > 0 && n_draws * 2 < n_sel_rows * C;
-    if ((rc = pruned ? msa_trunk(d_tok, B, R, C, idx_it, nullptr, P, n_draws) : msa_trunk(d_tok, B, R, C))) return rc;
-    if (P == 0) continue;
     float* lg = d_samp_logits_ ? d_samp_logits_ + (size_t)it * n_draws * V : logits.as<float>();
-    if ((rc = pruned ? head(nullptr, nullptr, 1, 1, n_draws, lg, x_sel.as<float>()) : head(idx_it, nullptr, P, C, n_draws, lg))) return rc;
+    if ((rc = masked_logits(d_tok, B, R, C, idx_it, nullptr, nullptr, n_sel_rows, P, sp->mask, sp->mask_idx, lg))) return rc;
+    if (P == 0) continue;
     int32_t* st = d_samp_tok_ ? d_samp_tok_ + (size_t)it * n_draws : nullptr;
     if ((rc = timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, C, lg, V, 1, idx_it, nullptr, n_sel_rows, P, sp, it, st, nullptr, range_err); }))) return rc;
   }
@@ -990,14 +978,10 @@ int Engine::msa_single_device(int32_t* d_tok, int B, int R, int C, int mask_row,
   order_items = 1;
   for (int s = 0; s < n_steps; ++s) {
     const int32_t* idx_s = d_step_idx + (size_t)s * n_draws;
-    if (P_max > 0)   // generate_single always masks (esm_msa_sampler.py:133), row -1 regardless of the target row
-      if ((rc = timed(PC_SAMPLE, [&] { return launch_mask_scatter(stream, d_tok, C, idx_s, d_mask_map, B, P_max, sp->mask_idx); }))) return rc;
-    static const int prune = [] { const char* e = getenv("PGIBBS_PRUNE_LAST"); return e ? atoi(e) : 1; }();
-    const bool pruned = prune && !strict() && P_max > 0 && (int64_t)P_max * 2 < (int64_t)R * C;
-    if ((rc = pruned ? msa_trunk(d_tok, B, R, C, idx_s, d_tgt_map, P_max, n_draws) : msa_trunk(d_tok, B, R, C))) return rc;
-    if (P_max == 0) continue;
     float* lg = d_samp_logits_ ? d_samp_logits_ + (size_t)s * n_draws * V : logits.as<float>();
-    if ((rc = pruned ? head(nullptr, nullptr, 1, 1, n_draws, lg, x_sel.as<float>()) : head(idx_s, d_tgt_map, P_max, C, n_draws, lg))) return rc;
+    // generate_single always masks (esm_msa_sampler.py:133), row -1 regardless of the target row
+    if ((rc = masked_logits(d_tok, B, R, C, idx_s, d_mask_map, d_tgt_map, B, P_max, true, sp->mask_idx, lg))) return rc;
+    if (P_max == 0) continue;
     int32_t* st = d_samp_tok_ ? d_samp_tok_ + (size_t)s * n_draws : nullptr;
     for (int b = 0; b < B; ++b) {           // one draw launch per template: its own Philox key, Philox row id = row_id_base
       pg_sample_params p = sp[b];
