@@ -311,6 +311,10 @@ int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const
  * of 64 above 256); variant 1 =
  * lockstep kernel, 2 = ping-pong kernel; epi: 0 bf16 out, 1 bf16+gelu, 2 fp32 residual, 3 fp32, 4 fp32+gelu */
 int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int iters, double* avg_ms);
+/* which kernel the GEMM dispatch picks for a shape on a device of n_cu compute units, as the text pg_prof_get_kernels reports for
+ * that launch ("pp192x256 250t + tail64 40t", "skinny8w 80t x4k"; empty for an ablation variant; "error: ..." for a refused shape).
+ * have_ws: split-K scratch is on offer (residual GEMMs of an engine); m_live: rows that hold tokens, 0 = all.  Touches no device. */
+int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int m_live, int n_cu, char* buf, int buf_bytes);
 /* round 6: gemm_rowln.hip (out-projection of d_model = 768 with the next LayerNorm in its epilogue) against the two launches it
  * replaces: ms[0] fused, ms[1] its main loop alone, ms[2] four half-steps + epilogue, ms[3] residual GEMM (256-column tiles),
  * ms[4] LayerNorm kernel; max_diff 0 = x and h bit-identical between the two paths. */

@@ -305,7 +305,7 @@ int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, in
     // fp32 scratch grows with B: 0.5 GB for 4 templates of 128 x 513, past 2 GB from about B = 9 at C = 576 or B = 32 at C = 300.
     // Templates are independent, so a larger batch is simply run in chunks that fit (same logits and tokens; ADVICE r03:
     // `--template_batch 32`, BASELINE config 5's "32 templates", used to fail with PG_ERR_INVALID).
-    static const size_t limit = [] { const char* ev = getenv("PGIBBS_SPLIT_SCRATCH_MB"); return (size_t)(ev ? atol(ev) : 1024) << 20; }();
+    static const size_t limit = (size_t)env_int("PGIBBS_SPLIT_SCRATCH_MB", 1024) << 20;
     const size_t need1 = msa_row_split_scratch_bytes(1, R, C, e.cfg.n_heads, e.cfg.n_heads);
     const int bc = need1 ? (int)std::max<size_t>(1, std::min<size_t>((size_t)B, limit / need1)) : B;
     if (bc < B) {
@@ -629,6 +629,14 @@ int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
   *avg_ms = ms / iters;
+  return PG_OK;
+}
+
+int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int m_live, int n_cu, char* buf, int buf_bytes) {
+  if (!buf || buf_bytes < 2 || M < 1 || N < 1 || K < 1 || n_cu < 1) return fail(PG_ERR_INVALID, "pg_dbg_gemm_plan: bad argument");
+  std::string text;
+  gemm_plan_text(M, N, K, epi, variant, have_ws != 0, m_live, n_cu, &text);
+  snprintf(buf, (size_t)buf_bytes, "%s", text.c_str());
   return PG_OK;
 }
 

@@ -478,8 +478,8 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
   // Round 6: split the pairs of a partial last round (see attention_kernel).  Whole-sequence kernels for chains (row_step 1) of at
   // least four query blocks, without <pad> mask / bias key (the Gibbs path).  Resident workgroups: two per CU up to 20 key blocks
   // (2 x 80 KB of LDS), one beyond.  PGIBBS_ATTN_SPLIT=0 switches it off.
-  static const int split_on = [] { const char* e = getenv("PGIBBS_ATTN_SPLIT"); return e ? atoi(e) : 1; }();
-  static const int n_cu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
+  static const int split_on = env_int("PGIBBS_ATTN_SPLIT", 1);
+  const int n_cu = device_cu_count();
   int split_from = 0, split = 1;
   if (split_on && !key_tok && !bias_kv && sl.row_step == 1 && T >= 64 && T <= 576) {
     const int kb = (((T + 15) / 16) + 1) & ~1;            // the rung of the ladder below: key blocks, even
@@ -505,7 +505,7 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
     else hipLaunchKernelGGL((attention_kernel<KB, false>), grid, block, 0, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok, pad_idx, bias_kv); \
   }
   const int Tk = T + (bias_kv ? 1 : 0);          // keys: the T tokens + ESM-1's bias_k / bias_v
-  static const int fine_ladder = [] { const char* e = getenv("PGIBBS_ATTN_LADDER"); return e ? atoi(e) : 1; }();   // 0: the coarse ladder only
+  static const int fine_ladder = env_int("PGIBBS_ATTN_LADDER", 1);   // 0: the coarse ladder only
   if (T <= 0) return fail(1, "attention: empty sequence");
   // extra rungs for the forms without ESM-1's bias key (the Gibbs path, and ragged batches): a chain of 200 residues has 13 key blocks, not 18 --
   // the blocks beyond T are zero-filled and masked, i.e. pure waste (and exact zeros in every sum: the bits do not depend on the rung)

@@ -622,8 +622,8 @@ int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split
   const int mode = attn_f32_mode();
   // 16-query blocks per wave of the split kernel (its workgroup = 64 * nqb queries, all of them against each staged K / V tile):
   // the smallest of 1, 2, 3, 5 that covers the sequence with one workgroup, else 5 (PGIBBS_ATTN_F32_NQB overrides: A/B runs)
-  static const int nqb_env = [] { const char* e = getenv("PGIBBS_ATTN_F32_NQB"); return e ? atoi(e) : 0; }();
-  static const int kb_env = [] { const char* e = getenv("PGIBBS_ATTN_F32_KB"); return e ? atoi(e) : 0; }();   // experiment: key-tile height
+  static const int nqb_env = env_int("PGIBBS_ATTN_F32_NQB", 0);
+  static const int kb_env = env_int("PGIBBS_ATTN_F32_KB", 0);   // experiment: key-tile height
   const int blocks = (T + 15) / 16;
   int nqb = blocks <= 4 ? 1 : (blocks <= 8 ? 2 : (blocks <= 12 ? 3 : 5));
   if (nqb_env == 1 || nqb_env == 2 || nqb_env == 3 || nqb_env == 5) nqb = nqb_env;

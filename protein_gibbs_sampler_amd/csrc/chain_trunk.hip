@@ -623,7 +623,7 @@ __global__ __launch_bounds__(512) void chain_trunk_kernel(PgChainTrunkArgs a) {
 
 // may the persistent trunk take this forward?  M = padded token rows (16 or 32)
 bool chain_trunk_ok(int M, int d_model, int d_ffn, int n_heads) {
-  static const int on = [] { const char* e = getenv("PGIBBS_CHAIN_TRUNK"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("PGIBBS_CHAIN_TRUNK", 1);
   // d_model 1024 or 1280: the widths at which the multi-launch path splits fc2's K = 4 d_model four ways, like this kernel
   return on && (M == 16 || M == 32) && (d_model == 1024 || d_model == 1280) && d_ffn == 4 * d_model && n_heads * 64 == d_model;
 }
@@ -652,7 +652,7 @@ static int chain_trunk_grid(int device) {
 }
 
 int launch_chain_trunk(hipStream_t s, const PgChainTrunkArgs& a, int M, int d_model) {
-  static const int g_env = [] { const char* e = getenv("PGIBBS_CHAIN_TRUNK_GRID"); return e ? atoi(e) : 0; }();
+  static const int g_env = env_int("PGIBBS_CHAIN_TRUNK_GRID", 0);
   if (a.n_layers <= 0) return 0;
   if (a.B * a.T > M || a.T > 32 || a.T < 1) return fail(1, "chain_trunk: shape");
   int dev = 0;

@@ -417,11 +417,8 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
   }
   {
     // one resident round of workgroups walking their rows when the plain grid would be 1 ... 4 rounds (layernorm_bf16_stride_kernel)
-    static const int on = [] { const char* e = getenv("PGIBBS_LN_STRIDE"); return e ? atoi(e) : 1; }();
-    static const int n_cu = [] {
-      hipDeviceProp_t p; int dv = 0; (void)hipGetDevice(&dv);
-      return hipGetDeviceProperties(&p, dv) == hipSuccess ? p.multiProcessorCount : 256;
-    }();
+    static const int on = env_int("PGIBBS_LN_STRIDE", 1);
+    const int n_cu = device_cu_count();
     const unsigned g1 = rows_grid(M);
     if (on && (d == 1280 || d == 768) && g1 > (unsigned)n_cu * 8 && g1 <= (unsigned)n_cu * 32) {
       // the grid = what is resident at once (occupancy of this very kernel x CUs, asked once per width)
@@ -495,7 +492,7 @@ int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const floa
   // identical arithmetic per logit (same per-lane partial sums, same wave reduction): bit-equal results.  Up to 1024 rows (round 5;
   // it was 128): a 32-chain shard's 800 sampled rows took 81 us on the row-per-wave kernel -- 200 workgroups, each wave walking the
   // decoder rows in nine dependent trips -- PGIBBS_LM_TAIL_SMALL=n moves the switch
-  static const int small_max = [] { const char* e = getenv("PGIBBS_LM_TAIL_SMALL"); return e ? atoi(e) : 1024; }();
+  static const int small_max = env_int("PGIBBS_LM_TAIL_SMALL", 1024);
   if (n <= small_max) {
     // no shared memory; every wave holds the row and four decoder rows' chunks (NCH + 4 float4 in flight at most: far below the
     // 128 VGPRs a 1024-thread workgroup may use per lane)

@@ -411,7 +411,7 @@ int Engine::sel_gemm_rows(int64_t n_sel, int64_t Np) const {
 // plain kernels over K' = 3K all three blocks.  A producer (LayerNorm, fc1's epilogue) skips the duplicate block -- a fifth of a
 // LayerNorm's traffic, a third of fc1's stores -- exactly when its consumer is the fused kernel.
 bool Engine::dense3_wants_dup(const DenseW& W, int Mp, bool gelu) const {
-  static const int nodup = [] { const char* e = getenv("PGIBBS_SPLIT3_NODUP"); return e ? atoi(e) : 1; }();
+  static const int nodup = env_int("PGIBBS_SPLIT3_NODUP", 1);
   if (!nodup) return true;
   if (gelu && W.N % 256 == 0 && Mp % 256 == 0) return false;          // dense3_gelu's fused form: always the 16-wave kernel
   return !gemm_split3_fused(Mp, W.N, W.K, EPI_F32);
@@ -502,7 +502,7 @@ int Engine::ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int 
 }
 
 bool Engine::prune_last(int64_t n_draws, int64_t token_rows) const {
-  static const int prune = [] { const char* e = getenv("PGIBBS_PRUNE_LAST"); return e ? atoi(e) : 1; }();
+  static const int prune = env_int("PGIBBS_PRUNE_LAST", 1);
   return prune && !strict() && n_draws > 0 && 2 * n_draws < token_rows;
 }
 
@@ -602,7 +602,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
       return rc;
     } else {
       // test hook: PGIBBS_CHAIN_TRUNK_FAULT=n makes the n-th persistent launch of the process report a barrier timeout
-      static const int fault_at = [] { const char* e = getenv("PGIBBS_CHAIN_TRUNK_FAULT"); return e ? atoi(e) : 0; }();
+      static const int fault_at = env_int("PGIBBS_CHAIN_TRUNK_FAULT", 0);
       static int launches = 0;
       if (fault_at > 0 && ++launches == fault_at) *chain_err = 1;
       if (!sel_idx) return PG_OK;
@@ -645,8 +645,9 @@ int Engine::resid_gemm_ln(const bf16_t* a, const DenseW& W, float* x, int M_rows
                           float* ws, size_t ws_bytes, int prof_class, int colmajor_R, int colmajor_C) {
   const int d = W.N, K = W.K;
   // d_model = 768, K <= 1024 (ESM-MSA-1b's attention out-projections) on big batches: one launch whose tiles span whole rows and
-  // normalise them in the epilogue (gemm_rowln.hip; same bits as the two launches below, so the choice is free)
-  static const int64_t rowln_min = [] { const char* e = getenv("PGIBBS_ROWLN_MIN_ROWS"); return e ? atoll(e) : 16384LL; }();
+  // normalise them in the epilogue (gemm_rowln.hip; same bits as the two launches below).  Opt-in through PGIBBS_ROWLN=1
+  // (gemm_rowln_ok): measured slower, 1.34-1.37 ms per launch against 1.26-1.28 ms for the two launches it replaces
+  static const int64_t rowln_min = env_int("PGIBBS_ROWLN_MIN_ROWS", 16384);
   if (!strict() && M_real >= rowln_min && M_real <= M_rows && OPS(gemm_rowln_ok, M_rows, d, K))
     return timed(prof_class, [&] { return OPS(launch_gemm_rowln, stream, a, W.w, W.b, x, ln.g, ln.b, h, (int)M_real, M_rows, K, lda, K, cfg.layer_norm_eps, colmajor_R, colmajor_C); });
   int rc = timed(prof_class, [&] { return OPS(launch_gemm_bf16, stream, a, W.w, W.b, x, M_rows, d, K, lda, K, d, EPI_F32_RESID, ws, ws_bytes, (int)M_real); });
@@ -718,7 +719,7 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
   const int64_t n_draws = (int64_t)B * P;
   int rc;
   if (!d_samp_logits_ && (rc = logits.ensure((size_t)(n_draws > 0 ? n_draws : 1) * V * 4, stream))) return rc;
-  static const int use_graph = [] { const char* e = getenv("PGIBBS_GRAPH"); return e ? atoi(e) : 1; }();
+  static const int use_graph = env_int("PGIBBS_GRAPH", 1);
   const bool pruned = prune_last(n_draws, (int64_t)B * T);
 
   // one Gibbs iteration; with dit != nullptr every iteration-dependent quantity is derived on the device from *dit

@@ -9,10 +9,10 @@
 //   * both operands are K-contiguous ([rows][K], PyTorch Linear layout), so W rows feed the MFMA
 //     A operand and activation rows the B operand: D[n][m].  A lane then holds 4 consecutive n
 //     for one token m.
-//   * four kernels, picked by how many tiles they put on the 256 CUs (launch_gemm_bf16_variant):
+//   * four kernels, picked by how many tiles they put on the 256 CUs (plan_gemm, at the end of this file):
 //       - 256x256x64 ping-pong kernel (gemm_bf16_pp_kernel): 8 waves as two staggered groups, LDS-DMA ring of four
-//         half-K buffers, LDS-staged coalesced epilogues with non-temporal stores; m-panels of a ragged last round of
-//         tiles are peeled into a second, small launch;
+//         half-K buffers, LDS-staged coalesced epilogues with non-temporal stores; the rows of a ragged last round of
+//         tiles run as 64x64 tail tiles in the same grid (gemm_epilogue.h);
 //       - 128x128 and 64x64 lockstep double-buffered tiles (gemm_bf16_kernel) for 64 .. ~4000 token rows;
 //       - weight-streaming kernel (gemm_bf16_skinny_kernel) up to 48 rows;
 //       - deep-K residual GEMMs with few tiles run as parallel K-splits + a fixed-order reduction.
@@ -23,6 +23,7 @@
 //     lane group touches 16 distinct 16-B slots (conflict-free).
 //   * 1-D grid remapped so each XCD (private L2) owns a contiguous range of tiles.
 //   * epilogues fused: +bias, GELU, bf16 pack, fp32 residual read-modify-write.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "gemm_epilogue.h"
@@ -605,7 +606,7 @@ static unsigned* round_sync_words() {
   // OFF by default: measured round 5 (profiles/r05_fc2_round_pacing.txt) -- pacing cuts fc2's fabric reads from 3.67 to 2.2 GB per
   // launch (FETCH_SIZE) and the launch gets 1 % SLOWER (756 -> 763 us; ESM-MSA-1b's fc2 +3 %): the re-fetches are served by the
   // Infinity Cache at no cost in time, while waiting for the slowest CU of a round is not free.  Kept as the ablation switch.
-  static const int on = [] { const char* e = getenv("PGIBBS_GEMM_RSYNC"); return e ? atoi(e) : 0; }();
+  static const int on = env_int("PGIBBS_GEMM_RSYNC", 0);
   int dev = 0;
   if (!on || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   if (!tried[dev]) {
@@ -620,169 +621,76 @@ static unsigned* round_sync_words() {
   return words[dev];
 }
 
+// The dispatch that picks this kernel records it (note_plan).
 static int launch_pp(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K,
                      int ldx, int ldw, int ldo, int epi, int abl = 0, int tail_rows = 0, int tile_rows = 256) {
   const int tiles_m = M / tile_rows, tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
-  static const int tail_last = [] { const char* e = getenv("PGIBBS_GEMM_TAIL_LAST"); return e ? atoi(e) : 0; }();
-  static const int rsync_k = [] { const char* e = getenv("PGIBBS_GEMM_RSYNC_K"); return e ? atoi(e) : 4096; }();
+  static const int rsync_k = env_int("PGIBBS_GEMM_RSYNC_K", 4096);
   const int n_tail_abs = (tail_rows / 64) * (N / 64), tail_m0 = M;
   // round pacing: deep-K residual GEMMs of more than two rounds of 256-row tiles (fc2 of a big batch); the tail tiles then ride
   // BEHIND the big ones (in front they would hold the first round's CUs back, and with them everybody who waits for that round)
   unsigned* rsync = (epi == EPI_F32_RESID && !abl && tile_rows == 256 && K >= rsync_k && n_tiles > 2 * 256 && n_tail_abs % 8 == 0)
                         ? round_sync_words() : nullptr;
-  const int n_tail = (tail_last || rsync) ? -n_tail_abs : n_tail_abs;
+  const int n_tail = (gemm_tail_last() || rsync) ? -n_tail_abs : n_tail_abs;
   dim3 grid(n_tiles + n_tail_abs), block(512);
-  if (!abl) {
-    note_kernel(tile_rows == 192 ? "pp192x256" : "pp256x256", n_tiles);
-    if (n_tail_abs) note_kernel("tail64", n_tail_abs);
-  }
-#define PG_PP_ARGS X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0, rsync
-  if (abl) {   // ablations: EPI_BF16 only
-    if (abl == 1) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 1>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 2) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 2>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 3) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 3>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 13) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 13>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 14) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_F32_RESID, 13>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 18) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 18>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 19) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 19>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 28) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_F32_RESID, 18>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 29) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_F32_RESID, 0>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 17) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 17>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 16) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 16>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 15) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 15>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 12) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 12>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 10) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 10>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 11) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 11>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 8) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 8>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 9) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 9>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 4) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 0, 1>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 5) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 0, 8>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 6) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 0, 2>), grid, block, 0, s, PG_PP_ARGS);
-    if (abl == 7) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_BF16, 0, 16>), grid, block, 0, s, PG_PP_ARGS);
-    PG_HIP(hipGetLastError());
-    return 0;
-  }
-  // m-panels per rasterisation group: 4, but 2 for deep K (fc2: a 256-row X panel of K = 5120 is 2.6 MB, four of them plus
-  // the W panels overflow the XCD's 4 MB L2 even slice-wise; measured 0.760 -> 0.733 ms with the bf16 epilogue)
-  static const int gm_env = [] { const char* e = getenv("PGIBBS_GEMM_GM"); return e ? atoi(e) : 0; }();
-  const int gm = gm_env ? gm_env : (K >= 4096 ? 2 : 4);
-  if (tile_rows == 192) {      // 192 x 256 tiles: residual epilogue only (launch_gemm_big)
+#define PG_PP(E, A, G, XJ) \
+  hipLaunchKernelGGL((gemm_bf16_pp_kernel<E, A, G, XJ>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0, rsync)
+  if (abl) {
+    // the ablation instances (tools/gemm_bench.py, tools/epi_cost.py: variant 20 + id, 40 + id from 60 on): id -> <EPI, ABL, GM>;
+    // the epilogue is the instance's, whatever `epi` says
+    switch (abl) {
+#define PG_PP_ABL(ID, E, A, G) case ID: PG_PP(E, A, G, 8); break;
+      PG_PP_ABL(1, EPI_BF16, 1, 4)
+      PG_PP_ABL(2, EPI_BF16, 2, 4)
+      PG_PP_ABL(3, EPI_BF16, 3, 4)
+      PG_PP_ABL(4, EPI_BF16, 0, 1)
+      PG_PP_ABL(5, EPI_BF16, 0, 8)
+      PG_PP_ABL(6, EPI_BF16, 0, 2)
+      PG_PP_ABL(7, EPI_BF16, 0, 16)
+      PG_PP_ABL(8, EPI_BF16, 8, 4)
+      PG_PP_ABL(9, EPI_BF16, 9, 4)
+      PG_PP_ABL(10, EPI_BF16, 10, 4)
+      PG_PP_ABL(11, EPI_BF16, 11, 4)
+      PG_PP_ABL(12, EPI_BF16, 12, 4)
+      PG_PP_ABL(13, EPI_BF16, 13, 4)
+      PG_PP_ABL(14, EPI_F32_RESID, 13, 4)
+      PG_PP_ABL(15, EPI_BF16, 15, 4)
+      PG_PP_ABL(16, EPI_BF16, 16, 4)
+      PG_PP_ABL(17, EPI_BF16, 17, 4)
+      PG_PP_ABL(18, EPI_BF16, 18, 4)
+      PG_PP_ABL(19, EPI_BF16, 19, 4)
+      PG_PP_ABL(28, EPI_F32_RESID, 18, 4)
+      PG_PP_ABL(29, EPI_F32_RESID, 0, 4)
+#undef PG_PP_ABL
+      default:
+        return fail(1, "gemm: unknown ablation");
+    }
+  } else if (tile_rows == 192) {      // 192 x 256 tiles: residual epilogue only (plan_big)
     if (epi != EPI_F32_RESID || M % 192) return fail(1, "gemm: 192-row tiles are for the residual epilogue");
-    if (gm == 2) hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_F32_RESID, 0, 2, 6>), grid, block, 0, s, PG_PP_ARGS);
-    else hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_F32_RESID, 0, 4, 6>), grid, block, 0, s, PG_PP_ARGS);
-    PG_HIP(hipGetLastError());
-    return 0;
-  }
-#define PG_GEMM_CASE(E)                                                                                                   \
-  case E:                                                                                                                 \
-    if (gm == 1) hipLaunchKernelGGL((gemm_bf16_pp_kernel<E, 0, 1>), grid, block, 0, s, PG_PP_ARGS); \
-    else if (gm == 2) hipLaunchKernelGGL((gemm_bf16_pp_kernel<E, 0, 2>), grid, block, 0, s, PG_PP_ARGS); \
-    else hipLaunchKernelGGL((gemm_bf16_pp_kernel<E>), grid, block, 0, s, PG_PP_ARGS); \
+    if (gemm_gm(GM_PP192, K) == 2) PG_PP(EPI_F32_RESID, 0, 2, 6);
+    else PG_PP(EPI_F32_RESID, 0, 4, 6);
+  } else {
+    const int gm = gemm_gm(GM_PP256, K);
+#define PG_GEMM_CASE(E)                 \
+  case E:                               \
+    if (gm == 1) PG_PP(E, 0, 1, 8);     \
+    else if (gm == 2) PG_PP(E, 0, 2, 8); \
+    else PG_PP(E, 0, 4, 8);             \
     break;
-  switch (epi) {
-    PG_GEMM_CASE(EPI_BF16)
-    PG_GEMM_CASE(EPI_BF16_GELU)
-    PG_GEMM_CASE(EPI_F32_RESID)
-    PG_GEMM_CASE(EPI_F32)
-    PG_GEMM_CASE(EPI_F32_GELU)
-    default:
-      return fail(1, "gemm: bad epilogue for the 8-wave tile kernel");
-  }
+    switch (epi) {
+      PG_GEMM_CASE(EPI_BF16)
+      PG_GEMM_CASE(EPI_BF16_GELU)
+      PG_GEMM_CASE(EPI_F32_RESID)
+      PG_GEMM_CASE(EPI_F32)
+      PG_GEMM_CASE(EPI_F32_GELU)
+      default:
+        return fail(1, "gemm: bad epilogue for the 8-wave tile kernel");
+    }
 #undef PG_GEMM_CASE
-#undef PG_PP_ARGS
+  }
+#undef PG_PP
   PG_HIP(hipGetLastError());
   return 0;
-}
-
-// geometry of a big-batch launch: m-panels of 256 x 256 tiles + rows of 64 x 64 tail tiles (launch_gemm_big)
-struct BigGeom { int m_main, tail_rows, gm; };
-static BigGeom big_geometry(int M, int N, int K) {
-  static const int n_cu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-  static const int tail_on = [] { const char* e = getenv("PGIBBS_GEMM_TAIL"); return e ? atoi(e) : 1; }();
-  static const int tail_max = [] { const char* e = getenv("PGIBBS_GEMM_TAIL_MAX"); return e ? atoi(e) : 4; }();   // tail tiles per CU at most
-  static const int gm_env = [] { const char* e = getenv("PGIBBS_GEMM_GM"); return e ? atoi(e) : 0; }();
-  const int tiles_n = N / 256, tiles_m = M / 256;
-  const long t256 = (long)tiles_m * tiles_n, full = t256 / n_cu, frac = t256 - full * n_cu;
-  BigGeom g{tiles_m, 0, gm_env ? (gm_env <= 2 ? gm_env : 4) : (K >= 4096 ? 2 : 4)};      // the GM the launchers instantiate
-  if (tail_on && frac > 0) {
-    const int mm = (int)(full * n_cu / tiles_n);             // m-panels that fill whole rounds (0: less than one round of big tiles)
-    const long n_tail = (long)(tiles_m - mm) * 4 * (N / 64);
-    if (n_tail <= (long)tail_max * n_cu) { g.m_main = mm; g.tail_rows = (tiles_m - mm) * 256; }
-  }
-  return g;
-}
-void gemm_big_geometry(int M, int N, int K, int* m_main_panels, int* tail_rows) {
-  const BigGeom g = big_geometry(M, N, K);
-  *m_main_panels = g.m_main;
-  *tail_rows = g.tail_rows;
-}
-// The big-batch GEMM: whole rounds of 256 x 256 tiles (one per CU) plus, in the SAME grid, 64 x 64 tail tiles for the rows
-// beyond the last full round when that round would be mostly empty (gemm_epilogue.h).  Kernel per epilogue: the 16-wave kernel
-// for the bf16 outputs (QKV projections: 3.5-4 % faster there; fc1: its one-pass GELU epilogue is 0.03 ms shorter per launch),
-// the 8-wave ping-pong kernel for the fp32 outputs (the 16-wave kernel loses 3-4 % on the residual read-modify-write);
-// PGIBBS_GEMM_BIG=pp / w16 forces one kernel for the plain epilogues.  M, N multiples of 256, K a multiple of 64, K >= 128.
-int launch_gemm_big(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldx,
-                    int ldw, int ldo, int epi, int m_live) {
-  if (M % 256 || N % 256 || K % 64 || K < 128 || M < 256) return fail(1, "gemm_big: shape");
-  static const int big = [] { const char* e = getenv("PGIBBS_GEMM_BIG"); return !e ? -1 : (e[0] == 'w' ? 16 : 0); }();
-  const BigGeom geo = big_geometry(M, N, K);
-  const int m_main = geo.m_main, tail_rows = geo.tail_rows;
-  const bool bf16out = epi == EPI_BF16 || epi == EPI_BF16_GELU;
-  const bool use16 = big == 16 || (big == -1 && bf16out);
-  static const int n_cu_l = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-  // Round 6: the tile-height ladder (gemm_ladder.hip; heights 160 ... 240 in steps of 16 rows).  Built for VERDICT r05's tile-count
-  // argument -- a partial last round of tiles costs a whole one, and N = 1280 (five tiles per row panel) quantises badly for a
-  // 1/8 ... 1/2 shard of config 3 -- and MEASURED (profiles/r06_ladder_bench.txt, r06_shard_proxy_ladder_ab.txt): every height
-  // takes the same time to within 3 % at every shard size (a 32-chain shard's fc2: 165 tiles of 256 rows 128.8 us, 220 of 192
-  // 127.0, 240 of 176 133.6, 190 of 224 128.7), bit-identical results.  These launches run at a fixed aggregate L2 -> LDS feed of
-  // ~8 TB/s whatever the tiling (bytes staged / time: 6.8 ... 8.5 TB/s from the 32-chain shard to the full batch), so idle CUs in a
-  // partial round are not lost throughput and a smaller tile only raises the bytes staged per FLOP.  OFF by default;
-  // PGIBBS_GEMM_LADDER=1 prices the candidates in rounds x height (the model that does not hold), =h forces height h where the
-  // epilogue has it (the A/B switch of tests/test_gpu_kernels.py and tools/ladder_bench.py).
-  static const int ladder = [] { const char* e = getenv("PGIBBS_GEMM_LADDER"); return e ? atoi(e) : 0; }();
-  const int live = m_live > 0 && m_live <= M ? m_live : M;
-  const int tiles_n_l = N / 256;
-  double cost_old;
-  {
-    const long t256 = (long)(M / 256) * tiles_n_l;
-    cost_old = tail_rows ? (double)((long)m_main * tiles_n_l / n_cu_l) + 0.15 : (double)((t256 + n_cu_l - 1) / n_cu_l);
-    static const int t192e = [] { const char* e = getenv("PGIBBS_GEMM_T192"); return e ? atoi(e) : 1; }();
-    if (t192e && epi == EPI_F32_RESID) {
-      const int m192 = M / 192, rest = M - m192 * 192;
-      const double r192 = 0.75 * (double)(((long)m192 * tiles_n_l + n_cu_l - 1) / n_cu_l) + (rest ? 0.2 : 0.0);
-      if (r192 <= 0.9 * cost_old) cost_old = r192;
-    }
-  }
-  if (ladder && (epi == EPI_F32_RESID || epi == EPI_BF16_GELU)) {
-    int best_h = 0;
-    double best = 0.95 * cost_old;
-    for (int h = 240; h >= 160; h -= 16) {
-      if (!gemm_ladder_has(epi, h) || (ladder > 1 && ladder != h)) continue;
-      const long tiles = (long)((live + h - 1) / h) * tiles_n_l;
-      const double c = (double)((tiles + n_cu_l - 1) / n_cu_l) * h / 256.0;
-      if (ladder == h || c < best - 1e-9) { best = c; best_h = h; if (ladder == h) break; }
-    }
-    if (best_h) return launch_gemm_ladder(s, X, W, bias, out, live, M, best_h, N, K, ldx, ldw, ldo, epi);
-  }
-  if (use16) return launch_gemm_w16(s, X, W, bias, out, m_main * 256, N, K, ldx, ldw, ldo, epi, 0, tail_rows);
-  // Residual GEMMs of mid-size batches: 256-row tiles quantise badly (a 32-chain shard's out-projection / fc2: 165 tiles on 256 CUs,
-  // a 64-chain one: 325 = two rounds of which the second is a quarter full).  192 x 256 tiles (same kernel, 6 instead of 8 row
-  // blocks per wave, same k order) cost three quarters of a round each: taken when that is at least 10 % fewer round-equivalents.
-  // The rows beyond the last 192-row tile (0, 64 or 128 of them: M is a multiple of 256) are 64 x 64 tail tiles of the same grid.
-  static const int t192 = [] { const char* e = getenv("PGIBBS_GEMM_T192"); return e ? atoi(e) : 1; }();
-  if (t192 && epi == EPI_F32_RESID) {
-    static const int n_cu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-    const int tiles_n = N / 256;
-    const long t256 = (long)(M / 256) * tiles_n;
-    const double r256 = tail_rows ? (double)((long)m_main * tiles_n / n_cu) + 0.15 : (double)((t256 + n_cu - 1) / n_cu);
-    const int m192 = M / 192, rest = M - m192 * 192;
-    const long t192n = (long)m192 * tiles_n;
-    // leftover rows cost a round of tail tiles in front of the big ones (~0.2 of a round: M = 9728, N = 1280 measured 51.2 us with
-    // 250 tiles of 192 rows + 40 tail tiles against 47.7 us for 190 tiles of 256 rows; tools/gemm_mid_resid_bench.py)
-    const double r192 = 0.75 * (double)((t192n + n_cu - 1) / n_cu) + (rest ? 0.2 : 0.0);
-    if (t192 == 2 || r192 <= 0.9 * r256) return launch_pp(s, X, W, bias, out, m192 * 192, N, K, ldx, ldw, ldo, epi, 0, rest, 192);
-  }
-  return launch_pp(s, X, W, bias, out, m_main * 256, N, K, ldx, ldw, ldo, epi, 0, tail_rows);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1017,16 +925,15 @@ __global__ __launch_bounds__(512) void gemm_ln_skinny_kernel(const float* __rest
 
 // may the LayerNorm-folding weight-streaming GEMM take this shape?  (M rows incl. padding; K = the normalised width)
 bool gemm_ln_skinny_ok(int M, int N, int K) {
-  static const int on = [] { const char* e = getenv("PGIBBS_LN_SKINNY"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("PGIBBS_LN_SKINNY", 1);
   return on && (M == 16 || M == 32) && N % 16 == 0 && K % 256 == 0 && K / 256 >= 1 && K / 256 <= 5;
 }
 int launch_gemm_ln_skinny(hipStream_t s, const float* X, int ldx, const float* gamma, const float* beta, float eps, const bf16_t* W,
                           const float* bias, void* out, int M, int N, int K, int ldw, int ldo, int epi) {
   if (!gemm_ln_skinny_ok(M, N, K) || (epi != EPI_BF16 && epi != EPI_BF16_GELU)) return fail(1, "gemm_ln_skinny: shape / epilogue");
   const int nks = K / 256;
-  static const int n_cu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-  static const int nb_env = [] { const char* e = getenv("PGIBBS_LN_SKINNY_NB"); return e ? atoi(e) : 0; }();
-  const int nb = nb_env ? nb_env : ((N / 16 > n_cu && N % 32 == 0) ? 2 : 1);
+  static const int nb_env = env_int("PGIBBS_LN_SKINNY_NB", 0);
+  const int nb = nb_env ? nb_env : ((N / 16 > device_cu_count() && N % 32 == 0) ? 2 : 1);
   if (nb == 2 && N % 32) return fail(1, "gemm_ln_skinny: N must be a multiple of 32 for two feature blocks per workgroup");
   dim3 grid(N / (16 * nb)), block(512);
   note_kernel("ln+skinny8w", N / (16 * nb));
@@ -1054,14 +961,14 @@ int launch_gemm_ln_skinny(hipStream_t s, const float* X, int ldx, const float* g
   return 0;
 }
 
+// 8 waves per workgroup (K split 8 ways: twice the loads in flight per CU) whenever each wave still gets whole 32-wide k-steps
+static bool skinny_8_waves(int K) { return K % 256 == 0; }
 template <int MT>
 static int launch_skinny_mt(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int N, int K, int ldx,
                             int ldw, int ldo, int epi, int splits = 1, long split_stride = 0) {
-  // 8 waves per workgroup (K split 8 ways: twice the loads in flight per CU) whenever each wave still gets whole
-  // 32-wide k-steps and the m-tile count keeps the register footprint small
-  const bool w8 = (K % 256 == 0) && MT <= 4;
+  static_assert(MT <= 4, "8 waves: the m-tile count keeps the register footprint small");
+  const bool w8 = skinny_8_waves(K);
   dim3 grid(N / 16, splits), block(w8 ? 512 : 256);
-  note_kernel(w8 ? "skinny8w" : "skinny4w", N / 16, splits);
 #define PG_GEMM_CASE(E)                                                                                              \
   case E:                                                                                                            \
     if (w8) hipLaunchKernelGGL((gemm_bf16_skinny_kernel<MT, E, 8>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, split_stride); \
@@ -1087,7 +994,6 @@ static int launch_cfg(hipStream_t s, const bf16_t* X, const bf16_t* W, const flo
                       int K, int ldx, int ldw, int ldo, int epi, int splits = 1, long split_stride = 0) {
   const int tiles_m = M / BM, tiles_n = N / BN, n_tiles = tiles_m * tiles_n;
   dim3 grid(n_tiles, splits), block((BM / WM) * (BN / WN) * 64);
-  note_kernel(BM == 64 ? "tile64x64" : (BM == 128 ? "tile128x128" : "tile256x256-lockstep"), n_tiles, splits);
 #define PG_GEMM_CASE(E)                                                                                              \
   case E:                                                                                                            \
     hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, E>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, \
@@ -1133,7 +1039,7 @@ size_t gemm_splitk_ws_bytes(int M, int N, int K) {       // the kernels write wh
 
 int launch_gemm_bf16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K,
                      int ldx, int ldw, int ldo, int epi, float* ws, size_t ws_bytes, int m_live) {
-  static const int variant = [] { const char* e = getenv("PGIBBS_GEMM"); return e ? atoi(e) : 2; }();
+  static const int variant = env_int("PGIBBS_GEMM", 2);
   return launch_gemm_bf16_variant(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, variant, ws, ws_bytes, m_live);
 }
 
@@ -1145,7 +1051,7 @@ int launch_gemm_bf16(hipStream_t s, const bf16_t* X, const bf16_t* W, const floa
 // blocks of an activation row's groups, the plain kernels all three: a producer may leave the duplicate hi block unwritten
 // exactly when this says yes for its consumer (Engine: LayerNorm rows, fc1's EPI_SPLIT2_GELU rows).
 bool gemm_split3_fused(int M, int N, int K, int epi) {
-  static const int fused = [] { const char* e = getenv("PGIBBS_SPLIT3_FUSED"); return e ? atoi(e) : 1; }();
+  static const int fused = env_int("PGIBBS_SPLIT3_FUSED", 1);
   const bool ok256 = M % 256 == 0 && N % 256 == 0 && K % 32 == 0 && M >= 256;
   return ok256 && (epi == EPI_SPLIT3_GELU || epi == EPI_SPLIT2_GELU || (fused && (long)(M / 256) * (N / 256) >= 128));
 }
@@ -1157,77 +1063,226 @@ int launch_gemm_split3(hipStream_t s, const bf16_t* X3, const bf16_t* W3, const 
 }
 #endif  // !PG_F16
 
-int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,
-                             int K, int ldx, int ldw, int ldo, int epi, int variant, float* ws, size_t ws_bytes, int m_live) {
-  // Dispatch by how many tiles each kernel would put on the 256 CUs (times in us, tools/gemm_mid_bench.py, N=1280 K=1280):
-  //   M =    16    64   256  1024  4096  16384
-  //   skinny 4.3   8.7  26.4                       one workgroup per 16 output features, weights streamed once
-  //   64^2         7.7   7.9  13.6  31.7           5 workgroups per CU: fills the chip from 64 token rows on
-  //   128^2             16.4  19.8  26.9   78
-  //   256^2 ping-pong         31.4  36.4   87      (wins from >= 128 tiles: 41 vs 49 us at M = 8192)
-  if (K % 64) return fail(1, "gemm: K must be a multiple of 64");
+
+// ------------------------------------------------------------------------------------------------
+// The dispatch.  plan_gemm says which kernel runs on which rows: a pure function of the shape, the device's CU count and the process's
+// PGIBBS_GEMM* switches, without a HIP call, so pg_dbg_gemm_plan prints its answers on a machine without a GPU
+// (tests/test_gemm_plan_cpu.py pins them for the shapes the project is measured on).  launch_plan is the one switch over it.
+// ------------------------------------------------------------------------------------------------
+enum { GEMM_INVALID, GEMM_SKINNY, GEMM_TILE64, GEMM_TILE128, GEMM_TILE256_LOCKSTEP, GEMM_PP, GEMM_W16, GEMM_LADDER };
+struct GemmPlan {
+  int kind = GEMM_INVALID;
+  int rows = 0;                  // token rows the kernel is launched on (LADDER: the live rows its panels cover)
+  int tile_rows = 0;             // PP: 256 or 192; LADDER: the tile height
+  int tail_rows = 0;             // PP, W16: rows of 64 x 64 tail tiles in the same grid, from row `rows` on
+  int splits = 1;                // > 1: K-splits side by side into ws, then splitk_reduce_kernel
+  int abl = 0;                   // PP, W16: micro-benchmark ablation
+  const char* error = nullptr;   // INVALID: why
+};
+static GemmPlan plan_error(const char* msg) { return {GEMM_INVALID, 0, 0, 0, 1, 0, msg}; }
+
+// geometry of a big-batch launch: m-panels of 256 x 256 tiles that fill whole rounds of one tile per CU + rows of 64 x 64 tail tiles
+// for the rest, when the last round would be partly empty and the tail is at most PGIBBS_GEMM_TAIL_MAX tiles per CU
+struct BigGeom { int m_main, tail_rows; };
+static BigGeom big_geometry(int M, int N, int n_cu) {
+  static const int tail_on = env_int("PGIBBS_GEMM_TAIL", 1);
+  static const int tail_max = env_int("PGIBBS_GEMM_TAIL_MAX", 4);
+  const int tiles_n = N / 256, tiles_m = M / 256;
+  const long t256 = (long)tiles_m * tiles_n, full = t256 / n_cu, frac = t256 - full * n_cu;
+  BigGeom g{tiles_m, 0};
+  if (tail_on && frac > 0) {
+    const int mm = (int)(full * n_cu / tiles_n);             // m-panels that fill whole rounds (0: less than one round of big tiles)
+    const long n_tail = (long)(tiles_m - mm) * 4 * (N / 64);
+    if (n_tail <= (long)tail_max * n_cu) { g.m_main = mm; g.tail_rows = (tiles_m - mm) * 256; }
+  }
+  return g;
+}
+void gemm_big_geometry(int M, int N, int K, int* m_main_panels, int* tail_rows) {
+  const BigGeom g = big_geometry(M, N, device_cu_count());
+  *m_main_panels = g.m_main;
+  *tail_rows = g.tail_rows;
+}
+
+// What a residual launch costs, in rounds of 256 x 256 tiles (one per CU).  Whole rounds of 256-row tiles + 0.15 for a round of tail tiles:
+static double rounds_256(const BigGeom& g, int M, int N, int n_cu) {
+  const int tiles_n = N / 256;
+  return g.tail_rows ? (double)((long)g.m_main * tiles_n / n_cu) + 0.15 : (double)(((long)(M / 256) * tiles_n + n_cu - 1) / n_cu);
+}
+// ... 192 x 256 tiles cost three quarters of a round each; leftover rows (0, 64 or 128: M is a multiple of 256) cost a round of tail
+// tiles in front of the big ones (~0.2 of a round: M = 9728, N = 1280 measured 51.2 us with 250 tiles of 192 rows + 40 tail tiles
+// against 47.7 us for 190 tiles of 256 rows; tools/gemm_mid_resid_bench.py)
+static double rounds_192(int M, int N, int n_cu) {
+  const int m192 = M / 192;
+  return 0.75 * (double)(((long)m192 * (N / 256) + n_cu - 1) / n_cu) + (M - m192 * 192 ? 0.2 : 0.0);
+}
+// ... the ladder's price of tiles of h rows: rounds x h / 256 (the model that does not hold, see below)
+static double rounds_ladder(int live, int h, int N, int n_cu) {
+  return (double)(((long)((live + h - 1) / h) * (N / 256) + n_cu - 1) / n_cu) * h / 256.0;
+}
+
+// The big-batch GEMM: whole rounds of 256 x 256 tiles (one per CU) plus, in the SAME grid, 64 x 64 tail tiles for the rows
+// beyond the last full round when that round would be mostly empty (gemm_epilogue.h).  Kernel per epilogue: the 16-wave kernel
+// for the bf16 outputs (QKV projections: 3.5-4 % faster there; fc1: its one-pass GELU epilogue is 0.03 ms shorter per launch),
+// the 8-wave ping-pong kernel for the fp32 outputs (the 16-wave kernel loses 3-4 % on the residual read-modify-write);
+// PGIBBS_GEMM_BIG=pp / w16 forces one kernel for the plain epilogues.  M, N multiples of 256, K a multiple of 64, K >= 128.
+static GemmPlan plan_big(int M, int N, int K, int epi, int m_live, int n_cu) {
+  static const int big = [] { const char* e = getenv("PGIBBS_GEMM_BIG"); return !e ? -1 : (e[0] == 'w' ? 16 : 0); }();
+  static const int t192 = env_int("PGIBBS_GEMM_T192", 1);
+  static const int ladder = env_int("PGIBBS_GEMM_LADDER", 0);
+  const BigGeom geo = big_geometry(M, N, n_cu);
+  // Residual GEMMs of mid-size batches: 256-row tiles quantise badly (a 32-chain shard's out-projection / fc2: 165 tiles on 256 CUs,
+  // a 64-chain one: 325 = two rounds of which the second is a quarter full).  192 x 256 tiles (same kernel, 6 instead of 8 row
+  // blocks per wave, same k order) are taken when that is at least 10 % fewer round-equivalents (PGIBBS_GEMM_T192=2: always).
+  // The rows beyond the last 192-row tile are 64 x 64 tail tiles of the same grid.
+  const double r256 = rounds_256(geo, M, N, n_cu), r192 = rounds_192(M, N, n_cu);
+  const bool cheaper192 = t192 && epi == EPI_F32_RESID && r192 <= 0.9 * r256;
+  // Round 6: the tile-height ladder (gemm_ladder.hip; heights 160 ... 240 in steps of 16 rows).  Built for VERDICT r05's tile-count
+  // argument -- a partial last round of tiles costs a whole one, and N = 1280 (five tiles per row panel) quantises badly for a
+  // 1/8 ... 1/2 shard of config 3 -- and MEASURED (profiles/r06_ladder_bench.txt, r06_shard_proxy_ladder_ab.txt): every height
+  // takes the same time to within 3 % at every shard size (a 32-chain shard's fc2: 165 tiles of 256 rows 128.8 us, 220 of 192
+  // 127.0, 240 of 176 133.6, 190 of 224 128.7), bit-identical results.  These launches run at a fixed aggregate L2 -> LDS feed of
+  // ~8 TB/s whatever the tiling (bytes staged / time: 6.8 ... 8.5 TB/s from the 32-chain shard to the full batch), so idle CUs in a
+  // partial round are not lost throughput and a smaller tile only raises the bytes staged per FLOP.  OFF by default;
+  // PGIBBS_GEMM_LADDER=1 prices the candidates in rounds x height (the model that does not hold), =h forces height h where the
+  // epilogue has it (the A/B switch of tests/test_gpu_kernels.py and tools/ladder_bench.py).
+  if (ladder && (epi == EPI_F32_RESID || epi == EPI_BF16_GELU)) {
+    const int live = m_live > 0 && m_live <= M ? m_live : M;
+    int best_h = 0;
+    double best = 0.95 * (cheaper192 ? r192 : r256);
+    for (int h = 240; h >= 160; h -= 16) {
+      if (!gemm_ladder_has(epi, h) || (ladder > 1 && ladder != h)) continue;
+      const double c = rounds_ladder(live, h, N, n_cu);
+      if (ladder == h || c < best - 1e-9) { best = c; best_h = h; if (ladder == h) break; }
+    }
+    if (best_h) return {GEMM_LADDER, live, best_h};
+  }
+  const bool bf16out = epi == EPI_BF16 || epi == EPI_BF16_GELU;
+  if (big == 16 || (big == -1 && bf16out)) return {GEMM_W16, geo.m_main * 256, 256, geo.tail_rows};
+  if (cheaper192 || (t192 == 2 && epi == EPI_F32_RESID)) return {GEMM_PP, M / 192 * 192, 192, M % 192};
+  return {GEMM_PP, geo.m_main * 256, 256, geo.tail_rows};
+}
+
+// Dispatch by how many tiles each kernel would put on the 256 CUs (times in us, tools/gemm_mid_bench.py, N=1280 K=1280):
+//   M =    16    64   256  1024  4096  16384
+//   skinny 4.3   8.7  26.4                       one workgroup per 16 output features, weights streamed once
+//   64^2         7.7   7.9  13.6  31.7           5 workgroups per CU: fills the chip from 64 token rows on
+//   128^2             16.4  19.8  26.9   78
+//   256^2 ping-pong         31.4  36.4   87      (wins from >= 128 tiles: 41 vs 49 us at M = 8192)
+// ws_bytes: the fp32 scratch on offer (0: none); variant: the table in kernels_ops.inc
+static GemmPlan plan_gemm(int M, int N, int K, int epi, int variant, size_t ws_bytes, int m_live, int n_cu) {
+  if (K % 64) return plan_error("gemm: K must be a multiple of 64");
+  const bool ok256 = M % 256 == 0 && N % 256 == 0 && K >= 128;
+  // ---- the benchmark variants that name a kernel take it where the shape allows.  Everything else is the production dispatch
+  // below; variants other than 2 ... 5 never split K, and variant 1 (lockstep tiles only) does not stream weights either
+  if (variant == 6 && M % 64 == 0 && N % 64 == 0) return {GEMM_TILE64, M};
+  if (variant == 7 && M % 128 == 0 && N % 128 == 0) return {GEMM_TILE128, M};
+  if (variant == 8 && epi == EPI_F32_RESID && ok256 && M >= 192) return {GEMM_PP, M / 192 * 192, 192, M % 192};
+  if ((variant == 1 || variant >= 20) && M > 256 && M % 128 == 0 && N % 64 == 0) {       // past the small-batch kernels and their checks
+    const int abl = variant >= 80 ? variant - 80 : (variant >= 60 ? variant - 40 : variant - 20);
+    if (variant >= 20 && ok256) return {variant >= 80 ? GEMM_W16 : GEMM_PP, M, 256, 0, 1, abl};
+    if (variant == 1 && N % 128 == 0) return {ok256 ? GEMM_TILE256_LOCKSTEP : GEMM_TILE128, M};
+  }
+  const bool may_split = variant != 1 && variant < 6, may_stream = variant != 1;
+
+  // ---- production (variant 2), top to bottom
   // Deep K with few tiles (fc2 of a few dozen chains: K = 5120, 80-320 tiles): K-splits run side by side into ws, then one
   // reduction adds them to the residual stream in fixed order.  M = 1024: 43 -> 21 us, M = 32: 15.6 -> 8 us.
-  if (epi == EPI_F32_RESID && ws && K >= 2048 && M >= 16 && M % 16 == 0 && N % 64 == 0 && variant != 1 && variant < 6) {
+  // (round 4: ONE launch of N / 16 workgroups with 16 waves splitting K instead of the K-splits + reduction was measured slower,
+  // config 1 1.73 -> 1.92 ms per iteration: every workgroup re-reads the whole [M][K] operand, 327 KB at K = 5120, and a CU's
+  // L2 -> L1 path carries ~130 GB/s -- the K-splits spread those reads over four times as many CUs)
+  if (may_split && epi == EPI_F32_RESID && ws_bytes && K >= 2048 && M >= 16 && M % 16 == 0 && N % 64 == 0) {
     const int splits = gemm_splitk_splits(K);
     const int Mr = M <= 16 ? 16 : (M <= 32 ? 32 : (M <= 256 ? (M + 63) / 64 * 64 : M));   // rows the kernels write (their tile heights)
     const long t64 = (long)(Mr / 64) * (N / 64);
     const bool pp_sized = M % 256 == 0 && N % 256 == 0 && (long)(M / 256) * (N / 256) >= 128;   // the 256^2 kernel fills the chip
     const bool small = M <= 48 || ((M <= 256 || M % 64 == 0) && t64 * splits <= 1280 && !pp_sized);
-    const long stride = (long)Mr * N;
-    // (round 4: ONE launch of N / 16 workgroups with 16 waves splitting K instead of the K-splits + reduction was measured slower,
-    // config 1 1.73 -> 1.92 ms per iteration: every workgroup re-reads the whole [M][K] operand, 327 KB at K = 5120, and a CU's
-    // L2 -> L1 path carries ~130 GB/s -- the K-splits spread those reads over four times as many CUs)
     // ws_bytes >= gemm_splitk_ws_bytes(M, N, K) by the callers' sizing: the comparison guards the buffer, it is not the dispatch
-    if (splits > 1 && small && (size_t)splits * stride * 4 <= ws_bytes && (K / splits) % 64 == 0) {
-      int rc;
-      const int Ks = K / splits;
-      if (M <= 48) {
-        const int mt = M / 16;
-        rc = mt <= 1 ? launch_skinny_mt<1>(s, X, W, bias, ws, N, Ks, ldx, ldw, N, EPI_F32_PARTIAL, splits, stride)
-           : mt <= 2 ? launch_skinny_mt<2>(s, X, W, bias, ws, N, Ks, ldx, ldw, N, EPI_F32_PARTIAL, splits, stride)
-                     : launch_skinny_mt<4>(s, X, W, bias, ws, N, Ks, ldx, ldw, N, EPI_F32_PARTIAL, splits, stride);
-      } else if (Mr % 128 == 0 && N % 128 == 0 && (long)(Mr / 128) * (N / 128) * splits >= 256) {
-        rc = launch_cfg<128, 128, 64, 64>(s, X, W, bias, ws, Mr, N, Ks, ldx, ldw, N, EPI_F32_PARTIAL, splits, stride);   // enough 128^2 tiles
-      } else {
-        rc = launch_cfg<64, 64, 32, 32>(s, X, W, bias, ws, Mr, N, Ks, ldx, ldw, N, EPI_F32_PARTIAL, splits, stride);
-      }
-      if (rc) return rc;
-      const long total4 = stride / 4;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, ws, bias, (float*)out, N / 4,
-                         ldo, total4, splits, stride);
-      PG_HIP(hipGetLastError());
-      return 0;
+    if (splits > 1 && small && (size_t)splits * Mr * N * 4 <= ws_bytes && (K / splits) % 64 == 0) {
+      const bool enough128 = Mr % 128 == 0 && N % 128 == 0 && (long)(Mr / 128) * (N / 128) * splits >= 256;
+      return {M <= 48 ? GEMM_SKINNY : (enough128 ? GEMM_TILE128 : GEMM_TILE64), Mr, 0, 0, splits};
     }
   }
-  if (variant == 6 && M % 64 == 0 && N % 64 == 0) return launch_cfg<64, 64, 32, 32>(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi);
-  if (variant == 7 && M % 128 == 0 && N % 128 == 0) return launch_cfg<128, 128, 64, 64>(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi);
-  if (variant == 8 && epi == EPI_F32_RESID && M % 256 == 0 && N % 256 == 0 && K >= 128 && M >= 192)      // micro-benchmark: 192-row tiles
-    return launch_pp(s, X, W, bias, out, (M / 192) * 192, N, K, ldx, ldw, ldo, epi, 0, M - (M / 192) * 192, 192);
-  if (M >= 16 && M <= 48 && M % 16 == 0 && N % 16 == 0 && variant != 1) {
-    const int mt = M / 16;
-    if (mt <= 1) return launch_skinny_mt<1>(s, X, W, bias, out, N, K, ldx, ldw, ldo, epi);
-    if (mt <= 2) return launch_skinny_mt<2>(s, X, W, bias, out, N, K, ldx, ldw, ldo, epi);
-    return launch_skinny_mt<4>(s, X, W, bias, out, N, K, ldx, ldw, ldo, epi);
-  }
+  if (may_stream && M >= 16 && M <= 48 && M % 16 == 0 && N % 16 == 0) return {GEMM_SKINNY, M};
   if (M <= 256) {
     // rows beyond M inside the last 64-row tile are read/written too: callers pad buffers to 256 rows
-    if (M % 16 || N % 64) return fail(1, "gemm: M must be a multiple of 16 and N of 64");
-    return launch_cfg<64, 64, 32, 32>(s, X, W, bias, out, (M + 63) / 64 * 64, N, K, ldx, ldw, ldo, epi);
+    if (M % 16 || N % 64) return plan_error("gemm: M must be a multiple of 16 and N of 64");
+    return {GEMM_TILE64, (M + 63) / 64 * 64};
   }
-  if (M % 128 || N % 64) return fail(1, "gemm: M must be a multiple of 128 and N of 64");
-  const bool ok256 = M % 256 == 0 && N % 256 == 0 && K >= 128, ok128 = N % 128 == 0;
-  const long t256 = (long)(M / 256) * (N / 256), t128 = (long)(M / 128) * (N / 128);
-  if (variant >= 80 && ok256) return launch_gemm_w16(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, variant - 80);
-  if (variant >= 60 && ok256) return launch_pp(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, variant - 40);   // pp ablations 20..
-  if (variant >= 20 && ok256) return launch_pp(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, variant - 20);
-  if (variant == 1) {
-    if (ok256) return launch_cfg<256, 256, 128, 64>(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi);
-    if (ok128) return launch_cfg<128, 128, 64, 64>(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi);
+  if (M % 128 || N % 64) return plan_error("gemm: M must be a multiple of 128 and N of 64");
+  if (ok256 && (long)(M / 256) * (N / 256) >= 128) return plan_big(M, N, K, epi, m_live, n_cu);
+  if (N % 128 == 0 && (long)(M / 128) * (N / 128) >= 200) return {GEMM_TILE128, M};
+  return {GEMM_TILE64, M};
+}
+
+// what a launch of the plan records (note_kernel); the ablation instances are not recorded
+static void note_plan(const GemmPlan& p, int N, int K) {
+  if (p.abl || p.kind == GEMM_INVALID) return;
+  const long tiles_n = N / 256;
+  char ladder[32];
+  switch (p.kind) {
+    case GEMM_SKINNY: note_kernel(skinny_8_waves(K / p.splits) ? "skinny8w" : "skinny4w", N / 16, p.splits); break;
+    case GEMM_TILE64: note_kernel("tile64x64", (long)(p.rows / 64) * (N / 64), p.splits); break;
+    case GEMM_TILE128: note_kernel("tile128x128", (long)(p.rows / 128) * (N / 128), p.splits); break;
+    case GEMM_TILE256_LOCKSTEP: note_kernel("tile256x256-lockstep", p.rows / 256 * tiles_n); break;
+    case GEMM_PP: note_kernel(p.tile_rows == 192 ? "pp192x256" : "pp256x256", p.rows / p.tile_rows * tiles_n); break;
+    case GEMM_W16: note_kernel("w16-256x256", p.rows / 256 * tiles_n); break;
+    case GEMM_LADDER:
+      snprintf(ladder, sizeof ladder, "ppx%dx256", p.tile_rows);
+      note_kernel(ladder, (p.rows + p.tile_rows - 1) / p.tile_rows * tiles_n);
+      break;
   }
-  if (ok256 && t256 >= 128) return launch_gemm_big(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, m_live);
-  if (ok128 && (t128 >= 200 || !(M % 64 == 0))) return launch_cfg<128, 128, 64, 64>(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi);
-  return launch_cfg<64, 64, 32, 32>(s, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi);
+  if (p.tail_rows) note_kernel("tail64", (long)(p.tail_rows / 64) * (N / 64));
+}
+void gemm_plan_text(int M, int N, int K, int epi, int variant, bool have_ws, int m_live, int n_cu, std::string* text) {
+  const GemmPlan p = plan_gemm(M, N, K, epi, variant, have_ws ? gemm_splitk_ws_bytes(M, N, K) : 0, m_live, n_cu);
+  clear_noted_kernels();
+  note_plan(p, N, K);
+  *text = p.kind == GEMM_INVALID ? std::string("error: ") + p.error : noted_kernels();
+  clear_noted_kernels();
+}
+
+// M = the rows that exist in X / out
+static int launch_plan(hipStream_t s, const GemmPlan& p, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,
+                       int K, int ldx, int ldw, int ldo, int epi, float* ws) {
+  if (p.kind == GEMM_INVALID) return fail(1, p.error);
+  note_plan(p, N, K);
+  // K-splits: the kernel writes bias-free partial sums of its K range to ws[split][rows][N]
+  const bool split = p.splits > 1;
+  const long stride = split ? (long)p.rows * N : 0;
+  void* o = split ? ws : out;
+  const int Ks = K / p.splits, ldos = split ? N : ldo, e = split ? (int)EPI_F32_PARTIAL : epi;
+  int rc = 0;
+  switch (p.kind) {
+    case GEMM_SKINNY:      // 16, 32 or up to 64 rows per workgroup
+      rc = p.rows <= 16 ? launch_skinny_mt<1>(s, X, W, bias, o, N, Ks, ldx, ldw, ldos, e, p.splits, stride)
+         : p.rows <= 32 ? launch_skinny_mt<2>(s, X, W, bias, o, N, Ks, ldx, ldw, ldos, e, p.splits, stride)
+                        : launch_skinny_mt<4>(s, X, W, bias, o, N, Ks, ldx, ldw, ldos, e, p.splits, stride);
+      break;
+    case GEMM_TILE64: rc = launch_cfg<64, 64, 32, 32>(s, X, W, bias, o, p.rows, N, Ks, ldx, ldw, ldos, e, p.splits, stride); break;
+    case GEMM_TILE128: rc = launch_cfg<128, 128, 64, 64>(s, X, W, bias, o, p.rows, N, Ks, ldx, ldw, ldos, e, p.splits, stride); break;
+    case GEMM_TILE256_LOCKSTEP: rc = launch_cfg<256, 256, 128, 64>(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi); break;
+    case GEMM_PP: rc = launch_pp(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi, p.abl, p.tail_rows, p.tile_rows); break;
+    case GEMM_W16: rc = launch_gemm_w16(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi, p.abl, p.tail_rows); break;
+    case GEMM_LADDER: rc = launch_gemm_ladder(s, X, W, bias, out, p.rows, M, p.tile_rows, N, K, ldx, ldw, ldo, epi); break;
+  }
+  if (rc || !split) return rc;
+  const long total4 = stride / 4;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, ws, bias, (float*)out, N / 4, ldo,
+                     total4, p.splits, stride);
+  PG_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gemm_big(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldx,
+                    int ldw, int ldo, int epi, int m_live) {
+  if (M % 256 || N % 256 || K % 64 || K < 128 || M < 256) return fail(1, "gemm_big: shape");
+  return launch_plan(s, plan_big(M, N, K, epi, m_live, device_cu_count()), X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, nullptr);
+}
+
+int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,
+                             int K, int ldx, int ldw, int ldo, int epi, int variant, float* ws, size_t ws_bytes, int m_live) {
+  const GemmPlan p = plan_gemm(M, N, K, epi, variant, ws ? ws_bytes : 0, m_live, device_cu_count());
+  return launch_plan(s, p, X, W, bias, out, M, N, K, ldx, ldw, ldo, epi, ws);
 }
 
 PG_OPS_END

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
 }
 
 bool colattn_ok(int R, int d_model, int n_heads) {
-  static const int on = [] { const char* e = getenv("PGIBBS_MSA_COLFUSE"); return e ? atoi(e) : 1; }();
+  static const int on = env_int("PGIBBS_MSA_COLFUSE", 1);
   return on && (R == 32 || R == 64 || R == 128 || R == 256) && d_model % 64 == 0 && n_heads * 64 == d_model;
 }
 

@@ -360,4 +360,24 @@ __device__ __forceinline__ void tile256_epilogue(ElemF&& elem, char* smem, int w
   }
 }
 
+// ---- switches the tile launchers share (host): one reader each, so that what a forced value means per kernel family can be compared ----
+// PGIBBS_GEMM_GM: m-panels per rasterisation group, the kernels' GM template parameter.  Unset: 4, but 2 for deep K (fc2: a 256-row
+// X panel of K = 5120 is 2.6 MB, four of them plus the W panels overflow the XCD's 4 MB L2 even slice-wise; measured 0.760 ->
+// 0.733 ms with the bf16 epilogue).  A forced value is mapped onto the instances the family has.
+enum { GM_PP256, GM_PP192, GM_W16, GM_LADDER };
+inline int gemm_gm(int family, int K) {
+  static const int env = env_int("PGIBBS_GEMM_GM", 0);
+  const int dflt = K >= 4096 ? 2 : 4;
+  switch (family) {
+    case GM_PP256: return !env ? dflt : (env == 1 || env == 2 ? env : 4);   // 8-wave kernel, 256-row tiles: 1, 2, 4
+    case GM_LADDER: return env == 2 || env == 4 ? env : dflt;                // ladder: 2, 4; anything else as unset
+    default: return (env ? env : dflt) == 2 ? 2 : 4;                         // 192-row tiles, 16-wave kernel: 2, else 4
+  }
+}
+// PGIBBS_GEMM_TAIL_LAST=1: the 64 x 64 tail tiles are the last workgroups of the grid instead of the first
+inline bool gemm_tail_last() {
+  static const int on = env_int("PGIBBS_GEMM_TAIL_LAST", 0);
+  return on != 0;
+}
+
 PG_OPS_END

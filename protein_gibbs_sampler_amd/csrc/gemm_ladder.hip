@@ -23,7 +23,6 @@
 //   * epilogue: phase g stages the rows of wave group g through LDS ((XJg x 16) rows x 1 KiB <= 128 KB) and all eight waves move
 //     them out as whole rows (2 XJg rows per wave) -- residual read-modify-write with the row loads of both phases issued before the
 //     first store, or fc1's bias + GELU + 16-bit pack.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "gemm_epilogue.h"
@@ -297,12 +296,8 @@ int launch_gemm_ladder(hipStream_t s, const bf16_t* X, const bf16_t* W, const fl
   if (!gemm_ladder_has(epi, h) || m_live < 1 || m_rows < h || m_rows < m_live || m_rows % 16 || N % 256 || K % 64 || K < 128)
     return fail(1, "gemm_ladder: shape / height / epilogue");
   const int tiles_m = (m_live + h - 1) / h;
-  static const int gm_env = [] { const char* e = getenv("PGIBBS_GEMM_GM"); return e ? atoi(e) : 0; }();
-  const int gm = gm_env == 2 || gm_env == 4 ? gm_env : (K >= 4096 ? 2 : 4);
+  const int gm = gemm_gm(GM_LADDER, K);
   const int tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
-  char label[32];
-  snprintf(label, sizeof label, "ppx%dx256", h);
-  note_kernel(label, n_tiles);
 #define PGL_ARGS s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, gm, m_rows
   if (epi == EPI_F32_RESID) {
     switch (h) {

@@ -284,8 +284,8 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(const bf16_t* __restric
 // 8 workgroups per CU in flight.  A second resident workgroup would need half the accumulators (a 56-row tile: 2x the W traffic per
 // FLOP) -- the trade round 4's 256 x 128 two-resident GEMM lost.  Closed.
 bool gemm_rowln_ok(int m_rows, int N, int K) {
-  static const int on = [] { const char* e = getenv("PGIBBS_ROWLN"); return e ? atoi(e) : 0; }();
-  static const int kmax = [] { const char* e = getenv("PGIBBS_ROWLN_KMAX"); return e ? atoi(e) : 1024; }();
+  static const int on = env_int("PGIBBS_ROWLN", 0);
+  static const int kmax = env_int("PGIBBS_ROWLN_KMAX", 1024);
   return on && N == rowln::N && K % 32 == 0 && K >= 128 && K <= kmax && m_rows >= rowln::TM && m_rows % 16 == 0;
 }
 
@@ -296,9 +296,9 @@ int launch_gemm_rowln(hipStream_t s, const bf16_t* A, const bf16_t* W, const flo
   const int tiles = (m_live + rowln::TM - 1) / rowln::TM;
   note_kernel("rowln112x768", tiles);
   // de-phasing of the first round (see the kernel): populations and the delay between them, in ticks of s_memrealtime (100 MHz)
-  static const int n_cu = [] { hipDeviceProp_t p; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&p, d) == hipSuccess ? p.multiProcessorCount : 256; }();
-  static const int pop_env = [] { const char* e = getenv("PGIBBS_ROWLN_POP"); return e ? atoi(e) : 1; }();        // measured: no effect (1 = off)
-  static const int us_env = [] { const char* e = getenv("PGIBBS_ROWLN_STAGGER_US"); return e ? atoi(e) : 0; }();
+  const int n_cu = device_cu_count();
+  static const int pop_env = env_int("PGIBBS_ROWLN_POP", 1);        // measured: no effect (1 = off)
+  static const int us_env = env_int("PGIBBS_ROWLN_STAGGER_US", 0);
   const int n_pop = (tiles >= 2 * n_cu && pop_env >= 1 && pop_env <= 8) ? pop_env : 1;      // fewer than two rounds: nothing to overlap
   const int period_us = us_env > 0 ? us_env * n_pop : (int)(0.043 * K + 41.0);                 // ~ one tile: main loop + epilogue
   const int stagger_ticks = n_pop > 1 ? period_us * 100 / n_pop : 0;

@@ -311,52 +311,42 @@ int launch_gemm_split3_w16(hipStream_t s, const bf16_t* X3, const bf16_t* W3, co
 
 #endif  // !PG_F16
 
-template <int ABL>
-static int launch_w16_abl(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int K, int ldx, int ldw,
-                          int ldo, int tiles_n, int n_tiles) {
-  hipLaunchKernelGGL((gemm_bf16_w16_kernel<EPI_BF16, 4, ABL>), dim3(n_tiles), dim3(1024), 0, s, X, W, bias, out, K, ldx, ldw, ldo,
-                     tiles_n, n_tiles, 0, 0);
-  PG_HIP(hipGetLastError());
-  return 0;
-}
-
-// M, N multiples of 256; K a multiple of 64.  abl > 0: micro-benchmark variants (bf16 epilogue only)
+// M, N multiples of 256; K a multiple of 64.  abl > 0: micro-benchmark variants (bf16 epilogue only, no tail tiles).  The
+// dispatch that picks this kernel records it (note_plan, gemm_bf16.hip).
 int launch_gemm_w16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldx,
                     int ldw, int ldo, int epi, int abl, int tail_rows) {
   const int tiles_m = M / 256, tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
-  static const int tail_last = [] { const char* e = getenv("PGIBBS_GEMM_TAIL_LAST"); return e ? atoi(e) : 0; }();
   const int n_tail_abs = (tail_rows / 64) * (N / 64), tail_m0 = M;
-  const int n_tail = tail_last ? -n_tail_abs : n_tail_abs;
-  if (M % 256 || N % 256 || K % 64 || K < 64 || tail_rows % 64 || n_tiles + n_tail_abs < 1) return fail(1, "gemm_w16: shape");
+  const int n_tail = gemm_tail_last() ? -n_tail_abs : n_tail_abs;
+  if (M % 256 || N % 256 || K % 64 || K < 64 || tail_rows % 64 || n_tiles + n_tail_abs < 1 || (abl && tail_rows))
+    return fail(1, "gemm_w16: shape");
+  const int gm = gemm_gm(GM_W16, K);
+  dim3 grid(n_tiles + n_tail_abs), block(1024);
+  // every instance of the kernel, one line each: (abl, epi) -> <EPI, GM, ABL>
+#define PG_W16(E, G, A)                                                                                                          \
+  hipLaunchKernelGGL((gemm_bf16_w16_kernel<E, G, A>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, \
+                     n_tail, tail_m0)
+#define PG_W16_CASE(E) case E: if (gm == 2) PG_W16(E, 2, 0); else PG_W16(E, 4, 0); break;
   switch (abl) {
-    case 0: break;
-    case 1: return launch_w16_abl<1>(s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles);
-    case 2: return launch_w16_abl<2>(s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles);
-    case 4: return launch_w16_abl<4>(s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles);
-    case 5: return launch_w16_abl<5>(s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles);
-    case 10: return launch_w16_abl<10>(s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles);
+    case 0:
+      switch (epi) {
+        PG_W16_CASE(EPI_BF16)
+        PG_W16_CASE(EPI_BF16_GELU)
+        PG_W16_CASE(EPI_F32_RESID)
+        PG_W16_CASE(EPI_F32)
+        PG_W16_CASE(EPI_F32_GELU)
+        default: return fail(1, "gemm_w16: bad epilogue");
+      }
+      break;
+    case 1: PG_W16(EPI_BF16, 4, 1); break;
+    case 2: PG_W16(EPI_BF16, 4, 2); break;
+    case 4: PG_W16(EPI_BF16, 4, 4); break;
+    case 5: PG_W16(EPI_BF16, 4, 5); break;
+    case 10: PG_W16(EPI_BF16, 4, 10); break;
     default: return fail(1, "gemm_w16: unknown ablation");
   }
-  static const int gm_env = [] { const char* e = getenv("PGIBBS_GEMM_GM"); return e ? atoi(e) : 0; }();
-  const int gm = gm_env ? gm_env : (K >= 4096 ? 2 : 4);
-  dim3 grid(n_tiles + n_tail_abs), block(1024);
-  note_kernel("w16-256x256", n_tiles);
-  if (n_tail_abs) note_kernel("tail64", n_tail_abs);
-#define PG_W16_CASE(E)                                                                                                     \
-  case E:                                                                                                                  \
-    if (gm == 2) hipLaunchKernelGGL((gemm_bf16_w16_kernel<E, 2, 0>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0); \
-    else hipLaunchKernelGGL((gemm_bf16_w16_kernel<E, 4, 0>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0);     \
-    break;
-  switch (epi) {
-    PG_W16_CASE(EPI_BF16)
-    PG_W16_CASE(EPI_BF16_GELU)
-    PG_W16_CASE(EPI_F32_RESID)
-    PG_W16_CASE(EPI_F32)
-    PG_W16_CASE(EPI_F32_GELU)
-    default:
-      return fail(1, "gemm_w16: bad epilogue");
-  }
 #undef PG_W16_CASE
+#undef PG_W16
   PG_HIP(hipGetLastError());
   return 0;
 }

@@ -12,8 +12,18 @@ int launch_gemm_bf16(hipStream_t s, const bf16_t* X, const bf16_t* W, const floa
 // the shape alone, never by how large a buffer happens to be
 int gemm_splitk_splits(int K);
 size_t gemm_splitk_ws_bytes(int M, int N, int K);
-// variant: 1 = lockstep tiles only, 2 = default dispatch, 6 / 7 = force 64^2 / 128^2 tiles, 21.. = ablations of the
-// ping-pong kernel (micro-benchmark entry)
+// The micro-benchmark entry (pg_dbg_gemm_bench, tools/).  variant:
+//    2        the production dispatch (what launch_gemm_bf16 runs unless PGIBBS_GEMM says otherwise; 3 ... 5 are the same)
+//    1        lockstep tiles only: 256^2, 128^2 or 64^2 by divisibility; no weight streaming, no K-splits
+//    6 / 7    64^2 / 128^2 lockstep tiles on every row
+//    8        192 x 256 ping-pong tiles + tail tiles (residual epilogue)
+//    20 + a   ablation a of the 8-wave ping-pong kernel (a = 0: the kernel itself on all rows, no tail tiles); its ids are listed in
+//             launch_pp (gemm_bf16.hip)
+//    60 + ... the same list, id = variant - 40 (68 / 69: ids 28 / 29)
+//    80 + a   ablation a of the 16-wave kernel (a = 0: the kernel itself); ids in launch_gemm_w16 (gemm_w16.hip)
+//    90       pg_dbg_gemm_bench only (api.hip): the strict mode's fused three-product kernel
+// A variant that names a kernel takes it where the shape allows (6 - 8: divisibility; 20 and up: more than 256 rows, M and N
+// multiples of 256) and is the production dispatch without K-splits elsewhere.  An ablation id that does not exist is an error.
 int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,
                              int K, int ldx, int ldw, int ldo, int epi, int variant, float* ws = nullptr, size_t ws_bytes = 0,
                              int m_live = 0);
@@ -44,6 +54,9 @@ bool gemm_rowln_ok(int m_rows, int N, int K);
 int launch_gemm_rowln(hipStream_t s, const bf16_t* A, const bf16_t* W, const float* bias, float* x, const float* gamma,
                       const float* beta, bf16_t* h, int m_live, int m_rows, int K, int lda, int ldw, float eps, int colmajor_R = 0,
                       int colmajor_C = 0, int abl = 0);      // abl: timing ablations (tools/rowln_bench.py)
+// what launch_gemm_bf16_variant would record for a shape (note_kernel's text; "error: ..." for a shape it refuses) on a device of
+// n_cu compute units, offered split-K scratch or not -- the dispatch decision alone, no HIP call (pg_dbg_gemm_plan)
+void gemm_plan_text(int M, int N, int K, int epi, int variant, bool have_ws, int m_live, int n_cu, std::string* text);
 // its split of the rows: m-panels of 256 x 256 tiles (whole rounds of one tile per CU) + rows of 64 x 64 tail tiles
 void gemm_big_geometry(int M, int N, int K, int* m_main_panels, int* tail_rows);
 // the 16-wave 256x256 tile kernel (gemm_w16.hip): M (may be 0 with tail_rows > 0), N multiples of 256, K a multiple of 64;

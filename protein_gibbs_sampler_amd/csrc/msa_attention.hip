@@ -266,7 +266,7 @@ static void row_split_geometry(int n_bh, int obh, int R, int C, int& nw, int& n_
   }
   // a rung for every even block count (round 4; PGIBBS_ATTN_LADDER=0: the coarse ladder 2 4 8 12 18 24 30 36): the key blocks beyond C
   // are zero-filled and masked -- exact zeros in every sum, so the rung does not change the bits, only the wasted work
-  static const int fine = [] { const char* e = getenv("PGIBBS_ATTN_LADDER"); return e ? atoi(e) : 1; }();
+  static const int fine = env_int("PGIBBS_ATTN_LADDER", 1);
   static const int kbs_fine[] = {2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32, 34, 36};
   static const int kbs_coarse[] = {2, 4, 8, 12, 18, 24, 30, 36};
   const int* kbs = fine ? kbs_fine : kbs_coarse;

@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
+#include <atomic>
 #include <string>
 
 namespace pg {
@@ -16,6 +18,28 @@ int fail(int code, const std::string& msg);
 void note_kernel(const char* label, long tiles = -1, int splits = 0);
 const std::string& noted_kernels();
 void clear_noted_kernels();
+
+// ---- process switches and device facts (host) -----------------------------------------------
+// A PGIBBS_* switch as an integer: unset = dflt.  Callers keep the answer in a function-local `static const int`, so a switch is
+// read once per process at the place that uses it.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// Compute units of the CURRENT device; 256 (one MI355X) when it cannot be asked.  Cached per device: a process that drives several
+// kinds of GPU gets each one's own count, not the count of whichever device launched first.
+inline int device_cu_count() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  int n = cached[dev].load(std::memory_order_relaxed);
+  if (!n) {
+    hipDeviceProp_t p;
+    n = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+    cached[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
 
 #define PG_HIP(expr)                                                                                  \
   do {                                                                                                \

@@ -134,10 +134,7 @@ static int rope_occupancy(Kern kern) {
 template <typename Buf>
 static int rope_launch(void (*kern)(Buf*, const float*, int, int, int, int), int occ, hipStream_t s, Buf* qkv, const float* table, int64_t M,
                        int T, int H, int ld) {
-  static const int n_cu = [] {
-    hipDeviceProp_t p; int dv = 0; (void)hipGetDevice(&dv);
-    return hipGetDeviceProperties(&p, dv) == hipSuccess ? p.multiProcessorCount : 256;
-  }();
+  const int n_cu = device_cu_count();
   const int64_t need = (M + 3) / 4, resident = (int64_t)n_cu * occ;
   hipLaunchKernelGGL(kern, dim3((unsigned)(need < resident ? need : resident)), dim3(256), 0, s, qkv, table, (int)M, T, H, ld);
   PG_HIP(hipGetLastError());

@@ -199,6 +199,18 @@ np.savez(sys.argv[1], *outs)
 """
 
 
+def test_unknown_gemm_ablation_is_an_error():
+    """A micro-benchmark variant whose ablation instance does not exist is refused; launching nothing and returning success made
+    tools time an empty loop.  (Variant table: csrc/kernels_ops.inc.)"""
+    import ctypes
+    L, ms = _lib.lib(), ctypes.c_double(0)
+    for variant in (50, 60, 83):          # ids 30 and 20 of the 8-wave kernel, 3 of the 16-wave kernel
+        assert L.pg_dbg_gemm_bench(0, 512, 256, 128, 0, variant, 1, ctypes.byref(ms)) != 0, variant
+        assert b"unknown ablation" in L.pg_last_error(), variant
+    _lib.check(L.pg_dbg_gemm_bench(0, 512, 256, 128, 0, 21, 1, ctypes.byref(ms)))
+    _lib.check(L.pg_dbg_gemm_bench(0, 512, 256, 128, 0, 81, 1, ctypes.byref(ms)))
+
+
 @pytest.mark.parametrize("height", [160, 176, 208, 224, 240])
 def test_tile_height_ladder_is_bit_identical_with_256_row_tiles(tmp_path, height):
     """gemm_ladder.hip (round 6): the 8-wave kernel with (XJ0 + XJ1) x 16 token rows per tile, picked by launch_gemm_big when a
