@@ -12,7 +12,7 @@
 // tiles of 64 keys staged in LDS as fp32 (all lanes read the same K/V row -> LDS broadcast), online softmax.
 #include <cstdlib>
 
-#include "kernels.h"
+#include "attn_frag.h"
 
 PG_OPS_BEGIN
 
@@ -39,10 +39,6 @@ __device__ __forceinline__ void store_ctx64(const float (&o)[64], float inv, bf1
   }
 }
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef short v4s __attribute__((ext_vector_type(4)));
-
 // 8 fp32 -> 8 bf16 hi (round to nearest even) + 8 bf16 lo = bf16(v - hi)
 __device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& hi, uint4& lo) {
   hi.x = pack_op2(a.x, a.y); hi.y = pack_op2(a.z, a.w); hi.z = pack_op2(b.x, b.y); hi.w = pack_op2(b.z, b.w);
@@ -53,16 +49,15 @@ __device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& 
 }
 
 // Building blocks shared by the three split-bf16 MFMA kernels (full attention, tied-row scores, tied-row apply).
-// Fragment geometry as in attention.hip: fr = lane & 15 is the wave's query (MFMA column), fq = lane >> 4; a score
-// block st[kb][r] = S[query fr][key kb*16 + fq*4 + r]; O^T blocks o[db][r] = O[query fr][d = db*16 + fq*4 + r].
+// Fragment geometry, tile layout and the transposing V^T read: attn_frag.h.
 template <int MAXKB>
 struct SplitAttn {
   static constexpr int tpad = MAXKB * 16, nkc = MAXKB / 2;
   static_assert(MAXKB % 2 == 0, "two 16-key blocks per 32-wide PV step");
   static constexpr float LOG2E = 1.44269504088896341f;
 
-  // rows 0 .. tpad-1 of 64 fp32 at src + row*ld (rows >= n_valid read as zero) -> (hi, lo) bf16 tiles; a tile row is
-  // 128 B with its 16-B chunks XOR-swizzled: row*128 + ((c ^ (row & 7)) << 4).  All global loads in flight first.
+  // rows 0 .. tpad-1 of 64 fp32 at src + row*ld (rows >= n_valid read as zero) -> (hi, lo) bf16 tiles (tile_addr).  All
+  // global loads in flight first.
   // extra (optional): 64 fp32 that stand in for row n_valid (ESM-1: the head's bias_k / bias_v behind the last token)
   template <bool EXTRA = false>
   static __device__ __forceinline__ void stage(const float* __restrict__ src, size_t ld, int n_valid, char* Xh, char* Xl, int tid,
@@ -90,7 +85,7 @@ struct SplitAttn {
       if (i < tpad * 8) {
         uint4 hi, lo;
         split8(r0[it], r1[it], hi, lo);
-        const int a = row * 128 + ((c ^ (row & 7)) << 4);
+        const int a = tile_addr(row, c);
         *(uint4*)(Xh + a) = hi;
         *(uint4*)(Xl + a) = lo;
       }
@@ -119,7 +114,7 @@ struct SplitAttn {
       bf16x8 kh[2];
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        const int ad = krow * 128 + (((kk * 4 + fq) ^ (krow & 7)) << 4);
+        const int ad = tile_addr(krow, kk * 4 + fq);
         kh[kk] = *(const bf16x8*)(Kh + ad);
         a = mfma_op16(*(const bf16x8*)(Kl + ad), qh[kk], a);
         a = mfma_op16(kh[kk], ql[kk], a);
@@ -167,16 +162,14 @@ struct SplitAttn {
       const bf16x8 pfh = __builtin_bit_cast(bf16x8, ph), pfl = __builtin_bit_cast(bf16x8, pl);
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        union { bf16x8 v; uint2 h2[2]; } vh, vl;
+        VtFrag vh, vl;
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {           // transposed LDS read (attention.hip): lane fr gets V[key0..key0+3][d = db*16 + fr]
+        for (int hh = 0; hh < 2; ++hh) {           // vt_half's address, once for the hi and the lo tile
           const int krow = (2 * c + hh) * 16 + fq * 4 + (fr >> 2);
           const int dcol = db * 16 + (fr & 3) * 4;
-          const int ad = krow * 128 + (((dcol >> 3) ^ (krow & 7)) << 4) + ((dcol >> 2) & 1) * 8;
-          vh.h2[hh] = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(
-                                                    (__attribute__((address_space(3))) char*)(Vh + ad))));
-          vl.h2[hh] = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(
-                                                    (__attribute__((address_space(3))) char*)(Vl + ad))));
+          const int ad = tile_addr(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8;
+          vh.h[hh] = lds_read_tr16(Vh + ad);
+          vl.h[hh] = lds_read_tr16(Vl + ad);
         }
         o[db] = mfma_op16(vl.v, pfh, o[db]);
         o[db] = mfma_op16(vh.v, pfl, o[db]);

@@ -1,0 +1,195 @@
+// The per-wave arithmetic of ONE block of 16 queries against keys that sit in LDS, shared by every MFMA attention kernel with
+// 16-bit operands (attention.hip, msa_attention.hip, the attention tail of gemm_colattn.hip, chain_trunk.hip's attention unit)
+// and, for the tile addressing and the transposing read, by the strict mode's SplitAttn (attention_f32.hip).  Kernels that
+// must give the same bits call the same functions here.  Included inside operand-flavoured files: pack_op2 / mfma_op16 resolve
+// per flavour (pg_common.h).
+//
+// The pieces take and return values (a score block, a fragment half) and spell a tile address as pointer + row*128 + swizzle:
+// hipcc optimises a __forceinline__ function on its own before it inlines it, and the forms that update a caller's array through
+// a reference under a condition, or hand the whole address over as one integer, cost the kernels registers (up to 76 VGPRs on the
+// tall rungs of attention_kernel) -- compare the ISA of every user before changing a signature here.
+//
+// Geometry (head dim 64).  A K or V tile is row-major in LDS, one key per 128-byte row, the row's eight 16-byte chunks
+// XOR-swizzled with (row & 7).  fr = lane & 15 is the lane's query (the MFMA column), fq = lane >> 4.
+//   * S^T = K.Q^T: a score block st[kb][r] = S[query fr][key kb*16 + fq*4 + r] -- a query's whole score row is lane-local up
+//     to a 4-lane (xor 16, 32) reduction, so the softmax runs in registers;
+//   * O^T = V^T.P^T: K-slot (fq*8 + j) of 32-key chunk c <-> key (2c + (j>>2))*16 + fq*4 + (j&3), exactly the order the lane
+//     holds P in; o[db][r] = O[query fr][d = db*16 + fq*4 + r] -> 8-byte row-major context stores.
+#pragma once
+#include "kernels.h"
+
+PG_OPS_BEGIN
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef short v4s __attribute__((ext_vector_type(4)));
+
+// ---- host: the key-block ladder.  A kernel template computes MAXKB 16-key blocks (even); the blocks beyond the last key are
+// zero-filled and masked -- exact zeros in every sum, so the rung changes the wasted work, never the bits.  `fine`: a rung for
+// every even block count; otherwise the coarse rungs, the only ones built for ESM-1's bias-key form.  0: more than 576 keys.
+constexpr int kCoarseRungs[] = {2, 4, 8, 12, 18, 24, 30, 36};
+constexpr bool coarse_rung(int kb) {
+  for (int r : kCoarseRungs)
+    if (r == kb) return true;
+  return false;
+}
+inline int attention_rung(int n_keys, bool fine) {
+  if (n_keys > 576) return 0;
+  if (fine) return (((n_keys + 15) / 16) + 1) & ~1;
+  for (int r : kCoarseRungs)
+    if (n_keys <= r * 16) return r;
+  return 0;
+}
+
+// ---- tiles ----------------------------------------------------------------------------------------------------------------
+// byte offset of 16-byte chunk `chunk` inside tile row `row`, and from the start of the tile
+__device__ __forceinline__ int tile_swz(int row, int chunk) { return (chunk ^ (row & 7)) << 4; }
+__device__ __forceinline__ int tile_addr(int row, int chunk) { return row * 128 + tile_swz(row, chunk); }
+
+// Staging by NT threads: item i = tid + it*NT is chunk (i & 7) of tile row (i >> 3).
+// One thread's share of one tile of TPAD rows, for kernels that put other work between a tile's loads and its LDS writes
+template <int TPAD, int NT>
+struct TileRegs {
+  static constexpr int NIT = (TPAD * 8 + NT - 1) / NT;
+  uint4 r[NIT];
+};
+template <int TPAD, int NT>
+__device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT>& g, int tid, char* dst) {
+#pragma unroll
+  for (int it = 0; it < TileRegs<TPAD, NT>::NIT; ++it) {
+    const int i = tid + it * NT, row = i >> 3, c = i & 7;
+    if (i < TPAD * 8) *(uint4*)(dst + row * 128 + tile_swz(row, c)) = g.r[it];
+  }
+}
+// The K and the V tile of one head together, rows row0 .. row0 + TPAD - 1 of the sequence's n_rows: all global loads of both are
+// issued before the first LDS write, so a workgroup pays about one memory round trip, not one per item.  bias_k / bias_v (with
+// EXTRA: ESM-1's bias key, 64 values each) stand in for row n_rows.
+template <int TPAD, int NT, bool EXTRA>
+__device__ __forceinline__ void stage_kv(char* Ks, char* Vs, int tid, const bf16_t* src, size_t ld, int k_off, int v_off, int row0,
+                                         int n_rows, const bf16_t* bias_k, const bf16_t* bias_v) {
+  constexpr int NIT = (TPAD * 8 + NT - 1) / NT;
+  uint4 kreg[NIT], vreg[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = tid + it * NT, row = row0 + (i >> 3), c = i & 7;       // row of the sequence
+    kreg[it] = make_uint4(0, 0, 0, 0);
+    vreg[it] = make_uint4(0, 0, 0, 0);
+    if (i < TPAD * 8 && row < n_rows) {
+      kreg[it] = *(const uint4*)(src + (size_t)row * ld + k_off + c * 8);
+      vreg[it] = *(const uint4*)(src + (size_t)row * ld + v_off + c * 8);
+    } else if (EXTRA && row == n_rows) {
+      kreg[it] = *(const uint4*)(bias_k + c * 8);
+      vreg[it] = *(const uint4*)(bias_v + c * 8);
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int i = tid + it * NT, row = i >> 3, c = i & 7;
+    if (i < TPAD * 8) {
+      *(uint4*)(Ks + row * 128 + tile_swz(row, c)) = kreg[it];
+      *(uint4*)(Vs + row * 128 + tile_swz(row, c)) = vreg[it];
+    }
+  }
+}
+
+// ---- fragments ------------------------------------------------------------------------------------------------------------
+// K (MFMA A operand of S^T) or Q (B operand) fragment out of a tile: row krow, d = kk*32 + fq*8 .. +7
+__device__ __forceinline__ bf16x8 k_frag(const char* Ks, int krow, int kk, int fq) {
+  return *(const bf16x8*)(Ks + krow * 128 + tile_swz(krow, kk * 4 + fq));
+}
+
+// V^T fragment (A operand of O^T) for d = db*16 .. +15 and a chunk of 32 keys, straight out of the row-major V tile through
+// gfx950's transposing LDS read ds_read_b64_tr_b16 (semantics probed on the device): the 16 lanes of a group point at 4 key
+// rows x four 8-byte pieces of 16 d (lane s -> row s>>2, piece s&3) and lane fr receives V[key .. key+3][d = db*16 + fr].
+// vt_half reads the half of the 16-key block that starts at key0 (a multiple of 16); a chunk is the halves of blocks 2c, 2c + 1.
+union VtFrag { bf16x8 v; uint2 h[2]; };
+__device__ __forceinline__ uint2 lds_read_tr16(const char* a) {
+  const v4s t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(
+      (__attribute__((address_space(3))) char*)a));
+  return __builtin_bit_cast(uint2, t);
+}
+__device__ __forceinline__ uint2 vt_half(const char* Vs, int key0, int db, int fr, int fq) {
+  const int krow = key0 + fq * 4 + (fr >> 2);
+  const int dcol = db * 16 + (fr & 3) * 4;                                     // 16-bit index inside the key row
+  return lds_read_tr16(Vs + krow * 128 + tile_swz(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8);
+}
+
+// P fragment (B operand of O^T) of one 32-key chunk from its two score blocks
+__device__ __forceinline__ bf16x8 p_frag(const f32x4& lo, const f32x4& hi) {
+  union { bf16x8 v; uint32_t u[4]; } pf;
+  pf.u[0] = pack_op2(lo[0], lo[1]);
+  pf.u[1] = pack_op2(lo[2], lo[3]);
+  pf.u[2] = pack_op2(hi[0], hi[1]);
+  pf.u[3] = pack_op2(hi[2], hi[3]);
+  return pf.v;
+}
+
+// ---- masks and softmax ----------------------------------------------------------------------------------------------------
+// keys past the last one, one score block: with tl = (keys of this tile) - fq*4, key kb*16 + fq*4 + r is padding iff
+// kb*16 + r >= tl.  The caller loops over the blocks that can hold any (a ladder rung has T > 16*(MAXKB-6)).
+__device__ __forceinline__ f32x4 mask_tail(f32x4 s, int kb, int tl) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (kb * 16 + r >= tl) s[r] = -3.0e38f;
+  return s;
+}
+// the lane's share of a query's row maximum (rows4_max of it = the maximum over all KB*16 keys)
+template <int KB>
+__device__ __forceinline__ float lane_max(const f32x4 (&st)[KB]) {
+  float mx = -3.0e38f;
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kb][r]);      // -> v_max3_f32
+  return mx;
+}
+// <pad> keys of a ragged batch: byte r of f4 is set iff the token of the block's key fq*4 + r is <pad>
+__device__ __forceinline__ f32x4 mask_pad(f32x4 s, uint32_t f4, float fill) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if ((f4 >> (8 * r)) & 0xffu) s[r] = fill;
+  return s;
+}
+// exact (non-online) softmax over a query's KB*16 keys, mx = its lane_max: st <- exp(st - max), returns 1 / sum -- applied to O
+// at the end, the lane's query is also its O column.  exp(s - m) = exp2(s*log2e - m*log2e), two scores per instruction
+// (v_pk_fma_f32 / v_pk_add_f32): 284 instead of 418 VALU instructions per 16-query block at 18 key blocks, 72 of them
+// quarter-rate v_exp_f32
+template <int KB>
+__device__ __forceinline__ float softmax_exact(f32x4 (&st)[KB], float mx) {
+  mx = rows4_max(mx);
+  const f32x2 l2e = {1.44269504088896341f, 1.44269504088896341f};
+  const float mneg1 = -mx * 1.44269504088896341f;
+  const f32x2 mneg = {mneg1, mneg1};
+  f32x2 sum2 = {0.f, 0.f};
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+    const f32x2 a = __builtin_elementwise_fma((f32x2){st[kb][0], st[kb][1]}, l2e, mneg);
+    const f32x2 b = __builtin_elementwise_fma((f32x2){st[kb][2], st[kb][3]}, l2e, mneg);
+    const f32x2 ea = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+    const f32x2 eb = {__builtin_amdgcn_exp2f(b[0]), __builtin_amdgcn_exp2f(b[1])};
+    st[kb] = (f32x4){ea[0], ea[1], eb[0], eb[1]};
+    sum2 += ea;
+    sum2 += eb;
+  }
+  return 1.0f / rows4_sum(sum2[0] + sum2[1]);
+}
+
+// ---- context --------------------------------------------------------------------------------------------------------------
+// the lane's 4 x 4 context values, scaled by inv, as four 8-byte pieces: store(db, piece) puts d = db*16 + fq*4 .. +3
+template <class Store>
+__device__ __forceinline__ void store_ctx(const f32x4 (&o)[4], float inv, Store&& store) {
+#pragma unroll
+  for (int db = 0; db < 4; ++db) {
+    uint2 p;
+    p.x = pack_op2(o[db][0] * inv, o[db][1] * inv);
+    p.y = pack_op2(o[db][2] * inv, o[db][3] * inv);
+    store(db, p);
+  }
+}
+// dst = the query's context row at column h*64 + fq*4
+__device__ __forceinline__ void store_ctx(const f32x4 (&o)[4], float inv, bf16_t* dst) {
+  store_ctx(o, inv, [&](int db, uint2 p) { *(uint2*)(dst + db * 16) = p; });
+}
+
+PG_OPS_END

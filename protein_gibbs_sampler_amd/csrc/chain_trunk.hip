@@ -25,8 +25,8 @@
 //     word, no serialisation: 2.2 us per barrier.
 //
 // Arithmetic.  Every phase is the statement-for-statement arithmetic of the kernel it replaces (gemm_ln_skinny_kernel,
-// gemm_bf16_skinny_kernel<.., 8 waves>, attention_kernel<2>, the 4-way split-K fc2 + splitk_reduce_kernel): the same K split over
-// the 8 waves, the same reduction orders, the same softmax.  The logits are BIT-IDENTICAL with the multi-launch path
+// gemm_bf16_skinny_kernel<.., 8 waves>, the 4-way split-K fc2 + splitk_reduce_kernel; the attention through the very functions
+// of attention_kernel<2>, attn_frag.h): the same K split over the 8 waves, the same reduction orders, the same softmax.  The logits are BIT-IDENTICAL with the multi-launch path
 // (PGIBBS_CHAIN_TRUNK=0); tests/test_gpu_chain_trunk.py compares the two.
 //
 // Work split (d = 1280): QKV 240 units of 16 features, out-proj 80 units, fc1 160 units of 2 x 16 features, fc2 160 units
@@ -40,13 +40,10 @@
 // launches for good and re-runs the call from the caller's intact inputs.
 #include <algorithm>
 
+#include "attn_frag.h"
 #include "gemm_epilogue.h"
-#include "kernels.h"
 
 PG_OPS_BEGIN
-
-typedef short ct_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(2))) float ct_f32x2;
 
 namespace {
 
@@ -422,7 +419,7 @@ __device__ __forceinline__ void ct_attention_unit(char* __restrict__ Vs, const b
     for (int it = 0; it < 4; ++it) {
       const int i = lane + it * 64;
       const int row = i >> 3, c = i & 7;
-      *(uint4*)(Vs + row * 128 + ((c ^ (row & 7)) << 4)) = vreg[it];
+      *(uint4*)(Vs + row * 128 + tile_swz(row, c)) = vreg[it];
     }
   }
   asm volatile("" ::: "memory");               // the V tile is the wave's own: LDS executes a wave's accesses in order, no barrier
@@ -448,7 +445,6 @@ __device__ __forceinline__ void ct_attention_unit(char* __restrict__ Vs, const b
   for (int u = 0; u < 2; ++u) st[u] = mfma_op16(kf[u][0], qf[0], (f32x4){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
   for (int u = 0; u < 2; ++u) st[u] = mfma_op16(kf[u][1], qf[1], st[u]);
-  float mx = -3.0e38f;
   const int tl = T - fq * 4;
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb)
@@ -457,60 +453,25 @@ __device__ __forceinline__ void ct_attention_unit(char* __restrict__ Vs, const b
       for (int r = 0; r < 4; ++r)
         if (kb * 16 + r >= tl) st[kb][r] = -3.0e38f;
     }
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kb][r]);
-  mx = rows4_max(mx);
-  const ct_f32x2 l2e = {1.44269504088896341f, 1.44269504088896341f};
-  const float mneg1 = -mx * 1.44269504088896341f;
-  const ct_f32x2 mneg = {mneg1, mneg1};
-  ct_f32x2 sum2 = {0.f, 0.f};
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-    const ct_f32x2 a = __builtin_elementwise_fma((ct_f32x2){st[kb][0], st[kb][1]}, l2e, mneg);
-    const ct_f32x2 b = __builtin_elementwise_fma((ct_f32x2){st[kb][2], st[kb][3]}, l2e, mneg);
-    const ct_f32x2 ea = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
-    const ct_f32x2 eb = {__builtin_amdgcn_exp2f(b[0]), __builtin_amdgcn_exp2f(b[1])};
-    st[kb] = (f32x4){ea[0], ea[1], eb[0], eb[1]};
-    sum2 += ea;
-    sum2 += eb;
-  }
-  float sum = sum2[0] + sum2[1];
-  sum = rows4_sum(sum);
-  const float inv = 1.0f / sum;
+  const float inv = softmax_exact(st, lane_max(st));
   f32x4 o[4];
-  union VF { bf16x8 v; uint2 h[2]; };
-  VF vb[4];
+  VtFrag vb[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) {
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
+    for (int hh = 0; hh < 2; ++hh) {           // vt_half(Vs, hh * 16, ..) spelled out: through the call this unit's addresses compile differently
       const int krow = hh * 16 + fq * 4 + (fr >> 2);
       const int dcol = db * 16 + (fr & 3) * 4;
-      const char* a = Vs + krow * 128 + (((dcol >> 3) ^ (krow & 7)) << 4) + ((dcol >> 2) & 1) * 8;
-      const ct_v4s t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ct_v4s __attribute__((address_space(3)))*)(
-          (__attribute__((address_space(3))) char*)a));
-      vb[db].h[hh] = __builtin_bit_cast(uint2, t);
+      vb[db].h[hh] = lds_read_tr16(Vs + krow * 128 + tile_swz(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8);
     }
   }
-  union { bf16x8 v; uint32_t u[4]; } pf;
-  pf.u[0] = pack_op2(st[0][0], st[0][1]);
-  pf.u[1] = pack_op2(st[0][2], st[0][3]);
-  pf.u[2] = pack_op2(st[1][0], st[1][1]);
-  pf.u[3] = pack_op2(st[1][2], st[1][3]);
+  const bf16x8 pf = p_frag(st[0], st[1]);
 #pragma unroll
-  for (int db = 0; db < 4; ++db) o[db] = mfma_op16(vb[db].v, pf.v, (f32x4){0.f, 0.f, 0.f, 0.f});
+  for (int db = 0; db < 4; ++db) o[db] = mfma_op16(vb[db].v, pf, (f32x4){0.f, 0.f, 0.f, 0.f});
   const int q = qb * 16 + fr;
   if (q < T) {
     const int dst = ((row0 + q) * ld_ctx + h * 64 + fq * 4) * 2;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      uint2 p;
-      p.x = pack_op2(o[db][0] * inv, o[db][1] * inv);
-      p.y = pack_op2(o[db][2] * inv, o[db][3] * inv);
-      ct_st_dev<uint2>(rc, dst + db * 16 * 2, p);
-    }
+    store_ctx(o, inv, [&](int db, uint2 p) { ct_st_dev<uint2>(rc, dst + db * 16 * 2, p); });
   }
 }
 

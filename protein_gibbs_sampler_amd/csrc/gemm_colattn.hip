@@ -7,20 +7,21 @@
 // column's sequence is only R = 32 ... 256 tokens, though, so with the operand rows in COLUMN-MAJOR order (row (b, c, r): the
 // preceding LayerNorm writes them there, elementwise.hip) one 256-row GEMM tile holds 256 / R whole sequences, and with the
 // weight rows grouped per head ([q_h | k_h | v_h], 192 rows) one 256 x 192 tile holds everything the attention of those sequences
-// and that head needs.  The tile's q, k, v go to LDS as bf16 (three 256 x 64 planes in the layout attention.hip uses), each of
+// and that head needs.  The tile's q, k, v go to LDS as bf16 (three 256 x 64 planes in the tile layout of attn_frag.h), each of
 // the 16 waves runs the attention of one (sequence, 16-query block) from there, and only the context rows leave the CU -- in the
 // ordinary token order, so nothing downstream changes.
 //
 //   * main loop: the 16-wave kernel's (gemm_w16.hip) with a 256 x 192 tile: wave tile 64 x 48, K-steps of 64 in two 56-KB slots
 //     (waves 0-7 stage the 32 activation pieces, waves 8-15 the 24 weight pieces), one s_barrier per K-step; same MFMA, operand
 //     roles and k order as every tile kernel, so q, k, v are the very bf16 values the unfused projection stores.
-//   * attention: attention_kernel's arithmetic, statement for statement (S^T = K.Q^T, exact softmax in registers, P.V through
-//     ds_read_b64_tr_b16) -- the context is bit-identical with the unfused path (tests/test_gpu_msa.py), so fused and unfused
-//     launches can be mixed freely across shards and batch sizes.
+//   * attention: attention_kernel's arithmetic through the same functions (attn_frag.h: S^T = K.Q^T, exact softmax in
+//     registers, P.V through ds_read_b64_tr_b16) -- the context is bit-identical with the unfused path (tests/test_gpu_msa.py),
+//     so fused and unfused launches can be mixed freely across shards and batch sizes.
 //   * depth R in {32, 64, 128, 256} (KB = R / 16 key blocks, a template parameter); other depths, <pad> batches and the strict
 //     mode take the unfused path.
 #include <stdlib.h>
 
+#include "attn_frag.h"
 #include "gemm_epilogue.h"
 
 PG_OPS_BEGIN
@@ -73,8 +74,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
   };
 
   const int fr = lane & 15, fq = lane >> 4;
-  const int foff0 = fr * 128 + ((fq ^ (fr & 7)) << 4);
-  const int foff1 = fr * 128 + (((4 + fq) ^ (fr & 7)) << 4);
+  const int foff0 = tile_addr(fr, fq);
+  const int foff1 = tile_addr(fr, 4 + fq);
   const int xbase = wm * 4 * 2048;
   const int wbase = 32 * 1024 + wn * 3 * 2048;
 
@@ -108,8 +109,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
   }
   __syncthreads();                                        // every wave is done with the operand ring
 
-  // ---- q, k, v of the tile as bf16 into three 256 x 64 planes (rows of 128 B, 16-B chunks XOR-swizzled with row & 7: the K / V
-  // tile layout of attention.hip).  acc[i][j][r] = D[n = wn*48 + i*16 + fq*4 + r][m = wm*64 + j*16 + fr]
+  // ---- q, k, v of the tile as bf16 into three 256 x 64 planes (the K / V tile layout of attn_frag.h).
+  // acc[i][j][r] = D[n = wn*48 + i*16 + fq*4 + r][m = wm*64 + j*16 + fr]
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const int n_loc = wn * 48 + i * 16 + fq * 4;
@@ -121,14 +122,12 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
       uint2 p;
       p.x = pack_op2(acc[i][j][0] + b4.x, acc[i][j][1] + b4.y);
       p.y = pack_op2(acc[i][j][2] + b4.z, acc[i][j][3] + b4.w);
-      *(uint2*)(smem + plane * 32768 + row * 128 + (((d >> 3) ^ (row & 7)) << 4) + (d & 4) * 2) = p;
+      *(uint2*)(smem + plane * 32768 + row * 128 + tile_swz(row, d >> 3) + (d & 4) * 2) = p;
     }
   }
   __syncthreads();
 
   // ---- attention of (sequence s of the tile, query block qb) on wave w = s * KB + qb: attention_kernel's arithmetic ----
-  typedef __attribute__((ext_vector_type(2))) float f32x2;
-  typedef short v4s __attribute__((ext_vector_type(4)));
   const char* Qs = smem;
   const char* Ks = smem + 32768;
   const char* Vs = smem + 65536;
@@ -136,69 +135,28 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
   if (s * KB * 16 >= 256) return;                         // KB = 16: one sequence, all waves busy; never taken otherwise
   const int r0 = s * (KB * 16);                           // first tile row of the sequence
   bf16x8 qf[2];
-  {
-    const int qrow = r0 + qb * 16 + fr;
+  const int qrow = r0 + qb * 16 + fr;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) qf[kk] = *(const bf16x8*)(Qs + qrow * 128 + (((kk * 4 + fq) ^ (qrow & 7)) << 4));
-  }
+  for (int kk = 0; kk < 2; ++kk) qf[kk] = k_frag(Qs, qrow, kk, fq);
   f32x4 st[KB];
 #pragma unroll
-  for (int kb = 0; kb < KB; ++kb) {
-    const int krow = r0 + kb * 16 + fr;
-    st[kb] = mfma_op16(*(const bf16x8*)(Ks + krow * 128 + ((fq ^ (krow & 7)) << 4)), qf[0], (f32x4){0.f, 0.f, 0.f, 0.f});
-  }
+  for (int kb = 0; kb < KB; ++kb) st[kb] = mfma_op16(k_frag(Ks, r0 + kb * 16 + fr, 0, fq), qf[0], (f32x4){0.f, 0.f, 0.f, 0.f});
 #pragma unroll
-  for (int kb = 0; kb < KB; ++kb) {
-    const int krow = r0 + kb * 16 + fr;
-    st[kb] = mfma_op16(*(const bf16x8*)(Ks + krow * 128 + (((4 + fq) ^ (krow & 7)) << 4)), qf[1], st[kb]);
-  }
-  float mx = -3.0e38f;
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kb][r]);
-  mx = rows4_max(mx);
-  const f32x2 l2e = {1.44269504088896341f, 1.44269504088896341f};
-  const float mneg1 = -mx * 1.44269504088896341f;
-  const f32x2 mneg = {mneg1, mneg1};
-  f32x2 sum2 = {0.f, 0.f};
-#pragma unroll
-  for (int kb = 0; kb < KB; ++kb) {
-    const f32x2 a = __builtin_elementwise_fma((f32x2){st[kb][0], st[kb][1]}, l2e, mneg);
-    const f32x2 b = __builtin_elementwise_fma((f32x2){st[kb][2], st[kb][3]}, l2e, mneg);
-    const f32x2 ea = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
-    const f32x2 eb = {__builtin_amdgcn_exp2f(b[0]), __builtin_amdgcn_exp2f(b[1])};
-    st[kb] = (f32x4){ea[0], ea[1], eb[0], eb[1]};
-    sum2 += ea;
-    sum2 += eb;
-  }
-  float sum = sum2[0] + sum2[1];
-  sum = rows4_sum(sum);
-  const float inv = 1.0f / sum;
+  for (int kb = 0; kb < KB; ++kb) st[kb] = mfma_op16(k_frag(Ks, r0 + kb * 16 + fr, 1, fq), qf[1], st[kb]);
+  const float inv = softmax_exact(st, lane_max(st));
 
   f32x4 o[4];
 #pragma unroll
   for (int db = 0; db < 4; ++db) o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int c = 0; c < KB / 2; ++c) {
-    union { bf16x8 v; uint32_t u[4]; } pf;
-    const f32x4 lo = st[2 * c], hi = st[2 * c + 1];
-    pf.u[0] = pack_op2(lo[0], lo[1]);
-    pf.u[1] = pack_op2(lo[2], lo[3]);
-    pf.u[2] = pack_op2(hi[0], hi[1]);
-    pf.u[3] = pack_op2(hi[2], hi[3]);
+    const bf16x8 pf = p_frag(st[2 * c], st[2 * c + 1]);
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
-      union { bf16x8 v; uint2 h2[2]; } vf;
+      VtFrag vf;
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const int krow = r0 + (2 * c + hh) * 16 + fq * 4 + (fr >> 2);
-        const int dcol = db * 16 + (fr & 3) * 4;
-        const char* a = Vs + krow * 128 + (((dcol >> 3) ^ (krow & 7)) << 4) + ((dcol >> 2) & 1) * 8;
-        vf.h2[hh] = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(
-                                                  (__attribute__((address_space(3))) char*)a)));
-      }
-      o[db] = mfma_op16(vf.v, pf.v, o[db]);
+      for (int hh = 0; hh < 2; ++hh) vf.h[hh] = vt_half(Vs, r0 + (2 * c + hh) * 16, db, fr, fq);
+      o[db] = mfma_op16(vf.v, pf, o[db]);
     }
   }
   // the query's token: operand row m' = (b*C + c)*R + r  ->  context row (b*R + r)*C + c (ordinary token order)
@@ -208,14 +166,7 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
     const int rr = (int)(mp - seq * R);
     const int64_t b = seq / C;
     const int cc = (int)(seq - b * C);
-    bf16_t* dst = ctx + ((b * R + rr) * C + cc) * ld_ctx + tile_n * 64 + fq * 4;
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      uint2 p;
-      p.x = pack_op2(o[db][0] * inv, o[db][1] * inv);
-      p.y = pack_op2(o[db][2] * inv, o[db][3] * inv);
-      *(uint2*)(dst + db * 16) = p;
-    }
+    store_ctx(o, inv, ctx + ((b * R + rr) * C + cc) * ld_ctx + tile_n * 64 + fq * 4);
   }
 }
 

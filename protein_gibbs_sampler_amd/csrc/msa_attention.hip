@@ -6,7 +6,7 @@
 //
 // One workgroup = (msa b, head h, NW*16 queries); wave w owns 16 of them.  Pass 1 streams K_r (C x 64) through LDS for
 // r = 0..R-1 and accumulates the S^T blocks of the wave's 16 queries in registers with v_mfma_f32_16x16x32_bf16
-// (the same lane-local layout as attention.hip: a lane holds one query's scores for 4 keys of every 16-key block),
+// (the lane-local layout of attn_frag.h: a lane holds one query's scores for 4 keys of every 16-key block),
 // then one exact softmax; pass 2 streams V_r through LDS the same way (V^T fragments via ds_read_b64_tr_b16) and emits
 // ctx for every row with the same P fragments.
 // Every workgroup of a (msa, head) re-streams all R tiles, so the workgroup is made as wide as the registers allow:
@@ -15,12 +15,9 @@
 // (one for the widest tiles); measured at 64 MSAs x 32 x 257: 1.79 -> 1.31 ms per layer, of which the strided K / V / Q
 // tile loads (128 contiguous bytes per token row) are 0.55 ms and the MFMAs 0.1 ms;
 // the query chunks of one (msa, head) are placed on one XCD so the re-streamed tiles hit its L2.
-#include "kernels.h"
+#include "attn_frag.h"
 
 PG_OPS_BEGIN
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 template <int MAXKB, int NW, int mode>
 __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
@@ -33,7 +30,8 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
   // mode 2: pass 2 over the row chunk rc only with the P fragments of mode 3.
   constexpr int tpad = MAXKB * 16;
   constexpr int NT = NW * 64;                      // threads
-  constexpr int NIT = (tpad * 8 + NT - 1) / NT;    // tile items per thread: one uint4 = 8 d of one key
+  using KRegs = TileRegs<tpad, NT>;                // one row's K (pass 2: V) tile share
+  constexpr int NIT = KRegs::NIT;                  // tile items per thread: one uint4 = 8 d of one key
   constexpr int AHEAD = (MAXKB <= 18 && NIT <= 9) ? 2 : 1;   // rows fetched ahead into registers (register budget)
   constexpr int BUF = tpad * 128;                  // one tile buffer: tpad key rows of 128 B (K_r in pass 1, V_r in pass 2)
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -77,24 +75,19 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
 
   // ---- pass 1: scores summed over rows.  Tile r goes to LDS buffer r & 1; the registers it came from are refilled with
   // row r + 2 right away, so a tile has two rows of MFMAs to arrive.
-  struct KRegs { uint4 k[NIT]; };                    // one row's K tile share
   KRegs kA, kB;
   auto load_k = [&](KRegs& g, int r, int off) {
     const bf16_t* rb = base + (size_t)r * C * ld_qkv;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int i = tid + it * NT, row = i >> 3, c = i & 7;
-      g.k[it] = make_uint4(0, 0, 0, 0);
-      if (i < tpad * 8 && row < C) g.k[it] = *(const uint4*)(rb + (size_t)row * ld_qkv + off + c * 8);
+      g.r[it] = make_uint4(0, 0, 0, 0);
+      if (i < tpad * 8 && row < C) g.r[it] = *(const uint4*)(rb + (size_t)row * ld_qkv + off + c * 8);
     }
   };
   auto score_row = [&](KRegs& g, int r) {
     char* Ks = smem + (r & 1) * BUF;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT, row = i >> 3, c = i & 7;
-      if (i < tpad * 8) *(uint4*)(Ks + row * 128 + ((c ^ (row & 7)) << 4)) = g.k[it];
-    }
+    tile_store(g, tid, Ks);
     const bf16_t* qp = base + ((size_t)r * C + qrow) * ld_qkv + fq * 8;     // in flight across the barrier
     const bf16x8 qf0 = *(const bf16x8*)qp, qf1 = *(const bf16x8*)(qp + 32);
     __syncthreads();                                  // tile r visible; everybody is done with tile r - 1 (other buffer)
@@ -104,11 +97,7 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-        for (int kb = 0; kb < MAXKB; ++kb) {
-          const int krow = kb * 16 + fr;
-          const bf16x8 kf = *(const bf16x8*)(Ks + krow * 128 + (((kk * 4 + fq) ^ (krow & 7)) << 4));
-          st[kb] = mfma_op16(kf, kk ? qf1 : qf0, st[kb]);
-        }
+        for (int kb = 0; kb < MAXKB; ++kb) st[kb] = mfma_op16(k_frag(Ks, kb * 16 + fr, kk, fq), kk ? qf1 : qf0, st[kb]);
       }
     }
   };
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
     sum = rows4_sum(sum);
     const float inv = 1.0f / sum;
   #pragma unroll
-    for (int c = 0; c < MAXKB / 2; ++c) {
+    for (int c = 0; c < MAXKB / 2; ++c) {           // P itself, not exp(s - max): pass 2 stores O as it is
       const f32x4 lo = st[2 * c], hi = st[2 * c + 1];
       pf[c].u[0] = pack_op2(lo[0] * inv, lo[1] * inv);
       pf[c].u[1] = pack_op2(lo[2] * inv, lo[3] * inv);
@@ -196,15 +185,10 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
 
   // ---- pass 2: ctx[r] = P . V_r for every row.  V_r tiles are staged exactly like the K_r tiles (row-major, swizzled,
   // two buffers, fetched AHEAD rows ahead); the V^T fragments of the PV MFMAs come out of them through the transposing
-  // LDS read ds_read_b64_tr_b16 (see attention.hip) -- the former transposition pass was most of this kernel's VALU work.
-  typedef short v4s __attribute__((ext_vector_type(4)));
+  // LDS read (vt_frag) -- the former transposition pass was most of this kernel's VALU work.
   auto apply_row = [&](KRegs& g, int r, int slot) {
     char* Vs = smem + slot * BUF;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * NT, row = i >> 3, c = i & 7;
-      if (i < tpad * 8) *(uint4*)(Vs + row * 128 + ((c ^ (row & 7)) << 4)) = g.k[it];
-    }
+    tile_store(g, tid, Vs);
     __syncthreads();
     if (r + AHEAD < r_hi) load_k(g, r + AHEAD, v_off);
     if (active) {
@@ -215,29 +199,14 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
       for (int c = 0; c < MAXKB / 2; ++c) {
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
-          union { bf16x8 v; uint2 h2[2]; } vf;
+          VtFrag vf;
 #pragma unroll
-          for (int hh = 0; hh < 2; ++hh) {
-            const int krow = (2 * c + hh) * 16 + fq * 4 + (fr >> 2);
-            const int dcol = db * 16 + (fr & 3) * 4;
-            const char* a = Vs + krow * 128 + (((dcol >> 3) ^ (krow & 7)) << 4) + ((dcol >> 2) & 1) * 8;
-            vf.h2[hh] = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(
-                                                      (__attribute__((address_space(3))) char*)a)));
-          }
+          for (int hh = 0; hh < 2; ++hh) vf.h[hh] = vt_half(Vs, (2 * c + hh) * 16, db, fr, fq);
           o[db] = mfma_op16(vf.v, pf[c].v, o[db]);
         }
       }
       const int q = q0 + fr;
-      if (q < C) {
-        bf16_t* dst = ctx + ((size_t)(b * R + r) * C + q) * ld_ctx + h * 64 + fq * 4;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-          uint2 p;
-          p.x = pack_op2(o[db][0], o[db][1]);
-          p.y = pack_op2(o[db][2], o[db][3]);
-          *(uint2*)(dst + db * 16) = p;
-        }
-      }
+      if (q < C) store_ctx(o, 1.0f, ctx + ((size_t)(b * R + r) * C + q) * ld_ctx + h * 64 + fq * 4);
     }
   };
   __syncthreads();                                    // pass 1's last tile (either buffer) fully consumed
@@ -264,29 +233,24 @@ static void row_split_geometry(int n_bh, int obh, int R, int C, int& nw, int& n_
     if (n_rc > R / 4) n_rc = R / 4;
     if (n_rc < 1) n_rc = 1;
   }
-  // a rung for every even block count (round 4; PGIBBS_ATTN_LADDER=0: the coarse ladder 2 4 8 12 18 24 30 36): the key blocks beyond C
-  // are zero-filled and masked -- exact zeros in every sum, so the rung does not change the bits, only the wasted work
+  // a rung for every even block count (round 4; PGIBBS_ATTN_LADDER=0: the coarse ladder only -- same bits, attn_frag.h)
   static const int fine = env_int("PGIBBS_ATTN_LADDER", 1);
-  static const int kbs_fine[] = {2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 30, 32, 34, 36};
-  static const int kbs_coarse[] = {2, 4, 8, 12, 18, 24, 30, 36};
-  const int* kbs = fine ? kbs_fine : kbs_coarse;
-  const int n_kbs = fine ? 18 : 8;
-  kb = 36;
-  for (int i = 0; i < n_kbs; ++i)
-    if (C <= kbs[i] * 16) { kb = kbs[i]; break; }
+  kb = attention_rung(C, fine);
   // One exception, measured (profiles/r04_attention_key_block_ladder_ab.txt): one template of 32 x 301 (288 workgroups, split-R form)
   // takes 0.97 ms on the 20-block rung against 0.88 on the 24-block one, while bigger grids gain 10 %.  (The 20-block rung's 80 KB of
   // LDS lets two workgroups share a CU; whether that is the cause was not established.)  Grids below two rounds stay on 24 blocks.
   if (kb == 20 && (long)n_bh * n_qblk * n_rc < 512) kb = 24;
-  (void)n_bh;
+}
+// fp32 scratch of the split-R form: n_rc partial score maps per (msa, head), then every wave's P fragments (1 KiB each)
+static size_t row_split_bytes(int n_bh, int C, int nw, int n_qblk, int n_rc, int kb) {
+  return (size_t)n_bh * n_rc * C * (kb * 16) * 4 + (size_t)n_bh * n_qblk * nw * (kb / 2) * 1024;
 }
 // bytes of fp32 scratch the split-R form needs for B alignments (0: the shape does not split)
 size_t msa_row_split_scratch_bytes(int B, int R, int C, int H, int order_bh) {
   if (C > 576) return 0;
   int nw, n_qblk, n_rc, kb;
   row_split_geometry(B * H, order_bh > 0 ? order_bh : B * H, R, C, nw, n_qblk, n_rc, kb);
-  if (n_rc <= 1) return 0;
-  return (size_t)B * H * n_rc * C * (kb * 16) * 4 + (size_t)B * H * n_qblk * nw * (kb / 2) * 1024;
+  return n_rc <= 1 ? 0 : row_split_bytes(B * H, C, nw, n_qblk, n_rc, kb);
 }
 
 int launch_msa_row_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int R, int C, int H, int ld_qkv,
@@ -302,13 +266,12 @@ int launch_msa_row_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx,
   // order_bh -- the (msa, head) count of the JOB, or of ONE template in a batched generate_single -- not from this call's share
   int nw, n_qblk, n_rc, kb_;
   row_split_geometry(n_bh, order_bh > 0 ? order_bh : n_bh, R, C, nw, n_qblk, n_rc, kb_);
-  if (!partial) n_rc = 1;
+  if (!partial || (n_rc > 1 && row_split_bytes(n_bh, C, nw, n_qblk, n_rc, kb_) > partial_bytes)) n_rc = 1;
 #define PG_ROWATT_K(KB, NWV, MODE, GRID, BLOCK)                                                                          \
   hipLaunchKernelGGL((msa_row_attention_kernel<KB, NWV, MODE>), GRID, BLOCK, 0, s, qkv, ctx, R, C, H, ld_qkv, ld_ctx,     \
                      k_off, v_off, scale, n_qblk, n_bh, n_rc, partial)
 #define PG_ROWATT(KB, NWV)                                                                                              \
   else if (kb_ == KB) {                                                                                                 \
-    if (n_rc > 1 && (size_t)n_bh * n_rc * C * (KB * 16) * 4 + (size_t)n_bh * n_qblk * nw * (KB / 2) * 1024 > partial_bytes) n_rc = 1; \
     const dim3 block(NWV * 64), grid((unsigned)(n_bh * n_qblk * n_rc));                                                 \
     if (n_rc == 1) {                                                                                                    \
       PG_ROWATT_K(KB, NWV, 0, grid, block);                                                                             \

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Tied row attention: K_r / V_r tiles by LDS-DMA into a three-buffer ring (PGIBBS_MSA_ROW_DMA=1, round 5) against the register-staged
-# tiles (=0).  Needs tools/probes/msa_row_attention_lds_dma.patch applied to csrc/msa_attention.hip (the variant lost and was taken
+# tiles (=0).  Needs tools/probes/msa_row_attention_lds_dma.patch applied to csrc/msa_attention.hip as of round 5 (it does not apply to the
+# kernel since its tile and fragment code moved to csrc/attn_frag.h; the variant lost and was taken
 # out of the library: profiles/r05_msa_row_attention_lds_dma_ab.txt).  (1) logits of an MSA forward bit for bit, several shapes incl. the split-R form; (2) configs 4 and 5, interleaved.
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; cd $ROOT
 cat > /tmp/rowdma_logits.py <<PY
