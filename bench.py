@@ -17,14 +17,18 @@ Multi-GPU (BASELINE config 3): the SAME 256 chains split contig
 [g*256/N, (g+1)*256/N) -- "scaling": "strong".  Chains never interact, so there is no data-path collective; the only
 collective is one RCCL all-gather of the final token buffers.  Every rank derives its slice of the position table from the
 one CPython-exact stream and token draws are keyed by global chain id, so the gathered result is bit-identical to the
-N = 1 result: rank 0 re-runs the whole job on its own GPU after the timed region and asserts that (`verified_vs_single_gpu`).
+N = 1 result: with `--full` rank 0 re-runs the whole job on its own GPU after the timed region and asserts that
+(`verified_vs_single_gpu`).
 `--weak` keeps 256 chains per GPU instead.
 
 `--dump-outputs DIR` writes what the last timed step handed back -- the token buffer, and that step's logits and draws at the
 sampled positions -- as DIR/<name>.npy (float32) after the timed region.  Every input is seeded (seeds, weights, position stream,
 draws), so equal arguments give equal inputs and two builds can be compared array for array.
 
-Output: ONE JSON line (rank 0) with the driver's contract plus
+Output: ONE JSON line (rank 0): `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the run's configuration.
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` if asked and prints that line -- nothing else runs, so
+the headline figure costs no more than it needs.
+`--full` runs every other leg and check after the timed region (each has a `--no-*` option there) and adds to the line
   roofline     -- the GEMM kernel family (96.5 % of the FLOPs): executed FLOPs / HIP-event time on the engine's stream
   strict_mode  -- (N = 1) the same workload in the parity mode (PG_PREC_FP32: split-bf16 x3 GEMMs and attention): its
                   positions/s and its measured max |logit error| against the fp32 oracle -- the mode north_star's 1e-3
@@ -61,6 +65,11 @@ def parse_args(argv=None):
     ap.add_argument("--weak", action="store_true", help="weak scaling: 256 chains PER GPU instead of 256 in total")
     ap.add_argument("--chains", type=int, default=TOTAL_CHAINS, help="chains in total (per GPU with --weak)")
     ap.add_argument("--length", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every leg and check around the headline: host-buffer entry, roofline, "
+                         "shard proxy, strict and fp16 modes, config 1, CPU baseline and logit check, ESM-MSA-1b; N > 1: the "
+                         "single-GPU re-run and the C-ABI gather.  The --no-* options and --native-gather choose among them and "
+                         "mean nothing without it")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"],
                     help="mode of the timed run: bf16 = throughput mode (the headline), fp16 = the same kernels with fp16 operands, "
                          "fp32 = strict parity mode")
@@ -95,7 +104,12 @@ def parse_args(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="N = 1: still create the torch.distributed process group (world_size 1) and run the final all-gather "
                          "through it, so that the RCCL path is executed on a single GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:              # a plain run: the headline and nothing else -- every leg after the timed steps is off
+        args.no_verify = args.no_cpu_baseline = args.no_roofline = args.no_strict = args.no_fp16 = args.no_host_entry = True
+        args.no_msa = args.no_shard_proxy = args.no_native_gather = True
+        args.native_gather = False
+    return args
 
 
 def self_launch(args):
@@ -527,6 +541,7 @@ def main():
         assert random_ok, "gather changed the chain order"
         out["verified_vs_single_gpu"] = random_ok
 
+    # ==== from here to the printed line: the legs and checks of --full (parse_args switches all of them off in a plain run) ====
     # ---- N = 1: the same job through the HOST-buffer entry point (pg_esm_gibbs_run: tokens and position table cross PCIe inside
     # the call, the tokens come back) -- the PCIe-inclusive rate; never `value`.  W + K iterations in one call from the initial
     # tokens: the result must equal the device-pointer job's tokens bit for bit.

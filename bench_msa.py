@@ -8,8 +8,8 @@ config 5: generate_single shape -- depth 128 x L=512 (C=513), steps=10, passes=3
           "batch=32 templates sharded over 8 x MI355X" = 4 templates per GPU: the templates of one GPU go through
           ESM_MSA_sampler.generate_single_batch as ONE native call (pg_msa_gibbs_single_batch_run, 4 MSAs per forward);
           `--templates 1` is the reference's own shape, one template per call (esm_msa_sampler.py:125).
-The headline metric of the repo is bench.py (config 2), which embeds both results under "msa" at N = 1 (run_config4 /
-run_config5 below are what it calls); stand-alone this script prints one JSON line per config.
+The headline metric of the repo is bench.py (config 2), whose `--full` run embeds both results under "msa" at N = 1
+(run_config4 / run_config5 below are what it calls); stand-alone this script prints one JSON line per config.
 """
 import argparse
 import ctypes

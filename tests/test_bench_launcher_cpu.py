@@ -61,6 +61,20 @@ def test_cpu_baseline_leg_and_traffic_file_selection():
     assert out["config1"]["cpu_ms_per_iter"] > 0 and out["reference_style_position_loop"]["us_per_position_one_core"] > 0
 
 
+def test_full_switches_the_legs_on_and_a_plain_run_has_none():
+    """Without `--full` every leg after the timed steps is off, whatever else is asked; with it each `--no-*` option skips its own."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = ("verify", "cpu_baseline", "roofline", "strict", "fp16", "host_entry", "msa", "shard_proxy", "native_gather")
+    for argv in ([], ["--gpus", "1", "--steps", "3", "--warmup", "1"], ["--native-gather"]):
+        a = bench.parse_args(argv)
+        assert not a.full and not a.native_gather and all(getattr(a, "no_" + leg) for leg in legs), argv
+    a = bench.parse_args(["--full"])
+    assert a.full and not any(getattr(a, "no_" + leg) for leg in legs)
+    a = bench.parse_args(["--full", "--no-msa", "--native-gather"])
+    assert a.no_msa and a.native_gather and not a.no_strict
+
+
 def test_dump_outputs_writes_the_final_tokens_once_and_reproducibly(tmp_path):
     """`--dump-outputs DIR`: rank 0 alone writes DIR/tokens.npy (float32, [chains, L + 2]); the inputs are seeded, so a second run --
     here with another number of ranks -- writes the same array.  (A dry run never touches the tokens: they are the seeds.)"""

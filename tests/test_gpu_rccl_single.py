@@ -1,5 +1,5 @@
 """RCCL executed on the one GPU a test box has: a world_size-1 `nccl` process group runs init, all-reduce, both forms of the
-product's all-gather on device tensors and `sharding.run_sharded` through the real engine; `bench.py --gpus 1 --force-dist`
+product's all-gather on device tensors and `sharding.run_sharded` through the real engine; `bench.py --full --gpus 1 --force-dist`
 runs the benchmark's N > 1 code path (gather + max-over-ranks + bit-equality check) on backend "nccl".  Child processes: a
 process group is process-global state."""
 import json
@@ -29,7 +29,7 @@ def test_rccl_world_size_one_collectives_and_run_sharded():
 
 
 def test_bench_single_gpu_through_rccl():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1",
                         "--layers", "2", "--no-cpu-baseline", "--no-strict", "--no-msa", "--no-roofline", "--native-gather"], capture_output=True,
                        text=True, env=_env(), timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

@@ -12,7 +12,7 @@ for st in 8000 20000 40000; do
 done
 cat $O/gemm_stagger.txt
 for mode in pp r2 pp r2; do
-  PGIBBS_GEMM_RESID=$mode python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-strict --no-msa > $O/bench_$mode.json 2> $O/bench_$mode.err
+  PGIBBS_GEMM_RESID=$mode python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-strict --no-msa > $O/bench_$mode.json 2> $O/bench_$mode.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench_$mode.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/r04d; mkdir -p $O
 python -m pytest tests/test_gpu_strict_kernels.py -x -q > $O/test_strict.txt 2>&1; tail -3 $O/test_strict.txt
 for nqb in 1 3 5 1 5; do
-  PGIBBS_ATTN_F32_NQB=$nqb python bench.py --precision fp32 --steps 3 --warmup 1 --no-cpu-baseline --no-msa > $O/strict_nqb$nqb.json 2> $O/strict.err
+  PGIBBS_ATTN_F32_NQB=$nqb python bench.py --full --precision fp32 --steps 3 --warmup 1 --no-cpu-baseline --no-msa > $O/strict_nqb$nqb.json 2> $O/strict.err
   python - <<PY
 import json
 d=json.loads(open("$O/strict_nqb$nqb.json").read().strip().splitlines()[-1])
@@ -12,7 +12,7 @@ print("strict nqb=$nqb", round(d["ms_per_step"],2), d.get("time_split_ms_per_ite
 PY
 done
 for p in bf16 fp16 bf16 fp16; do
-  python bench.py --precision $p --steps 10 --warmup 3 --no-cpu-baseline --no-msa --no-strict --no-fp16 > $O/ab_$p.json 2> $O/ab.err
+  python bench.py --full --precision $p --steps 10 --warmup 3 --no-cpu-baseline --no-msa --no-strict --no-fp16 > $O/ab_$p.json 2> $O/ab.err
   python - <<PY
 import json
 d=json.loads(open("$O/ab_$p.json").read().strip().splitlines()[-1])

@@ -26,7 +26,7 @@ case "$1" in
       PGIBBS_ROWLN_POP=1 PGIBBS_ROWLN_BENCH_ABL=$abl python tools/rowln_bench.py 2>&1 | grep -v amdgpu | sed -n 2,2p
     done | tee $O/rowln_epilogue_ablation.txt ;;
   ab)              # profiles/r06_shard_proxy_ladder_ab.txt, r06_msa_cfg4_rowln_ab.txt: the two kernels in the engine, interleaved
-    B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-strict --no-fp16 --no-msa --no-host-entry"
+    B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-strict --no-fp16 --no-msa --no-host-entry"
     for i in 1 2; do
       PGIBBS_GEMM_LADDER=1 $B > $O/proxy_ladder_on_$i.json; $B > $O/proxy_ladder_off_$i.json
       PGIBBS_ROWLN=1 python bench_msa.py --config 4 --steps 3 --warmup 1 > $O/cfg4_rowln1_$i.json; python bench_msa.py --config 4 --steps 3 --warmup 1 > $O/cfg4_rowln0_$i.json

@@ -23,7 +23,7 @@ if "--engine" in sys.argv:
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = None
     for chains in (256, 128, 64, 32):
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--chains", str(chains), "--steps", "10", "--warmup", "2",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--chains", str(chains), "--steps", "10", "--warmup", "2",
                               "--no-cpu-baseline", "--no-strict", "--no-msa"], capture_output=True, text=True)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         if not line:
