@@ -117,6 +117,8 @@ SIGNATURES = [
     ("pg_dbg_layernorm_operand", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),
     ("pg_dbg_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int]),
     ("pg_dbg_rope", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int]),
+    ("pg_dbg_attention_hd", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),
+    ("pg_dbg_rope_hd", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int]),
     ("pg_dbg_msa_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float]),
 ]
 

@@ -815,21 +815,35 @@ int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float
 }
 
 int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, int B, int T, int H) {
+  return pg_dbg_attention_hd(device, precision, qkv, ctx, B, T, H, 64, nullptr, -1);
+}
+
+/* pg_dbg_attention with the head dimension (64 or 32) and, optionally, the tokens of the keys: key_tok[B][T], keys whose token is
+ * pad_idx are masked as in a ragged batch (NULL: none) */
+int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+                        const int32_t* key_tok, int pad_idx) {
   if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
   if (!qkv || !ctx || B < 1 || T < 1 || H < 1) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
+  if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32");
   DeviceGuard g(-1);
   int rc = dbg_device(device);
   if (rc) return rc;
-  const int d = H * 64;
+  const int d = H * head_dim;
   const int64_t M = (int64_t)B * T;
   Tmp t;
   float* dq = (float*)t.get((size_t)M * 3 * d * 4);
+  int32_t* dtok = nullptr;
+  if (key_tok) {
+    dtok = (int32_t*)t.get((size_t)M * 4);
+    if (!dtok) return fail(PG_ERR_HIP, "hipMalloc failed");
+    PG_HIP(hipMemcpy(dtok, key_tok, (size_t)M * 4, hipMemcpyHostToDevice));
+  }
   if (precision == PG_PREC_FP32) {
     bf16_t* c3 = (bf16_t*)t.get((size_t)M * 3 * d * 2);
     if (!dq || !c3) return fail(PG_ERR_HIP, "hipMalloc failed");
     PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
     const SeqLayout chain = {1, T, 0, 1};
-    if ((rc = launch_attention_f32(nullptr, dq, c3, d, B, T, H, 3 * d, 3 * d, d, 2 * d, chain))) return rc;
+    if ((rc = launch_attention_f32(nullptr, dq, c3, d, B, T, H, 3 * d, 3 * d, d, 2 * d, chain, dtok, pad_idx, nullptr, head_dim))) return rc;
     return split3_rows_to_host(c3, ctx, M, d);
   }
   bf16_t* bq = (bf16_t*)t.get((size_t)M * 3 * d * 2);
@@ -838,7 +852,7 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
   if (!dq || !bq || !bc || !dc) return fail(PG_ERR_HIP, "hipMalloc failed");
   PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
   if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
-  if ((rc = OPS(launch_attention_bf16, nullptr, bq, bc, B, T, H, 3 * d, d, d, 2 * d, nullptr, -1))) return rc;
+  if ((rc = OPS(launch_attention_bf16, nullptr, bq, bc, B, T, H, 3 * d, d, d, 2 * d, dtok, pad_idx, nullptr, head_dim))) return rc;
   if ((rc = OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(ctx, dc, (size_t)M * d * 4, hipMemcpyDeviceToHost));
@@ -876,14 +890,20 @@ int pg_dbg_layernorm_operand(int device, int precision, const float* x, const fl
 /* ESM-2's rotary embedding on a host fp32 buffer qkv[B*T][3*H*64]: the q and k thirds rotated in place (row r at position r % T),
  * v left alone.  16-bit modes: through a device buffer of that type, the result widened back */
 int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
+  return pg_dbg_rope_hd(device, precision, qkv, B, T, H, 64);
+}
+
+/* pg_dbg_rope with the head dimension: 64 (H <= 40) or 32 (H <= 32) */
+int pg_dbg_rope_hd(int device, int precision, float* qkv, int B, int T, int H, int head_dim) {
   if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
-  if (!qkv || B < 1 || T < 1 || H < 1 || H > 40) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32");
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 64 ? 40 : 32)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
   DeviceGuard g(-1);
   int rc = dbg_device(device);
   if (rc) return rc;
-  const int d = H * 64;
+  const int d = H * head_dim;
   const int64_t M = (int64_t)B * T, n = M * 3 * d;
-  const std::vector<float> tab = rope_table(T);
+  const std::vector<float> tab = rope_table(T, head_dim);
   Tmp t;
   float* dq = (float*)t.get((size_t)n * 4);
   float* dtab = (float*)t.get(tab.size() * 4);
@@ -892,10 +912,10 @@ int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
   PG_HIP(hipMemcpy(dq, qkv, (size_t)n * 4, hipMemcpyHostToDevice));
   PG_HIP(hipMemcpy(dtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
   if (precision == PG_PREC_FP32) {
-    if ((rc = launch_rope(nullptr, dq, true, dtab, T, M, T, H, 3 * d))) return rc;
+    if ((rc = launch_rope(nullptr, dq, true, dtab, T, M, T, H, 3 * d, head_dim))) return rc;
   } else {
     if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, n, 1.f))) return rc;
-    if ((rc = OPS(launch_rope, nullptr, bq, false, dtab, T, M, T, H, 3 * d))) return rc;
+    if ((rc = OPS(launch_rope, nullptr, bq, false, dtab, T, M, T, H, 3 * d, head_dim))) return rc;
     if ((rc = OPS(launch_bf16_to_f32, nullptr, bq, dq, n))) return rc;
   }
   PG_HIP(hipDeviceSynchronize());

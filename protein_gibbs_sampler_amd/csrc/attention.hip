@@ -1,9 +1,10 @@
 // Fused multi-head self-attention for one sequence per workgroup (ESM-1b layers):
-//   ctx[b, t, h*64:(h+1)*64] = softmax_j( q[b,t,h] . k[b,j,h] ) @ v[b,:,h]        (q pre-scaled by 64^-0.5)
+//   ctx[b, t, h*HD:(h+1)*HD] = softmax_j( q[b,t,h] . k[b,j,h] ) @ v[b,:,h]        (q pre-scaled by HD^-0.5)
 // This is the attention inside fair-esm's ProteinBertModel that the reference reaches through
 // `self.model.model(batch)["logits"]` (/root/reference/src/pgen/esm_sampler.py:223).
 //
-// CDNA4 mapping (head dim is 64 in ESM-1b and MSA-1b):
+// CDNA4 mapping, written for head dim HD = 64 (ESM-1b, MSA-1b, ESM-2 650M / 3B); HD = 32 (ESM-2 150M) is the same kernel with half
+// the LDS row, one score MFMA per key block and two output blocks (attn_frag.h):
 //   * grid = B*H workgroups of 4 waves; K and V (both row-major, XOR-swizzled 16-B chunks) live in LDS for
 //     the whole sequence (T <= 576: 2 x 72 KB) and are shared by all query blocks; longer sequences use
 //     attention_long_kernel (288-key tiles, online softmax).
@@ -45,15 +46,23 @@ __device__ unsigned long long* pg_att_prof;      // [workgroup][wave][8 slots][8
 // split_from + u / split -- so that the partial last round of a launch (a 32-chain shard: 640 pairs on 512 resident workgroups =
 // one full round + a quarter-full one that takes as long) becomes short workgroups that fill the chip.  A query block's arithmetic
 // does not depend on which workgroup runs it: same bits.  The plain launch (SPLIT = false) is the kernel of rounds 1-5, unchanged.
-template <int MAXKB, bool PADMASK, bool BIASKV = false, bool SPLIT = false>
-__global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
+// HD: the head dimension, 64 or 32 (attn_frag.h).  At 32 a key is 64 bytes of LDS, K + V of 576 keys 72 KB: at least two
+// workgroups per CU on every rung (what limits a rung is the score row in registers, 4 VGPRs per key block, not the LDS -- which is
+// also why the whole-sequence kernel still ends at 576 keys).  The plain and SPLIT head-32 forms compile to <= 128 VGPRs up to 20 key
+// blocks and <= 168 up to 26 without a tighter bound, so four / three workgroups are resident there (attention_resident32: what the
+// host's split of a partial last round counts with; DESIGN 10 has the table).
+constexpr int attention_occupancy(int maxkb, int hd) { return hd == 64 ? (maxkb <= 18 ? 2 : 1) : 2; }
+constexpr int attention_resident32(int kb) { return kb <= 20 ? 4 : (kb <= 26 ? 3 : 2); }
+template <int MAXKB, bool PADMASK, bool BIASKV = false, bool SPLIT = false, int HD = 64>
+__global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
                                                        int H, int ld_qkv_, int ld_ctx_, int k_off, int v_off,
                                                        SeqLayout sl, const int32_t* __restrict__ key_tok, int pad_idx,
                                                        const bf16_t* __restrict__ bias_kv, int split_from = 0, int split = 1) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * MAXKB * 16 * 128 + (PADMASK ? MAXKB * 16 : 0)];
+  constexpr int ROW = HD * 2, NKK = HD / 32, NDB = HD / 16;      // bytes per key in LDS, score MFMAs per key block, 16-wide output blocks
+  __shared__ __attribute__((aligned(16))) char smem[2 * MAXKB * 16 * ROW + (PADMASK ? MAXKB * 16 : 0)];
   char* Ks = smem;
-  char* Vs = smem + MAXKB * 16 * 128;          // V rows, same layout as K (tile_addr)
-  char* padf = smem + 2 * MAXKB * 16 * 128;    // PADMASK: one byte per key, 1 = this key's token is <pad>
+  char* Vs = smem + MAXKB * 16 * ROW;          // V rows, same layout as K (tile_addr)
+  char* padf = smem + 2 * MAXKB * 16 * ROW;    // PADMASK: one byte per key, 1 = this key's token is <pad>
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   PG_T(7, 0);
@@ -69,7 +78,7 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
   const int seq = pair / H, h = pair % H;
   const size_t row0 = (size_t)(seq / sl.inner_count) * sl.outer_rows + (size_t)(seq % sl.inner_count) * sl.inner_rows;
   const size_t ld_qkv = (size_t)ld_qkv_ * sl.row_step, ld_ctx = (size_t)ld_ctx_ * sl.row_step;
-  const bf16_t* base = qkv + row0 * ld_qkv_ + h * 64;
+  const bf16_t* base = qkv + row0 * ld_qkv_ + h * HD;
   // ESM-1 (add_bias_kv): key T is the learned bias_k / bias_v of this head -- one more key, attended by every query, never masked
   const int Tk = T + (BIASKV ? 1 : 0);
   // All MAXKB key blocks are computed unconditionally: K rows / V^T columns past T are zero-filled and
@@ -77,7 +86,7 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
   constexpr int nkc = MAXKB / 2;
 
   // ---- stage K and V (swizzled rows)
-  stage_kv<MAXKB * 16, 256, BIASKV>(Ks, Vs, tid, base, ld_qkv, k_off, v_off, 0, T, bias_kv + h * 64, bias_kv + (H + h) * 64);
+  stage_kv<MAXKB * 16, 256, BIASKV, HD>(Ks, Vs, tid, base, ld_qkv, k_off, v_off, 0, T, bias_kv + h * HD, bias_kv + (H + h) * HD);
   if (PADMASK) {
     // the <pad> flags of the sequence's keys, once per workgroup (read per key inside the score loop they were 72 dependent global
     // loads per lane and query block: 292 bytes of scratch, a ragged batch's attention 5x the time of a full one)
@@ -92,12 +101,12 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
   const int nqb = (T + 15) >> 4;  // query blocks of 16
   // Q fragment (MFMA B operand): query fr, d = kk*32 + fq*8 .. +7; the next block's fragment is prefetched while
   // the current one is computed (a wave has nothing else to cover a global round trip with)
-  bf16x8 qf[2], qn[2];
-  auto load_q = [&](int qb, bf16x8 (&dst)[2]) {
+  bf16x8 qf[NKK], qn[NKK];
+  auto load_q = [&](int qb, bf16x8 (&dst)[NKK]) {
     int qrow = qb * 16 + fr;
     if (qrow >= T) qrow = T - 1;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) dst[kk] = *(const bf16x8*)(base + (size_t)qrow * ld_qkv + kk * 32 + fq * 8);
+    for (int kk = 0; kk < NKK; ++kk) dst[kk] = *(const bf16x8*)(base + (size_t)qrow * ld_qkv + kk * 32 + fq * 8);
   };
   if (qb_first < nqb) load_q(qb_first, qf);
   for (int qb = qb_first; qb < nqb; qb += qb_step) {
@@ -110,18 +119,18 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
       // K fragments are fetched one chunk (CH key blocks) ahead of the MFMAs that use them: with 2 waves per SIMD
       // the LDS latency must be covered inside the wave (PMC: 44 % of wave cycles were s_waitcnt before this)
       constexpr int CH = (MAXKB % 6 == 0) ? 6 : (MAXKB % 4 == 0 ? 4 : 2);
-      bf16x8 kbuf[2][CH][2];
-      auto load_chunk = [&](int ch, bf16x8 (&dst)[CH][2]) {
+      bf16x8 kbuf[2][CH][NKK];
+      auto load_chunk = [&](int ch, bf16x8 (&dst)[CH][NKK]) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
 #if defined(PG_ATT_PROF) && PG_ATT_ABL == 1      /* ablation: one K fragment read per chunk instead of CH */
           const int krow = (ch * CH + (u > 0 ? 0 : u)) * 16 + fr;
-          if (u > 0) { dst[u][0] = dst[0][0]; dst[u][1] = dst[0][1]; continue; }
+          if (u > 0) { for (int kk = 0; kk < NKK; ++kk) dst[u][kk] = dst[0][kk]; continue; }
 #else
           const int krow = (ch * CH + u) * 16 + fr;
 #endif
 #pragma unroll
-          for (int kk = 0; kk < 2; ++kk) dst[u][kk] = k_frag(Ks, krow, kk, fq);
+          for (int kk = 0; kk < NKK; ++kk) dst[u][kk] = k_frag<HD>(Ks, krow, kk, fq);
         }
       };
       load_chunk(0, kbuf[0]);
@@ -130,13 +139,16 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
         if (ch + 1 < MAXKB / CH) load_chunk(ch + 1, kbuf[(ch + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
         // the two d-halves of a key block as two sweeps over the chunk, so that no MFMA is issued right behind the one
-        // producing its accumulator input (hipcc otherwise pairs them through one temporary register)
+        // producing its accumulator input (hipcc otherwise pairs them through one temporary register); at head 32 one MFMA
+        // contracts the whole head and there is a single sweep
 #pragma unroll
         for (int u = 0; u < CH; ++u)
           st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][0], qf[0], (f32x4){0.f, 0.f, 0.f, 0.f});
+        if constexpr (NKK == 2) {
 #pragma unroll
-        for (int u = 0; u < CH; ++u)
-          st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][1], qf[1], st[ch * CH + u]);
+          for (int u = 0; u < CH; ++u)
+            st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][1], qf[1], st[ch * CH + u]);
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -167,20 +179,20 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
     PG_T(qb >> 2, 2);
 
     // O^T[d][q] = sum_key V^T[d][key] * P^T[key][q]
-    f32x4 o[4];
+    f32x4 o[NDB];
 #pragma unroll
-    for (int db = 0; db < 4; ++db) o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int db = 0; db < NDB; ++db) o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
     {
       // V^T fragments fetched two 32-key chunks ahead of the PV MFMAs
-      VtFrag vbuf[3][4];
-      auto load_v = [&](int c, VtFrag (&dst)[4]) {
+      VtFrag vbuf[3][NDB];
+      auto load_v = [&](int c, VtFrag (&dst)[NDB]) {
 #pragma unroll
-        for (int db = 0; db < 4; ++db) {
+        for (int db = 0; db < NDB; ++db) {
 #if defined(PG_ATT_PROF) && PG_ATT_ABL == 2      /* ablation: one V^T fragment read per chunk instead of 4 */
           if (db > 0) { dst[db] = dst[0]; continue; }
 #endif
 #pragma unroll
-          for (int hh = 0; hh < 2; ++hh) dst[db].h[hh] = vt_half(Vs, (2 * c + hh) * 16, db, fr, fq);
+          for (int hh = 0; hh < 2; ++hh) dst[db].h[hh] = vt_half<HD>(Vs, (2 * c + hh) * 16, db, fr, fq);
         }
       };
       load_v(0, vbuf[0]);
@@ -191,16 +203,16 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
         const bf16x8 pf = p_frag(st[2 * c], st[2 * c + 1]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int db = 0; db < 4; ++db) o[db] = mfma_op16(vbuf[c % 3][db].v, pf, o[db]);
+        for (int db = 0; db < NDB; ++db) o[db] = mfma_op16(vbuf[c % 3][db].v, pf, o[db]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     PG_T(qb >> 2, 3);
     // store: lane holds O[q = qb*16 + fr][d = db*16 + fq*4 + r]
     const int q = qb * 16 + fr;
-    if (q < T) store_ctx(o, inv, ctx + row0 * ld_ctx_ + (size_t)q * ld_ctx + h * 64 + fq * 4);
+    if (q < T) store_ctx(o, inv, ctx + row0 * ld_ctx_ + (size_t)q * ld_ctx + h * HD + fq * 4);
     qf[0] = qn[0];
-    qf[1] = qn[1];
+    if constexpr (NKK == 2) qf[1] = qn[1];
     PG_T(qb >> 2, 4);
   }
   PG_T(7, 3);
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(256, (MAXKB <= 18 ? 2 : 1)) void attention_kernel(c
 // MAXKB = 16-key blocks per tile (even), OCC = workgroups per CU the register / LDS budget is set for: <18, 2> is the long-sequence
 // kernel.  <10, 4> (160-key tiles, four workgroups per CU, 117 VGPRs) and <12, 3> were measured at config 2 in round 4 against
 // attention_kernel: 9.1 / 11.1 ms per iteration against 7.0 (EXPERIMENTS.md) -- every 64-query workgroup re-stages the head's K / V.
-template <int MAXKB, int OCC, bool PADMASK, bool BIASKV>
+template <int MAXKB, int OCC, bool PADMASK, bool BIASKV, int HD = 64>
 __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
                                                                int H, int ld_qkv_, int ld_ctx_, int k_off, int v_off,
                                                                SeqLayout sl, int n_qchunk, const int32_t* __restrict__ key_tok_,
@@ -225,36 +237,37 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
   const int32_t* __restrict__ key_tok = PADMASK ? key_tok_ : nullptr;
   const bf16_t* __restrict__ bias_kv = BIASKV ? bias_kv_ : nullptr;
   constexpr int tpad = MAXKB * 16, nkc = MAXKB / 2;
-  __shared__ __attribute__((aligned(16))) char smem[2 * tpad * 128 + (PADMASK ? tpad : 0)];
+  constexpr int ROW = HD * 2, NKK = HD / 32, NDB = HD / 16;      // as in attention_kernel
+  __shared__ __attribute__((aligned(16))) char smem[2 * tpad * ROW + (PADMASK ? tpad : 0)];
   char* Ks = smem;
-  char* Vs = smem + tpad * 128;
-  char* padf = smem + 2 * tpad * 128;             // PADMASK: one byte per key of the tile, 1 = <pad> token (see attention_kernel)
+  char* Vs = smem + tpad * ROW;
+  char* padf = smem + 2 * tpad * ROW;             // PADMASK: one byte per key of the tile, 1 = <pad> token (see attention_kernel)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int qc = blockIdx.x % n_qchunk, sh = blockIdx.x / n_qchunk;
   const int seq = sh / H, h = sh % H;
   const size_t row0 = (size_t)(seq / sl.inner_count) * sl.outer_rows + (size_t)(seq % sl.inner_count) * sl.inner_rows;
   const size_t ld_qkv = (size_t)ld_qkv_ * sl.row_step, ld_ctx = (size_t)ld_ctx_ * sl.row_step;
-  const bf16_t* base = qkv + row0 * ld_qkv_ + h * 64;
+  const bf16_t* base = qkv + row0 * ld_qkv_ + h * HD;
   const int fr = lane & 15, fq = lane >> 4;
   const int q0 = qc * 64 + wave * 16;
   const bool active = q0 < T;                        // wave-uniform
-  bf16x8 qf[2];
+  bf16x8 qf[NKK];
   {
     int qrow = q0 + fr;
     if (qrow >= T) qrow = T - 1;
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) qf[kk] = *(const bf16x8*)(base + (size_t)qrow * ld_qkv + kk * 32 + fq * 8);
+    for (int kk = 0; kk < NKK; ++kk) qf[kk] = *(const bf16x8*)(base + (size_t)qrow * ld_qkv + kk * 32 + fq * 8);
   }
-  f32x4 o[4];
+  f32x4 o[NDB];
 #pragma unroll
-  for (int db = 0; db < 4; ++db) o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int db = 0; db < NDB; ++db) o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float m = -3.0e38f, l = 0.f;
   constexpr float LOG2E = 1.44269504088896341f;
   const int Tk = T + (bias_kv ? 1 : 0);              // ESM-1: key T = this head's bias_k / bias_v (see attention_kernel)
 
   for (int k0 = 0; k0 < Tk; k0 += tpad) {
     __syncthreads();
-    stage_kv<tpad, 256, BIASKV>(Ks, Vs, tid, base, ld_qkv, k_off, v_off, k0, T, bias_kv + h * 64, bias_kv + (H + h) * 64);
+    stage_kv<tpad, 256, BIASKV, HD>(Ks, Vs, tid, base, ld_qkv, k_off, v_off, k0, T, bias_kv + h * HD, bias_kv + (H + h) * HD);
     if (PADMASK) {
       for (int key = tid; key < tpad; key += 256)
         padf[key] = (k0 + key < T && key_tok[row0 + (size_t)(k0 + key) * sl.row_step] == pad_idx) ? 1 : 0;
@@ -266,7 +279,7 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
     for (int kb = 0; kb < MAXKB; ++kb) {
       st[kb] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) st[kb] = mfma_op16(k_frag(Ks, kb * 16 + fr, kk, fq), qf[kk], st[kb]);
+      for (int kk = 0; kk < NKK; ++kk) st[kb] = mfma_op16(k_frag<HD>(Ks, kb * 16 + fr, kk, fq), qf[kk], st[kb]);
     }
     const int tl = Tk - k0 - fq * 4;
 #pragma unroll
@@ -298,48 +311,50 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
     l = l * alpha + psum;
     m = mn;
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
+    for (int db = 0; db < NDB; ++db) {
       o[db][0] *= alpha; o[db][1] *= alpha; o[db][2] *= alpha; o[db][3] *= alpha;
     }
 #pragma unroll
     for (int c = 0; c < nkc; ++c) {
       const bf16x8 pf = p_frag(st[2 * c], st[2 * c + 1]);
 #pragma unroll
-      for (int db = 0; db < 4; ++db) {
+      for (int db = 0; db < NDB; ++db) {
         VtFrag vf;
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh) vf.h[hh] = vt_half(Vs, (2 * c + hh) * 16, db, fr, fq);
+        for (int hh = 0; hh < 2; ++hh) vf.h[hh] = vt_half<HD>(Vs, (2 * c + hh) * 16, db, fr, fq);
         o[db] = mfma_op16(vf.v, pf, o[db]);
       }
     }
   }
   const int q = q0 + fr;
-  if (active && q < T) store_ctx(o, 1.0f / l, ctx + row0 * ld_ctx_ + (size_t)q * ld_ctx + h * 64 + fq * 4);
+  if (active && q < T) store_ctx(o, 1.0f / l, ctx + row0 * ld_ctx_ + (size_t)q * ld_ctx + h * HD + fq * 4);
 }
 
 int launch_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int T, int H, int ld_qkv, int ld_ctx,
-                          int k_off, int v_off, const int32_t* key_tok, int pad_idx, const bf16_t* bias_kv) {
+                          int k_off, int v_off, const int32_t* key_tok, int pad_idx, const bf16_t* bias_kv, int head_dim) {
   SeqLayout sl = {1, T, 0, 1};
-  return launch_attention_seq_bf16(s, qkv, ctx, B, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok, pad_idx, bias_kv);
+  return launch_attention_seq_bf16(s, qkv, ctx, B, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok, pad_idx, bias_kv, head_dim);
 }
 
 // one rung of the key-block ladder: the kernel's <PADMASK, BIASKV, SPLIT> form for this call.  The bias-key forms are built
-// on the coarse rungs only (attn_frag.h).
-template <int KB, class... Args>
+// on the coarse rungs only (attn_frag.h), and at head dimension 64 only (ESM-1 has heads of 64; the launcher refuses the rest).
+template <int KB, int HD, class... Args>
 static void launch_rung(bool pad, bool bias, bool split, dim3 grid, hipStream_t s, Args... args) {
   auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
-  if constexpr (coarse_rung(KB)) {
-    if (bias && pad) return go(attention_kernel<KB, true, true, false>);
-    if (bias) return go(attention_kernel<KB, false, true, false>);
+  if constexpr (coarse_rung(KB) && HD == 64) {
+    if (bias && pad) return go(attention_kernel<KB, true, true, false, HD>);
+    if (bias) return go(attention_kernel<KB, false, true, false, HD>);
   }
-  if (pad) go(attention_kernel<KB, true, false, false>);
-  else if (split) go(attention_kernel<KB, false, false, true>);
-  else go(attention_kernel<KB, false, false, false>);
+  if (pad) go(attention_kernel<KB, true, false, false, HD>);
+  else if (split) go(attention_kernel<KB, false, false, true, HD>);
+  else go(attention_kernel<KB, false, false, false, HD>);
 }
 
 int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int64_t n_seq, int T, int H, int ld_qkv,
                               int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok, int pad_idx,
-                              const bf16_t* bias_kv) {
+                              const bf16_t* bias_kv, int head_dim) {
+  if (head_dim != 64 && head_dim != 32) return fail(1, "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
+  if (head_dim != 64 && bias_kv) return fail(1, "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only");
   if (n_seq == 0) return 0;
   if (n_seq * H > 0x7fffffff) return fail(1, "attention: too many sequences");
   if (T <= 0) return fail(1, "attention: empty sequence");
@@ -350,11 +365,11 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
   const int kb = attention_rung(T + (bias_kv ? 1 : 0), fine_ladder && !bias_kv);
   // Round 6: split the pairs of a partial last round (see attention_kernel).  Whole-sequence kernels for chains (row_step 1) of at
   // least four query blocks, without <pad> mask / bias key (the Gibbs path).  Resident workgroups: two per CU up to 20 key blocks
-  // (2 x 80 KB of LDS), one beyond.  PGIBBS_ATTN_SPLIT=0 switches it off.
+  // (2 x 80 KB of LDS), one beyond; at head 32 four / three / two (attention_resident32).  PGIBBS_ATTN_SPLIT=0 switches it off.
   static const int split_on = env_int("PGIBBS_ATTN_SPLIT", 1);
   int split_from = 0, split = 1;
   if (split_on && !key_tok && !bias_kv && sl.row_step == 1 && T >= 64 && kb) {
-    const long pairs = n_seq * H, slots = (long)device_cu_count() * (kb <= 20 ? 2 : 1);
+    const long pairs = n_seq * H, slots = (long)device_cu_count() * (head_dim == 64 ? (kb <= 20 ? 2 : 1) : attention_resident32(kb));
     const long rem = pairs % slots;
     const int nqb = (T + 15) / 16;
     int sp = rem ? (int)(slots / rem) : 1;
@@ -369,8 +384,12 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
   switch (kb) {
 #define PG_RUNG(KB)                                                                                                          \
   case KB:                                                                                                                   \
-    launch_rung<KB>(key_tok, bias_kv, split > 1, grid, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok, pad_idx, \
-                    bias_kv, split_from, split);                                                                             \
+    if (head_dim == 64)                                                                                                      \
+      launch_rung<KB, 64>(key_tok, bias_kv, split > 1, grid, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok,   \
+                          pad_idx, bias_kv, split_from, split);                                                              \
+    else                                                                                                                     \
+      launch_rung<KB, 32>(key_tok, false, split > 1, grid, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok,     \
+                          pad_idx, bias_kv, split_from, split);                                                              \
     break;
     PG_RUNG(2) PG_RUNG(4) PG_RUNG(6) PG_RUNG(8) PG_RUNG(10) PG_RUNG(12) PG_RUNG(14) PG_RUNG(16) PG_RUNG(18) PG_RUNG(20)
     PG_RUNG(22) PG_RUNG(24) PG_RUNG(26) PG_RUNG(28) PG_RUNG(30) PG_RUNG(32) PG_RUNG(34) PG_RUNG(36)
@@ -380,10 +399,16 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
       if (n_seq * H * n_qchunk > 0x7fffffff) return fail(1, "attention: too many sequences");
       const dim3 g((unsigned)(n_seq * H * n_qchunk));
 #define PG_ATT_LONG(P, B) hipLaunchKernelGGL((attention_long_kernel<18, 2, P, B>), g, block, 0, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, n_qchunk, key_tok, pad_idx, bias_kv)
-      if (key_tok && bias_kv) PG_ATT_LONG(true, true);
+      // head 32: the same 288-key tiles (36 KB of LDS for K + V)
+#define PG_ATT_LONG32(P) hipLaunchKernelGGL((attention_long_kernel<18, 2, P, false, 32>), g, block, 0, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, n_qchunk, key_tok, pad_idx, bias_kv)
+      if (head_dim == 32) {
+        if (key_tok) PG_ATT_LONG32(true);
+        else PG_ATT_LONG32(false);
+      } else if (key_tok && bias_kv) PG_ATT_LONG(true, true);
       else if (key_tok) PG_ATT_LONG(true, false);
       else if (bias_kv) PG_ATT_LONG(false, true);
       else PG_ATT_LONG(false, false);
+#undef PG_ATT_LONG32
 #undef PG_ATT_LONG
     }
   }

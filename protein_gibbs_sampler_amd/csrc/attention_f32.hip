@@ -50,30 +50,32 @@ __device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& 
 
 // Building blocks shared by the three split-bf16 MFMA kernels (full attention, tied-row scores, tied-row apply).
 // Fragment geometry, tile layout and the transposing V^T read: attn_frag.h.
-template <int MAXKB>
+// HD: the head dimension, 64 or 32 (attn_frag.h; 32 is built for the full attention only)
+template <int MAXKB, int HD = 64>
 struct SplitAttn {
   static constexpr int tpad = MAXKB * 16, nkc = MAXKB / 2;
+  static constexpr int CPR = HD / 8, NKK = HD / 32, NDB = HD / 16;      // 16-byte chunks per key row, score MFMAs per key block, output blocks
   static_assert(MAXKB % 2 == 0, "two 16-key blocks per 32-wide PV step");
   static constexpr float LOG2E = 1.44269504088896341f;
 
-  // rows 0 .. tpad-1 of 64 fp32 at src + row*ld (rows >= n_valid read as zero) -> (hi, lo) bf16 tiles (tile_addr).  All
+  // rows 0 .. tpad-1 of HD fp32 at src + row*ld (rows >= n_valid read as zero) -> (hi, lo) bf16 tiles (tile_addr).  All
   // global loads in flight first.
   // extra (optional): 64 fp32 that stand in for row n_valid (ESM-1: the head's bias_k / bias_v behind the last token)
   template <bool EXTRA = false>
   static __device__ __forceinline__ void stage(const float* __restrict__ src, size_t ld, int n_valid, char* Xh, char* Xl, int tid,
                                                const float* __restrict__ extra = nullptr) {
-    constexpr int NIT = (tpad * 8 + 255) / 256;      // one item = 8 d of one key
+    constexpr int NIT = (tpad * CPR + 255) / 256;      // one item = 8 d of one key
     float4 r0[NIT], r1[NIT];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * 256, row = i >> 3, c = i & 7;
+      const int i = tid + it * 256, row = i / CPR, c = i & (CPR - 1);
       r0[it] = make_float4(0.f, 0.f, 0.f, 0.f);
       r1[it] = r0[it];
-      if (i < tpad * 8 && row < n_valid) {
+      if (i < tpad * CPR && row < n_valid) {
         const float4* p = (const float4*)(src + (size_t)row * ld + c * 8);
         r0[it] = p[0];
         r1[it] = p[1];
-      } else if (EXTRA && row == n_valid && i < tpad * 8) {
+      } else if (EXTRA && row == n_valid && i < tpad * CPR) {
         const float4* p = (const float4*)(extra + c * 8);
         r0[it] = p[0];
         r1[it] = p[1];
@@ -81,21 +83,21 @@ struct SplitAttn {
     }
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int i = tid + it * 256, row = i >> 3, c = i & 7;
-      if (i < tpad * 8) {
+      const int i = tid + it * 256, row = i / CPR, c = i & (CPR - 1);
+      if (i < tpad * CPR) {
         uint4 hi, lo;
         split8(r0[it], r1[it], hi, lo);
-        const int a = tile_addr(row, c);
+        const int a = tile_addr<HD>(row, c);
         *(uint4*)(Xh + a) = hi;
         *(uint4*)(Xl + a) = lo;
       }
     }
   }
 
-  // Q fragments (MFMA B operand) of the query whose 64 fp32 start at qrow: d = kk*32 + fq*8 .. +7
-  static __device__ __forceinline__ void load_q(const float* __restrict__ qrow, int fq, bf16x8 (&qh)[2], bf16x8 (&ql)[2]) {
+  // Q fragments (MFMA B operand) of the query whose HD fp32 start at qrow: d = kk*32 + fq*8 .. +7
+  static __device__ __forceinline__ void load_q(const float* __restrict__ qrow, int fq, bf16x8 (&qh)[NKK], bf16x8 (&ql)[NKK]) {
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
+    for (int kk = 0; kk < NKK; ++kk) {
       const float4* p = (const float4*)(qrow + kk * 32 + fq * 8);
       uint4 hi, lo;
       split8(p[0], p[1], hi, lo);
@@ -105,29 +107,29 @@ struct SplitAttn {
   }
 
   // st[kb] += (K tile rows kb*16 .. +15) . q :  kl.qh + kh.ql + kh.qh
-  static __device__ __forceinline__ void qk(const char* Kh, const char* Kl, const bf16x8 (&qh)[2], const bf16x8 (&ql)[2],
+  static __device__ __forceinline__ void qk(const char* Kh, const char* Kl, const bf16x8 (&qh)[NKK], const bf16x8 (&ql)[NKK],
                                             f32x4 (&st)[MAXKB], int fr, int fq) {
 #pragma unroll
     for (int kb = 0; kb < MAXKB; ++kb) {
       f32x4 a = st[kb];
       const int krow = kb * 16 + fr;
-      bf16x8 kh[2];
+      bf16x8 kh[NKK];
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ad = tile_addr(krow, kk * 4 + fq);
+      for (int kk = 0; kk < NKK; ++kk) {
+        const int ad = tile_addr<HD>(krow, kk * 4 + fq);
         kh[kk] = *(const bf16x8*)(Kh + ad);
         a = mfma_op16(*(const bf16x8*)(Kl + ad), qh[kk], a);
         a = mfma_op16(kh[kk], ql[kk], a);
       }
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) a = mfma_op16(kh[kk], qh[kk], a);
+      for (int kk = 0; kk < NKK; ++kk) a = mfma_op16(kh[kk], qh[kk], a);
       st[kb] = a;
     }
   }
 
   // One online-softmax step over the tile's scores st (masked entries hold -3e38), then O += V^T P^T with P and V split.
   // K-slot (fq*8 + j) of 32-key chunk c <-> key (2c + (j>>2))*16 + fq*4 + (j&3): exactly the order the lane holds P in.
-  static __device__ __forceinline__ void softmax_pv(f32x4 (&st)[MAXKB], f32x4 (&o)[4], float& m, float& l, const char* Vh,
+  static __device__ __forceinline__ void softmax_pv(f32x4 (&st)[MAXKB], f32x4 (&o)[NDB], float& m, float& l, const char* Vh,
                                                     const char* Vl, int fr, int fq) {
     float tmax = -3.0e38f;
 #pragma unroll
@@ -151,7 +153,7 @@ struct SplitAttn {
     l = l * alpha + psum;
     m = mn;
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
+    for (int db = 0; db < NDB; ++db) {
       o[db][0] *= alpha; o[db][1] *= alpha; o[db][2] *= alpha; o[db][3] *= alpha;
     }
 #pragma unroll
@@ -161,13 +163,13 @@ struct SplitAttn {
       split8(make_float4(p0[0], p0[1], p0[2], p0[3]), make_float4(p1[0], p1[1], p1[2], p1[3]), ph, pl);
       const bf16x8 pfh = __builtin_bit_cast(bf16x8, ph), pfl = __builtin_bit_cast(bf16x8, pl);
 #pragma unroll
-      for (int db = 0; db < 4; ++db) {
+      for (int db = 0; db < NDB; ++db) {
         VtFrag vh, vl;
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {           // vt_half's address, once for the hi and the lo tile
           const int krow = (2 * c + hh) * 16 + fq * 4 + (fr >> 2);
           const int dcol = db * 16 + (fr & 3) * 4;
-          const int ad = tile_addr(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8;
+          const int ad = tile_addr<HD>(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8;
           vh.h[hh] = lds_read_tr16(Vh + ad);
           vl.h[hh] = lds_read_tr16(Vl + ad);
         }
@@ -178,22 +180,22 @@ struct SplitAttn {
     }
   }
 
-  // row = the query's context row; the lane holds columns h*64 + db*16 + fq*4 .. +3.  bf16, or the strict mode's split operand
-  // row (groups of 32 columns [lo | hi | hi])
-  static __device__ __forceinline__ void store_ctx(const f32x4 (&o)[4], float l, bf16_t* row, int h, int fq, int split_d) {
+  // row = the query's context row; the lane holds columns h*HD + db*16 + fq*4 .. +3.  bf16, or the strict mode's split operand
+  // row (groups of 32 columns [lo | hi | hi]: a head of 64 is two groups, a head of 32 one)
+  static __device__ __forceinline__ void store_ctx(const f32x4 (&o)[NDB], float l, bf16_t* row, int h, int fq, int split_d) {
     const float inv = l > 0.f ? 1.0f / l : 0.f;     // every key masked (an all-<pad> sequence): zero context, not NaN
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
+    for (int db = 0; db < NDB; ++db) {
       const float a = o[db][0] * inv, b = o[db][1] * inv, c = o[db][2] * inv, d = o[db][3] * inv;
       uint2 p, r;
       p.x = pack_op2(a, b);
       p.y = pack_op2(c, d);
       if (!split_d) {
-        *(uint2*)(row + h * 64 + db * 16 + fq * 4) = p;
+        *(uint2*)(row + h * HD + db * 16 + fq * 4) = p;
       } else {
         r.x = pack_op2(a - __uint_as_float(p.x << 16), b - __uint_as_float(p.x & 0xffff0000u));
         r.y = pack_op2(c - __uint_as_float(p.y << 16), d - __uint_as_float(p.y & 0xffff0000u));
-        bf16_t* g = row + (2 * h + (db >> 1)) * 96 + (db & 1) * 16 + fq * 4;
+        bf16_t* g = row + (NKK * h + (db >> 1)) * 96 + (db & 1) * 16 + fq * 4;
         *(uint2*)g = r;
         *(uint2*)(g + 32) = p;
         if (split_d > 0) *(uint2*)(g + 64) = p;
@@ -208,36 +210,36 @@ struct SplitAttn {
 // (sequence, head) instead of five that each re-staged and re-split the same 132 KB of fp32 K and V (round 3: 28 ms of the strict
 // config-2 iteration were this kernel, 4x the bf16 mode's, most of it the 5x redundant fp32 tile traffic).  The per-query
 // arithmetic (tile order, products, rounding points) is unchanged: identical bits.
-template <int MAXKB, int NQB, bool BIASKV = false, bool PADMASK = false>
+template <int MAXKB, int NQB, bool BIASKV = false, bool PADMASK = false, int HD = 64>
 __global__ __launch_bounds__(256, 2) void attention_split_kernel(
     const float* __restrict__ qkv, bf16_t* __restrict__ ctx, int split_d, int T, int H, int ld_qkv_, int ld_ctx_, int k_off,
     int v_off, SeqLayout sl, int n_qchunk, const int32_t* __restrict__ key_tok, int pad_idx, const float* __restrict__ bias_kv) {
-  using A = SplitAttn<MAXKB>;
-  constexpr int tpad = A::tpad;
-  __shared__ __attribute__((aligned(16))) char smem[4 * tpad * 128];
-  char *Kh = smem, *Kl = smem + tpad * 128, *Vh = smem + 2 * tpad * 128, *Vl = smem + 3 * tpad * 128;
+  using A = SplitAttn<MAXKB, HD>;
+  constexpr int tpad = A::tpad, ROW = HD * 2;
+  __shared__ __attribute__((aligned(16))) char smem[4 * tpad * ROW];
+  char *Kh = smem, *Kl = smem + tpad * ROW, *Vh = smem + 2 * tpad * ROW, *Vl = smem + 3 * tpad * ROW;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int qc = blockIdx.x % n_qchunk, sh = blockIdx.x / n_qchunk;
   const int seq = sh / H, h = sh % H;
   const size_t row0 = (size_t)(seq / sl.inner_count) * sl.outer_rows + (size_t)(seq % sl.inner_count) * sl.inner_rows;
   const size_t ld_qkv = (size_t)ld_qkv_ * sl.row_step, ld_ctx = (size_t)ld_ctx_ * sl.row_step;
-  const float* base = qkv + row0 * ld_qkv_ + h * 64;
+  const float* base = qkv + row0 * ld_qkv_ + h * HD;
   const int fr = lane & 15, fq = lane >> 4;
   const int qbase = qc * (64 * NQB) + wave * 16;     // block j of this wave: queries qbase + j*64 .. +15
-  f32x4 o[NQB][4];
+  f32x4 o[NQB][A::NDB];
   float m[NQB], l[NQB];
 #pragma unroll
   for (int j = 0; j < NQB; ++j) {
 #pragma unroll
-    for (int db = 0; db < 4; ++db) o[j][db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int db = 0; db < A::NDB; ++db) o[j][db] = (f32x4){0.f, 0.f, 0.f, 0.f};
     m[j] = -3.0e38f;
     l[j] = 0.f;
   }
 
   // ESM-1 (add_bias_kv): key T = this head's bias_k / bias_v -- one more key, never masked (attention.hip)
   const int Tk = T + (BIASKV ? 1 : 0);
-  const float* bk = BIASKV ? bias_kv + h * 64 : nullptr;
-  const float* bv = BIASKV ? bias_kv + (H + h) * 64 : nullptr;
+  const float* bk = BIASKV ? bias_kv + h * HD : nullptr;
+  const float* bv = BIASKV ? bias_kv + (H + h) * HD : nullptr;
   for (int k0 = 0; k0 < Tk; k0 += tpad) {
     __syncthreads();
     A::template stage<BIASKV>(base + (size_t)k0 * ld_qkv + k_off, ld_qkv, T - k0, Kh, Kl, tid, bk);
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(
     for (int j = 0; j < NQB; ++j) {
       const int q0 = qbase + j * 64;
       if (q0 >= T) continue;                       // wave-uniform
-      bf16x8 qh[2], ql[2];
+      bf16x8 qh[A::NKK], ql[A::NKK];
       A::load_q(base + (size_t)(q0 + fr < T ? q0 + fr : T - 1) * ld_qkv, fq, qh, ql);
       f32x4 st[MAXKB];
 #pragma unroll
@@ -607,7 +609,11 @@ int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores,
 
 int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
                          int ld_qkv, int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok, int pad_idx,
-                         const float* bias_kv) {
+                         const float* bias_kv, int head_dim) {
+  if (head_dim != 64 && head_dim != 32) return fail(1, "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
+  if (head_dim != 64 && bias_kv) return fail(1, "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only");
+  if (head_dim != 64 && attn_f32_mode() < 0)
+    return fail(1, "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
   if (n_seq == 0) return 0;
   if (T <= 0) return fail(1, "attention: empty sequence");
   if (bias_kv && attn_f32_mode() < 0) return fail(1, "attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)");
@@ -645,7 +651,11 @@ int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split
     }
 #define PG_ATT_SPLIT(KB, NQ)                                                                                                  \
   do {                                                                                                                        \
-    if (bias_kv && key_tok) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, true, true>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
+    if (head_dim == 32 && key_tok) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, false, true, 32>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
+                                                      n_qchunk, key_tok, pad_idx, bias_kv);                                    \
+    else if (head_dim == 32) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, false, false, 32>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
+                                                n_qchunk, key_tok, pad_idx, bias_kv);                                          \
+    else if (bias_kv && key_tok) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, true, true>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
                                                n_qchunk, key_tok, pad_idx, bias_kv);                                           \
     else if (bias_kv) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, true, false>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
                                          n_qchunk, key_tok, pad_idx, bias_kv);                                                 \

@@ -9,12 +9,37 @@
 // a reference under a condition, or hand the whole address over as one integer, cost the kernels registers (up to 76 VGPRs on the
 // tall rungs of attention_kernel) -- compare the ISA of every user before changing a signature here.
 //
+// The head dimension is the template parameter HD of everything that touches a tile or the context: 64 (the default: ESM-1b,
+// ESM-1, MSA-1b, ESM-2 650M / 3B -- every caller that names no HD is the head-64 form, instruction for instruction what it was
+// before HD existed) or 32 (ESM-2 150M).  Softmax, masks, p_frag and the key-block ladder do not depend on it.
+//
 // Geometry (head dim 64).  A K or V tile is row-major in LDS, one key per 128-byte row, the row's eight 16-byte chunks
 // XOR-swizzled with (row & 7).  fr = lane & 15 is the lane's query (the MFMA column), fq = lane >> 4.
 //   * S^T = K.Q^T: a score block st[kb][r] = S[query fr][key kb*16 + fq*4 + r] -- a query's whole score row is lane-local up
 //     to a 4-lane (xor 16, 32) reduction, so the softmax runs in registers;
 //   * O^T = V^T.P^T: K-slot (fq*8 + j) of 32-key chunk c <-> key (2c + (j>>2))*16 + fq*4 + (j&3), exactly the order the lane
 //     holds P in; o[db][r] = O[query fr][d = db*16 + fq*4 + r] -> 8-byte row-major context stores.
+//
+// Geometry (head dim 32).  One key per 64-byte row of four 16-byte chunks; ONE v_mfma_f32_16x16x32 contracts the whole head
+// (k_frag: chunk fq of key row fr), two output blocks o[2].  Two keys share a 128-byte line and four a 256-byte bank row, so
+// chunk ^ (row & 7) no longer means anything; the swizzle is  chunk ^ ((row >> 1) & 2)  -- bit 2 of the key row swaps the two
+// 32-byte halves of its row.  Why that and nothing more (LDS banks: 64 x 4 bytes = sixteen 16-byte slots per bank row; the slot of
+// chunk c of row r is 4 (r & 3) + c before the swizzle):
+//   * the score fragment is a ds_read_b128, served in four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
+//     same + 32.  Lane = 16 fq + fr reads chunk fq of row fr, so a group holds rows {0-3, 12-15} at one chunk c and rows {4-11} at
+//     chunk c ^ 1: for every value of (r & 3) four rows, one from each quarter q2 = (r >> 2) & 3 of the block, that must land on
+//     the four different chunks of their slot group.  Unswizzled they land on two (c for q2 = 0, 3; c ^ 1 for q2 = 1, 2): a 2-way
+//     conflict on every read.  With g(q2) = 2 (q2 & 1) the physical chunks are c, c ^ 3, c ^ 1, c ^ 2 for q2 = 0, 1, 2, 3: all
+//     four, conflict-free.  (chunk ^ q2, the analogue of the head-64 form, gives c, c, c ^ 3, c ^ 3: still 2-way.)
+//   * the transposing read ds_read_b64_tr_b16 is served in two halves of 32 lanes; a half reads, for one d block db, 32 contiguous
+//     bytes (chunks 2 db, 2 db + 1) of 8 consecutive key rows key0 + 8 (fq >> 1) + 0..7.  Rows r and r + 4 of those eight sit 256
+//     bytes apart -- the same banks unless they read opposite 32-byte halves of their rows, which is exactly what flipping bit 1
+//     of the chunk by bit 2 of the row does (bit 0 of a swizzle would only swap two chunks inside the same 32 bytes).  The eight
+//     rows then cover all 64 banks once.
+//   * the staging writes (ds_write_b128, 8 consecutive lanes per group, 32 banks = 128 bytes) put 8 consecutive items = the four
+//     chunks of two neighbouring rows = one whole 128-byte line, whatever permutation the swizzle applies inside each row.
+// Packing two keys into one 128-byte row and keeping the head-64 swizzle was the alternative; it needs a second row index
+// (key >> 1) and chunk base ((key & 1) * 4) in every address and gives the same bank picture, so the 64-byte row was built.
 #pragma once
 #include "kernels.h"
 
@@ -44,38 +69,45 @@ inline int attention_rung(int n_keys, bool fine) {
 
 // ---- tiles ----------------------------------------------------------------------------------------------------------------
 // byte offset of 16-byte chunk `chunk` inside tile row `row`, and from the start of the tile
-__device__ __forceinline__ int tile_swz(int row, int chunk) { return (chunk ^ (row & 7)) << 4; }
-__device__ __forceinline__ int tile_addr(int row, int chunk) { return row * 128 + tile_swz(row, chunk); }
+template <int HD = 64>
+__device__ __forceinline__ int tile_swz(int row, int chunk) {
+  static_assert(HD == 64 || HD == 32, "head dimension 64 or 32");
+  return (HD == 64 ? chunk ^ (row & 7) : chunk ^ ((row >> 1) & 2)) << 4;
+}
+template <int HD = 64>
+__device__ __forceinline__ int tile_addr(int row, int chunk) { return row * (HD * 2) + tile_swz<HD>(row, chunk); }
 
-// Staging by NT threads: item i = tid + it*NT is chunk (i & 7) of tile row (i >> 3).
+// Staging by NT threads: item i = tid + it*NT is chunk (i & (HD/8 - 1)) of tile row (i >> log2(HD/8)).
 // One thread's share of one tile of TPAD rows, for kernels that put other work between a tile's loads and its LDS writes
-template <int TPAD, int NT>
+template <int TPAD, int NT, int HD = 64>
 struct TileRegs {
-  static constexpr int NIT = (TPAD * 8 + NT - 1) / NT;
+  static constexpr int NIT = (TPAD * (HD / 8) + NT - 1) / NT;
   uint4 r[NIT];
 };
-template <int TPAD, int NT>
-__device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT>& g, int tid, char* dst) {
+template <int TPAD, int NT, int HD>
+__device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT, HD>& g, int tid, char* dst) {
+  constexpr int CPR = HD / 8, CSH = HD == 64 ? 3 : 2;                     // 16-byte chunks per key row, and its log2
 #pragma unroll
-  for (int it = 0; it < TileRegs<TPAD, NT>::NIT; ++it) {
-    const int i = tid + it * NT, row = i >> 3, c = i & 7;
-    if (i < TPAD * 8) *(uint4*)(dst + row * 128 + tile_swz(row, c)) = g.r[it];
+  for (int it = 0; it < TileRegs<TPAD, NT, HD>::NIT; ++it) {
+    const int i = tid + it * NT, row = i >> CSH, c = i & (CPR - 1);
+    if (i < TPAD * CPR) *(uint4*)(dst + row * (HD * 2) + tile_swz<HD>(row, c)) = g.r[it];
   }
 }
 // The K and the V tile of one head together, rows row0 .. row0 + TPAD - 1 of the sequence's n_rows: all global loads of both are
 // issued before the first LDS write, so a workgroup pays about one memory round trip, not one per item.  bias_k / bias_v (with
-// EXTRA: ESM-1's bias key, 64 values each) stand in for row n_rows.
-template <int TPAD, int NT, bool EXTRA>
+// EXTRA: ESM-1's bias key, HD values each) stand in for row n_rows.
+template <int TPAD, int NT, bool EXTRA, int HD = 64>
 __device__ __forceinline__ void stage_kv(char* Ks, char* Vs, int tid, const bf16_t* src, size_t ld, int k_off, int v_off, int row0,
                                          int n_rows, const bf16_t* bias_k, const bf16_t* bias_v) {
-  constexpr int NIT = (TPAD * 8 + NT - 1) / NT;
+  constexpr int CPR = HD / 8, CSH = HD == 64 ? 3 : 2;                     // 16-byte chunks per key row, and its log2
+  constexpr int NIT = (TPAD * CPR + NT - 1) / NT;
   uint4 kreg[NIT], vreg[NIT];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int i = tid + it * NT, row = row0 + (i >> 3), c = i & 7;       // row of the sequence
+    const int i = tid + it * NT, row = row0 + (i >> CSH), c = i & (CPR - 1);       // row of the sequence
     kreg[it] = make_uint4(0, 0, 0, 0);
     vreg[it] = make_uint4(0, 0, 0, 0);
-    if (i < TPAD * 8 && row < n_rows) {
+    if (i < TPAD * CPR && row < n_rows) {
       kreg[it] = *(const uint4*)(src + (size_t)row * ld + k_off + c * 8);
       vreg[it] = *(const uint4*)(src + (size_t)row * ld + v_off + c * 8);
     } else if (EXTRA && row == n_rows) {
@@ -85,18 +117,19 @@ __device__ __forceinline__ void stage_kv(char* Ks, char* Vs, int tid, const bf16
   }
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int i = tid + it * NT, row = i >> 3, c = i & 7;
-    if (i < TPAD * 8) {
-      *(uint4*)(Ks + row * 128 + tile_swz(row, c)) = kreg[it];
-      *(uint4*)(Vs + row * 128 + tile_swz(row, c)) = vreg[it];
+    const int i = tid + it * NT, row = i >> CSH, c = i & (CPR - 1);
+    if (i < TPAD * CPR) {
+      *(uint4*)(Ks + row * (HD * 2) + tile_swz<HD>(row, c)) = kreg[it];
+      *(uint4*)(Vs + row * (HD * 2) + tile_swz<HD>(row, c)) = vreg[it];
     }
   }
 }
 
 // ---- fragments ------------------------------------------------------------------------------------------------------------
-// K (MFMA A operand of S^T) or Q (B operand) fragment out of a tile: row krow, d = kk*32 + fq*8 .. +7
+// K (MFMA A operand of S^T) or Q (B operand) fragment out of a tile: row krow, d = kk*32 + fq*8 .. +7 (kk < HD / 32)
+template <int HD = 64>
 __device__ __forceinline__ bf16x8 k_frag(const char* Ks, int krow, int kk, int fq) {
-  return *(const bf16x8*)(Ks + krow * 128 + tile_swz(krow, kk * 4 + fq));
+  return *(const bf16x8*)(Ks + krow * (HD * 2) + tile_swz<HD>(krow, kk * 4 + fq));
 }
 
 // V^T fragment (A operand of O^T) for d = db*16 .. +15 and a chunk of 32 keys, straight out of the row-major V tile through
@@ -109,10 +142,11 @@ __device__ __forceinline__ uint2 lds_read_tr16(const char* a) {
       (__attribute__((address_space(3))) char*)a));
   return __builtin_bit_cast(uint2, t);
 }
+template <int HD = 64>
 __device__ __forceinline__ uint2 vt_half(const char* Vs, int key0, int db, int fr, int fq) {
   const int krow = key0 + fq * 4 + (fr >> 2);
   const int dcol = db * 16 + (fr & 3) * 4;                                     // 16-bit index inside the key row
-  return lds_read_tr16(Vs + krow * 128 + tile_swz(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8);
+  return lds_read_tr16(Vs + krow * (HD * 2) + tile_swz<HD>(krow, dcol >> 3) + ((dcol >> 2) & 1) * 8);
 }
 
 // P fragment (B operand of O^T) of one 32-key chunk from its two score blocks
@@ -176,19 +210,20 @@ __device__ __forceinline__ float softmax_exact(f32x4 (&st)[KB], float mx) {
 }
 
 // ---- context --------------------------------------------------------------------------------------------------------------
-// the lane's 4 x 4 context values, scaled by inv, as four 8-byte pieces: store(db, piece) puts d = db*16 + fq*4 .. +3
-template <class Store>
-__device__ __forceinline__ void store_ctx(const f32x4 (&o)[4], float inv, Store&& store) {
+// the lane's NDB x 4 context values (NDB = HD / 16), scaled by inv, as 8-byte pieces: store(db, piece) puts d = db*16 + fq*4 .. +3
+template <int NDB, class Store>
+__device__ __forceinline__ void store_ctx(const f32x4 (&o)[NDB], float inv, Store&& store) {
 #pragma unroll
-  for (int db = 0; db < 4; ++db) {
+  for (int db = 0; db < NDB; ++db) {
     uint2 p;
     p.x = pack_op2(o[db][0] * inv, o[db][1] * inv);
     p.y = pack_op2(o[db][2] * inv, o[db][3] * inv);
     store(db, p);
   }
 }
-// dst = the query's context row at column h*64 + fq*4
-__device__ __forceinline__ void store_ctx(const f32x4 (&o)[4], float inv, bf16_t* dst) {
+// dst = the query's context row at column h*HD + fq*4
+template <int NDB>
+__device__ __forceinline__ void store_ctx(const f32x4 (&o)[NDB], float inv, bf16_t* dst) {
   store_ctx(o, inv, [&](int db, uint2 p) { *(uint2*)(dst + db * 16) = p; });
 }
 

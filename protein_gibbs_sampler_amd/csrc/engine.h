@@ -133,9 +133,10 @@ struct Engine {
   bool esm1() const { return cfg.arch == PG_ARCH_ESM1; }      // ESM-1 differences: see pgibbs.h PG_ARCH_ESM1
   bool esm2() const { return cfg.arch == PG_ARCH_ESM2; }      // ESM-2 differences: see pgibbs.h PG_ARCH_ESM2
   bool esm_family() const { return cfg.arch == PG_ARCH_ESM1B || cfg.arch == PG_ARCH_ESM1 || cfg.arch == PG_ARCH_ESM2; }   // the pg_esm_* entry points
-  // ESM-2 rotary embedding: cos / sin table [rope_rows][64] fp32 built at init (rope.hip); rope() rotates the q and k thirds of a
+  // ESM-2 rotary embedding: cos / sin table [rope_rows][head_dim] fp32 built at init (rope.hip); rope() rotates the q and k thirds of a
   // freshly projected qkv buffer (the engine's 16-bit type, fp32 in strict mode) of M token rows, T per sequence.  A no-op for
   // every other architecture
+  int head_dim = 64;          // d_model / n_heads: 64, or 32 (ESM-2 only) -- what every attention and rotation launch of the ESM path is given
   float* rope_tab = nullptr;
   int rope_rows = 0;
   int rope(void* qkv_rows, int64_t M, int T);
@@ -193,7 +194,7 @@ struct Engine {
 };
 
 // host side of the ESM-2 rotary embedding: the cos / sin table the rotation kernel reads (engine.hip)
-std::vector<float> rope_table(int rows);
+std::vector<float> rope_table(int rows, int hd = 64);
 
 // state-dict lookup used by init
 struct TensorMap {

@@ -215,8 +215,17 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   device = -1;
   if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_MSA1B && cfg.arch != PG_ARCH_ESM1 && cfg.arch != PG_ARCH_ESM2) return fail(PG_ERR_INVALID, "unknown arch");
   if (prec != PG_PREC_BF16 && prec != PG_PREC_FP32 && prec != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
-  if (cfg.d_model % 128 || cfg.d_ffn % 128 || cfg.n_heads * 64 != cfg.d_model)
-    return fail(PG_ERR_INVALID, "d_model and d_ffn must be multiples of 128 and head dim must be 64");
+  if (cfg.d_model % 128 || cfg.d_ffn % 128) return fail(PG_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
+  // head width: the attention and rotary kernels are built for 64 (every architecture) and 32 (ESM-2 only: esm2_t30_150M_UR50D)
+  head_dim = cfg.n_heads > 0 && cfg.d_model % cfg.n_heads == 0 ? cfg.d_model / cfg.n_heads : 0;
+  if (head_dim == 32 && cfg.arch != PG_ARCH_ESM2)
+    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
+                                    " with heads of 32: head dim must be 64 for this architecture (heads of 32 run for PG_ARCH_ESM2 only)");
+  if (head_dim != 64 && head_dim != 32)
+    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " with " + std::to_string(cfg.n_heads) +
+                                    " heads: head dim must be 64 (every architecture) or 32 (PG_ARCH_ESM2)");
+  if (head_dim == 32 && cfg.n_heads > 32)
+    return fail(PG_ERR_INVALID, "heads of 32: the rotary kernel holds at most 32 of them per row (d_model <= 1024; esm2_t30_150M_UR50D has 20)");
   // the row kernels (ln_row.h, rope.hip) hold a row of at most 2560 features per wave: 40 heads of 64, ESM-2 3B
   if (cfg.d_model > 2560)
     return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " > 2560: the engine runs up to 40 heads of 64 (esm2_t36_3B_UR50D)");
@@ -235,7 +244,11 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
     if (tensors[i].name) tm.m[tensors[i].name] = &tensors[i];
   Uploader up{this, &tm, prec, ""};
   const int d = cfg.d_model, f = cfg.d_ffn, V = cfg.vocab;
-  const float qs = 0.125f;  // head_dim^-0.5 = 64^-0.5, folded into W_q and b_q (exact in bf16)
+  float qs = 0.125f;  // head_dim^-0.5 = 64^-0.5, folded into W_q and b_q (exact in bf16)
+  // heads of 32: 32^-0.5 is no power of two.  Still folded into W_q and b_q, as an fp32 factor applied to the fp32 checkpoint values
+  // BEFORE they are rounded to the 16-bit operand (or split into the strict mode's bf16 pair) -- the kernels stay scale-free and
+  // the only new rounding is that fp32 product, 2^-24 relative, under an operand rounding of 2^-9 / 2^-12 / 2^-17
+  if (head_dim == 32) qs = 0.17677669529663687f;
   bool ok = true;
   ok = ok && (embed = up.f32("embed_tokens.weight", (int64_t)V * d));
   // ESM-2 has no position table (pos stays null: embed_ln_kernel adds nothing) -- positions enter through the rotation of q and k
@@ -287,7 +300,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   if (esm2()) {
     if (cfg.max_positions < 1) return fail(PG_ERR_INVALID, "max_positions must be positive");
     rope_rows = cfg.max_positions + 2;              // like the learned tables
-    const std::vector<float> tab = rope_table(rope_rows);
+    const std::vector<float> tab = rope_table(rope_rows, head_dim);
     void* dt = nullptr;
     PG_HIP(hipMalloc(&dt, tab.size() * 4));
     owned.push_back(dt);
@@ -446,18 +459,20 @@ float* Engine::splitk_ws(int rows, int n, int K, int64_t batch_rows) {
   return splitk.as<float>();
 }
 
-// The rotary embedding's table [rows][64]: [t][i] = cos, [t][32 + i] = sin of ang[t][i] = float(t) * inv_freq[i] (an fp32 product),
+// The rotary embedding's table [rows][hd], hd = the head dimension (64, or 32 with 16 in place of 32 below): [t][i] = cos,
+// [t][32 + i] = sin of ang[t][i] = float(t) * inv_freq[i] (an fp32 product),
 // inv_freq[i] = 1 / 10000^(2i / 64) in fp32 as fair-esm's RotaryEmbedding holds it (1.0 / (10000 ** (arange(0, 64, 2).float() / 64))).
 // The power is taken in double and rounded to fp32 -- the values torch's fp32 pow and glibc's powf give; a vectorised fp32 pow (numpy's)
 // is one ulp off at i = 5 and 27 --, the cosine and sine of the fp32 angle in double, rounded to fp32.
-std::vector<float> rope_table(int rows) {
-  std::vector<float> tab((size_t)rows * 64);
-  for (int i = 0; i < 32; ++i) {
-    const float inv_freq = 1.0f / (float)pow(10000.0, i / 32.0);
+std::vector<float> rope_table(int rows, int hd) {
+  const int half = hd / 2;
+  std::vector<float> tab((size_t)rows * hd);
+  for (int i = 0; i < half; ++i) {
+    const float inv_freq = 1.0f / (float)pow(10000.0, i / (double)half);
     for (int t = 0; t < rows; ++t) {
       const float ang = (float)t * inv_freq;
-      tab[(size_t)t * 64 + i] = (float)cos((double)ang);
-      tab[(size_t)t * 64 + 32 + i] = (float)sin((double)ang);
+      tab[(size_t)t * hd + i] = (float)cos((double)ang);
+      tab[(size_t)t * hd + half + i] = (float)sin((double)ang);
     }
   }
   return tab;
@@ -465,7 +480,7 @@ std::vector<float> rope_table(int rows) {
 
 int Engine::rope(void* qkv_rows, int64_t M, int T) {
   if (!esm2()) return PG_OK;
-  return timed(PC_ROPE, [&] { return OPS(launch_rope, stream, qkv_rows, strict(), rope_tab, rope_rows, M, T, cfg.n_heads, 3 * cfg.d_model); });
+  return timed(PC_ROPE, [&] { return OPS(launch_rope, stream, qkv_rows, strict(), rope_tab, rope_rows, M, T, cfg.n_heads, 3 * cfg.d_model, head_dim); });
 }
 
 int Engine::size_activations(int64_t Mp) {
@@ -560,7 +575,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
       if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln1.g, L.ln1.b, h.as<bf16_t>(), M, d, eps, true, 0, 0, dense3_wants_dup(L.qkv, Mi)); }))) return rc;
       if ((rc = dense3(h.as<bf16_t>(), L.qkv, QKVf, Mi, false))) return rc;
       if ((rc = rope(QKVf, M, T))) return rc;                                  // ESM-2 only
-      if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), dense3_wants_dup(L.out, Mi) ? d : -d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32); }))) return rc;
+      if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), dense3_wants_dup(L.out, Mi) ? d : -d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32, head_dim); }))) return rc;
       if ((rc = dense3(ctx.as<bf16_t>(), L.out, X, Mi, true))) return rc;
       if ((rc = ffn_strict(L.ffn, Mi, M))) return rc;
     }
@@ -622,7 +637,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
     }
     if (!attn_done && (rc = rope(QKV, M, T))) return rc;                       // ESM-2 only: q and k rotated by their positions
     if (!attn_done)
-      if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16); }))) return rc;
+      if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16, head_dim); }))) return rc;
     const bool last = l == cfg.n_layers - 1;
     // last layer: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
     if (sel_idx && last) return pruned_tail(L.out, L.ffn, sel_idx, nullptr, P, T, n_sel, d_iter_, sel_gemm_rows(n_sel, round_up64(n_sel, kRowPad)), ln_in_gemm);

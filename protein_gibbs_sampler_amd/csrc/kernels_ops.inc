@@ -73,15 +73,17 @@ bool gemm_split3_fused(int M, int N, int K, int epi);
 int launch_gemm_split3_w16(hipStream_t s, const bf16_t* X3, const bf16_t* W3, const float* bias, void* out, int M, int N, int K,
                            int ldo, int epi);
 
-// fused attention, one (sequence, head) per workgroup; qkv rows are [q | k | v] with head h at h*64
+// fused attention, one (sequence, head) per workgroup; qkv rows are [q | k | v] with head h at h*head_dim; head_dim 64, or 32
+// (ESM-2 150M; without bias_kv)
 // key_tok (optional): the int32 token buffer [n_seq][T]; keys whose token is pad_idx are masked (ragged batches)
 // bias_kv (optional, ESM-1's add_bias_kv): [bias_k | bias_v], d_model 16-bit values each -- ONE extra key / value per sequence,
 // appended behind the T token keys, never masked
 int launch_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int T, int H, int ld_qkv, int ld_ctx,
-                          int k_off, int v_off, const int32_t* key_tok = nullptr, int pad_idx = -1, const bf16_t* bias_kv = nullptr);
+                          int k_off, int v_off, const int32_t* key_tok = nullptr, int pad_idx = -1, const bf16_t* bias_kv = nullptr,
+                          int head_dim = 64);
 int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int64_t n_seq, int T, int H, int ld_qkv,
                               int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok = nullptr,
-                              int pad_idx = -1, const bf16_t* bias_kv = nullptr);
+                              int pad_idx = -1, const bf16_t* bias_kv = nullptr, int head_dim = 64);
 // MSA tied row attention (SURVEY.md A.3): one C x C map per (msa, head) from scores summed over the R rows
 // `partial` (optional fp32 scratch of partial_bytes) enables the split-R mode used when B*H is small
 // order_bh (0 = B * H): the (msa, head) count the split-R decision is taken on (job-level, so that shards agree);
@@ -97,10 +99,11 @@ int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, co
                     const float* gamma2 = nullptr, const float* beta2 = nullptr, bf16_t* h2 = nullptr,   // h2: also the first layer's LayerNorm of x
                     float embed_scale = 1.0f);   // gamma == nullptr: no emb_layer_norm_before; embed_scale = sqrt(d) (both: ESM-1);
                                                  // pos == nullptr: no position table either (ESM-2)
-// ESM-2 rotary position embedding (rope.hip): the q and k thirds of qkv[M][ld] (rows [q | k | v], H heads of 64 each) rotated in place,
-// row r at position r % T; table = [table_rows][64] fp32 ([t][0..31] cos, [t][32..63] sin of float(t) * inv_freq[i]); f32: the buffer
-// is fp32 (strict mode), else the flavour's 16-bit type.  Rows >= M are not touched
-int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld);
+// ESM-2 rotary position embedding (rope.hip): the q and k thirds of qkv[M][ld] (rows [q | k | v], H heads of head_dim each, 64 or 32)
+// rotated in place, row r at position r % T; table = [table_rows][head_dim] fp32 ([t][0 .. head_dim/2 - 1] cos, then as many sin, of
+// float(t) * inv_freq[i]: rope_table); f32: the buffer is fp32 (strict mode), else the flavour's 16-bit type.  Rows >= M are not touched
+int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld,
+                int head_dim = 64);
 int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
                           int d, float eps, bool split3 = false,   // split3: h rows are [lo | hi | hi], 3 d wide
                           int colmajor_R = 0, int colmajor_C = 0,  // > 0: token row (b*R + r)*C + c is written as row (b*C + c)*R + r
@@ -125,7 +128,8 @@ int launch_gelu_f32(hipStream_t s, float* p, int64_t n);
 // duplicate hi block (for an out-projection on the fused three-product kernel, gemm_split3_fused)
 int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
                          int ld_qkv, int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok = nullptr,
-                         int pad_idx = -1, const float* bias_kv = nullptr);     // bias_kv: fp32 [bias_k | bias_v] (ESM-1)
+                         int pad_idx = -1, const float* bias_kv = nullptr,      // bias_kv: fp32 [bias_k | bias_v]
+                         int head_dim = 64);                                    // 64, or 32 (split kernel only, without bias_kv) (ESM-1)
 // strict tied row attention; `scores` is an fp32 scratch of B*H*C rows of msa_row_scores_ld(C) floats
 static inline int msa_row_scores_ld(int C) { return (C + 3) & ~3; }
 // tok (optional): the int32 token buffer [B][R][C] of a batch that holds <pad> (ragged MSA lists): fair-esm's padding semantics

@@ -1,7 +1,7 @@
 // Rotary position embedding (ESM-2): the q and k thirds of a [q | k | v] row buffer rotated in place, one launch per layer between
 // the QKV projection and the attention kernel.
 //
-// fair-esm's RotaryEmbedding, "rotate-half" form, head dimension 64: with ang[t][i] = float(t) * inv_freq[i] (i = 0..31, t = the
+// fair-esm's RotaryEmbedding, "rotate-half" form, written here for head dimension 64 (heads of 32: below): with ang[t][i] = float(t) * inv_freq[i] (i = 0..31, t = the
 // token's index along the sequence axis, padding or not) a head vector u[0..63] of q or k becomes
 //   u'[i]      = u[i]      * cos(ang[t][i]) - u[i + 32] * sin(ang[t][i])
 //   u'[i + 32] = u[i + 32] * cos(ang[t][i]) + u[i]      * sin(ang[t][i])
@@ -20,6 +20,9 @@
 // 16-bit buffers 8 + 8 values, 4 lanes per head, 8 H lane-slots per row (160 at d = 1280); fp32 buffers 4 + 4 values, 8 lanes per
 // head, 16 H lane-slots.  Slot s = lane + 64 * pass: the lane's place inside the head (s mod 4 or 8) is the same in every pass, so
 // its cos / sin values are loaded once per row.  A row's loads are all issued before the first rotation.
+// Heads of 32 (ESM-2 150M, template parameter HD): pairs (i, i + 16), the same rule with half the head -- 16-bit buffers 8 + 8 values =
+// the lane's 16 bytes and the 16 bytes 32 bytes higher, 2 lanes per head, 4 H lane-slots per row (80 at d = 640: two passes); fp32
+// buffers 4 + 4 values, 4 lanes per head, 8 H lane-slots (three passes at d = 640); the table row is [16 cos | 16 sin].
 // Grid: at most one resident round of workgroups (the kernel's occupancy x CUs), every wave walking rows row, row + waves, ... -- a mid-size
 // batch has no nearly empty last round (the reason layernorm_bf16_stride_kernel exists), and stores retire behind the next row's
 // loads.  Rows >= M (the 256-row padding of the activation buffers) are not touched.
@@ -32,6 +35,8 @@ PG_OPS_BEGIN
 constexpr int kRopePass16 = 4, kRopePass16Wide = 5;    // 8 H lane-slots / 64 lanes
 constexpr int kRopePass32 = 8, kRopePass32Wide = 10;   // 16 H lane-slots / 64 lanes
 constexpr int kRopeHeads = 32, kRopeHeadsWide = 40;
+// heads of 32: up to 32 of them (d_model <= 1024; ESM-2 150M has 20) in 2 (16-bit: 4 H slots) and 4 (fp32: 8 H slots) passes
+constexpr int kRopePass16Hd32 = 2, kRopePass32Hd32 = 4;
 
 __device__ __forceinline__ void rope_pair(float& lo, float& hi, float c, float s) {
   const float a = lo, b = hi;
@@ -49,27 +54,28 @@ __device__ __forceinline__ void rope_word16(uint32_t& wl, uint32_t& wh, float c0
   wh = pack_op2(h0, h1);
 }
 
-template <int NP>
+template <int NP, int HD = 64>
 __global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, const float* __restrict__ tab, int M, int T, int H,
                                                     int ld) {
+  constexpr int LPH = HD / 16;                                  // lanes per head = uint4 in a head's half
   const int lane = threadIdx.x & 63;
   const int stride = (int)gridDim.x * 4;
-  const int slots = 8 * H;
-  const int c = lane & 3;                                       // values 8 c .. 8 c + 7 of the head's low half
+  const int slots = 2 * LPH * H;
+  const int c = lane & (LPH - 1);                               // values 8 c .. 8 c + 7 of the head's low half
   for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
-    const float4* tr = (const float4*)(tab + (size_t)(row % T) * 64);
-    uint4* base = (uint4*)(qkv + (size_t)row * ld);             // 8 uint4 per head
+    const float4* tr = (const float4*)(tab + (size_t)(row % T) * HD);
+    uint4* base = (uint4*)(qkv + (size_t)row * ld);             // 2 LPH uint4 per head
     uint4 lo[NP], hi[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
       if (s < slots) {
-        const uint4* p = base + (s >> 2) * 8 + c;
+        const uint4* p = base + (s / LPH) * (2 * LPH) + c;
         lo[i] = p[0];
-        hi[i] = p[4];
+        hi[i] = p[LPH];
       }
     }
-    const float4 ca = tr[2 * c], cb = tr[2 * c + 1], sa = tr[8 + 2 * c], sb = tr[8 + 2 * c + 1];
+    const float4 ca = tr[2 * c], cb = tr[2 * c + 1], sa = tr[HD / 8 + 2 * c], sb = tr[HD / 8 + 2 * c + 1];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
@@ -78,36 +84,37 @@ __global__ __launch_bounds__(256) void rope16_kernel(bf16_t* __restrict__ qkv, c
         rope_word16(lo[i].y, hi[i].y, ca.z, sa.z, ca.w, sa.w);
         rope_word16(lo[i].z, hi[i].z, cb.x, sb.x, cb.y, sb.y);
         rope_word16(lo[i].w, hi[i].w, cb.z, sb.z, cb.w, sb.w);
-        uint4* p = base + (s >> 2) * 8 + c;
+        uint4* p = base + (s / LPH) * (2 * LPH) + c;
         p[0] = lo[i];
-        p[4] = hi[i];
+        p[LPH] = hi[i];
       }
     }
   }
 }
 
 // strict precision mode: the same rotation on an fp32 buffer
-template <int NP>
+template <int NP, int HD = 64>
 __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, const float* __restrict__ tab, int M, int T, int H,
                                                     int ld) {
+  constexpr int LPH = HD / 8;                                   // lanes per head = float4 in a head's half
   const int lane = threadIdx.x & 63;
   const int stride = (int)gridDim.x * 4;
-  const int slots = 16 * H;
-  const int c = lane & 7;                                       // values 4 c .. 4 c + 3 of the head's low half
+  const int slots = 2 * LPH * H;
+  const int c = lane & (LPH - 1);                               // values 4 c .. 4 c + 3 of the head's low half
   for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
-    const float4* tr = (const float4*)(tab + (size_t)(row % T) * 64);
-    float4* base = (float4*)(qkv + (size_t)row * ld);           // 16 float4 per head
+    const float4* tr = (const float4*)(tab + (size_t)(row % T) * HD);
+    float4* base = (float4*)(qkv + (size_t)row * ld);           // 2 LPH float4 per head
     float4 lo[NP], hi[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
       if (s < slots) {
-        const float4* p = base + (s >> 3) * 16 + c;
+        const float4* p = base + (s / LPH) * (2 * LPH) + c;
         lo[i] = p[0];
-        hi[i] = p[8];
+        hi[i] = p[LPH];
       }
     }
-    const float4 cs = tr[c], sn = tr[8 + c];
+    const float4 cs = tr[c], sn = tr[LPH + c];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int s = lane + 64 * i;
@@ -116,9 +123,9 @@ __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, co
         rope_pair(lo[i].y, hi[i].y, cs.y, sn.y);
         rope_pair(lo[i].z, hi[i].z, cs.z, sn.z);
         rope_pair(lo[i].w, hi[i].w, cs.w, sn.w);
-        float4* p = base + (s >> 3) * 16 + c;
+        float4* p = base + (s / LPH) * (2 * LPH) + c;
         p[0] = lo[i];
-        p[8] = hi[i];
+        p[LPH] = hi[i];
       }
     }
   }
@@ -141,12 +148,21 @@ static int rope_launch(void (*kern)(Buf*, const float*, int, int, int, int), int
   return 0;
 }
 
-int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld) {
-  if (H < 1 || H > kRopeHeadsWide) return fail(1, "rope: 1..40 heads of 64 (d_model <= 2560)");
+int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld,
+                int head_dim) {
+  if (head_dim != 64 && head_dim != 32) return fail(1, "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
+  if (head_dim == 64 && (H < 1 || H > kRopeHeadsWide)) return fail(1, "rope: 1..40 heads of 64 (d_model <= 2560)");
+  if (head_dim == 32 && (H < 1 || H > kRopeHeads)) return fail(1, "rope: 1..32 heads of 32 (d_model <= 1024)");
   if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
-  if (ld < 3 * H * 64 || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
+  if (ld < 3 * H * head_dim || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
   if (M == 0) return 0;
   if (M > 0x7fffffff - 4 * 8 * 1024) return fail(1, "rope: too many rows");     // 32-bit row arithmetic in the kernels
+  if (head_dim == 32) {
+    static const int occ16h = rope_occupancy(rope16_kernel<kRopePass16Hd32, 32>);
+    static const int occ32h = rope_occupancy(rope32_kernel<kRopePass32Hd32, 32>);
+    return f32 ? rope_launch(rope32_kernel<kRopePass32Hd32, 32>, occ32h, s, (float*)qkv, table, M, T, H, ld)
+               : rope_launch(rope16_kernel<kRopePass16Hd32, 32>, occ16h, s, (bf16_t*)qkv, table, M, T, H, ld);
+  }
   // asked once per instantiation (function-local statics: initialised thread-safely)
   static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16>);
   static const int occ32 = rope_occupancy(rope32_kernel<kRopePass32>);

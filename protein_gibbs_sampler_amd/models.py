@@ -59,8 +59,9 @@ class ESM2(_Wrapper):
     """esm2_t33_650M_UR50D: fair-esm's ESM-2 at 650M parameters (not a model of the original pgen package; the successor of ESM-1b
     in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
     layout (weights.load_fair_esm_checkpoint).  This wrapper promises the 650M model: a checkpoint wider than d_model 2048 (the 3B
-    file, 4.4 times the work per token) is refused with a message naming ESM2_3B.  The other released sizes have heads of 16 / 24 /
-    32 (8M / 35M / 150M) or 128 (15B) and are refused by head width: the engine's attention kernels implement heads of 64."""
+    file, 4.4 times the work per token) is refused with a message naming ESM2_3B, and the 150M file (heads of 32) with one naming
+    ESM2_150M.  The other released sizes have heads of 16 / 24 (8M / 35M) or 128 (15B) and are refused by head width: the engine's
+    attention kernels implement heads of 64 and 32."""
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T33_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
@@ -77,6 +78,17 @@ class ESM2_3B(_Wrapper):
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T36_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
                          "esm2_t36_3B_UR50D.pt", seed, precision, synthetic, config is not None)
+
+
+class ESM2_150M(_Wrapper):
+    """esm2_t30_150M_UR50D: ESM-2 at 150M parameters -- 30 layers, d_model 640, 20 heads of 32, d_ffn 2560; a quarter of the 650M
+    model's GEMM work per token, the size to iterate a design loop with.  The same wrapper as ESM2 with the head-32 instantiations of
+    the attention and rotary kernels (csrc/attn_frag.h).  Sizes come from the file: any checkpoint with heads of 32 (at most 32 of
+    them) or of 64 loads here and runs as the model it is; heads of 32 load ONLY here -- ESM2 and ESM2_3B refuse them by name."""
+
+    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
+        super().__init__(config or dict(_w.ESM2_T30_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
+                         "esm2_t30_150M_UR50D.pt", seed, precision, synthetic, config is not None)
 
 
 class ESM_MSA1(_Wrapper):

@@ -31,21 +31,33 @@ ESM1_T34_CONFIG = dict(ESM1_T6_CONFIG, n_layers=34, d_model=1280, n_heads=20, d_
 
 # ESM-2 (fair-esm `ESM2`, esm2_t33_650M_UR50D -- models.ESM2): the ESM-1b block stack and LM head without a position table and without
 # emb_layer_norm_before; positions enter through rotary embeddings of q and k in every layer (include/pgibbs.h PG_ARCH_ESM2).  Of
-# the released sizes 650M and 3B have heads of 64 (8M / 35M / 150M: 16 / 24 / 32, 15B: 128 -- not engine models).
+# the released sizes 650M and 3B have heads of 64 and 150M heads of 32, the two widths the attention and rotary kernels are built for
+# (8M / 35M: 16 / 24, 15B: 128 -- not engine models).
 ESM2_T33_CONFIG = dict(arch=_lib.PG_ARCH_ESM2, vocab=33, d_model=1280, n_layers=33, n_heads=20, d_ffn=5120, max_positions=1024,
                        pad_idx=1, mask_idx=32, cls_idx=0, eos_idx=2, token_dropout=1, max_msa_rows=0, layer_norm_eps=1e-5)
 # esm2_t36_3B_UR50D -- models.ESM2_3B: 36 layers of 40 heads, 4.4 times the arithmetic of the 650M model per token
 ESM2_T36_CONFIG = dict(ESM2_T33_CONFIG, d_model=2560, n_layers=36, n_heads=40, d_ffn=10240)
+# esm2_t30_150M_UR50D -- models.ESM2_150M: 30 layers of 20 heads of 32; a quarter of the 650M model's GEMM work per token
+ESM2_T30_CONFIG = dict(ESM2_T33_CONFIG, d_model=640, n_layers=30, n_heads=20, d_ffn=2560)
+HEAD_DIMS = (64, 32)         # head widths the attention kernels are built for; 32 runs for ESM-2 only (csrc/attn_frag.h)
+MAX_HEADS_OF_32 = 32         # the rotary kernel's row of heads of 32 (csrc/rope.hip)
 MAX_D_MODEL = 2560           # the row kernels hold at most kMaxChWide * 256 features (csrc/ln_row.h)
 ESM2_650M_MAX_D_MODEL = 2048  # a wider file handed to a config of at most this width (models.ESM2) is refused: see below
 
 
-def rotary_inv_freq():
-    """fair-esm RotaryEmbedding's `inv_freq` for heads of 64, float32: 1.0 / (10000 ** (torch.arange(0, 64, 2).float() / 64)).  The
-    power is taken in double and rounded to float32 -- the values torch's float32 pow gives (numpy's vectorised float32 power is one
-    ulp off at i = 5 and 27), and what the engine builds its cos / sin table from (csrc/engine.hip rope_table)."""
-    p = (10000.0 ** (np.arange(32, dtype=np.float64) / 32.0)).astype(np.float32)
+def rotary_inv_freq(head_dim=64):
+    """fair-esm RotaryEmbedding's `inv_freq` for heads of `head_dim` (64: the default; 32: ESM-2 150M), float32:
+    1.0 / (10000 ** (torch.arange(0, head_dim, 2).float() / head_dim)).  The power is taken in double and rounded to float32 -- the
+    values torch's float32 pow gives (numpy's vectorised float32 power is one ulp off at i = 5 and 27 of 32), and what the engine
+    builds its cos / sin table from (csrc/engine.hip rope_table)."""
+    half = head_dim // 2
+    p = (10000.0 ** (np.arange(half, dtype=np.float64) / float(half))).astype(np.float32)
     return (np.float32(1.0) / p).astype(np.float32)
+
+
+def head_dim_of(cfg):
+    """d_model / n_heads of a configuration (0 when it does not divide)."""
+    return cfg["d_model"] // cfg["n_heads"] if cfg["n_heads"] > 0 and cfg["d_model"] % cfg["n_heads"] == 0 else 0
 
 
 def sinusoidal_positions(n_rows, d, pad_idx):
@@ -66,7 +78,7 @@ def make_config(base, **overrides):
     cfg = dict(base)
     cfg.update(overrides)
     if "n_heads" not in overrides and "d_model" in overrides:
-        cfg["n_heads"] = cfg["d_model"] // 64
+        cfg["n_heads"] = cfg["d_model"] // (head_dim_of(base) or 64)      # the base configuration's head width (64 but for ESM-2 150M)
     return cfg
 
 
@@ -182,10 +194,11 @@ def normalise_state_dict(sd, cfg, fair_esm_layout=True):
         if cfg["arch"] == _lib.PG_ARCH_ESM2 and name.endswith("rot_emb.inv_freq"):
             # a buffer fair-esm recomputes when it builds the module; the engine computes it too -- a file that disagrees is not ESM-2's
             got = (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, dtype=np.float32)).reshape(-1)
-            want_f = rotary_inv_freq()
+            hd = head_dim_of(cfg) or 64
+            want_f = rotary_inv_freq(hd)
             if got.shape != want_f.shape or not np.allclose(got, want_f, rtol=1e-6, atol=0.0):
-                raise ValueError("tensor %r disagrees with rotary inv_freq = 1 / 10000^(2i/64) for heads of 64: the engine's rotary "
-                                 "embedding implements that formula only" % (k,))
+                raise ValueError("tensor %r disagrees with rotary inv_freq = 1 / 10000^(2i/%d) for heads of %d: the engine's rotary "
+                                 "embedding implements that formula only" % (k, hd, hd))
             continue
         if fair_esm_layout:
             name = _strip_fair_esm_prefixes(name)
@@ -358,9 +371,19 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
         if bad:
             raise ValueError("config= disagrees with the checkpoint's own hyper-parameters: %s (given, in the file)" % bad)
     cfg.update(take)
-    if cfg["n_heads"] * 64 != cfg["d_model"]:
+    # Head width.  64 loads against every base configuration; 32 only against one whose own heads are 32 (ESM2_T30_CONFIG:
+    # models.ESM2_150M) -- a wrapper promises its model, as ESM2 refuses the 3B file below; 24 / 16 / 128 load nowhere.
+    hd = cfg["d_model"] / max(1, cfg["n_heads"])
+    if hd == 32 and head_dim_of(base_cfg) != 32:
+        raise ValueError("checkpoint has %d heads of dimension 32: the engine's attention kernels implement head dimension 64 for the "
+                         "configuration it was loaded against; load esm2_t30_150M_UR50D (heads of 32) with models.ESM2_150M / "
+                         "--model esm2_150m" % cfg["n_heads"])
+    if hd == 32 and cfg["n_heads"] > MAX_HEADS_OF_32:
+        raise ValueError("checkpoint has %d heads of dimension 32: the engine's rotary kernel holds at most %d of them (d_model <= %d; "
+                         "esm2_t30_150M_UR50D has 20)" % (cfg["n_heads"], MAX_HEADS_OF_32, 32 * MAX_HEADS_OF_32))
+    if hd not in HEAD_DIMS:
         raise ValueError("checkpoint has %d heads of dimension %g: the engine's attention kernels implement head dimension 64 "
-                         "(every model of pgen.models)" % (cfg["n_heads"], cfg["d_model"] / max(1, cfg["n_heads"])))
+                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D)" % (cfg["n_heads"], hd))
     if cfg["d_model"] > MAX_D_MODEL:
         raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head, rotation) hold at "
                          "most %d features per row, 40 heads of 64 (esm2_t36_3B_UR50D)" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL))
@@ -419,7 +442,7 @@ def to_fair_esm_checkpoint_layout(sd, cfg):
     if cfg["arch"] == _lib.PG_ARCH_ESM2:
         out["encoder.lm_head.weight"] = sd["embed_tokens.weight"]
         for i in range(cfg["n_layers"]):
-            out["encoder.sentence_encoder.layers.%d.self_attn.rot_emb.inv_freq" % i] = rotary_inv_freq()
+            out["encoder.sentence_encoder.layers.%d.self_attn.rot_emb.inv_freq" % i] = rotary_inv_freq(head_dim_of(cfg) or 64)
     return out
 
 

@@ -16,6 +16,12 @@ and the LayerNorm launches at d_model 2560 with their GB/s.  Both sizes record t
 ("gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2": the launches that see every token row) as ms per launch and
 TFLOP/s = 2 rows N K / time.
 
+`--size 150m` measures ESM-2 150M (30 x 640, 20 heads of 32; models.ESM2_150M) alone at the same three shapes, with the attention
+launches (class "attention") next to the rotation, and then the two head-32 kernels against their head-64 counterparts in the same
+process ("head32_vs_head64"): 3-layer models of 20 heads of 32 (d_model 640), 20 heads of 64 (d_model 1280: the same B, T, H for
+the attention launch) and 10 heads of 64 (d_model 640: the same bytes for the rotation), config-2 shape, profiled alternately for
+`--rounds` rounds; ms per launch is the median over the rounds.
+
 Prints one JSON line.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -41,10 +47,11 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3, help="alternations ESM-1b / ESM-2 per shape")
     ap.add_argument("--prof-iters", type=int, default=3, help="iterations of the profiled run")
     ap.add_argument("--layers", type=int, default=None, help="fewer layers for a rehearsal (default: 33, or 36 with --size 3b)")
-    ap.add_argument("--size", choices=["650m", "3b"], default="650m", help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone")
+    ap.add_argument("--size", choices=["650m", "3b", "150m"], default="650m",
+                    help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone; 150m: ESM-2 150M alone, then head 32 against head 64")
     args = ap.parse_args(argv)
     if args.layers is None:
-        args.layers = 36 if args.size == "3b" else 33
+        args.layers = {"3b": 36, "150m": 30}.get(args.size, 33)
 
     import torch
     from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
@@ -52,8 +59,8 @@ def main(argv=None):
         raise SystemExit("esm2_bench: no GPU visible -- nothing is measured without one")
     L_ = _lib.lib()
 
-    def build(cls, base):
-        cfg = weights.make_config(base, n_layers=args.layers)
+    def build(cls, base, **over):
+        cfg = weights.make_config(base, **dict(dict(n_layers=args.layers), **over))
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             m = cls(state_dict=weights.synthetic_state_dict(cfg, seed=0), config=cfg, precision="bf16")
@@ -62,6 +69,9 @@ def main(argv=None):
     if args.size == "3b":
         samplers = {"esm2_3b": build(models.ESM2_3B, weights.ESM2_T36_CONFIG)}
         rotary, model_cfg = "esm2_3b", weights.ESM2_T36_CONFIG
+    elif args.size == "150m":
+        samplers = {"esm2_150m": build(models.ESM2_150M, weights.ESM2_T30_CONFIG)}
+        rotary, model_cfg = "esm2_150m", weights.ESM2_T30_CONFIG
     else:
         samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), "esm2": build(models.ESM2, weights.ESM2_T33_CONFIG)}
         rotary, model_cfg = "esm2", weights.ESM2_T33_CONFIG
@@ -115,10 +125,14 @@ def main(argv=None):
         prof()
         rope_ms, rope_n = lm.prof_get("rope")
         ln_ms, ln_n = lm.prof_get("layernorm")
+        att_ms, att_n = lm.prof_get("attention")
         gemm = {c: lm.prof_get(c) for c in ("gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2")}
         gemm_kernels = {c: lm.prof_get_kernels(c) for c in gemm}
         lm.prof_enable(False)
         rows = B * T
+        if att_n:
+            rec["attention_ms_per_launch"] = round(att_ms / att_n, 5)
+            rec["attention_ms_per_iteration"] = round(att_ms / args.prof_iters, 4)
         rec["rope_launches_per_iteration"] = rope_n // args.prof_iters
         rec["rope_ms_per_launch"] = round(rope_ms / max(rope_n, 1), 5)
         rec["rope_ms_per_iteration"] = round(rope_ms / args.prof_iters, 4)
@@ -139,6 +153,36 @@ def main(argv=None):
                 rec[c] = {"launches": g_n, "ms_per_launch": round(g_ms / g_n, 5), "N": n, "K": k, "kernels": gemm_kernels[c],
                           "TFLOPs": round(2.0 * rows * n * k / (g_ms / g_n * 1e-3) / 1e12, 1)}
         out["shapes"][name] = rec
+    if args.size == "150m":
+        # the head-32 kernels against the head-64 ones: same process, alternating, config-2 shape
+        name, B, L, P = SHAPES[0]
+        rows = B * (L + 2)
+        trio = {"h20x32_d640": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=3),
+                "h20x64_d1280": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3),
+                "h10x64_d640": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3, d_model=640, d_ffn=2560)}
+        jobs = {k: job(s, B, L, P, args.prof_iters) for k, s in trio.items()}
+        for k in trio:
+            jobs[k]()                                   # warm-up of every shape, unprofiled
+        per = {k: {"attention": [], "rope": []} for k in trio}
+        for _ in range(max(args.rounds, 3)):
+            for k, s in trio.items():
+                lm = s.model.model
+                lm.prof_enable(True)
+                lm.prof_reset()
+                jobs[k]()
+                for c in ("attention", "rope"):
+                    c_ms, c_n = lm.prof_get(c)
+                    per[k][c].append(c_ms / max(c_n, 1))
+                lm.prof_enable(False)
+        cmp = {"shape": name, "rounds": max(args.rounds, 3)}
+        for k in trio:
+            dm = trio[k].model.cfg["d_model"]
+            r_ms = statistics.median(per[k]["rope"])
+            cmp[k] = {"attention_ms_per_launch": round(statistics.median(per[k]["attention"]), 5),
+                      "attention_ms_per_launch_rounds": [round(v, 5) for v in per[k]["attention"]],
+                      "rope_ms_per_launch": round(r_ms, 5), "rope_ms_per_launch_rounds": [round(v, 5) for v in per[k]["rope"]],
+                      "rope_GBps": round(rows * 2 * dm * 2 * 2 / (r_ms * 1e-3) / 1e9, 1) if r_ms > 0 else None}
+        out["head32_vs_head64"] = cmp
     print(json.dumps(out))
 
 
