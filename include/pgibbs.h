@@ -317,6 +317,15 @@ int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int
  * that launch ("pp192x256 250t + tail64 40t", "skinny8w 80t x4k"; empty for an ablation variant; "error: ..." for a refused shape).
  * have_ws: split-K scratch is on offer (residual GEMMs of an engine); m_live: rows that hold tokens, 0 = all.  Touches no device. */
 int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int m_live, int n_cu, char* buf, int buf_bytes);
+/* which kernel template an attention launcher picks for a shape, and on which grid, as the text pg_prof_get_kernels reports for that
+ * launch under "attention" ("whole kb18 hd64 split4 512+512wg", "split-f32 kb6 nqb5 hd64 5120wg", "row kb18 w9 rc1 2560wg"; "error:
+ * ..." for a shape the launcher refuses).  kind 0: full attention over n_seq sequences of T tokens (row_step 1: contiguous chains;
+ * else the strided sequences of the MSA column attention), has_pad / has_bias: with a <pad> key mask / ESM-1's bias key; kind 1:
+ * tied row attention of B alignments of R rows x C columns (head_dim, has_bias, row_step unused; order_bh: the (msa, head) count the
+ * split of the row loop is decided on, 0 = B * H).  precision PG_PREC_FP32: the strict launchers, else the 16-bit ones (both operand
+ * flavours share one plan).  A sequence length or column count < 1 is answered by the launcher's own refusal.  Touches no device. */
+int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_C, int R, int H, int head_dim, int has_pad, int has_bias,
+                          int row_step, int order_bh, int n_cu, char* buf, int buf_bytes);
 /* round 6: gemm_rowln.hip (out-projection of d_model = 768 with the next LayerNorm in its epilogue) against the two launches it
  * replaces: ms[0] fused, ms[1] its main loop alone, ms[2] four half-steps + epilogue, ms[3] residual GEMM (256-column tiles),
  * ms[4] LayerNorm kernel; max_diff 0 = x and h bit-identical between the two paths. */

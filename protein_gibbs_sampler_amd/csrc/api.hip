@@ -640,6 +640,21 @@ int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int
   return PG_OK;
 }
 
+int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_C, int R, int H, int head_dim, int has_pad, int has_bias,
+                          int row_step, int order_bh, int n_cu, char* buf, int buf_bytes) {
+  if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
+  if (!buf || buf_bytes < 2 || (kind != 0 && kind != 1) || n_seq_or_B < 1 || H < 1 || n_cu < 1 || (kind == 1 && (R < 1 || n_seq_or_B > 0x7fffffff)))
+    return fail(PG_ERR_INVALID, "pg_dbg_attention_plan: bad argument");
+  const bool strict = precision == PG_PREC_FP32;
+  std::string text;
+  if (kind == 0 && strict) attention_f32_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, row_step, &text);
+  else if (kind == 0) attention_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, row_step, n_cu, &text);
+  else if (strict) msa_row_f32_plan_text((int)n_seq_or_B, R, T_or_C, H, has_pad != 0, &text);
+  else msa_row_plan_text((int)n_seq_or_B, R, T_or_C, H, order_bh, &text);
+  snprintf(buf, (size_t)buf_bytes, "%s", text.c_str());
+  return PG_OK;
+}
+
 // round 6: the full-row out-projection + LayerNorm kernel (gemm_rowln.hip) against the two launches it replaces, on synthetic operands
 // of d_model = 768: ms[0] fused kernel, ms[1] its main loop alone, ms[2] four half-steps + its epilogue, ms[3] residual GEMM on
 // 256-column tiles (default dispatch), ms[4] LayerNorm kernel; max_diff = max |h fused - h unfused| over the 16-bit rows (0: bit-identical).

@@ -49,10 +49,14 @@ __device__ unsigned long long* pg_att_prof;      // [workgroup][wave][8 slots][8
 // HD: the head dimension, 64 or 32 (attn_frag.h).  At 32 a key is 64 bytes of LDS, K + V of 576 keys 72 KB: at least two
 // workgroups per CU on every rung (what limits a rung is the score row in registers, 4 VGPRs per key block, not the LDS -- which is
 // also why the whole-sequence kernel still ends at 576 keys).  The plain and SPLIT head-32 forms compile to <= 128 VGPRs up to 20 key
-// blocks and <= 168 up to 26 without a tighter bound, so four / three workgroups are resident there (attention_resident32: what the
-// host's split of a partial last round counts with; DESIGN 10 has the table).
+// blocks and <= 168 up to 26 without a tighter bound, so four / three workgroups are resident there (DESIGN 10 has the table).
 constexpr int attention_occupancy(int maxkb, int hd) { return hd == 64 ? (maxkb <= 18 ? 2 : 1) : 2; }
-constexpr int attention_resident32(int kb) { return kb <= 20 ? 4 : (kb <= 26 ? 3 : 2); }
+// Workgroups per CU that the HOST counts with when it splits a partial last round (plan_attention): what is resident, not what the
+// launch bound asks the compiler for.  Head 64: two up to 20 key blocks, one beyond.  The two functions differ at kb = 20: its
+// 2 x 80 KB of LDS fit a CU and the plain and SPLIT forms, compiled under the looser bound of 1, still come out at 158 VGPRs + 88
+// AGPRs = two waves per SIMD, so two workgroups do share a CU there and the split counts two.  Head 32: four / three / two (the
+// VGPR figures above).
+constexpr int attention_resident(int kb, int hd) { return hd == 64 ? (kb <= 20 ? 2 : 1) : (kb <= 20 ? 4 : (kb <= 26 ? 3 : 2)); }
 template <int MAXKB, bool PADMASK, bool BIASKV = false, bool SPLIT = false, int HD = 64>
 __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
                                                        int H, int ld_qkv_, int ld_ctx_, int k_off, int v_off,
@@ -330,14 +334,78 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
   if (active && q < T) store_ctx(o, 1.0f / l, ctx + row0 * ld_ctx_ + (size_t)q * ld_ctx + h * HD + fq * 4);
 }
 
-int launch_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int T, int H, int ld_qkv, int ld_ctx,
-                          int k_off, int v_off, const int32_t* key_tok, int pad_idx, const bf16_t* bias_kv, int head_dim) {
-  SeqLayout sl = {1, T, 0, 1};
-  return launch_attention_seq_bf16(s, qkv, ctx, B, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok, pad_idx, bias_kv, head_dim);
+// ------------------------------------------------------------------------------------------------
+// The dispatch.  plan_attention says which kernel template runs on which grid: a pure function of the shape, the device's CU count
+// and the process's PGIBBS_ATTN* switches, without a HIP call, so pg_dbg_attention_plan prints its answers on a machine without a GPU
+// (tests/test_attention_plan_cpu.py pins them for the shapes the project is measured on).  launch_attention_seq_bf16 is the one
+// switch over it.
+// ------------------------------------------------------------------------------------------------
+struct AttentionPlan {
+  std::string error;               // not empty: the call is refused (error code 1)
+  bool whole = true;               // attention_kernel on rung kb; false: attention_long_kernel (more than 576 keys)
+  int kb = 0, hd = 64;
+  bool pad = false, bias = false;  // the kernel's PADMASK / BIASKV form
+  int split_from = 0, split = 1;   // split > 1: the SPLIT form, the pairs from split_from on as `split` workgroups each
+  unsigned grid = 0;               // workgroups of 256 threads; 0: no sequences, nothing to launch
+  int n_qchunk = 0;                // the long kernel's 64-query chunks per (sequence, head) pair
+};
+
+static AttentionPlan plan_attention(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, int n_cu) {
+  AttentionPlan p;
+  p.hd = head_dim, p.pad = has_pad, p.bias = has_bias;
+  auto refuse = [&](const char* why) { p.error = why; return p; };
+  p.error = attention_head_error(head_dim, has_bias);
+  if (!p.error.empty() || n_seq == 0) return p;
+  const int64_t pairs = n_seq * H;
+  if (pairs > 0x7fffffff) return refuse("attention: too many sequences");
+  if (T <= 0) return refuse("attention: empty sequence");
+  // The rung: the T tokens + ESM-1's bias_k / bias_v key.  The forms without the bias key (the Gibbs path, and ragged batches)
+  // take the fine ladder: a chain of 200 residues has 13 key blocks, not 18.
+  p.kb = attention_rung(T + (has_bias ? 1 : 0), attention_fine_ladder() && !has_bias);
+  p.whole = p.kb != 0;
+  if (!p.whole) {                                // more than 576 keys: 288-key tiles (at head 32: 36 KB of LDS for K + V)
+    p.n_qchunk = (T + 63) / 64;
+    if (pairs * p.n_qchunk > 0x7fffffff) return refuse("attention: too many sequences");
+    p.grid = (unsigned)(pairs * p.n_qchunk);
+    return p;
+  }
+  p.grid = (unsigned)pairs;
+  // Round 6: split the pairs of a partial last round (see attention_kernel).  Whole-sequence kernels for chains (row_step 1) of at
+  // least four query blocks, without <pad> mask / bias key (the Gibbs path), counted in attention_resident workgroups per CU.
+  // PGIBBS_ATTN_SPLIT=0 switches it off.
+  static const int split_on = env_int("PGIBBS_ATTN_SPLIT", 1);
+  if (split_on && !has_pad && !has_bias && row_step == 1 && T >= 64) {
+    const long slots = (long)n_cu * attention_resident(p.kb, head_dim);
+    const long rem = pairs % slots;
+    const int nqb = (T + 15) / 16;
+    int sp = rem ? (int)(slots / rem) : 1;
+    if (sp > 4) sp = 4;
+    if (sp > nqb / 4) sp = nqb / 4;            // every part keeps at least one block per wave
+    if (sp >= 2) {
+      p.split = sp;
+      p.split_from = (int)(pairs - rem);
+      p.grid = (unsigned)(p.split_from + rem * sp);
+    }
+  }
+  return p;
+}
+
+// the plan in the text a launch records (note_kernel): the kernel template and its grid
+static std::string plan_text(const AttentionPlan& p) {
+  if (!p.error.empty()) return "error: " + p.error;
+  if (!p.grid) return "nothing";
+  std::string t = (p.whole ? "whole kb" + std::to_string(p.kb) : std::string("long t288")) + " hd" + std::to_string(p.hd);
+  if (p.pad) t += " pad";
+  if (p.bias) t += " bias";
+  if (p.split > 1) return t + " split" + std::to_string(p.split) + " " + std::to_string(p.split_from) + "+" + std::to_string(p.grid - p.split_from) + "wg";
+  return t + " " + std::to_string(p.grid) + "wg";
+}
+void attention_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, int n_cu, std::string* text) {
+  *text = plan_text(plan_attention(n_seq, T, H, head_dim, has_pad, has_bias, row_step, n_cu));
 }
 
 // one rung of the key-block ladder: the kernel's <PADMASK, BIASKV, SPLIT> form for this call.  The bias-key forms are built
-// on the coarse rungs only (attn_frag.h), and at head dimension 64 only (ESM-1 has heads of 64; the launcher refuses the rest).
+// on the coarse rungs only (attn_frag.h), and at head dimension 64 only (ESM-1 has heads of 64; the plan refuses the rest).
 template <int KB, int HD, class... Args>
 static void launch_rung(bool pad, bool bias, bool split, dim3 grid, hipStream_t s, Args... args) {
   auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
@@ -349,71 +417,45 @@ static void launch_rung(bool pad, bool bias, bool split, dim3 grid, hipStream_t 
   else if (split) go(attention_kernel<KB, false, false, true, HD>);
   else go(attention_kernel<KB, false, false, false, HD>);
 }
+// the long kernel's <PADMASK, BIASKV> form; no bias key at head 32
+template <int HD, class... Args>
+static void launch_long(bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
+  auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
+  if constexpr (HD == 64) {
+    if (bias && pad) return go(attention_long_kernel<18, 2, true, true, HD>);
+    if (bias) return go(attention_long_kernel<18, 2, false, true, HD>);
+  }
+  if (pad) go(attention_long_kernel<18, 2, true, false, HD>);
+  else go(attention_long_kernel<18, 2, false, false, HD>);
+}
 
 int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int64_t n_seq, int T, int H, int ld_qkv,
                               int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok, int pad_idx,
                               const bf16_t* bias_kv, int head_dim) {
-  if (head_dim != 64 && head_dim != 32) return fail(1, "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
-  if (head_dim != 64 && bias_kv) return fail(1, "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only");
-  if (n_seq == 0) return 0;
-  if (n_seq * H > 0x7fffffff) return fail(1, "attention: too many sequences");
-  if (T <= 0) return fail(1, "attention: empty sequence");
-  dim3 grid((unsigned)(n_seq * H)), block(256);
-  // The rung: the T tokens + ESM-1's bias_k / bias_v key.  The forms without the bias key (the Gibbs path, and ragged batches)
-  // take the fine ladder: a chain of 200 residues has 13 key blocks, not 18.  PGIBBS_ATTN_LADDER=0: the coarse ladder only.
-  static const int fine_ladder = env_int("PGIBBS_ATTN_LADDER", 1);
-  const int kb = attention_rung(T + (bias_kv ? 1 : 0), fine_ladder && !bias_kv);
-  // Round 6: split the pairs of a partial last round (see attention_kernel).  Whole-sequence kernels for chains (row_step 1) of at
-  // least four query blocks, without <pad> mask / bias key (the Gibbs path).  Resident workgroups: two per CU up to 20 key blocks
-  // (2 x 80 KB of LDS), one beyond; at head 32 four / three / two (attention_resident32).  PGIBBS_ATTN_SPLIT=0 switches it off.
-  static const int split_on = env_int("PGIBBS_ATTN_SPLIT", 1);
-  int split_from = 0, split = 1;
-  if (split_on && !key_tok && !bias_kv && sl.row_step == 1 && T >= 64 && kb) {
-    const long pairs = n_seq * H, slots = (long)device_cu_count() * (head_dim == 64 ? (kb <= 20 ? 2 : 1) : attention_resident32(kb));
-    const long rem = pairs % slots;
-    const int nqb = (T + 15) / 16;
-    int sp = rem ? (int)(slots / rem) : 1;
-    if (sp > 4) sp = 4;
-    if (sp > nqb / 4) sp = nqb / 4;            // every part keeps at least one block per wave
-    if (sp >= 2) {
-      split = sp;
-      split_from = (int)(pairs - rem);
-      grid = dim3((unsigned)(split_from + rem * sp));
-    }
-  }
-  switch (kb) {
-#define PG_RUNG(KB)                                                                                                          \
-  case KB:                                                                                                                   \
-    if (head_dim == 64)                                                                                                      \
-      launch_rung<KB, 64>(key_tok, bias_kv, split > 1, grid, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok,   \
-                          pad_idx, bias_kv, split_from, split);                                                              \
-    else                                                                                                                     \
-      launch_rung<KB, 32>(key_tok, false, split > 1, grid, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok,     \
-                          pad_idx, bias_kv, split_from, split);                                                              \
-    break;
-    PG_RUNG(2) PG_RUNG(4) PG_RUNG(6) PG_RUNG(8) PG_RUNG(10) PG_RUNG(12) PG_RUNG(14) PG_RUNG(16) PG_RUNG(18) PG_RUNG(20)
-    PG_RUNG(22) PG_RUNG(24) PG_RUNG(26) PG_RUNG(28) PG_RUNG(30) PG_RUNG(32) PG_RUNG(34) PG_RUNG(36)
-#undef PG_RUNG
-    default: {                                   // more than 576 keys
-      const int n_qchunk = (T + 63) / 64;
-      if (n_seq * H * n_qchunk > 0x7fffffff) return fail(1, "attention: too many sequences");
-      const dim3 g((unsigned)(n_seq * H * n_qchunk));
-#define PG_ATT_LONG(P, B) hipLaunchKernelGGL((attention_long_kernel<18, 2, P, B>), g, block, 0, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, n_qchunk, key_tok, pad_idx, bias_kv)
-      // head 32: the same 288-key tiles (36 KB of LDS for K + V)
-#define PG_ATT_LONG32(P) hipLaunchKernelGGL((attention_long_kernel<18, 2, P, false, 32>), g, block, 0, s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, n_qchunk, key_tok, pad_idx, bias_kv)
-      if (head_dim == 32) {
-        if (key_tok) PG_ATT_LONG32(true);
-        else PG_ATT_LONG32(false);
-      } else if (key_tok && bias_kv) PG_ATT_LONG(true, true);
-      else if (key_tok) PG_ATT_LONG(true, false);
-      else if (bias_kv) PG_ATT_LONG(false, true);
-      else PG_ATT_LONG(false, false);
-#undef PG_ATT_LONG32
-#undef PG_ATT_LONG
-    }
-  }
+  const AttentionPlan p = plan_attention(n_seq, T, H, head_dim, key_tok != nullptr, bias_kv != nullptr, sl.row_step, device_cu_count());
+  if (!p.error.empty()) return fail(1, p.error);
+  if (!p.grid) return 0;
+  note_kernel(plan_text(p).c_str());
+  auto launch = [&](auto hd) {
+    constexpr int HD = decltype(hd)::value;
+    if (!p.whole)
+      return launch_long<HD>(p.pad, p.bias, dim3(p.grid), s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, p.n_qchunk, key_tok,
+                             pad_idx, bias_kv);
+    visit_rung(p.kb, [&](auto kb) {
+      launch_rung<decltype(kb)::value, HD>(p.pad, p.bias, p.split > 1, dim3(p.grid), s, qkv, ctx, T, H, ld_qkv, ld_ctx, k_off, v_off,
+                                           sl, key_tok, pad_idx, bias_kv, p.split_from, p.split);
+    });
+  };
+  if (head_dim == 64) launch(std::integral_constant<int, 64>{});
+  else launch(std::integral_constant<int, 32>{});
   PG_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int T, int H, int ld_qkv, int ld_ctx,
+                          int k_off, int v_off, const int32_t* key_tok, int pad_idx, const bf16_t* bias_kv, int head_dim) {
+  SeqLayout sl = {1, T, 0, 1};
+  return launch_attention_seq_bf16(s, qkv, ctx, B, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, key_tok, pad_idx, bias_kv, head_dim);
 }
 
 PG_OPS_END

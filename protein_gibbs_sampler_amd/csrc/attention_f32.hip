@@ -572,107 +572,165 @@ __global__ __launch_bounds__(64) void msa_row_apply_f32_kernel(const float* __re
   if (valid) store_ctx64(o, l > 0.f ? 1.0f / l : 0.f, ctx + (((size_t)b * R + r) * C + qi) * ld_ctx, h, split_d);
 }
 
-static int attn_f32_mode() {
-  static const int mode = [] { const char* e = getenv("PGIBBS_ATTN_F32"); return !e ? 0 : (e[0] == 'v' ? -1 : atoi(e)); }();
-  return mode;
+// ------------------------------------------------------------------------------------------------
+// The dispatch: pure plans (no HIP call; pg_dbg_attention_plan prints them, tests/test_attention_plan_cpu.py pins them) and one
+// launch switch per launcher, as in attention.hip.
+// ------------------------------------------------------------------------------------------------
+// PGIBBS_ATTN_F32=valu (or a negative number): the all-VALU cross-check kernels instead of the split-bf16 MFMA ones
+static bool attn_f32_valu() {
+  static const bool valu = [] { const char* e = getenv("PGIBBS_ATTN_F32"); return e && (e[0] == 'v' || atoi(e) < 0); }();
+  return valu;
 }
+
+struct StrictRowPlan {
+  std::string error;
+  bool valu = false;
+  int kb = 10;                     // split kernels: key blocks per tile, 4 (up to 64 columns) or 10
+  int n_chunk = 0, n_ktile = 1;    // 64-query chunks, and key tiles of the scores kernel
+  unsigned grid_scores = 0, grid_apply = 0;      // 0: nothing to launch
+};
+static StrictRowPlan plan_msa_row_f32(int B, int R, int C, int H, bool has_pad) {
+  StrictRowPlan p;
+  if (B == 0 || R == 0) return p;
+  p.valu = attn_f32_valu();
+  if (has_pad && p.valu) { p.error = "row attention: the all-VALU cross-check kernels have no <pad> handling"; return p; }
+  p.n_chunk = (C + 63) / 64;
+  p.kb = C <= 64 ? 4 : 10;
+  p.n_ktile = p.valu ? p.n_chunk : (C <= 64 ? 1 : (C + 159) / 160);      // the all-VALU scores kernel: 64-key tiles
+  p.grid_scores = (unsigned)(B * H * p.n_chunk * p.n_ktile);
+  p.grid_apply = (unsigned)(B * H * R * p.n_chunk);
+  return p;
+}
+static std::string plan_text(const StrictRowPlan& p) {
+  if (!p.error.empty()) return "error: " + p.error;
+  if (!p.grid_apply) return "nothing";
+  return (p.valu ? std::string("row-valu-f32") : "row-split-f32 kb" + std::to_string(p.kb)) + " kt" + std::to_string(p.n_ktile) + " " +
+         std::to_string(p.grid_scores) + "wg, " + std::to_string(p.grid_apply) + "wg";
+}
+void msa_row_f32_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text) { *text = plan_text(plan_msa_row_f32(B, R, C, H, has_pad)); }
 
 int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores, bf16_t* ctx, int split_d, int B, int R,
                                  int C, int H, int ld_qkv, int ld_ctx, int k_off, int v_off, float scale, const int32_t* tok,
                                  int pad_idx) {
-  if (B == 0 || R == 0) return 0;
-  if (tok && attn_f32_mode() < 0) return fail(1, "row attention: the all-VALU cross-check kernels have no <pad> handling");
-  const int n_chunk = (C + 63) / 64;
+  const StrictRowPlan p = plan_msa_row_f32(B, R, C, H, tok != nullptr);
+  if (!p.error.empty()) return fail(1, p.error);
+  if (!p.grid_apply) return 0;
+  note_kernel(plan_text(p).c_str());
   const int ldS = msa_row_scores_ld(C);         // `scores` holds B*H*C rows of ldS floats
-  if (attn_f32_mode() < 0) {
-    hipLaunchKernelGGL(msa_row_scores_f32_kernel, dim3((unsigned)(B * H * n_chunk * n_chunk)), dim3(64), 0, s, qkv, scores, R, C, H,
-                       ld_qkv, k_off, scale, n_chunk, ldS);
-    hipLaunchKernelGGL(msa_row_apply_f32_kernel, dim3((unsigned)(B * H * R * n_chunk)), dim3(64), 0, s, qkv, scores, ctx, split_d,
-                       R, C, H, ld_qkv, ld_ctx, v_off, n_chunk, ldS);
+  auto split = [&](auto kb) {
+    constexpr int KB = decltype(kb)::value;
+    hipLaunchKernelGGL(msa_row_scores_split_kernel<KB>, dim3(p.grid_scores), dim3(256), 0, s, qkv, scores, R, C, H, ld_qkv, k_off,
+                       scale, p.n_chunk, p.n_ktile, ldS, tok, pad_idx);
+    hipLaunchKernelGGL(msa_row_apply_split_kernel<KB>, dim3(p.grid_apply), dim3(256), 0, s, qkv, scores, ctx, split_d, R, C, H,
+                       ld_qkv, ld_ctx, v_off, p.n_chunk, ldS);
+  };
+  if (p.valu) {
+    hipLaunchKernelGGL(msa_row_scores_f32_kernel, dim3(p.grid_scores), dim3(64), 0, s, qkv, scores, R, C, H, ld_qkv, k_off, scale,
+                       p.n_chunk, ldS);
+    hipLaunchKernelGGL(msa_row_apply_f32_kernel, dim3(p.grid_apply), dim3(64), 0, s, qkv, scores, ctx, split_d, R, C, H, ld_qkv,
+                       ld_ctx, v_off, p.n_chunk, ldS);
+  } else if (p.kb == 4) {
+    split(std::integral_constant<int, 4>{});
   } else {
-    if (C <= 64) {
-      hipLaunchKernelGGL(msa_row_scores_split_kernel<4>, dim3((unsigned)(B * H * n_chunk)), dim3(256), 0, s, qkv, scores, R, C, H,
-                         ld_qkv, k_off, scale, n_chunk, 1, ldS, tok, pad_idx);
-      hipLaunchKernelGGL(msa_row_apply_split_kernel<4>, dim3((unsigned)(B * H * R * n_chunk)), dim3(256), 0, s, qkv, scores, ctx,
-                         split_d, R, C, H, ld_qkv, ld_ctx, v_off, n_chunk, ldS);
-    } else {
-      const int n_ktile = (C + 159) / 160;
-      hipLaunchKernelGGL(msa_row_scores_split_kernel<10>, dim3((unsigned)(B * H * n_chunk * n_ktile)), dim3(256), 0, s, qkv, scores,
-                         R, C, H, ld_qkv, k_off, scale, n_chunk, n_ktile, ldS, tok, pad_idx);
-      hipLaunchKernelGGL(msa_row_apply_split_kernel<10>, dim3((unsigned)(B * H * R * n_chunk)), dim3(256), 0, s, qkv, scores, ctx,
-                         split_d, R, C, H, ld_qkv, ld_ctx, v_off, n_chunk, ldS);
-    }
+    split(std::integral_constant<int, 10>{});
   }
   PG_HIP(hipGetLastError());
   return 0;
 }
 
-int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
-                         int ld_qkv, int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok, int pad_idx,
-                         const float* bias_kv, int head_dim) {
-  if (head_dim != 64 && head_dim != 32) return fail(1, "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
-  if (head_dim != 64 && bias_kv) return fail(1, "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only");
-  if (head_dim != 64 && attn_f32_mode() < 0)
-    return fail(1, "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
-  if (n_seq == 0) return 0;
-  if (T <= 0) return fail(1, "attention: empty sequence");
-  if (bias_kv && attn_f32_mode() < 0) return fail(1, "attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)");
-  if (key_tok && sl.row_step != 1 && attn_f32_mode() < 0) return fail(1, "attention: the all-VALU cross-check kernel masks <pad> keys of contiguous chains only");
-  const int mode = attn_f32_mode();
+struct StrictAttentionPlan {
+  std::string error;               // not empty: the call is refused (error code 1)
+  bool valu = false;               // attention_f32_kernel, 64 threads; else attention_split_kernel<kb, nqb>, 256 threads
+  int kb = 0, nqb = 1, hd = 64;    // key blocks per tile and 16-query blocks per wave: one of the seven pairs that are built
+  bool pad = false, bias = false;  // the split kernel's PADMASK / BIASKV form
+  unsigned grid = 0;               // 0: no sequences, nothing to launch
+  int n_qchunk = 0;                // chunks of 64 * nqb queries per (sequence, head) pair
+};
+static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step) {
+  StrictAttentionPlan p;
+  p.hd = head_dim, p.pad = has_pad, p.bias = has_bias, p.valu = attn_f32_valu();
+  auto refuse = [&](const char* why) { p.error = why; return p; };
+  p.error = attention_head_error(head_dim, has_bias);
+  if (!p.error.empty()) return p;
+  if (head_dim != 64 && p.valu)
+    return refuse("attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
+  if (n_seq == 0) return p;
+  if (T <= 0) return refuse("attention: empty sequence");
+  if (has_bias && p.valu) return refuse("attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)");
+  if (has_pad && row_step != 1 && p.valu) return refuse("attention: the all-VALU cross-check kernel masks <pad> keys of contiguous chains only");
   // 16-query blocks per wave of the split kernel (its workgroup = 64 * nqb queries, all of them against each staged K / V tile):
   // the smallest of 1, 2, 3, 5 that covers the sequence with one workgroup, else 5 (PGIBBS_ATTN_F32_NQB overrides: A/B runs)
   static const int nqb_env = env_int("PGIBBS_ATTN_F32_NQB", 0);
   static const int kb_env = env_int("PGIBBS_ATTN_F32_KB", 0);   // experiment: key-tile height
+  const int Tk = T + (has_bias ? 1 : 0);           // every form: plain, <pad> mask, ESM-1's bias key (round 5)
+  const bool one_tile = Tk <= 64;                  // at most 64 keys: a single 64-key tile, one query block per wave
   const int blocks = (T + 15) / 16;
-  int nqb = blocks <= 4 ? 1 : (blocks <= 8 ? 2 : (blocks <= 12 ? 3 : 5));
-  if (nqb_env == 1 || nqb_env == 2 || nqb_env == 3 || nqb_env == 5) nqb = nqb_env;
-  if (mode < 0 || T < 64 || (T == 64 && !bias_kv)) nqb = 1;
-  const int n_qchunk = (T + 64 * nqb - 1) / (64 * nqb);
-  if (n_seq * H * n_qchunk > 0x7fffffff) return fail(1, "attention: too many sequences");
-  const dim3 grid((unsigned)(n_seq * H * n_qchunk));
-  if (mode < 0) {
-    hipLaunchKernelGGL(attention_f32_kernel, grid, dim3(64), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl,
-                       n_qchunk, key_tok, pad_idx);
-  } else {
-    // key tile: 64 keys for short sequences, else 160 (80 KB of LDS: two workgroups per CU; at T = 258 a single 288-key
-    // tile with one workgroup per CU was 1.6x slower)
-    // Long plain sequences (five query blocks per wave): the tile height of 6, 8 or 10 key blocks that pads the keys least -- the
+  p.nqb = blocks <= 4 ? 1 : (blocks <= 8 ? 2 : (blocks <= 12 ? 3 : 5));
+  if (nqb_env == 1 || nqb_env == 2 || nqb_env == 3 || nqb_env == 5) p.nqb = nqb_env;
+  if (p.valu || one_tile) p.nqb = 1;
+  p.n_qchunk = (T + 64 * p.nqb - 1) / (64 * p.nqb);
+  if (n_seq * H * p.n_qchunk > 0x7fffffff) return refuse("attention: too many sequences");
+  p.grid = (unsigned)(n_seq * H * p.n_qchunk);
+  // key tile: 64 keys for short sequences, else 160 (80 KB of LDS: two workgroups per CU; at T = 258 a single 288-key
+  // tile with one workgroup per CU was 1.6x slower)
+  p.kb = one_tile ? 4 : 10;
+  if (!one_tile && p.nqb == 5) {
+    // Long sequences (five query blocks per wave): the tile height of 6, 8 or 10 key blocks that pads the keys least -- the
     // kernel's time follows the padded key count (T = 258: 3 x 96 = 288 keys 18.8 ms per config-2 iteration, 2 x 160 = 320 keys
     // 20.5, 3 x 128 = 384 keys 25.7); ties go to the taller tile.  PGIBBS_ATTN_F32_KB = 6 / 8 / 10 forces one.
-    int kb5 = 10;
-    {
-      const int Tk = T + (bias_kv ? 1 : 0);            // every form: plain, <pad> mask, ESM-1's bias key (round 5)
-      long best = ((long)Tk + 159) / 160 * 160;
-      for (int k : {8, 6}) {
-        const long padded = ((long)Tk + 16 * k - 1) / (16 * k) * (16 * k);
-        if (padded < best) { best = padded; kb5 = k; }
-      }
-      if (kb_env == 6 || kb_env == 8 || kb_env == 10) kb5 = kb_env;
+    long best = ((long)Tk + 159) / 160 * 160;
+    for (int k : {8, 6}) {
+      const long padded = ((long)Tk + 16 * k - 1) / (16 * k) * (16 * k);
+      if (padded < best) { best = padded; p.kb = k; }
     }
-#define PG_ATT_SPLIT(KB, NQ)                                                                                                  \
-  do {                                                                                                                        \
-    if (head_dim == 32 && key_tok) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, false, true, 32>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
-                                                      n_qchunk, key_tok, pad_idx, bias_kv);                                    \
-    else if (head_dim == 32) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, false, false, 32>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
-                                                n_qchunk, key_tok, pad_idx, bias_kv);                                          \
-    else if (bias_kv && key_tok) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, true, true>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
-                                               n_qchunk, key_tok, pad_idx, bias_kv);                                           \
-    else if (bias_kv) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, true, false>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
-                                         n_qchunk, key_tok, pad_idx, bias_kv);                                                 \
-    else if (key_tok) hipLaunchKernelGGL((attention_split_kernel<KB, NQ, false, true>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
-                                         n_qchunk, key_tok, pad_idx, bias_kv);                                                 \
-    else hipLaunchKernelGGL((attention_split_kernel<KB, NQ, false, false>), grid, dim3(256), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl, \
-                            n_qchunk, key_tok, pad_idx, bias_kv);                                                              \
-  } while (0)
-    if (T < 64 || (T == 64 && !bias_kv)) PG_ATT_SPLIT(4, 1);
-    else if (nqb == 1) PG_ATT_SPLIT(10, 1);
-    else if (nqb == 2) PG_ATT_SPLIT(10, 2);
-    else if (nqb == 3) PG_ATT_SPLIT(10, 3);
-    else if (kb5 == 6) PG_ATT_SPLIT(6, 5);
-    else if (kb5 == 8) PG_ATT_SPLIT(8, 5);
-    else PG_ATT_SPLIT(10, 5);
-#undef PG_ATT_SPLIT
+    if (kb_env == 6 || kb_env == 8 || kb_env == 10) p.kb = kb_env;
   }
+  return p;
+}
+static std::string plan_text(const StrictAttentionPlan& p) {
+  if (!p.error.empty()) return "error: " + p.error;
+  if (!p.grid) return "nothing";
+  std::string t = p.valu ? "valu-f32" : "split-f32 kb" + std::to_string(p.kb) + " nqb" + std::to_string(p.nqb);
+  t += " hd" + std::to_string(p.hd);
+  if (p.pad) t += " pad";
+  if (p.bias) t += " bias";
+  return t + " " + std::to_string(p.grid) + "wg";
+}
+void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, std::string* text) {
+  *text = plan_text(plan_attention_f32(n_seq, T, H, head_dim, has_pad, has_bias, row_step));
+}
+
+// one (key tile, query blocks) pair of the split kernel: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32
+template <int KB, int NQB, class... Args>
+static void launch_split(int hd, bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
+  auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
+  if (hd == 32) return pad ? go(attention_split_kernel<KB, NQB, false, true, 32>) : go(attention_split_kernel<KB, NQB, false, false, 32>);
+  if (bias) return pad ? go(attention_split_kernel<KB, NQB, true, true>) : go(attention_split_kernel<KB, NQB, true, false>);
+  return pad ? go(attention_split_kernel<KB, NQB, false, true>) : go(attention_split_kernel<KB, NQB, false, false>);
+}
+
+int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
+                         int ld_qkv, int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok, int pad_idx,
+                         const float* bias_kv, int head_dim) {
+  const StrictAttentionPlan p = plan_attention_f32(n_seq, T, H, head_dim, key_tok != nullptr, bias_kv != nullptr, sl.row_step);
+  if (!p.error.empty()) return fail(1, p.error);
+  if (!p.grid) return 0;
+  note_kernel(plan_text(p).c_str());
+  auto split = [&](auto kb, auto nqb) {
+    launch_split<decltype(kb)::value, decltype(nqb)::value>(p.hd, p.pad, p.bias, dim3(p.grid), s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx,
+                                                            k_off, v_off, sl, p.n_qchunk, key_tok, pad_idx, bias_kv);
+  };
+  using std::integral_constant;
+  if (p.valu)
+    hipLaunchKernelGGL(attention_f32_kernel, dim3(p.grid), dim3(64), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl,
+                       p.n_qchunk, key_tok, pad_idx);
+  else if (p.kb == 4) split(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+  else if (p.kb == 6) split(integral_constant<int, 6>{}, integral_constant<int, 5>{});
+  else if (p.kb == 8) split(integral_constant<int, 8>{}, integral_constant<int, 5>{});
+  else if (p.nqb == 1) split(integral_constant<int, 10>{}, integral_constant<int, 1>{});
+  else if (p.nqb == 2) split(integral_constant<int, 10>{}, integral_constant<int, 2>{});
+  else if (p.nqb == 3) split(integral_constant<int, 10>{}, integral_constant<int, 3>{});
+  else split(integral_constant<int, 10>{}, integral_constant<int, 5>{});
   PG_HIP(hipGetLastError());
   return 0;
 }

@@ -41,6 +41,8 @@
 // Packing two keys into one 128-byte row and keeping the head-64 swizzle was the alternative; it needs a second row index
 // (key >> 1) and chunk base ((key & 1) * 4) in every address and gives the same bank picture, so the 64-byte row was built.
 #pragma once
+#include <type_traits>
+
 #include "kernels.h"
 
 PG_OPS_BEGIN
@@ -65,6 +67,29 @@ inline int attention_rung(int n_keys, bool fine) {
   for (int r : kCoarseRungs)
     if (n_keys <= r * 16) return r;
   return 0;
+}
+// PGIBBS_ATTN_LADDER=0: the coarse ladder only (same bits, more masked key blocks) -- the A/B switch of the fine ladder
+inline bool attention_fine_ladder() {
+  static const int fine = env_int("PGIBBS_ATTN_LADDER", 1);
+  return fine != 0;
+}
+// The launch switch over the ladder: f(std::integral_constant<int, kb>) for an even rung 2 ... 36, so that a launcher names its
+// kernel template once, in a generic lambda, and every rung is instantiated.  false: kb is no rung (more than 576 keys).
+template <int KB = 2, class F>
+inline bool visit_rung(int kb, F&& f) {
+  if constexpr (KB > 36) {
+    return false;
+  } else {
+    if (kb != KB) return visit_rung<KB + 2>(kb, f);
+    f(std::integral_constant<int, KB>{});
+    return true;
+  }
+}
+// what the full-attention plans (attention.hip, attention_f32.hip) refuse before they look at the shape; empty: nothing
+inline std::string attention_head_error(int head_dim, bool has_bias) {
+  if (head_dim != 64 && head_dim != 32) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32";
+  if (head_dim != 64 && has_bias) return "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only";
+  return {};
 }
 
 // ---- tiles ----------------------------------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ struct DevBuf {
 };
 
 struct Prof {
-  struct Rec { int cls; hipEvent_t a, b; std::string kernels; };   // kernels: what the GEMM dispatch noted (pg::note_kernel)
+  struct Rec { int cls; hipEvent_t a, b; std::string kernels; };   // kernels: what the GEMM / attention dispatch noted (pg::note_kernel)
   bool on = false;
   std::vector<Rec> recs;
   std::vector<hipEvent_t> pool;

@@ -89,6 +89,14 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
 // order_bh (0 = B * H): the (msa, head) count the split-R decision is taken on (job-level, so that shards agree);
 // msa_row_split_scratch_bytes: the fp32 scratch `partial` must offer for the split form (0 = this shape does not split)
 size_t msa_row_split_scratch_bytes(int B, int R, int C, int H, int order_bh);
+// What the attention launchers would record for a shape (note_kernel's text: kernel template and grid; "error: ..." for a shape they
+// refuse) -- the dispatch decision alone, no HIP call (pg_dbg_attention_plan).  attention_plan_text: launch_attention_seq_bf16 on a
+// device of n_cu compute units (row_step: SeqLayout's, 1 = contiguous chains); msa_row_plan_text: launch_msa_row_attention_bf16
+// with the scratch of msa_row_split_scratch_bytes on offer; the _f32 pair: the strict launchers (attention_f32.hip)
+void attention_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, int n_cu, std::string* text);
+void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, std::string* text);
+void msa_row_plan_text(int B, int R, int C, int H, int order_bh, std::string* text);
+void msa_row_f32_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text);
 int launch_msa_row_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int R, int C, int H, int ld_qkv,
                                   int ld_ctx, int k_off, int v_off, float scale, float* partial = nullptr,
                                   size_t partial_bytes = 0, int order_bh = 0);
@@ -128,8 +136,8 @@ int launch_gelu_f32(hipStream_t s, float* p, int64_t n);
 // duplicate hi block (for an out-projection on the fused three-product kernel, gemm_split3_fused)
 int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
                          int ld_qkv, int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok = nullptr,
-                         int pad_idx = -1, const float* bias_kv = nullptr,      // bias_kv: fp32 [bias_k | bias_v]
-                         int head_dim = 64);                                    // 64, or 32 (split kernel only, without bias_kv) (ESM-1)
+                         int pad_idx = -1, const float* bias_kv = nullptr,      // bias_kv: fp32 [bias_k | bias_v] (ESM-1)
+                         int head_dim = 64);                                    // 64, or 32 (split kernel only, without bias_kv)
 // strict tied row attention; `scores` is an fp32 scratch of B*H*C rows of msa_row_scores_ld(C) floats
 static inline int msa_row_scores_ld(int C) { return (C + 3) & ~3; }
 // tok (optional): the int32 token buffer [B][R][C] of a batch that holds <pad> (ragged MSA lists): fair-esm's padding semantics

@@ -222,74 +222,90 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
   }
 }
 
-// split-R geometry, shared by the launcher and by the engine's scratch sizing
-static void row_split_geometry(int n_bh, int obh, int R, int C, int& nw, int& n_qblk, int& n_rc, int& kb) {
-  const int chunks = (C + 15) / 16;
-  nw = C <= 64 ? 4 : (C <= 288 ? 9 : 8);
-  n_qblk = (chunks + nw - 1) / nw;
-  n_rc = 1;
-  if (obh * ((C + 63) / 64) < 384 && obh * n_qblk < 384 && R >= 8) {      // few (msa, head, 64-query) units: the chip would idle
-    n_rc = 512 / (obh * n_qblk);                      // two whole rounds of one workgroup per CU (measured best: 512 vs 768)
-    if (n_rc > R / 4) n_rc = R / 4;
-    if (n_rc < 1) n_rc = 1;
-  }
+// ------------------------------------------------------------------------------------------------
+// The dispatch, as in attention.hip: plan_msa_row is a pure function of the shape, the scratch on offer and PGIBBS_ATTN_LADDER
+// (pg_dbg_attention_plan prints it, tests/test_attention_plan_cpu.py pins it); the launcher and the engine's scratch sizing share it.
+// ------------------------------------------------------------------------------------------------
+// Waves per workgroup on rung kb: 4 up to 64 columns, beyond that the widest the register budget of the score fragments allows
+// (9 waves up to 288 keys, 8 beyond).  The one definition: the plan's geometry and the kernel template's NW both come from here.
+constexpr int row_attention_waves(int kb) { return kb <= 4 ? 4 : (kb <= 18 ? 9 : 8); }
+static_assert(row_attention_waves(20) == row_attention_waves(24), "the 20 -> 24 exception below keeps the query blocks it was decided on");
+
+struct RowPlan {
+  const char* error = nullptr;     // not null: the call is refused with error_code
+  int error_code = 0;
+  int kb = 0, nw = 0;              // msa_row_attention_kernel<kb, nw, mode>
+  int n_qblk = 0;                  // workgroups (nw * 16 queries each) per (msa, head)
+  int n_rc = 1;                    // > 1: the split-R form (modes 1, 3, 2) over n_rc row chunks, else the fused mode 0
+  size_t split_bytes = 0;          // fp32 scratch the split-R form of this shape needs (0: the shape does not split)
+  unsigned grid = 0;               // workgroups of nw waves (modes 0, 1, 2); 0: nothing to launch
+  unsigned grid_reduce = 0;        // mode 3: workgroups of one wave
+};
+// order_bh: the (msa, head) count the split-R decision is taken on.  The row loop is split over workgroups when the (msa, head,
+// query-chunk) grid alone cannot fill the chip; the number of row chunks fixes the order of the sum over alignment rows, so it is
+// derived from order_bh -- the (msa, head) count of the JOB, or of ONE template in a batched generate_single -- not from this
+// call's share.  scratch_bytes: the fp32 scratch on offer; a split-R form that does not fit runs fused.
+static RowPlan plan_msa_row(int B, int R, int C, int H, int order_bh, size_t scratch_bytes) {
+  RowPlan p;
+  auto refuse = [&](int code, const char* why) { p.error_code = code, p.error = why; return p; };
+  if (B == 0 || R == 0) return p;
+  if (C <= 0) return refuse(1, "row attention: empty alignment");
+  if (C > 576) return refuse(5, "row attention: alignments wider than 576 token columns (<cls> + 575 residues) take the fp32-scores path");
+  const int n_bh = B * H, obh = order_bh > 0 ? order_bh : n_bh;
   // a rung for every even block count (round 4; PGIBBS_ATTN_LADDER=0: the coarse ladder only -- same bits, attn_frag.h)
-  static const int fine = env_int("PGIBBS_ATTN_LADDER", 1);
-  kb = attention_rung(C, fine);
+  p.kb = attention_rung(C, attention_fine_ladder());
+  p.nw = row_attention_waves(p.kb);
+  p.n_qblk = ((C + 15) / 16 + p.nw - 1) / p.nw;
+  if (obh * ((C + 63) / 64) < 384 && obh * p.n_qblk < 384 && R >= 8) {      // few (msa, head, 64-query) units: the chip would idle
+    p.n_rc = 512 / (obh * p.n_qblk);                  // two whole rounds of one workgroup per CU (measured best: 512 vs 768)
+    if (p.n_rc > R / 4) p.n_rc = R / 4;
+    if (p.n_rc < 1) p.n_rc = 1;
+  }
   // One exception, measured (profiles/r04_attention_key_block_ladder_ab.txt): one template of 32 x 301 (288 workgroups, split-R form)
   // takes 0.97 ms on the 20-block rung against 0.88 on the 24-block one, while bigger grids gain 10 %.  (The 20-block rung's 80 KB of
   // LDS lets two workgroups share a CU; whether that is the cause was not established.)  Grids below two rounds stay on 24 blocks.
-  if (kb == 20 && (long)n_bh * n_qblk * n_rc < 512) kb = 24;
-}
-// fp32 scratch of the split-R form: n_rc partial score maps per (msa, head), then every wave's P fragments (1 KiB each)
-static size_t row_split_bytes(int n_bh, int C, int nw, int n_qblk, int n_rc, int kb) {
-  return (size_t)n_bh * n_rc * C * (kb * 16) * 4 + (size_t)n_bh * n_qblk * nw * (kb / 2) * 1024;
+  if (p.kb == 20 && (long)n_bh * p.n_qblk * p.n_rc < 512) p.kb = 24;
+  // fp32 scratch of the split-R form: n_rc partial score maps per (msa, head), then every wave's P fragments (1 KiB each)
+  if (p.n_rc > 1) p.split_bytes = (size_t)n_bh * p.n_rc * C * (p.kb * 16) * 4 + (size_t)n_bh * p.n_qblk * p.nw * (p.kb / 2) * 1024;
+  if (p.split_bytes > scratch_bytes) p.n_rc = 1;
+  p.grid = (unsigned)(n_bh * p.n_qblk * p.n_rc);
+  p.grid_reduce = p.n_rc > 1 ? (unsigned)(n_bh * p.n_qblk * p.nw) : 0;
+  return p;
 }
 // bytes of fp32 scratch the split-R form needs for B alignments (0: the shape does not split)
 size_t msa_row_split_scratch_bytes(int B, int R, int C, int H, int order_bh) {
-  if (C > 576) return 0;
-  int nw, n_qblk, n_rc, kb;
-  row_split_geometry(B * H, order_bh > 0 ? order_bh : B * H, R, C, nw, n_qblk, n_rc, kb);
-  return n_rc <= 1 ? 0 : row_split_bytes(B * H, C, nw, n_qblk, n_rc, kb);
+  return plan_msa_row(B, R, C, H, order_bh, ~(size_t)0).split_bytes;
+}
+
+static std::string plan_text(const RowPlan& p) {
+  if (p.error) return std::string("error: ") + p.error;
+  if (!p.grid) return "nothing";
+  std::string t = "row kb" + std::to_string(p.kb) + " w" + std::to_string(p.nw) + " rc" + std::to_string(p.n_rc) + " " + std::to_string(p.grid) + "wg";
+  return p.n_rc > 1 ? t + ", reduce " + std::to_string(p.grid_reduce) + "x1w, " + std::to_string(p.grid) + "wg" : t;
+}
+// with the scratch msa_row_split_scratch_bytes asks for on offer, as the engine launches it
+void msa_row_plan_text(int B, int R, int C, int H, int order_bh, std::string* text) {
+  *text = plan_text(plan_msa_row(B, R, C, H, order_bh, ~(size_t)0));
 }
 
 int launch_msa_row_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int R, int C, int H, int ld_qkv,
                                   int ld_ctx, int k_off, int v_off, float scale, float* partial, size_t partial_bytes,
                                   int order_bh) {
-  if (B == 0 || R == 0) return 0;
-  if (C <= 0) return fail(1, "row attention: empty alignment");
-  if (C > 576) return fail(5, "row attention: alignments wider than 576 token columns (<cls> + 575 residues) take the fp32-scores path");
-  const int n_bh = B * H;
-  // workgroup width: 4 waves up to 64 columns, beyond that the widest the register budget of the score fragments allows
-  // (9 waves up to 288 keys, 8 beyond).  The row loop is split over workgroups when the (msa, head, query-chunk) grid alone
-  // cannot fill the chip; the number of row chunks fixes the order of the sum over alignment rows, so it is derived from
-  // order_bh -- the (msa, head) count of the JOB, or of ONE template in a batched generate_single -- not from this call's share
-  int nw, n_qblk, n_rc, kb_;
-  row_split_geometry(n_bh, order_bh > 0 ? order_bh : n_bh, R, C, nw, n_qblk, n_rc, kb_);
-  if (!partial || (n_rc > 1 && row_split_bytes(n_bh, C, nw, n_qblk, n_rc, kb_) > partial_bytes)) n_rc = 1;
-#define PG_ROWATT_K(KB, NWV, MODE, GRID, BLOCK)                                                                          \
-  hipLaunchKernelGGL((msa_row_attention_kernel<KB, NWV, MODE>), GRID, BLOCK, 0, s, qkv, ctx, R, C, H, ld_qkv, ld_ctx,     \
-                     k_off, v_off, scale, n_qblk, n_bh, n_rc, partial)
-#define PG_ROWATT(KB, NWV)                                                                                              \
-  else if (kb_ == KB) {                                                                                                 \
-    const dim3 block(NWV * 64), grid((unsigned)(n_bh * n_qblk * n_rc));                                                 \
-    if (n_rc == 1) {                                                                                                    \
-      PG_ROWATT_K(KB, NWV, 0, grid, block);                                                                             \
-    } else {                                                                                                            \
-      PG_ROWATT_K(KB, NWV, 1, grid, block);                                                                             \
-      PG_ROWATT_K(KB, NWV, 3, dim3((unsigned)(n_bh * n_qblk * NWV)), dim3(64));                                         \
-      PG_ROWATT_K(KB, NWV, 2, grid, block);                                                                             \
-    }                                                                                                                   \
-  }
-  if (false) {}
-  PG_ROWATT(2, 4) PG_ROWATT(4, 4) PG_ROWATT(6, 9) PG_ROWATT(8, 9) PG_ROWATT(10, 9) PG_ROWATT(12, 9) PG_ROWATT(14, 9) PG_ROWATT(16, 9)
-  PG_ROWATT(18, 9) PG_ROWATT(20, 8) PG_ROWATT(22, 8) PG_ROWATT(24, 8) PG_ROWATT(26, 8) PG_ROWATT(28, 8) PG_ROWATT(30, 8) PG_ROWATT(32, 8)
-  PG_ROWATT(34, 8) PG_ROWATT(36, 8)
-#undef PG_ROWATT
-#undef PG_ROWATT_K
-  else {
-    return fail(5, "row attention: alignments wider than 576 token columns (<cls> + 575 residues) take the fp32-scores path");
-  }
+  const RowPlan p = plan_msa_row(B, R, C, H, order_bh, partial ? partial_bytes : 0);
+  if (p.error) return fail(p.error_code, p.error);
+  if (!p.grid) return 0;
+  note_kernel(plan_text(p).c_str());
+  visit_rung(p.kb, [&](auto kb) {
+    constexpr int KB = decltype(kb)::value, NW = row_attention_waves(KB);
+    auto go = [&](auto* kernel, dim3 grid, dim3 block) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, s, qkv, ctx, R, C, H, ld_qkv, ld_ctx, k_off, v_off, scale, p.n_qblk, B * H, p.n_rc, partial);
+    };
+    const dim3 grid(p.grid), block(NW * 64);
+    if (p.n_rc == 1) return go(msa_row_attention_kernel<KB, NW, 0>, grid, block);
+    go(msa_row_attention_kernel<KB, NW, 1>, grid, block);
+    go(msa_row_attention_kernel<KB, NW, 3>, dim3(p.grid_reduce), dim3(64));
+    go(msa_row_attention_kernel<KB, NW, 2>, grid, block);
+  });
   PG_HIP(hipGetLastError());
   return 0;
 }

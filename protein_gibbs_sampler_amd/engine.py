@@ -374,7 +374,8 @@ class NativeMaskedLM:
         _lib.check(_lib.lib().pg_prof_reset(self.handle))
 
     def prof_get_kernels(self, kernel_class):
-        """The kernels the GEMM dispatch picked for the profiled launches of `kernel_class` (pg_prof_get_kernels)."""
+        """The kernels the GEMM or attention dispatch picked for the profiled launches of `kernel_class` ("gemm_qkv", ..., "attention":
+        pg_prof_get_kernels), distinct texts joined by " | "."""
         buf = ctypes.create_string_buffer(1024)
         _lib.check(_lib.lib().pg_prof_get_kernels(self.handle, kernel_class.encode(), buf, len(buf)))
         return buf.value.decode()

@@ -12,6 +12,7 @@
 
 namespace pg {
 int fail(int code, const std::string& msg) { fprintf(stderr, "%s\n", msg.c_str()); return code; }
+void note_kernel(const char* label, long, int) { fprintf(stderr, "plan: %s\n", label); }      // what the launcher's dispatch picked
 }
 
 int main(int argc, char** argv) {
