@@ -93,11 +93,13 @@ inline std::string attention_head_error(int head_dim, bool has_bias) {
 }
 
 // ---- tiles ----------------------------------------------------------------------------------------------------------------
-// byte offset of 16-byte chunk `chunk` inside tile row `row`, and from the start of the tile
+// byte offset of 16-byte chunk `chunk` inside tile row `row`, and from the start of the tile.  The head-64 permutation is also the
+// GEMM tile kernels' 128-byte-row layout (gemm_tile.h), which takes it from here, DMA-source side and fragment side:
+#define PG_TILE128_CHUNK(row, chunk) ((chunk) ^ ((row) & 7))
 template <int HD = 64>
 __device__ __forceinline__ int tile_swz(int row, int chunk) {
   static_assert(HD == 64 || HD == 32, "head dimension 64 or 32");
-  return (HD == 64 ? chunk ^ (row & 7) : chunk ^ ((row >> 1) & 2)) << 4;
+  return (HD == 64 ? PG_TILE128_CHUNK(row, chunk) : chunk ^ ((row >> 1) & 2)) << 4;
 }
 template <int HD = 64>
 __device__ __forceinline__ int tile_addr(int row, int chunk) { return row * (HD * 2) + tile_swz<HD>(row, chunk); }

@@ -145,7 +145,7 @@ template <typename T> __device__ __forceinline__ T ct_ldg(const void* p) {
 #define CT_DEV_AUX 16
 #endif
 constexpr int CT_SC1 = CT_DEV_AUX;
-__device__ __forceinline__ rsrc_t ct_rsrc(const void* base) { return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000); }
+__device__ __forceinline__ rsrc_t ct_rsrc(const void* base) { return buf_rsrc(base); }
 template <typename T> __device__ __forceinline__ T ct_ld_dev(rsrc_t rs, int byte_off) {
   static_assert(sizeof(T) == 16, "16-byte accesses");
   return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, CT_SC1));

@@ -21,7 +21,8 @@
 //   * HBM/L2 -> LDS by direct `global_load_lds` (16 B/lane, no VGPR round trip); 16-B LDS chunks are XOR-swizzled by
 //     permuting the per-lane SOURCE address (the LDS image of a glds is lane-linear), so every ds_read_b128
 //     lane group touches 16 distinct 16-B slots (conflict-free).
-//   * 1-D grid remapped so each XCD (private L2) owns a contiguous range of tiles.
+//   * 1-D grid remapped so each XCD (private L2) owns a contiguous range of tiles (xcd_contiguous / grouped_tile, gemm_tile.h, where
+//     the two swizzle pairs and the row-shaped buffer access of the epilogues are defined too).
 //   * epilogues fused: +bias, GELU, bf16 pack, fp32 residual read-modify-write.
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,7 +37,7 @@ template <int ROWS, int NW>
 __device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ src, int ld, int row0, int k0, char* lds_tile,
                                            int wave, int lane) {
   const int rl = lane >> 3;
-  const int c = (lane & 7) ^ rl;
+  const int c = PG_TILE128_CHUNK(rl, lane & 7);
 #pragma unroll
   for (int i = 0; i < ROWS / 8 / NW; ++i) {
     const int rb = wave + i * NW;
@@ -63,12 +64,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_bf16_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave % NWM, wn = wave / NWM;
 
-  // XCD-aware bijective remap: block b runs on XCD b % 8; give each XCD a contiguous tile range.
+  // each XCD a contiguous tile range (gemm_tile.h); no grouping
   int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = n_tiles >> 3, r = n_tiles & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  bid = xcd_contiguous(bid, n_tiles);
   const int m0 = (bid / tiles_n) * BM;
   const int n0 = (bid % tiles_n) * BN;
 
@@ -86,7 +84,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_bf16_kernel(
 
   const int fr = lane & 15;        // fragment row within a 16-row MFMA tile
   const int fq = lane >> 4;        // k-chunk (8 bf16) within a 32-wide MFMA k-step
-  const int sw = fr & 7;           // row & 7 (tile bases are multiples of 16)
   int cur = 0;
   for (int t = 0; t < nk; ++t) {
     char* xt = smem + cur * TILE_BYTES;
@@ -98,7 +95,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_bf16_kernel(
     }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const int coff = (((fq + 4 * kk) ^ sw) << 4);
+      const int coff = PG_TILE128_CHUNK(fr, fq + 4 * kk) << 4;      // tile bases are multiples of 16: row & 7 = fr & 7
       bf16x8 wf[TN], xf[TM];
 #pragma unroll
       for (int i = 0; i < TN; ++i) wf[i] = *(const bf16x8*)(wt + (wn * WN + i * 16 + fr) * 128 + coff);
@@ -153,21 +150,65 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_bf16_kernel(
 // 64 lanes x 16 B = 1 KiB of contiguous output (bf16: two 512-B rows; fp32: one 1-KB row; the fp32 residual
 // read-modify-write uses the same row-shaped accesses, 16 loads in flight per lane).
 // ------------------------------------------------------------------------------------------------
-// The epilogue's row-shaped stores (and the residual rows it reads) are streamed with the non-temporal policy: a round of
-// tiles writes 4 MB per XCD -- its whole L2 -- which otherwise evicts the X / W k-slices the main loops share through it.
-// Measured at the four ESM-1b shapes: QKV 0.589 -> 0.580 ms, fc1 0.859 -> 0.818, out-proj 0.308 -> 0.285, fc2 0.856 -> 0.818;
-// whole iteration 96.1 -> 94.1 ms.  (Non-temporal loads/stores in LayerNorm: no effect.)
-#define PG_EPI_AUX 2                                             /* buffer ops: nt */
-#define PG_EPI_STORE(p, v) __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, v), (u32x4_t*)(p))
-__device__ __forceinline__ rsrc_t row_rsrc(void* base) { return __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000); }
-__device__ __forceinline__ f32x4 buf_load_f32x4(rsrc_t rs, int voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, PG_EPI_AUX));
-}
-// Stores keep the row step in the VGPR offset: with an SGPR soffset the compiler's hazard recogniser assumes a 128-bit
-// store's data registers may be overwritten by the very next VALU instruction, and on gfx950 that corrupted the last
-// dword of the stored row (seen as wrong .w components in lanes 12-15 of each 16) -- with soffset = 0 it pads the hazard.
-__device__ __forceinline__ void buf_store_f32x4(f32x4 v, rsrc_t rs, int voff, int row_off) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, voff + row_off, 0, PG_EPI_AUX);
+// (row-shaped buffer access and the non-temporal policy: gemm_tile.h)
+// out += tile, the residual read-modify-write of the 8-wave kernel: a wave holds token rows wm*16 XJ + j*16 + fr, j < XJ (XJ = 8: the
+// 256 x 256 tile, 6: 192 x 256).  Two phases of 16 XJ staged rows x 1 KiB; in phase p every wave stages its columns j = p XJ/2 ..
+// (8 XJ token rows per wave group), then wave w owns the 2 XJ staged rows w * 2 XJ .. = token rows grow(p) .. and moves them as whole
+// 1-KiB rows.  Buffer ops (gemm_tile.h): wave-uniform row base in the resource, the row step in the offset.  The row loads of a phase
+// (8 XJ VGPRs) are issued BEFORE that phase's LDS staging, and phase 1's loads before phase 0's stores, so a tile exposes about one
+// memory latency instead of four.  
+template <int XJ>
+__device__ __forceinline__ void epilogue_resid(f32x4 (&acc)[4][XJ], char* smem, int wm, int wn, int wave, int lane, int m0, int n0,
+                                               const float* __restrict__ bias, void* __restrict__ out, int ldo) {
+  constexpr int RPW = 2 * XJ;                                     // rows per phase and wave
+  const int fr = lane & 15, fq = lane >> 4;
+  __syncthreads();                                                // every wave is done with the operand ring
+  auto stage = [&](int p) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float4 b4 = *(const float4*)(bias + n0 + wn * 64 + i * 16 + fq * 4);
+      const int c = wn * 16 + i * 4 + fq;                         // 16-B chunk of the 1-KB row
+#pragma unroll
+      for (int jj = 0; jj < XJ / 2; ++jj) {
+        const int sr = wm * (8 * XJ) + jj * 16 + fr;
+        const f32x4 a = acc[i][p * (XJ / 2) + jj];
+        *(float4*)(smem + sr * 1024 + ((c ^ (sr & 63)) << 4)) = make_float4(a[0] + b4.x, a[1] + b4.y, a[2] + b4.z, a[3] + b4.w);
+      }
+    }
+  };
+  // one value in two spellings: hipcc's register allocation of the 16 XJ row registers follows the form, and each tile height keeps
+  // the one it was tuned with (the other form: 245 -> 256 VGPRs and 36 bytes of scratch at XJ = 8)
+  auto grow = [&](int p) {
+    return m0 + (wave >> 2) * (16 * XJ) + (XJ == 8 ? (p * 4 + (wave & 3)) * RPW : p * (8 * XJ) + (wave & 3) * RPW);
+  };
+  const rsrc_t rs0 = row_rsrc((float*)out + (size_t)grow(0) * ldo + n0);
+  const rsrc_t rs1 = row_rsrc((float*)out + (size_t)grow(1) * ldo + n0);
+  const int rstep = ldo * 4, voff = lane * 16;
+  f32x4 r0[RPW], r1[RPW];
+#pragma unroll
+  for (int it = 0; it < RPW; ++it) r0[it] = buf_load_f32x4(rs0, voff, it * rstep);
+  __builtin_amdgcn_sched_barrier(0);
+  stage(0);
+  __builtin_amdgcn_sched_barrier(0);          // r1 must not be hoisted above the staging (register budget)
+#pragma unroll
+  for (int it = 0; it < RPW; ++it) r1[it] = buf_load_f32x4(rs1, voff, it * rstep);
+  __builtin_amdgcn_sched_barrier(0);
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < RPW; ++it) {
+    const int sr = wave * RPW + it;
+    const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
+    buf_store_f32x4(r0[it] + v, rs0, voff, it * rstep);
+  }
+  __syncthreads();
+  stage(1);
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < RPW; ++it) {
+    const int sr = wave * RPW + it;
+    const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
+    buf_store_f32x4(r1[it] + v, rs1, voff, it * rstep);
+  }
 }
 
 template <int EPI, bool NO_STORE = false>
@@ -178,9 +219,9 @@ __device__ __forceinline__ void epilogue_256(f32x4 (&acc)[4][8], char* smem, int
   // fp32-staged epilogues (fp32 outputs, and fc1's bf16+GELU).  Two phases; in phase p EVERY wave stages its accumulator
   // columns j = 4p..4p+3 (64 token rows per wave group -> 128 staged rows x 1 KiB = all of LDS), then wave w owns the 16
   // staged rows w*16.. = token rows m0 + (w>>2)*128 + (4p + (w&3))*16 + it and moves them out as whole 1-KiB rows.
-  // Residual variant: the 16 row loads of a phase (64 VGPRs) are issued BEFORE that phase's LDS staging, and phase 1's
-  // loads before phase 0's stores, so a tile exposes about one memory latency instead of four.
-  if (EPI == EPI_BF16_GELU || EPI == EPI_F32 || EPI == EPI_F32_GELU || EPI == EPI_F32_RESID) {
+  // (The residual read-modify-write is epilogue_resid, called by the kernel directly.)
+  static_assert(EPI != EPI_F32_RESID, "residual epilogue: epilogue_resid");
+  if (EPI == EPI_BF16_GELU || EPI == EPI_F32 || EPI == EPI_F32_GELU) {
     auto stage = [&](int p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -219,41 +260,8 @@ __device__ __forceinline__ void epilogue_256(f32x4 (&acc)[4][8], char* smem, int
           v.y = gelu_bf16out_pack2(a.z, a.w);
           v.z = gelu_bf16out_pack2(b.x, b.y);
           v.w = gelu_bf16out_pack2(b.z, b.w);
-          PG_EPI_STORE((uint4*)(ob + (size_t)r2 * ldo + c8 * 8), v);
+          PG_NT_STORE((uint4*)(ob + (size_t)r2 * ldo + c8 * 8), v);
         }
-      }
-      return;
-    }
-    if (EPI == EPI_F32_RESID) {
-      // Row-shaped accesses as buffer ops: wave-uniform row base in the resource, the row step in an SGPR offset, one
-      // VGPR (lane*16) for all 64 accesses -- 64-bit per-row VGPR addresses would not leave room for 32 rows in flight.
-      const rsrc_t rs0 = row_rsrc((float*)out + (size_t)grow(0) * ldo + n0);
-      const rsrc_t rs1 = row_rsrc((float*)out + (size_t)grow(1) * ldo + n0);
-      const int rstep = ldo * 4, voff = lane * 16;
-      f32x4 r0[16], r1[16];
-#pragma unroll
-      for (int it = 0; it < 16; ++it) r0[it] = buf_load_f32x4(rs0, voff, it * rstep);
-      __builtin_amdgcn_sched_barrier(0);
-      stage(0);
-      __builtin_amdgcn_sched_barrier(0);          // r1 must not be hoisted above the staging (register budget)
-#pragma unroll
-      for (int it = 0; it < 16; ++it) r1[it] = buf_load_f32x4(rs1, voff, it * rstep);
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();
-#pragma unroll
-      for (int it = 0; it < 16; ++it) {
-        const int sr = wave * 16 + it;
-        const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
-        buf_store_f32x4(r0[it] + v, rs0, voff, it * rstep);
-      }
-      __syncthreads();
-      stage(1);
-      __syncthreads();
-#pragma unroll
-      for (int it = 0; it < 16; ++it) {
-        const int sr = wave * 16 + it;
-        const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
-        buf_store_f32x4(r1[it] + v, rs1, voff, it * rstep);
       }
       return;
     }
@@ -293,60 +301,8 @@ __device__ __forceinline__ void epilogue_256(f32x4 (&acc)[4][8], char* smem, int
       const int row = (wave * 16 + it) * 2 + (lane >> 5);
       const uint4 v = *(const uint4*)(smem + row * 512 + ((c ^ (row & 31)) << 4));
       if (NO_STORE) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); continue; }    // ablation: all but the global stores
-      PG_EPI_STORE((uint4*)((bf16_t*)out + (size_t)(m0 + row) * ldo + n0 + c * 8), v);
+      PG_NT_STORE((uint4*)((bf16_t*)out + (size_t)(m0 + row) * ldo + n0 + c * 8), v);
     }
-  }
-}
-
-// out += tile for the 192 x 256 tile (XJ = 6): a wave holds token rows wm*96 + j*16 + fr, j < 6.  Two phases of 96 staged rows x
-// 1 KiB; in phase p every wave stages its columns j = 3p .. 3p+2 (48 token rows per wave group), then wave w owns the 12 staged
-// rows w*12 .. = token rows m0 + (w>>2)*96 + p*48 + (w&3)*12 + it.  x_old + (acc + bias) per element, as epilogue_256's residual
-// branch computes it; the same early row loads (phase 1's before phase 0's stores).
-__device__ __forceinline__ void epilogue_192_resid(f32x4 (&acc)[4][6], char* smem, int wm, int wn, int wave, int lane, int m0,
-                                                   int n0, const float* __restrict__ bias, void* __restrict__ out, int ldo) {
-  const int fr = lane & 15, fq = lane >> 4;
-  __syncthreads();
-  auto stage = [&](int p) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 b4 = *(const float4*)(bias + n0 + wn * 64 + i * 16 + fq * 4);
-      const int c = wn * 16 + i * 4 + fq;                         // 16-B chunk of the 1-KB row
-#pragma unroll
-      for (int jj = 0; jj < 3; ++jj) {
-        const int sr = wm * 48 + jj * 16 + fr;
-        const f32x4 a = acc[i][p * 3 + jj];
-        *(float4*)(smem + sr * 1024 + ((c ^ (sr & 63)) << 4)) = make_float4(a[0] + b4.x, a[1] + b4.y, a[2] + b4.z, a[3] + b4.w);
-      }
-    }
-  };
-  auto grow = [&](int p) { return m0 + (wave >> 2) * 96 + p * 48 + (wave & 3) * 12; };
-  const rsrc_t rs0 = row_rsrc((float*)out + (size_t)grow(0) * ldo + n0);
-  const rsrc_t rs1 = row_rsrc((float*)out + (size_t)grow(1) * ldo + n0);
-  const int rstep = ldo * 4, voff = lane * 16;
-  f32x4 r0[12], r1[12];
-#pragma unroll
-  for (int it = 0; it < 12; ++it) r0[it] = buf_load_f32x4(rs0, voff, it * rstep);
-  __builtin_amdgcn_sched_barrier(0);
-  stage(0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int it = 0; it < 12; ++it) r1[it] = buf_load_f32x4(rs1, voff, it * rstep);
-  __builtin_amdgcn_sched_barrier(0);
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 12; ++it) {
-    const int sr = wave * 12 + it;
-    const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
-    buf_store_f32x4(r0[it] + v, rs0, voff, it * rstep);
-  }
-  __syncthreads();
-  stage(1);
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 12; ++it) {
-    const int sr = wave * 12 + it;
-    const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
-    buf_store_f32x4(r1[it] + v, rs1, voff, it * rstep);
   }
 }
 
@@ -366,8 +322,8 @@ __device__ __forceinline__ void epilogue_192_resid(f32x4 (&acc)[4][6], char* sme
 // A half-buffer is rewritten (for tile t+1) only after both groups finished reading tile t-1 from it:
 //   piece (t+1, kk) is issued in L(t, kk);  last read of (t-1, kk) is group 1's L(t-1, kk), which ends
 //   at least one barrier earlier for every wave.
-// 16-B chunks are XOR-swizzled with pi[(row>>2)&3], pi = {0,3,2,1} (applied to the DMA source address
-// and to the ds_read address) so that every ds_read_b128 lane group hits 16 distinct 16-B slots.
+// 16-B chunks are XOR-swizzled in the half-K layout of gemm_tile.h (PG_HALFK_SRC_CHUNK on the DMA source address,
+// PG_HALFK_FRAG on the ds_read address) so that every ds_read_b128 lane group hits 16 distinct 16-B slots.
 // ------------------------------------------------------------------------------------------------
 // ABL (micro-benchmark ablations only): 0 = real kernel, 1 = no LDS-DMA inside the K loop (tile 0 reused),
 // 2 = no MFMA (fragments kept alive), 3 = no ds_read (fragments loaded once)
@@ -383,16 +339,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
                                                           int tail_m0, unsigned* rsync) {
   constexpr int HALF_BYTES = 512 * 64;            // one half-buffer: (256 + 256) rows x 64 B
   __shared__ __attribute__((aligned(16))) char smem[4 * HALF_BYTES];
-  // the first n_tail workgroups: 64 x 64 tiles of the rows beyond the last full round of 256 x 256 tiles (gemm_epilogue.h)
-  // n_tail > 0: they are the FIRST workgroups of the grid; n_tail < 0: the LAST |n_tail| (PGIBBS_GEMM_TAIL_LAST)
-  const int nt_abs = n_tail < 0 ? -n_tail : n_tail;
-  if (ABL == 0 && nt_abs && (n_tail > 0 ? (int)blockIdx.x < nt_abs : (int)blockIdx.x >= n_tiles)) {
-    // workgroup b runs on XCD b % 8: all column tiles of a 64-row block go to one XCD (they share the block's X rows through its
-    // L2) whenever the row blocks divide by 8 (tail rows are multiples of 256: at least by 4)
-    const int tn64 = tiles_n * 4, bt = n_tail > 0 ? blockIdx.x : blockIdx.x - n_tiles, n_rb = nt_abs / tn64;
-    int rb, tn;
-    if ((n_rb & 7) == 0) { const int j = bt >> 3; rb = (j / tn64) * 8 + (bt & 7); tn = j % tn64; }
-    else { rb = bt / tn64; tn = bt % tn64; }
+  // 64 x 64 tiles of the rows beyond the last full round of 256 x 256 tiles (tail_tile, gemm_tile.h), column tiles of a row block per XCD
+  int rb, tn;
+  if (ABL == 0 && tail_tile<true>(n_tail, n_tiles, tiles_n, rb, tn)) {
     gemm_tail_tile64<8, EPI>(X, W, bias, out, K, ldx, ldw, ldo, tail_m0 + rb * 64, tn * 64, smem);
     return;
   }
@@ -442,20 +391,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
   }
   if (ABL == 18 && (bid & 7) != 0) return;        // timing experiment: only the workgroups of XCD 0 run (1/8 of the tiles)
   if (ABL == 19 && (bid & 7) > 1) return;         // ... XCDs 0 and 1
-  {
-    const int xcd = bid & 7, q = n_tiles >> 3, r = n_tiles & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  // grouped rasterisation inside the XCD's range: GM m-panels x all n-tiles per group, m fastest, so the ~32
-  // tiles an XCD runs concurrently form a GM x (32/GM) rectangle that shares X and W k-slices through its L2.
-  int tile_m, tile_n;
-  {
-    const int tiles_m = n_tiles / tiles_n;
-    const int gsz = GM * tiles_n, g = bid / gsz, within = bid - g * gsz;
-    const int rows = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tile_m = g * GM + within % rows;
-    tile_n = within / rows;
-  }
+  bid = xcd_contiguous(bid, n_tiles);
+  int tile_m, tile_n;                               // grouped rasterisation inside the XCD's range (gemm_tile.h)
+  grouped_tile<GM>(bid, n_tiles, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * TM;
   const int n0 = tile_n * 256;
 
@@ -466,7 +404,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
   const bf16_t* src = stage_w ? W : X;
   const int lds_ = stage_w ? ldw : ldx;
   const int srow0 = (stage_w ? n0 + (wave & 3) * 64 : m0 + (wave & 3) * (NPX * 16)) + (lane >> 2);
-  const int schunk = (lane & 3) ^ ((0 - (lane >> 4)) & 3);                 // pi[(row>>2)&3] = (-g)&3
+  const int schunk = PG_HALFK_SRC_CHUNK(lane);
   const bf16_t* gsrc = src + (size_t)srow0 * lds_ + schunk * 8;            // + i*16 rows, + k
   const size_t piece_stride = (size_t)16 * lds_;
   const int lds_piece0 = stage_w ? 256 * 64 + (wave & 3) * 4 * 1024 : (wave & 3) * NPX * 1024;  // byte offset inside a half-buffer
@@ -503,7 +441,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
   if (grp == 1) __builtin_amdgcn_s_barrier();      // stagger the two groups by one barrier interval
 
   const int fr = lane & 15, fq = lane >> 4;
-  const int foff = fr * 64 + ((fq ^ ((0 - (fr >> 2)) & 3)) << 4);          // row*64 + swizzled chunk*16
+  const int foff = PG_HALFK_FRAG(fr, fq);                                  // row*64 + swizzled chunk*16
   const int xoff = (wm * XJ * 16) * 64 + foff;
   const int woff = 256 * 64 + (wn * 64) * 64 + foff;
 
@@ -571,8 +509,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
       for (int j = 0; j < XJ; ++j) asm volatile("" ::"v"(acc[i][j]));
     return;
   }
-  if constexpr (XJ == 8) epilogue_256<EPI, ABL == 16>(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
-  else epilogue_192_resid(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
+  if constexpr (EPI == EPI_F32_RESID) epilogue_resid<XJ>(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
+  else epilogue_256<EPI, ABL == 16>(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
 }
 
 // Measured alternatives that were NOT faster on MI355X and were removed again (QKV GEMM, M=66048 N=3840 K=1280, steady-state
@@ -670,23 +608,11 @@ static int launch_pp(hipStream_t s, const bf16_t* X, const bf16_t* W, const floa
     if (gemm_gm(GM_PP192, K) == 2) PG_PP(EPI_F32_RESID, 0, 2, 6);
     else PG_PP(EPI_F32_RESID, 0, 4, 6);
   } else {
-    const int gm = gemm_gm(GM_PP256, K);
-#define PG_GEMM_CASE(E)                 \
-  case E:                               \
-    if (gm == 1) PG_PP(E, 0, 1, 8);     \
-    else if (gm == 2) PG_PP(E, 0, 2, 8); \
-    else PG_PP(E, 0, 4, 8);             \
-    break;
-    switch (epi) {
-      PG_GEMM_CASE(EPI_BF16)
-      PG_GEMM_CASE(EPI_BF16_GELU)
-      PG_GEMM_CASE(EPI_F32_RESID)
-      PG_GEMM_CASE(EPI_F32)
-      PG_GEMM_CASE(EPI_F32_GELU)
-      default:
-        return fail(1, "gemm: bad epilogue for the 8-wave tile kernel");
-    }
-#undef PG_GEMM_CASE
+    const int gm = gemm_gm(GM_PP256, K);        // 1, 2 or 4
+    if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU>(epi, [&](auto E) {
+          return visit_int<1, 2, 4>(gm, [&](auto G) { PG_PP(decltype(E)::value, 0, decltype(G)::value, 8); });
+        }))
+      return fail(1, "gemm: bad epilogue for the 8-wave tile kernel");
   }
 #undef PG_PP
   PG_HIP(hipGetLastError());
@@ -937,26 +863,18 @@ int launch_gemm_ln_skinny(hipStream_t s, const float* X, int ldx, const float* g
   if (nb == 2 && N % 32) return fail(1, "gemm_ln_skinny: N must be a multiple of 32 for two feature blocks per workgroup");
   dim3 grid(N / (16 * nb)), block(512);
   note_kernel("ln+skinny8w", N / (16 * nb));
-#define PG_LNS(MTV, E, NK)                                                                                                       \
-  do {                                                                                                                           \
-    if (nb == 2) hipLaunchKernelGGL((gemm_ln_skinny_kernel<MTV, E, NK, 2>), grid, block, 0, s, X, ldx, gamma, beta, eps, W, bias, out, K, ldw, ldo); \
-    else hipLaunchKernelGGL((gemm_ln_skinny_kernel<MTV, E, NK, 1>), grid, block, 0, s, X, ldx, gamma, beta, eps, W, bias, out, K, ldw, ldo);     \
-  } while (0)
-#define PG_LNS_NK(MTV, E)                                                       \
-  switch (nks) {                                                                \
-    case 1: PG_LNS(MTV, E, 1); break;                                           \
-    case 2: PG_LNS(MTV, E, 2); break;                                           \
-    case 3: PG_LNS(MTV, E, 3); break;                                           \
-    case 4: PG_LNS(MTV, E, 4); break;                                           \
-    default: PG_LNS(MTV, E, 5); break;                                          \
-  }
-  if (M == 16) {
-    if (epi == EPI_BF16) { PG_LNS_NK(1, EPI_BF16) } else { PG_LNS_NK(1, EPI_BF16_GELU) }
-  } else {
-    if (epi == EPI_BF16) { PG_LNS_NK(2, EPI_BF16) } else { PG_LNS_NK(2, EPI_BF16_GELU) }
-  }
-#undef PG_LNS_NK
-#undef PG_LNS
+  // m-tiles 1, 2 x the two epilogues x 1 ... 5 k-steps per wave x 1, 2 feature blocks (gemm_ln_skinny_ok and the checks above)
+  const bool known = visit_int<1, 2>(M / 16, [&](auto MT) {
+    return visit_int<EPI_BF16, EPI_BF16_GELU>(epi, [&](auto E) {
+      return visit_int<1, 2, 3, 4, 5>(nks, [&](auto NK) {
+        return visit_int<1, 2>(nb == 2 ? 2 : 1, [&](auto NB) {
+          hipLaunchKernelGGL((gemm_ln_skinny_kernel<decltype(MT)::value, decltype(E)::value, decltype(NK)::value, decltype(NB)::value>),
+                             grid, block, 0, s, X, ldx, gamma, beta, eps, W, bias, out, K, ldw, ldo);
+        });
+      });
+    });
+  });
+  if (!known) return fail(1, "gemm_ln_skinny: shape / epilogue");
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -969,22 +887,13 @@ static int launch_skinny_mt(hipStream_t s, const bf16_t* X, const bf16_t* W, con
   static_assert(MT <= 4, "8 waves: the m-tile count keeps the register footprint small");
   const bool w8 = skinny_8_waves(K);
   dim3 grid(N / 16, splits), block(w8 ? 512 : 256);
-#define PG_GEMM_CASE(E)                                                                                              \
-  case E:                                                                                                            \
-    if (w8) hipLaunchKernelGGL((gemm_bf16_skinny_kernel<MT, E, 8>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, split_stride); \
-    else hipLaunchKernelGGL((gemm_bf16_skinny_kernel<MT, E, 4>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, split_stride);    \
-    break;
-  switch (epi) {
-    PG_GEMM_CASE(EPI_BF16)
-    PG_GEMM_CASE(EPI_BF16_GELU)
-    PG_GEMM_CASE(EPI_F32_RESID)
-    PG_GEMM_CASE(EPI_F32)
-    PG_GEMM_CASE(EPI_F32_GELU)
-    PG_GEMM_CASE(EPI_F32_PARTIAL)
-    default:
-      return fail(1, "gemm: bad epilogue");
-  }
-#undef PG_GEMM_CASE
+  if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU, EPI_F32_PARTIAL>(epi, [&](auto E) {
+        return visit_int<4, 8>(w8 ? 8 : 4, [&](auto NW) {
+          hipLaunchKernelGGL((gemm_bf16_skinny_kernel<MT, decltype(E)::value, decltype(NW)::value>), grid, block, 0, s, X, W, bias, out, K,
+                             ldx, ldw, ldo, split_stride);
+        });
+      }))
+    return fail(1, "gemm: bad epilogue");
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -994,22 +903,11 @@ static int launch_cfg(hipStream_t s, const bf16_t* X, const bf16_t* W, const flo
                       int K, int ldx, int ldw, int ldo, int epi, int splits = 1, long split_stride = 0) {
   const int tiles_m = M / BM, tiles_n = N / BN, n_tiles = tiles_m * tiles_n;
   dim3 grid(n_tiles, splits), block((BM / WM) * (BN / WN) * 64);
-#define PG_GEMM_CASE(E)                                                                                              \
-  case E:                                                                                                            \
-    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, E>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, \
-                       tiles_n, n_tiles, split_stride);                                                     \
-    break;
-  switch (epi) {
-    PG_GEMM_CASE(EPI_BF16)
-    PG_GEMM_CASE(EPI_BF16_GELU)
-    PG_GEMM_CASE(EPI_F32_RESID)
-    PG_GEMM_CASE(EPI_F32)
-    PG_GEMM_CASE(EPI_F32_GELU)
-    PG_GEMM_CASE(EPI_F32_PARTIAL)
-    default:
-      return fail(1, "gemm: bad epilogue");
-  }
-#undef PG_GEMM_CASE
+  if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU, EPI_F32_PARTIAL>(epi, [&](auto E) {
+        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, decltype(E)::value>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo,
+                           tiles_n, n_tiles, split_stride);
+      }))
+    return fail(1, "gemm: bad epilogue");
   PG_HIP(hipGetLastError());
   return 0;
 }

@@ -11,7 +11,8 @@
 // the 16 waves runs the attention of one (sequence, 16-query block) from there, and only the context rows leave the CU -- in the
 // ordinary token order, so nothing downstream changes.
 //
-//   * main loop: the 16-wave kernel's (gemm_w16.hip) with a 256 x 192 tile: wave tile 64 x 48, K-steps of 64 in two 56-KB slots
+//   * main loop: the 16-wave kernel's (gemm_w16.hip; tile walk, 128-byte-row layout, band resource and piece DMA from gemm_tile.h)
+//     with a 256 x 192 tile: wave tile 64 x 48, K-steps of 64 in two 56-KB slots
 //     (waves 0-7 stage the 32 activation pieces, waves 8-15 the 24 weight pieces), one s_barrier per K-step; same MFMA, operand
 //     roles and k order as every tile kernel, so q, k, v are the very bf16 values the unfused projection stores.
 //   * attention: attention_kernel's arithmetic through the same functions (attn_frag.h: S^T = K.Q^T, exact softmax in
@@ -38,19 +39,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave & 3, wn = wave >> 2;           // wave tile: activation rows wm*64 .., weight rows wn*48 ..
 
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = n_tiles >> 3, r = n_tiles & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
   int tile_m, tile_n;                                // tile_n = head
-  {
-    const int tiles_m = n_tiles / tiles_n;
-    const int gsz = GM * tiles_n, g = bid / gsz, within = bid - g * gsz;
-    const int rows = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tile_m = g * GM + within % rows;
-    tile_n = within / rows;
-  }
+  grouped_tile<GM>(xcd_contiguous(blockIdx.x, n_tiles), n_tiles, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * 256, n0 = tile_n * 192;
 
   // ---- LDS-DMA: a slot holds 56 pieces of 1 KiB (0-31: activation rows 8p .., 32-55: weight rows); waves 0-7 stage 4
@@ -59,18 +49,15 @@ __global__ __launch_bounds__(1024, 1) void gemm_colattn_kernel(const bf16_t* __r
   const int ld_ = stage_w ? ldw : ldx;
   const int npc = stage_w ? 3 : 4;
   const bf16_t* src = stage_w ? W + (size_t)(n0 + (wave - 8) * 24) * ldw : X + (size_t)(m0 + wave * 32) * ldx;
-  const rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, ((npc * 8 - 1) * ld_ + K) * 2, 0x00020000);
-  const int dma_voff = ((lane >> 3) * ld_ + ((lane & 7) ^ (lane >> 3)) * 8) * 2;
+  const rsrc_t rs_src = band_rsrc(src, npc * 8, ld_, K);
+  const int dma_voff = PG_ROW128_SRC(lane, ld_);
   const int piece_bytes = 8 * ld_ * 2;
   const int lds_piece0 = stage_w ? 32 * 1024 + (wave - 8) * 3 * 1024 : wave * 4 * 1024;
   const int nk = K / 64;
   auto dma_step = [&](int t) {
     char* dst = smem + (t & 1) * CA_SLOT + lds_piece0;
-    const int soff = t * 128;
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, PG_LDS_PTR(dst + g * 1024), 16, dma_voff, soff + g * piece_bytes, 0, 0);
-    if (!stage_w) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, PG_LDS_PTR(dst + 3 * 1024), 16, dma_voff, soff + 3 * piece_bytes, 0, 0);
+    dma_pieces<0, 3>(rs_src, dst, dma_voff, t * 128, piece_bytes);
+    if (!stage_w) dma_pieces<3, 4>(rs_src, dst, dma_voff, t * 128, piece_bytes);
   };
 
   const int fr = lane & 15, fq = lane >> 4;

@@ -1,18 +1,13 @@
-// Pieces shared by the GEMM tile kernels (gemm_bf16.hip, gemm_w16.hip; tools/probes/gemm_w4.hip): vector types, the GELU forms
-// (one definition for all kernels) and the LDS-staged epilogue of the 256 x 256 tiles with 4 or 16 waves.
+// What the GEMM tile kernels share beyond gemm_tile.h (which this header includes: vector types, tile walk, LDS swizzles, row
+// buffer access, 16-wave operand DMA, visit_int): the GELU forms (one definition for all kernels), EpiTraits, the 64 x 64 tail tile
+// of the 256 x 256 grids (gemm_tail_tile64), the LDS-staged epilogue of a 256 x 256 tile held by 4 or 16 waves (tile256_epilogue) and
+// the switches the tile launchers share (gemm_gm, gemm_tail_last).  Users: gemm_bf16.hip, gemm_ladder.hip, gemm_rowln.hip,
+// gemm_w16.hip, gemm_colattn.hip, chain_trunk.hip, engine.hip, api.hip; tools/probes/gemm_w4.hip.
 #pragma once
+#include "gemm_tile.h"
 #include "kernels.h"
 
 PG_OPS_BEGIN
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-#define PG_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-#define PG_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define PG_NT_STORE(p, v) __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, v), (u32x4_t*)(p))
 
 // ---- the GELU forms, defined ONCE for every tile kernel: a batch split into shards may pick different kernels per shard, and
 // the logits must not depend on that ----
@@ -94,20 +89,20 @@ __device__ __forceinline__ void gemm_tail_tile64(const bf16_t* __restrict__ X, c
   const bool a_is_w = wave >= 8;
   const int ld_a = a_is_w ? ldw : ldx;
   const bf16_t* src_a = a_is_w ? W + (size_t)(n0 + (wave - 8) * 8) * ldw : X + (size_t)(m0 + wave * 8) * ldx;
-  const rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)src_a, 0, 7 * ld_a * 2 + kbytes, 0x00020000);
-  const int voff_a = ((lane >> 3) * ld_a + ((lane & 7) ^ (lane >> 3)) * 8) * 2;
-  const rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)(W + (size_t)(n0 + (wave & 7) * 8) * ldw), 0, 7 * ldw * 2 + kbytes, 0x00020000);
-  const int voff_b = ((lane >> 3) * ldw + ((lane & 7) ^ (lane >> 3)) * 8) * 2;
+  const rsrc_t rs_a = buf_rsrc(src_a, 7 * ld_a * 2 + kbytes);
+  const int voff_a = PG_ROW128_SRC(lane, ld_a);
+  const rsrc_t rs_b = buf_rsrc(W + (size_t)(n0 + (wave & 7) * 8) * ldw, 7 * ldw * 2 + kbytes);
+  const int voff_b = PG_ROW128_SRC(lane, ldw);
   auto dma = [&](int t) {
     char* dst = smem + (t & (STAGES - 1)) * STAGE_BYTES;
-    const int soff = t < nk ? t * KSTEP_BYTES : 0x7f000000;  // past the end of K: out of range, no memory traffic
+    const int soff = PG_KSTEP_SOFF(t, nk, KSTEP_BYTES);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, PG_LDS_PTR(dst + wave * 1024), 16, voff_a, soff, 0, 0);
     if (PPW == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, PG_LDS_PTR(dst + (wave + 8) * 1024), 16, voff_b, soff, 0, 0);
   };
 
   const int fr = lane & 15, fq = lane >> 4;
-  const int fo0 = fr * 128 + ((fq ^ (fr & 7)) << 4);
-  const int fo1 = fr * 128 + (((4 + fq) ^ (fr & 7)) << 4);
+  const int fo0 = PG_ROW128_FRAG(fr, fq);
+  const int fo1 = PG_ROW128_FRAG(fr, 4 + fq);
   const int ni = NW == 16 ? (wave >> 2) : (wave >> 1);       // 16-row block of W (output columns)
   const int mi0 = NW == 16 ? (wave & 3) : (wave & 1) * 2;    // first 16-row block of X (output rows)
   f32x4 acc[TM];
@@ -307,18 +302,18 @@ __device__ __forceinline__ void tile256_epilogue(ElemF&& elem, char* smem, int w
     // half of a wave's rows are in flight while the previous half is added and stored
     constexpr int HR = RF / 2;
     const int rstep = ldo * 4, voff = lane * 16;
-    auto rs = [&](int p) { return __builtin_amdgcn_make_buffer_rsrc((float*)out + (size_t)grow(p) * ldo + n0, 0, 0x7fffffff, 0x00020000); };
+    auto rs = [&](int p) { return row_rsrc((float*)out + (size_t)grow(p) * ldo + n0); };
     auto ldh = [&](f32x4 (&r)[HR], rsrc_t s, int first) {
 #pragma unroll
       for (int it = 0; it < HR; ++it)
-        r[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(s, voff + (first + it) * rstep, 0, 2));
+        r[it] = buf_load_f32x4(s, voff + (first + it) * rstep, 0);
     };
     auto sth = [&](f32x4 (&r)[HR], rsrc_t s, int first) {
 #pragma unroll
       for (int it = 0; it < HR; ++it) {
         const int sr = wave * RF + first + it;
         const f32x4 v = *(const f32x4*)(smem + sr * 1024 + ((lane ^ (sr & 63)) << 4));
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, r[it] + v), s, voff + (first + it) * rstep, 0, 2);
+        buf_store_f32x4(r[it] + v, s, voff, (first + it) * rstep);
       }
     };
     const rsrc_t rs0 = rs(0), rs1 = rs(1);

@@ -14,8 +14,8 @@
 // A row's products are accumulated in the same k order by the same MFMA as in every other tile kernel, so a row's bits do not
 // depend on the tile height: shards stay bit-identical with the whole batch (tests/test_gpu_kernels.py, test_gpu_fullsize.py).
 //
-// Differences from gemm_bf16_pp_kernel (gemm_bf16.hip), whose comments explain the ping-pong schedule, the LDS ring of four half-K
-// buffers and the swizzle:
+// Differences from gemm_bf16_pp_kernel (gemm_bf16.hip), whose comments explain the ping-pong schedule and the LDS ring of four
+// half-K buffers (tile walk, half-K swizzle pair and row buffer access: gemm_tile.h):
 //   * X staging: the (XJ0 + XJ1) 16-row pieces of a half-step are dealt round-robin to waves 0-3 (piece p -> wave p & 3), so a
 //     wave stages 3 or 4 (2 or 3 ...) pieces and waits with the matching vmcnt; waves 4-7 stage the four W pieces each, as before.
 //   * the two wave groups run the main loop with their own accumulator count (a wave-uniform branch at the top when XJ0 != XJ1:
@@ -30,16 +30,6 @@
 PG_OPS_BEGIN
 
 namespace ladder {
-
-#define PGL_AUX 2                                                /* buffer ops: nt (as the ping-pong kernel's epilogues) */
-__device__ __forceinline__ rsrc_t row_rsrc(void* base) { return __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000); }
-__device__ __forceinline__ f32x4 buf_load_f32x4(rsrc_t rs, int voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, PGL_AUX));
-}
-// the row step stays in the VGPR offset (gemm_bf16.hip: with an SGPR soffset the last dword of a 128-bit store was corrupted)
-__device__ __forceinline__ void buf_store_f32x4(f32x4 v, rsrc_t rs, int voff, int row_off) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, voff + row_off, 0, PGL_AUX);
-}
 
 constexpr int HALF_BYTES = 512 * 64;              // one half-buffer: (256 + 256) rows x 64 B
 
@@ -159,7 +149,7 @@ __device__ __forceinline__ void wave_body(char* smem, const bf16_t* gsrc, size_t
 #pragma unroll
     for (int j = 0; j < XJ; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int fr = lane & 15, fq = lane >> 4;
-  const int foff = fr * 64 + ((fq ^ ((0 - (fr >> 2)) & 3)) << 4);          // row*64 + swizzled chunk*16
+  const int foff = PG_HALFK_FRAG(fr, fq);                                  // row*64 + swizzled chunk*16
   const int xoff = (grp ? XJ0 * 16 : 0) * 64 + foff;
   const int woff = 256 * 64 + (wn * 64) * 64 + foff;
   bf16x8 wf[4], xf[XJ];
@@ -222,18 +212,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_ppx_kernel(const bf16_t* __rest
   const int wn = wave & 3;                         // wave tile: rows of group grp, W rows wn*64 ..
 
   int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = n_tiles >> 3, r = n_tiles & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  bid = xcd_contiguous(bid, n_tiles);
   int tile_m, tile_n;
-  {
-    const int tiles_m = n_tiles / tiles_n;
-    const int gsz = GM * tiles_n, g = bid / gsz, within = bid - g * gsz;
-    const int rows = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tile_m = g * GM + within % rows;
-    tile_n = within / rows;
-  }
+  grouped_tile<GM>(bid, n_tiles, tiles_n, tile_m, tile_n);
   // The last row panel may reach past the m_rows rows that exist (m_rows is a multiple of 16, >= TM): it is shifted up to end at
   // m_rows exactly, recomputes some of the previous panel's rows (same bits) and -- residual epilogue -- does not store them again.
   const int row_lo = tile_m * TM;
@@ -246,7 +227,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_ppx_kernel(const bf16_t* __rest
   const bf16_t* src = stage_w ? W : X;
   const int lds_ = stage_w ? ldw : ldx;
   const int srow0 = (stage_w ? n0 + wn * 64 : m0 + wn * 16) + (lane >> 2);
-  const int schunk = (lane & 3) ^ ((0 - (lane >> 4)) & 3);
+  const int schunk = PG_HALFK_SRC_CHUNK(lane);
   const bf16_t* gsrc = src + (size_t)srow0 * lds_ + schunk * 8;
   const size_t piece_stride = (size_t)(stage_w ? 16 : 64) * lds_;          // X: the wave's next piece is 4 pieces = 64 rows on
   const int lds_piece0 = stage_w ? 256 * 64 + wn * 4 * 1024 : wn * 1024;   // byte offset inside a half-buffer
@@ -270,16 +251,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_ppx_kernel(const bf16_t* __rest
 }
 #undef PGL_WAIT
 
-template <int EPI, int XJ0, int XJ1>
-static int launch_h(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int K, int ldx, int ldw, int ldo,
-                    int tiles_n, int n_tiles, int gm, int m_rows) {
-  dim3 grid(n_tiles), block(512);
-  if (gm == 2) hipLaunchKernelGGL((gemm_bf16_ppx_kernel<EPI, 2, XJ0, XJ1>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, m_rows);
-  else hipLaunchKernelGGL((gemm_bf16_ppx_kernel<EPI, 4, XJ0, XJ1>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, m_rows);
-  PG_HIP(hipGetLastError());
-  return 0;
-}
-
 }  // namespace ladder
 
 // Heights this build instantiates per epilogue (each is one more kernel per operand flavour and tile grouping)
@@ -298,22 +269,21 @@ int launch_gemm_ladder(hipStream_t s, const bf16_t* X, const bf16_t* W, const fl
   const int tiles_m = (m_live + h - 1) / h;
   const int gm = gemm_gm(GM_LADDER, K);
   const int tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
-#define PGL_ARGS s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, gm, m_rows
-  if (epi == EPI_F32_RESID) {
-    switch (h) {
-      case 160: return ladder::launch_h<EPI_F32_RESID, 5, 5>(PGL_ARGS);
-      case 176: return ladder::launch_h<EPI_F32_RESID, 6, 5>(PGL_ARGS);
-      case 208: return ladder::launch_h<EPI_F32_RESID, 7, 6>(PGL_ARGS);
-      case 224: return ladder::launch_h<EPI_F32_RESID, 7, 7>(PGL_ARGS);
-      default: return ladder::launch_h<EPI_F32_RESID, 8, 7>(PGL_ARGS);
-    }
-  }
-  switch (h) {
-    case 208: return ladder::launch_h<EPI_BF16_GELU, 7, 6>(PGL_ARGS);
-    case 224: return ladder::launch_h<EPI_BF16_GELU, 7, 7>(PGL_ARGS);
-    default: return ladder::launch_h<EPI_BF16_GELU, 8, 7>(PGL_ARGS);
-  }
-#undef PGL_ARGS
+  dim3 grid(n_tiles), block(512);
+  // the (epilogue, height) pairs of gemm_ladder_has: h = (XJ0 + XJ1) x 16 with XJ0 = ceil(h / 32), XJ1 = floor(h / 32)
+  auto launch = [&](auto E, auto H) {
+    constexpr int XJ0 = (decltype(H)::value / 16 + 1) / 2, XJ1 = decltype(H)::value / 32;
+    return visit_int<2, 4>(gm, [&](auto G) {
+      hipLaunchKernelGGL((ladder::gemm_bf16_ppx_kernel<decltype(E)::value, decltype(G)::value, XJ0, XJ1>), grid, block, 0, s, X, W, bias,
+                         out, K, ldx, ldw, ldo, tiles_n, n_tiles, m_rows);
+    });
+  };
+  const bool known = epi == EPI_F32_RESID
+      ? visit_int<160, 176, 208, 224, 240>(h, [&](auto H) { return launch(std::integral_constant<int, EPI_F32_RESID>{}, H); })
+      : visit_int<208, 224, 240>(h, [&](auto H) { return launch(std::integral_constant<int, EPI_BF16_GELU>{}, H); });
+  if (!known) return fail(1, "gemm_ladder: shape / height / epilogue");
+  PG_HIP(hipGetLastError());
+  return 0;
 }
 
 PG_OPS_END

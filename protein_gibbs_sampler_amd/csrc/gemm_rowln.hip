@@ -19,7 +19,7 @@
 //   * W is wave-PRIVATE in LDS: each wave stages the 96 weight rows it multiplies (6 pieces of 16 rows x 64 B per half-step of k = 32)
 //     into its own two slots -- no barrier is needed to recycle them, only the wave's own reads.  W (1.2 MB at K = 768) stays in L2.
 //   * the activation rows are shared: 7 pieces per half-step, one per wave 0..6, in a ring of four slots (they come from HBM: three
-//     half-steps of lead).  LDS-DMA (`global_load_lds`, 16 B per lane), XOR swizzle on the source side, as the ping-pong kernel.
+//     half-steps of lead).  LDS-DMA (`global_load_lds`, 16 B per lane), XOR swizzle on the source side: the half-K layout of gemm_tile.h.
 //   * the two wave groups (0-3 / 4-7; waves w and w + 4 share a SIMD) run one barrier apart: while one group's 42 MFMAs own the matrix
 //     pipe the other issues DMA and reads fragments.  Per half-step and wave: read 7 + 6 fragments, issue W(s+2) into the slot just read
 //     and X(s+3), wait until W(s+1) / X(s+1) have landed (counted vmcnt: X(s+2), W(s+2), X(s+3) stay in flight), barrier, MFMAs, barrier.
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(const bf16_t* __restric
   const int m0 = row_lo + TM > m_rows ? m_rows - TM : row_lo;
 
   // ---- LDS-DMA addressing: lane -> row (lane >> 2) of a 16-row piece, 16-B chunk (lane & 3), swizzled on the source side
-  const int schunk = (lane & 3) ^ ((0 - (lane >> 4)) & 3);
+  const int schunk = PG_HALFK_SRC_CHUNK(lane);
   const bf16_t* wsrc = W + (size_t)(wave * 96 + (lane >> 2)) * ldw + schunk * 8;      // + p * 16 rows, + k
   const size_t wpiece = (size_t)16 * ldw;
   const bool has_x = wave < XJ;                                                         // waves 0..6 stage one activation piece each
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(512) void gemm_rowln_kernel(const bf16_t* __restric
   if (grp == 1) __builtin_amdgcn_s_barrier();     // stagger the two groups by one barrier interval
 
   const int fr = lane & 15, fq = lane >> 4;
-  const int foff = fr * 64 + ((fq ^ ((0 - (fr >> 2)) & 3)) << 4);          // row*64 + swizzled chunk*16
+  const int foff = PG_HALFK_FRAG(fr, fq);                                  // row*64 + swizzled chunk*16
   bf16x8 wf[NB], xf[XJ];
   for (int s = 0; s < nhs; ++s) {
     // ---------------- L segment ----------------

@@ -11,10 +11,11 @@
 //
 //   * K-steps of 64: a slot is 256 X rows + 256 W rows of 128 B = 64 KB = 64 DMA pieces of 1 KiB (8 full 128-B rows per
 //     wave-instruction, so every line of X / W passes the L2 -> L1 path once); two slots; wave w stages pieces 4w .. 4w+3.
-//   * 16-B chunks of a row XOR-swizzled with (row & 7) (source-side permutation; conflict-free ds_read_b128).
+//   * 16-B chunks of a row XOR-swizzled with the row's low three bits (PG_ROW128_SRC / PG_ROW128_FRAG; conflict-free ds_read_b128).
 //   * one s_barrier per K-step: it publishes the landed pieces of step t and retires everybody's reads of step t-1's slot.
 //   * same k order and MFMA instruction as every other tile kernel -> bit-identical results for any split of a batch.
-//   * grouped, XCD-aware tile order and LDS-staged epilogues as in the other 256 x 256 kernels (gemm_epilogue.h).
+//   * grouped, XCD-aware tile order (xcd_contiguous / grouped_tile), the 128-byte-row swizzle pair and the band resource from
+//     gemm_tile.h; LDS-staged epilogues as in the other 256 x 256 kernels (tile256_epilogue, gemm_epilogue.h).
 // Measured and removed again (QKV shape, this kernel 0.551-0.560 ms, the 8-wave ping-pong kernel 0.571-0.579): no barrier at all
 // (timing only) 0.537; DMA never waited for 0.583 (= real: latency is covered); DMA pieces behind the first fragment reads, s_setprio
 // around the MFMA clusters: no change; the barrier moved between the reads and the MFMAs of the second half-step (so that a released
@@ -64,18 +65,9 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
   const int wm = wave & 3, wn = wave >> 2;           // wave tile: X rows wm*64 .., W rows wn*64 ..
 
   int bid = n_tail > 0 ? blockIdx.x - n_tail : blockIdx.x;
-  {
-    const int xcd = bid & 7, q = n_tiles >> 3, r = n_tiles & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  bid = xcd_contiguous(bid, n_tiles);
   int tile_m, tile_n;
-  {
-    const int tiles_m = n_tiles / tiles_n;
-    const int gsz = GM * tiles_n, g = bid / gsz, within = bid - g * gsz;
-    const int rows = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tile_m = g * GM + within % rows;
-    tile_n = within / rows;
-  }
+  grouped_tile<GM>(bid, n_tiles, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * 256, n0 = tile_n * 256;
 
   // ---- LDS-DMA: a slot holds 64 pieces (0-31: X rows 8p .. 8p+7, 32-63: W rows); wave w stages pieces 4w .. 4w+3, i.e. 32
@@ -84,15 +76,15 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
   const bool stage_w = wave >= 8;
   const int ld_ = stage_w ? ldw : ldx;
   const bf16_t* src = (stage_w ? W + (size_t)n0 * ldw : X + (size_t)m0 * ldx) + (size_t)(wave & 7) * 32 * ld_;
-  const rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (31 * ld_ + K) * 2, 0x00020000);
-  const int dma_voff = ((lane >> 3) * ld_ + ((lane & 7) ^ (lane >> 3)) * 8) * 2;
+  const rsrc_t rs_src = band_rsrc(src, 32, ld_, K);
+  const int dma_voff = PG_ROW128_SRC(lane, ld_);
   const int piece_bytes = 8 * ld_ * 2;
   const int lds_piece0 = wave * 4 * 1024;
   const int nk = K / 64;
 
   auto dma_step = [&](int t) {                       // this wave's 4 pieces of K-step t
     char* dst = smem + (t & 1) * W16_KSLOT + lds_piece0;
-    const int soff = t < nk ? t * 128 : 0x7f000000;
+    const int soff = PG_KSTEP_SOFF(t, nk, 128);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, PG_LDS_PTR(dst + g * 1024), 16, dma_voff, soff + g * piece_bytes, 0, 0);
@@ -100,8 +92,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
 
   // fragment tile T (16 rows x 128 B = 2 KiB), half kk: lane reads row fr, chunk (kk*4 + fq) ^ (fr & 7)
   const int fr = lane & 15, fq = lane >> 4;
-  const int foff0 = fr * 128 + ((fq ^ (fr & 7)) << 4);
-  const int foff1 = fr * 128 + (((4 + fq) ^ (fr & 7)) << 4);
+  const int foff0 = PG_ROW128_FRAG(fr, fq);
+  const int foff1 = PG_ROW128_FRAG(fr, 4 + fq);
   const int xbase = wm * 4 * 2048;
   const int wbase = 32 * 1024 + wn * 4 * 2048;
 
@@ -150,11 +142,7 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
     return;
   }
   // acc[i][j] is D[n = wn*64 + i*16 + fq*4 + r][m = wm*64 + j*16 + fr]
-  auto elem = [&](int e, int& m_loc, int& n_loc) -> f32x4 {
-    m_loc = wm * 64 + (e & 3) * 16 + fr;
-    n_loc = wn * 64 + (e >> 2) * 16 + fq * 4;
-    return acc[e >> 2][e & 3];
-  };
+  auto elem = [&](int e, int& m_loc, int& n_loc) -> f32x4 { return w16_elem(acc, e, wm, wn, fr, fq, m_loc, n_loc); };
   tile256_epilogue<EPI, 16>(elem, smem, wave, lane, m0, n0, bias, out, ldo);
 }
 
@@ -178,9 +166,7 @@ __global__ __launch_bounds__(1024, 1) void gemm_split3_w16_kernel(const bf16_t* 
   __shared__ __attribute__((aligned(16))) char smem[2 * W16_KSLOT];
   // the first n_tail workgroups: 64 x 64 tiles of the rows beyond the last full round of 256 x 256 tiles (gemm_epilogue.h)
   if ((int)blockIdx.x < n_tail) {
-    const int out_cols = (EPI == EPI_SPLIT3_GELU || EPI == EPI_SPLIT2_GELU) ? ldo / 3 : ldo;
     const int tn64 = tiles_n * 4, bt = blockIdx.x;
-    (void)out_cols;
     gemm_tail_tile64<16, EPI, true>(X, W, bias, out, K, ldx, ldw, ldo, tail_m0 + (bt / tn64) * 64, (bt % tn64) * 64, smem);
     return;
   }
@@ -188,41 +174,32 @@ __global__ __launch_bounds__(1024, 1) void gemm_split3_w16_kernel(const bf16_t* 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave & 3, wn = wave >> 2;
   int bid = blockIdx.x - n_tail;
-  {
-    const int xcd = bid & 7, q = n_tiles >> 3, r = n_tiles & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  bid = xcd_contiguous(bid, n_tiles);
   int tile_m, tile_n;
-  {
-    const int tiles_m = n_tiles / tiles_n;
-    const int gsz = GM * tiles_n, g = bid / gsz, within = bid - g * gsz;
-    const int rows = (tiles_m - g * GM) < GM ? (tiles_m - g * GM) : GM;
-    tile_m = g * GM + within % rows;
-    tile_n = within / rows;
-  }
+  grouped_tile<GM>(bid, n_tiles, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * 256, n0 = tile_n * 256;
 
   // K = logical depth (columns of the unsplit operand); ldx, ldw = 3K-wide rows
   const bool stage_w = wave >= 8;
   const int ld_ = stage_w ? ldw : ldx;
   const bf16_t* src = (stage_w ? W + (size_t)n0 * ldw : X + (size_t)m0 * ldx) + (size_t)(wave & 7) * 32 * ld_;
-  const rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (31 * ld_ + 3 * K) * 2, 0x00020000);
-  const int dma_voff = ((lane >> 3) * ld_ + ((lane & 7) ^ (lane >> 3)) * 8) * 2;
+  const rsrc_t rs_src = buf_rsrc(src, (31 * ld_ + 3 * K) * 2);      // band_rsrc(src, 32, ld_, 3 * K), spelled out: the call evaluates 3 * K first and the scalar multiplies swap
+  const int dma_voff = PG_ROW128_SRC(lane, ld_);
   const int piece_bytes = 8 * ld_ * 2;
   const int lds_piece0 = wave * 4 * 1024;
   const int nk = K / 32;                             // groups of 32 columns
 
   auto dma_step = [&](int t) {
     char* dst = smem + (t & 1) * W16_KSLOT + lds_piece0;
-    const int soff = t < nk ? t * 192 : 0x7f000000;
+    const int soff = PG_KSTEP_SOFF(t, nk, 192);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, PG_LDS_PTR(dst + g * 1024), 16, dma_voff, soff + g * piece_bytes, 0, 0);
   };
 
   const int fr = lane & 15, fq = lane >> 4;
-  const int foff0 = fr * 128 + ((fq ^ (fr & 7)) << 4);            // xl / wh: chunks 0-3 of the row
-  const int foff1 = fr * 128 + (((4 + fq) ^ (fr & 7)) << 4);      // xh / wl: chunks 4-7
+  const int foff0 = PG_ROW128_FRAG(fr, fq);                       // xl / wh: chunks 0-3 of the row
+  const int foff1 = PG_ROW128_FRAG(fr, 4 + fq);                   // xh / wl: chunks 4-7
   const int xbase = wm * 4 * 2048;
   const int wbase = 32 * 1024 + wn * 4 * 2048;
 
@@ -271,11 +248,7 @@ __global__ __launch_bounds__(1024, 1) void gemm_split3_w16_kernel(const bf16_t* 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  auto elem = [&](int e, int& m_loc, int& n_loc) -> f32x4 {
-    m_loc = wm * 64 + (e & 3) * 16 + fr;
-    n_loc = wn * 64 + (e >> 2) * 16 + fq * 4;
-    return acc[e >> 2][e & 3];
-  };
+  auto elem = [&](int e, int& m_loc, int& n_loc) -> f32x4 { return w16_elem(acc, e, wm, wn, fr, fq, m_loc, n_loc); };
   tile256_epilogue<EPI, 16>(elem, smem, wave, lane, m0, n0, bias, out, ldo);
 }
 
@@ -291,20 +264,13 @@ int launch_gemm_split3_w16(hipStream_t s, const bf16_t* X3, const bf16_t* W3, co
   const int n_tail = (tail_rows / 64) * (N / 64), tail_m0 = m_main * 256;
   const int gm = K >= 4096 ? 2 : 4;
   dim3 grid(n_tiles + n_tail), block(1024);
-#define PG_S3_CASE(E)                                                                                                          \
-  case E:                                                                                                                      \
-    if (gm == 2) hipLaunchKernelGGL((gemm_split3_w16_kernel<E, 2>), grid, block, 0, s, X3, W3, bias, out, K, 3 * K, 3 * K, ldo, tiles_n, n_tiles, n_tail, tail_m0); \
-    else hipLaunchKernelGGL((gemm_split3_w16_kernel<E, 4>), grid, block, 0, s, X3, W3, bias, out, K, 3 * K, 3 * K, ldo, tiles_n, n_tiles, n_tail, tail_m0);     \
-    break;
-  switch (epi) {
-    PG_S3_CASE(EPI_F32)
-    PG_S3_CASE(EPI_F32_RESID)
-    PG_S3_CASE(EPI_SPLIT3_GELU)
-    PG_S3_CASE(EPI_SPLIT2_GELU)
-    default:
-      return fail(1, "gemm_split3_w16: bad epilogue");
-  }
-#undef PG_S3_CASE
+  const bool known = visit_int<EPI_F32, EPI_F32_RESID, EPI_SPLIT3_GELU, EPI_SPLIT2_GELU>(epi, [&](auto E) {
+    return visit_int<2, 4>(gm, [&](auto G) {
+      hipLaunchKernelGGL((gemm_split3_w16_kernel<decltype(E)::value, decltype(G)::value>), grid, block, 0, s, X3, W3, bias, out, K, 3 * K,
+                         3 * K, ldo, tiles_n, n_tiles, n_tail, tail_m0);
+    });
+  });
+  if (!known) return fail(1, "gemm_split3_w16: bad epilogue");
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -322,21 +288,16 @@ int launch_gemm_w16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float
     return fail(1, "gemm_w16: shape");
   const int gm = gemm_gm(GM_W16, K);
   dim3 grid(n_tiles + n_tail_abs), block(1024);
-  // every instance of the kernel, one line each: (abl, epi) -> <EPI, GM, ABL>
+  // every instance of the kernel: abl 0 -> the five epilogues x GM 2, 4; the ablations one line each, abl -> <EPI, GM, ABL>
 #define PG_W16(E, G, A)                                                                                                          \
   hipLaunchKernelGGL((gemm_bf16_w16_kernel<E, G, A>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, \
                      n_tail, tail_m0)
-#define PG_W16_CASE(E) case E: if (gm == 2) PG_W16(E, 2, 0); else PG_W16(E, 4, 0); break;
   switch (abl) {
     case 0:
-      switch (epi) {
-        PG_W16_CASE(EPI_BF16)
-        PG_W16_CASE(EPI_BF16_GELU)
-        PG_W16_CASE(EPI_F32_RESID)
-        PG_W16_CASE(EPI_F32)
-        PG_W16_CASE(EPI_F32_GELU)
-        default: return fail(1, "gemm_w16: bad epilogue");
-      }
+      if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU>(epi, [&](auto E) {
+            return visit_int<2, 4>(gm, [&](auto G) { PG_W16(decltype(E)::value, decltype(G)::value, 0); });
+          }))
+        return fail(1, "gemm_w16: bad epilogue");
       break;
     case 1: PG_W16(EPI_BF16, 4, 1); break;
     case 2: PG_W16(EPI_BF16, 4, 2); break;
@@ -345,7 +306,6 @@ int launch_gemm_w16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float
     case 10: PG_W16(EPI_BF16, 4, 10); break;
     default: return fail(1, "gemm_w16: unknown ablation");
   }
-#undef PG_W16_CASE
 #undef PG_W16
   PG_HIP(hipGetLastError());
   return 0;
