@@ -359,6 +359,40 @@ int pg_dbg_rope_hd(int device, int precision, float* qkv_inout, int B, int T, in
  * operands */
 int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale);
 
+
+/* ---- the memory-bound row kernels (csrc/elementwise.hip), each through its launcher ----
+ * All five check on the host, before they look for a device, that no token, position row, row_map entry or gathered row the kernel
+ * would read lies outside the buffers as the caller sized them: PG_ERR_INVALID with a message, never a GPU fault.  16-bit rows are
+ * returned as raw bits in `precision` = PG_PREC_BF16 or PG_PREC_F16; buffers named _inout are copied to the device before the launch,
+ * so whatever the kernel leaves unwritten comes back holding the caller's pattern. */
+/* embed_ln_kernel: tokens[n_seq][T] (each in 0 .. V-1), embed[V][d] -> x[n_seq*T][d] fp32.  pos (NULL: no position table, ESM-2) has
+ * pos_rows rows; msa_pos (rows_per_msa > 0) has rows_per_msa rows; gamma / beta (both or neither): emb_layer_norm_before; gamma2 /
+ * beta2 / h2 (all or none): the first layer's LayerNorm of x as operand rows h2[n_seq*T][d] */
+int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
+                 int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
+                 const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2);
+/* launch_layernorm_bf16 on x[M][d]: form 0 = plain rows of d values, 1 = the strict mode's split rows of 3 d values (per 32 columns
+ * [lo | hi | hi]; bf16 only), 2 = the same without the duplicate block; colmajor_R / colmajor_C > 0: token row (b*R + r)*C + c is
+ * written as row (b*C + c)*R + r (form 0, d <= 2048, M a multiple of R*C).  h_inout holds h_rows >= M rows.  *kernel (may be NULL):
+ * the kernel the launcher chose -- 0 plain, 1 the stride kernel (d = 1280 / 768, ~8 k .. 33 k rows, PGIBBS_LN_STRIDE), 2 column-major */
+int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                          int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel);
+/* gather_ln_bf16_kernel: selected row r = LayerNorm of token row row_of(r / P) * width + (idx[r] & 0x3fffffff) of x[x_rows][d], zeros
+ * when idx[r] < 0 or the position is >= width; row_of = row_map[n_map] (NULL: the identity); idx == NULL: selected row r = token row r.
+ * split: 1 = [lo | hi | hi] rows (bf16).  h_inout holds h_rows >= n_sel rows */
+int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                     int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                     float eps, int split);
+/* gather_rows_kernel: dst[r] = src[row_of(r / P) * width + pos] for rows of row_bytes (a multiple of 16) bytes; pos = idx[r] without
+ * bit 30, 0 when that is negative or >= width.  n_iters = 0: idx[n_sel]; n_iters > 0: idx[n_iters][n_sel] and the kernel reads row
+ * `iter` of it through a device-side iteration counter.  dst_inout holds dst_rows >= n_sel rows */
+int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
+                       int iter, const int32_t* row_map, int64_t n_map, int P, int width, int64_t n_sel, int row_bytes);
+/* launch_lm_tail: logits[n][V] = LayerNorm(g[n][d]; gamma, beta) . embed[V][d]^T + out_bias (gamma == beta == NULL: no LayerNorm,
+ * ESM-1); V <= 64.  *small_kernel (may be NULL): 1 = the workgroup-per-row kernel ran (n <= PGIBBS_LM_TAIL_SMALL, default 1024) */
+int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                   float* logits, int64_t n, int d, int V, float eps, int* small_kernel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,16 @@ SIGNATURES = [
     ("pg_dbg_attention_hd", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),
     ("pg_dbg_rope_hd", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int]),
     ("pg_dbg_msa_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float]),
+    ("pg_dbg_embed", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    ("pg_dbg_layernorm_rows", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_int,
+                                      c_int, POINTER(c_int)]),
+    ("pg_dbg_gather_ln", c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_int64, c_int, c_float, c_int]),
+    ("pg_dbg_gather_rows", c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int,
+                                   c_int64, c_int]),
+    ("pg_dbg_lm_tail", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
+                               POINTER(c_int)]),
 ]
 
 

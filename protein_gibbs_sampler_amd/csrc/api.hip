@@ -983,4 +983,201 @@ int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, in
   return PG_OK;
 }
 
+// ---- the row kernels of elementwise.hip ---------------------------------------------------------------------------------------------
+// Every entry below checks its arguments on the host first -- shapes, then every token, position row, row_map entry and gathered
+// row the kernel would read against the sizes the caller states -- and only then looks for a device: a wrong array is
+// PG_ERR_INVALID with a message, never a GPU fault, and the refusals can be tested without a GPU.
+extern "C++" {
+namespace {
+int dbg_row_width(const char* who, int d) {
+  if (d < 4 || d % 4 || d > 2560) return      // row_d_ok of elementwise.hip
+    fail(PG_ERR_INVALID, std::string(who) + ": d must be a multiple of 4 and <= 2560");
+  return PG_OK;
+}
+int dbg_prec16(const char* who, int precision) {
+  if (precision != PG_PREC_BF16 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, std::string(who) + ": precision must be PG_PREC_BF16 or PG_PREC_F16");
+  return PG_OK;
+}
+// the token row a gather reads for selected row r (what gather_ln_bf16_kernel / gather_rows_kernel compute), -1 = none (zeros);
+// -2 = outside the source (error set)
+int64_t dbg_gather_src(const char* who, int64_t r, int32_t pos, bool zero_fill, const int32_t* row_map, int64_t n_map, int P, int width,
+                       int64_t src_rows) {
+  if (pos < 0 || (pos & 0x3fffffff) >= width) {
+    if (zero_fill) return -1;
+    pos = 0;
+  }
+  pos &= 0x3fffffff;
+  const int64_t s = r / P;
+  if (row_map && s >= n_map) { fail(PG_ERR_INVALID, std::string(who) + ": row_map is shorter than the selected rows need"); return -2; }
+  const int64_t row = (row_map ? (int64_t)row_map[s] : s) * width + pos;
+  if (row < 0 || row >= src_rows) {
+    fail(PG_ERR_INVALID, std::string(who) + ": selected row " + std::to_string(r) + " reads source row " + std::to_string(row) + " of " + std::to_string(src_rows));
+    return -2;
+  }
+  return row;
+}
+template <typename T>
+T* to_device(Tmp& t, const T* host, size_t n) {
+  T* p = (T*)t.get(n * sizeof(T));
+  if (p && n && hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  return p;
+}
+}  // namespace
+}  // extern "C++"
+
+int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
+                 int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
+                 const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2) {
+  int rc = dbg_prec16("pg_dbg_embed", precision);
+  if (rc) return rc;
+  if (!tokens || !embed || !x || n_seq < 1 || T < 1 || V < 1 || (pos && pos_rows < 1) || rows_per_msa < 0 || (rows_per_msa > 0 && !msa_pos) ||
+      !gamma != !beta || !gamma2 != !beta2 || !gamma2 != !h2)
+    return fail(PG_ERR_INVALID, "pg_dbg_embed: bad argument");
+  if ((rc = dbg_row_width("pg_dbg_embed", d))) return rc;
+  const int64_t n_tok = (int64_t)n_seq * T;
+  for (int64_t sq = 0; sq < n_seq; ++sq) {
+    int n_before = 0;
+    for (int t = 0; t < T; ++t) {
+      const int32_t tok = tokens[sq * T + t];
+      if (tok < 0 || tok >= V)
+        return fail(PG_ERR_INVALID, "pg_dbg_embed: token " + std::to_string(tok) + " is outside the embedding table of " + std::to_string(V) + " rows");
+      n_before += tok != pad_idx;
+      const int p = tok == pad_idx ? pad_idx : n_before + pad_idx;      // embed_ln_kernel's position row
+      if (pos && (p < 0 || p >= pos_rows))
+        return fail(PG_ERR_INVALID, "pg_dbg_embed: position row " + std::to_string(p) + " is outside the position table of " + std::to_string(pos_rows) + " rows");
+    }
+  }
+  DeviceGuard g(-1);
+  if ((rc = dbg_device(device))) return rc;
+  Tmp t;
+  const int32_t* dtok = to_device(t, tokens, (size_t)n_tok);
+  const float* de = to_device(t, embed, (size_t)V * d);
+  const float* dp = pos ? to_device(t, pos, (size_t)pos_rows * d) : nullptr;
+  const float* dm = rows_per_msa > 0 ? to_device(t, msa_pos, (size_t)rows_per_msa * d) : nullptr;
+  const float* dg = gamma ? to_device(t, gamma, (size_t)d) : nullptr;
+  const float* db = gamma ? to_device(t, beta, (size_t)d) : nullptr;
+  const float* dg2 = gamma2 ? to_device(t, gamma2, (size_t)d) : nullptr;
+  const float* db2 = gamma2 ? to_device(t, beta2, (size_t)d) : nullptr;
+  float* dx = (float*)t.get((size_t)n_tok * d * 4);
+  bf16_t* dh = h2 ? (bf16_t*)t.get((size_t)n_tok * d * 2) : nullptr;
+  if (!dtok || !de || (pos && !dp) || (rows_per_msa > 0 && !dm) || (gamma && (!dg || !db)) || (gamma2 && (!dg2 || !db2 || !dh)) || !dx)
+    return fail(PG_ERR_HIP, "hipMalloc / copy failed");
+  if ((rc = OPS(launch_embed_ln, nullptr, dtok, de, dp, dm, dg, db, dx, n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, dg2,
+                db2, dh, embed_scale)))
+    return rc;
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(x, dx, (size_t)n_tok * d * 4, hipMemcpyDeviceToHost));
+  if (h2) PG_HIP(hipMemcpy(h2, dh, (size_t)n_tok * d * 2, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
+int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                          int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel) {
+  int rc = dbg_prec16("pg_dbg_layernorm_rows", precision);
+  if (rc) return rc;
+  if (!x || !gamma || !beta || !h_inout || M < 1 || h_rows < M || form < 0 || form > 2 || colmajor_R < 0 || (colmajor_R > 0 && colmajor_C < 1))
+    return fail(PG_ERR_INVALID, "pg_dbg_layernorm_rows: bad argument");
+  if (form && (precision != PG_PREC_BF16 || d % 32))
+    return fail(PG_ERR_INVALID, "pg_dbg_layernorm_rows: split rows are bf16 pairs in groups of 32 columns");
+  if ((rc = OPS(layernorm_bf16_check, M, d, form != 0, colmajor_R, colmajor_C))) return rc;
+  DeviceGuard g(-1);
+  if ((rc = dbg_device(device))) return rc;
+  const size_t h_n = (size_t)h_rows * d * (form ? 3 : 1);
+  Tmp t;
+  const float* dx = to_device(t, x, (size_t)M * d);
+  const float* dg = to_device(t, gamma, (size_t)d);
+  const float* db = to_device(t, beta, (size_t)d);
+  bf16_t* dh = to_device(t, h_inout, h_n);      // the caller's pattern: what the kernel leaves unwritten keeps it
+  if (!dx || !dg || !db || !dh) return fail(PG_ERR_HIP, "hipMalloc / copy failed");
+  unsigned stride_grid = 0;
+  if (kernel) *kernel = OPS(layernorm_bf16_choice, M, d, colmajor_R, &stride_grid);
+  if ((rc = OPS(launch_layernorm_bf16, nullptr, dx, dg, db, dh, M, d, eps, form != 0, colmajor_R, colmajor_C, form != 2))) return rc;
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(h_inout, dh, h_n * 2, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
+int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                     int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                     float eps, int split) {
+  int rc = dbg_prec16("pg_dbg_gather_ln", precision);
+  if (rc) return rc;
+  if (!x || !gamma || !beta || !h_inout || x_rows < 1 || n_sel < 1 || h_rows < n_sel || P < 1 || width < 1 || (row_map && n_map < 1) ||
+      split < 0 || split > 1)
+    return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: bad argument");
+  if ((rc = dbg_row_width("pg_dbg_gather_ln", d))) return rc;
+  if (split && (precision != PG_PREC_BF16 || d % 32))
+    return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: split rows are bf16 pairs in groups of 32 columns");
+  if (!idx) {      // identity: selected row r = token row r
+    if (n_sel > x_rows) return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: more selected rows than source rows");
+  } else {
+    for (int64_t r = 0; r < n_sel; ++r)
+      if (dbg_gather_src("pg_dbg_gather_ln", r, idx[r], true, row_map, n_map, P, width, x_rows) == -2) return PG_ERR_INVALID;
+  }
+  DeviceGuard g(-1);
+  if ((rc = dbg_device(device))) return rc;
+  const size_t h_n = (size_t)h_rows * d * (split ? 3 : 1);
+  Tmp t;
+  const float* dx = to_device(t, x, (size_t)x_rows * d);
+  const int32_t* di = idx ? to_device(t, idx, (size_t)n_sel) : nullptr;
+  const int32_t* dm = row_map ? to_device(t, row_map, (size_t)n_map) : nullptr;
+  const float* dg = to_device(t, gamma, (size_t)d);
+  const float* db = to_device(t, beta, (size_t)d);
+  bf16_t* dh = to_device(t, h_inout, h_n);
+  if (!dx || (idx && !di) || (row_map && !dm) || !dg || !db || !dh) return fail(PG_ERR_HIP, "hipMalloc / copy failed");
+  if ((rc = OPS(launch_gather_ln_bf16, nullptr, dx, di, dm, P, width, dg, db, dh, n_sel, d, eps, split != 0))) return rc;
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(h_inout, dh, h_n * 2, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
+int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
+                       int iter, const int32_t* row_map, int64_t n_map, int P, int width, int64_t n_sel, int row_bytes) {
+  if (!src || !dst_inout || !idx || src_rows < 1 || n_sel < 1 || dst_rows < n_sel || P < 1 || width < 1 || (row_map && n_map < 1) ||
+      n_iters < 0 || (n_iters > 0 && (iter < 0 || iter >= n_iters)) || row_bytes < 16)
+    return fail(PG_ERR_INVALID, "pg_dbg_gather_rows: bad argument");
+  if (row_bytes % 16) return fail(PG_ERR_INVALID, "pg_dbg_gather_rows: rows must be multiples of 16 bytes");
+  const int32_t* now = idx + (n_iters > 0 ? (size_t)iter * n_sel : 0);      // the table row the kernel reads through d_iter
+  for (int64_t r = 0; r < n_sel; ++r)
+    if (dbg_gather_src("pg_dbg_gather_rows", r, now[r], false, row_map, n_map, P, width, src_rows) == -2) return PG_ERR_INVALID;
+  DeviceGuard g(-1);
+  int rc = dbg_device(device);
+  if (rc) return rc;
+  Tmp t;
+  const char* ds = to_device(t, (const char*)src, (size_t)src_rows * row_bytes);
+  char* dd = to_device(t, (const char*)dst_inout, (size_t)dst_rows * row_bytes);
+  const int32_t* di = to_device(t, idx, (size_t)(n_iters > 0 ? n_iters : 1) * n_sel);
+  const int32_t* dm = row_map ? to_device(t, row_map, (size_t)n_map) : nullptr;
+  const int32_t it32 = iter;
+  const int32_t* dit = n_iters > 0 ? to_device(t, &it32, 1) : nullptr;
+  if (!ds || !dd || !di || (row_map && !dm) || (n_iters > 0 && !dit)) return fail(PG_ERR_HIP, "hipMalloc / copy failed");
+  if ((rc = launch_gather_rows(nullptr, ds, dd, di, dm, P, width, n_sel, row_bytes, dit))) return rc;
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(dst_inout, dd, (size_t)dst_rows * row_bytes, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
+int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                   float* logits, int64_t n, int d, int V, float eps, int* small_kernel) {
+  if (!g || !embed || !out_bias || !logits || n < 1 || !gamma != !beta) return fail(PG_ERR_INVALID, "pg_dbg_lm_tail: bad argument");
+  if (V < 1 || V > 64) return fail(PG_ERR_INVALID, "pg_dbg_lm_tail: vocab must be in 1..64");
+  int rc = dbg_row_width("pg_dbg_lm_tail", d);
+  if (rc) return rc;
+  DeviceGuard guard(-1);
+  if ((rc = dbg_device(device))) return rc;
+  Tmp t;
+  const float* dg = to_device(t, g, (size_t)n * d);
+  const float* dga = gamma ? to_device(t, gamma, (size_t)d) : nullptr;
+  const float* dbe = gamma ? to_device(t, beta, (size_t)d) : nullptr;
+  const float* de = to_device(t, embed, (size_t)V * d);
+  const float* dob = to_device(t, out_bias, (size_t)V);
+  float* dl = to_device(t, logits, (size_t)n * V);      // the caller's pattern
+  if (!dg || (gamma && (!dga || !dbe)) || !de || !dob || !dl) return fail(PG_ERR_HIP, "hipMalloc / copy failed");
+  if (small_kernel) *small_kernel = lm_tail_small(n) ? 1 : 0;
+  if ((rc = launch_lm_tail(nullptr, dg, dga, dbe, de, dob, dl, n, d, V, eps))) return rc;
+  PG_HIP(hipDeviceSynchronize());
+  PG_HIP(hipMemcpy(logits, dl, (size_t)n * V * 4, hipMemcpyDeviceToHost));
+  return PG_OK;
+}
+
 }  // extern "C"

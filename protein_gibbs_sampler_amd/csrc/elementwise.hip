@@ -403,46 +403,62 @@ int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, co
   return 0;
 }
 
-int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
-                          int d, float eps, bool split3, int colmajor_R, int colmajor_C, bool split3_dup) {
+// The argument refusals of launch_layernorm_bf16 (0 = the launch may go ahead; touches no device) ...
+int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C) {
   if (!row_d_ok(d)) return fail(1, "layernorm: d must be a multiple of 4 and <= 2560");
   if (M == 0) return 0;
   if (!rows_fit(M)) return fail(1, "layernorm: too many rows");
   if (colmajor_R > 0) {
     if (row_wide(d)) return fail(1, "layernorm: column-major output needs d <= 2048");
     if (split3 || M % ((int64_t)colmajor_R * colmajor_C)) return fail(1, "layernorm: column-major output needs whole MSAs and plain bf16 rows");
-    hipLaunchKernelGGL(layernorm_bf16_colmajor_kernel, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, M, d, eps, colmajor_R, colmajor_C);
-    PG_HIP(hipGetLastError());
-    return 0;
   }
-  {
-    // one resident round of workgroups walking their rows when the plain grid would be 1 ... 4 rounds (layernorm_bf16_stride_kernel)
-    static const int on = env_int("PGIBBS_LN_STRIDE", 1);
-    const int n_cu = device_cu_count();
-    const unsigned g1 = rows_grid(M);
-    if (on && (d == 1280 || d == 768) && g1 > (unsigned)n_cu * 8 && g1 <= (unsigned)n_cu * 32) {
-      // the grid = what is resident at once (occupancy of this very kernel x CUs, asked once per width)
-      static int occ[2] = {0, 0};
-      int& oc = occ[d == 768];
-      if (oc == 0) {
-        int v = 0;
-        const hipError_t e = d == 1280 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, layernorm_bf16_stride_kernel<1280>, 256, 0)
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, layernorm_bf16_stride_kernel<768>, 256, 0);
-        oc = (e == hipSuccess && v > 0) ? v : -1;
-      }
-      if (oc > 0 && g1 > (unsigned)(n_cu * oc)) {
-        const dim3 grid((unsigned)(n_cu * oc));
-        const int sp = split3 ? (split3_dup ? 1 : 2) : 0;
-        if (d == 1280) hipLaunchKernelGGL(layernorm_bf16_stride_kernel<1280>, grid, dim3(256), 0, s, x, gamma, beta, h, sp, M, eps);
-        else hipLaunchKernelGGL(layernorm_bf16_stride_kernel<768>, grid, dim3(256), 0, s, x, gamma, beta, h, sp, M, eps);
-        PG_HIP(hipGetLastError());
-        return 0;
-      }
+  return 0;
+}
+// ... and its choice of kernel for M > 0 rows on the current device (LN_KERNEL_*; *stride_grid = the stride kernel's workgroups):
+// the launcher and pg_dbg_layernorm_rows, which reports it, both ask here
+int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_grid) {
+  if (colmajor_R > 0) return LN_KERNEL_COLMAJOR;
+  // one resident round of workgroups walking their rows when the plain grid would be 1 ... 4 rounds (layernorm_bf16_stride_kernel)
+  static const int on = env_int("PGIBBS_LN_STRIDE", 1);
+  const int n_cu = device_cu_count();
+  const unsigned g1 = rows_grid(M);
+  if (on && (d == 1280 || d == 768) && g1 > (unsigned)n_cu * 8 && g1 <= (unsigned)n_cu * 32) {
+    // the grid = what is resident at once (occupancy of this very kernel x CUs, asked once per width)
+    static int occ[2] = {0, 0};
+    int& oc = occ[d == 768];
+    if (oc == 0) {
+      int v = 0;
+      const hipError_t e = d == 1280 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, layernorm_bf16_stride_kernel<1280>, 256, 0)
+                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, layernorm_bf16_stride_kernel<768>, 256, 0);
+      oc = (e == hipSuccess && v > 0) ? v : -1;
+    }
+    if (oc > 0 && g1 > (unsigned)(n_cu * oc)) {
+      *stride_grid = (unsigned)(n_cu * oc);
+      return LN_KERNEL_STRIDE;
     }
   }
+  return LN_KERNEL_PLAIN;
+}
+
+int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
+                          int d, float eps, bool split3, int colmajor_R, int colmajor_C, bool split3_dup) {
+  const int rc = layernorm_bf16_check(M, d, split3, colmajor_R, colmajor_C);
+  if (rc) return rc;
+  if (M == 0) return 0;
   const int sp = split3 ? (split3_dup ? 1 : 2) : 0;
-  if (row_wide(d)) hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxChWide>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
-  else hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxCh>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+  unsigned stride_grid = 0;
+  switch (layernorm_bf16_choice(M, d, colmajor_R, &stride_grid)) {
+    case LN_KERNEL_COLMAJOR:
+      hipLaunchKernelGGL(layernorm_bf16_colmajor_kernel, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, M, d, eps, colmajor_R, colmajor_C);
+      break;
+    case LN_KERNEL_STRIDE:
+      if (d == 1280) hipLaunchKernelGGL(layernorm_bf16_stride_kernel<1280>, dim3(stride_grid), dim3(256), 0, s, x, gamma, beta, h, sp, M, eps);
+      else hipLaunchKernelGGL(layernorm_bf16_stride_kernel<768>, dim3(stride_grid), dim3(256), 0, s, x, gamma, beta, h, sp, M, eps);
+      break;
+    default:
+      if (row_wide(d)) hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxChWide>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+      else hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxCh>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+  }
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -483,6 +499,12 @@ int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t*
   return 0;
 }
 
+// launch_lm_tail's choice between lm_tail_small_kernel (true) and lm_tail_kernel; pg_dbg_lm_tail reports it
+bool lm_tail_small(int64_t n) {
+  static const int small_max = env_int("PGIBBS_LM_TAIL_SMALL", 1024);
+  return n <= small_max;
+}
+
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
                    const float* out_bias, float* logits, int64_t n, int d, int V, float eps) {
   if (V < 1 || V > 64) return fail(1, "lm_tail: vocab must be in 1..64");      // lane t keeps logit t; 64 * ceil(V / 4) <= 1024 threads
@@ -492,8 +514,7 @@ int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const floa
   // identical arithmetic per logit (same per-lane partial sums, same wave reduction): bit-equal results.  Up to 1024 rows (round 5;
   // it was 128): a 32-chain shard's 800 sampled rows took 81 us on the row-per-wave kernel -- 200 workgroups, each wave walking the
   // decoder rows in nine dependent trips -- PGIBBS_LM_TAIL_SMALL=n moves the switch
-  static const int small_max = env_int("PGIBBS_LM_TAIL_SMALL", 1024);
-  if (n <= small_max) {
+  if (lm_tail_small(n)) {
     // no shared memory; every wave holds the row and four decoder rows' chunks (NCH + 4 float4 in flight at most: far below the
     // 128 VGPRs a 1024-thread workgroup may use per lane)
     if (row_wide(d))

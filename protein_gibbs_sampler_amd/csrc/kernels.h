@@ -46,6 +46,9 @@ enum { EPI_BF16 = 0, EPI_BF16_GELU = 1, EPI_F32_RESID = 2, EPI_F32 = 3, EPI_F32_
        EPI_SPLIT2_GELU = 7 /* the same rows without the duplicate hi block ([lo | hi | --], same ldo): for an fc2 that runs on the fused
                               three-product kernel, which never reads it (gemm_split3_fused) -- a third less epilogue traffic */ };
 
+// launch_layernorm_bf16's kernels, as layernorm_bf16_choice names them (pg_dbg_layernorm_rows reports the value)
+enum { LN_KERNEL_PLAIN = 0, LN_KERNEL_STRIDE = 1, LN_KERNEL_COLMAJOR = 2 };
+
 // ---- the operand-flavoured kernel families (pg_common.h): declared in both namespaces, defined once per flavour ----
 inline namespace opbf16 {
 #include "kernels_ops.inc"

@@ -116,6 +116,10 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
                           int d, float eps, bool split3 = false,   // split3: h rows are [lo | hi | hi], 3 d wide
                           int colmajor_R = 0, int colmajor_C = 0,  // > 0: token row (b*R + r)*C + c is written as row (b*C + c)*R + r
                           bool split3_dup = true);                 // false: the duplicate hi block is not written (fused consumer)
+// its argument refusals alone (0 = fine; no HIP call), and the kernel it picks for M > 0 rows on the current device (LN_KERNEL_*;
+// *stride_grid = the stride kernel's workgroup count): one definition for the launcher and for the debug entry that reports it
+int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C);
+int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_grid);
 // ESM-MSA-1b column attention fused into its QKV projection (gemm_colattn.hip): X = LayerNorm rows in column-major token order,
 // W / bias = the projection's rows grouped per head (launch_headmajor_qkv); ctx rows in ordinary token order.  R in {32,64,128,256}
 bool colattn_ok(int R, int d_model, int n_heads);
@@ -149,6 +153,7 @@ int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t*
                        int64_t n_sel, int row_bytes, const int32_t* d_iter = nullptr);
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
                    const float* out_bias, float* logits, int64_t n, int d, int V, float eps);
+bool lm_tail_small(int64_t n);      // launch_lm_tail's choice: the workgroup-per-row kernel (n <= PGIBBS_LM_TAIL_SMALL, 1024)
 int launch_f32_to_bf16(hipStream_t s, const float* src, bf16_t* dst, int64_t n, float scale);
 int launch_bf16_to_f32(hipStream_t s, const bf16_t* src, float* dst, int64_t n);
 int launch_scale_f32(hipStream_t s, float* p, int64_t n, float scale);

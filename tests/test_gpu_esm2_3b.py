@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import _esm2_reference as ref
+from _ln_host import _fma32, _ln_inplace_host, _wave_sum  # noqa: F401  (the host restatement of csrc/ln_row.h)
 from oracle import draw as odraw
 from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
 
@@ -75,71 +76,6 @@ def test_layernorm_refuses_rows_wider_than_2560():
     assert L.pg_dbg_layernorm(0, _lib.ptr(x), _lib.ptr(g), _lib.ptr(b), _lib.ptr(y), 2, 2816, 1e-5) != 0
     assert b"2560" in L.pg_last_error()
     assert L.pg_dbg_layernorm_operand(0, _lib.PG_PREC_BF16, _lib.ptr(x), _lib.ptr(g), _lib.ptr(b), _lib.ptr(y), 2, 2816, 1e-5) != 0
-
-
-def _fma32(a, b, c):
-    """float32 fma(a, b, c) on arrays: the product is exact in double; the sum is rounded to double and then to float32, and the rare
-    double rounding (the double sum lands exactly on a float32 tie) is repaired from the exact error of the double addition."""
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = c.astype(np.float64)
-    s = p + c
-    bb = s - p
-    err = (p - (s - bb)) + (c - bb)                              # TwoSum: p + c = s + err exactly
-    r = s.astype(F32)
-    tie = (err != 0) & (((s.view(np.uint64) & np.uint64((1 << 29) - 1)) == np.uint64(1 << 28)))
-    if tie.any():
-        up = np.nextafter(s, np.where(err > 0, np.inf, -np.inf))  # move off the tie in the direction of the exact value
-        r = np.where(tie, up.astype(F32), r)
-    return r
-
-
-def _wave_sum(v):
-    """wave_sum of ln_row.h on [rows][64] float32: v += shfl_xor(v, o) for o = 32, 16, ... 1."""
-    lanes = np.arange(64)
-    for o in (32, 16, 8, 4, 2, 1):
-        v = (v + v[:, lanes ^ o]).astype(F32)
-    return v
-
-
-def _ln_inplace_host(x, g, b, eps, sqrt_ulps=0):
-    """ln_inplace (csrc/ln_row.h) in numpy float32, operation for operation: lane l holds float4 chunks l, l + 64, ...; per lane the
-    chunks in ascending order, then the butterfly.  The one operation a host cannot restate is the square root: the device's is the
-    hardware instruction, accurate to one ulp and not always the correctly rounded value -- `sqrt_ulps` moves the host's root by
-    that many ulps."""
-    M, d = x.shape
-    nch4 = d // 4
-    n_i = (nch4 + 63) // 64
-    v = np.zeros((M, n_i, 64, 4), dtype=F32)
-    have = np.zeros((n_i, 64), dtype=bool)
-    for i in range(n_i):
-        n = min(64, nch4 - 64 * i)
-        v[:, i, :n] = x[:, 256 * i:256 * i + 4 * n].reshape(M, n, 4)
-        have[i, :n] = True
-    s = np.zeros((M, 64), dtype=F32)
-    for i in range(n_i):
-        t = ((v[:, i, :, 0] + v[:, i, :, 1]).astype(F32) + (v[:, i, :, 2] + v[:, i, :, 3]).astype(F32)).astype(F32)
-        s = np.where(have[i], (s + t).astype(F32), s)
-    mean = (_wave_sum(s) / F32(d)).astype(F32)                  # [M][64], every lane the same value
-    q = np.zeros((M, 64), dtype=F32)
-    for i in range(n_i):
-        v[:, i] = (v[:, i] - mean[:, :, None]).astype(F32)
-        c = v[:, i]
-        t = (_fma32(c[..., 0], c[..., 0], (c[..., 1] * c[..., 1]).astype(F32)) +
-             _fma32(c[..., 2], c[..., 2], (c[..., 3] * c[..., 3]).astype(F32))).astype(F32)
-        q = np.where(have[i], (q + t).astype(F32), q)
-    var = ((_wave_sum(q) / F32(d)).astype(F32) + F32(eps)).astype(F32)
-    root = np.sqrt(var).astype(F32)
-    for _ in range(abs(sqrt_ulps)):
-        root = np.nextafter(root, F32(np.inf if sqrt_ulps > 0 else 0.0))
-    rstd = (F32(1.0) / root).astype(F32)
-    out = np.empty_like(x)
-    for i in range(n_i):
-        n = min(64, nch4 - 64 * i)
-        gg = g[256 * i:256 * i + 4 * n].reshape(n, 4)
-        bb = b[256 * i:256 * i + 4 * n].reshape(n, 4)
-        y = _fma32((v[:, i, :n] * rstd[:, :n, None]).astype(F32), np.broadcast_to(gg, (M, n, 4)), np.broadcast_to(bb, (M, n, 4)))
-        out[:, 256 * i:256 * i + 4 * n] = y.reshape(M, 4 * n)
-    return out
 
 
 @pytest.mark.parametrize("d", [1280, 768, 2560, 2304])
