@@ -353,11 +353,26 @@ int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H
 int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
                         const int32_t* key_tok, int pad_idx);
 int pg_dbg_rope_hd(int device, int precision, float* qkv_inout, int B, int T, int H, int head_dim);
+/* pg_dbg_attention_hd with ESM-1's bias key (add_bias_kv): bias_k / bias_v [H][head_dim] fp32, both or neither -- one more key behind
+ * the T token keys, attended by every query, never masked.  The entry lays the two out as the engine does ([bias_k | bias_v], k of
+ * head h at h*head_dim, v at (H + h)*head_dim), in the 16-bit type of `precision` or fp32 for PG_PREC_FP32.  Every argument is checked
+ * on the host before a device is looked for (null / non-null pairs, the head dimension, the bias key at head 32 -- the plan's own
+ * refusal text --, sizes): PG_ERR_INVALID with a message, never a launch.  plan (NULL: not wanted): receives the text the launch
+ * recorded, as pg_dbg_attention_plan words it.  The two entries above are calls of this one */
+int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+                        const int32_t* key_tok, int pad_idx, const float* bias_k, const float* bias_v, char* plan, int plan_bytes);
 
 /* MSA attention blocks: qkv[B][R][C][3*H*64] fp32 -> ctx[B][R][C][H*64]; which = 0 tied row attention (scores * scale),
  * 1 column attention (q pre-scaled); 2 / 3 = the same two with the strict precision mode's kernels; 4 / 5 = 0 / 1 with fp16
  * operands */
 int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale);
+/* the same with the tokens tok[B][R][C] of a batch that holds <pad> (NULL: none; pg_dbg_msa_attention is a call of this).  Column
+ * attention (which 1, 3, 5): the key rows that are pad_idx at a column get fair-esm's fill of -10000.  Tied row attention with tokens
+ * takes the engine's route for a ragged batch: which 0 widens the 16-bit q, k, v to fp32 and runs the fp32-scores kernels with 16-bit
+ * context rows, which 2 is the strict mode, which 4 (fp16) is refused with the engine's message (PG_ERR_UNSUPPORTED).  Arguments are
+ * checked on the host before a device is looked for.  plan (NULL: not wanted): the text the launches recorded */
+int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale,
+                             const int32_t* tok, int pad_idx, char* plan, int plan_bytes);
 
 
 /* ---- the memory-bound row kernels (csrc/elementwise.hip), each through its launcher ----

@@ -120,7 +120,11 @@ SIGNATURES = [
     ("pg_dbg_rope", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int]),
     ("pg_dbg_attention_hd", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),
     ("pg_dbg_rope_hd", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int]),
+    ("pg_dbg_attention_kv", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_char_p, c_int]),
     ("pg_dbg_msa_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float]),
+    ("pg_dbg_msa_attention_tok", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int,
+                                         c_char_p, c_int]),
     ("pg_dbg_embed", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     ("pg_dbg_layernorm_rows", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_int,

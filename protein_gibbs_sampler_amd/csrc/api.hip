@@ -837,9 +837,29 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
  * pad_idx are masked as in a ragged batch (NULL: none) */
 int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
                         const int32_t* key_tok, int pad_idx) {
+  return pg_dbg_attention_kv(device, precision, qkv, ctx, B, T, H, head_dim, key_tok, pad_idx, nullptr, nullptr, nullptr, 0);
+}
+
+namespace {
+// what a debug entry's launches recorded (note_kernel), into the caller's buffer
+void dbg_noted_text(char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) snprintf(plan, (size_t)plan_bytes, "%s", noted_kernels().c_str());
+}
+}  // namespace
+
+/* pg_dbg_attention_hd with ESM-1's bias key: bias_k / bias_v [H][head_dim] fp32 (both or neither), laid out as the engine lays them
+ * out -- [bias_k | bias_v], k of head h at h*HD, v at (H + h)*HD -- in the operand type of `precision` (fp32 for the strict
+ * kernels).  Everything is checked on the host before a device is looked for.  plan (may be NULL): the text the launch recorded */
+int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+                        const int32_t* key_tok, int pad_idx, const float* bias_k, const float* bias_v, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
   if (precision != PG_PREC_BF16 && precision != PG_PREC_FP32 && precision != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
-  if (!qkv || !ctx || B < 1 || T < 1 || H < 1) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
+  if (!qkv || !ctx || B < 1 || T < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
   if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32");
+  if (!bias_k != !bias_v) return fail(PG_ERR_INVALID, "pg_dbg_attention_kv: bias_k and bias_v come together or not at all");
+  const std::string head_err = attention_head_error(head_dim, bias_k != nullptr);      // the plans' own refusal of a bias key at head 32
+  if (!head_err.empty()) return fail(PG_ERR_INVALID, head_err);
+  if ((double)B * T * 3 * H * head_dim > 2147483647.0) return fail(PG_ERR_INVALID, "pg_dbg_attention: more than 2^31 - 1 qkv values");
   DeviceGuard g(-1);
   int rc = dbg_device(device);
   if (rc) return rc;
@@ -853,21 +873,33 @@ int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx,
     if (!dtok) return fail(PG_ERR_HIP, "hipMalloc failed");
     PG_HIP(hipMemcpy(dtok, key_tok, (size_t)M * 4, hipMemcpyHostToDevice));
   }
+  float* bias32 = nullptr;      // [bias_k | bias_v], d fp32 each
+  if (bias_k) {
+    bias32 = (float*)t.get((size_t)2 * d * 4);
+    if (!bias32) return fail(PG_ERR_HIP, "hipMalloc failed");
+    PG_HIP(hipMemcpy(bias32, bias_k, (size_t)d * 4, hipMemcpyHostToDevice));
+    PG_HIP(hipMemcpy(bias32 + d, bias_v, (size_t)d * 4, hipMemcpyHostToDevice));
+  }
+  clear_noted_kernels();
   if (precision == PG_PREC_FP32) {
     bf16_t* c3 = (bf16_t*)t.get((size_t)M * 3 * d * 2);
     if (!dq || !c3) return fail(PG_ERR_HIP, "hipMalloc failed");
     PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
     const SeqLayout chain = {1, T, 0, 1};
-    if ((rc = launch_attention_f32(nullptr, dq, c3, d, B, T, H, 3 * d, 3 * d, d, 2 * d, chain, dtok, pad_idx, nullptr, head_dim))) return rc;
+    if ((rc = launch_attention_f32(nullptr, dq, c3, d, B, T, H, 3 * d, 3 * d, d, 2 * d, chain, dtok, pad_idx, bias32, head_dim))) return rc;
+    dbg_noted_text(plan, plan_bytes);
     return split3_rows_to_host(c3, ctx, M, d);
   }
   bf16_t* bq = (bf16_t*)t.get((size_t)M * 3 * d * 2);
   bf16_t* bc = (bf16_t*)t.get((size_t)M * d * 2);
   float* dc = (float*)t.get((size_t)M * d * 4);
-  if (!dq || !bq || !bc || !dc) return fail(PG_ERR_HIP, "hipMalloc failed");
+  bf16_t* bias16 = bias_k ? (bf16_t*)t.get((size_t)2 * d * 2) : nullptr;
+  if (!dq || !bq || !bc || !dc || (bias_k && !bias16)) return fail(PG_ERR_HIP, "hipMalloc failed");
   PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
   if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
-  if ((rc = OPS(launch_attention_bf16, nullptr, bq, bc, B, T, H, 3 * d, d, d, 2 * d, dtok, pad_idx, nullptr, head_dim))) return rc;
+  if (bias_k && (rc = OPS(launch_f32_to_bf16, nullptr, bias32, bias16, 2 * d, 1.f))) return rc;
+  if ((rc = OPS(launch_attention_bf16, nullptr, bq, bc, B, T, H, 3 * d, d, d, 2 * d, dtok, pad_idx, bias16, head_dim))) return rc;
+  dbg_noted_text(plan, plan_bytes);
   if ((rc = OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(ctx, dc, (size_t)M * d * 4, hipMemcpyDeviceToHost));
@@ -941,7 +973,25 @@ int pg_dbg_rope_hd(int device, int precision, float* qkv, int B, int T, int H, i
 /* MSA attention blocks on fp32 host buffers qkv[B][R][C][3*H*64] -> ctx[B][R][C][H*64]; which: 0 = tied row attention
  * (scores scaled by `scale`), 1 = column attention (q already scaled); 2 / 3 = the same two in the strict precision mode */
 int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale) {
-  if (!qkv || !ctx || B < 1 || R < 1 || C < 1 || H < 1) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: bad argument");
+  return pg_dbg_msa_attention_tok(device, which, qkv, ctx, B, R, C, H, scale, nullptr, -1, nullptr, 0);
+}
+
+/* pg_dbg_msa_attention with the tokens tok[B][R][C] of a batch that holds <pad> (NULL: none, pg_dbg_msa_attention itself).  Column
+ * attention (which 1, 3, 5) hands them to its launcher.  Tied row attention with tokens takes the engine's route for a ragged batch:
+ * which 0 widens the bf16 q, k, v to fp32 and runs launch_msa_row_attention_f32 with 16-bit context rows, which 2 is the strict
+ * kernel, which 4 (fp16) is refused as the engine refuses it.  Everything is checked on the host before a device is looked for.
+ * plan (may be NULL): the text the launches recorded */
+int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale,
+                             const int32_t* tok, int pad_idx, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  if (!qkv || !ctx || B < 1 || R < 1 || C < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: bad argument");
+  if (which < 0 || which > 5) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: which must be 0 ... 5");
+  if ((double)B * R * C * 3 * H * 64 > 2147483647.0) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: more than 2^31 - 1 qkv values");
+  if (tok && which == 4)
+    return fail(PG_ERR_UNSUPPORTED, "fp16 precision mode: alignments wider than 576 columns take the split-bf16 row attention, "
+                                    "which exists for bf16 operands only -- use precision bf16 or fp32");
+  if ((which == 2 || (which == 0 && tok)) && (double)B * H * C * msa_row_scores_ld(C) > 1073741823.0)
+    return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: the fp32 score maps of this shape exceed 4 GiB");
   const int precision = (which == 4 || which == 5) ? PG_PREC_F16 : PG_PREC_BF16;      // 4 / 5: which 0 / 1 with fp16 operands
   if (which == 4 || which == 5) which -= 4;
   DeviceGuard g(-1);
@@ -951,15 +1001,23 @@ int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, in
   const int64_t M = (int64_t)B * R * C;
   Tmp t;
   float* dq = (float*)t.get((size_t)M * 3 * d * 4);
+  int32_t* dtok = nullptr;
+  if (tok) {
+    dtok = (int32_t*)t.get((size_t)M * 4);
+    if (!dtok) return fail(PG_ERR_HIP, "hipMalloc failed");
+    PG_HIP(hipMemcpy(dtok, tok, (size_t)M * 4, hipMemcpyHostToDevice));
+  }
+  clear_noted_kernels();
   if (which == 2 || which == 3) {      // strict precision mode kernels: fp32 in, [lo | hi | hi] operand rows out
     bf16_t* c3 = (bf16_t*)t.get((size_t)M * 3 * d * 2);
     float* sc = which == 2 ? (float*)t.get((size_t)B * H * C * msa_row_scores_ld(C) * 4) : nullptr;
     if (!dq || !c3 || (which == 2 && !sc)) return fail(PG_ERR_HIP, "hipMalloc failed");
     PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
     const SeqLayout col = {C, R * C, 1, C};
-    if (which == 2) rc = launch_msa_row_attention_f32(nullptr, dq, sc, c3, d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, scale);
-    else rc = launch_attention_f32(nullptr, dq, c3, d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, col);
+    if (which == 2) rc = launch_msa_row_attention_f32(nullptr, dq, sc, c3, d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, scale, dtok, pad_idx);
+    else rc = launch_attention_f32(nullptr, dq, c3, d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, col, dtok, pad_idx);
     if (rc) return rc;
+    dbg_noted_text(plan, plan_bytes);
     return split3_rows_to_host(c3, ctx, M, d);
   }
   bf16_t* bq = (bf16_t*)t.get((size_t)M * 3 * d * 2);
@@ -968,15 +1026,23 @@ int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, in
   if (!dq || !bq || !bc || !dc) return fail(PG_ERR_HIP, "hipMalloc failed");
   PG_HIP(hipMemcpy(dq, qkv, (size_t)M * 3 * d * 4, hipMemcpyHostToDevice));
   if ((rc = OPS(launch_f32_to_bf16, nullptr, dq, bq, M * 3 * d, 1.f))) return rc;
-  if (which == 0) {
+  if (which == 0 && tok) {
+    // a ragged batch, as Engine::msa_trunk runs it: the 16-bit q, k, v widened to fp32, fp32 scores through a scratch buffer
+    float* wide = (float*)t.get((size_t)M * 3 * d * 4);
+    float* sc = (float*)t.get((size_t)B * H * C * msa_row_scores_ld(C) * 4);
+    if (!wide || !sc) return fail(PG_ERR_HIP, "hipMalloc failed");
+    if ((rc = launch_bf16_to_f32(nullptr, bq, wide, M * 3 * d))) return rc;
+    if ((rc = launch_msa_row_attention_f32(nullptr, wide, sc, bc, 0, B, R, C, H, 3 * d, d, d, 2 * d, scale, dtok, pad_idx))) return rc;
+  } else if (which == 0) {
     // scratch for the split-R mode (taken when B*H*ceil(C/64) < 384 and R >= 8), so the tests exercise both modes
     const size_t pbytes = (size_t)B * H * 16 * C * 576 * 4 + (size_t)B * H * (C / 16 + 9) * 18 * 1024;
     float* part = pbytes <= ((size_t)1 << 30) ? (float*)t.get(pbytes) : nullptr;
     if ((rc = OPS(launch_msa_row_attention_bf16, nullptr, bq, bc, B, R, C, H, 3 * d, d, d, 2 * d, scale, part, part ? pbytes : 0, 0))) return rc;
   } else {
     SeqLayout col = {C, R * C, 1, C};
-    if ((rc = OPS(launch_attention_seq_bf16, nullptr, bq, bc, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, nullptr, -1))) return rc;
+    if ((rc = OPS(launch_attention_seq_bf16, nullptr, bq, bc, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, dtok, pad_idx))) return rc;
   }
+  dbg_noted_text(plan, plan_bytes);
   if ((rc = OPS(launch_bf16_to_f32, nullptr, bc, dc, M * d))) return rc;
   PG_HIP(hipDeviceSynchronize());
   PG_HIP(hipMemcpy(ctx, dc, (size_t)M * d * 4, hipMemcpyDeviceToHost));

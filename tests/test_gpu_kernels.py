@@ -4,6 +4,7 @@ transposed operand or output cannot pass."""
 import numpy as np
 import pytest
 
+import _attention_reference as ar
 from protein_gibbs_sampler_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -119,6 +120,9 @@ def test_attention(B, T, H):
     # P and the output are rounded to bf16 (8-bit mantissa): abs error ~ 2^-8 * |ctx|
     assert np.abs(ctx - ref).max() < 2.5e-2, np.abs(ctx - ref).max()
     assert np.abs(ctx - ref).mean() < 3e-3
+    # and element by element, under the bound derived in tests/_attention_reference.py (test_gpu_attention_kernels.py runs every form)
+    res = ar.chain_attention(_bf16(qkv), H, 64)
+    assert (np.abs(ctx - res.ref) <= ar.bound(res, "bf16")).all()
 
 
 _ATT_SPLIT_CHILD = """
