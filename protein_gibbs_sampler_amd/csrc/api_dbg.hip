@@ -1,0 +1,684 @@
+// The kernel-level test and measurement entries of include/pgibbs.h (pg_dbg_*; the two gather hooks live in comm.cpp).  No kernels here.
+// Every entry has the same three steps: validate on the host (a wrong argument is PG_ERR_INVALID with a message, before a device is
+// looked for); open a Dbg scope on the device; upload, check the scope once, launch, download.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "engine.h"
+#include "gemm_epilogue.h"
+
+using namespace pg;
+
+namespace {
+// One entry's device, buffers and copies.  A failed allocation or copy is remembered and turns the calls after it into no-ops that
+// return null: an entry asks check() once, after its uploads and before its first launch.  A null host pointer given to up() is an
+// optional array the caller left out -- a null device pointer, not a failure.  Leaving the scope frees the buffers and restores
+// the caller's device.
+struct Dbg {
+  int prev = -1;
+  bool bad = false;
+  std::vector<void*> bufs;
+  Dbg() { (void)hipGetDevice(&prev); }
+  ~Dbg() {
+    for (void* p : bufs) (void)hipFree(p);
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+  int open(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(PG_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= n) return fail(PG_ERR_INVALID, "bad device ordinal");
+    PG_HIP(hipSetDevice(device));
+    return PG_OK;
+  }
+  template <typename T>
+  T* alloc(size_t n) {      // zero-filled
+    const size_t bytes = n ? n * sizeof(T) : 4;
+    void* p = nullptr;
+    if (bad || hipMalloc(&p, bytes) != hipSuccess) {
+      bad = true;
+      return nullptr;
+    }
+    bufs.push_back(p);
+    (void)hipMemset(p, 0, bytes);
+    return (T*)p;
+  }
+  template <typename T>
+  void put(T* dev, const T* host, size_t n) {
+    if (bad || !n) return;
+    bad = hipMemcpy(dev, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess;
+  }
+  template <typename T>
+  T* up(const T* host, size_t n) {
+    T* p = host ? alloc<T>(n) : nullptr;
+    put(p, host, p ? n : 0);
+    return bad ? nullptr : p;
+  }
+  int check(const char* what = "hipMalloc failed") const { return bad ? fail(PG_ERR_HIP, what) : PG_OK; }
+  template <typename T>
+  int down(T* host, const T* dev, size_t n) const {
+    PG_HIP(hipDeviceSynchronize());
+    PG_HIP(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost));
+    return PG_OK;
+  }
+};
+
+// fp32_ok: the entry also runs the strict mode's kernels; otherwise it takes the two 16-bit modes only
+int dbg_precision(const char* who, int precision, bool fp32_ok) {
+  if (precision == PG_PREC_BF16 || precision == PG_PREC_F16) return PG_OK;
+  if (!fp32_ok) return fail(PG_ERR_INVALID, std::string(who) + ": precision must be PG_PREC_BF16 or PG_PREC_F16");
+  return precision == PG_PREC_FP32 ? PG_OK : fail(PG_ERR_INVALID, "unknown precision mode");
+}
+// n device fp32 values -> the 16-bit operand type of `precision`
+int to16(int precision, const float* src, bf16_t* dst, int64_t n, float scale = 1.f) {
+  return OPS(launch_f32_to_bf16, nullptr, src, dst, n, scale);
+}
+// n device values of the 16-bit type of `precision` -> host fp32, widened through the device buffer `wide`
+int down16(const Dbg& d, int precision, const bf16_t* rows, float* wide, float* host, int64_t n) {
+  const int rc = OPS(launch_bf16_to_f32, nullptr, rows, wide, n);
+  return rc ? rc : d.down(host, wide, (size_t)n);
+}
+// device rows in the strict mode's split operand layout (3 d bf16: per group of 32 columns [lo | hi | hi]) -> host fp32 rows
+// hi + lo; also checks that the two hi copies agree
+int split3_rows_to_host(const bf16_t* c3, float* dst, int64_t M, int d) {
+  PG_HIP(hipDeviceSynchronize());
+  std::vector<bf16_t> h((size_t)M * 3 * d);
+  PG_HIP(hipMemcpy(h.data(), c3, h.size() * 2, hipMemcpyDeviceToHost));
+  for (int64_t r = 0; r < M; ++r)
+    for (int c = 0; c < d; ++c) {
+      const size_t g = (size_t)r * 3 * d + (size_t)(c >> 5) * 96 + (c & 31);
+      const bf16_t lo = h[g], hi = h[g + 32], hi2 = h[g + 64];
+      if (hi != hi2) return fail(PG_ERR_HIP, "split operand row: the two hi copies differ");
+      dst[(size_t)r * d + c] = bf16_to_f32(hi) + bf16_to_f32(lo);
+    }
+  return PG_OK;
+}
+// the benches' operands: n values uniform in [-1, 1) from a 32-bit LCG
+std::vector<float> lcg_uniform(size_t n, uint32_t seed) {
+  std::vector<float> h(n);
+  for (auto& v : h) {
+    seed = seed * 1664525u + 1013904223u;
+    v = (seed >> 8) * (1.0f / 8388608.0f) - 1.0f;
+  }
+  return h;
+}
+// 2 warm-up launches, then `iters` launches between two events on the null stream: *avg_ms = elapsed / iters
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+template <typename Launch>
+int time_launches(Launch&& launch, int iters, double* avg_ms) {
+  EventPair ev;
+  for (hipEvent_t* e : {&ev.a, &ev.b}) PG_HIP(hipEventCreate(e));
+  int rc;
+  for (int i = 0; i < 2; ++i)
+    if ((rc = launch())) return rc;
+  PG_HIP(hipEventRecord(ev.a, nullptr));
+  for (int i = 0; i < iters; ++i)
+    if ((rc = launch())) return rc;
+  PG_HIP(hipEventRecord(ev.b, nullptr));
+  PG_HIP(hipEventSynchronize(ev.b));
+  float ms = 0;
+  PG_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+  *avg_ms = ms / iters;
+  return PG_OK;
+}
+// what a debug entry's launches recorded (note_kernel), into the caller's buffer
+void dbg_noted_text(char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) snprintf(plan, (size_t)plan_bytes, "%s", noted_kernels().c_str());
+}
+
+// What pg_dbg_attention_kv and pg_dbg_msa_attention_tok do once their arguments are checked and their scope is open, around
+// launch(dq, bq, out, dtok): qkv[M][3 d] and the optional tokens go up; strict: launch reads the fp32 dq (bq null) and writes split
+// rows `out` [M][3 d], returned as hi + lo; otherwise it reads the 16-bit bq and writes 16-bit rows `out` [M][d], returned widened.
+// Buffers of the entry's own are allocated in `s` before this is called, so that the one check covers them.
+template <typename Launch>
+int dbg_attention_run(Dbg& s, int precision, bool strict, const float* qkv, float* ctx, int64_t M, int d, const int32_t* tok, char* plan,
+                      int plan_bytes, Launch&& launch) {
+  const float* dq = s.up(qkv, (size_t)M * 3 * d);
+  const int32_t* dtok = s.up(tok, (size_t)M);
+  bf16_t* bq = strict ? nullptr : s.alloc<bf16_t>((size_t)M * 3 * d);
+  bf16_t* out = s.alloc<bf16_t>((size_t)M * d * (strict ? 3 : 1));
+  float* wide = strict ? nullptr : s.alloc<float>((size_t)M * d);
+  int rc = s.check();
+  if (rc) return rc;
+  clear_noted_kernels();
+  if (!strict && (rc = to16(precision, dq, bq, M * 3 * d))) return rc;
+  if ((rc = launch(dq, bq, out, dtok))) return rc;
+  dbg_noted_text(plan, plan_bytes);
+  return strict ? split3_rows_to_host(out, ctx, M, d) : down16(s, precision, out, wide, ctx, M * d);
+}
+}  // namespace
+
+extern "C" {
+
+int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N,
+                int K, int epi) {
+  int rc = dbg_precision("pg_dbg_gemm", precision, true);
+  if (rc) return rc;
+  if (!x || !w || !bias || !out || M < 1 || N % 64 || K % 64) return fail(PG_ERR_INVALID, "pg_dbg_gemm: bad argument");
+  const bool strict = precision == PG_PREC_FP32;      // K-concatenated split-bf16 operands (engine.h dense3)
+  if (strict && epi == 5 && N % 256) return fail(PG_ERR_INVALID, "pg_dbg_gemm: the fused GELU-and-split epilogue needs N a multiple of 256");
+  if (strict && epi != 0 && epi != 2 && epi != 5)
+    return fail(PG_ERR_UNSUPPORTED, "strict mode: plain (0), residual (2) and fused GELU-split (5) epilogues only");
+  Dbg d;
+  if ((rc = d.open(device))) return rc;
+  const int Mp = round_up(M, kRowPad), ks = strict ? 3 : 1;
+  const int M16 = M <= 256 ? round_up(M, 16) : Mp;      // the rows the 16-bit kernels are given
+  const bool out16 = !strict && (epi == 3 || epi == 4);      // bf16 outputs (the QKV / fc1 epilogues), widened to fp32 for the caller
+  float* dx = d.alloc<float>((size_t)Mp * K);
+  d.put(dx, x, (size_t)M * K);
+  const float* dw = d.up(w, (size_t)N * K);
+  const float* db = d.up(bias, (size_t)N);
+  float* dout = d.alloc<float>((size_t)Mp * N);
+  if (epi == 2) d.put(dout, out, (size_t)M * N);      // residual variant: out += x w^T + b
+  bf16_t* bx = d.alloc<bf16_t>((size_t)Mp * K * ks);
+  bf16_t* bw = d.alloc<bf16_t>((size_t)N * K * ks);
+  // fc1's fused strict epilogue (5): operand rows [lo | hi | hi] of gelu(x w^T + b), returned as hi + lo
+  bf16_t* o16 = strict && epi == 5 ? d.alloc<bf16_t>((size_t)Mp * 3 * N) : out16 ? d.alloc<bf16_t>((size_t)Mp * N) : nullptr;
+  // the residual variant gets split-K scratch, as the engine gives its fc2 GEMMs (taken for deep K and few tiles)
+  const size_t ws_bytes = !strict && epi == 2 ? OPS(gemm_splitk_ws_bytes, Mp, N, K) : 0;
+  float* ws = ws_bytes && ws_bytes <= ((size_t)1 << 30) ? (float*)d.alloc<char>(ws_bytes) : nullptr;
+  if ((rc = d.check())) return rc;
+  if (strict) {
+    if ((rc = launch_split3_bf16(nullptr, dx, bx, Mp, K, 1.f, false, false))) return rc;
+    if ((rc = launch_split3_bf16(nullptr, dw, bw, N, K, 1.f, false, true))) return rc;
+    if (epi == 5) {
+      if ((rc = launch_gemm_split3(nullptr, bx, bw, db, o16, Mp, N, K, 3 * N, EPI_SPLIT3_GELU))) return rc;
+      return split3_rows_to_host(o16, out, M, N);
+    }
+    if ((rc = launch_gemm_split3(nullptr, bx, bw, db, dout, Mp, N, K, N, epi == 2 ? EPI_F32_RESID : EPI_F32))) return rc;
+    return d.down(out, dout, (size_t)M * N);
+  }
+  if ((rc = to16(precision, dx, bx, (int64_t)Mp * K))) return rc;
+  if ((rc = to16(precision, dw, bw, (int64_t)N * K))) return rc;
+  if (out16) {
+    if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, o16, M16, N, K, K, K, N, epi == 4 ? EPI_BF16_GELU : EPI_BF16, nullptr, 0, M))) return rc;
+    return down16(d, precision, o16, dout, out, (int64_t)M * N);
+  }
+  if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, dout, M16, N, K, K, K, N, epi == 2 ? EPI_F32_RESID : (epi ? EPI_F32_GELU : EPI_F32), ws,
+                ws ? ws_bytes : 0, M))) return rc;
+  return d.down(out, dout, (size_t)M * N);
+}
+
+int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int iters, double* avg_ms) {
+  if (!avg_ms || M % 16 || (M > 256 && M % 64) || N % 64 || K % 64 || iters < 1) return fail(PG_ERR_INVALID, "pg_dbg_gemm_bench: bad argument");
+  if (variant == 90 && (K % 96 || (epi != EPI_F32 && epi != EPI_F32_RESID))) return fail(PG_ERR_INVALID, "variant 90: K = 3 x depth, fp32 epilogues");
+  Dbg d;
+  int rc = d.open(device);
+  if (rc) return rc;
+  const std::vector<float> h = lcg_uniform((size_t)(M > N ? M : N) * K, 12345u);
+  const float* f = d.up(h.data(), h.size());
+  bf16_t* bx = d.alloc<bf16_t>((size_t)round_up(M, kRowPad) * K);      // kernels may touch the padding rows of the last tile
+  bf16_t* bw = d.alloc<bf16_t>((size_t)N * K);
+  const float* db = d.alloc<float>((size_t)N);
+  void* dout = d.alloc<float>((size_t)round_up(M, kRowPad) * N);
+  const size_t ws_bytes = (epi == EPI_F32_RESID && M <= 8192) ? gemm_splitk_ws_bytes(M, N, K) : 0;
+  float* ws = ws_bytes ? (float*)d.alloc<char>(ws_bytes) : nullptr;
+  if ((rc = d.check())) return rc;
+  if ((rc = to16(PG_PREC_BF16, f, bx, (int64_t)M * K))) return rc;
+  if ((rc = to16(PG_PREC_BF16, f, bw, (int64_t)N * K, 0.05f))) return rc;
+  // variant 90: the strict mode's fused three-product kernel on operands of logical depth K / 3 (K = 3 x depth, as the plain
+  // kernels see them), so that "variant 2, K" and "variant 90, K" time the same arithmetic
+  return time_launches([&] {
+    if (variant == 90) return launch_gemm_split3_w16(nullptr, bx, bw, db, dout, M, N, K / 3, N, epi);
+    return launch_gemm_bf16_variant(nullptr, bx, bw, db, dout, M, N, K, K, K, N, epi, variant, ws, ws ? ws_bytes : 0);
+  }, iters, avg_ms);
+}
+
+int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int m_live, int n_cu, char* buf, int buf_bytes) {
+  if (!buf || buf_bytes < 2 || M < 1 || N < 1 || K < 1 || n_cu < 1) return fail(PG_ERR_INVALID, "pg_dbg_gemm_plan: bad argument");
+  std::string text;
+  gemm_plan_text(M, N, K, epi, variant, have_ws != 0, m_live, n_cu, &text);
+  snprintf(buf, (size_t)buf_bytes, "%s", text.c_str());
+  return PG_OK;
+}
+
+int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_C, int R, int H, int head_dim, int has_pad, int has_bias,
+                          int row_step, int order_bh, int n_cu, char* buf, int buf_bytes) {
+  const int rc = dbg_precision("pg_dbg_attention_plan", precision, true);
+  if (rc) return rc;
+  if (!buf || buf_bytes < 2 || (kind != 0 && kind != 1) || n_seq_or_B < 1 || H < 1 || n_cu < 1 || (kind == 1 && (R < 1 || n_seq_or_B > 0x7fffffff)))
+    return fail(PG_ERR_INVALID, "pg_dbg_attention_plan: bad argument");
+  const bool strict = precision == PG_PREC_FP32;
+  std::string text;
+  if (kind == 0 && strict) attention_f32_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, row_step, &text);
+  else if (kind == 0) attention_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, row_step, n_cu, &text);
+  else if (strict) msa_row_f32_plan_text((int)n_seq_or_B, R, T_or_C, H, has_pad != 0, &text);
+  else msa_row_plan_text((int)n_seq_or_B, R, T_or_C, H, order_bh, &text);
+  snprintf(buf, (size_t)buf_bytes, "%s", text.c_str());
+  return PG_OK;
+}
+
+// round 6: the full-row out-projection + LayerNorm kernel (gemm_rowln.hip) against the two launches it replaces, on synthetic operands
+// of d_model = 768: ms[0] fused kernel, ms[1] its main loop alone, ms[2] four half-steps + its epilogue, ms[3] residual GEMM on
+// 256-column tiles (default dispatch), ms[4] LayerNorm kernel; max_diff = max |h fused - h unfused| over the 16-bit rows (0: bit-identical).
+int pg_dbg_rowln_bench(int device, int M, int K, int iters, double* ms, double* max_diff) {
+  if (!ms || M < 256 || K % 64 || K < 128 || iters < 1) return fail(PG_ERR_INVALID, "pg_dbg_rowln_bench: bad argument");
+  Dbg d;
+  int rc = d.open(device);
+  if (rc) return rc;
+  const int N = 768, Mp = round_up(M, kRowPad);
+  const size_t n_f = (size_t)std::max(Mp, N) * std::max(K, N);
+  const std::vector<float> hbuf = lcg_uniform(n_f + 5, 4242u);      // + 5: x0 below starts at value 5 and can be as long as f
+  const float* f = d.up(hbuf.data(), n_f);
+  bf16_t* ba = d.alloc<bf16_t>((size_t)Mp * K);
+  bf16_t* bw = d.alloc<bf16_t>((size_t)N * K);
+  const float* db = d.up(hbuf.data() + 31, (size_t)N * 3);      // bias | gamma | beta
+  const float* x0 = d.up(hbuf.data() + 5, (size_t)Mp * N);
+  float* x1 = d.alloc<float>((size_t)Mp * N);
+  float* x2 = d.alloc<float>((size_t)Mp * N);
+  bf16_t* h1 = d.alloc<bf16_t>((size_t)Mp * N);
+  bf16_t* h2 = d.alloc<bf16_t>((size_t)Mp * N);
+  if ((rc = d.check())) return rc;
+  if ((rc = to16(PG_PREC_BF16, f, ba, (int64_t)Mp * K))) return rc;
+  if ((rc = to16(PG_PREC_BF16, f + 977, bw, (int64_t)N * K, 0.05f))) return rc;
+  const float *gam = db + N, *bet = db + 2 * N;
+  // correctness first: one application of each path to the same x
+  PG_HIP(hipMemcpy(x1, x0, (size_t)Mp * N * 4, hipMemcpyDeviceToDevice));
+  PG_HIP(hipMemcpy(x2, x0, (size_t)Mp * N * 4, hipMemcpyDeviceToDevice));
+  auto fused = [&](int ablation) { return launch_gemm_rowln(nullptr, ba, bw, db, x1, gam, bet, h1, M, Mp, K, K, K, 1e-5f, 0, 0, ablation); };
+  auto resid = [&] { return launch_gemm_bf16(nullptr, ba, bw, db, x2, Mp, N, K, K, K, N, EPI_F32_RESID, nullptr, 0, M); };
+  auto norm = [&] { return launch_layernorm_bf16(nullptr, x2, gam, bet, h2, M, N, 1e-5f); };
+  if ((rc = fused(0)) || (rc = resid()) || (rc = norm())) return rc;
+  PG_HIP(hipDeviceSynchronize());
+  if (max_diff) {
+    std::vector<bf16_t> c1((size_t)M * N), c2((size_t)M * N);
+    std::vector<float> y1((size_t)M * N), y2((size_t)M * N);
+    if ((rc = d.down(c1.data(), h1, c1.size())) || (rc = d.down(c2.data(), h2, c2.size()))) return rc;
+    if ((rc = d.down(y1.data(), x1, y1.size())) || (rc = d.down(y2.data(), x2, y2.size()))) return rc;
+    double md = 0;
+    for (size_t i = 0; i < c1.size(); ++i) {
+      if (c1[i] != c2[i]) md = std::max(md, 1.0 + std::fabs((double)bf16_to_f32(c1[i]) - (double)bf16_to_f32(c2[i])));
+      if (memcmp(&y1[i], &y2[i], 4)) md = std::max(md, 2.0 + std::fabs((double)y1[i] - (double)y2[i]));
+    }
+    *max_diff = md;
+  }
+  for (int i = 0; i < 3; ++i)
+    if ((rc = time_launches([&] { return fused(i); }, iters, ms + i))) return rc;
+  if (const char* e = getenv("PGIBBS_ROWLN_BENCH_ABL")) {      // timing ablation of the epilogue in place of ms[2]
+    const int abl = atoi(e);
+    if ((rc = time_launches([&] { return fused(abl); }, iters, ms + 2))) return rc;
+  }
+  if ((rc = time_launches(resid, iters, ms + 3))) return rc;
+  return time_launches(norm, iters, ms + 4);
+}
+
+// round 5 ablation ("QKV projection fused with attention for ESM-1b"): the fused kernel that exists --
+// gemm_colattn_kernel<16> with one "column" per chain IS projection + attention of whole sequences of T = 256 tokens, one head per
+// 256 x 192 tile, the fusion's best case (16 query blocks on 16 waves, no 17th block, no padded rows) -- against the two launches it
+// would replace (QKV projection with 256 x 256 tiles, attention_kernel) on the same operands.  ms[0] fused, ms[1] projection,
+// ms[2] attention; max_diff = max |ctx fused - ctx unfused| (0: the paths are bit-identical).
+int pg_dbg_qkv_attention_bench(int device, int B, int T, int H, int iters, double* ms, double* max_diff) {
+  if (!ms || B < 1 || H < 1 || iters < 1 || !(T == 32 || T == 64 || T == 128 || T == 256))
+    return fail(PG_ERR_INVALID, "pg_dbg_qkv_attention_bench: T must be 32, 64, 128 or 256");
+  Dbg s;
+  int rc = s.open(device);
+  if (rc) return rc;
+  const int d = H * 64;
+  const int64_t M = (int64_t)B * T, Mp = round_up64(M, kRowPad);
+  const std::vector<float> h = lcg_uniform((size_t)std::max<int64_t>(Mp, 3 * d) * d, 777u);
+  const float* fx = s.up(h.data(), (size_t)Mp * d);      // x, W and the bias all start at the sequence's first value
+  const float* fw = s.up(h.data(), (size_t)3 * d * d);
+  const float* db = s.up(h.data(), (size_t)3 * d);
+  bf16_t* bx = s.alloc<bf16_t>((size_t)Mp * d);
+  bf16_t* bw = s.alloc<bf16_t>((size_t)3 * d * d);
+  bf16_t* bwh = s.alloc<bf16_t>((size_t)3 * d * d);
+  float* dbh = s.alloc<float>((size_t)3 * d);
+  bf16_t* qkv = s.alloc<bf16_t>((size_t)Mp * 3 * d);
+  bf16_t* c1 = s.alloc<bf16_t>((size_t)Mp * d);
+  bf16_t* c2 = s.alloc<bf16_t>((size_t)Mp * d);
+  if ((rc = s.check())) return rc;
+  if ((rc = to16(PG_PREC_BF16, fx, bx, Mp * d))) return rc;
+  if ((rc = to16(PG_PREC_BF16, fw, bw, (int64_t)3 * d * d, 0.03f))) return rc;
+  if ((rc = launch_headmajor_qkv(nullptr, bw, db, bwh, dbh, H, d))) return rc;
+  auto fused = [&] { return launch_gemm_colattn(nullptr, bx, bwh, dbh, c1, B, T, 1, H, d, d); };
+  auto proj = [&] { return launch_gemm_bf16(nullptr, bx, bw, db, qkv, (int)Mp, 3 * d, d, d, d, 3 * d, EPI_BF16); };
+  auto attn = [&] { return launch_attention_bf16(nullptr, qkv, c2, B, T, H, 3 * d, d, d, 2 * d); };
+  if ((rc = time_launches(fused, iters, ms + 0)) || (rc = time_launches(proj, iters, ms + 1)) || (rc = time_launches(attn, iters, ms + 2)))
+    return rc;
+  if (max_diff) {
+    std::vector<bf16_t> a((size_t)M * d), b((size_t)M * d);
+    if ((rc = s.down(a.data(), c1, a.size())) || (rc = s.down(b.data(), c2, b.size()))) return rc;
+    double worst = 0;
+    for (size_t i = 0; i < a.size(); ++i) worst = std::max(worst, (double)fabsf(bf16_to_f32(a[i]) - bf16_to_f32(b[i])));
+    *max_diff = worst;
+  }
+  return PG_OK;
+}
+
+int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float* beta, float* y, int M, int d, float eps) {
+  if (!x || !gamma || !beta || !y || M < 1 || d < 4) return fail(PG_ERR_INVALID, "pg_dbg_layernorm: bad argument");
+  Dbg s;
+  int rc = s.open(device);
+  if (rc) return rc;
+  const float* dx = s.up(x, (size_t)M * d);
+  const float* dg = s.up(gamma, (size_t)d);
+  const float* dbt = s.up(beta, (size_t)d);
+  float* dy = s.alloc<float>((size_t)M * d);
+  if ((rc = s.check())) return rc;
+  if ((rc = launch_layernorm_f32(nullptr, dx, dg, dbt, dy, M, d, eps))) return rc;
+  return s.down(y, dy, (size_t)M * d);
+}
+
+int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, int B, int T, int H) {
+  return pg_dbg_attention_hd(device, precision, qkv, ctx, B, T, H, 64, nullptr, -1);
+}
+
+/* pg_dbg_attention with the head dimension (64 or 32) and, optionally, the tokens of the keys: key_tok[B][T], keys whose token is
+ * pad_idx are masked as in a ragged batch (NULL: none) */
+int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+                        const int32_t* key_tok, int pad_idx) {
+  return pg_dbg_attention_kv(device, precision, qkv, ctx, B, T, H, head_dim, key_tok, pad_idx, nullptr, nullptr, nullptr, 0);
+}
+
+/* pg_dbg_attention_hd with ESM-1's bias key: bias_k / bias_v [H][head_dim] fp32 (both or neither), laid out as the engine lays them
+ * out -- [bias_k | bias_v], k of head h at h*HD, v at (H + h)*HD -- in the operand type of `precision` (fp32 for the strict
+ * kernels).  Everything is checked on the host before a device is looked for.  plan (may be NULL): the text the launch recorded */
+int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+                        const int32_t* key_tok, int pad_idx, const float* bias_k, const float* bias_v, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  int rc = dbg_precision("pg_dbg_attention_kv", precision, true);
+  if (rc) return rc;
+  if (!qkv || !ctx || B < 1 || T < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
+  if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32");
+  if (!bias_k != !bias_v) return fail(PG_ERR_INVALID, "pg_dbg_attention_kv: bias_k and bias_v come together or not at all");
+  const std::string head_err = attention_head_error(head_dim, bias_k != nullptr);      // the plans' own refusal of a bias key at head 32
+  if (!head_err.empty()) return fail(PG_ERR_INVALID, head_err);
+  if ((double)B * T * 3 * H * head_dim > 2147483647.0) return fail(PG_ERR_INVALID, "pg_dbg_attention: more than 2^31 - 1 qkv values");
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const int d = H * head_dim;
+  const bool strict = precision == PG_PREC_FP32;
+  float* bias32 = bias_k ? s.alloc<float>((size_t)2 * d) : nullptr;      // [bias_k | bias_v], d fp32 each
+  if (bias_k) s.put(bias32, bias_k, (size_t)d), s.put(bias32 + d, bias_v, (size_t)d);
+  bf16_t* bias16 = bias_k && !strict ? s.alloc<bf16_t>((size_t)2 * d) : nullptr;
+  return dbg_attention_run(s, precision, strict, qkv, ctx, (int64_t)B * T, d, key_tok, plan, plan_bytes,
+                           [&](const float* dq, const bf16_t* bq, bf16_t* out, const int32_t* dtok) {
+    const SeqLayout chain = {1, T, 0, 1};
+    if (strict) return launch_attention_f32(nullptr, dq, out, d, B, T, H, 3 * d, 3 * d, d, 2 * d, chain, dtok, pad_idx, bias32, head_dim);
+    const int rc16 = bias_k ? to16(precision, bias32, bias16, 2 * d) : PG_OK;
+    return rc16 ? rc16 : OPS(launch_attention_bf16, nullptr, bq, out, B, T, H, 3 * d, d, d, 2 * d, dtok, pad_idx, bias16, head_dim);
+  });
+}
+
+/* LayerNorm as the engine's GEMMs read it: the operand rows launch_layernorm_bf16 writes in `precision`, widened to fp32 --
+ * bf16 or fp16 rows, or (PG_PREC_FP32) the strict mode's split rows [lo | hi | hi] returned as hi + lo, the two hi copies checked */
+int pg_dbg_layernorm_operand(int device, int precision, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
+                             float eps) {
+  int rc = dbg_precision("pg_dbg_layernorm_operand", precision, true);
+  if (rc) return rc;
+  if (!x || !gamma || !beta || !y || M < 1 || d < 32 || d % 32) return fail(PG_ERR_INVALID, "pg_dbg_layernorm_operand: bad argument");
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const bool split = precision == PG_PREC_FP32;
+  const float* dx = s.up(x, (size_t)M * d);
+  const float* dg = s.up(gamma, (size_t)d);
+  const float* dbt = s.up(beta, (size_t)d);
+  float* dy = s.alloc<float>((size_t)M * d);
+  bf16_t* h = s.alloc<bf16_t>((size_t)M * d * (split ? 3 : 1));
+  if ((rc = s.check())) return rc;
+  if ((rc = OPS(launch_layernorm_bf16, nullptr, dx, dg, dbt, h, M, d, eps, split, 0, 0, true))) return rc;
+  return split ? split3_rows_to_host(h, y, M, d) : down16(s, precision, h, dy, y, (int64_t)M * d);
+}
+
+/* ESM-2's rotary embedding on a host fp32 buffer qkv[B*T][3*H*64]: the q and k thirds rotated in place (row r at position r % T),
+ * v left alone.  16-bit modes: through a device buffer of that type, the result widened back */
+int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
+  return pg_dbg_rope_hd(device, precision, qkv, B, T, H, 64);
+}
+
+/* pg_dbg_rope with the head dimension: 64 (H <= 40) or 32 (H <= 32) */
+int pg_dbg_rope_hd(int device, int precision, float* qkv, int B, int T, int H, int head_dim) {
+  int rc = dbg_precision("pg_dbg_rope_hd", precision, true);
+  if (rc) return rc;
+  if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32");
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 64 ? 40 : 32)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const int d = H * head_dim;
+  const int64_t M = (int64_t)B * T, n = M * 3 * d;
+  const std::vector<float> tab = rope_table(T, head_dim);
+  float* dq = s.up(qkv, (size_t)n);
+  const float* dtab = s.up(tab.data(), tab.size());
+  bf16_t* bq = precision == PG_PREC_FP32 ? nullptr : s.alloc<bf16_t>((size_t)n);
+  if ((rc = s.check())) return rc;
+  if (precision == PG_PREC_FP32) {
+    if ((rc = launch_rope(nullptr, dq, true, dtab, T, M, T, H, 3 * d, head_dim))) return rc;
+    return s.down(qkv, dq, (size_t)n);
+  }
+  if ((rc = to16(precision, dq, bq, n))) return rc;
+  if ((rc = OPS(launch_rope, nullptr, bq, false, dtab, T, M, T, H, 3 * d, head_dim))) return rc;
+  return down16(s, precision, bq, dq, qkv, n);
+}
+
+/* MSA attention blocks on fp32 host buffers qkv[B][R][C][3*H*64] -> ctx[B][R][C][H*64]; which: 0 = tied row attention
+ * (scores scaled by `scale`), 1 = column attention (q already scaled); 2 / 3 = the same two in the strict precision mode */
+int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale) {
+  return pg_dbg_msa_attention_tok(device, which, qkv, ctx, B, R, C, H, scale, nullptr, -1, nullptr, 0);
+}
+
+/* pg_dbg_msa_attention with the tokens tok[B][R][C] of a batch that holds <pad> (NULL: none, pg_dbg_msa_attention itself).  Column
+ * attention (which 1, 3, 5) hands them to its launcher.  Tied row attention with tokens takes the engine's route for a ragged batch:
+ * which 0 widens the bf16 q, k, v to fp32 and runs launch_msa_row_attention_f32 with 16-bit context rows, which 2 is the strict
+ * kernel, which 4 (fp16) is refused as the engine refuses it.  Everything is checked on the host before a device is looked for.
+ * plan (may be NULL): the text the launches recorded */
+int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale,
+                             const int32_t* tok, int pad_idx, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  if (!qkv || !ctx || B < 1 || R < 1 || C < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: bad argument");
+  if (which < 0 || which > 5) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: which must be 0 ... 5");
+  if ((double)B * R * C * 3 * H * 64 > 2147483647.0) return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: more than 2^31 - 1 qkv values");
+  if (tok && which == 4)
+    return fail(PG_ERR_UNSUPPORTED, "fp16 precision mode: alignments wider than 576 columns take the split-bf16 row attention, "
+                                    "which exists for bf16 operands only -- use precision bf16 or fp32");
+  if ((which == 2 || (which == 0 && tok)) && (double)B * H * C * msa_row_scores_ld(C) > 1073741823.0)
+    return fail(PG_ERR_INVALID, "pg_dbg_msa_attention: the fp32 score maps of this shape exceed 4 GiB");
+  const int precision = (which == 4 || which == 5) ? PG_PREC_F16 : PG_PREC_BF16;      // 4 / 5: which 0 / 1 with fp16 operands
+  if (which == 4 || which == 5) which -= 4;
+  Dbg s;
+  int rc = s.open(device);
+  if (rc) return rc;
+  const int d = H * 64;
+  const int64_t M = (int64_t)B * R * C;
+  const bool strict = which == 2 || which == 3;      // strict precision mode kernels: fp32 in, [lo | hi | hi] operand rows out
+  const bool ragged = which == 0 && tok;
+  // a ragged batch, as Engine::msa_trunk runs it: the 16-bit q, k, v widened to fp32, fp32 scores through a scratch buffer
+  float* wide = ragged ? s.alloc<float>((size_t)M * 3 * d) : nullptr;
+  float* sc = which == 2 || ragged ? s.alloc<float>((size_t)B * H * C * msa_row_scores_ld(C)) : nullptr;
+  // scratch for the split-R mode (taken when B*H*ceil(C/64) < 384 and R >= 8), so the tests exercise both modes
+  const size_t pbytes = (size_t)B * H * 16 * C * 576 * 4 + (size_t)B * H * (C / 16 + 9) * 18 * 1024;
+  float* part = which == 0 && !tok && pbytes <= ((size_t)1 << 30) ? (float*)s.alloc<char>(pbytes) : nullptr;
+  return dbg_attention_run(s, precision, strict, qkv, ctx, M, d, tok, plan, plan_bytes,
+                           [&](const float* dq, const bf16_t* bq, bf16_t* out, const int32_t* dtok) {
+    const SeqLayout col = {C, R * C, 1, C};
+    if (which == 2) return launch_msa_row_attention_f32(nullptr, dq, sc, out, d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, scale, dtok, pad_idx);
+    if (which == 3) return launch_attention_f32(nullptr, dq, out, d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, col, dtok, pad_idx);
+    if (ragged) {
+      const int rcw = launch_bf16_to_f32(nullptr, bq, wide, M * 3 * d);
+      return rcw ? rcw : launch_msa_row_attention_f32(nullptr, wide, sc, out, 0, B, R, C, H, 3 * d, d, d, 2 * d, scale, dtok, pad_idx);
+    }
+    if (which == 0) return OPS(launch_msa_row_attention_bf16, nullptr, bq, out, B, R, C, H, 3 * d, d, d, 2 * d, scale, part, part ? pbytes : 0, 0);
+    return OPS(launch_attention_seq_bf16, nullptr, bq, out, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, dtok, pad_idx);
+  });
+}
+
+// ---- the row kernels of elementwise.hip ---------------------------------------------------------------------------------------------
+// Every entry below checks its arguments on the host first -- shapes, then every token, position row, row_map entry and gathered
+// row the kernel would read against the sizes the caller states -- and only then looks for a device: a wrong array is
+// PG_ERR_INVALID with a message, never a GPU fault, and the refusals can be tested without a GPU.
+extern "C++" {
+namespace {
+int dbg_row_width(const char* who, int d) {
+  if (d < 4 || d % 4 || d > 2560) return      // row_d_ok of elementwise.hip
+    fail(PG_ERR_INVALID, std::string(who) + ": d must be a multiple of 4 and <= 2560");
+  return PG_OK;
+}
+// the token row a gather reads for selected row r (what gather_ln_bf16_kernel / gather_rows_kernel compute), -1 = none (zeros);
+// -2 = outside the source (error set)
+int64_t dbg_gather_src(const char* who, int64_t r, int32_t pos, bool zero_fill, const int32_t* row_map, int64_t n_map, int P, int width,
+                       int64_t src_rows) {
+  if (pos < 0 || (pos & 0x3fffffff) >= width) {
+    if (zero_fill) return -1;
+    pos = 0;
+  }
+  pos &= 0x3fffffff;
+  const int64_t s = r / P;
+  if (row_map && s >= n_map) { fail(PG_ERR_INVALID, std::string(who) + ": row_map is shorter than the selected rows need"); return -2; }
+  const int64_t row = (row_map ? (int64_t)row_map[s] : s) * width + pos;
+  if (row < 0 || row >= src_rows) {
+    fail(PG_ERR_INVALID, std::string(who) + ": selected row " + std::to_string(r) + " reads source row " + std::to_string(row) + " of " + std::to_string(src_rows));
+    return -2;
+  }
+  return row;
+}
+const char* const kCopyFailed = "hipMalloc / copy failed";
+}  // namespace
+}  // extern "C++"
+
+int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
+                 int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
+                 const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2) {
+  int rc = dbg_precision("pg_dbg_embed", precision, false);
+  if (rc) return rc;
+  if (!tokens || !embed || !x || n_seq < 1 || T < 1 || V < 1 || (pos && pos_rows < 1) || rows_per_msa < 0 || (rows_per_msa > 0 && !msa_pos) ||
+      !gamma != !beta || !gamma2 != !beta2 || !gamma2 != !h2)
+    return fail(PG_ERR_INVALID, "pg_dbg_embed: bad argument");
+  if ((rc = dbg_row_width("pg_dbg_embed", d))) return rc;
+  const int64_t n_tok = (int64_t)n_seq * T;
+  for (int64_t sq = 0; sq < n_seq; ++sq) {
+    int n_before = 0;
+    for (int t = 0; t < T; ++t) {
+      const int32_t tok = tokens[sq * T + t];
+      if (tok < 0 || tok >= V)
+        return fail(PG_ERR_INVALID, "pg_dbg_embed: token " + std::to_string(tok) + " is outside the embedding table of " + std::to_string(V) + " rows");
+      n_before += tok != pad_idx;
+      const int p = tok == pad_idx ? pad_idx : n_before + pad_idx;      // embed_ln_kernel's position row
+      if (pos && (p < 0 || p >= pos_rows))
+        return fail(PG_ERR_INVALID, "pg_dbg_embed: position row " + std::to_string(p) + " is outside the position table of " + std::to_string(pos_rows) + " rows");
+    }
+  }
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const int32_t* dtok = s.up(tokens, (size_t)n_tok);
+  const float* de = s.up(embed, (size_t)V * d);
+  const float* dp = s.up(pos, (size_t)pos_rows * d);
+  const float* dm = rows_per_msa > 0 ? s.up(msa_pos, (size_t)rows_per_msa * d) : nullptr;
+  const float* dg = s.up(gamma, (size_t)d);
+  const float* db = s.up(beta, (size_t)d);
+  const float* dg2 = s.up(gamma2, (size_t)d);
+  const float* db2 = s.up(beta2, (size_t)d);
+  float* dx = s.alloc<float>((size_t)n_tok * d);
+  bf16_t* dh = h2 ? s.alloc<bf16_t>((size_t)n_tok * d) : nullptr;
+  if ((rc = s.check(kCopyFailed))) return rc;
+  if ((rc = OPS(launch_embed_ln, nullptr, dtok, de, dp, dm, dg, db, dx, n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, dg2,
+                db2, dh, embed_scale)))
+    return rc;
+  if ((rc = s.down(x, dx, (size_t)n_tok * d))) return rc;
+  return h2 ? s.down(h2, dh, (size_t)n_tok * d) : PG_OK;
+}
+
+int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                          int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel) {
+  int rc = dbg_precision("pg_dbg_layernorm_rows", precision, false);
+  if (rc) return rc;
+  if (!x || !gamma || !beta || !h_inout || M < 1 || h_rows < M || form < 0 || form > 2 || colmajor_R < 0 || (colmajor_R > 0 && colmajor_C < 1))
+    return fail(PG_ERR_INVALID, "pg_dbg_layernorm_rows: bad argument");
+  if (form && (precision != PG_PREC_BF16 || d % 32))
+    return fail(PG_ERR_INVALID, "pg_dbg_layernorm_rows: split rows are bf16 pairs in groups of 32 columns");
+  if ((rc = OPS(layernorm_bf16_check, M, d, form != 0, colmajor_R, colmajor_C))) return rc;
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const size_t h_n = (size_t)h_rows * d * (form ? 3 : 1);
+  const float* dx = s.up(x, (size_t)M * d);
+  const float* dg = s.up(gamma, (size_t)d);
+  const float* db = s.up(beta, (size_t)d);
+  bf16_t* dh = s.up(h_inout, h_n);      // the caller's pattern: what the kernel leaves unwritten keeps it
+  if ((rc = s.check(kCopyFailed))) return rc;
+  unsigned stride_grid = 0;
+  if (kernel) *kernel = OPS(layernorm_bf16_choice, M, d, colmajor_R, &stride_grid);
+  if ((rc = OPS(launch_layernorm_bf16, nullptr, dx, dg, db, dh, M, d, eps, form != 0, colmajor_R, colmajor_C, form != 2))) return rc;
+  return s.down(h_inout, dh, h_n);
+}
+
+int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                     int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                     float eps, int split) {
+  int rc = dbg_precision("pg_dbg_gather_ln", precision, false);
+  if (rc) return rc;
+  if (!x || !gamma || !beta || !h_inout || x_rows < 1 || n_sel < 1 || h_rows < n_sel || P < 1 || width < 1 || (row_map && n_map < 1) ||
+      split < 0 || split > 1)
+    return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: bad argument");
+  if ((rc = dbg_row_width("pg_dbg_gather_ln", d))) return rc;
+  if (split && (precision != PG_PREC_BF16 || d % 32))
+    return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: split rows are bf16 pairs in groups of 32 columns");
+  if (!idx) {      // identity: selected row r = token row r
+    if (n_sel > x_rows) return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: more selected rows than source rows");
+  } else {
+    for (int64_t r = 0; r < n_sel; ++r)
+      if (dbg_gather_src("pg_dbg_gather_ln", r, idx[r], true, row_map, n_map, P, width, x_rows) == -2) return PG_ERR_INVALID;
+  }
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const size_t h_n = (size_t)h_rows * d * (split ? 3 : 1);
+  const float* dx = s.up(x, (size_t)x_rows * d);
+  const int32_t* di = s.up(idx, (size_t)n_sel);
+  const int32_t* dm = s.up(row_map, (size_t)n_map);
+  const float* dg = s.up(gamma, (size_t)d);
+  const float* db = s.up(beta, (size_t)d);
+  bf16_t* dh = s.up(h_inout, h_n);
+  if ((rc = s.check(kCopyFailed))) return rc;
+  if ((rc = OPS(launch_gather_ln_bf16, nullptr, dx, di, dm, P, width, dg, db, dh, n_sel, d, eps, split != 0))) return rc;
+  return s.down(h_inout, dh, h_n);
+}
+
+int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
+                       int iter, const int32_t* row_map, int64_t n_map, int P, int width, int64_t n_sel, int row_bytes) {
+  if (!src || !dst_inout || !idx || src_rows < 1 || n_sel < 1 || dst_rows < n_sel || P < 1 || width < 1 || (row_map && n_map < 1) ||
+      n_iters < 0 || (n_iters > 0 && (iter < 0 || iter >= n_iters)) || row_bytes < 16)
+    return fail(PG_ERR_INVALID, "pg_dbg_gather_rows: bad argument");
+  if (row_bytes % 16) return fail(PG_ERR_INVALID, "pg_dbg_gather_rows: rows must be multiples of 16 bytes");
+  const int32_t* now = idx + (n_iters > 0 ? (size_t)iter * n_sel : 0);      // the table row the kernel reads through d_iter
+  for (int64_t r = 0; r < n_sel; ++r)
+    if (dbg_gather_src("pg_dbg_gather_rows", r, now[r], false, row_map, n_map, P, width, src_rows) == -2) return PG_ERR_INVALID;
+  Dbg s;
+  int rc = s.open(device);
+  if (rc) return rc;
+  const char* ds = s.up((const char*)src, (size_t)src_rows * row_bytes);
+  char* dd = s.up((const char*)dst_inout, (size_t)dst_rows * row_bytes);
+  const int32_t* di = s.up(idx, (size_t)(n_iters > 0 ? n_iters : 1) * n_sel);
+  const int32_t* dm = s.up(row_map, (size_t)n_map);
+  const int32_t it32 = iter;
+  const int32_t* dit = n_iters > 0 ? s.up(&it32, 1) : nullptr;
+  if ((rc = s.check(kCopyFailed))) return rc;
+  if ((rc = launch_gather_rows(nullptr, ds, dd, di, dm, P, width, n_sel, row_bytes, dit))) return rc;
+  return s.down((char*)dst_inout, dd, (size_t)dst_rows * row_bytes);
+}
+
+int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                   float* logits, int64_t n, int d, int V, float eps, int* small_kernel) {
+  if (!g || !embed || !out_bias || !logits || n < 1 || !gamma != !beta) return fail(PG_ERR_INVALID, "pg_dbg_lm_tail: bad argument");
+  if (V < 1 || V > 64) return fail(PG_ERR_INVALID, "pg_dbg_lm_tail: vocab must be in 1..64");
+  int rc = dbg_row_width("pg_dbg_lm_tail", d);
+  if (rc) return rc;
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const float* dg = s.up(g, (size_t)n * d);
+  const float* dga = s.up(gamma, (size_t)d);
+  const float* dbe = s.up(beta, (size_t)d);
+  const float* de = s.up(embed, (size_t)V * d);
+  const float* dob = s.up(out_bias, (size_t)V);
+  float* dl = s.up(logits, (size_t)n * V);      // the caller's pattern
+  if ((rc = s.check(kCopyFailed))) return rc;
+  if (small_kernel) *small_kernel = lm_tail_small(n) ? 1 : 0;
+  if ((rc = launch_lm_tail(nullptr, dg, dga, dbe, de, dob, dl, n, d, V, eps))) return rc;
+  return s.down(logits, dl, (size_t)n * V);
+}
+
+}  // extern "C"
