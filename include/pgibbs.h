@@ -403,6 +403,13 @@ int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, 
  * `iter` of it through a device-side iteration counter.  dst_inout holds dst_rows >= n_sel rows */
 int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
                        int iter, const int32_t* row_map, int64_t n_map, int P, int width, int64_t n_sel, int row_bytes);
+/* launch_split3_bf16 on x[rows][K] fp32 (K a multiple of 32): the strict mode's split operand rows of scale * x, 3 K bf16 words per row
+ * (csrc/split_operand.h), into h_inout[h_rows >= rows][3 K].  form = weight (1) + through GELU (2): 0 an activation row [lo | hi | hi]
+ * per 32 columns, 1 a weight row [hi | lo | hi], 2 an activation row of erf-GELU(x), which takes scale 1 and also returns
+ * gelu_out[rows][K] = launch_gelu_f32 of the same x; 3 (GELU on a weight) and every other value are refused.  All refusals are
+ * PG_ERR_INVALID on the host, before a device is looked for */
+int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_rows, int rows, int K, float scale, int form,
+                      float* gelu_out);
 /* launch_lm_tail: logits[n][V] = LayerNorm(g[n][d]; gamma, beta) . embed[V][d]^T + out_bias (gamma == beta == NULL: no LayerNorm,
  * ESM-1); V <= 64.  *small_kernel (may be NULL): 1 = the workgroup-per-row kernel ran (n <= PGIBBS_LM_TAIL_SMALL, default 1024) */
 int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,

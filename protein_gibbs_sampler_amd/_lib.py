@@ -133,6 +133,7 @@ SIGNATURES = [
                                  c_int64, c_int64, c_int, c_float, c_int]),
     ("pg_dbg_gather_rows", c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int,
                                    c_int64, c_int]),
+    ("pg_dbg_split_rows", c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p]),
     ("pg_dbg_lm_tail", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
                                POINTER(c_int)]),
 ]

@@ -80,16 +80,16 @@ int down16(const Dbg& d, int precision, const bf16_t* rows, float* wide, float* 
   const int rc = OPS(launch_bf16_to_f32, nullptr, rows, wide, n);
   return rc ? rc : d.down(host, wide, (size_t)n);
 }
-// device rows in the strict mode's split operand layout (3 d bf16: per group of 32 columns [lo | hi | hi]) -> host fp32 rows
-// hi + lo; also checks that the two hi copies agree
+// device rows in the strict mode's split operand layout (3 d bf16: split_operand.h, activation order) -> host fp32 rows hi + lo;
+// also checks that the two hi copies agree
 int split3_rows_to_host(const bf16_t* c3, float* dst, int64_t M, int d) {
   PG_HIP(hipDeviceSynchronize());
   std::vector<bf16_t> h((size_t)M * 3 * d);
   PG_HIP(hipMemcpy(h.data(), c3, h.size() * 2, hipMemcpyDeviceToHost));
   for (int64_t r = 0; r < M; ++r)
     for (int c = 0; c < d; ++c) {
-      const size_t g = (size_t)r * 3 * d + (size_t)(c >> 5) * 96 + (c & 31);
-      const bf16_t lo = h[g], hi = h[g + 32], hi2 = h[g + 64];
+      const size_t g = (size_t)r * 3 * d + split_lo_offset(c);
+      const bf16_t lo = h[g], hi = h[g + kSplitHi], hi2 = h[g + kSplitDup];
       if (hi != hi2) return fail(PG_ERR_HIP, "split operand row: the two hi copies differ");
       dst[(size_t)r * d + c] = bf16_to_f32(hi) + bf16_to_f32(lo);
     }
@@ -659,6 +659,27 @@ int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_
   if ((rc = s.check(kCopyFailed))) return rc;
   if ((rc = launch_gather_rows(nullptr, ds, dd, di, dm, P, width, n_sel, row_bytes, dit))) return rc;
   return s.down((char*)dst_inout, dd, (size_t)dst_rows * row_bytes);
+}
+
+int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_rows, int rows, int K, float scale, int form, float* gelu_out) {
+  if (!x || !h_inout || rows < 1 || h_rows < rows || K < 1) return fail(PG_ERR_INVALID, "pg_dbg_split_rows: bad argument");
+  if (K % kSplitCols) return fail(PG_ERR_INVALID, "pg_dbg_split_rows: K must be a multiple of 32");
+  if (form < 0 || form > 3) return fail(PG_ERR_INVALID, "pg_dbg_split_rows: form is weight (1) + through GELU (2)");
+  if (form == 3) return fail(PG_ERR_INVALID, "pg_dbg_split_rows: GELU on a weight operand");
+  if (form == 2 && scale != 1.0f) return fail(PG_ERR_INVALID, "pg_dbg_split_rows: the GELU form takes scale 1");
+  if (form == 2 && !gelu_out) return fail(PG_ERR_INVALID, "pg_dbg_split_rows: the GELU form returns gelu_out");
+  Dbg s;
+  int rc = s.open(device);
+  if (rc) return rc;
+  const size_t h_n = (size_t)h_rows * 3 * K;
+  float* dx = s.up(x, (size_t)rows * K);
+  bf16_t* dh = s.up(h_inout, h_n);      // the caller's pattern
+  if ((rc = s.check(kCopyFailed))) return rc;
+  if ((rc = launch_split3_bf16(nullptr, dx, dh, rows, K, scale, form == 2, form == 1))) return rc;
+  if ((rc = s.down(h_inout, dh, h_n))) return rc;
+  if (form != 2) return PG_OK;
+  if ((rc = launch_gelu_f32(nullptr, dx, (int64_t)rows * K))) return rc;
+  return s.down(gelu_out, dx, (size_t)rows * K);
 }
 
 int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,

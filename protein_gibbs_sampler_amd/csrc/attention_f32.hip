@@ -13,39 +13,22 @@
 #include <cstdlib>
 
 #include "attn_frag.h"
+#include "split_operand.h"
 
 PG_OPS_BEGIN
 
 // One thread's 64 context values of head h -> bf16 into the token's context row.  split_d != 0: the row is the strict mode's
-// split operand (3 * |split_d| values, groups of 32 columns [lo | hi | hi]; elementwise.hip store_row_bf16); split_d < 0: without
-// the duplicate hi block -- the out-projection that reads the rows is the fused three-product kernel (gemm_split3_fused).
+// split operand (3 * |split_d| values: split_operand.h); split_d < 0: without the duplicate hi block -- the out-projection that
+// reads the rows is the fused three-product kernel (gemm_split3_fused).
 __device__ __forceinline__ void store_ctx64(const float (&o)[64], float inv, bf16_t* row, int h, int split_d) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const float a = o[4 * i] * inv, b = o[4 * i + 1] * inv, c = o[4 * i + 2] * inv, d = o[4 * i + 3] * inv;
-    uint2 p, r;
-    p.x = pack_op2(a, b);
-    p.y = pack_op2(c, d);
-    if (!split_d) {
-      ((uint2*)(row + h * 64))[i] = p;
-    } else {
-      r.x = pack_op2(a - op16_to_f32((bf16_t)(p.x & 0xffff)), b - op16_to_f32((bf16_t)(p.x >> 16)));
-      r.y = pack_op2(c - op16_to_f32((bf16_t)(p.y & 0xffff)), d - op16_to_f32((bf16_t)(p.y >> 16)));
-      bf16_t* g = row + (2 * h + (i >> 3)) * 96 + (i & 7) * 4;       // columns h*64 + 4i .. +3
-      *(uint2*)g = r;
-      *(uint2*)(g + 32) = p;
-      if (split_d > 0) *(uint2*)(g + 64) = p;
-    }
+    uint2 hi, lo;
+    split4(a, b, c, d, hi, lo);
+    if (!split_d) ((uint2*)(row + h * 64))[i] = hi;
+    else split_store4(row + split_lo_offset(h * 64 + 4 * i), hi, lo, split_d > 0);
   }
-}
-
-// 8 fp32 -> 8 bf16 hi (round to nearest even) + 8 bf16 lo = bf16(v - hi)
-__device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& hi, uint4& lo) {
-  hi.x = pack_op2(a.x, a.y); hi.y = pack_op2(a.z, a.w); hi.z = pack_op2(b.x, b.y); hi.w = pack_op2(b.z, b.w);
-  lo.x = pack_op2(a.x - __uint_as_float(hi.x << 16), a.y - __uint_as_float(hi.x & 0xffff0000u));
-  lo.y = pack_op2(a.z - __uint_as_float(hi.y << 16), a.w - __uint_as_float(hi.y & 0xffff0000u));
-  lo.z = pack_op2(b.x - __uint_as_float(hi.z << 16), b.y - __uint_as_float(hi.z & 0xffff0000u));
-  lo.w = pack_op2(b.z - __uint_as_float(hi.w << 16), b.w - __uint_as_float(hi.w & 0xffff0000u));
 }
 
 // Building blocks shared by the three split-bf16 MFMA kernels (full attention, tied-row scores, tied-row apply).
@@ -181,24 +164,28 @@ struct SplitAttn {
   }
 
   // row = the query's context row; the lane holds columns h*HD + db*16 + fq*4 .. +3.  bf16, or the strict mode's split operand
-  // row (groups of 32 columns [lo | hi | hi]: a head of 64 is two groups, a head of 32 one)
+  // row (split_operand.h: a head of 64 is two groups, a head of 32 one)
   static __device__ __forceinline__ void store_ctx(const f32x4 (&o)[NDB], float l, bf16_t* row, int h, int fq, int split_d) {
     const float inv = l > 0.f ? 1.0f / l : 0.f;     // every key masked (an all-<pad> sequence): zero context, not NaN
 #pragma unroll
     for (int db = 0; db < NDB; ++db) {
       const float a = o[db][0] * inv, b = o[db][1] * inv, c = o[db][2] * inv, d = o[db][3] * inv;
+      // The split and the stores of split_operand.h, spelled out from its pieces (this file is built for bf16 operands only, so
+      // pack_op2 is the header's pack): with split4 + split_store4 here every form of attention_split_kernel and both
+      // msa_row_apply_split_kernel forms changed register allocation -- <4,1,bias,pad,64> 126 -> 128 VGPRs, <8,5,bias,pad,64>
+      // 253 -> 254 -- and <10,5,bias,pad,64> went from 64 to 68 bytes of scratch; as written they compile to the same code as before
       uint2 p, r;
       p.x = pack_op2(a, b);
       p.y = pack_op2(c, d);
       if (!split_d) {
         *(uint2*)(row + h * HD + db * 16 + fq * 4) = p;
       } else {
-        r.x = pack_op2(a - __uint_as_float(p.x << 16), b - __uint_as_float(p.x & 0xffff0000u));
-        r.y = pack_op2(c - __uint_as_float(p.y << 16), d - __uint_as_float(p.y & 0xffff0000u));
-        bf16_t* g = row + (NKK * h + (db >> 1)) * 96 + (db & 1) * 16 + fq * 4;
+        r.x = pack_op2(split_rest(a, p.x << 16), split_rest(b, p.x & 0xffff0000u));
+        r.y = pack_op2(split_rest(c, p.y << 16), split_rest(d, p.y & 0xffff0000u));
+        bf16_t* g = row + (NKK * h + (db >> 1)) * kSplitVals + (db & 1) * 16 + fq * 4;
         *(uint2*)g = r;
-        *(uint2*)(g + 32) = p;
-        if (split_d > 0) *(uint2*)(g + 64) = p;
+        *(uint2*)(g + kSplitHi) = p;
+        if (split_d > 0) *(uint2*)(g + kSplitDup) = p;
       }
     }
   }

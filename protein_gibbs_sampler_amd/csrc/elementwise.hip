@@ -12,6 +12,8 @@
 // nothing goes through LDS.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 #include "ln_row.h"
 
@@ -21,6 +23,17 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// the row of this wave: 256 threads = four rows per workgroup (rows_grid)
+__device__ __forceinline__ int64_t wave_row() { return (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); }
+// the lane's chunks lane, lane + 64, ... of a row of nch4 float4 that starts at src
+template <int NCH>
+__device__ __forceinline__ void load_row(float4 (&v)[NCH], const float* src, int nch4, int lane) {
+  const float4* x4 = (const float4*)src;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
 }
 
 // ---- embedding -------------------------------------------------------------------------------
@@ -37,7 +50,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
                                                       const float* __restrict__ gamma2, const float* __restrict__ beta2,
                                                       bf16_t* __restrict__ h2, float embed_scale) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = wave_row();
   if (row >= n_tok) return;
   const int64_t seq = row / T;
   const int t = (int)(row - seq * T);
@@ -97,14 +110,11 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const float* __rest
                                                             const float* __restrict__ beta, bf16_t* __restrict__ h,
                                                             int split3, int64_t M, int d, float eps) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = wave_row();
   if (row >= M) return;
   const int nch4 = d >> 2;
-  const float4* x4 = (const float4*)(x + (size_t)row * d);
   float4 v[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-    if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
+  load_row(v, x + (size_t)row * d, nch4, lane);
   ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   store_row_bf16(h + (size_t)row * d * (split3 ? 3 : 1), v, nch4, lane, split3, split3 != 2);       // split3 == 2: no duplicate hi block
 }
@@ -123,23 +133,13 @@ __global__ __launch_bounds__(256) void layernorm_bf16_stride_kernel(const float*
   constexpr int d = D, nch4 = D >> 2;
   const int lane = threadIdx.x & 63;
   const int64_t stride = (int64_t)gridDim.x * 4;
-  int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int64_t row = wave_row();
   if (row >= M) return;
   float4 v[kMaxCh], vn[kMaxCh];
-  {
-    const float4* x4 = (const float4*)(x + (size_t)row * d);
-#pragma unroll
-    for (int i = 0; i < kMaxCh; ++i)
-      if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
-  }
+  load_row(v, x + (size_t)row * d, nch4, lane);
   for (;;) {
     const int64_t next = row + stride;
-    if (next < M) {                                            // wave-uniform
-      const float4* x4 = (const float4*)(x + (size_t)next * d);
-#pragma unroll
-      for (int i = 0; i < kMaxCh; ++i)
-        if (lane + 64 * i < nch4) vn[i] = x4[lane + 64 * i];
-    }
+    if (next < M) load_row(vn, x + (size_t)next * d, nch4, lane);      // wave-uniform
     ln_inplace(v, nch4, lane, d, eps, gamma, beta);
     store_row_bf16(h + (size_t)row * d * (split3 ? 3 : 1), v, nch4, lane, split3, split3 != 2);
     if (next >= M) break;
@@ -156,14 +156,11 @@ __global__ __launch_bounds__(256) void layernorm_bf16_colmajor_kernel(const floa
                                                                      const float* __restrict__ beta, bf16_t* __restrict__ h,
                                                                      int64_t M, int d, float eps, int R, int C) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = wave_row();
   if (row >= M) return;
   const int nch4 = d >> 2;
-  const float4* x4 = (const float4*)(x + (size_t)row * d);
   float4 v[kMaxCh];
-#pragma unroll
-  for (int i = 0; i < kMaxCh; ++i)
-    if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
+  load_row(v, x + (size_t)row * d, nch4, lane);
   ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   const int64_t br = row / C;
   const int c = (int)(row - br * C);
@@ -178,14 +175,11 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
                                                            const float* __restrict__ beta, float* __restrict__ y,
                                                            int64_t M, int d, float eps) {
   const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t row = wave_row();
   if (row >= M) return;
   const int nch4 = d >> 2;
-  const float4* x4 = (const float4*)(x + (size_t)row * d);
   float4 v[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-    if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
+  load_row(v, x + (size_t)row * d, nch4, lane);
   ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   float4* o = (float4*)(y + (size_t)row * d);
 #pragma unroll
@@ -202,7 +196,7 @@ __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __rest
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             bf16_t* __restrict__ h, int split3, int64_t n_sel, int d, float eps) {
   const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t r = wave_row();
   if (r >= n_sel) return;
   const int nch4 = d >> 2;
   int pos = idx ? idx[r] : 0;
@@ -219,10 +213,7 @@ __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __rest
     } else {
       src = r;
     }
-    const float4* x4 = (const float4*)(x + (size_t)src * d);
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
+    load_row(v, x + (size_t)src * d, nch4, lane);
     ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   }
   store_row_bf16(h + (size_t)r * d * (split3 ? 3 : 1), v, nch4, lane, split3);
@@ -234,7 +225,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restric
                                                          const int32_t* __restrict__ idx, const int32_t* __restrict__ row_map,
                                                          int P, int width, int64_t n_sel, int chunks,
                                                          const int32_t* __restrict__ d_iter) {
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t r = wave_row();
   if (r >= n_sel) return;
   if (d_iter) idx += (size_t)(*d_iter) * n_sel;
   int pos = idx[r];
@@ -253,14 +244,11 @@ __global__ __launch_bounds__(256) void lm_tail_kernel(const float* __restrict__ 
                                                      const float* __restrict__ out_bias, float* __restrict__ logits,
                                                      int64_t n, int d, int V, float eps) {
   const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t r = wave_row();
   if (r >= n) return;
   const int nch4 = d >> 2;
-  const float4* x4 = (const float4*)(g + (size_t)r * d);
   float4 v[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-    if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
+  load_row(v, g + (size_t)r * d, nch4, lane);
   if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);      // gamma == nullptr: ESM-1's head has no LayerNorm
   float mine = 0.f;  // lane t keeps logit t (V <= 64)
   // four decoder rows per trip: their loads are all in flight before the first reduction (one row per trip was a chain
@@ -300,11 +288,8 @@ __global__ __launch_bounds__(1024) void lm_tail_small_kernel(const float* __rest
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t r = blockIdx.x;
   const int nch4 = d >> 2;
-  const float4* x4 = (const float4*)(g + (size_t)r * d);
   float4 v[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-    if (lane + 64 * i < nch4) v[i] = x4[lane + 64 * i];
+  load_row(v, g + (size_t)r * d, nch4, lane);
   if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);
   float s[4];
 #pragma unroll
@@ -331,8 +316,7 @@ __global__ __launch_bounds__(1024) void lm_tail_small_kernel(const float* __rest
 // ---- strict mode helpers: fp32 -> (hi, lo) bf16 pair, optionally through erf-GELU ----------------
 __device__ __forceinline__ float gelu_erf_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
-// src fp32 [rows][K] -> dst bf16 [rows][3K], per group of 32 columns [lo | hi | hi] (activation operand) or, WEIGHT, [hi | lo | hi]
-// (layout: store_row_bf16)
+// src fp32 [rows][K] -> dst bf16 [rows][3K]: the split operand row of an activation or, WEIGHT, of a weight (split_operand.h)
 template <bool GELU, bool WEIGHT>
 __global__ void split3_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int64_t n4, int k4, float scale) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,17 +325,13 @@ __global__ void split3_bf16_kernel(const float* __restrict__ src, bf16_t* __rest
     float4 v = ((const float4*)src)[i];
     v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
     if (GELU) { v.x = gelu_erf_exact(v.x); v.y = gelu_erf_exact(v.y); v.z = gelu_erf_exact(v.z); v.w = gelu_erf_exact(v.w); }
-    uint2 p, q;
-    p.x = pack_op2(v.x, v.y);
-    p.y = pack_op2(v.z, v.w);
-    q.x = pack_op2(v.x - op16_to_f32((bf16_t)(p.x & 0xffff)), v.y - op16_to_f32((bf16_t)(p.x >> 16)));
-    q.y = pack_op2(v.z - op16_to_f32((bf16_t)(p.y & 0xffff)), v.w - op16_to_f32((bf16_t)(p.y >> 16)));
+    uint2 hi, lo;
+    split4(v.x, v.y, v.z, v.w, hi, lo);
     const int64_t row = i / k4;
-    const int ci = (int)(i - row * k4);
-    uint2* o = (uint2*)dst + row * 3 * k4 + (ci >> 3) * 24 + (ci & 7);
-    o[0] = WEIGHT ? p : q;
-    o[8] = WEIGHT ? q : p;
-    o[16] = p;
+    const int ci = (int)(i - row * k4);                      // float4 index in the row = columns 4 ci .. 4 ci + 3
+    bf16_t* g = dst + row * 3 * (4 * k4) + split_lo_offset(4 * ci);
+    if (WEIGHT) split_store4_weight(g, hi, lo);
+    else split_store4(g, hi, lo, true);
   }
 }
 __global__ void gelu_f32_kernel(float* __restrict__ p, int64_t n) {
@@ -385,29 +365,47 @@ static inline bool rows_fit(int64_t rows) { return rows >= 0 && (rows + 3) / 4 <
 // it, unchanged), the 10-chunk one up to d = 2560
 static inline bool row_d_ok(int d) { return d >= 4 && d % 4 == 0 && d <= kMaxChWide * 256; }
 static inline bool row_wide(int d) { return d > kMaxCh * 256; }
+// f(integral_constant<int, NCH>) for the NCH of a row of d values: a launcher names its kernel template once
+template <class F>
+static inline void by_row_width(int d, F&& f) {
+  if (row_wide(d)) f(std::integral_constant<int, kMaxChWide>{});
+  else f(std::integral_constant<int, kMaxCh>{});
+}
+// A row launcher's admission of (d, rows) under the kernel's name `who`.  false: the launcher returns *rc -- 1, refused with the
+// error set, or 0, no rows and nothing to do
+static bool rows_go(const char* who, int d, int64_t rows, int* rc) {
+  *rc = 0;
+  if (!row_d_ok(d)) *rc = fail(1, std::string(who) + ": d must be a multiple of 4 and <= 2560");
+  else if (rows != 0 && !rows_fit(rows)) *rc = fail(1, std::string(who) + ": too many rows");
+  return *rc == 0 && rows != 0;
+}
+// n > 0 items over at most `cap` workgroups of 256 threads that stride the rest
+template <class Kernel, class... Args>
+static int launch_grid_stride(hipStream_t s, Kernel* kernel, int64_t n, int cap, Args... args) {
+  const unsigned grid = (unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, args...);
+  PG_HIP(hipGetLastError());
+  return 0;
+}
 
 int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, const float* pos, const float* msa_pos,
                     const float* gamma, const float* beta, float* x, int64_t n_tok, int T, int d, int pad_idx,
                     int mask_idx, int token_dropout, int rows_per_msa, float eps, const float* gamma2, const float* beta2,
                     bf16_t* h2, float embed_scale) {
-  if (!row_d_ok(d)) return fail(1, "embed: d must be a multiple of 4 and <= 2560");
-  if (n_tok == 0) return 0;
-  if (!rows_fit(n_tok)) return fail(1, "embed: too many rows");
-  if (row_wide(d))
-    hipLaunchKernelGGL(embed_ln_kernel<kMaxChWide>, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta, x,
-                       n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
-  else
-    hipLaunchKernelGGL(embed_ln_kernel<kMaxCh>, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta, x,
-                       n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
+  int rc;
+  if (!rows_go("embed", d, n_tok, &rc)) return rc;
+  by_row_width(d, [&](auto nch) {
+    hipLaunchKernelGGL(embed_ln_kernel<decltype(nch)::value>, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta,
+                       x, n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
+  });
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 // The argument refusals of launch_layernorm_bf16 (0 = the launch may go ahead; touches no device) ...
 int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C) {
-  if (!row_d_ok(d)) return fail(1, "layernorm: d must be a multiple of 4 and <= 2560");
-  if (M == 0) return 0;
-  if (!rows_fit(M)) return fail(1, "layernorm: too many rows");
+  int rc;
+  if (!rows_go("layernorm", d, M, &rc)) return rc;
   if (colmajor_R > 0) {
     if (row_wide(d)) return fail(1, "layernorm: column-major output needs d <= 2048");
     if (split3 || M % ((int64_t)colmajor_R * colmajor_C)) return fail(1, "layernorm: column-major output needs whole MSAs and plain bf16 rows");
@@ -456,8 +454,9 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
       else hipLaunchKernelGGL(layernorm_bf16_stride_kernel<768>, dim3(stride_grid), dim3(256), 0, s, x, gamma, beta, h, sp, M, eps);
       break;
     default:
-      if (row_wide(d)) hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxChWide>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
-      else hipLaunchKernelGGL(layernorm_bf16_kernel<kMaxCh>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+      by_row_width(d, [&](auto nch) {
+        hipLaunchKernelGGL(layernorm_bf16_kernel<decltype(nch)::value>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+      });
   }
   PG_HIP(hipGetLastError());
   return 0;
@@ -465,26 +464,23 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
 
 int launch_layernorm_f32(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t M, int d,
                          float eps) {
-  if (!row_d_ok(d)) return fail(1, "layernorm: d must be a multiple of 4 and <= 2560");
-  if (M == 0) return 0;
-  if (!rows_fit(M)) return fail(1, "layernorm: too many rows");
-  if (row_wide(d)) hipLaunchKernelGGL(layernorm_f32_kernel<kMaxChWide>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
-  else hipLaunchKernelGGL(layernorm_f32_kernel<kMaxCh>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
+  int rc;
+  if (!rows_go("layernorm", d, M, &rc)) return rc;
+  by_row_width(d, [&](auto nch) {
+    hipLaunchKernelGGL(layernorm_f32_kernel<decltype(nch)::value>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
+  });
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 int launch_gather_ln_bf16(hipStream_t s, const float* x, const int32_t* idx, const int32_t* row_map, int P, int width,
                           const float* gamma, const float* beta, bf16_t* h, int64_t n_sel, int d, float eps, bool split3) {
-  if (!row_d_ok(d)) return fail(1, "gather_ln: d must be a multiple of 4 and <= 2560");
-  if (n_sel == 0) return 0;
-  if (!rows_fit(n_sel)) return fail(1, "gather_ln: too many rows");
-  if (row_wide(d))
-    hipLaunchKernelGGL(gather_ln_bf16_kernel<kMaxChWide>, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
+  int rc;
+  if (!rows_go("gather_ln", d, n_sel, &rc)) return rc;
+  by_row_width(d, [&](auto nch) {
+    hipLaunchKernelGGL(gather_ln_bf16_kernel<decltype(nch)::value>, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
                        beta, h, split3 ? 1 : 0, n_sel, d, eps);
-  else
-    hipLaunchKernelGGL(gather_ln_bf16_kernel<kMaxCh>, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
-                       beta, h, split3 ? 1 : 0, n_sel, d, eps);
+  });
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -508,72 +504,44 @@ bool lm_tail_small(int64_t n) {
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
                    const float* out_bias, float* logits, int64_t n, int d, int V, float eps) {
   if (V < 1 || V > 64) return fail(1, "lm_tail: vocab must be in 1..64");      // lane t keeps logit t; 64 * ceil(V / 4) <= 1024 threads
-  if (!row_d_ok(d)) return fail(1, "lm_tail: d must be a multiple of 4 and <= 2560");
-  if (n == 0) return 0;
-  if (!rows_fit(n)) return fail(1, "lm_tail: too many rows");
+  int rc;
+  if (!rows_go("lm_tail", d, n, &rc)) return rc;
   // identical arithmetic per logit (same per-lane partial sums, same wave reduction): bit-equal results.  Up to 1024 rows (round 5;
   // it was 128): a 32-chain shard's 800 sampled rows took 81 us on the row-per-wave kernel -- 200 workgroups, each wave walking the
   // decoder rows in nine dependent trips -- PGIBBS_LM_TAIL_SMALL=n moves the switch
-  if (lm_tail_small(n)) {
-    // no shared memory; every wave holds the row and four decoder rows' chunks (NCH + 4 float4 in flight at most: far below the
-    // 128 VGPRs a 1024-thread workgroup may use per lane)
-    if (row_wide(d))
-      hipLaunchKernelGGL(lm_tail_small_kernel<kMaxChWide>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
+  const bool small = lm_tail_small(n);
+  by_row_width(d, [&](auto nch) {
+    constexpr int NCH = decltype(nch)::value;
+    // small: no shared memory; every wave holds the row and four decoder rows' chunks (NCH + 4 float4 in flight at most: far below
+    // the 128 VGPRs a 1024-thread workgroup may use per lane)
+    if (small)
+      hipLaunchKernelGGL(lm_tail_small_kernel<NCH>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
                          logits, d, V, eps);
     else
-      hipLaunchKernelGGL(lm_tail_small_kernel<kMaxCh>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
-                         logits, d, V, eps);
-    PG_HIP(hipGetLastError());
-    return 0;
-  }
-  if (row_wide(d))
-    hipLaunchKernelGGL(lm_tail_kernel<kMaxChWide>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
-  else
-    hipLaunchKernelGGL(lm_tail_kernel<kMaxCh>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
+      hipLaunchKernelGGL(lm_tail_kernel<NCH>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
+  });
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 int launch_split3_bf16(hipStream_t s, const float* src, bf16_t* dst, int64_t rows, int K, float scale, bool gelu, bool weight) {
   if (rows == 0) return 0;
-  if (K % 32) return fail(1, "split: K must be a multiple of 32");
+  if (K % kSplitCols) return fail(1, "split: K must be a multiple of 32");
+  if (gelu && weight) return fail(1, "split: GELU on a weight operand");
   const int64_t n4 = rows * (K / 4);
-  const unsigned grid = (unsigned)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-  if (gelu && !weight) hipLaunchKernelGGL((split3_bf16_kernel<true, false>), dim3(grid), dim3(256), 0, s, src, dst, n4, K / 4, scale);
-  else if (!gelu && weight) hipLaunchKernelGGL((split3_bf16_kernel<false, true>), dim3(grid), dim3(256), 0, s, src, dst, n4, K / 4, scale);
-  else if (!gelu) hipLaunchKernelGGL((split3_bf16_kernel<false, false>), dim3(grid), dim3(256), 0, s, src, dst, n4, K / 4, scale);
-  else return fail(1, "split: GELU on a weight operand");
-  PG_HIP(hipGetLastError());
-  return 0;
+  auto* kernel = gelu ? split3_bf16_kernel<true, false> : weight ? split3_bf16_kernel<false, true> : split3_bf16_kernel<false, false>;
+  return launch_grid_stride(s, kernel, n4, 8192, src, dst, n4, K / 4, scale);
 }
-int launch_gelu_f32(hipStream_t s, float* p, int64_t n) {
-  if (n == 0) return 0;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  hipLaunchKernelGGL(gelu_f32_kernel, dim3(grid), dim3(256), 0, s, p, n);
-  PG_HIP(hipGetLastError());
-  return 0;
-}
+int launch_gelu_f32(hipStream_t s, float* p, int64_t n) { return n ? launch_grid_stride(s, gelu_f32_kernel, n, 8192, p, n) : 0; }
 
 int launch_f32_to_bf16(hipStream_t s, const float* src, bf16_t* dst, int64_t n, float scale) {
-  if (n == 0) return 0;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(grid), dim3(256), 0, s, src, dst, n, scale);
-  PG_HIP(hipGetLastError());
-  return 0;
+  return n ? launch_grid_stride(s, f32_to_bf16_kernel, n, 4096, src, dst, n, scale) : 0;
 }
 int launch_bf16_to_f32(hipStream_t s, const bf16_t* src, float* dst, int64_t n) {
-  if (n == 0) return 0;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid), dim3(256), 0, s, src, dst, n);
-  PG_HIP(hipGetLastError());
-  return 0;
+  return n ? launch_grid_stride(s, bf16_to_f32_kernel, n, 4096, src, dst, n) : 0;
 }
 int launch_scale_f32(hipStream_t s, float* p, int64_t n, float scale) {
-  if (n == 0) return 0;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-  hipLaunchKernelGGL(scale_f32_kernel, dim3(grid), dim3(256), 0, s, p, n, scale);
-  PG_HIP(hipGetLastError());
-  return 0;
+  return n ? launch_grid_stride(s, scale_f32_kernel, n, 4096, p, n, scale) : 0;
 }
 
 PG_OPS_END

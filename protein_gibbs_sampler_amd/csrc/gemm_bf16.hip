@@ -957,7 +957,7 @@ int launch_gemm_split3(hipStream_t s, const bf16_t* X3, const bf16_t* W3, const 
                        int epi) {
   if (gemm_split3_fused(M, N, K, epi)) return launch_gemm_split3_w16(s, X3, W3, bias, out, M, N, K, ldo, epi);
   if (epi == EPI_SPLIT3_GELU || epi == EPI_SPLIT2_GELU) return fail(1, "gemm: split-operand epilogue needs M, N multiples of 256");
-  return launch_gemm_bf16(s, X3, W3, bias, out, M, N, 3 * K, 3 * K, 3 * K, ldo, epi);
+  return launch_gemm_bf16(s, X3, W3, bias, out, M, N, kSplitBlocks * K, kSplitBlocks * K, kSplitBlocks * K, ldo, epi);
 }
 #endif  // !PG_F16
 

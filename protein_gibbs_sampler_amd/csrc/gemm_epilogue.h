@@ -2,10 +2,11 @@
 // buffer access, 16-wave operand DMA, visit_int): the GELU forms (one definition for all kernels), EpiTraits, the 64 x 64 tail tile
 // of the 256 x 256 grids (gemm_tail_tile64), the LDS-staged epilogue of a 256 x 256 tile held by 4 or 16 waves (tile256_epilogue) and
 // the switches the tile launchers share (gemm_gm, gemm_tail_last).  Users: gemm_bf16.hip, gemm_ladder.hip, gemm_rowln.hip,
-// gemm_w16.hip, gemm_colattn.hip, chain_trunk.hip, engine.hip, api.hip; tools/probes/gemm_w4.hip.
+// gemm_w16.hip, gemm_colattn.hip, chain_trunk.hip, engine.hip, api_dbg.hip; tools/probes/gemm_w4.hip.
 #pragma once
 #include "gemm_tile.h"
 #include "kernels.h"
+#include "split_operand.h"
 
 PG_OPS_BEGIN
 
@@ -68,9 +69,9 @@ template <int EPI> struct EpiTraits {
 // instruction and k order as every other tile kernel: a row's result does not depend on which tile shape computed it.
 //   stage = 64 X rows + 64 W rows of 128 B = 16 pieces of 1 KiB (8 rows each); wave w stages piece w (and w + 8 with 8 waves)
 // ---------------------------------------------------------------------------------------------------------------------
-// SPLIT3 (strict precision mode, gemm_w16.hip): operands in the split layout, K = logical depth; a K-step is one group of 32
-// columns -- 128 B per row: xl | xh, wh | wl -- at a source stride of 192 B, and three products per step in the fused kernel's
-// order (wh.xl, wl.xh, wh.xh).
+// SPLIT3 (strict precision mode, gemm_w16.hip): operands in the split layout (split_operand.h), K = logical depth; a K-step is one
+// group of kSplitCols columns -- 128 B per row: xl | xh, wh | wl -- at a source stride of kSplitVals * 2 = 192 B, and three products
+// per step in the fused kernel's order (wh.xl, wl.xh, wh.xh).
 template <int NW, int EPI, bool SPLIT3 = false>
 __device__ __forceinline__ void gemm_tail_tile64(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                  const float* __restrict__ bias, void* __restrict__ out, int K, int ldx, int ldw,
@@ -80,9 +81,9 @@ __device__ __forceinline__ void gemm_tail_tile64(const bf16_t* __restrict__ X, c
   typedef EpiTraits<EPI> T;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nk = SPLIT3 ? K / 32 : K / 64;
+  const int nk = SPLIT3 ? K / kSplitCols : K / 64;
   const int kbytes = (SPLIT3 ? 3 * K : K) * 2;           // bytes of an operand row
-  constexpr int KSTEP_BYTES = SPLIT3 ? 192 : 128;
+  constexpr int KSTEP_BYTES = SPLIT3 ? kSplitVals * 2 : 128;
 
   // piece p (0-7: X rows 8p .., 8-15: W rows 8(p-8) ..): wave w stages piece w, and with 8 waves also piece w + 8 -- so piece A is
   // an X piece for w < 8 and piece B (8 waves only) always a W piece.  (No arrays of buffer resources: the type is opaque.)
@@ -150,8 +151,8 @@ __device__ __forceinline__ void gemm_tail_tile64(const bf16_t* __restrict__ X, c
     const int m_loc = (mi0 + j) * 16 + fr;
     float v0 = acc[j][0] + b4.x, v1 = acc[j][1] + b4.y, v2 = acc[j][2] + b4.z, v3 = acc[j][3] + b4.w;
     if (EPI == EPI_SPLIT3_GELU || EPI == EPI_SPLIT2_GELU) {
-      // strict fc1: GELU, the value split into its bf16 (hi, lo) pair, written as fc2's operand row [lo | hi | hi] per 32 columns
-      // (ldo = 3 N) -- the arithmetic of tile256_epilogue's EPI_SPLIT3_GELU branch
+      // strict fc1: GELU, the value split into its bf16 (hi, lo) pair, written as fc2's split operand row (split_operand.h; ldo = 3 N)
+      // -- the arithmetic of tile256_epilogue's EPI_SPLIT3_GELU branch
 #if PG_STRICT_GELU_POLY
       const pg_f32x2 ga = gelu_poly2(v0, v1), gb = gelu_poly2(v2, v3);
       const float g0 = ga[0], g1 = ga[1], g2 = gb[0], g3 = gb[1];
@@ -159,15 +160,8 @@ __device__ __forceinline__ void gemm_tail_tile64(const bf16_t* __restrict__ X, c
       const float g0 = gelu_erf(v0), g1 = gelu_erf(v1), g2 = gelu_erf(v2), g3 = gelu_erf(v3);
 #endif
       uint2 hi, lo;
-      hi.x = pack_op2(g0, g1);
-      hi.y = pack_op2(g2, g3);
-      lo.x = pack_op2(g0 - __uint_as_float(hi.x << 16), g1 - __uint_as_float(hi.x & 0xffff0000u));
-      lo.y = pack_op2(g2 - __uint_as_float(hi.y << 16), g3 - __uint_as_float(hi.y & 0xffff0000u));
-      const int n = n0 + n_loc;
-      bf16_t* o3 = (bf16_t*)out + (size_t)(m0 + m_loc) * ldo + (n >> 5) * 96 + (n & 31);
-      *(uint2*)o3 = lo;
-      *(uint2*)(o3 + 32) = hi;
-      if (EPI == EPI_SPLIT3_GELU) *(uint2*)(o3 + 64) = hi;
+      split4(g0, g1, g2, g3, hi, lo);
+      split_store4((bf16_t*)out + (size_t)(m0 + m_loc) * ldo + split_lo_offset(n0 + n_loc), hi, lo, EPI == EPI_SPLIT3_GELU);
       continue;
     }
     const size_t o = (size_t)(m0 + m_loc) * ldo + n0 + n_loc;
@@ -235,7 +229,7 @@ __device__ __forceinline__ void tile256_epilogue(ElemF&& elem, char* smem, int w
   }
   if (EPI == EPI_SPLIT3_GELU || EPI == EPI_SPLIT2_GELU) {
     // Strict-mode fc1 (16-wave element order only): erf-GELU in registers, the value split into its bf16 (hi, lo) pair, and
-    // the split operand rows of fc2 ([lo | hi | hi] per 32 columns, ldo = 3 N) written straight from here -- instead of an fp32 tile
+    // the split operand rows of fc2 (split_operand.h, ldo = 3 N) written straight from here -- instead of an fp32 tile
     // plus a separate GELU-and-split pass over it (8 of 14 bytes per element less traffic).  Two halves of 128 token rows
     // (half h = tile rows with bit 5 == h = elements with bit 1 of e == h), each staged as a hi tile and a lo tile of 64 KB.
     static_assert((EPI != EPI_SPLIT3_GELU && EPI != EPI_SPLIT2_GELU) || NW == 16, "element order of the 16-wave kernel");
@@ -255,10 +249,7 @@ __device__ __forceinline__ void tile256_epilogue(ElemF&& elem, char* smem, int w
         const float g0 = gelu_erf(a[0] + b4.x), g1 = gelu_erf(a[1] + b4.y), g2 = gelu_erf(a[2] + b4.z), g3 = gelu_erf(a[3] + b4.w);
 #endif
         uint2 hi, lo;
-        hi.x = pack_op2(g0, g1);
-        hi.y = pack_op2(g2, g3);
-        lo.x = pack_op2(g0 - __uint_as_float(hi.x << 16), g1 - __uint_as_float(hi.x & 0xffff0000u));
-        lo.y = pack_op2(g2 - __uint_as_float(hi.y << 16), g3 - __uint_as_float(hi.y & 0xffff0000u));
+        split4(g0, g1, g2, g3, hi, lo);
         const int hr = (row >> 6) * 32 + (row & 31);
         const int off = hr * 512 + (((n >> 3) ^ (hr & 31)) << 4) + (n & 4) * 2;
         *(uint2*)(smem + off) = hi;
@@ -271,11 +262,9 @@ __device__ __forceinline__ void tile256_epilogue(ElemF&& elem, char* smem, int w
         const int hr = wave * 8 + it * 2 + (lane >> 5);
         const uint4 vh = *(const uint4*)(smem + hr * 512 + ((c ^ (hr & 31)) << 4));
         const uint4 vl = *(const uint4*)(smem + 65536 + hr * 512 + ((c ^ (hr & 31)) << 4));
-        // columns n0 + 8c .. +7 of the token row -> group (n0 + 8c) / 32 of the split operand row, [lo | hi | hi] per 32 columns
-        bf16_t* o = (bf16_t*)out + (size_t)(m0 + (hr >> 5) * 64 + h * 32 + (hr & 31)) * ldo + ((n0 >> 5) + (c >> 2)) * 96 + (c & 3) * 8;
-        PG_NT_STORE((uint4*)o, vl);
-        PG_NT_STORE((uint4*)(o + 32), vh);
-        if (EPI == EPI_SPLIT3_GELU) PG_NT_STORE((uint4*)(o + 64), vh);      // EPI_SPLIT2_GELU: the duplicate block stays unwritten
+        // columns n0 + 8c .. +7 of the token row (EPI_SPLIT2_GELU: the duplicate block stays unwritten)
+        bf16_t* o = (bf16_t*)out + (size_t)(m0 + (hr >> 5) * 64 + h * 32 + (hr & 31)) * ldo + split_group_offset((n0 >> 5) + (c >> 2), (c & 3) * 8);
+        split_store8_nt(o, vh, vl, EPI == EPI_SPLIT3_GELU);
       }
     }
     return;

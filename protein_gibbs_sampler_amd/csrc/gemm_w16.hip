@@ -149,11 +149,11 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
 #ifndef PG_F16      /* the strict mode's split operands are bf16 pairs in either build */
 // ---------------------------------------------------------------------------------------------------------------------
 // Strict precision mode: the three split-bf16 products of a projection from ONE pass over the operands.
-//   X3 [M][3K], W3 [N][3K]: per group of 32 columns X3 = [xl | xh | xh], W3 = [wh | wl | wh] (elementwise.hip store_row_bf16).
+//   X3 [M][3K], W3 [N][3K]: per group of 32 columns X3 = [xl | xh | xh], W3 = [wh | wl | wh] (split_operand.h).
 // A "K-step" here is one group: the first 64 values (128 B) of the group from each operand row -- xl, xh / wh, wl of 32
 // columns -- land in the same 128-B LDS rows as a plain K-step of 64, so the DMA pieces, the swizzle and the fragment
 // addressing are those of gemm_bf16_w16_kernel (half 0 of a row = xl / wh, half 1 = xh / wl); only the source stride per
-// step (192 B instead of 128) and the MFMA list differ:   acc += wh.xl ; acc += wl.xh ; acc += wh.xh   (48 MFMAs per 64 KB
+// step (kSplitVals * 2 = 192 B instead of 128) and the MFMA list differ:   acc += wh.xl ; acc += wl.xh ; acc += wh.xh   (48 MFMAs per 64 KB
 // staged instead of 32: the operand feed, not the matrix pipe, bounds these kernels).  Per accumulator that is exactly the
 // sequence a plain bf16 GEMM over K' = 3K walks through on this layout -- the k order of every other tile kernel -- so the
 // result is bit-identical with launch_gemm_bf16 on the same operands (tests/test_gpu_strict_kernels.py), and a batch split
@@ -183,15 +183,15 @@ __global__ __launch_bounds__(1024, 1) void gemm_split3_w16_kernel(const bf16_t* 
   const bool stage_w = wave >= 8;
   const int ld_ = stage_w ? ldw : ldx;
   const bf16_t* src = (stage_w ? W + (size_t)n0 * ldw : X + (size_t)m0 * ldx) + (size_t)(wave & 7) * 32 * ld_;
-  const rsrc_t rs_src = buf_rsrc(src, (31 * ld_ + 3 * K) * 2);      // band_rsrc(src, 32, ld_, 3 * K), spelled out: the call evaluates 3 * K first and the scalar multiplies swap
+  const rsrc_t rs_src = buf_rsrc(src, (31 * ld_ + kSplitBlocks * K) * 2);      // band_rsrc(src, 32, ld_, 3 * K), spelled out: the call evaluates 3 * K first and the scalar multiplies swap
   const int dma_voff = PG_ROW128_SRC(lane, ld_);
   const int piece_bytes = 8 * ld_ * 2;
   const int lds_piece0 = wave * 4 * 1024;
-  const int nk = K / 32;                             // groups of 32 columns
+  const int nk = K / kSplitCols;                     // groups of 32 columns
 
   auto dma_step = [&](int t) {
     char* dst = smem + (t & 1) * W16_KSLOT + lds_piece0;
-    const int soff = PG_KSTEP_SOFF(t, nk, 192);
+    const int soff = PG_KSTEP_SOFF(t, nk, kSplitVals * 2);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, PG_LDS_PTR(dst + g * 1024), 16, dma_voff, soff + g * piece_bytes, 0, 0);
@@ -259,15 +259,15 @@ int launch_gemm_split3_w16(hipStream_t s, const bf16_t* X3, const bf16_t* W3, co
   if (M % 256 || N % 256 || K % 32 || K < 32 || M < 256) return fail(1, "gemm_split3_w16: shape");
   // whole rounds of 256 x 256 tiles + 64 x 64 tail tiles for the rows of a mostly empty last round, as launch_gemm_big
   int m_main = M / 256, tail_rows = 0;
-  gemm_big_geometry(M, N, 3 * K, &m_main, &tail_rows);
+  gemm_big_geometry(M, N, kSplitBlocks * K, &m_main, &tail_rows);
   const int tiles_m = m_main, tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
   const int n_tail = (tail_rows / 64) * (N / 64), tail_m0 = m_main * 256;
   const int gm = K >= 4096 ? 2 : 4;
   dim3 grid(n_tiles + n_tail), block(1024);
   const bool known = visit_int<EPI_F32, EPI_F32_RESID, EPI_SPLIT3_GELU, EPI_SPLIT2_GELU>(epi, [&](auto E) {
     return visit_int<2, 4>(gm, [&](auto G) {
-      hipLaunchKernelGGL((gemm_split3_w16_kernel<decltype(E)::value, decltype(G)::value>), grid, block, 0, s, X3, W3, bias, out, K, 3 * K,
-                         3 * K, ldo, tiles_n, n_tiles, n_tail, tail_m0);
+      hipLaunchKernelGGL((gemm_split3_w16_kernel<decltype(E)::value, decltype(G)::value>), grid, block, 0, s, X3, W3, bias, out, K,
+                         kSplitBlocks * K, kSplitBlocks * K, ldo, tiles_n, n_tiles, n_tail, tail_m0);
     });
   });
   if (!known) return fail(1, "gemm_split3_w16: bad epilogue");

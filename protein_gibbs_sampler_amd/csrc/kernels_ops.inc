@@ -21,7 +21,7 @@ size_t gemm_splitk_ws_bytes(int M, int N, int K);
 //             launch_pp (gemm_bf16.hip)
 //    60 + ... the same list, id = variant - 40 (68 / 69: ids 28 / 29)
 //    80 + a   ablation a of the 16-wave kernel (a = 0: the kernel itself); ids in launch_gemm_w16 (gemm_w16.hip)
-//    90       pg_dbg_gemm_bench only (api.hip): the strict mode's fused three-product kernel
+//    90       pg_dbg_gemm_bench only (api_dbg.hip): the strict mode's fused three-product kernel
 // A variant that names a kernel takes it where the shape allows (6 - 8: divisibility; 20 and up: more than 256 rows, M and N
 // multiples of 256) and is the production dispatch without K-splits elsewhere.  An ablation id that does not exist is an error.
 int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,

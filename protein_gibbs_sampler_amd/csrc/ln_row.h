@@ -4,6 +4,7 @@
 // intrinsic, so no translation unit's contraction choices can differ.
 #pragma once
 #include "pg_common.h"
+#include "split_operand.h"
 
 PG_OPS_BEGIN
 
@@ -49,12 +50,8 @@ __device__ __forceinline__ void ln_inplace(float4 (&v)[NCH], int nch4, int lane,
     }
 }
 
-// hi = bf16(v).  split3 (strict precision mode): the row becomes the split-bf16 activation operand of 3 * d values, interleaved
-// in groups of 32 columns: group g = [lo(32) | hi(32) | hi(32)] of columns 32g .. 32g+31, lo = bf16(v - hi).  Against a weight
-// row packed [hi | lo | hi] the same way, one bf16 GEMM over K' = 3 d sums, per 32 columns and in this order,
-// x_lo.w_hi + x_hi.w_lo + x_hi.w_hi in its fp32 accumulator -- whichever tile kernel runs it; the fused 16-wave kernel
-// (gemm_w16.hip) reads only the first two blocks of each group and issues the same three products from registers.
-// dup = false leaves the third block of every group unwritten (the consumer is the fused kernel: gemm_split3_fused).
+// The row as 16-bit operand values; split3 (strict precision mode): as the split operand row of 3 * d bf16 values (split_operand.h:
+// hi = bf16(v), lo = bf16(v - hi), per group of 32 columns [lo | hi | hi]); dup = false leaves the third block of every group unwritten.
 template <int NCH>
 __device__ __forceinline__ void store_row_bf16(bf16_t* dst, const float4 (&v)[NCH], int nch4, int lane, bool split3 = false,
                                                bool dup = true) {
@@ -68,13 +65,9 @@ __device__ __forceinline__ void store_row_bf16(bf16_t* dst, const float4 (&v)[NC
       if (!split3) {
         ((uint2*)dst)[ci] = p;
       } else {
-        uint2 q;
-        q.x = pack_op2(__fsub_rn(v[i].x, op16_to_f32((bf16_t)(p.x & 0xffff))), __fsub_rn(v[i].y, op16_to_f32((bf16_t)(p.x >> 16))));
-        q.y = pack_op2(__fsub_rn(v[i].z, op16_to_f32((bf16_t)(p.y & 0xffff))), __fsub_rn(v[i].w, op16_to_f32((bf16_t)(p.y >> 16))));
-        uint2* o = (uint2*)dst + (ci >> 3) * 24 + (ci & 7);      // group of 32 columns = 96 values = 24 uint2
-        o[0] = q;
-        o[8] = p;
-        if (dup) o[16] = p;
+        uint2 hi, lo;
+        split4(v[i].x, v[i].y, v[i].z, v[i].w, hi, lo);
+        split_store4(dst + split_group_offset(ci >> 3, (ci & 7) * 4), hi, lo, dup);
       }
     }
 }

@@ -54,6 +54,7 @@ def _cases():
                              "pg_dbg_gather_ln: bad argument"),
         "pg_dbg_gather_rows": ([0, _z(16, 16, dt=np.uint8), 16, _z(4, 16, dt=np.uint8), 4, _i32(0, 1, 2, 3), 0, 0, None, 0, 1, 4, 4, 16], 1,
                                "pg_dbg_gather_rows: bad argument"),
+        "pg_dbg_split_rows": ([0, _z(4, 64), _z(4, 192, dt=np.uint16), 4, 4, 64, 1.0, 0, None], 1, "pg_dbg_split_rows: bad argument"),
         "pg_dbg_lm_tail": ([0, _z(4, 64), None, None, _z(33, 64), _z(33), _z(4, 33), 4, 64, 33, 1e-5, None], 1,
                            "pg_dbg_lm_tail: bad argument"),
     }
@@ -110,13 +111,18 @@ def test_row_entries_take_16_bit_modes_only(name):
     assert _call(name, _with(args, 1, FP32)) == (_lib.PG_ERR_INVALID, name + ": precision must be PG_PREC_BF16 or PG_PREC_F16")
 
 
-# Three refusals that are argument checks like the rest and precede the device lookup like the rest: with or without a GPU the
+# Refusals that are argument checks like the rest and precede the device lookup like the rest: with or without a GPU the
 # answer is the refusal, not PG_ERR_NO_DEVICE.
 LATE = {
     "gemm_fused_gelu_split_needs_N_256": ("pg_dbg_gemm", {1: FP32, 9: 5}, _lib.PG_ERR_INVALID,
                                           "pg_dbg_gemm: the fused GELU-and-split epilogue needs N a multiple of 256"),
     "gemm_strict_epilogues": ("pg_dbg_gemm", {1: FP32, 9: 1}, _lib.PG_ERR_UNSUPPORTED,
                               "strict mode: plain (0), residual (2) and fused GELU-split (5) epilogues only"),
+    "split_rows_K_not_32": ("pg_dbg_split_rows", {5: 48}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: K must be a multiple of 32"),
+    "split_rows_no_rows": ("pg_dbg_split_rows", {4: 0}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: bad argument"),
+    "split_rows_unknown_form": ("pg_dbg_split_rows", {7: 4}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: form is weight (1) + through GELU (2)"),
+    "split_rows_gelu_on_weight": ("pg_dbg_split_rows", {7: 3, 8: _z(4, 64)}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: GELU on a weight operand"),
+    "split_rows_gelu_scale": ("pg_dbg_split_rows", {7: 2, 6: 0.37, 8: _z(4, 64)}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: the GELU form takes scale 1"),
     "gemm_bench_variant_90": ("pg_dbg_gemm_bench", {5: 90}, _lib.PG_ERR_INVALID, "variant 90: K = 3 x depth, fp32 epilogues"),
 }
 

@@ -220,3 +220,53 @@ def test_valu_attention_kernels_agree_too():
                        timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     assert "valu kernels OK" in p.stdout
+
+
+# ---- split3_bf16_kernel, the only writer of the weight order: bit for bit against the host restatement ------------------------------
+FILL = 0xBEEF
+SPLIT_SHAPES = [(1, 32), (3, 96), (5, 1280), (2049, 4096)]      # one group; the group index moves; the model's width; a second grid-stride trip
+
+
+def _split_input(rows, K):
+    rng = np.random.default_rng(rows * 7 + K)
+    x = rng.standard_normal((rows, K), dtype=np.float32)
+    flat = x.reshape(-1)
+    flat[::17] = np.float32(0.0)
+    flat[3::29] = np.float32(1.5)            # exact bf16 values: lo = 0
+    flat[5::31] = np.float32(-0.0078125)
+    return x
+
+
+def _split_rows(x, scale, form):
+    from _ln_host import F32
+    rows, K = x.shape
+    h = np.full((rows + 2, 3 * K), FILL, dtype=np.uint16)
+    g = np.empty((rows, K), dtype=F32) if form == 2 else None
+    _lib.check(_lib.lib().pg_dbg_split_rows(0, _lib.ptr(x), _lib.ptr(h), rows + 2, rows, K, float(scale), form,
+                                            _lib.ptr(g) if g is not None else None))
+    assert (h[rows:] == FILL).all(), "rows past `rows` must keep the caller's fill"
+    return h[:rows], g
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.37])
+@pytest.mark.parametrize("weight", [0, 1])
+@pytest.mark.parametrize("rows,K", SPLIT_SHAPES)
+def test_split_rows_equal_the_host_restatement(rows, K, weight, scale):
+    from _ln_host import F32, SPLIT_DUP, store_rows_host
+    x = _split_input(rows, K)
+    got, _ = _split_rows(x, scale, weight)
+    want = store_rows_host((x * F32(scale)).astype(F32), SPLIT_DUP).reshape(rows, K // 32, 3, 32)
+    if weight:
+        want = want[:, :, [1, 0, 2]]          # [lo | hi | hi] -> [hi | lo | hi]
+    bad = int((got != want.reshape(rows, 3 * K)).sum())
+    print("\nsplit rows %s weight %d scale %g: %d of %d words differ" % ((rows, K), weight, scale, bad, got.size))
+    assert bad == 0
+
+
+@pytest.mark.parametrize("rows,K", SPLIT_SHAPES)
+def test_split_rows_through_gelu_equal_the_split_of_gelu_f32(rows, K):
+    from _ln_host import SPLIT_DUP, store_rows_host
+    got, g = _split_rows(_split_input(rows, K), 1.0, 2)
+    bad = int((got != store_rows_host(g, SPLIT_DUP)).sum())
+    print("\nsplit rows through GELU %s: %d of %d words differ" % ((rows, K), bad, got.size))
+    assert bad == 0
