@@ -309,6 +309,16 @@ int pg_prof_get_kernels(pg_engine*, const char* kernel_class, char* buf, int buf
  * path's kernels with fp16 operands (epi 0-4) */
 int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N,
                 int K, int epi);
+/* pg_dbg_gemm with the kernel named and reported (pg_dbg_gemm is this with variant -1, have_ws -1, m_live M, no plan).
+ * variant: -1 = the process's dispatch (launch_gemm_bf16, PGIBBS_GEMM), else one of the variants of pg_dbg_gemm_bench that compute a
+ * whole result -- 1 lockstep tiles, 2 production dispatch, 6 / 7 64^2 / 128^2 tiles, 8 192 x 256 tiles + tail tiles (residual), 20 the
+ * 8-wave ping-pong kernel, 80 the 16-wave kernel; every other value, the ablation ids included, is PG_ERR_INVALID.  PG_PREC_FP32 takes
+ * variant -1 only (PG_ERR_UNSUPPORTED otherwise).  have_ws: 0 = no split-K scratch, 1 = scratch on offer whatever the epilogue (the
+ * dispatch takes it for the residual epilogue only), -1 = on offer to the residual epilogue.  m_live: rows that hold tokens, 0 = all.
+ * plan (NULL: not wanted): the text the GEMM launch alone recorded, as pg_dbg_gemm_plan words it; the strict mode's fused kernel
+ * records "gemm_split3_w16 <tiles>t".  All refusals precede the device lookup; a shape the dispatch refuses is the launcher's error. */
+int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N, int K, int epi,
+                  int variant, int have_ws, int m_live, char* plan, int plan_bytes);
 /* times `iters` back-to-back launches of the GEMM on device-resident random bf16 operands (HIP events; M a multiple of 16,
  * of 64 above 256); variant 1 =
  * lockstep kernel, 2 = ping-pong kernel; epi: 0 bf16 out, 1 bf16+gelu, 2 fp32 residual, 3 fp32, 4 fp32+gelu */

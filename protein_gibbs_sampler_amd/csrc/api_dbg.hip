@@ -160,10 +160,25 @@ extern "C" {
 
 int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N,
                 int K, int epi) {
+  return pg_dbg_gemm_v(device, precision, x, w, bias, out, M, N, K, epi, -1, -1, M, nullptr, 0);
+}
+
+/* pg_dbg_gemm with the kernel named: variant -1 = launch_gemm_bf16 (the process's PGIBBS_GEMM), else launch_gemm_bf16_variant with one
+ * of the variants that compute a whole result; have_ws 0 / 1 = split-K scratch withheld / on offer whatever the epilogue, -1 = on offer
+ * to the residual epilogue; plan (may be NULL): the text the GEMM launch alone recorded.  Everything is refused on the host before a
+ * device is looked for; a shape plan_gemm refuses comes back as the launcher's error. */
+int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N, int K, int epi,
+                  int variant, int have_ws, int m_live, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
   int rc = dbg_precision("pg_dbg_gemm", precision, true);
   if (rc) return rc;
-  if (!x || !w || !bias || !out || M < 1 || N % 64 || K % 64) return fail(PG_ERR_INVALID, "pg_dbg_gemm: bad argument");
+  if (!x || !w || !bias || !out || M < 1 || N % 64 || K % 64 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_gemm: bad argument");
+  if (have_ws < -1 || have_ws > 1 || m_live < 0 || m_live > M) return fail(PG_ERR_INVALID, "pg_dbg_gemm_v: have_ws is -1, 0 or 1 and m_live 0 ... M");
+  // the ablation instances (21 ..., 60 ..., 81 ..., 90) compute deliberately incomplete results: nothing to compare
+  const bool whole = variant == 1 || variant == 2 || variant == 6 || variant == 7 || variant == 8 || variant == 20 || variant == 80;
+  if (variant != -1 && !whole) return fail(PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80");
   const bool strict = precision == PG_PREC_FP32;      // K-concatenated split-bf16 operands (engine.h dense3)
+  if (strict && variant != -1) return fail(PG_ERR_UNSUPPORTED, "strict mode: launch_gemm_split3 has no variant (-1 only)");
   if (strict && epi == 5 && N % 256) return fail(PG_ERR_INVALID, "pg_dbg_gemm: the fused GELU-and-split epilogue needs N a multiple of 256");
   if (strict && epi != 0 && epi != 2 && epi != 5)
     return fail(PG_ERR_UNSUPPORTED, "strict mode: plain (0), residual (2) and fused GELU-split (5) epilogues only");
@@ -182,29 +197,35 @@ int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const
   bf16_t* bw = d.alloc<bf16_t>((size_t)N * K * ks);
   // fc1's fused strict epilogue (5): operand rows [lo | hi | hi] of gelu(x w^T + b), returned as hi + lo
   bf16_t* o16 = strict && epi == 5 ? d.alloc<bf16_t>((size_t)Mp * 3 * N) : out16 ? d.alloc<bf16_t>((size_t)Mp * N) : nullptr;
-  // the residual variant gets split-K scratch, as the engine gives its fc2 GEMMs (taken for deep K and few tiles)
-  const size_t ws_bytes = !strict && epi == 2 ? OPS(gemm_splitk_ws_bytes, Mp, N, K) : 0;
+  // the residual variant gets split-K scratch, as the engine gives its fc2 GEMMs (taken for deep K and few tiles); have_ws 1 offers
+  // it to every epilogue (the plan takes it for the residual one only), 0 withholds it
+  const bool offer = have_ws < 0 ? epi == 2 : have_ws == 1;
+  const size_t ws_bytes = !strict && offer ? OPS(gemm_splitk_ws_bytes, Mp, N, K) : 0;
   float* ws = ws_bytes && ws_bytes <= ((size_t)1 << 30) ? (float*)d.alloc<char>(ws_bytes) : nullptr;
   if ((rc = d.check())) return rc;
   if (strict) {
     if ((rc = launch_split3_bf16(nullptr, dx, bx, Mp, K, 1.f, false, false))) return rc;
     if ((rc = launch_split3_bf16(nullptr, dw, bw, N, K, 1.f, false, true))) return rc;
+    clear_noted_kernels();
     if (epi == 5) {
       if ((rc = launch_gemm_split3(nullptr, bx, bw, db, o16, Mp, N, K, 3 * N, EPI_SPLIT3_GELU))) return rc;
+      dbg_noted_text(plan, plan_bytes);
       return split3_rows_to_host(o16, out, M, N);
     }
     if ((rc = launch_gemm_split3(nullptr, bx, bw, db, dout, Mp, N, K, N, epi == 2 ? EPI_F32_RESID : EPI_F32))) return rc;
+    dbg_noted_text(plan, plan_bytes);
     return d.down(out, dout, (size_t)M * N);
   }
   if ((rc = to16(precision, dx, bx, (int64_t)Mp * K))) return rc;
   if ((rc = to16(precision, dw, bw, (int64_t)N * K))) return rc;
-  if (out16) {
-    if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, o16, M16, N, K, K, K, N, epi == 4 ? EPI_BF16_GELU : EPI_BF16, nullptr, 0, M))) return rc;
-    return down16(d, precision, o16, dout, out, (int64_t)M * N);
-  }
-  if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, dout, M16, N, K, K, K, N, epi == 2 ? EPI_F32_RESID : (epi ? EPI_F32_GELU : EPI_F32), ws,
-                ws ? ws_bytes : 0, M))) return rc;
-  return d.down(out, dout, (size_t)M * N);
+  clear_noted_kernels();
+  void* o = out16 ? (void*)o16 : (void*)dout;
+  const int e = out16 ? (epi == 4 ? EPI_BF16_GELU : EPI_BF16) : (epi == 2 ? EPI_F32_RESID : (epi ? EPI_F32_GELU : EPI_F32));
+  rc = variant < 0 ? OPS(launch_gemm_bf16, nullptr, bx, bw, db, o, M16, N, K, K, K, N, e, ws, ws ? ws_bytes : 0, m_live)
+                   : OPS(launch_gemm_bf16_variant, nullptr, bx, bw, db, o, M16, N, K, K, K, N, e, variant, ws, ws ? ws_bytes : 0, m_live);
+  if (rc) return rc;
+  dbg_noted_text(plan, plan_bytes);
+  return out16 ? down16(d, precision, o16, dout, out, (int64_t)M * N) : d.down(out, dout, (size_t)M * N);
 }
 
 int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int iters, double* avg_ms) {

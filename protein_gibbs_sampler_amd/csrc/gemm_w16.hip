@@ -264,6 +264,8 @@ int launch_gemm_split3_w16(hipStream_t s, const bf16_t* X3, const bf16_t* W3, co
   const int n_tail = (tail_rows / 64) * (N / 64), tail_m0 = m_main * 256;
   const int gm = K >= 4096 ? 2 : 4;
   dim3 grid(n_tiles + n_tail), block(1024);
+  note_kernel("gemm_split3_w16", n_tiles);
+  if (n_tail) note_kernel("tail64", n_tail);
   const bool known = visit_int<EPI_F32, EPI_F32_RESID, EPI_SPLIT3_GELU, EPI_SPLIT2_GELU>(epi, [&](auto E) {
     return visit_int<2, 4>(gm, [&](auto G) {
       hipLaunchKernelGGL((gemm_split3_w16_kernel<decltype(E)::value, decltype(G)::value>), grid, block, 0, s, X3, W3, bias, out, K,

@@ -34,6 +34,7 @@ def _cases():
     h16 = _z(4, 64, dt=np.uint16)
     return {
         "pg_dbg_gemm": ([0, BF16, x, w, b, _z(4, 64), 4, 64, 64, 0], 2, "pg_dbg_gemm: bad argument"),
+        "pg_dbg_gemm_v": ([0, BF16, x, w, b, _z(4, 64), 4, 64, 64, 0, -1, -1, 4, None, 0], 2, "pg_dbg_gemm: bad argument"),
         "pg_dbg_gemm_bench": ([0, 16, 64, 64, 0, 1, 1, _dbl(1)], 7, "pg_dbg_gemm_bench: bad argument"),
         "pg_dbg_rowln_bench": ([0, 256, 128, 1, _dbl(5), _dbl(1)], 4, "pg_dbg_rowln_bench: bad argument"),
         "pg_dbg_qkv_attention_bench": ([0, 1, 32, 1, 1, _dbl(3), _dbl(1)], 5, "pg_dbg_qkv_attention_bench: T must be 32, 64, 128 or 256"),
@@ -94,7 +95,7 @@ def test_valid_arguments_without_a_gpu_are_no_device(name):
     assert _call(name, args) == (_lib.PG_ERR_NO_DEVICE, "no HIP device visible")
 
 
-@pytest.mark.parametrize("name", ["pg_dbg_gemm", "pg_dbg_attention_kv", "pg_dbg_layernorm_operand", "pg_dbg_rope_hd"])
+@pytest.mark.parametrize("name", ["pg_dbg_gemm", "pg_dbg_gemm_v", "pg_dbg_attention_kv", "pg_dbg_layernorm_operand", "pg_dbg_rope_hd"])
 def test_unknown_precision_mode(name):
     args, _, _ = _cases()[name]
     assert _call(name, _with(args, 1, 7)) == (_lib.PG_ERR_INVALID, "unknown precision mode")
@@ -118,6 +119,19 @@ LATE = {
                                           "pg_dbg_gemm: the fused GELU-and-split epilogue needs N a multiple of 256"),
     "gemm_strict_epilogues": ("pg_dbg_gemm", {1: FP32, 9: 1}, _lib.PG_ERR_UNSUPPORTED,
                               "strict mode: plain (0), residual (2) and fused GELU-split (5) epilogues only"),
+    "gemm_v_fused_gelu_split_needs_N_256": ("pg_dbg_gemm_v", {1: FP32, 9: 5}, _lib.PG_ERR_INVALID,
+                                            "pg_dbg_gemm: the fused GELU-and-split epilogue needs N a multiple of 256"),
+    "gemm_v_unknown_variant": ("pg_dbg_gemm_v", {10: 3}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80"),
+    "gemm_v_ablation_pp": ("pg_dbg_gemm_v", {10: 21}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80"),
+    "gemm_v_ablation_pp_60": ("pg_dbg_gemm_v", {10: 60}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80"),
+    "gemm_v_ablation_w16": ("pg_dbg_gemm_v", {10: 81}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80"),
+    "gemm_v_variant_90": ("pg_dbg_gemm_v", {10: 90}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80"),
+    "gemm_v_variant_below_minus_1": ("pg_dbg_gemm_v", {10: -2}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: variant must be -1, 1, 2, 6, 7, 8, 20 or 80"),
+    "gemm_v_strict_has_no_variant": ("pg_dbg_gemm_v", {1: FP32, 10: 2}, _lib.PG_ERR_UNSUPPORTED,
+                                     "strict mode: launch_gemm_split3 has no variant (-1 only)"),
+    "gemm_v_have_ws": ("pg_dbg_gemm_v", {11: 2}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: have_ws is -1, 0 or 1 and m_live 0 ... M"),
+    "gemm_v_m_live": ("pg_dbg_gemm_v", {12: 5}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_v: have_ws is -1, 0 or 1 and m_live 0 ... M"),
+    "gemm_v_plan_without_room": ("pg_dbg_gemm_v", {13: ctypes.create_string_buffer(8), 14: 0}, _lib.PG_ERR_INVALID, "pg_dbg_gemm: bad argument"),
     "split_rows_K_not_32": ("pg_dbg_split_rows", {5: 48}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: K must be a multiple of 32"),
     "split_rows_no_rows": ("pg_dbg_split_rows", {4: 0}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: bad argument"),
     "split_rows_unknown_form": ("pg_dbg_split_rows", {7: 4}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: form is weight (1) + through GELU (2)"),

@@ -199,8 +199,27 @@ for (M, N, K, epi, prec) in [(8256, 1280, 1280, 2, _lib.PG_PREC_BF16), (8256, 12
     out = rng.standard_normal((M, N), dtype=np.float32)
     _lib.check(_lib.lib().pg_dbg_gemm(0, prec, _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out), M, N, K, epi))
     outs.append(np.concatenate([out[::5], out[-300:]]).copy())          # a sample of all rows + the whole last row panels
+# one exact case (tests/_gemm_reference.py: small-integer operands, every partial sum exact in fp32), which the parent also compares
+# with the int64 reference: 33 row panels x 4 column tiles, two K-tiles, live rows below the padding
+sys.path.insert(0, sys.path[0] + "/tests")
+import _gemm_reference as gr
+e = gr.integers(*gr.LADDER_EXACT, seed=1, residual=True)
+out = e.res.copy()
+_lib.check(_lib.lib().pg_dbg_gemm(0, _lib.PG_PREC_BF16, _lib.ptr(e.x), _lib.ptr(e.w), _lib.ptr(e.bias), _lib.ptr(out), *gr.LADDER_EXACT, 2))
+np.save(sys.argv[1] + ".exact.npy", np.concatenate([out[::5], out[-300:]]))
 np.savez(sys.argv[1], *outs)
 """
+
+
+_LADDER_REF = []
+
+
+def _ladder_reference():
+    if not _LADDER_REF:
+        import _gemm_reference as gr
+        ref = gr.integers(*gr.LADDER_EXACT, seed=1, residual=True).ref.astype(np.float32)
+        _LADDER_REF.append(np.concatenate([ref[::5], ref[-300:]]))
+    return _LADDER_REF[0]
 
 
 def test_unknown_gemm_ablation_is_an_error():
@@ -236,6 +255,10 @@ def test_tile_height_ladder_is_bit_identical_with_256_row_tiles(tmp_path, height
     for k in res["0"].files:
         assert np.isfinite(res["0"][k]).all()
         assert (res[str(height)][k] == res["0"][k]).all(), (height, k)
+    # the exact-integer case: both settings against the int64 reference, bit for bit
+    for sw in (str(height), "0"):
+        exact = np.load(str(tmp_path / ("ladder_%s.npz.exact.npy" % sw)))
+        assert (exact.view(np.uint32) == _ladder_reference().view(np.uint32)).all(), (height, sw)
 
 
 def test_192_row_tiles_are_bit_identical_with_256_row_tiles(tmp_path):
