@@ -319,6 +319,18 @@ int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const
  * records "gemm_split3_w16 <tiles>t".  All refusals precede the device lookup; a shape the dispatch refuses is the launcher's error. */
 int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N, int K, int epi,
                   int variant, int have_ws, int m_live, char* plan, int plan_bytes);
+/* The single-chain GEMM that computes the preceding LayerNorm in its operand load (gemm_ln_skinny_kernel), alone:
+ * out = LayerNorm(x; gamma, beta, eps) . w^T + bias, through GELU when gelu = 1, in the 16-bit type of `precision` (PG_PREC_BF16 or
+ * PG_PREC_F16).  x[M][K] fp32: the live rows, M in 1 ... 32; the kernel runs on Mi = 16 or 32 rows, and x_pad[Mi - M][K] (NULL: zeros)
+ * is what the rows behind the live ones hold.  gamma[K], beta[K], bias[N] fp32; w[N][K] fp32, converted to the 16-bit type on the
+ * device.  N a multiple of 16; K = 256, 512, 768, 1024 or 1280.  out[out_rows][N], out_rows >= Mi: its contents are converted to the
+ * 16-bit type and uploaded first, the kernel writes its Mi rows, and all out_rows rows are returned widened -- whatever the kernel does
+ * not write keeps the caller's (16-bit representable) pattern.  nb: 16-feature blocks per workgroup, 1 or 2 (2: N a multiple of 32),
+ * 0 = the launcher's choice (PGIBBS_LN_SKINNY_NB, else 2 when N / 16 exceeds the CU count).  plan (NULL: not wanted): the text the
+ * launch recorded, "ln+skinny8w <N / (16 nb)>t".  All refusals are PG_ERR_INVALID and precede the device lookup. */
+int pg_dbg_gemm_ln(int device, int precision, const float* x, const float* x_pad, const float* gamma, const float* beta, float eps,
+                   const float* w, const float* bias, float* out, int out_rows, int M, int N, int K, int gelu, int nb, char* plan,
+                   int plan_bytes);
 /* times `iters` back-to-back launches of the GEMM on device-resident random bf16 operands (HIP events; M a multiple of 16,
  * of 64 above 256); variant 1 =
  * lockstep kernel, 2 = ping-pong kernel; epi: 0 bf16 out, 1 bf16+gelu, 2 fp32 residual, 3 fp32, 4 fp32+gelu */

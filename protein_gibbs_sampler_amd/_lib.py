@@ -111,6 +111,8 @@ SIGNATURES = [
     ("pg_dbg_gemm", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
     ("pg_dbg_gemm_v", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_char_p, c_int]),
+    ("pg_dbg_gemm_ln", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                               c_int, c_int, c_int, c_int, c_char_p, c_int]),
     ("pg_dbg_gemm_bench", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_double)]),
     ("pg_dbg_gemm_plan", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),
     ("pg_dbg_attention_plan", c_int, [c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),

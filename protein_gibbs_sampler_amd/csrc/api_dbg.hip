@@ -228,6 +228,50 @@ int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, con
   return out16 ? down16(d, precision, o16, dout, out, (int64_t)M * N) : d.down(out, dout, (size_t)M * N);
 }
 
+/* gemm_ln_skinny_kernel alone: out = LayerNorm(x; gamma, beta, eps) . w^T + bias (+ GELU) in the 16-bit type of `precision`.
+ * x[M][K] holds the live rows, M = 1 .. 32; the kernel runs on Mi = 16 or 32 rows, and x_pad[Mi - M][K] (NULL: zeros) is what the rows
+ * behind the live ones hold.  out[out_rows][N], out_rows >= Mi, is converted to 16 bits and uploaded first, the kernel writes its Mi
+ * rows into it, and all out_rows rows come back widened: what the kernel does not write keeps the caller's pattern.  nb: 16-feature
+ * blocks per workgroup, 0 = the launcher's choice.  plan (may be NULL): the text the launch recorded.  Everything is refused on the host
+ * before a device is looked for. */
+int pg_dbg_gemm_ln(int device, int precision, const float* x, const float* x_pad, const float* gamma, const float* beta, float eps,
+                   const float* w, const float* bias, float* out, int out_rows, int M, int N, int K, int gelu, int nb, char* plan,
+                   int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  int rc = dbg_precision("pg_dbg_gemm_ln", precision, false);
+  if (rc) return rc;
+  if (!x || !gamma || !beta || !w || !bias || !out || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument");
+  if (M < 1 || M > 32) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: M must be in 1 ... 32");
+  if (N < 16 || N % 16 || N > 65536) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: N must be a multiple of 16, at most 65536");
+  if (K < 256 || K % 256) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: K must be a multiple of 256");
+  if (K / 256 > 5) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: K / 256 must be in 1 ... 5");
+  if (gelu < 0 || gelu > 1 || nb < 0 || nb > 2) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: gelu is 0 or 1 and nb 0, 1 or 2");
+  if (nb == 2 && N % 32) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: two feature blocks per workgroup need N a multiple of 32");
+  if (!(eps >= 0.f)) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: eps must not be negative");
+  const int Mi = round_up(M, 16);
+  if (out_rows < Mi || out_rows > 4096) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: out_rows must be in Mi ... 4096");
+  if (!OPS(gemm_ln_skinny_ok, Mi, N, K)) return fail(PG_ERR_INVALID, "pg_dbg_gemm_ln: the kernel is switched off (PGIBBS_LN_SKINNY=0)");
+  Dbg d;
+  if ((rc = d.open(device))) return rc;
+  float* dx = d.alloc<float>((size_t)Mi * K);
+  d.put(dx, x, (size_t)M * K);
+  if (x_pad) d.put(dx + (size_t)M * K, x_pad, (size_t)(Mi - M) * K);
+  const float* dg = d.up(gamma, (size_t)K);
+  const float* dbt = d.up(beta, (size_t)K);
+  const float* dw = d.up(w, (size_t)N * K);
+  const float* db = d.up(bias, (size_t)N);
+  float* dout = d.up(out, (size_t)out_rows * N);      // the caller's pattern, fp32 on the way in and on the way out
+  bf16_t* bw = d.alloc<bf16_t>((size_t)N * K);
+  bf16_t* o16 = d.alloc<bf16_t>((size_t)out_rows * N);
+  if ((rc = d.check())) return rc;
+  if ((rc = to16(precision, dw, bw, (int64_t)N * K))) return rc;
+  if ((rc = to16(precision, dout, o16, (int64_t)out_rows * N))) return rc;
+  clear_noted_kernels();
+  if ((rc = OPS(launch_gemm_ln_skinny, nullptr, dx, K, dg, dbt, eps, bw, db, o16, Mi, N, K, K, N, gelu ? EPI_BF16_GELU : EPI_BF16, nb))) return rc;
+  dbg_noted_text(plan, plan_bytes);
+  return down16(d, precision, o16, dout, out, (int64_t)out_rows * N);
+}
+
 int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int iters, double* avg_ms) {
   if (!avg_ms || M % 16 || (M > 256 && M % 64) || N % 64 || K % 64 || iters < 1) return fail(PG_ERR_INVALID, "pg_dbg_gemm_bench: bad argument");
   if (variant == 90 && (K % 96 || (epi != EPI_F32 && epi != EPI_F32_RESID))) return fail(PG_ERR_INVALID, "variant 90: K = 3 x depth, fp32 epilogues");

@@ -855,11 +855,13 @@ bool gemm_ln_skinny_ok(int M, int N, int K) {
   return on && (M == 16 || M == 32) && N % 16 == 0 && K % 256 == 0 && K / 256 >= 1 && K / 256 <= 5;
 }
 int launch_gemm_ln_skinny(hipStream_t s, const float* X, int ldx, const float* gamma, const float* beta, float eps, const bf16_t* W,
-                          const float* bias, void* out, int M, int N, int K, int ldw, int ldo, int epi) {
+                          const float* bias, void* out, int M, int N, int K, int ldw, int ldo, int epi, int nb_force) {
   if (!gemm_ln_skinny_ok(M, N, K) || (epi != EPI_BF16 && epi != EPI_BF16_GELU)) return fail(1, "gemm_ln_skinny: shape / epilogue");
   const int nks = K / 256;
   static const int nb_env = env_int("PGIBBS_LN_SKINNY_NB", 0);
-  const int nb = nb_env ? nb_env : ((N / 16 > device_cu_count() && N % 32 == 0) ? 2 : 1);
+  // feature blocks per workgroup: the caller's (pg_dbg_gemm_ln), else the process switch, else by residency
+  const int nb = nb_force ? nb_force : nb_env ? nb_env : ((N / 16 > device_cu_count() && N % 32 == 0) ? 2 : 1);
+  if (nb < 1 || nb > 2) return fail(1, "gemm_ln_skinny: one or two feature blocks per workgroup");
   if (nb == 2 && N % 32) return fail(1, "gemm_ln_skinny: N must be a multiple of 32 for two feature blocks per workgroup");
   dim3 grid(N / (16 * nb)), block(512);
   note_kernel("ln+skinny8w", N / (16 * nb));

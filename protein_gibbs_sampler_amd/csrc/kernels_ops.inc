@@ -31,8 +31,10 @@ int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, co
 // weight-streaming GEMM with the preceding LayerNorm folded into its operand load (single chains; gemm_bf16.hip):
 // out bf16 = LayerNorm(x fp32 [M][K]; gamma, beta) . W^T + bias (+ GELU); M = 16 or 32 rows, K = 256 .. 1280 in steps of 256
 bool gemm_ln_skinny_ok(int M, int N, int K);
+// nb_force: 16-feature blocks per workgroup, 1 or 2 (2: N a multiple of 32); 0 = PGIBBS_LN_SKINNY_NB, else 2 when N / 16 workgroups
+// exceed the CU count
 int launch_gemm_ln_skinny(hipStream_t s, const float* X, int ldx, const float* gamma, const float* beta, float eps, const bf16_t* W,
-                          const float* bias, void* out, int M, int N, int K, int ldw, int ldo, int epi);
+                          const float* bias, void* out, int M, int N, int K, int ldw, int ldo, int epi, int nb_force = 0);
 // every layer of a single short chain (<= 32 token rows) as ONE persistent launch with device-wide barriers (chain_trunk.hip);
 // bit-identical with the per-layer launches it replaces.  M = padded token rows (16 / 32)
 bool chain_trunk_ok(int M, int d_model, int d_ffn, int n_heads);

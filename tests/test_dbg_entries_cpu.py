@@ -35,6 +35,8 @@ def _cases():
     return {
         "pg_dbg_gemm": ([0, BF16, x, w, b, _z(4, 64), 4, 64, 64, 0], 2, "pg_dbg_gemm: bad argument"),
         "pg_dbg_gemm_v": ([0, BF16, x, w, b, _z(4, 64), 4, 64, 64, 0, -1, -1, 4, None, 0], 2, "pg_dbg_gemm: bad argument"),
+        "pg_dbg_gemm_ln": ([0, BF16, _z(4, 256), None, _z(256), _z(256), 1e-5, _z(32, 256), _z(32), _z(16, 32), 16, 4, 32, 256, 0, 0, None, 0], 2,
+                           "pg_dbg_gemm_ln: bad argument"),
         "pg_dbg_gemm_bench": ([0, 16, 64, 64, 0, 1, 1, _dbl(1)], 7, "pg_dbg_gemm_bench: bad argument"),
         "pg_dbg_rowln_bench": ([0, 256, 128, 1, _dbl(5), _dbl(1)], 4, "pg_dbg_rowln_bench: bad argument"),
         "pg_dbg_qkv_attention_bench": ([0, 1, 32, 1, 1, _dbl(3), _dbl(1)], 5, "pg_dbg_qkv_attention_bench: T must be 32, 64, 128 or 256"),
@@ -106,7 +108,7 @@ def test_unknown_precision_mode_of_the_attention_plan():
     assert _call("pg_dbg_attention_plan", [0, 7, 1, 16, 1, 1, 64, 0, 0, 1, 0, 256, buf, 256]) == (_lib.PG_ERR_INVALID, "unknown precision mode")
 
 
-@pytest.mark.parametrize("name", ["pg_dbg_embed", "pg_dbg_layernorm_rows", "pg_dbg_gather_ln"])
+@pytest.mark.parametrize("name", ["pg_dbg_embed", "pg_dbg_layernorm_rows", "pg_dbg_gather_ln", "pg_dbg_gemm_ln"])
 def test_row_entries_take_16_bit_modes_only(name):
     args, _, _ = _cases()[name]
     assert _call(name, _with(args, 1, FP32)) == (_lib.PG_ERR_INVALID, name + ": precision must be PG_PREC_BF16 or PG_PREC_F16")
@@ -137,6 +139,29 @@ LATE = {
     "split_rows_unknown_form": ("pg_dbg_split_rows", {7: 4}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: form is weight (1) + through GELU (2)"),
     "split_rows_gelu_on_weight": ("pg_dbg_split_rows", {7: 3, 8: _z(4, 64)}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: GELU on a weight operand"),
     "split_rows_gelu_scale": ("pg_dbg_split_rows", {7: 2, 6: 0.37, 8: _z(4, 64)}, _lib.PG_ERR_INVALID, "pg_dbg_split_rows: the GELU form takes scale 1"),
+    "gemm_ln_gamma": ("pg_dbg_gemm_ln", {4: None}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument"),
+    "gemm_ln_beta": ("pg_dbg_gemm_ln", {5: None}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument"),
+    "gemm_ln_w": ("pg_dbg_gemm_ln", {7: None}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument"),
+    "gemm_ln_bias": ("pg_dbg_gemm_ln", {8: None}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument"),
+    "gemm_ln_out": ("pg_dbg_gemm_ln", {9: None}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument"),
+    "gemm_ln_plan_without_room": ("pg_dbg_gemm_ln", {16: ctypes.create_string_buffer(8), 17: 0}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: bad argument"),
+    "gemm_ln_unknown_precision": ("pg_dbg_gemm_ln", {1: 7}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: precision must be PG_PREC_BF16 or PG_PREC_F16"),
+    "gemm_ln_no_rows": ("pg_dbg_gemm_ln", {11: 0}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: M must be in 1 ... 32"),
+    "gemm_ln_33_rows": ("pg_dbg_gemm_ln", {11: 33}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: M must be in 1 ... 32"),
+    "gemm_ln_N_not_16": ("pg_dbg_gemm_ln", {12: 24}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: N must be a multiple of 16, at most 65536"),
+    "gemm_ln_N_zero": ("pg_dbg_gemm_ln", {12: 0}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: N must be a multiple of 16, at most 65536"),
+    "gemm_ln_K_not_256": ("pg_dbg_gemm_ln", {13: 320}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: K must be a multiple of 256"),
+    "gemm_ln_K_zero": ("pg_dbg_gemm_ln", {13: 0}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: K must be a multiple of 256"),
+    "gemm_ln_K_1536": ("pg_dbg_gemm_ln", {13: 1536}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: K / 256 must be in 1 ... 5"),
+    "gemm_ln_gelu": ("pg_dbg_gemm_ln", {14: 2}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: gelu is 0 or 1 and nb 0, 1 or 2"),
+    "gemm_ln_nb_3": ("pg_dbg_gemm_ln", {15: 3}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: gelu is 0 or 1 and nb 0, 1 or 2"),
+    "gemm_ln_nb_negative": ("pg_dbg_gemm_ln", {15: -1}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: gelu is 0 or 1 and nb 0, 1 or 2"),
+    "gemm_ln_nb_2_N_48": ("pg_dbg_gemm_ln", {12: 48, 15: 2}, _lib.PG_ERR_INVALID,
+                          "pg_dbg_gemm_ln: two feature blocks per workgroup need N a multiple of 32"),
+    "gemm_ln_eps": ("pg_dbg_gemm_ln", {6: -1e-5}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: eps must not be negative"),
+    "gemm_ln_eps_nan": ("pg_dbg_gemm_ln", {6: float("nan")}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: eps must not be negative"),
+    "gemm_ln_out_rows": ("pg_dbg_gemm_ln", {10: 15}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: out_rows must be in Mi ... 4096"),
+    "gemm_ln_out_rows_17_live": ("pg_dbg_gemm_ln", {10: 31, 11: 17}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: out_rows must be in Mi ... 4096"),
     "gemm_bench_variant_90": ("pg_dbg_gemm_bench", {5: 90}, _lib.PG_ERR_INVALID, "variant 90: K = 3 x depth, fp32 epilogues"),
 }
 
@@ -148,3 +173,18 @@ def test_shape_refusals_precede_the_device_lookup(case):
     for index, value in changes.items():
         args = _with(args, index, value)
     assert _call(name, args) == (code, message)
+
+
+def test_gemm_ln_is_refused_where_the_kernel_is_switched_off():
+    """PGIBBS_LN_SKINNY is read once per process: a child with it set to 0 gets the refusal, before the device lookup"""
+    import os
+    import subprocess
+    import sys
+    code = ("import numpy as np; from protein_gibbs_sampler_amd import _lib; z = lambda *s: np.zeros(s, np.float32); "
+            "a = [z(4, 256), None, z(256), z(256)], [z(32, 256), z(32), z(16, 32)]; p = lambda v: None if v is None else _lib.ptr(v); "
+            "rc = _lib.lib().pg_dbg_gemm_ln(0, 0, *map(p, a[0]), 1e-5, *map(p, a[1]), 16, 4, 32, 256, 0, 0, None, 0); "
+            "print(rc, _lib.lib().pg_last_error().decode())")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PGIBBS_LN_SKINNY="0", PYTHONPATH=root), cwd=root,
+                         capture_output=True, text=True, timeout=120)
+    assert out.stdout.strip() == "%d pg_dbg_gemm_ln: the kernel is switched off (PGIBBS_LN_SKINNY=0)" % _lib.PG_ERR_INVALID, out
