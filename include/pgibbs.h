@@ -240,6 +240,34 @@ int pg_msa_forward_logprobs(pg_engine*, const int32_t* tokens, int B, int R, int
 int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
                              const int32_t* d_row_map, const int32_t* d_targets, int64_t n_sel, int P, float* d_out);
 
+/* ---- masked-marginal substitution tables -------------------------------------------------------------
+ * The same forward, with the whole row kept instead of one entry of it: for every scored entry (s, p) -- addressed exactly as
+ * above: row_of / row_map, idx, entries < 0 skipped -- out[s][p][c] = log-probability of vocabulary token cols[c], c < n_cols, and
+ * optionally entropy[s][p] = -sum p log p in nats over the normalisation set.  Skipped entries yield zeros in both.
+ * Replaces ESM_MSA_sampler.probs_single as src/pgen/pgen_msa_seq_probs.py:31-45 calls it (the reference class no longer has that
+ * method) and the log_softmax of src/pgen/esm_sampler.py:340-345 before its gather.
+ *   norm PG_TABLE_NORM_VOCAB    log_softmax over all V logits, then the columns are picked (esm_sampler.py:340-345): the value at
+ *                               column c is bit-identical with what pg_*_forward_logprobs / pg_logprob_gather_device return for
+ *                               target cols[c] (one device function computes the maximum and the log-sum for both kernels)
+ *   norm PG_TABLE_NORM_COLUMNS  log_softmax over the n_cols selected logits only: the distribution generate_step draws from when
+ *                               temperature is None and top-k is off (Categorical(logits = valid logits), esm_sampler.py:8-45)
+ * V in 1..64, n_cols in 1..V, every column in 0..V-1, counts >= 0: anything else is PG_ERR_INVALID before a device is touched.
+ * The engine entries take cols as a HOST pointer and check its contents; pg_logprob_table_device takes a DEVICE pointer whose
+ * contents it cannot check -- the caller guarantees 0 <= d_cols[c] < V (a column outside reads as NaN, never out of bounds).
+ * pg_esm_forward_logprob_table / pg_msa_forward_logprob_table: the twins of pg_*_forward_logprobs (same checks, same forward, LM head
+ * at the scored rows only, PG_ERR_RANGE on non-finite logits before `out` is written).
+ * pg_logprob_table_device: the table kernel on a caller's device-resident full logits[n_rows][width][V] (plug-in models). */
+#define PG_TABLE_NORM_VOCAB 0
+#define PG_TABLE_NORM_COLUMNS 1
+int pg_logprob_table_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
+                            const int32_t* d_row_map, int64_t n_sel, int P, const int32_t* d_cols, int n_cols, int norm,
+                            float* d_out /* [n_sel][P][n_cols] */, float* d_entropy /* [n_sel][P] or NULL */);
+int pg_esm_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
+                                 int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy_or_null);
+int pg_msa_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+                                 const int32_t* idx, int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out,
+                                 float* entropy_or_null);
+
 /* ---- stand-alone data-parallel ends of the iteration --------------------------------------
  * For plug-in models whose forward is not this engine (the reference accepts any object with
  * .model/.alphabet/.batch_converter, esm_sampler.py:54-58): logits come from the caller's model,

@@ -217,3 +217,40 @@ def score_positions(model_callable, tokens_i64, row_of, idx, targets, device):
                                                        ctypes.c_void_p(res.data_ptr())))
         torch.cuda.synchronize(dev)
     return res.cpu().numpy()
+
+
+def score_table(model_callable, tokens_i64, row_of, idx, cols, device, normalise="vocab", want_entropy=False):
+    """The table form of score_positions: out[s, p, c] = log-probability of token cols[c] at (token row row_of[s], position
+    idx[s][p]), normalised over the vocabulary ("vocab") or over the selected columns ("columns"); idx < 0 -> zeros.  Returns
+    (out float32 [n_sel, P, n_cols], entropy float32 [n_sel, P] or None).
+    Engine models: one native call.  Plug-in models: the caller's forward, then the HIP table kernel `pg_logprob_table_device` on
+    its device-resident logits."""
+    import torch
+    from .engine import NativeMaskedLM
+    if normalise not in _lib.TABLE_NORMS:
+        raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
+    row_of = np.ascontiguousarray(row_of, dtype=np.int32)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    if isinstance(model_callable, NativeMaskedLM):
+        return model_callable.forward_logprob_table(tokens_i64.numpy() if hasattr(tokens_i64, "numpy") else tokens_i64, row_of, idx,
+                                                    cols, normalise, want_entropy)
+    if not torch.cuda.is_available():
+        raise RuntimeError("no MI355X visible: masked-marginal tables have no CPU implementation in this package")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        out = model_callable(tokens_i64.to(dev))["logits"].to(device=dev, dtype=torch.float32).contiguous()
+        width, V = out.shape[-2], out.shape[-1]
+        if len(cols) and (cols.min() < 0 or cols.max() >= V):
+            raise ValueError("score_table: a column lies outside the model's vocabulary of %d" % V)
+        n_rows = out.numel() // (width * V)
+        d_idx, d_row, d_cols = (torch.from_numpy(a).to(dev) for a in (idx, row_of, cols))
+        res = torch.zeros(idx.shape + (len(cols),), dtype=torch.float32, device=dev)
+        ent = torch.zeros(idx.shape, dtype=torch.float32, device=dev) if want_entropy else None
+        _lib.check(_lib.lib().pg_logprob_table_device(_current_stream_ptr(dev), ctypes.c_void_p(out.data_ptr()), n_rows, width, V,
+                                                      ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(d_row.data_ptr()),
+                                                      idx.shape[0], idx.shape[1], ctypes.c_void_p(d_cols.data_ptr()), len(cols),
+                                                      _lib.TABLE_NORMS[normalise],
+                                                      ctypes.c_void_p(res.data_ptr()), ctypes.c_void_p(ent.data_ptr()) if want_entropy else None))
+        torch.cuda.synchronize(dev)
+    return res.cpu().numpy(), (ent.cpu().numpy() if want_entropy else None)

@@ -19,6 +19,8 @@ PG_ERR_INVALID, PG_ERR_HIP, PG_ERR_NO_DEVICE, PG_ERR_WEIGHTS, PG_ERR_UNSUPPORTED
 PG_ARCH_ESM1B, PG_ARCH_MSA1B, PG_ARCH_ESM1, PG_ARCH_ESM2 = 1, 2, 3, 4
 PG_COMM_ID_BYTES = 128
 PG_PREC_BF16, PG_PREC_FP32, PG_PREC_F16 = 0, 1, 2
+PG_TABLE_NORM_VOCAB, PG_TABLE_NORM_COLUMNS = 0, 1
+TABLE_NORMS = {"vocab": PG_TABLE_NORM_VOCAB, "columns": PG_TABLE_NORM_COLUMNS}
 INT32_MAX = 2**31 - 1
 
 
@@ -93,6 +95,12 @@ SIGNATURES = [
                                         c_void_p]),
     ("pg_logprob_gather_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                          c_void_p]),
+    ("pg_logprob_table_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                        c_int, c_void_p, c_void_p]),
+    ("pg_esm_forward_logprob_table", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                             c_void_p, c_void_p]),
+    ("pg_msa_forward_logprob_table", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                             c_int, c_void_p, c_void_p]),
     ("pg_mask_scatter_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int]),
     ("pg_sample_writeback_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                            c_int, POINTER(SampleParams), c_int, c_void_p]),

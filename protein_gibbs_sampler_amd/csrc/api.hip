@@ -426,6 +426,84 @@ int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows
   return launch_logprob_gather((hipStream_t)stream, d_logits, V, 0, width, d_idx, d_row_map, d_targets, n_sel, P, d_out);
 }
 
+// ---- masked-marginal substitution tables: forward_logprobs with the table kernel in the gather's place ----------------------
+// out[s][P][n_cols] = log-probability of token cols[c] at (token row row_of[s], position idx[s][p]), entropy[s][P] optional
+static int check_table_cols(const int32_t* cols, int n_cols, int V) {
+  for (int c = 0; c < n_cols; ++c)
+    if (cols[c] < 0 || cols[c] >= V)
+      return fail(PG_ERR_INVALID, "logprob table: column " + std::to_string(cols[c]) + " is outside the vocabulary of " + std::to_string(V));
+  return PG_OK;
+}
+
+static int forward_logprob_table(Engine& e, const int32_t* tokens, int B, int R, int C, const int32_t* row_of, const int32_t* idx,
+                                 int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy) {
+  DeviceGuard g(e.device);
+  const int V = e.cfg.vocab;
+  const int64_t M = (int64_t)B * R * C;
+  const int64_t n = (int64_t)n_sel * P;
+  int rc;
+  if ((rc = check_logprob_table_args(V, n_cols, norm, n_sel, P)) || (rc = check_table_cols(cols, n_cols, V))) return rc;
+  if (n == 0 || B == 0) return PG_OK;
+  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
+  if ((rc = e.d_idx.ensure((size_t)n * 4, e.stream)) || (rc = e.d_samp_tok.ensure((size_t)n_cols * 4, e.stream))) return rc;
+  if ((rc = e.d_rowmap.ensure((size_t)n_sel * 4, e.stream))) return rc;
+  // d_samp_logits: the table, then the entropies
+  if ((rc = e.logits.ensure((size_t)n * V * 4, e.stream)) || (rc = e.d_samp_logits.ensure((size_t)n * (n_cols + 1) * 4, e.stream))) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] >= C) return fail(PG_ERR_INVALID, "logprob table: index out of range");
+  for (int i = 0; i < n_sel; ++i)
+    if (row_of[i] < 0 || row_of[i] >= B * R) return fail(PG_ERR_INVALID, "logprob table: row out of range");
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
+  PG_HIP(hipMemcpyAsync(e.d_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
+  PG_HIP(hipMemcpyAsync(e.d_samp_tok.p, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e.stream));
+  PG_HIP(hipMemcpyAsync(e.d_rowmap.p, row_of, (size_t)n_sel * 4, hipMemcpyHostToDevice, e.stream));
+  {
+    PadFlag pad(e, tokens, (size_t)M);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
+  }
+  if (rc) return rc;
+  if ((rc = e.head(e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(), P, C, n, e.logits.as<float>()))) return rc;
+  float* d_out = e.d_samp_logits.as<float>();
+  float* d_ent = entropy ? d_out + (size_t)n * n_cols : nullptr;
+  if ((rc = launch_logprob_table(e.stream, e.logits.as<float>(), V, 1, C, e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(),
+                                 e.d_samp_tok.as<int32_t>(), n_cols, norm, n_sel, P, d_out, d_ent, e.range_err))) return rc;
+  // the results wait on the device until the range check has passed: a PG_ERR_RANGE call leaves the caller's buffers alone
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.finish_check())) return rc;
+  PG_HIP(hipMemcpyAsync(out, d_out, (size_t)n * n_cols * 4, hipMemcpyDeviceToHost, e.stream));
+  if (entropy) PG_HIP(hipMemcpyAsync(entropy, d_ent, (size_t)n * 4, hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  return PG_OK;
+}
+
+int pg_esm_forward_logprob_table(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
+                                 int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy) {
+  if (!h || !tokens || !row_of || !idx || !cols || !out) return fail(PG_ERR_INVALID, "pg_esm_forward_logprob_table: null argument");
+  if (!h->e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
+  if (B < 0 || T < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
+  if (T > h->e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprob_table(h->e, tokens, B, 1, T, row_of, idx, n_sel, P, cols, n_cols, norm, out, entropy));
+}
+
+int pg_msa_forward_logprob_table(pg_engine* h, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+                                 const int32_t* idx, int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out,
+                                 float* entropy) {
+  if (!h || !tokens || !row_of || !idx || !cols || !out) return fail(PG_ERR_INVALID, "pg_msa_forward_logprob_table: null argument");
+  if (h->e.cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
+  if (B < 0 || R < 1 || C < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
+  return forward_logprob_table(h->e, tokens, B, R, C, row_of, idx, n_sel, P, cols, n_cols, norm, out, entropy);
+}
+
+int pg_logprob_table_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
+                            const int32_t* d_row_map, int64_t n_sel, int P, const int32_t* d_cols, int n_cols, int norm,
+                            float* d_out, float* d_entropy) {
+  if (!d_logits || !d_idx || !d_cols || !d_out) return fail(PG_ERR_INVALID, "pg_logprob_table_device: null argument");
+  if (int rc = check_logprob_table_args(V, n_cols, norm, n_sel, P)) return rc;
+  if (n_rows < 0 || width < 1) return fail(PG_ERR_INVALID, "bad shape");
+  return launch_logprob_table((hipStream_t)stream, d_logits, V, 0, width, d_idx, d_row_map, d_cols, n_cols, norm, n_sel, P, d_out,
+                              d_entropy);
+}
+
 // ---- stand-alone ends of the iteration ---------------------------------------------------------
 int pg_mask_scatter_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const int32_t* d_idx,
                            const int32_t* d_row_map, int64_t n_sel, int P, int mask_idx) {

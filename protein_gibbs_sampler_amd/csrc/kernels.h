@@ -66,6 +66,12 @@ int launch_graph_state(hipStream_t st, int32_t* d_iter, int iteration, const pg_
 int launch_logprob_gather(hipStream_t st, const float* logits, int V, int compact, int width, const int32_t* idx,
                           const int32_t* row_map, const int32_t* targets, int64_t n_sel, int P, float* out,
                           unsigned* nonfinite = nullptr);     // nonfinite: device-visible word set to 1 when a logit row holds NaN / inf
+// the table form of the gather: out[n_sel][P][n_cols], entropy[n_sel][P] (may be null); cols[n_cols] is device-resident.
+// check_logprob_table_args is the launcher's own host-side refusal, for callers that have work to queue before the launch
+int check_logprob_table_args(int V, int n_cols, int norm, int64_t n_sel, int P);
+int launch_logprob_table(hipStream_t st, const float* logits, int V, int compact, int width, const int32_t* idx,
+                         const int32_t* row_map, const int32_t* cols, int n_cols, int norm, int64_t n_sel, int P, float* out,
+                         float* entropy, unsigned* nonfinite = nullptr);
 int launch_mask_scatter(hipStream_t st, int32_t* tokens, int width, const int32_t* idx, const int32_t* row_map,
                         int64_t n_sel, int P, int mask_idx, const int32_t* d_iter = nullptr);
 int launch_sample_writeback(hipStream_t st, int32_t* tokens, int width, const float* logits, int V, int compact,

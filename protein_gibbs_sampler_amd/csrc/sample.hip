@@ -173,6 +173,18 @@ __global__ __launch_bounds__(256) void mask_scatter_kernel(int32_t* __restrict__
   tokens[trow * width + (raw & 0x3fffffff)] = mask_idx;
 }
 
+// The two numbers a log_softmax needs: mx = the maximum of at(0) ... at(n - 1), logsum = logf(sum of expf(at(v) - mx)).  The gather
+// kernel and the table kernel both call this, so log p = x - mx - logsum carries the same bits in both (kernels that must agree
+// bit for bit call the same function, in this translation unit and under its -ffp-contract=off).
+template <typename At>
+__device__ __forceinline__ void row_max_logsum(At at, int n, float& mx, float& logsum) {
+  mx = at(0);
+  for (int v = 1; v < n; ++v) mx = fmaxf(mx, at(v));
+  float sum = 0.f;
+  for (int v = 0; v < n; ++v) sum += expf(at(v) - mx);
+  logsum = logf(sum);
+}
+
 // log p(target | context) at the selected rows: log_softmax over the FULL vocabulary then gather
 // (== torch.log_softmax(logits, -1)[..., target], /root/reference/src/pgen/esm_sampler.py:340-345,
 //  esm_msa_sampler.py:403-410).  One thread per selected entry; V <= 64 floats per row.
@@ -188,11 +200,9 @@ __global__ __launch_bounds__(256) void logprob_gather_kernel(const float* __rest
   const int64_t s = i / P;
   const int64_t trow = row_map ? (int64_t)row_map[s] : s;
   const float* row = compact ? logits + (size_t)i * V : logits + ((size_t)trow * width + pos) * V;
-  float mx = row[0];
-  for (int v = 1; v < V; ++v) mx = fmaxf(mx, row[v]);
-  float sum = 0.f;
-  for (int v = 0; v < V; ++v) sum += expf(row[v] - mx);
-  const float lp = row[targets[i]] - mx - logf(sum);
+  float mx, logsum;
+  row_max_logsum([row](int v) { return row[v]; }, V, mx, logsum);
+  const float lp = row[targets[i]] - mx - logsum;
   if (nonfinite && !(fabsf(mx) <= 3.0e38f)) *nonfinite = 1u;      // NaN or inf anywhere in the row ends up in mx or in lp
   if (nonfinite && lp != lp) *nonfinite = 1u;
   out[i] = lp;
@@ -204,6 +214,84 @@ int launch_logprob_gather(hipStream_t st, const float* logits, int V, int compac
   if (n == 0) return 0;
   hipLaunchKernelGGL(logprob_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, logits, V, compact, width, idx,
                      row_map, targets, n_sel, P, out, nonfinite);
+  PG_HIP(hipGetLastError());
+  return 0;
+}
+
+// The whole row instead of one entry of it: out[i][c] = log p(cols[c]) for c < n_cols, and optionally the entropy in nats,
+// -sum p log p over the normalisation set (== pgen_msa_seq_probs.py:31-45 of the reference, whose probs_single no longer exists, and
+// esm_sampler.py:340-345 before its gather).  norm PG_TABLE_NORM_VOCAB: log_softmax over all V logits, then the columns are picked --
+// the value at a column is the gather kernel's for that target, bit for bit.  PG_TABLE_NORM_COLUMNS: log_softmax over the n_cols
+// selected logits only (Categorical(logits = valid logits), what generate_step draws from without temperature or top-k).
+// Addressing, skipped entries (zeros) and the nonfinite word are the gather kernel's.  One thread per scored entry: at most a few
+// tens of thousands of entries of <= 64 floats.  A column outside 0 .. V-1 (the engine entries refuse it on the host) reads as NaN.
+__global__ __launch_bounds__(256) void logprob_table_kernel(const float* __restrict__ logits, int V, int compact, int width,
+                                                           const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ row_map,
+                                                           const int32_t* __restrict__ cols, int n_cols, int norm, int64_t n_sel,
+                                                           int P, float* __restrict__ out, float* __restrict__ entropy,
+                                                           unsigned* nonfinite) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_sel * P) return;
+  float* o = out + (size_t)i * n_cols;
+  const int pos = idx[i];
+  if (pos < 0 || pos >= width) {
+    for (int c = 0; c < n_cols; ++c) o[c] = 0.f;
+    if (entropy) entropy[i] = 0.f;
+    return;
+  }
+  const int64_t s = i / P;
+  const int64_t trow = row_map ? (int64_t)row_map[s] : s;
+  const float* row = compact ? logits + (size_t)i * V : logits + ((size_t)trow * width + pos) * V;
+  auto at_col = [row, cols, V](int c) {
+    const int v = cols[c];
+    return (unsigned)v < (unsigned)V ? row[v] : __int_as_float(0x7fc00000);
+  };
+  auto at_row = [row](int v) { return row[v]; };
+  const bool over_cols = norm == PG_TABLE_NORM_COLUMNS;
+  float mx, logsum;
+  if (over_cols) row_max_logsum(at_col, n_cols, mx, logsum);
+  else row_max_logsum(at_row, V, mx, logsum);
+  bool bad = !(fabsf(mx) <= 3.0e38f);                // as the gather kernel: NaN or inf in the row ends up in mx or in a log p
+  if (over_cols)                                     // ... of which this form reads only the selected ones: look at the others too
+    for (int v = 0; v < V; ++v) bad |= !(fabsf(row[v]) <= 3.0e38f);
+  for (int c = 0; c < n_cols; ++c) {
+    const float lp = at_col(c) - mx - logsum;
+    bad |= lp != lp;
+    o[c] = lp;
+  }
+  if (entropy) {
+    float h = 0.f;
+    const int n = over_cols ? n_cols : V;
+    for (int v = 0; v < n; ++v) {
+      const float lp = (over_cols ? at_col(v) : at_row(v)) - mx - logsum;
+      const float pv = expf(lp);
+      if (pv > 0.f) h -= pv * lp;                     // p log p -> 0 as p -> 0
+    }
+    bad |= h != h;
+    entropy[i] = h;
+  }
+  if (nonfinite && bad) *nonfinite = 1u;
+}
+
+int check_logprob_table_args(int V, int n_cols, int norm, int64_t n_sel, int P) {
+  if (V < 1 || V > 64) return fail(1, "logprob table: V must be in 1..64");
+  if (n_cols < 1 || n_cols > V) return fail(1, "logprob table: n_cols must be in 1..V");
+  if (norm != PG_TABLE_NORM_VOCAB && norm != PG_TABLE_NORM_COLUMNS)
+    return fail(1, "logprob table: unknown norm (PG_TABLE_NORM_VOCAB or PG_TABLE_NORM_COLUMNS)");
+  if (n_sel < 0 || P < 0) return fail(1, "logprob table: negative count");
+  return 0;
+}
+
+int launch_logprob_table(hipStream_t st, const float* logits, int V, int compact, int width, const int32_t* idx,
+                         const int32_t* row_map, const int32_t* cols, int n_cols, int norm, int64_t n_sel, int P, float* out,
+                         float* entropy, unsigned* nonfinite) {
+  if (int rc = check_logprob_table_args(V, n_cols, norm, n_sel, P)) return rc;
+  const int64_t n = n_sel * P;
+  if (n == 0) return 0;
+  if (!logits || !idx || !cols || !out) return fail(1, "logprob table: null pointer");
+  hipLaunchKernelGGL(logprob_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, logits, V, compact, width, idx,
+                     row_map, cols, n_cols, norm, n_sel, P, out, entropy, nonfinite);
   PG_HIP(hipGetLastError());
   return 0;
 }

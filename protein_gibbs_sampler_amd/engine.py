@@ -295,6 +295,35 @@ class NativeMaskedLM:
                                                                          _lib.ptr(targets), n_sel, P, _lib.ptr(out))), tok)
         return out
 
+    def forward_logprob_table(self, tokens, row_of, idx, cols, normalise="vocab", want_entropy=False):
+        """The masked-marginal table (C ABI pg_*_forward_logprob_table): out[s, p, c] = log-probability of token cols[c] at position
+        idx[s, p] of token row row_of[s]; normalise "vocab" (log_softmax over the vocabulary, then the columns: the value at a column
+        is forward_logprobs' for that target, bit for bit) or "columns" (log_softmax over the selected logits only).  Entries with
+        idx < 0 are zeros.  Returns (out float32 [n_sel, P, n_cols], entropy float32 [n_sel, P] in nats or None)."""
+        if normalise not in _lib.TABLE_NORMS:
+            raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
+        norm = _lib.TABLE_NORMS[normalise]
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        row_of = np.ascontiguousarray(row_of, dtype=np.int32)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        n_sel, P = idx.shape
+        n_cols = len(cols)
+        out = np.zeros((n_sel, P, n_cols), dtype=np.float32)
+        ent = np.zeros((n_sel, P), dtype=np.float32) if want_entropy else None
+        ent_p = _lib.ptr(ent) if want_entropy else None
+        L = _lib.lib()
+        if self.is_msa:
+            B, R, C = tok.shape
+            self._check_fp16_msa_shape(tok)
+            self._guarded(lambda h: _lib.check(L.pg_msa_forward_logprob_table(h, _lib.ptr(tok), B, R, C, _lib.ptr(row_of), _lib.ptr(idx),
+                                                                              n_sel, P, _lib.ptr(cols), n_cols, norm, _lib.ptr(out), ent_p)), tok)
+        else:
+            B, T = tok.shape
+            self._guarded(lambda h: _lib.check(L.pg_esm_forward_logprob_table(h, _lib.ptr(tok), B, T, _lib.ptr(row_of), _lib.ptr(idx),
+                                                                              n_sel, P, _lib.ptr(cols), n_cols, norm, _lib.ptr(out), ent_p)), tok)
+        return out, ent
+
     # ---- whole Gibbs loops -----------------------------------------------------------------
     def gibbs_run(self, tokens, target_idx, params, want_logits=False, want_tokens=False):
         """tokens int32 [B,T] or [B,R,C] (modified in place); target_idx int32 [iters, B, P] / [iters, B, R, P]."""

@@ -301,6 +301,28 @@ class ESM_MSA_sampler():
         columns around it under fair-esm's padding semantics (and its tied row attention's 1/sqrt(R) from the padded depth); the
         same here, through the engine's <pad> handling."""
         self._require_gpu("log_likelihood_batch")
+        for group in self._scoring_groups(msa_list, target_index, with_masking, count_gaps, mask_distance, batch_size):
+            lps = [_gibbs.score_positions(self.model.model, tokens, row_of, idx, tgt, self.device)
+                   for tokens, row_of, idx, tgt in group["calls"]]
+            for item in group["items"]:
+                likelihood_sum = np.float32(0.0)
+                likelihood_list = []
+                for call, sel, pos in item["rows"]:
+                    for p_ in range(len(pos)):
+                        likelihood_sum = np.float32(likelihood_sum + lps[call][sel, p_])
+                        likelihood_list.append(float(lps[call][sel, p_]))
+                if with_masking:
+                    assert len(likelihood_list) == item["denom"]
+                if item["denom"] == 0:                   # all-gap target row with count_gaps=False: the reference's 0.0 / 0
+                    raise ZeroDivisionError("float division by zero")
+                yield (float(likelihood_sum / np.float32(item["denom"])), likelihood_list)
+
+    def _scoring_groups(self, msa_list, target_index, with_masking, count_gaps, mask_distance, batch_size):
+        """What log_likelihood_batch and masked_marginals_batch run, as groups of forwards: `calls` = the (tokens, row_of, idx, tgt)
+        of every forward of the group -- idx / tgt [n_sel, P]: scored token positions (-1 padded) and the original tokens there --
+        and `items` = the MSAs those forwards score completely, each with `denom` (its scored positions) and `rows` = (call, selected
+        row, token positions) in the order the reference appends them.  Unmasked: one group per `batch_size` MSAs of the padded
+        list; masked: one group per MSA, its strided-mask copies in chunks of `batch_size`."""
         gap_tokens = {self.model.alphabet.get_idx(x) for x in ESM_MSA_GAP_CHARACTERS}
         if batch_size is None:
             batch_size = len(msa_list)
@@ -336,18 +358,12 @@ class ESM_MSA_sampler():
                     idx[i, :len(pos)] = pos
                     tgt[i, :len(pos)] = orig[i][pos]
                 row_of = np.arange(nb) * R + np.asarray(rows_of[batch_start:batch_start + nb])
-                lp = _gibbs.score_positions(self.model.model, chunk, row_of, idx, tgt, self.device)
+                items = []
                 for i in range(nb):
                     msa = msa_list[batch_start + i]
                     denom = len(msa[target_index]) - (0 if count_gaps else sum(msa[target_index].count(g) for g in ESM_MSA_GAP_CHARACTERS))
-                    likelihood_sum = np.float32(0.0)
-                    likelihood_list = []
-                    for p_ in range(len(pos_of[i])):
-                        likelihood_sum = np.float32(likelihood_sum + lp[i, p_])
-                        likelihood_list.append(float(lp[i, p_]))
-                    if denom == 0:                       # all-gap target row with count_gaps=False: the reference's 0.0 / 0
-                        raise ZeroDivisionError("float division by zero")
-                    yield (float(likelihood_sum / np.float32(denom)), likelihood_list)
+                    items.append(dict(denom=denom, rows=[(0, i, pos_of[i])], start=range_start))
+                yield dict(calls=[(chunk, row_of, idx, tgt)], items=items)
             return
         for msa in msa_list:
             reformatted = [(str(i), self.clean_seed_seq(seq)) for i, seq in enumerate(msa)]
@@ -371,18 +387,88 @@ class ESM_MSA_sampler():
             for i, pos in enumerate(pos_of):
                 idx[i, :len(pos)] = pos
                 tgt[i, :len(pos)] = orig[pos]
-            likelihood_sum = np.float32(0.0)
-            likelihood_list = []
+            calls, rows = [], []
             for batch_start in range(0, n, max(1, batch_size)):
                 sl = slice(batch_start, batch_start + max(1, batch_size))
                 nb = copies[sl].shape[0]
                 row_of = np.arange(nb) * R + tr
-                lp = _gibbs.score_positions(self.model.model, copies[sl], row_of, idx[sl], tgt[sl], self.device)
+                rows += [(len(calls), i, pos_of[batch_start + i]) for i in range(nb)]
+                calls.append((copies[sl], row_of, idx[sl], tgt[sl]))
+            yield dict(calls=calls, items=[dict(denom=denom, rows=rows, start=range_start)])
+
+    # ---- masked-marginal substitution tables ------------------------------------------------------------
+    def masked_marginals_batch(self, msa_list, target_index=0, with_masking=True, count_gaps=False, mask_distance=float("inf"),
+                               batch_size=1, normalise="vocab"):
+        """The twin of log_likelihood_batch that keeps the whole row: for the row `target_index` of every MSA yields
+        (logp float32 [n, 21], entropy float32 [n] in nats, positions, toks) -- one table row per scored position, `positions`
+        their 0-based residue indices in ascending order (gap positions of the target row are left out unless count_gaps), columns
+        = self.toks (the 21 symbols of self.valid_aa_idx, in that order).  Same copies and the same forwards as
+        log_likelihood_batch; normalise "vocab" (logp at a position's own symbol is bit for bit what log_likelihood_batch lists
+        there) or "columns" (over the 21 symbols only)."""
+        self._require_gpu("masked_marginals_batch")
+        if normalise not in _lib.TABLE_NORMS:
+            raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
+        for group in self._scoring_groups(msa_list, target_index, with_masking, count_gaps, mask_distance, batch_size):
+            tabs = [_gibbs.score_table(self.model.model, tokens, row_of, idx, self.valid_aa_idx, self.device, normalise, want_entropy=True)
+                    for tokens, row_of, idx, _ in group["calls"]]
+            for item in group["items"]:
+                where = sorted((p_, call, sel, j) for call, sel, pos in item["rows"] for j, p_ in enumerate(pos))
+                logp = np.zeros((len(where), len(self.valid_aa_idx)), dtype=np.float32)
+                entropy = np.zeros(len(where), dtype=np.float32)
+                for k, (_, call, sel, j) in enumerate(where):
+                    logp[k] = tabs[call][0][sel, j]
+                    entropy[k] = tabs[call][1][sel, j]
+                yield logp, entropy, [w[0] - item["start"] for w in where], list(self.toks)
+
+    def _probs_single_bins(self, sequence_length, steps):
+        """The mask bins of probs_single: the target row's token positions 1 .. L shuffled with random.shuffle on the interpreter's
+        global RNG (CPython-exact, consuming it as generate_single's one pass does) and split by `partition`; None = one per position."""
+        from . import pyrandom
+        positions = list(range(1, sequence_length + 1))
+        pyrandom.global_shuffle(positions)
+        return partition(positions, sequence_length if steps is None else steps)
+
+    def probs_single(self, msa, steps=None, target_index=-1, show_progress_bar=True, batch_size=None):
+        """The call the reference's pgen_msa_seq_probs.py:31 makes (its ESM_MSA_sampler no longer has the method): the probability
+        of every symbol at every position of row `target_index`, by masking.  The row's positions are shuffled and split into
+        `steps` bins (None: one bin per position) as generate_single does; for each bin the row is masked at the bin's positions,
+        the model runs, and the distribution generate_step would draw from there (softmax over the 21 valid symbols, no
+        temperature, no top-k) is read at those positions.  Bins never see each other's results, so all bins of a call are ONE
+        batched job of `steps` alignments, run `batch_size` at a time (None: all at once; the result does not depend on it).
+        Returns (probs float32 [len(toks), L], toks)."""
+        self._require_gpu("probs_single")
+        sequence_length = len(msa[0])
+        reformatted = [(str(i), self.clean_seed_seq(seq)) for i, seq in enumerate(msa)]
+        _, _, one = self.model.batch_converter(reformatted)               # [1, R, C]
+        R = one.shape[1]
+        if not -R <= target_index < R:
+            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (target_index, R))
+        bins = self._probs_single_bins(sequence_length, steps)
+        tr = target_index % R
+        n = len(bins)
+        copies = one.repeat(n, 1, 1)
+        P = max(len(b) for b in bins)
+        idx = np.full((n, P), -1, dtype=np.int32)
+        for i, b in enumerate(bins):
+            copies[i, tr, b] = self.model.alphabet.mask_idx
+            idx[i, :len(b)] = b
+        probs = np.zeros((len(self.toks), sequence_length), dtype=np.float32)
+        step = n if batch_size is None else max(1, batch_size)
+        native = isinstance(self.model.model, NativeMaskedLM)
+        if native:
+            # every chunk is a shard of the one n-alignment job: kernel choices that change a summation order are taken on the
+            # job's size, so the table does not depend on batch_size (pgibbs.h pg_engine_set_job_items)
+            self.model.model.set_job_items(n)
+        try:
+            for b0 in trange(0, n, step, disable=(not show_progress_bar)):
+                sl = slice(b0, b0 + step)
+                nb = copies[sl].shape[0]
+                tab, _ = _gibbs.score_table(self.model.model, copies[sl], np.arange(nb) * R + tr, idx[sl], self.valid_aa_idx,
+                                            self.device, "columns")
                 for i in range(nb):
-                    for p in range(len(pos_of[batch_start + i])):
-                        likelihood_sum = np.float32(likelihood_sum + lp[i, p])
-                        likelihood_list.append(float(lp[i, p]))
-            assert len(likelihood_list) == denom
-            if denom == 0:
-                raise ZeroDivisionError("float division by zero")
-            yield (float(likelihood_sum / np.float32(denom)), likelihood_list)
+                    b = np.asarray(bins[b0 + i], dtype=np.int64)
+                    probs[:, b - 1] = np.exp(tab[i, :len(b)]).T
+        finally:
+            if native:
+                self.model.model.set_job_items(0)
+        return probs, list(self.toks)

@@ -28,6 +28,19 @@ from .engine import NativeMaskedLM
 ESM_ALLOWED_AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"
 
 _step_counter = [0]
+_MUTATION = re.compile(r"^([A-Za-z])([0-9]+)([A-Za-z])$")
+
+
+def parse_mutation(mutation):
+    """"A24G" -> ("A", 23, "G"): wild-type residue, 0-based position (the text counts from 1), mutant residue."""
+    m = _MUTATION.match(mutation.strip()) if isinstance(mutation, str) else None
+    if not m or int(m.group(2)) < 1:
+        raise ValueError("Invalid mutation %r: expected <wild type><1-based position><mutant>, such as 'A24G'" % (mutation,))
+    wt, mut = m.group(1).upper(), m.group(3).upper()
+    for aa in (wt, mut):
+        if aa not in ESM_ALLOWED_AMINO_ACIDS:
+            raise ValueError("Invalid mutation %r: %r is not one of %s" % (mutation, aa, ESM_ALLOWED_AMINO_ACIDS))
+    return wt, int(m.group(2)) - 1, mut
 
 
 def _device_of(t):
@@ -245,6 +258,24 @@ class ESM_sampler():
         if not self.cuda:
             raise RuntimeError("ESM_sampler.log_likelihood_batch needs device 'gpu'/'cuda:N' on an MI355X: "
                                "there is no CPU implementation")
+        for job in self._masked_copy_jobs(seq_list, with_masking, mask_distance, batch_size):
+            likelihood_sum = np.float32(0.0)
+            likelihood_list = []
+            for sl, first in job["chunks"]:
+                nb = job["copies"][sl].shape[0]
+                lp = _gibbs.score_positions(self.model.model, job["copies"][sl], np.arange(nb), job["idx"][sl], job["tgt"][sl], self.device)
+                for i in range(nb):
+                    # the reference appends in (copy, position) order; positions of one copy ascend (stride n)
+                    for p in range(len(job["pos_of"][first + i])):
+                        likelihood_sum = np.float32(likelihood_sum + lp[i, p])
+                        likelihood_list.append(float(lp[i, p]))
+            yield (float(likelihood_sum / np.float32(len(job["seq"]))), likelihood_list)
+
+    def _masked_copy_jobs(self, seq_list, with_masking, mask_distance, batch_size):
+        """What log_likelihood_batch and masked_marginals_batch run, one job per sequence: `copies` [n, T] (copy i masked at every
+        n-th position starting at i, n = min(mask_distance, len); one unmasked copy without masking), `pos_of[i]` the token positions
+        read from copy i, `idx` / `tgt` [n, P] the same positions (-1 padded) and the original tokens there, `chunks` the
+        (slice, first copy) of every forward of `batch_size` copies, `start` the token position of residue 0."""
         n_batches = len(seq_list)
         if batch_size is None:
             batch_size = n_batches
@@ -279,17 +310,57 @@ class ESM_sampler():
             for i, pos in enumerate(pos_of):
                 idx[i, :len(pos)] = pos
                 tgt[i, :len(pos)] = old_toks[seq_idx, pos]
-            likelihood_sum = np.float32(0.0)
-            likelihood_list = []
-            for batch_start in range(0, n, max(1, batch_size)):
-                sl = slice(batch_start, batch_start + max(1, batch_size))
-                nb = copies[sl].shape[0]
-                lp = _gibbs.score_positions(self.model.model, copies[sl], np.arange(nb), idx[sl], tgt[sl], self.device)
+            step = max(1, batch_size)
+            chunks = [(slice(b0, b0 + step), b0) for b0 in range(0, n, step)]
+            yield dict(seq=seq_list[seq_idx], copies=copies, pos_of=pos_of, idx=idx, tgt=tgt, chunks=chunks, start=range_start)
+
+    # ---- masked-marginal substitution tables (the zero-shot variant scoring ESM-1v was released for) ---------
+    def masked_marginals(self, seq, with_masking=True, mask_distance=float("inf"), batch_size=None, normalise="vocab"):
+        """(logp, entropy, toks) of one sequence -- see masked_marginals_batch."""
+        return next(self.masked_marginals_batch([seq], with_masking, mask_distance, batch_size, normalise))
+
+    def masked_marginals_batch(self, seq_list, with_masking=True, mask_distance=float("inf"), batch_size=None, normalise="vocab"):
+        """For every sequence yields (logp float32 [L, 20], entropy float32 [L] in nats, toks): logp[i, c] = log-probability of
+        residue toks[c] (the tokens of self.valid_aa_idx, in that order) at position i, read from the copy in which position i is
+        masked.  The masked copies, position lists and `batch_size` chunks are log_likelihood_batch's, so the forwards are the same
+        launches on the same data; only the last step keeps the row instead of one entry of it (pg_esm_forward_logprob_table).
+        normalise "vocab": log_softmax over the model's whole vocabulary -- logp at a position's own residue is bit for bit what
+        log_likelihood_batch lists there; "columns": over the 20 residues only (rows sum to 1)."""
+        if not self.cuda:
+            raise RuntimeError("ESM_sampler.masked_marginals_batch needs device 'gpu'/'cuda:N' on an MI355X: "
+                               "there is no CPU implementation")
+        if normalise not in _lib.TABLE_NORMS:
+            raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
+        toks = [self.model.alphabet.get_tok(i) for i in self.valid_aa_idx]
+        for job in self._masked_copy_jobs(seq_list, with_masking, mask_distance, batch_size):
+            L = len(job["seq"])
+            logp = np.zeros((L, len(self.valid_aa_idx)), dtype=np.float32)
+            entropy = np.zeros(L, dtype=np.float32)
+            for sl, first in job["chunks"]:
+                nb = job["copies"][sl].shape[0]
+                tab, ent = _gibbs.score_table(self.model.model, job["copies"][sl], np.arange(nb), job["idx"][sl], self.valid_aa_idx,
+                                              self.device, normalise, want_entropy=True)
                 for i in range(nb):
-                    for p in range(len(pos_of[batch_start + i])):
-                        likelihood_sum = np.float32(likelihood_sum + lp[i, p])
-                        likelihood_list.append(float(lp[i, p]))
-            if with_masking:
-                # the reference appends in (copy, position) order; positions of one copy ascend (stride n)
-                pass
-            yield (float(likelihood_sum / np.float32(len(seq_list[seq_idx]))), likelihood_list)
+                    pos = np.asarray(job["pos_of"][first + i], dtype=np.int64) - job["start"]
+                    logp[pos] = tab[i, :len(pos)]
+                    entropy[pos] = ent[i, :len(pos)]
+            yield logp, entropy, toks
+
+    def score_mutations(self, seq, mutations, **kwargs):
+        """Masked-marginal scores of point mutations such as "A24G" (wild type, 1-based position, mutant):
+        logp[pos, mutant] - logp[pos, wild type], all from ONE masked_marginals table of `seq` (keyword arguments go to it).
+        ValueError, naming the mutation, when its wild type is not the residue `seq` has there.  Returns a list of floats."""
+        seq = self.clean_seed_seq(seq)
+        parsed = []
+        for mutation in mutations:
+            wt, pos, mut = parse_mutation(mutation)
+            if pos >= len(seq):
+                raise ValueError("Mutation %r: position %d is beyond the sequence of %d residues" % (mutation, pos + 1, len(seq)))
+            if seq[pos] != wt:
+                raise ValueError("Mutation %r: the sequence has %r at position %d, not %r" % (mutation, seq[pos], pos + 1, wt))
+            parsed.append((wt, pos, mut))
+        if not parsed:
+            return []
+        logp, _, toks = self.masked_marginals(seq, **kwargs)
+        col = {t: c for c, t in enumerate(toks)}
+        return [float(logp[pos, col[mut]] - logp[pos, col[wt]]) for wt, pos, mut in parsed]
