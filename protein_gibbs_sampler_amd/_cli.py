@@ -1,6 +1,8 @@
-"""Shared pieces of the command-line front ends (pgen_esm.py / pgen_msa.py)."""
+"""Shared pieces of the command-line front ends (pgen_*.py, likelihood_*.py, seq_probs_esm.py)."""
 import argparse
 import ast
+import contextlib
+import sys
 
 
 class RawAndDefaultsFormatter(argparse.ArgumentDefaultsHelpFormatter, argparse.RawTextHelpFormatter):
@@ -38,6 +40,50 @@ def add_engine_args(parser):
                              "fp16 = the same kernels with fp16 operands, no fallback (8x smaller logit error than bf16, ~3 %% "
                              "slower); fp32 = parity mode (split-bf16 GEMMs and attention, logits within 1e-3 of fp32)")
     parser.add_argument("--seed", type=int, default=None, help="seed random and torch (positions and token draws) for reproducible output")
+
+
+def add_scoring_args(parser, input_help, batch_size_default, batch_size_help, mask_distance_default="one position at a time",
+                     csv_help="If set, then output will be a csv file.", model_choices=None):
+    """The flags the scoring front ends share (likelihood_esm, seq_probs_esm, likelihood_esm_msa)."""
+    parser.add_argument("-o", type=str, default=None, help="output table (default: stdout)")
+    parser.add_argument("-i", default=None, help=input_help)
+    parser.add_argument("--batch_size", type=int, default=batch_size_default, help=batch_size_help)
+    parser.add_argument("--device", type=str, default="gpu", help="gpu (cuda:0) or cuda:[int]")
+    parser.add_argument("--masking_off", action="store_true", default=False, help="If set, no masking is done.")
+    parser.add_argument("--mask_distance", type=int, default=None,
+                        help="mask several positions per copy, (mask_distance - 1) unmasked positions apart. Default: %s." % mask_distance_default)
+    if model_choices is not None:
+        parser.add_argument("--model", type=str, default="esm1v", choices=sorted(model_choices), help="Which model to use.")
+    parser.add_argument("--csv", action="store_true", default=False, help=csv_help)
+
+
+def mask_distance_from(args, refuse_with_masking_off=True):
+    """--mask_distance as the samplers take it (absent: one position per copy), with the front ends' two argument errors."""
+    mask_distance = float("inf") if args.mask_distance is None else args.mask_distance
+    if mask_distance < 1:
+        raise ValueError("mask distance must be an integer >= 1.")
+    if refuse_with_masking_off and args.masking_off and args.mask_distance is not None:
+        raise ValueError("--masking_off and --mask_distance are both set, that doesn't make sense.")
+    return mask_distance
+
+
+def model_kwargs(args):
+    """The engine flags as the keyword arguments of the models.* constructors."""
+    return dict(checkpoint=args.checkpoint, precision=args.precision, synthetic=args.synthetic_weights)
+
+
+@contextlib.contextmanager
+def open_io(args, newline=None):
+    """(input handle, output handle) of -i / -o, stdin / stdout where a flag is absent; files it opened are closed on exit."""
+    input_handle = open(args.i) if args.i is not None else sys.stdin
+    output_handle = open(args.o, "w", newline=newline) if args.o is not None else sys.stdout
+    try:
+        yield input_handle, output_handle
+    finally:
+        if args.i is not None:
+            input_handle.close()
+        if args.o is not None:
+            output_handle.close()
 
 
 def seed_everything(seed):

@@ -1,13 +1,18 @@
-"""Host-side pieces shared by ESM_sampler and ESM_MSA_sampler: target-position tables and the
-device loop for plug-in (non-engine) models.  Everything that touches tokens or logits per position
-is a HIP kernel behind the C ABI; this file only prepares index tables and sequences the calls.
+"""Host-side pieces shared by ESM_sampler and ESM_MSA_sampler: target-position tables, masked copies, the
+one-batch runner of generate() and the device loop and scoring calls for plug-in (non-engine) models.
+Everything that touches tokens or logits per position is a HIP kernel behind the C ABI; this file only
+prepares index tables and sequences the calls.
 """
+import contextlib
 import ctypes
+import re
 
 import numpy as np
+import torch
 
-from . import _lib
+from . import _lib, sharding
 from . import pyrandom as _pyr
+from .engine import NativeMaskedLM
 
 SHADOW_BIT = 1 << 30   # include/pgibbs.h: sampled but not written (a later duplicate in the same row wins)
 
@@ -15,9 +20,6 @@ SHADOW_BIT = 1 << 30   # include/pgibbs.h: sampled but not written (a later dupl
 def resolve_device(device):
     """The reference's device grammar (esm_sampler.py:66-78, esm_msa_sampler.py:47-61): "cpu" | "gpu" | "cuda:N", with
     its three error messages.  Returns (device string, uses_gpu)."""
-    import re
-
-    import torch
     if device == "gpu":
         device = "cuda:0"
     if re.match("^cuda:[0-9]+$", device):
@@ -137,8 +139,71 @@ def build_target_table(n_iters, n_rows_shape, indexes, num_positions, in_order, 
     return table.reshape((n_iters,) + tuple(n_rows_shape) + (P,)), last_i
 
 
+def padded_positions(pos_of, tokens_at=None, min_width=0):
+    """A ragged list of position lists as one table: idx int32 [n, P], -1 padded, P = the longest list (at least min_width),
+    and -- when tokens_at gives the token row each list points into -- tgt int32 [n, P], the tokens found there (else None)."""
+    P = max(max((len(pos) for pos in pos_of), default=0), min_width)
+    idx = np.full((len(pos_of), P), -1, dtype=np.int32)
+    tgt = None if tokens_at is None else np.zeros((len(pos_of), P), dtype=np.int32)
+    for i, pos in enumerate(pos_of):
+        idx[i, :len(pos)] = pos
+        if tgt is not None:
+            tgt[i, :len(pos)] = tokens_at[i][pos]
+    return idx, tgt
+
+
+def masked_copies(one, bins, mask_idx, row=None):
+    """len(bins) copies of the token tensor `one` ([1, T], or [1, R, C] with `row` the alignment row that is masked), copy i
+    masked at the positions bins[i]."""
+    copies = one.repeat(len(bins), *([1] * (one.dim() - 1)))
+    for i, pos in enumerate(bins):
+        if row is None:
+            copies[i, pos] = mask_idx
+        else:
+            copies[i, row, pos] = mask_idx
+    return copies
+
+
+def strided_mask_copies(one, n, start, end, mask_idx, row=None):
+    """The masked-likelihood copies of both samplers (esm_sampler.py:300-317): n copies, copy i masked at start + i,
+    start + i + n, ... below `end`.  Returns (copies, pos_all) with pos_all[i] the positions masked in copy i."""
+    pos_all = [list(range(start + i, end, n)) for i in range(n)]
+    return masked_copies(one, pos_all, mask_idx, row), pos_all
+
+
+def chunks(n, batch_size):
+    """(slice, first index) of every run of max(1, batch_size) items out of n."""
+    step = max(1, batch_size)
+    for b0 in range(0, n, step):
+        yield slice(b0, b0 + step), b0
+
+
+def draw_seed(sampler):
+    """Key of the token-draw generator: the sampler's pinned `draw_seed`, else one draw from torch's global RNG."""
+    return sampler.draw_seed if sampler.draw_seed is not None else int(torch.randint(0, 2**62, (1,)).item())
+
+
+def shard_context(sampler, native, digest_parts, what, shard=None):
+    """The prologue of a job that may be split over torch.distributed ranks: a DistContext when the model is the
+    engine, sharding is switched on (`shard`, default: the sampler's opt-in) and there are several ranks, else None.  With a
+    context: record=True is refused, every rank must have been handed the same job (digest_parts() -> the arguments that
+    define it, evaluated only here) and all ranks continue from rank 0's interpreter RNG state."""
+    if shard is None:
+        shard = sharding.sharding_requested(sampler.shard_over_ranks)
+    ctx = sharding.dist_context() if (native and shard) else None
+    if ctx is not None:
+        if sampler.record:
+            raise ValueError("record=True is not supported together with shard_over_ranks (per-draw logits stay on their rank)")
+        sharding.check_same_job(ctx, sharding.job_digest(*digest_parts()), what)
+        sharding.sync_host_rng(ctx)
+    return ctx
+
+
+def _dptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
 def _current_stream_ptr(device):
-    import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
@@ -154,7 +219,6 @@ def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=N
     sample_flags: optional per-iteration override of `sample` (generate_single's pass_num < burn_in).
     Returns the final tokens as a torch int64 CPU tensor of the input shape.
     """
-    import torch
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: the Gibbs hot path has no CPU implementation in this package")
     L = _lib.lib()
@@ -166,17 +230,16 @@ def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=N
     n_iters, n_sel, P = table.shape
     d_table = torch.from_numpy(np.ascontiguousarray(table)).to(dev)
     d_rowmap = torch.from_numpy(np.ascontiguousarray(row_map, dtype=np.int32)).to(dev) if row_map is not None else None
-    rm_ptr = ctypes.c_void_p(d_rowmap.data_ptr()) if d_rowmap is not None else None
+    rm_ptr = _dptr(d_rowmap) if d_rowmap is not None else None
     d_mrowmap = (torch.from_numpy(np.ascontiguousarray(mask_row_map, dtype=np.int32)).to(dev)
                  if mask_row_map is not None else None)
-    mrm_ptr = ctypes.c_void_p(d_mrowmap.data_ptr()) if d_mrowmap is not None else rm_ptr
+    mrm_ptr = _dptr(d_mrowmap) if d_mrowmap is not None else rm_ptr
     with torch.cuda.device(dev):
         for it in range(n_iters):
             stream = _current_stream_ptr(dev)
-            idx_ptr = ctypes.c_void_p(d_table[it].data_ptr())
+            idx_ptr = _dptr(d_table[it])
             if params.mask and P > 0:
-                _lib.check(L.pg_mask_scatter_device(stream, ctypes.c_void_p(tok.data_ptr()), n_rows, width, idx_ptr,
-                                                    mrm_ptr, n_sel, P, params.mask_idx))
+                _lib.check(L.pg_mask_scatter_device(stream, _dptr(tok), n_rows, width, idx_ptr, mrm_ptr, n_sel, P, params.mask_idx))
             out = model_callable(tok.to(torch.int64).reshape(shape))["logits"]
             if P == 0:
                 continue
@@ -184,38 +247,78 @@ def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=N
             V = out.shape[-1]
             if sample_flags is not None:
                 params.burnin = _lib.INT32_MAX if sample_flags[it] else 0
-            _lib.check(L.pg_sample_writeback_device(stream, ctypes.c_void_p(tok.data_ptr()), n_rows, width,
-                                                    ctypes.c_void_p(out.data_ptr()), V, idx_ptr, rm_ptr, n_sel, P,
+            _lib.check(L.pg_sample_writeback_device(stream, _dptr(tok), n_rows, width, _dptr(out), V, idx_ptr, rm_ptr, n_sel, P,
                                                     ctypes.byref(params), it, None))
         torch.cuda.synchronize(dev)
     return tok.to(device="cpu", dtype=torch.int64).reshape(shape)
+
+
+def run_gibbs_batch(sampler, ctx, batch, table, params, row_id_base, rows_per_item, record_plugin=False):
+    """One batch of either generate(): `batch` (torch int64 [B, T] or [B, R, C]) through every iteration of `table`
+    (int32 [iters, B, P] / [iters, B, R, P]); returns the final tokens as a torch int64 tensor of the same shape.
+    Engine models: one native call -- or, with a DistContext `ctx`, this rank's block of the batch (announced to the engine as
+    a shard of a B-item job) and one gather; row_id_base / rows_per_item are the Philox row id of the batch's first row and
+    the ids one item consumes.  Plug-in models: the device loop over the table flattened to [iters, rows, P].
+    sampler.record appends the run to sampler.last_run; a plug-in run only when the caller asks for it (record_plugin)."""
+    lm = sampler.model.model
+    if not isinstance(lm, NativeMaskedLM):
+        flat = table.reshape(table.shape[0], int(np.prod(table.shape[1:-1])), table.shape[-1]) if table.ndim > 3 else table
+        batch = run_plugin_loop(lm, batch, flat, params, sampler.device)
+        if sampler.record and record_plugin:
+            sampler.last_run.append(dict(table=table, tokens=batch.numpy().copy()))
+        return batch
+    tok = np.ascontiguousarray(batch.numpy(), dtype=np.int32)
+    if ctx is not None:
+        def run_block(ltok, ltable, base):
+            params.row_id_base = base & 0xFFFFFFFF
+            lm.set_job_items(batch.shape[0])      # shard of a batch.shape[0]-item job
+            try:
+                lm.gibbs_run(ltok, ltable, params)
+            finally:
+                lm.set_job_items(0)
+        tok = sharding.run_sharded(ctx, tok, table, row_id_base, rows_per_item, run_block, sampler.device, guard=lm)
+    else:
+        lg, st = lm.gibbs_run(tok, table, params, want_logits=sampler.record, want_tokens=sampler.record)
+        if sampler.record:
+            sampler.last_run.append(dict(table=table, sampled_logits=lg, sampled_tokens=st, tokens=tok.copy()))
+    return torch.from_numpy(tok.astype(np.int64))
+
+
+@contextlib.contextmanager
+def _plugin_logits(model_callable, tokens_i64, device, no_gpu, *arrays):
+    """The plug-in side of score_positions / score_table: the caller's forward on `device`, its logits as one contiguous fp32
+    tensor, and device copies of the int32 `arrays`.  Yields (stream, logits, (n_rows, width, V), device copies) for the
+    caller's one kernel launch and synchronizes after it.  Without a GPU: RuntimeError(no_gpu)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(no_gpu)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        out = model_callable(tokens_i64.to(dev))["logits"].to(device=dev, dtype=torch.float32).contiguous()
+        width, V = out.shape[-2], out.shape[-1]
+        yield _current_stream_ptr(dev), out, (out.numel() // (width * V), width, V), [torch.from_numpy(a).to(dev) for a in arrays]
+        torch.cuda.synchronize(dev)
+
+
+def _int32(*arrays):
+    return [np.ascontiguousarray(a, dtype=np.int32) for a in arrays]
+
+
+def _host_tokens(tokens):
+    return tokens.numpy() if hasattr(tokens, "numpy") else tokens
 
 
 def score_positions(model_callable, tokens_i64, row_of, idx, targets, device):
     """log_softmax(logits)[target] at (token row row_of[s], position idx[s][p]); idx < 0 -> 0.
     Engine models: one native call (LM head only at the scored rows).  Plug-in models: the caller's forward, then the
     HIP gather kernel `pg_logprob_gather_device` on its device-resident logits."""
-    import torch
-    from .engine import NativeMaskedLM
-    row_of = np.ascontiguousarray(row_of, dtype=np.int32)
-    idx = np.ascontiguousarray(idx, dtype=np.int32)
-    targets = np.ascontiguousarray(targets, dtype=np.int32)
+    row_of, idx, targets = _int32(row_of, idx, targets)
     if isinstance(model_callable, NativeMaskedLM):
-        return model_callable.forward_logprobs(tokens_i64.numpy() if hasattr(tokens_i64, "numpy") else tokens_i64, row_of, idx, targets)
-    if not torch.cuda.is_available():
-        raise RuntimeError("no MI355X visible: log-likelihood scoring has no CPU implementation in this package")
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        out = model_callable(tokens_i64.to(dev))["logits"].to(device=dev, dtype=torch.float32).contiguous()
-        width, V = out.shape[-2], out.shape[-1]
-        n_rows = out.numel() // (width * V)
-        d_idx, d_row, d_tgt = (torch.from_numpy(a).to(dev) for a in (idx, row_of, targets))
-        res = torch.zeros(idx.shape, dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().pg_logprob_gather_device(_current_stream_ptr(dev), ctypes.c_void_p(out.data_ptr()), n_rows, width, V,
-                                                       ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(d_row.data_ptr()),
-                                                       ctypes.c_void_p(d_tgt.data_ptr()), idx.shape[0], idx.shape[1],
-                                                       ctypes.c_void_p(res.data_ptr())))
-        torch.cuda.synchronize(dev)
+        return model_callable.forward_logprobs(_host_tokens(tokens_i64), row_of, idx, targets)
+    no_gpu = "no MI355X visible: log-likelihood scoring has no CPU implementation in this package"
+    with _plugin_logits(model_callable, tokens_i64, device, no_gpu, idx, row_of, targets) as (stream, out, dims, (d_idx, d_row, d_tgt)):
+        res = torch.zeros(idx.shape, dtype=torch.float32, device=out.device)
+        _lib.check(_lib.lib().pg_logprob_gather_device(stream, _dptr(out), *dims, _dptr(d_idx), _dptr(d_row), _dptr(d_tgt),
+                                                       idx.shape[0], idx.shape[1], _dptr(res)))
     return res.cpu().numpy()
 
 
@@ -225,32 +328,19 @@ def score_table(model_callable, tokens_i64, row_of, idx, cols, device, normalise
     (out float32 [n_sel, P, n_cols], entropy float32 [n_sel, P] or None).
     Engine models: one native call.  Plug-in models: the caller's forward, then the HIP table kernel `pg_logprob_table_device` on
     its device-resident logits."""
-    import torch
-    from .engine import NativeMaskedLM
     if normalise not in _lib.TABLE_NORMS:
         raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
-    row_of = np.ascontiguousarray(row_of, dtype=np.int32)
-    idx = np.ascontiguousarray(idx, dtype=np.int32)
-    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    row_of, idx, cols = _int32(row_of, idx, cols)
+    cols = cols.reshape(-1)
     if isinstance(model_callable, NativeMaskedLM):
-        return model_callable.forward_logprob_table(tokens_i64.numpy() if hasattr(tokens_i64, "numpy") else tokens_i64, row_of, idx,
-                                                    cols, normalise, want_entropy)
-    if not torch.cuda.is_available():
-        raise RuntimeError("no MI355X visible: masked-marginal tables have no CPU implementation in this package")
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        out = model_callable(tokens_i64.to(dev))["logits"].to(device=dev, dtype=torch.float32).contiguous()
-        width, V = out.shape[-2], out.shape[-1]
-        if len(cols) and (cols.min() < 0 or cols.max() >= V):
-            raise ValueError("score_table: a column lies outside the model's vocabulary of %d" % V)
-        n_rows = out.numel() // (width * V)
-        d_idx, d_row, d_cols = (torch.from_numpy(a).to(dev) for a in (idx, row_of, cols))
-        res = torch.zeros(idx.shape + (len(cols),), dtype=torch.float32, device=dev)
-        ent = torch.zeros(idx.shape, dtype=torch.float32, device=dev) if want_entropy else None
-        _lib.check(_lib.lib().pg_logprob_table_device(_current_stream_ptr(dev), ctypes.c_void_p(out.data_ptr()), n_rows, width, V,
-                                                      ctypes.c_void_p(d_idx.data_ptr()), ctypes.c_void_p(d_row.data_ptr()),
-                                                      idx.shape[0], idx.shape[1], ctypes.c_void_p(d_cols.data_ptr()), len(cols),
-                                                      _lib.TABLE_NORMS[normalise],
-                                                      ctypes.c_void_p(res.data_ptr()), ctypes.c_void_p(ent.data_ptr()) if want_entropy else None))
-        torch.cuda.synchronize(dev)
+        return model_callable.forward_logprob_table(_host_tokens(tokens_i64), row_of, idx, cols, normalise, want_entropy)
+    no_gpu = "no MI355X visible: masked-marginal tables have no CPU implementation in this package"
+    with _plugin_logits(model_callable, tokens_i64, device, no_gpu, idx, row_of, cols) as (stream, out, dims, (d_idx, d_row, d_cols)):
+        if len(cols) and (cols.min() < 0 or cols.max() >= dims[2]):
+            raise ValueError("score_table: a column lies outside the model's vocabulary of %d" % dims[2])
+        res = torch.zeros(idx.shape + (len(cols),), dtype=torch.float32, device=out.device)
+        ent = torch.zeros(idx.shape, dtype=torch.float32, device=out.device) if want_entropy else None
+        _lib.check(_lib.lib().pg_logprob_table_device(stream, _dptr(out), *dims, _dptr(d_idx), _dptr(d_row), idx.shape[0], idx.shape[1],
+                                                      _dptr(d_cols), len(cols), _lib.TABLE_NORMS[normalise], _dptr(res),
+                                                      _dptr(ent) if want_entropy else None))
     return res.cpu().numpy(), (ent.cpu().numpy() if want_entropy else None)

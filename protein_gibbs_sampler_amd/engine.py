@@ -178,17 +178,10 @@ class NativeMaskedLM:
         else:
             tok = np.concatenate([np.full((2, 1), c["cls_idx"]), body, np.full((2, 1), c["eos_idx"])], axis=1)
         try:
-            L = _lib.lib()
-            if self.is_msa:
-                B, R, C = tok.shape
-                out = np.empty((B, R, C, self.cfg["vocab"]), dtype=np.float32)
-                t32 = np.ascontiguousarray(tok, dtype=np.int32)
-                _lib.check(L.pg_msa_forward_logits(self._h, _lib.ptr(t32), B, R, C, _lib.ptr(out)))
-            else:
-                B, T = tok.shape
-                out = np.empty((B, T, self.cfg["vocab"]), dtype=np.float32)
-                t32 = np.ascontiguousarray(tok, dtype=np.int32)
-                _lib.check(L.pg_esm_forward_logits(self._h, _lib.ptr(t32), B, T, _lib.ptr(out)))
+            t32 = np.ascontiguousarray(tok, dtype=np.int32)
+            fn, shape = self._entry("forward_logits", t32)
+            out = np.empty(shape + (self.cfg["vocab"],), dtype=np.float32)
+            _lib.check(fn(self._h, _lib.ptr(t32), *shape, _lib.ptr(out)))      # unguarded: a range error rebuilds the engine below
         except _lib.PgError as e:
             if e.code != _lib.PG_ERR_RANGE:
                 raise
@@ -260,19 +253,25 @@ class NativeMaskedLM:
             out = out.to(tokens.device)
         return {"logits": out}
 
-    def forward_logits(self, tokens):
-        tok = np.ascontiguousarray(tokens, dtype=np.int32)
-        V = self.cfg["vocab"]
-        L = _lib.lib()
+    def _entry(self, name, tok):
+        """The C entry pg_msa_<name> / pg_esm_<name> of this architecture and the shape arguments that follow its token pointer:
+        (B, R, C) of an alignment batch, (B, T) of a sequence batch."""
         if self.is_msa:
             B, R, C = tok.shape
-            self._check_fp16_msa_shape(tok)
-            out = np.empty((B, R, C, V), dtype=np.float32)
-            self._guarded(lambda h: _lib.check(L.pg_msa_forward_logits(h, _lib.ptr(tok), B, R, C, _lib.ptr(out))), tok)
-        else:
-            B, T = tok.shape
-            out = np.empty((B, T, V), dtype=np.float32)
-            self._guarded(lambda h: _lib.check(L.pg_esm_forward_logits(h, _lib.ptr(tok), B, T, _lib.ptr(out))), tok)
+            return getattr(_lib.lib(), "pg_msa_" + name), (B, R, C)
+        B, T = tok.shape
+        return getattr(_lib.lib(), "pg_esm_" + name), (B, T)
+
+    def _call(self, name, tok, *args, inout=None, per_item=None):
+        """pg_{msa,esm}_<name>(handle, tok, shape..., *args) behind the explicit-fp16 shape check and the auto-fp16 guard."""
+        fn, shape = self._entry(name, tok)
+        self._check_fp16_msa_shape(tok)
+        return self._guarded(lambda h: _lib.check(fn(h, _lib.ptr(tok), *shape, *args)), tok, inout, per_item)
+
+    def forward_logits(self, tokens):
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        out = np.empty(tok.shape + (self.cfg["vocab"],), dtype=np.float32)
+        self._call("forward_logits", tok, _lib.ptr(out))
         return out
 
     def forward_logprobs(self, tokens, row_of, idx, targets):
@@ -283,16 +282,7 @@ class NativeMaskedLM:
         targets = np.ascontiguousarray(targets, dtype=np.int32)
         n_sel, P = idx.shape
         out = np.zeros((n_sel, P), dtype=np.float32)
-        L = _lib.lib()
-        if self.is_msa:
-            B, R, C = tok.shape
-            self._check_fp16_msa_shape(tok)
-            self._guarded(lambda h: _lib.check(L.pg_msa_forward_logprobs(h, _lib.ptr(tok), B, R, C, _lib.ptr(row_of), _lib.ptr(idx),
-                                                                         _lib.ptr(targets), n_sel, P, _lib.ptr(out))), tok)
-        else:
-            B, T = tok.shape
-            self._guarded(lambda h: _lib.check(L.pg_esm_forward_logprobs(h, _lib.ptr(tok), B, T, _lib.ptr(row_of), _lib.ptr(idx),
-                                                                         _lib.ptr(targets), n_sel, P, _lib.ptr(out))), tok)
+        self._call("forward_logprobs", tok, _lib.ptr(row_of), _lib.ptr(idx), _lib.ptr(targets), n_sel, P, _lib.ptr(out))
         return out
 
     def forward_logprob_table(self, tokens, row_of, idx, cols, normalise="vocab", want_entropy=False):
@@ -302,26 +292,15 @@ class NativeMaskedLM:
         idx < 0 are zeros.  Returns (out float32 [n_sel, P, n_cols], entropy float32 [n_sel, P] in nats or None)."""
         if normalise not in _lib.TABLE_NORMS:
             raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
-        norm = _lib.TABLE_NORMS[normalise]
         tok = np.ascontiguousarray(tokens, dtype=np.int32)
         row_of = np.ascontiguousarray(row_of, dtype=np.int32)
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
         n_sel, P = idx.shape
-        n_cols = len(cols)
-        out = np.zeros((n_sel, P, n_cols), dtype=np.float32)
+        out = np.zeros((n_sel, P, len(cols)), dtype=np.float32)
         ent = np.zeros((n_sel, P), dtype=np.float32) if want_entropy else None
-        ent_p = _lib.ptr(ent) if want_entropy else None
-        L = _lib.lib()
-        if self.is_msa:
-            B, R, C = tok.shape
-            self._check_fp16_msa_shape(tok)
-            self._guarded(lambda h: _lib.check(L.pg_msa_forward_logprob_table(h, _lib.ptr(tok), B, R, C, _lib.ptr(row_of), _lib.ptr(idx),
-                                                                              n_sel, P, _lib.ptr(cols), n_cols, norm, _lib.ptr(out), ent_p)), tok)
-        else:
-            B, T = tok.shape
-            self._guarded(lambda h: _lib.check(L.pg_esm_forward_logprob_table(h, _lib.ptr(tok), B, T, _lib.ptr(row_of), _lib.ptr(idx),
-                                                                              n_sel, P, _lib.ptr(cols), n_cols, norm, _lib.ptr(out), ent_p)), tok)
+        self._call("forward_logprob_table", tok, _lib.ptr(row_of), _lib.ptr(idx), n_sel, P, _lib.ptr(cols), len(cols),
+                   _lib.TABLE_NORMS[normalise], _lib.ptr(out), _lib.ptr(ent) if want_entropy else None)
         return out, ent
 
     # ---- whole Gibbs loops -----------------------------------------------------------------
@@ -330,20 +309,11 @@ class NativeMaskedLM:
         tok = tokens
         assert tok.dtype == np.int32 and tok.flags.c_contiguous
         idx = np.ascontiguousarray(target_idx, dtype=np.int32)
-        n_iters, P = idx.shape[0], idx.shape[-1]
-        V = self.cfg["vocab"]
-        lg = np.empty(idx.shape + (V,), dtype=np.float32) if want_logits else None
+        lg = np.empty(idx.shape + (self.cfg["vocab"],), dtype=np.float32) if want_logits else None
         st = np.empty(idx.shape, dtype=np.int32) if want_tokens else None
-        L = _lib.lib()
-        if self.is_msa:
-            B, R, C = tok.shape
-            self._check_fp16_msa_shape(tok)
-            self._guarded(lambda h: _lib.check(L.pg_msa_gibbs_run(h, _lib.ptr(tok), B, R, C, _lib.ptr(idx), n_iters, P, ctypes.byref(params),
-                                                                  _lib.ptr(lg) if want_logits else None, _lib.ptr(st) if want_tokens else None)), tok, tok)
-        else:
-            B, T = tok.shape
-            self._guarded(lambda h: _lib.check(L.pg_esm_gibbs_run(h, _lib.ptr(tok), B, T, _lib.ptr(idx), n_iters, P, ctypes.byref(params),
-                                                                  _lib.ptr(lg) if want_logits else None, _lib.ptr(st) if want_tokens else None)), tok, tok)
+        # params goes as it is (the POINTER(SampleParams) argtype takes its address): nothing is marshalled before the shape check
+        self._call("gibbs_run", tok, _lib.ptr(idx), idx.shape[0], idx.shape[-1], params,
+                   _lib.ptr(lg) if want_logits else None, _lib.ptr(st) if want_tokens else None, inout=tok)
         return lg, st
 
     def gibbs_single_run(self, tokens, mask_row, target_row, step_idx, step_sample, params, want_logits=False,

@@ -8,12 +8,10 @@ cleaning with the 21-symbol alphabet :93-99; `<mask>` padding through the patche
 pass, :129); `generate_single` masking row -1 while sampling `target_index` (quirk Q2, :133-145).
 """
 import math
-import random
-import re
 
 import numpy as np
 import torch
-from tqdm import trange
+from tqdm import tqdm, trange
 
 from . import _gibbs, _lib, sharding
 from .engine import NativeMaskedLM
@@ -78,9 +76,6 @@ class ESM_MSA_sampler():
             raise RuntimeError("ESM_MSA_sampler.%s needs device 'gpu'/'cuda:N' on an MI355X: the Gibbs hot path is "
                                "implemented as HIP kernels only, there is no CPU implementation" % what)
 
-    def _draw_seed(self):
-        return self.draw_seed if self.draw_seed is not None else int(torch.randint(0, 2**62, (1,)).item())
-
     # ---- single-row resampling (reference :101-147) -------------------------------------------
     def generate_single(self, seed_msa, steps=10, passes=3, burn_in=1, target_index=0, k=1, exclude_positions=None):
         return self.generate_single_batch([seed_msa], steps=steps, passes=passes, burn_in=burn_in, target_index=target_index, k=k,
@@ -104,14 +99,8 @@ class ESM_MSA_sampler():
         self._require_gpu("generate_single")
         from . import pyrandom
         native = isinstance(self.model.model, NativeMaskedLM)
-        shard = sharding.sharding_requested(self.shard_over_ranks) if _shard is None else _shard
-        ctx = sharding.dist_context() if (native and shard) else None
-        if ctx is not None:
-            if self.record:
-                raise ValueError("record=True is not supported together with shard_over_ranks (per-draw logits stay on their rank)")
-            sharding.check_same_job(ctx, sharding.job_digest(seed_msas, steps, passes, burn_in, target_index, k, exclude_positions,
-                                                             self.rng_stream), "ESM_MSA_sampler.generate_single_batch")
-            sharding.sync_host_rng(ctx)
+        ctx = _gibbs.shard_context(self, native, lambda: (seed_msas, steps, passes, burn_in, target_index, k, exclude_positions,
+                                                          self.rng_stream), "ESM_MSA_sampler.generate_single_batch", shard=_shard)
 
         # every MSA's step lists, decided up front in the serial order (selection never depends on the logits)
         jobs = []
@@ -129,7 +118,7 @@ class ESM_MSA_sampler():
                 for step in partition(positions, steps):
                     steps_all.append(list(step))
                     flags.append(1 if pass_num < burn_in else 0)
-            jobs.append(dict(batch=batch, steps=steps_all, flags=flags, tr=target_index % R, seed=self._draw_seed()))
+            jobs.append(dict(batch=batch, steps=steps_all, flags=flags, tr=target_index % R, seed=_gibbs.draw_seed(self)))
         if ctx is not None:
             seeds = sharding.broadcast_object(ctx, [j["seed"] for j in jobs])      # rank 0's torch draws
             for j, sd in zip(jobs, seeds):
@@ -138,10 +127,7 @@ class ESM_MSA_sampler():
         mask_idx = self.model.alphabet.mask_idx
 
         def table_of(job, P):
-            t = np.full((len(job["steps"]), P), -1, dtype=np.int32)
-            for i, st in enumerate(job["steps"]):
-                t[i, :len(st)] = st
-            return t
+            return _gibbs.padded_positions(job["steps"], min_width=P)[0]
 
         lo, hi = (0, n) if ctx is None else sharding.shard_range(n, ctx.world, ctx.rank)
         if native:
@@ -152,8 +138,8 @@ class ESM_MSA_sampler():
                 key = (tuple(job["batch"].shape), len(job["steps"]), tuple(job["flags"]), job["tr"])
                 groups.setdefault(key, []).append(j)
             for key, members in groups.items():
-                for c0 in range(0, len(members), max(1, max_batch)):
-                    chunk = members[c0:c0 + max(1, max_batch)]
+                for sl, _ in _gibbs.chunks(len(members), max_batch):
+                    chunk = members[sl]
                     P = max((len(st) for j in chunk for st in jobs[j]["steps"]), default=0)
                     table = np.stack([table_of(jobs[j], P) for j in chunk], axis=1)         # [n_steps, b, P]
                     tok = np.ascontiguousarray(np.concatenate([jobs[j]["batch"].numpy() for j in chunk]), dtype=np.int32)
@@ -182,10 +168,7 @@ class ESM_MSA_sampler():
             for i, j in enumerate(range(lo, hi)):
                 row = jobs[j]["batch"][0, jobs[j]["tr"]].numpy()
                 mine[i, :len(row)] = row
-            counts = [sharding.shard_range(n, ctx.world, r)[1] - sharding.shard_range(n, ctx.world, r)[0] for r in range(ctx.world)]
-            t = torch.from_numpy(mine)
-            on_gpu = ctx.dist.get_backend() != "gloo"
-            full = sharding.gather_tokens(ctx.dist, t.to(self.device) if on_gpu else t, counts).cpu().numpy()
+            full = sharding.gather_blocks(ctx, mine, n, self.device)
             self.last_run = []                    # per-draw records are refused together with sharding (above)
             return ["".join(self.model.alphabet.get_tok(int(v)) for v in full[j, 1:jobs[j]["batch"].shape[2]]) for j in range(n)]
         if not self.record:
@@ -207,17 +190,12 @@ class ESM_MSA_sampler():
         if max_len is None:
             max_len = sequence_length
         self._require_gpu("generate")
-        draw_seed = self._draw_seed()
-        native = isinstance(self.model.model, NativeMaskedLM)
+        draw_seed = _gibbs.draw_seed(self)
         self.last_run = []
-        ctx = sharding.dist_context() if (native and sharding.sharding_requested(self.shard_over_ranks)) else None
+        ctx = _gibbs.shard_context(self, isinstance(self.model.model, NativeMaskedLM), lambda: (
+            n_samples, seed_msa, batch_size, in_order, max_len, leader_length, top_k, temperature, num_iters, burnin, mask,
+            num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream), "ESM_MSA_sampler.generate")
         if ctx is not None:
-            if self.record:
-                raise ValueError("record=True is not supported together with shard_over_ranks (per-draw logits stay on their rank)")
-            sharding.check_same_job(ctx, sharding.job_digest(
-                n_samples, seed_msa, batch_size, in_order, max_len, leader_length, top_k, temperature, num_iters, burnin, mask,
-                num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream), "ESM_MSA_sampler.generate")
-            sharding.sync_host_rng(ctx)
             draw_seed = sharding.broadcast_object(ctx, draw_seed)
 
         for generation_round in trange(n_generation_rounds, disable=(not show_progress_bar)):
@@ -231,26 +209,9 @@ class ESM_MSA_sampler():
             params = _lib.make_sample_params(mask, self.model.alphabet.mask_idx, top_k, burnin, temperature,
                                              self.valid_aa_idx, draw_seed, rng_stream=self.rng_stream,
                                              row_id_base=generation_round * batch_size * num_sequences)
-            if native and ctx is not None:
-                def run_block(ltok, ltable, base):
-                    params.row_id_base = base & 0xFFFFFFFF
-                    self.model.model.set_job_items(batch.shape[0])      # shard of a batch.shape[0]-item job
-                    try:
-                        self.model.model.gibbs_run(ltok, ltable, params)
-                    finally:
-                        self.model.model.set_job_items(0)
-                tok = sharding.run_sharded(ctx, np.ascontiguousarray(batch.numpy(), dtype=np.int32), table,
-                                           generation_round * batch_size * num_sequences, num_sequences, run_block, self.device, guard=self.model.model)
-                batch = torch.from_numpy(tok.astype(np.int64))
-            elif native:
-                tok = np.ascontiguousarray(batch.numpy(), dtype=np.int32)
-                lg, st = self.model.model.gibbs_run(tok, table, params, want_logits=self.record, want_tokens=self.record)
-                batch = torch.from_numpy(tok.astype(np.int64))
-                if self.record:
-                    self.last_run.append(dict(table=table, sampled_logits=lg, sampled_tokens=st, tokens=tok.copy()))
-            else:
-                flat = table.reshape(num_iters, batch_size * num_sequences, table.shape[-1])
-                batch = _gibbs.run_plugin_loop(self.model.model, batch, flat, params, self.device)
+            # a plug-in run is not recorded here (ESM_sampler.generate records it): the one difference between the two callers
+            batch = _gibbs.run_gibbs_batch(self, ctx, batch, table, params, generation_round * batch_size * num_sequences, num_sequences,
+                                           record_plugin=False)
             strs = self.untokenize_batch(batch)
             if generation_round == (n_generation_rounds - 1):
                 sequences += strs[0:n_samples - len(sequences)]
@@ -341,8 +302,8 @@ class ESM_MSA_sampler():
             # tokens[:, target_index]; on a ragged list the reference reads that row of the PADDED tensor -- a <pad> row for every
             # shallower MSA, whose "likelihoods" are those of <pad> tokens -- a deliberate deviation.
             rows_of = [target_index if target_index >= 0 else len(msa) + target_index for msa in msa_list]
-            for batch_start in range(0, n, max(1, batch_size)):
-                chunk = tokens[batch_start:batch_start + max(1, batch_size)]
+            for sl, batch_start in _gibbs.chunks(n, batch_size):
+                chunk = tokens[sl]
                 nb = chunk.shape[0]
                 pos_of, orig = [], []
                 for i in range(nb):
@@ -351,12 +312,7 @@ class ESM_MSA_sampler():
                     end = len(msa[target_index]) + range_start
                     pos_of.append([p_ for p_ in range(range_start, end) if count_gaps or int(o[p_]) not in gap_tokens])
                     orig.append(o)
-                P = max((len(p_) for p_ in pos_of), default=0)
-                idx = np.full((nb, max(P, 1)), -1, dtype=np.int32)
-                tgt = np.zeros((nb, max(P, 1)), dtype=np.int32)
-                for i, pos in enumerate(pos_of):
-                    idx[i, :len(pos)] = pos
-                    tgt[i, :len(pos)] = orig[i][pos]
+                idx, tgt = _gibbs.padded_positions(pos_of, orig, min_width=1)
                 row_of = np.arange(nb) * R + np.asarray(rows_of[batch_start:batch_start + nb])
                 items = []
                 for i in range(nb):
@@ -375,21 +331,11 @@ class ESM_MSA_sampler():
             denom = seq_len - (0 if count_gaps else sum(msa[target_index].count(g) for g in ESM_MSA_GAP_CHARACTERS))
             end = seq_len + range_start
             orig = one[0, tr].numpy()
-            n = int(min(mask_distance, seq_len))
-            copies = one.repeat(n, 1, 1)
-            pos_all = [list(range(range_start + i, end, n)) for i in range(n)]
-            for i, pos in enumerate(pos_all):
-                copies[i, tr, pos] = mask_idx
+            copies, pos_all = _gibbs.strided_mask_copies(one, int(min(mask_distance, seq_len)), range_start, end, mask_idx, row=tr)
             pos_of = [[p for p in pos if count_gaps or int(orig[p]) not in gap_tokens] for pos in pos_all]
-            P = max((len(p) for p in pos_of), default=0)
-            idx = np.full((n, max(P, 1)), -1, dtype=np.int32)
-            tgt = np.zeros((n, max(P, 1)), dtype=np.int32)
-            for i, pos in enumerate(pos_of):
-                idx[i, :len(pos)] = pos
-                tgt[i, :len(pos)] = orig[pos]
+            idx, tgt = _gibbs.padded_positions(pos_of, [orig] * len(pos_of), min_width=1)
             calls, rows = [], []
-            for batch_start in range(0, n, max(1, batch_size)):
-                sl = slice(batch_start, batch_start + max(1, batch_size))
+            for sl, batch_start in _gibbs.chunks(len(pos_of), batch_size):
                 nb = copies[sl].shape[0]
                 row_of = np.arange(nb) * R + tr
                 rows += [(len(calls), i, pos_of[batch_start + i]) for i in range(nb)]
@@ -446,22 +392,16 @@ class ESM_MSA_sampler():
         bins = self._probs_single_bins(sequence_length, steps)
         tr = target_index % R
         n = len(bins)
-        copies = one.repeat(n, 1, 1)
-        P = max(len(b) for b in bins)
-        idx = np.full((n, P), -1, dtype=np.int32)
-        for i, b in enumerate(bins):
-            copies[i, tr, b] = self.model.alphabet.mask_idx
-            idx[i, :len(b)] = b
+        copies = _gibbs.masked_copies(one, bins, self.model.alphabet.mask_idx, row=tr)
+        idx, _ = _gibbs.padded_positions(bins)
         probs = np.zeros((len(self.toks), sequence_length), dtype=np.float32)
-        step = n if batch_size is None else max(1, batch_size)
         native = isinstance(self.model.model, NativeMaskedLM)
         if native:
             # every chunk is a shard of the one n-alignment job: kernel choices that change a summation order are taken on the
             # job's size, so the table does not depend on batch_size (pgibbs.h pg_engine_set_job_items)
             self.model.model.set_job_items(n)
         try:
-            for b0 in trange(0, n, step, disable=(not show_progress_bar)):
-                sl = slice(b0, b0 + step)
+            for sl, b0 in tqdm(list(_gibbs.chunks(n, n if batch_size is None else batch_size)), disable=(not show_progress_bar)):
                 nb = copies[sl].shape[0]
                 tab, _ = _gibbs.score_table(self.model.model, copies[sl], np.arange(nb) * R + tr, idx[sl], self.valid_aa_idx,
                                             self.device, "columns")

@@ -43,10 +43,6 @@ def parse_mutation(mutation):
     return wt, int(m.group(2)) - 1, mut
 
 
-def _device_of(t):
-    return t.device if isinstance(t, torch.Tensor) else torch.device("cpu")
-
-
 def generate_step(out, gen_idx, temperature=None, top_k=0, sample=False, valid_idx=None, rng_seed=None, counter=None):
     """Generate a token id from out[gen_idx] (reference :8-45) on the GPU.
 
@@ -147,16 +143,13 @@ class ESM_sampler():
         device token tensor goes through the HIP scatter kernel."""
         mask_idx = self.model.alphabet.mask_idx
         if isinstance(batch, torch.Tensor) and batch.device.type == "cuda":
-            P = max((len(t) for t in target_indexes), default=0)
-            table = np.full((len(target_indexes), P), -1, dtype=np.int32)
-            for b, t in enumerate(target_indexes):
-                table[b, :len(t)] = t
+            table, _ = _gibbs.padded_positions(target_indexes)
             tok = batch.to(torch.int32).contiguous()
             d_table = torch.from_numpy(table).to(batch.device)
             with torch.cuda.device(batch.device):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(batch.device).cuda_stream)
                 _lib.check(_lib.lib().pg_mask_scatter_device(stream, ctypes.c_void_p(tok.data_ptr()), tok.shape[0], tok.shape[1],
-                                                             ctypes.c_void_p(d_table.data_ptr()), None, len(target_indexes), P,
+                                                             ctypes.c_void_p(d_table.data_ptr()), None, table.shape[0], table.shape[1],
                                                              mask_idx))
             batch.copy_(tok.to(batch.dtype))
             return
@@ -166,6 +159,10 @@ class ESM_sampler():
 
     def calculate_indexes(self, indexes, leader_length, max_len, rollover_from_start):
         return _gibbs.candidate_indexes(indexes, leader_length, max_len, rollover_from_start)
+
+    def _require_gpu(self, what, why="there is no CPU implementation"):
+        if not self.cuda:
+            raise RuntimeError("ESM_sampler.%s needs device 'gpu'/'cuda:N' on an MI355X: %s" % (what, why))
 
     # ---- the sampler -----------------------------------------------------------------------------
     def generate(self, n_samples, seed_seq, batch_size=1, in_order=False, max_len=None, leader_length=0,
@@ -187,21 +184,14 @@ class ESM_sampler():
         num_positions, leader_length = _gibbs.derive_counts(max_len, num_positions, num_positions_percent, leader_length,
                                                             leader_length_percent)
 
-        if not self.cuda:
-            raise RuntimeError("ESM_sampler.generate needs device 'gpu'/'cuda:N' on an MI355X: this package implements the "
-                               "Gibbs hot path as HIP kernels only and has no CPU implementation")
-        draw_seed = self.draw_seed if self.draw_seed is not None else int(torch.randint(0, 2**62, (1,)).item())
-        native = isinstance(self.model.model, NativeMaskedLM)
+        self._require_gpu("generate", "this package implements the Gibbs hot path as HIP kernels only and has no CPU implementation")
+        draw_seed = _gibbs.draw_seed(self)
         self.last_run = []
         # several torch.distributed ranks (one per GPU): every batch is split contiguously over them
-        ctx = sharding.dist_context() if (native and sharding.sharding_requested(self.shard_over_ranks)) else None
+        ctx = _gibbs.shard_context(self, isinstance(self.model.model, NativeMaskedLM), lambda: (
+            n_samples, seed_seq, batch_size, in_order, max_len, leader_length, top_k, temperature, num_iters, burnin, mask,
+            num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream), "ESM_sampler.generate")
         if ctx is not None:
-            if self.record:
-                raise ValueError("record=True is not supported together with shard_over_ranks (per-draw logits stay on their rank)")
-            sharding.check_same_job(ctx, sharding.job_digest(
-                n_samples, seed_seq, batch_size, in_order, max_len, leader_length, top_k, temperature, num_iters, burnin, mask,
-                num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream), "ESM_sampler.generate")
-            sharding.sync_host_rng(ctx)
             draw_seed = sharding.broadcast_object(ctx, draw_seed)
 
         for batch_n in trange(n_batches, disable=(not show_progress_bar)):
@@ -215,27 +205,7 @@ class ESM_sampler():
             table, last_i = _gibbs.build_target_table(num_iters, (batch_size,), indexes, num_positions, in_order, last_i)
             params = _lib.make_sample_params(mask, self.model.alphabet.mask_idx, top_k, burnin, temperature, self.valid_aa_idx,
                                              draw_seed, rng_stream=self.rng_stream, row_id_base=batch_n * batch_size)
-            if native and ctx is not None:
-                def run_block(ltok, ltable, base):
-                    params.row_id_base = base & 0xFFFFFFFF
-                    self.model.model.set_job_items(batch.shape[0])      # shard of a batch.shape[0]-item job
-                    try:
-                        self.model.model.gibbs_run(ltok, ltable, params)
-                    finally:
-                        self.model.model.set_job_items(0)
-                tok = sharding.run_sharded(ctx, np.ascontiguousarray(batch.numpy(), dtype=np.int32), table,
-                                           batch_n * batch_size, 1, run_block, self.device, guard=self.model.model)
-                batch = torch.from_numpy(tok.astype(np.int64))
-            elif native:
-                tok = np.ascontiguousarray(batch.numpy(), dtype=np.int32)
-                lg, st = self.model.model.gibbs_run(tok, table, params, want_logits=self.record, want_tokens=self.record)
-                batch = torch.from_numpy(tok.astype(np.int64))
-                if self.record:
-                    self.last_run.append(dict(table=table, sampled_logits=lg, sampled_tokens=st, tokens=tok.copy()))
-            else:
-                batch = _gibbs.run_plugin_loop(self.model.model, batch, table, params, self.device)
-                if self.record:
-                    self.last_run.append(dict(table=table, tokens=batch.numpy().copy()))
+            batch = _gibbs.run_gibbs_batch(self, ctx, batch, table, params, batch_n * batch_size, 1, record_plugin=True)
 
             strs = self.untokenize_batch(batch, self.model.alphabet.prepend_bos, self.model.alphabet.append_eos)
             if batch_n == (n_batches - 1):
@@ -255,9 +225,7 @@ class ESM_sampler():
         num_copies-th position starting at i; the log-probability of the original residue is read at the masked
         positions.  The forward, log-softmax and gather run on the GPU (pg_esm_forward_logprobs: the LM head is
         evaluated only at the scored rows)."""
-        if not self.cuda:
-            raise RuntimeError("ESM_sampler.log_likelihood_batch needs device 'gpu'/'cuda:N' on an MI355X: "
-                               "there is no CPU implementation")
+        self._require_gpu("log_likelihood_batch")
         for job in self._masked_copy_jobs(seq_list, with_masking, mask_distance, batch_size):
             likelihood_sum = np.float32(0.0)
             likelihood_list = []
@@ -294,25 +262,14 @@ class ESM_sampler():
             # tokens of THIS sequence alone (no padding reaches the model, as in the reference's masked path)
             _, _, one = self.model.batch_converter([(0, original_string)])
             if with_masking:
-                n = int(min(mask_distance, len(original_string)))
-                copies = one.repeat(n, 1)
-                pos_of = [list(range(range_start + i, end, n)) for i in range(n)]
-                for i, pos in enumerate(pos_of):
-                    copies[i, pos] = mask_idx
+                copies, pos_of = _gibbs.strided_mask_copies(one, int(min(mask_distance, len(original_string))), range_start, end,
+                                                            mask_idx)
                 assert sum(len(p) for p in pos_of) == len(original_string)
             else:
-                n = 1
-                copies = one
-                pos_of = [list(range(range_start, end))]
-            P = max((len(p) for p in pos_of), default=0)
-            idx = np.full((n, P), -1, dtype=np.int32)
-            tgt = np.zeros((n, P), dtype=np.int32)
-            for i, pos in enumerate(pos_of):
-                idx[i, :len(pos)] = pos
-                tgt[i, :len(pos)] = old_toks[seq_idx, pos]
-            step = max(1, batch_size)
-            chunks = [(slice(b0, b0 + step), b0) for b0 in range(0, n, step)]
-            yield dict(seq=seq_list[seq_idx], copies=copies, pos_of=pos_of, idx=idx, tgt=tgt, chunks=chunks, start=range_start)
+                copies, pos_of = one, [list(range(range_start, end))]
+            idx, tgt = _gibbs.padded_positions(pos_of, [old_toks[seq_idx]] * len(pos_of))
+            yield dict(seq=seq_list[seq_idx], copies=copies, pos_of=pos_of, idx=idx, tgt=tgt,
+                       chunks=list(_gibbs.chunks(len(pos_of), batch_size)), start=range_start)
 
     # ---- masked-marginal substitution tables (the zero-shot variant scoring ESM-1v was released for) ---------
     def masked_marginals(self, seq, with_masking=True, mask_distance=float("inf"), batch_size=None, normalise="vocab"):
@@ -326,9 +283,7 @@ class ESM_sampler():
         launches on the same data; only the last step keeps the row instead of one entry of it (pg_esm_forward_logprob_table).
         normalise "vocab": log_softmax over the model's whole vocabulary -- logp at a position's own residue is bit for bit what
         log_likelihood_batch lists there; "columns": over the 20 residues only (rows sum to 1)."""
-        if not self.cuda:
-            raise RuntimeError("ESM_sampler.masked_marginals_batch needs device 'gpu'/'cuda:N' on an MI355X: "
-                               "there is no CPU implementation")
+        self._require_gpu("masked_marginals_batch")
         if normalise not in _lib.TABLE_NORMS:
             raise ValueError("normalise must be 'vocab' or 'columns', got %r" % (normalise,))
         toks = [self.model.alphabet.get_tok(i) for i in self.valid_aa_idx]

@@ -4,11 +4,10 @@
 output is `id<sep>score` rows (tab or comma), optionally a second table with the ';'-joined per-position
 log-likelihoods rounded to 3 decimals."""
 import argparse
-import sys
 import textwrap
 
 from . import models
-from ._cli import RawAndDefaultsFormatter, add_engine_args
+from ._cli import RawAndDefaultsFormatter, add_engine_args, add_scoring_args, mask_distance_from, model_kwargs, open_io
 from .esm_sampler import ESM_sampler
 from .fasta_io import parse_fasta
 
@@ -51,15 +50,8 @@ def build_parser():
     writes a tab separated output file with columns:
     sequence name, score
     """), formatter_class=RawAndDefaultsFormatter)
-    parser.add_argument("-o", type=str, default=None, help="output table (default: stdout)")
-    parser.add_argument("-i", default=None, help="A fasta file with sequences to score. Gaps and stop codons are removed first.")
-    parser.add_argument("--batch_size", type=int, default=1, help="How many sequences to batch together.")
-    parser.add_argument("--device", type=str, default="gpu", help="gpu (cuda:0) or cuda:[int]")
-    parser.add_argument("--masking_off", action="store_true", default=False, help="If set, no masking is done.")
-    parser.add_argument("--mask_distance", type=int, default=None,
-                        help="mask several positions per copy, (mask_distance - 1) unmasked positions apart. Default: one position at a time.")
-    parser.add_argument("--model", type=str, default="esm1v", choices=sorted(model_map), help="Which model to use.")
-    parser.add_argument("--csv", action="store_true", default=False, help="If set, then output will be a csv file.")
+    add_scoring_args(parser, "A fasta file with sequences to score. Gaps and stop codons are removed first.", 1,
+                     "How many sequences to batch together.", model_choices=model_map)
     parser.add_argument("--score_name", type=str, default=None, help="name of the second column (default: the model name).")
     parser.add_argument("--positionwise", type=str, default=None, help="also write per-position log likelihoods (';' separated) to this file.")
     add_engine_args(parser)
@@ -68,22 +60,11 @@ def build_parser():
 
 def cli(argv=None):
     args = build_parser().parse_args(argv)
-    mask_distance = float("inf") if args.mask_distance is None else args.mask_distance
-    if mask_distance < 1:
-        raise ValueError("mask distance must be an integer >= 1.")
-    if args.masking_off and args.mask_distance is not None:
-        raise ValueError("--masking_off and --mask_distance are both set, that doesn't make sense.")
-    sampler = ESM_sampler(model_map[args.model](checkpoint=args.checkpoint, precision=args.precision, synthetic=args.synthetic_weights), device=args.device)
-    input_handle = open(args.i) if args.i is not None else sys.stdin
-    output_handle = open(args.o, "w") if args.o is not None else sys.stdout
-    try:
+    mask_distance = mask_distance_from(args)
+    sampler = ESM_sampler(model_map[args.model](**model_kwargs(args)), device=args.device)
+    with open_io(args) as (input_handle, output_handle):
         main(input_handle, output_handle, args.masking_off, args.device, args.model, args.batch_size, mask_distance, args.csv,
              args.score_name, args.positionwise, sampler=sampler)
-    finally:
-        if args.i is not None:
-            input_handle.close()
-        if args.o is not None:
-            output_handle.close()
 
 
 if __name__ == "__main__":

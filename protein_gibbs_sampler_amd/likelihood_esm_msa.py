@@ -14,7 +14,7 @@ import textwrap
 import warnings
 
 from . import models
-from ._cli import RawAndDefaultsFormatter, add_engine_args
+from ._cli import RawAndDefaultsFormatter, add_engine_args, add_scoring_args, mask_distance_from, model_kwargs, open_io
 from .esm_msa_sampler import ESM_MSA_sampler
 from .fasta_io import SequenceSubsetter, parse_fasta, write_sequential_fasta
 from .msa_tools import add_to_msa, delete_msa_cols, generate_alignment, run_phmmer  # noqa: F401
@@ -98,19 +98,16 @@ def build_parser():
     writes a tab separated output file with columns:
     sequence name, score
     """), formatter_class=RawAndDefaultsFormatter)
-    parser.add_argument("-o", type=str, default=None, help="output table (default: stdout)")
-    parser.add_argument("-i", default=None, help="A fasta file with sequences to calculate log likelihood for")
+    add_scoring_args(parser, "A fasta file with sequences to calculate log likelihood for", 1, "msa instances per forward.",
+                     mask_distance_default="one at a time", csv_help="If set, then outputs will be csv files.")
     parser.add_argument("--reference_msa", default=None, required=True,
                         help="fasta with the reference msa (for subset_strategy top_hits: unaligned reference sequences).")
-    parser.add_argument("--device", type=str, default="gpu", help="gpu (cuda:0) or cuda:[int]")
-    parser.add_argument("--masking_off", action="store_true", default=False, help="If set, no masking is done.")
     parser.add_argument("--delete_insertions", action="store_true", default=False,
                         help="remove all lowercase and '.' characters from input sequences. Default: lower -> upper and '.' -> '-'.")
     parser.add_argument("--alignment_size", type=int, default=sys.maxsize,
                         help="sample this many sequences from the reference alignment (recommended 31-255). Default: all of it.")
     parser.add_argument("--keep_identical", action="store_true", default=False,
                         help="top_hits: keep hits identical to the query (thrown out by default).")
-    parser.add_argument("--batch_size", type=int, default=1, help="msa instances per forward.")
     parser.add_argument("--subset_strategy", default="random", choices=["in_order", "random", "top_hits"],
                         help="random: draw randomly, in_order: first sequences of the reference alignment, top_hits: phmmer per query "
                              "against the reference sequences and a MAFFT MSA of the top hits.")
@@ -118,9 +115,6 @@ def build_parser():
     parser.add_argument("--redraw", action="store_true", default=False, help="random: a new draw of reference sequences for each query.")
     parser.add_argument("--unaligned_queries", action="store_true", default=False,
                         help="queries are unaligned / from another alignment: add each to the reference alignment with muscle -profile.")
-    parser.add_argument("--mask_distance", type=int, default=None,
-                        help="mask several positions per copy, (mask_distance - 1) unmasked positions apart. Default: one at a time.")
-    parser.add_argument("--csv", action="store_true", default=False, help="If set, then outputs will be csv files.")
     parser.add_argument("--positionwise", type=str, default=None, help="also write per-position log likelihoods (';' separated) to this file.")
     add_engine_args(parser)
     return parser
@@ -131,24 +125,14 @@ def cli(argv=None):
     if args.redraw and args.subset_strategy == "in_order":
         raise ValueError("redraw is set, but subset_strategy is 'in_order', so all the draws will be the same. "
                          "That's probably not what you're trying to do.")
-    mask_distance = float("inf") if args.mask_distance is None else args.mask_distance
-    if mask_distance < 1:
-        raise ValueError("mask distance must be an integer >= 1.")
-    sampler = ESM_MSA_sampler(models.ESM_MSA1(checkpoint=args.checkpoint, precision=args.precision, synthetic=args.synthetic_weights), device=args.device)
-    input_handle = open(args.i) if args.i is not None else sys.stdin
-    output_handle = open(args.o, "w") if args.o is not None else sys.stdout
-    try:
-        with open(args.reference_msa) as reference_msa_handle:
-            main(input_h=input_handle, output_h=output_handle, masking_off=args.masking_off, sampler=sampler,
-                 reference_msa_handle=reference_msa_handle, delete_insertions=args.delete_insertions, batch_size=args.batch_size,
-                 subset_strategy=args.subset_strategy, alignment_size=args.alignment_size, subset_random_seed=args.subset_random_seed,
-                 redraw=args.redraw, unaligned_queries=args.unaligned_queries, mask_distance=mask_distance, csv=args.csv,
-                 positionwise=args.positionwise, keep_identical=args.keep_identical)
-    finally:
-        if args.i is not None:
-            input_handle.close()
-        if args.o is not None:
-            output_handle.close()
+    mask_distance = mask_distance_from(args, refuse_with_masking_off=False)       # this front end never refused the pair
+    sampler = ESM_MSA_sampler(models.ESM_MSA1(**model_kwargs(args)), device=args.device)
+    with open_io(args) as (input_handle, output_handle), open(args.reference_msa) as reference_msa_handle:
+        main(input_h=input_handle, output_h=output_handle, masking_off=args.masking_off, sampler=sampler,
+             reference_msa_handle=reference_msa_handle, delete_insertions=args.delete_insertions, batch_size=args.batch_size,
+             subset_strategy=args.subset_strategy, alignment_size=args.alignment_size, subset_random_seed=args.subset_random_seed,
+             redraw=args.redraw, unaligned_queries=args.unaligned_queries, mask_distance=mask_distance, csv=args.csv,
+             positionwise=args.positionwise, keep_identical=args.keep_identical)
 
 
 if __name__ == "__main__":

@@ -8,10 +8,9 @@ log-probabilities (columns named by residue, in the sampler's token order) and t
 The score of a substitution is row[mutant] - row[wt]."""
 import argparse
 import csv
-import sys
 import textwrap
 
-from ._cli import RawAndDefaultsFormatter, add_engine_args
+from ._cli import RawAndDefaultsFormatter, add_engine_args, add_scoring_args, mask_distance_from, model_kwargs, open_io
 from .esm_sampler import ESM_sampler
 from .fasta_io import parse_fasta
 from .likelihood_esm import model_map
@@ -67,38 +66,21 @@ def build_parser():
     writes a tab separated output file with columns:
     sequence name, position, wild type, 20 log-probabilities, entropy
     """), formatter_class=RawAndDefaultsFormatter)
-    parser.add_argument("-o", type=str, default=None, help="output table (default: stdout)")
-    parser.add_argument("-i", default=None, help="A fasta file with sequences to score. Gaps and stop codons are removed first.")
-    parser.add_argument("--batch_size", type=int, default=None, help="masked copies of a sequence per forward (default: the number of sequences in the input, as ESM_sampler.log_likelihood_batch counts it).")
-    parser.add_argument("--device", type=str, default="gpu", help="gpu (cuda:0) or cuda:[int]")
-    parser.add_argument("--masking_off", action="store_true", default=False, help="If set, no masking is done.")
-    parser.add_argument("--mask_distance", type=int, default=None,
-                        help="mask several positions per copy, (mask_distance - 1) unmasked positions apart. Default: one position at a time.")
-    parser.add_argument("--model", type=str, default="esm1v", choices=sorted(model_map), help="Which model to use.")
+    add_scoring_args(parser, "A fasta file with sequences to score. Gaps and stop codons are removed first.", None,
+                     "masked copies of a sequence per forward (default: the number of sequences in the input, as "
+                     "ESM_sampler.log_likelihood_batch counts it).", model_choices=model_map)
     parser.add_argument("--normalise", type=str, default="vocab", choices=["vocab", "columns"],
                         help="vocab: log-softmax over the model's whole vocabulary (as likelihood_esm); columns: over the 20 residues only.")
-    parser.add_argument("--csv", action="store_true", default=False, help="If set, then output will be a csv file.")
     add_engine_args(parser)
     return parser
 
 
 def cli(argv=None):
     args = build_parser().parse_args(argv)
-    mask_distance = float("inf") if args.mask_distance is None else args.mask_distance
-    if mask_distance < 1:
-        raise ValueError("mask distance must be an integer >= 1.")
-    if args.masking_off and args.mask_distance is not None:
-        raise ValueError("--masking_off and --mask_distance are both set, that doesn't make sense.")
-    sampler = ESM_sampler(model_map[args.model](checkpoint=args.checkpoint, precision=args.precision, synthetic=args.synthetic_weights), device=args.device)
-    input_handle = open(args.i) if args.i is not None else sys.stdin
-    output_handle = open(args.o, "w", newline="") if args.o is not None else sys.stdout
-    try:
+    mask_distance = mask_distance_from(args)
+    sampler = ESM_sampler(model_map[args.model](**model_kwargs(args)), device=args.device)
+    with open_io(args, newline="") as (input_handle, output_handle):
         main(input_handle, output_handle, args.masking_off, mask_distance, args.batch_size, args.normalise, args.csv, sampler)
-    finally:
-        if args.i is not None:
-            input_handle.close()
-        if args.o is not None:
-            output_handle.close()
 
 
 if __name__ == "__main__":

@@ -80,7 +80,6 @@ def run_sharded(ctx, tokens, table, row_id_base, rows_per_item, run_fn, device=N
     run again in bf16 (engine.py); the single-GPU call would then have run the WHOLE batch in bf16, so the ranks agree first (one
     all-gather of a flag) and, if any block overflowed, every other rank repeats its block in bf16 too -- the gathered result
     stays bit-identical with the single-GPU run."""
-    import torch
     B = tokens.shape[0]
     lo, hi = shard_range(B, ctx.world, ctx.rank)
     local = np.ascontiguousarray(tokens[lo:hi])
@@ -97,13 +96,19 @@ def run_sharded(ctx, tokens, table, row_id_base, rows_per_item, run_fn, device=N
             local = np.ascontiguousarray(tokens[lo:hi])
             with guard.forced_bf16():
                 run_fn(local, np.ascontiguousarray(table[:, lo:hi]), row_id_base + lo * rows_per_item)
-    counts = [shard_range(B, ctx.world, r)[1] - shard_range(B, ctx.world, r)[0] for r in range(ctx.world)]
+    return gather_blocks(ctx, local, B, device)
+
+
+def gather_blocks(ctx, local, n_items, device=None):
+    """The one collective of a sharded job: rank r holds the block shard_range(n_items, world, r) of an [n_items, ...] integer
+    array as the numpy array `local`; every rank gets the whole array back.  Gloo gathers host tensors, any other backend
+    gathers on `device`."""
+    import torch
+    counts = [hi - lo for lo, hi in (shard_range(n_items, ctx.world, r) for r in range(ctx.world))]
     t = torch.from_numpy(local)
-    on_gpu = ctx.dist.get_backend() != "gloo"
-    if on_gpu:
+    if ctx.dist.get_backend() != "gloo":
         t = t.to(device if device is not None else "cuda")
-    full = gather_tokens(ctx.dist, t, counts)
-    return full.cpu().numpy() if on_gpu else full.numpy()
+    return gather_tokens(ctx.dist, t, counts).cpu().numpy()
 
 
 def shard_range(n_items, world_size, rank):

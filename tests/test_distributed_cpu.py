@@ -10,6 +10,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from protein_gibbs_sampler_amd import pyrandom, sharding
+from _fake_engine import fake_engine_model as _fake_engine_model
 
 B, L, P, ITERS = 10, 40, 4, 3
 
@@ -86,57 +87,6 @@ def test_shard_range_covers_everything():
 
 
 # ---- the product entry point: ESM_sampler.generate / ESM_MSA_sampler.generate over torch.distributed ranks --------------
-def _fake_engine_model(msa):
-    """A plug-in whose `.model` is a NativeMaskedLM subclass with the device call replaced by a deterministic function of
-    (global Philox row id, iteration, slot): what the sharded generate() must reproduce for any number of ranks."""
-    from protein_gibbs_sampler_amd.alphabet import Alphabet
-    from protein_gibbs_sampler_amd.engine import NativeMaskedLM
-
-    class FakeLM(NativeMaskedLM):
-        def __init__(self):
-            self.calls = []
-            self.job_items = []
-
-        def set_job_items(self, n):          # the samplers announce the whole batch around every shard call and reset it
-            self.job_items.append(int(n))
-
-        def eval(self):
-            return self
-
-        def to(self, device):
-            return self
-
-        def gibbs_run(self, tokens, target_idx, params, want_logits=False, want_tokens=False):
-            self.calls.append(tokens.shape)
-            flat = tokens.reshape(-1, tokens.shape[-1])
-            idx = np.asarray(target_idx).reshape(target_idx.shape[0], -1, target_idx.shape[-1])
-            for it in range(idx.shape[0]):
-                for r in range(flat.shape[0]):
-                    for p in range(idx.shape[2]):
-                        flat[r, idx[it, r, p]] = 4 + ((params.row_id_base + r) * 7 + it * 3 + p + params.rng_seed) % 20
-            return None, None
-
-        def gibbs_single_batch_run(self, tokens, mask_row, target_row, step_idx, step_sample, params_list, want_logits=False,
-                                   want_tokens=False):
-            self.calls.append(tokens.shape)
-            for s_i in range(step_idx.shape[0]):
-                for b in range(tokens.shape[0]):
-                    for p, pos in enumerate(step_idx[s_i, b]):
-                        if pos >= 0:
-                            tokens[b, mask_row, pos] = 32
-                            tokens[b, target_row, pos] = 4 + (params_list[b].rng_seed * 5 + s_i * 3 + p + int(step_sample[s_i])) % 20
-            return None, None
-
-    class Plug:
-        pass
-
-    plug = Plug()
-    plug.alphabet = Alphabet(True, not msa)
-    plug.batch_converter = plug.alphabet.get_batch_converter(msa=msa)
-    plug.model = FakeLM()
-    return plug
-
-
 def _generate_both(seed, shard=True, esm_seeds=("MEPAATGQEAEECAHSGRGEAW", "MKPAATGQEA")):
     """ESM: 2 batches of 5 chains (ragged split 3 + 2 over two ranks); MSA: 2 rounds of 3 MSAs x 2 rows."""
     import torch as _t
