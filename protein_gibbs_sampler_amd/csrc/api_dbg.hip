@@ -452,7 +452,7 @@ int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx,
   int rc = dbg_precision("pg_dbg_attention_kv", precision, true);
   if (rc) return rc;
   if (!qkv || !ctx || B < 1 || T < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
-  if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B)");
   if (!bias_k != !bias_v) return fail(PG_ERR_INVALID, "pg_dbg_attention_kv: bias_k and bias_v come together or not at all");
   const std::string head_err = attention_head_error(head_dim, bias_k != nullptr);      // the plans' own refusal of a bias key at head 32
   if (!head_err.empty()) return fail(PG_ERR_INVALID, head_err);
@@ -499,12 +499,12 @@ int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
   return pg_dbg_rope_hd(device, precision, qkv, B, T, H, 64);
 }
 
-/* pg_dbg_rope with the head dimension: 64 (H <= 40) or 32 (H <= 32) */
+/* pg_dbg_rope with the head dimension: 64 (H <= 40), 32 (H <= 32) or 128 (H <= 40) */
 int pg_dbg_rope_hd(int device, int precision, float* qkv, int B, int T, int H, int head_dim) {
   int rc = dbg_precision("pg_dbg_rope_hd", precision, true);
   if (rc) return rc;
-  if (head_dim != 64 && head_dim != 32) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32");
-  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 64 ? 40 : 32)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B)");
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 32 ? 32 : 40)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
   Dbg s;
   if ((rc = s.open(device))) return rc;
   const int d = H * head_dim;
@@ -581,8 +581,8 @@ int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx
 extern "C++" {
 namespace {
 int dbg_row_width(const char* who, int d) {
-  if (d < 4 || d % 4 || d > 2560) return      // row_d_ok of elementwise.hip
-    fail(PG_ERR_INVALID, std::string(who) + ": d must be a multiple of 4 and <= 2560");
+  if (d < 4 || d % 4 || (d > 2560 && (d % 512 || d > 5120))) return      // row_d_ok of elementwise.hip
+    fail(PG_ERR_INVALID, std::string(who) + ": d must be a multiple of 4 and <= 2560, or a multiple of 512 up to 5120");
   return PG_OK;
 }
 // the token row a gather reads for selected row r (what gather_ln_bf16_kernel / gather_rows_kernel compute), -1 = none (zeros);
@@ -762,7 +762,7 @@ int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* 
   const float* dob = s.up(out_bias, (size_t)V);
   float* dl = s.up(logits, (size_t)n * V);      // the caller's pattern
   if ((rc = s.check(kCopyFailed))) return rc;
-  if (small_kernel) *small_kernel = lm_tail_small(n) ? 1 : 0;
+  if (small_kernel) *small_kernel = lm_tail_small(n, d) ? 1 : 0;
   if ((rc = launch_lm_tail(nullptr, dg, dga, dbe, de, dob, dl, n, d, V, eps))) return rc;
   return s.down(logits, dl, (size_t)n * V);
 }

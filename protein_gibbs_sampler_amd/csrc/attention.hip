@@ -4,7 +4,8 @@
 // `self.model.model(batch)["logits"]` (/root/reference/src/pgen/esm_sampler.py:223).
 //
 // CDNA4 mapping, written for head dim HD = 64 (ESM-1b, MSA-1b, ESM-2 650M / 3B); HD = 32 (ESM-2 150M) is the same kernel with half
-// the LDS row, one score MFMA per key block and two output blocks (attn_frag.h):
+// the LDS row, one score MFMA per key block and two output blocks; HD = 128 (ESM-2 15B) with twice the row, four score MFMAs and eight
+// output blocks, whole sequences up to 288 keys and 128-key tiles beyond (attn_frag.h):
 //   * grid = B*H workgroups of 4 waves; K and V (both row-major, XOR-swizzled 16-B chunks) live in LDS for
 //     the whole sequence (T <= 576: 2 x 72 KB) and are shared by all query blocks; longer sequences use
 //     attention_long_kernel (288-key tiles, online softmax).
@@ -50,15 +51,25 @@ __device__ unsigned long long* pg_att_prof;      // [workgroup][wave][8 slots][8
 // workgroups per CU on every rung (what limits a rung is the score row in registers, 4 VGPRs per key block, not the LDS -- which is
 // also why the whole-sequence kernel still ends at 576 keys).  The plain and SPLIT head-32 forms compile to <= 128 VGPRs up to 20 key
 // blocks and <= 168 up to 26 without a tighter bound, so four / three workgroups are resident there (DESIGN 10 has the table).
-constexpr int attention_occupancy(int maxkb, int hd) { return hd == 64 ? (maxkb <= 18 ? 2 : 1) : 2; }
+// HD = 128: K + V are MAXKB * 8 KB of LDS, so two workgroups share a CU up to 10 key blocks (2 x 80 KB, as head 64's rung 20) and one
+// holds it alone on rungs 12 .. 18; the launch bound follows the LDS.  The K look-ahead is two key blocks there (kbuf[2][2][4] = 64
+// VGPRs; the six of head 64 would be 192), the V look-ahead stays two chunks (vbuf[3][8] = 96 VGPRs).
+// (the PADMASK form of 10 blocks adds 160 flag bytes to the 80 KB and is alone on its CU: pad = true asks for 1 there)
+constexpr int attention_occupancy(int maxkb, int hd, bool pad = false) {
+  return hd == 128 ? (maxkb <= 8 || (maxkb == 10 && !pad) ? 2 : 1) : hd == 64 ? (maxkb <= 18 ? 2 : 1) : 2;
+}
 // Workgroups per CU that the HOST counts with when it splits a partial last round (plan_attention): what is resident, not what the
 // launch bound asks the compiler for.  Head 64: two up to 20 key blocks, one beyond.  The two functions differ at kb = 20: its
 // 2 x 80 KB of LDS fit a CU and the plain and SPLIT forms, compiled under the looser bound of 1, still come out at 158 VGPRs + 88
 // AGPRs = two waves per SIMD, so two workgroups do share a CU there and the split counts two.  Head 32: four / three / two (the
 // VGPR figures above).
-constexpr int attention_resident(int kb, int hd) { return hd == 64 ? (kb <= 20 ? 2 : 1) : (kb <= 20 ? 4 : (kb <= 26 ? 3 : 2)); }
+// Head 128 (the plain and SPLIT forms; DESIGN 10 has the table): four at 4 key blocks (32 KB, 124 VGPRs), three at 6 (48 KB, 160
+// VGPRs), two up to 10 (80 KB), one beyond -- the LDS decides from 8 blocks on.
+constexpr int attention_resident(int kb, int hd) {
+  return hd == 128 ? (kb <= 4 ? 4 : (kb <= 6 ? 3 : (kb <= 10 ? 2 : 1))) : hd == 64 ? (kb <= 20 ? 2 : 1) : (kb <= 20 ? 4 : (kb <= 26 ? 3 : 2));
+}
 template <int MAXKB, bool PADMASK, bool BIASKV = false, bool SPLIT = false, int HD = 64>
-__global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
+__global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD, PADMASK)) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
                                                        int H, int ld_qkv_, int ld_ctx_, int k_off, int v_off,
                                                        SeqLayout sl, const int32_t* __restrict__ key_tok, int pad_idx,
                                                        const bf16_t* __restrict__ bias_kv, int split_from = 0, int split = 1) {
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention
     {
       // K fragments are fetched one chunk (CH key blocks) ahead of the MFMAs that use them: with 2 waves per SIMD
       // the LDS latency must be covered inside the wave (PMC: 44 % of wave cycles were s_waitcnt before this)
-      constexpr int CH = (MAXKB % 6 == 0) ? 6 : (MAXKB % 4 == 0 ? 4 : 2);
+      constexpr int CH = HD == 128 ? 2 : (MAXKB % 6 == 0) ? 6 : (MAXKB % 4 == 0 ? 4 : 2);
       bf16x8 kbuf[2][CH][NKK];
       auto load_chunk = [&](int ch, bf16x8 (&dst)[CH][NKK]) {
 #pragma unroll
@@ -152,6 +163,13 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention
 #pragma unroll
           for (int u = 0; u < CH; ++u)
             st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][1], qf[1], st[ch * CH + u]);
+        }
+        if constexpr (NKK == 4) {                      // head 128: three more sweeps, one per 32 d
+#pragma unroll
+          for (int kk = 1; kk < 4; ++kk)
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+              st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][kk], qf[kk], st[ch * CH + u]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -217,6 +235,7 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention
     if (q < T) store_ctx(o, inv, ctx + row0 * ld_ctx_ + (size_t)q * ld_ctx + h * HD + fq * 4);
     qf[0] = qn[0];
     if constexpr (NKK == 2) qf[1] = qn[1];
+    if constexpr (NKK == 4) { qf[1] = qn[1]; qf[2] = qn[2]; qf[3] = qn[3]; }
     PG_T(qb >> 2, 4);
   }
   PG_T(7, 3);
@@ -231,6 +250,7 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD)) void attention
 // MAXKB = 16-key blocks per tile (even), OCC = workgroups per CU the register / LDS budget is set for: <18, 2> is the long-sequence
 // kernel.  <10, 4> (160-key tiles, four workgroups per CU, 117 VGPRs) and <12, 3> were measured at config 2 in round 4 against
 // attention_kernel: 9.1 / 11.1 ms per iteration against 7.0 (EXPERIMENTS.md) -- every 64-query workgroup re-stages the head's K / V.
+// Head 128: <8, 2> -- 128-key tiles, 64 KB + 128 flag bytes, the tallest even tile of which two fit a CU (attn_frag.h).
 template <int MAXKB, int OCC, bool PADMASK, bool BIASKV, int HD = 64>
 __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
                                                                int H, int ld_qkv_, int ld_ctx_, int k_off, int v_off,
@@ -361,9 +381,13 @@ static AttentionPlan plan_attention(int64_t n_seq, int T, int H, int head_dim, b
   if (T <= 0) return refuse("attention: empty sequence");
   // The rung: the T tokens + ESM-1's bias_k / bias_v key.  The forms without the bias key (the Gibbs path, and ragged batches)
   // take the fine ladder: a chain of 200 residues has 13 key blocks, not 18.
-  p.kb = attention_rung(T + (has_bias ? 1 : 0), attention_fine_ladder() && !has_bias);
+  // PGIBBS_ATTN_HD128_WHOLE=0: head 128 takes the tiled kernel at every length (the A/B switch of the whole-sequence form there)
+  static const int whole128 = env_int("PGIBBS_ATTN_HD128_WHOLE", 1);
+  p.kb = head_dim == 128 && !whole128 ? 0
+                                      : attention_rung(T + (has_bias ? 1 : 0), attention_fine_ladder() && !has_bias, attention_max_keys(head_dim));
   p.whole = p.kb != 0;
-  if (!p.whole) {                                // more than 576 keys: 288-key tiles (at head 32: 36 KB of LDS for K + V)
+  if (!p.whole) {                                // more than 576 keys: 288-key tiles (at head 32: 36 KB of LDS for K + V);
+                                                 // head 128: more than 288 keys, 128-key tiles
     p.n_qchunk = (T + 63) / 64;
     if (pairs * p.n_qchunk > 0x7fffffff) return refuse("attention: too many sequences");
     p.grid = (unsigned)(pairs * p.n_qchunk);
@@ -394,7 +418,7 @@ static AttentionPlan plan_attention(int64_t n_seq, int T, int H, int head_dim, b
 static std::string plan_text(const AttentionPlan& p) {
   if (!p.error.empty()) return "error: " + p.error;
   if (!p.grid) return "nothing";
-  std::string t = (p.whole ? "whole kb" + std::to_string(p.kb) : std::string("long t288")) + " hd" + std::to_string(p.hd);
+  std::string t = (p.whole ? "whole kb" + std::to_string(p.kb) : std::string(p.hd == 128 ? "long t128" : "long t288")) + " hd" + std::to_string(p.hd);
   if (p.pad) t += " pad";
   if (p.bias) t += " bias";
   if (p.split > 1) return t + " split" + std::to_string(p.split) + " " + std::to_string(p.split_from) + "+" + std::to_string(p.grid - p.split_from) + "wg";
@@ -413,11 +437,13 @@ static void launch_rung(bool pad, bool bias, bool split, dim3 grid, hipStream_t 
     if (bias && pad) return go(attention_kernel<KB, true, true, false, HD>);
     if (bias) return go(attention_kernel<KB, false, true, false, HD>);
   }
-  if (pad) go(attention_kernel<KB, true, false, false, HD>);
-  else if (split) go(attention_kernel<KB, false, false, true, HD>);
-  else go(attention_kernel<KB, false, false, false, HD>);
+  if constexpr (KB * 16 <= attention_max_keys(HD)) {      // head 128 above rung 18 is not built, and the plan never asks for it
+    if (pad) go(attention_kernel<KB, true, false, false, HD>);
+    else if (split) go(attention_kernel<KB, false, false, true, HD>);
+    else go(attention_kernel<KB, false, false, false, HD>);
+  }
 }
-// the long kernel's <PADMASK, BIASKV> form; no bias key at head 32
+// the long kernel's <PADMASK, BIASKV> form; no bias key at head 32 / 128; 128-key tiles at head 128, else 288
 template <int HD, class... Args>
 static void launch_long(bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
   auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
@@ -425,8 +451,9 @@ static void launch_long(bool pad, bool bias, dim3 grid, hipStream_t s, Args... a
     if (bias && pad) return go(attention_long_kernel<18, 2, true, true, HD>);
     if (bias) return go(attention_long_kernel<18, 2, false, true, HD>);
   }
-  if (pad) go(attention_long_kernel<18, 2, true, false, HD>);
-  else go(attention_long_kernel<18, 2, false, false, HD>);
+  constexpr int KB = HD == 128 ? 8 : 18;
+  if (pad) go(attention_long_kernel<KB, 2, true, false, HD>);
+  else go(attention_long_kernel<KB, 2, false, false, HD>);
 }
 
 int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int64_t n_seq, int T, int H, int ld_qkv,
@@ -447,6 +474,7 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
     });
   };
   if (head_dim == 64) launch(std::integral_constant<int, 64>{});
+  else if (head_dim == 128) launch(std::integral_constant<int, 128>{});
   else launch(std::integral_constant<int, 32>{});
   PG_HIP(hipGetLastError());
   return 0;

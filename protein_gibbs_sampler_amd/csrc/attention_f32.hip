@@ -33,7 +33,7 @@ __device__ __forceinline__ void store_ctx64(const float (&o)[64], float inv, bf1
 
 // Building blocks shared by the three split-bf16 MFMA kernels (full attention, tied-row scores, tied-row apply).
 // Fragment geometry, tile layout and the transposing V^T read: attn_frag.h.
-// HD: the head dimension, 64 or 32 (attn_frag.h; 32 is built for the full attention only)
+// HD: the head dimension, 64, 32 or 128 (attn_frag.h; 32 and 128 are built for the full attention only)
 template <int MAXKB, int HD = 64>
 struct SplitAttn {
   static constexpr int tpad = MAXKB * 16, nkc = MAXKB / 2;
@@ -628,7 +628,7 @@ int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores,
 struct StrictAttentionPlan {
   std::string error;               // not empty: the call is refused (error code 1)
   bool valu = false;               // attention_f32_kernel, 64 threads; else attention_split_kernel<kb, nqb>, 256 threads
-  int kb = 0, nqb = 1, hd = 64;    // key blocks per tile and 16-query blocks per wave: one of the seven pairs that are built
+  int kb = 0, nqb = 1, hd = 64;    // key blocks per tile and 16-query blocks per wave: one of the pairs that are built
   bool pad = false, bias = false;  // the split kernel's PADMASK / BIASKV form
   unsigned grid = 0;               // 0: no sequences, nothing to launch
   int n_qchunk = 0;                // chunks of 64 * nqb queries per (sequence, head) pair
@@ -640,7 +640,8 @@ static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int h
   p.error = attention_head_error(head_dim, has_bias);
   if (!p.error.empty()) return p;
   if (head_dim != 64 && p.valu)
-    return refuse("attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
+    return refuse(head_dim == 128 ? "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 128"
+                                  : "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
   if (n_seq == 0) return p;
   if (T <= 0) return refuse("attention: empty sequence");
   if (has_bias && p.valu) return refuse("attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)");
@@ -672,6 +673,19 @@ static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int h
     }
     if (kb_env == 6 || kb_env == 8 || kb_env == 10) p.kb = kb_env;
   }
+  // Head 128: the four tiles (hi + lo of K and of V, 256-byte rows) are 1 KB per key, so the 80 KB that leave room for two workgroups
+  // per CU hold 80 keys and the tallest even block count is 4: 64-key tiles (64 KB) at every length.  The taller tiles of heads 64 /
+  // 32 would be 96 - 160 KB, one workgroup per CU -- the form that was 1.6x slower at head 64 --, so PGIBBS_ATTN_F32_KB is not read.
+  // Five query blocks per wave would be o[5][8] = 160 accumulator registers and spill under the two-workgroup bound: three at most.
+  if (head_dim == 128) {
+    p.kb = 4;
+    if (p.nqb > 3) {
+      p.nqb = 3;
+      p.n_qchunk = (T + 64 * 3 - 1) / (64 * 3);
+      if (n_seq * H * p.n_qchunk > 0x7fffffff) return refuse("attention: too many sequences");
+      p.grid = (unsigned)(n_seq * H * p.n_qchunk);
+    }
+  }
   return p;
 }
 static std::string plan_text(const StrictAttentionPlan& p) {
@@ -687,13 +701,24 @@ void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has
   *text = plan_text(plan_attention_f32(n_seq, T, H, head_dim, has_pad, has_bias, row_step));
 }
 
-// one (key tile, query blocks) pair of the split kernel: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32
+// one (key tile, query blocks) pair of the split kernel: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32 / 128.
+// Head 128 runs 64-key tiles with 1, 2 or 3 query blocks per wave (plan_attention_f32); heads 64 / 32 pair 64-key tiles with one
+// query block only, so <4, 2> and <4, 3> exist at head 128 alone
+// false: the pair is not built at this head width and nothing was launched (the launcher turns that into an error)
 template <int KB, int NQB, class... Args>
-static void launch_split(int hd, bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
-  auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
-  if (hd == 32) return pad ? go(attention_split_kernel<KB, NQB, false, true, 32>) : go(attention_split_kernel<KB, NQB, false, false, 32>);
-  if (bias) return pad ? go(attention_split_kernel<KB, NQB, true, true>) : go(attention_split_kernel<KB, NQB, true, false>);
-  return pad ? go(attention_split_kernel<KB, NQB, false, true>) : go(attention_split_kernel<KB, NQB, false, false>);
+static bool launch_split(int hd, bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
+  auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); return true; };
+  if constexpr (KB == 4) {
+    if (hd == 128) return pad ? go(attention_split_kernel<KB, NQB, false, true, 128>) : go(attention_split_kernel<KB, NQB, false, false, 128>);
+  } else {
+    if (hd == 128) return false;
+  }
+  if constexpr (KB != 4 || NQB == 1) {
+    if (hd == 32) return pad ? go(attention_split_kernel<KB, NQB, false, true, 32>) : go(attention_split_kernel<KB, NQB, false, false, 32>);
+    if (bias) return pad ? go(attention_split_kernel<KB, NQB, true, true>) : go(attention_split_kernel<KB, NQB, true, false>);
+    return pad ? go(attention_split_kernel<KB, NQB, false, true>) : go(attention_split_kernel<KB, NQB, false, false>);
+  }
+  return false;
 }
 
 int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
@@ -703,14 +728,17 @@ int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split
   if (!p.error.empty()) return fail(1, p.error);
   if (!p.grid) return 0;
   note_kernel(plan_text(p).c_str());
+  bool launched = true;
   auto split = [&](auto kb, auto nqb) {
-    launch_split<decltype(kb)::value, decltype(nqb)::value>(p.hd, p.pad, p.bias, dim3(p.grid), s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx,
+    launched = launch_split<decltype(kb)::value, decltype(nqb)::value>(p.hd, p.pad, p.bias, dim3(p.grid), s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx,
                                                             k_off, v_off, sl, p.n_qchunk, key_tok, pad_idx, bias_kv);
   };
   using std::integral_constant;
   if (p.valu)
     hipLaunchKernelGGL(attention_f32_kernel, dim3(p.grid), dim3(64), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl,
                        p.n_qchunk, key_tok, pad_idx);
+  else if (p.kb == 4 && p.nqb == 2) split(integral_constant<int, 4>{}, integral_constant<int, 2>{});      // nqb > 1 at 64-key tiles: head 128
+  else if (p.kb == 4 && p.nqb == 3) split(integral_constant<int, 4>{}, integral_constant<int, 3>{});
   else if (p.kb == 4) split(integral_constant<int, 4>{}, integral_constant<int, 1>{});
   else if (p.kb == 6) split(integral_constant<int, 6>{}, integral_constant<int, 5>{});
   else if (p.kb == 8) split(integral_constant<int, 8>{}, integral_constant<int, 5>{});
@@ -718,6 +746,7 @@ int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split
   else if (p.nqb == 2) split(integral_constant<int, 10>{}, integral_constant<int, 2>{});
   else if (p.nqb == 3) split(integral_constant<int, 10>{}, integral_constant<int, 3>{});
   else split(integral_constant<int, 10>{}, integral_constant<int, 5>{});
+  if (!launched) return fail(1, "attention: the strict kernel is not built for this (key tile, query blocks, head dimension)");
   PG_HIP(hipGetLastError());
   return 0;
 }

@@ -11,7 +11,8 @@
 //
 // The head dimension is the template parameter HD of everything that touches a tile or the context: 64 (the default: ESM-1b,
 // ESM-1, MSA-1b, ESM-2 650M / 3B -- every caller that names no HD is the head-64 form, instruction for instruction what it was
-// before HD existed) or 32 (ESM-2 150M).  Softmax, masks, p_frag and the key-block ladder do not depend on it.
+// before HD existed), 32 (ESM-2 150M) or 128 (ESM-2 15B).  Softmax, masks and p_frag do not depend on it; the key-block ladder ends
+// at 18 blocks at 128 (below).
 //
 // Geometry (head dim 64).  A K or V tile is row-major in LDS, one key per 128-byte row, the row's eight 16-byte chunks
 // XOR-swizzled with (row & 7).  fr = lane & 15 is the lane's query (the MFMA column), fq = lane >> 4.
@@ -40,6 +41,25 @@
 //     chunks of two neighbouring rows = one whole 128-byte line, whatever permutation the swizzle applies inside each row.
 // Packing two keys into one 128-byte row and keeping the head-64 swizzle was the alternative; it needs a second row index
 // (key >> 1) and chunk base ((key & 1) * 4) in every address and gives the same bank picture, so the 64-byte row was built.
+//
+// Geometry (head dim 128).  One key per 256-byte row of sixteen 16-byte chunks = exactly one bank row: unswizzled, chunk c of EVERY
+// key sits on slot c.  FOUR v_mfma_f32_16x16x32 steps contract the head (k_frag: chunk 4 kk + fq of key row fr), eight output blocks
+// o[8].  The swizzle is  chunk ^ ((row & 7) << 1)  -- the low three bits of the key row pick one of the eight 32-byte chunk pairs.
+// By the same bank rules:
+//   * the score fragment (ds_read_b128): a group of 16 lanes holds rows {0-3, 12-15} at one chunk c and rows {4-11} at chunk c ^ 1 and
+//     needs all sixteen slots.  Unswizzled they land on two: an 8-way conflict on every read.  g(r) = (r & 7) << 1 is even, and over
+//     either set of eight rows r & 7 takes every value once ({12-15} give 4-7; {4-11} give 4-7, 0-3): the first set covers the eight
+//     slots c ^ {0, 2, .. 14}, the second the eight slots c ^ 1 ^ {0, 2, .. 14} -- together all sixteen, conflict-free.  (chunk ^
+//     (row & 15), a plain 4-bit analogue of the head-64 form, also serves this read but fails the next one.)
+//   * the transposing read (ds_read_b64_tr_b16): a half of 32 lanes reads the 32 contiguous bytes of chunk pair db of 8 consecutive key
+//     rows (an aligned group of eight).  The swizzle never touches bit 0 of the chunk, so the pair stays 32 contiguous bytes, and pair
+//     db of row r sits in pair slot db ^ (r & 7): eight different slots = all 64 banks once.
+//   * the staging writes (ds_write_b128): 8 consecutive lanes write chunks 0-7 or 8-15 of one row; XOR with one constant maps either
+//     set onto one whole 128-byte half of the row, each chunk once.
+// LDS budget: K + V of MAXKB key blocks are MAXKB * 8 KB, so the whole-sequence kernel ends at rung 18 (288 keys, 144 KB + the pad
+// flags: one workgroup per CU; rung 20 would be the CU's whole 160 KB and is not built) and longer sequences take the tiled kernel
+// with 128-key tiles: 2 x 32 KB + 128 flag bytes per workgroup, the tallest even block count that leaves room for two workgroups
+// per CU (160-key tiles would be 80 KB + flags each: one too many bytes for two).
 #pragma once
 #include <type_traits>
 
@@ -61,8 +81,10 @@ constexpr bool coarse_rung(int kb) {
     if (r == kb) return true;
   return false;
 }
-inline int attention_rung(int n_keys, bool fine) {
-  if (n_keys > 576) return 0;
+// max_keys: the tallest rung's keys -- 576, or 288 at head dimension 128 (attention_max_keys)
+constexpr int attention_max_keys(int hd) { return hd == 128 ? 288 : 576; }
+inline int attention_rung(int n_keys, bool fine, int max_keys = 576) {
+  if (n_keys > max_keys) return 0;
   if (fine) return (((n_keys + 15) / 16) + 1) & ~1;
   for (int r : kCoarseRungs)
     if (n_keys <= r * 16) return r;
@@ -87,7 +109,7 @@ inline bool visit_rung(int kb, F&& f) {
 }
 // what the full-attention plans (attention.hip, attention_f32.hip) refuse before they look at the shape; empty: nothing
 inline std::string attention_head_error(int head_dim, bool has_bias) {
-  if (head_dim != 64 && head_dim != 32) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32";
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32";
   if (head_dim != 64 && has_bias) return "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only";
   return {};
 }
@@ -98,7 +120,8 @@ inline std::string attention_head_error(int head_dim, bool has_bias) {
 #define PG_TILE128_CHUNK(row, chunk) ((chunk) ^ ((row) & 7))
 template <int HD = 64>
 __device__ __forceinline__ int tile_swz(int row, int chunk) {
-  static_assert(HD == 64 || HD == 32, "head dimension 64 or 32");
+  static_assert(HD == 64 || HD == 32 || HD == 128, "head dimension 64, 32 or 128");
+  if constexpr (HD == 128) return (chunk ^ ((row & 7) << 1)) << 4;
   return (HD == 64 ? PG_TILE128_CHUNK(row, chunk) : chunk ^ ((row >> 1) & 2)) << 4;
 }
 template <int HD = 64>
@@ -113,7 +136,7 @@ struct TileRegs {
 };
 template <int TPAD, int NT, int HD>
 __device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT, HD>& g, int tid, char* dst) {
-  constexpr int CPR = HD / 8, CSH = HD == 64 ? 3 : 2;                     // 16-byte chunks per key row, and its log2
+  constexpr int CPR = HD / 8, CSH = HD == 128 ? 4 : (HD == 64 ? 3 : 2);                     // 16-byte chunks per key row, and its log2
 #pragma unroll
   for (int it = 0; it < TileRegs<TPAD, NT, HD>::NIT; ++it) {
     const int i = tid + it * NT, row = i >> CSH, c = i & (CPR - 1);
@@ -126,7 +149,7 @@ __device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT, HD>& g, int 
 template <int TPAD, int NT, bool EXTRA, int HD = 64>
 __device__ __forceinline__ void stage_kv(char* Ks, char* Vs, int tid, const bf16_t* src, size_t ld, int k_off, int v_off, int row0,
                                          int n_rows, const bf16_t* bias_k, const bf16_t* bias_v) {
-  constexpr int CPR = HD / 8, CSH = HD == 64 ? 3 : 2;                     // 16-byte chunks per key row, and its log2
+  constexpr int CPR = HD / 8, CSH = HD == 128 ? 4 : (HD == 64 ? 3 : 2);                     // 16-byte chunks per key row, and its log2
   constexpr int NIT = (TPAD * CPR + NT - 1) / NT;
   uint4 kreg[NIT], vreg[NIT];
 #pragma unroll

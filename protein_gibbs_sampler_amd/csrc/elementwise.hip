@@ -362,20 +362,23 @@ static inline unsigned rows_grid(int64_t rows) { return (unsigned)((rows + 3) / 
 // rows_grid's result is a 32-bit workgroup count; past it the launch would cover the first rows only
 static inline bool rows_fit(int64_t rows) { return rows >= 0 && (rows + 3) / 4 <= 0x7fffffffLL; }
 // the row kernels hold a row as float4 v[NCH] per lane: the 8-chunk instantiation up to d = 2048 (every model before ESM-2 3B runs
-// it, unchanged), the 10-chunk one up to d = 2560
-static inline bool row_d_ok(int d) { return d >= 4 && d % 4 == 0 && d <= kMaxChWide * 256; }
+// it, unchanged), the 10-chunk one up to d = 2560, the 20-chunk one for the whole 512-feature units above it up to d = 5120
+static inline bool row_d_ok(int d) {
+  return d >= 4 && d % 4 == 0 && (d <= kMaxChWide * 256 || (d % kRowUnit5k == 0 && d <= kMaxCh5k * 256));
+}
 static inline bool row_wide(int d) { return d > kMaxCh * 256; }
 // f(integral_constant<int, NCH>) for the NCH of a row of d values: a launcher names its kernel template once
 template <class F>
 static inline void by_row_width(int d, F&& f) {
-  if (row_wide(d)) f(std::integral_constant<int, kMaxChWide>{});
+  if (d > kMaxChWide * 256) f(std::integral_constant<int, kMaxCh5k>{});
+  else if (row_wide(d)) f(std::integral_constant<int, kMaxChWide>{});
   else f(std::integral_constant<int, kMaxCh>{});
 }
 // A row launcher's admission of (d, rows) under the kernel's name `who`.  false: the launcher returns *rc -- 1, refused with the
 // error set, or 0, no rows and nothing to do
 static bool rows_go(const char* who, int d, int64_t rows, int* rc) {
   *rc = 0;
-  if (!row_d_ok(d)) *rc = fail(1, std::string(who) + ": d must be a multiple of 4 and <= 2560");
+  if (!row_d_ok(d)) *rc = fail(1, std::string(who) + ": d must be a multiple of 4 and <= 2560, or a multiple of 512 up to 5120");
   else if (rows != 0 && !rows_fit(rows)) *rc = fail(1, std::string(who) + ": too many rows");
   return *rc == 0 && rows != 0;
 }
@@ -496,9 +499,11 @@ int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t*
 }
 
 // launch_lm_tail's choice between lm_tail_small_kernel (true) and lm_tail_kernel; pg_dbg_lm_tail reports it
-bool lm_tail_small(int64_t n) {
+// Rows wider than 2560 features always take lm_tail_kernel: a 1024-thread workgroup has 128 VGPRs per lane, which do not hold the 80
+// of a 20-chunk row next to the decoder chunks in flight (that instantiation spilled 28 bytes and is not built).  Same bits either way
+bool lm_tail_small(int64_t n, int d) {
   static const int small_max = env_int("PGIBBS_LM_TAIL_SMALL", 1024);
-  return n <= small_max;
+  return n <= small_max && d <= kMaxChWide * 256;
 }
 
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
@@ -509,16 +514,19 @@ int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const floa
   // identical arithmetic per logit (same per-lane partial sums, same wave reduction): bit-equal results.  Up to 1024 rows (round 5;
   // it was 128): a 32-chain shard's 800 sampled rows took 81 us on the row-per-wave kernel -- 200 workgroups, each wave walking the
   // decoder rows in nine dependent trips -- PGIBBS_LM_TAIL_SMALL=n moves the switch
-  const bool small = lm_tail_small(n);
+  const bool small = lm_tail_small(n, d);
   by_row_width(d, [&](auto nch) {
     constexpr int NCH = decltype(nch)::value;
     // small: no shared memory; every wave holds the row and four decoder rows' chunks (NCH + 4 float4 in flight at most: far below
     // the 128 VGPRs a 1024-thread workgroup may use per lane)
-    if (small)
-      hipLaunchKernelGGL(lm_tail_small_kernel<NCH>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
-                         logits, d, V, eps);
-    else
-      hipLaunchKernelGGL(lm_tail_kernel<NCH>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
+    if constexpr (NCH <= kMaxChWide) {
+      if (small) {
+        hipLaunchKernelGGL(lm_tail_small_kernel<NCH>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
+                           logits, d, V, eps);
+        return;
+      }
+    }
+    hipLaunchKernelGGL(lm_tail_kernel<NCH>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
   });
   PG_HIP(hipGetLastError());
   return 0;

@@ -3,6 +3,8 @@
 //   mask scatter -> forward -> LM head at the sampled rows -> draw + write-back
 // which replaces the reference's per-iteration Python loop
 // (/root/reference/src/pgen/esm_sampler.py:209-234) with zero host round trips per iteration.
+#include <algorithm>
+
 #include "engine.h"
 
 #include <math.h>
@@ -216,18 +218,28 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_MSA1B && cfg.arch != PG_ARCH_ESM1 && cfg.arch != PG_ARCH_ESM2) return fail(PG_ERR_INVALID, "unknown arch");
   if (prec != PG_PREC_BF16 && prec != PG_PREC_FP32 && prec != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
   if (cfg.d_model % 128 || cfg.d_ffn % 128) return fail(PG_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
-  // head width: the attention and rotary kernels are built for 64 (every architecture) and 32 (ESM-2 only: esm2_t30_150M_UR50D)
+  // head width: the attention and rotary kernels are built for 64 (every architecture), 32 and 128 (ESM-2 only: esm2_t30_150M_UR50D,
+  // esm2_t48_15B_UR50D)
   head_dim = cfg.n_heads > 0 && cfg.d_model % cfg.n_heads == 0 ? cfg.d_model / cfg.n_heads : 0;
   if (head_dim == 32 && cfg.arch != PG_ARCH_ESM2)
     return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
                                     " with heads of 32: head dim must be 64 for this architecture (heads of 32 run for PG_ARCH_ESM2 only)");
-  if (head_dim != 64 && head_dim != 32)
+  if (head_dim == 128 && cfg.arch != PG_ARCH_ESM2)
+    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
+                                    " with heads of 128: head dim must be 64 for this architecture (heads of 128 run for PG_ARCH_ESM2 only)");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128)
     return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " with " + std::to_string(cfg.n_heads) +
-                                    " heads: head dim must be 64 (every architecture) or 32 (PG_ARCH_ESM2)");
+                                    " heads: head dim must be 64 (every architecture), or 32 or 128 (PG_ARCH_ESM2)");
   if (head_dim == 32 && cfg.n_heads > 32)
     return fail(PG_ERR_INVALID, "heads of 32: the rotary kernel holds at most 32 of them per row (d_model <= 1024; esm2_t30_150M_UR50D has 20)");
-  // the row kernels (ln_row.h, rope.hip) hold a row of at most 2560 features per wave: 40 heads of 64, ESM-2 3B
-  if (cfg.d_model > 2560)
+  // heads of 128 (esm2_t48_15B_UR50D): at most 40 of them, and above 2560 features the row kernels take whole 512-feature units
+  if (head_dim == 128 && cfg.n_heads > 40)
+    return fail(PG_ERR_INVALID, "heads of 128: the rotary and row kernels hold at most 40 of them per row (d_model <= 5120; esm2_t48_15B_UR50D has 40), not " +
+                                    std::to_string(cfg.n_heads) + " (d_model " + std::to_string(cfg.d_model) + ")");
+  if (head_dim == 128 && cfg.d_model > 2560 && cfg.d_model % 512)
+    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " > 2560 with heads of 128: the row kernels take multiples of 512 up to 5120 there");
+  // the row kernels (ln_row.h, rope.hip) hold a row of at most 2560 features per wave at heads of 64 / 32: 40 heads of 64, ESM-2 3B
+  if (head_dim != 128 && cfg.d_model > 2560)
     return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " > 2560: the engine runs up to 40 heads of 64 (esm2_t36_3B_UR50D)");
   if (cfg.vocab < 1 || cfg.vocab > 64) return fail(PG_ERR_INVALID, "vocab must be in 1..64");
   int ndev = 0;
@@ -249,6 +261,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   // BEFORE they are rounded to the 16-bit operand (or split into the strict mode's bf16 pair) -- the kernels stay scale-free and
   // the only new rounding is that fp32 product, 2^-24 relative, under an operand rounding of 2^-9 / 2^-12 / 2^-17
   if (head_dim == 32) qs = 0.17677669529663687f;
+  if (head_dim == 128) qs = 0.08838834764831845f;      // 128^-0.5: the same fold
   bool ok = true;
   ok = ok && (embed = up.f32("embed_tokens.weight", (int64_t)V * d));
   // ESM-2 has no position table (pos stays null: embed_ln_kernel adds nothing) -- positions enter through the rotation of q and k
@@ -487,6 +500,10 @@ int Engine::size_activations(int64_t Mp) {
   if (Mp > 0x7fffffff / 4) return fail(PG_ERR_INVALID, "too many tokens in one call");
   const size_t d = cfg.d_model, f = cfg.d_ffn;
   const size_t w = strict() ? 3 : 1;                 // strict: h, ctx and ffn hold [lo | hi | hi] rows, qkv is fp32
+  // Heads of 128 (ESM-2 15B) are the first models whose 16-bit activation buffers pass 2^31 bytes in one call (fc1's output at config
+  // 2: 66048 x 20480 x 2 B = 2.7 GB; the strict mode's fp32 qkv 4.1 GB).  Every kernel that walks an [M][ld] buffer forms its row or
+  // band base as a 64-bit product and keeps only per-band offsets in 32 bits (the list: DESIGN.md section 10, "Buffers of 2 GB and
+  // more"), so no limit is set here beyond the row count above; tests/test_gpu_esm2_15b.py runs such a call against its shards.
   int rc;
   if ((rc = x.ensure((size_t)Mp * d * 4, stream))) return rc;
   if ((rc = h.ensure((size_t)Mp * w * d * 2, stream))) return rc;

@@ -155,7 +155,7 @@ int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t*
                        int64_t n_sel, int row_bytes, const int32_t* d_iter = nullptr);
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
                    const float* out_bias, float* logits, int64_t n, int d, int V, float eps);
-bool lm_tail_small(int64_t n);      // launch_lm_tail's choice: the workgroup-per-row kernel (n <= PGIBBS_LM_TAIL_SMALL, 1024)
+bool lm_tail_small(int64_t n, int d);      // launch_lm_tail's choice: the workgroup-per-row kernel (n <= PGIBBS_LM_TAIL_SMALL, 1024, and d <= 2560)
 int launch_f32_to_bf16(hipStream_t s, const float* src, bf16_t* dst, int64_t n, float scale);
 int launch_bf16_to_f32(hipStream_t s, const bf16_t* src, float* dst, int64_t n);
 int launch_scale_f32(hipStream_t s, float* p, int64_t n, float scale);

@@ -11,9 +11,13 @@ PG_OPS_BEGIN
 // A lane holds chunks lane, lane + 64, ... of the row as float4 v[NCH]: NCH is a template parameter of everything below, deduced
 // from the array.  kMaxCh = 8 (d <= 2048) is the form every model up to d_model 2048 runs, and the only one the residual GEMMs
 // (gemm_epilogue.h, gemm_rowln.hip) instantiate; kMaxChWide = 10 (d <= 2560: ESM-2 3B) costs 40 VGPRs per row instead of 32.
+// kMaxCh5k = 20 (d <= 5120: ESM-2 15B) holds 80 VGPRs of row; above 2560 only whole 512-feature units are accepted (3072, 3584, ..
+// 5120: kRowUnit5k), so every lane holds the same number of chunks there.
 // The arithmetic and its order -- per lane the chunks in ascending order, then wave_sum -- do not depend on NCH.
 constexpr int kMaxCh = 8;       // d <= 8 * 256 = 2048
 constexpr int kMaxChWide = 10;  // d <= 10 * 256 = 2560
+constexpr int kMaxCh5k = 20;    // d <= 20 * 256 = 5120, in units of kRowUnit5k
+constexpr int kRowUnit5k = 512;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -23,6 +23,9 @@
 // Heads of 32 (ESM-2 150M, template parameter HD): pairs (i, i + 16), the same rule with half the head -- 16-bit buffers 8 + 8 values =
 // the lane's 16 bytes and the 16 bytes 32 bytes higher, 2 lanes per head, 4 H lane-slots per row (80 at d = 640: two passes); fp32
 // buffers 4 + 4 values, 4 lanes per head, 8 H lane-slots (three passes at d = 640); the table row is [16 cos | 16 sin].
+// Heads of 128 (ESM-2 15B): pairs (i, i + 64), the same rule with twice the head -- 16-bit buffers 8 + 8 values = the lane's 16 bytes and
+// the 16 bytes 128 bytes higher, 8 lanes per head, 16 H lane-slots per row (640 at d = 5120: ten passes); fp32 buffers 4 + 4 values, 16
+// lanes per head, 32 H lane-slots (twenty passes at d = 5120, ten in flight at a time); the table row is [64 cos | 64 sin].
 // Grid: at most one resident round of workgroups (the kernel's occupancy x CUs), every wave walking rows row, row + waves, ... -- a mid-size
 // batch has no nearly empty last round (the reason layernorm_bf16_stride_kernel exists), and stores retire behind the next row's
 // loads.  Rows >= M (the 256-row padding of the activation buffers) are not touched.
@@ -37,6 +40,10 @@ constexpr int kRopePass32 = 8, kRopePass32Wide = 10;   // 16 H lane-slots / 64 l
 constexpr int kRopeHeads = 32, kRopeHeadsWide = 40;
 // heads of 32: up to 32 of them (d_model <= 1024; ESM-2 150M has 20) in 2 (16-bit: 4 H slots) and 4 (fp32: 8 H slots) passes
 constexpr int kRopePass16Hd32 = 2, kRopePass32Hd32 = 4;
+// heads of 128: up to 20 of them in 5 (16-bit: 16 H slots) and 10 (fp32: 32 H slots) passes, up to 40 (d_model 5120: ESM-2 15B) in 10 and 20
+constexpr int kRopePass16Hd128 = 5, kRopePass16Hd128Wide = 10;
+constexpr int kRopePass32Hd128 = 10, kRopePass32Hd128Wide = 20;
+constexpr int kRopeHeadsHd128 = 20, kRopeHeadsHd128Wide = 40;
 
 __device__ __forceinline__ void rope_pair(float& lo, float& hi, float c, float s) {
   const float a = lo, b = hi;
@@ -104,28 +111,62 @@ __global__ __launch_bounds__(256) void rope32_kernel(float* __restrict__ qkv, co
   for (int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6); row < M; row += stride) {
     const float4* tr = (const float4*)(tab + (size_t)(row % T) * HD);
     float4* base = (float4*)(qkv + (size_t)row * ld);           // 2 LPH float4 per head
-    float4 lo[NP], hi[NP];
+    if constexpr (NP <= 10) {
+      float4 lo[NP], hi[NP];
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int s = lane + 64 * i;
-      if (s < slots) {
-        const float4* p = base + (s / LPH) * (2 * LPH) + c;
-        lo[i] = p[0];
-        hi[i] = p[LPH];
+      for (int i = 0; i < NP; ++i) {
+        const int s = lane + 64 * i;
+        if (s < slots) {
+          const float4* p = base + (s / LPH) * (2 * LPH) + c;
+          lo[i] = p[0];
+          hi[i] = p[LPH];
+        }
       }
-    }
-    const float4 cs = tr[c], sn = tr[LPH + c];
+      const float4 cs = tr[c], sn = tr[LPH + c];
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int s = lane + 64 * i;
-      if (s < slots) {
-        rope_pair(lo[i].x, hi[i].x, cs.x, sn.x);
-        rope_pair(lo[i].y, hi[i].y, cs.y, sn.y);
-        rope_pair(lo[i].z, hi[i].z, cs.z, sn.z);
-        rope_pair(lo[i].w, hi[i].w, cs.w, sn.w);
-        float4* p = base + (s / LPH) * (2 * LPH) + c;
-        p[0] = lo[i];
-        p[LPH] = hi[i];
+      for (int i = 0; i < NP; ++i) {
+        const int s = lane + 64 * i;
+        if (s < slots) {
+          rope_pair(lo[i].x, hi[i].x, cs.x, sn.x);
+          rope_pair(lo[i].y, hi[i].y, cs.y, sn.y);
+          rope_pair(lo[i].z, hi[i].z, cs.z, sn.z);
+          rope_pair(lo[i].w, hi[i].w, cs.w, sn.w);
+          float4* p = base + (s / LPH) * (2 * LPH) + c;
+          p[0] = lo[i];
+          p[LPH] = hi[i];
+        }
+      }
+    } else {
+      // 40 heads of 128: twenty passes would be 160 VGPRs of row (256 + AGPR copies as compiled, one wave per SIMD); two groups of ten
+      // passes, each loaded whole before its first rotation -- the same per-element arithmetic
+      constexpr int G = 10;
+      static_assert(NP % G == 0, "whole groups of passes");
+      const float4 cs = tr[c], sn = tr[LPH + c];
+#pragma unroll
+      for (int g = 0; g < NP; g += G) {
+        float4 lo[G], hi[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+          const int s = lane + 64 * (g + i);
+          if (s < slots) {
+            const float4* p = base + (s / LPH) * (2 * LPH) + c;
+            lo[i] = p[0];
+            hi[i] = p[LPH];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+          const int s = lane + 64 * (g + i);
+          if (s < slots) {
+            rope_pair(lo[i].x, hi[i].x, cs.x, sn.x);
+            rope_pair(lo[i].y, hi[i].y, cs.y, sn.y);
+            rope_pair(lo[i].z, hi[i].z, cs.z, sn.z);
+            rope_pair(lo[i].w, hi[i].w, cs.w, sn.w);
+            float4* p = base + (s / LPH) * (2 * LPH) + c;
+            p[0] = lo[i];
+            p[LPH] = hi[i];
+          }
+        }
       }
     }
   }
@@ -150,7 +191,8 @@ static int rope_launch(void (*kern)(Buf*, const float*, int, int, int, int), int
 
 int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld,
                 int head_dim) {
-  if (head_dim != 64 && head_dim != 32) return fail(1, "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return fail(1, "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
+  if (head_dim == 128 && (H < 1 || H > kRopeHeadsHd128Wide)) return fail(1, "rope: 1..40 heads of 128 (d_model <= 5120)");
   if (head_dim == 64 && (H < 1 || H > kRopeHeadsWide)) return fail(1, "rope: 1..40 heads of 64 (d_model <= 2560)");
   if (head_dim == 32 && (H < 1 || H > kRopeHeads)) return fail(1, "rope: 1..32 heads of 32 (d_model <= 1024)");
   if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
@@ -162,6 +204,17 @@ int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int tabl
     static const int occ32h = rope_occupancy(rope32_kernel<kRopePass32Hd32, 32>);
     return f32 ? rope_launch(rope32_kernel<kRopePass32Hd32, 32>, occ32h, s, (float*)qkv, table, M, T, H, ld)
                : rope_launch(rope16_kernel<kRopePass16Hd32, 32>, occ16h, s, (bf16_t*)qkv, table, M, T, H, ld);
+  }
+  if (head_dim == 128) {
+    static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16Hd128, 128>);
+    static const int occ32 = rope_occupancy(rope32_kernel<kRopePass32Hd128, 128>);
+    static const int occ16w = rope_occupancy(rope16_kernel<kRopePass16Hd128Wide, 128>);
+    static const int occ32w = rope_occupancy(rope32_kernel<kRopePass32Hd128Wide, 128>);
+    const bool wide = H > kRopeHeadsHd128;
+    if (f32) return wide ? rope_launch(rope32_kernel<kRopePass32Hd128Wide, 128>, occ32w, s, (float*)qkv, table, M, T, H, ld)
+                         : rope_launch(rope32_kernel<kRopePass32Hd128, 128>, occ32, s, (float*)qkv, table, M, T, H, ld);
+    return wide ? rope_launch(rope16_kernel<kRopePass16Hd128Wide, 128>, occ16w, s, (bf16_t*)qkv, table, M, T, H, ld)
+                : rope_launch(rope16_kernel<kRopePass16Hd128, 128>, occ16, s, (bf16_t*)qkv, table, M, T, H, ld);
   }
   // asked once per instantiation (function-local statics: initialised thread-safely)
   static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16>);

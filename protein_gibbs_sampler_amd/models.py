@@ -60,8 +60,8 @@ class ESM2(_Wrapper):
     in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
     layout (weights.load_fair_esm_checkpoint).  This wrapper promises the 650M model: a checkpoint wider than d_model 2048 (the 3B
     file, 4.4 times the work per token) is refused with a message naming ESM2_3B, and the 150M file (heads of 32) with one naming
-    ESM2_150M.  The other released sizes have heads of 16 / 24 (8M / 35M) or 128 (15B) and are refused by head width: the engine's
-    attention kernels implement heads of 64 and 32."""
+    ESM2_150M, and the 15B file (heads of 128) with one naming ESM2_15B.  The other released sizes have heads of 16 / 24 (8M / 35M)
+    and are refused by head width: the engine's attention kernels implement heads of 64, 32 and 128."""
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T33_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
@@ -89,6 +89,21 @@ class ESM2_150M(_Wrapper):
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T30_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
                          "esm2_t30_150M_UR50D.pt", seed, precision, synthetic, config is not None)
+
+
+class ESM2_15B(_Wrapper):
+    """esm2_t48_15B_UR50D: ESM-2 at 15B parameters -- 48 layers, d_model 5120, 40 heads of 128, d_ffn 20480.  The same wrapper as ESM2
+    with the head-128 instantiations of the attention and rotary kernels (csrc/attn_frag.h) and the 20-chunk row kernels
+    (csrc/ln_row.h).  Sizes come from the file: any checkpoint with heads of 128 (at most 40 of them; d_model a multiple of 512 above
+    2560) or of 64 loads here and runs as the model it is; heads of 128 load ONLY here -- ESM2, ESM2_3B and ESM2_150M refuse them by
+    name.  Device footprint of the weights, hipMemGetInfo before / after engine creation on an MI355X (profiles/esm2_15b_bench_mi355x.json):
+    16-bit modes 2.573 GB at 4 layers and 5.090 GB at 8, i.e. 0.629 GB per layer and 30.3 GB at 48 layers; strict mode
+    (precision="fp32") 4.096 GB at 2 layers and 7.713 GB at 4, i.e. 1.809 GB per layer and 87.3 GB at 48.  The 48-layer figures are
+    extrapolated from those measurements: the full model has not been created (its synthetic fp32 weights are 60 GB on the host)."""
+
+    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
+        super().__init__(config or dict(_w.ESM2_T48_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
+                         "esm2_t48_15B_UR50D.pt", seed, precision, synthetic, config is not None)
 
 
 class ESM_MSA1(_Wrapper):

@@ -22,6 +22,14 @@ process ("head32_vs_head64"): 3-layer models of 20 heads of 32 (d_model 640), 20
 the attention launch) and 10 heads of 64 (d_model 640: the same bytes for the rotation), config-2 shape, profiled alternately for
 `--rounds` rounds; ms per launch is the median over the rounds.
 
+`--size 15b` measures ESM-2 15B (48 x 5120, 40 heads of 128, d_ffn 20480; models.ESM2_15B) at the same three shapes with the attention,
+rotation, LayerNorm and GEMM classes.  The synthetic fp32 weights of all 48 layers are 60 GB of host memory; with `--layers L` < 48 the
+tool also builds the model of L / 2 layers, times both alternately, and reports per shape the 48-layer figure EXTRAPOLATED from the two
+(`ms_per_iteration_48_layers_extrapolated` = ms(L) + (48 - L) x (ms(L) - ms(L / 2)) / (L / 2): the embedding and the LM head are
+counted once) -- every such key says "extrapolated".  `device_bytes` holds what hipMemGetInfo says is in use before and after each
+engine is created (weights in the operand type, per precision mode) and after the config-2 run (with the activation buffers), and
+the same extrapolation of the weights to 48 layers.
+
 Prints one JSON line.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -47,11 +55,12 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3, help="alternations ESM-1b / ESM-2 per shape")
     ap.add_argument("--prof-iters", type=int, default=3, help="iterations of the profiled run")
     ap.add_argument("--layers", type=int, default=None, help="fewer layers for a rehearsal (default: 33, or 36 with --size 3b)")
-    ap.add_argument("--size", choices=["650m", "3b", "150m"], default="650m",
-                    help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone; 150m: ESM-2 150M alone, then head 32 against head 64")
+    ap.add_argument("--size", choices=["650m", "3b", "150m", "15b"], default="650m",
+                    help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone; 150m: ESM-2 150M alone, then head 32 against head 64; "
+                         "15b: ESM-2 15B alone (with --layers L < 48: L and L / 2 layers, 48 extrapolated)")
     args = ap.parse_args(argv)
     if args.layers is None:
-        args.layers = {"3b": 36, "150m": 30}.get(args.size, 33)
+        args.layers = {"3b": 36, "150m": 30, "15b": 48}.get(args.size, 33)
 
     import torch
     from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
@@ -59,12 +68,19 @@ def main(argv=None):
         raise SystemExit("esm2_bench: no GPU visible -- nothing is measured without one")
     L_ = _lib.lib()
 
-    def build(cls, base, **over):
+    def build(cls, base, precision="bf16", **over):
         cfg = weights.make_config(base, **dict(dict(n_layers=args.layers), **over))
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            m = cls(state_dict=weights.synthetic_state_dict(cfg, seed=0), config=cfg, precision="bf16")
+            m = cls(state_dict=weights.synthetic_state_dict(cfg, seed=0), config=cfg, precision=precision)
         return esm_sampler.ESM_sampler(m, device="cuda:0")
+
+    def in_use():
+        torch.cuda.synchronize()
+        free, total = torch.cuda.mem_get_info()          # hipMemGetInfo
+        return int(total - free)
+
+    device_bytes = {}
 
     if args.size == "3b":
         samplers = {"esm2_3b": build(models.ESM2_3B, weights.ESM2_T36_CONFIG)}
@@ -72,6 +88,37 @@ def main(argv=None):
     elif args.size == "150m":
         samplers = {"esm2_150m": build(models.ESM2_150M, weights.ESM2_T30_CONFIG)}
         rotary, model_cfg = "esm2_150m", weights.ESM2_T30_CONFIG
+    elif args.size == "15b":
+        import gc
+        half = args.layers // 2 if args.layers < 48 else 0
+        if args.layers < 48 and (args.layers < 4 or args.layers % 4):
+            raise SystemExit("esm2_bench --size 15b: --layers below 48 must be a multiple of 4 (L, L / 2 and L / 4 layers are built)")
+        # the strict mode's weights first, at L / 4 and L / 2 layers (or 1 and 2 of the full model), then released
+        a, b = (args.layers // 4, args.layers // 2) if half else (1, 2)
+        base0 = in_use()
+        m_a = build(models.ESM2_15B, weights.ESM2_T48_CONFIG, precision="fp32", n_layers=a)
+        used_a = in_use()
+        m_b = build(models.ESM2_15B, weights.ESM2_T48_CONFIG, precision="fp32", n_layers=b)
+        used_b = in_use()
+        device_bytes["fp32"] = {"layers": [a, b], "weights_bytes": [used_a - base0, used_b - used_a]}
+        pl = (device_bytes["fp32"]["weights_bytes"][1] - device_bytes["fp32"]["weights_bytes"][0]) / float(b - a)
+        device_bytes["fp32"]["weights_bytes_48_layers_extrapolated"] = int(device_bytes["fp32"]["weights_bytes"][1] + (48 - b) * pl)
+        del m_a, m_b
+        gc.collect()
+        base1 = in_use()
+        samplers = {}
+        if half:
+            samplers["esm2_15b_half"] = build(models.ESM2_15B, weights.ESM2_T48_CONFIG, n_layers=half)
+        used_h = in_use()
+        samplers["esm2_15b"] = build(models.ESM2_15B, weights.ESM2_T48_CONFIG)
+        used_f = in_use()
+        device_bytes["bf16"] = {"layers": [half, args.layers] if half else [args.layers],
+                                "weights_bytes": [used_h - base1, used_f - used_h] if half else [used_f - base1],
+                                "in_use_before_the_bf16_engines": base1}
+        if half:
+            pl = ((used_f - used_h) - (used_h - base1)) / float(args.layers - half)
+            device_bytes["bf16"]["weights_bytes_48_layers_extrapolated"] = int((used_f - used_h) + (48 - args.layers) * pl)
+        rotary, model_cfg = "esm2_15b", weights.ESM2_T48_CONFIG
     else:
         samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), "esm2": build(models.ESM2, weights.ESM2_T33_CONFIG)}
         rotary, model_cfg = "esm2", weights.ESM2_T33_CONFIG
@@ -115,6 +162,12 @@ def main(argv=None):
         for k in samplers:
             rec[k + "_ms_per_iteration"] = round(statistics.median(ms[k]), 4)
             rec[k + "_ms_per_iteration_rounds"] = [round(v, 4) for v in ms[k]]
+        if "esm2_15b_half" in samplers:
+            full, hv, Lf = rec["esm2_15b_ms_per_iteration"], rec["esm2_15b_half_ms_per_iteration"], args.layers
+            rec["ms_per_layer"] = round((full - hv) / (Lf - Lf // 2), 4)
+            rec["ms_per_iteration_48_layers_extrapolated"] = round(full + (48 - Lf) * (full - hv) / (Lf - Lf // 2), 3)
+        if name == SHAPES[0][0] and device_bytes:
+            device_bytes["in_use_after_the_config2_runs"] = in_use()
         if "esm1b" in samplers:
             rec["esm2_over_esm1b"] = round(rec["esm2_ms_per_iteration"] / rec["esm1b_ms_per_iteration"], 4)
         # the rotation and the LayerNorm launches, by HIP events, in a run of their own
@@ -153,6 +206,8 @@ def main(argv=None):
                 rec[c] = {"launches": g_n, "ms_per_launch": round(g_ms / g_n, 5), "N": n, "K": k, "kernels": gemm_kernels[c],
                           "TFLOPs": round(2.0 * rows * n * k / (g_ms / g_n * 1e-3) / 1e12, 1)}
         out["shapes"][name] = rec
+    if device_bytes:
+        out["device_bytes"] = device_bytes
     if args.size == "150m":
         # the head-32 kernels against the head-64 ones: same process, alternating, config-2 shape
         name, B, L, P = SHAPES[0]
