@@ -86,11 +86,12 @@ typedef struct pg_engine pg_engine;
                            esm2_t30_150M_UR50D: heads of 32, at most 32 of them = d_model <= 1024, this architecture only;
                            esm2_t48_15B_UR50D: heads of 128, at most 40 of them = d_model <= 5120 (a multiple of 512 above 2560), this
                            architecture only;
+                           esm2_t6_8M_UR50D: heads of 16, at most 32 of them = d_model <= 512, this architecture only (d_model 320);
                            pg_engine_create answers PG_ERR_INVALID for any other head width or a wider model).  The ESM-1b block
                            stack, token dropout, emb_layer_norm_after and tied RoBERTa LM head, with three differences: no position
                            table (`embed_positions.weight` is neither required nor read) -- positions enter through ROTARY embeddings
                            applied to q and k of every attention layer ("rotate-half" pairs (i, i + 32) of each 64-wide head, angle
-                           float(t) * 10000^(-2i/64) -- (i, i + 16) and 10000^(-2i/32) for heads of 32, (i, i + 64) and 10000^(-2i/128) for heads of 128 --, t = the token's index along the sequence axis whether or not it is <pad>; one
+                           float(t) * 10000^(-2i/64) -- (i, i + 16) and 10000^(-2i/32) for heads of 32, (i, i + 64) and 10000^(-2i/128) for heads of 128, (i, i + 8) and 10000^(-2i/16) for heads of 16 --, t = the token's index along the sequence axis whether or not it is <pad>; one
                            extra launch per layer between the QKV projection and the attention kernel, all three precision modes;
                            the cos / sin table of max_positions + 2 rows is built when the engine is created); no
                            emb_layer_norm_before (not required); vocabulary of 33 as ESM-1b.  Tensors read: `embed_tokens.weight`,
@@ -117,10 +118,10 @@ typedef struct pg_engine pg_engine;
 typedef struct {
   int32_t arch;
   int32_t vocab;         /* 33 */
-  int32_t d_model;       /* 1280 (ESM-1b) / 768 (MSA-1b); multiple of 128 */
+  int32_t d_model;       /* 1280 (ESM-1b) / 768 (MSA-1b); multiple of 128 -- of 64 for PG_ARCH_ESM2 (esm2_t6_8M_UR50D: 320) */
   int32_t n_layers;      /* 33 / 12 */
-  int32_t n_heads;       /* d_model / 64: head dim is 64 in every model but ESM-2 150M / 15B; PG_ARCH_ESM2 also takes d_model / 32 (heads of
-                            32, n_heads <= 32) and d_model / 128 (heads of 128, n_heads <= 40); the head dim is derived as d_model / n_heads and anything else is PG_ERR_INVALID */
+  int32_t n_heads;       /* d_model / 64: head dim is 64 in every model but ESM-2 150M / 15B / 8M; PG_ARCH_ESM2 also takes d_model / 32 (heads of
+                            32, n_heads <= 32), d_model / 128 (heads of 128, n_heads <= 40) and d_model / 16 (heads of 16, n_heads <= 32); the head dim is derived as d_model / n_heads and anything else is PG_ERR_INVALID */
   int32_t d_ffn;         /* 5120 / 3072; multiple of 128 */
   int32_t max_positions; /* learned position table has max_positions + pad_idx + 1 rows (ESM-2: longest T; sizes the rotary table) */
   int32_t pad_idx, mask_idx, cls_idx, eos_idx;
@@ -400,7 +401,7 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
  * r % T, in `precision` (16-bit modes: through a device buffer of that type, the result widened back); the v third is left alone */
 int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H);      /* H <= 40 */
 /* the same two with the head dimension as an argument: head_dim 64 (what pg_dbg_attention / pg_dbg_rope run), 32 (ESM-2 150M;
- * pg_dbg_rope_hd: H <= 32) or 128 (ESM-2 15B; pg_dbg_rope_hd: H <= 40), buffers [..][3*H*head_dim] and [..][H*head_dim].  key_tok (NULL: none): int32 tokens [B][T] of the keys;
+ * pg_dbg_rope_hd: H <= 32), 128 (ESM-2 15B; pg_dbg_rope_hd: H <= 40) or 16 (ESM-2 8M; pg_dbg_rope_hd: H <= 32), buffers [..][3*H*head_dim] and [..][H*head_dim].  key_tok (NULL: none): int32 tokens [B][T] of the keys;
  * a key whose token equals pad_idx is masked, as the <pad> keys of a ragged batch are */
 int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
                         const int32_t* key_tok, int pad_idx);

@@ -452,7 +452,7 @@ int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx,
   int rc = dbg_precision("pg_dbg_attention_kv", precision, true);
   if (rc) return rc;
   if (!qkv || !ctx || B < 1 || T < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B)");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B) or 16 (ESM-2 8M)");
   if (!bias_k != !bias_v) return fail(PG_ERR_INVALID, "pg_dbg_attention_kv: bias_k and bias_v come together or not at all");
   const std::string head_err = attention_head_error(head_dim, bias_k != nullptr);      // the plans' own refusal of a bias key at head 32
   if (!head_err.empty()) return fail(PG_ERR_INVALID, head_err);
@@ -499,12 +499,12 @@ int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
   return pg_dbg_rope_hd(device, precision, qkv, B, T, H, 64);
 }
 
-/* pg_dbg_rope with the head dimension: 64 (H <= 40), 32 (H <= 32) or 128 (H <= 40) */
+/* pg_dbg_rope with the head dimension: 64 (H <= 40), 32 (H <= 32), 128 (H <= 40) or 16 (H <= 32) */
 int pg_dbg_rope_hd(int device, int precision, float* qkv, int B, int T, int H, int head_dim) {
   int rc = dbg_precision("pg_dbg_rope_hd", precision, true);
   if (rc) return rc;
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B)");
-  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 32 ? 32 : 40)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B) or 16 (ESM-2 8M)");
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 32 || head_dim == 16 ? 32 : 40)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
   Dbg s;
   if ((rc = s.open(device))) return rc;
   const int d = H * head_dim;

@@ -5,7 +5,8 @@
 //
 // CDNA4 mapping, written for head dim HD = 64 (ESM-1b, MSA-1b, ESM-2 650M / 3B); HD = 32 (ESM-2 150M) is the same kernel with half
 // the LDS row, one score MFMA per key block and two output blocks; HD = 128 (ESM-2 15B) with twice the row, four score MFMAs and eight
-// output blocks, whole sequences up to 288 keys and 128-key tiles beyond (attn_frag.h):
+// output blocks, whole sequences up to 288 keys and 128-key tiles beyond; HD = 16 (ESM-2 8M) with a 32-byte row, one half-depth score
+// MFMA per key block and one output block (attn_frag.h):
 //   * grid = B*H workgroups of 4 waves; K and V (both row-major, XOR-swizzled 16-B chunks) live in LDS for
 //     the whole sequence (T <= 576: 2 x 72 KB) and are shared by all query blocks; longer sequences use
 //     attention_long_kernel (288-key tiles, online softmax).
@@ -55,6 +56,8 @@ __device__ unsigned long long* pg_att_prof;      // [workgroup][wave][8 slots][8
 // holds it alone on rungs 12 .. 18; the launch bound follows the LDS.  The K look-ahead is two key blocks there (kbuf[2][2][4] = 64
 // VGPRs; the six of head 64 would be 192), the V look-ahead stays two chunks (vbuf[3][8] = 96 VGPRs).
 // (the PADMASK form of 10 blocks adds 160 flag bytes to the 80 KB and is alone on its CU: pad = true asks for 1 there)
+// HD = 16: K + V are MAXKB KB of LDS (36 KB at 576 keys) and never the limit; the launch bound stays the 2 of head 32 (the score row
+// st[MAXKB] alone is 144 VGPRs on rung 36) and the compiler's own register counts give more on the lower rungs (attention_resident).
 constexpr int attention_occupancy(int maxkb, int hd, bool pad = false) {
   return hd == 128 ? (maxkb <= 8 || (maxkb == 10 && !pad) ? 2 : 1) : hd == 64 ? (maxkb <= 18 ? 2 : 1) : 2;
 }
@@ -65,15 +68,21 @@ constexpr int attention_occupancy(int maxkb, int hd, bool pad = false) {
 // VGPR figures above).
 // Head 128 (the plain and SPLIT forms; DESIGN 10 has the table): four at 4 key blocks (32 KB, 124 VGPRs), three at 6 (48 KB, 160
 // VGPRs), two up to 10 (80 KB), one beyond -- the LDS decides from 8 blocks on.
+// Head 16 (the plain and SPLIT forms, as compiled: waves per SIMD = workgroups per CU, the hardware's 8 at most): 8 up to 6 key
+// blocks (<= 54 VGPRs), 7 at 8 (66), 6 at 10 (78), 5 up to 14 (92), 4 up to 22 (126), 3 up to 34 (166), 2 at 36 (174).
+constexpr int attention_resident16(int kb) {
+  return kb <= 6 ? 8 : kb <= 8 ? 7 : kb <= 10 ? 6 : kb <= 14 ? 5 : kb <= 22 ? 4 : kb <= 34 ? 3 : 2;
+}
 constexpr int attention_resident(int kb, int hd) {
-  return hd == 128 ? (kb <= 4 ? 4 : (kb <= 6 ? 3 : (kb <= 10 ? 2 : 1))) : hd == 64 ? (kb <= 20 ? 2 : 1) : (kb <= 20 ? 4 : (kb <= 26 ? 3 : 2));
+  return hd == 16 ? attention_resident16(kb) : hd == 128 ? (kb <= 4 ? 4 : (kb <= 6 ? 3 : (kb <= 10 ? 2 : 1))) : hd == 64 ? (kb <= 20 ? 2 : 1) : (kb <= 20 ? 4 : (kb <= 26 ? 3 : 2));
 }
 template <int MAXKB, bool PADMASK, bool BIASKV = false, bool SPLIT = false, int HD = 64>
 __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD, PADMASK)) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx, int T,
                                                        int H, int ld_qkv_, int ld_ctx_, int k_off, int v_off,
                                                        SeqLayout sl, const int32_t* __restrict__ key_tok, int pad_idx,
                                                        const bf16_t* __restrict__ bias_kv, int split_from = 0, int split = 1) {
-  constexpr int ROW = HD * 2, NKK = HD / 32, NDB = HD / 16;      // bytes per key in LDS, score MFMAs per key block, 16-wide output blocks
+  constexpr int ROW = HD * 2, NKK = score_steps(HD), NDB = HD / 16;      // bytes per key in LDS, score MFMAs per key block, 16-wide output blocks
+  typedef kfrag_t<HD> kf_t;                                              // the score product's fragment (attn_frag.h)
   __shared__ __attribute__((aligned(16))) char smem[2 * MAXKB * 16 * ROW + (PADMASK ? MAXKB * 16 : 0)];
   char* Ks = smem;
   char* Vs = smem + MAXKB * 16 * ROW;          // V rows, same layout as K (tile_addr)
@@ -116,12 +125,12 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD, PADMASK)) void 
   const int nqb = (T + 15) >> 4;  // query blocks of 16
   // Q fragment (MFMA B operand): query fr, d = kk*32 + fq*8 .. +7; the next block's fragment is prefetched while
   // the current one is computed (a wave has nothing else to cover a global round trip with)
-  bf16x8 qf[NKK], qn[NKK];
-  auto load_q = [&](int qb, bf16x8 (&dst)[NKK]) {
+  kf_t qf[NKK], qn[NKK];
+  auto load_q = [&](int qb, kf_t (&dst)[NKK]) {
     int qrow = qb * 16 + fr;
     if (qrow >= T) qrow = T - 1;
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) dst[kk] = *(const bf16x8*)(base + (size_t)qrow * ld_qkv + kk * 32 + fq * 8);
+    for (int kk = 0; kk < NKK; ++kk) dst[kk] = q_frag<HD>(base + (size_t)qrow * ld_qkv, kk, fq);
   };
   if (qb_first < nqb) load_q(qb_first, qf);
   for (int qb = qb_first; qb < nqb; qb += qb_step) {
@@ -134,8 +143,8 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD, PADMASK)) void 
       // K fragments are fetched one chunk (CH key blocks) ahead of the MFMAs that use them: with 2 waves per SIMD
       // the LDS latency must be covered inside the wave (PMC: 44 % of wave cycles were s_waitcnt before this)
       constexpr int CH = HD == 128 ? 2 : (MAXKB % 6 == 0) ? 6 : (MAXKB % 4 == 0 ? 4 : 2);
-      bf16x8 kbuf[2][CH][NKK];
-      auto load_chunk = [&](int ch, bf16x8 (&dst)[CH][NKK]) {
+      kf_t kbuf[2][CH][NKK];
+      auto load_chunk = [&](int ch, kf_t (&dst)[CH][NKK]) {
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
 #if defined(PG_ATT_PROF) && PG_ATT_ABL == 1      /* ablation: one K fragment read per chunk instead of CH */
@@ -158,18 +167,18 @@ __global__ __launch_bounds__(256, attention_occupancy(MAXKB, HD, PADMASK)) void 
         // contracts the whole head and there is a single sweep
 #pragma unroll
         for (int u = 0; u < CH; ++u)
-          st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][0], qf[0], (f32x4){0.f, 0.f, 0.f, 0.f});
+          st[ch * CH + u] = score_mfma(kbuf[ch & 1][u][0], qf[0], (f32x4){0.f, 0.f, 0.f, 0.f});
         if constexpr (NKK == 2) {
 #pragma unroll
           for (int u = 0; u < CH; ++u)
-            st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][1], qf[1], st[ch * CH + u]);
+            st[ch * CH + u] = score_mfma(kbuf[ch & 1][u][1], qf[1], st[ch * CH + u]);
         }
         if constexpr (NKK == 4) {                      // head 128: three more sweeps, one per 32 d
 #pragma unroll
           for (int kk = 1; kk < 4; ++kk)
 #pragma unroll
             for (int u = 0; u < CH; ++u)
-              st[ch * CH + u] = mfma_op16(kbuf[ch & 1][u][kk], qf[kk], st[ch * CH + u]);
+              st[ch * CH + u] = score_mfma(kbuf[ch & 1][u][kk], qf[kk], st[ch * CH + u]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -261,7 +270,8 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
   const int32_t* __restrict__ key_tok = PADMASK ? key_tok_ : nullptr;
   const bf16_t* __restrict__ bias_kv = BIASKV ? bias_kv_ : nullptr;
   constexpr int tpad = MAXKB * 16, nkc = MAXKB / 2;
-  constexpr int ROW = HD * 2, NKK = HD / 32, NDB = HD / 16;      // as in attention_kernel
+  constexpr int ROW = HD * 2, NKK = score_steps(HD), NDB = HD / 16;      // as in attention_kernel
+  typedef kfrag_t<HD> kf_t;
   __shared__ __attribute__((aligned(16))) char smem[2 * tpad * ROW + (PADMASK ? tpad : 0)];
   char* Ks = smem;
   char* Vs = smem + tpad * ROW;
@@ -275,12 +285,12 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
   const int fr = lane & 15, fq = lane >> 4;
   const int q0 = qc * 64 + wave * 16;
   const bool active = q0 < T;                        // wave-uniform
-  bf16x8 qf[NKK];
+  kf_t qf[NKK];
   {
     int qrow = q0 + fr;
     if (qrow >= T) qrow = T - 1;
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) qf[kk] = *(const bf16x8*)(base + (size_t)qrow * ld_qkv + kk * 32 + fq * 8);
+    for (int kk = 0; kk < NKK; ++kk) qf[kk] = q_frag<HD>(base + (size_t)qrow * ld_qkv, kk, fq);
   }
   f32x4 o[NDB];
 #pragma unroll
@@ -303,7 +313,7 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
     for (int kb = 0; kb < MAXKB; ++kb) {
       st[kb] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) st[kb] = mfma_op16(k_frag<HD>(Ks, kb * 16 + fr, kk, fq), qf[kk], st[kb]);
+      for (int kk = 0; kk < NKK; ++kk) st[kb] = score_mfma(k_frag<HD>(Ks, kb * 16 + fr, kk, fq), qf[kk], st[kb]);
     }
     const int tl = Tk - k0 - fq * 4;
 #pragma unroll
@@ -443,7 +453,7 @@ static void launch_rung(bool pad, bool bias, bool split, dim3 grid, hipStream_t 
     else go(attention_kernel<KB, false, false, false, HD>);
   }
 }
-// the long kernel's <PADMASK, BIASKV> form; no bias key at head 32 / 128; 128-key tiles at head 128, else 288
+// the long kernel's <PADMASK, BIASKV> form; no bias key at head 32 / 128 / 16; 128-key tiles at head 128, else 288
 template <int HD, class... Args>
 static void launch_long(bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
   auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); };
@@ -475,6 +485,7 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
   };
   if (head_dim == 64) launch(std::integral_constant<int, 64>{});
   else if (head_dim == 128) launch(std::integral_constant<int, 128>{});
+  else if (head_dim == 16) launch(std::integral_constant<int, 16>{});
   else launch(std::integral_constant<int, 32>{});
   PG_HIP(hipGetLastError());
   return 0;

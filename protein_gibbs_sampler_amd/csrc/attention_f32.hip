@@ -33,11 +33,12 @@ __device__ __forceinline__ void store_ctx64(const float (&o)[64], float inv, bf1
 
 // Building blocks shared by the three split-bf16 MFMA kernels (full attention, tied-row scores, tied-row apply).
 // Fragment geometry, tile layout and the transposing V^T read: attn_frag.h.
-// HD: the head dimension, 64, 32 or 128 (attn_frag.h; 32 and 128 are built for the full attention only)
+// HD: the head dimension, 64, 32, 128 or 16 (attn_frag.h; 32, 128 and 16 are built for the full attention only)
 template <int MAXKB, int HD = 64>
 struct SplitAttn {
   static constexpr int tpad = MAXKB * 16, nkc = MAXKB / 2;
-  static constexpr int CPR = HD / 8, NKK = HD / 32, NDB = HD / 16;      // 16-byte chunks per key row, score MFMAs per key block, output blocks
+  static constexpr int CPR = HD / 8, NKK = score_steps(HD), NDB = HD / 16;      // 16-byte chunks per key row, score MFMAs per key block, output blocks
+  typedef kfrag_t<HD> kf_t;                                                      // the score product's fragment (attn_frag.h)
   static_assert(MAXKB % 2 == 0, "two 16-key blocks per 32-wide PV step");
   static constexpr float LOG2E = 1.44269504088896341f;
 
@@ -77,35 +78,46 @@ struct SplitAttn {
     }
   }
 
-  // Q fragments (MFMA B operand) of the query whose HD fp32 start at qrow: d = kk*32 + fq*8 .. +7
-  static __device__ __forceinline__ void load_q(const float* __restrict__ qrow, int fq, bf16x8 (&qh)[NKK], bf16x8 (&ql)[NKK]) {
+  // Q fragments (MFMA B operand) of the query whose HD fp32 start at qrow: d = kk*32 + fq*8 .. +7; head 16: d = fq*4 .. +3
+  static __device__ __forceinline__ void load_q(const float* __restrict__ qrow, int fq, kf_t (&qh)[NKK], kf_t (&ql)[NKK]) {
+    if constexpr (HD == 16) {
+      const float4 p = *(const float4*)(qrow + fq * 4);
+      uint2 hi, lo;
+      split4(p.x, p.y, p.z, p.w, hi, lo);
+      qh[0] = __builtin_bit_cast(bf16x4, hi);
+      ql[0] = __builtin_bit_cast(bf16x4, lo);
+    } else {
 #pragma unroll
-    for (int kk = 0; kk < NKK; ++kk) {
-      const float4* p = (const float4*)(qrow + kk * 32 + fq * 8);
-      uint4 hi, lo;
-      split8(p[0], p[1], hi, lo);
-      qh[kk] = __builtin_bit_cast(bf16x8, hi);
-      ql[kk] = __builtin_bit_cast(bf16x8, lo);
+      for (int kk = 0; kk < NKK; ++kk) {
+        const float4* p = (const float4*)(qrow + kk * 32 + fq * 8);
+        uint4 hi, lo;
+        split8(p[0], p[1], hi, lo);
+        qh[kk] = __builtin_bit_cast(bf16x8, hi);
+        ql[kk] = __builtin_bit_cast(bf16x8, lo);
+      }
     }
   }
 
   // st[kb] += (K tile rows kb*16 .. +15) . q :  kl.qh + kh.ql + kh.qh
-  static __device__ __forceinline__ void qk(const char* Kh, const char* Kl, const bf16x8 (&qh)[NKK], const bf16x8 (&ql)[NKK],
+  static __device__ __forceinline__ void qk(const char* Kh, const char* Kl, const kf_t (&qh)[NKK], const kf_t (&ql)[NKK],
                                             f32x4 (&st)[MAXKB], int fr, int fq) {
 #pragma unroll
     for (int kb = 0; kb < MAXKB; ++kb) {
       f32x4 a = st[kb];
       const int krow = kb * 16 + fr;
-      bf16x8 kh[NKK];
+      kf_t kh[NKK];
 #pragma unroll
       for (int kk = 0; kk < NKK; ++kk) {
-        const int ad = tile_addr<HD>(krow, kk * 4 + fq);
-        kh[kk] = *(const bf16x8*)(Kh + ad);
-        a = mfma_op16(*(const bf16x8*)(Kl + ad), qh[kk], a);
-        a = mfma_op16(kh[kk], ql[kk], a);
+        // head 16: the 8-byte piece fq & 1 of chunk fq >> 1 (k_frag's address, once for the hi and the lo tile)
+        const int ad = HD == 16 ? tile_addr<HD>(krow, fq >> 1) + (fq & 1) * 8 : tile_addr<HD>(krow, kk * 4 + fq);
+        kf_t kl;
+        if constexpr (HD == 16) kh[kk] = lds_read_b64(Kh + ad), kl = lds_read_b64(Kl + ad);      // kept ds_read_b64 (attn_frag.h)
+        else kh[kk] = *(const kf_t*)(Kh + ad), kl = *(const kf_t*)(Kl + ad);
+        a = score_mfma(kl, qh[kk], a);
+        a = score_mfma(kh[kk], ql[kk], a);
       }
 #pragma unroll
-      for (int kk = 0; kk < NKK; ++kk) a = mfma_op16(kh[kk], qh[kk], a);
+      for (int kk = 0; kk < NKK; ++kk) a = score_mfma(kh[kk], qh[kk], a);
       st[kb] = a;
     }
   }
@@ -164,7 +176,7 @@ struct SplitAttn {
   }
 
   // row = the query's context row; the lane holds columns h*HD + db*16 + fq*4 .. +3.  bf16, or the strict mode's split operand
-  // row (split_operand.h: a head of 64 is two groups, a head of 32 one)
+  // row (split_operand.h: a head of 64 is two groups, a head of 32 one, a head of 16 half of one -- heads 2 g and 2 g + 1 share group g)
   static __device__ __forceinline__ void store_ctx(const f32x4 (&o)[NDB], float l, bf16_t* row, int h, int fq, int split_d) {
     const float inv = l > 0.f ? 1.0f / l : 0.f;     // every key masked (an all-<pad> sequence): zero context, not NaN
 #pragma unroll
@@ -182,7 +194,7 @@ struct SplitAttn {
       } else {
         r.x = pack_op2(split_rest(a, p.x << 16), split_rest(b, p.x & 0xffff0000u));
         r.y = pack_op2(split_rest(c, p.y << 16), split_rest(d, p.y & 0xffff0000u));
-        bf16_t* g = row + (NKK * h + (db >> 1)) * kSplitVals + (db & 1) * 16 + fq * 4;
+        bf16_t* g = HD == 16 ? row + split_lo_offset(h * 16 + fq * 4) : row + (NKK * h + (db >> 1)) * kSplitVals + (db & 1) * 16 + fq * 4;
         *(uint2*)g = r;
         *(uint2*)(g + kSplitHi) = p;
         if (split_d > 0) *(uint2*)(g + kSplitDup) = p;
@@ -248,7 +260,7 @@ __global__ __launch_bounds__(256, 2) void attention_split_kernel(
     for (int j = 0; j < NQB; ++j) {
       const int q0 = qbase + j * 64;
       if (q0 >= T) continue;                       // wave-uniform
-      bf16x8 qh[A::NKK], ql[A::NKK];
+      typename A::kf_t qh[A::NKK], ql[A::NKK];
       A::load_q(base + (size_t)(q0 + fr < T ? q0 + fr : T - 1) * ld_qkv, fq, qh, ql);
       f32x4 st[MAXKB];
 #pragma unroll
@@ -641,6 +653,7 @@ static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int h
   if (!p.error.empty()) return p;
   if (head_dim != 64 && p.valu)
     return refuse(head_dim == 128 ? "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 128"
+                  : head_dim == 16 ? "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 16"
                                   : "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
   if (n_seq == 0) return p;
   if (T <= 0) return refuse("attention: empty sequence");
@@ -701,8 +714,8 @@ void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has
   *text = plan_text(plan_attention_f32(n_seq, T, H, head_dim, has_pad, has_bias, row_step));
 }
 
-// one (key tile, query blocks) pair of the split kernel: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32 / 128.
-// Head 128 runs 64-key tiles with 1, 2 or 3 query blocks per wave (plan_attention_f32); heads 64 / 32 pair 64-key tiles with one
+// one (key tile, query blocks) pair of the split kernel: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32 / 128 / 16.
+// Head 128 runs 64-key tiles with 1, 2 or 3 query blocks per wave (plan_attention_f32); heads 64 / 32 / 16 pair 64-key tiles with one
 // query block only, so <4, 2> and <4, 3> exist at head 128 alone
 // false: the pair is not built at this head width and nothing was launched (the launcher turns that into an error)
 template <int KB, int NQB, class... Args>
@@ -715,6 +728,7 @@ static bool launch_split(int hd, bool pad, bool bias, dim3 grid, hipStream_t s, 
   }
   if constexpr (KB != 4 || NQB == 1) {
     if (hd == 32) return pad ? go(attention_split_kernel<KB, NQB, false, true, 32>) : go(attention_split_kernel<KB, NQB, false, false, 32>);
+    if (hd == 16) return pad ? go(attention_split_kernel<KB, NQB, false, true, 16>) : go(attention_split_kernel<KB, NQB, false, false, 16>);
     if (bias) return pad ? go(attention_split_kernel<KB, NQB, true, true>) : go(attention_split_kernel<KB, NQB, true, false>);
     return pad ? go(attention_split_kernel<KB, NQB, false, true>) : go(attention_split_kernel<KB, NQB, false, false>);
   }

@@ -11,8 +11,8 @@
 //
 // The head dimension is the template parameter HD of everything that touches a tile or the context: 64 (the default: ESM-1b,
 // ESM-1, MSA-1b, ESM-2 650M / 3B -- every caller that names no HD is the head-64 form, instruction for instruction what it was
-// before HD existed), 32 (ESM-2 150M) or 128 (ESM-2 15B).  Softmax, masks and p_frag do not depend on it; the key-block ladder ends
-// at 18 blocks at 128 (below).
+// before HD existed), 32 (ESM-2 150M), 128 (ESM-2 15B) or 16 (ESM-2 8M).  Softmax, masks and p_frag do not depend on it; the
+// key-block ladder ends at 18 blocks at 128 (below).
 //
 // Geometry (head dim 64).  A K or V tile is row-major in LDS, one key per 128-byte row, the row's eight 16-byte chunks
 // XOR-swizzled with (row & 7).  fr = lane & 15 is the lane's query (the MFMA column), fq = lane >> 4.
@@ -60,6 +60,28 @@
 // flags: one workgroup per CU; rung 20 would be the CU's whole 160 KB and is not built) and longer sequences take the tiled kernel
 // with 128-key tiles: 2 x 32 KB + 128 flag bytes per workgroup, the tallest even block count that leaves room for two workgroups
 // per CU (160-key tiles would be 80 KB + flags each: one too many bytes for two).
+//
+// Geometry (head dim 16).  One key per 32-byte row of two 16-byte chunks; eight keys share a 256-byte bank row.  The score product
+// contracts 16 values: ONE v_mfma_f32_16x16x16 (mfma_op16_k16, pg_common.h), whose lane holds the 4 values d = 4 fq .. 4 fq + 3 of
+// row fr -- k_frag is a ds_read_b64 of 8-byte piece fq of key row fr, the Q fragment an 8-byte global load; same output layout as the
+// 16x16x32, so st[kb][r] means what it means above.  The alternative was the 16x16x32 with d = 16 .. 31 supplied as zeros in both
+// operands (lanes fq >= 2 hold zeros and read nothing): twice the contraction depth per score block for the same result, a 16-byte
+// fragment (4 VGPRs, not 2) per key block in the K look-ahead, and a select per fragment to keep the upper lanes off the LDS.  The
+// microarchitecture guide gives 16 cycles per 16x16x32 on one SIMD and no figure for the 16x16x16; at worst it costs the same MFMA
+// cycles, and it halves the fragment registers and issues one plain b64 read per key block with nothing masked, so it was built.
+// (Not timed against each other on the device.)  The context product keeps the 16x16x32 -- its K is the keys -- with ONE output
+// block o[1]; the transposing read's four key rows x four 8-byte pieces are exactly four whole rows.
+// The swizzle is  chunk ^ ((row >> 3) & 1)  -- bit 3 of the key row swaps the two 16-byte chunks of its row.  By the bank rules:
+//   * the score fragment (ds_read_b64, served in two halves of 32 lanes, bank = (address / 4) % 64): lane 16 fq + fr reads piece fq
+//     of row fr, so a half (fq = 0, 1 or fq = 2, 3) reads ONE 16-byte chunk c of the block's 16 rows = two bank rows.  Unswizzled,
+//     rows r and r + 8 put chunk c on the same four banks: 2-way on every read.  Swapping the chunks of rows 8 - 15 sends them to
+//     the other 16 bytes of their 32: the sixteen chunks cover all 64 banks once, conflict-free.
+//   * the transposing read (ds_read_b64_tr_b16, two halves of 32 lanes): a half reads all 32 bytes of the 8 consecutive key rows
+//     key0 + 8 (fq >> 1) + 0 .. 7 -- one whole aligned bank row, every bank once, whatever happens inside a row.
+//   * the staging writes (ds_write_b128, groups of 8 consecutive lanes, bank = (address / 4) % 32): 8 consecutive items = both chunks
+//     of four neighbouring rows = one whole aligned 128-byte line, each chunk once, whatever happens inside a row.
+// All three conflict-free (tools/lds_bank_model.py evaluates it next to no swizzle and chunk ^ (row & 1)).
+// LDS budget: K + V are 64 bytes per key, 36 KB at 576 keys: registers, not the LDS, set the occupancy on every rung.
 #pragma once
 #include <type_traits>
 
@@ -68,6 +90,13 @@
 PG_OPS_BEGIN
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+// the score product's operand fragment: 8 values of a 32-deep step, or at head dimension 16 the 4 values of the one 16-deep step
+template <int HD> struct KFrag { typedef bf16x8 type; };
+template <> struct KFrag<16> { typedef bf16x4 type; };
+template <int HD> using kfrag_t = typename KFrag<HD>::type;
+// score MFMAs per key block
+constexpr int score_steps(int hd) { return hd == 16 ? 1 : hd / 32; }
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef short v4s __attribute__((ext_vector_type(4)));
@@ -109,7 +138,7 @@ inline bool visit_rung(int kb, F&& f) {
 }
 // what the full-attention plans (attention.hip, attention_f32.hip) refuse before they look at the shape; empty: nothing
 inline std::string attention_head_error(int head_dim, bool has_bias) {
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32";
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32";
   if (head_dim != 64 && has_bias) return "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only";
   return {};
 }
@@ -120,8 +149,9 @@ inline std::string attention_head_error(int head_dim, bool has_bias) {
 #define PG_TILE128_CHUNK(row, chunk) ((chunk) ^ ((row) & 7))
 template <int HD = 64>
 __device__ __forceinline__ int tile_swz(int row, int chunk) {
-  static_assert(HD == 64 || HD == 32 || HD == 128, "head dimension 64, 32 or 128");
+  static_assert(HD == 64 || HD == 32 || HD == 128 || HD == 16, "head dimension 64, 32, 128 or 16");
   if constexpr (HD == 128) return (chunk ^ ((row & 7) << 1)) << 4;
+  if constexpr (HD == 16) return (chunk ^ ((row >> 3) & 1)) << 4;
   return (HD == 64 ? PG_TILE128_CHUNK(row, chunk) : chunk ^ ((row >> 1) & 2)) << 4;
 }
 template <int HD = 64>
@@ -136,7 +166,7 @@ struct TileRegs {
 };
 template <int TPAD, int NT, int HD>
 __device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT, HD>& g, int tid, char* dst) {
-  constexpr int CPR = HD / 8, CSH = HD == 128 ? 4 : (HD == 64 ? 3 : 2);                     // 16-byte chunks per key row, and its log2
+  constexpr int CPR = HD / 8, CSH = HD == 128 ? 4 : (HD == 64 ? 3 : (HD == 32 ? 2 : 1));                     // 16-byte chunks per key row, and its log2
 #pragma unroll
   for (int it = 0; it < TileRegs<TPAD, NT, HD>::NIT; ++it) {
     const int i = tid + it * NT, row = i >> CSH, c = i & (CPR - 1);
@@ -149,7 +179,7 @@ __device__ __forceinline__ void tile_store(const TileRegs<TPAD, NT, HD>& g, int 
 template <int TPAD, int NT, bool EXTRA, int HD = 64>
 __device__ __forceinline__ void stage_kv(char* Ks, char* Vs, int tid, const bf16_t* src, size_t ld, int k_off, int v_off, int row0,
                                          int n_rows, const bf16_t* bias_k, const bf16_t* bias_v) {
-  constexpr int CPR = HD / 8, CSH = HD == 128 ? 4 : (HD == 64 ? 3 : 2);                     // 16-byte chunks per key row, and its log2
+  constexpr int CPR = HD / 8, CSH = HD == 128 ? 4 : (HD == 64 ? 3 : (HD == 32 ? 2 : 1));                     // 16-byte chunks per key row, and its log2
   constexpr int NIT = (TPAD * CPR + NT - 1) / NT;
   uint4 kreg[NIT], vreg[NIT];
 #pragma unroll
@@ -176,11 +206,28 @@ __device__ __forceinline__ void stage_kv(char* Ks, char* Vs, int tid, const bf16
 }
 
 // ---- fragments ------------------------------------------------------------------------------------------------------------
-// K (MFMA A operand of S^T) or Q (B operand) fragment out of a tile: row krow, d = kk*32 + fq*8 .. +7 (kk < HD / 32)
-template <int HD = 64>
-__device__ __forceinline__ bf16x8 k_frag(const char* Ks, int krow, int kk, int fq) {
-  return *(const bf16x8*)(Ks + krow * (HD * 2) + tile_swz<HD>(krow, kk * 4 + fq));
+// One ds_read_b64, kept one: left to itself hipcc pairs the fragment reads of two key blocks (512 bytes apart) into a
+// ds_read2st64_b64, which the LDS serves in 8 cycles where two ds_read_b64 take 4, on 32 banks instead of 64 (the head-16 swizzle is
+// derived for 64).  A volatile access through an LDS-qualified pointer is not paired and keeps its immediate offset.
+__device__ __forceinline__ bf16x4 lds_read_b64(const char* a) {
+  return *(const volatile bf16x4 __attribute__((address_space(3)))*)((__attribute__((address_space(3))) char*)a);
 }
+// K (MFMA A operand of S^T) or Q (B operand) fragment out of a tile: row krow, d = kk*32 + fq*8 .. +7 (kk < HD / 32); at head
+// dimension 16 d = fq*4 .. +3, the 8-byte piece fq & 1 of chunk fq >> 1 (kk = 0)
+template <int HD = 64>
+__device__ __forceinline__ kfrag_t<HD> k_frag(const char* Ks, int krow, int kk, int fq) {
+  if constexpr (HD == 16) return lds_read_b64(Ks + krow * (HD * 2) + tile_swz<HD>(krow, fq >> 1) + (fq & 1) * 8);
+  else return *(const bf16x8*)(Ks + krow * (HD * 2) + tile_swz<HD>(krow, kk * 4 + fq));
+}
+// the same fragment of a query straight from its row of 16-bit values in memory (qrow = the head's first value)
+template <int HD = 64>
+__device__ __forceinline__ kfrag_t<HD> q_frag(const bf16_t* qrow, int kk, int fq) {
+  if constexpr (HD == 16) return *(const bf16x4*)(qrow + fq * 4);
+  else return *(const bf16x8*)(qrow + kk * 32 + fq * 8);
+}
+// one step of the score product: the 32-deep MFMA, or the 16-deep one that is the whole product at head dimension 16
+__device__ __forceinline__ f32x4 score_mfma(bf16x8 k, bf16x8 q, f32x4 c) { return mfma_op16(k, q, c); }
+__device__ __forceinline__ f32x4 score_mfma(bf16x4 k, bf16x4 q, f32x4 c) { return mfma_op16_k16(k, q, c); }
 
 // V^T fragment (A operand of O^T) for d = db*16 .. +15 and a chunk of 32 keys, straight out of the row-major V tile through
 // gfx950's transposing LDS read ds_read_b64_tr_b16 (semantics probed on the device): the 16 lanes of a group point at 4 key

@@ -217,9 +217,20 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   device = -1;
   if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_MSA1B && cfg.arch != PG_ARCH_ESM1 && cfg.arch != PG_ARCH_ESM2) return fail(PG_ERR_INVALID, "unknown arch");
   if (prec != PG_PREC_BF16 && prec != PG_PREC_FP32 && prec != PG_PREC_F16) return fail(PG_ERR_INVALID, "unknown precision mode");
-  if (cfg.d_model % 128 || cfg.d_ffn % 128) return fail(PG_ERR_INVALID, "d_model and d_ffn must be multiples of 128");
-  // head width: the attention and rotary kernels are built for 64 (every architecture), 32 and 128 (ESM-2 only: esm2_t30_150M_UR50D,
-  // esm2_t48_15B_UR50D)
+  // d_model: a multiple of 64 for ESM-2 (esm2_t6_8M_UR50D: 320 = 5 x 64), of 128 for the other architectures.  The rule of 128 dates
+  // from the first GEMM, whose tiles were 128 x 128 (N a multiple of 128).  Today every consumer of d_model on the ESM-2 path takes
+  // multiples of 64: plan_gemm as N (64 x 64 tiles; 16 for the weight-streaming kernel) and as K (64; the strict mode's K' = 3K with
+  // it), the split operand's 32-column groups, the row kernels (multiples of 4; the operand LayerNorm 32), the LM head and the
+  // embedding (4); the forms that want more -- the LayerNorm-folding single-chain GEMM (K a multiple of 256), the fused row-LayerNorm
+  // GEMM (N = 1280), the 128- and 256-wide tiles -- are admissions with a fallback, not requirements (DESIGN.md section 10 walks the
+  // list).  The single-chain trunk (ESM-1b), the head-major column-attention weights and the tied-row kernels (MSA-1b) were not
+  // walked, so those architectures keep the rule.  d_ffn stays at 128: the strict mode's fused GELU-and-split and the big tiles want
+  // N = d_ffn in units of 256 / 128 and no released model needs less.
+  if (cfg.d_model % (cfg.arch == PG_ARCH_ESM2 ? 64 : 128) || cfg.d_ffn % 128)
+    return fail(PG_ERR_INVALID, cfg.arch == PG_ARCH_ESM2 ? "d_model must be a multiple of 64 (PG_ARCH_ESM2) and d_ffn of 128"
+                                                         : "d_model and d_ffn must be multiples of 128");
+  // head width: the attention and rotary kernels are built for 64 (every architecture), 32, 128 and 16 (ESM-2 only:
+  // esm2_t30_150M_UR50D, esm2_t48_15B_UR50D, esm2_t6_8M_UR50D)
   head_dim = cfg.n_heads > 0 && cfg.d_model % cfg.n_heads == 0 ? cfg.d_model / cfg.n_heads : 0;
   if (head_dim == 32 && cfg.arch != PG_ARCH_ESM2)
     return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
@@ -227,9 +238,15 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   if (head_dim == 128 && cfg.arch != PG_ARCH_ESM2)
     return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
                                     " with heads of 128: head dim must be 64 for this architecture (heads of 128 run for PG_ARCH_ESM2 only)");
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128)
+  if (head_dim == 16 && cfg.arch != PG_ARCH_ESM2)
+    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
+                                    " with heads of 16: head dim must be 64 for this architecture (heads of 16 run for PG_ARCH_ESM2 only)");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16)
     return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " with " + std::to_string(cfg.n_heads) +
-                                    " heads: head dim must be 64 (every architecture), or 32 or 128 (PG_ARCH_ESM2)");
+                                    " heads: head dim must be 64 (every architecture), or 32, 128 or 16 (PG_ARCH_ESM2)");
+  if (head_dim == 16 && cfg.n_heads > 32)
+    return fail(PG_ERR_INVALID, "heads of 16: the rotary kernel holds at most 32 of them per row (d_model <= 512; esm2_t6_8M_UR50D has 20), not " +
+                                    std::to_string(cfg.n_heads));
   if (head_dim == 32 && cfg.n_heads > 32)
     return fail(PG_ERR_INVALID, "heads of 32: the rotary kernel holds at most 32 of them per row (d_model <= 1024; esm2_t30_150M_UR50D has 20)");
   // heads of 128 (esm2_t48_15B_UR50D): at most 40 of them, and above 2560 features the row kernels take whole 512-feature units
@@ -262,6 +279,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   // the only new rounding is that fp32 product, 2^-24 relative, under an operand rounding of 2^-9 / 2^-12 / 2^-17
   if (head_dim == 32) qs = 0.17677669529663687f;
   if (head_dim == 128) qs = 0.08838834764831845f;      // 128^-0.5: the same fold
+  if (head_dim == 16) qs = 0.25f;                      // 16^-0.5: a power of two again, exact like the 0.125 of heads of 64
   bool ok = true;
   ok = ok && (embed = up.f32("embed_tokens.weight", (int64_t)V * d));
   // ESM-2 has no position table (pos stays null: embed_ln_kernel adds nothing) -- positions enter through the rotation of q and k
@@ -472,7 +490,7 @@ float* Engine::splitk_ws(int rows, int n, int K, int64_t batch_rows) {
   return splitk.as<float>();
 }
 
-// The rotary embedding's table [rows][hd], hd = the head dimension (64, or 32 with 16 in place of 32 below): [t][i] = cos,
+// The rotary embedding's table [rows][hd], hd = the head dimension (64, or 32 / 128 / 16 with 16 / 64 / 8 in place of 32 below): [t][i] = cos,
 // [t][32 + i] = sin of ang[t][i] = float(t) * inv_freq[i] (an fp32 product),
 // inv_freq[i] = 1 / 10000^(2i / 64) in fp32 as fair-esm's RotaryEmbedding holds it (1.0 / (10000 ** (arange(0, 64, 2).float() / 64))).
 // The power is taken in double and rounded to fp32 -- the values torch's fp32 pow and glibc's powf give; a vectorised fp32 pow (numpy's)

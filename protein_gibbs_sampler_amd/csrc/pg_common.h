@@ -84,6 +84,7 @@ inline namespace opbf16 {}
 namespace opf16 {}
 PG_OPS_NS_OPEN
 typedef __attribute__((ext_vector_type(8))) __bf16 pg_op16x8_t;      // 8 operand values = one 16-byte fragment (raw 16-bit lanes)
+typedef __attribute__((ext_vector_type(4))) __bf16 pg_op16x4_t;      // 4 operand values = the 8-byte fragment of the half-depth product
 #ifdef PG_F16
 // device: v_cvt_pk_f16_f32 (round-to-nearest-even).  No saturation: |x| > 65504 becomes inf -- the 16-bit tensors of this forward
 // (LayerNorm outputs, q/k/v, softmax numerators in [0, 1], context, GELU(fc1)) stay orders of magnitude below that.
@@ -99,6 +100,13 @@ __device__ __forceinline__ __attribute__((ext_vector_type(4))) float mfma_op16(p
                                                                                __attribute__((ext_vector_type(4))) float c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pg_f16x8_t, a), __builtin_bit_cast(pg_f16x8_t, b), c, 0, 0, 0);
 }
+// the half-depth product, 16 x 16 x 16: a lane holds 4 values (k = 4 (lane >> 4) .. + 3) of row / column lane & 15 -- the score product
+// of a head of 16 (attn_frag.h), whose whole contraction it is
+typedef _Float16 pg_f16x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __attribute__((ext_vector_type(4))) float mfma_op16_k16(pg_op16x4_t a, pg_op16x4_t b,
+                                                                                   __attribute__((ext_vector_type(4))) float c) {
+  return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(pg_f16x4_t, a), __builtin_bit_cast(pg_f16x4_t, b), c, 0, 0, 0);
+}
 #else
 // device: the cast lowers to gfx950's v_cvt_pk_bf16_f32 (round-to-nearest-even)
 typedef __bf16 pg_bf16x2_t __attribute__((ext_vector_type(2)));
@@ -111,6 +119,12 @@ __device__ __forceinline__ float op16_to_f32(bf16_t v) { return bf16_to_f32(v); 
 __device__ __forceinline__ __attribute__((ext_vector_type(4))) float mfma_op16(pg_op16x8_t a, pg_op16x8_t b,
                                                                                __attribute__((ext_vector_type(4))) float c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// the half-depth product, 16 x 16 x 16 (see the fp16 flavour above)
+typedef short pg_s16x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __attribute__((ext_vector_type(4))) float mfma_op16_k16(pg_op16x4_t a, pg_op16x4_t b,
+                                                                                   __attribute__((ext_vector_type(4))) float c) {
+  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(pg_s16x4_t, a), __builtin_bit_cast(pg_s16x4_t, b), c, 0, 0, 0);
 }
 #endif
 }  // the flavour namespace

@@ -26,6 +26,9 @@
 // Heads of 128 (ESM-2 15B): pairs (i, i + 64), the same rule with twice the head -- 16-bit buffers 8 + 8 values = the lane's 16 bytes and
 // the 16 bytes 128 bytes higher, 8 lanes per head, 16 H lane-slots per row (640 at d = 5120: ten passes); fp32 buffers 4 + 4 values, 16
 // lanes per head, 32 H lane-slots (twenty passes at d = 5120, ten in flight at a time); the table row is [64 cos | 64 sin].
+// Heads of 16 (ESM-2 8M): pairs (i, i + 8), the same rule with a quarter of the head -- 16-bit buffers 8 + 8 values = the lane's 16
+// bytes (the head's whole low half) and the next 16 bytes, ONE lane per head, 2 H lane-slots per row (40 at d = 320: one pass, up to
+// 32 heads); fp32 buffers 4 + 4 values, 2 lanes per head, 4 H lane-slots (two passes); the table row is [8 cos | 8 sin].
 // Grid: at most one resident round of workgroups (the kernel's occupancy x CUs), every wave walking rows row, row + waves, ... -- a mid-size
 // batch has no nearly empty last round (the reason layernorm_bf16_stride_kernel exists), and stores retire behind the next row's
 // loads.  Rows >= M (the 256-row padding of the activation buffers) are not touched.
@@ -44,6 +47,9 @@ constexpr int kRopePass16Hd32 = 2, kRopePass32Hd32 = 4;
 constexpr int kRopePass16Hd128 = 5, kRopePass16Hd128Wide = 10;
 constexpr int kRopePass32Hd128 = 10, kRopePass32Hd128Wide = 20;
 constexpr int kRopeHeadsHd128 = 20, kRopeHeadsHd128Wide = 40;
+// heads of 16: up to 32 of them (d_model <= 512; ESM-2 8M has 20) in 1 (16-bit: 2 H slots) and 2 (fp32: 4 H slots) passes
+constexpr int kRopePass16Hd16 = 1, kRopePass32Hd16 = 2;
+constexpr int kRopeHeadsHd16 = 32;
 
 __device__ __forceinline__ void rope_pair(float& lo, float& hi, float c, float s) {
   const float a = lo, b = hi;
@@ -191,10 +197,11 @@ static int rope_launch(void (*kern)(Buf*, const float*, int, int, int, int), int
 
 int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld,
                 int head_dim) {
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128) return fail(1, "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
+  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return fail(1, "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
   if (head_dim == 128 && (H < 1 || H > kRopeHeadsHd128Wide)) return fail(1, "rope: 1..40 heads of 128 (d_model <= 5120)");
   if (head_dim == 64 && (H < 1 || H > kRopeHeadsWide)) return fail(1, "rope: 1..40 heads of 64 (d_model <= 2560)");
   if (head_dim == 32 && (H < 1 || H > kRopeHeads)) return fail(1, "rope: 1..32 heads of 32 (d_model <= 1024)");
+  if (head_dim == 16 && (H < 1 || H > kRopeHeadsHd16)) return fail(1, "rope: 1..32 heads of 16 (d_model <= 512)");
   if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
   if (ld < 3 * H * head_dim || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
   if (M == 0) return 0;
@@ -204,6 +211,12 @@ int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int tabl
     static const int occ32h = rope_occupancy(rope32_kernel<kRopePass32Hd32, 32>);
     return f32 ? rope_launch(rope32_kernel<kRopePass32Hd32, 32>, occ32h, s, (float*)qkv, table, M, T, H, ld)
                : rope_launch(rope16_kernel<kRopePass16Hd32, 32>, occ16h, s, (bf16_t*)qkv, table, M, T, H, ld);
+  }
+  if (head_dim == 16) {
+    static const int occ16q = rope_occupancy(rope16_kernel<kRopePass16Hd16, 16>);
+    static const int occ32q = rope_occupancy(rope32_kernel<kRopePass32Hd16, 16>);
+    return f32 ? rope_launch(rope32_kernel<kRopePass32Hd16, 16>, occ32q, s, (float*)qkv, table, M, T, H, ld)
+               : rope_launch(rope16_kernel<kRopePass16Hd16, 16>, occ16q, s, (bf16_t*)qkv, table, M, T, H, ld);
   }
   if (head_dim == 128) {
     static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16Hd128, 128>);

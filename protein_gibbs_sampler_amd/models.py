@@ -60,8 +60,9 @@ class ESM2(_Wrapper):
     in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
     layout (weights.load_fair_esm_checkpoint).  This wrapper promises the 650M model: a checkpoint wider than d_model 2048 (the 3B
     file, 4.4 times the work per token) is refused with a message naming ESM2_3B, and the 150M file (heads of 32) with one naming
-    ESM2_150M, and the 15B file (heads of 128) with one naming ESM2_15B.  The other released sizes have heads of 16 / 24 (8M / 35M)
-    and are refused by head width: the engine's attention kernels implement heads of 64, 32 and 128."""
+    ESM2_150M, the 15B file (heads of 128) with one naming ESM2_15B and the 8M file (heads of 16) with one naming ESM2_8M.  The one
+    other released size, 35M, has heads of 24 and d_model 480 and is refused by head width: the engine's attention kernels implement
+    heads of 64, 32, 128 and 16 (and its GEMMs take d_model in multiples of 64)."""
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T33_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
@@ -104,6 +105,18 @@ class ESM2_15B(_Wrapper):
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.ESM2_T48_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
                          "esm2_t48_15B_UR50D.pt", seed, precision, synthetic, config is not None)
+
+
+class ESM2_8M(_Wrapper):
+    """esm2_t6_8M_UR50D: ESM-2 at 8M parameters -- 6 layers, d_model 320, 20 heads of 16, d_ffn 1280; the smallest released size, the
+    one to tune a design loop of thousands of chains on.  The same wrapper as ESM2 with the head-16 instantiations of the attention and
+    rotary kernels (csrc/attn_frag.h: a half-depth score MFMA, 32-byte LDS rows).  Sizes come from the file: any checkpoint with heads
+    of 16 (at most 32 of them, d_model a multiple of 64) or of 64 loads here and runs as the model it is; heads of 16 load ONLY here --
+    ESM2, ESM2_3B, ESM2_150M and ESM2_15B refuse them by name."""
+
+    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
+        super().__init__(config or dict(_w.ESM2_T6_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
+                         "esm2_t6_8M_UR50D.pt", seed, precision, synthetic, config is not None)
 
 
 class ESM_MSA1(_Wrapper):

@@ -31,8 +31,8 @@ ESM1_T34_CONFIG = dict(ESM1_T6_CONFIG, n_layers=34, d_model=1280, n_heads=20, d_
 
 # ESM-2 (fair-esm `ESM2`, esm2_t33_650M_UR50D -- models.ESM2): the ESM-1b block stack and LM head without a position table and without
 # emb_layer_norm_before; positions enter through rotary embeddings of q and k in every layer (include/pgibbs.h PG_ARCH_ESM2).  Of
-# the released sizes 650M and 3B have heads of 64, 150M heads of 32 and 15B heads of 128, the three widths the attention and rotary
-# kernels are built for (8M / 35M: 16 / 24 -- not engine models).
+# the released sizes 650M and 3B have heads of 64, 150M heads of 32, 15B heads of 128 and 8M heads of 16, the four widths the attention
+# and rotary kernels are built for (35M: heads of 24 and d_model 480, no multiple of 64, which the GEMMs need -- not an engine model).
 ESM2_T33_CONFIG = dict(arch=_lib.PG_ARCH_ESM2, vocab=33, d_model=1280, n_layers=33, n_heads=20, d_ffn=5120, max_positions=1024,
                        pad_idx=1, mask_idx=32, cls_idx=0, eos_idx=2, token_dropout=1, max_msa_rows=0, layer_norm_eps=1e-5)
 # esm2_t36_3B_UR50D -- models.ESM2_3B: 36 layers of 40 heads, 4.4 times the arithmetic of the 650M model per token
@@ -41,8 +41,11 @@ ESM2_T36_CONFIG = dict(ESM2_T33_CONFIG, d_model=2560, n_layers=36, n_heads=40, d
 ESM2_T30_CONFIG = dict(ESM2_T33_CONFIG, d_model=640, n_layers=30, n_heads=20, d_ffn=2560)
 # esm2_t48_15B_UR50D -- models.ESM2_15B: 48 layers of 40 heads of 128; about 30 GB of 16-bit weights
 ESM2_T48_CONFIG = dict(ESM2_T33_CONFIG, d_model=5120, n_layers=48, n_heads=40, d_ffn=20480)
-HEAD_DIMS = (64, 32, 128)    # head widths the attention kernels are built for; 32 and 128 run for ESM-2 only (csrc/attn_frag.h)
+# esm2_t6_8M_UR50D -- models.ESM2_8M: 6 layers of 20 heads of 16
+ESM2_T6_CONFIG = dict(ESM2_T33_CONFIG, d_model=320, n_layers=6, n_heads=20, d_ffn=1280)
+HEAD_DIMS = (64, 32, 128, 16)  # head widths the attention kernels are built for; 32, 128 and 16 run for ESM-2 only (csrc/attn_frag.h)
 MAX_HEADS_OF_32 = 32         # the rotary kernel's row of heads of 32 (csrc/rope.hip)
+MAX_HEADS_OF_16 = 32         # the rotary kernel's row of heads of 16: d_model <= 512 (csrc/rope.hip)
 MAX_D_MODEL = 2560           # heads of 64 / 32: the row kernels hold at most kMaxChWide * 256 features (csrc/ln_row.h)
 MAX_HEADS_OF_128 = 40        # heads of 128: at most 40 of them, d_model <= 5120 (kMaxCh5k * 256), in 512-feature units above 2560
 MAX_D_MODEL_HD128 = 128 * MAX_HEADS_OF_128
@@ -50,7 +53,7 @@ ESM2_650M_MAX_D_MODEL = 2048  # a wider file handed to a config of at most this 
 
 
 def rotary_inv_freq(head_dim=64):
-    """fair-esm RotaryEmbedding's `inv_freq` for heads of `head_dim` (64: the default; 32: ESM-2 150M; 128: ESM-2 15B), float32:
+    """fair-esm RotaryEmbedding's `inv_freq` for heads of `head_dim` (64: the default; 32: ESM-2 150M; 128: ESM-2 15B; 16: ESM-2 8M), float32:
     1.0 / (10000 ** (torch.arange(0, head_dim, 2).float() / head_dim)).  The power is taken in double and rounded to float32 -- the
     values torch's float32 pow gives (numpy's vectorised float32 power is one ulp off at i = 5 and 27 of 32), and what the engine
     builds its cos / sin table from (csrc/engine.hip rope_table)."""
@@ -377,7 +380,8 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
     cfg.update(take)
     # Head width.  64 loads against every base configuration; 32 only against one whose own heads are 32 (ESM2_T30_CONFIG:
     # models.ESM2_150M) and 128 only against one whose own heads are 128 (ESM2_T48_CONFIG: models.ESM2_15B) -- a wrapper promises its
-    # model, as ESM2 refuses the 3B file below; 24 / 16 load nowhere.
+    # model, as ESM2 refuses the 3B file below --, 16 only against one whose own heads are 16 (ESM2_T6_CONFIG: models.ESM2_8M); 24
+    # loads nowhere.
     hd = cfg["d_model"] / max(1, cfg["n_heads"])
     if hd == 32 and head_dim_of(base_cfg) != 32:
         raise ValueError("checkpoint has %d heads of dimension 32: the engine's attention kernels implement head dimension 64 for the "
@@ -394,10 +398,18 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
         raise ValueError("checkpoint has %d heads of dimension 128: the engine's rotary and row kernels hold at most %d of them "
                          "(d_model <= %d, in multiples of 512 above %d; esm2_t48_15B_UR50D has 40)"
                          % (cfg["n_heads"], MAX_HEADS_OF_128, MAX_D_MODEL_HD128, MAX_D_MODEL))
+    if hd == 16 and head_dim_of(base_cfg) != 16:
+        raise ValueError("checkpoint has %d heads of dimension 16: the engine's attention kernels implement head dimension 64 "
+                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D) and 128 (esm2_t48_15B_UR50D) for the "
+                         "configuration it was loaded against; load esm2_t6_8M_UR50D (heads of 16) with models.ESM2_8M / "
+                         "--model esm2_8m" % cfg["n_heads"])
+    if hd == 16 and cfg["n_heads"] > MAX_HEADS_OF_16:
+        raise ValueError("checkpoint has %d heads of dimension 16: the engine's rotary kernel holds at most %d of them (d_model <= %d; "
+                         "esm2_t6_8M_UR50D has 20)" % (cfg["n_heads"], MAX_HEADS_OF_16, 16 * MAX_HEADS_OF_16))
     if hd not in HEAD_DIMS:
         raise ValueError("checkpoint has %d heads of dimension %g: the engine's attention kernels implement head dimension 64 "
-                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D) and 128 (esm2_t48_15B_UR50D)"
-                         % (cfg["n_heads"], hd))
+                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D), 128 (esm2_t48_15B_UR50D) and 16 "
+                         "(esm2_t6_8M_UR50D)" % (cfg["n_heads"], hd))
     if hd != 128 and cfg["d_model"] > MAX_D_MODEL:
         raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head, rotation) hold at "
                          "most %d features per row, 40 heads of 64 (esm2_t36_3B_UR50D)" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL))

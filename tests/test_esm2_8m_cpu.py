@@ -1,0 +1,241 @@
+"""ESM-2 8M (esm2_t6_8M_UR50D: 20 heads of 16, d_model 320) on the host: the configuration, the rotary frequencies for heads of 16, the
+v2 checkpoint reader and which head widths load against which configuration, models.ESM2_8M, the command-line model maps, the numpy
+reference at heads of 16 against the HuggingFace fixture, the attention and GEMM plans at the 8M shapes, the LDS bank model of the
+32-byte key row, and the host-side refusals of the debug entries.  Needs no GPU."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _esm2_reference_hd as ref
+from protein_gibbs_sampler_amd import _lib, weights
+from test_attention_plan_cpu import F16, att, plans, strict
+from test_gemm_plan_cpu import layer, rows
+from test_gemm_plan_cpu import plans as gemm_plans
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+def test_t6_config_values():
+    cfg = weights.ESM2_T6_CONFIG
+    assert (cfg["arch"], cfg["d_model"], cfg["n_layers"], cfg["n_heads"], cfg["d_ffn"], cfg["vocab"]) == (_lib.PG_ARCH_ESM2, 320, 6, 20, 1280, 33)
+    assert weights.head_dim_of(cfg) == 16 and 16 in weights.HEAD_DIMS and 24 not in weights.HEAD_DIMS
+    same = ("max_positions", "pad_idx", "mask_idx", "cls_idx", "eos_idx", "token_dropout", "max_msa_rows", "layer_norm_eps")
+    assert all(cfg[k] == weights.ESM2_T33_CONFIG[k] for k in same)
+    assert weights.MAX_HEADS_OF_16 == 32
+    assert weights.make_config(weights.ESM2_T6_CONFIG, d_model=128, n_layers=2, d_ffn=512)["n_heads"] == 8      # the base's head width
+    assert weights.ESM2_T30_CONFIG["n_heads"] == 20 and weights.ESM2_T48_CONFIG["n_heads"] == 40                  # the others are untouched
+
+
+def test_inv_freq_16_is_torchs():
+    torch = pytest.importorskip("torch")
+    want = (1.0 / (10000 ** (torch.arange(0, 16, 2).float() / 16))).numpy()
+    assert np.array_equal(weights.rotary_inv_freq(16), want)
+
+
+@pytest.fixture(scope="module")
+def hd16_file(tmp_path_factory):
+    """A v2 checkpoint file of 2 layers x 320 with 20 heads of 16 and the state dict it was written from."""
+    torch = pytest.importorskip("torch")
+    cfg = weights.make_config(weights.ESM2_T6_CONFIG, n_layers=2, max_positions=40)
+    assert (cfg["d_model"], cfg["n_heads"], cfg["d_ffn"]) == (320, 20, 1280)
+    sd = weights.synthetic_state_dict(cfg, seed=12, embed_std=0.3)
+    path = tmp_path_factory.mktemp("esm2_8m") / "esm2_hd16.pt"
+    torch.save(weights.to_fair_esm_checkpoint_v2(sd, cfg), path)
+    return str(path), cfg, sd
+
+
+def test_v2_round_trip_with_heads_of_16(hd16_file):
+    torch = pytest.importorskip("torch")
+    path, cfg, sd = hd16_file
+    blob = torch.load(path, weights_only=False)
+    stored = blob["model"]["encoder.sentence_encoder.layers.1.self_attn.rot_emb.inv_freq"].numpy()
+    assert stored.shape == (8,) and np.array_equal(stored, weights.rotary_inv_freq(16))
+    got, cfg2 = weights.load_fair_esm_checkpoint(path, weights.ESM2_T6_CONFIG, return_config=True)
+    assert (cfg2["d_model"], cfg2["n_layers"], cfg2["n_heads"], cfg2["d_ffn"], cfg2["token_dropout"]) == (320, 2, 20, 1280, 1)
+    assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
+
+
+def test_t6_takes_the_8m_sizes_from_hyper_parameters_alone():
+    cfg = weights.config_from_checkpoint_v2(dict(encoder_embed_dim=320, encoder_layers=6, encoder_attention_heads=20, token_dropout=True),
+                                            [], weights.ESM2_T6_CONFIG)
+    assert (cfg["d_model"], cfg["n_heads"], cfg["d_ffn"], cfg["n_layers"]) == (320, 20, 1280, 6)
+    cfg = weights.config_from_checkpoint_v2(dict(encoder_embed_dim=1280, encoder_layers=33, encoder_attention_heads=20), [], weights.ESM2_T6_CONFIG)
+    assert (cfg["d_model"], cfg["n_heads"]) == (1280, 20)                                   # heads of 64 load against every configuration
+
+
+def test_more_than_32_heads_of_16_and_heads_of_24_are_refused():
+    with pytest.raises(ValueError, match="33 heads of dimension 16.*at most 32"):
+        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=33 * 16, encoder_layers=2, encoder_attention_heads=33), [], weights.ESM2_T6_CONFIG)
+    with pytest.raises(ValueError, match="heads of dimension 24"):                          # esm2_t12_35M_UR50D
+        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=480, encoder_layers=12, encoder_attention_heads=20), [], weights.ESM2_T6_CONFIG)
+    with pytest.raises(ValueError, match="esm2_150m"):                                      # heads of 32 still load against t30 only
+        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=640, encoder_layers=2, encoder_attention_heads=20), [], weights.ESM2_T6_CONFIG)
+    with pytest.raises(ValueError, match="esm2_15b"):
+        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=256, encoder_layers=2, encoder_attention_heads=2), [], weights.ESM2_T6_CONFIG)
+
+
+def test_inv_freq_check_at_16(hd16_file, tmp_path):
+    torch = pytest.importorskip("torch")
+    path, cfg, sd = hd16_file
+    blob = weights.to_fair_esm_checkpoint_v2(sd, cfg)
+    key = "encoder.sentence_encoder.layers.0.self_attn.rot_emb.inv_freq"
+    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(32))                      # the head-32 table in a head-16 file
+    p = tmp_path / "bad.pt"
+    torch.save(blob, p)
+    with pytest.raises(ValueError, match=r"inv_freq.*heads of 16"):
+        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T6_CONFIG)
+    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(16) * np.float32(1.001))
+    torch.save(blob, p)
+    with pytest.raises(ValueError, match="inv_freq"):
+        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T6_CONFIG)
+
+
+@pytest.mark.parametrize("base", ["t33", "t36", "t30", "t48"])
+def test_heads_of_16_met_by_the_other_wrappers_name_esm2_8m(hd16_file, base):
+    path, cfg, sd = hd16_file
+    base_cfg = {"t33": weights.ESM2_T33_CONFIG, "t36": weights.ESM2_T36_CONFIG, "t30": weights.ESM2_T30_CONFIG,
+                "t48": weights.ESM2_T48_CONFIG}[base]
+    with pytest.raises(ValueError, match=r"heads of dimension 16: .*head dimension 64.*models\.ESM2_8M / --model esm2_8m"):
+        weights.load_fair_esm_checkpoint(path, base_cfg)
+    with pytest.raises(ValueError, match="esm2_8m"):
+        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=320, encoder_layers=6, encoder_attention_heads=20), [], base_cfg)
+
+
+def test_models_esm2_8m_reads_a_v2_file_without_a_gpu(hd16_file):
+    from protein_gibbs_sampler_amd import models
+    path, cfg, sd = hd16_file
+    m = models.ESM2_8M(checkpoint=path)
+    assert m.cfg["arch"] == _lib.PG_ARCH_ESM2 and (m.cfg["d_model"], m.cfg["n_heads"], m.cfg["d_ffn"], m.cfg["n_layers"]) == (320, 20, 1280, 2)
+    assert m.alphabet.mask_idx == 32 and len(m.alphabet.all_toks) == 33 and m.alphabet.prepend_bos and m.alphabet.append_eos
+    for other in (models.ESM2, models.ESM2_3B, models.ESM2_150M, models.ESM2_15B):
+        with pytest.raises(ValueError, match="esm2_8m"):
+            other(checkpoint=path)
+    if not weights.find_cached_checkpoint("esm2_t6_8M_UR50D.pt"):
+        with pytest.raises(FileNotFoundError, match="esm2_t6_8M_UR50D"):
+            models.ESM2_8M()
+
+
+def test_command_lines_accept_esm2_8m():
+    from protein_gibbs_sampler_amd import likelihood_esm, models, pgen_esm, pgen_esm_from_fasta, seq_probs_esm
+    for mod in (pgen_esm, pgen_esm_from_fasta, likelihood_esm):
+        assert mod.model_map["esm2_8m"] is models.ESM2_8M and mod.model_map["esm2_15b"] is models.ESM2_15B
+        assert mod.build_parser().parse_args(["--model", "esm2_8m"]).model == "esm2_8m"
+    assert seq_probs_esm.model_map["esm2_8m"] is models.ESM2_8M
+    assert pgen_esm.build_parser().parse_args([]).model == "esm1b"                       # defaults unchanged
+    assert likelihood_esm.build_parser().parse_args([]).model == "esm1v"
+
+
+# ---- the numpy reference at heads of 16 ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hf16():
+    z = np.load(os.path.join(HERE, "golden", "esm2_hf_hd16.npz"))
+    cfg = weights.make_config(weights.ESM2_T6_CONFIG, **json.loads(str(z["cfg"])))
+    sd = weights.synthetic_state_dict(cfg, seed=int(z["seed"]), std=float(z["std"]), embed_std=float(z["embed_std"]),
+                                      ln_jitter=float(z["ln_jitter"]))
+    return z, cfg, sd
+
+
+def test_reference_at_16_agrees_with_huggingface(hf16):
+    z, cfg, sd = hf16
+    assert (cfg["d_model"], cfg["n_heads"], cfg["n_layers"]) == (320, 20, 6) and z["tokens"].shape == (2, 258)
+    got = ref.esm2_forward(sd, ref.Esm2Config.of(cfg), z["tokens"][:1])
+    assert np.abs(got - z["logits"][:1]).max() < 2e-4 and z["logits"].std() > 3.0
+
+
+def test_the_same_weights_as_10_heads_of_32_are_a_different_model(hf16):
+    z, cfg, sd = hf16
+    other = dict(cfg, n_heads=10)
+    got = ref.esm2_forward(sd, ref.Esm2Config.of(other), z["tokens"][:1, :40])
+    mine = ref.esm2_forward(sd, ref.Esm2Config.of(cfg), z["tokens"][:1, :40])
+    assert np.abs(got - mine).max() > 0.5
+
+
+# ---- plans at the 8M shapes (an MI355X: 256 CUs) ---------------------------------------------------------------------------------------
+def a16(n_seq, T, **kw):
+    return att(n_seq, T, H=20, hd=16, **kw)
+
+
+PLANS = [
+    (a16(256, 258), "whole kb18 hd16 5120wg"),                       # config 2: 5 rounds of four workgroups per CU
+    (a16(32, 258), "whole kb18 hd16 640wg"),                         # 640 of 1024 slots: one partial round, nothing to split
+    (a16(64, 258), "whole kb18 hd16 split4 1024+1024wg"),
+    (a16(1, 27), "whole kb2 hd16 20wg"),
+    (a16(2, 576), "whole kb36 hd16 split4 0+160wg"),                 # the tallest rung: 40 pairs on 512 slots
+    (a16(2, 577), "long t288 hd16 400wg"),
+    (a16(1, 1026), "long t288 hd16 340wg"),
+    (a16(3, 258, pad=1), "whole kb18 hd16 pad 60wg"),
+    (a16(3, 600, pad=1), "long t288 hd16 pad 600wg"),
+    (a16(2, 258, bias=1), "error: attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only"),
+    (att(2, 258, hd=24), "error: attention: head dimension 24: the kernels are built for 64 and 32"),
+    (att(2, 258, hd=48), "error: attention: head dimension 48: the kernels are built for 64 and 32"),
+    (strict(2, 27, hd=16), "split-f32 kb4 nqb1 hd16 40wg"),
+    (strict(2, 258, hd=16), "split-f32 kb6 nqb5 hd16 40wg"),
+    (strict(2, 100, hd=16, pad=1), "split-f32 kb10 nqb2 hd16 pad 40wg"),
+    (strict(2, 258, hd=16, bias=1), "error: attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only"),
+    (att(2, 258, hd=16, precision=F16), "whole kb18 hd16 split4 0+160wg"),    # 40 pairs on 1024 slots: four parts each
+    (att(256, 258), "whole kb18 hd64 5120wg"),                       # heads of 64 / 32 / 128 as they were
+    (att(64, 258, hd=32), "whole kb18 hd32 split4 1024+1024wg"),
+    (att(2, 289, H=40, hd=128), "long t128 hd128 400wg"),
+]
+
+
+def test_attention_plans_at_head_16():
+    got = plans([list(c) for c, _ in PLANS])
+    wrong = [(c, g, w) for (c, w), g in zip(PLANS, got) if g != w]
+    assert not wrong, "\n".join("%r: plan %r, expected %r" % t for t in wrong)
+
+
+def test_strict_valu_switch_refuses_heads_of_16_by_name():
+    got = plans([list(strict(2, 27, H=2, hd=16))], PGIBBS_ATTN_F32="valu")
+    assert "PGIBBS_ATTN_F32=valu" in got[0] and "heads of 16" in got[0] and got[0].startswith("error: ")
+
+
+def test_gemm_plans_at_the_8m_shapes():
+    """N = 320 / 960 are no multiples of 128: 64 x 64 tiles at every height above the weight-streaming kernel's; fc1 (N = 1280,
+    K = 320) is a shape of the 256 x 256 kernels at config 2; a single chain (32 rows) streams the weights."""
+    shapes = layer(320, 1280)
+    table = rows(66048, shapes, [""] * 4) + rows(8448, shapes, [""] * 4) + rows(32, shapes, [""] * 4)
+    got = gemm_plans([list(c) for c, _ in table])
+    qkv, out, fc1, fc2 = got[0:4]
+    assert qkv.startswith("tile64x64 ") and out.startswith("tile64x64 ") and fc2.startswith("tile64x64 "), got[0:4]
+    assert fc1.startswith("w16-256x256 "), fc1
+    assert all(g.startswith("tile64x64 ") for g in (got[4], got[5], got[7])), got[4:8]
+    assert all(g.startswith("skinny") for g in got[8:12]), got[8:12]
+    assert not any(g.startswith("error") for g in got)
+    bad = gemm_plans([[66048, 480, 480, 2, 2, 1, 0]])[0]                                   # esm2_t12_35M: K = 480
+    assert bad == "error: gemm: K must be a multiple of 64"
+
+
+# ---- the LDS bank model -----------------------------------------------------------------------------------------------------------------
+def test_bank_model_reports_the_built_swizzle_conflict_free():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "lds_bank_model.py")], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    lines = [l for l in out.stdout.splitlines() if l.startswith("HD 16 ")]
+    by = lambda kind, what: [l for l in lines if l.startswith("HD 16 %s " % kind) and what in l]
+    assert "(2 = conflict-free): {2}  tr_b16 cycles (2 = conflict-free): {2}" in by("built", "b64 cycles")[0]
+    assert by("built", "staging-write")[0].endswith("{8}")
+    assert "b64 cycles per read (2 = conflict-free): {4}" in by("none", "b64 cycles")[0]  # unswizzled: 2-way on every score read
+    assert "b64 cycles per read (2 = conflict-free): {4}" in by("r1", "b64 cycles")[0]
+    other = [l for l in out.stdout.splitlines() if l.startswith(("HD 64 built", "HD 32 built", "HD 128 built")) and "tr_b16" in l]
+    assert len(other) == 3 and all("{4}  tr_b16 cycles (2 = conflict-free): {2}" in l for l in other)      # as they were
+
+
+# ---- host-side refusals of the debug entries -------------------------------------------------------------------------------------------
+def test_debug_entries_refuse_on_the_host():
+    L = _lib.lib()
+    x = np.zeros((2, 3 * 33 * 16), np.float32)
+    assert L.pg_dbg_rope_hd(0, _lib.PG_PREC_BF16, _lib.ptr(x), 1, 2, 33, 16) == _lib.PG_ERR_INVALID              # 33 heads of 16
+    assert L.pg_dbg_rope_hd(0, _lib.PG_PREC_BF16, _lib.ptr(x), 1, 2, 2, 24) == _lib.PG_ERR_INVALID
+    H, T = 2, 16
+    qkv = np.zeros((1, T, 3 * H * 16), np.float32)
+    ctx = np.zeros((1, T, H * 16), np.float32)
+    bias = np.zeros((H, 16), np.float32)
+    rc = L.pg_dbg_attention_kv(0, _lib.PG_PREC_BF16, _lib.ptr(qkv), _lib.ptr(ctx), 1, T, H, 16, None, -1, _lib.ptr(bias), _lib.ptr(bias), None, 0)
+    assert rc == _lib.PG_ERR_INVALID and b"heads of 64 only" in L.pg_last_error()
+    rc = L.pg_dbg_attention_hd(0, _lib.PG_PREC_BF16, _lib.ptr(qkv), _lib.ptr(ctx), 1, T, H, 24, None, -1)
+    assert rc == _lib.PG_ERR_INVALID and b"head_dim must be 64 or 32" in L.pg_last_error()

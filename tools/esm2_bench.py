@@ -30,6 +30,11 @@ counted once) -- every such key says "extrapolated".  `device_bytes` holds what 
 engine is created (weights in the operand type, per precision mode) and after the config-2 run (with the activation buffers), and
 the same extrapolation of the weights to 48 layers.
 
+`--size 8m` measures ESM-2 8M (6 x 320, 20 heads of 16, d_ffn 1280; models.ESM2_8M) alone at the same three shapes with the attention,
+rotation, LayerNorm and GEMM classes, and then the head-16 attention launch against the head-32 one of the same B, T, H in the same
+process ("head16_vs_head32": 3-layer models of 20 heads of 16 (d_model 320) and 20 heads of 32 (d_model 640), config-2 shape,
+profiled alternately).
+
 Prints one JSON line.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -55,12 +60,13 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3, help="alternations ESM-1b / ESM-2 per shape")
     ap.add_argument("--prof-iters", type=int, default=3, help="iterations of the profiled run")
     ap.add_argument("--layers", type=int, default=None, help="fewer layers for a rehearsal (default: 33, or 36 with --size 3b)")
-    ap.add_argument("--size", choices=["650m", "3b", "150m", "15b"], default="650m",
+    ap.add_argument("--size", choices=["650m", "3b", "150m", "15b", "8m"], default="650m",
                     help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone; 150m: ESM-2 150M alone, then head 32 against head 64; "
-                         "15b: ESM-2 15B alone (with --layers L < 48: L and L / 2 layers, 48 extrapolated)")
+                         "15b: ESM-2 15B alone (with --layers L < 48: L and L / 2 layers, 48 extrapolated); "
+                         "8m: ESM-2 8M alone, then head 16 against head 32")
     args = ap.parse_args(argv)
     if args.layers is None:
-        args.layers = {"3b": 36, "150m": 30, "15b": 48}.get(args.size, 33)
+        args.layers = {"3b": 36, "150m": 30, "15b": 48, "8m": 6}.get(args.size, 33)
 
     import torch
     from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
@@ -88,6 +94,9 @@ def main(argv=None):
     elif args.size == "150m":
         samplers = {"esm2_150m": build(models.ESM2_150M, weights.ESM2_T30_CONFIG)}
         rotary, model_cfg = "esm2_150m", weights.ESM2_T30_CONFIG
+    elif args.size == "8m":
+        samplers = {"esm2_8m": build(models.ESM2_8M, weights.ESM2_T6_CONFIG)}
+        rotary, model_cfg = "esm2_8m", weights.ESM2_T6_CONFIG
     elif args.size == "15b":
         import gc
         half = args.layers // 2 if args.layers < 48 else 0
@@ -208,13 +217,17 @@ def main(argv=None):
         out["shapes"][name] = rec
     if device_bytes:
         out["device_bytes"] = device_bytes
-    if args.size == "150m":
-        # the head-32 kernels against the head-64 ones: same process, alternating, config-2 shape
+    if args.size in ("150m", "8m"):
+        # the head-32 kernels against the head-64 ones (8m: head 16 against head 32): same process, alternating, config-2 shape
         name, B, L, P = SHAPES[0]
         rows = B * (L + 2)
-        trio = {"h20x32_d640": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=3),
-                "h20x64_d1280": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3),
-                "h10x64_d640": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3, d_model=640, d_ffn=2560)}
+        if args.size == "8m":
+            trio = {"h20x16_d320": build(models.ESM2_8M, weights.ESM2_T6_CONFIG, n_layers=3),
+                    "h20x32_d640": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=3)}
+        else:
+            trio = {"h20x32_d640": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=3),
+                    "h20x64_d1280": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3),
+                    "h10x64_d640": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3, d_model=640, d_ffn=2560)}
         jobs = {k: job(s, B, L, P, args.prof_iters) for k, s in trio.items()}
         for k in trio:
             jobs[k]()                                   # warm-up of every shape, unprofiled
@@ -237,7 +250,7 @@ def main(argv=None):
                       "attention_ms_per_launch_rounds": [round(v, 5) for v in per[k]["attention"]],
                       "rope_ms_per_launch": round(r_ms, 5), "rope_ms_per_launch_rounds": [round(v, 5) for v in per[k]["rope"]],
                       "rope_GBps": round(rows * 2 * dm * 2 * 2 / (r_ms * 1e-3) / 1e9, 1) if r_ms > 0 else None}
-        out["head32_vs_head64"] = cmp
+        out["head16_vs_head32" if args.size == "8m" else "head32_vs_head64"] = cmp
     print(json.dumps(out))
 
 
