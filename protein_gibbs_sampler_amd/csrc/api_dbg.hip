@@ -9,6 +9,7 @@
 
 #include "engine.h"
 #include "gemm_epilogue.h"
+#include "ln_row.h"
 
 using namespace pg;
 
@@ -436,7 +437,7 @@ int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, in
   return pg_dbg_attention_hd(device, precision, qkv, ctx, B, T, H, 64, nullptr, -1);
 }
 
-/* pg_dbg_attention with the head dimension (64 or 32) and, optionally, the tokens of the keys: key_tok[B][T], keys whose token is
+/* pg_dbg_attention with the head dimension (a width of head_width.h) and, optionally, the tokens of the keys: key_tok[B][T], keys whose token is
  * pad_idx are masked as in a ragged batch (NULL: none) */
 int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
                         const int32_t* key_tok, int pad_idx) {
@@ -452,7 +453,7 @@ int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx,
   int rc = dbg_precision("pg_dbg_attention_kv", precision, true);
   if (rc) return rc;
   if (!qkv || !ctx || B < 1 || T < 1 || H < 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_attention: bad argument");
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B) or 16 (ESM-2 8M)");
+  if (!head_width(head_dim)) return fail(PG_ERR_INVALID, "pg_dbg_attention_hd: head_dim must be " + head_widths_text(false));
   if (!bias_k != !bias_v) return fail(PG_ERR_INVALID, "pg_dbg_attention_kv: bias_k and bias_v come together or not at all");
   const std::string head_err = attention_head_error(head_dim, bias_k != nullptr);      // the plans' own refusal of a bias key at head 32
   if (!head_err.empty()) return fail(PG_ERR_INVALID, head_err);
@@ -499,12 +500,13 @@ int pg_dbg_rope(int device, int precision, float* qkv, int B, int T, int H) {
   return pg_dbg_rope_hd(device, precision, qkv, B, T, H, 64);
 }
 
-/* pg_dbg_rope with the head dimension: 64 (H <= 40), 32 (H <= 32), 128 (H <= 40) or 16 (H <= 32) */
+/* pg_dbg_rope with the head dimension: a width of head_width.h, at most its max_heads heads */
 int pg_dbg_rope_hd(int device, int precision, float* qkv, int B, int T, int H, int head_dim) {
   int rc = dbg_precision("pg_dbg_rope_hd", precision, true);
   if (rc) return rc;
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be 64 or 32, or 128 (ESM-2 15B) or 16 (ESM-2 8M)");
-  if (!qkv || B < 1 || T < 1 || H < 1 || H > (head_dim == 32 || head_dim == 16 ? 32 : 40)) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
+  const HeadWidth* w = head_width(head_dim);
+  if (!w) return fail(PG_ERR_INVALID, "pg_dbg_rope_hd: head_dim must be " + head_widths_text(false));
+  if (!qkv || B < 1 || T < 1 || H < 1 || H > w->max_heads) return fail(PG_ERR_INVALID, "pg_dbg_rope: bad argument");
   Dbg s;
   if ((rc = s.open(device))) return rc;
   const int d = H * head_dim;
@@ -581,7 +583,7 @@ int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx
 extern "C++" {
 namespace {
 int dbg_row_width(const char* who, int d) {
-  if (d < 4 || d % 4 || (d > 2560 && (d % 512 || d > 5120))) return      // row_d_ok of elementwise.hip
+  if (!row_d_ok(d)) return
     fail(PG_ERR_INVALID, std::string(who) + ": d must be a multiple of 4 and <= 2560, or a multiple of 512 up to 5120");
   return PG_OK;
 }

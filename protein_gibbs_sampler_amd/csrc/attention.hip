@@ -483,10 +483,7 @@ int launch_attention_seq_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int
                                            sl, key_tok, pad_idx, bias_kv, p.split_from, p.split);
     });
   };
-  if (head_dim == 64) launch(std::integral_constant<int, 64>{});
-  else if (head_dim == 128) launch(std::integral_constant<int, 128>{});
-  else if (head_dim == 16) launch(std::integral_constant<int, 16>{});
-  else launch(std::integral_constant<int, 32>{});
+  visit_head_width(head_dim, launch);
   PG_HIP(hipGetLastError());
   return 0;
 }

@@ -648,13 +648,12 @@ struct StrictAttentionPlan {
 static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step) {
   StrictAttentionPlan p;
   p.hd = head_dim, p.pad = has_pad, p.bias = has_bias, p.valu = attn_f32_valu();
-  auto refuse = [&](const char* why) { p.error = why; return p; };
+  auto refuse = [&](const std::string& why) { p.error = why; return p; };
   p.error = attention_head_error(head_dim, has_bias);
   if (!p.error.empty()) return p;
   if (head_dim != 64 && p.valu)
-    return refuse(head_dim == 128 ? "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 128"
-                  : head_dim == 16 ? "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 16"
-                                  : "attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of 32");
+    return refuse("attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of " +
+                  std::to_string(head_dim));
   if (n_seq == 0) return p;
   if (T <= 0) return refuse("attention: empty sequence");
   if (has_bias && p.valu) return refuse("attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)");

@@ -138,7 +138,7 @@ inline bool visit_rung(int kb, F&& f) {
 }
 // what the full-attention plans (attention.hip, attention_f32.hip) refuse before they look at the shape; empty: nothing
 inline std::string attention_head_error(int head_dim, bool has_bias) {
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32";
+  if (!head_width(head_dim)) return "attention: head dimension " + std::to_string(head_dim) + ": the kernels are built for " + head_widths_text(true);
   if (head_dim != 64 && has_bias) return "attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only";
   return {};
 }

@@ -363,9 +363,7 @@ static inline unsigned rows_grid(int64_t rows) { return (unsigned)((rows + 3) / 
 static inline bool rows_fit(int64_t rows) { return rows >= 0 && (rows + 3) / 4 <= 0x7fffffffLL; }
 // the row kernels hold a row as float4 v[NCH] per lane: the 8-chunk instantiation up to d = 2048 (every model before ESM-2 3B runs
 // it, unchanged), the 10-chunk one up to d = 2560, the 20-chunk one for the whole 512-feature units above it up to d = 5120
-static inline bool row_d_ok(int d) {
-  return d >= 4 && d % 4 == 0 && (d <= kMaxChWide * 256 || (d % kRowUnit5k == 0 && d <= kMaxCh5k * 256));
-}
+// (row_d_ok of ln_row.h)
 static inline bool row_wide(int d) { return d > kMaxCh * 256; }
 // f(integral_constant<int, NCH>) for the NCH of a row of d values: a launcher names its kernel template once
 template <class F>

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include "gemm_epilogue.h"
+#include "ln_row.h"
 
 namespace pg {
 
@@ -229,35 +230,24 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   if (cfg.d_model % (cfg.arch == PG_ARCH_ESM2 ? 64 : 128) || cfg.d_ffn % 128)
     return fail(PG_ERR_INVALID, cfg.arch == PG_ARCH_ESM2 ? "d_model must be a multiple of 64 (PG_ARCH_ESM2) and d_ffn of 128"
                                                          : "d_model and d_ffn must be multiples of 128");
-  // head width: the attention and rotary kernels are built for 64 (every architecture), 32, 128 and 16 (ESM-2 only:
-  // esm2_t30_150M_UR50D, esm2_t48_15B_UR50D, esm2_t6_8M_UR50D)
+  // head width (head_width.h): a width the attention and rotary kernels are built for, for this architecture; then no more heads than
+  // the rotary and row kernels hold per row at that width; then a row width the row kernels take (ln_row.h: above 2560 features,
+  // which only heads of 128 reach, whole 512-feature units)
   head_dim = cfg.n_heads > 0 && cfg.d_model % cfg.n_heads == 0 ? cfg.d_model / cfg.n_heads : 0;
-  if (head_dim == 32 && cfg.arch != PG_ARCH_ESM2)
-    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
-                                    " with heads of 32: head dim must be 64 for this architecture (heads of 32 run for PG_ARCH_ESM2 only)");
-  if (head_dim == 128 && cfg.arch != PG_ARCH_ESM2)
-    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
-                                    " with heads of 128: head dim must be 64 for this architecture (heads of 128 run for PG_ARCH_ESM2 only)");
-  if (head_dim == 16 && cfg.arch != PG_ARCH_ESM2)
-    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") +
-                                    " with heads of 16: head dim must be 64 for this architecture (heads of 16 run for PG_ARCH_ESM2 only)");
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16)
-    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " with " + std::to_string(cfg.n_heads) +
-                                    " heads: head dim must be 64 (every architecture), or 32, 128 or 16 (PG_ARCH_ESM2)");
-  if (head_dim == 16 && cfg.n_heads > 32)
-    return fail(PG_ERR_INVALID, "heads of 16: the rotary kernel holds at most 32 of them per row (d_model <= 512; esm2_t6_8M_UR50D has 20), not " +
-                                    std::to_string(cfg.n_heads));
-  if (head_dim == 32 && cfg.n_heads > 32)
-    return fail(PG_ERR_INVALID, "heads of 32: the rotary kernel holds at most 32 of them per row (d_model <= 1024; esm2_t30_150M_UR50D has 20)");
-  // heads of 128 (esm2_t48_15B_UR50D): at most 40 of them, and above 2560 features the row kernels take whole 512-feature units
-  if (head_dim == 128 && cfg.n_heads > 40)
-    return fail(PG_ERR_INVALID, "heads of 128: the rotary and row kernels hold at most 40 of them per row (d_model <= 5120; esm2_t48_15B_UR50D has 40), not " +
-                                    std::to_string(cfg.n_heads) + " (d_model " + std::to_string(cfg.d_model) + ")");
-  if (head_dim == 128 && cfg.d_model > 2560 && cfg.d_model % 512)
-    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " > 2560 with heads of 128: the row kernels take multiples of 512 up to 5120 there");
-  // the row kernels (ln_row.h, rope.hip) hold a row of at most 2560 features per wave at heads of 64 / 32: 40 heads of 64, ESM-2 3B
-  if (head_dim != 128 && cfg.d_model > 2560)
-    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " > 2560: the engine runs up to 40 heads of 64 (esm2_t36_3B_UR50D)");
+  const HeadWidth* hw = head_width(head_dim);
+  const std::string heads_of = "heads of " + std::to_string(head_dim);
+  if (!hw)
+    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " with " + std::to_string(cfg.n_heads) + " heads: head dim must be " +
+                                    head_widths_text(true));
+  if (hw->esm2_only && cfg.arch != PG_ARCH_ESM2)
+    return fail(PG_ERR_INVALID, std::string(cfg.arch == PG_ARCH_ESM1B ? "ESM-1b" : cfg.arch == PG_ARCH_MSA1B ? "ESM-MSA-1b" : "ESM-1") + " with " + heads_of +
+                                    ": head dim must be 64 for this architecture (" + heads_of + " run for PG_ARCH_ESM2 only)");
+  if (cfg.n_heads > hw->max_heads)
+    return fail(PG_ERR_INVALID, heads_of + ": the rotary and row kernels hold at most " + std::to_string(hw->max_heads) + " of them per row (d_model <= " +
+                                    std::to_string(hw->max_heads * head_dim) + ": " + hw->model + "), not " + std::to_string(cfg.n_heads) + " (d_model " +
+                                    std::to_string(cfg.d_model) + ")");
+  if (!row_d_ok(cfg.d_model))
+    return fail(PG_ERR_INVALID, "d_model " + std::to_string(cfg.d_model) + " with " + heads_of + ": the row kernels take up to 2560 features, and multiples of 512 up to 5120 above");
   if (cfg.vocab < 1 || cfg.vocab > 64) return fail(PG_ERR_INVALID, "vocab must be in 1..64");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -273,13 +263,11 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
     if (tensors[i].name) tm.m[tensors[i].name] = &tensors[i];
   Uploader up{this, &tm, prec, ""};
   const int d = cfg.d_model, f = cfg.d_ffn, V = cfg.vocab;
-  float qs = 0.125f;  // head_dim^-0.5 = 64^-0.5, folded into W_q and b_q (exact in bf16)
-  // heads of 32: 32^-0.5 is no power of two.  Still folded into W_q and b_q, as an fp32 factor applied to the fp32 checkpoint values
-  // BEFORE they are rounded to the 16-bit operand (or split into the strict mode's bf16 pair) -- the kernels stay scale-free and
-  // the only new rounding is that fp32 product, 2^-24 relative, under an operand rounding of 2^-9 / 2^-12 / 2^-17
-  if (head_dim == 32) qs = 0.17677669529663687f;
-  if (head_dim == 128) qs = 0.08838834764831845f;      // 128^-0.5: the same fold
-  if (head_dim == 16) qs = 0.25f;                      // 16^-0.5: a power of two again, exact like the 0.125 of heads of 64
+  // head_dim^-0.5, folded into W_q and b_q.  A power of two at heads of 64 and 16 (exact in bf16).  32^-0.5 and 128^-0.5 are none:
+  // still folded, as an fp32 factor applied to the fp32 checkpoint values BEFORE they are rounded to the 16-bit operand (or split into
+  // the strict mode's bf16 pair) -- the kernels stay scale-free and the only new rounding is that fp32 product, 2^-24 relative, under
+  // an operand rounding of 2^-9 / 2^-12 / 2^-17
+  const float qs = hw->q_scale;
   bool ok = true;
   ok = ok && (embed = up.f32("embed_tokens.weight", (int64_t)V * d));
   // ESM-2 has no position table (pos stays null: embed_ln_kernel adds nothing) -- positions enter through the rotation of q and k

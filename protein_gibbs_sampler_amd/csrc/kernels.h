@@ -1,6 +1,7 @@
 // Launchers of the gfx950 kernels (one translation unit per kernel family).
 #pragma once
 #include "pg_common.h"
+#include "head_width.h"
 
 #include "../../include/pgibbs.h"
 

@@ -18,6 +18,10 @@ constexpr int kMaxCh = 8;       // d <= 8 * 256 = 2048
 constexpr int kMaxChWide = 10;  // d <= 10 * 256 = 2560
 constexpr int kMaxCh5k = 20;    // d <= 20 * 256 = 5120, in units of kRowUnit5k
 constexpr int kRowUnit5k = 512;
+// the row widths the instantiations above cover: what the row launchers (elementwise.hip), their debug entries and the engine admit
+constexpr bool row_d_ok(int d) {
+  return d >= 4 && d % 4 == 0 && (d <= kMaxChWide * 256 || (d % kRowUnit5k == 0 && d <= kMaxCh5k * 256));
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -36,21 +36,6 @@
 
 PG_OPS_BEGIN
 
-// passes per row = lane-slots / 64, a template parameter of the kernels: H <= 32 (d_model <= 2048) keeps the 4- and 8-pass forms,
-// H <= 40 (d_model 2560: ESM-2 3B) runs 5 and 10 passes -- the same lane ownership and the same arithmetic, a wider row in registers
-constexpr int kRopePass16 = 4, kRopePass16Wide = 5;    // 8 H lane-slots / 64 lanes
-constexpr int kRopePass32 = 8, kRopePass32Wide = 10;   // 16 H lane-slots / 64 lanes
-constexpr int kRopeHeads = 32, kRopeHeadsWide = 40;
-// heads of 32: up to 32 of them (d_model <= 1024; ESM-2 150M has 20) in 2 (16-bit: 4 H slots) and 4 (fp32: 8 H slots) passes
-constexpr int kRopePass16Hd32 = 2, kRopePass32Hd32 = 4;
-// heads of 128: up to 20 of them in 5 (16-bit: 16 H slots) and 10 (fp32: 32 H slots) passes, up to 40 (d_model 5120: ESM-2 15B) in 10 and 20
-constexpr int kRopePass16Hd128 = 5, kRopePass16Hd128Wide = 10;
-constexpr int kRopePass32Hd128 = 10, kRopePass32Hd128Wide = 20;
-constexpr int kRopeHeadsHd128 = 20, kRopeHeadsHd128Wide = 40;
-// heads of 16: up to 32 of them (d_model <= 512; ESM-2 8M has 20) in 1 (16-bit: 2 H slots) and 2 (fp32: 4 H slots) passes
-constexpr int kRopePass16Hd16 = 1, kRopePass32Hd16 = 2;
-constexpr int kRopeHeadsHd16 = 32;
-
 __device__ __forceinline__ void rope_pair(float& lo, float& hi, float c, float s) {
   const float a = lo, b = hi;
   lo = __fsub_rn(__fmul_rn(a, c), __fmul_rn(b, s));
@@ -184,61 +169,57 @@ static int rope_occupancy(Kern kern) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, 0) == hipSuccess && v > 0 ? v : 4;
 }
 
+struct RopePlan {
+  std::string error;      // not empty: the call is refused (error code 1)
+  int hd = 0, passes = 0; // the kernel's <NP, HD>
+};
+// which instantiation rotates rows of H heads of head_dim: the narrow one up to the width's rope_narrow heads, else the wide one
+static RopePlan plan_rope(bool f32, int H, int head_dim) {
+  RopePlan p;
+  const HeadWidth* w = head_width(head_dim);
+  if (!w) p.error = "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for " + head_widths_text(true);
+  else if (H < 1 || H > w->max_heads)
+    p.error = "rope: 1.." + std::to_string(w->max_heads) + " heads of " + std::to_string(head_dim) + " (d_model <= " + std::to_string(w->max_heads * head_dim) + ")";
+  else p.hd = head_dim, p.passes = rope_passes(head_dim, H <= w->rope_narrow ? w->rope_narrow : w->max_heads, f32);
+  return p;
+}
+
+// the <NP, HD> kernel of a buffer type
+template <int NP, int HD> static auto rope_kernel(bf16_t*) { return rope16_kernel<NP, HD>; }
+template <int NP, int HD> static auto rope_kernel(float*) { return rope32_kernel<NP, HD>; }
+
 // the grid = what is resident at once (occupancy of the kernel x CUs), or fewer workgroups when the rows need fewer
-template <typename Buf>
-static int rope_launch(void (*kern)(Buf*, const float*, int, int, int, int), int occ, hipStream_t s, Buf* qkv, const float* table, int64_t M,
-                       int T, int H, int ld) {
-  const int n_cu = device_cu_count();
-  const int64_t need = (M + 3) / 4, resident = (int64_t)n_cu * occ;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(need < resident ? need : resident)), dim3(256), 0, s, qkv, table, (int)M, T, H, ld);
-  PG_HIP(hipGetLastError());
-  return 0;
+template <int NP, int HD, typename Buf>
+static void rope_launch(hipStream_t s, Buf* qkv, const float* table, int64_t M, int T, int H, int ld) {
+  // asked once per instantiation (function-local static: initialised thread-safely)
+  static const int occ = rope_occupancy(rope_kernel<NP, HD>(qkv));
+  const int64_t need = (M + 3) / 4, resident = (int64_t)device_cu_count() * occ;
+  hipLaunchKernelGGL((rope_kernel<NP, HD>(qkv)), dim3((unsigned)(need < resident ? need : resident)), dim3(256), 0, s, qkv, table, (int)M, T, H, ld);
 }
 
 int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int table_rows, int64_t M, int T, int H, int ld,
                 int head_dim) {
-  if (head_dim != 64 && head_dim != 32 && head_dim != 128 && head_dim != 16) return fail(1, "rope: head dimension " + std::to_string(head_dim) + ": the kernels are built for 64 and 32");
-  if (head_dim == 128 && (H < 1 || H > kRopeHeadsHd128Wide)) return fail(1, "rope: 1..40 heads of 128 (d_model <= 5120)");
-  if (head_dim == 64 && (H < 1 || H > kRopeHeadsWide)) return fail(1, "rope: 1..40 heads of 64 (d_model <= 2560)");
-  if (head_dim == 32 && (H < 1 || H > kRopeHeads)) return fail(1, "rope: 1..32 heads of 32 (d_model <= 1024)");
-  if (head_dim == 16 && (H < 1 || H > kRopeHeadsHd16)) return fail(1, "rope: 1..32 heads of 16 (d_model <= 512)");
+  const RopePlan p = plan_rope(f32, H, head_dim);
+  if (!p.error.empty()) return fail(1, p.error);
   if (T < 1 || T > table_rows) return fail(1, "rope: sequence longer than the cos / sin table");
   if (ld < 3 * H * head_dim || ld % (f32 ? 4 : 8)) return fail(1, "rope: rows must hold [q | k | v] and keep 16-byte alignment");
   if (M == 0) return 0;
   if (M > 0x7fffffff - 4 * 8 * 1024) return fail(1, "rope: too many rows");     // 32-bit row arithmetic in the kernels
-  if (head_dim == 32) {
-    static const int occ16h = rope_occupancy(rope16_kernel<kRopePass16Hd32, 32>);
-    static const int occ32h = rope_occupancy(rope32_kernel<kRopePass32Hd32, 32>);
-    return f32 ? rope_launch(rope32_kernel<kRopePass32Hd32, 32>, occ32h, s, (float*)qkv, table, M, T, H, ld)
-               : rope_launch(rope16_kernel<kRopePass16Hd32, 32>, occ16h, s, (bf16_t*)qkv, table, M, T, H, ld);
-  }
-  if (head_dim == 16) {
-    static const int occ16q = rope_occupancy(rope16_kernel<kRopePass16Hd16, 16>);
-    static const int occ32q = rope_occupancy(rope32_kernel<kRopePass32Hd16, 16>);
-    return f32 ? rope_launch(rope32_kernel<kRopePass32Hd16, 16>, occ32q, s, (float*)qkv, table, M, T, H, ld)
-               : rope_launch(rope16_kernel<kRopePass16Hd16, 16>, occ16q, s, (bf16_t*)qkv, table, M, T, H, ld);
-  }
-  if (head_dim == 128) {
-    static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16Hd128, 128>);
-    static const int occ32 = rope_occupancy(rope32_kernel<kRopePass32Hd128, 128>);
-    static const int occ16w = rope_occupancy(rope16_kernel<kRopePass16Hd128Wide, 128>);
-    static const int occ32w = rope_occupancy(rope32_kernel<kRopePass32Hd128Wide, 128>);
-    const bool wide = H > kRopeHeadsHd128;
-    if (f32) return wide ? rope_launch(rope32_kernel<kRopePass32Hd128Wide, 128>, occ32w, s, (float*)qkv, table, M, T, H, ld)
-                         : rope_launch(rope32_kernel<kRopePass32Hd128, 128>, occ32, s, (float*)qkv, table, M, T, H, ld);
-    return wide ? rope_launch(rope16_kernel<kRopePass16Hd128Wide, 128>, occ16w, s, (bf16_t*)qkv, table, M, T, H, ld)
-                : rope_launch(rope16_kernel<kRopePass16Hd128, 128>, occ16, s, (bf16_t*)qkv, table, M, T, H, ld);
-  }
-  // asked once per instantiation (function-local statics: initialised thread-safely)
-  static const int occ16 = rope_occupancy(rope16_kernel<kRopePass16>);
-  static const int occ32 = rope_occupancy(rope32_kernel<kRopePass32>);
-  static const int occ16w = rope_occupancy(rope16_kernel<kRopePass16Wide>);
-  static const int occ32w = rope_occupancy(rope32_kernel<kRopePass32Wide>);
-  const bool wide = H > kRopeHeads;
-  if (f32) return wide ? rope_launch(rope32_kernel<kRopePass32Wide>, occ32w, s, (float*)qkv, table, M, T, H, ld)
-                       : rope_launch(rope32_kernel<kRopePass32>, occ32, s, (float*)qkv, table, M, T, H, ld);
-  return wide ? rope_launch(rope16_kernel<kRopePass16Wide>, occ16w, s, (bf16_t*)qkv, table, M, T, H, ld)
-              : rope_launch(rope16_kernel<kRopePass16>, occ16, s, (bf16_t*)qkv, table, M, T, H, ld);
+  // width x {narrow, wide} x {16-bit, fp32}: a width whose narrow row is its widest has no wide form
+  visit_head_width(p.hd, [&](auto hd) {
+    constexpr int HD = decltype(hd)::value;
+    constexpr HeadWidth w = *head_width(HD);
+    auto go = [&](auto heads) {
+      constexpr int HEADS = decltype(heads)::value;
+      if (f32) rope_launch<rope_passes(HD, HEADS, true), HD>(s, (float*)qkv, table, M, T, H, ld);
+      else rope_launch<rope_passes(HD, HEADS, false), HD>(s, (bf16_t*)qkv, table, M, T, H, ld);
+    };
+    if constexpr (w.rope_narrow < w.max_heads)
+      if (p.passes > rope_passes(HD, w.rope_narrow, f32)) return go(std::integral_constant<int, w.max_heads>{});
+    go(std::integral_constant<int, w.rope_narrow>{});
+  });
+  PG_HIP(hipGetLastError());
+  return 0;
 }
 
 PG_OPS_END

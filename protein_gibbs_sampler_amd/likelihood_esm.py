@@ -13,8 +13,7 @@ from .fasta_io import parse_fasta
 
 POSITIONAL_SCORE_SEP = ";"
 model_map = {"esm1b": models.ESM1b, "esm6": models.ESM6, "esm12": models.ESM12, "esm34": models.ESM34, "esm1v": models.ESM1v,
-             "esm2": models.ESM2, "esm2_3b": models.ESM2_3B, "esm2_150m": models.ESM2_150M, "esm2_15b": models.ESM2_15B,
-             "esm2_8m": models.ESM2_8M}
+             **models.ESM2_MODELS}
 
 
 def main(input_h, output_h, masking_off, device, model, batch_size, mask_distance, csv, score_name, positionwise=None, sampler=None):

@@ -55,7 +55,16 @@ class ESM1v(_Wrapper):
                          "esm1v_t33_650M_UR90S_1.pt", seed, precision, synthetic, config is not None)
 
 
-class ESM2(_Wrapper):
+class _ESM2(_Wrapper):
+    """ESM-2 family: the ESM-1b alphabet, <cls> prepended and <eos> appended; the v2 checkpoint layout."""
+    _cfg, _file = None, None
+
+    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
+        super().__init__(config or dict(self._cfg), Alphabet(True, True), False, state_dict, checkpoint,
+                         self._file, seed, precision, synthetic, config is not None)
+
+
+class ESM2(_ESM2):
     """esm2_t33_650M_UR50D: fair-esm's ESM-2 at 650M parameters (not a model of the original pgen package; the successor of ESM-1b
     in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
     layout (weights.load_fair_esm_checkpoint).  This wrapper promises the 650M model: a checkpoint wider than d_model 2048 (the 3B
@@ -63,36 +72,27 @@ class ESM2(_Wrapper):
     ESM2_150M, the 15B file (heads of 128) with one naming ESM2_15B and the 8M file (heads of 16) with one naming ESM2_8M.  The one
     other released size, 35M, has heads of 24 and d_model 480 and is refused by head width: the engine's attention kernels implement
     heads of 64, 32, 128 and 16 (and its GEMMs take d_model in multiples of 64)."""
-
-    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
-        super().__init__(config or dict(_w.ESM2_T33_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
-                         "esm2_t33_650M_UR50D.pt", seed, precision, synthetic, config is not None)
+    _cfg, _file = _w.ESM2_T33_CONFIG, "esm2_t33_650M_UR50D.pt"
 
 
-class ESM2_3B(_Wrapper):
+class ESM2_3B(_ESM2):
     """esm2_t36_3B_UR50D: ESM-2 at 3B parameters -- 36 layers, d_model 2560, 40 heads of 64, d_ffn 10240; about 5.7 GB of 16-bit
     weights on the device (17 GB in precision="fp32").  The same wrapper as ESM2 (v2 checkpoint layout, ESM-1b alphabet and LM head)
     with the wider configuration; the widest model the engine's row kernels hold (csrc/ln_row.h).  Sizes come from the file: a
     narrower checkpoint with heads of 64 (the 650M file included) loads here without remark and runs as the model it is -- only the
     opposite mismatch, a 3B file met by ESM2, is refused."""
-
-    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
-        super().__init__(config or dict(_w.ESM2_T36_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
-                         "esm2_t36_3B_UR50D.pt", seed, precision, synthetic, config is not None)
+    _cfg, _file = _w.ESM2_T36_CONFIG, "esm2_t36_3B_UR50D.pt"
 
 
-class ESM2_150M(_Wrapper):
+class ESM2_150M(_ESM2):
     """esm2_t30_150M_UR50D: ESM-2 at 150M parameters -- 30 layers, d_model 640, 20 heads of 32, d_ffn 2560; a quarter of the 650M
     model's GEMM work per token, the size to iterate a design loop with.  The same wrapper as ESM2 with the head-32 instantiations of
     the attention and rotary kernels (csrc/attn_frag.h).  Sizes come from the file: any checkpoint with heads of 32 (at most 32 of
     them) or of 64 loads here and runs as the model it is; heads of 32 load ONLY here -- ESM2 and ESM2_3B refuse them by name."""
-
-    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
-        super().__init__(config or dict(_w.ESM2_T30_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
-                         "esm2_t30_150M_UR50D.pt", seed, precision, synthetic, config is not None)
+    _cfg, _file = _w.ESM2_T30_CONFIG, "esm2_t30_150M_UR50D.pt"
 
 
-class ESM2_15B(_Wrapper):
+class ESM2_15B(_ESM2):
     """esm2_t48_15B_UR50D: ESM-2 at 15B parameters -- 48 layers, d_model 5120, 40 heads of 128, d_ffn 20480.  The same wrapper as ESM2
     with the head-128 instantiations of the attention and rotary kernels (csrc/attn_frag.h) and the 20-chunk row kernels
     (csrc/ln_row.h).  Sizes come from the file: any checkpoint with heads of 128 (at most 40 of them; d_model a multiple of 512 above
@@ -101,22 +101,20 @@ class ESM2_15B(_Wrapper):
     16-bit modes 2.573 GB at 4 layers and 5.090 GB at 8, i.e. 0.629 GB per layer and 30.3 GB at 48 layers; strict mode
     (precision="fp32") 4.096 GB at 2 layers and 7.713 GB at 4, i.e. 1.809 GB per layer and 87.3 GB at 48.  The 48-layer figures are
     extrapolated from those measurements: the full model has not been created (its synthetic fp32 weights are 60 GB on the host)."""
-
-    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
-        super().__init__(config or dict(_w.ESM2_T48_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
-                         "esm2_t48_15B_UR50D.pt", seed, precision, synthetic, config is not None)
+    _cfg, _file = _w.ESM2_T48_CONFIG, "esm2_t48_15B_UR50D.pt"
 
 
-class ESM2_8M(_Wrapper):
+class ESM2_8M(_ESM2):
     """esm2_t6_8M_UR50D: ESM-2 at 8M parameters -- 6 layers, d_model 320, 20 heads of 16, d_ffn 1280; the smallest released size, the
     one to tune a design loop of thousands of chains on.  The same wrapper as ESM2 with the head-16 instantiations of the attention and
     rotary kernels (csrc/attn_frag.h: a half-depth score MFMA, 32-byte LDS rows).  Sizes come from the file: any checkpoint with heads
     of 16 (at most 32 of them, d_model a multiple of 64) or of 64 loads here and runs as the model it is; heads of 16 load ONLY here --
     ESM2, ESM2_3B, ESM2_150M and ESM2_15B refuse them by name."""
+    _cfg, _file = _w.ESM2_T6_CONFIG, "esm2_t6_8M_UR50D.pt"
 
-    def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
-        super().__init__(config or dict(_w.ESM2_T6_CONFIG), Alphabet(True, True), False, state_dict, checkpoint,
-                         "esm2_t6_8M_UR50D.pt", seed, precision, synthetic, config is not None)
+
+# the ESM-2 wrappers under their command-line names (--model)
+ESM2_MODELS = {"esm2": ESM2, "esm2_3b": ESM2_3B, "esm2_150m": ESM2_150M, "esm2_15b": ESM2_15B, "esm2_8m": ESM2_8M}
 
 
 class ESM_MSA1(_Wrapper):

@@ -12,8 +12,7 @@ from .esm_sampler import ESM_sampler
 from .fasta_io import write_sequential_fasta
 
 model_map = {"esm1b": models.ESM1b, "esm1v": models.ESM1v, "esm6": models.ESM6, "esm12": models.ESM12, "esm34": models.ESM34,
-             "esm2": models.ESM2, "esm2_3b": models.ESM2_3B, "esm2_150m": models.ESM2_150M, "esm2_15b": models.ESM2_15B,
-             "esm2_8m": models.ESM2_8M}
+             **models.ESM2_MODELS}
 
 
 def main(input_h, output_p, args):

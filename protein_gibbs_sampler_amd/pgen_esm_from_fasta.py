@@ -14,9 +14,8 @@ from .esm_sampler import ESM_sampler
 from .fasta_io import parse_fasta, write_sequential_fasta
 from .msa_tools import add_gaps_back, unalign
 
-model_map = {"esm1b": models.ESM1b, "esm6": models.ESM6, "esm12": models.ESM12, "esm34": models.ESM34, "esm2": models.ESM2,
-             "esm2_3b": models.ESM2_3B, "esm2_150m": models.ESM2_150M, "esm2_15b": models.ESM2_15B,
-             "esm2_8m": models.ESM2_8M}
+model_map = {"esm1b": models.ESM1b, "esm6": models.ESM6, "esm12": models.ESM12, "esm34": models.ESM34,
+             **models.ESM2_MODELS}
 
 
 def main(input_h, output_p, args, sampler=None):

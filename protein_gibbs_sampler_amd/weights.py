@@ -43,12 +43,23 @@ ESM2_T30_CONFIG = dict(ESM2_T33_CONFIG, d_model=640, n_layers=30, n_heads=20, d_
 ESM2_T48_CONFIG = dict(ESM2_T33_CONFIG, d_model=5120, n_layers=48, n_heads=40, d_ffn=20480)
 # esm2_t6_8M_UR50D -- models.ESM2_8M: 6 layers of 20 heads of 16
 ESM2_T6_CONFIG = dict(ESM2_T33_CONFIG, d_model=320, n_layers=6, n_heads=20, d_ffn=1280)
-HEAD_DIMS = (64, 32, 128, 16)  # head widths the attention kernels are built for; 32, 128 and 16 run for ESM-2 only (csrc/attn_frag.h)
-MAX_HEADS_OF_32 = 32         # the rotary kernel's row of heads of 32 (csrc/rope.hip)
-MAX_HEADS_OF_16 = 32         # the rotary kernel's row of heads of 16: d_model <= 512 (csrc/rope.hip)
-MAX_D_MODEL = 2560           # heads of 64 / 32: the row kernels hold at most kMaxChWide * 256 features (csrc/ln_row.h)
-MAX_HEADS_OF_128 = 40        # heads of 128: at most 40 of them, d_model <= 5120 (kMaxCh5k * 256), in 512-feature units above 2560
-MAX_D_MODEL_HD128 = 128 * MAX_HEADS_OF_128
+# The head widths the attention and rotary kernels are built for, row for row the table of csrc/head_width.h (tests/test_head_widths_cpu.py
+# holds the two together): at most max_heads heads per row, for ESM-2 only or every architecture, q scaled by q_scale = width^-0.5 as
+# float32; then the released model that needs the width at its widest -- its configuration, file, wrapper (models.*) and --model name
+HEAD_WIDTHS = {
+    64: dict(max_heads=40, esm2_only=False, q_scale=0.125, config=ESM2_T36_CONFIG, file="esm2_t36_3B_UR50D", wrapper="ESM2_3B", cli="esm2_3b"),
+    32: dict(max_heads=32, esm2_only=True, q_scale=0.17677669529663687, config=ESM2_T30_CONFIG, file="esm2_t30_150M_UR50D", wrapper="ESM2_150M",
+             cli="esm2_150m"),
+    128: dict(max_heads=40, esm2_only=True, q_scale=0.08838834764831845, config=ESM2_T48_CONFIG, file="esm2_t48_15B_UR50D", wrapper="ESM2_15B",
+              cli="esm2_15b"),
+    16: dict(max_heads=32, esm2_only=True, q_scale=0.25, config=ESM2_T6_CONFIG, file="esm2_t6_8M_UR50D", wrapper="ESM2_8M", cli="esm2_8m"),
+}
+HEAD_DIMS = tuple(HEAD_WIDTHS)
+MAX_HEADS_OF_32 = HEAD_WIDTHS[32]["max_heads"]
+MAX_HEADS_OF_16 = HEAD_WIDTHS[16]["max_heads"]
+MAX_HEADS_OF_128 = HEAD_WIDTHS[128]["max_heads"]
+MAX_D_MODEL = 64 * HEAD_WIDTHS[64]["max_heads"]  # the row kernels hold at most kMaxChWide * 256 = 2560 features (csrc/ln_row.h) ...
+MAX_D_MODEL_HD128 = 128 * MAX_HEADS_OF_128       # ... or, above them, whole 512-feature units up to kMaxCh5k * 256 = 5120: heads of 128
 ESM2_650M_MAX_D_MODEL = 2048  # a wider file handed to a config of at most this width (models.ESM2) is refused: see below
 
 
@@ -378,41 +389,24 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
         if bad:
             raise ValueError("config= disagrees with the checkpoint's own hyper-parameters: %s (given, in the file)" % bad)
     cfg.update(take)
-    # Head width.  64 loads against every base configuration; 32 only against one whose own heads are 32 (ESM2_T30_CONFIG:
-    # models.ESM2_150M) and 128 only against one whose own heads are 128 (ESM2_T48_CONFIG: models.ESM2_15B) -- a wrapper promises its
-    # model, as ESM2 refuses the 3B file below --, 16 only against one whose own heads are 16 (ESM2_T6_CONFIG: models.ESM2_8M); 24
-    # loads nowhere.
+    # Head width (HEAD_WIDTHS).  64 loads against every base configuration; a width built for ESM-2 only loads against a configuration
+    # whose own heads have that width (32: ESM2_T30_CONFIG, models.ESM2_150M, and so on) -- a wrapper promises its model, as ESM2 refuses
+    # the 3B file below; 24 loads nowhere.  Then the engine's own order: heads per row, row width (csrc/engine.hip, csrc/ln_row.h).
     hd = cfg["d_model"] / max(1, cfg["n_heads"])
-    if hd == 32 and head_dim_of(base_cfg) != 32:
-        raise ValueError("checkpoint has %d heads of dimension 32: the engine's attention kernels implement head dimension 64 for the "
-                         "configuration it was loaded against; load esm2_t30_150M_UR50D (heads of 32) with models.ESM2_150M / "
-                         "--model esm2_150m" % cfg["n_heads"])
-    if hd == 32 and cfg["n_heads"] > MAX_HEADS_OF_32:
-        raise ValueError("checkpoint has %d heads of dimension 32: the engine's rotary kernel holds at most %d of them (d_model <= %d; "
-                         "esm2_t30_150M_UR50D has 20)" % (cfg["n_heads"], MAX_HEADS_OF_32, 32 * MAX_HEADS_OF_32))
-    if hd == 128 and head_dim_of(base_cfg) != 128:
-        raise ValueError("checkpoint has %d heads of dimension 128: the engine's attention kernels implement head dimension 64 "
-                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D) for the configuration it was loaded "
-                         "against; load esm2_t48_15B_UR50D (heads of 128) with models.ESM2_15B / --model esm2_15b" % cfg["n_heads"])
-    if hd == 128 and (cfg["n_heads"] > MAX_HEADS_OF_128 or (cfg["d_model"] > MAX_D_MODEL and cfg["d_model"] % 512)):
-        raise ValueError("checkpoint has %d heads of dimension 128: the engine's rotary and row kernels hold at most %d of them "
-                         "(d_model <= %d, in multiples of 512 above %d; esm2_t48_15B_UR50D has 40)"
-                         % (cfg["n_heads"], MAX_HEADS_OF_128, MAX_D_MODEL_HD128, MAX_D_MODEL))
-    if hd == 16 and head_dim_of(base_cfg) != 16:
-        raise ValueError("checkpoint has %d heads of dimension 16: the engine's attention kernels implement head dimension 64 "
-                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D) and 128 (esm2_t48_15B_UR50D) for the "
-                         "configuration it was loaded against; load esm2_t6_8M_UR50D (heads of 16) with models.ESM2_8M / "
-                         "--model esm2_8m" % cfg["n_heads"])
-    if hd == 16 and cfg["n_heads"] > MAX_HEADS_OF_16:
-        raise ValueError("checkpoint has %d heads of dimension 16: the engine's rotary kernel holds at most %d of them (d_model <= %d; "
-                         "esm2_t6_8M_UR50D has 20)" % (cfg["n_heads"], MAX_HEADS_OF_16, 16 * MAX_HEADS_OF_16))
-    if hd not in HEAD_DIMS:
-        raise ValueError("checkpoint has %d heads of dimension %g: the engine's attention kernels implement head dimension 64 "
-                         "(every model of pgen.models) and, for ESM-2, 32 (esm2_t30_150M_UR50D), 128 (esm2_t48_15B_UR50D) and 16 "
-                         "(esm2_t6_8M_UR50D)" % (cfg["n_heads"], hd))
-    if hd != 128 and cfg["d_model"] > MAX_D_MODEL:
-        raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head, rotation) hold at "
-                         "most %d features per row, 40 heads of 64 (esm2_t36_3B_UR50D)" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL))
+    has = "checkpoint has %d heads of dimension %g: " % (cfg["n_heads"], hd)
+    row = HEAD_WIDTHS.get(hd)
+    if row is None:
+        raise ValueError(has + "the engine's attention kernels implement head dimension 64 (every model of pgen.models) and, for ESM-2, "
+                         + ", ".join("%d (%s)" % (w, r["file"]) for w, r in HEAD_WIDTHS.items() if r["esm2_only"]))
+    if row["esm2_only"] and head_dim_of(base_cfg) != hd:
+        raise ValueError(has + "the engine's attention kernels implement head dimension 64 for the configuration it was loaded against; "
+                         "load %s (heads of %g) with models.%s / --model %s" % (row["file"], hd, row["wrapper"], row["cli"]))
+    if cfg["n_heads"] > row["max_heads"]:
+        raise ValueError(has + "the engine's rotary and row kernels hold at most %d of them per row (d_model %d > %d; %s has %d)"
+                         % (row["max_heads"], cfg["d_model"], hd * row["max_heads"], row["file"], row["config"]["n_heads"]))
+    if cfg["d_model"] > MAX_D_MODEL and cfg["d_model"] % 512:
+        raise ValueError("checkpoint has d_model %d > %d: the engine's row kernels (LayerNorm, embedding, LM head, rotation) take "
+                         "multiples of 512 up to %d there" % (cfg["d_model"], MAX_D_MODEL, MAX_D_MODEL_HD128))
     # models.ESM2 / --model esm2 promise the 650M model: a 3B file is 4.4 times the work and is loaded on purpose, not by accident
     if cfg["d_model"] > ESM2_650M_MAX_D_MODEL and base_cfg["d_model"] <= ESM2_650M_MAX_D_MODEL:
         raise ValueError("checkpoint has d_model %d > %d, wider than the ESM-2 650M configuration it was loaded against: load "

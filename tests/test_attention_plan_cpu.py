@@ -129,12 +129,12 @@ ROWS = [
     (row(2, 8, 64, precision=FP32, pad=1), "row-split-f32 kb4 kt1 24wg, 192wg"),
 ]
 REFUSED = [
-    (att(2, 100, hd=48), "error: attention: head dimension 48: the kernels are built for 64 and 32"),
+    (att(2, 100, hd=48), "error: attention: head dimension 48: the kernels are built for 64 (every architecture) or 32, 128, 16 (ESM-2 only)"),
     (att(2, 100, hd=32, bias=1), "error: attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only"),
     (att(2, 0), "error: attention: empty sequence"),
     (att(200000000, 27), "error: attention: too many sequences"),
     (att(100000000, 600), "error: attention: too many sequences"),      # the long kernel's grid: pairs x ten query chunks
-    (strict(2, 100, hd=48), "error: attention: head dimension 48: the kernels are built for 64 and 32"),
+    (strict(2, 100, hd=48), "error: attention: head dimension 48: the kernels are built for 64 (every architecture) or 32, 128, 16 (ESM-2 only)"),
     (strict(2, 100, hd=32, bias=1), "error: attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only"),
     (strict(2, 0), "error: attention: empty sequence"),
     (strict(200000000, 27), "error: attention: too many sequences"),

@@ -148,7 +148,7 @@ PLANS = [
                                                                       # query blocks allow two parts of at least one block per wave
     (a128(4, 100), "whole kb8 hd128 160wg"),                          # seven query blocks: too few to split
     (a128(2, 258, bias=1), "error: attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only"),
-    (att(2, 258, hd=48), "error: attention: head dimension 48: the kernels are built for 64 and 32"),
+    (att(2, 258, hd=48), "error: attention: head dimension 48: the kernels are built for 64 (every architecture) or 32, 128, 16 (ESM-2 only)"),
     (strict(2, 27, H=40, hd=128), "split-f32 kb4 nqb1 hd128 80wg"),
     (strict(2, 100, H=40, hd=128), "split-f32 kb4 nqb2 hd128 80wg"),
     (strict(2, 258, H=40, hd=128), "split-f32 kb4 nqb3 hd128 160wg"),  # never five query blocks per wave at 128

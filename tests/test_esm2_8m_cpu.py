@@ -171,8 +171,8 @@ PLANS = [
     (a16(3, 258, pad=1), "whole kb18 hd16 pad 60wg"),
     (a16(3, 600, pad=1), "long t288 hd16 pad 600wg"),
     (a16(2, 258, bias=1), "error: attention: the bias_k / bias_v key (ESM-1) is built for heads of 64 only"),
-    (att(2, 258, hd=24), "error: attention: head dimension 24: the kernels are built for 64 and 32"),
-    (att(2, 258, hd=48), "error: attention: head dimension 48: the kernels are built for 64 and 32"),
+    (att(2, 258, hd=24), "error: attention: head dimension 24: the kernels are built for 64 (every architecture) or 32, 128, 16 (ESM-2 only)"),
+    (att(2, 258, hd=48), "error: attention: head dimension 48: the kernels are built for 64 (every architecture) or 32, 128, 16 (ESM-2 only)"),
     (strict(2, 27, hd=16), "split-f32 kb4 nqb1 hd16 40wg"),
     (strict(2, 258, hd=16), "split-f32 kb6 nqb5 hd16 40wg"),
     (strict(2, 100, hd=16, pad=1), "split-f32 kb10 nqb2 hd16 pad 40wg"),

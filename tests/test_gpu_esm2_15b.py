@@ -3,45 +3,30 @@ alone (pg_dbg_attention_kv: the whole-sequence ladder up to 288 keys, 128-key ti
 element under the bounds of tests/_attention_reference.py, the head-128 rotation (pg_dbg_rope_hd) against the separately rounded
 numpy loop, the 20-chunk row kernels (LayerNorm, embedding, gather, LM tail) at d = 3072 .. 5120, the engine forward of one full-width
 layer and of a HuggingFace fixture, the sampler on a small deep model, and the refusals."""
-import ctypes
-import hashlib
 import json
 import os
 import random
-import subprocess
-import sys
 import warnings
 
 import numpy as np
 import pytest
 
+import _esm2_gpu_common as common
 import _attention_reference as ar
 import _esm2_reference_hd as ref
 import _row_reference as rr
 import test_gpu_attention_kernels as ak
 import test_gpu_gemm_kernels as gm
 import test_gpu_row_kernels as rk
+from _esm2_gpu_common import PREC, SEED25, replay_draws as _replay_draws, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
 from _ln_host import PLAIN, SPLIT_DUP, _ln_inplace_host
-from oracle import draw as odraw
 from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 F32 = np.float32
 HD = 128
-SEED25 = "MEPAATGQEAEECAHSGRGEAWEEV"
-PREC = {"fp32": _lib.PG_PREC_FP32, "bf16": _lib.PG_PREC_BF16, "fp16": _lib.PG_PREC_F16}
-
-
-def _round_bf16(x):
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    return ((u + (((u >> 16) & 1) + np.uint32(0x7fff))) & np.uint32(0xffff0000)).view(np.float32)
-
-
-def _round_f16(x):
-    return np.asarray(x, dtype=np.float32).astype(np.float16).astype(np.float32)
 
 
 # ---- the attention kernels ----------------------------------------------------------------------------------------------------------
@@ -167,6 +152,33 @@ def test_rope_kernel_at_heads_of_128(T, H):
         x16 = rnd(x)
         want = rnd(_rotate_rows_strict(x16, B, T, H))
         assert np.array_equal(got[:, d2:], x16[:, d2:])                          # v: the input's 16-bit value, untouched
+        ulp16 = np.spacing(np.maximum(np.abs(want[:, :d2]), np.float32(2.0 ** -14))) * np.float32(2.0 ** (23 - mant))
+        assert (np.abs(got[:, :d2] - want[:, :d2]) <= ulp16).all()
+
+
+@pytest.mark.parametrize("hd, H", [(64, 32), (64, 33), (128, 20), (128, 21)])
+def test_rope_at_the_narrow_wide_boundary(hd, H):
+    """The rotary launcher's two instantiations per width (csrc/head_width.h: rope_narrow heads, then max_heads) on both sides of the
+    threshold: the last head count the narrow kernel takes and the first one of the wide kernel -- a threshold one too high would
+    leave the last heads of the row unrotated."""
+    B, T = 2, 27
+    rng = np.random.default_rng(hd * 31 + H)
+    x = (rng.standard_normal((B * T, 3 * H * hd)) * 2.0).astype(np.float32)
+    L = _lib.lib()
+    d2 = 2 * H * hd
+    got = x.copy()
+    _lib.check(L.pg_dbg_rope_hd(0, _lib.PG_PREC_FP32, _lib.ptr(got), B, T, H, hd))
+    want = ref.rotate_qkv_rows(x, B, T, H, hd)
+    print("\n[rope %d heads of %d, fp32] %d of %d values differ from the numpy loop" % (H, hd, int((got != want).sum()), got.size))
+    assert np.array_equal(got, want)                                            # strict mode: the host fp32 loop, bit for bit (v included)
+    assert np.array_equal(got[:, d2:], x[:, d2:]) and np.array_equal(got[0, :d2], x[0, :d2])
+    assert not np.array_equal(got[1, d2 - hd:d2], x[1, d2 - hd:d2])             # the last head of k is rotated
+    for prec, rnd, mant in ((_lib.PG_PREC_BF16, _round_bf16, 7), (_lib.PG_PREC_F16, _round_f16, 10)):
+        got = x.copy()
+        _lib.check(L.pg_dbg_rope_hd(0, prec, _lib.ptr(got), B, T, H, hd))
+        x16 = rnd(x)
+        want = rnd(ref.rotate_qkv_rows(x16, B, T, H, hd))
+        assert np.array_equal(got[:, d2:], x16[:, d2:])
         ulp16 = np.spacing(np.maximum(np.abs(want[:, :d2]), np.float32(2.0 ** -14))) * np.float32(2.0 ** (23 - mant))
         assert (np.abs(got[:, :d2] - want[:, :d2]) <= ulp16).all()
 
@@ -370,8 +382,6 @@ def _sample(M, N):
     rows = np.unique(np.concatenate([np.arange(0, M, 37), np.arange(max(0, M - 70), M)]))
     cols = np.unique(np.concatenate([np.arange(0, N, 53), np.arange(N - 70, N)]))
     return rows, cols
-
-
 @pytest.mark.parametrize("M", [32, 258, 8256])
 @pytest.mark.parametrize("N,K,epi,fmts", [(20480, 5120, 4, ("bf16", "f16")), (20480, 5120, 5, ("f32",)), (5120, 5120, 1, ("bf16", "f16"))])
 def test_gemm_gelu_epilogues_at_15b_shapes(M, N, K, epi, fmts):
@@ -432,15 +442,7 @@ def test_fc2_split_k_at_15b_depth(M):
 
 # ---- forward: one layer at the full width ------------------------------------------------------------------------------------------------
 def _model(cfg, sd, precision):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return models.ESM2_15B(state_dict=sd, config=cfg, precision=precision)
-
-
-def _tokens(rng, B, T, mask_every=7):
-    tok = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, T - 2)), np.full((B, 1), 2)], axis=1)
-    tok[:, 2:T - 1:mask_every] = 32
-    return tok
+    return common.model(models.ESM2_15B, cfg, sd, precision)
 
 
 _WIDE = {}
@@ -510,15 +512,6 @@ def _case(n_layers=4, d=256, seed=7, **over):
     return cfg, sd, ref.Esm2Config.of(cfg)
 
 
-def _replay_draws(s, run, B, P, iters, top_k, burnin, temperature, draw_seed):
-    for it in range(iters):
-        rows = run["sampled_logits"][it].reshape(-1, 33)
-        assert np.isfinite(rows).all()
-        toks = odraw.draw_rows(rows, s.valid_aa_idx, top_k, it < burnin, temperature, np.repeat(np.arange(B), P), it,
-                               np.tile(np.arange(P), B), 0, draw_seed)
-        assert (toks == run["sampled_tokens"][it].reshape(-1)).all(), "draw differs from the oracle"
-
-
 def test_esm2_hd128_sampler_positions_draws_and_likelihoods():
     cfg, sd, rcfg = _case()
     s = esm_sampler.ESM_sampler(_model(cfg, sd, "fp32"), device="cuda:0")
@@ -569,80 +562,27 @@ def test_esm2_hd128_auto_precision_and_small_job_independence():
 
 
 def _single_chain_run():
-    """One chain of 25 residues (27 token rows: weight-streaming GEMMs), 12 iterations, not recorded: the hipGraph path when on."""
     cfg, sd, _ = _case(n_layers=3, seed=13)
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "bf16"), device="cuda:0")
-    s.draw_seed, s.record = 21, False
-    random.seed(4)
-    out = s.generate(1, SEED25, batch_size=1, num_iters=12, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
-    return s, out
+    return common.single_chain_run(_model(cfg, sd, "bf16"))
 
 
 def _single_chain_child():
-    _, out = _single_chain_run()
-    print("CHILD_TOKENS " + json.dumps(out))
+    common.single_chain_child(_single_chain_run)
 
 
 def _child(call, **env):
-    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_esm2_15b as t; t.%s()" % (ROOT, HERE, call)
-    child = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0, child.stderr[-2000:]
-    return child.stdout.splitlines()
+    return common.child("test_gpu_esm2_15b", call, **env)
 
 
 def test_esm2_hd128_single_chain_replays_a_graph_and_equals_the_eager_loop():
-    s, out = _single_chain_run()
-    lm = s.model.model
-    assert lm.get_stat("graph_captures") == 1 and lm.get_stat("graph_replays") > 0
-    line = [l for l in _child("_single_chain_child", PGIBBS_GRAPH="0") if l.startswith("CHILD_TOKENS ")][-1]
-    assert json.loads(line[len("CHILD_TOKENS "):]) == out
-    s.draw_seed, s.record = 21, True
-    random.seed(4)
-    again = s.generate(1, SEED25, batch_size=1, num_iters=12, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
-    assert again == out
-    _replay_draws(s, s.last_run[0], 1, 3, 12, 0, float("inf"), 1.0, 21)
+    common.check_single_chain(_single_chain_run, "test_gpu_esm2_15b")
 
 
 def test_esm2_hd128_shards_reproduce_the_whole_job():
     """A 64-chain job of config 2's chain length (18 key blocks: one workgroup per CU), whole and as 2, 4 and 8 contiguous shards that
     know the job's size: tokens and sampled-position logits bit for bit."""
-    import torch
-
-    from protein_gibbs_sampler_amd import pyrandom, sharding
     cfg, sd, _ = _case(n_layers=3)
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "bf16"), device="cuda:0")
-    lm = s.model.model
-    B, L, P, iters = 64, 256, 5, 2
-    T = L + 2
-    rng = np.random.default_rng(1234)
-    tok_all = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, L)), np.full((B, 1), 2)], axis=1).astype(np.int32)
-    L_ = _lib.lib()
-
-    def run(lo, hi):
-        r = pyrandom.NativePyRandom()
-        r.seed(0)
-        table = sharding.local_slice(sharding.global_position_table(r, list(range(1, L + 1)), P, iters, B), lo, hi)
-        params = _lib.make_sample_params(True, 32, 0, float("inf"), 1.0, s.valid_aa_idx, rng_seed=0, row_id_base=lo)
-        d_tok = torch.from_numpy(tok_all[lo:hi].copy()).cuda()
-        d_idx = torch.from_numpy(table).cuda()
-        d_lg = torch.empty((iters, hi - lo, P, 33), dtype=torch.float32, device="cuda")
-        lm.set_job_items(B)
-        try:
-            _lib.check(L_.pg_esm_gibbs_run_device(lm.handle, ctypes.c_void_p(d_tok.data_ptr()), hi - lo, T,
-                                                  ctypes.c_void_p(d_idx.data_ptr()), iters, P, ctypes.byref(params),
-                                                  ctypes.c_void_p(d_lg.data_ptr()), None))
-            lm.synchronize()
-        finally:
-            lm.set_job_items(0)
-        return d_tok.cpu().numpy(), d_lg.cpu().numpy()
-
-    whole, whole_lg = run(0, B)
-    assert (whole != tok_all).any() and np.isfinite(whole_lg).all()
-    for world in (2, 4, 8):
-        parts = [run(*sharding.shard_range(B, world, g)) for g in range(world)]
-        assert (np.concatenate([p[1] for p in parts], axis=1) == whole_lg).all(), "world=%d: sampled-position logits differ" % world
-        assert (np.concatenate([p[0] for p in parts]) == whole).all(), "world=%d" % world
-    assert hashlib.sha256(whole.tobytes()).hexdigest()
+    assert common.shard_job(_model(cfg, sd, "bf16"), (2, 4, 8))
 
 
 # ---- activation buffers past 2^31 bytes ------------------------------------------------------------------------------------------------
@@ -653,39 +593,16 @@ def test_config2_call_with_buffers_over_2_gib_equals_its_shards(precision):
     a 32-bit row offset in any kernel would show.  Each 32-chain shard keeps every buffer under 2^31 bytes (0.34 GB; strict 1.0 GB), the
     sizes every other test runs, and under set_job_items the kernels are row-invariant: the whole job must give the shards' tokens
     and sampled logits bit for bit.  (Two layers: the last one is pruned to the sampled rows and would never fill the buffer.)"""
-    import torch
-
-    from protein_gibbs_sampler_amd import pyrandom, sharding
+    from protein_gibbs_sampler_amd import sharding
     cfg = weights.make_config(weights.ESM2_T48_CONFIG, n_layers=2)
     assert (cfg["d_model"], cfg["d_ffn"], cfg["n_heads"]) == (5120, 20480, 40)
     if "sd" not in _BIG:
         _BIG["sd"] = weights.synthetic_state_dict(cfg, seed=3, std=0.012, embed_std=0.1, ln_jitter=0.1)
     s = esm_sampler.ESM_sampler(_model(cfg, _BIG["sd"], precision), device="cuda:0")
-    lm = s.model.model
     B, L, P, iters = 256, 256, 5, 1
-    T = L + 2
-    assert B * T * cfg["d_ffn"] * 2 > 2 ** 31
-    rng = np.random.default_rng(4321)
-    tok_all = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, L)), np.full((B, 1), 2)], axis=1).astype(np.int32)
-    L_ = _lib.lib()
-
-    def run(lo, hi):
-        r = pyrandom.NativePyRandom()
-        r.seed(0)
-        table = sharding.local_slice(sharding.global_position_table(r, list(range(1, L + 1)), P, iters, B), lo, hi)
-        params = _lib.make_sample_params(True, 32, 0, float("inf"), 1.0, s.valid_aa_idx, rng_seed=0, row_id_base=lo)
-        d_tok = torch.from_numpy(tok_all[lo:hi].copy()).cuda()
-        d_idx = torch.from_numpy(table).cuda()
-        d_lg = torch.empty((iters, hi - lo, P, 33), dtype=torch.float32, device="cuda")
-        lm.set_job_items(B)
-        try:
-            _lib.check(L_.pg_esm_gibbs_run_device(lm.handle, ctypes.c_void_p(d_tok.data_ptr()), hi - lo, T,
-                                                  ctypes.c_void_p(d_idx.data_ptr()), iters, P, ctypes.byref(params),
-                                                  ctypes.c_void_p(d_lg.data_ptr()), None))
-            lm.synchronize()
-        finally:
-            lm.set_job_items(0)
-        return d_tok.cpu().numpy(), d_lg.cpu().numpy()
+    assert B * (L + 2) * cfg["d_ffn"] * 2 > 2 ** 31
+    tok_all = common.shard_tokens(B, L, seed=4321)
+    run = common.shard_runner(s, tok_all, P, iters)
 
     parts = [run(*sharding.shard_range(B, 8, g)) for g in range(8)]           # the shards first: the sizes that are known ground
     whole, whole_lg = run(0, B)
@@ -724,11 +641,4 @@ def test_strict_valu_switch_refuses_heads_of_128_by_name():
 
 
 def _refuse_valu_child():
-    x = np.zeros((1, 16, 3 * 2 * HD), np.float32)
-    y = np.zeros((1, 16, 2 * HD), np.float32)
-    rc = _lib.lib().pg_dbg_attention_hd(0, _lib.PG_PREC_FP32, _lib.ptr(x), _lib.ptr(y), 1, 16, 2, HD, None, -1)
-    assert rc != 0
-    try:
-        _lib.check(rc)
-    except Exception as e:      # noqa: BLE001
-        print("CHILD_REFUSED " + str(e))
+    common.refuse_valu_child(HD)

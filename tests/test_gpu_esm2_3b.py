@@ -2,36 +2,22 @@
 its four forms at d = 2560 and 2304, the rotation at H = 40) against numpy, the 8-chunk LayerNorm at d = 1280 bit for bit against a
 host loop in the kernel's operation order (up to the hardware square root), the GEMM dispatcher at the 3B shapes, the forward of a 3-layer cut and once at full size
 against the fp32 reference (tests/_esm2_reference.py), and the sampler on the models.ESM2_3B holder."""
-import ctypes
 import json
-import os
 import random
-import subprocess
-import sys
 import warnings
 
 import numpy as np
 import pytest
 
+import _esm2_gpu_common as common
 import _esm2_reference as ref
+from _esm2_gpu_common import SEED25, replay_draws as _replay_draws, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
 from _ln_host import _fma32, _ln_inplace_host, _wave_sum  # noqa: F401  (the host restatement of csrc/ln_row.h)
-from oracle import draw as odraw
 from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 F32 = np.float32
-
-
-def _round_bf16(x):
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    return ((u + (((u >> 16) & 1) + np.uint32(0x7fff))) & np.uint32(0xffff0000)).view(np.float32)
-
-
-def _round_f16(x):
-    return np.asarray(x, dtype=np.float32).astype(np.float16).astype(np.float32)
 
 
 # ---- LayerNorm: the 10-chunk row kernels ------------------------------------------------------------------------------------------
@@ -223,15 +209,7 @@ def _cached_case(**kw):
 
 
 def _model(cfg, sd, precision):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return models.ESM2_3B(state_dict=sd, config=cfg, precision=precision)
-
-
-def _tokens(rng, B, T, mask_every=7):
-    tok = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, T - 2)), np.full((B, 1), 2)], axis=1)
-    tok[:, 2:T - 1:mask_every] = 32
-    return tok
+    return common.model(models.ESM2_3B, cfg, sd, precision)
 
 
 def test_engine_refuses_wider_models_by_name():
@@ -354,16 +332,6 @@ def test_esm2_3b_full_size_strict_logits():
 
 
 # ---- the sampler --------------------------------------------------------------------------------------------------------------------
-SEED25 = "MEPAATGQEAEECAHSGRGEAWEEV"
-
-
-def _replay_draws(s, run, B, P, iters, top_k, burnin, temperature, draw_seed):
-    for it in range(iters):
-        rows = run["sampled_logits"][it].reshape(-1, 33)
-        assert np.isfinite(rows).all()
-        toks = odraw.draw_rows(rows, s.valid_aa_idx, top_k, it < burnin, temperature, np.repeat(np.arange(B), P), it,
-                               np.tile(np.arange(P), B), 0, draw_seed)
-        assert (toks == run["sampled_tokens"][it].reshape(-1)).all(), "draw differs from the oracle"
 
 
 def test_esm2_3b_sampler_positions_draws_and_likelihoods():
@@ -408,74 +376,20 @@ def test_models_esm2_3b_synthetic_holder():
 
 
 def _single_chain_run():
-    """One chain of 25 residues (27 token rows), 12 iterations, not recorded: the hipGraph path when on."""
     cfg, sd, _ = _case(seed=13)
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "bf16"), device="cuda:0")
-    s.draw_seed, s.record = 21, False
-    random.seed(4)
-    out = s.generate(1, SEED25, batch_size=1, num_iters=12, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
-    return s, out
+    return common.single_chain_run(_model(cfg, sd, "bf16"))
 
 
 def _single_chain_child():
-    _, out = _single_chain_run()
-    print("CHILD_TOKENS " + json.dumps(out))
+    common.single_chain_child(_single_chain_run)
 
 
 def test_esm2_3b_single_chain_replays_a_graph_and_equals_the_eager_loop():
-    s, out = _single_chain_run()
-    lm = s.model.model
-    assert lm.get_stat("graph_captures") == 1 and lm.get_stat("graph_replays") > 0
-    # the same job in a fresh child process with graphs off (PGIBBS_GRAPH is read once per process)
-    env = dict(os.environ, PGIBBS_GRAPH="0")
-    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_esm2_3b as t; t._single_chain_child()" % (ROOT, HERE)
-    child = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert child.returncode == 0, child.stderr[-2000:]
-    line = [l for l in child.stdout.splitlines() if l.startswith("CHILD_TOKENS ")][-1]
-    assert json.loads(line[len("CHILD_TOKENS "):]) == out
-    s.draw_seed, s.record = 21, True
-    random.seed(4)
-    again = s.generate(1, SEED25, batch_size=1, num_iters=12, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
-    assert again == out
-    _replay_draws(s, s.last_run[0], 1, 3, 12, 0, float("inf"), 1.0, 21)
+    common.check_single_chain(_single_chain_run, "test_gpu_esm2_3b", timeout=600)
 
 
 def test_esm2_3b_shards_reproduce_the_whole_job():
     """A 32-chain job of config 2's chain length (8256 token rows) run whole and as 2 and 4 contiguous shards that know the job's
     size (pg_engine_set_job_items): tokens and the logits of every draw, bit for bit."""
-    import torch
-
-    from protein_gibbs_sampler_amd import pyrandom, sharding
     cfg, sd, _ = _cached_case()
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "bf16"), device="cuda:0")
-    lm = s.model.model
-    B, L, P, iters = 32, 256, 5, 2
-    T = L + 2
-    rng = np.random.default_rng(1234)
-    tok_all = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, L)), np.full((B, 1), 2)], axis=1).astype(np.int32)
-    L_ = _lib.lib()
-
-    def run(lo, hi):
-        r = pyrandom.NativePyRandom()
-        r.seed(0)
-        table = sharding.local_slice(sharding.global_position_table(r, list(range(1, L + 1)), P, iters, B), lo, hi)
-        params = _lib.make_sample_params(True, 32, 0, float("inf"), 1.0, s.valid_aa_idx, rng_seed=0, row_id_base=lo)
-        d_tok = torch.from_numpy(tok_all[lo:hi].copy()).cuda()
-        d_idx = torch.from_numpy(table).cuda()
-        d_lg = torch.empty((iters, hi - lo, P, 33), dtype=torch.float32, device="cuda")
-        lm.set_job_items(B)
-        try:
-            _lib.check(L_.pg_esm_gibbs_run_device(lm.handle, ctypes.c_void_p(d_tok.data_ptr()), hi - lo, T,
-                                                  ctypes.c_void_p(d_idx.data_ptr()), iters, P, ctypes.byref(params),
-                                                  ctypes.c_void_p(d_lg.data_ptr()), None))
-            lm.synchronize()
-        finally:
-            lm.set_job_items(0)
-        return d_tok.cpu().numpy(), d_lg.cpu().numpy()
-
-    whole, whole_lg = run(0, B)
-    assert (whole != tok_all).any() and np.isfinite(whole_lg).all()
-    for world in (2, 4):
-        parts = [run(*sharding.shard_range(B, world, g)) for g in range(world)]
-        assert (np.concatenate([p[1] for p in parts], axis=1) == whole_lg).all(), "world=%d: sampled-position logits differ" % world
-        assert (np.concatenate([p[0] for p in parts]) == whole).all(), "world=%d" % world
+    common.shard_job(_model(cfg, sd, "bf16"), (2, 4), B=32)

@@ -3,30 +3,25 @@
 (pg_dbg_rope_hd) against numpy, the row kernels at d = 320, the engine forward against the numpy reference and a HuggingFace fixture
 (the 6 x 320 model IS the full-size model), which GEMM kernels a forward takes, the sampler (positions, draws, likelihoods,
 substitution tables, hipGraph replay, shards), and the refusals of heads of 16 elsewhere."""
-import ctypes
-import hashlib
 import json
 import os
 import random
-import subprocess
-import sys
 import warnings
 
 import numpy as np
 import pytest
 
+import _esm2_gpu_common as common
 import _esm2_reference_hd as ref
 import _row_reference as rr
 import test_gpu_row_kernels as rk
+from _esm2_gpu_common import PREC, SEED25, replay_draws as _replay_draws, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
 from _ln_host import PLAIN, _ln_inplace_host
-from oracle import draw as odraw
 from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SEED25 = "MEPAATGQEAEECAHSGRGEAWEEV"
 HD = 16
 F32 = np.float32
 
@@ -39,27 +34,7 @@ def _case(n_layers=6, d=320, seed=7, **over):
 
 
 def _model(cfg, sd, precision):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return models.ESM2_8M(state_dict=sd, config=cfg, precision=precision)
-
-
-def _tokens(rng, B, T, mask_every=7):
-    tok = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, T - 2)), np.full((B, 1), 2)], axis=1)
-    tok[:, 2:T - 1:mask_every] = 32
-    return tok
-
-
-def _round_bf16(x):
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    return ((u + (((u >> 16) & 1) + np.uint32(0x7fff))) & np.uint32(0xffff0000)).view(np.float32)
-
-
-def _round_f16(x):
-    return np.asarray(x, dtype=np.float32).astype(np.float16).astype(np.float32)
-
-
-PREC = {"fp32": _lib.PG_PREC_FP32, "bf16": _lib.PG_PREC_BF16, "fp16": _lib.PG_PREC_F16}
+    return common.model(models.ESM2_8M, cfg, sd, precision)
 
 
 # ---- the attention kernels ----------------------------------------------------------------------------------------------------------
@@ -211,8 +186,6 @@ def test_lm_tail_at_320(n):
 # ---- forward ------------------------------------------------------------------------------------------------------------------------
 # max |engine - reference| per unit of logit std: the 650M / 150M tests' bounds
 FWD_TOL = {"fp32": None, "bf16": 0.05, "fp16": 0.008}
-
-
 @pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
 def test_esm2_8m_forward_against_the_reference(precision):
     """esm2_t6_8M_UR50D's own shape: 6 layers x 320, 20 heads of 16."""
@@ -321,15 +294,6 @@ def test_engine_refuses_33_heads_of_16_and_heads_of_24():
 
 
 # ---- the sampler --------------------------------------------------------------------------------------------------------------------
-def _replay_draws(s, run, B, P, iters, top_k, burnin, temperature, draw_seed):
-    for it in range(iters):
-        rows = run["sampled_logits"][it].reshape(-1, 33)
-        assert np.isfinite(rows).all()
-        toks = odraw.draw_rows(rows, s.valid_aa_idx, top_k, it < burnin, temperature, np.repeat(np.arange(B), P), it,
-                               np.tile(np.arange(P), B), 0, draw_seed)
-        assert (toks == run["sampled_tokens"][it].reshape(-1)).all(), "draw differs from the oracle"
-
-
 def test_esm2_8m_sampler_positions_draws_and_likelihoods():
     cfg, sd, rcfg = _case(n_layers=4)
     s = esm_sampler.ESM_sampler(_model(cfg, sd, "fp32"), device="cuda:0")
@@ -367,80 +331,27 @@ def test_esm2_8m_sampler_positions_draws_and_likelihoods():
 
 
 def _single_chain_run():
-    """One chain of 25 residues (27 token rows: weight-streaming GEMMs), 12 iterations, not recorded: the hipGraph path when on."""
     cfg, sd, _ = _case(n_layers=3, seed=13)
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "bf16"), device="cuda:0")
-    s.draw_seed, s.record = 21, False
-    random.seed(4)
-    out = s.generate(1, SEED25, batch_size=1, num_iters=12, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
-    return s, out
+    return common.single_chain_run(_model(cfg, sd, "bf16"))
 
 
 def _single_chain_child():
-    _, out = _single_chain_run()
-    print("CHILD_TOKENS " + json.dumps(out))
+    common.single_chain_child(_single_chain_run)
 
 
 def _child(call, **env):
-    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_esm2_8m as t; t.%s()" % (ROOT, HERE, call)
-    child = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert child.returncode == 0, child.stderr[-2000:]
-    return child.stdout.splitlines()
+    return common.child("test_gpu_esm2_8m", call, **env)
 
 
 def test_esm2_8m_single_chain_replays_a_graph_and_equals_the_eager_loop():
-    s, out = _single_chain_run()
-    lm = s.model.model
-    assert lm.get_stat("graph_captures") == 1 and lm.get_stat("graph_replays") > 0
-    line = [l for l in _child("_single_chain_child", PGIBBS_GRAPH="0") if l.startswith("CHILD_TOKENS ")][-1]
-    assert json.loads(line[len("CHILD_TOKENS "):]) == out
-    s.draw_seed, s.record = 21, True
-    random.seed(4)
-    again = s.generate(1, SEED25, batch_size=1, num_iters=12, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
-    assert again == out
-    _replay_draws(s, s.last_run[0], 1, 3, 12, 0, float("inf"), 1.0, 21)
+    common.check_single_chain(_single_chain_run, "test_gpu_esm2_8m")
 
 
 def _shard_job(worlds):
     """A 64-chain job of config 2's chain length, whole and as contiguous shards that know the job's size: a digest of (tokens,
     logits) of the whole job, after checking every world against it bit for bit."""
-    import torch
-
-    from protein_gibbs_sampler_amd import pyrandom, sharding
     cfg, sd, _ = _case(n_layers=3)
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "bf16"), device="cuda:0")
-    lm = s.model.model
-    B, L, P, iters = 64, 256, 5, 2
-    T = L + 2
-    rng = np.random.default_rng(1234)
-    tok_all = np.concatenate([np.zeros((B, 1), np.int64), rng.integers(4, 24, (B, L)), np.full((B, 1), 2)], axis=1).astype(np.int32)
-    L_ = _lib.lib()
-
-    def run(lo, hi):
-        r = pyrandom.NativePyRandom()
-        r.seed(0)
-        table = sharding.local_slice(sharding.global_position_table(r, list(range(1, L + 1)), P, iters, B), lo, hi)
-        params = _lib.make_sample_params(True, 32, 0, float("inf"), 1.0, s.valid_aa_idx, rng_seed=0, row_id_base=lo)
-        d_tok = torch.from_numpy(tok_all[lo:hi].copy()).cuda()
-        d_idx = torch.from_numpy(table).cuda()
-        d_lg = torch.empty((iters, hi - lo, P, 33), dtype=torch.float32, device="cuda")
-        lm.set_job_items(B)
-        try:
-            _lib.check(L_.pg_esm_gibbs_run_device(lm.handle, ctypes.c_void_p(d_tok.data_ptr()), hi - lo, T,
-                                                  ctypes.c_void_p(d_idx.data_ptr()), iters, P, ctypes.byref(params),
-                                                  ctypes.c_void_p(d_lg.data_ptr()), None))
-            lm.synchronize()
-        finally:
-            lm.set_job_items(0)
-        return d_tok.cpu().numpy(), d_lg.cpu().numpy()
-
-    whole, whole_lg = run(0, B)
-    assert (whole != tok_all).any() and np.isfinite(whole_lg).all()
-    for world in worlds:
-        parts = [run(*sharding.shard_range(B, world, g)) for g in range(world)]
-        assert (np.concatenate([p[1] for p in parts], axis=1) == whole_lg).all(), "world=%d: sampled-position logits differ" % world
-        assert (np.concatenate([p[0] for p in parts]) == whole).all(), "world=%d" % world
-    return hashlib.sha256(whole.tobytes() + whole_lg.tobytes()).hexdigest()
+    return common.shard_job(_model(cfg, sd, "bf16"), worlds)
 
 
 def _shard_child():
@@ -463,11 +374,4 @@ def test_strict_valu_switch_refuses_heads_of_16_by_name():
 
 
 def _refuse_valu_child():
-    x = np.zeros((1, 16, 3 * 2 * HD), np.float32)
-    y = np.zeros((1, 16, 2 * HD), np.float32)
-    rc = _lib.lib().pg_dbg_attention_hd(0, _lib.PG_PREC_FP32, _lib.ptr(x), _lib.ptr(y), 1, 16, 2, HD, None, -1)
-    assert rc != 0
-    try:
-        _lib.check(rc)
-    except Exception as e:      # noqa: BLE001
-        print("CHILD_REFUSED " + str(e))
+    common.refuse_valu_child(HD)
