@@ -32,8 +32,9 @@ struct Prof {
   void destroy();
 };
 
-// PC_GEMM_*: the four per-layer projections of a full-batch forward, timed apart (bench.py's per-kernel roofline); "gemm" = all five
-enum ProfClass { PC_GEMM = 0, PC_ATTN, PC_LN, PC_EMBED, PC_HEAD, PC_SAMPLE, PC_GEMM_QKV, PC_GEMM_OUT, PC_GEMM_FC1, PC_GEMM_FC2,
+// PC_GEMM_*: the four per-layer projections of a full-batch forward, timed apart (bench.py's per-kernel roofline); "gemm" = all five.
+// PC_NONE: an op inside a timed() block of its caller's (the LM head's one record) -- no record of its own
+enum ProfClass { PC_NONE = -1, PC_GEMM = 0, PC_ATTN, PC_LN, PC_EMBED, PC_HEAD, PC_SAMPLE, PC_GEMM_QKV, PC_GEMM_OUT, PC_GEMM_FC1, PC_GEMM_FC2,
                  PC_ROPE /* ESM-2: the rotation of q and k, one launch per layer */, PC_COUNT };
 
 struct DenseW {   // y = x W^T + b ; W bf16 [N][K], b fp32 [N].  Strict precision mode: w is [N][3K], each row the
@@ -59,14 +60,36 @@ struct MsaLayer {
   DenseW col_qkv_hm;      // col_qkv with its rows grouped per head ([q_h | k_h | v_h]): operand of the fused column kernel (gemm_colattn.hip)
 };
 
+// What a captured Gibbs iteration depends on besides the device-side state block: a graph is replayed only under an equal key
+struct GraphKey {
+  int32_t mask = 0, mask_idx = 0;                 // baked into the captured launches (the scatter and its argument)
+  const void *tok = nullptr, *idx = nullptr;      // the caller's buffers: the graph holds raw pointers
+  int64_t B = 0, T = 0, P = 0;
+  hipStream_t stream = nullptr;
+  uint64_t epoch_pad = 0;                         // 2 x the allocation epoch (a workspace buffer that moved) + <pad> in the batch
+  int64_t job_items = 0;                          // picks kernels (sel_gemm_rows, splitk_ws): no replay under another job size
+  bool operator==(const GraphKey& o) const {
+    return mask == o.mask && mask_idx == o.mask_idx && tok == o.tok && idx == o.idx && B == o.B && T == o.T && P == o.P &&
+           stream == o.stream && epoch_pad == o.epoch_pad && job_items == o.job_items;
+  }
+  void reset() { *this = GraphKey(); }            // equals no call's key (tok == nullptr)
+};
+
 struct Engine {
   pg_model_config cfg;
   int device = 0;
   int precision = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
-  std::vector<void*> owned;   // every hipMalloc'd weight block
+  bool strict() const { return precision == PG_PREC_FP32; }
+  bool esm1() const { return cfg.arch == PG_ARCH_ESM1; }      // ESM-1 differences: see pgibbs.h PG_ARCH_ESM1
+  bool esm2() const { return cfg.arch == PG_ARCH_ESM2; }      // ESM-2 differences: see pgibbs.h PG_ARCH_ESM2
+  bool esm_family() const { return cfg.arch == PG_ARCH_ESM1B || cfg.arch == PG_ARCH_ESM1 || cfg.arch == PG_ARCH_ESM2; }   // the pg_esm_* entry points
 
-  // weights
+  ~Engine();
+  int init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int precision);
+
+  // ---- weights ----
+  std::vector<void*> owned;   // every hipMalloc'd weight block
   float *embed = nullptr, *pos = nullptr, *msa_pos = nullptr, *embed_out = nullptr;
   float embed_scale() const { return cfg.arch == PG_ARCH_ESM1 ? sqrtf((float)cfg.d_model) : 1.0f; }
   LnW ln_before, ln_after, head_ln;
@@ -74,30 +97,36 @@ struct Engine {
   float* head_bias = nullptr;
   std::vector<EsmLayer> esm_layers;
   std::vector<MsaLayer> msa_layers;
+  int head_dim = 64;          // d_model / n_heads, a width of head_width.h's table -- what every attention and rotation launch of the ESM path is given
+  // ESM-2 rotary embedding: cos / sin table [rope_rows][head_dim] fp32 built at init (rope.hip)
+  float* rope_tab = nullptr;
+  int rope_rows = 0;
+  // persistent single-chain trunk (chain_trunk.hip): device table of the layers' weight pointers
+  PgChainLayerW* chain_layers = nullptr;
 
-  // workspace (grow-only)
+  // ---- workspace (grow-only) ----
   DevBuf x, h, qkv, ctx, ffn, sel_h, sel_g, logits, d_tokens, d_idx, d_samp_tok, d_samp_logits, d_rowmap, scratch;
   DevBuf x_sel, ctx_sel, h_sel, ffn_sel;   // last-layer pruning (compact rows)
-  // x (+)= a W^T + b, then h = LayerNorm(x; ln): residual GEMM + LayerNorm kernel
-  int resid_gemm_ln(const bf16_t* a, const DenseW& W, float* x, int M_rows, int64_t M_real, int lda, const LnW& ln, bf16_t* h,
-                    float* ws = nullptr, size_t ws_bytes = 0, int prof_class = PC_GEMM, int colmajor_R = 0, int colmajor_C = 0);
   DevBuf tmp_idx, tmp_out;                 // batched generate_single on small MSAs: one template's step table / outputs
   DevBuf splitk;                           // fp32 partial maps of split-K fc2 GEMMs (small batches)
-  bool esm_pad_in_batch = false;           // set by the host-token entry points: some token is <pad> -> key-padding mask
+  // strict precision mode (PG_PREC_FP32): h, ctx, ffn, sel_h hold [lo | hi | hi] rows (3x wide); fp32 fc1 output;
+  // row-attention scores (also the bf16 mode's wide-alignment fallback)
+  DevBuf ffn_f32, scores;
+  DevBuf chain_sync, chain_part;           // persistent single-chain trunk: barrier block, fc2 partials
+  int size_activations(int64_t Mp);        // x, h, qkv, ctx, ffn for Mp padded token rows
   float* splitk_ws(int rows, int n, int K, int64_t batch_rows);
+
+  // ---- job-order knobs: what keeps a shard's arithmetic that of the whole job ----
+  bool esm_pad_in_batch = false;           // set by the host-token entry points: some token is <pad> -> key-padding mask
   int64_t job_items = 0;                   // pg_engine_set_job_items: batch items of the whole (multi-GPU) job, 0 = this call
   int64_t order_items = 0;                 // > 0: order-changing kernel choices as for a job of this many items (batched generate_single: 1)
   int64_t job_batch(int64_t B) const { return order_items > 0 ? order_items : (job_items > B ? job_items : B); }
   int64_t batch_rows_for(int64_t B, int64_t rows_per_item) const { return job_batch(B) * rows_per_item; }
   int64_t batch_rows = 0;                  // token rows of the JOB's forward (batch_rows_for; set by the trunks)
   int sel_gemm_rows(int64_t n_sel, int64_t Np) const;
-  // launch-bound (small) Gibbs loops: one iteration captured as a hipGraph and replayed; the iteration number lives in
-  // d_iter on the device, so the same graph serves every iteration
-  DevBuf d_iter;
-  // persistent single-chain trunk (chain_trunk.hip): device table of the layers' weight pointers, barrier block, fc2 partials,
-  // and a host-pinned error word the kernel sets when a device-wide barrier timed out
-  PgChainLayerW* chain_layers = nullptr;
-  DevBuf chain_sync, chain_part;
+
+  // ---- persistent-trunk recovery ----
+  // a host-pinned error word the kernel sets when a device-wide barrier timed out
   unsigned* chain_err = nullptr;
   // after a stream synchronisation: PG_ERR_HIP if chain_err is set.  The kernel is then switched off for the rest of this engine's
   // life (the device is evidently shared with another persistent grid) and chain_retry tells the host-buffer entry points, whose
@@ -123,54 +152,74 @@ struct Engine {
   unsigned* range_err = nullptr;
   int range_check();
   int finish_check() { int rc = chain_check(); return rc ? rc : range_check(); }      // right after a stream synchronisation
+
+  // ---- graph ----
+  // launch-bound (small) Gibbs loops: one iteration captured as a hipGraph and replayed; the iteration number lives in
+  // d_iter on the device, so the same graph serves every iteration
+  DevBuf d_iter;
   hipGraphExec_t graph_exec = nullptr;
-  std::vector<uint8_t> graph_key;
+  GraphKey graph_key;                                          // of graph_exec
   int64_t stat_graph_captures = 0, stat_graph_replays = 0;     // pg_engine_get_stat
-  // strict precision mode (PG_PREC_FP32): h, ctx, ffn, sel_h hold [lo | hi | hi] rows (3x wide); fp32 fc1 output;
-  // row-attention scores (also the bf16 mode's wide-alignment fallback)
-  DevBuf ffn_f32, scores;
-  bool strict() const { return precision == PG_PREC_FP32; }
-  bool esm1() const { return cfg.arch == PG_ARCH_ESM1; }      // ESM-1 differences: see pgibbs.h PG_ARCH_ESM1
-  bool esm2() const { return cfg.arch == PG_ARCH_ESM2; }      // ESM-2 differences: see pgibbs.h PG_ARCH_ESM2
-  bool esm_family() const { return cfg.arch == PG_ARCH_ESM1B || cfg.arch == PG_ARCH_ESM1 || cfg.arch == PG_ARCH_ESM2; }   // the pg_esm_* entry points
-  // ESM-2 rotary embedding: cos / sin table [rope_rows][head_dim] fp32 built at init (rope.hip); rope() rotates the q and k thirds of a
-  // freshly projected qkv buffer (the engine's 16-bit type, fp32 in strict mode) of M token rows, T per sequence.  A no-op for
-  // every other architecture
-  int head_dim = 64;          // d_model / n_heads: 64, or 32 (ESM-2 only) -- what every attention and rotation launch of the ESM path is given
-  float* rope_tab = nullptr;
-  int rope_rows = 0;
-  int rope(void* qkv_rows, int64_t M, int T);
+
+  // ---- strict mode (PG_PREC_FP32) ----
   // out[Mp][N] fp32 (=|+=) X.W^T + b with X = xh + xl, W = wh + wl as ONE bf16 GEMM over K' = 3K:
   // [xl | xh | xh] . [wh | wl | wh]^T = xl.wh + xh.wl + xh.wh  (the dropped xl.wl term is ~2^-17 relative)
   int dense3(const bf16_t* x3, const DenseW& W, float* out, int Mp, bool accumulate);
   int dense3_gelu(const bf16_t* x3, const DenseW& W, int Mp, const DenseW* next = nullptr);   // fc1: ffn (operand rows) = split3(gelu(.)); next = the projection that reads them
   bool dense3_wants_dup(const DenseW& W, int Mp, bool gelu = false) const;   // does this projection read the duplicate hi block of its operand rows?
+  // the attention sub-block of a strict layer on x: h = LN(x) -> qkv (fp32) = qkv_w(h) -> ctx = attn(split_d) -> x += out_w(ctx).
+  // attn launches the attention (ESM-2: after the rotation) on qkv given ctx's form, split_d = +-d_model (launch_attention_f32):
+  // without the duplicate hi block when out_w never reads it
+  template <typename Attn> int strict_attention(const LnW& ln, const DenseW& qkv_w, const DenseW& out_w, int Mi, int64_t M, Attn&& attn);
+  int ffn_strict(const FfnW& F, int Mi, int64_t M);           // the FFN of a strict layer on x
+
+  // ---- forward ops (all on `stream`, device pointers; each a record of its profiling class) ----
   Prof prof;
-
-  ~Engine();
-  int init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int precision);
-
-  // ---- forward pieces (all on `stream`, device pointers) ----
-  int size_activations(int64_t Mp);   // x, h, qkv, ctx, ffn for Mp padded token rows
-  // the end of a layer on all Mi token rows (M real), both trunks.  ffn_block (bf16 / fp16): x += out(ctx); h = LN(x);
-  // x += fc2(gelu(fc1(h))); h = next_ln(x) when a layer follows.  ffn_strict: the FFN alone
-  int ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int Mi, int64_t M);
-  int ffn_strict(const FfnW& F, int Mi, int64_t M);
+  template <typename F> int timed(int cls, F&& f);
+  // x = the embedded tokens (+ h = first_ln(x), the first projection's operand rows); rows_per_msa > 0: an alignment batch
+  int embed_rows(const int32_t* d_tok, int64_t M, int T, int rows_per_msa, const LnW* first_ln);
+  // out[rows][W.N] (+)= a[rows][W.K] W^T + b through the epilogue epi: the flavour's GEMM dispatch with every leading dimension W's
+  // own.  m_live: the real token rows among `rows` (0: not said -- launch_gemm_bf16).  splitk: offer the split-K scratch (splitk_ws)
+  int dense(int cls, const bf16_t* a, const DenseW& W, void* out, int rows, int epi, int m_live = 0, bool splitk = false);
+  // out (16-bit) = LayerNorm(x; ln) W^T + b: the weight-streaming GEMM with the LayerNorm in its operand load (gemm_ln_skinny_ok)
+  int dense_ln(const float* x, const LnW& ln, const DenseW& W, bf16_t* out, int rows, int epi);
+  // h = LayerNorm(x; ln) on M rows, as operand rows of the projection that reads them: 16-bit, or in strict mode split rows whose
+  // duplicate hi block is written only if that projection looks at it (dup = its dense3_wants_dup).  colmajor: launch_layernorm_bf16
+  int layer_norm(const float* x, const LnW& ln, bf16_t* h, int64_t M, bool dup = true, int colmajor_R = 0, int colmajor_C = 0);
+  // x (+)= a W^T + b as dense(cls, ..., m_live = M_real), then h = LayerNorm(x; ln): residual GEMM + LayerNorm kernel
+  int resid_gemm_ln(int cls, const bf16_t* a, const DenseW& W, float* x, int rows, int64_t M_real, const LnW& ln, bf16_t* h,
+                    bool splitk = false, int colmajor_R = 0, int colmajor_C = 0);
+  // rope() rotates the q and k thirds of a freshly projected qkv buffer (the engine's 16-bit type, fp32 in strict mode) of M token
+  // rows, T per sequence.  A no-op for every architecture but ESM-2
+  int rope(void* qkv_rows, int64_t M, int T);
+  // the end of a 16-bit layer on all Mi token rows (M real), both trunks, from the attention's ctx on.  Tile regime: x += out(ctx);
+  // h = LN(x); x += fc2(gelu(fc1(h))); h = next_ln(x) when a layer follows.  folded (single chains): the same with both LayerNorms
+  // inside the weight-streaming GEMMs that read them -- fc1 here, the next layer's QKV projection in the trunk -- so h is not written
+  int ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int Mi, int64_t M, bool folded = false);
   // finish the last layer on the n_draws selected rows only?  (PGIBBS_PRUNE_LAST=0: never) ... and that tail: the selected rows of
   // x and ctx -> x_sel / ctx_sel, then ffn_block's steps on GEMMs of height Ni.  ln_in_gemm: the trunk folds LayerNorm into the
   // weight-streaming GEMMs (fc1's too when Ni allows)
   bool prune_last(int64_t n_draws, int64_t token_rows) const;
   int pruned_tail(const DenseW& out, const FfnW& F, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int width, int64_t n_sel,
                   const int32_t* d_iter, int Ni, bool ln_in_gemm);
+  // every layer of a single short chain in ONE persistent launch, when the shape and this engine's state allow: *ran says how far
+  // the forward got.  stop_at_last_attention: the caller finishes the last layer on selected rows (pruned_tail)
+  enum ChainRan { CHAIN_NOT_RUN, CHAIN_TO_LAST_ATTENTION, CHAIN_WHOLE_FORWARD };
+  int chain_forward(int B, int T, int Mi, bool stop_at_last_attention, ChainRan* ran);
   // tokens -> x (before ln_after).  With a selection (sel_idx != nullptr, bf16 mode) the LAST layer's out-proj, LN2 and
   // FFN run only on the selected rows and x_sel [n_sel][d] holds their residual stream (exact: nothing else reads
-  // the last layer's output); head_compact() then consumes x_sel.
+  // the last layer's output); head() then reads x_sel (masked_logits).
   int esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx, int P, int64_t n_sel, const int32_t* d_iter);
-  int head(const int32_t* d_idx, const int32_t* d_row_map, int P, int width, int64_t n_sel, float* d_logits,
-           const float* x_src = nullptr);
+  // tokens[B][R][C] -> x; with a selection the LAST layer's column out-projection and FFN run on the selected rows only
+  // (x_sel), as in esm_trunk
+  int msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int64_t n_sel);
   // the trunk of this engine's architecture on tokens[B][R][C]; R = 1 for the ESM family (d_iter: its captured iteration only)
   int trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx = nullptr, const int32_t* sel_row_map = nullptr, int P = 0,
             int64_t n_sel = 0, const int32_t* d_iter = nullptr);
+  int head(const int32_t* d_idx, const int32_t* d_row_map, int P, int width, int64_t n_sel, float* d_logits,
+           const float* x_src = nullptr);
+
+  // ---- entry points ----
   // One Gibbs iteration up to its logits: mask_idx scattered (if mask) to idx[n_rows][P] of the token rows mask_map, the trunk
   // (pruned when prune_last says so), the LM head at idx[n_rows][P] of the token rows sel_map -> lg[n_rows * P][V].  A null map:
   // row i is token row i.  dit: the device-side iteration counter of a captured iteration (pruned only)
@@ -178,9 +227,6 @@ struct Engine {
                     int64_t n_rows, int P, bool mask, int mask_idx, float* lg, const int32_t* dit = nullptr);
   int esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx, int n_iters, int P, const pg_sample_params* sp,
                        float* d_samp_logits, int32_t* d_samp_tok);
-  // tokens[B][R][C] -> x; with a selection the LAST layer's column out-projection and FFN run on the selected rows only
-  // (x_sel), as in esm_trunk
-  int msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int64_t n_sel);
   int msa_gibbs_device(int32_t* d_tok, int B, int R, int C, const int32_t* d_idx, int n_iters, int P,
                        const pg_sample_params* sp, float* d_samp_logits, int32_t* d_samp_tok);
   // generate_single on B templates of equal shape: step s masks row mask_row of every template and samples row target_row of
@@ -188,9 +234,6 @@ struct Engine {
   int msa_single_device(int32_t* d_tok, int B, int R, int C, int mask_row, int target_row, const int32_t* d_step_idx,
                         const int32_t* step_sample_flag_host, int n_steps, int P_max, const pg_sample_params* sp,
                         float* d_samp_logits, int32_t* d_samp_tok);
-
-  // timing helper
-  template <typename F> int timed(int cls, F&& f);
 };
 
 // host side of the ESM-2 rotary embedding: the cos / sin table the rotation kernel reads (engine.hip)

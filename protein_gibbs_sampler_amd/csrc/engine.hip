@@ -82,7 +82,7 @@ void Prof::destroy() {
 }
 
 template <typename F> int Engine::timed(int cls, F&& f) {
-  if (!prof.on) return f();
+  if (!prof.on || cls == PC_NONE) return f();
   hipEvent_t a = prof.get(), b = prof.get();
   clear_noted_kernels();
   PG_HIP(hipEventRecord(a, stream));
@@ -129,12 +129,21 @@ struct Uploader {
   const int precision;      // the engine's: OPS
   std::string err;
 
+  // a device block the engine owns until it dies (keep), or one the caller frees; on failure null and err = "hipMalloc failed <what>"
+  void* alloc(size_t bytes, const std::string& what, bool keep = true) {
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) { err = "hipMalloc failed " + what; return nullptr; }
+    if (keep) e->owned.push_back(d);
+    return d;
+  }
+  struct Staging {      // freed on every way out of its scope
+    void* p;
+    ~Staging() { if (p) (void)hipFree(p); }
+  };
   float* f32(const std::string& name, int64_t numel) {
     const float* src = tm->get(name, numel, err);
-    if (!src) return nullptr;
-    void* d = nullptr;
-    if (hipMalloc(&d, (size_t)numel * 4) != hipSuccess) { err = "hipMalloc failed for " + name; return nullptr; }
-    e->owned.push_back(d);
+    void* d = src ? alloc((size_t)numel * 4, "for " + name) : nullptr;
+    if (!d) return nullptr;
     if (hipMemcpy(d, src, (size_t)numel * 4, hipMemcpyHostToDevice) != hipSuccess) { err = "H2D failed for " + name; return nullptr; }
     return (float*)d;
   }
@@ -142,16 +151,17 @@ struct Uploader {
   bool dense(DenseW& out, const std::vector<std::string>& prefixes, const std::vector<float>& scales, int n_each, int K) {
     const int parts = (int)prefixes.size();
     const int64_t N = (int64_t)n_each * parts;
-    void *dw = nullptr, *db = nullptr, *tmp = nullptr;
     const int Kw = e->strict() ? 3 * K : K;      // strict: rows are [hi | lo | hi]
-    if (hipMalloc(&dw, (size_t)N * Kw * 2) != hipSuccess || hipMalloc(&db, (size_t)N * 4) != hipSuccess ||
-        hipMalloc(&tmp, (size_t)n_each * K * 4) != hipSuccess) { err = "hipMalloc failed for " + prefixes[0]; return false; }
-    e->owned.push_back(dw);
-    e->owned.push_back(db);
+    const std::string what = "for " + prefixes[0];
+    void* dw = alloc((size_t)N * Kw * 2, what);
+    void* db = dw ? alloc((size_t)N * 4, what) : nullptr;
+    Staging staging{db ? alloc((size_t)n_each * K * 4, what, false) : nullptr};
+    void* tmp = staging.p;
+    if (!tmp) return false;
     for (int p = 0; p < parts; ++p) {
       const float* w = tm->get(prefixes[p] + ".weight", (int64_t)n_each * K, err);
       const float* b = w ? tm->get(prefixes[p] + ".bias", n_each, err) : nullptr;
-      if (!w || !b) { (void)hipFree(tmp); return false; }
+      if (!w || !b) return false;
       bool ok = hipMemcpy(tmp, w, (size_t)n_each * K * 4, hipMemcpyHostToDevice) == hipSuccess;
       if (e->strict())
         ok = ok && launch_split3_bf16(e->stream, (const float*)tmp, (bf16_t*)dw + (size_t)p * n_each * Kw, n_each, K, scales[p],
@@ -162,9 +172,8 @@ struct Uploader {
       ok = ok && hipMemcpy((float*)db + (size_t)p * n_each, b, (size_t)n_each * 4, hipMemcpyHostToDevice) == hipSuccess;
       if (ok && scales[p] != 1.0f) ok = launch_scale_f32(e->stream, (float*)db + (size_t)p * n_each, n_each, scales[p]) == 0 &&
                                         hipStreamSynchronize(e->stream) == hipSuccess;
-      if (!ok) { err = "upload failed for " + prefixes[p]; (void)hipFree(tmp); return false; }
+      if (!ok) { err = "upload failed for " + prefixes[p]; return false; }
     }
-    (void)hipFree(tmp);
     out.w = (bf16_t*)dw;
     out.b = (float*)db;
     out.N = (int)N;
@@ -176,10 +185,9 @@ struct Uploader {
     const float* bk = tm->get(kname, d, err);
     const float* bv = bk ? tm->get(vname, d, err) : nullptr;
     if (!bk || !bv) return false;
-    void *d32 = nullptr, *d16 = nullptr;
-    if (hipMalloc(&d32, (size_t)2 * d * 4) != hipSuccess || hipMalloc(&d16, (size_t)2 * d * 2) != hipSuccess) { err = "hipMalloc failed for " + kname; return false; }
-    e->owned.push_back(d32);
-    e->owned.push_back(d16);
+    void* d32 = alloc((size_t)2 * d * 4, "for " + kname);
+    void* d16 = d32 ? alloc((size_t)2 * d * 2, "for " + kname) : nullptr;
+    if (!d16) return false;
     bool ok = hipMemcpy(d32, bk, (size_t)d * 4, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy((float*)d32 + d, bv, (size_t)d * 4, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && OPS(launch_f32_to_bf16, e->stream, (const float*)d32, (bf16_t*)d16, 2 * d, 1.f) == 0;
@@ -191,10 +199,9 @@ struct Uploader {
   }
   // a [q | k | v] projection with its rows regrouped per head (the fused column QKV + attention kernel's weight operand)
   bool headmajor(DenseW& out, const DenseW& in, int H) {
-    void *dw = nullptr, *db = nullptr;
-    if (hipMalloc(&dw, (size_t)in.N * in.K * 2) != hipSuccess || hipMalloc(&db, (size_t)in.N * 4) != hipSuccess) { err = "hipMalloc failed (head-major projection)"; return false; }
-    e->owned.push_back(dw);
-    e->owned.push_back(db);
+    void* dw = alloc((size_t)in.N * in.K * 2, "(head-major projection)");
+    void* db = dw ? alloc((size_t)in.N * 4, "(head-major projection)") : nullptr;
+    if (!db) return false;
     const bool ok = OPS(launch_headmajor_qkv, e->stream, in.w, in.b, (bf16_t*)dw, (float*)db, H, in.K) == 0 &&
                     hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) { err = "head-major projection copy failed"; return false; }
@@ -397,7 +404,7 @@ int Engine::chain_check() {
   // follows -- they raise it again if the logits really are non-finite
   if (range_err) *range_err = 0;
   if (chain_sync.p) (void)hipMemsetAsync(chain_sync.p, 0, chain_sync.bytes, stream);
-  if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; graph_key.clear(); }   // it holds the persistent launch
+  if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; graph_key.reset(); }   // it holds the persistent launch
   if (!chain_disabled)
     fprintf(stderr, "pgibbs: a device-wide barrier of the persistent single-chain trunk timed out (another persistent grid on this GPU?); "
                     "this engine uses the per-layer launches from now on\n");
@@ -422,6 +429,34 @@ int Engine::chain_check() {
   }
   return fail(PG_ERR_HIP, "single-chain trunk: a device-wide barrier timed out (is another persistent kernel sharing this GPU? "
                           "PGIBBS_CHAIN_TRUNK=0 selects the per-layer launches); the results of this call are invalid");
+}
+
+// ------------------------------------------------------------------------------------------------
+// forward ops: the launchers every 16-bit projection, every LayerNorm and the embedding go through (engine.h)
+// ------------------------------------------------------------------------------------------------
+int Engine::dense(int cls, const bf16_t* a, const DenseW& W, void* out, int rows, int epi, int m_live, bool use_splitk) {
+  // the scratch first, its size after: splitk_ws may grow the buffer
+  float* ws = use_splitk ? splitk_ws(rows, W.N, W.K, batch_rows) : nullptr;
+  const size_t ws_bytes = use_splitk ? splitk.bytes : 0;
+  return timed(cls, [&] { return OPS(launch_gemm_bf16, stream, a, W.w, W.b, out, rows, W.N, W.K, W.K, W.K, W.N, epi, ws, ws_bytes, m_live); });
+}
+
+int Engine::dense_ln(const float* x, const LnW& ln, const DenseW& W, bf16_t* out, int rows, int epi) {
+  return timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, x, W.K, ln.g, ln.b, cfg.layer_norm_eps, W.w, W.b, out, rows, W.N, W.K, W.K, W.N, epi); });
+}
+
+int Engine::layer_norm(const float* x, const LnW& ln, bf16_t* h, int64_t M, bool dup, int colmajor_R, int colmajor_C) {
+  return timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, x, ln.g, ln.b, h, M, cfg.d_model, cfg.layer_norm_eps, strict(), colmajor_R, colmajor_C, dup); });
+}
+
+// x = embedding (+ positions, emb_layer_norm_before) of M tokens, T per sequence; rows_per_msa > 0: an alignment batch (its row
+// positions, no token dropout).  first_ln: in the same pass over the row also h = that LayerNorm of x, the first projection's operand
+int Engine::embed_rows(const int32_t* d_tok, int64_t M, int T, int rows_per_msa, const LnW* first_ln) {
+  return timed(PC_EMBED, [&] {
+    return OPS(launch_embed_ln, stream, d_tok, embed, pos, msa_pos, ln_before.g, ln_before.b, x.as<float>(), M, T, cfg.d_model, cfg.pad_idx,
+                           cfg.mask_idx, rows_per_msa ? 0 : cfg.token_dropout, rows_per_msa, cfg.layer_norm_eps, first_ln ? first_ln->g : nullptr,
+                           first_ln ? first_ln->b : nullptr, first_ln ? h.as<bf16_t>() : nullptr, embed_scale());
+  });
 }
 
 // strict precision mode GEMM: one bf16 MFMA GEMM over the K-concatenated split operands (engine.h) reproduces an
@@ -522,21 +557,38 @@ int Engine::ffn_strict(const FfnW& F, int Mi, int64_t M) {
   float* X = x.as<float>();
   bf16_t* H3 = h.as<bf16_t>();
   int rc;
-  if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, F.ln.g, F.ln.b, H3, M, cfg.d_model, cfg.layer_norm_eps, true, 0, 0, dense3_wants_dup(F.fc1, Mi, true)); }))) return rc;
+  if ((rc = layer_norm(X, F.ln, H3, M, dense3_wants_dup(F.fc1, Mi, true)))) return rc;
   if ((rc = dense3_gelu(H3, F.fc1, Mi, &F.fc2))) return rc;
   return dense3(ffn.as<bf16_t>(), F.fc2, X, Mi, true);
 }
 
-int Engine::ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int Mi, int64_t M) {
-  const int d = cfg.d_model, f = cfg.d_ffn;
+template <typename Attn>
+int Engine::strict_attention(const LnW& ln, const DenseW& qkv_w, const DenseW& out_w, int Mi, int64_t M, Attn&& attn) {
+  float* X = x.as<float>();
+  bf16_t* H3 = h.as<bf16_t>();
+  int rc;
+  if ((rc = layer_norm(X, ln, H3, M, dense3_wants_dup(qkv_w, Mi)))) return rc;
+  if ((rc = dense3(H3, qkv_w, qkv.as<float>(), Mi, false))) return rc;
+  if ((rc = attn(dense3_wants_dup(out_w, Mi) ? cfg.d_model : -cfg.d_model))) return rc;
+  return dense3(ctx.as<bf16_t>(), out_w, X, Mi, true);
+}
+
+int Engine::ffn_block(const DenseW& out, const FfnW& F, const LnW* next_ln, int Mi, int64_t M, bool folded) {
   float* X = x.as<float>();
   bf16_t* Hh = h.as<bf16_t>();
+  bf16_t* CTX = ctx.as<bf16_t>();
   bf16_t* FFN = ffn.as<bf16_t>();
   int rc;
-  if ((rc = resid_gemm_ln(ctx.as<bf16_t>(), out, X, Mi, M, d, F.ln, Hh, nullptr, 0, PC_GEMM_OUT))) return rc;
-  if ((rc = timed(PC_GEMM_FC1, [&] { return OPS(launch_gemm_bf16, stream, Hh, F.fc1.w, F.fc1.b, FFN, Mi, f, d, d, d, f, EPI_BF16_GELU, nullptr, 0, (int)M); }))) return rc;
-  if (next_ln) return resid_gemm_ln(FFN, F.fc2, X, Mi, M, f, *next_ln, Hh, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, PC_GEMM_FC2);
-  return timed(PC_GEMM_FC2, [&] { return OPS(launch_gemm_bf16, stream, FFN, F.fc2.w, F.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); });
+  if (folded) {
+    // the out-projection does not say its live rows and all three are "gemm_other": the launch-bound regime is not timed per projection
+    if ((rc = dense(PC_GEMM, CTX, out, X, Mi, EPI_F32_RESID))) return rc;
+    if ((rc = dense_ln(X, F.ln, F.fc1, FFN, Mi, EPI_BF16_GELU))) return rc;
+    return dense(PC_GEMM, FFN, F.fc2, X, Mi, EPI_F32_RESID, (int)M, true);
+  }
+  if ((rc = resid_gemm_ln(PC_GEMM_OUT, CTX, out, X, Mi, M, F.ln, Hh))) return rc;
+  if ((rc = dense(PC_GEMM_FC1, Hh, F.fc1, FFN, Mi, EPI_BF16_GELU, (int)M))) return rc;
+  if (next_ln) return resid_gemm_ln(PC_GEMM_FC2, FFN, F.fc2, X, Mi, M, *next_ln, Hh, true);
+  return dense(PC_GEMM_FC2, FFN, F.fc2, X, Mi, EPI_F32_RESID, (int)M, true);
 }
 
 bool Engine::prune_last(int64_t n_draws, int64_t token_rows) const {
@@ -547,12 +599,12 @@ bool Engine::prune_last(int64_t n_draws, int64_t token_rows) const {
 int Engine::pruned_tail(const DenseW& out, const FfnW& F, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int width,
                         int64_t n_sel, const int32_t* d_iter_, int Ni, bool ln_in_gemm) {
   const int d = cfg.d_model, f = cfg.d_ffn;
-  const float eps = cfg.layer_norm_eps;
   const int64_t Np = round_up64(n_sel, kRowPad);
   int rc;
   if ((rc = x_sel.ensure((size_t)Np * d * 4, stream)) || (rc = ctx_sel.ensure((size_t)Np * d * 2, stream)) ||
       (rc = h_sel.ensure((size_t)Np * d * 2, stream)) || (rc = ffn_sel.ensure((size_t)Np * f * 2, stream))) return rc;
   float* XS = x_sel.as<float>();
+  bf16_t* HS = h_sel.as<bf16_t>();
   bf16_t* FS = ffn_sel.as<bf16_t>();
   rc = timed(PC_HEAD, [&] {
     int r2 = launch_gather_rows(stream, x.as<float>(), XS, sel_idx, sel_row_map, P, width, n_sel, d * 4, d_iter_);
@@ -560,14 +612,16 @@ int Engine::pruned_tail(const DenseW& out, const FfnW& F, const int32_t* sel_idx
     return launch_gather_rows(stream, ctx.as<bf16_t>(), ctx_sel.as<bf16_t>(), sel_idx, sel_row_map, P, width, n_sel, d * 2, d_iter_);
   });
   if (rc) return rc;
-  if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, ctx_sel.as<bf16_t>(), out.w, out.b, XS, Ni, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
+  // ffn_block's steps on the compact rows -- a body of its own: other buffers, Ni rows under one class, no projection says its live
+  // rows (not the same request as saying Ni or n_sel), and the LayerNorm is folded by what Ni allows, not by the trunk's regime alone
+  if ((rc = dense(PC_GEMM, ctx_sel.as<bf16_t>(), out, XS, Ni, EPI_F32_RESID))) return rc;
   if (ln_in_gemm && gemm_ln_skinny_ok(Ni, f, d)) {
-    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, XS, d, F.ln.g, F.ln.b, eps, F.fc1.w, F.fc1.b, FS, Ni, f, d, d, f, EPI_BF16_GELU); }))) return rc;
+    if ((rc = dense_ln(XS, F.ln, F.fc1, FS, Ni, EPI_BF16_GELU))) return rc;
   } else {
-    if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, XS, F.ln.g, F.ln.b, h_sel.as<bf16_t>(), n_sel, d, eps); }))) return rc;
-    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, h_sel.as<bf16_t>(), F.fc1.w, F.fc1.b, FS, Ni, f, d, d, d, f, EPI_BF16_GELU); }))) return rc;
+    if ((rc = layer_norm(XS, F.ln, HS, n_sel))) return rc;
+    if ((rc = dense(PC_GEMM, HS, F.fc1, FS, Ni, EPI_BF16_GELU))) return rc;
   }
-  return timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FS, F.fc2.w, F.fc2.b, XS, Ni, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Ni, d, f, batch_rows), splitk.bytes); });
+  return dense(PC_GEMM, FS, F.fc2, XS, Ni, EPI_F32_RESID, 0, true);
 }
 
 int Engine::trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_idx, const int32_t* sel_row_map, int P, int64_t n_sel,
@@ -583,31 +637,24 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
   if ((rc = size_activations(Mp))) return rc;
   batch_rows = batch_rows_for(B, T);
   float* X = x.as<float>();
-  const float eps = cfg.layer_norm_eps;
   if (strict()) {
     float* QKVf = qkv.as<float>();
     const int Mi = (int)Mp;
-    rc = timed(PC_EMBED, [&] {
-      return OPS(launch_embed_ln, stream, d_tok, embed, pos, nullptr, ln_before.g, ln_before.b, X, M, T, d, cfg.pad_idx,
-                             cfg.mask_idx, cfg.token_dropout, 0, eps, nullptr, nullptr, nullptr, embed_scale());
-    });
-    if (rc) return rc;
+    if ((rc = embed_rows(d_tok, M, T, 0, nullptr))) return rc;
     const SeqLayout chain = {1, T, 0, 1};
-    for (int l = 0; l < cfg.n_layers; ++l) {
-      const EsmLayer& L = esm_layers[l];
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln1.g, L.ln1.b, h.as<bf16_t>(), M, d, eps, true, 0, 0, dense3_wants_dup(L.qkv, Mi)); }))) return rc;
-      if ((rc = dense3(h.as<bf16_t>(), L.qkv, QKVf, Mi, false))) return rc;
-      if ((rc = rope(QKVf, M, T))) return rc;                                  // ESM-2 only
-      if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), dense3_wants_dup(L.out, Mi) ? d : -d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32, head_dim); }))) return rc;
-      if ((rc = dense3(ctx.as<bf16_t>(), L.out, X, Mi, true))) return rc;
-      if ((rc = ffn_strict(L.ffn, Mi, M))) return rc;
+    for (const EsmLayer& L : esm_layers) {
+      rc = strict_attention(L.ln1, L.qkv, L.out, Mi, M, [&](int split_d) {
+        const int r = rope(QKVf, M, T);                                        // ESM-2 only
+        if (r) return r;
+        return timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), split_d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32, head_dim); });
+      });
+      if (rc || (rc = ffn_strict(L.ffn, Mi, M))) return rc;
     }
     return PG_OK;
   }
   bf16_t* Hh = h.as<bf16_t>();
   bf16_t* QKV = qkv.as<bf16_t>();
   bf16_t* CTX = ctx.as<bf16_t>();
-  bf16_t* FFN = ffn.as<bf16_t>();
   // <= 256 rows: 64-row tiles, <= 48 rows the weight-streaming GEMM (buffers stay 256-padded) -- the latter not for a tiny shard
   // of a big job (sel_gemm_rows)
   const int Mi = sel_gemm_rows(M, Mp);
@@ -616,81 +663,70 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
   const bool ln_in_gemm = gemm_ln_skinny_ok(Mi, 3 * d, d) && gemm_ln_skinny_ok(Mi, f, d);
 
   // embedding + emb_layer_norm_before, and in the same pass over the row the first layer's LayerNorm (its bf16 operand rows)
-  rc = timed(PC_EMBED, [&] {
-    return OPS(launch_embed_ln, stream, d_tok, embed, pos, nullptr, ln_before.g, ln_before.b, X, M, T, d, cfg.pad_idx,
-                           cfg.mask_idx, cfg.token_dropout, 0, eps, ln_in_gemm ? nullptr : esm_layers[0].ln1.g,
-                           ln_in_gemm ? nullptr : esm_layers[0].ln1.b, ln_in_gemm ? nullptr : Hh, embed_scale());
-  });
-  if (rc) return rc;
-  // a single short chain (<= 32 token rows): every layer in ONE persistent launch (chain_trunk.hip; same bits as the per-layer
-  // launches below).  With a selection it stops after the last layer's attention and the pruned tail below finishes on the
-  // selected rows.
-  int l_first = 0;
-  bool attn_done = false;
-  if (ln_in_gemm && chain_layers && !chain_disabled && !esm_pad_in_batch && T <= 32 && M <= Mi && OPS(chain_trunk_ok, Mi, d, f, cfg.n_heads)) {
-    if ((rc = chain_sync.ensure(OPS(chain_trunk_sync_bytes), stream)) || (rc = chain_part.ensure(OPS(chain_trunk_part_bytes, Mi, d), stream))) return rc;
-    PgChainTrunkArgs ca;
-    ca.layers = chain_layers; ca.n_layers = cfg.n_layers; ca.partial_last = sel_idx ? 1 : 0; ca.B = B; ca.T = T;
-    ca.x = X; ca.qkv = QKV; ca.ctx = CTX; ca.ffn = FFN; ca.part = chain_part.as<float>(); ca.sync = chain_sync.as<unsigned>();
-    ca.err = chain_err; ca.eps = eps;
-    rc = timed(PC_GEMM, [&] { return OPS(launch_chain_trunk, stream, ca, Mi, d); });
-    if (rc == kChainTrunkUnfit) {              // the grid cannot be co-resident on this device: per-layer launches, for good
-      chain_disabled = true;
-    } else if (rc) {
-      return rc;
-    } else {
-      // test hook: PGIBBS_CHAIN_TRUNK_FAULT=n makes the n-th persistent launch of the process report a barrier timeout
-      static const int fault_at = env_int("PGIBBS_CHAIN_TRUNK_FAULT", 0);
-      static int launches = 0;
-      if (fault_at > 0 && ++launches == fault_at) *chain_err = 1;
-      if (!sel_idx) return PG_OK;
-      l_first = cfg.n_layers - 1;
-      attn_done = true;
-    }
-  }
-  for (int l = l_first; l < cfg.n_layers; ++l) {
+  if ((rc = embed_rows(d_tok, M, T, 0, ln_in_gemm ? nullptr : &esm_layers[0].ln1))) return rc;
+  // a single short chain: the persistent launch, when it may run.  With a selection it stops after the last layer's attention and
+  // the pruned tail finishes on the selected rows
+  ChainRan ran = CHAIN_NOT_RUN;
+  if (ln_in_gemm && (rc = chain_forward(B, T, Mi, sel_idx != nullptr, &ran))) return rc;
+  if (ran == CHAIN_WHOLE_FORWARD) return PG_OK;
+  // last layer with a selection: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
+  const EsmLayer& tail = esm_layers.back();
+  auto finish_selected = [&] { return pruned_tail(tail.out, tail.ffn, sel_idx, nullptr, P, T, n_sel, d_iter_, sel_gemm_rows(n_sel, round_up64(n_sel, kRowPad)), ln_in_gemm); };
+  if (ran == CHAIN_TO_LAST_ATTENTION) return finish_selected();
+  for (int l = 0; l < cfg.n_layers; ++l) {
     const EsmLayer& L = esm_layers[l];
-    // Hh holds LN1(x): written by the previous layer's fc2 launch (or the LayerNorm kernel) -- see resid_gemm_ln
-    if (attn_done) {
-      // q | k | v and the attention of this (last) layer were part of the persistent launch
-    } else if (ln_in_gemm) {
-      if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, X, d, L.ln1.g, L.ln1.b, eps, L.qkv.w, L.qkv.b, QKV, Mi, 3 * d, d, d, 3 * d, EPI_BF16); }))) return rc;
-    } else {
-      if ((rc = timed(PC_GEMM_QKV, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.qkv.w, L.qkv.b, QKV, Mi, 3 * d, d, d, d, 3 * d, EPI_BF16); }))) return rc;
-    }
-    if (!attn_done && (rc = rope(QKV, M, T))) return rc;                       // ESM-2 only: q and k rotated by their positions
-    if (!attn_done)
-      if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16, head_dim); }))) return rc;
+    // tile regime: Hh holds LN1(x), written by the previous layer's fc2 launch (or the LayerNorm kernel) -- see resid_gemm_ln
+    if ((rc = ln_in_gemm ? dense_ln(X, L.ln1, L.qkv, QKV, Mi, EPI_BF16) : dense(PC_GEMM_QKV, Hh, L.qkv, QKV, Mi, EPI_BF16))) return rc;
+    if ((rc = rope(QKV, M, T))) return rc;                                     // ESM-2 only: q and k rotated by their positions
+    if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16, head_dim); }))) return rc;
     const bool last = l == cfg.n_layers - 1;
-    // last layer: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
-    if (sel_idx && last) return pruned_tail(L.out, L.ffn, sel_idx, nullptr, P, T, n_sel, d_iter_, sel_gemm_rows(n_sel, round_up64(n_sel, kRowPad)), ln_in_gemm);
-    if (!ln_in_gemm) {
-      if ((rc = ffn_block(L.out, L.ffn, last ? nullptr : &esm_layers[l + 1].ln1, Mi, M))) return rc;
-      continue;
-    }
-    const FfnW& F = L.ffn;
-    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, CTX, L.out.w, L.out.b, X, Mi, d, d, d, d, d, EPI_F32_RESID); }))) return rc;
-    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_ln_skinny, stream, X, d, F.ln.g, F.ln.b, eps, F.fc1.w, F.fc1.b, FFN, Mi, f, d, d, f, EPI_BF16_GELU); }))) return rc;
-    if ((rc = timed(PC_GEMM, [&] { return OPS(launch_gemm_bf16, stream, FFN, F.fc2.w, F.fc2.b, X, Mi, d, f, f, f, d, EPI_F32_RESID, splitk_ws(Mi, d, f, batch_rows), splitk.bytes, (int)M); }))) return rc;
+    if (sel_idx && last) return finish_selected();
+    if ((rc = ffn_block(L.out, L.ffn, last ? nullptr : &esm_layers[l + 1].ln1, Mi, M, ln_in_gemm))) return rc;
   }
+  return PG_OK;
+}
+
+// A single short chain (<= 32 token rows): every layer in ONE persistent launch (chain_trunk.hip; same bits as the per-layer
+// launches of esm_trunk's folded regime, whose buffers it works on).  With stop_at_last_attention it ends after the last layer's
+// attention.  *ran stays CHAIN_NOT_RUN when the shape, a <pad> batch or this engine's state (no table, switched off) rule it out
+int Engine::chain_forward(int B, int T, int Mi, bool stop_at_last_attention, ChainRan* ran) {
+  const int d = cfg.d_model, f = cfg.d_ffn;
+  if (!(chain_layers && !chain_disabled && !esm_pad_in_batch && T <= 32 && (int64_t)B * T <= Mi && OPS(chain_trunk_ok, Mi, d, f, cfg.n_heads))) return PG_OK;
+  int rc;
+  if ((rc = chain_sync.ensure(OPS(chain_trunk_sync_bytes), stream)) || (rc = chain_part.ensure(OPS(chain_trunk_part_bytes, Mi, d), stream))) return rc;
+  PgChainTrunkArgs ca;
+  ca.layers = chain_layers; ca.n_layers = cfg.n_layers; ca.partial_last = stop_at_last_attention ? 1 : 0; ca.B = B; ca.T = T;
+  ca.x = x.as<float>(); ca.qkv = qkv.as<bf16_t>(); ca.ctx = ctx.as<bf16_t>(); ca.ffn = ffn.as<bf16_t>();
+  ca.part = chain_part.as<float>(); ca.sync = chain_sync.as<unsigned>();
+  ca.err = chain_err; ca.eps = cfg.layer_norm_eps;
+  rc = timed(PC_GEMM, [&] { return OPS(launch_chain_trunk, stream, ca, Mi, d); });
+  if (rc == kChainTrunkUnfit) {              // the grid cannot be co-resident on this device: per-layer launches, for good
+    chain_disabled = true;
+    return PG_OK;
+  }
+  if (rc) return rc;
+  // test hook: PGIBBS_CHAIN_TRUNK_FAULT=n makes the n-th persistent launch of the process report a barrier timeout
+  static const int fault_at = env_int("PGIBBS_CHAIN_TRUNK_FAULT", 0);
+  static int launches = 0;
+  if (fault_at > 0 && ++launches == fault_at) *chain_err = 1;
+  *ran = stop_at_last_attention ? CHAIN_TO_LAST_ATTENTION : CHAIN_WHOLE_FORWARD;
   return PG_OK;
 }
 
 // x[M_rows][d] += a[M_rows][K] W^T + b, then h = LayerNorm(x; ln) as the next GEMM's bf16 operand: the residual GEMM the dispatch
 // picks, followed by the LayerNorm kernel at its HBM roofline.  (Normalising inside the GEMM was built in round 3, bit-identical
 // and slower; it left the library in round 4: tools/probes/gemm_ln_fused.hip.)
-int Engine::resid_gemm_ln(const bf16_t* a, const DenseW& W, float* x, int M_rows, int64_t M_real, int lda, const LnW& ln, bf16_t* h,
-                          float* ws, size_t ws_bytes, int prof_class, int colmajor_R, int colmajor_C) {
+int Engine::resid_gemm_ln(int cls, const bf16_t* a, const DenseW& W, float* x, int M_rows, int64_t M_real, const LnW& ln, bf16_t* h,
+                          bool use_splitk, int colmajor_R, int colmajor_C) {
   const int d = W.N, K = W.K;
   // d_model = 768, K <= 1024 (ESM-MSA-1b's attention out-projections) on big batches: one launch whose tiles span whole rows and
   // normalise them in the epilogue (gemm_rowln.hip; same bits as the two launches below).  Opt-in through PGIBBS_ROWLN=1
   // (gemm_rowln_ok): measured slower, 1.34-1.37 ms per launch against 1.26-1.28 ms for the two launches it replaces
   static const int64_t rowln_min = env_int("PGIBBS_ROWLN_MIN_ROWS", 16384);
   if (!strict() && M_real >= rowln_min && M_real <= M_rows && OPS(gemm_rowln_ok, M_rows, d, K))
-    return timed(prof_class, [&] { return OPS(launch_gemm_rowln, stream, a, W.w, W.b, x, ln.g, ln.b, h, (int)M_real, M_rows, K, lda, K, cfg.layer_norm_eps, colmajor_R, colmajor_C); });
-  int rc = timed(prof_class, [&] { return OPS(launch_gemm_bf16, stream, a, W.w, W.b, x, M_rows, d, K, lda, K, d, EPI_F32_RESID, ws, ws_bytes, (int)M_real); });
-  if (rc) return rc;
-  return timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, x, ln.g, ln.b, h, M_real, d, cfg.layer_norm_eps, false, colmajor_R, colmajor_C); });
+    return timed(cls, [&] { return OPS(launch_gemm_rowln, stream, a, W.w, W.b, x, ln.g, ln.b, h, (int)M_real, M_rows, K, K, K, cfg.layer_norm_eps, colmajor_R, colmajor_C); });
+  const int rc = dense(cls, a, W, x, M_rows, EPI_F32_RESID, (int)M_real, use_splitk);
+  return rc ? rc : layer_norm(x, ln, h, M_real, true, colmajor_R, colmajor_C);
 }
 
 // LM head evaluated ONLY at the selected rows: emb_layer_norm_after -> dense -> GELU ->
@@ -727,9 +763,7 @@ int Engine::head(const int32_t* d_idx_, const int32_t* d_row_map, int P, int wid
     int r = OPS(launch_gather_ln_bf16, stream, x_src, d_idx_, d_row_map, P, width, ln_after.g, ln_after.b,
                                   sel_h.as<bf16_t>(), n_sel, d, eps);
     if (r) return r;
-    r = OPS(launch_gemm_bf16, stream, sel_h.as<bf16_t>(), head_dense.w, head_dense.b, sel_g.as<float>(),
-                         sel_gemm_rows(n_sel, Np), d, d, d, d, d, EPI_F32_GELU);
-    if (r) return r;
+    if ((r = dense(PC_NONE, sel_h.as<bf16_t>(), head_dense, sel_g.as<float>(), sel_gemm_rows(n_sel, Np), EPI_F32_GELU))) return r;
     return launch_lm_tail(stream, sel_g.as<float>(), head_ln.g, head_ln.b, embed, head_bias, d_logits, n_sel, d, V, eps);
   });
 }
@@ -777,15 +811,9 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
   // sequence (BASELINE config 1) captures once, not once per call.  Before a capture iteration 0 runs eagerly (it sizes every
   // workspace buffer: no allocation inside the capture).
   const bool graphable = use_graph && pruned && !prof.on && !d_samp_logits_ && !d_samp_tok_ && (int64_t)B * T <= 4096;
-  std::vector<uint8_t> key(2 * sizeof(int32_t) + 8 * sizeof(int64_t));
-  if (graphable) {
-    const int32_t flags[2] = {sp->mask, sp->mask_idx};      // baked into the captured launches (the scatter and its argument)
-    memcpy(key.data(), flags, sizeof(flags));
-    // job_items picks kernels (sel_gemm_rows, splitk_ws): a graph captured under another job size must not be replayed
-    const int64_t dims[8] = {(int64_t)(uintptr_t)d_tok, (int64_t)(uintptr_t)d_idx_, B, T, P, (int64_t)(uintptr_t)stream,
-                             (int64_t)(g_alloc_epoch * 2 + (esm_pad_in_batch ? 1 : 0)), job_items};
-    memcpy(key.data() + sizeof(flags), dims, sizeof(dims));
-  }
+  auto epoch_pad = [&] { return g_alloc_epoch * 2 + (esm_pad_in_batch ? 1 : 0); };
+  GraphKey key;
+  if (graphable) key = {sp->mask, sp->mask_idx, d_tok, d_idx_, B, T, P, stream, epoch_pad(), job_items};
   const bool reuse = graphable && graph_exec && key == graph_key;
   if (!graphable || (!reuse && n_iters < 3)) {
     for (int it = 0; it < n_iters; ++it)
@@ -797,10 +825,7 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
     if ((rc = d_iter.ensure(graph_state_bytes(), stream))) return rc;
     if ((rc = iteration(0, nullptr))) return rc;
     first = 1;
-    {   // a buffer grown by iteration 0 moved the epoch: the key must describe the state the graph is captured in
-      const int64_t ep = (int64_t)(g_alloc_epoch * 2 + (esm_pad_in_batch ? 1 : 0));
-      memcpy(key.data() + 2 * sizeof(int32_t) + 6 * sizeof(int64_t), &ep, sizeof(ep));
-    }
+    key.epoch_pad = epoch_pad();      // a buffer grown by iteration 0 moved the epoch: the key must describe the state the graph is captured in
     if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
     hipGraph_t graph = nullptr;
     PG_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
@@ -837,7 +862,6 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
   bf16_t* Hh = h.as<bf16_t>();
   bf16_t* QKV = qkv.as<bf16_t>();
   bf16_t* CTX = ctx.as<bf16_t>();
-  const float eps = cfg.layer_norm_eps;
   const int Mi = (int)Mp;
   const float row_scale = 0.125f / sqrtf((float)R);      // dh^-0.5 / sqrt(R): depends on R, applied to the scores
   // A batch that holds <pad> (a ragged list of MSAs padded to one tensor by the unmasked log_likelihood_batch, esm_msa_sampler.py:341,
@@ -851,39 +875,29 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
   if (strict()) {
     if ((rc = scores.ensure((size_t)B * H * C * msa_row_scores_ld(C) * 4, stream))) return rc;
     float* QKVf = qkv.as<float>();
-    rc = timed(PC_EMBED, [&] {
-      return OPS(launch_embed_ln, stream, d_tok, embed, pos, msa_pos, ln_before.g, ln_before.b, X, M, C, d, cfg.pad_idx,
-                             cfg.mask_idx, 0, R, eps);
-    });
-    if (rc) return rc;
+    if ((rc = embed_rows(d_tok, M, C, R, nullptr))) return rc;
     const SeqLayout colS = {C, R * C, 1, C};
-    for (int l = 0; l < cfg.n_layers; ++l) {
-      const MsaLayer& L = msa_layers[l];
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln_row.g, L.ln_row.b, Hh, M, d, eps, true, 0, 0, dense3_wants_dup(L.row_qkv, Mi)); }))) return rc;
-      if ((rc = dense3(Hh, L.row_qkv, QKVf, Mi, false))) return rc;
-      if ((rc = timed(PC_ATTN, [&] { return launch_msa_row_attention_f32(stream, QKVf, scores.as<float>(), CTX, dense3_wants_dup(L.row_out, Mi) ? d : -d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, row_scale, pad_tok, cfg.pad_idx); }))) return rc;
-      if ((rc = dense3(CTX, L.row_out, X, Mi, true))) return rc;
-      if ((rc = timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, X, L.ln_col.g, L.ln_col.b, Hh, M, d, eps, true, 0, 0, dense3_wants_dup(L.col_qkv, Mi)); }))) return rc;
-      if ((rc = dense3(Hh, L.col_qkv, QKVf, Mi, false))) return rc;
-      if ((rc = timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, CTX, dense3_wants_dup(L.col_out, Mi) ? d : -d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, colS, pad_tok, cfg.pad_idx); }))) return rc;
-      if ((rc = dense3(CTX, L.col_out, X, Mi, true))) return rc;
-      if ((rc = ffn_strict(L.ffn, Mi, M))) return rc;
+    for (const MsaLayer& L : msa_layers) {
+      rc = strict_attention(L.ln_row, L.row_qkv, L.row_out, Mi, M, [&](int split_d) {
+        return timed(PC_ATTN, [&] { return launch_msa_row_attention_f32(stream, QKVf, scores.as<float>(), CTX, split_d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, row_scale, pad_tok, cfg.pad_idx); });
+      });
+      if (rc) return rc;
+      rc = strict_attention(L.ln_col, L.col_qkv, L.col_out, Mi, M, [&](int split_d) {
+        return timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, CTX, split_d, (int64_t)B * C, R, H, 3 * d, 3 * d, d, 2 * d, colS, pad_tok, cfg.pad_idx); });
+      });
+      if (rc || (rc = ffn_strict(L.ffn, Mi, M))) return rc;
     }
     return PG_OK;
   }
 
   // embedding + emb_layer_norm_before, and in the same pass over the row the first layer's row-attention LayerNorm
-  rc = timed(PC_EMBED, [&] {
-    return OPS(launch_embed_ln, stream, d_tok, embed, pos, msa_pos, ln_before.g, ln_before.b, X, M, C, d, cfg.pad_idx,
-                           cfg.mask_idx, 0, R, eps, msa_layers[0].ln_row.g, msa_layers[0].ln_row.b, Hh);
-  });
-  if (rc) return rc;
+  if ((rc = embed_rows(d_tok, M, C, R, &msa_layers[0].ln_row))) return rc;
   const SeqLayout col = {C, R * C, 1, C};                   // column c of msa b: rows (b*R + r)*C + c
   // Hh always holds the LayerNorm the next projection reads: written by the embedding pass / the LayerNorm after a residual GEMM
   for (int l = 0; l < cfg.n_layers; ++l) {
     const MsaLayer& L = msa_layers[l];
     // tied row attention
-    if ((rc = timed(PC_GEMM_QKV, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.row_qkv.w, L.row_qkv.b, QKV, Mi, 3 * d, d, d, d, 3 * d, EPI_BF16); }))) return rc;
+    if ((rc = dense(PC_GEMM_QKV, Hh, L.row_qkv, QKV, Mi, EPI_BF16))) return rc;
     if (C <= 576 && !pad_tok) {
       float* part = nullptr;
       // few workgroups: give the kernel scratch for its split-R mode (decided on the job's batch: the split changes the
@@ -913,12 +927,12 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
     // column block: fused QKV projection + attention when the depth allows (gemm_colattn.hip: the LayerNorm writes its rows in
     // column-major token order, q / k / v never leave the CU; bit-identical context), else projection + attention kernel
     const bool col_fused = !pad_tok && colattn_ok(R, d, H) && L.col_qkv_hm.w;
-    if ((rc = resid_gemm_ln(CTX, L.row_out, X, Mi, M, d, L.ln_col, Hh, nullptr, 0, PC_GEMM_OUT, col_fused ? R : 0, col_fused ? C : 0))) return rc;   // x += row_out(ctx); h = LN_col(x)
+    if ((rc = resid_gemm_ln(PC_GEMM_OUT, CTX, L.row_out, X, Mi, M, L.ln_col, Hh, false, col_fused ? R : 0, col_fused ? C : 0))) return rc;   // x += row_out(ctx); h = LN_col(x)
     if (col_fused) {
       if ((rc = timed(PC_GEMM_QKV, [&] { return OPS(launch_gemm_colattn, stream, Hh, L.col_qkv_hm.w, L.col_qkv_hm.b, CTX, B, R, C, H, d, d); }))) return rc;
     } else {
       // column attention (q pre-scaled by dh^-0.5 in the weights)
-      if ((rc = timed(PC_GEMM_QKV, [&] { return OPS(launch_gemm_bf16, stream, Hh, L.col_qkv.w, L.col_qkv.b, QKV, Mi, 3 * d, d, d, d, 3 * d, EPI_BF16); }))) return rc;
+      if ((rc = dense(PC_GEMM_QKV, Hh, L.col_qkv, QKV, Mi, EPI_BF16))) return rc;
       if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_seq_bf16, stream, QKV, CTX, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col, pad_tok, cfg.pad_idx, nullptr); }))) return rc;
     }
     const bool last = l == cfg.n_layers - 1;
