@@ -87,7 +87,8 @@ typedef struct pg_engine pg_engine;
                            esm2_t48_15B_UR50D: heads of 128, at most 40 of them = d_model <= 5120 (a multiple of 512 above 2560), this
                            architecture only;
                            esm2_t6_8M_UR50D: heads of 16, at most 32 of them = d_model <= 512, this architecture only (d_model 320);
-                           pg_engine_create answers PG_ERR_INVALID for any other head width or a wider model).  The ESM-1b block
+                           pg_engine_create answers PG_ERR_INVALID for any other head width or a wider model;
+                           esm2_t12_35M_UR50D, heads of 24, runs through pg_engine_create_embedded below).  The ESM-1b block
                            stack, token dropout, emb_layer_norm_after and tied RoBERTa LM head, with three differences: no position
                            table (`embed_positions.weight` is neither required nor read) -- positions enter through ROTARY embeddings
                            applied to q and k of every attention layer ("rotate-half" pairs (i, i + 32) of each 64-wide head, angle
@@ -144,6 +145,19 @@ typedef struct {
 
 int pg_engine_create(const pg_model_config* cfg, const pg_tensor* tensors, int n_tensors, int device_ordinal,
                      int precision, pg_engine** out);
+/* An EMBEDDED model: a PG_ARCH_ESM2 model whose head width no kernel is built for (esm2_t12_35M_UR50D: d_model 480, 20 heads of 24),
+ * run with every head in a slot of a built width, head_slot (32 for heads of 24).  cfg carries the model's OWN sizes (480 / 20 / 1920)
+ * and the tensors are its natural fair-esm ones.  The engine runs the shape d_model = n_heads * head_slot (640: the kernels of
+ * esm2_t30_150M_UR50D) on zero-padded weights: residual-stream feature c stays column c, columns d_model .. of every row stay 0;
+ * feature j of head h goes to column h * head_slot + j for j < width / 2 and to h * head_slot + j + (head_slot - width) / 2 above, so
+ * that rotate-half partners stay half a slot apart; q is scaled by float(width^-0.5); the rotary table carries the frequencies of a
+ * head of `width` (cos 1, sin 0 in the pad columns).  A zero-padded transformer computes the same function except in LayerNorm, whose
+ * kernels normalise over the live features and write zeros behind them.  Refused with PG_ERR_INVALID, in this order: an architecture
+ * other than PG_ARCH_ESM2; a slot that is no built head width; a width that is not a multiple of 4 or not smaller than the slot; more
+ * heads than the slot's width allows per row; then pg_engine_create's own rules on the run shape.  Every entry point, precision mode and
+ * knob works on such an engine as on any other.  pg_engine_create itself keeps refusing such a configuration. */
+int pg_engine_create_embedded(const pg_model_config* cfg, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal,
+                              int precision, pg_engine** out);
 void pg_engine_destroy(pg_engine*);
 /* run on a caller-provided hipStream_t (NULL = the engine's own stream) */
 int pg_engine_set_stream(pg_engine*, void* hip_stream);
@@ -435,7 +449,8 @@ int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx
  * so whatever the kernel leaves unwritten comes back holding the caller's pattern. */
 /* embed_ln_kernel: tokens[n_seq][T] (each in 0 .. V-1), embed[V][d] -> x[n_seq*T][d] fp32.  pos (NULL: no position table, ESM-2) has
  * pos_rows rows; msa_pos (rows_per_msa > 0) has rows_per_msa rows; gamma / beta (both or neither): emb_layer_norm_before; gamma2 /
- * beta2 / h2 (all or none): the first layer's LayerNorm of x as operand rows h2[n_seq*T][d] */
+ * beta2 / h2 (all or none): the first layer's LayerNorm of x as operand rows h2[n_seq*T][d]; h2 is _inout like the other 16-bit row
+ * buffers: copied to the device before the launch (the kernel writes every row of it) */
 int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
                  int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
                  const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2);
@@ -467,6 +482,32 @@ int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_r
  * ESM-1); V <= 64.  *small_kernel (may be NULL): 1 = the workgroup-per-row kernel ran (n <= PGIBBS_LM_TAIL_SMALL, default 1024) */
 int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
                    float* logits, int64_t n, int d, int V, float eps, int* small_kernel);
+
+/* ---- the live-width forms of pg_dbg_embed, pg_dbg_layernorm_rows, pg_dbg_gather_ln and pg_dbg_lm_tail (an embedded model's rows) ----
+ * Every table, row and vector is d wide in memory; its first d_live features (a multiple of 4, at most d) are the model's own.
+ * Statistics, affine and the decoder's dot products run over d_live features -- on them, bit for bit what the same entry gives for
+ * rows of d = d_live -- and the d - d_live pad features of every 16-bit output row are written as zeros, in the split forms too.
+ * d_live = d is the entry above; each entry names itself in its error messages.  No live form: emb_layer_norm_before (gamma / beta of pg_dbg_embed), column-major rows, the stride kernel */
+int pg_embedded_embed_rows(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d,
+                           const float* pos, int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta,
+                           const float* gamma2, const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale,
+                           float* x, uint16_t* h2, int d_live);
+int pg_embedded_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                               int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel, int d_live);
+int pg_embedded_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                          int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                          float eps, int split, int d_live);
+int pg_embedded_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                        float* logits, int64_t n, int d, int V, float eps, int* small_kernel, int d_live);
+/* Host only (no device is looked for): the run-shape image pg_engine_create_embedded uploads for the natural tensor `name` (its role is
+ * read from the fair-esm key: embed_tokens.weight, layers.i.self_attn.{q,k,v,out}_proj.*, layers.i.fc1.* / fc2.*, every *layer_norm*,
+ * lm_head.dense.*, lm_head.bias) of a model of n_heads heads of head_width in slots of head_slot: live values at their run positions,
+ * 0.0 everywhere else.  numel / image_numel must be the natural and the run size */
+int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
+                      float* image, int64_t image_numel);
+/* Host only: the rotary table [rows][head_slot] of such an engine: row t = [cos(t f_i), i < head_width / 2, then 1 ... | sin(t f_i),
+ * then 0 ...], f_i = 10000^(-2i / head_width) as fp32 (head_width == head_slot: the table of a built width) */
+int pg_embedded_rope_table(int rows, int head_width, int head_slot, float* table);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,7 @@ SIGNATURES = [
     ("pg_pyrandom_shuffle", c_int, [c_void_p, _P32, c_int]),
     ("pg_pyrandom_choices", c_int, [c_void_p, c_int, c_int, _P32]),
     ("pg_engine_create", c_int, [POINTER(ModelConfig), POINTER(Tensor), c_int, c_int, c_int, POINTER(c_void_p)]),
+    ("pg_engine_create_embedded", c_int, [POINTER(ModelConfig), c_int, POINTER(Tensor), c_int, c_int, c_int, POINTER(c_void_p)]),
     ("pg_engine_destroy", None, [c_void_p]),
     ("pg_engine_set_stream", c_int, [c_void_p, c_void_p]),
     ("pg_engine_synchronize", c_int, [c_void_p]),
@@ -148,6 +149,18 @@ SIGNATURES = [
     ("pg_dbg_split_rows", c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p]),
     ("pg_dbg_lm_tail", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
                                POINTER(c_int)]),
+    # embedded models (pg_engine_create_embedded): the live-width forms of pg_dbg_embed / _layernorm_rows / _gather_ln / _lm_tail, and
+    # the two host-only entries
+    ("pg_embedded_embed_rows", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int]),
+    ("pg_embedded_layernorm_rows", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_int,
+                                           c_int, POINTER(c_int), c_int]),
+    ("pg_embedded_gather_ln", c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_int64, c_int, c_float, c_int, c_int]),
+    ("pg_embedded_lm_tail", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
+                                    POINTER(c_int), c_int]),
+    ("pg_embedded_image", c_int, [c_char_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64]),
+    ("pg_embedded_rope_table", c_int, [c_int, c_int, c_int, c_void_p]),
 ]
 
 

@@ -158,6 +158,25 @@ int pg_engine_create(const pg_model_config* cfg, const pg_tensor* tensors, int n
   return PG_OK;
 }
 
+int pg_engine_create_embedded(const pg_model_config* cfg, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal,
+                              int precision, pg_engine** out) {
+  if (!cfg || !out || (n_tensors > 0 && !tensors)) return fail(PG_ERR_INVALID, "pg_engine_create_embedded: null argument");
+  *out = nullptr;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  pg_engine* h = new pg_engine;
+  int rc = h->e.init_embedded(cfg, head_slot, tensors, n_tensors, device_ordinal, precision);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  if (rc != PG_OK) {
+    std::string keep = pg_last_error();
+    delete h;
+    set_error(keep);
+    return rc;
+  }
+  *out = h;
+  return PG_OK;
+}
+
 void pg_engine_destroy(pg_engine* h) { delete h; }
 
 int pg_engine_set_stream(pg_engine* h, void* hip_stream) {

@@ -582,9 +582,10 @@ int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx
 // PG_ERR_INVALID with a message, never a GPU fault, and the refusals can be tested without a GPU.
 extern "C++" {
 namespace {
-int dbg_row_width(const char* who, int d) {
+int dbg_row_width(const char* who, int d, int d_live) {
   if (!row_d_ok(d)) return
     fail(PG_ERR_INVALID, std::string(who) + ": d must be a multiple of 4 and <= 2560, or a multiple of 512 up to 5120");
+  if (!row_live_ok(d, d_live)) return fail(PG_ERR_INVALID, std::string(who) + ": the live width must be a multiple of 4, at most d");
   return PG_OK;
 }
 // the token row a gather reads for selected row r (what gather_ln_bf16_kernel / gather_rows_kernel compute), -1 = none (zeros);
@@ -609,26 +610,31 @@ const char* const kCopyFailed = "hipMalloc / copy failed";
 }  // namespace
 }  // extern "C++"
 
-int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
-                 int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
-                 const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2) {
-  int rc = dbg_precision("pg_dbg_embed", precision, false);
+/* The live-width forms (pgibbs.h; the pg_dbg_* entries are these at d_live = d): rows d wide in memory whose first d_live features are
+ * the model's own.  Tables, rows and vectors are all d wide; h2 / h_inout come back with the caller's pattern wherever the kernel
+ * wrote nothing */
+static int dbg_embed_rows(const char* who, int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d,
+                           const float* pos, int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta,
+                           const float* gamma2, const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale,
+                           float* x, uint16_t* h2, int d_live) {
+  int rc = dbg_precision(who, precision, false);
   if (rc) return rc;
   if (!tokens || !embed || !x || n_seq < 1 || T < 1 || V < 1 || (pos && pos_rows < 1) || rows_per_msa < 0 || (rows_per_msa > 0 && !msa_pos) ||
       !gamma != !beta || !gamma2 != !beta2 || !gamma2 != !h2)
-    return fail(PG_ERR_INVALID, "pg_dbg_embed: bad argument");
-  if ((rc = dbg_row_width("pg_dbg_embed", d))) return rc;
+    return fail(PG_ERR_INVALID, std::string(who) + ": bad argument");
+  if ((rc = dbg_row_width(who, d, d_live))) return rc;
+  if (d_live != d && gamma) return fail(PG_ERR_INVALID, std::string(who) + ": emb_layer_norm_before has no live-width form");
   const int64_t n_tok = (int64_t)n_seq * T;
   for (int64_t sq = 0; sq < n_seq; ++sq) {
     int n_before = 0;
     for (int t = 0; t < T; ++t) {
       const int32_t tok = tokens[sq * T + t];
       if (tok < 0 || tok >= V)
-        return fail(PG_ERR_INVALID, "pg_dbg_embed: token " + std::to_string(tok) + " is outside the embedding table of " + std::to_string(V) + " rows");
+        return fail(PG_ERR_INVALID, std::string(who) + ": token " + std::to_string(tok) + " is outside the embedding table of " + std::to_string(V) + " rows");
       n_before += tok != pad_idx;
       const int p = tok == pad_idx ? pad_idx : n_before + pad_idx;      // embed_ln_kernel's position row
       if (pos && (p < 0 || p >= pos_rows))
-        return fail(PG_ERR_INVALID, "pg_dbg_embed: position row " + std::to_string(p) + " is outside the position table of " + std::to_string(pos_rows) + " rows");
+        return fail(PG_ERR_INVALID, std::string(who) + ": position row " + std::to_string(p) + " is outside the position table of " + std::to_string(pos_rows) + " rows");
     }
   }
   Dbg s;
@@ -642,24 +648,39 @@ int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, in
   const float* dg2 = s.up(gamma2, (size_t)d);
   const float* db2 = s.up(beta2, (size_t)d);
   float* dx = s.alloc<float>((size_t)n_tok * d);
-  bf16_t* dh = h2 ? s.alloc<bf16_t>((size_t)n_tok * d) : nullptr;
+  bf16_t* dh = h2 ? s.up((const bf16_t*)h2, (size_t)n_tok * d) : nullptr;      // the caller's pattern
   if ((rc = s.check(kCopyFailed))) return rc;
   if ((rc = OPS(launch_embed_ln, nullptr, dtok, de, dp, dm, dg, db, dx, n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, dg2,
-                db2, dh, embed_scale)))
+                db2, dh, embed_scale, d_live)))
     return rc;
   if ((rc = s.down(x, dx, (size_t)n_tok * d))) return rc;
   return h2 ? s.down(h2, dh, (size_t)n_tok * d) : PG_OK;
 }
 
-int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
-                          int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel) {
-  int rc = dbg_precision("pg_dbg_layernorm_rows", precision, false);
+int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
+                 int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
+                 const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2) {
+  return dbg_embed_rows("pg_dbg_embed", device, precision, tokens, n_seq, T, embed, V, d, pos, pos_rows, msa_pos, rows_per_msa, gamma, beta, gamma2, beta2,
+                                pad_idx, mask_idx, token_dropout, eps, embed_scale, x, h2, d);
+}
+
+int pg_embedded_embed_rows(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d,
+                           const float* pos, int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta,
+                           const float* gamma2, const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale,
+                           float* x, uint16_t* h2, int d_live) {
+  return dbg_embed_rows("pg_embedded_embed_rows", device, precision, tokens, n_seq, T, embed, V, d, pos, pos_rows, msa_pos, rows_per_msa, gamma, beta, gamma2, beta2, pad_idx, mask_idx, token_dropout, eps, embed_scale, x, h2, d_live);
+}
+
+static int dbg_layernorm_rows(const char* who, int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                               int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel, int d_live) {
+  int rc = dbg_precision(who, precision, false);
   if (rc) return rc;
   if (!x || !gamma || !beta || !h_inout || M < 1 || h_rows < M || form < 0 || form > 2 || colmajor_R < 0 || (colmajor_R > 0 && colmajor_C < 1))
-    return fail(PG_ERR_INVALID, "pg_dbg_layernorm_rows: bad argument");
+    return fail(PG_ERR_INVALID, std::string(who) + ": bad argument");
   if (form && (precision != PG_PREC_BF16 || d % 32))
-    return fail(PG_ERR_INVALID, "pg_dbg_layernorm_rows: split rows are bf16 pairs in groups of 32 columns");
-  if ((rc = OPS(layernorm_bf16_check, M, d, form != 0, colmajor_R, colmajor_C))) return rc;
+    return fail(PG_ERR_INVALID, std::string(who) + ": split rows are bf16 pairs in groups of 32 columns");
+  if (row_d_ok(d) && !row_live_ok(d, d_live)) return fail(PG_ERR_INVALID, std::string(who) + ": the live width must be a multiple of 4, at most d");
+  if ((rc = OPS(layernorm_bf16_check, M, d, form != 0, colmajor_R, colmajor_C, d_live))) return rc;
   Dbg s;
   if ((rc = s.open(device))) return rc;
   const size_t h_n = (size_t)h_rows * d * (form ? 3 : 1);
@@ -669,27 +690,37 @@ int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float
   bf16_t* dh = s.up(h_inout, h_n);      // the caller's pattern: what the kernel leaves unwritten keeps it
   if ((rc = s.check(kCopyFailed))) return rc;
   unsigned stride_grid = 0;
-  if (kernel) *kernel = OPS(layernorm_bf16_choice, M, d, colmajor_R, &stride_grid);
-  if ((rc = OPS(launch_layernorm_bf16, nullptr, dx, dg, db, dh, M, d, eps, form != 0, colmajor_R, colmajor_C, form != 2))) return rc;
+  if (kernel) *kernel = OPS(layernorm_bf16_choice, M, d, colmajor_R, &stride_grid, d_live);
+  if ((rc = OPS(launch_layernorm_bf16, nullptr, dx, dg, db, dh, M, d, eps, form != 0, colmajor_R, colmajor_C, form != 2, d_live))) return rc;
   return s.down(h_inout, dh, h_n);
 }
 
-int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
-                     int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
-                     float eps, int split) {
-  int rc = dbg_precision("pg_dbg_gather_ln", precision, false);
+int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                          int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel) {
+  return dbg_layernorm_rows("pg_dbg_layernorm_rows", device, precision, x, gamma, beta, h_inout, h_rows, M, d, eps, form, colmajor_R, colmajor_C, kernel, d);
+}
+
+int pg_embedded_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+                               int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel, int d_live) {
+  return dbg_layernorm_rows("pg_embedded_layernorm_rows", device, precision, x, gamma, beta, h_inout, h_rows, M, d, eps, form, colmajor_R, colmajor_C, kernel, d_live);
+}
+
+static int dbg_gather_ln_rows(const char* who, int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                          int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                          float eps, int split, int d_live) {
+  int rc = dbg_precision(who, precision, false);
   if (rc) return rc;
   if (!x || !gamma || !beta || !h_inout || x_rows < 1 || n_sel < 1 || h_rows < n_sel || P < 1 || width < 1 || (row_map && n_map < 1) ||
       split < 0 || split > 1)
-    return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: bad argument");
-  if ((rc = dbg_row_width("pg_dbg_gather_ln", d))) return rc;
+    return fail(PG_ERR_INVALID, std::string(who) + ": bad argument");
+  if ((rc = dbg_row_width(who, d, d_live))) return rc;
   if (split && (precision != PG_PREC_BF16 || d % 32))
-    return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: split rows are bf16 pairs in groups of 32 columns");
+    return fail(PG_ERR_INVALID, std::string(who) + ": split rows are bf16 pairs in groups of 32 columns");
   if (!idx) {      // identity: selected row r = token row r
-    if (n_sel > x_rows) return fail(PG_ERR_INVALID, "pg_dbg_gather_ln: more selected rows than source rows");
+    if (n_sel > x_rows) return fail(PG_ERR_INVALID, std::string(who) + ": more selected rows than source rows");
   } else {
     for (int64_t r = 0; r < n_sel; ++r)
-      if (dbg_gather_src("pg_dbg_gather_ln", r, idx[r], true, row_map, n_map, P, width, x_rows) == -2) return PG_ERR_INVALID;
+      if (dbg_gather_src(who, r, idx[r], true, row_map, n_map, P, width, x_rows) == -2) return PG_ERR_INVALID;
   }
   Dbg s;
   if ((rc = s.open(device))) return rc;
@@ -701,8 +732,20 @@ int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, 
   const float* db = s.up(beta, (size_t)d);
   bf16_t* dh = s.up(h_inout, h_n);
   if ((rc = s.check(kCopyFailed))) return rc;
-  if ((rc = OPS(launch_gather_ln_bf16, nullptr, dx, di, dm, P, width, dg, db, dh, n_sel, d, eps, split != 0))) return rc;
+  if ((rc = OPS(launch_gather_ln_bf16, nullptr, dx, di, dm, P, width, dg, db, dh, n_sel, d, eps, split != 0, d_live))) return rc;
   return s.down(h_inout, dh, h_n);
+}
+
+int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                     int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                     float eps, int split) {
+  return dbg_gather_ln_rows("pg_dbg_gather_ln", device, precision, x, x_rows, idx, row_map, n_map, P, width, gamma, beta, h_inout, h_rows, n_sel, d, eps, split, d);
+}
+
+int pg_embedded_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+                          int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
+                          float eps, int split, int d_live) {
+  return dbg_gather_ln_rows("pg_embedded_gather_ln", device, precision, x, x_rows, idx, row_map, n_map, P, width, gamma, beta, h_inout, h_rows, n_sel, d, eps, split, d_live);
 }
 
 int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
@@ -749,11 +792,11 @@ int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_r
   return s.down(gelu_out, dx, (size_t)rows * K);
 }
 
-int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
-                   float* logits, int64_t n, int d, int V, float eps, int* small_kernel) {
-  if (!g || !embed || !out_bias || !logits || n < 1 || !gamma != !beta) return fail(PG_ERR_INVALID, "pg_dbg_lm_tail: bad argument");
-  if (V < 1 || V > 64) return fail(PG_ERR_INVALID, "pg_dbg_lm_tail: vocab must be in 1..64");
-  int rc = dbg_row_width("pg_dbg_lm_tail", d);
+static int dbg_lm_tail_rows(const char* who, int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                        float* logits, int64_t n, int d, int V, float eps, int* small_kernel, int d_live) {
+  if (!g || !embed || !out_bias || !logits || n < 1 || !gamma != !beta) return fail(PG_ERR_INVALID, std::string(who) + ": bad argument");
+  if (V < 1 || V > 64) return fail(PG_ERR_INVALID, std::string(who) + ": vocab must be in 1..64");
+  int rc = dbg_row_width(who, d, d_live);
   if (rc) return rc;
   Dbg s;
   if ((rc = s.open(device))) return rc;
@@ -765,8 +808,43 @@ int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* 
   float* dl = s.up(logits, (size_t)n * V);      // the caller's pattern
   if ((rc = s.check(kCopyFailed))) return rc;
   if (small_kernel) *small_kernel = lm_tail_small(n, d) ? 1 : 0;
-  if ((rc = launch_lm_tail(nullptr, dg, dga, dbe, de, dob, dl, n, d, V, eps))) return rc;
+  if ((rc = launch_lm_tail(nullptr, dg, dga, dbe, de, dob, dl, n, d, V, eps, d_live))) return rc;
   return s.down(logits, dl, (size_t)n * V);
+}
+
+int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                   float* logits, int64_t n, int d, int V, float eps, int* small_kernel) {
+  return dbg_lm_tail_rows("pg_dbg_lm_tail", device, g, gamma, beta, embed, out_bias, logits, n, d, V, eps, small_kernel, d);
+}
+
+int pg_embedded_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+                        float* logits, int64_t n, int d, int V, float eps, int* small_kernel, int d_live) {
+  return dbg_lm_tail_rows("pg_embedded_lm_tail", device, g, gamma, beta, embed, out_bias, logits, n, d, V, eps, small_kernel, d_live);
+}
+
+/* ---- embedded models: the host side of pg_engine_create_embedded, no device ---- */
+int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
+                      float* image, int64_t image_numel) {
+  if (!name || !src || !image || n_heads < 1 || d_ffn < 1 || vocab < 1 || head_width < 2 || head_width % 2 || head_slot <= head_width || head_slot % 2)
+    return fail(PG_ERR_INVALID, "pg_embedded_image: bad argument");
+  const EmbedShape es = {n_heads, head_width, head_slot, d_ffn, vocab};
+  int64_t r = 0, c = 0;
+  if (!embedded_image(name, es, nullptr, &r, &c, nullptr)) return fail(PG_ERR_INVALID, std::string("pg_embedded_image: '") + name + "' is not a tensor of an ESM-2 model");
+  if (numel != r * c) return fail(PG_ERR_INVALID, std::string("tensor '") + name + "' has " + std::to_string(numel) + " elements, expected " + std::to_string(r * c));
+  std::vector<float> img;
+  embedded_image(name, es, src, &r, &c, &img);
+  if ((int64_t)img.size() != image_numel)
+    return fail(PG_ERR_INVALID, std::string("pg_embedded_image: the image of '") + name + "' has " + std::to_string(img.size()) + " elements");
+  memcpy(image, img.data(), img.size() * 4);
+  return PG_OK;
+}
+
+int pg_embedded_rope_table(int rows, int head_width, int head_slot, float* table) {
+  if (!table || rows < 1 || head_width < 2 || head_width % 2 || head_slot < head_width || head_slot % 2)
+    return fail(PG_ERR_INVALID, "pg_embedded_rope_table: bad argument");
+  const std::vector<float> tab = rope_table(rows, head_slot, head_width == head_slot ? 0 : head_width);
+  memcpy(table, tab.data(), tab.size() * 4);
+  return PG_OK;
 }
 
 }  // extern "C"

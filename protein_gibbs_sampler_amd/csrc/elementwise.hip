@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
                                                       float* __restrict__ x, int64_t n_tok, int T, int d, int pad_idx,
                                                       int mask_idx, int token_dropout, int rows_per_msa, float eps,
                                                       const float* __restrict__ gamma2, const float* __restrict__ beta2,
-                                                      bf16_t* __restrict__ h2, float embed_scale) {
+                                                      bf16_t* __restrict__ h2, float embed_scale, int d_live) {
   const int lane = threadIdx.x & 63;
   const int64_t row = wave_row();
   if (row >= n_tok) return;
@@ -99,8 +99,10 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
       o[lane + 64 * i] = v[i];
     }
   if (h2) {      // the first layer's LayerNorm on the row just written (same values, same code as layernorm_bf16_kernel: same bits)
-    ln_inplace(v, nch4, lane, d, eps, gamma2, beta2);
-    store_row_bf16(h2 + (size_t)row * d, v, nch4, lane);
+    const int nl4 = d_live >> 2;      // an embedded model (ln_row.h): over the live features, zeros behind them
+    ln_inplace(v, nl4, lane, d_live, eps, gamma2, beta2);
+    store_row_bf16(h2 + (size_t)row * d, v, nl4, lane);
+    zero_row_pad_bf16(h2 + (size_t)row * d, nl4, nch4, lane);
   }
 }
 
@@ -108,15 +110,17 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
 template <int NCH>
 __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, bf16_t* __restrict__ h,
-                                                            int split3, int64_t M, int d, float eps) {
+                                                            int split3, int64_t M, int d, float eps, int d_live) {
   const int lane = threadIdx.x & 63;
   const int64_t row = wave_row();
   if (row >= M) return;
-  const int nch4 = d >> 2;
+  const int nch4 = d >> 2, nl4 = d_live >> 2;      // d_live < d: an embedded model's row (ln_row.h)
   float4 v[NCH];
-  load_row(v, x + (size_t)row * d, nch4, lane);
-  ln_inplace(v, nch4, lane, d, eps, gamma, beta);
-  store_row_bf16(h + (size_t)row * d * (split3 ? 3 : 1), v, nch4, lane, split3, split3 != 2);       // split3 == 2: no duplicate hi block
+  load_row(v, x + (size_t)row * d, nl4, lane);
+  ln_inplace(v, nl4, lane, d_live, eps, gamma, beta);
+  bf16_t* o = h + (size_t)row * d * (split3 ? 3 : 1);
+  store_row_bf16(o, v, nl4, lane, split3, split3 != 2);       // split3 == 2: no duplicate hi block
+  zero_row_pad_bf16(o, nl4, nch4, lane, split3, split3 != 2);
 }
 
 // Mid-size batches (a 32 ... 128-chain shard of a multi-GPU job: 8 k ... 33 k token rows): with one row per wave the grid is 1.03 ...
@@ -173,18 +177,19 @@ __global__ __launch_bounds__(256) void layernorm_bf16_colmajor_kernel(const floa
 template <int NCH>
 __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ y,
-                                                           int64_t M, int d, float eps) {
+                                                           int64_t M, int d, float eps, int d_live) {
   const int lane = threadIdx.x & 63;
   const int64_t row = wave_row();
   if (row >= M) return;
-  const int nch4 = d >> 2;
+  const int nch4 = d >> 2, nl4 = d_live >> 2;
   float4 v[NCH];
-  load_row(v, x + (size_t)row * d, nch4, lane);
-  ln_inplace(v, nch4, lane, d, eps, gamma, beta);
+  load_row(v, x + (size_t)row * d, nl4, lane);
+  ln_inplace(v, nl4, lane, d_live, eps, gamma, beta);
   float4* o = (float4*)(y + (size_t)row * d);
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
-    if (lane + 64 * i < nch4) o[lane + 64 * i] = v[i];
+    if (lane + 64 * i < nl4) o[lane + 64 * i] = v[i];
+  for (int ci = nl4 + lane; ci < nch4; ci += 64) o[ci] = make_float4(0.f, 0.f, 0.f, 0.f);      // an embedded model's pad features
 }
 
 // ---- gather the sampled rows + final LayerNorm -> bf16 (LM-head dense operand) ---------------
@@ -194,11 +199,12 @@ template <int NCH>
 __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __restrict__ x, const int32_t* __restrict__ idx,
                                                             const int32_t* __restrict__ row_map, int P, int width,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            bf16_t* __restrict__ h, int split3, int64_t n_sel, int d, float eps) {
+                                                            bf16_t* __restrict__ h, int split3, int64_t n_sel, int d, float eps,
+                                                            int d_live) {
   const int lane = threadIdx.x & 63;
   const int64_t r = wave_row();
   if (r >= n_sel) return;
-  const int nch4 = d >> 2;
+  const int nch4 = d >> 2, nl4 = d_live >> 2;
   int pos = idx ? idx[r] : 0;
   float4 v[NCH];
   if (pos < 0 || (idx && (pos & 0x3fffffff) >= width)) {
@@ -213,10 +219,12 @@ __global__ __launch_bounds__(256) void gather_ln_bf16_kernel(const float* __rest
     } else {
       src = r;
     }
-    load_row(v, x + (size_t)src * d, nch4, lane);
-    ln_inplace(v, nch4, lane, d, eps, gamma, beta);
+    load_row(v, x + (size_t)src * d, nl4, lane);
+    ln_inplace(v, nl4, lane, d_live, eps, gamma, beta);
   }
-  store_row_bf16(h + (size_t)r * d * (split3 ? 3 : 1), v, nch4, lane, split3);
+  bf16_t* o = h + (size_t)r * d * (split3 ? 3 : 1);
+  store_row_bf16(o, v, nl4, lane, split3);
+  zero_row_pad_bf16(o, nl4, nch4, lane, split3);
 }
 
 // ---- plain row gathers (last-layer pruning: only the sampled rows go through out-proj / FFN of the final layer) ----
@@ -242,14 +250,15 @@ template <int NCH>
 __global__ __launch_bounds__(256) void lm_tail_kernel(const float* __restrict__ g, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, const float* __restrict__ embed,
                                                      const float* __restrict__ out_bias, float* __restrict__ logits,
-                                                     int64_t n, int d, int V, float eps) {
+                                                     int64_t n, int d, int V, float eps, int d_live) {
   const int lane = threadIdx.x & 63;
   const int64_t r = wave_row();
   if (r >= n) return;
-  const int nch4 = d >> 2;
+  // rows of g and of the decoder are d apart; the LayerNorm and the dot products run over the d_live live features (ln_row.h)
+  const int nch4 = d_live >> 2;
   float4 v[NCH];
   load_row(v, g + (size_t)r * d, nch4, lane);
-  if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);      // gamma == nullptr: ESM-1's head has no LayerNorm
+  if (gamma) ln_inplace(v, nch4, lane, d_live, eps, gamma, beta);      // gamma == nullptr: ESM-1's head has no LayerNorm
   float mine = 0.f;  // lane t keeps logit t (V <= 64)
   // four decoder rows per trip: their loads are all in flight before the first reduction (one row per trip was a chain
   // of V dependent L2 round trips: 81 us for a handful of rows)
@@ -284,13 +293,13 @@ template <int NCH>
 __global__ __launch_bounds__(1024) void lm_tail_small_kernel(const float* __restrict__ g, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const float* __restrict__ embed,
                                                             const float* __restrict__ out_bias, float* __restrict__ logits,
-                                                            int d, int V, float eps) {
+                                                            int d, int V, float eps, int d_live) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t r = blockIdx.x;
-  const int nch4 = d >> 2;
+  const int nch4 = d_live >> 2;      // as lm_tail_kernel: strides of d, arithmetic over d_live
   float4 v[NCH];
   load_row(v, g + (size_t)r * d, nch4, lane);
-  if (gamma) ln_inplace(v, nch4, lane, d, eps, gamma, beta);
+  if (gamma) ln_inplace(v, nch4, lane, d_live, eps, gamma, beta);
   float s[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
@@ -374,9 +383,12 @@ static inline void by_row_width(int d, F&& f) {
 }
 // A row launcher's admission of (d, rows) under the kernel's name `who`.  false: the launcher returns *rc -- 1, refused with the
 // error set, or 0, no rows and nothing to do
-static bool rows_go(const char* who, int d, int64_t rows, int* rc) {
+// d_live (0 = d): the live width of an embedded model's rows (ln_row.h); resolved in place
+static bool rows_go(const char* who, int d, int64_t rows, int* rc, int* d_live = nullptr) {
   *rc = 0;
+  if (d_live && *d_live == 0) *d_live = d;
   if (!row_d_ok(d)) *rc = fail(1, std::string(who) + ": d must be a multiple of 4 and <= 2560, or a multiple of 512 up to 5120");
+  else if (d_live && !row_live_ok(d, *d_live)) *rc = fail(1, std::string(who) + ": the live width must be a multiple of 4, at most d");
   else if (rows != 0 && !rows_fit(rows)) *rc = fail(1, std::string(who) + ": too many rows");
   return *rc == 0 && rows != 0;
 }
@@ -392,22 +404,24 @@ static int launch_grid_stride(hipStream_t s, Kernel* kernel, int64_t n, int cap,
 int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, const float* pos, const float* msa_pos,
                     const float* gamma, const float* beta, float* x, int64_t n_tok, int T, int d, int pad_idx,
                     int mask_idx, int token_dropout, int rows_per_msa, float eps, const float* gamma2, const float* beta2,
-                    bf16_t* h2, float embed_scale) {
+                    bf16_t* h2, float embed_scale, int d_live) {
   int rc;
-  if (!rows_go("embed", d, n_tok, &rc)) return rc;
+  if (!rows_go("embed", d, n_tok, &rc, &d_live)) return rc;
+  if (d_live != d && gamma) return fail(1, "embed: emb_layer_norm_before has no live-width form");
   by_row_width(d, [&](auto nch) {
     hipLaunchKernelGGL(embed_ln_kernel<decltype(nch)::value>, dim3(rows_grid(n_tok)), dim3(256), 0, s, tokens, embed, pos, msa_pos, gamma, beta,
-                       x, n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale);
+                       x, n_tok, T, d, pad_idx, mask_idx, token_dropout, rows_per_msa, eps, gamma2, beta2, h2, embed_scale, d_live);
   });
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 // The argument refusals of launch_layernorm_bf16 (0 = the launch may go ahead; touches no device) ...
-int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C) {
+int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C, int d_live) {
   int rc;
-  if (!rows_go("layernorm", d, M, &rc)) return rc;
+  if (!rows_go("layernorm", d, M, &rc, &d_live)) return rc;
   if (colmajor_R > 0) {
+    if (d_live != d) return fail(1, "layernorm: column-major output has no live-width form");
     if (row_wide(d)) return fail(1, "layernorm: column-major output needs d <= 2048");
     if (split3 || M % ((int64_t)colmajor_R * colmajor_C)) return fail(1, "layernorm: column-major output needs whole MSAs and plain bf16 rows");
   }
@@ -415,8 +429,9 @@ int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colm
 }
 // ... and its choice of kernel for M > 0 rows on the current device (LN_KERNEL_*; *stride_grid = the stride kernel's workgroups):
 // the launcher and pg_dbg_layernorm_rows, which reports it, both ask here
-int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_grid) {
+int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_grid, int d_live) {
   if (colmajor_R > 0) return LN_KERNEL_COLMAJOR;
+  if (d_live && d_live != d) return LN_KERNEL_PLAIN;      // the stride kernel has no live-width form
   // one resident round of workgroups walking their rows when the plain grid would be 1 ... 4 rounds (layernorm_bf16_stride_kernel)
   static const int on = env_int("PGIBBS_LN_STRIDE", 1);
   const int n_cu = device_cu_count();
@@ -440,13 +455,14 @@ int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_gri
 }
 
 int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
-                          int d, float eps, bool split3, int colmajor_R, int colmajor_C, bool split3_dup) {
-  const int rc = layernorm_bf16_check(M, d, split3, colmajor_R, colmajor_C);
+                          int d, float eps, bool split3, int colmajor_R, int colmajor_C, bool split3_dup, int d_live) {
+  const int rc = layernorm_bf16_check(M, d, split3, colmajor_R, colmajor_C, d_live);
   if (rc) return rc;
   if (M == 0) return 0;
+  if (d_live == 0) d_live = d;
   const int sp = split3 ? (split3_dup ? 1 : 2) : 0;
   unsigned stride_grid = 0;
-  switch (layernorm_bf16_choice(M, d, colmajor_R, &stride_grid)) {
+  switch (layernorm_bf16_choice(M, d, colmajor_R, &stride_grid, d_live)) {
     case LN_KERNEL_COLMAJOR:
       hipLaunchKernelGGL(layernorm_bf16_colmajor_kernel, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, M, d, eps, colmajor_R, colmajor_C);
       break;
@@ -456,7 +472,7 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
       break;
     default:
       by_row_width(d, [&](auto nch) {
-        hipLaunchKernelGGL(layernorm_bf16_kernel<decltype(nch)::value>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps);
+        hipLaunchKernelGGL(layernorm_bf16_kernel<decltype(nch)::value>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, h, sp, M, d, eps, d_live);
       });
   }
   PG_HIP(hipGetLastError());
@@ -464,23 +480,23 @@ int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, con
 }
 
 int launch_layernorm_f32(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t M, int d,
-                         float eps) {
+                         float eps, int d_live) {
   int rc;
-  if (!rows_go("layernorm", d, M, &rc)) return rc;
+  if (!rows_go("layernorm", d, M, &rc, &d_live)) return rc;
   by_row_width(d, [&](auto nch) {
-    hipLaunchKernelGGL(layernorm_f32_kernel<decltype(nch)::value>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps);
+    hipLaunchKernelGGL(layernorm_f32_kernel<decltype(nch)::value>, dim3(rows_grid(M)), dim3(256), 0, s, x, gamma, beta, y, M, d, eps, d_live);
   });
   PG_HIP(hipGetLastError());
   return 0;
 }
 
 int launch_gather_ln_bf16(hipStream_t s, const float* x, const int32_t* idx, const int32_t* row_map, int P, int width,
-                          const float* gamma, const float* beta, bf16_t* h, int64_t n_sel, int d, float eps, bool split3) {
+                          const float* gamma, const float* beta, bf16_t* h, int64_t n_sel, int d, float eps, bool split3, int d_live) {
   int rc;
-  if (!rows_go("gather_ln", d, n_sel, &rc)) return rc;
+  if (!rows_go("gather_ln", d, n_sel, &rc, &d_live)) return rc;
   by_row_width(d, [&](auto nch) {
     hipLaunchKernelGGL(gather_ln_bf16_kernel<decltype(nch)::value>, dim3(rows_grid(n_sel)), dim3(256), 0, s, x, idx, row_map, P, width, gamma,
-                       beta, h, split3 ? 1 : 0, n_sel, d, eps);
+                       beta, h, split3 ? 1 : 0, n_sel, d, eps, d_live);
   });
   PG_HIP(hipGetLastError());
   return 0;
@@ -505,10 +521,10 @@ bool lm_tail_small(int64_t n, int d) {
 }
 
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
-                   const float* out_bias, float* logits, int64_t n, int d, int V, float eps) {
+                   const float* out_bias, float* logits, int64_t n, int d, int V, float eps, int d_live) {
   if (V < 1 || V > 64) return fail(1, "lm_tail: vocab must be in 1..64");      // lane t keeps logit t; 64 * ceil(V / 4) <= 1024 threads
   int rc;
-  if (!rows_go("lm_tail", d, n, &rc)) return rc;
+  if (!rows_go("lm_tail", d, n, &rc, &d_live)) return rc;
   // identical arithmetic per logit (same per-lane partial sums, same wave reduction): bit-equal results.  Up to 1024 rows (round 5;
   // it was 128): a 32-chain shard's 800 sampled rows took 81 us on the row-per-wave kernel -- 200 workgroups, each wave walking the
   // decoder rows in nine dependent trips -- PGIBBS_LM_TAIL_SMALL=n moves the switch
@@ -520,11 +536,11 @@ int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const floa
     if constexpr (NCH <= kMaxChWide) {
       if (small) {
         hipLaunchKernelGGL(lm_tail_small_kernel<NCH>, dim3((unsigned)n), dim3(64 * ((V + 3) / 4)), 0, s, g, gamma, beta, embed, out_bias,
-                           logits, d, V, eps);
+                           logits, d, V, eps, d_live);
         return;
       }
     }
-    hipLaunchKernelGGL(lm_tail_kernel<NCH>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps);
+    hipLaunchKernelGGL(lm_tail_kernel<NCH>, dim3(rows_grid(n)), dim3(256), 0, s, g, gamma, beta, embed, out_bias, logits, n, d, V, eps, d_live);
   });
   PG_HIP(hipGetLastError());
   return 0;

@@ -86,7 +86,13 @@ struct Engine {
   bool esm_family() const { return cfg.arch == PG_ARCH_ESM1B || cfg.arch == PG_ARCH_ESM1 || cfg.arch == PG_ARCH_ESM2; }   // the pg_esm_* entry points
 
   ~Engine();
-  int init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int precision);
+  // live_head > 0 (init_embedded): c is the run shape, the tensors are the natural ones of a model with heads of live_head
+  int init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int precision, int live_head = 0);
+  // An embedded model: heads of a width no kernel is built for, each in a slot of a built width (head_slot), the other features of
+  // the slot structurally zero.  c carries the model's own sizes and the tensors are its natural fair-esm ones; the engine runs the
+  // shape d_model = n_heads * head_slot with every tensor scattered into its run-shape image (embedded_image), which computes the
+  // same function but in LayerNorm -- the row launchers are given d_live
+  int init_embedded(const pg_model_config* c, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal, int precision);
 
   // ---- weights ----
   std::vector<void*> owned;   // every hipMalloc'd weight block
@@ -97,6 +103,8 @@ struct Engine {
   float* head_bias = nullptr;
   std::vector<EsmLayer> esm_layers;
   std::vector<MsaLayer> msa_layers;
+  int d_live = 0;             // the model's own features per row: cfg.d_model, less for an embedded model (what the row launchers normalise over)
+  bool embedded() const { return d_live != cfg.d_model; }
   int head_dim = 64;          // d_model / n_heads, a width of head_width.h's table -- what every attention and rotation launch of the ESM path is given
   // ESM-2 rotary embedding: cos / sin table [rope_rows][head_dim] fp32 built at init (rope.hip)
   float* rope_tab = nullptr;
@@ -237,7 +245,16 @@ struct Engine {
 };
 
 // host side of the ESM-2 rotary embedding: the cos / sin table the rotation kernel reads (engine.hip)
-std::vector<float> rope_table(int rows, int hd = 64);
+// live > 0: heads of `live` in slots of hd -- the frequencies of a head of `live`, cos 1 and sin 0 in a half's pad columns
+std::vector<float> rope_table(int rows, int hd = 64, int live = 0);
+// An embedded model's tensors (Engine::init_embedded).  A tensor's role is read from its fair-esm name; *rows x *cols is its natural
+// shape (a vector: cols 1) and the result its run-shape image, live values at their run positions and 0.0 everywhere else:
+// residual-stream features keep their index, feature j of head h goes to h * slot + j (j < width / 2) or h * slot + j + (slot - width) / 2.
+// false: the name is none of an ESM-2 model's tensors
+struct EmbedShape { int n_heads, width, slot, d_ffn, vocab; };
+bool embedded_image(const std::string& name, const EmbedShape& es, const float* src, int64_t* rows, int64_t* cols, std::vector<float>* image);
+// the embedded entry's own refusals, in the order pgibbs.h states (PG_OK: init's checks of the run shape follow)
+int embedded_check(const pg_model_config* c, int head_slot);
 
 // state-dict lookup used by init
 struct TensorMap {

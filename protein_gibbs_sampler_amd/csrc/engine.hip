@@ -219,8 +219,75 @@ struct Uploader {
 };
 }  // namespace
 
-int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int prec) {
+// ------------------------------------------------------------------------------------------------
+// embedded models: the host side (what goes where; engine.h)
+// ------------------------------------------------------------------------------------------------
+namespace {
+enum EmbedAxis { AX_SAME, AX_STREAM, AX_HEAD };
+bool ends_with(const std::string& s, const char* t) {
+  const size_t n = strlen(t);
+  return s.size() >= n && !s.compare(s.size() - n, n, t);
+}
+}  // namespace
+
+bool embedded_image(const std::string& name, const EmbedShape& es, const float* src, int64_t* rows, int64_t* cols, std::vector<float>* image) {
+  const int64_t d = (int64_t)es.n_heads * es.width, D = (int64_t)es.n_heads * es.slot, f = es.d_ffn, V = es.vocab;
+  EmbedAxis ra, ca = AX_SAME;
+  int64_t R, C = 1;
+  const bool w = ends_with(name, ".weight");
+  const bool qkv = name.find("self_attn.q_proj.") != std::string::npos || name.find("self_attn.k_proj.") != std::string::npos ||
+                   name.find("self_attn.v_proj.") != std::string::npos;
+  if (name == "embed_tokens.weight") { ra = AX_SAME; R = V; ca = AX_STREAM; C = d; }
+  else if (name == "lm_head.bias") { ra = AX_SAME; R = V; }
+  else if (name.find("layer_norm") != std::string::npos) { ra = AX_STREAM; R = d; }
+  else if (qkv) { ra = AX_HEAD; R = d; if (w) { ca = AX_STREAM; C = d; } }
+  else if (name.find("self_attn.out_proj.") != std::string::npos) { ra = AX_STREAM; R = d; if (w) { ca = AX_HEAD; C = d; } }
+  else if (name.find(".fc1.") != std::string::npos) { ra = AX_SAME; R = f; if (w) { ca = AX_STREAM; C = d; } }
+  else if (name.find(".fc2.") != std::string::npos) { ra = AX_STREAM; R = d; if (w) { ca = AX_SAME; C = f; } }
+  else if (name.rfind("lm_head.dense.", 0) == 0) { ra = AX_STREAM; R = d; if (w) { ca = AX_STREAM; C = d; } }
+  else return false;
+  if (!w && !ends_with(name, ".bias")) return false;
+  *rows = R;
+  *cols = C;
+  if (!image) return true;
+  const int half = es.width / 2, shift = (es.slot - es.width) / 2;
+  auto to = [&](EmbedAxis a, int64_t i) { return a != AX_HEAD ? i : (i / es.width) * es.slot + (i % es.width) + ((i % es.width) < half ? 0 : shift); };
+  const int64_t Rr = ra == AX_SAME ? R : D, Cr = ca == AX_SAME ? C : D;
+  image->assign((size_t)(Rr * Cr), 0.0f);
+  for (int64_t r = 0; r < R; ++r) {
+    float* dst = image->data() + to(ra, r) * Cr;
+    const float* s = src + r * C;
+    if (ca != AX_HEAD) memcpy(dst, s, (size_t)C * 4);
+    else for (int64_t c = 0; c < C; ++c) dst[to(ca, c)] = s[c];
+  }
+  return true;
+}
+
+int embedded_check(const pg_model_config* c, int head_slot) {
+  if (c->arch != PG_ARCH_ESM2) return fail(PG_ERR_INVALID, "embedded head widths run for PG_ARCH_ESM2 only");
+  const HeadWidth* hw = head_width(head_slot);
+  if (!hw) return fail(PG_ERR_INVALID, "head slot " + std::to_string(head_slot) + ": a slot must be a built head width, " + head_widths_text(false));
+  const int w = c->n_heads > 0 && c->d_model > 0 && c->d_model % c->n_heads == 0 ? c->d_model / c->n_heads : 0;
+  if (w < 4 || w % 4 || w >= head_slot)
+    return fail(PG_ERR_INVALID, "d_model " + std::to_string(c->d_model) + " with " + std::to_string(c->n_heads) + " heads in slots of " + std::to_string(head_slot) +
+                                    ": an embedded head width must be a multiple of 4 and smaller than its slot");
+  if (c->n_heads > hw->max_heads)
+    return fail(PG_ERR_INVALID, "heads of " + std::to_string(w) + " in slots of " + std::to_string(head_slot) + ": the rotary and row kernels hold at most " +
+                                    std::to_string(hw->max_heads) + " slots per row, not " + std::to_string(c->n_heads));
+  return PG_OK;
+}
+
+int Engine::init_embedded(const pg_model_config* c, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal, int prec) {
+  const int rc = embedded_check(c, head_slot);
+  if (rc) return rc;
+  pg_model_config run = *c;
+  run.d_model = c->n_heads * head_slot;
+  return init(&run, tensors, n_tensors, device_ordinal, prec, c->d_model / c->n_heads);
+}
+
+int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tensors, int device_ordinal, int prec, int live_head) {
   cfg = *c;
+  d_live = live_head ? live_head * cfg.n_heads : cfg.d_model;
   precision = prec;
   device = -1;
   if (cfg.arch != PG_ARCH_ESM1B && cfg.arch != PG_ARCH_MSA1B && cfg.arch != PG_ARCH_ESM1 && cfg.arch != PG_ARCH_ESM2) return fail(PG_ERR_INVALID, "unknown arch");
@@ -265,6 +332,23 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   PG_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
   stream = own_stream;
 
+  // an embedded model: the run-shape images of its natural tensors, alive until the upload below is done
+  std::vector<std::vector<float>> images;
+  std::vector<pg_tensor> run_tensors;
+  if (live_head) {
+    const EmbedShape es = {cfg.n_heads, live_head, head_dim, cfg.d_ffn, cfg.vocab};
+    images.resize(n_tensors);
+    for (int i = 0; i < n_tensors; ++i) {
+      int64_t r = 0, cc = 0;
+      if (!tensors[i].name || !embedded_image(tensors[i].name, es, nullptr, &r, &cc, nullptr)) continue;      // not a tensor the engine reads
+      if (tensors[i].numel != r * cc)
+        return fail(PG_ERR_WEIGHTS, std::string("tensor '") + tensors[i].name + "' has " + std::to_string(tensors[i].numel) + " elements, expected " + std::to_string(r * cc));
+      embedded_image(tensors[i].name, es, tensors[i].data, &r, &cc, &images[i]);
+      run_tensors.push_back({tensors[i].name, images[i].data(), (int64_t)images[i].size()});
+    }
+    tensors = run_tensors.data();
+    n_tensors = (int)run_tensors.size();
+  }
   TensorMap tm;
   for (int i = 0; i < n_tensors; ++i)
     if (tensors[i].name) tm.m[tensors[i].name] = &tensors[i];
@@ -274,7 +358,8 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   // still folded, as an fp32 factor applied to the fp32 checkpoint values BEFORE they are rounded to the 16-bit operand (or split into
   // the strict mode's bf16 pair) -- the kernels stay scale-free and the only new rounding is that fp32 product, 2^-24 relative, under
   // an operand rounding of 2^-9 / 2^-12 / 2^-17
-  const float qs = hw->q_scale;
+  // An embedded model: its own width^-0.5, not the slot's -- the scores are those of the live head
+  const float qs = live_head ? (float)pow((double)live_head, -0.5) : hw->q_scale;
   bool ok = true;
   ok = ok && (embed = up.f32("embed_tokens.weight", (int64_t)V * d));
   // ESM-2 has no position table (pos stays null: embed_ln_kernel adds nothing) -- positions enter through the rotation of q and k
@@ -326,7 +411,7 @@ int Engine::init(const pg_model_config* c, const pg_tensor* tensors, int n_tenso
   if (esm2()) {
     if (cfg.max_positions < 1) return fail(PG_ERR_INVALID, "max_positions must be positive");
     rope_rows = cfg.max_positions + 2;              // like the learned tables
-    const std::vector<float> tab = rope_table(rope_rows, head_dim);
+    const std::vector<float> tab = rope_table(rope_rows, head_dim, live_head);
     void* dt = nullptr;
     PG_HIP(hipMalloc(&dt, tab.size() * 4));
     owned.push_back(dt);
@@ -446,7 +531,7 @@ int Engine::dense_ln(const float* x, const LnW& ln, const DenseW& W, bf16_t* out
 }
 
 int Engine::layer_norm(const float* x, const LnW& ln, bf16_t* h, int64_t M, bool dup, int colmajor_R, int colmajor_C) {
-  return timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, x, ln.g, ln.b, h, M, cfg.d_model, cfg.layer_norm_eps, strict(), colmajor_R, colmajor_C, dup); });
+  return timed(PC_LN, [&] { return OPS(launch_layernorm_bf16, stream, x, ln.g, ln.b, h, M, cfg.d_model, cfg.layer_norm_eps, strict(), colmajor_R, colmajor_C, dup, d_live); });
 }
 
 // x = embedding (+ positions, emb_layer_norm_before) of M tokens, T per sequence; rows_per_msa > 0: an alignment batch (its row
@@ -455,7 +540,7 @@ int Engine::embed_rows(const int32_t* d_tok, int64_t M, int T, int rows_per_msa,
   return timed(PC_EMBED, [&] {
     return OPS(launch_embed_ln, stream, d_tok, embed, pos, msa_pos, ln_before.g, ln_before.b, x.as<float>(), M, T, cfg.d_model, cfg.pad_idx,
                            cfg.mask_idx, rows_per_msa ? 0 : cfg.token_dropout, rows_per_msa, cfg.layer_norm_eps, first_ln ? first_ln->g : nullptr,
-                           first_ln ? first_ln->b : nullptr, first_ln ? h.as<bf16_t>() : nullptr, embed_scale());
+                           first_ln ? first_ln->b : nullptr, first_ln ? h.as<bf16_t>() : nullptr, embed_scale(), d_live);
   });
 }
 
@@ -518,11 +603,18 @@ float* Engine::splitk_ws(int rows, int n, int K, int64_t batch_rows) {
 // inv_freq[i] = 1 / 10000^(2i / 64) in fp32 as fair-esm's RotaryEmbedding holds it (1.0 / (10000 ** (arange(0, 64, 2).float() / 64))).
 // The power is taken in double and rounded to fp32 -- the values torch's fp32 pow and glibc's powf give; a vectorised fp32 pow (numpy's)
 // is one ulp off at i = 5 and 27 --, the cosine and sine of the fp32 angle in double, rounded to fp32.
-std::vector<float> rope_table(int rows, int hd) {
-  const int half = hd / 2;
+// An embedded head (live > 0: heads of `live` in slots of hd): column i < live / 2 of a half carries frequency i of a head of `live`,
+// the other columns of the half cos = 1 and sin = 0 (they rotate structural zeros).
+std::vector<float> rope_table(int rows, int hd, int live) {
+  const int half = hd / 2, lhalf = live > 0 ? live / 2 : half;
   std::vector<float> tab((size_t)rows * hd);
   for (int i = 0; i < half; ++i) {
-    const float inv_freq = 1.0f / (float)pow(10000.0, i / (double)half);
+    if (i >= lhalf) {
+      for (int t = 0; t < rows; ++t) tab[(size_t)t * hd + i] = 1.0f, tab[(size_t)t * hd + half + i] = 0.0f;
+      continue;
+    }
+    // the exponent as torch forms it, a float32 quotient: exact for the built widths (powers of two), rounded for a head of 24
+    const float inv_freq = 1.0f / (float)pow(10000.0, (double)((float)(2 * i) / (float)(2 * lhalf)));
     for (int t = 0; t < rows; ++t) {
       const float ang = (float)t * inv_freq;
       tab[(size_t)t * hd + i] = (float)cos((double)ang);
@@ -660,7 +752,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
   const int Mi = sel_gemm_rows(M, Mp);
   // single chains (<= 32 token rows): LayerNorm is folded into the operand load of the weight-streaming QKV / fc1 GEMMs
   // (gemm_ln_skinny_kernel) -- two launches per layer less in the launch-bound regime
-  const bool ln_in_gemm = gemm_ln_skinny_ok(Mi, 3 * d, d) && gemm_ln_skinny_ok(Mi, f, d);
+  const bool ln_in_gemm = !embedded() && gemm_ln_skinny_ok(Mi, 3 * d, d) && gemm_ln_skinny_ok(Mi, f, d);      // no live-width form
 
   // embedding + emb_layer_norm_before, and in the same pass over the row the first layer's LayerNorm (its bf16 operand rows)
   if ((rc = embed_rows(d_tok, M, T, 0, ln_in_gemm ? nullptr : &esm_layers[0].ln1))) return rc;
@@ -723,7 +815,7 @@ int Engine::resid_gemm_ln(int cls, const bf16_t* a, const DenseW& W, float* x, i
   // normalise them in the epilogue (gemm_rowln.hip; same bits as the two launches below).  Opt-in through PGIBBS_ROWLN=1
   // (gemm_rowln_ok): measured slower, 1.34-1.37 ms per launch against 1.26-1.28 ms for the two launches it replaces
   static const int64_t rowln_min = env_int("PGIBBS_ROWLN_MIN_ROWS", 16384);
-  if (!strict() && M_real >= rowln_min && M_real <= M_rows && OPS(gemm_rowln_ok, M_rows, d, K))
+  if (!strict() && !embedded() && M_real >= rowln_min && M_real <= M_rows && OPS(gemm_rowln_ok, M_rows, d, K))
     return timed(cls, [&] { return OPS(launch_gemm_rowln, stream, a, W.w, W.b, x, ln.g, ln.b, h, (int)M_real, M_rows, K, K, K, cfg.layer_norm_eps, colmajor_R, colmajor_C); });
   const int rc = dense(cls, a, W, x, M_rows, EPI_F32_RESID, (int)M_real, use_splitk);
   return rc ? rc : layer_norm(x, ln, h, M_real, true, colmajor_R, colmajor_C);
@@ -754,17 +846,17 @@ int Engine::head(const int32_t* d_idx_, const int32_t* d_row_map, int P, int wid
   if (strict()) {
     if ((rc = sel_h.ensure((size_t)Np * 3 * d * 2, stream))) return rc;
     if ((rc = OPS(launch_gather_ln_bf16, stream, x_src, d_idx_, d_row_map, P, width, ln_after.g, ln_after.b,
-                                    sel_h.as<bf16_t>(), n_sel, d, eps, true))) return rc;
+                                    sel_h.as<bf16_t>(), n_sel, d, eps, true, d_live))) return rc;
     if ((rc = dense3(sel_h.as<bf16_t>(), head_dense, sel_g.as<float>(), (int)Np, false))) return rc;
     if ((rc = launch_gelu_f32(stream, sel_g.as<float>(), Np * d))) return rc;
-    return launch_lm_tail(stream, sel_g.as<float>(), head_ln.g, head_ln.b, embed, head_bias, d_logits, n_sel, d, V, eps);
+    return launch_lm_tail(stream, sel_g.as<float>(), head_ln.g, head_ln.b, embed, head_bias, d_logits, n_sel, d, V, eps, d_live);
   }
   return timed(PC_HEAD, [&] {
     int r = OPS(launch_gather_ln_bf16, stream, x_src, d_idx_, d_row_map, P, width, ln_after.g, ln_after.b,
-                                  sel_h.as<bf16_t>(), n_sel, d, eps);
+                                  sel_h.as<bf16_t>(), n_sel, d, eps, false, d_live);
     if (r) return r;
     if ((r = dense(PC_NONE, sel_h.as<bf16_t>(), head_dense, sel_g.as<float>(), sel_gemm_rows(n_sel, Np), EPI_F32_GELU))) return r;
-    return launch_lm_tail(stream, sel_g.as<float>(), head_ln.g, head_ln.b, embed, head_bias, d_logits, n_sel, d, V, eps);
+    return launch_lm_tail(stream, sel_g.as<float>(), head_ln.g, head_ln.b, embed, head_bias, d_logits, n_sel, d, V, eps, d_live);
   });
 }
 

@@ -107,8 +107,12 @@ int launch_embed_ln(hipStream_t s, const int32_t* tokens, const float* embed, co
                     const float* gamma, const float* beta, float* x, int64_t n_tok, int T, int d, int pad_idx,
                     int mask_idx, int token_dropout, int rows_per_msa, float eps,
                     const float* gamma2 = nullptr, const float* beta2 = nullptr, bf16_t* h2 = nullptr,   // h2: also the first layer's LayerNorm of x
-                    float embed_scale = 1.0f);   // gamma == nullptr: no emb_layer_norm_before; embed_scale = sqrt(d) (both: ESM-1);
+                    float embed_scale = 1.0f,    // gamma == nullptr: no emb_layer_norm_before; embed_scale = sqrt(d) (both: ESM-1);
                                                  // pos == nullptr: no position table either (ESM-2)
+                    int d_live = 0);             // the live width of the row launchers, here of h2's LayerNorm (below)
+// d_live (0 = d) of the row launchers: the rows are d wide in memory and their first d_live features are the model's own (an embedded
+// model, engine.h): statistics, affine and the decoder's dot products run over d_live features -- on them, bit for bit what the same
+// kernel gives for rows of d = d_live -- and the pad features of every output row are written as zeros (ln_row.h)
 // ESM-2 rotary position embedding (rope.hip): the q and k thirds of qkv[M][ld] (rows [q | k | v], H heads of head_dim each, 64 or 32)
 // rotated in place, row r at position r % T; table = [table_rows][head_dim] fp32 ([t][0 .. head_dim/2 - 1] cos, then as many sin, of
 // float(t) * inv_freq[i]: rope_table); f32: the buffer is fp32 (strict mode), else the flavour's 16-bit type.  Rows >= M are not touched
@@ -117,11 +121,12 @@ int launch_rope(hipStream_t s, void* qkv, bool f32, const float* table, int tabl
 int launch_layernorm_bf16(hipStream_t s, const float* x, const float* gamma, const float* beta, bf16_t* h, int64_t M,
                           int d, float eps, bool split3 = false,   // split3: h rows are [lo | hi | hi], 3 d wide
                           int colmajor_R = 0, int colmajor_C = 0,  // > 0: token row (b*R + r)*C + c is written as row (b*C + c)*R + r
-                          bool split3_dup = true);                 // false: the duplicate hi block is not written (fused consumer)
+                          bool split3_dup = true,                  // false: the duplicate hi block is not written (fused consumer)
+                          int d_live = 0);                         // no column-major form, never the stride kernel
 // its argument refusals alone (0 = fine; no HIP call), and the kernel it picks for M > 0 rows on the current device (LN_KERNEL_*;
 // *stride_grid = the stride kernel's workgroup count): one definition for the launcher and for the debug entry that reports it
-int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C);
-int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_grid);
+int layernorm_bf16_check(int64_t M, int d, bool split3, int colmajor_R, int colmajor_C, int d_live = 0);
+int layernorm_bf16_choice(int64_t M, int d, int colmajor_R, unsigned* stride_grid, int d_live = 0);
 // ESM-MSA-1b column attention fused into its QKV projection (gemm_colattn.hip): X = LayerNorm rows in column-major token order,
 // W / bias = the projection's rows grouped per head (launch_headmajor_qkv); ctx rows in ordinary token order.  R in {32,64,128,256}
 bool colattn_ok(int R, int d_model, int n_heads);
@@ -129,10 +134,10 @@ int launch_gemm_colattn(hipStream_t s, const bf16_t* X, const bf16_t* W, const f
                         int d, int ld_ctx);
 int launch_headmajor_qkv(hipStream_t s, const bf16_t* w, const float* b, bf16_t* w2, float* b2, int H, int K);
 int launch_layernorm_f32(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, int64_t M, int d,
-                         float eps);
+                         float eps, int d_live = 0);
 int launch_gather_ln_bf16(hipStream_t s, const float* x, const int32_t* idx, const int32_t* row_map, int P, int width,
                           const float* gamma, const float* beta, bf16_t* h, int64_t n_sel, int d, float eps,
-                          bool split3 = false);
+                          bool split3 = false, int d_live = 0);
 // strict precision mode: fp32 [rows][K] -> K-concatenated split-bf16 operand bf16 [rows][3K], [lo | hi | hi] for an
 // activation (optionally through erf-GELU), [hi | lo | hi] for a weight; fp32 GELU in place
 int launch_split3_bf16(hipStream_t s, const float* src, bf16_t* dst, int64_t rows, int K, float scale, bool gelu, bool weight);
@@ -154,7 +159,7 @@ int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores,
 int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t* idx, const int32_t* row_map, int P, int width,
                        int64_t n_sel, int row_bytes, const int32_t* d_iter = nullptr);
 int launch_lm_tail(hipStream_t s, const float* g, const float* gamma, const float* beta, const float* embed,
-                   const float* out_bias, float* logits, int64_t n, int d, int V, float eps);
+                   const float* out_bias, float* logits, int64_t n, int d, int V, float eps, int d_live = 0);
 bool lm_tail_small(int64_t n, int d);      // launch_lm_tail's choice: the workgroup-per-row kernel (n <= PGIBBS_LM_TAIL_SMALL, 1024, and d <= 2560)
 int launch_f32_to_bf16(hipStream_t s, const float* src, bf16_t* dst, int64_t n, float scale);
 int launch_bf16_to_f32(hipStream_t s, const bf16_t* src, float* dst, int64_t n);

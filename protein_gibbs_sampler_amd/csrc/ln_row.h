@@ -80,4 +80,18 @@ __device__ __forceinline__ void store_row_bf16(bf16_t* dst, const float4 (&v)[NC
     }
 }
 
+// Live width (an embedded model: engine.h d_live): the row is d wide in memory, its first d_live features are the model's own and
+// the rest are structural zeros.  The kernels then load, normalise (ln_inplace with nch4 = d_live / 4 and d = d_live: the bits of a
+// row of d_live features) and store the live chunks as above, and this writes the pad chunks nl4 .. nch4 - 1 of the output row as
+// zeros, in the same two forms -- the buffer is reused and may hold anything, NaN patterns included.  No trip when d_live == d.
+__device__ __forceinline__ void zero_row_pad_bf16(bf16_t* dst, int nl4, int nch4, int lane, bool split3 = false, bool dup = true) {
+  const uint2 z = make_uint2(0u, 0u);
+  for (int ci = nl4 + lane; ci < nch4; ci += 64) {
+    if (!split3) ((uint2*)dst)[ci] = z;
+    else split_store4(dst + split_group_offset(ci >> 3, (ci & 7) * 4), z, z, dup);
+  }
+}
+// d_live of a row of d features: a multiple of 4, at most d
+constexpr bool row_live_ok(int d, int d_live) { return d_live >= 4 && d_live % 4 == 0 && d_live <= d; }
+
 PG_OPS_END

@@ -12,6 +12,7 @@ import re
 import numpy as np
 
 from . import _lib
+from .weights import embedded_slot
 
 
 FP16_MAX = 65504.0
@@ -86,7 +87,11 @@ class NativeMaskedLM:
             arr[i].data = a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
             arr[i].numel = a.size
         h = ctypes.c_void_p()
-        _lib.check(L.pg_engine_create(ctypes.byref(c), arr, len(names), int(m.group(1)), precision, ctypes.byref(h)))
+        slot = embedded_slot(self.cfg)      # heads of a width no kernel is built for (ESM-2 35M): the embedded entry, natural tensors
+        if slot:
+            _lib.check(L.pg_engine_create_embedded(ctypes.byref(c), slot, arr, len(names), int(m.group(1)), precision, ctypes.byref(h)))
+        else:
+            _lib.check(L.pg_engine_create(ctypes.byref(c), arr, len(names), int(m.group(1)), precision, ctypes.byref(h)))
         return h
 
     def _alt_handle(self):

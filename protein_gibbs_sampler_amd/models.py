@@ -69,9 +69,8 @@ class ESM2(_ESM2):
     in fair-esm) -- rotary position embeddings, no emb_layer_norm_before, the ESM-1b alphabet and LM head.  Reads the v2 checkpoint
     layout (weights.load_fair_esm_checkpoint).  This wrapper promises the 650M model: a checkpoint wider than d_model 2048 (the 3B
     file, 4.4 times the work per token) is refused with a message naming ESM2_3B, and the 150M file (heads of 32) with one naming
-    ESM2_150M, the 15B file (heads of 128) with one naming ESM2_15B and the 8M file (heads of 16) with one naming ESM2_8M.  The one
-    other released size, 35M, has heads of 24 and d_model 480 and is refused by head width: the engine's attention kernels implement
-    heads of 64, 32, 128 and 16 (and its GEMMs take d_model in multiples of 64)."""
+    ESM2_150M, the 15B file (heads of 128) with one naming ESM2_15B, the 8M file (heads of 16) with one naming ESM2_8M and the 35M
+    file (heads of 24, which run embedded in slots of 32) with one naming ESM2_35M."""
     _cfg, _file = _w.ESM2_T33_CONFIG, "esm2_t33_650M_UR50D.pt"
 
 
@@ -113,8 +112,19 @@ class ESM2_8M(_ESM2):
     _cfg, _file = _w.ESM2_T6_CONFIG, "esm2_t6_8M_UR50D.pt"
 
 
+class ESM2_35M(_ESM2):
+    """esm2_t12_35M_UR50D: ESM-2 at 35M parameters -- 12 layers, d_model 480, 20 heads of 24, d_ffn 1920.  No kernel is built for heads
+    of 24 and the GEMMs take multiples of 64, so the engine runs this model EMBEDDED in a shape it already runs: every head in a slot of
+    32, rows of 640 features whose last 160 are structurally zero -- the geometry of ESM2_150M, 1.48 times the model's own GEMM work and
+    1.33 times its attention work.  A zero-padded transformer computes the same function except in LayerNorm, whose kernels normalise
+    over the 480 live features (include/pgibbs.h pg_engine_create_embedded).  Sizes come from the file: any
+    checkpoint with heads of 24 (at most 32 of them) or of 64 loads here and runs as the model it is; heads of 24 load ONLY here -- the
+    other wrappers refuse them by name."""
+    _cfg, _file = _w.ESM2_T12_CONFIG, "esm2_t12_35M_UR50D.pt"
+
+
 # the ESM-2 wrappers under their command-line names (--model)
-ESM2_MODELS = {"esm2": ESM2, "esm2_3b": ESM2_3B, "esm2_150m": ESM2_150M, "esm2_15b": ESM2_15B, "esm2_8m": ESM2_8M}
+ESM2_MODELS = {"esm2": ESM2, "esm2_3b": ESM2_3B, "esm2_150m": ESM2_150M, "esm2_15b": ESM2_15B, "esm2_8m": ESM2_8M, "esm2_35m": ESM2_35M}
 
 
 class ESM_MSA1(_Wrapper):

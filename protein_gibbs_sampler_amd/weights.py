@@ -32,7 +32,8 @@ ESM1_T34_CONFIG = dict(ESM1_T6_CONFIG, n_layers=34, d_model=1280, n_heads=20, d_
 # ESM-2 (fair-esm `ESM2`, esm2_t33_650M_UR50D -- models.ESM2): the ESM-1b block stack and LM head without a position table and without
 # emb_layer_norm_before; positions enter through rotary embeddings of q and k in every layer (include/pgibbs.h PG_ARCH_ESM2).  Of
 # the released sizes 650M and 3B have heads of 64, 150M heads of 32, 15B heads of 128 and 8M heads of 16, the four widths the attention
-# and rotary kernels are built for (35M: heads of 24 and d_model 480, no multiple of 64, which the GEMMs need -- not an engine model).
+# and rotary kernels are built for.  35M has heads of 24 and d_model 480, which neither those kernels nor the GEMMs (multiples of 64) take:
+# it runs EMBEDDED, every head in a slot of 32 and its rows 640 wide (EMBEDDED_WIDTHS below; include/pgibbs.h pg_engine_create_embedded).
 ESM2_T33_CONFIG = dict(arch=_lib.PG_ARCH_ESM2, vocab=33, d_model=1280, n_layers=33, n_heads=20, d_ffn=5120, max_positions=1024,
                        pad_idx=1, mask_idx=32, cls_idx=0, eos_idx=2, token_dropout=1, max_msa_rows=0, layer_norm_eps=1e-5)
 # esm2_t36_3B_UR50D -- models.ESM2_3B: 36 layers of 40 heads, 4.4 times the arithmetic of the 650M model per token
@@ -55,6 +56,24 @@ HEAD_WIDTHS = {
     16: dict(max_heads=32, esm2_only=True, q_scale=0.25, config=ESM2_T6_CONFIG, file="esm2_t6_8M_UR50D", wrapper="ESM2_8M", cli="esm2_8m"),
 }
 HEAD_DIMS = tuple(HEAD_WIDTHS)
+# esm2_t12_35M_UR50D -- models.ESM2_35M: 12 layers of 20 heads of 24.  head_slot is the configuration's own say that its heads run embedded
+# in slots of that width (not a field of pg_model_config): a configuration derived from this one keeps it, one derived from another
+# base with heads of 24 does not have it and stays refused by pg_engine_create
+ESM2_T12_CONFIG = dict(ESM2_T33_CONFIG, d_model=480, n_layers=12, n_heads=20, d_ffn=1920, head_slot=32)
+# Head widths that are no kernel width and run embedded in a slot of one (csrc/engine.hip init_embedded): the engine runs n_heads * slot
+# features per row on zero-padded weights and scales q by q_scale = width^-0.5 as float32, the width's own
+EMBEDDED_WIDTHS = {
+    24: dict(slot=32, q_scale=float(np.float32(24 ** -0.5)), config=ESM2_T12_CONFIG, file="esm2_t12_35M_UR50D", wrapper="ESM2_35M", cli="esm2_35m"),
+}
+
+
+def embedded_slot(cfg):
+    """The slot width an ESM-2 configuration says its heads run embedded in (its head_slot, for a width of EMBEDDED_WIDTHS); 0: the
+    configuration goes to pg_engine_create as it is."""
+    row = EMBEDDED_WIDTHS.get(head_dim_of(cfg)) if cfg["arch"] == _lib.PG_ARCH_ESM2 else None
+    return row["slot"] if row and cfg.get("head_slot") == row["slot"] else 0
+
+
 MAX_HEADS_OF_32 = HEAD_WIDTHS[32]["max_heads"]
 MAX_HEADS_OF_16 = HEAD_WIDTHS[16]["max_heads"]
 MAX_HEADS_OF_128 = HEAD_WIDTHS[128]["max_heads"]
@@ -64,12 +83,14 @@ ESM2_650M_MAX_D_MODEL = 2048  # a wider file handed to a config of at most this 
 
 
 def rotary_inv_freq(head_dim=64):
-    """fair-esm RotaryEmbedding's `inv_freq` for heads of `head_dim` (64: the default; 32: ESM-2 150M; 128: ESM-2 15B; 16: ESM-2 8M), float32:
+    """fair-esm RotaryEmbedding's `inv_freq` for heads of `head_dim` (64: the default; 32: ESM-2 150M; 128: ESM-2 15B; 16: ESM-2 8M; 24: ESM-2
+    35M), float32:
     1.0 / (10000 ** (torch.arange(0, head_dim, 2).float() / head_dim)).  The power is taken in double and rounded to float32 -- the
     values torch's float32 pow gives (numpy's vectorised float32 power is one ulp off at i = 5 and 27 of 32), and what the engine
     builds its cos / sin table from (csrc/engine.hip rope_table)."""
-    half = head_dim // 2
-    p = (10000.0 ** (np.arange(half, dtype=np.float64) / float(half))).astype(np.float32)
+    # the exponent is torch's float32 quotient: exact when head_dim is a power of two, rounded at 24 (i / 12 is no float32 value)
+    e = (np.arange(0, head_dim, 2, dtype=np.float32) / np.float32(head_dim)).astype(np.float32)
+    p = (10000.0 ** e.astype(np.float64)).astype(np.float32)
     return (np.float32(1.0) / p).astype(np.float32)
 
 
@@ -391,10 +412,17 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
     cfg.update(take)
     # Head width (HEAD_WIDTHS).  64 loads against every base configuration; a width built for ESM-2 only loads against a configuration
     # whose own heads have that width (32: ESM2_T30_CONFIG, models.ESM2_150M, and so on) -- a wrapper promises its model, as ESM2 refuses
-    # the 3B file below; 24 loads nowhere.  Then the engine's own order: heads per row, row width (csrc/engine.hip, csrc/ln_row.h).
+    # the 3B file below; 24, an embedded width (EMBEDDED_WIDTHS), loads against ESM2_T12_CONFIG only and then under its slot's limits.  Then the engine's own order: heads per row, row width (csrc/engine.hip, csrc/ln_row.h).
     hd = cfg["d_model"] / max(1, cfg["n_heads"])
     has = "checkpoint has %d heads of dimension %g: " % (cfg["n_heads"], hd)
     row = HEAD_WIDTHS.get(hd)
+    emb = EMBEDDED_WIDTHS.get(hd)
+    if emb is not None:
+        # an embedded width loads only against a configuration whose own heads have it (models.ESM2_35M); the slot's limits then
+        if head_dim_of(base_cfg) != hd:
+            raise ValueError(has + "the engine's attention kernels implement head dimension 64 for the configuration it was loaded against; "
+                             "load %s (heads of %g) with models.%s / --model %s" % (emb["file"], hd, emb["wrapper"], emb["cli"]))
+        row = dict(HEAD_WIDTHS[emb["slot"]], esm2_only=False, file=emb["file"], config=emb["config"])
     if row is None:
         raise ValueError(has + "the engine's attention kernels implement head dimension 64 (every model of pgen.models) and, for ESM-2, "
                          + ", ".join("%d (%s)" % (w, r["file"]) for w, r in HEAD_WIDTHS.items() if r["esm2_only"]))

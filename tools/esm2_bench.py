@@ -35,6 +35,10 @@ rotation, LayerNorm and GEMM classes, and then the head-16 attention launch agai
 process ("head16_vs_head32": 3-layer models of 20 heads of 16 (d_model 320) and 20 heads of 32 (d_model 640), config-2 shape,
 profiled alternately).
 
+`--size 35m` measures ESM-2 35M (12 x 480, 20 heads of 24, d_ffn 1920; models.ESM2_35M), which the engine runs embedded in slots of 32
+(rows of 640 features: the byte and FLOP figures of its kernel classes are those of the RUN shape, what the kernels move and multiply),
+with ESM-2 150M (30 x 640: the model whose kernels it runs) alternating in the same process at the same three shapes.
+
 Prints one JSON line.  Needs a GPU: there is no CPU path.
 """
 import argparse
@@ -60,13 +64,13 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3, help="alternations ESM-1b / ESM-2 per shape")
     ap.add_argument("--prof-iters", type=int, default=3, help="iterations of the profiled run")
     ap.add_argument("--layers", type=int, default=None, help="fewer layers for a rehearsal (default: 33, or 36 with --size 3b)")
-    ap.add_argument("--size", choices=["650m", "3b", "150m", "15b", "8m"], default="650m",
+    ap.add_argument("--size", choices=["650m", "3b", "150m", "15b", "8m", "35m"], default="650m",
                     help="650m: ESM-2 650M next to ESM-1b; 3b: ESM-2 3B alone; 150m: ESM-2 150M alone, then head 32 against head 64; "
                          "15b: ESM-2 15B alone (with --layers L < 48: L and L / 2 layers, 48 extrapolated); "
-                         "8m: ESM-2 8M alone, then head 16 against head 32")
+                         "8m: ESM-2 8M alone, then head 16 against head 32; 35m: ESM-2 35M (embedded in slots of 32) next to ESM-2 150M")
     args = ap.parse_args(argv)
     if args.layers is None:
-        args.layers = {"3b": 36, "150m": 30, "15b": 48, "8m": 6}.get(args.size, 33)
+        args.layers = {"3b": 36, "150m": 30, "15b": 48, "8m": 6, "35m": 12}.get(args.size, 33)
 
     import torch
     from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
@@ -97,6 +101,11 @@ def main(argv=None):
     elif args.size == "8m":
         samplers = {"esm2_8m": build(models.ESM2_8M, weights.ESM2_T6_CONFIG)}
         rotary, model_cfg = "esm2_8m", weights.ESM2_T6_CONFIG
+    elif args.size == "35m":
+        samplers = {"esm2_35m": build(models.ESM2_35M, weights.ESM2_T12_CONFIG),
+                    "esm2_150m": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=30 if args.layers == 12 else args.layers)}
+        slot = weights.EMBEDDED_WIDTHS[24]["slot"]
+        rotary, model_cfg = "esm2_35m", dict(weights.ESM2_T12_CONFIG, d_model=weights.ESM2_T12_CONFIG["n_heads"] * slot)      # the run shape
     elif args.size == "15b":
         import gc
         half = args.layers // 2 if args.layers < 48 else 0
@@ -154,6 +163,8 @@ def main(argv=None):
 
     out = {"tool": "esm2_bench", "size": args.size, "d_model": d_model, "device": torch.cuda.get_device_name(0), "precision": "bf16",
            "layers": args.layers,
+           **({"d_model_live": 480, "head_width": 24, "head_slot": 32, "esm2_150m_layers": samplers["esm2_150m"].model.cfg["n_layers"]}
+              if args.size == "35m" else {}),
            "iters": args.iters, "warmup": args.warmup, "rounds": args.rounds, "shapes": {}}
     for name, B, L, P in SHAPES:
         T = L + 2
