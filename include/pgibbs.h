@@ -483,6 +483,34 @@ int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_r
 int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
                    float* logits, int64_t n, int d, int V, float eps, int* small_kernel);
 
+/* ---- the draw and the mask scatter (csrc/sample.hip), in every form the engine launches ----
+ * n_steps steps; step s is iteration it = first_iter + s: launch_mask_scatter (mask_idx >= 0), then launch_sample_writeback, both on
+ * the null stream, everything downloaded after each step.
+ *   tokens_inout[n_rows][width]    the token rows before, and after the last step
+ *   logits, V, compact             compact 1: [n_tables][n_sel*P][V], step s reads table it (the engine's LM head at the sampled rows);
+ *                                  compact 0: [n_rows][width][V], shared by all steps (pg_sample_writeback_device's addressing)
+ *   idx[n_tables][n_sel][P]        entries < 0 are padding, bit 30 marks a shadowed duplicate (drawn, not written); step s reads table it
+ *   row_map[n_sel] (NULL: s)       the token row of selected row s
+ *   params                         mask / mask_idx of it are not read (mask_idx below is)
+ *   device_iter 0                  the step's table (idx + it * n_sel * P) and iteration = it are host arguments, d_iter = NULL
+ *   device_iter 1                  what Engine captures, without a graph: launch_graph_state(first_iter, params) once; every step passes
+ *                                  the table base, iteration 0 and the state block as d_iter; launch_iter_counter after each step
+ *   mask_idx                       < 0: no mask step
+ *   permit_out_of_range 1          positions >= width are let through to the kernels' own guards (pos >= width: -1, nothing read or
+ *                                  written); 0: they are refused
+ *   sampled_out[n_steps][n_sel][P] copied to the device before each step, so an entry the kernel leaves unwritten keeps the caller's
+ *                                  pattern; -1 for padding and out-of-range entries
+ *   masked_tokens_out[n_steps][n_rows][width] (NULL: not wanted)   the token rows after each step's mask scatter
+ *   nonfinite_out (NULL: not wanted)   the word the draw kernel sets when a logit it reads is NaN or inf
+ * Refused on the host before a device is looked for, each with its own message: null required pointers, counts < 1, flags other than
+ * 0 / 1, masked_tokens_out without a mask step, n_tables < first_iter + n_steps, n_valid outside 1..32, a valid_idx outside 0..V-1, an
+ * array of more than 2^31 - 1 values, n_sel > n_rows without a row_map, a row_map entry outside 0..n_rows-1, and (without the permit)
+ * a position & 0x3fffffff >= width in any table. */
+int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact, const int32_t* idx,
+                  int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params, int first_iter, int n_steps,
+                  int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out, int32_t* masked_tokens_out,
+                  unsigned* nonfinite_out);
+
 /* ---- the live-width forms of pg_dbg_embed, pg_dbg_layernorm_rows, pg_dbg_gather_ln and pg_dbg_lm_tail (an embedded model's rows) ----
  * Every table, row and vector is d wide in memory; its first d_live features (a multiple of 4, at most d) are the model's own.
  * Statistics, affine and the decoder's dot products run over d_live features -- on them, bit for bit what the same entry gives for

@@ -149,6 +149,8 @@ SIGNATURES = [
     ("pg_dbg_split_rows", c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_int, c_void_p]),
     ("pg_dbg_lm_tail", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
                                POINTER(c_int)]),
+    ("pg_dbg_sample", c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int,
+                              POINTER(SampleParams), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     # embedded models (pg_engine_create_embedded): the live-width forms of pg_dbg_embed / _layernorm_rows / _gather_ln / _lm_tail, and
     # the two host-only entries
     ("pg_embedded_embed_rows", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,

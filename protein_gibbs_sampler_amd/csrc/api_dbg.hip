@@ -822,6 +822,71 @@ int pg_embedded_lm_tail(int device, const float* g, const float* gamma, const fl
   return dbg_lm_tail_rows("pg_embedded_lm_tail", device, g, gamma, beta, embed, out_bias, logits, n, d, V, eps, small_kernel, d_live);
 }
 
+/* ---- the two index ends of an iteration (csrc/sample.hip), in every form the engine launches ----
+ * n_steps times: launch_mask_scatter (mask_idx >= 0), then launch_sample_writeback, on the null stream, downloading after each.
+ * device_iter 0: the step's index table and iteration number are host arguments; 1: the launches Engine::gibbs captures, without the
+ * graph -- launch_graph_state once, the table base, iteration 0 and the state block in every step, launch_iter_counter after it.
+ * Everything is checked on the host before a device is looked for; with permit_out_of_range a position >= width goes through to the
+ * kernels' own guards, which read and write nothing for it. */
+int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact, const int32_t* idx,
+                  int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params, int first_iter, int n_steps,
+                  int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out, int32_t* masked_tokens_out,
+                  unsigned* nonfinite_out) {
+  if (!tokens_inout || !logits || !idx || !params || !sampled_out) return fail(PG_ERR_INVALID, "pg_dbg_sample: bad argument");
+  if (n_rows < 1 || width < 1 || V < 1 || n_tables < 1 || n_sel < 1 || P < 1 || first_iter < 0 || n_steps < 1)
+    return fail(PG_ERR_INVALID, "pg_dbg_sample: bad argument");
+  if (compact < 0 || compact > 1 || device_iter < 0 || device_iter > 1 || permit_out_of_range < 0 || permit_out_of_range > 1)
+    return fail(PG_ERR_INVALID, "pg_dbg_sample: compact, device_iter and permit_out_of_range are 0 or 1");
+  if (masked_tokens_out && mask_idx < 0) return fail(PG_ERR_INVALID, "pg_dbg_sample: masked_tokens_out without a mask step (mask_idx < 0)");
+  if ((int64_t)first_iter + n_steps > n_tables) return fail(PG_ERR_INVALID, "pg_dbg_sample: n_tables must be at least first_iter + n_steps");
+  if (params->n_valid < 1 || params->n_valid > 32) return fail(PG_ERR_INVALID, "pg_dbg_sample: n_valid must be in 1..32");
+  for (int j = 0; j < params->n_valid; ++j)
+    if (params->valid_idx[j] < 0 || params->valid_idx[j] >= V) return fail(PG_ERR_INVALID, "pg_dbg_sample: valid_idx out of range");
+  const double n_d = (double)n_sel * P;
+  if (n_d * n_tables * (compact ? V : 1) > 2147483647.0 || (double)n_rows * width * (compact ? 1 : V) > 2147483647.0)
+    return fail(PG_ERR_INVALID, "pg_dbg_sample: more than 2^31 - 1 values in one array");
+  if (!row_map && n_sel > n_rows) return fail(PG_ERR_INVALID, "pg_dbg_sample: more selected rows than token rows");
+  if (row_map)
+    for (int64_t s = 0; s < n_sel; ++s)
+      if (row_map[s] < 0 || row_map[s] >= n_rows)
+        return fail(PG_ERR_INVALID, "pg_dbg_sample: row_map entry " + std::to_string(row_map[s]) + " is outside the " + std::to_string(n_rows) + " token rows");
+  const size_t n = (size_t)n_sel * P, n_tok = (size_t)n_rows * width;
+  if (!permit_out_of_range)
+    for (size_t i = 0; i < n * n_tables; ++i)
+      if (idx[i] >= 0 && (idx[i] & 0x3fffffff) >= width)
+        return fail(PG_ERR_INVALID, "pg_dbg_sample: target position " + std::to_string(idx[i] & 0x3fffffff) + " is out of range for a token row of width " +
+                                        std::to_string(width));
+  Dbg d;
+  int rc = d.open(device);
+  if (rc) return rc;
+  int32_t* dtok = d.up(tokens_inout, n_tok);
+  const float* dlog = d.up(logits, compact ? n * n_tables * V : n_tok * V);
+  const int32_t* didx = d.up(idx, n * n_tables);
+  const int32_t* dmap = d.up(row_map, (size_t)n_sel);
+  int32_t* dout = d.alloc<int32_t>(n);
+  int32_t* dstate = device_iter ? (int32_t*)d.alloc<char>(graph_state_bytes()) : nullptr;
+  unsigned* dnf = nonfinite_out ? d.alloc<unsigned>(1) : nullptr;
+  if ((rc = d.check(kCopyFailed))) return rc;
+  if (device_iter && (rc = launch_graph_state(nullptr, dstate, first_iter, params))) return rc;
+  for (int s = 0; s < n_steps; ++s) {
+    const int it = first_iter + s;
+    const int32_t* idx_s = device_iter ? didx : didx + (size_t)it * n;      // the kernels add *d_iter tables themselves
+    if (mask_idx >= 0) {
+      if ((rc = launch_mask_scatter(nullptr, dtok, width, idx_s, dmap, n_sel, P, mask_idx, dstate))) return rc;
+      if (masked_tokens_out && (rc = d.down(masked_tokens_out + (size_t)s * n_tok, dtok, n_tok))) return rc;
+    }
+    d.put(dout, sampled_out + (size_t)s * n, n);      // the caller's pattern: an entry the kernel does not write keeps it
+    if ((rc = d.check(kCopyFailed))) return rc;
+    const float* lg = compact ? dlog + (size_t)it * n * V : dlog;
+    if ((rc = launch_sample_writeback(nullptr, dtok, width, lg, V, compact, idx_s, dmap, n_sel, P, params, device_iter ? 0 : it, dout, dstate, dnf)))
+      return rc;
+    if ((rc = d.down(sampled_out + (size_t)s * n, dout, n))) return rc;
+    if (device_iter && (rc = launch_iter_counter(nullptr, dstate, false, 0))) return rc;
+  }
+  if ((rc = d.down(tokens_inout, dtok, n_tok))) return rc;
+  return nonfinite_out ? d.down(nonfinite_out, dnf, 1) : PG_OK;
+}
+
 /* ---- embedded models: the host side of pg_engine_create_embedded, no device ---- */
 int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
                       float* image, int64_t image_numel) {

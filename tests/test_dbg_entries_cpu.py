@@ -25,6 +25,12 @@ def _i32(*v):
     return np.asarray(v, dtype=np.int32)
 
 
+def _params(n_valid=20, first_valid=4):
+    p = _lib.make_sample_params(False, 32, 0, 0, None, list(range(first_valid, first_valid + 20)), 0)
+    p.n_valid = n_valid
+    return ctypes.byref(p)
+
+
 # name -> (valid tiny arguments, index of a required pointer, the message of the refusal when that pointer is null).
 # M = 4, d = 64, B = 1, T = 16, H = 1; the two benches take the smallest shapes they accept.
 def _cases():
@@ -60,6 +66,9 @@ def _cases():
         "pg_dbg_split_rows": ([0, _z(4, 64), _z(4, 192, dt=np.uint16), 4, 4, 64, 1.0, 0, None], 1, "pg_dbg_split_rows: bad argument"),
         "pg_dbg_lm_tail": ([0, _z(4, 64), None, None, _z(33, 64), _z(33), _z(4, 33), 4, 64, 33, 1e-5, None], 1,
                            "pg_dbg_lm_tail: bad argument"),
+        # 2 token rows of 8, compact logits [1][2 * 2][33], one index table [1][2][2], one step, no mask step
+        "pg_dbg_sample": ([0, _z(2, 8, dt=np.int32), 2, 8, _z(1, 4, 33), 33, 1, _i32(1, 2, 3, -1), 1, None, 2, 2, _params(), 0, 1, 0, -1, 0,
+                           _z(1, 2, 2, dt=np.int32), None, None], 4, "pg_dbg_sample: bad argument"),
     }
 
 
@@ -162,6 +171,34 @@ LATE = {
     "gemm_ln_eps_nan": ("pg_dbg_gemm_ln", {6: float("nan")}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: eps must not be negative"),
     "gemm_ln_out_rows": ("pg_dbg_gemm_ln", {10: 15}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: out_rows must be in Mi ... 4096"),
     "gemm_ln_out_rows_17_live": ("pg_dbg_gemm_ln", {10: 31, 11: 17}, _lib.PG_ERR_INVALID, "pg_dbg_gemm_ln: out_rows must be in Mi ... 4096"),
+    "sample_tokens": ("pg_dbg_sample", {1: None}, _lib.PG_ERR_INVALID, "pg_dbg_sample: bad argument"),
+    "sample_idx": ("pg_dbg_sample", {7: None}, _lib.PG_ERR_INVALID, "pg_dbg_sample: bad argument"),
+    "sample_params": ("pg_dbg_sample", {12: None}, _lib.PG_ERR_INVALID, "pg_dbg_sample: bad argument"),
+    "sample_sampled_out": ("pg_dbg_sample", {18: None}, _lib.PG_ERR_INVALID, "pg_dbg_sample: bad argument"),
+    "sample_no_steps": ("pg_dbg_sample", {14: 0}, _lib.PG_ERR_INVALID, "pg_dbg_sample: bad argument"),
+    "sample_negative_first_iter": ("pg_dbg_sample", {13: -1}, _lib.PG_ERR_INVALID, "pg_dbg_sample: bad argument"),
+    "sample_compact_2": ("pg_dbg_sample", {6: 2}, _lib.PG_ERR_INVALID, "pg_dbg_sample: compact, device_iter and permit_out_of_range are 0 or 1"),
+    "sample_device_iter_2": ("pg_dbg_sample", {15: 2}, _lib.PG_ERR_INVALID,
+                             "pg_dbg_sample: compact, device_iter and permit_out_of_range are 0 or 1"),
+    "sample_permit_minus_1": ("pg_dbg_sample", {17: -1}, _lib.PG_ERR_INVALID,
+                              "pg_dbg_sample: compact, device_iter and permit_out_of_range are 0 or 1"),
+    "sample_masked_out_without_mask": ("pg_dbg_sample", {19: _z(1, 2, 8, dt=np.int32)}, _lib.PG_ERR_INVALID,
+                                       "pg_dbg_sample: masked_tokens_out without a mask step (mask_idx < 0)"),
+    "sample_too_few_tables": ("pg_dbg_sample", {13: 1}, _lib.PG_ERR_INVALID, "pg_dbg_sample: n_tables must be at least first_iter + n_steps"),
+    "sample_too_few_tables_for_the_steps": ("pg_dbg_sample", {14: 2, 18: _z(2, 2, 2, dt=np.int32)}, _lib.PG_ERR_INVALID,
+                                            "pg_dbg_sample: n_tables must be at least first_iter + n_steps"),
+    "sample_n_valid_0": ("pg_dbg_sample", {12: _params(0)}, _lib.PG_ERR_INVALID, "pg_dbg_sample: n_valid must be in 1..32"),
+    "sample_n_valid_33": ("pg_dbg_sample", {12: _params(33)}, _lib.PG_ERR_INVALID, "pg_dbg_sample: n_valid must be in 1..32"),
+    "sample_valid_idx_is_V": ("pg_dbg_sample", {12: _params(20, 14)}, _lib.PG_ERR_INVALID, "pg_dbg_sample: valid_idx out of range"),
+    "sample_valid_idx_negative": ("pg_dbg_sample", {12: _params(20, -1)}, _lib.PG_ERR_INVALID, "pg_dbg_sample: valid_idx out of range"),
+    "sample_more_selected_than_token_rows": ("pg_dbg_sample", {2: 1}, _lib.PG_ERR_INVALID, "pg_dbg_sample: more selected rows than token rows"),
+    "sample_row_map_entry": ("pg_dbg_sample", {9: _i32(0, 2)}, _lib.PG_ERR_INVALID, "pg_dbg_sample: row_map entry 2 is outside the 2 token rows"),
+    "sample_row_map_negative": ("pg_dbg_sample", {9: _i32(-1, 0)}, _lib.PG_ERR_INVALID,
+                                "pg_dbg_sample: row_map entry -1 is outside the 2 token rows"),
+    "sample_position_is_width": ("pg_dbg_sample", {7: _i32(1, 2, 8, -1)}, _lib.PG_ERR_INVALID,
+                                 "pg_dbg_sample: target position 8 is out of range for a token row of width 8"),
+    "sample_shadowed_position_past_width": ("pg_dbg_sample", {7: _i32(1, 2, 3, 9 | 1 << 30)}, _lib.PG_ERR_INVALID,
+                                            "pg_dbg_sample: target position 9 is out of range for a token row of width 8"),
     "gemm_bench_variant_90": ("pg_dbg_gemm_bench", {5: 90}, _lib.PG_ERR_INVALID, "variant 90: K = 3 x depth, fp32 epilogues"),
 }
 
