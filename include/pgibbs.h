@@ -300,6 +300,46 @@ int pg_sample_writeback_device(void* stream, int32_t* d_tokens, int64_t n_rows, 
                                int V, const int32_t* d_idx, const int32_t* d_row_map, int64_t n_sel, int P,
                                const pg_sample_params* params, int iteration, int32_t* d_sampled_tokens);
 
+/* ---- guided draws: "pg_draw v2" (not in the reference) ------------------------------------------------
+ * Three ways to steer the draw, each optional; with none of them every bit is pg_draw v1's.  For one draw at token row `trow`,
+ * position `pos`, call-local iteration `it`, over the valid list j = 0 .. n_valid-1:
+ *   x_j = logits[valid_idx[j]]                      (the non-finite check applies to these raw logits)
+ *   x_j = fl32(x_j + bias[brow][pos][j])            brow = 0 when bias_rows == 1, else trow; -inf = residue j forbidden here
+ *   x_j = fl32(x_j / T)                             T = temperatures[it] with a schedule -- pg_sample_params.temperature is then not
+ *                                                   read --, else as v1
+ *   stable descending rank and k as v1, then k = min(k, number of x_j > -inf): the forbidden entries sort last and are cut
+ *   e_r, c_j as v1;  top-p (set, < 1, not in burn-in -- as top_k): q = fl32(top_p c_{k-1}), k' = min(k, 1 + #{j < k : c_j < q})
+ *   t = fl32(u c_{k'-1}); the first j < k' with c_j > t, else k' - 1.  Philox counter, key and u are v1's.
+ * pg_draw_guide holds HOST pointers: bias fp32 [bias_rows][width][n_valid] indexed by valid-list position (NULL: none; width and
+ * n_valid are then not read), temperatures fp32 [n_temperatures] (NULL: none), top_p (NaN = off; 1 = the whole list).
+ * pg_engine_set_draw_guide checks the tables, uploads them once and makes every later Gibbs entry of the engine -- pg_esm_gibbs_run[_device],
+ * pg_msa_gibbs_run[_device], pg_msa_gibbs_single_run, pg_msa_gibbs_single_batch_run (these two: it = the step number; a per-row table has
+ * B * R rows) -- draw v2 until it is set again; NULL, or a guide with nothing set, clears it.  The guide is read when a call's launches
+ * run, so it stays set until the calls made under it have been synchronised.  PG_ERR_INVALID at set time, each with its own message, the
+ * first five before a device is touched: n_valid outside 1..32 or width / bias_rows < 1 (with a bias), a NaN or +inf bias entry, a (row,
+ * position) with no entry > -inf, a temperature that is not finite and > 0, top_p outside (0, 1].  PG_ERR_INVALID at run time, before
+ * the call launches anything: bias width != T (or C), bias n_valid != params->n_valid, bias_rows neither 1 nor the call's token rows
+ * (B, or B * R), n_temperatures < n_iters (or n_steps).  The device pointers travel in the graph state block: the captured iteration
+ * of the few-token ESM loop is replayed across guided calls with different tables (one capture for guided calls, one for unguided). */
+typedef struct {
+  const float* bias;
+  int64_t bias_rows;
+  int width;
+  int n_valid;
+  const float* temperatures;
+  int n_temperatures;
+  float top_p;
+} pg_draw_guide;
+int pg_engine_set_draw_guide(pg_engine*, const pg_draw_guide* guide_or_null);
+/* pg_sample_writeback_device with a guide whose tables are DEVICE pointers (plug-in models): d_bias [bias_rows][width][n_valid of params]
+ * or NULL, bias_rows 1 or n_rows; d_temperatures [n_temperatures] or NULL, read at `iteration`, which must be < n_temperatures; top_p NaN =
+ * off, else in (0, 1].  It cannot check what the tables hold: the caller guarantees bias entries finite or -inf with one > -inf per
+ * (row, position), and temperatures finite and > 0 (a cell with nothing allowed yields its first entry; nothing is read out of bounds). */
+int pg_sample_writeback_guided_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const float* d_logits, int V,
+                                      const int32_t* d_idx, const int32_t* d_row_map, int64_t n_sel, int P,
+                                      const pg_sample_params* params, int iteration, int32_t* d_sampled_tokens, const float* d_bias,
+                                      int64_t bias_rows, const float* d_temperatures, int n_temperatures, float top_p);
+
 /* ---- multi-GPU tail: the one collective of a sharded job -------------------------------------------
  * Chains / MSAs / templates are independent, so a job shards as contiguous blocks over the GPUs of a node with NO data-path
  * collective; what the reference untokenises at the end of a batch -- the token buffer of ALL chains,
@@ -510,6 +550,16 @@ int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, 
                   int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params, int first_iter, int n_steps,
                   int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out, int32_t* masked_tokens_out,
                   unsigned* nonfinite_out);
+/* pg_dbg_sample with a draw guide (host pointers, as pg_engine_set_draw_guide takes them; NULL or nothing set: pg_dbg_sample's bits): the
+ * same addressing forms, device_iter modes and outputs.  Step s draws at call-local iteration first_iter + s, so a schedule needs
+ * n_temperatures >= first_iter + n_steps; a per-row bias table has n_rows rows.  With device_iter 1 the iteration AND the guide's device
+ * pointers are read from the state block.  Refusals: pg_dbg_sample's, then the guide's set-time and run-time ones, all on the host
+ * before a device is looked for.  pg_guided_sizeof_draw_guide: sizeof(pg_draw_guide), for bindings that mirror the struct. */
+int pg_guided_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact,
+                         const int32_t* idx, int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params,
+                         int first_iter, int n_steps, int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out,
+                         int32_t* masked_tokens_out, unsigned* nonfinite_out, const pg_draw_guide* guide);
+int pg_guided_sizeof_draw_guide(void);
 
 /* ---- the live-width forms of pg_dbg_embed, pg_dbg_layernorm_rows, pg_dbg_gather_ln and pg_dbg_lm_tail (an embedded model's rows) ----
  * Every table, row and vector is d wide in memory; its first d_live features (a multiple of 4, at most d) are the model's own.

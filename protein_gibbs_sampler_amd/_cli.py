@@ -28,6 +28,34 @@ def parse_line_args(text):
     return out
 
 
+GUIDE_EPILOG = """Guided draws (not in the reference; see INTEGRATION.md): top_p (nucleus truncation, in (0, 1]),
+temperature_schedule (one temperature per iteration, or 'kind:t_start:t_end' with kind linear or geometric),
+position_bias ({position: {residue: bias}}), allowed_residues ({position: 'DE'}), forbidden_residues ('C', or {position: 'C'});
+positions are token positions, as for indexes (residue 0 behind <cls> is position 1)."""
+
+
+def add_guide_args(parser):
+    """--top_p / --temperature_schedule / --forbid of the front ends that take sampler arguments as flags (guided draws)."""
+    parser.add_argument("--top_p", type=float, default=None, help="nucleus truncation of the draw after burn-in: sample from the "
+                        "smallest set of most probable residues whose probability reaches this value, in (0, 1] (default: off).")
+    parser.add_argument("--temperature_schedule", type=str, default=None, metavar="kind:t0:t1",
+                        help="anneal the sampling temperature from t0 to t1 over the iterations; kind is linear or geometric (default: off).")
+    parser.add_argument("--forbid", type=str, default=None, metavar="RESIDUES", help="residues that are never drawn, at any position, "
+                        "e.g. C (default: none).")
+
+
+def guide_kwargs(args):
+    """The sampler keyword arguments of the flags of add_guide_args that were given."""
+    kw = {}
+    if getattr(args, "top_p", None) is not None:
+        kw["top_p"] = args.top_p
+    if getattr(args, "temperature_schedule", None) is not None:
+        kw["temperature_schedule"] = args.temperature_schedule
+    if getattr(args, "forbid", None):
+        kw["forbidden_residues"] = args.forbid
+    return kw
+
+
 def add_engine_args(parser):
     parser.add_argument("--checkpoint", default=None, help="fair-esm .pt checkpoint to load (default: torch hub cache; it is an "
                         "error if none is found)")

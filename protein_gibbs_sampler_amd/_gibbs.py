@@ -208,7 +208,7 @@ def _current_stream_ptr(device):
 
 
 def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=None, mask_row_map=None,
-                    sample_flags=None):
+                    sample_flags=None, guide=None):
     """Gibbs loop for a plug-in model whose forward is not the HIP engine (any callable
     tokens[int64, device] -> {"logits": float tensor}): mask scatter and draw/write-back are the HIP kernels
     `pg_mask_scatter_device` / `pg_sample_writeback_device`; the token buffer stays on the device.
@@ -216,7 +216,9 @@ def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=N
     tokens_i64: torch int64 tensor [..rows.., width] (any device); table int32 [n_iters, n_sel, P];
     row_map: optional int32 [n_sel] token-row sampled for each selected row (generate_single);
     mask_row_map: token-row masked for each selected row (defaults to row_map; generate_single masks row -1);
-    sample_flags: optional per-iteration override of `sample` (generate_single's pass_num < burn_in).
+    sample_flags: optional per-iteration override of `sample` (generate_single's pass_num < burn_in);
+    guide: optional guides.CompiledGuide -- the draw is then `pg_sample_writeback_guided_device` (pg_draw v2) on device copies
+    of its tables, iteration `it` reading temperature `it` of a schedule.
     Returns the final tokens as a torch int64 CPU tensor of the input shape.
     """
     if not torch.cuda.is_available():
@@ -234,6 +236,16 @@ def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=N
     d_mrowmap = (torch.from_numpy(np.ascontiguousarray(mask_row_map, dtype=np.int32)).to(dev)
                  if mask_row_map is not None else None)
     mrm_ptr = _dptr(d_mrowmap) if d_mrowmap is not None else rm_ptr
+    if guide is not None and guide.empty:
+        guide = None
+    if guide is not None:
+        if guide.temperatures is not None and len(guide.temperatures) < n_iters:
+            raise ValueError("temperature_schedule has %d entries, the call runs %d iterations" % (len(guide.temperatures), n_iters))
+        d_bias = torch.from_numpy(guide.bias).to(dev) if guide.bias is not None else None
+        d_temps = torch.from_numpy(guide.temperatures).to(dev) if guide.temperatures is not None else None
+        guide_args = (_dptr(d_bias) if d_bias is not None else None, 0 if d_bias is None else d_bias.shape[0],
+                      _dptr(d_temps) if d_temps is not None else None, 0 if d_temps is None else d_temps.shape[0],
+                      float("nan") if guide.top_p is None else guide.top_p)
     with torch.cuda.device(dev):
         for it in range(n_iters):
             stream = _current_stream_ptr(dev)
@@ -247,40 +259,47 @@ def run_plugin_loop(model_callable, tokens_i64, table, params, device, row_map=N
             V = out.shape[-1]
             if sample_flags is not None:
                 params.burnin = _lib.INT32_MAX if sample_flags[it] else 0
-            _lib.check(L.pg_sample_writeback_device(stream, _dptr(tok), n_rows, width, _dptr(out), V, idx_ptr, rm_ptr, n_sel, P,
-                                                    ctypes.byref(params), it, None))
+            if guide is not None:
+                _lib.check(L.pg_sample_writeback_guided_device(stream, _dptr(tok), n_rows, width, _dptr(out), V, idx_ptr, rm_ptr, n_sel,
+                                                               P, ctypes.byref(params), it, None, *guide_args))
+            else:
+                _lib.check(L.pg_sample_writeback_device(stream, _dptr(tok), n_rows, width, _dptr(out), V, idx_ptr, rm_ptr, n_sel, P,
+                                                        ctypes.byref(params), it, None))
         torch.cuda.synchronize(dev)
     return tok.to(device="cpu", dtype=torch.int64).reshape(shape)
 
 
-def run_gibbs_batch(sampler, ctx, batch, table, params, row_id_base, rows_per_item, record_plugin=False):
+def run_gibbs_batch(sampler, ctx, batch, table, params, row_id_base, rows_per_item, record_plugin=False, guide=None):
     """One batch of either generate(): `batch` (torch int64 [B, T] or [B, R, C]) through every iteration of `table`
     (int32 [iters, B, P] / [iters, B, R, P]); returns the final tokens as a torch int64 tensor of the same shape.
     Engine models: one native call -- or, with a DistContext `ctx`, this rank's block of the batch (announced to the engine as
     a shard of a B-item job) and one gather; row_id_base / rows_per_item are the Philox row id of the batch's first row and
     the ids one item consumes.  Plug-in models: the device loop over the table flattened to [iters, rows, P].
-    sampler.record appends the run to sampler.last_run; a plug-in run only when the caller asks for it (record_plugin)."""
+    sampler.record appends the run to sampler.last_run; a plug-in run only when the caller asks for it (record_plugin).
+    guide (guides.CompiledGuide or None): the draws are pg_draw v2 under it -- set on the engine around the native call and cleared
+    after it whatever happens, or handed to the plug-in loop."""
     lm = sampler.model.model
     if not isinstance(lm, NativeMaskedLM):
         flat = table.reshape(table.shape[0], int(np.prod(table.shape[1:-1])), table.shape[-1]) if table.ndim > 3 else table
-        batch = run_plugin_loop(lm, batch, flat, params, sampler.device)
+        batch = run_plugin_loop(lm, batch, flat, params, sampler.device, guide=guide)
         if sampler.record and record_plugin:
             sampler.last_run.append(dict(table=table, tokens=batch.numpy().copy()))
         return batch
     tok = np.ascontiguousarray(batch.numpy(), dtype=np.int32)
-    if ctx is not None:
-        def run_block(ltok, ltable, base):
-            params.row_id_base = base & 0xFFFFFFFF
-            lm.set_job_items(batch.shape[0])      # shard of a batch.shape[0]-item job
-            try:
-                lm.gibbs_run(ltok, ltable, params)
-            finally:
-                lm.set_job_items(0)
-        tok = sharding.run_sharded(ctx, tok, table, row_id_base, rows_per_item, run_block, sampler.device, guard=lm)
-    else:
-        lg, st = lm.gibbs_run(tok, table, params, want_logits=sampler.record, want_tokens=sampler.record)
-        if sampler.record:
-            sampler.last_run.append(dict(table=table, sampled_logits=lg, sampled_tokens=st, tokens=tok.copy()))
+    with (lm.draw_guide(guide) if guide is not None else contextlib.nullcontext()):      # unguided: the engine object is not touched
+        if ctx is not None:
+            def run_block(ltok, ltable, base):
+                params.row_id_base = base & 0xFFFFFFFF
+                lm.set_job_items(batch.shape[0])      # shard of a batch.shape[0]-item job
+                try:
+                    lm.gibbs_run(ltok, ltable, params)
+                finally:
+                    lm.set_job_items(0)
+            tok = sharding.run_sharded(ctx, tok, table, row_id_base, rows_per_item, run_block, sampler.device, guard=lm)
+        else:
+            lg, st = lm.gibbs_run(tok, table, params, want_logits=sampler.record, want_tokens=sampler.record)
+            if sampler.record:
+                sampler.last_run.append(dict(table=table, sampled_logits=lg, sampled_tokens=st, tokens=tok.copy()))
     return torch.from_numpy(tok.astype(np.int64))
 
 

@@ -48,6 +48,12 @@ class SampleParams(Structure):
                 ("rng_stream", c_uint32), ("row_id_base", c_uint32), ("iter_base", c_int32)]
 
 
+class DrawGuideStruct(Structure):
+    """pg_draw_guide (include/pgibbs.h): host pointers to the tables of a guided draw (pg_draw v2)."""
+    _fields_ = [("bias", POINTER(c_float)), ("bias_rows", c_int64), ("width", c_int), ("n_valid", c_int),
+                ("temperatures", POINTER(c_float)), ("n_temperatures", c_int), ("top_p", c_float)]
+
+
 _lib = None
 
 # (name, restype, argtypes) -- one row per symbol of include/pgibbs.h
@@ -105,6 +111,16 @@ SIGNATURES = [
     ("pg_mask_scatter_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int]),
     ("pg_sample_writeback_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                            c_int, POINTER(SampleParams), c_int, c_void_p]),
+    ("pg_engine_set_draw_guide", c_int, [c_void_p, POINTER(DrawGuideStruct)]),
+    ("pg_sample_writeback_guided_device", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                                  c_int, POINTER(SampleParams), c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                                  c_float]),
+    # the guided draw's own debug entry (pg_dbg_sample with a guide) and the size of pg_draw_guide; named pg_guided_*, as the embedded
+    # models' entries are pg_embedded_*: the pg_dbg_* rows are the set tests/test_dbg_entries_cpu.py pins case by case
+    ("pg_guided_dbg_sample", c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int,
+                                     POINTER(SampleParams), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     POINTER(DrawGuideStruct)]),
+    ("pg_guided_sizeof_draw_guide", c_int, []),
     ("pg_comm_unique_id", c_int, [c_void_p]),
     ("pg_comm_create", c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),
     ("pg_comm_destroy", None, [c_void_p]),
@@ -221,3 +237,25 @@ def make_sample_params(mask, mask_idx, top_k, burnin, temperature, valid_idx, rn
     p.row_id_base = int(row_id_base) & 0xFFFFFFFF
     p.iter_base = int(iter_base)
     return p
+
+
+def make_draw_guide(bias=None, temperatures=None, top_p=None):
+    """(pg_draw_guide, keep): the struct over the caller's tables -- bias float32 [bias_rows, width, n_valid] or None, temperatures
+    float32 [n] or None, top_p float or None -- and the arrays it points into, which must outlive its use."""
+    import numpy as np
+    g = DrawGuideStruct()
+    keep = []
+    if bias is not None:
+        b = np.ascontiguousarray(bias, dtype=np.float32)
+        if b.ndim != 3:
+            raise ValueError("a draw guide's bias table is [bias_rows, width, n_valid]")
+        keep.append(b)
+        g.bias = b.ctypes.data_as(POINTER(c_float))
+        g.bias_rows, g.width, g.n_valid = b.shape
+    if temperatures is not None:
+        t = np.ascontiguousarray(temperatures, dtype=np.float32).reshape(-1)
+        keep.append(t)
+        g.temperatures = t.ctypes.data_as(POINTER(c_float))
+        g.n_temperatures = len(t)
+    g.top_p = float("nan") if top_p is None else float(top_p)
+    return g, keep

@@ -206,6 +206,15 @@ int pg_engine_set_job_items(pg_engine* h, int64_t job_items) {
   return PG_OK;
 }
 
+int pg_engine_set_draw_guide(pg_engine* h, const pg_draw_guide* guide) {
+  // what the tables hold is refused first: it needs neither a device nor, for that matter, an engine
+  if (guide)
+    if (int rc = check_draw_guide_tables(guide, "pg_engine_set_draw_guide")) return rc;
+  if (!h) return fail(PG_ERR_INVALID, "null engine");
+  DeviceGuard g(h->e.device);
+  return h->e.set_draw_guide(guide);
+}
+
 int pg_engine_get_stat(pg_engine* h, const char* name, int64_t* value) {
   if (!h || !name || !value) return fail(PG_ERR_INVALID, "pg_engine_get_stat: null argument");
   if (!strcmp(name, "graph_captures")) *value = h->e.stat_graph_captures;
@@ -246,6 +255,7 @@ int pg_esm_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int T,
   int rc = check_params(params, h->e.cfg.vocab);
   if (rc) return rc;
   Engine& e = h->e;
+  if ((rc = check_draw_guide(e.draw_guide(), "pg_esm_gibbs_run_device", T, params->n_valid, B, n_iters))) return rc;
   DeviceGuard g(e.device);
   // An earlier asynchronous call has reported a barrier timeout of the persistent trunk: repair (restore the logged token rows,
   // run the logged calls again on the per-layer launches) BEFORE this call is queued on top of those tokens -- whatever this
@@ -273,6 +283,7 @@ static int esm_gibbs_run_once(pg_engine* h, int32_t* tokens_inout, int B, int T,
   if (B < 0 || T < 1 || P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "bad shape");
   if (B == 0) return PG_OK;
   Engine& e = h->e;
+  if ((rc = check_draw_guide(e.draw_guide(), "pg_esm_gibbs_run", T, params->n_valid, B, n_iters))) return rc;
   DeviceGuard g(e.device);
   const size_t n_draws = (size_t)B * P * n_iters;
   if (n_draws && (rc = check_idx_table(target_idx, n_draws, T, "pg_esm_gibbs_run"))) return rc;
@@ -305,6 +316,7 @@ int pg_msa_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, c
   if (B < 0 || R < 1 || C < 1 || P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "bad shape");
   if (B == 0) return PG_OK;
   Engine& e = h->e;
+  if ((rc = check_draw_guide(e.draw_guide(), "pg_msa_gibbs_run", C, params->n_valid, (int64_t)B * R, n_iters))) return rc;
   DeviceGuard g(e.device);
   const size_t n_draws = (size_t)B * R * P * n_iters;
   if (n_draws && (rc = check_idx_table(target_idx, n_draws, C, "pg_msa_gibbs_run"))) return rc;
@@ -314,9 +326,11 @@ int pg_msa_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, c
                      });
 }
 
-int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
-                                  const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
-                                  const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
+// the body of pg_msa_gibbs_single_batch_run; it runs a batch too large for the row-split scratch as chunks of itself, below the public
+// entry's check of the draw guide against the WHOLE call (a chunk has fewer token rows than a per-row bias table)
+static int single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
+                            const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
+                            const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
   if (!h || !tokens_inout || (n_steps > 0 && (!step_sample_flag || (!step_idx && P_max > 0))))
     return fail(PG_ERR_INVALID, "pg_msa_gibbs_single_batch_run: null argument");
   if (B < 0 || R < 1 || C < 1 || P_max < 0 || n_steps < 0) return fail(PG_ERR_INVALID, "bad shape");
@@ -346,9 +360,14 @@ int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, in
           memcpy(idx_c.data() + (size_t)s2 * nb * P_max, step_idx + ((size_t)s2 * B + b0) * P_max, (size_t)nb * P_max * 4);
         if (sampled_logits) lg_c.assign((size_t)n_steps * nb * P_max * V + 1, 0.f);
         if (sampled_tokens) tok_c.assign((size_t)n_steps * nb * P_max + 1, 0);
-        if ((rc = pg_msa_gibbs_single_batch_run(h, tokens_inout + (size_t)b0 * R * C, nb, R, C, mask_row, target_row, idx_c.data(),
-                                                step_sample_flag, n_steps, P_max, params + b0, sampled_logits ? lg_c.data() : nullptr,
-                                                sampled_tokens ? tok_c.data() : nullptr))) return rc;
+        {
+          // a per-row bias table is indexed by the token row of the whole call: this chunk's rows start b0 * R rows further on
+          struct GuideRows { DrawGuideDev& g; const float* bias; ~GuideRows() { g.bias = bias; } } rows{e.guide, e.guide.bias};
+          if (e.guide.bias && e.guide.bias_rows > 1) e.guide.bias += (size_t)b0 * R * C * e.guide.n_valid;
+          rc = single_batch_run(h, tokens_inout + (size_t)b0 * R * C, nb, R, C, mask_row, target_row, idx_c.data(), step_sample_flag, n_steps,
+                                P_max, params + b0, sampled_logits ? lg_c.data() : nullptr, sampled_tokens ? tok_c.data() : nullptr);
+        }
+        if (rc) return rc;
         for (int s2 = 0; s2 < n_steps && P_max > 0; ++s2) {
           if (sampled_logits) memcpy(sampled_logits + ((size_t)s2 * B + b0) * P_max * V, lg_c.data() + (size_t)s2 * nb * P_max * V, (size_t)nb * P_max * V * 4);
           if (sampled_tokens) memcpy(sampled_tokens + ((size_t)s2 * B + b0) * P_max, tok_c.data() + (size_t)s2 * nb * P_max, (size_t)nb * P_max * 4);
@@ -363,6 +382,16 @@ int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, in
                      [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
                        return e.msa_single_device(d_tok, B, R, C, mask_row, target_row, d_idx, step_sample_flag, n_steps, P_max, params, d_lg, d_st);
                      });
+}
+
+int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
+                                  const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
+                                  const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
+  if (h && params && B > 0 && R > 0 && n_steps > 0)
+    for (int b = 0; b < B; ++b)
+      if (int rc = check_draw_guide(h->e.draw_guide(), "pg_msa_gibbs_single_batch_run", C, params[b].n_valid, (int64_t)B * R, n_steps)) return rc;
+  return single_batch_run(h, tokens_inout, B, R, C, mask_row, target_row, step_idx, step_sample_flag, n_steps, P_max, params, sampled_logits,
+                          sampled_tokens);
 }
 
 // generate_single == the batched form with one template
@@ -382,6 +411,7 @@ int pg_msa_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int R,
     return fail(PG_ERR_INVALID, "pg_msa_gibbs_run_device: null argument");
   int rc = check_params(params, h->e.cfg.vocab);
   if (rc) return rc;
+  if ((rc = check_draw_guide(h->e.draw_guide(), "pg_msa_gibbs_run_device", C, params->n_valid, (int64_t)B * R, n_iters))) return rc;
   DeviceGuard g(h->e.device);
   return h->e.msa_gibbs_device(d_tokens_inout, B, R, C, d_target_idx, n_iters, P, params, d_sampled_logits, d_sampled_tokens);
 }
@@ -540,6 +570,28 @@ int pg_sample_writeback_device(void* stream, int32_t* d_tokens, int64_t n_rows, 
   if (n_rows < 0 || width < 1 || n_sel < 0 || P < 0 || V < 1) return fail(PG_ERR_INVALID, "bad shape");
   return launch_sample_writeback((hipStream_t)stream, d_tokens, width, d_logits, V, 0, d_idx, d_row_map, n_sel, P, params,
                                  iteration, d_sampled_tokens);
+}
+
+int pg_sample_writeback_guided_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const float* d_logits, int V,
+                                      const int32_t* d_idx, const int32_t* d_row_map, int64_t n_sel, int P,
+                                      const pg_sample_params* params, int iteration, int32_t* d_sampled_tokens, const float* d_bias,
+                                      int64_t bias_rows, const float* d_temperatures, int n_temperatures, float top_p) {
+  if (!d_tokens || !d_logits || (!d_idx && n_sel * P > 0)) return fail(PG_ERR_INVALID, "pg_sample_writeback_guided_device: null argument");
+  int rc = check_params(params, V);
+  if (rc) return rc;
+  if (n_rows < 0 || width < 1 || n_sel < 0 || P < 0 || V < 1) return fail(PG_ERR_INVALID, "bad shape");
+  if (top_p == top_p && !(top_p > 0.f && top_p <= 1.0f))
+    return fail(PG_ERR_INVALID, "pg_sample_writeback_guided_device: top_p must be in (0, 1] (NaN = off)");
+  if (d_temperatures && iteration < 0) return fail(PG_ERR_INVALID, "pg_sample_writeback_guided_device: negative iteration with a temperature schedule");
+  DrawGuideDev g;
+  g.bias = d_bias;
+  if (d_bias) { g.bias_rows = bias_rows; g.width = width; g.n_valid = params->n_valid; }
+  g.temps = d_temperatures;
+  g.n_temps = d_temperatures ? n_temperatures : 0;
+  g.top_p = top_p;
+  if ((rc = check_draw_guide(&g, "pg_sample_writeback_guided_device", width, params->n_valid, n_rows, (int64_t)iteration + 1))) return rc;
+  return launch_sample_writeback((hipStream_t)stream, d_tokens, width, d_logits, V, 0, d_idx, d_row_map, n_sel, P, params, iteration,
+                                 d_sampled_tokens, nullptr, nullptr, &g);
 }
 
 // ---- measurement ----------------------------------------------------------------------------

@@ -832,6 +832,18 @@ int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, 
                   int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params, int first_iter, int n_steps,
                   int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out, int32_t* masked_tokens_out,
                   unsigned* nonfinite_out) {
+  return pg_guided_dbg_sample(device, tokens_inout, n_rows, width, logits, V, compact, idx, n_tables, row_map, n_sel, P, params, first_iter,
+                              n_steps, device_iter, mask_idx, permit_out_of_range, sampled_out, masked_tokens_out, nonfinite_out, nullptr);
+}
+
+int pg_guided_sizeof_draw_guide(void) { return (int)sizeof(pg_draw_guide); }
+
+/* pg_dbg_sample with a draw guide (pg_draw v2): the guide's tables are checked as pg_engine_set_draw_guide checks them and against this
+ * call's shape as the Gibbs entries do, then uploaded; every draw launch is given them, and with device_iter 1 the state block holds them. */
+int pg_guided_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact,
+                         const int32_t* idx, int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params,
+                         int first_iter, int n_steps, int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out,
+                         int32_t* masked_tokens_out, unsigned* nonfinite_out, const pg_draw_guide* guide) {
   if (!tokens_inout || !logits || !idx || !params || !sampled_out) return fail(PG_ERR_INVALID, "pg_dbg_sample: bad argument");
   if (n_rows < 1 || width < 1 || V < 1 || n_tables < 1 || n_sel < 1 || P < 1 || first_iter < 0 || n_steps < 1)
     return fail(PG_ERR_INVALID, "pg_dbg_sample: bad argument");
@@ -856,9 +868,19 @@ int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, 
       if (idx[i] >= 0 && (idx[i] & 0x3fffffff) >= width)
         return fail(PG_ERR_INVALID, "pg_dbg_sample: target position " + std::to_string(idx[i] & 0x3fffffff) + " is out of range for a token row of width " +
                                         std::to_string(width));
+  int rc;
+  DrawGuideDev g;
+  if (guide) {
+    if ((rc = check_draw_guide_tables(guide, "pg_guided_dbg_sample"))) return rc;
+    g.top_p = guide->top_p;
+    if (guide->bias) { g.bias = guide->bias; g.bias_rows = guide->bias_rows; g.width = guide->width; g.n_valid = guide->n_valid; }
+    if (guide->temperatures) { g.temps = guide->temperatures; g.n_temps = guide->n_temperatures; }
+    if ((rc = check_draw_guide(&g, "pg_guided_dbg_sample", width, params->n_valid, n_rows, (int64_t)first_iter + n_steps))) return rc;
+  }
   Dbg d;
-  int rc = d.open(device);
-  if (rc) return rc;
+  if ((rc = d.open(device))) return rc;
+  if (g.bias) g.bias = d.up(guide->bias, (size_t)g.bias_rows * g.width * g.n_valid);
+  if (g.temps) g.temps = d.up(guide->temperatures, (size_t)g.n_temps);
   int32_t* dtok = d.up(tokens_inout, n_tok);
   const float* dlog = d.up(logits, compact ? n * n_tables * V : n_tok * V);
   const int32_t* didx = d.up(idx, n * n_tables);
@@ -867,7 +889,7 @@ int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, 
   int32_t* dstate = device_iter ? (int32_t*)d.alloc<char>(graph_state_bytes()) : nullptr;
   unsigned* dnf = nonfinite_out ? d.alloc<unsigned>(1) : nullptr;
   if ((rc = d.check(kCopyFailed))) return rc;
-  if (device_iter && (rc = launch_graph_state(nullptr, dstate, first_iter, params))) return rc;
+  if (device_iter && (rc = launch_graph_state(nullptr, dstate, first_iter, params, &g))) return rc;
   for (int s = 0; s < n_steps; ++s) {
     const int it = first_iter + s;
     const int32_t* idx_s = device_iter ? didx : didx + (size_t)it * n;      // the kernels add *d_iter tables themselves
@@ -878,7 +900,7 @@ int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, 
     d.put(dout, sampled_out + (size_t)s * n, n);      // the caller's pattern: an entry the kernel does not write keeps it
     if ((rc = d.check(kCopyFailed))) return rc;
     const float* lg = compact ? dlog + (size_t)it * n * V : dlog;
-    if ((rc = launch_sample_writeback(nullptr, dtok, width, lg, V, compact, idx_s, dmap, n_sel, P, params, device_iter ? 0 : it, dout, dstate, dnf)))
+    if ((rc = launch_sample_writeback(nullptr, dtok, width, lg, V, compact, idx_s, dmap, n_sel, P, params, device_iter ? 0 : it, dout, dstate, dnf, &g)))
       return rc;
     if ((rc = d.down(sampled_out + (size_t)s * n, dout, n))) return rc;
     if (device_iter && (rc = launch_iter_counter(nullptr, dstate, false, 0))) return rc;

@@ -68,9 +68,10 @@ struct GraphKey {
   hipStream_t stream = nullptr;
   uint64_t epoch_pad = 0;                         // 2 x the allocation epoch (a workspace buffer that moved) + <pad> in the batch
   int64_t job_items = 0;                          // picks kernels (sel_gemm_rows, splitk_ws): no replay under another job size
+  bool guided = false;                            // which draw kernel was captured (v1 or v2); the guide's tables are in the state block
   bool operator==(const GraphKey& o) const {
     return mask == o.mask && mask_idx == o.mask_idx && tok == o.tok && idx == o.idx && B == o.B && T == o.T && P == o.P &&
-           stream == o.stream && epoch_pad == o.epoch_pad && job_items == o.job_items;
+           stream == o.stream && epoch_pad == o.epoch_pad && job_items == o.job_items && guided == o.guided;
   }
   void reset() { *this = GraphKey(); }            // equals no call's key (tok == nullptr)
 };
@@ -160,6 +161,14 @@ struct Engine {
   unsigned* range_err = nullptr;
   int range_check();
   int finish_check() { int rc = chain_check(); return rc ? rc : range_check(); }      // right after a stream synchronisation
+
+  // ---- draw guide (pg_engine_set_draw_guide; pg_draw v2) ----
+  // Device copies of the guide's tables: allocations of their own, not DevBufs -- a new guide must not move the allocation epoch a
+  // captured iteration is keyed on (its pointers reach the kernel through the state block, not through the graph)
+  DrawGuideDev guide;
+  float *guide_bias_dev = nullptr, *guide_temps_dev = nullptr;
+  int set_draw_guide(const pg_draw_guide* g);
+  const DrawGuideDev* draw_guide() const { return guide.active() ? &guide : nullptr; }
 
   // ---- graph ----
   // launch-bound (small) Gibbs loops: one iteration captured as a hipGraph and replayed; the iteration number lives in

@@ -114,6 +114,8 @@ Engine::~Engine() {
   for (DevBuf* b : bufs) b->release();
   if (chain_err) (void)hipHostFree(chain_err);
   if (range_err) (void)hipHostFree(range_err);
+  if (guide_bias_dev) (void)hipFree(guide_bias_dev);
+  if (guide_temps_dev) (void)hipFree(guide_temps_dev);
   prof.destroy();
   if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
   if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -893,7 +895,7 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
     int r = masked_logits(d_tok, B, 1, T, idx_it, nullptr, nullptr, n_sel_rows, P, sp->mask, sp->mask_idx, lg, dit);
     if (r || P == 0) return r;
     int32_t* st = d_samp_tok_ ? d_samp_tok_ + (size_t)it * n_draws : nullptr;
-    return timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, T, lg, V, 1, idx_it, nullptr, n_sel_rows, P, sp, dit ? 0 : it, st, dit, range_err); });
+    return timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, T, lg, V, 1, idx_it, nullptr, n_sel_rows, P, sp, dit ? 0 : it, st, dit, range_err, draw_guide()); });
   };
 
   // Launch-bound regime (few tokens: ~270 launches of a few microseconds each): capture ONE iteration as a hipGraph and
@@ -905,7 +907,7 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
   const bool graphable = use_graph && pruned && !prof.on && !d_samp_logits_ && !d_samp_tok_ && (int64_t)B * T <= 4096;
   auto epoch_pad = [&] { return g_alloc_epoch * 2 + (esm_pad_in_batch ? 1 : 0); };
   GraphKey key;
-  if (graphable) key = {sp->mask, sp->mask_idx, d_tok, d_idx_, B, T, P, stream, epoch_pad(), job_items};
+  if (graphable) key = {sp->mask, sp->mask_idx, d_tok, d_idx_, B, T, P, stream, epoch_pad(), job_items, draw_guide() != nullptr};
   const bool reuse = graphable && graph_exec && key == graph_key;
   if (!graphable || (!reuse && n_iters < 3)) {
     for (int it = 0; it < n_iters; ++it)
@@ -933,7 +935,7 @@ int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_
     ++stat_graph_captures;
   }
   // replay: the counter selects the idx slice, the Philox iteration word and the burn-in flag; the parameters are this call's
-  if ((rc = launch_graph_state(stream, d_iter.as<int32_t>(), first, sp))) return rc;
+  if ((rc = launch_graph_state(stream, d_iter.as<int32_t>(), first, sp, draw_guide()))) return rc;
   for (int it = first; it < n_iters; ++it) PG_HIP(hipGraphLaunch(graph_exec, stream));
   stat_graph_replays += n_iters - first;
   return PG_OK;
@@ -1036,6 +1038,43 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
   return PG_OK;
 }
 
+// The tables of a draw guide, checked on the host and uploaded once; nullptr or a guide with nothing set clears it.  Work queued under
+// the previous guide is waited for before its tables are freed.
+int Engine::set_draw_guide(const pg_draw_guide* g) {
+  int rc;
+  if (g && (rc = check_draw_guide_tables(g, "pg_engine_set_draw_guide"))) return rc;      // before a device is touched
+  DrawGuideDev next;
+  if (g) {
+    next.top_p = g->top_p;
+    if (g->bias) { next.bias_rows = g->bias_rows; next.width = g->width; next.n_valid = g->n_valid; }
+    if (g->temperatures) next.n_temps = g->n_temperatures;
+  }
+  const bool had = guide_bias_dev || guide_temps_dev;
+  if (!had && !(g && (g->bias || g->temperatures))) {      // no table to free or to upload: no device call
+    guide = next;
+    return PG_OK;
+  }
+  PG_HIP(hipStreamSynchronize(stream));      // the caller (pg_engine_set_draw_guide) has made the engine's device current
+  if (guide_bias_dev) (void)hipFree(guide_bias_dev);
+  if (guide_temps_dev) (void)hipFree(guide_temps_dev);
+  guide_bias_dev = guide_temps_dev = nullptr;
+  guide = DrawGuideDev();
+  if (g && g->bias) {
+    const size_t bytes = (size_t)g->bias_rows * g->width * g->n_valid * 4;
+    PG_HIP(hipMalloc((void**)&guide_bias_dev, bytes));
+    PG_HIP(hipMemcpyAsync(guide_bias_dev, g->bias, bytes, hipMemcpyHostToDevice, stream));
+    next.bias = guide_bias_dev;
+  }
+  if (g && g->temperatures) {
+    PG_HIP(hipMalloc((void**)&guide_temps_dev, (size_t)g->n_temperatures * 4));
+    PG_HIP(hipMemcpyAsync(guide_temps_dev, g->temperatures, (size_t)g->n_temperatures * 4, hipMemcpyHostToDevice, stream));
+    next.temps = guide_temps_dev;
+  }
+  PG_HIP(hipStreamSynchronize(stream));      // the caller's host tables are free again
+  guide = next;
+  return PG_OK;
+}
+
 static int check_msa_shape(const pg_model_config& cfg, int B, int R, int C) {
   if (cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
   if (B < 0 || R < 1 || C < 1) return fail(PG_ERR_INVALID, "bad MSA shape");
@@ -1060,7 +1099,7 @@ int Engine::msa_gibbs_device(int32_t* d_tok, int B, int R, int C, const int32_t*
     if ((rc = masked_logits(d_tok, B, R, C, idx_it, nullptr, nullptr, n_sel_rows, P, sp->mask, sp->mask_idx, lg))) return rc;
     if (P == 0) continue;
     int32_t* st = d_samp_tok_ ? d_samp_tok_ + (size_t)it * n_draws : nullptr;
-    if ((rc = timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, C, lg, V, 1, idx_it, nullptr, n_sel_rows, P, sp, it, st, nullptr, range_err); }))) return rc;
+    if ((rc = timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, C, lg, V, 1, idx_it, nullptr, n_sel_rows, P, sp, it, st, nullptr, range_err, draw_guide()); }))) return rc;
   }
   return PG_OK;
 }
@@ -1095,8 +1134,14 @@ int Engine::msa_single_device(int32_t* d_tok, int B, int R, int C, int mask_row,
         lg_b = d_samp_logits_ ? tmp_out.as<float>() : nullptr;
         st_b = d_samp_tok_ ? (int32_t*)(tmp_out.as<float>() + (size_t)n_steps * (P_max > 0 ? P_max : 1) * cfg.vocab) : nullptr;
       }
-      if ((rc = msa_single_device(d_tok + (size_t)b * R * C, 1, R, C, mask_row, target_row, tmp_idx.as<int32_t>(), step_sample_flag_host,
-                                  n_steps, P_max, sp + b, lg_b, st_b))) return rc;
+      {
+        // a per-row bias table is indexed by the token row of the whole call: template b's rows start R rows further on
+        struct GuideRows { DrawGuideDev& g; const float* bias; ~GuideRows() { g.bias = bias; } } rows{guide, guide.bias};
+        if (guide.bias && guide.bias_rows > 1) guide.bias += (size_t)b * R * C * guide.n_valid;
+        rc = msa_single_device(d_tok + (size_t)b * R * C, 1, R, C, mask_row, target_row, tmp_idx.as<int32_t>(), step_sample_flag_host,
+                               n_steps, P_max, sp + b, lg_b, st_b);
+      }
+      if (rc) return rc;
       for (int s2 = 0; s2 < n_steps && P_max > 0; ++s2) {
         if (lg_b) PG_HIP(hipMemcpyAsync(d_samp_logits_ + ((size_t)s2 * B + b) * P_max * cfg.vocab, lg_b + (size_t)s2 * P_max * cfg.vocab,
                                         (size_t)P_max * cfg.vocab * 4, hipMemcpyDeviceToDevice, stream));
@@ -1132,7 +1177,7 @@ int Engine::msa_single_device(int32_t* d_tok, int B, int R, int C, int mask_row,
       pg_sample_params p = sp[b];
       p.burnin = step_sample_flag_host[s] ? 0x7fffffff : 0;   // sample=(pass_num < burn_in), esm_msa_sampler.py:143
       if ((rc = timed(PC_SAMPLE, [&] { return launch_sample_writeback(stream, d_tok, C, lg + (size_t)b * P_max * V, V, 1, idx_s + (size_t)b * P_max,
-                                                                      d_tgt_map + b, 1, P_max, &p, s, st ? st + (size_t)b * P_max : nullptr, nullptr, range_err); }))) return rc;
+                                                                      d_tgt_map + b, 1, P_max, &p, s, st ? st + (size_t)b * P_max : nullptr, nullptr, range_err, draw_guide()); }))) return rc;
     }
   }
   return PG_OK;

@@ -63,7 +63,20 @@ int launch_iter_counter(hipStream_t st, int32_t* d_iter, bool set, int value);
 // graph state block (graph_state_bytes() bytes): d_iter[0] = iteration, then the call's sampling parameters -- the kernels of a
 // captured iteration read both from the device, so ONE graph serves every iteration of every call of the same shape
 size_t graph_state_bytes();
-int launch_graph_state(hipStream_t st, int32_t* d_iter, int iteration, const pg_sample_params* p);
+// A draw guide on the device (pg_draw v2): what pg_engine_set_draw_guide uploaded, or a plug-in caller's own
+// device tables.  check_draw_guide is the run-time refusal every entry makes before it launches with one.
+struct DrawGuideDev {
+  const float* bias = nullptr;      // [bias_rows][width][n_valid], -inf = forbidden
+  int64_t bias_rows = 0;            // 1 = shared, else the call's token rows
+  int width = 0, n_valid = 0;
+  const float* temps = nullptr;     // [n_temps]
+  int n_temps = 0;
+  float top_p = __builtin_nanf(""); // NaN = off
+  bool active() const;              // anything set: the launch takes the v2 kernel
+};
+int check_draw_guide_tables(const pg_draw_guide* g, const char* who);      // what the host tables hold (set time); touches no device
+int check_draw_guide(const DrawGuideDev* g, const char* who, int width, int n_valid, int64_t token_rows, int64_t n_iters);
+int launch_graph_state(hipStream_t st, int32_t* d_iter, int iteration, const pg_sample_params* p, const DrawGuideDev* guide = nullptr);
 int launch_logprob_gather(hipStream_t st, const float* logits, int V, int compact, int width, const int32_t* idx,
                           const int32_t* row_map, const int32_t* targets, int64_t n_sel, int P, float* out,
                           unsigned* nonfinite = nullptr);     // nonfinite: device-visible word set to 1 when a logit row holds NaN / inf
@@ -77,6 +90,7 @@ int launch_mask_scatter(hipStream_t st, int32_t* tokens, int width, const int32_
                         int64_t n_sel, int P, int mask_idx, const int32_t* d_iter = nullptr);
 int launch_sample_writeback(hipStream_t st, int32_t* tokens, int width, const float* logits, int V, int compact,
                             const int32_t* idx, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* p,
-                            int iteration, int32_t* sampled_tokens, const int32_t* d_iter = nullptr, unsigned* nonfinite = nullptr);
+                            int iteration, int32_t* sampled_tokens, const int32_t* d_iter = nullptr, unsigned* nonfinite = nullptr,
+                            const DrawGuideDev* guide = nullptr);      // guide: null or inactive = pg_draw v1's kernel
 
 }  // namespace pg

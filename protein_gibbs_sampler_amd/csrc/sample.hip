@@ -67,27 +67,51 @@ struct SampleArgs {
   int32_t burnin;             // used with a device-side iteration counter: sample = (it < burnin)
 };
 
+// pg_draw v2: what a guided draw reads besides SampleArgs.  All device pointers; a null pointer / use_top_p 0
+// switches that part off, and with all three off the guided kernel computes v1's bits.
+struct GuideArgs {
+  const float* bias;    // [bias_rows][width][n_valid] in valid-list order, -inf = forbidden; null: none
+  const float* temps;   // [>= iterations of the call]: T = temps[it] and SampleArgs::temperature is not read; null: none
+  int32_t bias_per_row; // 1: the table row is the draw's token row; 0: one shared row
+  int32_t use_top_p;
+  float top_p;
+  int32_t it;           // call-local iteration (index into temps); a device-side counter is added to it
+};
+struct GuidedSampleArgs {
+  SampleArgs s;         // first: the graph state block holds a GuidedSampleArgs, and the v1 kernel reads its SampleArgs prefix
+  GuideArgs g;
+};
+template <bool Guided> struct DrawArgs { using type = SampleArgs; };
+template <> struct DrawArgs<true> { using type = GuidedSampleArgs; };
+__device__ __forceinline__ SampleArgs& sample_part(SampleArgs& a) { return a; }
+__device__ __forceinline__ SampleArgs& sample_part(GuidedSampleArgs& a) { return a.s; }
+
 // logits addressing: compact [n_sel*P][V] (engine path: LM head evaluated only at the sampled rows),
 // or full [n_rows][width][V] (plug-in models).
 // One WAVE per draw (round 4; it was one thread per draw -- a 32 x 32 rank loop and 32 exponentials in a single lane, 42 us
 // however few draws there were, 3 % of a config-1 iteration): lane j holds valid entry j.  Every floating-point operation and its
 // order is the one-thread form's (the cumulative sums are accumulated in rank order, one after the other, in a value all lanes
 // hold), so the draws are the same bit for bit.
+// Guided = false is pg_draw v1 and stays the code it was (the `if constexpr (Guided)` parts are not compiled into it); Guided = true
+// is v2: bias and scheduled temperature before the rank, the forbidden entries cut from k, the nucleus cut after the sums.
+template <bool Guided>
 __global__ __launch_bounds__(256) void sample_writeback_kernel(int32_t* __restrict__ tokens, int width,
                                                               const float* __restrict__ logits, int V, int compact,
                                                               const int32_t* __restrict__ idx,
                                                               const int32_t* __restrict__ row_map, int64_t n_sel, int P,
-                                                              SampleArgs a, int32_t* __restrict__ sampled_tokens,
+                                                              typename DrawArgs<Guided>::type args, int32_t* __restrict__ sampled_tokens,
                                                               const int32_t* __restrict__ d_iter, unsigned* nonfinite) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (i >= n_sel * P) return;   // wave-uniform
+  SampleArgs& a = sample_part(args);
   if (d_iter) {               // graph replay: the iteration number AND the sampling parameters live on the device, so one
     const int it = *d_iter;   // captured graph serves every iteration of every call with this shape (launch_graph_state)
-    a = *(const SampleArgs*)(d_iter + kGraphArgsOffset);
+    args = *(const typename DrawArgs<Guided>::type*)(d_iter + kGraphArgsOffset);
     idx += (size_t)it * n_sel * P;
     a.iter += (uint32_t)it;
     a.sample = it < a.burnin ? 1 : 0;
+    if constexpr (Guided) args.g.it += it;
   }
   const int64_t s = i / P;
   const int slot = (int)(i - s * P);
@@ -119,7 +143,21 @@ __global__ __launch_bounds__(256) void sample_writeback_kernel(int32_t* __restri
     // a non-finite logit (an overflowed fp16 operand upstream: inf -> NaN through the next LayerNorm) is reported, not sampled
     // from silently: the engine's entry points return PG_ERR_RANGE (Engine::range_check)
     if (nonfinite && !(fabsf(v) <= 3.0e38f)) *nonfinite = 1u;
-    if (a.use_temp) v = v / a.temperature;
+    if constexpr (Guided) {
+      if (args.g.bias) {
+        const int64_t cell = (args.g.bias_per_row ? trow * width : (int64_t)0) + pos;
+        v = v + args.g.bias[(size_t)cell * nv + lane];
+      }
+      if (args.g.temps) v = v / args.g.temps[args.g.it];
+      else if (a.use_temp) v = v / a.temperature;
+    } else {
+      if (a.use_temp) v = v / a.temperature;
+    }
+  }
+  if constexpr (Guided) {      // the forbidden entries (-inf) rank last: cutting k to the allowed count cuts exactly them
+    const int n_allowed = __popcll(__ballot(mine && v > -INFINITY));
+    if (k > n_allowed) k = n_allowed;
+    if (k < 1) k = 1;          // a cell with nothing allowed (refused where the table is on the host): still a defined pick
   }
   // stable descending rank of every valid entry
   int rank = 0;
@@ -148,6 +186,16 @@ __global__ __launch_bounds__(256) void sample_writeback_kernel(int32_t* __restri
   uint32_t w0;
   philox4x32_10(a.row_id_base + (uint32_t)s, a.iter, (uint32_t)slot, a.stream, a.seed_lo, a.seed_hi, w0);
   const float u = (float)(w0 >> 8) * 0x1.0p-24f;
+  if constexpr (Guided) {      // nucleus: the shortest prefix whose sum reaches top_p of the whole; not in burn-in, as top_k
+    if (args.g.use_top_p && !a.sample) {
+      const float q = args.g.top_p * acc;
+      const int kp = 1 + __popcll(__ballot(lane < k && cum < q));
+      if (kp < k) {
+        k = kp;
+        acc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cum), k - 1));
+      }
+    }
+  }
   const float t = u * acc;
   const unsigned long long hit = __ballot(lane < k && cum > t);
   const int jsel = hit ? (int)__builtin_ctzll(hit) : k - 1;
@@ -305,6 +353,60 @@ int launch_iter_counter(hipStream_t st, int32_t* d_iter, bool set, int value) {
   return 0;
 }
 
+bool DrawGuideDev::active() const { return bias || temps || (top_p == top_p && top_p < 1.0f); }
+
+// what a guide's host tables hold, before anything is uploaded: the kernel assumes all of it
+int check_draw_guide_tables(const pg_draw_guide* g, const char* who) {
+  const std::string w(who);
+  if (g->bias) {
+    if (g->n_valid < 1 || g->n_valid > 32) return fail(1, w + ": the draw guide's n_valid must be in 1..32");
+    if (g->width < 1 || g->bias_rows < 1) return fail(1, w + ": the draw guide's bias table needs width >= 1 and bias_rows >= 1");
+    if ((double)g->bias_rows * g->width * g->n_valid > 2147483647.0) return fail(1, w + ": the draw guide's bias table has more than 2^31 - 1 entries");
+    const int64_t cells = g->bias_rows * g->width;
+    for (int64_t c = 0; c < cells; ++c) {
+      const float* b = g->bias + c * g->n_valid;
+      int allowed = 0;
+      for (int j = 0; j < g->n_valid; ++j) {
+        if (b[j] != b[j] || b[j] == INFINITY)
+          return fail(1, w + ": the draw guide's bias holds " + (b[j] != b[j] ? "NaN" : "+inf") + " at row " + std::to_string(c / g->width) +
+                             ", position " + std::to_string(c % g->width) + ", entry " + std::to_string(j) + " (entries are finite, or -inf = forbidden)");
+        allowed += b[j] > -INFINITY;
+      }
+      if (!allowed)
+        return fail(1, w + ": the draw guide's bias forbids every residue at row " + std::to_string(c / g->width) + ", position " +
+                           std::to_string(c % g->width));
+    }
+  }
+  if (g->temperatures) {
+    if (g->n_temperatures < 1) return fail(1, w + ": the draw guide's temperature schedule is empty");
+    for (int i = 0; i < g->n_temperatures; ++i)
+      if (!(g->temperatures[i] > 0.f && g->temperatures[i] < INFINITY))
+        return fail(1, w + ": the draw guide's temperature " + std::to_string(i) + " is not finite and > 0");
+  }
+  if (g->top_p == g->top_p && !(g->top_p > 0.f && g->top_p <= 1.0f)) return fail(1, w + ": the draw guide's top_p must be in (0, 1] (NaN = off)");
+  return 0;
+}
+
+// the guide against the shape of the call that is about to draw with it: the kernel indexes the bias table by (token row, position,
+// valid-list entry) and the schedule by the call-local iteration, so each of these is a bound on a device read
+int check_draw_guide(const DrawGuideDev* g, const char* who, int width, int n_valid, int64_t token_rows, int64_t n_iters) {
+  if (!g || !g->active()) return 0;
+  const std::string w(who);
+  if (g->bias) {
+    if (g->width != width)
+      return fail(1, w + ": the draw guide's bias table is " + std::to_string(g->width) + " positions wide, the token rows " + std::to_string(width));
+    if (g->n_valid != n_valid)
+      return fail(1, w + ": the draw guide's bias table has " + std::to_string(g->n_valid) + " entries per position, the valid list " + std::to_string(n_valid));
+    if (g->bias_rows != 1 && g->bias_rows != token_rows)
+      return fail(1, w + ": the draw guide's bias table has " + std::to_string(g->bias_rows) + " rows, which is neither 1 nor the call's " +
+                         std::to_string(token_rows) + " token rows");
+  }
+  if (g->temps && g->n_temps < n_iters)
+    return fail(1, w + ": the draw guide's temperature schedule has " + std::to_string(g->n_temps) + " entries, the call " + std::to_string(n_iters) +
+                       " iterations");
+  return 0;
+}
+
 static SampleArgs make_sample_args(const pg_sample_params* p, int iteration) {
   SampleArgs a;
   a.top_k = p->top_k;
@@ -322,16 +424,29 @@ static SampleArgs make_sample_args(const pg_sample_params* p, int iteration) {
   return a;
 }
 
-// graph state block: iteration counter + the call's sampling parameters (passed by value: no host buffer has to outlive the call)
-__global__ void graph_state_kernel(int32_t* d_iter, int value, SampleArgs a) {
+static GuidedSampleArgs make_guided_args(const pg_sample_params* p, int iteration, const DrawGuideDev* g) {
+  GuidedSampleArgs a;
+  a.s = make_sample_args(p, iteration);
+  a.g.bias = g ? g->bias : nullptr;
+  a.g.temps = g ? g->temps : nullptr;
+  a.g.bias_per_row = g && g->bias_rows > 1 ? 1 : 0;
+  a.g.use_top_p = g && g->top_p == g->top_p && g->top_p < 1.0f ? 1 : 0;
+  a.g.top_p = a.g.use_top_p ? g->top_p : 1.0f;
+  a.g.it = iteration;
+  return a;
+}
+
+// graph state block: iteration counter + the call's sampling parameters and draw guide (passed by value: no host buffer has to
+// outlive the call).  The block always holds a GuidedSampleArgs; the v1 kernel reads the SampleArgs it starts with.
+__global__ void graph_state_kernel(int32_t* d_iter, int value, GuidedSampleArgs a) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     *d_iter = value;
-    *(SampleArgs*)(d_iter + kGraphArgsOffset) = a;
+    *(GuidedSampleArgs*)(d_iter + kGraphArgsOffset) = a;
   }
 }
-size_t graph_state_bytes() { return kGraphArgsOffset * 4 + sizeof(SampleArgs); }
-int launch_graph_state(hipStream_t st, int32_t* d_iter, int iteration, const pg_sample_params* p) {
-  hipLaunchKernelGGL(graph_state_kernel, dim3(1), dim3(64), 0, st, d_iter, iteration, make_sample_args(p, 0));
+size_t graph_state_bytes() { return kGraphArgsOffset * 4 + sizeof(GuidedSampleArgs); }
+int launch_graph_state(hipStream_t st, int32_t* d_iter, int iteration, const pg_sample_params* p, const DrawGuideDev* guide) {
+  hipLaunchKernelGGL(graph_state_kernel, dim3(1), dim3(64), 0, st, d_iter, iteration, make_guided_args(p, 0, guide));
   PG_HIP(hipGetLastError());
   return 0;
 }
@@ -348,14 +463,22 @@ int launch_mask_scatter(hipStream_t st, int32_t* tokens, int width, const int32_
 
 int launch_sample_writeback(hipStream_t st, int32_t* tokens, int width, const float* logits, int V, int compact,
                             const int32_t* idx, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* p,
-                            int iteration, int32_t* sampled_tokens, const int32_t* d_iter, unsigned* nonfinite) {
+                            int iteration, int32_t* sampled_tokens, const int32_t* d_iter, unsigned* nonfinite,
+                            const DrawGuideDev* guide) {
   if (p->n_valid < 1 || p->n_valid > 32) return fail(1, "sample: n_valid must be in 1..32");
   for (int j = 0; j < p->n_valid; ++j)
     if (p->valid_idx[j] < 0 || p->valid_idx[j] >= V) return fail(1, "sample: valid_idx out of range");
   const int64_t n = n_sel * P;
   if (n == 0) return 0;
+  if (guide && guide->active()) {      // pg_draw v2; the caller has checked the guide against this call's shape (check_draw_guide)
+    const GuidedSampleArgs ga = make_guided_args(p, iteration, guide);
+    hipLaunchKernelGGL(sample_writeback_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, tokens, width, logits, V,
+                       compact, idx, row_map, n_sel, P, ga, sampled_tokens, d_iter, nonfinite);
+    PG_HIP(hipGetLastError());
+    return 0;
+  }
   const SampleArgs a = make_sample_args(p, iteration);
-  hipLaunchKernelGGL(sample_writeback_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, tokens, width, logits, V,
+  hipLaunchKernelGGL(sample_writeback_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, tokens, width, logits, V,
                      compact, idx, row_map, n_sel, P, a, sampled_tokens, d_iter, nonfinite);      // one wave per draw
   PG_HIP(hipGetLastError());
   return 0;

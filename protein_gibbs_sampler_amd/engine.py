@@ -58,6 +58,7 @@ class NativeMaskedLM:
         self._h = None
         self._alt = None                   # auto mode: the bf16-operand engine of the same weights (created on first need)
         self._job_items = 0
+        self._guide = None                 # inside draw_guide(): (pg_draw_guide struct, the arrays it points into)
         self._force_bf16 = 0               # > 0: inside forced_bf16()
         self._fell_back = False            # a call since the last take_fell_back() was run again in bf16 (PG_ERR_RANGE)
         self._warned = False
@@ -101,6 +102,8 @@ class NativeMaskedLM:
             self._alt = self._create(_lib.PG_PREC_BF16)
             if self._job_items:
                 _lib.check(_lib.lib().pg_engine_set_job_items(self._alt, self._job_items))
+            if self._guide is not None:
+                _lib.check(_lib.lib().pg_engine_set_draw_guide(self._alt, ctypes.byref(self._guide[0])))
         return self._alt
 
     def _shape_needs_bf16(self, tok):
@@ -391,6 +394,34 @@ class NativeMaskedLM:
 
     def synchronize(self):
         _lib.check(_lib.lib().pg_engine_synchronize(self.handle))
+
+    def draw_guide(self, compiled):
+        """Context manager: the Gibbs calls inside draw pg_draw v2 under `compiled` (guides.CompiledGuide; None or empty: nothing
+        changes).  The guide is set on the engine (pg_engine_set_draw_guide), and on the bf16 twin of an auto-precision engine, and
+        cleared on the way out, also when a call inside raises."""
+        lm = self
+
+        class _Guided:
+            def __enter__(self_):
+                if compiled is None or compiled.empty:
+                    return
+                lm._guide = _lib.make_draw_guide(compiled.bias, compiled.temperatures, compiled.top_p)
+                try:
+                    for h in (lm.handle, lm._alt):
+                        if h is not None:
+                            _lib.check(_lib.lib().pg_engine_set_draw_guide(h, ctypes.byref(lm._guide[0])))
+                except Exception:
+                    self_.__exit__()
+                    raise
+
+            def __exit__(self_, *exc):
+                if lm._guide is None:
+                    return
+                lm._guide = None
+                for h in (lm._h, lm._alt):
+                    if h is not None:
+                        _lib.check(_lib.lib().pg_engine_set_draw_guide(h, None))
+        return _Guided()
 
     def set_job_items(self, n):
         """Batch items (chains / MSAs) of the whole multi-GPU job the following calls are shards of; 0 = whole jobs again

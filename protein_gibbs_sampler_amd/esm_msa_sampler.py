@@ -7,13 +7,14 @@ cleaning with the 21-symbol alphabet :93-99; `<mask>` padding through the patche
 :189-218; RNG consumption order (one random.sample per (msa, row), :272-279; one random.shuffle per
 pass, :129); `generate_single` masking row -1 while sampling `target_index` (quirk Q2, :133-145).
 """
+import contextlib
 import math
 
 import numpy as np
 import torch
 from tqdm import tqdm, trange
 
-from . import _gibbs, _lib, sharding
+from . import _gibbs, _lib, guides, sharding
 from .engine import NativeMaskedLM
 from .esm_sampler import generate_step  # noqa: F401  (same re-export as the reference, :6)
 
@@ -77,12 +78,16 @@ class ESM_MSA_sampler():
                                "implemented as HIP kernels only, there is no CPU implementation" % what)
 
     # ---- single-row resampling (reference :101-147) -------------------------------------------
-    def generate_single(self, seed_msa, steps=10, passes=3, burn_in=1, target_index=0, k=1, exclude_positions=None):
+    def generate_single(self, seed_msa, steps=10, passes=3, burn_in=1, target_index=0, k=1, exclude_positions=None, top_p=None,
+                        temperature_schedule=None, position_bias=None, allowed_residues=None, forbidden_residues=None):
         return self.generate_single_batch([seed_msa], steps=steps, passes=passes, burn_in=burn_in, target_index=target_index, k=k,
-                                          exclude_positions=[exclude_positions], _shard=False)[0]
+                                          exclude_positions=[exclude_positions], _shard=False, top_p=top_p,
+                                          temperature_schedule=temperature_schedule, position_bias=position_bias,
+                                          allowed_residues=allowed_residues, forbidden_residues=forbidden_residues)[0]
 
     def generate_single_batch(self, seed_msas, steps=10, passes=3, burn_in=1, target_index=0, k=1, exclude_positions=None,
-                              max_batch=4, _shard=None):
+                              max_batch=4, _shard=None, top_p=None, temperature_schedule=None, position_bias=None,
+                              allowed_residues=None, forbidden_residues=None):
         """== [self.generate_single(m, steps, passes, burn_in, target_index, k, ex) for m, ex in zip(seed_msas, exclude_positions)]
         -- the loop of pgen_msa_revised over templates and sequences per template (reference pgen_msa_revised.py:107-115) --
         with MSAs of equal shape resampled together, up to `max_batch` per native call (BASELINE config 5: batches of templates),
@@ -90,7 +95,12 @@ class ESM_MSA_sampler():
 
         Same interpreter-RNG consumption as the serial calls (one random.shuffle per MSA and pass, MSA-major), one torch seed per
         MSA in list order, and the same strings: each MSA's arithmetic is independent of its batch mates (pgibbs.h
-        pg_msa_gibbs_single_batch_run).  exclude_positions: None or one list (or None) per MSA."""
+        pg_msa_gibbs_single_batch_run).  exclude_positions: None or one list (or None) per MSA.
+
+        top_p, temperature_schedule, position_bias, allowed_residues, forbidden_residues (not in the reference; guides.DrawGuide):
+        a guided draw of the sampled row, keyed by token column (residue 0 is column 1); the schedule is indexed by the step
+        number (passes * steps of them) and top_p is ignored in burn-in passes, as k is."""
+        guide = guides.from_arguments(top_p, temperature_schedule, position_bias, allowed_residues, forbidden_residues)
         n = len(seed_msas)
         if exclude_positions is None:
             exclude_positions = [None] * n
@@ -100,7 +110,8 @@ class ESM_MSA_sampler():
         from . import pyrandom
         native = isinstance(self.model.model, NativeMaskedLM)
         ctx = _gibbs.shard_context(self, native, lambda: (seed_msas, steps, passes, burn_in, target_index, k, exclude_positions,
-                                                          self.rng_stream), "ESM_MSA_sampler.generate_single_batch", shard=_shard)
+                                                          self.rng_stream, None if guide is None else guide.digest_parts()),
+                                     "ESM_MSA_sampler.generate_single_batch", shard=_shard)
 
         # every MSA's step lists, decided up front in the serial order (selection never depends on the logits)
         jobs = []
@@ -146,8 +157,10 @@ class ESM_MSA_sampler():
                     R = tok.shape[1]
                     params = [_lib.make_sample_params(True, mask_idx, k, 0, None, self.valid_aa_idx, jobs[j]["seed"],
                                                       rng_stream=self.rng_stream, row_id_base=jobs[j]["tr"]) for j in chunk]
-                    lg, st = self.model.model.gibbs_single_batch_run(tok, R - 1, key[3], table, list(key[2]), params,
-                                                                     want_logits=self.record, want_tokens=self.record)
+                    compiled = guides.compile_for(self, guide, tok.shape[2], table.shape[0])
+                    with (self.model.model.draw_guide(compiled) if compiled is not None else contextlib.nullcontext()):
+                        lg, st = self.model.model.gibbs_single_batch_run(tok, R - 1, key[3], table, list(key[2]), params,
+                                                                         want_logits=self.record, want_tokens=self.record)
                     for i, j in enumerate(chunk):
                         jobs[j]["batch"] = torch.from_numpy(tok[i:i + 1].astype(np.int64))
                         if self.record:
@@ -160,7 +173,8 @@ class ESM_MSA_sampler():
                 params = _lib.make_sample_params(True, mask_idx, k, 0, None, self.valid_aa_idx, job["seed"],
                                                  rng_stream=self.rng_stream, row_id_base=job["tr"])
                 job["batch"] = _gibbs.run_plugin_loop(self.model.model, job["batch"], table_of(job, P)[:, None, :], params, self.device,
-                                                      row_map=[job["tr"]], mask_row_map=[R - 1], sample_flags=job["flags"])
+                                                      row_map=[job["tr"]], mask_row_map=[R - 1], sample_flags=job["flags"],
+                                                      guide=guides.compile_for(self, guide, job["batch"].shape[2], len(job["steps"])))
         if ctx is not None:
             # the one collective: the resampled rows, padded to the widest alignment, blocks in rank order
             width = max(j["batch"].shape[2] for j in jobs)
@@ -180,7 +194,12 @@ class ESM_MSA_sampler():
     def generate(self, n_samples, seed_msa, batch_size=1, in_order=False, max_len=None, leader_length=0,
                  leader_length_percent=None, top_k=0, temperature=None, num_iters=10, burnin=float('inf'),
                  mask=True, num_positions=0, num_positions_percent=None, indexes=None, rollover_from_start=False,
-                 show_progress_bar=True):
+                 show_progress_bar=True, top_p=None, temperature_schedule=None, position_bias=None, allowed_residues=None,
+                 forbidden_residues=None):
+        """Arguments as pgen.esm_msa_sampler.ESM_MSA_sampler.generate, then the five of a guided draw, which the reference does not
+        have (guides.DrawGuide; pg_draw v2): one table per token column (residue 0 is column 1), applied to every row of every MSA;
+        temperature_schedule needs at least num_iters entries and replaces `temperature`."""
+        guide = guides.from_arguments(top_p, temperature_schedule, position_bias, allowed_residues, forbidden_residues)
         num_sequences = len(seed_msa)
         sequence_length = len(seed_msa[0])
         sequences = []
@@ -194,7 +213,8 @@ class ESM_MSA_sampler():
         self.last_run = []
         ctx = _gibbs.shard_context(self, isinstance(self.model.model, NativeMaskedLM), lambda: (
             n_samples, seed_msa, batch_size, in_order, max_len, leader_length, top_k, temperature, num_iters, burnin, mask,
-            num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream), "ESM_MSA_sampler.generate")
+            num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream,
+            None if guide is None else guide.digest_parts()), "ESM_MSA_sampler.generate")
         if ctx is not None:
             draw_seed = sharding.broadcast_object(ctx, draw_seed)
 
@@ -211,7 +231,7 @@ class ESM_MSA_sampler():
                                              row_id_base=generation_round * batch_size * num_sequences)
             # a plug-in run is not recorded here (ESM_sampler.generate records it): the one difference between the two callers
             batch = _gibbs.run_gibbs_batch(self, ctx, batch, table, params, generation_round * batch_size * num_sequences, num_sequences,
-                                           record_plugin=False)
+                                           record_plugin=False, guide=guides.compile_for(self, guide, batch.shape[2], num_iters))
             strs = self.untokenize_batch(batch)
             if generation_round == (n_generation_rounds - 1):
                 sequences += strs[0:n_samples - len(sequences)]

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 from tqdm import trange
 
-from . import _gibbs, _lib, sharding
+from . import _gibbs, _lib, guides, sharding
 from .engine import NativeMaskedLM
 
 ESM_ALLOWED_AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"
@@ -168,8 +168,13 @@ class ESM_sampler():
     def generate(self, n_samples, seed_seq, batch_size=1, in_order=False, max_len=None, leader_length=0,
                  leader_length_percent=None, top_k=0, temperature=None, num_iters=10, burnin=float('inf'), mask=True,
                  num_positions=0, num_positions_percent=None, indexes=None, rollover_from_start=False,
-                 show_progress_bar=True):
-        """generate sequences -- arguments exactly as pgen.esm_sampler.ESM_sampler.generate (reference :128-170)."""
+                 show_progress_bar=True, top_p=None, temperature_schedule=None, position_bias=None, allowed_residues=None,
+                 forbidden_residues=None):
+        """generate sequences -- arguments exactly as pgen.esm_sampler.ESM_sampler.generate (reference :128-170), then the five
+        of a guided draw, which the reference does not have (guides.DrawGuide; pg_draw v2): top_p in (0, 1],
+        temperature_schedule (one temperature per iteration, or "kind:t_start:t_end"; at least num_iters long; `temperature` is
+        then not used), position_bias, allowed_residues, forbidden_residues -- keyed by token position, as `indexes` is."""
+        guide = guides.from_arguments(top_p, temperature_schedule, position_bias, allowed_residues, forbidden_residues)
         if isinstance(seed_seq, str):
             sequence_length = len(seed_seq)
         elif isinstance(seed_seq, list):
@@ -190,7 +195,8 @@ class ESM_sampler():
         # several torch.distributed ranks (one per GPU): every batch is split contiguously over them
         ctx = _gibbs.shard_context(self, isinstance(self.model.model, NativeMaskedLM), lambda: (
             n_samples, seed_seq, batch_size, in_order, max_len, leader_length, top_k, temperature, num_iters, burnin, mask,
-            num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream), "ESM_sampler.generate")
+            num_positions, None if indexes is None else list(indexes), rollover_from_start, self.rng_stream,
+            None if guide is None else guide.digest_parts()), "ESM_sampler.generate")
         if ctx is not None:
             draw_seed = sharding.broadcast_object(ctx, draw_seed)
 
@@ -205,7 +211,8 @@ class ESM_sampler():
             table, last_i = _gibbs.build_target_table(num_iters, (batch_size,), indexes, num_positions, in_order, last_i)
             params = _lib.make_sample_params(mask, self.model.alphabet.mask_idx, top_k, burnin, temperature, self.valid_aa_idx,
                                              draw_seed, rng_stream=self.rng_stream, row_id_base=batch_n * batch_size)
-            batch = _gibbs.run_gibbs_batch(self, ctx, batch, table, params, batch_n * batch_size, 1, record_plugin=True)
+            batch = _gibbs.run_gibbs_batch(self, ctx, batch, table, params, batch_n * batch_size, 1, record_plugin=True,
+                                           guide=guides.compile_for(self, guide, batch.shape[1], num_iters))
 
             strs = self.untokenize_batch(batch, self.model.alphabet.prepend_bos, self.model.alphabet.append_eos)
             if batch_n == (n_batches - 1):

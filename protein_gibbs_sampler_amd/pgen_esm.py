@@ -7,7 +7,7 @@ import textwrap
 from pathlib import Path
 
 from . import models
-from ._cli import RawAndDefaultsFormatter, add_engine_args, parse_line_args, seed_everything
+from ._cli import GUIDE_EPILOG, RawAndDefaultsFormatter, add_engine_args, parse_line_args, seed_everything
 from .esm_sampler import ESM_sampler
 from .fasta_io import write_sequential_fasta
 
@@ -44,7 +44,9 @@ def build_parser():
         epilog=textwrap.dedent("""
             Available sampler arguments: seed_seq, in_order, max_len, leader_length, leader_length_percent, top_k, temperature,
             num_iters, burnin, mask, num_positions, num_positions_percent, indexes, rollover_from_start
-            (see ESM_sampler.generate)."""),
+            (see ESM_sampler.generate).
+
+            """) + GUIDE_EPILOG,
         formatter_class=RawAndDefaultsFormatter)
     parser.add_argument("-o", default=".", help="a directory to save the outputs to.")
     parser.add_argument("-i", default=None, help="tab separated file: [sample name] \\t [dict of arguments for the sampler].")

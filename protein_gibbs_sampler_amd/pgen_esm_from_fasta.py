@@ -9,7 +9,7 @@ import textwrap
 from pathlib import Path
 
 from . import models
-from ._cli import RawAndDefaultsFormatter, add_engine_args, parse_line_args, seed_everything
+from ._cli import RawAndDefaultsFormatter, add_engine_args, add_guide_args, guide_kwargs, parse_line_args, seed_everything
 from .esm_sampler import ESM_sampler
 from .fasta_io import parse_fasta, write_sequential_fasta
 from .msa_tools import add_gaps_back, unalign
@@ -30,7 +30,7 @@ def main(input_h, output_p, args, sampler=None):
                 continue
             print("\t".join(fields))
             print("\t".join(fields), file=output_h)
-            name, line_args = fields[0], parse_line_args(fields[1])
+            name, line_args = fields[0], {**guide_kwargs(args), **parse_line_args(fields[1])}      # the line's own arguments win
             seeds = parse_fasta(fields[2], clean=None)
             sequences = []
             for _ in range(args.num_output_sequences):
@@ -57,6 +57,7 @@ def build_parser():
     parser.add_argument("--model", type=str, default="esm1b", choices=sorted(model_map), help="which model to use")
     parser.add_argument("--keep_gap_positions", action="store_true", default=False,
                         help="remember where the gaps are in the seed and put them back into the generated sequence.")
+    add_guide_args(parser)
     add_engine_args(parser)
     return parser
 

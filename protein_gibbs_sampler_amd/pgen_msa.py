@@ -8,7 +8,7 @@ import textwrap
 from pathlib import Path
 
 from . import models
-from ._cli import RawAndDefaultsFormatter, add_engine_args, parse_line_args, seed_everything
+from ._cli import GUIDE_EPILOG, RawAndDefaultsFormatter, add_engine_args, parse_line_args, seed_everything
 from .esm_msa_sampler import ESM_MSA_sampler
 from .fasta_io import SequenceSubsetter, parse_fasta, write_sequential_fasta
 
@@ -48,7 +48,7 @@ def build_parser():
             Input should be a tab separated file where columns are:
             sample name, dict of sampler arguments, fasta of seed sequences
             """),
-        epilog="Available sampler arguments: see ESM_MSA_sampler.generate.", formatter_class=RawAndDefaultsFormatter)
+        epilog="Available sampler arguments: see ESM_MSA_sampler.generate.\n\n" + GUIDE_EPILOG, formatter_class=RawAndDefaultsFormatter)
     parser.add_argument("-o", default=".", help="a directory to save the outputs in")
     parser.add_argument("-i", default=None, help="tab separated file: [sample name] \\t [dict of arguments] \\t [seed msa, fasta or a2m].")
     parser.add_argument("--batch_size", type=int, default=1, help="MSA instances per iteration (the reference CLI only allows 1; "

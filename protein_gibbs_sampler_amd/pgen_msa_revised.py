@@ -17,7 +17,7 @@ import textwrap
 import warnings
 
 from . import models, sharding
-from ._cli import RawAndDefaultsFormatter, add_engine_args, seed_everything
+from ._cli import RawAndDefaultsFormatter, add_engine_args, add_guide_args, guide_kwargs, seed_everything
 from .esm_msa_sampler import ESM_MSA_sampler
 from .fasta_io import parse_fasta, write_sequential_fasta
 from .msa_tools import apply_gap_threshold, count_gaps_per_column, delete_msa_cols, generate_alignment, run_phmmer  # noqa: F401
@@ -68,7 +68,7 @@ def _output_path_for_this_process(sampler, output_path):
 
 def pgen_msa(templates_path, references_path, output_path, seqs_per_template, keep_identical, steps, passes, burn_in, device,
              model, alignment_size, ep, op, top_k, legacy=False, gap_percent_threshold=80, debug=False, sampler=None,
-             template_batch=4):
+             template_batch=4, guide_kwargs=None):
     templates = list(zip(*parse_fasta(templates_path, clean="unalign", return_names=True)))
     references = parse_fasta(references_path, clean="unalign")
     if sampler is None:
@@ -101,7 +101,7 @@ def pgen_msa(templates_path, references_path, output_path, seqs_per_template, ke
                 return
             new_seqs = sampler.generate_single_batch([p[1] for p in pending], steps=steps, passes=passes, burn_in=burn_in, k=top_k,
                                                      target_index=row, exclude_positions=[p[2] for p in pending],
-                                                     max_batch=template_batch)
+                                                     max_batch=template_batch, **(guide_kwargs or {}))
             if outfile is not None:
                 for (name, _, _), new_seq in zip(pending, new_seqs):
                     print(f">{name}\n{new_seq.replace('-', '')}", file=outfile, flush=True)
@@ -147,6 +147,7 @@ def build_parser():
     parser.add_argument("--shard_templates", action="store_true", default=False,
                         help="under torchrun (one process per GPU): split the list of templates over the ranks (contiguous blocks, "
                              "one RCCL gather of the resampled rows at the end); the output is identical to a single-GPU run.")
+    add_guide_args(parser)
     add_engine_args(parser)
     return parser
 
@@ -165,7 +166,8 @@ def main(argv=None):
     sampler.shard_over_ranks = args.shard_templates
     pgen_msa(args.templates, args.references, args.o, args.seqs_per_template, args.keep_identical, args.steps, args.passes,
              args.burn_in, args.device, args.model, args.alignment_size, args.ep, args.op, args.top_k, legacy=args.legacy,
-             gap_percent_threshold=args.gap_percent_threshold, debug=args.debug, sampler=sampler, template_batch=args.template_batch)
+             gap_percent_threshold=args.gap_percent_threshold, debug=args.debug, sampler=sampler, template_batch=args.template_batch,
+             guide_kwargs=guide_kwargs(args))
 
 
 if __name__ == "__main__":
