@@ -55,6 +55,11 @@ class ESM1v(_Wrapper):
                          "esm1v_t33_650M_UR90S_1.pt", seed, precision, synthetic, config is not None)
 
 
+def _size(cli):
+    """(configuration, checkpoint file name) of a released ESM-2 size: its row of weights.ESM2_SIZES"""
+    return _w.ESM2_SIZES[cli]["config"], _w.ESM2_SIZES[cli]["file"] + ".pt"
+
+
 class _ESM2(_Wrapper):
     """ESM-2 family: the ESM-1b alphabet, <cls> prepended and <eos> appended; the v2 checkpoint layout."""
     _cfg, _file = None, None
@@ -71,7 +76,7 @@ class ESM2(_ESM2):
     file, 4.4 times the work per token) is refused with a message naming ESM2_3B, and the 150M file (heads of 32) with one naming
     ESM2_150M, the 15B file (heads of 128) with one naming ESM2_15B, the 8M file (heads of 16) with one naming ESM2_8M and the 35M
     file (heads of 24, which run embedded in slots of 32) with one naming ESM2_35M."""
-    _cfg, _file = _w.ESM2_T33_CONFIG, "esm2_t33_650M_UR50D.pt"
+    _cfg, _file = _size("esm2")
 
 
 class ESM2_3B(_ESM2):
@@ -80,7 +85,7 @@ class ESM2_3B(_ESM2):
     with the wider configuration; the widest model the engine's row kernels hold (csrc/ln_row.h).  Sizes come from the file: a
     narrower checkpoint with heads of 64 (the 650M file included) loads here without remark and runs as the model it is -- only the
     opposite mismatch, a 3B file met by ESM2, is refused."""
-    _cfg, _file = _w.ESM2_T36_CONFIG, "esm2_t36_3B_UR50D.pt"
+    _cfg, _file = _size("esm2_3b")
 
 
 class ESM2_150M(_ESM2):
@@ -88,7 +93,7 @@ class ESM2_150M(_ESM2):
     model's GEMM work per token, the size to iterate a design loop with.  The same wrapper as ESM2 with the head-32 instantiations of
     the attention and rotary kernels (csrc/attn_frag.h).  Sizes come from the file: any checkpoint with heads of 32 (at most 32 of
     them) or of 64 loads here and runs as the model it is; heads of 32 load ONLY here -- ESM2 and ESM2_3B refuse them by name."""
-    _cfg, _file = _w.ESM2_T30_CONFIG, "esm2_t30_150M_UR50D.pt"
+    _cfg, _file = _size("esm2_150m")
 
 
 class ESM2_15B(_ESM2):
@@ -100,7 +105,7 @@ class ESM2_15B(_ESM2):
     16-bit modes 2.573 GB at 4 layers and 5.090 GB at 8, i.e. 0.629 GB per layer and 30.3 GB at 48 layers; strict mode
     (precision="fp32") 4.096 GB at 2 layers and 7.713 GB at 4, i.e. 1.809 GB per layer and 87.3 GB at 48.  The 48-layer figures are
     extrapolated from those measurements: the full model has not been created (its synthetic fp32 weights are 60 GB on the host)."""
-    _cfg, _file = _w.ESM2_T48_CONFIG, "esm2_t48_15B_UR50D.pt"
+    _cfg, _file = _size("esm2_15b")
 
 
 class ESM2_8M(_ESM2):
@@ -109,7 +114,7 @@ class ESM2_8M(_ESM2):
     rotary kernels (csrc/attn_frag.h: a half-depth score MFMA, 32-byte LDS rows).  Sizes come from the file: any checkpoint with heads
     of 16 (at most 32 of them, d_model a multiple of 64) or of 64 loads here and runs as the model it is; heads of 16 load ONLY here --
     ESM2, ESM2_3B, ESM2_150M and ESM2_15B refuse them by name."""
-    _cfg, _file = _w.ESM2_T6_CONFIG, "esm2_t6_8M_UR50D.pt"
+    _cfg, _file = _size("esm2_8m")
 
 
 class ESM2_35M(_ESM2):
@@ -120,11 +125,11 @@ class ESM2_35M(_ESM2):
     over the 480 live features (include/pgibbs.h pg_engine_create_embedded).  Sizes come from the file: any
     checkpoint with heads of 24 (at most 32 of them) or of 64 loads here and runs as the model it is; heads of 24 load ONLY here -- the
     other wrappers refuse them by name."""
-    _cfg, _file = _w.ESM2_T12_CONFIG, "esm2_t12_35M_UR50D.pt"
+    _cfg, _file = _size("esm2_35m")
 
 
 # the ESM-2 wrappers under their command-line names (--model)
-ESM2_MODELS = {"esm2": ESM2, "esm2_3b": ESM2_3B, "esm2_150m": ESM2_150M, "esm2_15b": ESM2_15B, "esm2_8m": ESM2_8M, "esm2_35m": ESM2_35M}
+ESM2_MODELS = {cli: globals()[row["wrapper"]] for cli, row in _w.ESM2_SIZES.items()}
 
 
 class ESM_MSA1(_Wrapper):

@@ -44,26 +44,30 @@ ESM2_T30_CONFIG = dict(ESM2_T33_CONFIG, d_model=640, n_layers=30, n_heads=20, d_
 ESM2_T48_CONFIG = dict(ESM2_T33_CONFIG, d_model=5120, n_layers=48, n_heads=40, d_ffn=20480)
 # esm2_t6_8M_UR50D -- models.ESM2_8M: 6 layers of 20 heads of 16
 ESM2_T6_CONFIG = dict(ESM2_T33_CONFIG, d_model=320, n_layers=6, n_heads=20, d_ffn=1280)
-# The head widths the attention and rotary kernels are built for, row for row the table of csrc/head_width.h (tests/test_head_widths_cpu.py
-# holds the two together): at most max_heads heads per row, for ESM-2 only or every architecture, q scaled by q_scale = width^-0.5 as
-# float32; then the released model that needs the width at its widest -- its configuration, file, wrapper (models.*) and --model name
-HEAD_WIDTHS = {
-    64: dict(max_heads=40, esm2_only=False, q_scale=0.125, config=ESM2_T36_CONFIG, file="esm2_t36_3B_UR50D", wrapper="ESM2_3B", cli="esm2_3b"),
-    32: dict(max_heads=32, esm2_only=True, q_scale=0.17677669529663687, config=ESM2_T30_CONFIG, file="esm2_t30_150M_UR50D", wrapper="ESM2_150M",
-             cli="esm2_150m"),
-    128: dict(max_heads=40, esm2_only=True, q_scale=0.08838834764831845, config=ESM2_T48_CONFIG, file="esm2_t48_15B_UR50D", wrapper="ESM2_15B",
-              cli="esm2_15b"),
-    16: dict(max_heads=32, esm2_only=True, q_scale=0.25, config=ESM2_T6_CONFIG, file="esm2_t6_8M_UR50D", wrapper="ESM2_8M", cli="esm2_8m"),
-}
-HEAD_DIMS = tuple(HEAD_WIDTHS)
 # esm2_t12_35M_UR50D -- models.ESM2_35M: 12 layers of 20 heads of 24.  head_slot is the configuration's own say that its heads run embedded
 # in slots of that width (not a field of pg_model_config): a configuration derived from this one keeps it, one derived from another
 # base with heads of 24 does not have it and stays refused by pg_engine_create
 ESM2_T12_CONFIG = dict(ESM2_T33_CONFIG, d_model=480, n_layers=12, n_heads=20, d_ffn=1920, head_slot=32)
+# The released sizes under their --model names: configuration, checkpoint file (without ".pt") and wrapper (models.*).  Head width and
+# slot follow from the configuration (head_dim_of, embedded_slot); models.ESM2_MODELS and tools/esm2_bench.py read this table
+ESM2_SIZES = {cli: dict(config=config, file=file, wrapper=wrapper, cli=cli) for cli, config, file, wrapper in (
+    ("esm2", ESM2_T33_CONFIG, "esm2_t33_650M_UR50D", "ESM2"), ("esm2_3b", ESM2_T36_CONFIG, "esm2_t36_3B_UR50D", "ESM2_3B"),
+    ("esm2_150m", ESM2_T30_CONFIG, "esm2_t30_150M_UR50D", "ESM2_150M"), ("esm2_15b", ESM2_T48_CONFIG, "esm2_t48_15B_UR50D", "ESM2_15B"),
+    ("esm2_8m", ESM2_T6_CONFIG, "esm2_t6_8M_UR50D", "ESM2_8M"), ("esm2_35m", ESM2_T12_CONFIG, "esm2_t12_35M_UR50D", "ESM2_35M"))}
+# The head widths the attention and rotary kernels are built for, row for row the table of csrc/head_width.h (tests/test_head_widths_cpu.py
+# holds the two together): at most max_heads heads per row, for ESM-2 only or every architecture, q scaled by q_scale = width^-0.5 as
+# float32; then the released size that needs the width at its widest -- its row of ESM2_SIZES (config, file, wrapper, cli)
+HEAD_WIDTHS = {
+    64: dict(max_heads=40, esm2_only=False, q_scale=0.125, **ESM2_SIZES["esm2_3b"]),
+    32: dict(max_heads=32, esm2_only=True, q_scale=0.17677669529663687, **ESM2_SIZES["esm2_150m"]),
+    128: dict(max_heads=40, esm2_only=True, q_scale=0.08838834764831845, **ESM2_SIZES["esm2_15b"]),
+    16: dict(max_heads=32, esm2_only=True, q_scale=0.25, **ESM2_SIZES["esm2_8m"]),
+}
+HEAD_DIMS = tuple(HEAD_WIDTHS)
 # Head widths that are no kernel width and run embedded in a slot of one (csrc/engine.hip init_embedded): the engine runs n_heads * slot
 # features per row on zero-padded weights and scales q by q_scale = width^-0.5 as float32, the width's own
 EMBEDDED_WIDTHS = {
-    24: dict(slot=32, q_scale=float(np.float32(24 ** -0.5)), config=ESM2_T12_CONFIG, file="esm2_t12_35M_UR50D", wrapper="ESM2_35M", cli="esm2_35m"),
+    24: dict(slot=32, q_scale=float(np.float32(24 ** -0.5)), **ESM2_SIZES["esm2_35m"]),
 }
 
 
@@ -311,6 +315,24 @@ def checkpoint_args(blob):
     return out
 
 
+def _take(cfg, take, explicit):
+    """cfg.update(take), the file's own hyper-parameters; with explicit=True (the caller passed `config=`) a disagreement raises"""
+    bad = {k: (cfg[k], v) for k, v in take.items() if cfg[k] != v} if explicit else None
+    if bad:
+        raise ValueError("config= disagrees with the checkpoint's own hyper-parameters: %s (given, in the file)" % bad)
+    cfg.update(take)
+
+
+def _count_layers(cfg, take, state_names, explicit):
+    """-> cfg with the number of layers the tensors show, which may stand in for a number nobody stated and must agree with a stated one"""
+    n_layers_seen = 1 + max([int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", n) for n in state_names) if m] or [-1])
+    if n_layers_seen and n_layers_seen != cfg["n_layers"]:
+        if "n_layers" in take or explicit:
+            raise ValueError("checkpoint holds %d layers but its hyper-parameters say %d" % (n_layers_seen, cfg["n_layers"]))
+        cfg["n_layers"] = n_layers_seen
+    return cfg
+
+
 def config_from_checkpoint(args, state_names, base_cfg, explicit=False):
     """The engine configuration a checkpoint asks for: `base_cfg` (the wrapper's architecture defaults) overridden by the
     checkpoint's own hyper-parameters -- what `esm.pretrained.*` builds the module from in the reference
@@ -340,11 +362,7 @@ def config_from_checkpoint(args, state_names, base_cfg, explicit=False):
     esm1b = cfg["arch"] == _lib.PG_ARCH_ESM1B
     if esm1b and "token_dropout" in args:
         take["token_dropout"] = 1 if args["token_dropout"] else 0
-    if explicit:
-        bad = {k: (cfg[k], v) for k, v in take.items() if cfg[k] != v}
-        if bad:
-            raise ValueError("config= disagrees with the checkpoint's own hyper-parameters: %s (given, in the file)" % bad)
-    cfg.update(take)
+    _take(cfg, take, explicit)
     if cfg["n_heads"] * 64 != cfg["d_model"]:
         raise ValueError("checkpoint has %d heads of dimension %g: the engine's attention kernels implement head dimension 64 "
                          "(every model of pgen.models)" % (cfg["n_heads"], cfg["d_model"] / max(1, cfg["n_heads"])))
@@ -373,12 +391,7 @@ def config_from_checkpoint(args, state_names, base_cfg, explicit=False):
                              "does not implement it (none of esm1_t6 / t12 / t34 sets it)")
         if cfg["arch"] == _lib.PG_ARCH_MSA1B:
             warnings.warn("token_dropout=True in an msa_transformer checkpoint is ignored: fair-esm's MSATransformer never reads it")
-    n_layers_seen = 1 + max([int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", n) for n in state_names) if m] or [-1])
-    if n_layers_seen and n_layers_seen != cfg["n_layers"]:
-        if "n_layers" in take or explicit:
-            raise ValueError("checkpoint holds %d layers but its hyper-parameters say %d" % (n_layers_seen, cfg["n_layers"]))
-        cfg["n_layers"] = n_layers_seen
-    return cfg
+    return _count_layers(cfg, take, state_names, explicit)
 
 
 def checkpoint_cfg_v2(blob):
@@ -405,11 +418,7 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
         take["d_ffn"] = 4 * take["d_model"]
     if "token_dropout" in model_cfg:
         take["token_dropout"] = 1 if model_cfg["token_dropout"] else 0
-    if explicit:
-        bad = {k: (cfg[k], v) for k, v in take.items() if cfg[k] != v}
-        if bad:
-            raise ValueError("config= disagrees with the checkpoint's own hyper-parameters: %s (given, in the file)" % bad)
-    cfg.update(take)
+    _take(cfg, take, explicit)
     # Head width (HEAD_WIDTHS).  64 loads against every base configuration; a width built for ESM-2 only loads against a configuration
     # whose own heads have that width (32: ESM2_T30_CONFIG, models.ESM2_150M, and so on) -- a wrapper promises its model, as ESM2 refuses
     # the 3B file below; 24, an embedded width (EMBEDDED_WIDTHS), loads against ESM2_T12_CONFIG only and then under its slot's limits.  Then the engine's own order: heads per row, row width (csrc/engine.hip, csrc/ln_row.h).
@@ -417,18 +426,15 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
     has = "checkpoint has %d heads of dimension %g: " % (cfg["n_heads"], hd)
     row = HEAD_WIDTHS.get(hd)
     emb = EMBEDDED_WIDTHS.get(hd)
-    if emb is not None:
-        # an embedded width loads only against a configuration whose own heads have it (models.ESM2_35M); the slot's limits then
-        if head_dim_of(base_cfg) != hd:
-            raise ValueError(has + "the engine's attention kernels implement head dimension 64 for the configuration it was loaded against; "
-                             "load %s (heads of %g) with models.%s / --model %s" % (emb["file"], hd, emb["wrapper"], emb["cli"]))
-        row = dict(HEAD_WIDTHS[emb["slot"]], esm2_only=False, file=emb["file"], config=emb["config"])
+    own = emb or (row if row and row["esm2_only"] else None)      # a width that loads only against a configuration whose heads have it
+    if own and head_dim_of(base_cfg) != hd:
+        raise ValueError(has + "the engine's attention kernels implement head dimension 64 for the configuration it was loaded against; "
+                         "load %s (heads of %g) with models.%s / --model %s" % (own["file"], hd, own["wrapper"], own["cli"]))
+    if emb:
+        row = dict(HEAD_WIDTHS[emb["slot"]], **ESM2_SIZES[emb["cli"]])      # the slot's limits, the size's own names
     if row is None:
         raise ValueError(has + "the engine's attention kernels implement head dimension 64 (every model of pgen.models) and, for ESM-2, "
                          + ", ".join("%d (%s)" % (w, r["file"]) for w, r in HEAD_WIDTHS.items() if r["esm2_only"]))
-    if row["esm2_only"] and head_dim_of(base_cfg) != hd:
-        raise ValueError(has + "the engine's attention kernels implement head dimension 64 for the configuration it was loaded against; "
-                         "load %s (heads of %g) with models.%s / --model %s" % (row["file"], hd, row["wrapper"], row["cli"]))
     if cfg["n_heads"] > row["max_heads"]:
         raise ValueError(has + "the engine's rotary and row kernels hold at most %d of them per row (d_model %d > %d; %s has %d)"
                          % (row["max_heads"], cfg["d_model"], hd * row["max_heads"], row["file"], row["config"]["n_heads"]))
@@ -438,16 +444,10 @@ def config_from_checkpoint_v2(model_cfg, state_names, base_cfg, explicit=False):
     # models.ESM2 / --model esm2 promise the 650M model: a 3B file is 4.4 times the work and is loaded on purpose, not by accident
     if cfg["d_model"] > ESM2_650M_MAX_D_MODEL and base_cfg["d_model"] <= ESM2_650M_MAX_D_MODEL:
         raise ValueError("checkpoint has d_model %d > %d, wider than the ESM-2 650M configuration it was loaded against: load "
-                         "esm2_t36_3B_UR50D with models.ESM2_3B / --model esm2_3b"
-                         % (cfg["d_model"], ESM2_650M_MAX_D_MODEL))
+                         % (cfg["d_model"], ESM2_650M_MAX_D_MODEL) + "%(file)s with models.%(wrapper)s / --model %(cli)s" % ESM2_SIZES["esm2_3b"])
     if any(n.startswith("emb_layer_norm_before") or n.startswith("embed_positions") for n in state_names):
         raise ValueError("ESM-2 checkpoint with emb_layer_norm_before / embed_positions tensors: the ESM-2 engine has neither")
-    n_layers_seen = 1 + max([int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", n) for n in state_names) if m] or [-1])
-    if n_layers_seen and n_layers_seen != cfg["n_layers"]:
-        if "n_layers" in take or explicit:
-            raise ValueError("checkpoint holds %d layers but its hyper-parameters say %d" % (n_layers_seen, cfg["n_layers"]))
-        cfg["n_layers"] = n_layers_seen
-    return cfg
+    return _count_layers(cfg, take, state_names, explicit)
 
 
 def load_fair_esm_checkpoint(path, cfg, return_config=False, explicit_config=False):

@@ -9,46 +9,19 @@ Written from the published algorithm of fair-esm's `ESM2.forward` (include/pgibb
   x = emb_layer_norm_after(x)
   logits = LN(gelu(dense(x))) @ embed_tokens^T + lm_head.bias      (tied decoder)
 
-MHA_rotary: per head of 64, q = (h W_q^T + b_q) * 64^-0.5 and k = h W_k^T + b_k are rotated before q k^T:
-  inv_freq[i] = 1 / 10000^(2i/64), ang[t][i] = float32(t) * inv_freq[i], t = index along the token axis (0 for <cls>, padding or not)
-  u'[i] = u[i] cos - u[i+32] sin,  u'[i+32] = u[i+32] cos + u[i] sin        ("rotate-half": pairs (i, i + 32)); v is not rotated.
+MHA_rotary: per head of hd = d_model / n_heads (64 by default), q = (h W_q^T + b_q) * hd^-0.5 (a float32 factor) and k = h W_k^T + b_k
+are rotated before q k^T:
+  inv_freq[i] = 1 / 10000^(2i/hd), ang[t][i] = float32(t) * inv_freq[i], t = index along the token axis (0 for <cls>, padding or not)
+  u'[i] = u[i] cos - u[i+hd/2] sin,  u'[i+hd/2] = u[i+hd/2] cos + u[i] sin  ("rotate-half": pairs (i, i + hd/2)); v is not rotated.
 
-Corroborated against an independent implementation, HuggingFace `transformers.EsmForMaskedLM` with rotary positions
-(tests/golden/make_golden_esm2.py -> esm2_hf_*.npz; tests/test_esm2_cpu.py).  Weights: a dict keyed by fair-esm state-dict names.
+Corroborated against an independent implementation, HuggingFace `transformers.EsmForMaskedLM` with rotary positions, at heads of 64,
+32, 128, 16 and 24 (tests/golden/make_golden_esm2.py -> esm2_hf_*.npz; tests/test_esm2_cpu.py, tests/test_esm2_sizes_cpu.py).
+Weights: a dict keyed by fair-esm state-dict names.
 """
 import numpy as np
 from scipy.special import erf
 
 F32 = np.float32
-
-
-def inv_freq():
-    """float32, as torch computes 1.0 / (10000 ** (arange(0, 64, 2).float() / 64)): the power in double, rounded to float32 (numpy's
-    own float32 power is one ulp off at two of the 32 entries)."""
-    return (F32(1.0) / (10000.0 ** (np.arange(32, dtype=np.float64) / 32.0)).astype(F32)).astype(F32)
-
-
-def cos_sin(T):
-    """cos / sin [T][32] float32 of the float32 angle t * inv_freq[i], evaluated in double and rounded."""
-    ang = (np.arange(T, dtype=F32)[:, None] * inv_freq()[None, :]).astype(F32)
-    return np.cos(ang.astype(np.float64)).astype(F32), np.sin(ang.astype(np.float64)).astype(F32)
-
-
-def rotate(u, cos, sin):
-    """u [..., T, 64] float32 -> rotated, every product and the add / subtract rounded to float32 separately."""
-    u = u.astype(F32)
-    lo, hi = u[..., :32], u[..., 32:]
-    return np.concatenate([(lo * cos).astype(F32) - (hi * sin).astype(F32), (hi * cos).astype(F32) + (lo * sin).astype(F32)],
-                          axis=-1).astype(F32)
-
-
-def rotate_qkv_rows(qkv, B, T, H):
-    """[B*T][3*H*64] float32 -> the q and k thirds rotated (row r at position r % T), v untouched: what pg_dbg_rope computes."""
-    cos, sin = cos_sin(T)
-    x = np.array(qkv, dtype=F32).reshape(B, T, 3, H, 64)
-    for part in (0, 1):
-        x[:, :, part] = rotate(x[:, :, part].transpose(0, 2, 1, 3), cos, sin).transpose(0, 2, 1, 3)
-    return x.reshape(B * T, 3 * H * 64)
 
 
 def layer_norm(x, w, b, eps=1e-5):
@@ -73,11 +46,55 @@ def linear(x, w, b):
     return (x @ w.T + b).astype(F32)
 
 
+def inv_freq(hd=64):
+    """float32, as torch computes 1.0 / (10000 ** (arange(0, hd, 2).float() / hd)): the power in double, rounded to float32."""
+    half = hd // 2
+    return (F32(1.0) / (10000.0 ** (np.arange(half, dtype=np.float64) / float(half))).astype(F32)).astype(F32)
+
+
+def cos_sin(T, hd=64):
+    """cos / sin [T][hd/2] float32 of the float32 angle t * inv_freq[i], evaluated in double and rounded."""
+    ang = (np.arange(T, dtype=F32)[:, None] * inv_freq(hd)[None, :]).astype(F32)
+    return np.cos(ang.astype(np.float64)).astype(F32), np.sin(ang.astype(np.float64)).astype(F32)
+
+
+def rotate(u, cos, sin):
+    """u [..., T, hd] float32 -> rotated, every product and the add / subtract rounded to float32 separately."""
+    u = u.astype(F32)
+    half = u.shape[-1] // 2
+    lo, hi = u[..., :half], u[..., half:]
+    return np.concatenate([(lo * cos).astype(F32) - (hi * sin).astype(F32), (hi * cos).astype(F32) + (lo * sin).astype(F32)],
+                          axis=-1).astype(F32)
+
+
+def rotate_qkv_rows(qkv, B, T, H, hd=64):
+    """[B*T][3*H*hd] float32 -> the q and k thirds rotated (row r at position r % T), v untouched: what pg_dbg_rope_hd computes."""
+    cos, sin = cos_sin(T, hd)
+    x = np.array(qkv, dtype=F32).reshape(B, T, 3, H, hd)
+    for part in (0, 1):
+        x[:, :, part] = rotate(x[:, :, part].transpose(0, 2, 1, 3), cos, sin).transpose(0, 2, 1, 3)
+    return x.reshape(B * T, 3 * H * hd)
+
+
+def softmax_attention(qkv, B, T, H, hd, pad=None):
+    """qkv [B][T][3*H*hd] float32 (q already scaled) -> ctx [B][T][H*hd] in float64 arithmetic: what pg_dbg_attention_hd computes.
+    pad [B][T] bool: keys to mask."""
+    x = np.asarray(qkv, dtype=np.float64).reshape(B, T, 3, H, hd).transpose(2, 0, 3, 1, 4)
+    a = x[0] @ x[1].transpose(0, 1, 3, 2)
+    if pad is not None:
+        a = np.where(np.asarray(pad, bool)[:, None, None, :], -np.inf, a)
+    a = a - a.max(axis=-1, keepdims=True)
+    e = np.exp(a)
+    return ((e / e.sum(axis=-1, keepdims=True)) @ x[2]).transpose(0, 2, 1, 3).reshape(B, T, H * hd)
+
+
+
 class Esm2Config:
     def __init__(self, d_model=1280, n_layers=33, n_heads=20, vocab=33, pad_idx=1, mask_idx=32, token_dropout=True, eps=1e-5):
         self.d_model, self.n_layers, self.n_heads, self.vocab = d_model, n_layers, n_heads, vocab
         self.pad_idx, self.mask_idx, self.token_dropout, self.eps = pad_idx, mask_idx, token_dropout, eps
-        assert d_model == 64 * n_heads
+        assert d_model % n_heads == 0
+        self.head_dim = d_model // n_heads
 
     @classmethod
     def of(cls, cfg):
@@ -88,13 +105,13 @@ class Esm2Config:
 
 def _attention(w, p, cfg, h, pad, cos, sin):
     B, T, d = h.shape
-    H = cfg.n_heads
-    q = linear(h, w[p + "q_proj.weight"], w[p + "q_proj.bias"]) * F32(0.125)
+    H, hd = cfg.n_heads, cfg.head_dim
+    q = linear(h, w[p + "q_proj.weight"], w[p + "q_proj.bias"]) * F32(hd ** -0.5)
     k = linear(h, w[p + "k_proj.weight"], w[p + "k_proj.bias"])
     v = linear(h, w[p + "v_proj.weight"], w[p + "v_proj.bias"])
-    q = rotate(q.reshape(B, T, H, 64).transpose(0, 2, 1, 3), cos, sin)
-    k = rotate(k.reshape(B, T, H, 64).transpose(0, 2, 1, 3), cos, sin)
-    v = v.reshape(B, T, H, 64).transpose(0, 2, 1, 3)
+    q = rotate(q.reshape(B, T, H, hd).transpose(0, 2, 1, 3), cos, sin)
+    k = rotate(k.reshape(B, T, H, hd).transpose(0, 2, 1, 3), cos, sin)
+    v = v.reshape(B, T, H, hd).transpose(0, 2, 1, 3)
     a = (q @ k.transpose(0, 1, 3, 2)).astype(F32)
     if pad.any():
         a = np.where(pad[:, None, None, :], F32(-np.inf), a)
@@ -117,7 +134,7 @@ def esm2_forward(w, cfg, tokens):
         ratio = is_mask.sum(axis=1).astype(F32) / (~pad).sum(axis=1).astype(F32)
         x = (x * (F32(1 - 0.15 * 0.8) / (F32(1) - ratio)).astype(F32)[:, None, None]).astype(F32)
     x = np.where(pad[..., None], F32(0), x).astype(F32)
-    cos, sin = cos_sin(T)
+    cos, sin = cos_sin(T, cfg.head_dim)
     for i in range(cfg.n_layers):
         p = "layers.%d." % i
         h = layer_norm(x, w[p + "self_attn_layer_norm.weight"], w[p + "self_attn_layer_norm.bias"], cfg.eps)

@@ -1,13 +1,17 @@
 """Regenerates tests/golden/esm2_hf_*.npz: logits of HuggingFace `transformers.EsmForMaskedLM` with ROTARY positions -- an implementation
 of the ESM-2 architecture independent of this repository -- on seeded synthetic weights, cross-checked against the numpy reference
-tests/_esm2_reference.py at record time (max |difference| < 2e-4).  Modelled on gen_hf of make_golden.py.
+tests/_esm2_reference.py at record time (max |difference| < 2e-4).  Modelled on gen_hf of make_golden.py.  One fixture per head width
+beside the two at 64: hd32 (the esm2_t30_150M_UR50D head width: 6 layers x 640 with 20 heads), hd128 (esm2_t48_15B_UR50D's: 6 layers x
+512 with 4 heads), hd16 (esm2_t6_8M_UR50D itself in shape: 6 layers x 320 with 20 heads) and hd24 (esm2_t12_35M_UR50D itself in shape:
+12 layers x 480 with 20 heads; the engine runs this model embedded in slots of 32).
 
 Needs `transformers` (the test suite does not: it only reads the .npz files, which hold the tokens, the logits and the recipe of the
 weights -- weights.synthetic_state_dict(cfg, seed, std, embed_std, ln_jitter)).  Token batches are UNPADDED: HuggingFace derives
 rotary positions for padded input its own way, so padding is pinned by the contract and the numpy reference, not by these files.
 
-    python tests/golden/make_golden_esm2.py
+    python tests/golden/make_golden_esm2.py [--out DIR] [NAME ...]         (no name: every fixture; DIR: this directory)
 """
+import argparse
 import json
 import os
 import sys
@@ -19,15 +23,19 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-# name -> (config overrides of weights.ESM2_T33_CONFIG, B, L, seed, std, embed_std, ln_jitter)
+# name -> (base configuration of weights, its overrides, B, L, seed of the weights, std, embed_std, ln_jitter, seed of the tokens)
 CASES = {
-    "small": (dict(d_model=256, n_layers=4, d_ffn=1024, max_positions=128), 3, 64, 21, 0.05, 0.3, 0.1),
-    "mid": (dict(d_model=640, n_layers=6, d_ffn=2560, max_positions=512), 2, 256, 22, 0.03, 0.3, 0.1),
+    "small": ("ESM2_T33_CONFIG", dict(d_model=256, n_layers=4, d_ffn=1024, max_positions=128), 3, 64, 21, 0.05, 0.3, 0.1, 301),
+    "mid": ("ESM2_T33_CONFIG", dict(d_model=640, n_layers=6, d_ffn=2560, max_positions=512), 2, 256, 22, 0.03, 0.3, 0.1, 302),
+    "hd32": ("ESM2_T30_CONFIG", dict(n_layers=6, max_positions=512), 2, 256, 23, 0.03, 0.3, 0.1, 303),
+    "hd128": ("ESM2_T48_CONFIG", dict(n_layers=6, d_model=512, d_ffn=2048, max_positions=512), 2, 256, 29, 0.035, 0.3, 0.1, 1283),
+    "hd16": ("ESM2_T6_CONFIG", dict(n_layers=6, max_positions=512), 2, 256, 29, 0.03, 0.3, 0.1, 161),
+    "hd24": ("ESM2_T12_CONFIG", dict(n_layers=12, max_positions=512), 2, 256, 31, 0.03, 0.3, 0.1, 241),
 }
 
 
 def tokens_for(name, B, L):
-    rng = np.random.default_rng({"small": 301, "mid": 302}[name])
+    rng = np.random.default_rng(CASES[name][-1])
     tok = rng.integers(4, 24, size=(B, L + 2))
     tok[:, 0] = 0
     tok[:, -1] = 2
@@ -38,14 +46,20 @@ def tokens_for(name, B, L):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("names", nargs="*", help="the fixtures to write, of %s (default: all)" % ", ".join(CASES))
+    ap.add_argument("--out", default=HERE, help="directory to write esm2_hf_NAME.npz into")
+    args = ap.parse_args()
     import torch
     from transformers import EsmConfig as HC, EsmForMaskedLM
 
     import _esm2_reference as ref
     from protein_gibbs_sampler_amd import weights
 
-    for name, (over, B, L, seed, std, estd, jit) in CASES.items():
-        cfg = weights.make_config(weights.ESM2_T33_CONFIG, **over)
+    for name in args.names or CASES:
+        base, over, B, L, seed, std, estd, jit, _ = CASES[name]
+        cfg = weights.make_config(getattr(weights, base), **over)
+        assert weights.head_dim_of(cfg) == weights.head_dim_of(getattr(weights, base))       # the width the fixture is named for
         w = weights.synthetic_state_dict(cfg, seed=seed, std=std, embed_std=estd, ln_jitter=jit)
         hc = HC(vocab_size=33, hidden_size=cfg["d_model"], num_hidden_layers=cfg["n_layers"], num_attention_heads=cfg["n_heads"],
                 intermediate_size=cfg["d_ffn"], max_position_embeddings=cfg["max_positions"] + 2, position_embedding_type="rotary",
@@ -80,7 +94,7 @@ def main():
         err = float(np.abs(mine - hf_logits).max())
         print("HF cross-check %s: max|reference - HF| = %.3e  (logit std %.3f)" % (name, err, hf_logits.std()))
         assert err < 2e-4, err
-        np.savez_compressed(os.path.join(HERE, "esm2_hf_%s.npz" % name), tokens=tok.astype(np.int32),
+        np.savez_compressed(os.path.join(args.out, "esm2_hf_%s.npz" % name), tokens=tok.astype(np.int32),
                             logits=hf_logits.astype(np.float32), cfg=json.dumps(over), seed=seed, std=std, embed_std=estd, ln_jitter=jit)
 
 

@@ -1,25 +1,16 @@
-"""ESM-2 15B (esm2_t48_15B_UR50D: 40 heads of 128, d_model 5120) on the host: the configuration, the rotary frequencies for heads of
-128, the v2 checkpoint reader and which head widths load against which configuration, models.ESM2_15B, the command-line model maps,
-the attention plans at head dimension 128 (whole sequences up to 288 keys, 128-key tiles beyond) and the row entries' acceptance of
-widths above 2560 in whole 512-feature units only.  Needs no GPU."""
+"""ESM-2 15B (esm2_t48_15B_UR50D: 40 heads of 128, d_model 5120) on the host: the tensor shapes at 5120, which sizes and head widths
+load against the configuration, the attention plans at head dimension 128 (whole sequences up to 288 keys, 128-key tiles beyond) and
+the row entries' acceptance of widths above 2560 in whole 512-feature units only; and, as shared bodies of tests/_esm2_cpu_common.py,
+the rotary frequencies, the refusal of a head-128 file by the other sizes and the command-line model maps.  The configuration's values,
+the v2 file's round trip and inv_freq check and models.ESM2_15B are the esm2_15b rows of tests/test_esm2_sizes_cpu.py.  Needs no GPU."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import _esm2_cpu_common as common
 from protein_gibbs_sampler_amd import _lib, weights
 from test_attention_plan_cpu import F16, att, plans, strict
-
-
-def test_t48_config_values():
-    cfg = weights.ESM2_T48_CONFIG
-    assert (cfg["arch"], cfg["d_model"], cfg["n_layers"], cfg["n_heads"], cfg["d_ffn"], cfg["vocab"]) == (_lib.PG_ARCH_ESM2, 5120, 48, 40, 20480, 33)
-    assert weights.head_dim_of(cfg) == 128 and 128 in weights.HEAD_DIMS
-    same = ("max_positions", "pad_idx", "mask_idx", "cls_idx", "eos_idx", "token_dropout", "max_msa_rows", "layer_norm_eps")
-    assert all(cfg[k] == weights.ESM2_T33_CONFIG[k] for k in same)
-    assert weights.MAX_D_MODEL == 2560 and weights.MAX_D_MODEL_HD128 == 5120 and weights.MAX_HEADS_OF_128 == 40
-    assert weights.make_config(weights.ESM2_T48_CONFIG, d_model=256, n_layers=2, d_ffn=512)["n_heads"] == 2      # the base's head width
-    assert weights.ESM2_T36_CONFIG["n_heads"] == 40 and weights.ESM2_T30_CONFIG["n_heads"] == 20                   # the others are untouched
 
 
 def test_tensor_names_and_shapes_at_5120():
@@ -32,69 +23,12 @@ def test_tensor_names_and_shapes_at_5120():
     assert not any(k.startswith(("embed_positions", "emb_layer_norm_before")) for k in sd)
 
 
-def test_inv_freq_128_is_torchs():
-    torch = pytest.importorskip("torch")
-    want = (1.0 / (10000 ** (torch.arange(0, 128, 2).float() / 128))).numpy()
-    assert np.array_equal(weights.rotary_inv_freq(128), want)
-    want64 = (1.0 / (10000 ** (torch.arange(0, 64, 2).float() / 64))).numpy()
-    assert np.array_equal(weights.rotary_inv_freq(), want64)
-
-
-@pytest.fixture(scope="module")
-def hd128_file(tmp_path_factory):
-    """A v2 checkpoint file of 2 layers x 256 with two heads of 128 and the state dict it was written from."""
-    torch = pytest.importorskip("torch")
-    cfg = weights.make_config(weights.ESM2_T48_CONFIG, d_model=256, n_layers=2, d_ffn=1024, max_positions=40)
-    assert cfg["n_heads"] == 2
-    sd = weights.synthetic_state_dict(cfg, seed=12, embed_std=0.3)
-    path = tmp_path_factory.mktemp("esm2_15b") / "esm2_hd128.pt"
-    torch.save(weights.to_fair_esm_checkpoint_v2(sd, cfg), path)
-    return str(path), cfg, sd
-
-
-def test_v2_round_trip_with_heads_of_128(hd128_file):
-    torch = pytest.importorskip("torch")
-    path, cfg, sd = hd128_file
-    blob = torch.load(path, weights_only=False)
-    stored = blob["model"]["encoder.sentence_encoder.layers.1.self_attn.rot_emb.inv_freq"].numpy()
-    assert stored.shape == (64,) and np.array_equal(stored, weights.rotary_inv_freq(128))
-    got, cfg2 = weights.load_fair_esm_checkpoint(path, weights.ESM2_T48_CONFIG, return_config=True)
-    assert (cfg2["d_model"], cfg2["n_layers"], cfg2["n_heads"], cfg2["d_ffn"], cfg2["token_dropout"]) == (256, 2, 2, 1024, 1)
-    assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
-
-
-def test_inv_freq_check_at_128(hd128_file, tmp_path):
-    torch = pytest.importorskip("torch")
-    path, cfg, sd = hd128_file
-    blob = weights.to_fair_esm_checkpoint_v2(sd, cfg)
-    key = "encoder.sentence_encoder.layers.0.self_attn.rot_emb.inv_freq"
-    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(64))                      # the head-64 table in a head-128 file
-    p = tmp_path / "bad.pt"
-    torch.save(blob, p)
-    with pytest.raises(ValueError, match=r"inv_freq.*heads of 128"):
-        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T48_CONFIG)
-    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(128) * np.float32(1.001))
-    torch.save(blob, p)
-    with pytest.raises(ValueError, match="inv_freq"):
-        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T48_CONFIG)
-
-
 def test_t48_takes_the_15b_sizes_from_hyper_parameters_alone():
     cfg = weights.config_from_checkpoint_v2(dict(encoder_embed_dim=5120, encoder_layers=48, encoder_attention_heads=40, token_dropout=True),
                                             [], weights.ESM2_T48_CONFIG)
     assert (cfg["d_model"], cfg["n_heads"], cfg["d_ffn"], cfg["n_layers"]) == (5120, 40, 20480, 48)
     cfg = weights.config_from_checkpoint_v2(dict(encoder_embed_dim=2560, encoder_layers=36, encoder_attention_heads=40), [], weights.ESM2_T48_CONFIG)
     assert (cfg["d_model"], cfg["n_heads"]) == (2560, 40)                                   # heads of 64 load against every configuration
-
-
-@pytest.mark.parametrize("base", ["t33", "t36", "t30"])
-def test_heads_of_128_met_by_the_other_wrappers_name_esm2_15b(hd128_file, base):
-    path, cfg, sd = hd128_file
-    base_cfg = {"t33": weights.ESM2_T33_CONFIG, "t36": weights.ESM2_T36_CONFIG, "t30": weights.ESM2_T30_CONFIG}[base]
-    with pytest.raises(ValueError, match=r"heads of dimension 128: .*head dimension 64.*models\.ESM2_15B / --model esm2_15b"):
-        weights.load_fair_esm_checkpoint(path, base_cfg)
-    with pytest.raises(ValueError, match="esm2_15b"):
-        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=5120, encoder_layers=48, encoder_attention_heads=40), [], base_cfg)
 
 
 def test_more_than_40_heads_of_128_and_odd_widths_are_refused():
@@ -106,28 +40,6 @@ def test_more_than_40_heads_of_128_and_odd_widths_are_refused():
         weights.config_from_checkpoint_v2(dict(encoder_embed_dim=480, encoder_layers=2, encoder_attention_heads=20), [], weights.ESM2_T48_CONFIG)
     with pytest.raises(ValueError, match="esm2_150m"):                                      # heads of 32 still load against t30 only
         weights.config_from_checkpoint_v2(dict(encoder_embed_dim=640, encoder_layers=2, encoder_attention_heads=20), [], weights.ESM2_T48_CONFIG)
-
-
-def test_models_esm2_15b_reads_a_v2_file_without_a_gpu(hd128_file):
-    from protein_gibbs_sampler_amd import models
-    path, cfg, sd = hd128_file
-    m = models.ESM2_15B(checkpoint=path)
-    assert m.cfg["arch"] == _lib.PG_ARCH_ESM2 and (m.cfg["d_model"], m.cfg["n_heads"], m.cfg["d_ffn"], m.cfg["n_layers"]) == (256, 2, 1024, 2)
-    assert m.alphabet.mask_idx == 32 and len(m.alphabet.all_toks) == 33 and m.alphabet.prepend_bos and m.alphabet.append_eos
-    for other in (models.ESM2, models.ESM2_3B, models.ESM2_150M):
-        with pytest.raises(ValueError, match="esm2_15b"):
-            other(checkpoint=path)
-    if not weights.find_cached_checkpoint("esm2_t48_15B_UR50D.pt"):
-        with pytest.raises(FileNotFoundError, match="esm2_t48_15B_UR50D"):
-            models.ESM2_15B()
-
-
-def test_command_lines_accept_esm2_15b():
-    from protein_gibbs_sampler_amd import likelihood_esm, models, pgen_esm, pgen_esm_from_fasta
-    for mod in (pgen_esm, pgen_esm_from_fasta, likelihood_esm):
-        assert mod.model_map["esm2_15b"] is models.ESM2_15B and mod.model_map["esm2_3b"] is models.ESM2_3B
-        assert mod.build_parser().parse_args(["--model", "esm2_15b"]).model == "esm2_15b"
-    assert pgen_esm.build_parser().parse_args([]).model == "esm1b"                       # defaults unchanged
 
 
 # ---- attention plans at head dimension 128 (an MI355X: 256 CUs) ------------------------------------------------------------------------
@@ -202,3 +114,17 @@ def test_rope_entry_takes_40_heads_of_128_and_refuses_41_on_the_host():
     assert L.pg_dbg_rope_hd(0, _lib.PG_PREC_BF16, _lib.ptr(x), 1, 2, 41, 128) == _lib.PG_ERR_INVALID
     assert L.pg_dbg_rope(0, _lib.PG_PREC_BF16, _lib.ptr(x), 1, 2, 41) == _lib.PG_ERR_INVALID                  # head 64: still 40 at most
     assert L.pg_dbg_rope_hd(0, _lib.PG_PREC_BF16, _lib.ptr(x), 1, 2, 2, 48) == _lib.PG_ERR_INVALID
+
+
+# ---- the shared bodies (tests/_esm2_cpu_common.py) at this size -------------------------------------------------------------------------
+def test_inv_freq_128_is_torchs():
+    common.check_inv_freq_is_torchs("esm2_15b")
+
+
+@pytest.mark.parametrize("base", common.other_bases("esm2_15b"))
+def test_heads_of_128_met_by_the_other_wrappers_name_esm2_15b(tmp_path_factory, base):
+    common.check_met_by_another_size("esm2_15b", base, tmp_path_factory)
+
+
+def test_command_lines_accept_esm2_15b():
+    common.check_command_lines_accept("esm2_15b")

@@ -1,14 +1,16 @@
 """ESM-2 35M (esm2_t12_35M_UR50D: 20 heads of 24, d_model 480) on the host.  Heads of 24 are no kernel width: the engine runs the model
 embedded, every head in a slot of 32 and its rows 640 wide (include/pgibbs.h pg_engine_create_embedded).  Here: the configuration and
-the table of embedded widths, the rotary frequencies for heads of 24, the v2 checkpoint reader and which configuration such a file
-loads against, models.ESM2_35M, the command-line maps, the embedded entry's refusals (no device is needed to be refused), the
-run-shape image of every tensor role -- live values exactly where the layout says, 0.0 everywhere else -- and the rotary table.
-Needs no GPU."""
+the table of embedded widths, what loads against the configuration, the embedded entry's refusals (no device is needed to be
+refused), the run-shape image of every tensor role -- live values exactly where the layout says, 0.0 everywhere else -- and the rotary
+table; and, as shared bodies of tests/_esm2_cpu_common.py, the rotary frequencies for heads of 24, the refusal of a head-24 file by the
+other sizes and the command-line model maps.  The v2 file's round trip and inv_freq check and models.ESM2_35M are the esm2_35m rows of
+tests/test_esm2_sizes_cpu.py.  Needs no GPU."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import _esm2_cpu_common as common
 from protein_gibbs_sampler_amd import _lib, weights
 
 W, SLOT = 24, 32
@@ -33,35 +35,6 @@ def test_t12_config_values_and_the_embedded_table():
     assert weights.make_config(cfg, d_model=96, n_layers=2, d_ffn=256)["n_heads"] == 4                        # the base's head width
 
 
-def test_inv_freq_24_is_torchs():
-    torch = pytest.importorskip("torch")
-    want = (1.0 / (10000 ** (torch.arange(0, 24, 2).float() / 24))).numpy()
-    assert np.array_equal(weights.rotary_inv_freq(24), want)
-
-
-@pytest.fixture(scope="module")
-def hd24_file(tmp_path_factory):
-    """A v2 checkpoint file of 2 layers x 480 with 20 heads of 24 and the state dict it was written from."""
-    torch = pytest.importorskip("torch")
-    cfg = weights.make_config(weights.ESM2_T12_CONFIG, n_layers=2, max_positions=40)
-    assert (cfg["d_model"], cfg["n_heads"], cfg["d_ffn"]) == (480, 20, 1920)
-    sd = weights.synthetic_state_dict(cfg, seed=12, embed_std=0.3)
-    path = tmp_path_factory.mktemp("esm2_35m") / "esm2_hd24.pt"
-    torch.save(weights.to_fair_esm_checkpoint_v2(sd, cfg), path)
-    return str(path), cfg, sd
-
-
-def test_v2_round_trip_with_heads_of_24(hd24_file):
-    torch = pytest.importorskip("torch")
-    path, cfg, sd = hd24_file
-    blob = torch.load(path, weights_only=False)
-    stored = blob["model"]["encoder.sentence_encoder.layers.1.self_attn.rot_emb.inv_freq"].numpy()
-    assert stored.shape == (12,) and np.array_equal(stored, weights.rotary_inv_freq(24))
-    got, cfg2 = weights.load_fair_esm_checkpoint(path, weights.ESM2_T12_CONFIG, return_config=True)
-    assert (cfg2["d_model"], cfg2["n_layers"], cfg2["n_heads"], cfg2["d_ffn"], cfg2["token_dropout"]) == (480, 2, 20, 1920, 1)
-    assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
-
-
 def test_t12_takes_the_35m_sizes_from_hyper_parameters_alone():
     cfg = weights.config_from_checkpoint_v2(dict(encoder_embed_dim=480, encoder_layers=12, encoder_attention_heads=20, token_dropout=True),
                                             [], weights.ESM2_T12_CONFIG)
@@ -70,58 +43,6 @@ def test_t12_takes_the_35m_sizes_from_hyper_parameters_alone():
         weights.config_from_checkpoint_v2(dict(encoder_embed_dim=33 * 24, encoder_layers=2, encoder_attention_heads=33), [], weights.ESM2_T12_CONFIG)
     with pytest.raises(ValueError, match="esm2_150m"):                                                         # heads of 32 load against t30 only
         weights.config_from_checkpoint_v2(dict(encoder_embed_dim=640, encoder_layers=2, encoder_attention_heads=20), [], weights.ESM2_T12_CONFIG)
-
-
-def test_inv_freq_check_at_24(hd24_file, tmp_path):
-    torch = pytest.importorskip("torch")
-    path, cfg, sd = hd24_file
-    blob = weights.to_fair_esm_checkpoint_v2(sd, cfg)
-    key = "encoder.sentence_encoder.layers.0.self_attn.rot_emb.inv_freq"
-    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(32))                      # the head-32 table in a head-24 file
-    p = tmp_path / "bad.pt"
-    torch.save(blob, p)
-    with pytest.raises(ValueError, match=r"inv_freq.*heads of 24"):
-        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T12_CONFIG)
-    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(24) * np.float32(1.001))
-    torch.save(blob, p)
-    with pytest.raises(ValueError, match="inv_freq"):
-        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T12_CONFIG)
-
-
-@pytest.mark.parametrize("base", ["t6", "t30", "t33", "t36", "t48"])
-def test_heads_of_24_met_by_the_other_wrappers_name_esm2_35m(hd24_file, base):
-    path, cfg, sd = hd24_file
-    base_cfg = {"t6": weights.ESM2_T6_CONFIG, "t30": weights.ESM2_T30_CONFIG, "t33": weights.ESM2_T33_CONFIG, "t36": weights.ESM2_T36_CONFIG,
-                "t48": weights.ESM2_T48_CONFIG}[base]
-    with pytest.raises(ValueError, match=r"checkpoint has 20 heads of dimension 24: .*head dimension 64.*models\.ESM2_35M / --model esm2_35m$"):
-        weights.load_fair_esm_checkpoint(path, base_cfg)
-    with pytest.raises(ValueError, match="esm2_35m"):
-        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=480, encoder_layers=12, encoder_attention_heads=20), [], base_cfg)
-
-
-def test_models_esm2_35m_reads_a_v2_file_without_a_gpu(hd24_file):
-    from protein_gibbs_sampler_amd import models
-    path, cfg, sd = hd24_file
-    m = models.ESM2_35M(checkpoint=path)
-    assert m.cfg["arch"] == _lib.PG_ARCH_ESM2 and (m.cfg["d_model"], m.cfg["n_heads"], m.cfg["d_ffn"], m.cfg["n_layers"]) == (480, 20, 1920, 2)
-    assert m.alphabet.mask_idx == 32 and len(m.alphabet.all_toks) == 33 and m.alphabet.prepend_bos and m.alphabet.append_eos
-    assert models.ESM2_MODELS["esm2_35m"] is models.ESM2_35M
-    for other in (models.ESM2, models.ESM2_3B, models.ESM2_150M, models.ESM2_15B, models.ESM2_8M):
-        with pytest.raises(ValueError, match="esm2_35m"):
-            other(checkpoint=path)
-    if not weights.find_cached_checkpoint("esm2_t12_35M_UR50D.pt"):
-        with pytest.raises(FileNotFoundError, match="esm2_t12_35M_UR50D"):
-            models.ESM2_35M()
-
-
-def test_command_lines_accept_esm2_35m():
-    from protein_gibbs_sampler_amd import likelihood_esm, models, pgen_esm, pgen_esm_from_fasta, seq_probs_esm
-    for mod in (pgen_esm, pgen_esm_from_fasta, likelihood_esm):
-        assert mod.model_map["esm2_35m"] is models.ESM2_35M and mod.model_map["esm2_8m"] is models.ESM2_8M
-        assert mod.build_parser().parse_args(["--model", "esm2_35m"]).model == "esm2_35m"
-    assert seq_probs_esm.model_map["esm2_35m"] is models.ESM2_35M
-    assert pgen_esm.build_parser().parse_args([]).model == "esm1b"                       # defaults unchanged
-    assert likelihood_esm.build_parser().parse_args([]).model == "esm1v"
 
 
 # ---- the embedded entry: refused, or past every check, before a device is looked for ---------------------------------------------------
@@ -307,3 +228,17 @@ def test_live_row_entries_take_16_bit_modes_only():
         args = _live_cases()[name][0]
         rc, msg = _call(name, args[:1] + [_lib.PG_PREC_FP32] + args[2:])
         assert rc == _lib.PG_ERR_INVALID and msg == name + ": precision must be PG_PREC_BF16 or PG_PREC_F16"
+
+
+# ---- the shared bodies (tests/_esm2_cpu_common.py) at this size -------------------------------------------------------------------------
+def test_inv_freq_24_is_torchs():
+    common.check_inv_freq_is_torchs("esm2_35m")
+
+
+@pytest.mark.parametrize("base", common.other_bases("esm2_35m"))
+def test_heads_of_24_met_by_the_other_wrappers_name_esm2_35m(tmp_path_factory, base):
+    common.check_met_by_another_size("esm2_35m", base, tmp_path_factory)
+
+
+def test_command_lines_accept_esm2_35m():
+    common.check_command_lines_accept("esm2_35m")

@@ -1,19 +1,11 @@
 """ESM-2 3B (esm2_t36_3B_UR50D) on the host: the configuration, the v2 checkpoint reader at d_model 2560, which widths are loaded
-against which configuration, models.ESM2_3B and the command-line model maps.  Needs no GPU."""
+against which configuration, models.ESM2_3B and the command-line model maps (a shared body of tests/_esm2_cpu_common.py).  The
+configuration's values are the esm2_3b row of tests/test_esm2_sizes_cpu.py.  Needs no GPU."""
 import numpy as np
 import pytest
 
+import _esm2_cpu_common as common
 from protein_gibbs_sampler_amd import _lib, weights
-
-
-def test_t36_config_values():
-    cfg = weights.ESM2_T36_CONFIG
-    assert (cfg["arch"], cfg["d_model"], cfg["n_layers"], cfg["n_heads"], cfg["d_ffn"], cfg["vocab"]) == (_lib.PG_ARCH_ESM2, 2560, 36, 40, 10240, 33)
-    assert cfg["n_heads"] * 64 == cfg["d_model"] and cfg["d_ffn"] == 4 * cfg["d_model"]
-    same = ("max_positions", "pad_idx", "mask_idx", "cls_idx", "eos_idx", "token_dropout", "max_msa_rows", "layer_norm_eps")
-    assert all(cfg[k] == weights.ESM2_T33_CONFIG[k] for k in same)
-    assert weights.MAX_D_MODEL == 2560
-    assert weights.ESM2_T33_CONFIG["d_model"] == 1280 and weights.ESM2_T33_CONFIG["n_layers"] == 33          # the 650M config is untouched
 
 
 def test_t36_tensor_names_and_shapes():
@@ -107,11 +99,4 @@ def test_models_esm2_3b_reads_a_v2_file_without_a_gpu(wide_file, tmp_path):
 
 
 def test_command_lines_accept_esm2_3b():
-    from protein_gibbs_sampler_amd import likelihood_esm, models, pgen_esm, pgen_esm_from_fasta
-    for mod in (pgen_esm, pgen_esm_from_fasta, likelihood_esm):
-        assert mod.model_map["esm2_3b"] is models.ESM2_3B and mod.model_map["esm2"] is models.ESM2
-    assert pgen_esm.build_parser().parse_args(["--model", "esm2_3b", "--synthetic-weights"]).model == "esm2_3b"
-    assert likelihood_esm.build_parser().parse_args(["--model", "esm2_3b"]).model == "esm2_3b"
-    assert pgen_esm_from_fasta.build_parser().parse_args(["--model", "esm2_3b"]).model == "esm2_3b"
-    assert pgen_esm.build_parser().parse_args([]).model == "esm1b"                   # defaults unchanged
-    assert likelihood_esm.build_parser().parse_args([]).model == "esm1v"
+    common.check_command_lines_accept("esm2_3b")

@@ -1,7 +1,8 @@
-"""ESM-2 8M (esm2_t6_8M_UR50D: 20 heads of 16, d_model 320) on the host: the configuration, the rotary frequencies for heads of 16, the
-v2 checkpoint reader and which head widths load against which configuration, models.ESM2_8M, the command-line model maps, the numpy
-reference at heads of 16 against the HuggingFace fixture, the attention and GEMM plans at the 8M shapes, the LDS bank model of the
-32-byte key row, and the host-side refusals of the debug entries.  Needs no GPU."""
+"""ESM-2 8M (esm2_t6_8M_UR50D: 20 heads of 16, d_model 320) on the host: which sizes and head widths load against the configuration,
+the numpy reference at heads of 16 against the HuggingFace fixture, the attention and GEMM plans at the 8M shapes, the LDS bank model
+of the 32-byte key row, the host-side refusals of the debug entries and, as shared bodies of tests/_esm2_cpu_common.py, the rotary
+frequencies, the refusal of a head-16 file by the other sizes and the command-line model maps.  The configuration's values, the v2
+file's round trip and inv_freq check and models.ESM2_8M are the esm2_8m rows of tests/test_esm2_sizes_cpu.py.  Needs no GPU."""
 import json
 import os
 import subprocess
@@ -10,7 +11,8 @@ import sys
 import numpy as np
 import pytest
 
-import _esm2_reference_hd as ref
+import _esm2_cpu_common as common
+import _esm2_reference as ref
 from protein_gibbs_sampler_amd import _lib, weights
 from test_attention_plan_cpu import F16, att, plans, strict
 from test_gemm_plan_cpu import layer, rows
@@ -18,46 +20,6 @@ from test_gemm_plan_cpu import plans as gemm_plans
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def test_t6_config_values():
-    cfg = weights.ESM2_T6_CONFIG
-    assert (cfg["arch"], cfg["d_model"], cfg["n_layers"], cfg["n_heads"], cfg["d_ffn"], cfg["vocab"]) == (_lib.PG_ARCH_ESM2, 320, 6, 20, 1280, 33)
-    assert weights.head_dim_of(cfg) == 16 and 16 in weights.HEAD_DIMS and 24 not in weights.HEAD_DIMS
-    same = ("max_positions", "pad_idx", "mask_idx", "cls_idx", "eos_idx", "token_dropout", "max_msa_rows", "layer_norm_eps")
-    assert all(cfg[k] == weights.ESM2_T33_CONFIG[k] for k in same)
-    assert weights.MAX_HEADS_OF_16 == 32
-    assert weights.make_config(weights.ESM2_T6_CONFIG, d_model=128, n_layers=2, d_ffn=512)["n_heads"] == 8      # the base's head width
-    assert weights.ESM2_T30_CONFIG["n_heads"] == 20 and weights.ESM2_T48_CONFIG["n_heads"] == 40                  # the others are untouched
-
-
-def test_inv_freq_16_is_torchs():
-    torch = pytest.importorskip("torch")
-    want = (1.0 / (10000 ** (torch.arange(0, 16, 2).float() / 16))).numpy()
-    assert np.array_equal(weights.rotary_inv_freq(16), want)
-
-
-@pytest.fixture(scope="module")
-def hd16_file(tmp_path_factory):
-    """A v2 checkpoint file of 2 layers x 320 with 20 heads of 16 and the state dict it was written from."""
-    torch = pytest.importorskip("torch")
-    cfg = weights.make_config(weights.ESM2_T6_CONFIG, n_layers=2, max_positions=40)
-    assert (cfg["d_model"], cfg["n_heads"], cfg["d_ffn"]) == (320, 20, 1280)
-    sd = weights.synthetic_state_dict(cfg, seed=12, embed_std=0.3)
-    path = tmp_path_factory.mktemp("esm2_8m") / "esm2_hd16.pt"
-    torch.save(weights.to_fair_esm_checkpoint_v2(sd, cfg), path)
-    return str(path), cfg, sd
-
-
-def test_v2_round_trip_with_heads_of_16(hd16_file):
-    torch = pytest.importorskip("torch")
-    path, cfg, sd = hd16_file
-    blob = torch.load(path, weights_only=False)
-    stored = blob["model"]["encoder.sentence_encoder.layers.1.self_attn.rot_emb.inv_freq"].numpy()
-    assert stored.shape == (8,) and np.array_equal(stored, weights.rotary_inv_freq(16))
-    got, cfg2 = weights.load_fair_esm_checkpoint(path, weights.ESM2_T6_CONFIG, return_config=True)
-    assert (cfg2["d_model"], cfg2["n_layers"], cfg2["n_heads"], cfg2["d_ffn"], cfg2["token_dropout"]) == (320, 2, 20, 1280, 1)
-    assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
 
 
 def test_t6_takes_the_8m_sizes_from_hyper_parameters_alone():
@@ -77,57 +39,6 @@ def test_more_than_32_heads_of_16_and_heads_of_24_are_refused():
         weights.config_from_checkpoint_v2(dict(encoder_embed_dim=640, encoder_layers=2, encoder_attention_heads=20), [], weights.ESM2_T6_CONFIG)
     with pytest.raises(ValueError, match="esm2_15b"):
         weights.config_from_checkpoint_v2(dict(encoder_embed_dim=256, encoder_layers=2, encoder_attention_heads=2), [], weights.ESM2_T6_CONFIG)
-
-
-def test_inv_freq_check_at_16(hd16_file, tmp_path):
-    torch = pytest.importorskip("torch")
-    path, cfg, sd = hd16_file
-    blob = weights.to_fair_esm_checkpoint_v2(sd, cfg)
-    key = "encoder.sentence_encoder.layers.0.self_attn.rot_emb.inv_freq"
-    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(32))                      # the head-32 table in a head-16 file
-    p = tmp_path / "bad.pt"
-    torch.save(blob, p)
-    with pytest.raises(ValueError, match=r"inv_freq.*heads of 16"):
-        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T6_CONFIG)
-    blob["model"][key] = torch.from_numpy(weights.rotary_inv_freq(16) * np.float32(1.001))
-    torch.save(blob, p)
-    with pytest.raises(ValueError, match="inv_freq"):
-        weights.load_fair_esm_checkpoint(str(p), weights.ESM2_T6_CONFIG)
-
-
-@pytest.mark.parametrize("base", ["t33", "t36", "t30", "t48"])
-def test_heads_of_16_met_by_the_other_wrappers_name_esm2_8m(hd16_file, base):
-    path, cfg, sd = hd16_file
-    base_cfg = {"t33": weights.ESM2_T33_CONFIG, "t36": weights.ESM2_T36_CONFIG, "t30": weights.ESM2_T30_CONFIG,
-                "t48": weights.ESM2_T48_CONFIG}[base]
-    with pytest.raises(ValueError, match=r"heads of dimension 16: .*head dimension 64.*models\.ESM2_8M / --model esm2_8m"):
-        weights.load_fair_esm_checkpoint(path, base_cfg)
-    with pytest.raises(ValueError, match="esm2_8m"):
-        weights.config_from_checkpoint_v2(dict(encoder_embed_dim=320, encoder_layers=6, encoder_attention_heads=20), [], base_cfg)
-
-
-def test_models_esm2_8m_reads_a_v2_file_without_a_gpu(hd16_file):
-    from protein_gibbs_sampler_amd import models
-    path, cfg, sd = hd16_file
-    m = models.ESM2_8M(checkpoint=path)
-    assert m.cfg["arch"] == _lib.PG_ARCH_ESM2 and (m.cfg["d_model"], m.cfg["n_heads"], m.cfg["d_ffn"], m.cfg["n_layers"]) == (320, 20, 1280, 2)
-    assert m.alphabet.mask_idx == 32 and len(m.alphabet.all_toks) == 33 and m.alphabet.prepend_bos and m.alphabet.append_eos
-    for other in (models.ESM2, models.ESM2_3B, models.ESM2_150M, models.ESM2_15B):
-        with pytest.raises(ValueError, match="esm2_8m"):
-            other(checkpoint=path)
-    if not weights.find_cached_checkpoint("esm2_t6_8M_UR50D.pt"):
-        with pytest.raises(FileNotFoundError, match="esm2_t6_8M_UR50D"):
-            models.ESM2_8M()
-
-
-def test_command_lines_accept_esm2_8m():
-    from protein_gibbs_sampler_amd import likelihood_esm, models, pgen_esm, pgen_esm_from_fasta, seq_probs_esm
-    for mod in (pgen_esm, pgen_esm_from_fasta, likelihood_esm):
-        assert mod.model_map["esm2_8m"] is models.ESM2_8M and mod.model_map["esm2_15b"] is models.ESM2_15B
-        assert mod.build_parser().parse_args(["--model", "esm2_8m"]).model == "esm2_8m"
-    assert seq_probs_esm.model_map["esm2_8m"] is models.ESM2_8M
-    assert pgen_esm.build_parser().parse_args([]).model == "esm1b"                       # defaults unchanged
-    assert likelihood_esm.build_parser().parse_args([]).model == "esm1v"
 
 
 # ---- the numpy reference at heads of 16 ------------------------------------------------------------------------------------------------
@@ -239,3 +150,17 @@ def test_debug_entries_refuse_on_the_host():
     assert rc == _lib.PG_ERR_INVALID and b"heads of 64 only" in L.pg_last_error()
     rc = L.pg_dbg_attention_hd(0, _lib.PG_PREC_BF16, _lib.ptr(qkv), _lib.ptr(ctx), 1, T, H, 24, None, -1)
     assert rc == _lib.PG_ERR_INVALID and b"head_dim must be 64 or 32" in L.pg_last_error()
+
+
+# ---- the shared bodies (tests/_esm2_cpu_common.py) at this size -------------------------------------------------------------------------
+def test_inv_freq_16_is_torchs():
+    common.check_inv_freq_is_torchs("esm2_8m")
+
+
+@pytest.mark.parametrize("base", common.other_bases("esm2_8m"))
+def test_heads_of_16_met_by_the_other_wrappers_name_esm2_8m(tmp_path_factory, base):
+    common.check_met_by_another_size("esm2_8m", base, tmp_path_factory)
+
+
+def test_command_lines_accept_esm2_8m():
+    common.check_command_lines_accept("esm2_8m")

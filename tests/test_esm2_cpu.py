@@ -1,11 +1,13 @@
 """ESM-2 on the host: the numpy reference against an independent implementation (HuggingFace rotary ESM, stored logits), the
-rotate-half identities, the v2 checkpoint reader and the command-line model maps.  Needs no GPU."""
+rotate-half identities, the v2 checkpoint reader and, as shared bodies of tests/_esm2_cpu_common.py, the rotary frequencies against
+torch's and the command-line model maps.  Needs no GPU."""
 import json
 import os
 
 import numpy as np
 import pytest
 
+import _esm2_cpu_common as common
 import _esm2_reference as ref
 from protein_gibbs_sampler_amd import _lib, weights
 
@@ -39,12 +41,6 @@ def test_config_and_tensor_names():
     assert {"embed_tokens.weight", "emb_layer_norm_after.weight", "lm_head.dense.weight", "layers.1.self_attn.q_proj.bias",
             "layers.0.fc2.weight"} <= names
     assert set(weights.synthetic_state_dict(small, seed=1)) == names
-
-
-def test_inv_freq_is_torchs():
-    torch = pytest.importorskip("torch")
-    want = (1.0 / (10000 ** (torch.arange(0, 64, 2).float() / 64))).numpy()
-    assert np.array_equal(ref.inv_freq(), want) and np.array_equal(weights.rotary_inv_freq(), want)
 
 
 def test_rotation_preserves_pair_norms_and_is_relative():
@@ -152,12 +148,10 @@ def test_models_esm2_reads_a_v2_file_without_a_gpu(tmp_path):
             models.ESM2()
 
 
+# ---- the shared bodies (tests/_esm2_cpu_common.py) at this size -------------------------------------------------------------------------
+def test_inv_freq_is_torchs():
+    common.check_inv_freq_is_torchs("esm2")
+
+
 def test_command_lines_accept_esm2():
-    from protein_gibbs_sampler_amd import likelihood_esm, models, pgen_esm, pgen_esm_from_fasta
-    for mod in (pgen_esm, pgen_esm_from_fasta, likelihood_esm):
-        assert mod.model_map["esm2"] is models.ESM2
-    assert pgen_esm.build_parser().parse_args(["--model", "esm2", "--synthetic-weights"]).model == "esm2"
-    assert pgen_esm.build_parser().parse_args([]).model == "esm1b"                 # defaults unchanged
-    assert likelihood_esm.build_parser().parse_args(["--model", "esm2"]).model == "esm2"
-    assert likelihood_esm.build_parser().parse_args([]).model == "esm1v"
-    assert pgen_esm_from_fasta.model_map.keys() >= {"esm1b", "esm2"}
+    common.check_command_lines_accept("esm2")

@@ -1,30 +1,28 @@
 """ESM-2 15B (esm2_t48_15B_UR50D: 40 heads of 128, d_model 5120; models.ESM2_15B) on the HIP engine: the head-128 attention kernels
 alone (pg_dbg_attention_kv: the whole-sequence ladder up to 288 keys, 128-key tiles beyond, <pad> keys, three precisions) element by
 element under the bounds of tests/_attention_reference.py, the head-128 rotation (pg_dbg_rope_hd) against the separately rounded
-numpy loop, the 20-chunk row kernels (LayerNorm, embedding, gather, LM tail) at d = 3072 .. 5120, the engine forward of one full-width
-layer and of a HuggingFace fixture, the sampler on a small deep model, and the refusals."""
-import json
-import os
-import random
+numpy loop, the 20-chunk row kernels (LayerNorm, embedding, gather, LM tail) at d = 3072 .. 5120, the GEMMs at the 15B shapes, the engine
+forward of one full-width layer and of a HuggingFace fixture, a call whose buffers pass 2 GiB, and the refusals of wider models and of
+heads of 128 elsewhere.  The sampler on a small deep model, the single chain and the shards are the esm2_15b rows of
+tests/test_gpu_esm2_sizes.py."""
 import warnings
 
 import numpy as np
 import pytest
 
-import _esm2_gpu_common as common
 import _attention_reference as ar
-import _esm2_reference_hd as ref
+import _esm2_gpu_common as common
+import _esm2_reference as ref
 import _row_reference as rr
 import test_gpu_attention_kernels as ak
 import test_gpu_gemm_kernels as gm
 import test_gpu_row_kernels as rk
-from _esm2_gpu_common import PREC, SEED25, replay_draws as _replay_draws, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
+from _esm2_gpu_common import PREC, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
 from _ln_host import PLAIN, SPLIT_DUP, _ln_inplace_host
 from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F32 = np.float32
 HD = 128
 
@@ -494,56 +492,13 @@ def test_esm2_15b_width_forward_against_the_reference(precision):
 
 
 def test_esm2_hd128_forward_against_huggingface_logits():
-    z = np.load(os.path.join(HERE, "golden", "esm2_hf_hd128.npz"))
-    cfg = weights.make_config(weights.ESM2_T48_CONFIG, **json.loads(str(z["cfg"])))
-    assert (cfg["d_model"], cfg["n_heads"], cfg["n_layers"]) == (512, 4, 6)
-    sd = weights.synthetic_state_dict(cfg, seed=int(z["seed"]), std=float(z["std"]), embed_std=float(z["embed_std"]),
-                                      ln_jitter=float(z["ln_jitter"]))
-    for precision, tol in (("fp32", 1e-3), ("fp16", 0.04)):                      # the head-32 fixture's bounds
-        got = _model(cfg, sd, precision).model.to("cuda:0").forward_logits(z["tokens"])
-        assert np.abs(got - z["logits"]).max() < tol, precision
+    common.check_huggingface_logits("hd128")
 
 
-# ---- a deeper small model: 4 layers x 256, two heads of 128 -----------------------------------------------------------------------------
-def _case(n_layers=4, d=256, seed=7, **over):
-    cfg = weights.make_config(weights.ESM2_T48_CONFIG, n_layers=n_layers, d_model=d, d_ffn=4 * d, **over)
-    assert cfg["n_heads"] * HD == d
-    sd = weights.synthetic_state_dict(cfg, seed=seed, std=0.045, embed_std=0.2, ln_jitter=0.1)
-    return cfg, sd, ref.Esm2Config.of(cfg)
-
-
-def test_esm2_hd128_sampler_positions_draws_and_likelihoods():
-    cfg, sd, rcfg = _case()
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "fp32"), device="cuda:0")
-    s.draw_seed, s.record = 11, True
-    random.seed(2)
-    out = s.generate(4, SEED25, batch_size=4, num_iters=3, num_positions=5, top_k=3, burnin=2, temperature=0.9, show_progress_bar=False)
-    assert len(out) == 4 and all(len(x) == 25 for x in out)
-    run = s.last_run[0]
-    random.seed(2)
-    table = np.asarray([[random.sample(range(1, 26), 5) for _ in range(4)] for _ in range(3)])
-    assert (run["table"] == table).all(), "position selection is not bit-exact with random.sample"
-    _replay_draws(s, run, 4, 5, 3, 3, 2, 0.9, 11)
-    tok = s.get_init_seq(SEED25, 25, 4).numpy()
-    for b in range(4):
-        tok[b, table[0, b]] = 32
-    want = ref.esm2_forward(sd, rcfg, tok)
-    for b in range(4):
-        assert np.abs(run["sampled_logits"][0][b] - want[b, table[0, b]]).max() < 1e-3
-    seq = "MRHGDISSSNDTVGVAVVNYKMPRLHTAAEVLDNAR"
-    ll, per = s.log_likelihood(seq)
-    tok = s.get_init_seq(seq, len(seq), 1).numpy()
-    masked = []
-    for i in range(1, len(seq) + 1):
-        t = tok.copy()
-        t[0, i] = 32
-        masked.append(ref.log_softmax(ref.esm2_forward(sd, rcfg, t)[0, i])[tok[0, i]])
-    assert np.abs(np.asarray(per) - np.asarray(masked)).max() < 2e-3 and abs(ll - np.mean(masked)) < 1e-3
-
-
+# ---- a deeper small model: two heads of 128 ----------------------------------------------------------------------------------------------
 def test_esm2_hd128_auto_precision_and_small_job_independence():
     """precision="auto" resolves and runs; a small job's logits do not depend on what the engine ran before (grow-only buffers)"""
-    cfg, sd, rcfg = _case(n_layers=2)
+    cfg, sd, rcfg = common.case("esm2_15b", n_layers=2)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         lm = models.ESM2_15B(state_dict=sd, config=cfg).model.to("cuda:0")        # precision="auto"
@@ -559,30 +514,6 @@ def test_esm2_hd128_auto_precision_and_small_job_independence():
         other = models.ESM2_15B(state_dict=sd, config=cfg).model.to("cuda:0")
     other.forward_logits(large)
     assert np.array_equal(other.forward_logits(small), first)
-
-
-def _single_chain_run():
-    cfg, sd, _ = _case(n_layers=3, seed=13)
-    return common.single_chain_run(_model(cfg, sd, "bf16"))
-
-
-def _single_chain_child():
-    common.single_chain_child(_single_chain_run)
-
-
-def _child(call, **env):
-    return common.child("test_gpu_esm2_15b", call, **env)
-
-
-def test_esm2_hd128_single_chain_replays_a_graph_and_equals_the_eager_loop():
-    common.check_single_chain(_single_chain_run, "test_gpu_esm2_15b")
-
-
-def test_esm2_hd128_shards_reproduce_the_whole_job():
-    """A 64-chain job of config 2's chain length (18 key blocks: one workgroup per CU), whole and as 2, 4 and 8 contiguous shards that
-    know the job's size: tokens and sampled-position logits bit for bit."""
-    cfg, sd, _ = _case(n_layers=3)
-    assert common.shard_job(_model(cfg, sd, "bf16"), (2, 4, 8))
 
 
 # ---- activation buffers past 2^31 bytes ------------------------------------------------------------------------------------------------
@@ -615,16 +546,10 @@ _BIG = {}
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("base, name", [("ESM1B_CONFIG", "ESM-1b"), ("MSA1B_CONFIG", "ESM-MSA-1b")])
+@pytest.mark.parametrize("base, name", [("ESM1B_CONFIG", "ESM-1b"), ("MSA1B_CONFIG", "ESM-MSA-1b"), ("ESM1_T6_CONFIG", "ESM-1")])
 def test_engine_refuses_heads_of_128_for_the_other_architectures(base, name):
-    cfg = weights.make_config(getattr(weights, base), n_layers=1, d_model=256, n_heads=2, d_ffn=512, max_positions=40)
-    sd = weights.synthetic_state_dict(cfg, seed=1)
-    cls = models.ESM_MSA1 if base == "MSA1B_CONFIG" else models.ESM1b
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        m = cls(state_dict=sd, config=cfg, precision="bf16")
-    with pytest.raises(Exception, match=r"%s with heads of 128.*64" % name):
-        m.model.to("cuda:0")
+    assert common.OTHER_ARCHS[name][0] == base
+    common.check_other_architectures_refuse_the_width("esm2_15b", name)
 
 
 @pytest.mark.parametrize("d_model, n_heads, words", [(6144, 48, "at most 40"), (5632, 44, "at most 40"), (2688, 21, "multiples of 512")])
@@ -633,12 +558,3 @@ def test_engine_refuses_models_wider_than_40_heads_of_128(d_model, n_heads, word
     sd = weights.synthetic_state_dict(cfg, seed=1)
     with pytest.raises(Exception, match=words):
         _model(cfg, sd, "bf16").model.to("cuda:0")
-
-
-def test_strict_valu_switch_refuses_heads_of_128_by_name():
-    out = _child("_refuse_valu_child", PGIBBS_ATTN_F32="valu")
-    assert any(l.startswith("CHILD_REFUSED ") and "PGIBBS_ATTN_F32" in l and "128" in l for l in out), out
-
-
-def _refuse_valu_child():
-    common.refuse_valu_child(HD)

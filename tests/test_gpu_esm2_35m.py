@@ -2,30 +2,24 @@
 head in a slot of 32, rows of 640 features whose last 160 are structural zeros (include/pgibbs.h pg_engine_create_embedded), on the
 GEMM, attention and rotary kernels of the 150M shape.  The one kernel family that had to learn something is the row kernels, which
 normalise over the live features and write zeros behind them: here each of them in its live-width form against the existing entry on
-rows of d = d_live, bit for bit; then the engine forward against the numpy reference at the NATURAL shape (heads of 24) and a
-HuggingFace fixture, under the bounds tests/test_gpu_esm2_150m.py holds for the same kernels at the same run shape; the sampler
-(positions, draws, likelihoods, hipGraph replay, shards); and the refusals that stay."""
+rows of d = d_live, bit for bit; the refusals that stay; and the engine forward against the numpy reference at the NATURAL shape
+(heads of 24) and a HuggingFace fixture, under the bounds the 150M row holds for the same kernels at the same run shape (the shared
+bodies of tests/_esm2_gpu_common.py).  The full size, precision="auto" and the sampler are the esm2_35m rows of
+tests/test_gpu_esm2_sizes.py."""
 import ctypes
-import json
-import os
-import random
-import warnings
 
 import numpy as np
 import pytest
 
 import _esm2_gpu_common as common
-import _esm2_reference_hd as ref
 import _row_reference as rr
 import test_gpu_row_kernels as rk
-from _esm2_gpu_common import SEED25, replay_draws as _replay_draws, tokens as _tokens
+from _esm2_sizes import PRECISIONS, SIZES
 from _ln_host import PLAIN, SPLIT_DUP, SPLIT_NODUP
-from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
+from protein_gibbs_sampler_amd import _lib, models, weights
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-HD = 24
 F32 = np.float32
 _p = rk._p
 
@@ -218,104 +212,6 @@ def test_live_embedding_and_its_fused_first_layernorm(M, d, dl):
     assert rc == _lib.PG_ERR_INVALID and b"emb_layer_norm_before" in _lib.lib().pg_last_error()
 
 
-# ---- forward ------------------------------------------------------------------------------------------------------------------------
-def _case(n_layers=2, d=480, seed=7, **over):
-    over.setdefault("d_ffn", 4 * d)
-    cfg = weights.make_config(weights.ESM2_T12_CONFIG, n_layers=n_layers, d_model=d, **over)
-    assert cfg["n_heads"] * HD == d
-    sd = weights.synthetic_state_dict(cfg, seed=seed, std=0.03, embed_std=0.15, ln_jitter=0.1)
-    return cfg, sd, ref.Esm2Config.of(cfg)
-
-
-def _model(cfg, sd, precision):
-    return common.model(models.ESM2_35M, cfg, sd, precision)
-
-
-# max |engine - reference| per unit of logit std: tests/test_gpu_esm2_150m.py's bounds -- the same kernels at the same run shape
-FWD_TOL = {"fp32": None, "bf16": 0.05, "fp16": 0.008}
-SHAPES = {"35m": dict(d=480), "4 heads": dict(d=96, d_ffn=256)}
-
-
-@pytest.mark.parametrize("shape", list(SHAPES))
-@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
-def test_esm2_35m_forward_against_the_reference(precision, shape):
-    """The reference runs the NATURAL model (heads of 24, rows of 480 / 96); the engine its embedding in slots of 32 (rows of 640 / 128)."""
-    cfg, sd, rcfg = _case(**SHAPES[shape])
-    lm = _model(cfg, sd, precision).model.to("cuda:0")
-    rng = np.random.default_rng(5)
-    worst, std = 0.0, 1.0
-    for T in (16, 27, 64, 160, 258, 288, 600):
-        B = 3 if T < 300 else 1
-        tok = _tokens(rng, B, T)
-        want = ref.esm2_forward(sd, rcfg, tok)
-        got = lm.forward_logits(tok)
-        assert got.shape == want.shape == (B, T, 33)
-        std = float(want.std())
-        err = np.abs(got - want).max()
-        worst = max(worst, err / (1.0 if precision == "fp32" else std))
-        print("\n[ESM-2 %s, heads of 24, %s, T=%d] max|engine - reference| = %.3e (logit std %.2f)" % (shape, precision, T, err, std))
-        assert err < (1e-3 if precision == "fp32" else FWD_TOL[precision] * std), (T, err, std)
-    # a right-padded batch: <pad> keys masked, positions are token indices
-    tok = np.full((3, 40), 1, dtype=np.int64)
-    lens = (40, 23, 9)
-    for b, n in enumerate(lens):
-        tok[b, :n] = _tokens(rng, 1, n, mask_every=5)[0]
-    got = lm.forward_logits(tok)
-    want = ref.esm2_forward(sd, rcfg, tok)
-    for b, n in enumerate(lens):
-        err = np.abs(got[b, :n] - want[b, :n]).max()
-        assert err < (1e-3 if precision == "fp32" else FWD_TOL[precision] * float(want.std())), (b, err)
-        alone = lm.forward_logits(tok[b:b + 1, :n])
-        assert np.abs(alone[0] - got[b, :n]).max() < (2e-4 if precision == "fp32" else 0.08)
-    print("\n[ESM-2 %s, heads of 24, %s] max|engine - reference| = %.3e %s (logit std %.2f)"
-          % (shape, precision, worst, "absolute" if precision == "fp32" else "per unit of logit std", std))
-
-
-def test_esm2_35m_forward_against_huggingface_logits():
-    z = np.load(os.path.join(HERE, "golden", "esm2_hf_hd24.npz"))
-    cfg = weights.make_config(weights.ESM2_T12_CONFIG, **json.loads(str(z["cfg"])))
-    assert (cfg["d_model"], cfg["n_heads"], cfg["n_layers"], cfg["d_ffn"]) == (480, 20, 12, 1920) and z["tokens"].shape == (2, 258)
-    sd = weights.synthetic_state_dict(cfg, seed=int(z["seed"]), std=float(z["std"]), embed_std=float(z["embed_std"]),
-                                      ln_jitter=float(z["ln_jitter"]))
-    for precision, tol in (("fp32", 1e-3), ("fp16", 0.04)):
-        got = _model(cfg, sd, precision).model.to("cuda:0").forward_logits(z["tokens"])
-        err = np.abs(got - z["logits"]).max()
-        print("\n[ESM-2 12 x 480 against HuggingFace, %s] max|engine - HF| = %.3e" % (precision, err))
-        assert err < tol, precision
-
-
-def test_esm2_35m_full_size_strict_logits():
-    """esm2_t12_35M's shape (12 layers x 480, 20 heads of 24), two chains of config 2's length, strict mode."""
-    cfg = dict(weights.ESM2_T12_CONFIG)
-    sd = weights.synthetic_state_dict(cfg, seed=0, std=0.035, embed_std=0.3, ln_jitter=0.1)
-    lm = _model(cfg, sd, "fp32").model.to("cuda:0")
-    tok = _tokens(np.random.default_rng(3), 2, 258, mask_every=9)
-    got = lm.forward_logits(tok)
-    want = ref.esm2_forward(sd, ref.Esm2Config.of(cfg), tok)
-    err = np.abs(got - want).max()
-    print("\n[ESM-2 12 x 480, fp32] max|engine - reference| = %.3e (logit std %.2f)" % (err, want.std()))
-    assert err < 1e-3
-
-
-def test_esm2_35m_auto_precision_and_synthetic_default():
-    """precision="auto" (fp16 behind the range guard) resolves and runs; synthetic=True builds the full 35M configuration."""
-    cfg, sd, rcfg = _case(d=96, d_ffn=256)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        m = models.ESM2_35M(state_dict=sd, config=cfg)                           # precision="auto"
-    lm = m.model.to("cuda:0")
-    tok = _tokens(np.random.default_rng(1), 2, 30)
-    want = ref.esm2_forward(sd, rcfg, tok)
-    assert np.abs(lm.forward_logits(tok) - want).max() < 0.05 * max(1.0, float(want.std()))
-    if not weights.find_cached_checkpoint("esm2_t12_35M_UR50D.pt"):
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            full = models.ESM2_35M(synthetic=True)
-        assert (full.cfg["d_model"], full.cfg["n_heads"], full.cfg["n_layers"], full.cfg["d_ffn"]) == (480, 20, 12, 1920)
-        out = full.model.to("cuda:0").forward_logits(tok)
-        assert out.shape == (2, 30, 33) and np.isfinite(out).all()
-
-
 # ---- refusals that stay ---------------------------------------------------------------------------------------------------------------
 def test_pg_engine_create_still_names_the_built_widths_and_the_embedded_entry_is_esm2s():
     cfg = dict(weights.ESM2_T12_CONFIG)
@@ -330,65 +226,19 @@ def test_pg_engine_create_still_names_the_built_widths_and_the_embedded_entry_is
     assert L.pg_engine_create_embedded(ctypes.byref(c), 32, None, 0, 0, _lib.PG_PREC_BF16, ctypes.byref(h)) == _lib.PG_ERR_INVALID
     assert b"PG_ARCH_ESM2 only" in L.pg_last_error()
     # a tensor of the wrong size is the loader's error, named
-    cfg2, sd, _ = _case(d=96, d_ffn=256)
+    cfg2, sd, _ = common.case("esm2_35m", d=96, d_ffn=256)
     sd = dict(sd)
     sd["layers.0.fc1.weight"] = sd["layers.0.fc1.weight"][:, :95].copy()
     with pytest.raises(Exception, match=r"layers\.0\.fc1\.weight.*expected 24576"):
-        _model(cfg2, sd, "bf16").model.to("cuda:0")
+        common.model(models.ESM2_35M, cfg2, sd, "bf16").model.to("cuda:0")
 
 
-# ---- the sampler --------------------------------------------------------------------------------------------------------------------
-def test_esm2_35m_sampler_positions_draws_and_likelihoods():
-    cfg, sd, rcfg = _case(n_layers=4)
-    s = esm_sampler.ESM_sampler(_model(cfg, sd, "fp32"), device="cuda:0")
-    s.draw_seed, s.record = 11, True
-    random.seed(2)
-    out = s.generate(4, SEED25, batch_size=4, num_iters=3, num_positions=5, top_k=3, burnin=2, temperature=0.9, show_progress_bar=False)
-    assert len(out) == 4 and all(len(x) == 25 for x in out)
-    run = s.last_run[0]
-    random.seed(2)
-    table = np.asarray([[random.sample(range(1, 26), 5) for _ in range(4)] for _ in range(3)])
-    assert (run["table"] == table).all(), "position selection is not bit-exact with random.sample"
-    _replay_draws(s, run, 4, 5, 3, 3, 2, 0.9, 11)
-    tok = s.get_init_seq(SEED25, 25, 4).numpy()
-    for b in range(4):
-        tok[b, table[0, b]] = 32
-    want = ref.esm2_forward(sd, rcfg, tok)
-    for b in range(4):
-        assert np.abs(run["sampled_logits"][0][b] - want[b, table[0, b]]).max() < 1e-3
-    seq = "MRHGDISSSNDTVGVAVVNYKMPRLHTAAEVLDNAR"
-    ll, per = s.log_likelihood(seq)
-    tok = s.get_init_seq(seq, len(seq), 1).numpy()
-    masked = []
-    for i in range(1, len(seq) + 1):
-        t = tok.copy()
-        t[0, i] = 32
-        masked.append(ref.log_softmax(ref.esm2_forward(sd, rcfg, t)[0, i])[tok[0, i]])
-    assert np.abs(np.asarray(per) - np.asarray(masked)).max() < 2e-3 and abs(ll - np.mean(masked)) < 1e-3
-    ll0, per0 = s.log_likelihood(seq, with_masking=False)
-    lp = ref.log_softmax(ref.esm2_forward(sd, rcfg, tok)[0])
-    plain = [lp[i, tok[0, i]] for i in range(1, len(seq) + 1)]
-    assert np.abs(np.asarray(per0) - np.asarray(plain)).max() < 2e-3 and abs(ll0 - np.mean(plain)) < 1e-3
+# ---- forward: the shared bodies (tests/_esm2_gpu_common.py) at this size ---------------------------------------------------------------
+@pytest.mark.parametrize("shape", list(SIZES["esm2_35m"]["forward"]["shapes"]))
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_esm2_35m_forward_against_the_reference(precision, shape):
+    common.check_forward("esm2_35m", shape, precision)
 
 
-def _single_chain_run():
-    cfg, sd, _ = _case(n_layers=3, seed=13)
-    return common.single_chain_run(_model(cfg, sd, "bf16"))
-
-
-def _single_chain_child():
-    common.single_chain_child(_single_chain_run)
-
-
-def _child(call, **env):
-    return common.child("test_gpu_esm2_35m", call, **env)
-
-
-def test_esm2_35m_single_chain_replays_a_graph_and_equals_the_eager_loop():
-    common.check_single_chain(_single_chain_run, "test_gpu_esm2_35m")
-
-
-def test_esm2_35m_shards_reproduce_the_whole_job():
-    """A 64-chain job of config 2's chain length and its 2, 4 and 8 shards: the same tokens and logits, bit for bit."""
-    cfg, sd, _ = _case(n_layers=3)
-    common.shard_job(_model(cfg, sd, "bf16"), (2, 4, 8))
+def test_esm2_35m_forward_against_huggingface_logits():
+    common.check_huggingface_logits("hd24")

@@ -1,8 +1,8 @@
 """ESM-2 3B (esm2_t36_3B_UR50D: d_model 2560, 40 heads -- models.ESM2_3B) on the HIP engine: the wide-row kernels alone (LayerNorm in
 its four forms at d = 2560 and 2304, the rotation at H = 40) against numpy, the 8-chunk LayerNorm at d = 1280 bit for bit against a
-host loop in the kernel's operation order (up to the hardware square root), the GEMM dispatcher at the 3B shapes, the forward of a 3-layer cut and once at full size
-against the fp32 reference (tests/_esm2_reference.py), and the sampler on the models.ESM2_3B holder."""
-import json
+host loop in the kernel's operation order (up to the hardware square root), the GEMM dispatcher at the 3B shapes, the forward of a
+3-layer cut against the fp32 reference (tests/_esm2_reference.py), fc2's split-K form and the models.ESM2_3B synthetic holder.  The full
+size, the sampler, the single chain and the shards are the esm2_3b rows of tests/test_gpu_esm2_sizes.py."""
 import random
 import warnings
 
@@ -11,7 +11,7 @@ import pytest
 
 import _esm2_gpu_common as common
 import _esm2_reference as ref
-from _esm2_gpu_common import SEED25, replay_draws as _replay_draws, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
+from _esm2_gpu_common import SEED25, round_bf16 as _round_bf16, round_f16 as _round_f16, tokens as _tokens
 from _ln_host import _fma32, _ln_inplace_host, _wave_sum  # noqa: F401  (the host restatement of csrc/ln_row.h)
 from protein_gibbs_sampler_amd import _lib, esm_sampler, models, weights
 
@@ -191,21 +191,9 @@ def test_gemm_at_3b_shapes(M, N, K, epis16, epis32):
 
 
 # ---- forward ------------------------------------------------------------------------------------------------------------------------
-def _case(n_layers=3, seed=7, **over):
-    cfg = weights.make_config(weights.ESM2_T36_CONFIG, n_layers=n_layers, **over)
-    sd = weights.synthetic_state_dict(cfg, seed=seed, std=0.017, embed_std=0.1, ln_jitter=0.1)      # logit std ~5 at d = 2560
-    return cfg, sd, ref.Esm2Config.of(cfg)
-
-
-_CASES = {}
-
-
-def _cached_case(**kw):
-    key = json.dumps(kw, sort_keys=True)
-    if key not in _CASES:
-        _CASES.clear()                                           # one 3-layer model of 236 M weights on the host at a time
-        _CASES[key] = _case(**kw)
-    return _CASES[key]
+def _cached_case():
+    """the 3-layer cut of the shared suite (236 M weights on the host), drawn once while the tests that use it follow each other"""
+    return common.case("esm2_3b")
 
 
 def _model(cfg, sd, precision):
@@ -311,59 +299,7 @@ def test_esm2_3b_one_chain_of_27_tokens():
         assert err < (1e-3 if precision == "fp32" else FWD_TOL[precision] * want.std()), (precision, err)
 
 
-# synthetic weights that put the logit std of the 36 x 2560 model near 10 (measured 10.20; the 650M test's 0.025 / 0.3 would give ~15:
-# the tied decoder's logits scale with embed_std * sqrt(d_model))
-FULL_STD, FULL_EMBED_STD = 0.018, 0.21
-
-
-def test_esm2_3b_full_size_strict_logits():
-    """esm2_t36_3B's shape (36 layers x 2560, 40 heads), two chains of 66 tokens, strict mode against the fp32 reference."""
-    cfg = dict(weights.ESM2_T36_CONFIG)
-    sd = weights.synthetic_state_dict(cfg, seed=0, std=FULL_STD, embed_std=FULL_EMBED_STD, ln_jitter=0.1)
-    lm = _model(cfg, sd, "fp32").model.to("cuda:0")
-    tok = _tokens(np.random.default_rng(3), 2, 66, mask_every=9)
-    got = lm.forward_logits(tok)
-    want = ref.esm2_forward(sd, ref.Esm2Config.of(cfg), tok)
-    err = np.abs(got - want).max()
-    print("\n[ESM-2 36 x 2560, fp32] std %g embed_std %g: max|engine - reference| = %.3e (logit std %.2f)"
-          % (FULL_STD, FULL_EMBED_STD, err, want.std()))
-    assert 7.0 < want.std() < 14.0
-    assert err < 1e-3                                            # first measured run: 6.87e-4
-
-
 # ---- the sampler --------------------------------------------------------------------------------------------------------------------
-
-
-def test_esm2_3b_sampler_positions_draws_and_likelihoods():
-    cfg, sd, rcfg = _cached_case()
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        s = esm_sampler.ESM_sampler(models.ESM2_3B(config=cfg, state_dict=sd, precision="fp32"), device="cuda:0")
-    s.draw_seed, s.record = 11, True
-    random.seed(2)
-    out = s.generate(4, SEED25, batch_size=4, num_iters=3, num_positions=5, top_k=3, burnin=2, temperature=0.9, show_progress_bar=False)
-    assert len(out) == 4 and all(len(x) == 25 for x in out)
-    run = s.last_run[0]
-    random.seed(2)
-    table = np.asarray([[random.sample(range(1, 26), 5) for _ in range(4)] for _ in range(3)])
-    assert (run["table"] == table).all(), "position selection is not bit-exact with random.sample"
-    _replay_draws(s, run, 4, 5, 3, 3, 2, 0.9, 11)
-    tok = s.get_init_seq(SEED25, 25, 4).numpy()
-    for b in range(4):
-        tok[b, table[0, b]] = 32
-    want = ref.esm2_forward(sd, rcfg, tok)
-    for b in range(4):
-        assert np.abs(run["sampled_logits"][0][b] - want[b, table[0, b]]).max() < 1e-3
-    seq = "MRHGDISSSNDTVGVAVVNY"
-    ll, per = s.log_likelihood(seq)
-    tok = s.get_init_seq(seq, len(seq), 1).numpy()
-    batch = np.repeat(tok, len(seq), axis=0)
-    batch[np.arange(len(seq)), np.arange(1, len(seq) + 1)] = 32
-    lg = ref.esm2_forward(sd, rcfg, batch)
-    masked = [ref.log_softmax(lg[i, i + 1])[tok[0, i + 1]] for i in range(len(seq))]
-    assert np.abs(np.asarray(per) - np.asarray(masked)).max() < 2e-3 and abs(ll - np.mean(masked)) < 1e-3
-
-
 def test_models_esm2_3b_synthetic_holder():
     cfg = weights.make_config(weights.ESM2_T36_CONFIG, n_layers=3)
     with warnings.catch_warnings():
@@ -373,23 +309,3 @@ def test_models_esm2_3b_synthetic_holder():
     random.seed(1)
     out = s.generate(2, SEED25, batch_size=2, num_iters=2, num_positions=3, top_k=0, temperature=1.0, burnin=float("inf"), show_progress_bar=False)
     assert len(out) == 2 and all(len(x) == 25 and set(x) <= set("ACDEFGHIKLMNPQRSTVWY") for x in out)
-
-
-def _single_chain_run():
-    cfg, sd, _ = _case(seed=13)
-    return common.single_chain_run(_model(cfg, sd, "bf16"))
-
-
-def _single_chain_child():
-    common.single_chain_child(_single_chain_run)
-
-
-def test_esm2_3b_single_chain_replays_a_graph_and_equals_the_eager_loop():
-    common.check_single_chain(_single_chain_run, "test_gpu_esm2_3b", timeout=600)
-
-
-def test_esm2_3b_shards_reproduce_the_whole_job():
-    """A 32-chain job of config 2's chain length (8256 token rows) run whole and as 2 and 4 contiguous shards that know the job's
-    size (pg_engine_set_job_items): tokens and the logits of every draw, bit for bit."""
-    cfg, sd, _ = _cached_case()
-    common.shard_job(_model(cfg, sd, "bf16"), (2, 4), B=32)

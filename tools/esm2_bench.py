@@ -69,11 +69,13 @@ def main(argv=None):
                          "15b: ESM-2 15B alone (with --layers L < 48: L and L / 2 layers, 48 extrapolated); "
                          "8m: ESM-2 8M alone, then head 16 against head 32; 35m: ESM-2 35M (embedded in slots of 32) next to ESM-2 150M")
     args = ap.parse_args(argv)
-    if args.layers is None:
-        args.layers = {"3b": 36, "150m": 30, "15b": 48, "8m": 6, "35m": 12}.get(args.size, 33)
 
     import torch
     from protein_gibbs_sampler_amd import _lib, esm_sampler, models, pyrandom, sharding, weights
+    rotary = "esm2" if args.size == "650m" else "esm2_" + args.size      # the size's row of weights.ESM2_SIZES: wrapper, configuration, layers
+    model_cfg = weights.ESM2_SIZES[rotary]["config"]
+    if args.layers is None:
+        args.layers = model_cfg["n_layers"]
     if not torch.cuda.is_available():
         raise SystemExit("esm2_bench: no GPU visible -- nothing is measured without one")
     L_ = _lib.lib()
@@ -85,6 +87,9 @@ def main(argv=None):
             m = cls(state_dict=weights.synthetic_state_dict(cfg, seed=0), config=cfg, precision=precision)
         return esm_sampler.ESM_sampler(m, device="cuda:0")
 
+    def build_size(cli, **kw):
+        return build(getattr(models, weights.ESM2_SIZES[cli]["wrapper"]), weights.ESM2_SIZES[cli]["config"], **kw)
+
     def in_use():
         torch.cuda.synchronize()
         free, total = torch.cuda.mem_get_info()          # hipMemGetInfo
@@ -92,20 +97,9 @@ def main(argv=None):
 
     device_bytes = {}
 
-    if args.size == "3b":
-        samplers = {"esm2_3b": build(models.ESM2_3B, weights.ESM2_T36_CONFIG)}
-        rotary, model_cfg = "esm2_3b", weights.ESM2_T36_CONFIG
-    elif args.size == "150m":
-        samplers = {"esm2_150m": build(models.ESM2_150M, weights.ESM2_T30_CONFIG)}
-        rotary, model_cfg = "esm2_150m", weights.ESM2_T30_CONFIG
-    elif args.size == "8m":
-        samplers = {"esm2_8m": build(models.ESM2_8M, weights.ESM2_T6_CONFIG)}
-        rotary, model_cfg = "esm2_8m", weights.ESM2_T6_CONFIG
-    elif args.size == "35m":
-        samplers = {"esm2_35m": build(models.ESM2_35M, weights.ESM2_T12_CONFIG),
-                    "esm2_150m": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=30 if args.layers == 12 else args.layers)}
-        slot = weights.EMBEDDED_WIDTHS[24]["slot"]
-        rotary, model_cfg = "esm2_35m", dict(weights.ESM2_T12_CONFIG, d_model=weights.ESM2_T12_CONFIG["n_heads"] * slot)      # the run shape
+    if args.size == "35m":
+        samplers = {rotary: build_size(rotary), "esm2_150m": build_size("esm2_150m", n_layers=30 if args.layers == 12 else args.layers)}
+        model_cfg = dict(model_cfg, d_model=model_cfg["n_heads"] * weights.embedded_slot(model_cfg))      # the run shape
     elif args.size == "15b":
         import gc
         half = args.layers // 2 if args.layers < 48 else 0
@@ -114,9 +108,9 @@ def main(argv=None):
         # the strict mode's weights first, at L / 4 and L / 2 layers (or 1 and 2 of the full model), then released
         a, b = (args.layers // 4, args.layers // 2) if half else (1, 2)
         base0 = in_use()
-        m_a = build(models.ESM2_15B, weights.ESM2_T48_CONFIG, precision="fp32", n_layers=a)
+        m_a = build_size(rotary, precision="fp32", n_layers=a)
         used_a = in_use()
-        m_b = build(models.ESM2_15B, weights.ESM2_T48_CONFIG, precision="fp32", n_layers=b)
+        m_b = build_size(rotary, precision="fp32", n_layers=b)
         used_b = in_use()
         device_bytes["fp32"] = {"layers": [a, b], "weights_bytes": [used_a - base0, used_b - used_a]}
         pl = (device_bytes["fp32"]["weights_bytes"][1] - device_bytes["fp32"]["weights_bytes"][0]) / float(b - a)
@@ -126,9 +120,9 @@ def main(argv=None):
         base1 = in_use()
         samplers = {}
         if half:
-            samplers["esm2_15b_half"] = build(models.ESM2_15B, weights.ESM2_T48_CONFIG, n_layers=half)
+            samplers["esm2_15b_half"] = build_size(rotary, n_layers=half)
         used_h = in_use()
-        samplers["esm2_15b"] = build(models.ESM2_15B, weights.ESM2_T48_CONFIG)
+        samplers["esm2_15b"] = build_size(rotary)
         used_f = in_use()
         device_bytes["bf16"] = {"layers": [half, args.layers] if half else [args.layers],
                                 "weights_bytes": [used_h - base1, used_f - used_h] if half else [used_f - base1],
@@ -136,10 +130,10 @@ def main(argv=None):
         if half:
             pl = ((used_f - used_h) - (used_h - base1)) / float(args.layers - half)
             device_bytes["bf16"]["weights_bytes_48_layers_extrapolated"] = int((used_f - used_h) + (48 - args.layers) * pl)
-        rotary, model_cfg = "esm2_15b", weights.ESM2_T48_CONFIG
+    elif args.size == "650m":
+        samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), rotary: build_size(rotary)}
     else:
-        samplers = {"esm1b": build(models.ESM1b, weights.ESM1B_CONFIG), "esm2": build(models.ESM2, weights.ESM2_T33_CONFIG)}
-        rotary, model_cfg = "esm2", weights.ESM2_T33_CONFIG
+        samplers = {rotary: build_size(rotary)}
     d_model, d_ffn = model_cfg["d_model"], model_cfg["d_ffn"]
 
     def job(s, B, L, P, iters):
@@ -233,12 +227,10 @@ def main(argv=None):
         name, B, L, P = SHAPES[0]
         rows = B * (L + 2)
         if args.size == "8m":
-            trio = {"h20x16_d320": build(models.ESM2_8M, weights.ESM2_T6_CONFIG, n_layers=3),
-                    "h20x32_d640": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=3)}
+            trio = {"h20x16_d320": build_size("esm2_8m", n_layers=3), "h20x32_d640": build_size("esm2_150m", n_layers=3)}
         else:
-            trio = {"h20x32_d640": build(models.ESM2_150M, weights.ESM2_T30_CONFIG, n_layers=3),
-                    "h20x64_d1280": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3),
-                    "h10x64_d640": build(models.ESM2, weights.ESM2_T33_CONFIG, n_layers=3, d_model=640, d_ffn=2560)}
+            trio = {"h20x32_d640": build_size("esm2_150m", n_layers=3), "h20x64_d1280": build_size("esm2", n_layers=3),
+                    "h10x64_d640": build_size("esm2", n_layers=3, d_model=640, d_ffn=2560)}
         jobs = {k: job(s, B, L, P, args.prof_iters) for k, s in trio.items()}
         for k in trio:
             jobs[k]()                                   # warm-up of every shape, unprofiled
