@@ -191,6 +191,27 @@ typedef struct {
   int32_t iter_base;   /* Philox counter word 1 = iter_base + iteration */
 } pg_sample_params;
 
+/* ---- what the engine entries refuse, and in which order -----------------------------------------
+ * The 13 entries below that take tokens (pg_esm_* / pg_msa_*: forward_logits, gibbs_run[_device], gibbs_single[_batch]_run,
+ * forward_logprobs, forward_logprob_table) answer PG_ERR_INVALID on the host, before anything is allocated, copied or launched and
+ * with the caller's buffers untouched, for the first of these that applies:
+ *   1. a null pointer among the required arguments                       "<entry>: null argument"
+ *   2. sample parameters: n_valid outside 1..32, a valid_idx outside the vocabulary
+ *   3. the call itself, one check for every entry: an engine of the other architecture ("engine was not built for ..."); B < 0,
+ *      R < 1, C (T) < 1 ("bad shape"); R > max_msa_rows ("MSA has more rows than msa_position_embedding"); C or T > max_positions
+ *      ("alignment / sequence longer than the learned position table") -- the embedding reads one row of those tables per token
+ *   4. counts: P, n_iters, n_steps, P_max, n_sel < 0 ("bad shape"); mask_row / target_row outside 0..R-1; the table entries' V,
+ *      n_cols, norm and columns
+ *   5. nothing to do (B == 0, no iterations or steps, no scored entries): PG_OK, nothing further is looked at
+ *   6. the draw guide against the call (pg_engine_set_draw_guide's run-time refusals)
+ *   7. index tables on the host: a target position >= the row's width, a scoring target outside the vocabulary, a row_of entry
+ *      outside the token rows
+ *   8. tokens on the host: the first id outside 0..vocab-1, by entry, flat index and value
+ *      ("<entry>: token 33 at flat index 11 is outside the vocabulary of 33")
+ * No test of the suite pins another order for any pair.  The *_device entries take device pointers and cannot look into their index
+ * table or tokens (7, 8): the caller guarantees 0 <= token < vocab; positions outside the row are skipped by the kernels.
+ * pg_msa_gibbs_single_run names itself in 1 and is pg_msa_gibbs_single_batch_run with B = 1 from there on. */
+
 /* ---- ESM-1b -------------------------------------------------------------------------------
  * pg_esm_forward_logits: model.model(tokens)["logits"] (esm_sampler.py:223): tokens[B,T] -> logits[B,T,V].
  * pg_esm_gibbs_run: the whole `for ii in range(num_iters)` loop of ESM_sampler.generate
@@ -205,7 +226,8 @@ int pg_esm_forward_logits(pg_engine*, const int32_t* tokens, int B, int T, float
 int pg_esm_gibbs_run(pg_engine*, int32_t* tokens_inout, int B, int T, const int32_t* target_idx, int n_iters, int P,
                      const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens);
 /* same, every pointer device-resident (tokens stay in HBM; used by bench.py and multi-GPU drivers).  Asynchronous: returns after
- * enqueueing on the engine's stream; every buffer (incl. d_target_idx) must stay valid until pg_engine_synchronize.  Single short
+ * enqueueing on the engine's stream; every buffer (incl. d_target_idx) must stay valid until pg_engine_synchronize.  The tokens are
+ * device-resident, so their range is NOT checked: the caller guarantees 0 <= token < vocab (pg_msa_gibbs_run_device too).  Single short
  * chains (<= 32 token rows) may run on a persistent launch whose device-wide barriers can time out when the GPU is shared; such
  * calls are logged with a snapshot of their token rows, and the next pg_esm_gibbs_run_device / pg_engine_synchronize that sees
  * the timeout restores the rows and runs the logged calls again on the per-layer launches (same results, one warning).
@@ -249,6 +271,8 @@ int pg_msa_gibbs_single_batch_run(pg_engine*, int32_t* tokens_inout, int B, int 
  * src/pgen/esm_msa_sampler.py:398-410,421-431).  Sample s scores token row row_of[s] (ESM: the chain index;
  * MSA: b*R + target_index) at positions idx[s][P] (entries < 0 are skipped and yield 0) against targets[s][P];
  * out[s][P] = log_softmax(logits[row, pos, :])[target].  The LM head runs only at the scored rows.
+ * pg_*_forward_logprobs writes nothing to `out` when it returns an error (PG_ERR_RANGE included: the results wait on the device
+ * until the range check has passed).
  * pg_logprob_gather_device: the same gather on a caller's device-resident full logits[n_rows][width][V]. */
 int pg_esm_forward_logprobs(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
                             const int32_t* targets, int n_sel, int P, float* out);

@@ -58,29 +58,44 @@ int check_finite(Engine& e, const float* v, size_t n) {
   *e.range_err = 1;
   return e.range_check();
 }
-bool has_token(const int32_t* tokens, size_t n, int32_t id) {
-  for (size_t i = 0; i < n; ++i)
-    if (tokens[i] == id) return true;
-  return false;
+// The one pass over the tokens of a host-buffer call.  The first id outside the vocabulary is refused by entry, flat index and value:
+// embed_ln_kernel reads embed + tok * d with whatever it is handed (device-pointer entries cannot look).  *has_pad: <pad> occurs
+int scan_tokens(const Engine& e, const char* who, const int32_t* tokens, size_t n, bool* has_pad) {
+  bool pad = false;
+  for (size_t i = 0; i < n; ++i) {
+    const int32_t t = tokens[i];
+    if (t < 0 || t >= e.cfg.vocab)
+      return fail(PG_ERR_INVALID, std::string(who) + ": token " + std::to_string(t) + " at flat index " + std::to_string(i) +
+                                      " is outside the vocabulary of " + std::to_string(e.cfg.vocab));
+    pad |= t == e.cfg.pad_idx;
+  }
+  *has_pad = pad;
+  return PG_OK;
 }
 // A ragged batch (<pad> in some row; for the MSA model a ragged list of MSAs padded to one tensor, esm_msa_sampler.py:341): while
 // this lives the trunks mask keys at <pad> in attention, as fair-esm's key_padding_mask does
 struct PadFlag {
   Engine& e;
-  PadFlag(Engine& e_, const int32_t* tokens, size_t n) : e(e_) { e.esm_pad_in_batch = has_token(tokens, n, e.cfg.pad_idx); }
+  PadFlag(Engine& e_, bool pad) : e(e_) { e.esm_pad_in_batch = pad; }
   ~PadFlag() { e.esm_pad_in_batch = false; }
 };
 
 // tokens[B][R][C] in (R = 1 for the ESM family), logits of every position out
-int forward_logits(Engine& e, const int32_t* tokens, int B, int R, int C, float* logits_out) {
-  DeviceGuard g(e.device);
+int forward_logits(pg_engine* h, const char* who, bool msa, const int32_t* tokens, int B, int R, int C, float* logits_out) {
+  if (!h || !tokens || !logits_out) return fail(PG_ERR_INVALID, std::string(who) + ": null argument");
+  Engine& e = h->e;
   const int64_t M = (int64_t)B * R * C;
   int rc;
+  bool has_pad;
+  if ((rc = e.check_call(msa, B, R, C))) return rc;
+  if (B == 0) return PG_OK;
+  if ((rc = scan_tokens(e, who, tokens, (size_t)M, &has_pad))) return rc;
+  DeviceGuard g(e.device);
   if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
   if ((rc = e.logits.ensure((size_t)M * e.cfg.vocab * 4, e.stream))) return rc;
   PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
   {
-    PadFlag pad(e, tokens, (size_t)M);
+    PadFlag pad(e, has_pad);
     rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
   }
   if (rc) return rc;
@@ -118,6 +133,93 @@ int stage_gibbs(Engine& e, int32_t* tokens_inout, size_t n_tokens, const int32_t
   PG_HIP(hipStreamSynchronize(e.stream));
   return PG_OK;
 }
+
+// What every Gibbs entry refuses before it touches a device, in the order pgibbs.h states: null pointers (other_null: a pointer only this
+// entry has), the n_params sample parameters, the call check with its counts and row indices, and -- unless there is nothing to do --
+// the draw guide against the WHOLE call and, for an entry on host buffers, its index table idx[n_iters][idx_rows][P] and its tokens
+int gibbs_prologue(pg_engine* h, const char* who, bool msa, bool host, const int32_t* tokens, int B, int R, int C, const int32_t* idx,
+                   int64_t idx_rows, int n_iters, int P, const pg_sample_params* params, int n_params = 1, bool* has_pad = nullptr,
+                   bool other_null = false, int mask_row = 0, int target_row = 0) {
+  if (!h || !tokens || other_null || (!idx && P > 0 && n_iters > 0)) return fail(PG_ERR_INVALID, std::string(who) + ": null argument");
+  Engine& e = h->e;
+  int rc;
+  for (int b = 0; b < n_params; ++b)
+    if ((rc = check_params(params ? params + b : nullptr, e.cfg.vocab))) return rc;
+  if ((rc = e.check_call(msa, B, R, C, n_iters, P, mask_row, target_row))) return rc;
+  if (B == 0 || n_iters == 0) return PG_OK;
+  for (int b = 0; b < n_params; ++b)
+    if ((rc = check_draw_guide(e.draw_guide(), who, C, params[b].n_valid, (int64_t)B * R, n_iters))) return rc;
+  if (!host) return PG_OK;
+  const size_t n_draws = (size_t)idx_rows * P * n_iters;
+  if (n_draws && (rc = check_idx_table(idx, n_draws, C, who))) return rc;
+  bool pad;
+  if ((rc = scan_tokens(e, who, tokens, (size_t)B * R * C, &pad))) return rc;
+  if (has_pad) *has_pad = pad;
+  return PG_OK;
+}
+
+// The scoring entries below their own argument checks.  Sample s scores token row row_of[s] of tokens[B][R][C] at idx[s][P]: those
+// three and aux[n_aux], the int32 array of the entry's own kernel (targets, or columns), go to the device; the trunk and the LM head at
+// the scored rows run; launch(d_aux, d_res) queues the kernel that fills d_res[n_res].  The results wait on the device until the range
+// check has passed -- a PG_ERR_RANGE call leaves the caller's buffers alone --, then n_out floats go to out and the n_out2 behind them
+// to out2 (may be null).  what: the entry's name in the index messages
+template <typename Launch>
+int score_rows(Engine& e, const char* who, const std::string& what, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+               const int32_t* idx, int n_sel, int P, const int32_t* aux, size_t n_aux, size_t n_res, Launch&& launch, float* out,
+               size_t n_out, float* out2, size_t n_out2) {
+  const int64_t M = (int64_t)B * R * C;
+  const int64_t n = (int64_t)n_sel * P;
+  int rc;
+  bool has_pad;
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] >= C) return fail(PG_ERR_INVALID, what + ": index out of range");
+  for (int i = 0; i < n_sel; ++i)
+    if (row_of[i] < 0 || row_of[i] >= B * R) return fail(PG_ERR_INVALID, what + ": row out of range");
+  if ((rc = scan_tokens(e, who, tokens, (size_t)M, &has_pad))) return rc;
+  DeviceGuard g(e.device);
+  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
+  if ((rc = e.d_idx.ensure((size_t)n * 4, e.stream)) || (rc = e.d_samp_tok.ensure(n_aux * 4, e.stream))) return rc;
+  if ((rc = e.d_rowmap.ensure((size_t)n_sel * 4, e.stream))) return rc;
+  if ((rc = e.logits.ensure((size_t)n * e.cfg.vocab * 4, e.stream)) || (rc = e.d_samp_logits.ensure(n_res * 4, e.stream))) return rc;
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
+  PG_HIP(hipMemcpyAsync(e.d_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
+  PG_HIP(hipMemcpyAsync(e.d_samp_tok.p, aux, n_aux * 4, hipMemcpyHostToDevice, e.stream));
+  PG_HIP(hipMemcpyAsync(e.d_rowmap.p, row_of, (size_t)n_sel * 4, hipMemcpyHostToDevice, e.stream));
+  {
+    PadFlag pad(e, has_pad);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
+  }
+  if (rc) return rc;
+  if ((rc = e.head(e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(), P, C, n, e.logits.as<float>()))) return rc;
+  float* d_res = e.d_samp_logits.as<float>();
+  if ((rc = launch(e.d_samp_tok.as<int32_t>(), d_res))) return rc;
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.finish_check())) return rc;
+  PG_HIP(hipMemcpyAsync(out, d_res, n_out * 4, hipMemcpyDeviceToHost, e.stream));
+  if (out2) PG_HIP(hipMemcpyAsync(out2, d_res + n_out, n_out2 * 4, hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  return PG_OK;
+}
+
+// pg_engine_create / pg_engine_create_embedded around their init(Engine&); the caller's current device is put back
+template <typename Init>
+int create_engine(const char* who, const pg_model_config* cfg, const pg_tensor* tensors, int n_tensors, pg_engine** out, Init&& init) {
+  if (!cfg || !out || (n_tensors > 0 && !tensors)) return fail(PG_ERR_INVALID, std::string(who) + ": null argument");
+  *out = nullptr;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  pg_engine* h = new pg_engine;
+  int rc = init(h->e);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  if (rc != PG_OK) {
+    std::string keep = pg_last_error();
+    delete h;
+    set_error(keep);
+    return rc;
+  }
+  *out = h;
+  return PG_OK;
+}
 // the profiling classes by name (pg_prof_get, pg_prof_get_kernels): the PC_* index, -1 = no such class
 int prof_class(const char* name) {
   static const char* const names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed",    "head", "sample",
@@ -141,40 +243,14 @@ int pg_device_count(void) {
 
 int pg_engine_create(const pg_model_config* cfg, const pg_tensor* tensors, int n_tensors, int device_ordinal,
                      int precision, pg_engine** out) {
-  if (!cfg || !out || (n_tensors > 0 && !tensors)) return fail(PG_ERR_INVALID, "pg_engine_create: null argument");
-  *out = nullptr;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  pg_engine* h = new pg_engine;
-  int rc = h->e.init(cfg, tensors, n_tensors, device_ordinal, precision);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  if (rc != PG_OK) {
-    std::string keep = pg_last_error();
-    delete h;
-    set_error(keep);
-    return rc;
-  }
-  *out = h;
-  return PG_OK;
+  return create_engine("pg_engine_create", cfg, tensors, n_tensors, out,
+                       [&](Engine& e) { return e.init(cfg, tensors, n_tensors, device_ordinal, precision); });
 }
 
 int pg_engine_create_embedded(const pg_model_config* cfg, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal,
                               int precision, pg_engine** out) {
-  if (!cfg || !out || (n_tensors > 0 && !tensors)) return fail(PG_ERR_INVALID, "pg_engine_create_embedded: null argument");
-  *out = nullptr;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  pg_engine* h = new pg_engine;
-  int rc = h->e.init_embedded(cfg, head_slot, tensors, n_tensors, device_ordinal, precision);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  if (rc != PG_OK) {
-    std::string keep = pg_last_error();
-    delete h;
-    set_error(keep);
-    return rc;
-  }
-  *out = h;
-  return PG_OK;
+  return create_engine("pg_engine_create_embedded", cfg, tensors, n_tensors, out,
+                       [&](Engine& e) { return e.init_embedded(cfg, head_slot, tensors, n_tensors, device_ordinal, precision); });
 }
 
 void pg_engine_destroy(pg_engine* h) { delete h; }
@@ -223,16 +299,6 @@ int pg_engine_get_stat(pg_engine* h, const char* name, int64_t* value) {
   return PG_OK;
 }
 
-// ---- ESM-1b ---------------------------------------------------------------------------------
-static int esm_forward_logits_once(pg_engine* h, const int32_t* tokens, int B, int T, float* logits_out) {
-  if (!h || !tokens || !logits_out) return fail(PG_ERR_INVALID, "pg_esm_forward_logits: null argument");
-  Engine& e = h->e;
-  if (!e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
-  if (B < 0 || T < 1) return fail(PG_ERR_INVALID, "bad shape");
-  if (T > e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
-  if (B == 0) return PG_OK;
-  return forward_logits(e, tokens, B, 1, T, logits_out);
-}
 // The persistent single-chain trunk is an optimistic fast path: when one of its barriers timed out (Engine::chain_check) the
 // call's inputs are still intact in the caller's buffers, so it runs once more, now on the per-layer launches.
 #define PG_RETRY_WITHOUT_CHAIN_TRUNK(h, call)                          \
@@ -244,18 +310,17 @@ static int esm_forward_logits_once(pg_engine* h, const int32_t* tokens, int B, i
     }                                                                 \
     return rc_;                                                       \
   } while (0)
+
+// ---- ESM-1b ---------------------------------------------------------------------------------
 int pg_esm_forward_logits(pg_engine* h, const int32_t* tokens, int B, int T, float* logits_out) {
-  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, esm_forward_logits_once(h, tokens, B, T, logits_out));
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logits(h, "pg_esm_forward_logits", false, tokens, B, 1, T, logits_out));
 }
 
 int pg_esm_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int T, const int32_t* d_target_idx, int n_iters,
                             int P, const pg_sample_params* params, float* d_sampled_logits, int32_t* d_sampled_tokens) {
-  if (!h || !d_tokens_inout || (!d_target_idx && P > 0 && n_iters > 0))
-    return fail(PG_ERR_INVALID, "pg_esm_gibbs_run_device: null argument");
-  int rc = check_params(params, h->e.cfg.vocab);
+  int rc = gibbs_prologue(h, "pg_esm_gibbs_run_device", false, false, d_tokens_inout, B, 1, T, d_target_idx, B, n_iters, P, params);
   if (rc) return rc;
   Engine& e = h->e;
-  if ((rc = check_draw_guide(e.draw_guide(), "pg_esm_gibbs_run_device", T, params->n_valid, B, n_iters))) return rc;
   DeviceGuard g(e.device);
   // An earlier asynchronous call has reported a barrier timeout of the persistent trunk: repair (restore the logged token rows,
   // run the logged calls again on the per-layer launches) BEFORE this call is queued on top of those tokens -- whatever this
@@ -277,18 +342,13 @@ int pg_esm_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int T,
 
 static int esm_gibbs_run_once(pg_engine* h, int32_t* tokens_inout, int B, int T, const int32_t* target_idx, int n_iters, int P,
                               const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
-  if (!h || !tokens_inout || (!target_idx && P > 0 && n_iters > 0)) return fail(PG_ERR_INVALID, "pg_esm_gibbs_run: null argument");
-  int rc = check_params(params, h->e.cfg.vocab);
-  if (rc) return rc;
-  if (B < 0 || T < 1 || P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "bad shape");
-  if (B == 0) return PG_OK;
+  bool has_pad = false;
+  int rc = gibbs_prologue(h, "pg_esm_gibbs_run", false, true, tokens_inout, B, 1, T, target_idx, B, n_iters, P, params, 1, &has_pad);
+  if (rc || B == 0 || n_iters == 0) return rc;
   Engine& e = h->e;
-  if ((rc = check_draw_guide(e.draw_guide(), "pg_esm_gibbs_run", T, params->n_valid, B, n_iters))) return rc;
   DeviceGuard g(e.device);
-  const size_t n_draws = (size_t)B * P * n_iters;
-  if (n_draws && (rc = check_idx_table(target_idx, n_draws, T, "pg_esm_gibbs_run"))) return rc;
-  PadFlag pad(e, tokens_inout, (size_t)B * T);
-  return stage_gibbs(e, tokens_inout, (size_t)B * T, target_idx, n_draws, sampled_logits, sampled_tokens,
+  PadFlag pad(e, has_pad);
+  return stage_gibbs(e, tokens_inout, (size_t)B * T, target_idx, (size_t)B * P * n_iters, sampled_logits, sampled_tokens,
                      [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
                        return e.esm_gibbs_device(d_tok, B, T, d_idx, n_iters, P, params, d_lg, d_st);
                      });
@@ -300,98 +360,67 @@ int pg_esm_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int T, const in
 
 // ---- ESM-MSA-1b -----------------------------------------------------------------------------
 int pg_msa_forward_logits(pg_engine* h, const int32_t* tokens, int B, int R, int C, float* logits_out) {
-  if (!h || !tokens || !logits_out) return fail(PG_ERR_INVALID, "pg_msa_forward_logits: null argument");
-  Engine& e = h->e;
-  if (e.cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
-  if (B < 0 || R < 1 || C < 1) return fail(PG_ERR_INVALID, "bad shape");
-  if (B == 0) return PG_OK;
-  return forward_logits(e, tokens, B, R, C, logits_out);
+  return forward_logits(h, "pg_msa_forward_logits", true, tokens, B, R, C, logits_out);
 }
 
 int pg_msa_gibbs_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, const int32_t* target_idx, int n_iters,
                      int P, const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
-  if (!h || !tokens_inout || (!target_idx && P > 0 && n_iters > 0)) return fail(PG_ERR_INVALID, "pg_msa_gibbs_run: null argument");
-  int rc = check_params(params, h->e.cfg.vocab);
-  if (rc) return rc;
-  if (B < 0 || R < 1 || C < 1 || P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "bad shape");
-  if (B == 0) return PG_OK;
+  int rc = gibbs_prologue(h, "pg_msa_gibbs_run", true, true, tokens_inout, B, R, C, target_idx, (int64_t)B * R, n_iters, P, params);
+  if (rc || B == 0 || n_iters == 0) return rc;
   Engine& e = h->e;
-  if ((rc = check_draw_guide(e.draw_guide(), "pg_msa_gibbs_run", C, params->n_valid, (int64_t)B * R, n_iters))) return rc;
   DeviceGuard g(e.device);
-  const size_t n_draws = (size_t)B * R * P * n_iters;
-  if (n_draws && (rc = check_idx_table(target_idx, n_draws, C, "pg_msa_gibbs_run"))) return rc;
-  return stage_gibbs(e, tokens_inout, (size_t)B * R * C, target_idx, n_draws, sampled_logits, sampled_tokens,
+  return stage_gibbs(e, tokens_inout, (size_t)B * R * C, target_idx, (size_t)B * R * P * n_iters, sampled_logits, sampled_tokens,
                      [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
                        return e.msa_gibbs_device(d_tok, B, R, C, d_idx, n_iters, P, params, d_lg, d_st);
-                     });
-}
-
-// the body of pg_msa_gibbs_single_batch_run; it runs a batch too large for the row-split scratch as chunks of itself, below the public
-// entry's check of the draw guide against the WHOLE call (a chunk has fewer token rows than a per-row bias table)
-static int single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
-                            const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
-                            const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
-  if (!h || !tokens_inout || (n_steps > 0 && (!step_sample_flag || (!step_idx && P_max > 0))))
-    return fail(PG_ERR_INVALID, "pg_msa_gibbs_single_batch_run: null argument");
-  if (B < 0 || R < 1 || C < 1 || P_max < 0 || n_steps < 0) return fail(PG_ERR_INVALID, "bad shape");
-  if (B == 0) return PG_OK;
-  int rc;
-  if (!params) return fail(PG_ERR_INVALID, "null pg_sample_params");
-  for (int b = 0; b < B; ++b)
-    if ((rc = check_params(params + b, h->e.cfg.vocab))) return rc;
-  Engine& e = h->e;
-  DeviceGuard g(e.device);
-  {
-    // The tied row attention of a template batch runs in its split-R form (every template as if alone), whose
-    // fp32 scratch grows with B: 0.5 GB for 4 templates of 128 x 513, past 2 GB from about B = 9 at C = 576 or B = 32 at C = 300.
-    // Templates are independent, so a larger batch is simply run in chunks that fit (same logits and tokens; ADVICE r03:
-    // `--template_batch 32`, BASELINE config 5's "32 templates", used to fail with PG_ERR_INVALID).
-    static const size_t limit = (size_t)env_int("PGIBBS_SPLIT_SCRATCH_MB", 1024) << 20;
-    const size_t need1 = msa_row_split_scratch_bytes(1, R, C, e.cfg.n_heads, e.cfg.n_heads);
-    const int bc = need1 ? (int)std::max<size_t>(1, std::min<size_t>((size_t)B, limit / need1)) : B;
-    if (bc < B) {
-      std::vector<int32_t> idx_c, tok_c;
-      std::vector<float> lg_c;
-      const int V = e.cfg.vocab;
-      for (int b0 = 0; b0 < B; b0 += bc) {
-        const int nb = std::min(bc, B - b0);
-        idx_c.assign((size_t)n_steps * nb * P_max + 1, -1);
-        for (int s2 = 0; s2 < n_steps && P_max > 0; ++s2)
-          memcpy(idx_c.data() + (size_t)s2 * nb * P_max, step_idx + ((size_t)s2 * B + b0) * P_max, (size_t)nb * P_max * 4);
-        if (sampled_logits) lg_c.assign((size_t)n_steps * nb * P_max * V + 1, 0.f);
-        if (sampled_tokens) tok_c.assign((size_t)n_steps * nb * P_max + 1, 0);
-        {
-          // a per-row bias table is indexed by the token row of the whole call: this chunk's rows start b0 * R rows further on
-          struct GuideRows { DrawGuideDev& g; const float* bias; ~GuideRows() { g.bias = bias; } } rows{e.guide, e.guide.bias};
-          if (e.guide.bias && e.guide.bias_rows > 1) e.guide.bias += (size_t)b0 * R * C * e.guide.n_valid;
-          rc = single_batch_run(h, tokens_inout + (size_t)b0 * R * C, nb, R, C, mask_row, target_row, idx_c.data(), step_sample_flag, n_steps,
-                                P_max, params + b0, sampled_logits ? lg_c.data() : nullptr, sampled_tokens ? tok_c.data() : nullptr);
-        }
-        if (rc) return rc;
-        for (int s2 = 0; s2 < n_steps && P_max > 0; ++s2) {
-          if (sampled_logits) memcpy(sampled_logits + ((size_t)s2 * B + b0) * P_max * V, lg_c.data() + (size_t)s2 * nb * P_max * V, (size_t)nb * P_max * V * 4);
-          if (sampled_tokens) memcpy(sampled_tokens + ((size_t)s2 * B + b0) * P_max, tok_c.data() + (size_t)s2 * nb * P_max, (size_t)nb * P_max * 4);
-        }
-      }
-      return PG_OK;
-    }
-  }
-  const size_t n_draws = (size_t)B * P_max * n_steps;
-  if (n_draws && (rc = check_idx_table(step_idx, n_draws, C, "pg_msa_gibbs_single_batch_run"))) return rc;
-  return stage_gibbs(e, tokens_inout, (size_t)B * R * C, step_idx, n_draws, sampled_logits, sampled_tokens,
-                     [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
-                       return e.msa_single_device(d_tok, B, R, C, mask_row, target_row, d_idx, step_sample_flag, n_steps, P_max, params, d_lg, d_st);
                      });
 }
 
 int pg_msa_gibbs_single_batch_run(pg_engine* h, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
                                   const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
                                   const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens) {
-  if (h && params && B > 0 && R > 0 && n_steps > 0)
-    for (int b = 0; b < B; ++b)
-      if (int rc = check_draw_guide(h->e.draw_guide(), "pg_msa_gibbs_single_batch_run", C, params[b].n_valid, (int64_t)B * R, n_steps)) return rc;
-  return single_batch_run(h, tokens_inout, B, R, C, mask_row, target_row, step_idx, step_sample_flag, n_steps, P_max, params, sampled_logits,
-                          sampled_tokens);
+  // every check is of the WHOLE call: a block of it (below) has fewer token rows than a per-row bias table
+  int rc = gibbs_prologue(h, "pg_msa_gibbs_single_batch_run", true, true, tokens_inout, B, R, C, step_idx, B, n_steps, P_max, params, B,
+                          nullptr, n_steps > 0 && !step_sample_flag, mask_row, target_row);
+  if (rc || B == 0 || n_steps == 0) return rc;
+  Engine& e = h->e;
+  DeviceGuard g(e.device);
+  const int V = e.cfg.vocab;
+  // templates [b0, b0 + nb) as one staged call: their tokens, their step table idx[n_steps][nb][P_max], their parameters and outputs
+  auto run = [&](int b0, int nb, const int32_t* idx, float* lg, int32_t* st) {
+    return stage_gibbs(e, tokens_inout + (size_t)b0 * R * C, (size_t)nb * R * C, idx, (size_t)nb * P_max * n_steps, lg, st,
+                       [&](int32_t* d_tok, const int32_t* d_idx, float* d_lg, int32_t* d_st) {
+                         return e.msa_single_device(d_tok, nb, R, C, mask_row, target_row, d_idx, step_sample_flag, n_steps, P_max,
+                                                    params + b0, d_lg, d_st);
+                       });
+  };
+  // The tied row attention of a template batch runs in its split-R form (every template as if alone), whose
+  // fp32 scratch grows with B: 0.5 GB for 4 templates of 128 x 513, past 2 GB from about B = 9 at C = 576 or B = 32 at C = 300.
+  // Templates are independent, so a larger batch is simply run in blocks that fit (same logits and tokens; ADVICE r03:
+  // `--template_batch 32`, BASELINE config 5's "32 templates", used to fail with PG_ERR_INVALID).
+  static const size_t limit = (size_t)env_int("PGIBBS_SPLIT_SCRATCH_MB", 1024) << 20;
+  const size_t need1 = msa_row_split_scratch_bytes(1, R, C, e.cfg.n_heads, e.cfg.n_heads);
+  const int bc = need1 ? (int)std::max<size_t>(1, std::min<size_t>((size_t)B, limit / need1)) : B;
+  if (bc >= B) return run(0, B, step_idx, sampled_logits, sampled_tokens);
+  std::vector<int32_t> idx_c, tok_c;
+  std::vector<float> lg_c;
+  auto to_block = [](auto* block, const auto* table, size_t n) { memcpy(block, table, n * sizeof(*block)); return PG_OK; };
+  auto to_table = [](const auto* block, auto* table, size_t n) { memcpy(table, block, n * sizeof(*block)); return PG_OK; };
+  for (int b0 = 0; b0 < B; b0 += bc) {
+    const int nb = std::min(bc, B - b0);
+    const size_t n1 = (size_t)n_steps * nb * P_max;
+    idx_c.assign(n1 + 1, -1);
+    (void)template_block_rows(idx_c.data(), step_idx, n_steps, B, b0, nb, P_max, to_block);
+    if (sampled_logits) lg_c.assign(n1 * V + 1, 0.f);
+    if (sampled_tokens) tok_c.assign(n1 + 1, 0);
+    {
+      Engine::GuideRowShift rows(e, (int64_t)b0 * R, C);
+      rc = run(b0, nb, idx_c.data(), sampled_logits ? lg_c.data() : nullptr, sampled_tokens ? tok_c.data() : nullptr);
+    }
+    if (rc) return rc;
+    if (sampled_logits) (void)template_block_rows(lg_c.data(), sampled_logits, n_steps, B, b0, nb, (size_t)P_max * V, to_table);
+    if (sampled_tokens) (void)template_block_rows(tok_c.data(), sampled_tokens, n_steps, B, b0, nb, P_max, to_table);
+  }
+  return PG_OK;
 }
 
 // generate_single == the batched form with one template
@@ -407,11 +436,8 @@ int pg_msa_gibbs_single_run(pg_engine* h, int32_t* tokens_inout, int R, int C, i
 int pg_msa_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int R, int C, const int32_t* d_target_idx,
                             int n_iters, int P, const pg_sample_params* params, float* d_sampled_logits,
                             int32_t* d_sampled_tokens) {
-  if (!h || !d_tokens_inout || (!d_target_idx && P > 0 && n_iters > 0))
-    return fail(PG_ERR_INVALID, "pg_msa_gibbs_run_device: null argument");
-  int rc = check_params(params, h->e.cfg.vocab);
+  int rc = gibbs_prologue(h, "pg_msa_gibbs_run_device", true, false, d_tokens_inout, B, R, C, d_target_idx, (int64_t)B * R, n_iters, P, params);
   if (rc) return rc;
-  if ((rc = check_draw_guide(h->e.draw_guide(), "pg_msa_gibbs_run_device", C, params->n_valid, (int64_t)B * R, n_iters))) return rc;
   DeviceGuard g(h->e.device);
   return h->e.msa_gibbs_device(d_tokens_inout, B, R, C, d_target_idx, n_iters, P, params, d_sampled_logits, d_sampled_tokens);
 }
@@ -419,53 +445,31 @@ int pg_msa_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int R,
 // ---- masked log-likelihood scoring (next-tier path: log_likelihood_batch) ---------------------------
 // rows: tokens[n_rows][width]; sample s scores token row row_of[s] at positions idx[s][P] (entries < 0 skipped, out = 0)
 // against targets[s][P]; out[s][P] = log_softmax(logits)[target].
-static int forward_logprobs(Engine& e, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+static int forward_logprobs(pg_engine* h, const char* who, bool msa, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
                             const int32_t* idx, const int32_t* targets, int n_sel, int P, float* out) {
-  DeviceGuard g(e.device);
-  const int64_t M = (int64_t)B * R * C;
-  const int64_t n = (int64_t)n_sel * P;
-  int rc;
+  if (!h || !tokens || !row_of || !idx || !targets || !out) return fail(PG_ERR_INVALID, std::string(who) + ": null argument");
+  Engine& e = h->e;
+  if (int rc = e.check_call(msa, B, R, C, n_sel, P)) return rc;
+  const size_t n = (size_t)n_sel * P;
   if (n == 0 || B == 0) return PG_OK;
-  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
-  if ((rc = e.d_idx.ensure((size_t)n * 4, e.stream)) || (rc = e.d_samp_tok.ensure((size_t)n * 4, e.stream))) return rc;
-  if ((rc = e.d_rowmap.ensure((size_t)n_sel * 4, e.stream))) return rc;
-  if ((rc = e.logits.ensure((size_t)n * e.cfg.vocab * 4, e.stream)) || (rc = e.d_samp_logits.ensure((size_t)n * 4, e.stream))) return rc;
-  for (int64_t i = 0; i < n; ++i)
-    if (idx[i] >= C || (idx[i] >= 0 && (targets[i] < 0 || targets[i] >= e.cfg.vocab))) return fail(PG_ERR_INVALID, "logprobs: index out of range");
-  for (int i = 0; i < n_sel; ++i)
-    if (row_of[i] < 0 || row_of[i] >= B * R) return fail(PG_ERR_INVALID, "logprobs: row out of range");
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
-  PG_HIP(hipMemcpyAsync(e.d_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
-  PG_HIP(hipMemcpyAsync(e.d_samp_tok.p, targets, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
-  PG_HIP(hipMemcpyAsync(e.d_rowmap.p, row_of, (size_t)n_sel * 4, hipMemcpyHostToDevice, e.stream));
-  {
-    PadFlag pad(e, tokens, (size_t)M);
-    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
-  }
-  if (rc) return rc;
-  if ((rc = e.head(e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(), P, C, n, e.logits.as<float>()))) return rc;
-  if ((rc = launch_logprob_gather(e.stream, e.logits.as<float>(), e.cfg.vocab, 1, C, e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(),
-                                  e.d_samp_tok.as<int32_t>(), n_sel, P, e.d_samp_logits.as<float>(), e.range_err))) return rc;
-  PG_HIP(hipMemcpyAsync(out, e.d_samp_logits.p, (size_t)n * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  return e.finish_check();
+  for (size_t i = 0; i < n; ++i)
+    if (idx[i] >= 0 && (targets[i] < 0 || targets[i] >= e.cfg.vocab)) return fail(PG_ERR_INVALID, "logprobs: index out of range");
+  return score_rows(e, who, "logprobs", tokens, B, R, C, row_of, idx, n_sel, P, targets, n, n,
+                    [&](const int32_t* d_targets, float* d_out) {
+                      return launch_logprob_gather(e.stream, e.logits.as<float>(), e.cfg.vocab, 1, C, e.d_idx.as<int32_t>(),
+                                                   e.d_rowmap.as<int32_t>(), d_targets, n_sel, P, d_out, e.range_err);
+                    },
+                    out, n, nullptr, 0);
 }
 
 int pg_esm_forward_logprobs(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
                             const int32_t* targets, int n_sel, int P, float* out) {
-  if (!h || !tokens || !row_of || !idx || !targets || !out) return fail(PG_ERR_INVALID, "pg_esm_forward_logprobs: null argument");
-  if (!h->e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
-  if (B < 0 || T < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
-  if (T > h->e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
-  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprobs(h->e, tokens, B, 1, T, row_of, idx, targets, n_sel, P, out));
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprobs(h, "pg_esm_forward_logprobs", false, tokens, B, 1, T, row_of, idx, targets, n_sel, P, out));
 }
 
 int pg_msa_forward_logprobs(pg_engine* h, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
                             const int32_t* idx, const int32_t* targets, int n_sel, int P, float* out) {
-  if (!h || !tokens || !row_of || !idx || !targets || !out) return fail(PG_ERR_INVALID, "pg_msa_forward_logprobs: null argument");
-  if (h->e.cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
-  if (B < 0 || R < 1 || C < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
-  return forward_logprobs(h->e, tokens, B, R, C, row_of, idx, targets, n_sel, P, out);
+  return forward_logprobs(h, "pg_msa_forward_logprobs", true, tokens, B, R, C, row_of, idx, targets, n_sel, P, out);
 }
 
 int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
@@ -484,63 +488,35 @@ static int check_table_cols(const int32_t* cols, int n_cols, int V) {
   return PG_OK;
 }
 
-static int forward_logprob_table(Engine& e, const int32_t* tokens, int B, int R, int C, const int32_t* row_of, const int32_t* idx,
-                                 int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy) {
-  DeviceGuard g(e.device);
+static int forward_logprob_table(pg_engine* h, const char* who, bool msa, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+                                 const int32_t* idx, int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy) {
+  if (!h || !tokens || !row_of || !idx || !cols || !out) return fail(PG_ERR_INVALID, std::string(who) + ": null argument");
+  Engine& e = h->e;
   const int V = e.cfg.vocab;
-  const int64_t M = (int64_t)B * R * C;
-  const int64_t n = (int64_t)n_sel * P;
   int rc;
+  if ((rc = e.check_call(msa, B, R, C, n_sel, P))) return rc;
   if ((rc = check_logprob_table_args(V, n_cols, norm, n_sel, P)) || (rc = check_table_cols(cols, n_cols, V))) return rc;
+  const size_t n = (size_t)n_sel * P;
   if (n == 0 || B == 0) return PG_OK;
-  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream))) return rc;
-  if ((rc = e.d_idx.ensure((size_t)n * 4, e.stream)) || (rc = e.d_samp_tok.ensure((size_t)n_cols * 4, e.stream))) return rc;
-  if ((rc = e.d_rowmap.ensure((size_t)n_sel * 4, e.stream))) return rc;
-  // d_samp_logits: the table, then the entropies
-  if ((rc = e.logits.ensure((size_t)n * V * 4, e.stream)) || (rc = e.d_samp_logits.ensure((size_t)n * (n_cols + 1) * 4, e.stream))) return rc;
-  for (int64_t i = 0; i < n; ++i)
-    if (idx[i] >= C) return fail(PG_ERR_INVALID, "logprob table: index out of range");
-  for (int i = 0; i < n_sel; ++i)
-    if (row_of[i] < 0 || row_of[i] >= B * R) return fail(PG_ERR_INVALID, "logprob table: row out of range");
-  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
-  PG_HIP(hipMemcpyAsync(e.d_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, e.stream));
-  PG_HIP(hipMemcpyAsync(e.d_samp_tok.p, cols, (size_t)n_cols * 4, hipMemcpyHostToDevice, e.stream));
-  PG_HIP(hipMemcpyAsync(e.d_rowmap.p, row_of, (size_t)n_sel * 4, hipMemcpyHostToDevice, e.stream));
-  {
-    PadFlag pad(e, tokens, (size_t)M);
-    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
-  }
-  if (rc) return rc;
-  if ((rc = e.head(e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(), P, C, n, e.logits.as<float>()))) return rc;
-  float* d_out = e.d_samp_logits.as<float>();
-  float* d_ent = entropy ? d_out + (size_t)n * n_cols : nullptr;
-  if ((rc = launch_logprob_table(e.stream, e.logits.as<float>(), V, 1, C, e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(),
-                                 e.d_samp_tok.as<int32_t>(), n_cols, norm, n_sel, P, d_out, d_ent, e.range_err))) return rc;
-  // the results wait on the device until the range check has passed: a PG_ERR_RANGE call leaves the caller's buffers alone
-  PG_HIP(hipStreamSynchronize(e.stream));
-  if ((rc = e.finish_check())) return rc;
-  PG_HIP(hipMemcpyAsync(out, d_out, (size_t)n * n_cols * 4, hipMemcpyDeviceToHost, e.stream));
-  if (entropy) PG_HIP(hipMemcpyAsync(entropy, d_ent, (size_t)n * 4, hipMemcpyDeviceToHost, e.stream));
-  PG_HIP(hipStreamSynchronize(e.stream));
-  return PG_OK;
+  // the device holds the table, then the entropies
+  return score_rows(e, who, "logprob table", tokens, B, R, C, row_of, idx, n_sel, P, cols, (size_t)n_cols, n * (n_cols + 1),
+                    [&](const int32_t* d_cols, float* d_out) {
+                      return launch_logprob_table(e.stream, e.logits.as<float>(), V, 1, C, e.d_idx.as<int32_t>(), e.d_rowmap.as<int32_t>(),
+                                                  d_cols, n_cols, norm, n_sel, P, d_out, entropy ? d_out + n * n_cols : nullptr, e.range_err);
+                    },
+                    out, n * n_cols, entropy, n);
 }
 
 int pg_esm_forward_logprob_table(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
                                  int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy) {
-  if (!h || !tokens || !row_of || !idx || !cols || !out) return fail(PG_ERR_INVALID, "pg_esm_forward_logprob_table: null argument");
-  if (!h->e.esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
-  if (B < 0 || T < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
-  if (T > h->e.cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
-  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprob_table(h->e, tokens, B, 1, T, row_of, idx, n_sel, P, cols, n_cols, norm, out, entropy));
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logprob_table(h, "pg_esm_forward_logprob_table", false, tokens, B, 1, T, row_of, idx, n_sel, P, cols,
+                                                        n_cols, norm, out, entropy));
 }
 
 int pg_msa_forward_logprob_table(pg_engine* h, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
                                  const int32_t* idx, int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out,
                                  float* entropy) {
-  if (!h || !tokens || !row_of || !idx || !cols || !out) return fail(PG_ERR_INVALID, "pg_msa_forward_logprob_table: null argument");
-  if (h->e.cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
-  if (B < 0 || R < 1 || C < 1 || n_sel < 0 || P < 0) return fail(PG_ERR_INVALID, "bad shape");
-  return forward_logprob_table(h->e, tokens, B, R, C, row_of, idx, n_sel, P, cols, n_cols, norm, out, entropy);
+  return forward_logprob_table(h, "pg_msa_forward_logprob_table", true, tokens, B, R, C, row_of, idx, n_sel, P, cols, n_cols, norm, out, entropy);
 }
 
 int pg_logprob_table_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,

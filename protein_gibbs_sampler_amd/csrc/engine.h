@@ -237,6 +237,23 @@ struct Engine {
            const float* x_src = nullptr);
 
   // ---- entry points ----
+  // Can this engine run a call on tokens[B][R][C]?  Answered from cfg and the call's scalars alone, one message per condition, in this
+  // order: the architecture (msa: the call came through a pg_msa_* entry or method; else a pg_esm_* one, R = 1), B >= 0 and R, C >= 1,
+  // R within msa_position_embedding, C within the position table, then the call's two counts (P / n_iters, P_max / n_steps,
+  // n_sel / P) >= 0 and its two row indices (generate_single's mask_row / target_row) within R.  The one such check: every C entry
+  // that takes tokens makes it before anything is allocated or copied, and so do the *_device methods below.  (Hidden: the library's
+  // dynamic symbol table stays what it was before this function existed)
+  __attribute__((visibility("hidden"))) int check_call(bool msa, int B, int R, int C, int count0 = 0, int count1 = 0, int row0 = 0, int row1 = 0) const;
+  // A per-row bias table of the draw guide is indexed by the token row of the WHOLE call: while this lives, a call on a block of its
+  // alignments (generate_single batches) that begins at token row row0 reads its own rows of the table
+  struct GuideRowShift {
+    DrawGuideDev& g;
+    const float* bias;
+    GuideRowShift(Engine& e, int64_t row0, int C) : g(e.guide), bias(e.guide.bias) {
+      if (g.bias && g.bias_rows > 1) g.bias += (size_t)row0 * C * g.n_valid;
+    }
+    ~GuideRowShift() { g.bias = bias; }
+  };
   // One Gibbs iteration up to its logits: mask_idx scattered (if mask) to idx[n_rows][P] of the token rows mask_map, the trunk
   // (pruned when prune_last says so), the LM head at idx[n_rows][P] of the token rows sel_map -> lg[n_rows * P][V].  A null map:
   // row i is token row i.  dit: the device-side iteration counter of a captured iteration (pruned only)
@@ -252,6 +269,16 @@ struct Engine {
                         const int32_t* step_sample_flag_host, int n_steps, int P_max, const pg_sample_params* sp,
                         float* d_samp_logits, int32_t* d_samp_tok);
 };
+
+// Templates [b0, b0 + nb) of a generate_single batch as a call of their own: their rows of a [n_steps][B][row] table (step positions,
+// sampled logits, sampled tokens) <-> a contiguous [n_steps][nb][row] block, one copy(block part, table part, values) per step.  The
+// copy picks the direction and the memory: memcpy on host tables (api.hip), hipMemcpyAsync on the stream on device ones (engine.hip)
+template <typename Tb, typename Tt, typename Copy>
+int template_block_rows(Tb* block, Tt* table, int n_steps, int B, int b0, int nb, size_t row, Copy&& copy) {
+  for (int s = 0; s < n_steps && row > 0; ++s)
+    if (int rc = copy(block + (size_t)s * nb * row, table + ((size_t)s * B + b0) * row, (size_t)nb * row)) return rc;
+  return PG_OK;
+}
 
 // host side of the ESM-2 rotary embedding: the cos / sin table the rotation kernel reads (engine.hip)
 // live > 0: heads of `live` in slots of hd -- the frequencies of a head of `live`, cos 1 and sin 0 in a half's pad columns

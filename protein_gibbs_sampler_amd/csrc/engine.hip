@@ -876,14 +876,12 @@ int Engine::masked_logits(int32_t* d_tok, int B, int R, int C, const int32_t* id
 
 int Engine::esm_gibbs_device(int32_t* d_tok, int B, int T, const int32_t* d_idx_, int n_iters, int P,
                              const pg_sample_params* sp, float* d_samp_logits_, int32_t* d_samp_tok_) {
-  if (!esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
-  if (B < 0 || T < 1 || P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "gibbs: negative size");
-  if (T > cfg.max_positions) return fail(PG_ERR_INVALID, "sequence longer than the learned position table");
+  int rc = check_call(false, B, 1, T, n_iters, P);
+  if (rc) return rc;
   if (B == 0 || n_iters == 0) return PG_OK;
   const int V = cfg.vocab;
   const int64_t n_sel_rows = B;              // one selected token row per chain
   const int64_t n_draws = (int64_t)B * P;
-  int rc;
   if (!d_samp_logits_ && (rc = logits.ensure((size_t)(n_draws > 0 ? n_draws : 1) * V * 4, stream))) return rc;
   static const int use_graph = env_int("PGIBBS_GRAPH", 1);
   const bool pruned = prune_last(n_draws, (int64_t)B * T);
@@ -1075,19 +1073,23 @@ int Engine::set_draw_guide(const pg_draw_guide* g) {
   return PG_OK;
 }
 
-static int check_msa_shape(const pg_model_config& cfg, int B, int R, int C) {
-  if (cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
-  if (B < 0 || R < 1 || C < 1) return fail(PG_ERR_INVALID, "bad MSA shape");
-  if (R > cfg.max_msa_rows) return fail(PG_ERR_INVALID, "MSA has more rows than msa_position_embedding");
-  if (C > cfg.max_positions) return fail(PG_ERR_INVALID, "alignment longer than the learned position table");
+// embed_ln_kernel reads pos + p * d and msa_pos + (row % R) * d of tables of max_positions + pad_idx + 1 and max_msa_rows rows (init)
+int Engine::check_call(bool msa, int B, int R, int C, int count0, int count1, int row0, int row1) const {
+  if (msa && cfg.arch != PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, "engine was not built for the MSA-1b architecture");
+  if (!msa && !esm_family()) return fail(PG_ERR_INVALID, "engine was not built for an ESM-1b / ESM-1 / ESM-2 architecture");
+  if (B < 0 || R < 1 || C < 1) return fail(PG_ERR_INVALID, "bad shape");
+  if (msa && R > cfg.max_msa_rows) return fail(PG_ERR_INVALID, "MSA has more rows than msa_position_embedding");
+  if (C > cfg.max_positions)
+    return fail(PG_ERR_INVALID, msa ? "alignment longer than the learned position table" : "sequence longer than the learned position table");
+  if (count0 < 0 || count1 < 0) return fail(PG_ERR_INVALID, "bad shape");
+  if (row0 < 0 || row0 >= R || row1 < 0 || row1 >= R) return fail(PG_ERR_INVALID, "row index out of range");
   return PG_OK;
 }
 
 int Engine::msa_gibbs_device(int32_t* d_tok, int B, int R, int C, const int32_t* d_idx_, int n_iters, int P,
                              const pg_sample_params* sp, float* d_samp_logits_, int32_t* d_samp_tok_) {
-  int rc = check_msa_shape(cfg, B, R, C);
+  int rc = check_call(true, B, R, C, n_iters, P);
   if (rc) return rc;
-  if (P < 0 || n_iters < 0) return fail(PG_ERR_INVALID, "gibbs: negative size");
   if (B == 0 || n_iters == 0) return PG_OK;
   const int V = cfg.vocab;
   const int64_t n_sel_rows = (int64_t)B * R;         // every row of every MSA draws its own P positions
@@ -1112,46 +1114,42 @@ int Engine::msa_gibbs_device(int32_t* d_tok, int B, int R, int C, const int32_t*
 int Engine::msa_single_device(int32_t* d_tok, int B, int R, int C, int mask_row, int target_row, const int32_t* d_step_idx,
                               const int32_t* step_sample_flag_host, int n_steps, int P_max, const pg_sample_params* sp,
                               float* d_samp_logits_, int32_t* d_samp_tok_) {
-  int rc = check_msa_shape(cfg, B, R, C);
+  int rc = check_call(true, B, R, C, n_steps, P_max, mask_row, target_row);
   if (rc) return rc;
-  if (mask_row < 0 || mask_row >= R || target_row < 0 || target_row >= R) return fail(PG_ERR_INVALID, "row index out of range");
-  if (P_max < 0 || n_steps < 0) return fail(PG_ERR_INVALID, "negative size");
   if (n_steps == 0 || B == 0) return PG_OK;
+  const int V = cfg.vocab;
   if (B > 1 && (int64_t)R * C <= 2048) {
     // few-token regime: K-splits and the weight-streaming GEMM are picked by the local shape there, so a
     // batch would not reproduce the single calls -- run the templates one after the other (launch-bound either way)
+    auto copy = [&](auto* dst, const auto* src, size_t n) -> int {
+      PG_HIP(hipMemcpyAsync(dst, src, n * sizeof(*dst), hipMemcpyDeviceToDevice, stream));
+      return PG_OK;
+    };
+    auto to_table = [&](auto* block, auto* table, size_t n) { return copy(table, block, n); };
+    const size_t n1 = (size_t)n_steps * (P_max > 0 ? P_max : 1);
     for (int b = 0; b < B; ++b) {
       // template b's steps, contiguous [n_steps][P_max]
       if ((rc = tmp_idx.ensure((size_t)(n_steps * (size_t)P_max + 1) * 4, stream))) return rc;
-      for (int s2 = 0; s2 < n_steps && P_max > 0; ++s2)
-        PG_HIP(hipMemcpyAsync(tmp_idx.as<int32_t>() + (size_t)s2 * P_max, d_step_idx + ((size_t)s2 * B + b) * P_max, (size_t)P_max * 4,
-                              hipMemcpyDeviceToDevice, stream));
+      if ((rc = template_block_rows(tmp_idx.as<int32_t>(), d_step_idx, n_steps, B, b, 1, P_max, copy))) return rc;
       // per-template outputs land in scratch-free strided form: sample into temporaries, then scatter
       float* lg_b = nullptr;
       int32_t* st_b = nullptr;
       if (d_samp_logits_ || d_samp_tok_) {
-        if ((rc = tmp_out.ensure((size_t)n_steps * (P_max > 0 ? P_max : 1) * cfg.vocab * 4 + (size_t)n_steps * (P_max > 0 ? P_max : 1) * 4, stream))) return rc;
+        if ((rc = tmp_out.ensure(n1 * V * 4 + n1 * 4, stream))) return rc;
         lg_b = d_samp_logits_ ? tmp_out.as<float>() : nullptr;
-        st_b = d_samp_tok_ ? (int32_t*)(tmp_out.as<float>() + (size_t)n_steps * (P_max > 0 ? P_max : 1) * cfg.vocab) : nullptr;
+        st_b = d_samp_tok_ ? (int32_t*)(tmp_out.as<float>() + n1 * V) : nullptr;
       }
       {
-        // a per-row bias table is indexed by the token row of the whole call: template b's rows start R rows further on
-        struct GuideRows { DrawGuideDev& g; const float* bias; ~GuideRows() { g.bias = bias; } } rows{guide, guide.bias};
-        if (guide.bias && guide.bias_rows > 1) guide.bias += (size_t)b * R * C * guide.n_valid;
+        GuideRowShift rows(*this, (int64_t)b * R, C);
         rc = msa_single_device(d_tok + (size_t)b * R * C, 1, R, C, mask_row, target_row, tmp_idx.as<int32_t>(), step_sample_flag_host,
                                n_steps, P_max, sp + b, lg_b, st_b);
       }
       if (rc) return rc;
-      for (int s2 = 0; s2 < n_steps && P_max > 0; ++s2) {
-        if (lg_b) PG_HIP(hipMemcpyAsync(d_samp_logits_ + ((size_t)s2 * B + b) * P_max * cfg.vocab, lg_b + (size_t)s2 * P_max * cfg.vocab,
-                                        (size_t)P_max * cfg.vocab * 4, hipMemcpyDeviceToDevice, stream));
-        if (st_b) PG_HIP(hipMemcpyAsync(d_samp_tok_ + ((size_t)s2 * B + b) * P_max, st_b + (size_t)s2 * P_max, (size_t)P_max * 4,
-                                        hipMemcpyDeviceToDevice, stream));
-      }
+      if (lg_b && (rc = template_block_rows(lg_b, d_samp_logits_, n_steps, B, b, 1, (size_t)P_max * V, to_table))) return rc;
+      if (st_b && (rc = template_block_rows(st_b, d_samp_tok_, n_steps, B, b, 1, P_max, to_table))) return rc;
     }
     return PG_OK;
   }
-  const int V = cfg.vocab;
   if ((rc = d_rowmap.ensure((size_t)2 * B * 4, stream))) return rc;
   std::vector<int32_t> maps((size_t)2 * B);
   for (int b = 0; b < B; ++b) {

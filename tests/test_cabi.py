@@ -76,6 +76,29 @@ def test_compute_entry_points_fail_loudly_without_gpu():
     assert b"no CPU fallback" in L.pg_last_error()
 
 
+# every entry that takes an engine handle and answers with a code (pg_engine_device answers -1, pg_engine_destroy nothing)
+_ENGINE_ENTRIES = [(n, a) for n, r, a in _lib.SIGNATURES
+                   if n.startswith(("pg_engine_", "pg_esm_", "pg_msa_", "pg_prof_")) and r is ctypes.c_int and a[0] is ctypes.c_void_p
+                   and n != "pg_engine_device"]
+_PLAIN_NULL_ENGINE = {"pg_engine_set_stream", "pg_engine_synchronize", "pg_engine_set_job_items", "pg_engine_set_draw_guide",
+                      "pg_prof_enable", "pg_prof_reset"}
+
+
+@pytest.mark.parametrize("name,argtypes", _ENGINE_ENTRIES, ids=[n for n, _ in _ENGINE_ENTRIES])
+def test_engine_entries_refuse_a_null_handle(name, argtypes):
+    """No entry looks into a null engine: PG_ERR_INVALID with the entry's own message, every other argument null or zero."""
+    zero = {ctypes.c_int: 0, ctypes.c_int64: 0, ctypes.c_float: 0.0}
+    args = [zero.get(t) for t in argtypes]                      # pointers of every kind: None
+    assert getattr(_lib.lib(), name)(*args) == _lib.PG_ERR_INVALID
+    want = "null engine" if name in _PLAIN_NULL_ENGINE else name + ": null argument"
+    assert _lib.lib().pg_last_error().decode() == want
+
+
+def test_engine_entries_with_a_handle_are_the_ones_expected():
+    names = {n for n, _ in _ENGINE_ENTRIES}
+    assert len(names) == 21 and {"pg_esm_gibbs_run_device", "pg_msa_gibbs_single_run", "pg_msa_forward_logprob_table"} <= names
+
+
 def test_comm_entry_points_reject_bad_arguments_and_need_a_gpu():
     """pg_comm_* (the C-ABI form of the one RCCL gather): argument checks run on the host; joining a communicator
     without a GPU is PG_ERR_NO_DEVICE, never a silent single-process fallback."""

@@ -117,6 +117,105 @@ def test_c_abi_rejects_out_of_range_positions(small_sampler):
     assert (d_tok.cpu().numpy() == want).all()
 
 
+# ---- what an engine can run: the position tables' bounds and the vocabulary, refused on the host by every token entry ------------
+VALID = list(range(4, 24))
+ENTRIES = ("forward_logits", "forward_logprobs", "forward_logprob_table", "gibbs_run")
+
+
+@pytest.fixture(scope="module")
+def tiny_msa():
+    cfg = weights.make_config(weights.MSA1B_CONFIG, d_model=128, n_layers=1, d_ffn=256, max_positions=16, max_msa_rows=4)
+    sd = weights.synthetic_state_dict(cfg, seed=3, std=0.08, embed_std=0.5)
+    return models.ESM_MSA1(state_dict=sd, config=cfg, precision="bf16").model.to("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def tiny_esm():
+    cfg = weights.make_config(weights.ESM1B_CONFIG, d_model=128, n_layers=1, d_ffn=256, max_positions=16)
+    sd = weights.synthetic_state_dict(cfg, seed=3, std=0.08, embed_std=0.5)
+    return models.ESM1b(state_dict=sd, config=cfg, precision="bf16").model.to("cuda:0")
+
+
+def _tokens(*shape):
+    """<cls>, then residues: every id inside the vocabulary, no <pad>"""
+    tok = (4 + np.arange(int(np.prod(shape))) % 20).reshape(shape).astype(np.int32)
+    tok[..., 0] = 0
+    return tok
+
+
+def _drive(lm, entry, tok):
+    """One call of a host-buffer entry on tok ([B, T] or [B, R, C]), positions 1 and 2 of every token row: its float outputs."""
+    rows = int(np.prod(tok.shape[:-1]))
+    at = np.tile(np.array([1, 2], np.int32), (rows, 1))
+    if entry == "forward_logits":
+        return [lm.forward_logits(tok)]
+    if entry == "forward_logprobs":
+        return [lm.forward_logprobs(tok, np.arange(rows), at, np.full((rows, 2), 5))]
+    if entry == "forward_logprob_table":
+        return list(lm.forward_logprob_table(tok, np.arange(rows), at, VALID, want_entropy=True))
+    params = _lib.make_sample_params(True, 32, 0, float("inf"), None, VALID, 1)
+    return [lm.gibbs_run(tok, at.reshape((1,) + tok.shape[:-1] + (2,)), params, want_logits=True)[0]]      # one iteration
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_calls_at_the_position_tables_bounds_run(tiny_msa, tiny_esm, entry):
+    for lm, shape in ((tiny_msa, (1, 4, 16)), (tiny_esm, (2, 16))):
+        for out in _drive(lm, entry, _tokens(*shape)):
+            assert out.size and np.isfinite(out).all()
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("arch,shape,text", [("msa", (1, 5, 8), "more rows than msa_position_embedding"),
+                                             ("msa", (1, 2, 17), "longer than the learned position table"),
+                                             ("esm", (2, 17), "longer than the learned position table")])
+def test_calls_one_past_a_position_table_are_refused(tiny_msa, tiny_esm, arch, shape, text, entry):
+    tok = _tokens(*shape)
+    before = tok.copy()
+    with pytest.raises(_lib.PgError, match=text) as ei:
+        _drive(tiny_msa if arch == "msa" else tiny_esm, entry, tok)
+    assert ei.value.code == _lib.PG_ERR_INVALID and (tok == before).all()
+
+
+@pytest.mark.parametrize("bad", [33, -1])
+@pytest.mark.parametrize("arch,entry", [("esm", e) for e in ENTRIES] + [("msa", e) for e in ENTRIES + ("gibbs_single_batch_run",)])
+def test_tokens_outside_the_vocabulary_are_refused_by_entry_and_index(tiny_msa, tiny_esm, arch, entry, bad):
+    lm = tiny_msa if arch == "msa" else tiny_esm
+    assert lm.cfg["vocab"] == 33
+    tok = _tokens(1, 2, 8) if arch == "msa" else _tokens(2, 8)
+    tok.reshape(-1)[11] = bad
+    before = tok.copy()
+    with pytest.raises(_lib.PgError) as ei:
+        if entry == "gibbs_single_batch_run":
+            params = [_lib.make_sample_params(True, 32, 0, float("inf"), None, VALID, 1)]
+            lm.gibbs_single_batch_run(tok, 1, 0, np.array([[[1, 2]], [[3, 4]]], np.int32), [1, 0], params)
+        else:
+            _drive(lm, entry, tok)
+    assert ei.value.code == _lib.PG_ERR_INVALID and (tok == before).all()
+    msg = ei.value.msg
+    assert "pg_%s_%s:" % (arch, entry) in msg and "token %d " % bad in msg and "flat index 11 " in msg
+
+
+def test_scoring_entries_leave_out_alone_on_a_range_error():
+    """pgibbs.h: PG_ERR_RANGE is reported before a host buffer of the caller's is written -- by both scoring entries."""
+    from test_gpu_fp16_mode import _auto_setup
+    cfg, sd, tok = _auto_setup(scale_fc1=1e5)
+    lm = models.ESM1b(state_dict=sd, config=cfg, precision="fp16").model.to("cuda:0")
+    L, p = _lib.lib(), _lib.ptr
+    B, T = tok.shape
+    row_of = np.arange(B, dtype=np.int32)
+    idx = np.tile(np.array([3, 9], np.int32), (B, 1))
+    targets = np.full((B, 2), 5, np.int32)
+    cols = np.asarray(VALID, np.int32)
+    sentinel = np.float32(-12345.5)
+    out = np.full((B, 2), sentinel)
+    assert L.pg_esm_forward_logprobs(lm.handle, p(tok), B, T, p(row_of), p(idx), p(targets), B, 2, p(out)) == _lib.PG_ERR_RANGE
+    assert (out == sentinel).all()
+    table, ent = np.full((B, 2, len(cols)), sentinel), np.full((B, 2), sentinel)
+    assert L.pg_esm_forward_logprob_table(lm.handle, p(tok), B, T, p(row_of), p(idx), B, 2, p(cols), len(cols), _lib.PG_TABLE_NORM_VOCAB,
+                                          p(table), p(ent)) == _lib.PG_ERR_RANGE
+    assert (table == sentinel).all() and (ent == sentinel).all()
+
+
 def test_ragged_list_seeds_mask_pad_keys_in_the_gibbs_run(small_sampler):
     """List seeds longer than max_len leave no <mask> padding and the batch converter pads the shorter rows with <pad>
     (esm_sampler.py:113-115): the Gibbs run must then mask <pad> keys in attention as the scoring entry points do."""
