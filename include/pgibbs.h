@@ -23,6 +23,15 @@
 extern "C" {
 #endif
 
+/* Every entry point below is marked PG_API: the shared library exports these symbols and nothing else. */
+#ifndef PG_API
+#if defined(__GNUC__) || defined(__clang__)
+#define PG_API __attribute__((visibility("default")))
+#else
+#define PG_API
+#endif
+#endif
+
 #define PG_OK 0
 #define PG_ERR_INVALID 1   /* bad argument / shape */
 #define PG_ERR_HIP 2       /* HIP runtime failure (message has hipGetErrorString) */
@@ -34,10 +43,10 @@ extern "C" {
                               BEFORE they overwrite the caller's buffers, so the call can be repeated on a PG_PREC_BF16 engine;
                               device-pointer entry points report it at pg_engine_synchronize */
 
-const char* pg_version(void);
-const char* pg_last_error(void);
+PG_API const char* pg_version(void);
+PG_API const char* pg_last_error(void);
 /* number of HIP devices visible (0 when there is none or the runtime cannot initialise) */
-int pg_device_count(void);
+PG_API int pg_device_count(void);
 
 /* ------------------------------------------------------------------------------------------
  * Host: CPython-exact Mersenne Twister.
@@ -50,21 +59,21 @@ int pg_device_count(void);
  * the interpreter's RNG is left exactly where the reference would have left it.
  * ------------------------------------------------------------------------------------------ */
 typedef struct pg_pyrandom pg_pyrandom;
-pg_pyrandom* pg_pyrandom_create(void);
-void pg_pyrandom_destroy(pg_pyrandom*);
+PG_API pg_pyrandom* pg_pyrandom_create(void);
+PG_API void pg_pyrandom_destroy(pg_pyrandom*);
 /* random.seed(int): key = little-endian 32-bit words of abs(n) (at least one word) */
-int pg_pyrandom_seed(pg_pyrandom*, const uint32_t* key_words, int n_words);
-int pg_pyrandom_setstate(pg_pyrandom*, const uint32_t* mt624, int index);
-int pg_pyrandom_getstate(const pg_pyrandom*, uint32_t* mt624, int* index);
-uint32_t pg_pyrandom_getrandbits32(pg_pyrandom*, int k /* 1..32 */);
-double pg_pyrandom_random(pg_pyrandom*);
+PG_API int pg_pyrandom_seed(pg_pyrandom*, const uint32_t* key_words, int n_words);
+PG_API int pg_pyrandom_setstate(pg_pyrandom*, const uint32_t* mt624, int index);
+PG_API int pg_pyrandom_getstate(const pg_pyrandom*, uint32_t* mt624, int* index);
+PG_API uint32_t pg_pyrandom_getrandbits32(pg_pyrandom*, int k /* 1..32 */);
+PG_API double pg_pyrandom_random(pg_pyrandom*);
 /* random.sample(population, k): out[k] = chosen population values */
-int pg_pyrandom_sample(pg_pyrandom*, const int32_t* population, int n, int k, int32_t* out);
+PG_API int pg_pyrandom_sample(pg_pyrandom*, const int32_t* population, int n, int k, int32_t* out);
 /* n_rows successive random.sample calls (one per chain / MSA row), out[n_rows][k] */
-int pg_pyrandom_sample_table(pg_pyrandom*, const int32_t* population, int n, int k, int64_t n_rows, int32_t* out);
-int pg_pyrandom_shuffle(pg_pyrandom*, int32_t* x, int n);
+PG_API int pg_pyrandom_sample_table(pg_pyrandom*, const int32_t* population, int n, int k, int64_t n_rows, int32_t* out);
+PG_API int pg_pyrandom_shuffle(pg_pyrandom*, int32_t* x, int n);
 /* random.choices(range(n), k=k) (no weights): out[k] = chosen indices */
-int pg_pyrandom_choices(pg_pyrandom*, int n, int k, int32_t* out);
+PG_API int pg_pyrandom_choices(pg_pyrandom*, int n, int k, int32_t* out);
 
 /* ------------------------------------------------------------------------------------------
  * Engine: holds the weights of one masked LM on one MI355X and runs the Gibbs hot path.
@@ -143,7 +152,7 @@ typedef struct {
   int64_t numel;
 } pg_tensor;
 
-int pg_engine_create(const pg_model_config* cfg, const pg_tensor* tensors, int n_tensors, int device_ordinal,
+PG_API int pg_engine_create(const pg_model_config* cfg, const pg_tensor* tensors, int n_tensors, int device_ordinal,
                      int precision, pg_engine** out);
 /* An EMBEDDED model: a PG_ARCH_ESM2 model whose head width no kernel is built for (esm2_t12_35M_UR50D: d_model 480, 20 heads of 24),
  * run with every head in a slot of a built width, head_slot (32 for heads of 24).  cfg carries the model's OWN sizes (480 / 20 / 1920)
@@ -156,23 +165,23 @@ int pg_engine_create(const pg_model_config* cfg, const pg_tensor* tensors, int n
  * other than PG_ARCH_ESM2; a slot that is no built head width; a width that is not a multiple of 4 or not smaller than the slot; more
  * heads than the slot's width allows per row; then pg_engine_create's own rules on the run shape.  Every entry point, precision mode and
  * knob works on such an engine as on any other.  pg_engine_create itself keeps refusing such a configuration. */
-int pg_engine_create_embedded(const pg_model_config* cfg, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal,
+PG_API int pg_engine_create_embedded(const pg_model_config* cfg, int head_slot, const pg_tensor* tensors, int n_tensors, int device_ordinal,
                               int precision, pg_engine** out);
-void pg_engine_destroy(pg_engine*);
+PG_API void pg_engine_destroy(pg_engine*);
 /* run on a caller-provided hipStream_t (NULL = the engine's own stream) */
-int pg_engine_set_stream(pg_engine*, void* hip_stream);
-int pg_engine_synchronize(pg_engine*);
-int pg_engine_device(const pg_engine*);
+PG_API int pg_engine_set_stream(pg_engine*, void* hip_stream);
+PG_API int pg_engine_synchronize(pg_engine*);
+PG_API int pg_engine_device(const pg_engine*);
 /* Multi-GPU jobs (contiguous blocks of chains / MSAs per GPU): the number of batch items (chains, MSAs) of the
  * WHOLE job this engine's calls are a shard of; 0 (default) = every call is a whole job.  Kernel choices that change the
  * order of a floating-point sum (K-split GEMMs and the weight-streaming GEMM of the few-chain regime, the row-split form of
  * the tied row attention) are then taken on the job's size instead of the shard's, so that every shard computes bit for bit
  * what a single engine computes on the whole batch (jobs with more than 2048 token rows; smaller jobs run in the few-chain
  * regime whose kernels are picked by the local shape).  No effect on results of a call that is a whole job. */
-int pg_engine_set_job_items(pg_engine*, int64_t job_items);
+PG_API int pg_engine_set_job_items(pg_engine*, int64_t job_items);
 /* engine counters: "graph_captures" / "graph_replays" = hipGraph captures and replayed iterations of the launch-bound
  * (few-token) Gibbs loop, which replays ONE captured iteration for every call of the same shape (tests assert the path taken) */
-int pg_engine_get_stat(pg_engine*, const char* name, int64_t* value);
+PG_API int pg_engine_get_stat(pg_engine*, const char* name, int64_t* value);
 
 /* Sampling parameters == the kwargs of generate() that reach generate_step
  * (src/pgen/esm_sampler.py:8-45, 227-232). */
@@ -222,8 +231,8 @@ typedef struct {
  *   row (sampled but not written back: keeps the reference's sequential last-write-wins result).
  *   Optional outputs (NULL to skip): sampled_logits[n_iters][B][P][V], sampled_tokens[n_iters][B][P].
  */
-int pg_esm_forward_logits(pg_engine*, const int32_t* tokens, int B, int T, float* logits_out);
-int pg_esm_gibbs_run(pg_engine*, int32_t* tokens_inout, int B, int T, const int32_t* target_idx, int n_iters, int P,
+PG_API int pg_esm_forward_logits(pg_engine*, const int32_t* tokens, int B, int T, float* logits_out);
+PG_API int pg_esm_gibbs_run(pg_engine*, int32_t* tokens_inout, int B, int T, const int32_t* target_idx, int n_iters, int P,
                      const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens);
 /* same, every pointer device-resident (tokens stay in HBM; used by bench.py and multi-GPU drivers).  Asynchronous: returns after
  * enqueueing on the engine's stream; every buffer (incl. d_target_idx) must stay valid until pg_engine_synchronize.  The tokens are
@@ -233,7 +242,7 @@ int pg_esm_gibbs_run(pg_engine*, int32_t* tokens_inout, int B, int T, const int3
  * the timeout restores the rows and runs the logged calls again on the per-layer launches (same results, one warning).
  * Consequence for the caller: between two synchronisations nothing but pg_*_device calls of this engine may write a token buffer
  * that was handed to such a call -- the replay restores the snapshot taken at the first logged call and re-runs only those. */
-int pg_esm_gibbs_run_device(pg_engine*, int32_t* d_tokens_inout, int B, int T, const int32_t* d_target_idx,
+PG_API int pg_esm_gibbs_run_device(pg_engine*, int32_t* d_tokens_inout, int B, int T, const int32_t* d_target_idx,
                             int n_iters, int P, const pg_sample_params* params, float* d_sampled_logits,
                             int32_t* d_sampled_tokens);
 
@@ -245,13 +254,13 @@ int pg_esm_gibbs_run_device(pg_engine*, int32_t* d_tokens_inout, int B, int T, c
  *   n_steps forwards; step s masks row `mask_row` and samples row `target_row` at
  *   step_idx[s][P_max] (entries < 0 = padding of the shorter partitions); sample flag per step.
  */
-int pg_msa_forward_logits(pg_engine*, const int32_t* tokens, int B, int R, int C, float* logits_out);
-int pg_msa_gibbs_run(pg_engine*, int32_t* tokens_inout, int B, int R, int C, const int32_t* target_idx, int n_iters,
+PG_API int pg_msa_forward_logits(pg_engine*, const int32_t* tokens, int B, int R, int C, float* logits_out);
+PG_API int pg_msa_gibbs_run(pg_engine*, int32_t* tokens_inout, int B, int R, int C, const int32_t* target_idx, int n_iters,
                      int P, const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens);
-int pg_msa_gibbs_run_device(pg_engine*, int32_t* d_tokens_inout, int B, int R, int C, const int32_t* d_target_idx,
+PG_API int pg_msa_gibbs_run_device(pg_engine*, int32_t* d_tokens_inout, int B, int R, int C, const int32_t* d_target_idx,
                             int n_iters, int P, const pg_sample_params* params, float* d_sampled_logits,
                             int32_t* d_sampled_tokens);
-int pg_msa_gibbs_single_run(pg_engine*, int32_t* tokens_inout, int R, int C, int mask_row, int target_row,
+PG_API int pg_msa_gibbs_single_run(pg_engine*, int32_t* tokens_inout, int R, int C, int mask_row, int target_row,
                             const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
                             const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens);
 /* pg_msa_gibbs_single_batch_run: B calls of generate_single on B MSAs ("templates") of equal shape R x C in ONE pass -- the inner
@@ -262,7 +271,7 @@ int pg_msa_gibbs_single_run(pg_engine*, int32_t* tokens_inout, int R, int C, int
  *   sampled_logits[n_steps][B][P_max][V], sampled_tokens[n_steps][B][P_max] optional.
  *   Template b's result is bit-identical with pg_msa_gibbs_single_run on it alone (kernel choices that change a summation order
  *   are taken per template), hence independent of how templates are batched or sharded over GPUs. */
-int pg_msa_gibbs_single_batch_run(pg_engine*, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
+PG_API int pg_msa_gibbs_single_batch_run(pg_engine*, int32_t* tokens_inout, int B, int R, int C, int mask_row, int target_row,
                                   const int32_t* step_idx, const int32_t* step_sample_flag, int n_steps, int P_max,
                                   const pg_sample_params* params, float* sampled_logits, int32_t* sampled_tokens);
 
@@ -274,11 +283,11 @@ int pg_msa_gibbs_single_batch_run(pg_engine*, int32_t* tokens_inout, int B, int 
  * pg_*_forward_logprobs writes nothing to `out` when it returns an error (PG_ERR_RANGE included: the results wait on the device
  * until the range check has passed).
  * pg_logprob_gather_device: the same gather on a caller's device-resident full logits[n_rows][width][V]. */
-int pg_esm_forward_logprobs(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
+PG_API int pg_esm_forward_logprobs(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
                             const int32_t* targets, int n_sel, int P, float* out);
-int pg_msa_forward_logprobs(pg_engine*, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+PG_API int pg_msa_forward_logprobs(pg_engine*, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
                             const int32_t* idx, const int32_t* targets, int n_sel, int P, float* out);
-int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
+PG_API int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
                              const int32_t* d_row_map, const int32_t* d_targets, int64_t n_sel, int P, float* d_out);
 
 /* ---- masked-marginal substitution tables -------------------------------------------------------------
@@ -300,12 +309,12 @@ int pg_logprob_gather_device(void* stream, const float* d_logits, int64_t n_rows
  * pg_logprob_table_device: the table kernel on a caller's device-resident full logits[n_rows][width][V] (plug-in models). */
 #define PG_TABLE_NORM_VOCAB 0
 #define PG_TABLE_NORM_COLUMNS 1
-int pg_logprob_table_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
+PG_API int pg_logprob_table_device(void* stream, const float* d_logits, int64_t n_rows, int width, int V, const int32_t* d_idx,
                             const int32_t* d_row_map, int64_t n_sel, int P, const int32_t* d_cols, int n_cols, int norm,
                             float* d_out /* [n_sel][P][n_cols] */, float* d_entropy /* [n_sel][P] or NULL */);
-int pg_esm_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
+PG_API int pg_esm_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* row_of, const int32_t* idx,
                                  int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out, float* entropy_or_null);
-int pg_msa_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
+PG_API int pg_msa_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int R, int C, const int32_t* row_of,
                                  const int32_t* idx, int n_sel, int P, const int32_t* cols, int n_cols, int norm, float* out,
                                  float* entropy_or_null);
 
@@ -318,9 +327,9 @@ int pg_msa_forward_logprob_table(pg_engine*, const int32_t* tokens, int B, int R
  * pg_mask_scatter_device  == mask_target_indexes      (esm_sampler.py:259-262, esm_msa_sampler.py:255-264)
  * pg_sample_writeback_device == generate_step + write (esm_sampler.py:225-234)
  */
-int pg_mask_scatter_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const int32_t* d_idx,
+PG_API int pg_mask_scatter_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const int32_t* d_idx,
                            const int32_t* d_row_map, int64_t n_sel, int P, int mask_idx);
-int pg_sample_writeback_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const float* d_logits,
+PG_API int pg_sample_writeback_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const float* d_logits,
                                int V, const int32_t* d_idx, const int32_t* d_row_map, int64_t n_sel, int P,
                                const pg_sample_params* params, int iteration, int32_t* d_sampled_tokens);
 
@@ -354,12 +363,12 @@ typedef struct {
   int n_temperatures;
   float top_p;
 } pg_draw_guide;
-int pg_engine_set_draw_guide(pg_engine*, const pg_draw_guide* guide_or_null);
+PG_API int pg_engine_set_draw_guide(pg_engine*, const pg_draw_guide* guide_or_null);
 /* pg_sample_writeback_device with a guide whose tables are DEVICE pointers (plug-in models): d_bias [bias_rows][width][n_valid of params]
  * or NULL, bias_rows 1 or n_rows; d_temperatures [n_temperatures] or NULL, read at `iteration`, which must be < n_temperatures; top_p NaN =
  * off, else in (0, 1].  It cannot check what the tables hold: the caller guarantees bias entries finite or -inf with one > -inf per
  * (row, position), and temperatures finite and > 0 (a cell with nothing allowed yields its first entry; nothing is read out of bounds). */
-int pg_sample_writeback_guided_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const float* d_logits, int V,
+PG_API int pg_sample_writeback_guided_device(void* stream, int32_t* d_tokens, int64_t n_rows, int width, const float* d_logits, int V,
                                       const int32_t* d_idx, const int32_t* d_row_map, int64_t n_sel, int P,
                                       const pg_sample_params* params, int iteration, int32_t* d_sampled_tokens, const float* d_bias,
                                       int64_t bias_rows, const float* d_temperatures, int n_temperatures, float top_p);
@@ -379,12 +388,12 @@ int pg_sample_writeback_guided_device(void* stream, int32_t* d_tokens, int64_t n
  *                       the host.  Order it after the engine's work (pg_engine_synchronize, or pass the engine's stream). */
 #define PG_COMM_ID_BYTES 128
 typedef struct pg_comm pg_comm;
-int pg_comm_unique_id(void* id_out);
-int pg_comm_create(int rank, int world, const void* unique_id, int device_ordinal, pg_comm** out);
-void pg_comm_destroy(pg_comm*);
-int pg_comm_rank(const pg_comm*);
-int pg_comm_world(const pg_comm*);
-int pg_gather_tokens(pg_comm*, void* hip_stream, const int32_t* d_local, int64_t rows, int width, const int64_t* counts,
+PG_API int pg_comm_unique_id(void* id_out);
+PG_API int pg_comm_create(int rank, int world, const void* unique_id, int device_ordinal, pg_comm** out);
+PG_API void pg_comm_destroy(pg_comm*);
+PG_API int pg_comm_rank(const pg_comm*);
+PG_API int pg_comm_world(const pg_comm*);
+PG_API int pg_gather_tokens(pg_comm*, void* hip_stream, const int32_t* d_local, int64_t rows, int width, const int64_t* counts,
                      int32_t* d_out);
 /* Rehearsal of pg_gather_tokens without GPUs (tests only): the SAME bookkeeping -- which form, block size, scratch layout, per-rank
  * pack offsets -- on HOST buffers, with the all-gather injected by the caller: allgather(ctx, send, recv, n) must fill recv with
@@ -393,22 +402,22 @@ int pg_gather_tokens(pg_comm*, void* hip_stream, const int32_t* d_local, int64_t
  * the plan itself: out7 = {equal form?, nothing to move?, rows of a padded block, bytes per row, bytes per block, scratch bytes,
  * bytes of the gathered output}, out_off_bytes[world] = byte offset of every rank's rows in the output (may be NULL). */
 typedef int (*pg_allgather_fn)(void* ctx, const void* send, void* recv, size_t n_int32);
-int pg_dbg_gather_tokens_host(int rank, int world, const int32_t* local, int64_t rows, int width, const int64_t* counts,
+PG_API int pg_dbg_gather_tokens_host(int rank, int world, const int32_t* local, int64_t rows, int width, const int64_t* counts,
                               int force_padded, pg_allgather_fn allgather, void* ctx, int32_t* out);
-int pg_dbg_gather_plan(int rank, int world, int64_t rows, int width, const int64_t* counts, int force_padded, int64_t* out7,
+PG_API int pg_dbg_gather_plan(int rank, int world, int64_t rows, int width, const int64_t* counts, int force_padded, int64_t* out7,
                        int64_t* out_off_bytes);
 
 /* ---- measurement ---------------------------------------------------------------------------
  * HIP-event timing of kernel classes on the engine's stream (bench.py's roofline figure).
  * class names: "gemm", "attention", "layernorm", "embed", "head", "sample", and "rope": ESM-2's rotation of q and k, timed under
  * its own class (not under "attention"; no launch of the other architectures falls into it).  */
-int pg_prof_enable(pg_engine*, int on);
-int pg_prof_reset(pg_engine*);
-int pg_prof_get(pg_engine*, const char* kernel_class, double* total_ms, int64_t* launches);
+PG_API int pg_prof_enable(pg_engine*, int on);
+PG_API int pg_prof_reset(pg_engine*);
+PG_API int pg_prof_get(pg_engine*, const char* kernel_class, double* total_ms, int64_t* launches);
 /* the kernels the GEMM dispatch picked for the profiled launches of a class ("gemm_qkv", "gemm_out", "gemm_fc1", "gemm_fc2",
  * "gemm_other", "head"): distinct labels such as "pp192 220t" (220 tiles of 192 x 256) or "tile64 400t x4k" (64 x 64 tiles,
  * 4 K-splits), separated by " | ", into buf. */
-int pg_prof_get_kernels(pg_engine*, const char* kernel_class, char* buf, int buf_bytes);
+PG_API int pg_prof_get_kernels(pg_engine*, const char* kernel_class, char* buf, int buf_bytes);
 
 /* ---- kernel-level debug entry points (parity tests call individual kernels through these) --- */
 /* out[M][N] = x[M][K] @ w[N][K]^T + bias (fp32 host buffers; computed in `precision`); epi: 0 none, 1 gelu,
@@ -416,7 +425,7 @@ int pg_prof_get_kernels(pg_engine*, const char* kernel_class, char* buf, int buf
  * strict-mode projection: one GEMM over K-concatenated split-bf16 operands) takes epi 0, 2 and 5 = fc1's fused epilogue
  * (GELU, then the split operand rows fc2 reads; N a multiple of 256; out = hi + lo of those rows); PG_PREC_F16 = the bf16
  * path's kernels with fp16 operands (epi 0-4) */
-int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N,
+PG_API int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N,
                 int K, int epi);
 /* pg_dbg_gemm with the kernel named and reported (pg_dbg_gemm is this with variant -1, have_ws -1, m_live M, no plan).
  * variant: -1 = the process's dispatch (launch_gemm_bf16, PGIBBS_GEMM), else one of the variants of pg_dbg_gemm_bench that compute a
@@ -426,7 +435,7 @@ int pg_dbg_gemm(int device, int precision, const float* x, const float* w, const
  * dispatch takes it for the residual epilogue only), -1 = on offer to the residual epilogue.  m_live: rows that hold tokens, 0 = all.
  * plan (NULL: not wanted): the text the GEMM launch alone recorded, as pg_dbg_gemm_plan words it; the strict mode's fused kernel
  * records "gemm_split3_w16 <tiles>t".  All refusals precede the device lookup; a shape the dispatch refuses is the launcher's error. */
-int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N, int K, int epi,
+PG_API int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, const float* bias, float* out, int M, int N, int K, int epi,
                   int variant, int have_ws, int m_live, char* plan, int plan_bytes);
 /* The single-chain GEMM that computes the preceding LayerNorm in its operand load (gemm_ln_skinny_kernel), alone:
  * out = LayerNorm(x; gamma, beta, eps) . w^T + bias, through GELU when gelu = 1, in the 16-bit type of `precision` (PG_PREC_BF16 or
@@ -437,17 +446,17 @@ int pg_dbg_gemm_v(int device, int precision, const float* x, const float* w, con
  * not write keeps the caller's (16-bit representable) pattern.  nb: 16-feature blocks per workgroup, 1 or 2 (2: N a multiple of 32),
  * 0 = the launcher's choice (PGIBBS_LN_SKINNY_NB, else 2 when N / 16 exceeds the CU count).  plan (NULL: not wanted): the text the
  * launch recorded, "ln+skinny8w <N / (16 nb)>t".  All refusals are PG_ERR_INVALID and precede the device lookup. */
-int pg_dbg_gemm_ln(int device, int precision, const float* x, const float* x_pad, const float* gamma, const float* beta, float eps,
+PG_API int pg_dbg_gemm_ln(int device, int precision, const float* x, const float* x_pad, const float* gamma, const float* beta, float eps,
                    const float* w, const float* bias, float* out, int out_rows, int M, int N, int K, int gelu, int nb, char* plan,
                    int plan_bytes);
 /* times `iters` back-to-back launches of the GEMM on device-resident random bf16 operands (HIP events; M a multiple of 16,
  * of 64 above 256); variant 1 =
  * lockstep kernel, 2 = ping-pong kernel; epi: 0 bf16 out, 1 bf16+gelu, 2 fp32 residual, 3 fp32, 4 fp32+gelu */
-int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int iters, double* avg_ms);
+PG_API int pg_dbg_gemm_bench(int device, int M, int N, int K, int epi, int variant, int iters, double* avg_ms);
 /* which kernel the GEMM dispatch picks for a shape on a device of n_cu compute units, as the text pg_prof_get_kernels reports for
  * that launch ("pp192x256 250t + tail64 40t", "skinny8w 80t x4k"; empty for an ablation variant; "error: ..." for a refused shape).
  * have_ws: split-K scratch is on offer (residual GEMMs of an engine); m_live: rows that hold tokens, 0 = all.  Touches no device. */
-int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int m_live, int n_cu, char* buf, int buf_bytes);
+PG_API int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int m_live, int n_cu, char* buf, int buf_bytes);
 /* which kernel template an attention launcher picks for a shape, and on which grid, as the text pg_prof_get_kernels reports for that
  * launch under "attention" ("whole kb18 hd64 split4 512+512wg", "split-f32 kb6 nqb5 hd64 5120wg", "row kb18 w9 rc1 2560wg"; "error:
  * ..." for a shape the launcher refuses).  kind 0: full attention over n_seq sequences of T tokens (row_step 1: contiguous chains;
@@ -455,54 +464,50 @@ int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_ws, int
  * tied row attention of B alignments of R rows x C columns (head_dim, has_bias, row_step unused; order_bh: the (msa, head) count the
  * split of the row loop is decided on, 0 = B * H).  precision PG_PREC_FP32: the strict launchers, else the 16-bit ones (both operand
  * flavours share one plan).  A sequence length or column count < 1 is answered by the launcher's own refusal.  Touches no device. */
-int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_C, int R, int H, int head_dim, int has_pad, int has_bias,
+PG_API int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_C, int R, int H, int head_dim, int has_pad, int has_bias,
                           int row_step, int order_bh, int n_cu, char* buf, int buf_bytes);
-/* round 6: gemm_rowln.hip (out-projection of d_model = 768 with the next LayerNorm in its epilogue) against the two launches it
- * replaces: ms[0] fused, ms[1] its main loop alone, ms[2] four half-steps + epilogue, ms[3] residual GEMM (256-column tiles),
- * ms[4] LayerNorm kernel; max_diff 0 = x and h bit-identical between the two paths. */
-int pg_dbg_rowln_bench(int device, int M, int K, int iters, double* ms, double* max_diff);
 /* round-5 ablation: QKV projection + attention of B sequences of T in {32, 64, 128, 256} tokens as ONE launch (the fused
  * projection-attention kernel of the MSA column block, one head per 256 x 192 tile) against the two launches of the ESM-1b path;
  * ms[0] fused, ms[1] projection, ms[2] attention (HIP events, `iters` launches each); max_diff = max |fused - unfused| context */
-int pg_dbg_qkv_attention_bench(int device, int B, int T, int H, int iters, double* ms, double* max_diff);
+PG_API int pg_dbg_qkv_attention_bench(int device, int B, int T, int H, int iters, double* ms, double* max_diff);
 /* y = LayerNorm(x[M][d]) * gamma + beta */
-int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
+PG_API int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
                      float eps);
 /* the same LayerNorm as the GEMMs read it (d a multiple of 32, <= 2560, or a multiple of 512 up to 5120): the operand rows written in `precision` and widened to fp32
  * -- bf16 (PG_PREC_BF16) or fp16 (PG_PREC_F16) rows, or the strict mode's split rows (PG_PREC_FP32) returned as hi + lo */
-int pg_dbg_layernorm_operand(int device, int precision, const float* x, const float* gamma, const float* beta, float* y, int M,
+PG_API int pg_dbg_layernorm_operand(int device, int precision, const float* x, const float* gamma, const float* beta, float* y, int M,
                              int d, float eps);
 /* softmax(q k^T) v per (b, h); q already scaled; qkv[B][T][3*H*64] fp32 -> ctx[B][T][H*64]; PG_PREC_BF16 or PG_PREC_FP32
  * (split-bf16 MFMA kernel, output = hi + lo of the operand rows it writes) or PG_PREC_F16 (the bf16 kernel with fp16 operands) */
-int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, int B, int T, int H);
+PG_API int pg_dbg_attention(int device, int precision, const float* qkv, float* ctx, int B, int T, int H);
 /* ESM-2's rotary embedding: the q and k thirds of qkv_inout[B*T][3*H*64] (fp32 host buffer) rotated in place, row r at position
  * r % T, in `precision` (16-bit modes: through a device buffer of that type, the result widened back); the v third is left alone */
-int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H);      /* H <= 40 */
+PG_API int pg_dbg_rope(int device, int precision, float* qkv_inout, int B, int T, int H);      /* H <= 40 */
 /* the same two with the head dimension as an argument: head_dim 64 (what pg_dbg_attention / pg_dbg_rope run), 32 (ESM-2 150M;
  * pg_dbg_rope_hd: H <= 32), 128 (ESM-2 15B; pg_dbg_rope_hd: H <= 40) or 16 (ESM-2 8M; pg_dbg_rope_hd: H <= 32), buffers [..][3*H*head_dim] and [..][H*head_dim].  key_tok (NULL: none): int32 tokens [B][T] of the keys;
  * a key whose token equals pad_idx is masked, as the <pad> keys of a ragged batch are */
-int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+PG_API int pg_dbg_attention_hd(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
                         const int32_t* key_tok, int pad_idx);
-int pg_dbg_rope_hd(int device, int precision, float* qkv_inout, int B, int T, int H, int head_dim);
+PG_API int pg_dbg_rope_hd(int device, int precision, float* qkv_inout, int B, int T, int H, int head_dim);
 /* pg_dbg_attention_hd with ESM-1's bias key (add_bias_kv): bias_k / bias_v [H][head_dim] fp32, both or neither -- one more key behind
  * the T token keys, attended by every query, never masked.  The entry lays the two out as the engine does ([bias_k | bias_v], k of
  * head h at h*head_dim, v at (H + h)*head_dim), in the 16-bit type of `precision` or fp32 for PG_PREC_FP32.  Every argument is checked
  * on the host before a device is looked for (null / non-null pairs, the head dimension, the bias key at head 32 -- the plan's own
  * refusal text --, sizes): PG_ERR_INVALID with a message, never a launch.  plan (NULL: not wanted): receives the text the launch
  * recorded, as pg_dbg_attention_plan words it.  The two entries above are calls of this one */
-int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
+PG_API int pg_dbg_attention_kv(int device, int precision, const float* qkv, float* ctx, int B, int T, int H, int head_dim,
                         const int32_t* key_tok, int pad_idx, const float* bias_k, const float* bias_v, char* plan, int plan_bytes);
 
 /* MSA attention blocks: qkv[B][R][C][3*H*64] fp32 -> ctx[B][R][C][H*64]; which = 0 tied row attention (scores * scale),
  * 1 column attention (q pre-scaled); 2 / 3 = the same two with the strict precision mode's kernels; 4 / 5 = 0 / 1 with fp16
  * operands */
-int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale);
+PG_API int pg_dbg_msa_attention(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale);
 /* the same with the tokens tok[B][R][C] of a batch that holds <pad> (NULL: none; pg_dbg_msa_attention is a call of this).  Column
  * attention (which 1, 3, 5): the key rows that are pad_idx at a column get fair-esm's fill of -10000.  Tied row attention with tokens
  * takes the engine's route for a ragged batch: which 0 widens the 16-bit q, k, v to fp32 and runs the fp32-scores kernels with 16-bit
  * context rows, which 2 is the strict mode, which 4 (fp16) is refused with the engine's message (PG_ERR_UNSUPPORTED).  Arguments are
  * checked on the host before a device is looked for.  plan (NULL: not wanted): the text the launches recorded */
-int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale,
+PG_API int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx, int B, int R, int C, int H, float scale,
                              const int32_t* tok, int pad_idx, char* plan, int plan_bytes);
 
 
@@ -515,36 +520,36 @@ int pg_dbg_msa_attention_tok(int device, int which, const float* qkv, float* ctx
  * pos_rows rows; msa_pos (rows_per_msa > 0) has rows_per_msa rows; gamma / beta (both or neither): emb_layer_norm_before; gamma2 /
  * beta2 / h2 (all or none): the first layer's LayerNorm of x as operand rows h2[n_seq*T][d]; h2 is _inout like the other 16-bit row
  * buffers: copied to the device before the launch (the kernel writes every row of it) */
-int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
+PG_API int pg_dbg_embed(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d, const float* pos,
                  int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta, const float* gamma2,
                  const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale, float* x, uint16_t* h2);
 /* launch_layernorm_bf16 on x[M][d]: form 0 = plain rows of d values, 1 = the strict mode's split rows of 3 d values (per 32 columns
  * [lo | hi | hi]; bf16 only), 2 = the same without the duplicate block; colmajor_R / colmajor_C > 0: token row (b*R + r)*C + c is
  * written as row (b*C + c)*R + r (form 0, d <= 2048, M a multiple of R*C).  h_inout holds h_rows >= M rows.  *kernel (may be NULL):
  * the kernel the launcher chose -- 0 plain, 1 the stride kernel (d = 1280 / 768, ~8 k .. 33 k rows, PGIBBS_LN_STRIDE), 2 column-major */
-int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+PG_API int pg_dbg_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
                           int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel);
 /* gather_ln_bf16_kernel: selected row r = LayerNorm of token row row_of(r / P) * width + (idx[r] & 0x3fffffff) of x[x_rows][d], zeros
  * when idx[r] < 0 or the position is >= width; row_of = row_map[n_map] (NULL: the identity); idx == NULL: selected row r = token row r.
  * split: 1 = [lo | hi | hi] rows (bf16).  h_inout holds h_rows >= n_sel rows */
-int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+PG_API int pg_dbg_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
                      int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
                      float eps, int split);
 /* gather_rows_kernel: dst[r] = src[row_of(r / P) * width + pos] for rows of row_bytes (a multiple of 16) bytes; pos = idx[r] without
  * bit 30, 0 when that is negative or >= width.  n_iters = 0: idx[n_sel]; n_iters > 0: idx[n_iters][n_sel] and the kernel reads row
  * `iter` of it through a device-side iteration counter.  dst_inout holds dst_rows >= n_sel rows */
-int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
+PG_API int pg_dbg_gather_rows(int device, const void* src, int64_t src_rows, void* dst_inout, int64_t dst_rows, const int32_t* idx, int n_iters,
                        int iter, const int32_t* row_map, int64_t n_map, int P, int width, int64_t n_sel, int row_bytes);
 /* launch_split3_bf16 on x[rows][K] fp32 (K a multiple of 32): the strict mode's split operand rows of scale * x, 3 K bf16 words per row
  * (csrc/split_operand.h), into h_inout[h_rows >= rows][3 K].  form = weight (1) + through GELU (2): 0 an activation row [lo | hi | hi]
  * per 32 columns, 1 a weight row [hi | lo | hi], 2 an activation row of erf-GELU(x), which takes scale 1 and also returns
  * gelu_out[rows][K] = launch_gelu_f32 of the same x; 3 (GELU on a weight) and every other value are refused.  All refusals are
  * PG_ERR_INVALID on the host, before a device is looked for */
-int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_rows, int rows, int K, float scale, int form,
+PG_API int pg_dbg_split_rows(int device, const float* x, uint16_t* h_inout, int64_t h_rows, int rows, int K, float scale, int form,
                       float* gelu_out);
 /* launch_lm_tail: logits[n][V] = LayerNorm(g[n][d]; gamma, beta) . embed[V][d]^T + out_bias (gamma == beta == NULL: no LayerNorm,
  * ESM-1); V <= 64.  *small_kernel (may be NULL): 1 = the workgroup-per-row kernel ran (n <= PGIBBS_LM_TAIL_SMALL, default 1024) */
-int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+PG_API int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
                    float* logits, int64_t n, int d, int V, float eps, int* small_kernel);
 
 /* ---- the draw and the mask scatter (csrc/sample.hip), in every form the engine launches ----
@@ -570,7 +575,7 @@ int pg_dbg_lm_tail(int device, const float* g, const float* gamma, const float* 
  * 0 / 1, masked_tokens_out without a mask step, n_tables < first_iter + n_steps, n_valid outside 1..32, a valid_idx outside 0..V-1, an
  * array of more than 2^31 - 1 values, n_sel > n_rows without a row_map, a row_map entry outside 0..n_rows-1, and (without the permit)
  * a position & 0x3fffffff >= width in any table. */
-int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact, const int32_t* idx,
+PG_API int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact, const int32_t* idx,
                   int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params, int first_iter, int n_steps,
                   int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out, int32_t* masked_tokens_out,
                   unsigned* nonfinite_out);
@@ -579,37 +584,37 @@ int pg_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, 
  * n_temperatures >= first_iter + n_steps; a per-row bias table has n_rows rows.  With device_iter 1 the iteration AND the guide's device
  * pointers are read from the state block.  Refusals: pg_dbg_sample's, then the guide's set-time and run-time ones, all on the host
  * before a device is looked for.  pg_guided_sizeof_draw_guide: sizeof(pg_draw_guide), for bindings that mirror the struct. */
-int pg_guided_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact,
+PG_API int pg_guided_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int width, const float* logits, int V, int compact,
                          const int32_t* idx, int n_tables, const int32_t* row_map, int64_t n_sel, int P, const pg_sample_params* params,
                          int first_iter, int n_steps, int device_iter, int mask_idx, int permit_out_of_range, int32_t* sampled_out,
                          int32_t* masked_tokens_out, unsigned* nonfinite_out, const pg_draw_guide* guide);
-int pg_guided_sizeof_draw_guide(void);
+PG_API int pg_guided_sizeof_draw_guide(void);
 
 /* ---- the live-width forms of pg_dbg_embed, pg_dbg_layernorm_rows, pg_dbg_gather_ln and pg_dbg_lm_tail (an embedded model's rows) ----
  * Every table, row and vector is d wide in memory; its first d_live features (a multiple of 4, at most d) are the model's own.
  * Statistics, affine and the decoder's dot products run over d_live features -- on them, bit for bit what the same entry gives for
  * rows of d = d_live -- and the d - d_live pad features of every 16-bit output row are written as zeros, in the split forms too.
  * d_live = d is the entry above; each entry names itself in its error messages.  No live form: emb_layer_norm_before (gamma / beta of pg_dbg_embed), column-major rows, the stride kernel */
-int pg_embedded_embed_rows(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d,
+PG_API int pg_embedded_embed_rows(int device, int precision, const int32_t* tokens, int n_seq, int T, const float* embed, int V, int d,
                            const float* pos, int pos_rows, const float* msa_pos, int rows_per_msa, const float* gamma, const float* beta,
                            const float* gamma2, const float* beta2, int pad_idx, int mask_idx, int token_dropout, float eps, float embed_scale,
                            float* x, uint16_t* h2, int d_live);
-int pg_embedded_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
+PG_API int pg_embedded_layernorm_rows(int device, int precision, const float* x, const float* gamma, const float* beta, uint16_t* h_inout,
                                int64_t h_rows, int M, int d, float eps, int form, int colmajor_R, int colmajor_C, int* kernel, int d_live);
-int pg_embedded_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
+PG_API int pg_embedded_gather_ln(int device, int precision, const float* x, int64_t x_rows, const int32_t* idx, const int32_t* row_map, int64_t n_map,
                           int P, int width, const float* gamma, const float* beta, uint16_t* h_inout, int64_t h_rows, int64_t n_sel, int d,
                           float eps, int split, int d_live);
-int pg_embedded_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
+PG_API int pg_embedded_lm_tail(int device, const float* g, const float* gamma, const float* beta, const float* embed, const float* out_bias,
                         float* logits, int64_t n, int d, int V, float eps, int* small_kernel, int d_live);
 /* Host only (no device is looked for): the run-shape image pg_engine_create_embedded uploads for the natural tensor `name` (its role is
  * read from the fair-esm key: embed_tokens.weight, layers.i.self_attn.{q,k,v,out}_proj.*, layers.i.fc1.* / fc2.*, every *layer_norm*,
  * lm_head.dense.*, lm_head.bias) of a model of n_heads heads of head_width in slots of head_slot: live values at their run positions,
  * 0.0 everywhere else.  numel / image_numel must be the natural and the run size */
-int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
+PG_API int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
                       float* image, int64_t image_numel);
 /* Host only: the rotary table [rows][head_slot] of such an engine: row t = [cos(t f_i), i < head_width / 2, then 1 ... | sin(t f_i),
  * then 0 ...], f_i = 10000^(-2i / head_width) as fp32 (head_width == head_slot: the table of a built width) */
-int pg_embedded_rope_table(int rows, int head_width, int head_slot, float* table);
+PG_API int pg_embedded_rope_table(int rows, int head_width, int head_slot, float* table);
 
 #ifdef __cplusplus
 }

@@ -322,60 +322,6 @@ int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_
   return PG_OK;
 }
 
-// round 6: the full-row out-projection + LayerNorm kernel (gemm_rowln.hip) against the two launches it replaces, on synthetic operands
-// of d_model = 768: ms[0] fused kernel, ms[1] its main loop alone, ms[2] four half-steps + its epilogue, ms[3] residual GEMM on
-// 256-column tiles (default dispatch), ms[4] LayerNorm kernel; max_diff = max |h fused - h unfused| over the 16-bit rows (0: bit-identical).
-int pg_dbg_rowln_bench(int device, int M, int K, int iters, double* ms, double* max_diff) {
-  if (!ms || M < 256 || K % 64 || K < 128 || iters < 1) return fail(PG_ERR_INVALID, "pg_dbg_rowln_bench: bad argument");
-  Dbg d;
-  int rc = d.open(device);
-  if (rc) return rc;
-  const int N = 768, Mp = round_up(M, kRowPad);
-  const size_t n_f = (size_t)std::max(Mp, N) * std::max(K, N);
-  const std::vector<float> hbuf = lcg_uniform(n_f + 5, 4242u);      // + 5: x0 below starts at value 5 and can be as long as f
-  const float* f = d.up(hbuf.data(), n_f);
-  bf16_t* ba = d.alloc<bf16_t>((size_t)Mp * K);
-  bf16_t* bw = d.alloc<bf16_t>((size_t)N * K);
-  const float* db = d.up(hbuf.data() + 31, (size_t)N * 3);      // bias | gamma | beta
-  const float* x0 = d.up(hbuf.data() + 5, (size_t)Mp * N);
-  float* x1 = d.alloc<float>((size_t)Mp * N);
-  float* x2 = d.alloc<float>((size_t)Mp * N);
-  bf16_t* h1 = d.alloc<bf16_t>((size_t)Mp * N);
-  bf16_t* h2 = d.alloc<bf16_t>((size_t)Mp * N);
-  if ((rc = d.check())) return rc;
-  if ((rc = to16(PG_PREC_BF16, f, ba, (int64_t)Mp * K))) return rc;
-  if ((rc = to16(PG_PREC_BF16, f + 977, bw, (int64_t)N * K, 0.05f))) return rc;
-  const float *gam = db + N, *bet = db + 2 * N;
-  // correctness first: one application of each path to the same x
-  PG_HIP(hipMemcpy(x1, x0, (size_t)Mp * N * 4, hipMemcpyDeviceToDevice));
-  PG_HIP(hipMemcpy(x2, x0, (size_t)Mp * N * 4, hipMemcpyDeviceToDevice));
-  auto fused = [&](int ablation) { return launch_gemm_rowln(nullptr, ba, bw, db, x1, gam, bet, h1, M, Mp, K, K, K, 1e-5f, 0, 0, ablation); };
-  auto resid = [&] { return launch_gemm_bf16(nullptr, ba, bw, db, x2, Mp, N, K, K, K, N, EPI_F32_RESID, nullptr, 0, M); };
-  auto norm = [&] { return launch_layernorm_bf16(nullptr, x2, gam, bet, h2, M, N, 1e-5f); };
-  if ((rc = fused(0)) || (rc = resid()) || (rc = norm())) return rc;
-  PG_HIP(hipDeviceSynchronize());
-  if (max_diff) {
-    std::vector<bf16_t> c1((size_t)M * N), c2((size_t)M * N);
-    std::vector<float> y1((size_t)M * N), y2((size_t)M * N);
-    if ((rc = d.down(c1.data(), h1, c1.size())) || (rc = d.down(c2.data(), h2, c2.size()))) return rc;
-    if ((rc = d.down(y1.data(), x1, y1.size())) || (rc = d.down(y2.data(), x2, y2.size()))) return rc;
-    double md = 0;
-    for (size_t i = 0; i < c1.size(); ++i) {
-      if (c1[i] != c2[i]) md = std::max(md, 1.0 + std::fabs((double)bf16_to_f32(c1[i]) - (double)bf16_to_f32(c2[i])));
-      if (memcmp(&y1[i], &y2[i], 4)) md = std::max(md, 2.0 + std::fabs((double)y1[i] - (double)y2[i]));
-    }
-    *max_diff = md;
-  }
-  for (int i = 0; i < 3; ++i)
-    if ((rc = time_launches([&] { return fused(i); }, iters, ms + i))) return rc;
-  if (const char* e = getenv("PGIBBS_ROWLN_BENCH_ABL")) {      // timing ablation of the epilogue in place of ms[2]
-    const int abl = atoi(e);
-    if ((rc = time_launches([&] { return fused(abl); }, iters, ms + 2))) return rc;
-  }
-  if ((rc = time_launches(resid, iters, ms + 3))) return rc;
-  return time_launches(norm, iters, ms + 4);
-}
-
 // round 5 ablation ("QKV projection fused with attention for ESM-1b"): the fused kernel that exists --
 // gemm_colattn_kernel<16> with one "column" per chain IS projection + attention of whole sequences of T = 256 tokens, one head per
 // 256 x 192 tile, the fusion's best case (16 query blocks on 16 waves, no 17th block, no padded rows) -- against the two launches it

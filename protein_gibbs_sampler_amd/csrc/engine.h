@@ -241,9 +241,8 @@ struct Engine {
   // order: the architecture (msa: the call came through a pg_msa_* entry or method; else a pg_esm_* one, R = 1), B >= 0 and R, C >= 1,
   // R within msa_position_embedding, C within the position table, then the call's two counts (P / n_iters, P_max / n_steps,
   // n_sel / P) >= 0 and its two row indices (generate_single's mask_row / target_row) within R.  The one such check: every C entry
-  // that takes tokens makes it before anything is allocated or copied, and so do the *_device methods below.  (Hidden: the library's
-  // dynamic symbol table stays what it was before this function existed)
-  __attribute__((visibility("hidden"))) int check_call(bool msa, int B, int R, int C, int count0 = 0, int count1 = 0, int row0 = 0, int row1 = 0) const;
+  // that takes tokens makes it before anything is allocated or copied, and so do the *_device methods below.
+  int check_call(bool msa, int B, int R, int C, int count0 = 0, int count1 = 0, int row0 = 0, int row1 = 0) const;
   // A per-row bias table of the draw guide is indexed by the token row of the WHOLE call: while this lives, a call on a block of its
   // alignments (generate_single batches) that begins at token row row0 reads its own rows of the table
   struct GuideRowShift {

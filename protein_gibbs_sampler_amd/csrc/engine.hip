@@ -809,16 +809,10 @@ int Engine::chain_forward(int B, int T, int Mi, bool stop_at_last_attention, Cha
 
 // x[M_rows][d] += a[M_rows][K] W^T + b, then h = LayerNorm(x; ln) as the next GEMM's bf16 operand: the residual GEMM the dispatch
 // picks, followed by the LayerNorm kernel at its HBM roofline.  (Normalising inside the GEMM was built in round 3, bit-identical
-// and slower; it left the library in round 4: tools/probes/gemm_ln_fused.hip.)
+// and slower; it left the library in round 4: tools/probes/gemm_ln_fused.hip.  So was round 6's tile of whole 768-wide rows with the
+// LayerNorm in its epilogue: 1.34-1.37 ms per launch against 1.26-1.28 ms for these two launches, EXPERIMENTS.md.)
 int Engine::resid_gemm_ln(int cls, const bf16_t* a, const DenseW& W, float* x, int M_rows, int64_t M_real, const LnW& ln, bf16_t* h,
                           bool use_splitk, int colmajor_R, int colmajor_C) {
-  const int d = W.N, K = W.K;
-  // d_model = 768, K <= 1024 (ESM-MSA-1b's attention out-projections) on big batches: one launch whose tiles span whole rows and
-  // normalise them in the epilogue (gemm_rowln.hip; same bits as the two launches below).  Opt-in through PGIBBS_ROWLN=1
-  // (gemm_rowln_ok): measured slower, 1.34-1.37 ms per launch against 1.26-1.28 ms for the two launches it replaces
-  static const int64_t rowln_min = env_int("PGIBBS_ROWLN_MIN_ROWS", 16384);
-  if (!strict() && !embedded() && M_real >= rowln_min && M_real <= M_rows && OPS(gemm_rowln_ok, M_rows, d, K))
-    return timed(cls, [&] { return OPS(launch_gemm_rowln, stream, a, W.w, W.b, x, ln.g, ln.b, h, (int)M_real, M_rows, K, K, K, cfg.layer_norm_eps, colmajor_R, colmajor_C); });
   const int rc = dense(cls, a, W, x, M_rows, EPI_F32_RESID, (int)M_real, use_splitk);
   return rc ? rc : layer_norm(x, ln, h, M_real, true, colmajor_R, colmajor_C);
 }

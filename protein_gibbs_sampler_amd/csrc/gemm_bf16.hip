@@ -211,7 +211,7 @@ __device__ __forceinline__ void epilogue_resid(f32x4 (&acc)[4][XJ], char* smem, 
   }
 }
 
-template <int EPI, bool NO_STORE = false>
+template <int EPI>
 __device__ __forceinline__ void epilogue_256(f32x4 (&acc)[4][8], char* smem, int wm, int wn, int wave, int lane, int m0,
                                              int n0, const float* __restrict__ bias, void* __restrict__ out, int ldo) {
   const int fr = lane & 15, fq = lane >> 4;
@@ -300,7 +300,6 @@ __device__ __forceinline__ void epilogue_256(f32x4 (&acc)[4][8], char* smem, int
     for (int it = 0; it < 16; ++it) {
       const int row = (wave * 16 + it) * 2 + (lane >> 5);
       const uint4 v = *(const uint4*)(smem + row * 512 + ((c ^ (row & 31)) << 4));
-      if (NO_STORE) { asm volatile("" ::"v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w)); continue; }    // ablation: all but the global stores
       PG_NT_STORE((uint4*)((bf16_t*)out + (size_t)(m0 + row) * ldo + n0 + c * 8), v);
     }
   }
@@ -325,23 +324,19 @@ __device__ __forceinline__ void epilogue_256(f32x4 (&acc)[4][8], char* smem, int
 // 16-B chunks are XOR-swizzled in the half-K layout of gemm_tile.h (PG_HALFK_SRC_CHUNK on the DMA source address,
 // PG_HALFK_FRAG on the ds_read address) so that every ds_read_b128 lane group hits 16 distinct 16-B slots.
 // ------------------------------------------------------------------------------------------------
-// ABL (micro-benchmark ablations only): 0 = real kernel, 1 = no LDS-DMA inside the K loop (tile 0 reused),
-// 2 = no MFMA (fragments kept alive), 3 = no ds_read (fragments loaded once)
 // XJ = 16-row blocks of token rows per wave: 8 = the 256 x 256 tile; 6 = a 192 x 256 tile (residual epilogue only), chosen by
 // launch_gemm_big when 256-row tiles would leave a third of the CUs idle (165 tiles of a 32-chain shard's out-projection / fc2 on
 // 256 CUs: 220 tiles of three quarters the work instead).  Same k order per accumulator: a row's bits do not depend on the tile.
-constexpr int RS_ROUNDS = 1024;                   // rounds per XCD the pacing words cover (beyond: no pacing)
-constexpr unsigned long long RS_LIMIT = 4000;     // give up after 40 us of waiting (s_memrealtime ticks of 10 ns)
-template <int EPI, int ABL = 0, int GM = 4, int XJ = 8>
+template <int EPI, int GM = 4, int XJ = 8>
 __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                           const float* __restrict__ bias, void* __restrict__ out, int K,
                                                           int ldx, int ldw, int ldo, int tiles_n, int n_tiles, int n_tail,
-                                                          int tail_m0, unsigned* rsync) {
+                                                          int tail_m0) {
   constexpr int HALF_BYTES = 512 * 64;            // one half-buffer: (256 + 256) rows x 64 B
   __shared__ __attribute__((aligned(16))) char smem[4 * HALF_BYTES];
   // 64 x 64 tiles of the rows beyond the last full round of 256 x 256 tiles (tail_tile, gemm_tile.h), column tiles of a row block per XCD
   int rb, tn;
-  if (ABL == 0 && tail_tile<true>(n_tail, n_tiles, tiles_n, rb, tn)) {
+  if (tail_tile<true>(n_tail, tiles_n, rb, tn)) {
     gemm_tail_tile64<8, EPI>(X, W, bias, out, K, ldx, ldw, ldo, tail_m0 + rb * 64, tn * 64, smem);
     return;
   }
@@ -350,47 +345,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int grp = wave >> 2;                      // 0: leads, 1: lags by one barrier
   const int wm = grp, wn = wave & 3;              // wave tile: rows wm*(16 XJ).. of X, rows wn*64.. of W
-  static_assert(XJ == 8 || (XJ == 6 && EPI == EPI_F32_RESID && ABL == 0), "192-row tiles: residual epilogue only");
+  static_assert(XJ == 8 || (XJ == 6 && EPI == EPI_F32_RESID), "192-row tiles: residual epilogue only");
   constexpr int TM = XJ * 32;                     // token rows per tile
   constexpr int NPX = XJ / 2;                     // 16-row DMA pieces per X-staging wave and half-step (W-staging waves: 4)
 
-  int bid = n_tail > 0 ? blockIdx.x - n_tail : blockIdx.x;
-  // Round pacing (round 5; rsync != nullptr: deep-K residual GEMMs, fc2).  Workgroup b runs on XCD b % 8 and an XCD's 32 CUs take
-  // its workgroups in order, so workgroups 32r .. 32r+31 of an XCD are its "round" r: the GM x n rectangle of tiles that is meant to
-  // walk K together and share X / W k-slices through the XCD's 4 MB L2.  Only the first round does by itself -- afterwards every
-  // CU starts its next tile whenever it finishes, the rectangle's tiles drift apart by more K-steps than the L2 holds (352 KB per
-  // step, 80 steps at K = 5120) and each re-fetches its slices through the fabric: fc2 read 3.3 GB per launch against 1.2 GB for
-  // walking in step, and a lone round of 255 tiles -- launch, fill and drain included -- took 150 us where a steady-state round
-  // took 157 (profiles/r05_lockstep_rounds.txt).  With PGIBBS_GEMM_RSYNC=1 the workgroups of a round wait for each other before their
-  // first DMA (an ablation: it removes 40 % of the reads and does not pay, see round_sync_words()).  This
-  // is a scheduling hint, not a dependency: after RS_LIMIT the wait gives up (CUs taken by another process, a CU mask) and switches
-  // the pacing off for good; results cannot depend on it.
-  if (rsync && ABL == 0) {
-    if (threadIdx.x == 0 && __hip_atomic_load(rsync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-      const int xcd = bid & 7, q = bid >> 3, round = q >> 5;
-      const int per_xcd = (n_tiles >> 3) + (xcd < (n_tiles & 7) ? 1 : 0);
-      const unsigned size = (unsigned)((per_xcd - round * 32) < 32 ? (per_xcd - round * 32) : 32);
-      if (round < RS_ROUNDS && round > 0) {         // round 0 starts together anyway
-        unsigned* a = rsync + 16 + ((xcd * RS_ROUNDS + round) << 1);
-        __hip_atomic_fetch_add(a, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        bool gave_up = false;
-        while (__hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < size) {
-          __builtin_amdgcn_s_sleep(8);
-          if (__builtin_amdgcn_s_memrealtime() - t0 > RS_LIMIT) { gave_up = true; break; }
-        }
-        if (gave_up) __hip_atomic_store(rsync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // re-arm for the next launch: whoever leaves last clears both words (nobody is waiting on them any more)
-        if (__hip_atomic_fetch_add(a + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == size - 1u) {
-          __hip_atomic_store(a, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(a + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    }
-    __builtin_amdgcn_s_barrier();
-  }
-  if (ABL == 18 && (bid & 7) != 0) return;        // timing experiment: only the workgroups of XCD 0 run (1/8 of the tiles)
-  if (ABL == 19 && (bid & 7) > 1) return;         // ... XCDs 0 and 1
+  int bid = blockIdx.x - n_tail;
   bid = xcd_contiguous(bid, n_tiles);
   int tile_m, tile_n;                               // grouped rasterisation inside the XCD's range (gemm_tile.h)
   grouped_tile<GM>(bid, n_tiles, tiles_n, tile_m, tile_n);
@@ -411,7 +370,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
 
   auto stage_pieces = [&](int t, int kk, int i0, int i1) {
     char* hb = smem + ((t & 1) * 2 + kk) * HALF_BYTES + lds_piece0;
-    const bf16_t* g = gsrc + (size_t)(ABL == 17 ? 0 : t) * 64 + kk * 32;   // ABL 17: always K-tile 0 -> every DMA hits in L2
+    const bf16_t* g = gsrc + (size_t)t * 64 + kk * 32;
 #pragma unroll
     for (int i = i0; i < i1; ++i)
       __builtin_amdgcn_global_load_lds(PG_GLB_PTR(g + i * piece_stride), PG_LDS_PTR(hb + i * 1024), 16, 0, 0);
@@ -446,30 +405,22 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
   const int woff = 256 * 64 + (wn * 64) * 64 + foff;
 
   bf16x8 wf[4], xf[XJ];
-  for (int t = 0; t < (ABL == 13 ? 1 : nk); ++t) {          // ABL 13: one K-tile only -> times prologue + epilogue
-    const bool has1 = (t + 1 < nk) && ABL != 13, has2 = (t + 2 < nk) && ABL != 13;
+  for (int t = 0; t < nk; ++t) {
+    const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       // ---------------- L segment: fragments of half-step s = (t, kk) + DMA of half-step s+3 ----------------
-      constexpr bool NO_DMA = (ABL == 1 || ABL == 8 || ABL == 9 || ABL == 11), NO_DS = (ABL == 3 || ABL == 8 || ABL == 9 || ABL == 11 || ABL == 12),
-                     NO_BAR = (ABL == 9 || ABL == 11 || ABL == 12);
-      const char* hb = smem + (((NO_DMA ? 0 : (t & 1)) * 2) + kk) * HALF_BYTES;
+      const char* hb = smem + ((t & 1) * 2 + kk) * HALF_BYTES;
       const bool issue = kk == 0 ? has1 : has2;
-      if (issue && !NO_DMA) {
+      if (issue) {
         if (kk == 0) stage_half(t + 1, 1); else stage_half(t + 2, 0);
       }
-      if (!NO_DS || t == 0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) wf[i] = *(const bf16x8*)(hb + woff + i * 1024);
+      for (int i = 0; i < 4; ++i) wf[i] = *(const bf16x8*)(hb + woff + i * 1024);
 #pragma unroll
-        for (int j = 0; j < XJ; ++j) xf[j] = *(const bf16x8*)(hb + xoff + j * 1024);
-      }
+      for (int j = 0; j < XJ; ++j) xf[j] = *(const bf16x8*)(hb + xoff + j * 1024);
       // half-step s+1 must have landed before the barrier; s+2 and s+3 (4 pieces each) may stay in flight
-      if (NO_DMA) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      } else if (ABL == 15) {                                         // timing only: never wait for the DMA
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      } else if (issue) {
+      if (issue) {
         PG_PP_WAIT(2, " lgkmcnt(0)");
       } else if (kk == 1 && has1) {
         PG_PP_WAIT(1, " lgkmcnt(0)");                                 // (t+1,0) needed, (t+1,1) in flight
@@ -477,40 +428,26 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (!NO_BAR) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       // ---------------- C segment: 32 MFMAs ----------------
       __builtin_amdgcn_s_setprio(1);
-      if (ABL != 2 && ABL != 12) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < XJ; ++j)
-            acc[i][j] = mfma_op16(wf[i], xf[j], acc[i][j]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(wf[i]));
-#pragma unroll
-        for (int j = 0; j < XJ; ++j) asm volatile("" ::"v"(xf[j]));
-      }
+        for (int j = 0; j < XJ; ++j)
+          acc[i][j] = mfma_op16(wf[i], xf[j], acc[i][j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (!NO_BAR) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
     }
   }
   if (grp == 0) __builtin_amdgcn_s_barrier();      // balance the barrier count
 #undef PG_PP_WAIT
 
-  if (ABL == 10 || ABL == 11 || ABL == 12) {     // ablation: keep the accumulators alive, store nothing
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < XJ; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
   if constexpr (EPI == EPI_F32_RESID) epilogue_resid<XJ>(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
-  else epilogue_256<EPI, ABL == 16>(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
+  else epilogue_256<EPI>(acc, smem, wm, wn, wave, lane, m0, n0, bias, out, ldo);
 }
 
 // Measured alternatives that were NOT faster on MI355X and were removed again (QKV GEMM, M=66048 N=3840 K=1280, steady-state
@@ -520,7 +457,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
 //   * 1 or 2 of the 4 DMA pieces issued inside the MFMA segment: -1 % / -2 %;
 //   * half of the first round's workgroups started half a tile late (to de-phase the chip-wide store bursts): 0 ... -2 %;
 //   * a "W-stationary" tile order (4-5 n-tiles at a time over a band of 32 m-panels, so their W panels stay in the XCD's
-//     L2 while X streams): 0 ... -2 % on all four shapes, although making EVERY DMA hit in L2 (ablation 17) is worth 14 %;
+//     L2 while X streams): 0 ... -2 % on all four shapes, although making EVERY DMA hit in L2 (a timing ablation) is worth 14 %;
 //   * direct 16-B stores from the accumulators (16 rows x 64-B segments per instruction, possible with a permuted W-row
 //     to fragment assignment) instead of the LDS-staged 512-B rows: timing-only ablation 0.582 vs 0.573 ms;
 //   * touching the residual tile's cache lines at the start of the main loop (so that the read half of the epilogue's
@@ -528,89 +465,34 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(const bf16_t* __restr
 //   * a persistent kernel (one workgroup per CU; after a tile, waves 0-3 store it from 64 KB of LDS staging while waves
 //     4-7 issue the next tile's first three half-steps of DMA; the split is by wave because vmcnt counts stores too):
 //     QKV +1.2 %, fc1 +2 %, fp32-residual outputs -7 % (only 4 waves doing the read-modify-write), whole iteration +0.2 %.
-// Where the time goes (tools/gemm_bench.py variants 21-36, tools/epi_cost.py): MFMA-only loop 0.30 ms, LDS-DMA + ds_read +
+//   * round pacing (the workgroups of an XCD's round of 32 tiles wait for each other before their first DMA, so that the round walks
+//     K together and shares k-slices through the L2): fc2's fabric reads 3.67 -> 2.2 GB per launch and the launch 1 % SLOWER (756 ->
+//     763 us, ESM-MSA-1b's fc2 +3 %; profiles/r05_fc2_round_pacing.txt) -- the re-fetches are served by the Infinity Cache at no
+//     cost in time, while waiting for the slowest CU of a round is not free.
+// Where the time goes (timing instances of this kernel that the tree carried up to commit 2e0ada3: tools/gemm_bench.py variants
+// 21-36 and tools/epi_cost.py there): MFMA-only loop 0.30 ms, LDS-DMA + ds_read +
 // barriers without MFMA 0.34, both 0.47 (not DMA latency: never waiting for the DMA gives the same time; a deeper ring
 // changes nothing), prologue + one K-tile + epilogue 0.12.  The epilogue cost is the chip-wide HBM burst: it scales with
 // the bytes (bf16 0.09, fp32 0.16, fp32 read-modify-write 0.32 ms at this shape = 5.5-6.3 TB/s), a lone workgroup's
 // epilogue takes < 2 us against 6 us per tile when all 256 CUs store together.  The vendor BLAS runs the same four shapes
 // without any epilogue at 1245-1273 TFLOP/s.
-// M rows of 256 x 256 tiles (M may be 0) + tail_rows rows of 64 x 64 tail tiles starting at row M, one grid
-// the pacing words of the current device (gemm_bf16_pp_kernel: "round pacing"): [0] = switched off by a timeout, [16 + 2 i] /
-// [17 + 2 i] = arrivals / departures of (XCD, round) i; zeroed once, re-armed by the kernel itself.  nullptr: no pacing here
-// (PGIBBS_GEMM_RSYNC=0, a device that is not 8 XCDs x 32 CUs, allocation failure).
-static unsigned* round_sync_words() {
-  static unsigned* words[64];
-  static bool tried[64];
-  // OFF by default: measured round 5 (profiles/r05_fc2_round_pacing.txt) -- pacing cuts fc2's fabric reads from 3.67 to 2.2 GB per
-  // launch (FETCH_SIZE) and the launch gets 1 % SLOWER (756 -> 763 us; ESM-MSA-1b's fc2 +3 %): the re-fetches are served by the
-  // Infinity Cache at no cost in time, while waiting for the slowest CU of a round is not free.  Kept as the ablation switch.
-  static const int on = env_int("PGIBBS_GEMM_RSYNC", 0);
-  int dev = 0;
-  if (!on || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  if (!tried[dev]) {
-    tried[dev] = true;
-    hipDeviceProp_t p;
-    void* w = nullptr;
-    const size_t bytes = (size_t)(16 + 2 * 8 * RS_ROUNDS) * 4;
-    if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount == 256 && hipMalloc(&w, bytes) == hipSuccess) {
-      if (hipMemset(w, 0, bytes) == hipSuccess) words[dev] = (unsigned*)w;
-    }
-  }
-  return words[dev];
-}
-
+// M rows of 256 x 256 tiles (M may be 0) + tail_rows rows of 64 x 64 tail tiles starting at row M, one grid.
 // The dispatch that picks this kernel records it (note_plan).
 static int launch_pp(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K,
-                     int ldx, int ldw, int ldo, int epi, int abl = 0, int tail_rows = 0, int tile_rows = 256) {
+                     int ldx, int ldw, int ldo, int epi, int tail_rows = 0, int tile_rows = 256) {
   const int tiles_m = M / tile_rows, tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
-  static const int rsync_k = env_int("PGIBBS_GEMM_RSYNC_K", 4096);
-  const int n_tail_abs = (tail_rows / 64) * (N / 64), tail_m0 = M;
-  // round pacing: deep-K residual GEMMs of more than two rounds of 256-row tiles (fc2 of a big batch); the tail tiles then ride
-  // BEHIND the big ones (in front they would hold the first round's CUs back, and with them everybody who waits for that round)
-  unsigned* rsync = (epi == EPI_F32_RESID && !abl && tile_rows == 256 && K >= rsync_k && n_tiles > 2 * 256 && n_tail_abs % 8 == 0)
-                        ? round_sync_words() : nullptr;
-  const int n_tail = (gemm_tail_last() || rsync) ? -n_tail_abs : n_tail_abs;
-  dim3 grid(n_tiles + n_tail_abs), block(512);
-#define PG_PP(E, A, G, XJ) \
-  hipLaunchKernelGGL((gemm_bf16_pp_kernel<E, A, G, XJ>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0, rsync)
-  if (abl) {
-    // the ablation instances (tools/gemm_bench.py, tools/epi_cost.py: variant 20 + id, 40 + id from 60 on): id -> <EPI, ABL, GM>;
-    // the epilogue is the instance's, whatever `epi` says
-    switch (abl) {
-#define PG_PP_ABL(ID, E, A, G) case ID: PG_PP(E, A, G, 8); break;
-      PG_PP_ABL(1, EPI_BF16, 1, 4)
-      PG_PP_ABL(2, EPI_BF16, 2, 4)
-      PG_PP_ABL(3, EPI_BF16, 3, 4)
-      PG_PP_ABL(4, EPI_BF16, 0, 1)
-      PG_PP_ABL(5, EPI_BF16, 0, 8)
-      PG_PP_ABL(6, EPI_BF16, 0, 2)
-      PG_PP_ABL(7, EPI_BF16, 0, 16)
-      PG_PP_ABL(8, EPI_BF16, 8, 4)
-      PG_PP_ABL(9, EPI_BF16, 9, 4)
-      PG_PP_ABL(10, EPI_BF16, 10, 4)
-      PG_PP_ABL(11, EPI_BF16, 11, 4)
-      PG_PP_ABL(12, EPI_BF16, 12, 4)
-      PG_PP_ABL(13, EPI_BF16, 13, 4)
-      PG_PP_ABL(14, EPI_F32_RESID, 13, 4)
-      PG_PP_ABL(15, EPI_BF16, 15, 4)
-      PG_PP_ABL(16, EPI_BF16, 16, 4)
-      PG_PP_ABL(17, EPI_BF16, 17, 4)
-      PG_PP_ABL(18, EPI_BF16, 18, 4)
-      PG_PP_ABL(19, EPI_BF16, 19, 4)
-      PG_PP_ABL(28, EPI_F32_RESID, 18, 4)
-      PG_PP_ABL(29, EPI_F32_RESID, 0, 4)
-#undef PG_PP_ABL
-      default:
-        return fail(1, "gemm: unknown ablation");
-    }
-  } else if (tile_rows == 192) {      // 192 x 256 tiles: residual epilogue only (plan_big)
+  const int n_tail = (tail_rows / 64) * (N / 64), tail_m0 = M;
+  dim3 grid(n_tiles + n_tail), block(512);
+#define PG_PP(E, G, XJ) \
+  hipLaunchKernelGGL((gemm_bf16_pp_kernel<E, G, XJ>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0)
+  if (tile_rows == 192) {      // 192 x 256 tiles: residual epilogue only (plan_big)
     if (epi != EPI_F32_RESID || M % 192) return fail(1, "gemm: 192-row tiles are for the residual epilogue");
-    if (gemm_gm(GM_PP192, K) == 2) PG_PP(EPI_F32_RESID, 0, 2, 6);
-    else PG_PP(EPI_F32_RESID, 0, 4, 6);
+    if (gemm_gm(GM_PP192, K) == 2) PG_PP(EPI_F32_RESID, 2, 6);
+    else PG_PP(EPI_F32_RESID, 4, 6);
   } else {
     const int gm = gemm_gm(GM_PP256, K);        // 1, 2 or 4
     if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU>(epi, [&](auto E) {
-          return visit_int<1, 2, 4>(gm, [&](auto G) { PG_PP(decltype(E)::value, 0, decltype(G)::value, 8); });
+          return visit_int<1, 2, 4>(gm, [&](auto G) { PG_PP(decltype(E)::value, decltype(G)::value, 8); });
         }))
       return fail(1, "gemm: bad epilogue for the 8-wave tile kernel");
   }
@@ -969,17 +851,16 @@ int launch_gemm_split3(hipStream_t s, const bf16_t* X3, const bf16_t* W3, const 
 // PGIBBS_GEMM* switches, without a HIP call, so pg_dbg_gemm_plan prints its answers on a machine without a GPU
 // (tests/test_gemm_plan_cpu.py pins them for the shapes the project is measured on).  launch_plan is the one switch over it.
 // ------------------------------------------------------------------------------------------------
-enum { GEMM_INVALID, GEMM_SKINNY, GEMM_TILE64, GEMM_TILE128, GEMM_TILE256_LOCKSTEP, GEMM_PP, GEMM_W16, GEMM_LADDER };
+enum { GEMM_INVALID, GEMM_SKINNY, GEMM_TILE64, GEMM_TILE128, GEMM_TILE256_LOCKSTEP, GEMM_PP, GEMM_W16 };
 struct GemmPlan {
   int kind = GEMM_INVALID;
-  int rows = 0;                  // token rows the kernel is launched on (LADDER: the live rows its panels cover)
-  int tile_rows = 0;             // PP: 256 or 192; LADDER: the tile height
+  int rows = 0;                  // token rows the kernel is launched on
+  int tile_rows = 0;             // PP: 256 or 192
   int tail_rows = 0;             // PP, W16: rows of 64 x 64 tail tiles in the same grid, from row `rows` on
   int splits = 1;                // > 1: K-splits side by side into ws, then splitk_reduce_kernel
-  int abl = 0;                   // PP, W16: micro-benchmark ablation
   const char* error = nullptr;   // INVALID: why
 };
-static GemmPlan plan_error(const char* msg) { return {GEMM_INVALID, 0, 0, 0, 1, 0, msg}; }
+static GemmPlan plan_error(const char* msg) { return {GEMM_INVALID, 0, 0, 0, 1, msg}; }
 
 // geometry of a big-batch launch: m-panels of 256 x 256 tiles that fill whole rounds of one tile per CU + rows of 64 x 64 tail tiles
 // for the rest, when the last round would be partly empty and the tail is at most PGIBBS_GEMM_TAIL_MAX tiles per CU
@@ -1015,10 +896,6 @@ static double rounds_192(int M, int N, int n_cu) {
   const int m192 = M / 192;
   return 0.75 * (double)(((long)m192 * (N / 256) + n_cu - 1) / n_cu) + (M - m192 * 192 ? 0.2 : 0.0);
 }
-// ... the ladder's price of tiles of h rows: rounds x h / 256 (the model that does not hold, see below)
-static double rounds_ladder(int live, int h, int N, int n_cu) {
-  return (double)(((long)((live + h - 1) / h) * (N / 256) + n_cu - 1) / n_cu) * h / 256.0;
-}
 
 // The big-batch GEMM: whole rounds of 256 x 256 tiles (one per CU) plus, in the SAME grid, 64 x 64 tail tiles for the rows
 // beyond the last full round when that round would be mostly empty (gemm_epilogue.h).  Kernel per epilogue: the 16-wave kernel
@@ -1028,7 +905,6 @@ static double rounds_ladder(int live, int h, int N, int n_cu) {
 static GemmPlan plan_big(int M, int N, int K, int epi, int m_live, int n_cu) {
   static const int big = [] { const char* e = getenv("PGIBBS_GEMM_BIG"); return !e ? -1 : (e[0] == 'w' ? 16 : 0); }();
   static const int t192 = env_int("PGIBBS_GEMM_T192", 1);
-  static const int ladder = env_int("PGIBBS_GEMM_LADDER", 0);
   const BigGeom geo = big_geometry(M, N, n_cu);
   // Residual GEMMs of mid-size batches: 256-row tiles quantise badly (a 32-chain shard's out-projection / fc2: 165 tiles on 256 CUs,
   // a 64-chain one: 325 = two rounds of which the second is a quarter full).  192 x 256 tiles (same kernel, 6 instead of 8 row
@@ -1036,26 +912,6 @@ static GemmPlan plan_big(int M, int N, int K, int epi, int m_live, int n_cu) {
   // The rows beyond the last 192-row tile are 64 x 64 tail tiles of the same grid.
   const double r256 = rounds_256(geo, M, N, n_cu), r192 = rounds_192(M, N, n_cu);
   const bool cheaper192 = t192 && epi == EPI_F32_RESID && r192 <= 0.9 * r256;
-  // Round 6: the tile-height ladder (gemm_ladder.hip; heights 160 ... 240 in steps of 16 rows).  Built for VERDICT r05's tile-count
-  // argument -- a partial last round of tiles costs a whole one, and N = 1280 (five tiles per row panel) quantises badly for a
-  // 1/8 ... 1/2 shard of config 3 -- and MEASURED (profiles/r06_ladder_bench.txt, r06_shard_proxy_ladder_ab.txt): every height
-  // takes the same time to within 3 % at every shard size (a 32-chain shard's fc2: 165 tiles of 256 rows 128.8 us, 220 of 192
-  // 127.0, 240 of 176 133.6, 190 of 224 128.7), bit-identical results.  These launches run at a fixed aggregate L2 -> LDS feed of
-  // ~8 TB/s whatever the tiling (bytes staged / time: 6.8 ... 8.5 TB/s from the 32-chain shard to the full batch), so idle CUs in a
-  // partial round are not lost throughput and a smaller tile only raises the bytes staged per FLOP.  OFF by default;
-  // PGIBBS_GEMM_LADDER=1 prices the candidates in rounds x height (the model that does not hold), =h forces height h where the
-  // epilogue has it (the A/B switch of tests/test_gpu_kernels.py and tools/ladder_bench.py).
-  if (ladder && (epi == EPI_F32_RESID || epi == EPI_BF16_GELU)) {
-    const int live = m_live > 0 && m_live <= M ? m_live : M;
-    int best_h = 0;
-    double best = 0.95 * (cheaper192 ? r192 : r256);
-    for (int h = 240; h >= 160; h -= 16) {
-      if (!gemm_ladder_has(epi, h) || (ladder > 1 && ladder != h)) continue;
-      const double c = rounds_ladder(live, h, N, n_cu);
-      if (ladder == h || c < best - 1e-9) { best = c; best_h = h; if (ladder == h) break; }
-    }
-    if (best_h) return {GEMM_LADDER, live, best_h};
-  }
   const bool bf16out = epi == EPI_BF16 || epi == EPI_BF16_GELU;
   if (big == 16 || (big == -1 && bf16out)) return {GEMM_W16, geo.m_main * 256, 256, geo.tail_rows};
   if (cheaper192 || (t192 == 2 && epi == EPI_F32_RESID)) return {GEMM_PP, M / 192 * 192, 192, M % 192};
@@ -1071,6 +927,7 @@ static GemmPlan plan_big(int M, int N, int K, int epi, int m_live, int n_cu) {
 // ws_bytes: the fp32 scratch on offer (0: none); variant: the table in kernels_ops.inc
 static GemmPlan plan_gemm(int M, int N, int K, int epi, int variant, size_t ws_bytes, int m_live, int n_cu) {
   if (K % 64) return plan_error("gemm: K must be a multiple of 64");
+  if (!((variant >= 1 && variant <= 8) || variant == 20 || variant == 80)) return plan_error("gemm: unknown variant");
   const bool ok256 = M % 256 == 0 && N % 256 == 0 && K >= 128;
   // ---- the benchmark variants that name a kernel take it where the shape allows.  Everything else is the production dispatch
   // below; variants other than 2 ... 5 never split K, and variant 1 (lockstep tiles only) does not stream weights either
@@ -1078,8 +935,7 @@ static GemmPlan plan_gemm(int M, int N, int K, int epi, int variant, size_t ws_b
   if (variant == 7 && M % 128 == 0 && N % 128 == 0) return {GEMM_TILE128, M};
   if (variant == 8 && epi == EPI_F32_RESID && ok256 && M >= 192) return {GEMM_PP, M / 192 * 192, 192, M % 192};
   if ((variant == 1 || variant >= 20) && M > 256 && M % 128 == 0 && N % 64 == 0) {       // past the small-batch kernels and their checks
-    const int abl = variant >= 80 ? variant - 80 : (variant >= 60 ? variant - 40 : variant - 20);
-    if (variant >= 20 && ok256) return {variant >= 80 ? GEMM_W16 : GEMM_PP, M, 256, 0, 1, abl};
+    if (variant >= 20 && ok256) return {variant == 80 ? GEMM_W16 : GEMM_PP, M, 256};      // 20 / 80: the kernel on all rows, no tail tiles
     if (variant == 1 && N % 128 == 0) return {ok256 ? GEMM_TILE256_LOCKSTEP : GEMM_TILE128, M};
   }
   const bool may_split = variant != 1 && variant < 6, may_stream = variant != 1;
@@ -1114,11 +970,10 @@ static GemmPlan plan_gemm(int M, int N, int K, int epi, int variant, size_t ws_b
   return {GEMM_TILE64, M};
 }
 
-// what a launch of the plan records (note_kernel); the ablation instances are not recorded
+// what a launch of the plan records (note_kernel)
 static void note_plan(const GemmPlan& p, int N, int K) {
-  if (p.abl || p.kind == GEMM_INVALID) return;
+  if (p.kind == GEMM_INVALID) return;
   const long tiles_n = N / 256;
-  char ladder[32];
   switch (p.kind) {
     case GEMM_SKINNY: note_kernel(skinny_8_waves(K / p.splits) ? "skinny8w" : "skinny4w", N / 16, p.splits); break;
     case GEMM_TILE64: note_kernel("tile64x64", (long)(p.rows / 64) * (N / 64), p.splits); break;
@@ -1126,10 +981,6 @@ static void note_plan(const GemmPlan& p, int N, int K) {
     case GEMM_TILE256_LOCKSTEP: note_kernel("tile256x256-lockstep", p.rows / 256 * tiles_n); break;
     case GEMM_PP: note_kernel(p.tile_rows == 192 ? "pp192x256" : "pp256x256", p.rows / p.tile_rows * tiles_n); break;
     case GEMM_W16: note_kernel("w16-256x256", p.rows / 256 * tiles_n); break;
-    case GEMM_LADDER:
-      snprintf(ladder, sizeof ladder, "ppx%dx256", p.tile_rows);
-      note_kernel(ladder, (p.rows + p.tile_rows - 1) / p.tile_rows * tiles_n);
-      break;
   }
   if (p.tail_rows) note_kernel("tail64", (long)(p.tail_rows / 64) * (N / 64));
 }
@@ -1161,9 +1012,8 @@ static int launch_plan(hipStream_t s, const GemmPlan& p, const bf16_t* X, const 
     case GEMM_TILE64: rc = launch_cfg<64, 64, 32, 32>(s, X, W, bias, o, p.rows, N, Ks, ldx, ldw, ldos, e, p.splits, stride); break;
     case GEMM_TILE128: rc = launch_cfg<128, 128, 64, 64>(s, X, W, bias, o, p.rows, N, Ks, ldx, ldw, ldos, e, p.splits, stride); break;
     case GEMM_TILE256_LOCKSTEP: rc = launch_cfg<256, 256, 128, 64>(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi); break;
-    case GEMM_PP: rc = launch_pp(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi, p.abl, p.tail_rows, p.tile_rows); break;
-    case GEMM_W16: rc = launch_gemm_w16(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi, p.abl, p.tail_rows); break;
-    case GEMM_LADDER: rc = launch_gemm_ladder(s, X, W, bias, out, p.rows, M, p.tile_rows, N, K, ldx, ldw, ldo, epi); break;
+    case GEMM_PP: rc = launch_pp(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi, p.tail_rows, p.tile_rows); break;
+    case GEMM_W16: rc = launch_gemm_w16(s, X, W, bias, out, p.rows, N, K, ldx, ldw, ldo, epi, p.tail_rows); break;
   }
   if (rc || !split) return rc;
   const long total4 = stride / 4;

@@ -1,7 +1,7 @@
 // What the GEMM tile kernels share beyond gemm_tile.h (which this header includes: vector types, tile walk, LDS swizzles, row
 // buffer access, 16-wave operand DMA, visit_int): the GELU forms (one definition for all kernels), EpiTraits, the 64 x 64 tail tile
 // of the 256 x 256 grids (gemm_tail_tile64), the LDS-staged epilogue of a 256 x 256 tile held by 4 or 16 waves (tile256_epilogue) and
-// the switches the tile launchers share (gemm_gm, gemm_tail_last).  Users: gemm_bf16.hip, gemm_ladder.hip, gemm_rowln.hip,
+// the switch the tile launchers share (gemm_gm).  Users: gemm_bf16.hip,
 // gemm_w16.hip, gemm_colattn.hip, chain_trunk.hip, engine.hip, api_dbg.hip; tools/probes/gemm_w4.hip.
 #pragma once
 #include "gemm_tile.h"
@@ -344,24 +344,18 @@ __device__ __forceinline__ void tile256_epilogue(ElemF&& elem, char* smem, int w
   }
 }
 
-// ---- switches the tile launchers share (host): one reader each, so that what a forced value means per kernel family can be compared ----
+// ---- the switch the tile launchers share (host): one reader, so that what a forced value means per kernel family can be compared ----
 // PGIBBS_GEMM_GM: m-panels per rasterisation group, the kernels' GM template parameter.  Unset: 4, but 2 for deep K (fc2: a 256-row
 // X panel of K = 5120 is 2.6 MB, four of them plus the W panels overflow the XCD's 4 MB L2 even slice-wise; measured 0.760 ->
 // 0.733 ms with the bf16 epilogue).  A forced value is mapped onto the instances the family has.
-enum { GM_PP256, GM_PP192, GM_W16, GM_LADDER };
+enum { GM_PP256, GM_PP192, GM_W16 };
 inline int gemm_gm(int family, int K) {
   static const int env = env_int("PGIBBS_GEMM_GM", 0);
   const int dflt = K >= 4096 ? 2 : 4;
   switch (family) {
     case GM_PP256: return !env ? dflt : (env == 1 || env == 2 ? env : 4);   // 8-wave kernel, 256-row tiles: 1, 2, 4
-    case GM_LADDER: return env == 2 || env == 4 ? env : dflt;                // ladder: 2, 4; anything else as unset
     default: return (env ? env : dflt) == 2 ? 2 : 4;                         // 192-row tiles, 16-wave kernel: 2, else 4
   }
-}
-// PGIBBS_GEMM_TAIL_LAST=1: the 64 x 64 tail tiles are the last workgroups of the grid instead of the first
-inline bool gemm_tail_last() {
-  static const int on = env_int("PGIBBS_GEMM_TAIL_LAST", 0);
-  return on != 0;
 }
 
 PG_OPS_END

@@ -5,13 +5,11 @@
 // it, and as functions these expressions moved the instruction schedule of default-path kernels (gemm_tail_tile64's callers,
 // gemm_bf16_w16_kernel: prologue instructions reordered, registers renamed) -- compare the ISA of every user before changing a form.
 // For the same reason the two w16 kernels spell out their (plain) 64 x 64 tail prologue and their 4-piece DMA loop, and the ping-pong
-// half-step loop stays in gemm_bf16_pp_kernel and ladder::wave_body: as shared functions they renamed the scalar registers of every
+// half-step loop stays in gemm_bf16_pp_kernel: as shared functions they renamed the scalar registers of every
 // w16 / split3 instance and moved the schedule of every gemm_bf16_pp_kernel instance.
 //   kernel                                            tile walk                      operand layout in LDS
 //   gemm_bf16_kernel (lockstep; gemm_bf16.hip)        xcd_contiguous                 128-byte rows
 //   gemm_bf16_pp_kernel (gemm_bf16.hip)               xcd_contiguous + grouped_tile  half-K (64-byte rows)
-//   gemm_bf16_ppx_kernel (gemm_ladder.hip)            xcd_contiguous + grouped_tile  half-K
-//   gemm_rowln_kernel (gemm_rowln.hip)                one row panel per workgroup    half-K
 //   gemm_bf16_w16_kernel, gemm_split3_w16_kernel      xcd_contiguous + grouped_tile  128-byte rows
 //   gemm_colattn_kernel (gemm_colattn.hip)            xcd_contiguous + grouped_tile  128-byte rows
 //   gemm_tail_tile64 (gemm_epilogue.h)                tail_tile (8-wave) / caller's  128-byte rows
@@ -53,17 +51,14 @@ __device__ __forceinline__ void grouped_tile(int bid, int n_tiles, int tiles_n, 
   tile_m = g * GM + within % rows;
   tile_n = within / rows;
 }
-// The 64 x 64 tail tiles of a 256 x 256 grid (gemm_tail_tile64, gemm_epilogue.h) are |n_tail| extra workgroups: the FIRST of the
-// grid when n_tail > 0, the LAST when n_tail < 0 (PGIBBS_GEMM_TAIL_LAST; only where LAST_OK).  tail_tile: is this workgroup one, and
-// of which 64-row block rb and 64-column tile tn.  XCD_ROWS (the ping-pong kernel): all column tiles of a row block go to one XCD
-// (they share the block's X rows through its L2) whenever the row blocks divide by 8 (tail rows are multiples of 256: at least by 4);
+// The 64 x 64 tail tiles of a 256 x 256 grid (gemm_tail_tile64, gemm_epilogue.h) are n_tail extra workgroups, the FIRST of the
+// grid.  tail_tile: is this workgroup one, and of which 64-row block rb and 64-column tile tn.  XCD_ROWS (the ping-pong kernel): all
+// column tiles of a row block go to one XCD (they share the block's X rows through its L2) whenever the row blocks divide by 8 (tail rows are multiples of 256: at least by 4);
 // otherwise, and without XCD_ROWS (the plain mapping the 16-wave kernels spell out themselves, see above), row blocks in grid order.
-template <bool XCD_ROWS, bool LAST_OK = true>
-__device__ __forceinline__ bool tail_tile(int n_tail, int n_tiles, int tiles_n, int& rb, int& tn) {
-  const int nt_abs = LAST_OK && n_tail < 0 ? -n_tail : n_tail;
-  const bool first = !LAST_OK || n_tail > 0;
-  if (!(LAST_OK ? nt_abs && (first ? (int)blockIdx.x < nt_abs : (int)blockIdx.x >= n_tiles) : (int)blockIdx.x < n_tail)) return false;
-  const int tn64 = tiles_n * 4, bt = first ? blockIdx.x : blockIdx.x - n_tiles, n_rb = nt_abs / tn64;
+template <bool XCD_ROWS>
+__device__ __forceinline__ bool tail_tile(int n_tail, int tiles_n, int& rb, int& tn) {
+  if ((int)blockIdx.x >= n_tail) return false;
+  const int tn64 = tiles_n * 4, bt = blockIdx.x, n_rb = n_tail / tn64;
   if (XCD_ROWS && (n_rb & 7) == 0) { const int j = bt >> 3; rb = (j / tn64) * 8 + (bt & 7); tn = j % tn64; }
   else { rb = bt / tn64; tn = bt % tn64; }
   return true;

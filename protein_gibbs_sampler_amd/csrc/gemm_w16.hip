@@ -44,9 +44,7 @@ __device__ unsigned long long* pg_w16_prof;      // [workgroup][4]: shader clock
 #define PG_W16_T(i)
 #endif
 
-// ABL (micro-benchmark ablations): 0 real kernel; 1 no LDS-DMA in the loop (slot 0 reused); 2 no MFMA; 4 no epilogue;
-// 5 no barrier (timing only); 10 DMA never waited for (timing only)
-template <int EPI, int GM, int ABL>
+template <int EPI, int GM>
 __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                                const float* __restrict__ bias, void* __restrict__ out, int K,
                                                                int ldx, int ldw, int ldo, int tiles_n, int n_tiles, int n_tail,
@@ -54,9 +52,8 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
   __shared__ __attribute__((aligned(16))) char smem[2 * W16_KSLOT];
 
   // the first n_tail workgroups: 64 x 64 tiles of the rows beyond the last full round of 256 x 256 tiles (gemm_epilogue.h)
-  const int nt_abs = n_tail < 0 ? -n_tail : n_tail;       // n_tail < 0: the tail workgroups are the LAST of the grid
-  if (ABL == 0 && nt_abs && (n_tail > 0 ? (int)blockIdx.x < nt_abs : (int)blockIdx.x >= n_tiles)) {
-    const int tn64 = tiles_n * 4, bt = n_tail > 0 ? blockIdx.x : blockIdx.x - n_tiles;
+  if ((int)blockIdx.x < n_tail) {
+    const int tn64 = tiles_n * 4, bt = blockIdx.x;
     gemm_tail_tile64<16, EPI>(X, W, bias, out, K, ldx, ldw, ldo, tail_m0 + (bt / tn64) * 64, (bt % tn64) * 64, smem);
     return;
   }
@@ -64,7 +61,7 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave & 3, wn = wave >> 2;           // wave tile: X rows wm*64 .., W rows wn*64 ..
 
-  int bid = n_tail > 0 ? blockIdx.x - n_tail : blockIdx.x;
+  int bid = blockIdx.x - n_tail;
   bid = xcd_contiguous(bid, n_tiles);
   int tile_m, tile_n;
   grouped_tile<GM>(bid, n_tiles, tiles_n, tile_m, tile_n);
@@ -106,12 +103,12 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
   dma_step(0);
   PG_W16_T(0);
   for (int t = 0; t < nk; ++t) {
-    if ((ABL != 1 && ABL != 10) || t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my pieces of K-step t have landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my pieces of K-step t have landed
     __builtin_amdgcn_sched_barrier(0);
-    if (ABL != 5) __builtin_amdgcn_s_barrier();      // everybody's have; everybody is done reading slot (t+1)&1 (step t-1)
+    __builtin_amdgcn_s_barrier();                    // everybody's have; everybody is done reading slot (t+1)&1 (step t-1)
     __builtin_amdgcn_sched_barrier(0);
-    if (ABL != 1) dma_step(t + 1);
-    const char* sb = smem + ((ABL == 1 ? 0 : t) & 1) * W16_KSLOT;
+    dma_step(t + 1);
+    const char* sb = smem + (t & 1) * W16_KSLOT;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       const int fo = kk ? foff1 : foff0;
@@ -120,27 +117,15 @@ __global__ __launch_bounds__(1024, 1) void gemm_bf16_w16_kernel(const bf16_t* __
       for (int i = 0; i < 4; ++i) wf[i] = *(const bf16x8*)(sb + wbase + i * 2048 + fo);
 #pragma unroll
       for (int j = 0; j < 4; ++j) xf[j] = *(const bf16x8*)(sb + xbase + j * 2048 + fo);
-      if (ABL != 2) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mfma_op16(wf[i], xf[j], acc[i][j]);
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(wf[i]), "v"(xf[i]));
-      }
+        for (int j = 0; j < 4; ++j) acc[i][j] = mfma_op16(wf[i], xf[j], acc[i][j]);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the trailing zero-fill pieces, before the LDS is reused
   PG_W16_T(2);
 
-  if (ABL == 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
   // acc[i][j] is D[n = wn*64 + i*16 + fq*4 + r][m = wm*64 + j*16 + fr]
   auto elem = [&](int e, int& m_loc, int& n_loc) -> f32x4 { return w16_elem(acc, e, wm, wn, fr, fq, m_loc, n_loc); };
   tile256_epilogue<EPI, 16>(elem, smem, wave, lane, m0, n0, bias, out, ldo);
@@ -279,36 +264,22 @@ int launch_gemm_split3_w16(hipStream_t s, const bf16_t* X3, const bf16_t* W3, co
 
 #endif  // !PG_F16
 
-// M, N multiples of 256; K a multiple of 64.  abl > 0: micro-benchmark variants (bf16 epilogue only, no tail tiles).  The
-// dispatch that picks this kernel records it (note_plan, gemm_bf16.hip).
+// M, N multiples of 256; K a multiple of 64.  The dispatch that picks this kernel records it (note_plan, gemm_bf16.hip).
 int launch_gemm_w16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldx,
-                    int ldw, int ldo, int epi, int abl, int tail_rows) {
+                    int ldw, int ldo, int epi, int tail_rows) {
   const int tiles_m = M / 256, tiles_n = N / 256, n_tiles = tiles_m * tiles_n;
-  const int n_tail_abs = (tail_rows / 64) * (N / 64), tail_m0 = M;
-  const int n_tail = gemm_tail_last() ? -n_tail_abs : n_tail_abs;
-  if (M % 256 || N % 256 || K % 64 || K < 64 || tail_rows % 64 || n_tiles + n_tail_abs < 1 || (abl && tail_rows))
-    return fail(1, "gemm_w16: shape");
+  const int n_tail = (tail_rows / 64) * (N / 64), tail_m0 = M;
+  if (M % 256 || N % 256 || K % 64 || K < 64 || tail_rows % 64 || n_tiles + n_tail < 1) return fail(1, "gemm_w16: shape");
   const int gm = gemm_gm(GM_W16, K);
-  dim3 grid(n_tiles + n_tail_abs), block(1024);
-  // every instance of the kernel: abl 0 -> the five epilogues x GM 2, 4; the ablations one line each, abl -> <EPI, GM, ABL>
-#define PG_W16(E, G, A)                                                                                                          \
-  hipLaunchKernelGGL((gemm_bf16_w16_kernel<E, G, A>), grid, block, 0, s, X, W, bias, out, K, ldx, ldw, ldo, tiles_n, n_tiles, \
-                     n_tail, tail_m0)
-  switch (abl) {
-    case 0:
-      if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU>(epi, [&](auto E) {
-            return visit_int<2, 4>(gm, [&](auto G) { PG_W16(decltype(E)::value, decltype(G)::value, 0); });
-          }))
-        return fail(1, "gemm_w16: bad epilogue");
-      break;
-    case 1: PG_W16(EPI_BF16, 4, 1); break;
-    case 2: PG_W16(EPI_BF16, 4, 2); break;
-    case 4: PG_W16(EPI_BF16, 4, 4); break;
-    case 5: PG_W16(EPI_BF16, 4, 5); break;
-    case 10: PG_W16(EPI_BF16, 4, 10); break;
-    default: return fail(1, "gemm_w16: unknown ablation");
-  }
-#undef PG_W16
+  dim3 grid(n_tiles + n_tail), block(1024);
+  // every instance of the kernel: the five epilogues x GM 2, 4
+  if (!visit_int<EPI_BF16, EPI_BF16_GELU, EPI_F32_RESID, EPI_F32, EPI_F32_GELU>(epi, [&](auto E) {
+        return visit_int<2, 4>(gm, [&](auto G) {
+          hipLaunchKernelGGL((gemm_bf16_w16_kernel<decltype(E)::value, decltype(G)::value>), grid, block, 0, s, X, W, bias, out, K, ldx,
+                             ldw, ldo, tiles_n, n_tiles, n_tail, tail_m0);
+        });
+      }))
+    return fail(1, "gemm_w16: bad epilogue");
   PG_HIP(hipGetLastError());
   return 0;
 }

@@ -3,8 +3,8 @@
 // (activation buffers are padded to 256 rows: kernels may touch the padding rows of the last tile).
 // ws (optional, fp32 scratch): lets a residual GEMM with few tiles and a deep K (fc2 of a small batch) run as parallel
 // K-splits into ws followed by one fixed-order reduction into out -- bit-reproducible, no atomics.
-// m_live (optional): the rows of X / out that hold real tokens (M counts the padded rows): lets the big-batch dispatch pick a tile
-// height by the real row count (launch_gemm_big)
+// m_live (optional): the rows of X / out that hold real tokens (M counts the padded rows).  No kernel choice reads it today: every
+// tile kernel works on the padded rows
 int launch_gemm_bf16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K,
                      int ldx, int ldw, int ldo, int epi, float* ws = nullptr, size_t ws_bytes = 0, int m_live = 0);
 // The K-splits a residual GEMM of depth K runs as when it is given scratch and has few tiles (1: never split), and the scratch that
@@ -17,13 +17,11 @@ size_t gemm_splitk_ws_bytes(int M, int N, int K);
 //    1        lockstep tiles only: 256^2, 128^2 or 64^2 by divisibility; no weight streaming, no K-splits
 //    6 / 7    64^2 / 128^2 lockstep tiles on every row
 //    8        192 x 256 ping-pong tiles + tail tiles (residual epilogue)
-//    20 + a   ablation a of the 8-wave ping-pong kernel (a = 0: the kernel itself on all rows, no tail tiles); its ids are listed in
-//             launch_pp (gemm_bf16.hip)
-//    60 + ... the same list, id = variant - 40 (68 / 69: ids 28 / 29)
-//    80 + a   ablation a of the 16-wave kernel (a = 0: the kernel itself); ids in launch_gemm_w16 (gemm_w16.hip)
+//    20       the 8-wave ping-pong kernel on all rows, no tail tiles
+//    80       the 16-wave kernel on all rows, no tail tiles
 //    90       pg_dbg_gemm_bench only (api_dbg.hip): the strict mode's fused three-product kernel
-// A variant that names a kernel takes it where the shape allows (6 - 8: divisibility; 20 and up: more than 256 rows, M and N
-// multiples of 256) and is the production dispatch without K-splits elsewhere.  An ablation id that does not exist is an error.
+// A variant that names a kernel takes it where the shape allows (6 - 8: divisibility; 20, 80: more than 256 rows, M and N
+// multiples of 256) and is the production dispatch without K-splits elsewhere.  Any other variant is an error ("gemm: unknown variant").
 int launch_gemm_bf16_variant(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N,
                              int K, int ldx, int ldw, int ldo, int epi, int variant, float* ws = nullptr, size_t ws_bytes = 0,
                              int m_live = 0);
@@ -44,18 +42,6 @@ int launch_chain_trunk(hipStream_t s, const PgChainTrunkArgs& a, int M, int d_mo
 // the big-batch GEMM: whole rounds of 256 x 256 tiles + 64 x 64 tail tiles in one grid (gemm_bf16.hip); M, N multiples of 256
 int launch_gemm_big(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldx,
                     int ldw, int ldo, int epi, int m_live = 0);
-// the tile-height ladder of the 8-wave kernel (gemm_ladder.hip): ceil(m_live / h) row panels of h token rows, h in 160 ... 240;
-// residual and fc1 (bias + GELU, 16-bit out) epilogues; m_rows = rows that exist in X / out
-bool gemm_ladder_has(int epi, int h);
-int launch_gemm_ladder(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int m_live, int m_rows, int h,
-                       int N, int K, int ldx, int ldw, int ldo, int epi);
-// ESM-MSA-1b's attention out-projections with the next LayerNorm in the epilogue (gemm_rowln.hip): x[m_rows][768] += A . W^T + bias,
-// h = LayerNorm(x) as 16-bit rows (rows < m_live; column-major token order when colmajor_R > 0) -- tiles of 112 rows x all 768
-// columns, bit-identical with launch_gemm_bf16(EPI_F32_RESID) + launch_layernorm_bf16
-bool gemm_rowln_ok(int m_rows, int N, int K);
-int launch_gemm_rowln(hipStream_t s, const bf16_t* A, const bf16_t* W, const float* bias, float* x, const float* gamma,
-                      const float* beta, bf16_t* h, int m_live, int m_rows, int K, int lda, int ldw, float eps, int colmajor_R = 0,
-                      int colmajor_C = 0, int abl = 0);      // abl: timing ablations (tools/rowln_bench.py)
 // what launch_gemm_bf16_variant would record for a shape (note_kernel's text; "error: ..." for a shape it refuses) on a device of
 // n_cu compute units, offered split-K scratch or not -- the dispatch decision alone, no HIP call (pg_dbg_gemm_plan)
 void gemm_plan_text(int M, int N, int K, int epi, int variant, bool have_ws, int m_live, int n_cu, std::string* text);
@@ -64,7 +50,7 @@ void gemm_big_geometry(int M, int N, int K, int* m_main_panels, int* tail_rows);
 // the 16-wave 256x256 tile kernel (gemm_w16.hip): M (may be 0 with tail_rows > 0), N multiples of 256, K a multiple of 64;
 // tail_rows rows of 64 x 64 tail tiles from row M on
 int launch_gemm_w16(hipStream_t s, const bf16_t* X, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldx,
-                    int ldw, int ldo, int epi, int abl = 0, int tail_rows = 0);
+                    int ldw, int ldo, int epi, int tail_rows = 0);
 // strict mode: the three split-bf16 products of a projection in one pass (gemm_w16.hip); X3 / W3 in the split operand layout,
 // K = logical depth; bit-identical with launch_gemm_bf16 over K' = 3K on the same operands
 int launch_gemm_split3(hipStream_t s, const bf16_t* X3, const bf16_t* W3, const float* bias, void* out, int M, int N, int K, int ldo,

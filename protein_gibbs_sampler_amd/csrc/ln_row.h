@@ -1,6 +1,5 @@
-// One LayerNorm row on one 64-lane wave -- the ONLY definition of the arithmetic, shared by the stand-alone kernels
-// (elementwise.hip) and by the residual GEMMs that normalise a finished row panel themselves (gemm_epilogue.h): a row's
-// bf16 operand is bit-identical whichever kernel produced it.  Every floating-point operation is an explicitly rounded
+// One LayerNorm row on one 64-lane wave -- the ONLY definition of the arithmetic, shared by every row kernel (elementwise.hip):
+// a row's bf16 operand is bit-identical whichever kernel produced it.  Every floating-point operation is an explicitly rounded
 // intrinsic, so no translation unit's contraction choices can differ.
 #pragma once
 #include "pg_common.h"
@@ -9,8 +8,7 @@
 PG_OPS_BEGIN
 
 // A lane holds chunks lane, lane + 64, ... of the row as float4 v[NCH]: NCH is a template parameter of everything below, deduced
-// from the array.  kMaxCh = 8 (d <= 2048) is the form every model up to d_model 2048 runs, and the only one the residual GEMMs
-// (gemm_epilogue.h, gemm_rowln.hip) instantiate; kMaxChWide = 10 (d <= 2560: ESM-2 3B) costs 40 VGPRs per row instead of 32.
+// from the array.  kMaxCh = 8 (d <= 2048) is the form every model up to d_model 2048 runs; kMaxChWide = 10 (d <= 2560: ESM-2 3B) costs 40 VGPRs per row instead of 32.
 // kMaxCh5k = 20 (d <= 5120: ESM-2 15B) holds 80 VGPRs of row; above 2560 only whole 512-feature units are accepted (3072, 3584, ..
 // 5120: kRowUnit5k), so every lane holds the same number of chunks there.
 // The arithmetic and its order -- per lane the chunks in ascending order, then wave_sum -- do not depend on NCH.

@@ -258,8 +258,6 @@ CASES = _cases()
 PRODUCTION_TAIL = (4352, 4096, 128)
 # strict fused kernel at the smallest shapes with a full round of tiles on 256 CUs: 256 tiles, and 260 = one round + a tail panel
 BIG_STRICT = ((16384, 1024, 64), (16640, 1024, 64))
-# the exact case of the tile-height ladder's child process (tests/test_gpu_kernels.py): >= 128 tiles of 256 x 256, residual epilogue
-LADDER_EXACT = (8256, 1024, 128)
 
 
 def expected_plan(c):

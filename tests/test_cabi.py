@@ -23,6 +23,16 @@ def test_header_symbols_exported():
     assert declared == {n for n, _, _ in _lib.SIGNATURES}       # the ctypes table covers the whole header
 
 
+def test_library_exports_the_c_abi_only():
+    """The dynamic symbol table holds the pg_* entry points and no C++ symbol of the library's own namespace (launchers, kernel handles);
+    every name of the ctypes prototype table is among the exported ones."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    assert not sorted(s for s in exported if "_ZN2pg" in s)[:10]
+    assert not {n for n, _, _ in _lib.SIGNATURES} - exported
+
+
 def test_version_and_error_string():
     L = _lib.lib()
     assert b"gfx950" in L.pg_version()

@@ -44,7 +44,6 @@ def _cases():
         "pg_dbg_gemm_ln": ([0, BF16, _z(4, 256), None, _z(256), _z(256), 1e-5, _z(32, 256), _z(32), _z(16, 32), 16, 4, 32, 256, 0, 0, None, 0], 2,
                            "pg_dbg_gemm_ln: bad argument"),
         "pg_dbg_gemm_bench": ([0, 16, 64, 64, 0, 1, 1, _dbl(1)], 7, "pg_dbg_gemm_bench: bad argument"),
-        "pg_dbg_rowln_bench": ([0, 256, 128, 1, _dbl(5), _dbl(1)], 4, "pg_dbg_rowln_bench: bad argument"),
         "pg_dbg_qkv_attention_bench": ([0, 1, 32, 1, 1, _dbl(3), _dbl(1)], 5, "pg_dbg_qkv_attention_bench: T must be 32, 64, 128 or 256"),
         "pg_dbg_layernorm": ([0, x, g, g, _z(4, 64), 4, 64, 1e-5], 1, "pg_dbg_layernorm: bad argument"),
         "pg_dbg_layernorm_operand": ([0, BF16, x, g, g, _z(4, 64), 4, 64, 1e-5], 2, "pg_dbg_layernorm_operand: bad argument"),

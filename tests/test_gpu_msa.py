@@ -253,59 +253,3 @@ def test_fused_column_attention_is_bit_identical_with_the_unfused_path(precision
     for k in res["1"].files:
         assert np.isfinite(res["1"][k]).all(), k
         assert np.array_equal(res["1"][k].view(np.uint32), res["0"][k].view(np.uint32)), k
-
-
-_ROWLN_CHILD = """
-import sys, warnings, numpy as np
-sys.path.insert(0, %r)
-from protein_gibbs_sampler_amd import models, weights
-cfg = weights.make_config(weights.MSA1B_CONFIG, d_model=768, n_layers=2, d_ffn=1024, max_positions=600, max_msa_rows=128)
-sd = weights.synthetic_state_dict(cfg, seed=3, std=0.03, embed_std=0.3, ln_jitter=0.1)
-outs = []
-for prec in ("bf16", "fp16"):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        m = models.ESM_MSA1(state_dict=sd, config=cfg, precision=prec).model.to("cuda:0")
-    # depth 32 / 64 / 128: the fused column block (LayerNorm rows in column-major token order); depth 5 / 37: ordinary order; row counts
-    # that are no multiple of the 112-row tile, a last panel shifted up against the padded rows, several MSAs per call
-    for (B, R, C) in [(1, 32, 257), (2, 5, 70), (3, 64, 100), (1, 37, 130), (1, 128, 513), (4, 32, 57)]:
-        rng = np.random.default_rng(B * 100 + R + C)
-        tok = rng.integers(4, 24, (B, R, C))
-        tok[rng.random((B, R, C)) < 0.1] = 30
-        tok[rng.random((B, R, C)) < 0.08] = 32
-        tok[..., 0] = 0
-        outs.append(m.forward_logits(tok.astype(np.int32))[:, ::3, ::5].copy())
-np.savez(sys.argv[1], *outs)
-"""
-
-
-def test_full_row_out_projection_with_layernorm_epilogue_is_bit_identical(tmp_path):
-    """gemm_rowln.hip (round 6): ESM-MSA-1b's attention out-projections as tiles of 112 token rows x all 768 columns whose epilogue
-    adds the residual and normalises the finished rows (no LayerNorm launch, 2.4 GB less HBM traffic per out-projection at config
-    4).  Same MFMA / k order, the ping-pong epilogue's x_old + (acc + bias), ln_row.h's LayerNorm on one wave per row: the logits
-    are bit-identical with the two-launch path (PGIBBS_ROWLN=0), in both operand flavours, token-order and column-major h rows."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = {}
-    for sw in ("1", "0"):
-        f = str(tmp_path / ("rowln_%s.npz" % sw))
-        p = subprocess.run([sys.executable, "-c", _ROWLN_CHILD % root, f], capture_output=True, text=True,
-                           env=dict(os.environ, PGIBBS_ROWLN=sw, PGIBBS_ROWLN_MIN_ROWS="0"), timeout=1200)
-        assert p.returncode == 0, p.stderr[-3000:]
-        res[sw] = np.load(f)
-    assert len(res["0"].files) == 12
-    for k in res["0"].files:
-        assert np.isfinite(res["0"][k]).all() and res["0"][k].std() > 0.1
-        assert (res["1"][k].view(np.uint32) == res["0"][k].view(np.uint32)).all(), k
-
-
-def test_full_row_kernel_against_the_two_launches_on_raw_operands():
-    """pg_dbg_rowln_bench: gemm_rowln.hip and residual GEMM + LayerNorm kernel applied once to the same synthetic operands (16 448 and
-    65 664 token rows: a last row panel shifted against the padding, K = 768 and 256): x (fp32) and h (16-bit) equal bit for bit."""
-    import ctypes
-    L = _lib.lib()
-    for M, K in ((16448, 768), (65664, 768), (5000, 256)):
-        ms = (ctypes.c_double * 5)()
-        md = ctypes.c_double(-1)
-        _lib.check(L.pg_dbg_rowln_bench(0, M, K, 1, ms, ctypes.byref(md)))
-        assert md.value == 0.0, (M, K, md.value)

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""GEMM micro-benchmark on the forward pass's shapes (M = 66048 tokens): TFLOP/s per kernel variant."""
+"""GEMM micro-benchmark on the forward pass's shapes (M = 66048 tokens): TFLOP/s per kernel variant (arguments; default 1 2).
+Variants: 1 lockstep tiles, 2 production dispatch, 6 / 7 64^2 / 128^2 tiles, 8 192-row tiles (residual shapes), 20 the 8-wave kernel,
+80 the 16-wave kernel on all rows (table: csrc/kernels_ops.inc)."""
 import ctypes
 import os
 import sys
