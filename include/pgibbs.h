@@ -461,7 +461,7 @@ PG_API int pg_dbg_gemm_plan(int M, int N, int K, int epi, int variant, int have_
  * launch under "attention" ("whole kb18 hd64 split4 512+512wg", "split-f32 kb6 nqb5 hd64 5120wg", "row kb18 w9 rc1 2560wg"; "error:
  * ..." for a shape the launcher refuses).  kind 0: full attention over n_seq sequences of T tokens (row_step 1: contiguous chains;
  * else the strided sequences of the MSA column attention), has_pad / has_bias: with a <pad> key mask / ESM-1's bias key; kind 1:
- * tied row attention of B alignments of R rows x C columns (head_dim, has_bias, row_step unused; order_bh: the (msa, head) count the
+ * tied row attention of B alignments of R rows x C columns (head_dim, has_pad, has_bias, row_step unused; order_bh: the (msa, head) count the
  * split of the row loop is decided on, 0 = B * H).  precision PG_PREC_FP32: the strict launchers, else the 16-bit ones (both operand
  * flavours share one plan).  A sequence length or column count < 1 is answered by the launcher's own refusal.  Touches no device. */
 PG_API int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_C, int R, int H, int head_dim, int has_pad, int has_bias,

@@ -314,9 +314,9 @@ int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, int T_or_
     return fail(PG_ERR_INVALID, "pg_dbg_attention_plan: bad argument");
   const bool strict = precision == PG_PREC_FP32;
   std::string text;
-  if (kind == 0 && strict) attention_f32_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, row_step, &text);
+  if (kind == 0 && strict) attention_f32_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, &text);
   else if (kind == 0) attention_plan_text(n_seq_or_B, T_or_C, H, head_dim, has_pad != 0, has_bias != 0, row_step, n_cu, &text);
-  else if (strict) msa_row_f32_plan_text((int)n_seq_or_B, R, T_or_C, H, has_pad != 0, &text);
+  else if (strict) msa_row_f32_plan_text((int)n_seq_or_B, R, T_or_C, H, &text);
   else msa_row_plan_text((int)n_seq_or_B, R, T_or_C, H, order_bh, &text);
   snprintf(buf, (size_t)buf_bytes, "%s", text.c_str());
   return PG_OK;

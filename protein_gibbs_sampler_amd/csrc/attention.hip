@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256, OCC) void attention_long_kernel(const bf16_t* 
 
 // ------------------------------------------------------------------------------------------------
 // The dispatch.  plan_attention says which kernel template runs on which grid: a pure function of the shape, the device's CU count
-// and the process's PGIBBS_ATTN* switches, without a HIP call, so pg_dbg_attention_plan prints its answers on a machine without a GPU
+// and the process's PGIBBS_ATTN_SPLIT switch, without a HIP call, so pg_dbg_attention_plan prints its answers on a machine without a GPU
 // (tests/test_attention_plan_cpu.py pins them for the shapes the project is measured on).  launch_attention_seq_bf16 is the one
 // switch over it.
 // ------------------------------------------------------------------------------------------------
@@ -391,10 +391,7 @@ static AttentionPlan plan_attention(int64_t n_seq, int T, int H, int head_dim, b
   if (T <= 0) return refuse("attention: empty sequence");
   // The rung: the T tokens + ESM-1's bias_k / bias_v key.  The forms without the bias key (the Gibbs path, and ragged batches)
   // take the fine ladder: a chain of 200 residues has 13 key blocks, not 18.
-  // PGIBBS_ATTN_HD128_WHOLE=0: head 128 takes the tiled kernel at every length (the A/B switch of the whole-sequence form there)
-  static const int whole128 = env_int("PGIBBS_ATTN_HD128_WHOLE", 1);
-  p.kb = head_dim == 128 && !whole128 ? 0
-                                      : attention_rung(T + (has_bias ? 1 : 0), attention_fine_ladder() && !has_bias, attention_max_keys(head_dim));
+  p.kb = attention_rung(T + (has_bias ? 1 : 0), !has_bias, attention_max_keys(head_dim));
   p.whole = p.kb != 0;
   if (!p.whole) {                                // more than 576 keys: 288-key tiles (at head 32: 36 KB of LDS for K + V);
                                                  // head 128: more than 288 keys, 128-key tiles

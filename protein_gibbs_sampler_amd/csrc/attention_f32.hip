@@ -1,35 +1,15 @@
 // Strict-precision attention (PG_PREC_FP32): the same softmax(q k^T) v per (sequence, head) as attention.hip from
 // fp32 q, k, v, for the 1e-3 logit-parity mode.
 //
-// attention_split_kernel (the default): the MFMA formulation of attention.hip's attention_long_kernel with every
+// attention_split_kernel: the MFMA formulation of attention.hip's attention_long_kernel with every
 // operand split into a bf16 (hi, lo) pair in registers -- S = ql.kh + qh.kl + qh.kh and O = vl.ph + vh.pl + vh.ph, fp32
 // accumulation, small terms first -- so q, k, v and P keep ~16 mantissa bits (the dropped lo.lo terms are ~2^-17
 // relative).  One workgroup = (sequence, head, 64 queries); K and V tiles of MAXKB*16 keys are split while they are
 // staged (four LDS tiles: Kh, Kl, Vh, Vl); online softmax across tiles; exp2 on fp32 scores.
-//
-// attention_f32_kernel (PGIBBS_ATTN_F32=valu): the all-VALU fp32 form, kept as an independent cross-check.  One
-// 64-lane workgroup = 64 queries of one (sequence, head); a thread owns one query: q[64] and o[64] in registers, K/V
-// tiles of 64 keys staged in LDS as fp32 (all lanes read the same K/V row -> LDS broadcast), online softmax.
-#include <cstdlib>
-
 #include "attn_frag.h"
 #include "split_operand.h"
 
 PG_OPS_BEGIN
-
-// One thread's 64 context values of head h -> bf16 into the token's context row.  split_d != 0: the row is the strict mode's
-// split operand (3 * |split_d| values: split_operand.h); split_d < 0: without the duplicate hi block -- the out-projection that
-// reads the rows is the fused three-product kernel (gemm_split3_fused).
-__device__ __forceinline__ void store_ctx64(const float (&o)[64], float inv, bf16_t* row, int h, int split_d) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const float a = o[4 * i] * inv, b = o[4 * i + 1] * inv, c = o[4 * i + 2] * inv, d = o[4 * i + 3] * inv;
-    uint2 hi, lo;
-    split4(a, b, c, d, hi, lo);
-    if (!split_d) ((uint2*)(row + h * 64))[i] = hi;
-    else split_store4(row + split_lo_offset(h * 64 + 4 * i), hi, lo, split_d > 0);
-  }
-}
 
 // Building blocks shared by the three split-bf16 MFMA kernels (full attention, tied-row scores, tied-row apply).
 // Fragment geometry, tile layout and the transposing V^T read: attn_frag.h.
@@ -176,7 +156,9 @@ struct SplitAttn {
   }
 
   // row = the query's context row; the lane holds columns h*HD + db*16 + fq*4 .. +3.  bf16, or the strict mode's split operand
-  // row (split_operand.h: a head of 64 is two groups, a head of 32 one, a head of 16 half of one -- heads 2 g and 2 g + 1 share group g)
+  // row (split_operand.h: a head of 64 is two groups, a head of 32 one, a head of 16 half of one -- heads 2 g and 2 g + 1 share group g).
+  // split_d != 0: the split row, 3 * |split_d| values; split_d < 0: without the duplicate hi block -- the out-projection that reads
+  // the rows is the fused three-product kernel (gemm_split3_fused)
   static __device__ __forceinline__ void store_ctx(const f32x4 (&o)[NDB], float l, bf16_t* row, int h, int fq, int split_d) {
     const float inv = l > 0.f ? 1.0f / l : 0.f;     // every key masked (an all-<pad> sequence): zero context, not NaN
 #pragma unroll
@@ -393,226 +375,37 @@ __global__ __launch_bounds__(256, 2) void msa_row_apply_split_kernel(const float
   if (active && q < C) A::store_ctx(o, l, ctx + (((size_t)b * R + r) * C + q) * ld_ctx, h, fq, split_d);
 }
 
-__global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ ctx,
-                                                          int split_d, int T, int H, int ld_qkv_,
-                                                          int ld_ctx_, int k_off, int v_off, SeqLayout sl, int n_qchunk,
-                                                          const int32_t* __restrict__ key_tok, int pad_idx) {
-  __shared__ __attribute__((aligned(16))) float Ks[64 * 64];
-  __shared__ __attribute__((aligned(16))) float Vs[64 * 64];
-  const int lane = threadIdx.x;
-  const int qc = blockIdx.x % n_qchunk;
-  const int sh = blockIdx.x / n_qchunk;
-  const int seq = sh / H, h = sh % H;
-  const size_t row0 = (size_t)(seq / sl.inner_count) * sl.outer_rows + (size_t)(seq % sl.inner_count) * sl.inner_rows;
-  const size_t ld_qkv = (size_t)ld_qkv_ * sl.row_step, ld_ctx = (size_t)ld_ctx_ * sl.row_step;
-  const float* base = qkv + row0 * ld_qkv_ + h * 64;
-  const int qi = qc * 64 + lane;
-  const bool valid = qi < T;
-  float q[64], o[64];
-  {
-    const float4* qp = (const float4*)(base + (size_t)(valid ? qi : T - 1) * ld_qkv);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float4 v = qp[i];
-      q[4 * i] = v.x; q[4 * i + 1] = v.y; q[4 * i + 2] = v.z; q[4 * i + 3] = v.w;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 64; ++i) o[i] = 0.f;
-  float m = -3.0e38f, l = 0.f;
-  for (int k0 = 0; k0 < T; k0 += 64) {
-    __syncthreads();
-    const int nk = (T - k0) < 64 ? (T - k0) : 64;
-    for (int i = lane; i < 64 * 16; i += 64) {       // 64 keys x 16 float4
-      const int key = i >> 4, c = i & 15;
-      float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-      if (key < nk) {
-        kv = *(const float4*)(base + (size_t)(k0 + key) * ld_qkv + k_off + c * 4);
-        vv = *(const float4*)(base + (size_t)(k0 + key) * ld_qkv + v_off + c * 4);
-      }
-      ((float4*)Ks)[i] = kv;
-      ((float4*)Vs)[i] = vv;
-    }
-    __syncthreads();
-    float s[64];
-    float tmax = -3.0e38f;
-#pragma unroll
-    for (int key = 0; key < 64; ++key) {
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const float4 kv = ((const float4*)Ks)[key * 16 + c];
-        acc = fmaf(q[4 * c], kv.x, acc);
-        acc = fmaf(q[4 * c + 1], kv.y, acc);
-        acc = fmaf(q[4 * c + 2], kv.z, acc);
-        acc = fmaf(q[4 * c + 3], kv.w, acc);
-      }
-      // keys beyond T, and <pad> keys of a ragged batch (key_tok = token buffer, sequence seq at seq*T)
-      const bool masked = key >= nk || (key_tok && key_tok[(size_t)seq * T + k0 + key] == pad_idx);
-      s[key] = masked ? -3.0e38f : acc;
-      tmax = fmaxf(tmax, s[key]);
-    }
-    const float mn = fmaxf(m, tmax);
-    const float alpha = expf(m - mn);
-    l *= alpha;
-#pragma unroll
-    for (int i = 0; i < 64; ++i) o[i] *= alpha;
-#pragma unroll
-    for (int key = 0; key < 64; ++key) {
-      const float p = s[key] > -1.0e38f ? expf(s[key] - mn) : 0.f;
-      l += p;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const float4 vv = ((const float4*)Vs)[key * 16 + c];
-        o[4 * c] = fmaf(p, vv.x, o[4 * c]);
-        o[4 * c + 1] = fmaf(p, vv.y, o[4 * c + 1]);
-        o[4 * c + 2] = fmaf(p, vv.z, o[4 * c + 2]);
-        o[4 * c + 3] = fmaf(p, vv.w, o[4 * c + 3]);
-      }
-    }
-    m = mn;
-  }
-  if (valid) store_ctx64(o, l > 0.f ? 1.0f / l : 0.f, ctx + row0 * ld_ctx_ + (size_t)qi * ld_ctx, h, split_d);
-}
-
-// ---- strict tied row attention (MSA): S = scale * sum_r q_r k_r^T (fp32, to a scratch buffer), then
-//      ctx[r] = softmax_j(S) v_r with the row statistics recomputed per thread ------------------------------
-__global__ __launch_bounds__(64) void msa_row_scores_f32_kernel(const float* __restrict__ qkv, float* __restrict__ S, int R,
-                                                               int C, int H, int ld_qkv, int k_off, float scale, int n_chunk, int ldS) {
-  __shared__ __attribute__((aligned(16))) float Ks[64 * 64];
-  const int lane = threadIdx.x;
-  const int jc = blockIdx.x % n_chunk, ic = (blockIdx.x / n_chunk) % n_chunk, bh = blockIdx.x / (n_chunk * n_chunk);
-  const int b = bh / H, h = bh % H;
-  const float* base = qkv + (size_t)b * R * C * ld_qkv + h * 64;
-  const int qi = ic * 64 + lane;
-  const int nk = (C - jc * 64) < 64 ? (C - jc * 64) : 64;
-  float s[64];
-#pragma unroll
-  for (int i = 0; i < 64; ++i) s[i] = 0.f;
-  for (int r = 0; r < R; ++r) {
-    const float* rb = base + (size_t)r * C * ld_qkv;
-    __syncthreads();
-    for (int i = lane; i < 64 * 16; i += 64) {
-      const int key = i >> 4, c = i & 15;
-      float4 kv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (key < nk) kv = *(const float4*)(rb + (size_t)(jc * 64 + key) * ld_qkv + k_off + c * 4);
-      ((float4*)Ks)[i] = kv;
-    }
-    __syncthreads();
-    float q[64];
-    const float4* qp = (const float4*)(rb + (size_t)(qi < C ? qi : C - 1) * ld_qkv);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float4 v = qp[i];
-      q[4 * i] = v.x; q[4 * i + 1] = v.y; q[4 * i + 2] = v.z; q[4 * i + 3] = v.w;
-    }
-#pragma unroll
-    for (int key = 0; key < 64; ++key) {
-      float acc = s[key];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const float4 kv = ((const float4*)Ks)[key * 16 + c];
-        acc = fmaf(q[4 * c], kv.x, acc);
-        acc = fmaf(q[4 * c + 1], kv.y, acc);
-        acc = fmaf(q[4 * c + 2], kv.z, acc);
-        acc = fmaf(q[4 * c + 3], kv.w, acc);
-      }
-      s[key] = acc;
-    }
-  }
-  if (qi < C) {
-    float* dst = S + ((size_t)bh * C + qi) * ldS + jc * 64;
-#pragma unroll
-    for (int key = 0; key < 64; ++key)
-      if (key < nk) dst[key] = s[key] * scale;
-  }
-}
-
-__global__ __launch_bounds__(64) void msa_row_apply_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ S,
-                                                              bf16_t* __restrict__ ctx, int split_d, int R,
-                                                              int C, int H, int ld_qkv, int ld_ctx, int v_off, int n_chunk, int ldS) {
-  __shared__ __attribute__((aligned(16))) float Vs[64 * 64];
-  const int lane = threadIdx.x;
-  const int ic = blockIdx.x % n_chunk, r = (blockIdx.x / n_chunk) % R, bh = blockIdx.x / (n_chunk * R);
-  const int b = bh / H, h = bh % H;
-  const float* rb = qkv + ((size_t)b * R + r) * C * ld_qkv + h * 64;
-  const int qi = ic * 64 + lane;
-  const bool valid = qi < C;
-  const float* srow = S + ((size_t)bh * C + (valid ? qi : C - 1)) * ldS;
-  float m = -3.0e38f;
-  for (int j = 0; j < C; ++j) m = fmaxf(m, srow[j]);
-  float l = 0.f;
-  for (int j = 0; j < C; ++j) l += expf(srow[j] - m);
-  float o[64];
-#pragma unroll
-  for (int i = 0; i < 64; ++i) o[i] = 0.f;
-  for (int k0 = 0; k0 < C; k0 += 64) {
-    const int nk = (C - k0) < 64 ? (C - k0) : 64;
-    __syncthreads();
-    for (int i = lane; i < 64 * 16; i += 64) {
-      const int key = i >> 4, c = i & 15;
-      float4 vv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (key < nk) vv = *(const float4*)(rb + (size_t)(k0 + key) * ld_qkv + v_off + c * 4);
-      ((float4*)Vs)[i] = vv;
-    }
-    __syncthreads();
-    for (int key = 0; key < nk; ++key) {
-      const float p = expf(srow[k0 + key] - m);
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const float4 vv = ((const float4*)Vs)[key * 16 + c];
-        o[4 * c] = fmaf(p, vv.x, o[4 * c]);
-        o[4 * c + 1] = fmaf(p, vv.y, o[4 * c + 1]);
-        o[4 * c + 2] = fmaf(p, vv.z, o[4 * c + 2]);
-        o[4 * c + 3] = fmaf(p, vv.w, o[4 * c + 3]);
-      }
-    }
-  }
-  if (valid) store_ctx64(o, l > 0.f ? 1.0f / l : 0.f, ctx + (((size_t)b * R + r) * C + qi) * ld_ctx, h, split_d);
-}
-
 // ------------------------------------------------------------------------------------------------
 // The dispatch: pure plans (no HIP call; pg_dbg_attention_plan prints them, tests/test_attention_plan_cpu.py pins them) and one
 // launch switch per launcher, as in attention.hip.
 // ------------------------------------------------------------------------------------------------
-// PGIBBS_ATTN_F32=valu (or a negative number): the all-VALU cross-check kernels instead of the split-bf16 MFMA ones
-static bool attn_f32_valu() {
-  static const bool valu = [] { const char* e = getenv("PGIBBS_ATTN_F32"); return e && (e[0] == 'v' || atoi(e) < 0); }();
-  return valu;
-}
-
 struct StrictRowPlan {
-  std::string error;
-  bool valu = false;
-  int kb = 10;                     // split kernels: key blocks per tile, 4 (up to 64 columns) or 10
+  int kb = 10;                     // key blocks per tile, 4 (up to 64 columns) or 10
   int n_chunk = 0, n_ktile = 1;    // 64-query chunks, and key tiles of the scores kernel
   unsigned grid_scores = 0, grid_apply = 0;      // 0: nothing to launch
 };
-static StrictRowPlan plan_msa_row_f32(int B, int R, int C, int H, bool has_pad) {
+static StrictRowPlan plan_msa_row_f32(int B, int R, int C, int H) {
   StrictRowPlan p;
   if (B == 0 || R == 0) return p;
-  p.valu = attn_f32_valu();
-  if (has_pad && p.valu) { p.error = "row attention: the all-VALU cross-check kernels have no <pad> handling"; return p; }
   p.n_chunk = (C + 63) / 64;
   p.kb = C <= 64 ? 4 : 10;
-  p.n_ktile = p.valu ? p.n_chunk : (C <= 64 ? 1 : (C + 159) / 160);      // the all-VALU scores kernel: 64-key tiles
+  p.n_ktile = C <= 64 ? 1 : (C + 159) / 160;
   p.grid_scores = (unsigned)(B * H * p.n_chunk * p.n_ktile);
   p.grid_apply = (unsigned)(B * H * R * p.n_chunk);
   return p;
 }
 static std::string plan_text(const StrictRowPlan& p) {
-  if (!p.error.empty()) return "error: " + p.error;
   if (!p.grid_apply) return "nothing";
-  return (p.valu ? std::string("row-valu-f32") : "row-split-f32 kb" + std::to_string(p.kb)) + " kt" + std::to_string(p.n_ktile) + " " +
-         std::to_string(p.grid_scores) + "wg, " + std::to_string(p.grid_apply) + "wg";
+  return "row-split-f32 kb" + std::to_string(p.kb) + " kt" + std::to_string(p.n_ktile) + " " + std::to_string(p.grid_scores) + "wg, " +
+         std::to_string(p.grid_apply) + "wg";
 }
-void msa_row_f32_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text) { *text = plan_text(plan_msa_row_f32(B, R, C, H, has_pad)); }
+// <pad> tokens change what the kernels compute, not the plan
+void msa_row_f32_plan_text(int B, int R, int C, int H, std::string* text) { *text = plan_text(plan_msa_row_f32(B, R, C, H)); }
 
 int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores, bf16_t* ctx, int split_d, int B, int R,
                                  int C, int H, int ld_qkv, int ld_ctx, int k_off, int v_off, float scale, const int32_t* tok,
                                  int pad_idx) {
-  const StrictRowPlan p = plan_msa_row_f32(B, R, C, H, tok != nullptr);
-  if (!p.error.empty()) return fail(1, p.error);
+  const StrictRowPlan p = plan_msa_row_f32(B, R, C, H);
   if (!p.grid_apply) return 0;
   note_kernel(plan_text(p).c_str());
   const int ldS = msa_row_scores_ld(C);         // `scores` holds B*H*C rows of ldS floats
@@ -623,51 +416,56 @@ int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores,
     hipLaunchKernelGGL(msa_row_apply_split_kernel<KB>, dim3(p.grid_apply), dim3(256), 0, s, qkv, scores, ctx, split_d, R, C, H,
                        ld_qkv, ld_ctx, v_off, p.n_chunk, ldS);
   };
-  if (p.valu) {
-    hipLaunchKernelGGL(msa_row_scores_f32_kernel, dim3(p.grid_scores), dim3(64), 0, s, qkv, scores, R, C, H, ld_qkv, k_off, scale,
-                       p.n_chunk, ldS);
-    hipLaunchKernelGGL(msa_row_apply_f32_kernel, dim3(p.grid_apply), dim3(64), 0, s, qkv, scores, ctx, split_d, R, C, H, ld_qkv,
-                       ld_ctx, v_off, p.n_chunk, ldS);
-  } else if (p.kb == 4) {
-    split(std::integral_constant<int, 4>{});
-  } else {
-    split(std::integral_constant<int, 10>{});
-  }
+  if (p.kb == 4) split(std::integral_constant<int, 4>{});
+  else split(std::integral_constant<int, 10>{});
   PG_HIP(hipGetLastError());
   return 0;
 }
 
+// The (key blocks per tile, 16-query blocks per wave) pairs attention_split_kernel is built for -- every pair plan_attention_f32
+// can produce -- and the head widths each is built at.  Head 128 runs 64-key tiles with 1, 2 or 3 query blocks per wave; heads 64 /
+// 32 / 16 pair 64-key tiles with one query block only, so <4, 2> and <4, 3> exist at head 128 alone.
+struct SplitPair {
+  int kb, nqb;
+  bool hd128, narrow;      // built at head 128; at heads 64 (with and without ESM-1's bias key), 32 and 16
+};
+constexpr SplitPair kSplitPairs[] = {{4, 1, true, true},   {4, 2, true, false},  {4, 3, true, false},  {6, 5, false, true}, {8, 5, false, true},
+                                     {10, 1, false, true}, {10, 2, false, true}, {10, 3, false, true}, {10, 5, false, true}};
+constexpr int kNSplitPairs = sizeof(kSplitPairs) / sizeof(kSplitPairs[0]);
+// The launch switch over the pairs, as visit_rung (attn_frag.h): f(std::integral_constant<int, i>) for the entry i that is
+// <kb, nqb>, and what it returns.  false: no such pair.
+template <int I = 0, class F>
+static bool visit_split_pair(int kb, int nqb, F&& f) {
+  if constexpr (I == kNSplitPairs) {
+    return false;
+  } else {
+    if (kb != kSplitPairs[I].kb || nqb != kSplitPairs[I].nqb) return visit_split_pair<I + 1>(kb, nqb, f);
+    return f(std::integral_constant<int, I>{});
+  }
+}
+
 struct StrictAttentionPlan {
   std::string error;               // not empty: the call is refused (error code 1)
-  bool valu = false;               // attention_f32_kernel, 64 threads; else attention_split_kernel<kb, nqb>, 256 threads
-  int kb = 0, nqb = 1, hd = 64;    // key blocks per tile and 16-query blocks per wave: one of the pairs that are built
-  bool pad = false, bias = false;  // the split kernel's PADMASK / BIASKV form
+  int kb = 0, nqb = 1, hd = 64;    // key blocks per tile and 16-query blocks per wave: one of kSplitPairs
+  bool pad = false, bias = false;  // the kernel's PADMASK / BIASKV form
   unsigned grid = 0;               // 0: no sequences, nothing to launch
   int n_qchunk = 0;                // chunks of 64 * nqb queries per (sequence, head) pair
 };
-static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step) {
+static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias) {
   StrictAttentionPlan p;
-  p.hd = head_dim, p.pad = has_pad, p.bias = has_bias, p.valu = attn_f32_valu();
+  p.hd = head_dim, p.pad = has_pad, p.bias = has_bias;
   auto refuse = [&](const std::string& why) { p.error = why; return p; };
   p.error = attention_head_error(head_dim, has_bias);
   if (!p.error.empty()) return p;
-  if (head_dim != 64 && p.valu)
-    return refuse("attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 only; unset it to run heads of " +
-                  std::to_string(head_dim));
   if (n_seq == 0) return p;
   if (T <= 0) return refuse("attention: empty sequence");
-  if (has_bias && p.valu) return refuse("attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)");
-  if (has_pad && row_step != 1 && p.valu) return refuse("attention: the all-VALU cross-check kernel masks <pad> keys of contiguous chains only");
-  // 16-query blocks per wave of the split kernel (its workgroup = 64 * nqb queries, all of them against each staged K / V tile):
-  // the smallest of 1, 2, 3, 5 that covers the sequence with one workgroup, else 5 (PGIBBS_ATTN_F32_NQB overrides: A/B runs)
-  static const int nqb_env = env_int("PGIBBS_ATTN_F32_NQB", 0);
-  static const int kb_env = env_int("PGIBBS_ATTN_F32_KB", 0);   // experiment: key-tile height
+  // 16-query blocks per wave (the workgroup = 64 * nqb queries, all of them against each staged K / V tile): the smallest of 1, 2,
+  // 3, 5 that covers the sequence with one workgroup, else 5
   const int Tk = T + (has_bias ? 1 : 0);           // every form: plain, <pad> mask, ESM-1's bias key (round 5)
   const bool one_tile = Tk <= 64;                  // at most 64 keys: a single 64-key tile, one query block per wave
   const int blocks = (T + 15) / 16;
   p.nqb = blocks <= 4 ? 1 : (blocks <= 8 ? 2 : (blocks <= 12 ? 3 : 5));
-  if (nqb_env == 1 || nqb_env == 2 || nqb_env == 3 || nqb_env == 5) p.nqb = nqb_env;
-  if (p.valu || one_tile) p.nqb = 1;
+  if (one_tile) p.nqb = 1;
   p.n_qchunk = (T + 64 * p.nqb - 1) / (64 * p.nqb);
   if (n_seq * H * p.n_qchunk > 0x7fffffff) return refuse("attention: too many sequences");
   p.grid = (unsigned)(n_seq * H * p.n_qchunk);
@@ -677,17 +475,16 @@ static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int h
   if (!one_tile && p.nqb == 5) {
     // Long sequences (five query blocks per wave): the tile height of 6, 8 or 10 key blocks that pads the keys least -- the
     // kernel's time follows the padded key count (T = 258: 3 x 96 = 288 keys 18.8 ms per config-2 iteration, 2 x 160 = 320 keys
-    // 20.5, 3 x 128 = 384 keys 25.7); ties go to the taller tile.  PGIBBS_ATTN_F32_KB = 6 / 8 / 10 forces one.
+    // 20.5, 3 x 128 = 384 keys 25.7); ties go to the taller tile.
     long best = ((long)Tk + 159) / 160 * 160;
     for (int k : {8, 6}) {
       const long padded = ((long)Tk + 16 * k - 1) / (16 * k) * (16 * k);
       if (padded < best) { best = padded; p.kb = k; }
     }
-    if (kb_env == 6 || kb_env == 8 || kb_env == 10) p.kb = kb_env;
   }
   // Head 128: the four tiles (hi + lo of K and of V, 256-byte rows) are 1 KB per key, so the 80 KB that leave room for two workgroups
   // per CU hold 80 keys and the tallest even block count is 4: 64-key tiles (64 KB) at every length.  The taller tiles of heads 64 /
-  // 32 would be 96 - 160 KB, one workgroup per CU -- the form that was 1.6x slower at head 64 --, so PGIBBS_ATTN_F32_KB is not read.
+  // 32 would be 96 - 160 KB, one workgroup per CU -- the form that was 1.6x slower at head 64.
   // Five query blocks per wave would be o[5][8] = 160 accumulator registers and spill under the two-workgroup bound: three at most.
   if (head_dim == 128) {
     p.kb = 4;
@@ -703,33 +500,35 @@ static StrictAttentionPlan plan_attention_f32(int64_t n_seq, int T, int H, int h
 static std::string plan_text(const StrictAttentionPlan& p) {
   if (!p.error.empty()) return "error: " + p.error;
   if (!p.grid) return "nothing";
-  std::string t = p.valu ? "valu-f32" : "split-f32 kb" + std::to_string(p.kb) + " nqb" + std::to_string(p.nqb);
-  t += " hd" + std::to_string(p.hd);
+  std::string t = "split-f32 kb" + std::to_string(p.kb) + " nqb" + std::to_string(p.nqb) + " hd" + std::to_string(p.hd);
   if (p.pad) t += " pad";
   if (p.bias) t += " bias";
   return t + " " + std::to_string(p.grid) + "wg";
 }
-void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, std::string* text) {
-  *text = plan_text(plan_attention_f32(n_seq, T, H, head_dim, has_pad, has_bias, row_step));
+void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, std::string* text) {
+  *text = plan_text(plan_attention_f32(n_seq, T, H, head_dim, has_pad, has_bias));
 }
 
-// one (key tile, query blocks) pair of the split kernel: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32 / 128 / 16.
-// Head 128 runs 64-key tiles with 1, 2 or 3 query blocks per wave (plan_attention_f32); heads 64 / 32 / 16 pair 64-key tiles with one
-// query block only, so <4, 2> and <4, 3> exist at head 128 alone
-// false: the pair is not built at this head width and nothing was launched (the launcher turns that into an error)
-template <int KB, int NQB, class... Args>
+// entry I of kSplitPairs: its <BIASKV, PADMASK, HD> form for this call; no bias key at head 32 / 128 / 16.
+// false: the pair is not built at this head width and nothing was launched
+template <int I, class... Args>
 static bool launch_split(int hd, bool pad, bool bias, dim3 grid, hipStream_t s, Args... args) {
-  auto go = [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...); return true; };
-  if constexpr (KB == 4) {
-    if (hd == 128) return pad ? go(attention_split_kernel<KB, NQB, false, true, 128>) : go(attention_split_kernel<KB, NQB, false, false, 128>);
-  } else {
-    if (hd == 128) return false;
-  }
-  if constexpr (KB != 4 || NQB == 1) {
-    if (hd == 32) return pad ? go(attention_split_kernel<KB, NQB, false, true, 32>) : go(attention_split_kernel<KB, NQB, false, false, 32>);
-    if (hd == 16) return pad ? go(attention_split_kernel<KB, NQB, false, true, 16>) : go(attention_split_kernel<KB, NQB, false, false, 16>);
-    if (bias) return pad ? go(attention_split_kernel<KB, NQB, true, true>) : go(attention_split_kernel<KB, NQB, true, false>);
-    return pad ? go(attention_split_kernel<KB, NQB, false, true>) : go(attention_split_kernel<KB, NQB, false, false>);
+  constexpr SplitPair P = kSplitPairs[I];
+  auto form = [&](auto bias_c, auto hd_c) {
+    constexpr bool BIASKV = decltype(bias_c)::value;
+    constexpr int HD = decltype(hd_c)::value;
+    if (pad) hipLaunchKernelGGL((attention_split_kernel<P.kb, P.nqb, BIASKV, true, HD>), grid, dim3(256), 0, s, args...);
+    else hipLaunchKernelGGL((attention_split_kernel<P.kb, P.nqb, BIASKV, false, HD>), grid, dim3(256), 0, s, args...);
+    return true;
+  };
+  using std::false_type;
+  using std::integral_constant;
+  if (hd == 128) {
+    if constexpr (P.hd128) return form(false_type{}, integral_constant<int, 128>{});
+  } else if constexpr (P.narrow) {
+    if (hd == 32) return form(false_type{}, integral_constant<int, 32>{});
+    if (hd == 16) return form(false_type{}, integral_constant<int, 16>{});
+    return bias ? form(std::true_type{}, integral_constant<int, 64>{}) : form(false_type{}, integral_constant<int, 64>{});
   }
   return false;
 }
@@ -737,28 +536,15 @@ static bool launch_split(int hd, bool pad, bool bias, dim3 grid, hipStream_t s, 
 int launch_attention_f32(hipStream_t s, const float* qkv, bf16_t* ctx, int split_d, int64_t n_seq, int T, int H,
                          int ld_qkv, int ld_ctx, int k_off, int v_off, SeqLayout sl, const int32_t* key_tok, int pad_idx,
                          const float* bias_kv, int head_dim) {
-  const StrictAttentionPlan p = plan_attention_f32(n_seq, T, H, head_dim, key_tok != nullptr, bias_kv != nullptr, sl.row_step);
+  const StrictAttentionPlan p = plan_attention_f32(n_seq, T, H, head_dim, key_tok != nullptr, bias_kv != nullptr);
   if (!p.error.empty()) return fail(1, p.error);
   if (!p.grid) return 0;
   note_kernel(plan_text(p).c_str());
-  bool launched = true;
-  auto split = [&](auto kb, auto nqb) {
-    launched = launch_split<decltype(kb)::value, decltype(nqb)::value>(p.hd, p.pad, p.bias, dim3(p.grid), s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx,
-                                                            k_off, v_off, sl, p.n_qchunk, key_tok, pad_idx, bias_kv);
-  };
-  using std::integral_constant;
-  if (p.valu)
-    hipLaunchKernelGGL(attention_f32_kernel, dim3(p.grid), dim3(64), 0, s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl,
-                       p.n_qchunk, key_tok, pad_idx);
-  else if (p.kb == 4 && p.nqb == 2) split(integral_constant<int, 4>{}, integral_constant<int, 2>{});      // nqb > 1 at 64-key tiles: head 128
-  else if (p.kb == 4 && p.nqb == 3) split(integral_constant<int, 4>{}, integral_constant<int, 3>{});
-  else if (p.kb == 4) split(integral_constant<int, 4>{}, integral_constant<int, 1>{});
-  else if (p.kb == 6) split(integral_constant<int, 6>{}, integral_constant<int, 5>{});
-  else if (p.kb == 8) split(integral_constant<int, 8>{}, integral_constant<int, 5>{});
-  else if (p.nqb == 1) split(integral_constant<int, 10>{}, integral_constant<int, 1>{});
-  else if (p.nqb == 2) split(integral_constant<int, 10>{}, integral_constant<int, 2>{});
-  else if (p.nqb == 3) split(integral_constant<int, 10>{}, integral_constant<int, 3>{});
-  else split(integral_constant<int, 10>{}, integral_constant<int, 5>{});
+  const bool launched = visit_split_pair(p.kb, p.nqb, [&](auto i) {
+    return launch_split<decltype(i)::value>(p.hd, p.pad, p.bias, dim3(p.grid), s, qkv, ctx, split_d, T, H, ld_qkv, ld_ctx, k_off, v_off, sl,
+                                            p.n_qchunk, key_tok, pad_idx, bias_kv);
+  });
+  // the plan produced a pair outside kSplitPairs, or one that is not built at this head width: a bug in plan_attention_f32
   if (!launched) return fail(1, "attention: the strict kernel is not built for this (key tile, query blocks, head dimension)");
   PG_HIP(hipGetLastError());
   return 0;

@@ -119,11 +119,6 @@ inline int attention_rung(int n_keys, bool fine, int max_keys = 576) {
     if (n_keys <= r * 16) return r;
   return 0;
 }
-// PGIBBS_ATTN_LADDER=0: the coarse ladder only (same bits, more masked key blocks) -- the A/B switch of the fine ladder
-inline bool attention_fine_ladder() {
-  static const int fine = env_int("PGIBBS_ATTN_LADDER", 1);
-  return fine != 0;
-}
 // The launch switch over the ladder: f(std::integral_constant<int, kb>) for an even rung 2 ... 36, so that a launcher names its
 // kernel template once, in a generic lambda, and every rung is instantiated.  false: kb is no rung (more than 576 keys).
 template <int KB = 2, class F>

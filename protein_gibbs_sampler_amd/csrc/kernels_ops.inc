@@ -82,9 +82,9 @@ size_t msa_row_split_scratch_bytes(int B, int R, int C, int H, int order_bh);
 // device of n_cu compute units (row_step: SeqLayout's, 1 = contiguous chains); msa_row_plan_text: launch_msa_row_attention_bf16
 // with the scratch of msa_row_split_scratch_bytes on offer; the _f32 pair: the strict launchers (attention_f32.hip)
 void attention_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, int n_cu, std::string* text);
-void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, int row_step, std::string* text);
+void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, std::string* text);
 void msa_row_plan_text(int B, int R, int C, int H, int order_bh, std::string* text);
-void msa_row_f32_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text);
+void msa_row_f32_plan_text(int B, int R, int C, int H, std::string* text);
 int launch_msa_row_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int R, int C, int H, int ld_qkv,
                                   int ld_ctx, int k_off, int v_off, float scale, float* partial = nullptr,
                                   size_t partial_bytes = 0, int order_bh = 0);

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(NW * 64) void msa_row_attention_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// The dispatch, as in attention.hip: plan_msa_row is a pure function of the shape, the scratch on offer and PGIBBS_ATTN_LADDER
+// The dispatch, as in attention.hip: plan_msa_row is a pure function of the shape and the scratch on offer
 // (pg_dbg_attention_plan prints it, tests/test_attention_plan_cpu.py pins it); the launcher and the engine's scratch sizing share it.
 // ------------------------------------------------------------------------------------------------
 // Waves per workgroup on rung kb: 4 up to 64 columns, beyond that the widest the register budget of the score fragments allows
@@ -252,8 +252,8 @@ static RowPlan plan_msa_row(int B, int R, int C, int H, int order_bh, size_t scr
   if (C <= 0) return refuse(1, "row attention: empty alignment");
   if (C > 576) return refuse(5, "row attention: alignments wider than 576 token columns (<cls> + 575 residues) take the fp32-scores path");
   const int n_bh = B * H, obh = order_bh > 0 ? order_bh : n_bh;
-  // a rung for every even block count (round 4; PGIBBS_ATTN_LADDER=0: the coarse ladder only -- same bits, attn_frag.h)
-  p.kb = attention_rung(C, attention_fine_ladder());
+  // a rung for every even block count (round 4)
+  p.kb = attention_rung(C, true);
   p.nw = row_attention_waves(p.kb);
   p.n_qblk = ((C + 15) / 16 + p.nw - 1) / p.nw;
   if (obh * ((C + 63) / 64) < 384 && obh * p.n_qblk < 384 && R >= 8) {      // few (msa, head, 64-query) units: the chip would idle

@@ -8,8 +8,8 @@
 // the same three products from registers; the producer of an activation row may then leave the third block unwritten (dup = false:
 // launch_layernorm_bf16 split3_dup, EPI_SPLIT2_GELU, split_d < 0; the consumer is gemm_split3_fused's to name).
 // The pair is bf16 in either operand flavour (pg_common.h): nothing here goes through pack_op2 / op16_to_f32.
-// Writers: store_row_bf16 (ln_row.h), split3_bf16_kernel (elementwise.hip), the two split epilogues of gemm_epilogue.h, store_ctx64
-// and SplitAttn::store_ctx (attention_f32.hip; the latter from this header's pieces, its comment says why).  Readers: every GEMM (as
+// Writers: store_row_bf16 (ln_row.h), split3_bf16_kernel (elementwise.hip), the two split epilogues of gemm_epilogue.h and
+// SplitAttn::store_ctx (attention_f32.hip; from this header's pieces, its comment says why).  Readers: every GEMM (as
 // plain rows of 3 d), gemm_split3_w16_kernel and gemm_tail_tile64<SPLIT3>, split3_rows_to_host (api_dbg.hip).
 // tests/_ln_host.py store_rows_host restates it independently.
 #pragma once

@@ -3,7 +3,7 @@ uses: token batches, the 16-bit roundings, the wrapper call, the oracle's replay
 Then the test bodies that are the same at every size, each taking a --model name whose row of tests/_esm2_sizes.py holds what differs:
 tests/test_gpu_esm2_sizes.py parametrises over that table the ones that are one item per size, and each size's own file runs the ones
 with many cases (its T, H, precision and shape lists are its decorators).  A child process (the switches are read once per process) imports
-this module and calls `_single_chain_child` / `_shard_child` / `_refuse_valu_child` with the name."""
+this module and calls `_single_chain_child` / `_shard_child` with the name."""
 import ctypes
 import hashlib
 import json
@@ -339,25 +339,6 @@ def check_other_architectures_refuse_the_width(size, arch):
     m = model(getattr(models, cls), cfg, sd, "bf16")
     with pytest.raises(Exception, match=r"%s with heads of %d.*64" % (arch, SIZES[size]["hd"])):
         m.model.to("cuda:0")
-
-
-def _refuse_valu_child(size):
-    """the strict attention entry at the size's head width under PGIBBS_ATTN_F32=valu: prints the refusal"""
-    hd = SIZES[size]["hd"]
-    x = np.zeros((1, 16, 3 * 2 * hd), np.float32)
-    y = np.zeros((1, 16, 2 * hd), np.float32)
-    rc = _lib.lib().pg_dbg_attention_hd(0, _lib.PG_PREC_FP32, _lib.ptr(x), _lib.ptr(y), 1, 16, 2, hd, None, -1)
-    assert rc != 0
-    try:
-        _lib.check(rc)
-    except Exception as e:      # noqa: BLE001
-        print("CHILD_REFUSED " + str(e))
-
-
-def check_strict_valu_switch_refuses_the_width_by_name(size):
-    """PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, built for heads of 64 only: it must refuse, not run wrong."""
-    out = child(__name__, "_refuse_valu_child", size, PGIBBS_ATTN_F32="valu")
-    assert any(l.startswith("CHILD_REFUSED ") and "PGIBBS_ATTN_F32" in l and "heads of %d" % SIZES[size]["hd"] in l for l in out), out
 
 
 # ---- the sampler --------------------------------------------------------------------------------------------------------------------

@@ -66,7 +66,6 @@ SIZES = {
         # 64 chains x 20 heads at 18 key blocks: the whole job and the 32- and 8-chain shards each end in a partial round that the
         # attention launch splits -- and with PGIBBS_ATTN_SPLIT=0 (read once per process: a child) the same bits come out
         shards=dict(case=dict(n_layers=3), worlds=(2, 8), B=64, split_child=True),
-        valu=True,
     ),
     "esm2_15b": dict(
         hd=128, shape=(5120, 48, 40, 20480), max_heads=40, cut=(256, 2), other_table=64,
@@ -82,7 +81,6 @@ SIZES = {
         single_chain=dict(n_layers=3, seed=13),
         # 18 key blocks: one workgroup per CU; 2, 4 and 8 contiguous shards
         shards=dict(case=dict(n_layers=3), worlds=(2, 4, 8), B=64, split_child=False),
-        valu=True,
     ),
     "esm2_8m": dict(
         hd=16, shape=(320, 6, 20, 1280), max_heads=32, cut=(128, 8), other_table=32,
@@ -101,7 +99,6 @@ SIZES = {
         # quarter that the attention launch splits; the 32- and 8-chain shards are partial rounds -- and with PGIBBS_ATTN_SPLIT=0 (read
         # once per process: a child) the same bits come out
         shards=dict(case=dict(n_layers=3), worlds=(2, 8), B=64, split_child=True),
-        valu=True,
     ),
     "esm2_35m": dict(
         hd=24, shape=(480, 12, 20, 1920), max_heads=32, other_table=32,
@@ -122,7 +119,6 @@ SIZES = {
         sampler=dict(n_layers=4), seq=LONG_SEQ,
         single_chain=dict(n_layers=3, seed=13),
         shards=dict(case=dict(n_layers=3), worlds=(2, 4, 8), B=64, split_child=False),
-        valu=None,                                                               # the strict attention entry has no heads of 24 to refuse
     ),
 }
 for _cli, _row in SIZES.items():

@@ -163,34 +163,10 @@ def test_refusals():
     check(REFUSED)
 
 
-VALU_REFUSED = [
-    (strict(2, 258, hd=32), "error: attention: PGIBBS_ATTN_F32=valu selects the all-VALU cross-check kernel, which is built for heads of 64 "
-                            "only; unset it to run heads of 32"),
-    (strict(3, 258, H=12, bias=1), "error: attention: the all-VALU cross-check kernel has no bias_k / bias_v key (ESM-1)"),
-    (strict(513, 128, H=12, row_step=513, pad=1), "error: attention: the all-VALU cross-check kernel masks <pad> keys of contiguous chains only"),
-    (row(2, 8, 64, precision=FP32, pad=1), "error: row attention: the all-VALU cross-check kernels have no <pad> handling"),
-]
 # the switches: name -> (environment, table)
 SWITCHED = {
-    "coarse ladder only": ({"PGIBBS_ATTN_LADDER": "0"}, [
-        (att(8, 200), "whole kb18 hd64 split3 0+480wg"), (att(8, 65), "whole kb8 hd64 160wg"), (att(2, 289, pad=1), "whole kb24 hd64 pad 40wg"),
-        (att(256, 258), "whole kb18 hd64 5120wg"), (row(64, 32, 140), "row kb12 w9 rc1 768wg"),
-        (row(1, 32, 301), "row kb24 w8 rc8 288wg, reduce 288x1w, 288wg")]),
     "no split of the last round": ({"PGIBBS_ATTN_SPLIT": "0"}, [
         (att(32, 258), "whole kb18 hd64 640wg"), (att(33, 258), "whole kb18 hd64 660wg"), (att(64, 258, hd=32), "whole kb18 hd32 1280wg")]),
-    "all-VALU cross-check": ({"PGIBBS_ATTN_F32": "valu"}, [
-        (strict(256, 258), "valu-f32 hd64 25600wg"),                   # five 64-query chunks per pair, 64 threads each
-        (strict(2, 27), "valu-f32 hd64 40wg"),
-        (strict(2, 100, pad=1), "valu-f32 hd64 pad 80wg"),
-        (row(1, 128, 513, precision=FP32), "row-valu-f32 kt9 972wg, 13824wg"),
-        (att(32, 258), "whole kb18 hd64 split4 512+512wg")] + VALU_REFUSED),        # the 16-bit launchers do not read the switch
-    "one query block per wave": ({"PGIBBS_ATTN_F32_NQB": "1"}, [
-        (strict(2, 258), "split-f32 kb10 nqb1 hd64 200wg"), (strict(2, 27), "split-f32 kb4 nqb1 hd64 40wg")]),
-    "two query blocks per wave": ({"PGIBBS_ATTN_F32_NQB": "2"}, [(strict(2, 258), "split-f32 kb10 nqb2 hd64 120wg")]),
-    "five query blocks per wave": ({"PGIBBS_ATTN_F32_NQB": "5"}, [(strict(2, 100), "split-f32 kb8 nqb5 hd64 40wg")]),      # 128 padded keys against 160, 192
-    "key tiles of 10 blocks": ({"PGIBBS_ATTN_F32_KB": "10"}, [
-        (strict(2, 258), "split-f32 kb10 nqb5 hd64 40wg"), (strict(2, 129), "split-f32 kb10 nqb3 hd64 40wg")]),
-    "key tiles of 8 blocks": ({"PGIBBS_ATTN_F32_KB": "8"}, [(strict(2, 258), "split-f32 kb8 nqb5 hd64 40wg")]),
 }
 
 
@@ -198,6 +174,16 @@ SWITCHED = {
 def test_switches(name):
     env, table = SWITCHED[name]
     check(table, **env)
+
+
+def test_removed_switches_are_inert():
+    """the names of the switches that left the library (the all-VALU strict kernels, forced strict tile pairs, the coarse ladder, the
+    tiled kernel at head 128) select nothing any more: every default text, and a head-128 chain at T = 258 on the whole-sequence kernel"""
+    removed = dict(PGIBBS_ATTN_F32="valu", PGIBBS_ATTN_F32_NQB="1", PGIBBS_ATTN_F32_KB="10", PGIBBS_ATTN_LADDER="0", PGIBBS_ATTN_HD128_WHOLE="0")
+    table, hd128 = CHAINS + STRICT + ROWS, list(att(256, 258, H=40, hd=128))
+    got = plans([list(c) for c, _ in table] + [hd128], **removed)
+    assert got[:-1] == [w for _, w in table]
+    assert got[-1:] == plans([hd128]) and got[-1].startswith("whole kb18 hd128 ")
 
 
 def test_other_cu_counts():

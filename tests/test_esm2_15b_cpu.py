@@ -78,11 +78,6 @@ def test_attention_plans_at_head_128():
     assert not wrong, "\n".join("%r: plan %r, expected %r" % t for t in wrong)
 
 
-def test_strict_valu_switch_refuses_heads_of_128_by_name():
-    got = plans([list(strict(2, 27, H=2, hd=128))], PGIBBS_ATTN_F32="valu")
-    assert "PGIBBS_ATTN_F32=valu" in got[0] and "heads of 128" in got[0] and got[0].startswith("error: ")
-
-
 # ---- rows wider than 2560 features -----------------------------------------------------------------------------------------------------
 def _ln_rows(M, d):
     x = np.zeros((M, d), np.float32)

@@ -101,11 +101,6 @@ def test_attention_plans_at_head_16():
     assert not wrong, "\n".join("%r: plan %r, expected %r" % t for t in wrong)
 
 
-def test_strict_valu_switch_refuses_heads_of_16_by_name():
-    got = plans([list(strict(2, 27, H=2, hd=16))], PGIBBS_ATTN_F32="valu")
-    assert "PGIBBS_ATTN_F32=valu" in got[0] and "heads of 16" in got[0] and got[0].startswith("error: ")
-
-
 def test_gemm_plans_at_the_8m_shapes():
     """N = 320 / 960 are no multiples of 128: 64 x 64 tiles at every height above the weight-streaming kernel's; fc1 (N = 1280,
     K = 320) is a shape of the 256 x 256 kernels at config 2; a single chain (32 rows) streams the weights."""

@@ -4,7 +4,7 @@ reference of tests/_attention_reference.py, element by element under the bound d
   * attention_kernel / attention_long_kernel at every edge of the key-block ladder, head dimensions 64 and 32, bf16 and fp16 operands,
     plain, with <pad> keys, with ESM-1's bias key and with both, the SPLIT form, on six input families (gaussian, negative scores,
     late maximum on the last key / on the first key of the last 288-key tile, unity, integer-coded v);
-  * the strict kernels (split-bf16 MFMA and, in a child process, the all-VALU ones) at their tile edges;
+  * the strict kernels (split-bf16 MFMA) at their tile edges;
   * the MSA column attention with <pad> rows and an all-<pad> column in the three precisions, the padded tied-row attention on the
     engine's route below and above 576 columns, the plain tied-row attention whole and split over the rows.
 
@@ -86,8 +86,7 @@ def _check_chain(fmt, T, hd, pad, bias, families, n_seq=None, H=None, want_split
             kernel, form = "hd32", form if kb else {"plain": "long", "pad": "long pad"}[form]
     else:
         kernel, form = "strict hd%d" % hd, _form(pad, bias)
-        valu = os.environ.get("PGIBBS_ATTN_F32", "").startswith("v")
-        assert ("valu-f32" if valu else "split-f32") in want and (" pad" in want) == pad and (" bias" in want) == bias, want
+        assert "split-f32" in want and (" pad" in want) == pad and (" bias" in want) == bias, want
     live = np.ones((n_seq, T), bool) if tok is None else tok != ar.PAD
     for family in families:
         if family == "late_tile" and T <= 288:
@@ -171,29 +170,6 @@ STRICT_LENGTHS = [64, 65, 160, 161, 288, 289, 700]
 def test_strict_attention_forms(T):
     for hd, pad, bias in ((64, False, False), (64, True, False), (64, False, True), (64, True, True), (32, False, False), (32, True, False)):
         _check_chain("f32", T, hd, pad, bias, FAMILIES)
-
-
-_VALU_CHILD = r"""
-import sys
-sys.path.insert(0, %r)
-sys.path.insert(0, %r)
-import test_gpu_attention_kernels as t
-for T in t.STRICT_LENGTHS:
-    for pad in (False, True):
-        t._check_chain("f32", T, 64, pad, False, t.FAMILIES)
-assert t.SEEN == {("strict hd64", "plain"), ("strict hd64", "pad")}
-print("valu kernels OK")
-"""
-
-
-def test_valu_attention_kernel_meets_the_same_bounds():
-    """PGIBBS_ATTN_F32=valu (read once per process, hence the child): the all-VALU kernel, plain and with <pad> keys of chains -- the
-    two forms it has"""
-    env = dict(os.environ, PGIBBS_ATTN_F32="valu")
-    p = subprocess.run([sys.executable, "-c", _VALU_CHILD % (ROOT, os.path.join(ROOT, "tests"))], capture_output=True, text=True, env=env,
-                       timeout=600, cwd=ROOT)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
-    assert "valu kernels OK" in p.stdout
 
 
 # ---- MSA ---------------------------------------------------------------------------------------------------------------------------------

@@ -34,12 +34,6 @@ def test_auto_precision_and_synthetic_default(size):
     common.check_auto_precision(size)
 
 
-# ---- refusals -----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("size", having("valu"))
-def test_strict_valu_switch_refuses_the_width_by_name(size):
-    common.check_strict_valu_switch_refuses_the_width_by_name(size)
-
-
 # ---- the sampler --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", having("sampler"))
 def test_sampler_positions_draws_and_likelihoods(size):

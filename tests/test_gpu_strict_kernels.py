@@ -3,9 +3,7 @@ float64 numpy on the UNROUNDED fp32 inputs -- no bf16 rounding is granted to the
 
   * the projection: one bf16 MFMA GEMM over the K-concatenated split operands [xl | xh | xh] . [wh | wl | wh]^T (engine.h dense3),
   * attention: q, k, v and P split into bf16 (hi, lo) pairs, three MFMAs per product (csrc/attention_f32.hip) -- whole-sequence,
-    multi-tile (online softmax), tied-row scores + apply, column layout,
-  * the all-VALU fp32 attention kernels (PGIBBS_ATTN_F32=valu, read once per process -> child process) as an independent
-    second implementation: both must agree with numpy to the same bound.
+    multi-tile (online softmax), tied-row scores + apply, column layout.
 
 Outputs come back as hi + lo of the operand rows the kernels write (16 mantissa bits), so the bound is ~2^-16 relative.
 """
@@ -196,30 +194,6 @@ def test_strict_msa_attention(B, R, C, H):
         _lib.check(_lib.lib().pg_dbg_msa_attention(0, which, _lib.ptr(qkv), _lib.ptr(ctx), B, R, C, H, float(scale)))
         err = np.abs(ctx - ref).max()
         assert err < REL * max(1.0, np.abs(ref).max()), (which, err)
-
-
-_CHILD = r"""
-import sys
-import numpy as np
-sys.path.insert(0, %r)
-sys.path.insert(0, %r)
-import test_gpu_strict_kernels as t
-for c in t.ATT_CASES[:6]:
-    t.test_strict_attention(*c)
-for c in t.MSA_CASES[:5]:
-    t.test_strict_msa_attention(*c)
-print("valu kernels OK")
-"""
-
-
-def test_valu_attention_kernels_agree_too():
-    """PGIBBS_ATTN_F32=valu selects the all-VALU fp32 kernels: an independent formulation (no MFMA, no operand split, thread per
-    query) that must meet the same bound against numpy -- a cross-check that the bound above is not an artefact of the split."""
-    env = dict(os.environ, PGIBBS_ATTN_F32="valu")
-    p = subprocess.run([sys.executable, "-c", _CHILD % (ROOT, os.path.join(ROOT, "tests"))], capture_output=True, text=True, env=env,
-                       timeout=900, cwd=ROOT)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
-    assert "valu kernels OK" in p.stdout
 
 
 # ---- split3_bf16_kernel, the only writer of the weight order: bit for bit against the host restatement ------------------------------

@@ -92,8 +92,6 @@ def expected_launches(text, prec):
         return [(ns + "attention_long_kernel<18,2,%s,%s,%d>" % (b(pad), b(bias), num("hd")), wg[0], 256)]
     if w[0] == "split-f32":
         return [("pg::opbf16::attention_split_kernel<%d,%d,%s,%s,%d>" % (num("kb"), num("nqb"), b(bias), b(pad), num("hd")), wg[0], 256)]
-    if w[0] == "valu-f32":
-        return [("pg::opbf16::attention_f32_kernel", wg[0], 64)]
     if w[0] == "row":
         k, nw = num("kb"), num("w")
         name = ns + "msa_row_attention_kernel<%d,%d,%%d>" % (k, nw)
@@ -103,8 +101,6 @@ def expected_launches(text, prec):
         return [(name % 1, wg[0], nw * 64), (name % 3, red, 64), (name % 2, wg[1], nw * 64)]
     if w[0] == "row-split-f32":
         return [("pg::opbf16::msa_row_scores_split_kernel<%d>" % num("kb"), wg[0], 256), ("pg::opbf16::msa_row_apply_split_kernel<%d>" % num("kb"), wg[1], 256)]
-    if w[0] == "row-valu-f32":
-        return [("pg::opbf16::msa_row_scores_f32_kernel", wg[0], 64), ("pg::opbf16::msa_row_apply_f32_kernel", wg[1], 64)]
     raise ValueError(text)
 
 
@@ -115,7 +111,7 @@ def read_trace(out_dir):
         with open(path, newline="") as f:
             for r in csv.DictReader(f):
                 name = r["Kernel_Name"]
-                if not re.search(r"attention_(long_|split_|f32_)?kernel|msa_row_\w+_kernel", name):
+                if not re.search(r"attention_(long_|split_)?kernel|msa_row_\w+_kernel", name):
                     continue
                 wgs = int(r.get("Workgroup_Size_X") or r["Workgroup_Size"])
                 grid = int(r.get("Grid_Size_X") or r["Grid_Size"])
