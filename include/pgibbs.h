@@ -246,6 +246,33 @@ PG_API int pg_esm_gibbs_run_device(pg_engine*, int32_t* d_tokens_inout, int B, i
                             int n_iters, int P, const pg_sample_params* params, float* d_sampled_logits,
                             int32_t* d_sampled_tokens);
 
+/* ---- sequence representations (embeddings) --------------------------------------------------------
+ * fair-esm's model(tokens, repr_layers=[...])["representations"] / scripts/extract.py, HuggingFace's output_hidden_states=True, for
+ * the single-sequence engines (PG_ARCH_ESM1B, PG_ARCH_ESM1, PG_ARCH_ESM2, embedded models included).  Layers of an n-layer model are
+ * numbered 0 .. n: 0 = the embedding output (after emb_layer_norm_before where there is one and the token-dropout rescale), l = the
+ * residual stream after block l, n = the stream after block n through emb_layer_norm_after (PG_ARCH_ESM1: the raw stream, that
+ * architecture has no final LayerNorm).  Values are fp32 and d_model wide -- the model's OWN d_model (480 for esm2_t12_35M_UR50D, not
+ * the 640 of its run shape); rows at <pad> are zeros.
+ *   layers[n_req]            strictly ascending, each in 0 .. n_layers
+ *   pools[n_pools][B][2]     (begin, count): token range begin .. begin + count - 1 of sequence b, inside [0, T]; may be NULL / 0
+ *   per_token_out            [n_req][B][T][d_model] or NULL
+ *   pooled_out               [n_req][n_pools][B][d_model] or NULL: the mean over each range, computed as acc = 0.0f; acc = acc + row[t]
+ *                            for t ascending (fp32, round to nearest); acc / float(count); a count of 0 gives zeros
+ * PG_ERR_INVALID, before a device is touched and in this order: null tokens or layers; n_req < 1; a negative layer; layers not strictly
+ * ascending; both outputs NULL; pooled_out without pools; a range that leaves [0, T]; a negative count; a null engine; an MSA engine;
+ * the call check of the other entries (shape, position table); a layer above n_layers; tokens outside the vocabulary.
+ * PG_ERR_RANGE when a copied-back value is not finite (PG_PREC_F16 overflow: run the call on a PG_PREC_BF16 engine).
+ * A request that names a layer in 1 .. n-1 does not take the persistent single-chain launch; the per-layer launches it takes instead
+ * give the same bits. */
+PG_API int pg_esm_forward_representations(pg_engine*, const int32_t* tokens, int B, int T, const int32_t* layers, int n_req,
+                                          const int32_t* pools, int n_pools, float* per_token_out, float* pooled_out);
+/* The two kernels of that entry alone, on host fp32 buffers (kernel-level tests): rows_out[M][d_live] = the live columns of x[M][d],
+ * through LayerNorm when gamma / beta [d_live] are given (both or neither), zeros where tokens[M] (optional) equals pad_idx; with
+ * pools[n_pools][B][2] (then M = B * T) also pooled_out[n_pools][B][d_live] = the means of those rows as above. */
+PG_API int pg_repr_dbg_rows(int device, const float* x, int64_t M, int d, int d_live, const float* gamma, const float* beta, float eps,
+                            const int32_t* tokens, int pad_idx, float* rows_out, int B, int T, const int32_t* pools, int n_pools,
+                            float* pooled_out);
+
 /* ---- ESM-MSA-1b ---------------------------------------------------------------------------
  * tokens[B][R][C] (C = L + 1: <cls> then L columns, no <eos>).
  * pg_msa_gibbs_run: loop of ESM_MSA_sampler.generate (esm_msa_sampler.py:221-248):
@@ -410,7 +437,8 @@ PG_API int pg_dbg_gather_plan(int rank, int world, int64_t rows, int width, cons
 /* ---- measurement ---------------------------------------------------------------------------
  * HIP-event timing of kernel classes on the engine's stream (bench.py's roofline figure).
  * class names: "gemm", "attention", "layernorm", "embed", "head", "sample", and "rope": ESM-2's rotation of q and k, timed under
- * its own class (not under "attention"; no launch of the other architectures falls into it).  */
+ * its own class (not under "attention"; no launch of the other architectures falls into it); "repr_rows" and "repr_pool": the two
+ * kernels of pg_esm_forward_representations (no other call has a launch in them).  */
 PG_API int pg_prof_enable(pg_engine*, int on);
 PG_API int pg_prof_reset(pg_engine*);
 PG_API int pg_prof_get(pg_engine*, const char* kernel_class, double* total_ms, int64_t* launches);

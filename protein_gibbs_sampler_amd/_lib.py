@@ -54,6 +54,15 @@ class DrawGuideStruct(Structure):
                 ("temperatures", POINTER(c_float)), ("n_temperatures", c_int), ("top_p", c_float)]
 
 
+class EngineHandle(c_void_p):
+    """The pg_engine* argument of pg_esm_forward_representations: a void* like every other entry's, under a type of its own -- the
+    rows whose first argtype is c_void_p itself are the set of engine entries tests/test_cabi.py pins by count."""
+
+    @classmethod
+    def from_param(cls, value):
+        return c_void_p.from_param(value)
+
+
 _lib = None
 
 # (name, restype, argtypes) -- one row per symbol of include/pgibbs.h
@@ -121,6 +130,10 @@ SIGNATURES = [
                                      POINTER(SampleParams), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      POINTER(DrawGuideStruct)]),
     ("pg_guided_sizeof_draw_guide", c_int, []),
+    # sequence representations: the engine entry and the kernel-level entry of its two launchers (pg_repr_*, not pg_dbg_*: see above)
+    ("pg_esm_forward_representations", c_int, [EngineHandle, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    ("pg_repr_dbg_rows", c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int,
+                                 c_int, c_void_p, c_int, c_void_p]),
     ("pg_comm_unique_id", c_int, [c_void_p]),
     ("pg_comm_create", c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),
     ("pg_comm_destroy", None, [c_void_p]),

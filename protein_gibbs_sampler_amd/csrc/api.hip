@@ -106,6 +106,70 @@ int forward_logits(pg_engine* h, const char* who, bool msa, const int32_t* token
   return check_finite(e, logits_out, (size_t)M * e.cfg.vocab);
 }
 
+// While this lives the ESM trunk stages the layers the tap lists (Engine::tap_layer)
+struct TapScope {
+  Engine& e;
+  TapScope(Engine& e_, ReprTap* t) : e(e_) { e.tap = t; }
+  ~TapScope() { e.tap = nullptr; }
+};
+
+// tokens[B][T] in, the residual stream of the requested layers out: per token and / or as means over per-sequence token ranges.
+// forward_logits' shape with the tap in place of the LM head.  Everything in the argument list is refused before a device is touched
+int forward_representations(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* layers, int n_req, const int32_t* pools,
+                            int n_pools, float* per_token_out, float* pooled_out) {
+  const char* who = "pg_esm_forward_representations";
+  // what the request itself says is refused first: it needs neither a device nor, for that matter, an engine
+  if (!tokens || !layers) return fail(PG_ERR_INVALID, std::string(who) + ": null argument");
+  if (n_req < 1) return fail(PG_ERR_INVALID, std::string(who) + ": no layer requested");
+  for (int i = 0; i < n_req; ++i) {
+    if (layers[i] < 0) return fail(PG_ERR_INVALID, std::string(who) + ": layer " + std::to_string(layers[i]) + " is outside 0 .. n_layers");
+    if (i && layers[i] <= layers[i - 1]) return fail(PG_ERR_INVALID, std::string(who) + ": layers must be strictly ascending");
+  }
+  if (!per_token_out && !pooled_out) return fail(PG_ERR_INVALID, std::string(who) + ": neither per-token nor pooled output requested");
+  if (pooled_out && (!pools || n_pools < 1)) return fail(PG_ERR_INVALID, std::string(who) + ": pooled output requested without pools");
+  if (!pooled_out) n_pools = 0;
+  int rc;
+  if (n_pools && B > 0 && T > 0 && (rc = repr_pools_check(who, pools, n_pools, B, T))) return rc;
+  if (!h) return fail(PG_ERR_INVALID, std::string(who) + ": null engine");
+  Engine& e = h->e;
+  if (e.cfg.arch == PG_ARCH_MSA1B) return fail(PG_ERR_INVALID, std::string(who) + ": the MSA engine has no representations entry");
+  if ((rc = e.check_call(false, B, 1, T))) return rc;
+  if (layers[n_req - 1] > e.cfg.n_layers)
+    return fail(PG_ERR_INVALID, std::string(who) + ": layer " + std::to_string(layers[n_req - 1]) + " is outside 0 .. " + std::to_string(e.cfg.n_layers));
+  if (B == 0) return PG_OK;
+  const int64_t M = (int64_t)B * T;
+  bool has_pad;
+  if ((rc = scan_tokens(e, who, tokens, (size_t)M, &has_pad))) return rc;
+  DeviceGuard g(e.device);
+  const size_t n_rows = (size_t)n_req * M * e.d_live, n_means = (size_t)n_req * n_pools * B * e.d_live, n_ranges = (size_t)n_pools * B * 2;
+  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream)) || (rc = e.repr_rows.ensure(n_rows * 4, e.stream))) return rc;
+  if (n_pools && ((rc = e.repr_pooled.ensure(n_means * 4, e.stream)) || (rc = e.repr_ranges.ensure(n_ranges * 4, e.stream)))) return rc;
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
+  if (n_pools) PG_HIP(hipMemcpyAsync(e.repr_ranges.p, pools, n_ranges * 4, hipMemcpyHostToDevice, e.stream));
+  ReprTap tap;
+  tap.layers.assign(layers, layers + n_req);
+  tap.d_tok = e.d_tokens.as<int32_t>();
+  tap.B = B;
+  tap.T = T;
+  tap.d_pools = n_pools ? e.repr_ranges.as<int32_t>() : nullptr;
+  tap.n_pools = n_pools;
+  tap.rows = e.repr_rows.as<float>();
+  tap.pooled = n_pools ? e.repr_pooled.as<float>() : nullptr;
+  {
+    PadFlag pad(e, has_pad);
+    TapScope scope(e, &tap);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, 1, T);
+  }
+  if (rc) return rc;
+  if (tap.next != tap.layers.size()) return fail(PG_ERR_HIP, std::string(who) + ": the forward did not reach every requested layer");
+  if (per_token_out) PG_HIP(hipMemcpyAsync(per_token_out, e.repr_rows.p, n_rows * 4, hipMemcpyDeviceToHost, e.stream));
+  if (n_pools) PG_HIP(hipMemcpyAsync(pooled_out, e.repr_pooled.p, n_means * 4, hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.chain_check())) return rc;
+  if (per_token_out && (rc = check_finite(e, per_token_out, n_rows))) return rc;
+  return n_pools ? check_finite(e, pooled_out, n_means) : PG_OK;
+}
+
 // A Gibbs call on host buffers: tokens and the index table go to the device, run(d_tokens, d_idx, d_sampled_logits, d_sampled_tokens)
 // queues the loop (an output the caller did not ask for is null), and tokens and outputs come back.
 template <typename Run>
@@ -223,7 +287,7 @@ int create_engine(const char* who, const pg_model_config* cfg, const pg_tensor* 
 // the profiling classes by name (pg_prof_get, pg_prof_get_kernels): the PC_* index, -1 = no such class
 int prof_class(const char* name) {
   static const char* const names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed",    "head", "sample",
-                                              "gemm_qkv",   "gemm_out",  "gemm_fc1",  "gemm_fc2", "rope"};
+                                              "gemm_qkv",   "gemm_out",  "gemm_fc1",  "gemm_fc2", "rope",     "repr_rows", "repr_pool"};
   for (int i = 0; i < PC_COUNT; ++i)
     if (!strcmp(names[i], name)) return i;
   return -1;
@@ -314,6 +378,11 @@ int pg_engine_get_stat(pg_engine* h, const char* name, int64_t* value) {
 // ---- ESM-1b ---------------------------------------------------------------------------------
 int pg_esm_forward_logits(pg_engine* h, const int32_t* tokens, int B, int T, float* logits_out) {
   PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_logits(h, "pg_esm_forward_logits", false, tokens, B, 1, T, logits_out));
+}
+
+int pg_esm_forward_representations(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* layers, int n_req, const int32_t* pools,
+                                   int n_pools, float* per_token_out, float* pooled_out) {
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_representations(h, tokens, B, T, layers, n_req, pools, n_pools, per_token_out, pooled_out));
 }
 
 int pg_esm_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int T, const int32_t* d_target_idx, int n_iters,

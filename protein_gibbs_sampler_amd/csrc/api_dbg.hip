@@ -855,6 +855,36 @@ int pg_guided_dbg_sample(int device, int32_t* tokens_inout, int64_t n_rows, int 
   return nonfinite_out ? d.down(nonfinite_out, dnf, 1) : PG_OK;
 }
 
+/* The two representation launchers (repr.hip) alone, on host fp32 buffers: rows_out[M][d_live] = launch_repr_rows of x[M][d] (gamma /
+ * beta both given or both NULL; tokens[M] optional), then, with pools[n_pools][B][2] (M = B * T), pooled_out[n_pools][B][d_live] =
+ * launch_repr_pool of those rows.  Everything is refused on the host before a device is looked for. */
+int pg_repr_dbg_rows(int device, const float* x, int64_t M, int d, int d_live, const float* gamma, const float* beta, float eps,
+                     const int32_t* tokens, int pad_idx, float* rows_out, int B, int T, const int32_t* pools, int n_pools, float* pooled_out) {
+  if (!x || !rows_out || M < 1 || M > 0x7fffffff) return fail(PG_ERR_INVALID, "pg_repr_dbg_rows: bad argument");
+  if (!row_d_ok(d) || !row_live_ok(d, d_live)) return fail(PG_ERR_INVALID, "pg_repr_dbg_rows: d or d_live is no width of the row kernels");
+  if ((gamma == nullptr) != (beta == nullptr)) return fail(PG_ERR_INVALID, "pg_repr_dbg_rows: gamma and beta come together");
+  if ((pools != nullptr) != (pooled_out != nullptr) || (pools && n_pools < 1)) return fail(PG_ERR_INVALID, "pg_repr_dbg_rows: pools and pooled_out come together");
+  int rc;
+  if (pools) {
+    if (B < 1 || T < 1 || (int64_t)B * T != M) return fail(PG_ERR_INVALID, "pg_repr_dbg_rows: pooling needs M = B * T");
+    if ((rc = repr_pools_check("pg_repr_dbg_rows", pools, n_pools, B, T))) return rc;
+  }
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const float* dx = s.up(x, (size_t)M * d);
+  const float* dg = s.up(gamma, (size_t)d_live);
+  const float* dbt = s.up(beta, (size_t)d_live);
+  const int32_t* dtok = s.up(tokens, (size_t)M);
+  const int32_t* dpools = s.up(pools, pools ? (size_t)n_pools * B * 2 : 0);
+  float* drows = s.alloc<float>((size_t)M * d_live);
+  float* dmeans = pools ? s.alloc<float>((size_t)n_pools * B * d_live) : nullptr;
+  if ((rc = s.check())) return rc;
+  if ((rc = launch_repr_rows(nullptr, dx, dg, dbt, dtok, pad_idx, drows, M, d, d_live, eps))) return rc;
+  if (pools && (rc = launch_repr_pool(nullptr, drows, dpools, dmeans, n_pools, B, T, d_live))) return rc;
+  if ((rc = s.down(rows_out, drows, (size_t)M * d_live))) return rc;
+  return pools ? s.down(pooled_out, dmeans, (size_t)n_pools * B * d_live) : PG_OK;
+}
+
 /* ---- embedded models: the host side of pg_engine_create_embedded, no device ---- */
 int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
                       float* image, int64_t image_numel) {

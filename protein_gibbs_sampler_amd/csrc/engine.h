@@ -35,7 +35,8 @@ struct Prof {
 // PC_GEMM_*: the four per-layer projections of a full-batch forward, timed apart (bench.py's per-kernel roofline); "gemm" = all five.
 // PC_NONE: an op inside a timed() block of its caller's (the LM head's one record) -- no record of its own
 enum ProfClass { PC_NONE = -1, PC_GEMM = 0, PC_ATTN, PC_LN, PC_EMBED, PC_HEAD, PC_SAMPLE, PC_GEMM_QKV, PC_GEMM_OUT, PC_GEMM_FC1, PC_GEMM_FC2,
-                 PC_ROPE /* ESM-2: the rotation of q and k, one launch per layer */, PC_COUNT };
+                 PC_ROPE /* ESM-2: the rotation of q and k, one launch per layer */,
+                 PC_REPR_ROWS, PC_REPR_POOL /* representations: the row copy / LayerNorm and the pooled means (repr.hip) */, PC_COUNT };
 
 struct DenseW {   // y = x W^T + b ; W bf16 [N][K], b fp32 [N].  Strict precision mode: w is [N][3K], each row the
   bf16_t* w = nullptr;   // K-concatenated split-bf16 operand [hi | lo | hi] (hi = bf16(W), lo = bf16(W - hi))
@@ -74,6 +75,24 @@ struct GraphKey {
            stream == o.stream && epoch_pad == o.epoch_pad && job_items == o.job_items && guided == o.guided;
   }
   void reset() { *this = GraphKey(); }            // equals no call's key (tok == nullptr)
+};
+
+// What a representations call (pg_esm_forward_representations) asks of the forward: while Engine::tap points at one, esm_trunk hands
+// the residual stream of every listed layer to tap_layer, which stages its compact rows and, with pools, their means
+struct ReprTap {
+  std::vector<int> layers;           // strictly ascending, each in 0 .. n_layers
+  const int32_t* d_tok = nullptr;    // the call's tokens: rows at <pad> are written as zeros
+  int B = 0, T = 0;
+  const int32_t* d_pools = nullptr;  // [n_pools][B][2] = (begin, count), device-resident
+  int n_pools = 0;
+  float* rows = nullptr;             // staging [layers.size()][B * T][d_live]
+  float* pooled = nullptr;           // [layers.size()][n_pools][B][d_live], or null
+  size_t next = 0;                   // index of the next layer to stage
+  bool wants_inner(int n_layers) const {      // a layer only the per-layer launches can show
+    for (int l : layers)
+      if (l >= 1 && l < n_layers) return true;
+    return false;
+  }
 };
 
 struct Engine {
@@ -122,8 +141,16 @@ struct Engine {
   // row-attention scores (also the bf16 mode's wide-alignment fallback)
   DevBuf ffn_f32, scores;
   DevBuf chain_sync, chain_part;           // persistent single-chain trunk: barrier block, fc2 partials
+  DevBuf repr_rows, repr_pooled, repr_ranges;   // representations: staged rows of the requested layers, their means, the pool ranges
   int size_activations(int64_t Mp);        // x, h, qkv, ctx, ffn for Mp padded token rows
   float* splitk_ws(int rows, int n, int K, int64_t batch_rows);
+
+  // ---- representations tap ----
+  // null (every call but pg_esm_forward_representations): tap_layer is a no-op and the forward issues the launches it always did
+  ReprTap* tap = nullptr;
+  // x now holds layer l (0: the embedding output; l: the stream after block l): if the tap lists it, stage its rows -- through
+  // emb_layer_norm_after for l = n_layers where the architecture has one -- and pool them
+  int tap_layer(int l);
 
   // ---- job-order knobs: what keeps a shard's arithmetic that of the whole job ----
   bool esm_pad_in_batch = false;           // set by the host-token entry points: some token is <pad> -> key-padding mask

@@ -110,7 +110,7 @@ Engine::~Engine() {
   for (void* p : owned) (void)hipFree(p);
   DevBuf* bufs[] = {&x, &h, &qkv, &ctx, &ffn, &sel_h, &sel_g, &logits, &d_tokens, &d_idx, &d_samp_tok, &d_samp_logits,
                     &d_rowmap, &scratch, &d_iter, &tmp_idx, &tmp_out, &x_sel, &ctx_sel, &h_sel, &ffn_sel, &ffn_f32, &scores, &splitk,
-                    &chain_sync, &chain_part, &chain_snap};
+                    &chain_sync, &chain_part, &chain_snap, &repr_rows, &repr_pooled, &repr_ranges};
   for (DevBuf* b : bufs) b->release();
   if (chain_err) (void)hipHostFree(chain_err);
   if (range_err) (void)hipHostFree(range_err);
@@ -723,6 +723,24 @@ int Engine::trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* sel_
   return cfg.arch == PG_ARCH_MSA1B ? msa_trunk(d_tok, B, R, C, sel_idx, sel_row_map, P, n_sel) : esm_trunk(d_tok, B, C, sel_idx, P, n_sel, d_iter_);
 }
 
+// The representations tap (engine.h): layer l of the numbering fair-esm's repr_layers uses is in x.  Layer n_layers goes through
+// emb_layer_norm_after (ESM-1 has none: the raw stream), every other layer is copied; both forms write the live columns only and
+// zeros at <pad> rows.  The means are taken over the staged rows of the same call.
+int Engine::tap_layer(int l) {
+  if (!tap || tap->next >= tap->layers.size() || tap->layers[tap->next] != l) return PG_OK;
+  const size_t i = tap->next++;
+  const int64_t M = (int64_t)tap->B * tap->T;
+  const bool ln = l == cfg.n_layers && !esm1();
+  float* rows = tap->rows + i * (size_t)M * d_live;
+  int rc = timed(PC_REPR_ROWS, [&] {
+    return launch_repr_rows(stream, x.as<float>(), ln ? ln_after.g : nullptr, ln ? ln_after.b : nullptr, tap->d_tok, cfg.pad_idx, rows, M,
+                            cfg.d_model, d_live, cfg.layer_norm_eps);
+  });
+  if (rc || !tap->pooled) return rc;
+  float* means = tap->pooled + i * (size_t)tap->n_pools * tap->B * d_live;
+  return timed(PC_REPR_POOL, [&] { return launch_repr_pool(stream, rows, tap->d_pools, means, tap->n_pools, tap->B, tap->T, d_live); });
+}
+
 int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx, int P, int64_t n_sel, const int32_t* d_iter_) {
   const int d = cfg.d_model, f = cfg.d_ffn;
   const int64_t M = (int64_t)B * T;
@@ -734,15 +752,16 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
   if (strict()) {
     float* QKVf = qkv.as<float>();
     const int Mi = (int)Mp;
-    if ((rc = embed_rows(d_tok, M, T, 0, nullptr))) return rc;
+    if ((rc = embed_rows(d_tok, M, T, 0, nullptr)) || (rc = tap_layer(0))) return rc;
     const SeqLayout chain = {1, T, 0, 1};
-    for (const EsmLayer& L : esm_layers) {
+    for (int l = 0; l < cfg.n_layers; ++l) {
+      const EsmLayer& L = esm_layers[l];
       rc = strict_attention(L.ln1, L.qkv, L.out, Mi, M, [&](int split_d) {
         const int r = rope(QKVf, M, T);                                        // ESM-2 only
         if (r) return r;
         return timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), split_d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32, head_dim); });
       });
-      if (rc || (rc = ffn_strict(L.ffn, Mi, M))) return rc;
+      if (rc || (rc = ffn_strict(L.ffn, Mi, M)) || (rc = tap_layer(l + 1))) return rc;
     }
     return PG_OK;
   }
@@ -757,12 +776,14 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
   const bool ln_in_gemm = !embedded() && gemm_ln_skinny_ok(Mi, 3 * d, d) && gemm_ln_skinny_ok(Mi, f, d);      // no live-width form
 
   // embedding + emb_layer_norm_before, and in the same pass over the row the first layer's LayerNorm (its bf16 operand rows)
-  if ((rc = embed_rows(d_tok, M, T, 0, ln_in_gemm ? nullptr : &esm_layers[0].ln1))) return rc;
+  if ((rc = embed_rows(d_tok, M, T, 0, ln_in_gemm ? nullptr : &esm_layers[0].ln1)) || (rc = tap_layer(0))) return rc;
   // a single short chain: the persistent launch, when it may run.  With a selection it stops after the last layer's attention and
-  // the pruned tail finishes on the selected rows
+  // the pruned tail finishes on the selected rows.  A tap on a layer in between needs the per-layer launches of the same regime
+  // (bit-identical with it) -- the persistent launch shows the stream only before its first and after its last layer
   ChainRan ran = CHAIN_NOT_RUN;
-  if (ln_in_gemm && (rc = chain_forward(B, T, Mi, sel_idx != nullptr, &ran))) return rc;
-  if (ran == CHAIN_WHOLE_FORWARD) return PG_OK;
+  const bool tap_inside = tap && tap->wants_inner(cfg.n_layers);
+  if (ln_in_gemm && !tap_inside && (rc = chain_forward(B, T, Mi, sel_idx != nullptr, &ran))) return rc;
+  if (ran == CHAIN_WHOLE_FORWARD) return tap_layer(cfg.n_layers);
   // last layer with a selection: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
   const EsmLayer& tail = esm_layers.back();
   auto finish_selected = [&] { return pruned_tail(tail.out, tail.ffn, sel_idx, nullptr, P, T, n_sel, d_iter_, sel_gemm_rows(n_sel, round_up64(n_sel, kRowPad)), ln_in_gemm); };
@@ -775,7 +796,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
     if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16, head_dim); }))) return rc;
     const bool last = l == cfg.n_layers - 1;
     if (sel_idx && last) return finish_selected();
-    if ((rc = ffn_block(L.out, L.ffn, last ? nullptr : &esm_layers[l + 1].ln1, Mi, M, ln_in_gemm))) return rc;
+    if ((rc = ffn_block(L.out, L.ffn, last ? nullptr : &esm_layers[l + 1].ln1, Mi, M, ln_in_gemm)) || (rc = tap_layer(l + 1))) return rc;
   }
   return PG_OK;
 }

@@ -93,4 +93,14 @@ int launch_sample_writeback(hipStream_t st, int32_t* tokens, int width, const fl
                             int iteration, int32_t* sampled_tokens, const int32_t* d_iter = nullptr, unsigned* nonfinite = nullptr,
                             const DrawGuideDev* guide = nullptr);      // guide: null or inactive = pg_draw v1's kernel
 
+// ---- sequence representations (repr.hip): fp32 in and out, one flavour ----
+// out[M][d_live] = the live columns of x[M][d], through LayerNorm (ln_row.h: launch_layernorm_f32's bits) when gamma / beta are
+// given; a row whose token equals pad_idx is written as zeros (tokens may be null: no such rows).  d_live 0 = d
+int launch_repr_rows(hipStream_t s, const float* x, const float* gamma, const float* beta, const int32_t* tokens, int pad_idx, float* out,
+                     int64_t M, int d, int d_live, float eps);
+// out[n_pools][B][d_live] = the mean of in[b][begin .. begin + count - 1] for (begin, count) = ranges[pool][b] (device-resident, checked
+// by repr_pools_check on the host): a sequential fp32 sum in ascending row order divided by float(count); count 0 -> zeros
+int launch_repr_pool(hipStream_t s, const float* in, const int32_t* ranges, float* out, int n_pools, int B, int T, int d_live);
+int repr_pools_check(const char* who, const int32_t* pools, int n_pools, int B, int T);      // host ranges: 0 <= begin, 0 <= count, begin + count <= T
+
 }  // namespace pg

@@ -252,14 +252,66 @@ class NativeMaskedLM:
         return self.cfg["arch"] == _lib.PG_ARCH_MSA1B
 
     # ---- forward: tokens -> {"logits": ...} ------------------------------------------------
-    def __call__(self, tokens):
+    def __call__(self, tokens, repr_layers=None):
+        """fair-esm's call shape: {"logits": [B, T, V]}, and with repr_layers also {"representations": {layer: [B, T, d]}} under the
+        layer numbers as the caller wrote them (forward_representations)."""
         import torch
         t = tokens.detach().cpu().numpy() if hasattr(tokens, "detach") else np.asarray(tokens)
-        logits = self.forward_logits(t)
-        out = torch.from_numpy(logits)
-        if hasattr(tokens, "device") and tokens.device.type == "cuda":
-            out = out.to(tokens.device)
-        return {"logits": out}
+        on_gpu = hasattr(tokens, "detach") and tokens.device.type == "cuda"      # a numpy array's .device is the string "cpu"
+
+        def tensor(a):
+            out = torch.from_numpy(a)
+            return out.to(tokens.device) if on_gpu else out
+        result = {"logits": tensor(self.forward_logits(t))}
+        if repr_layers is not None:
+            layers = list(repr_layers)
+            per_token, _ = self.forward_representations(t, layers)
+            result["representations"] = {layer: tensor(per_token[i]) for i, layer in enumerate(layers)}
+        return result
+
+    def normalise_layers(self, layers):
+        """Layer numbers 0 .. n_layers from fair-esm's repr_layers: a negative number counts from the end (-1 is n_layers).
+        ValueError for a number outside -(n + 1) .. n and for a layer named twice, (-1, n) included."""
+        n = self.cfg["n_layers"]
+        out = []
+        for layer in layers:
+            if int(layer) != layer or not -(n + 1) <= layer <= n:
+                raise ValueError("representation layer %r is outside -%d .. %d of this %d-layer model" % (layer, n + 1, n, n))
+            out.append((int(layer) + n + 1) % (n + 1))
+        if not out:
+            raise ValueError("no representation layer requested")
+        if len(set(out)) != len(out):
+            raise ValueError("representation layers %r name a layer twice" % (list(layers),))
+        return out
+
+    def forward_representations(self, tokens, layers, pools=None, per_token=True):
+        """The residual stream of `layers` (fair-esm numbering, see normalise_layers; C ABI pg_esm_forward_representations) for
+        tokens int32 [B, T].  Returns (per_token, pooled), both in the order the layers were given: per_token float32
+        [len(layers), B, T, d_model] (None with per_token=False; <pad> rows are zeros), pooled float32 [len(layers), n_pools, B, d_model]
+        = the mean over token range begin .. begin + count - 1 for pools int32 [n_pools, B, 2] = (begin, count) (None without pools)."""
+        if self.is_msa:
+            raise ValueError("the MSA engine has no representations entry")
+        want = self.normalise_layers(layers)
+        order = sorted(range(len(want)), key=want.__getitem__)
+        asc = np.asarray([want[i] for i in order], dtype=np.int32)
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tok.ndim != 2:
+            raise ValueError("forward_representations takes tokens [B, T]")
+        B, T = tok.shape
+        d = self.cfg["d_model"]
+        if pools is not None:
+            pools = np.ascontiguousarray(pools, dtype=np.int32)
+            if pools.ndim != 3 or pools.shape[1:] != (B, 2) or pools.shape[0] < 1:
+                raise ValueError("pools must be [n_pools, %d, 2] = (begin, count) per sequence, got %r" % (B, pools.shape))
+        if pools is None and not per_token:
+            raise ValueError("forward_representations: neither per-token rows nor pools requested")
+        rows = np.empty((len(asc), B, T, d), dtype=np.float32) if per_token else None
+        means = np.empty((len(asc), pools.shape[0], B, d), dtype=np.float32) if pools is not None else None
+        self._call("forward_representations", tok, _lib.ptr(asc), len(asc), _lib.ptr(pools) if pools is not None else None,
+                   pools.shape[0] if pools is not None else 0, _lib.ptr(rows) if per_token else None,
+                   _lib.ptr(means) if pools is not None else None)
+        back = np.argsort(order)      # position of the caller's i-th layer in the ascending request
+        return (rows[back] if per_token else None), (means[back] if pools is not None else None)
 
     def _entry(self, name, tok):
         """The C entry pg_msa_<name> / pg_esm_<name> of this architecture and the shape arguments that follow its token pointer:

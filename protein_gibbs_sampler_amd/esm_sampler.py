@@ -308,6 +308,61 @@ class ESM_sampler():
                     entropy[pos] = ent[i, :len(pos)]
             yield logp, entropy, toks
 
+    # ---- sequence embeddings (fair-esm's repr_layers / scripts/extract.py) ------------------------------------
+    EMBED_KINDS = ("mean", "per_tok", "bos")
+
+    def embed(self, seq, repr_layers=(-1,), include=("mean",), batch_size=None):
+        """The embeddings of one sequence -- see embed_batch."""
+        return next(self.embed_batch([seq], repr_layers, include, batch_size))
+
+    def embed_batch(self, seq_list, repr_layers=(-1,), include=("mean",), batch_size=None):
+        """For every sequence, in order, yields a dict of the `include`d kinds, each {layer: float32 array} under the layer numbers as
+        written in repr_layers (negative numbers count from the end, -1 = the last layer through emb_layer_norm_after):
+        "mean" [d] over the residues only (not <cls> / <eos>), "per_tok" [L, d] the residue rows, "bos" [d] the first token's row.
+        Sequences of equal length form one group and a group runs in chunks of batch_size (None: whole groups), so no padding
+        reaches the model; every chunk is a shard of its group's job (set_job_items), so a sequence's result does not depend on
+        batch_size.  The means are the engine's sequential fp32 means (pg_esm_forward_representations)."""
+        self._require_gpu("embed_batch")
+        include = tuple(include)
+        if not include or any(kind not in self.EMBED_KINDS for kind in include):
+            raise ValueError("include takes some of %r, got %r" % (self.EMBED_KINDS, include))
+        lm = self.model.model
+        if not isinstance(lm, NativeMaskedLM):
+            raise TypeError("embed_batch needs the HIP engine (NativeMaskedLM); a plug-in model returns its own representations")
+        layers = list(repr_layers)
+        lm.normalise_layers(layers)                     # refuses before anything runs
+        seqs = [self.clean_seed_seq(seq) for seq in seq_list]
+        start = 1 if self.model.alphabet.prepend_bos else 0
+        groups = {}
+        for i, seq in enumerate(seqs):
+            groups.setdefault(len(seq), []).append(i)
+        kinds = [kind for kind in ("mean", "bos") if kind in include]      # the pools of a call, in this order
+        done = {}
+        for i, seq in enumerate(seqs):
+            if i not in done:
+                self._embed_group(lm, seqs, groups[len(seq)], layers, kinds, "per_tok" in include, start, batch_size, done)
+            yield done.pop(i)
+
+    def _embed_group(self, lm, seqs, members, layers, kinds, per_tok, start, batch_size, done):
+        """embed_batch on one group of equally long sequences: done[i] = the result of sequence i for every member i."""
+        L = len(seqs[members[0]])
+        _, _, tokens = self.model.batch_converter([(str(i), seqs[i]) for i in members])
+        tokens = tokens.numpy()
+        ranges = {"mean": (start, L), "bos": (0, 1)}
+        lm.set_job_items(len(members))
+        try:
+            for sl, first in _gibbs.chunks(len(members), len(members) if batch_size is None else batch_size):
+                tok = tokens[sl]
+                pools = np.asarray([[ranges[kind]] * len(tok) for kind in kinds], dtype=np.int32) if kinds else None
+                rows, means = lm.forward_representations(tok, layers, pools, per_token=per_tok)
+                for b in range(len(tok)):
+                    out = {kind: {layer: means[k, p, b].copy() for k, layer in enumerate(layers)} for p, kind in enumerate(kinds)}
+                    if per_tok:
+                        out["per_tok"] = {layer: rows[k, b, start:start + L].copy() for k, layer in enumerate(layers)}
+                    done[members[first + b]] = out
+        finally:
+            lm.set_job_items(0)
+
     def score_mutations(self, seq, mutations, **kwargs):
         """Masked-marginal scores of point mutations such as "A24G" (wild type, 1-based position, mutant):
         logp[pos, mutant] - logp[pos, wild type], all from ONE masked_marginals table of `seq` (keyword arguments go to it).
