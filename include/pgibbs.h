@@ -106,7 +106,8 @@ typedef struct pg_engine pg_engine;
                            the cos / sin table of max_positions + 2 rows is built when the engine is created); no
                            emb_layer_norm_before (not required); vocabulary of 33 as ESM-1b.  Tensors read: `embed_tokens.weight`,
                            `layers.i.*` as ESM-1b, `emb_layer_norm_after.*`, `lm_head.dense.*`, `lm_head.layer_norm.*`, `lm_head.bias`;
-                           `layers.i.self_attn.rot_emb.inv_freq` and `contact_head.*` are ignored when handed in.  Runs through the
+                           `layers.i.self_attn.rot_emb.inv_freq` and `contact_head.*` are ignored when handed in (the contact regression
+                           is set apart, pg_engine_set_contact_head).  Runs through the
                            pg_esm_* entry points (the pg_msa_* ones answer PG_ERR_INVALID); max_positions bounds T as for ESM-1b
                            (default 1024).  The persistent single-chain trunk is ESM-1b-only: ESM-2 chains of <= 32 token rows take
                            the per-layer launches (weight-streaming GEMMs, hipGraph replay); at d_model > 1280 their LayerNorm is a
@@ -273,6 +274,49 @@ PG_API int pg_repr_dbg_rows(int device, const float* x, int64_t M, int d, int d_
                             const int32_t* tokens, int pad_idx, float* rows_out, int B, int T, const int32_t* pools, int n_pools,
                             float* pooled_out);
 
+/* ---- contact prediction --------------------------------------------------------------------------
+ * fair-esm's model.predict_contacts(tokens) / return_contacts=True and need_head_weights=True, HuggingFace's predict_contacts and
+ * output_attentions=True, for PG_ARCH_ESM1B and PG_ARCH_ESM2 engines (embedded models included: channel l * n_heads + h with the
+ * model's own head count).  PG_ARCH_ESM1 (its bias key changes the softmax and the map shape) and the MSA engine are refused.
+ * With A[b][l][h][i][j] = block l's softmax probability of query i over key j (<pad> keys masked, as in the forward):
+ *   live[b][t]  = tokens[b][t] != eos_idx && tokens[b][t] != pad_idx; A is zeroed wherever i or j is not live, then the first and the
+ *                 last row and column are cut off: the window t = 1 .. T-2 of W = T - 2 positions;
+ *   S = A + A^T per channel c = l * n_heads + h;  a1[i] = sum_j S[i][j], a12 = sum_i a1[i];  N[i][j] = S[i][j] - a1[i] * a1[j] / a12;
+ *   logit[b][i][j] = bias + sum_c w[c] * N_c[i][j], c ascending;  contact = 1 / (1 + exp(-logit)).
+ * All in fp32; the order of every add, the place of the division and the reduction order of the sums are fixed and written down in
+ * csrc/contact.hip (tests/_contact_reference.py restates them).  Where this engine's own convention applies:
+ *   - a channel with a12 == 0 (no live residue in the window) contributes 0 -- fair-esm divides by zero there and yields NaN;
+ *   - a window entry whose row or column is not live (<pad>, or an <eos> before the row's end) gets logit = bias exactly.
+ * The attention probabilities come from a kernel of their own (the fused attention kernels never hold them): same operands, same
+ * masks, fp32 softmax; deterministic, and a sequence's result does not depend on the other sequences of the call.
+ *
+ * pg_engine_set_contact_head: weight[n_weights] with n_weights == n_layers * n_heads, uploaded once; weight NULL clears the head.
+ * PG_ERR_INVALID: null engine; an MSA or ESM-1 engine (the message names the architecture); a wrong count; a non-finite value.
+ *
+ * pg_esm_forward_contacts:
+ *   contacts_out / logits_out   [B][T-2][T-2] or NULL
+ *   attn_layers[n_attn]         0-based block indices, strictly ascending; may be NULL / 0
+ *   attn_out                    [n_attn][B][n_heads][T][T] or NULL; given exactly when layers are.  Needs no head: attn_out alone works
+ *                               on an engine without one (fair-esm's need_head_weights)
+ * PG_ERR_INVALID, before a device is touched and in this order: null tokens; all three outputs NULL; attn_out without layers or layers
+ * without attn_out; a negative layer or layers not strictly ascending; T < 3; a null engine; an MSA or ESM-1 engine; contacts or logits
+ * wanted with no head set; the call check of the other entries (shape, position table); a layer >= n_layers; tokens outside the
+ * vocabulary.  PG_ERR_RANGE when a copied-back value is not finite (PG_PREC_F16 overflow: run the call on a PG_PREC_BF16 engine).
+ * The call never takes the persistent single-chain launch; one layer's maps (B * n_heads * T * T fp32) are staged at a time. */
+PG_API int pg_engine_set_contact_head(pg_engine*, const float* weight, int n_weights, float bias);
+PG_API int pg_esm_forward_contacts(pg_engine*, const int32_t* tokens, int B, int T, float* contacts_out, float* logits_out,
+                                   const int32_t* attn_layers, int n_attn, float* attn_out);
+/* The two launchers of that entry alone, on host buffers (kernel-level tests).  pg_contact_dbg_probs: probs_out[n_seq][H][T][T] from
+ * qkv[n_seq * T][3 * H * head_dim] fp32 (rows [q | k | v], q already scaled), rounded to the 16-bit type of `precision` first or kept
+ * fp32 for PG_PREC_FP32; key_tok[n_seq][T] optional: keys whose token is pad_idx are masked; plan / plan_bytes optional: the launcher's
+ * plan text -- with probs_out NULL only that, without a device.  pg_contact_dbg_accumulate: one layer's P[B][H][T][T] folded with
+ * w[H] into logits_inout[B][T-2][T-2] (started from 0 when `first`, else from the values handed in); `last` adds bias and writes
+ * contacts_out (optional). */
+PG_API int pg_contact_dbg_probs(int device, int precision, const float* qkv, int n_seq, int T, int H, int head_dim, const int32_t* key_tok,
+                                int pad_idx, float* probs_out, char* plan, int plan_bytes);
+PG_API int pg_contact_dbg_accumulate(int device, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
+                                     int first, int last, float* logits_inout, float* contacts_out, int B, int T, int H);
+
 /* ---- ESM-MSA-1b ---------------------------------------------------------------------------
  * tokens[B][R][C] (C = L + 1: <cls> then L columns, no <eos>).
  * pg_msa_gibbs_run: loop of ESM_MSA_sampler.generate (esm_msa_sampler.py:221-248):
@@ -438,7 +482,8 @@ PG_API int pg_dbg_gather_plan(int rank, int world, int64_t rows, int width, cons
  * HIP-event timing of kernel classes on the engine's stream (bench.py's roofline figure).
  * class names: "gemm", "attention", "layernorm", "embed", "head", "sample", and "rope": ESM-2's rotation of q and k, timed under
  * its own class (not under "attention"; no launch of the other architectures falls into it); "repr_rows" and "repr_pool": the two
- * kernels of pg_esm_forward_representations (no other call has a launch in them).  */
+ * kernels of pg_esm_forward_representations (no other call has a launch in them); "attn_probs" and "contact": the attention
+ * probabilities and the APC / regression fold of pg_esm_forward_contacts (likewise).  */
 PG_API int pg_prof_enable(pg_engine*, int on);
 PG_API int pg_prof_reset(pg_engine*);
 PG_API int pg_prof_get(pg_engine*, const char* kernel_class, double* total_ms, int64_t* launches);

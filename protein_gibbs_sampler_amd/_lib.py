@@ -134,6 +134,12 @@ SIGNATURES = [
     ("pg_esm_forward_representations", c_int, [EngineHandle, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     ("pg_repr_dbg_rows", c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int,
                                  c_int, c_void_p, c_int, c_void_p]),
+    # contact prediction: the head, the engine entry and the kernel-level entries of its two launchers (EngineHandle: see above)
+    ("pg_engine_set_contact_head", c_int, [EngineHandle, c_void_p, c_int, c_float]),
+    ("pg_esm_forward_contacts", c_int, [EngineHandle, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    ("pg_contact_dbg_probs", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_char_p, c_int]),
+    ("pg_contact_dbg_accumulate", c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
+                                          c_int, c_int, c_int]),
     ("pg_comm_unique_id", c_int, [c_void_p]),
     ("pg_comm_create", c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),
     ("pg_comm_destroy", None, [c_void_p]),

@@ -170,6 +170,85 @@ int forward_representations(pg_engine* h, const int32_t* tokens, int B, int T, c
   return n_pools ? check_finite(e, pooled_out, n_means) : PG_OK;
 }
 
+// While this lives the ESM trunk hands every block's qkv to Engine::tap_attention
+struct ContactScope {
+  Engine& e;
+  ContactScope(Engine& e_, ContactTap* t) : e(e_) { e.ctap = t; }
+  ~ContactScope() { e.ctap = nullptr; }
+};
+const char* arch_name(int arch) {
+  return arch == PG_ARCH_MSA1B ? "MSA-1b" : arch == PG_ARCH_ESM1 ? "ESM-1" : arch == PG_ARCH_ESM2 ? "ESM-2" : "ESM-1b";
+}
+// the architectures with a contacts entry: ESM-1b and ESM-2 (<cls> ... <eos>, no bias key); 0 = fine
+int contact_arch_check(const char* who, const Engine& e) {
+  if (e.cfg.arch == PG_ARCH_MSA1B || e.cfg.arch == PG_ARCH_ESM1)
+    return fail(PG_ERR_INVALID, std::string(who) + ": the " + arch_name(e.cfg.arch) + " architecture has no contact head in this engine (ESM-1b and ESM-2 only)");
+  return PG_OK;
+}
+
+// tokens[B][T] in; contact probabilities and / or logits [B][T-2][T-2] and / or the attention maps of the listed blocks out.
+// Everything in the argument list is refused before a device is touched, in the order pgibbs.h states
+int forward_contacts(pg_engine* h, const int32_t* tokens, int B, int T, float* contacts_out, float* logits_out, const int32_t* attn_layers,
+                     int n_attn, float* attn_out) {
+  const std::string who = "pg_esm_forward_contacts";
+  if (!tokens) return fail(PG_ERR_INVALID, who + ": null tokens");
+  if (!contacts_out && !logits_out && !attn_out) return fail(PG_ERR_INVALID, who + ": no output requested");
+  const bool want_layers = attn_layers && n_attn > 0;
+  if (n_attn < 0 || (attn_out != nullptr) != want_layers || (!attn_layers && n_attn > 0))
+    return fail(PG_ERR_INVALID, who + ": attention layers and attn_out come together or not at all");
+  for (int i = 0; i < n_attn; ++i) {
+    if (attn_layers[i] < 0) return fail(PG_ERR_INVALID, who + ": attention layer " + std::to_string(attn_layers[i]) + " is negative");
+    if (i && attn_layers[i] <= attn_layers[i - 1]) return fail(PG_ERR_INVALID, who + ": attention layers must be strictly ascending");
+  }
+  if (T < 3) return fail(PG_ERR_INVALID, who + ": T = " + std::to_string(T) + ": a contact map needs <cls>, at least one position and <eos>");
+  if (!h) return fail(PG_ERR_INVALID, who + ": null engine");
+  Engine& e = h->e;
+  int rc;
+  if ((rc = contact_arch_check(who.c_str(), e))) return rc;
+  const bool fold = contacts_out || logits_out;
+  if (fold && !e.contact_w) return fail(PG_ERR_INVALID, who + ": no contact head set (pg_engine_set_contact_head); attention maps alone need none");
+  if ((rc = e.check_call(false, B, 1, T))) return rc;
+  if (n_attn && attn_layers[n_attn - 1] >= e.cfg.n_layers)
+    return fail(PG_ERR_INVALID, who + ": attention layer " + std::to_string(attn_layers[n_attn - 1]) + " is outside 0 .. " + std::to_string(e.cfg.n_layers - 1));
+  if (B == 0) return PG_OK;
+  const int64_t M = (int64_t)B * T;
+  bool has_pad;
+  if ((rc = scan_tokens(e, who.c_str(), tokens, (size_t)M, &has_pad))) return rc;
+  DeviceGuard g(e.device);
+  const int W = T - 2, H = e.cfg.n_heads;
+  const size_t n_map = (size_t)B * H * T * T, n_win = (size_t)B * W * W;
+  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream)) || (rc = e.contact_P.ensure(n_map * 4, e.stream))) return rc;
+  if (n_attn && (rc = e.contact_attn.ensure(n_map * n_attn * 4, e.stream))) return rc;
+  if (fold && ((rc = e.contact_logits.ensure(n_win * 4, e.stream)) || (rc = e.contact_probs.ensure(n_win * 4, e.stream)) ||
+               (rc = e.contact_sums.ensure(contact_sums_floats(B, H, T) * 4, e.stream)))) return rc;
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
+  ContactTap tap;
+  tap.d_tok = e.d_tokens.as<int32_t>();
+  tap.B = B;
+  tap.T = T;
+  tap.fold = fold;
+  tap.logits = fold ? e.contact_logits.as<float>() : nullptr;
+  tap.contacts = contacts_out ? e.contact_probs.as<float>() : nullptr;
+  if (n_attn) tap.attn_layers.assign(attn_layers, attn_layers + n_attn);
+  tap.attn_out = n_attn ? e.contact_attn.as<float>() : nullptr;
+  {
+    PadFlag pad(e, has_pad);
+    ContactScope scope(e, &tap);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, 1, T);
+  }
+  if (rc) return rc;
+  if (tap.folded != e.cfg.n_layers || tap.next_attn != tap.attn_layers.size())
+    return fail(PG_ERR_HIP, who + ": the forward did not show every layer's attention");
+  if (contacts_out) PG_HIP(hipMemcpyAsync(contacts_out, e.contact_probs.p, n_win * 4, hipMemcpyDeviceToHost, e.stream));
+  if (logits_out) PG_HIP(hipMemcpyAsync(logits_out, e.contact_logits.p, n_win * 4, hipMemcpyDeviceToHost, e.stream));
+  if (n_attn) PG_HIP(hipMemcpyAsync(attn_out, e.contact_attn.p, n_map * n_attn * 4, hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.chain_check())) return rc;
+  if (contacts_out && (rc = check_finite(e, contacts_out, n_win))) return rc;
+  if (logits_out && (rc = check_finite(e, logits_out, n_win))) return rc;
+  return n_attn ? check_finite(e, attn_out, n_map * n_attn) : PG_OK;
+}
+
 // A Gibbs call on host buffers: tokens and the index table go to the device, run(d_tokens, d_idx, d_sampled_logits, d_sampled_tokens)
 // queues the loop (an output the caller did not ask for is null), and tokens and outputs come back.
 template <typename Run>
@@ -287,7 +366,8 @@ int create_engine(const char* who, const pg_model_config* cfg, const pg_tensor* 
 // the profiling classes by name (pg_prof_get, pg_prof_get_kernels): the PC_* index, -1 = no such class
 int prof_class(const char* name) {
   static const char* const names[PC_COUNT] = {"gemm_other", "attention", "layernorm", "embed",    "head", "sample",
-                                              "gemm_qkv",   "gemm_out",  "gemm_fc1",  "gemm_fc2", "rope",     "repr_rows", "repr_pool"};
+                                              "gemm_qkv",   "gemm_out",  "gemm_fc1",  "gemm_fc2", "rope",     "repr_rows", "repr_pool",
+                                              "attn_probs", "contact"};
   for (int i = 0; i < PC_COUNT; ++i)
     if (!strcmp(names[i], name)) return i;
   return -1;
@@ -383,6 +463,29 @@ int pg_esm_forward_logits(pg_engine* h, const int32_t* tokens, int B, int T, flo
 int pg_esm_forward_representations(pg_engine* h, const int32_t* tokens, int B, int T, const int32_t* layers, int n_req, const int32_t* pools,
                                    int n_pools, float* per_token_out, float* pooled_out) {
   PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_representations(h, tokens, B, T, layers, n_req, pools, n_pools, per_token_out, pooled_out));
+}
+
+int pg_esm_forward_contacts(pg_engine* h, const int32_t* tokens, int B, int T, float* contacts_out, float* logits_out, const int32_t* attn_layers,
+                            int n_attn, float* attn_out) {
+  PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_contacts(h, tokens, B, T, contacts_out, logits_out, attn_layers, n_attn, attn_out));
+}
+
+int pg_engine_set_contact_head(pg_engine* h, const float* weight, int n_weights, float bias) {
+  const char* who = "pg_engine_set_contact_head";
+  if (!h) return fail(PG_ERR_INVALID, std::string(who) + ": null engine");
+  Engine& e = h->e;
+  if (int rc = contact_arch_check(who, e)) return rc;
+  if (weight) {
+    const int want = e.cfg.n_layers * e.cfg.n_heads;
+    if (n_weights != want)
+      return fail(PG_ERR_INVALID, std::string(who) + ": " + std::to_string(n_weights) + " weights for a model of " + std::to_string(e.cfg.n_layers) + " layers x " +
+                                      std::to_string(e.cfg.n_heads) + " heads = " + std::to_string(want) + " channels");
+    for (int i = 0; i < n_weights; ++i)
+      if (!(fabsf(weight[i]) <= 3.0e38f)) return fail(PG_ERR_INVALID, std::string(who) + ": weight " + std::to_string(i) + " is not finite");
+    if (!(fabsf(bias) <= 3.0e38f)) return fail(PG_ERR_INVALID, std::string(who) + ": the bias is not finite");
+  }
+  DeviceGuard g(e.device);
+  return e.set_contact_head(weight, n_weights, bias);
 }
 
 int pg_esm_gibbs_run_device(pg_engine* h, int32_t* d_tokens_inout, int B, int T, const int32_t* d_target_idx, int n_iters,

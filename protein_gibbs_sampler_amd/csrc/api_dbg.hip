@@ -885,6 +885,70 @@ int pg_repr_dbg_rows(int device, const float* x, int64_t M, int d, int d_live, c
   return pools ? s.down(pooled_out, dmeans, (size_t)n_pools * B * d_live) : PG_OK;
 }
 
+/* The two contact launchers (contact.hip) alone, on host buffers.  pg_contact_dbg_probs: probs_out[n_seq][H][T][T] = launch_attn_probs
+ * of qkv[n_seq * T][3 H head_dim] fp32 -- rounded to the 16-bit type of `precision` first, kept fp32 for PG_PREC_FP32 (the strict
+ * launcher) -- read as the engine's ESM trunks hand it over (ld = 3 d, k at d, contiguous chains).  plan (may be NULL): the launcher's
+ * plan text; with probs_out NULL the plan alone, without a device.  Everything is refused on the host before a device is looked for. */
+int pg_contact_dbg_probs(int device, int precision, const float* qkv, int n_seq, int T, int H, int head_dim, const int32_t* key_tok, int pad_idx,
+                         float* probs_out, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  int rc = dbg_precision("pg_contact_dbg_probs", precision, true);
+  if (rc) return rc;
+  if (n_seq < 1 || T < 1 || H < 1 || (plan && plan_bytes < 1) || (!probs_out && !plan) || (probs_out && !qkv))
+    return fail(PG_ERR_INVALID, "pg_contact_dbg_probs: bad argument");
+  if (!head_width(head_dim)) return fail(PG_ERR_INVALID, "pg_contact_dbg_probs: head_dim must be " + head_widths_text(false));
+  const bool strict = precision == PG_PREC_FP32;
+  if (!probs_out) {
+    std::string text;
+    if (strict) attn_probs_f32_plan_text(n_seq, T, H, head_dim, key_tok != nullptr, &text);
+    else OPS(attn_probs_plan_text, n_seq, T, H, head_dim, key_tok != nullptr, &text);
+    snprintf(plan, (size_t)plan_bytes, "%s", text.c_str());
+    return PG_OK;
+  }
+  if ((double)n_seq * T * 3 * H * head_dim > 2147483647.0 || (double)n_seq * H * T * T > 2147483647.0)
+    return fail(PG_ERR_INVALID, "pg_contact_dbg_probs: more than 2^31 - 1 values");
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const int d = H * head_dim;
+  const int64_t M = (int64_t)n_seq * T;
+  const size_t n_map = (size_t)n_seq * H * T * T;
+  const float* dq = s.up(qkv, (size_t)M * 3 * d);
+  const int32_t* dtok = s.up(key_tok, (size_t)M);
+  bf16_t* bq = strict ? nullptr : s.alloc<bf16_t>((size_t)M * 3 * d);
+  float* dP = s.alloc<float>(n_map);
+  if ((rc = s.check())) return rc;
+  clear_noted_kernels();
+  const SeqLayout chain = {1, T, 0, 1};
+  if (strict) rc = launch_attn_probs_f32(nullptr, dq, dP, n_seq, T, H, 3 * d, d, chain, dtok, pad_idx, head_dim);
+  else if (!(rc = to16(precision, dq, bq, M * 3 * d))) rc = OPS(launch_attn_probs, nullptr, bq, dP, n_seq, T, H, 3 * d, d, chain, dtok, pad_idx, head_dim);
+  if (rc) return rc;
+  dbg_noted_text(plan, plan_bytes);
+  return s.down(probs_out, dP, n_map);
+}
+
+/* pg_contact_dbg_accumulate: launch_contact_accumulate of P[B][H][T][T] with the H weights w into logits_inout[B][T-2][T-2] (read
+ * unless `first`), contacts_out (optional) written when `last`. */
+int pg_contact_dbg_accumulate(int device, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias, int first,
+                              int last, float* logits_inout, float* contacts_out, int B, int T, int H) {
+  if (!P || !tokens || !w || !logits_inout || B < 1 || H < 1) return fail(PG_ERR_INVALID, "pg_contact_dbg_accumulate: bad argument");
+  if (T < 3) return fail(PG_ERR_INVALID, "pg_contact_dbg_accumulate: T must be at least 3");
+  if ((double)B * H * T * T > 2147483647.0) return fail(PG_ERR_INVALID, "pg_contact_dbg_accumulate: more than 2^31 - 1 values");
+  Dbg s;
+  int rc;
+  if ((rc = s.open(device))) return rc;
+  const size_t n_win = (size_t)B * (T - 2) * (T - 2);
+  const float* dP = s.up(P, (size_t)B * H * T * T);
+  const int32_t* dtok = s.up(tokens, (size_t)B * T);
+  const float* dw = s.up(w, (size_t)H);
+  float* dlog = s.up(logits_inout, n_win);
+  float* dcon = contacts_out ? s.alloc<float>(n_win) : nullptr;
+  float* dsum = s.alloc<float>(contact_sums_floats(B, H, T));
+  if ((rc = s.check())) return rc;
+  if ((rc = launch_contact_accumulate(nullptr, dP, dtok, eos_idx, pad_idx, dw, bias, first != 0, last != 0, dsum, dlog, dcon, B, T, H))) return rc;
+  if ((rc = s.down(logits_inout, dlog, n_win))) return rc;
+  return contacts_out && last ? s.down(contacts_out, dcon, n_win) : PG_OK;
+}
+
 /* ---- embedded models: the host side of pg_engine_create_embedded, no device ---- */
 int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
                       float* image, int64_t image_numel) {

@@ -36,7 +36,8 @@ struct Prof {
 // PC_NONE: an op inside a timed() block of its caller's (the LM head's one record) -- no record of its own
 enum ProfClass { PC_NONE = -1, PC_GEMM = 0, PC_ATTN, PC_LN, PC_EMBED, PC_HEAD, PC_SAMPLE, PC_GEMM_QKV, PC_GEMM_OUT, PC_GEMM_FC1, PC_GEMM_FC2,
                  PC_ROPE /* ESM-2: the rotation of q and k, one launch per layer */,
-                 PC_REPR_ROWS, PC_REPR_POOL /* representations: the row copy / LayerNorm and the pooled means (repr.hip) */, PC_COUNT };
+                 PC_REPR_ROWS, PC_REPR_POOL /* representations: the row copy / LayerNorm and the pooled means (repr.hip) */,
+                 PC_ATTN_PROBS, PC_CONTACT /* contact prediction: the attention probabilities and the APC / regression fold (contact.hip) */, PC_COUNT };
 
 struct DenseW {   // y = x W^T + b ; W bf16 [N][K], b fp32 [N].  Strict precision mode: w is [N][3K], each row the
   bf16_t* w = nullptr;   // K-concatenated split-bf16 operand [hi | lo | hi] (hi = bf16(W), lo = bf16(W - hi))
@@ -95,6 +96,22 @@ struct ReprTap {
   }
 };
 
+// What a contacts call (pg_esm_forward_contacts) asks of the forward: while Engine::ctap points at one, esm_trunk hands every block's
+// qkv buffer -- after the rotary kernel, next to the fused attention launch, which does not modify it -- to tap_attention.  The
+// probabilities of ONE layer are staged at a time (contact_P: B H T T fp32, so memory does not grow with depth) and folded into the
+// contact logits; a layer whose map the caller asked for is written to its slot of attn_out instead and folded from there
+struct ContactTap {
+  const int32_t* d_tok = nullptr;    // the call's tokens [B][T]
+  int B = 0, T = 0;
+  bool fold = false;                 // contacts or logits wanted: the engine's head is folded over every layer into `logits`
+  float* logits = nullptr;           // [B][T-2][T-2]
+  float* contacts = nullptr;         // the same shape, or null
+  std::vector<int> attn_layers;      // 0-based block indices, strictly ascending
+  float* attn_out = nullptr;         // [attn_layers.size()][B][H][T][T]
+  size_t next_attn = 0;              // index of the next requested layer
+  int folded = 0;                    // layers seen
+};
+
 struct Engine {
   pg_model_config cfg;
   int device = 0;
@@ -151,6 +168,16 @@ struct Engine {
   // x now holds layer l (0: the embedding output; l: the stream after block l): if the tap lists it, stage its rows -- through
   // emb_layer_norm_after for l = n_layers where the architecture has one -- and pool them
   int tap_layer(int l);
+  // ---- contacts tap (pg_esm_forward_contacts) ----
+  // null (every other call): tap_attention returns at once and the forward issues the launches it always did.  With a tap the call
+  // carries no selection and never takes the persistent single-chain launch, which hides the per-layer qkv
+  ContactTap* ctap = nullptr;
+  int tap_attention(int l, const void* qkv_rows);      // block l's qkv (the engine's 16-bit type; fp32 in strict mode) is ready
+  // the regression head (pg_engine_set_contact_head): n_layers * n_heads weights on the device (channel l * n_heads + h), null = none
+  float* contact_w = nullptr;
+  float contact_bias = 0.f;
+  int set_contact_head(const float* weight, int n_weights, float bias);
+  DevBuf contact_P, contact_sums, contact_logits, contact_probs, contact_attn;   // one layer's maps, a1 / a12, the outputs, the requested maps
 
   // ---- job-order knobs: what keeps a shard's arithmetic that of the whole job ----
   bool esm_pad_in_batch = false;           // set by the host-token entry points: some token is <pad> -> key-padding mask

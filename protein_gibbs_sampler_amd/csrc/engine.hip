@@ -110,12 +110,14 @@ Engine::~Engine() {
   for (void* p : owned) (void)hipFree(p);
   DevBuf* bufs[] = {&x, &h, &qkv, &ctx, &ffn, &sel_h, &sel_g, &logits, &d_tokens, &d_idx, &d_samp_tok, &d_samp_logits,
                     &d_rowmap, &scratch, &d_iter, &tmp_idx, &tmp_out, &x_sel, &ctx_sel, &h_sel, &ffn_sel, &ffn_f32, &scores, &splitk,
-                    &chain_sync, &chain_part, &chain_snap, &repr_rows, &repr_pooled, &repr_ranges};
+                    &chain_sync, &chain_part, &chain_snap, &repr_rows, &repr_pooled, &repr_ranges,
+                    &contact_P, &contact_sums, &contact_logits, &contact_probs, &contact_attn};
   for (DevBuf* b : bufs) b->release();
   if (chain_err) (void)hipHostFree(chain_err);
   if (range_err) (void)hipHostFree(range_err);
   if (guide_bias_dev) (void)hipFree(guide_bias_dev);
   if (guide_temps_dev) (void)hipFree(guide_temps_dev);
+  if (contact_w) (void)hipFree(contact_w);
   prof.destroy();
   if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
   if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -741,6 +743,43 @@ int Engine::tap_layer(int l) {
   return timed(PC_REPR_POOL, [&] { return launch_repr_pool(stream, rows, tap->d_pools, means, tap->n_pools, tap->B, tap->T, d_live); });
 }
 
+// The contacts tap (engine.h): block l's qkv is ready.  Its attention probabilities go to the one-layer staging buffer, or to the
+// caller's slot when the map of this layer was asked for, and -- with a head to fold -- into the running contact logits.  Layers come
+// in ascending order, so the channel order l * n_heads + h of the regression is fixed
+int Engine::tap_attention(int l, const void* qkv_rows) {
+  if (!ctap) return PG_OK;
+  ContactTap& t = *ctap;
+  const int d = cfg.d_model, H = cfg.n_heads;
+  const size_t map = (size_t)t.B * H * t.T * t.T;
+  float* Pl = contact_P.as<float>();
+  if (t.next_attn < t.attn_layers.size() && t.attn_layers[t.next_attn] == l) Pl = t.attn_out + map * t.next_attn++;
+  const SeqLayout chain = {1, t.T, 0, 1};
+  const int32_t* key_tok = esm_pad_in_batch ? t.d_tok : nullptr;
+  int rc = timed(PC_ATTN_PROBS, [&] {
+    if (strict()) return launch_attn_probs_f32(stream, (const float*)qkv_rows, Pl, t.B, t.T, H, 3 * d, d, chain, key_tok, cfg.pad_idx, head_dim);
+    return OPS(launch_attn_probs, stream, (const bf16_t*)qkv_rows, Pl, t.B, t.T, H, 3 * d, d, chain, key_tok, cfg.pad_idx, head_dim);
+  });
+  ++t.folded;
+  if (rc || !t.fold) return rc;
+  return timed(PC_CONTACT, [&] {
+    return launch_contact_accumulate(stream, Pl, t.d_tok, cfg.eos_idx, cfg.pad_idx, contact_w + (size_t)l * H, contact_bias, l == 0,
+                                     l == cfg.n_layers - 1, contact_sums.as<float>(), t.logits, t.contacts, t.B, t.T, H);
+  });
+}
+
+int Engine::set_contact_head(const float* weight, int n_weights, float bias) {
+  if (contact_w) {
+    PG_HIP(hipStreamSynchronize(stream));
+    PG_HIP(hipFree(contact_w));
+    contact_w = nullptr;
+  }
+  if (!weight) return PG_OK;
+  PG_HIP(hipMalloc((void**)&contact_w, (size_t)n_weights * 4));
+  PG_HIP(hipMemcpy(contact_w, weight, (size_t)n_weights * 4, hipMemcpyHostToDevice));
+  contact_bias = bias;
+  return PG_OK;
+}
+
 int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx, int P, int64_t n_sel, const int32_t* d_iter_) {
   const int d = cfg.d_model, f = cfg.d_ffn;
   const int64_t M = (int64_t)B * T;
@@ -757,8 +796,8 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
     for (int l = 0; l < cfg.n_layers; ++l) {
       const EsmLayer& L = esm_layers[l];
       rc = strict_attention(L.ln1, L.qkv, L.out, Mi, M, [&](int split_d) {
-        const int r = rope(QKVf, M, T);                                        // ESM-2 only
-        if (r) return r;
+        int r = rope(QKVf, M, T);                                              // ESM-2 only
+        if (r || (r = tap_attention(l, QKVf))) return r;
         return timed(PC_ATTN, [&] { return launch_attention_f32(stream, QKVf, ctx.as<bf16_t>(), split_d, B, T, cfg.n_heads, 3 * d, 3 * d, d, 2 * d, chain, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv32, head_dim); });
       });
       if (rc || (rc = ffn_strict(L.ffn, Mi, M)) || (rc = tap_layer(l + 1))) return rc;
@@ -779,10 +818,11 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
   if ((rc = embed_rows(d_tok, M, T, 0, ln_in_gemm ? nullptr : &esm_layers[0].ln1)) || (rc = tap_layer(0))) return rc;
   // a single short chain: the persistent launch, when it may run.  With a selection it stops after the last layer's attention and
   // the pruned tail finishes on the selected rows.  A tap on a layer in between needs the per-layer launches of the same regime
-  // (bit-identical with it) -- the persistent launch shows the stream only before its first and after its last layer
+  // (bit-identical with it) -- the persistent launch shows the stream only before its first and after its last layer; a contacts
+  // tap needs every layer's qkv
   ChainRan ran = CHAIN_NOT_RUN;
   const bool tap_inside = tap && tap->wants_inner(cfg.n_layers);
-  if (ln_in_gemm && !tap_inside && (rc = chain_forward(B, T, Mi, sel_idx != nullptr, &ran))) return rc;
+  if (ln_in_gemm && !tap_inside && !ctap && (rc = chain_forward(B, T, Mi, sel_idx != nullptr, &ran))) return rc;
   if (ran == CHAIN_WHOLE_FORWARD) return tap_layer(cfg.n_layers);
   // last layer with a selection: only the selected rows are ever read again -> gather them and finish the layer on n_sel rows
   const EsmLayer& tail = esm_layers.back();
@@ -792,7 +832,7 @@ int Engine::esm_trunk(const int32_t* d_tok, int B, int T, const int32_t* sel_idx
     const EsmLayer& L = esm_layers[l];
     // tile regime: Hh holds LN1(x), written by the previous layer's fc2 launch (or the LayerNorm kernel) -- see resid_gemm_ln
     if ((rc = ln_in_gemm ? dense_ln(X, L.ln1, L.qkv, QKV, Mi, EPI_BF16) : dense(PC_GEMM_QKV, Hh, L.qkv, QKV, Mi, EPI_BF16))) return rc;
-    if ((rc = rope(QKV, M, T))) return rc;                                     // ESM-2 only: q and k rotated by their positions
+    if ((rc = rope(QKV, M, T)) || (rc = tap_attention(l, QKV))) return rc;     // ESM-2 only: q and k rotated by their positions
     if ((rc = timed(PC_ATTN, [&] { return OPS(launch_attention_bf16, stream, QKV, CTX, B, T, cfg.n_heads, 3 * d, d, d, 2 * d, esm_pad_in_batch ? d_tok : nullptr, cfg.pad_idx, L.bias_kv16, head_dim); }))) return rc;
     const bool last = l == cfg.n_layers - 1;
     if (sel_idx && last) return finish_selected();

@@ -103,4 +103,13 @@ int launch_repr_rows(hipStream_t s, const float* x, const float* gamma, const fl
 int launch_repr_pool(hipStream_t s, const float* in, const int32_t* ranges, float* out, int n_pools, int B, int T, int d_live);
 int repr_pools_check(const char* who, const int32_t* pools, int n_pools, int B, int T);      // host ranges: 0 <= begin, 0 <= count, begin + count <= T
 
+// ---- contact prediction (contact.hip): fp32, one flavour ----
+// One layer folded into the running contact logits: logits[B][T-2][T-2] (+)= sum_h w[h] * APC(P[b][h]) for P[B][H][T][T] (launch_attn_probs),
+// the arithmetic contract and its reduction order at the top of contact.hip.  first: the logits start from 0, not from the stored
+// values; last: bias is added and, with a contacts buffer, contacts = sigmoid(logits).  sums: scratch of contact_sums_floats floats.
+// T >= 3.  w: the H weights of this layer (device)
+size_t contact_sums_floats(int B, int H, int T);
+int launch_contact_accumulate(hipStream_t s, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
+                              bool first, bool last, float* sums, float* logits, float* contacts, int B, int T, int H);
+
 }  // namespace pg

@@ -85,6 +85,17 @@ void attention_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad
 void attention_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, bool has_bias, std::string* text);
 void msa_row_plan_text(int B, int R, int C, int H, int order_bh, std::string* text);
 void msa_row_f32_plan_text(int B, int R, int C, int H, std::string* text);
+// attention probabilities for contact prediction (contact.hip): P[n_seq][H][T][T] fp32 = softmax over the keys of q . k, from one
+// layer's qkv buffer read as that layer's fused attention launch reads it (after the rotary kernel, q pre-scaled; v is not looked at).
+// Keys whose token (key_tok, optional) is pad_idx get exactly 0.  Every T: two sweeps over 64-key tiles, no T-dependent branch.
+// The _f32 pair is the strict mode's (fp32 qkv, split-bf16 three-product scores; bf16 flavour only).  *_plan_text: note_kernel's text
+// for a shape ("error: ..." for one they refuse), no HIP call
+int launch_attn_probs(hipStream_t s, const bf16_t* qkv, float* P, int64_t n_seq, int T, int H, int ld_qkv, int k_off, SeqLayout sl,
+                      const int32_t* key_tok = nullptr, int pad_idx = -1, int head_dim = 64);
+int launch_attn_probs_f32(hipStream_t s, const float* qkv, float* P, int64_t n_seq, int T, int H, int ld_qkv, int k_off, SeqLayout sl,
+                          const int32_t* key_tok = nullptr, int pad_idx = -1, int head_dim = 64);
+void attn_probs_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, std::string* text);
+void attn_probs_f32_plan_text(int64_t n_seq, int T, int H, int head_dim, bool has_pad, std::string* text);
 int launch_msa_row_attention_bf16(hipStream_t s, const bf16_t* qkv, bf16_t* ctx, int B, int R, int C, int H, int ld_qkv,
                                   int ld_ctx, int k_off, int v_off, float scale, float* partial = nullptr,
                                   size_t partial_bytes = 0, int order_bh = 0);

@@ -59,6 +59,7 @@ class NativeMaskedLM:
         self._alt = None                   # auto mode: the bf16-operand engine of the same weights (created on first need)
         self._job_items = 0
         self._guide = None                 # inside draw_guide(): (pg_draw_guide struct, the arrays it points into)
+        self._contact_head = None          # set_contact_head(): (weight float32 [n_layers * n_heads], bias), set on every handle _create builds
         self._force_bf16 = 0               # > 0: inside forced_bf16()
         self._fell_back = False            # a call since the last take_fell_back() was run again in bf16 (PG_ERR_RANGE)
         self._warned = False
@@ -93,7 +94,18 @@ class NativeMaskedLM:
             _lib.check(L.pg_engine_create_embedded(ctypes.byref(c), slot, arr, len(names), int(m.group(1)), precision, ctypes.byref(h)))
         else:
             _lib.check(L.pg_engine_create(ctypes.byref(c), arr, len(names), int(m.group(1)), precision, ctypes.byref(h)))
+        # every handle this object ever holds is built here (.to, the probe's bf16 rebuild, the bf16 twin): the head goes with it
+        if self._contact_head is not None:
+            try:
+                self._apply_contact_head(h)
+            except Exception:
+                L.pg_engine_destroy(h)
+                raise
         return h
+
+    def _apply_contact_head(self, h):
+        w, bias = self._contact_head if self._contact_head is not None else (None, 0.0)
+        _lib.check(_lib.lib().pg_engine_set_contact_head(h, _lib.ptr(w) if w is not None else None, w.size if w is not None else 0, float(bias)))
 
     def _alt_handle(self):
         """The bf16-operand engine of the same weights on the same device (auto mode only), built on first need."""
@@ -252,9 +264,10 @@ class NativeMaskedLM:
         return self.cfg["arch"] == _lib.PG_ARCH_MSA1B
 
     # ---- forward: tokens -> {"logits": ...} ------------------------------------------------
-    def __call__(self, tokens, repr_layers=None):
+    def __call__(self, tokens, repr_layers=None, return_contacts=False, need_head_weights=False):
         """fair-esm's call shape: {"logits": [B, T, V]}, and with repr_layers also {"representations": {layer: [B, T, d]}} under the
-        layer numbers as the caller wrote them (forward_representations)."""
+        layer numbers as the caller wrote them (forward_representations); return_contacts adds "contacts" [B, T-2, T-2]
+        (predict_contacts) and need_head_weights "attentions" [B, n_layers, n_heads, T, T] (forward_attentions of every layer)."""
         import torch
         t = tokens.detach().cpu().numpy() if hasattr(tokens, "detach") else np.asarray(tokens)
         on_gpu = hasattr(tokens, "detach") and tokens.device.type == "cuda"      # a numpy array's .device is the string "cpu"
@@ -267,7 +280,83 @@ class NativeMaskedLM:
             layers = list(repr_layers)
             per_token, _ = self.forward_representations(t, layers)
             result["representations"] = {layer: tensor(per_token[i]) for i, layer in enumerate(layers)}
+        if return_contacts:
+            result["contacts"] = tensor(self.predict_contacts(t))
+        if need_head_weights:
+            result["attentions"] = tensor(np.ascontiguousarray(self.forward_attentions(t, range(self.cfg["n_layers"])).transpose(1, 0, 2, 3, 4)))
         return result
+
+    # ---- contact prediction ---------------------------------------------------------------------
+    def _check_contact_arch(self):
+        if self.is_msa or self.cfg["arch"] == _lib.PG_ARCH_ESM1:
+            raise ValueError("the %s engine has no contact head (ESM-1b and ESM-2 only)" % ("MSA" if self.is_msa else "ESM-1"))
+
+    def set_contact_head(self, weight, bias):
+        """The contact regression (fair-esm's contact_head.regression): weight [n_layers * n_heads] in channel order l * n_heads + h,
+        and its bias; weight None clears it.  Kept on this object and set on every engine handle it builds from now on (the
+        resident one, the bf16 twin of precision="auto", a rebuilt one after the fp16 probe or a later .to())."""
+        self._check_contact_arch()
+        if weight is None:
+            self._contact_head = None
+        else:
+            w = np.ascontiguousarray(weight, dtype=np.float32).reshape(-1)
+            want = self.cfg["n_layers"] * self.cfg["n_heads"]
+            if w.size != want:
+                raise ValueError("contact head of %d weights for a model of %d layers x %d heads = %d channels"
+                                 % (w.size, self.cfg["n_layers"], self.cfg["n_heads"], want))
+            if not (np.isfinite(w).all() and np.isfinite(float(bias))):
+                raise ValueError("contact head: weights and bias must be finite")
+            self._contact_head = (w, float(bias))
+        for h in (self._h, self._alt):
+            if h is not None:
+                self._apply_contact_head(h)
+
+    @property
+    def has_contact_head(self):
+        return self._contact_head is not None
+
+    def forward_contacts(self, tokens, contacts=True, logits=False, attn_layers=()):
+        """C ABI pg_esm_forward_contacts for tokens int32 [B, T]: (contacts float32 [B, T-2, T-2] or None, logits of the same shape or
+        None, attentions float32 [len(attn_layers), B, n_heads, T, T] in the order the layers were given, or None).  attn_layers:
+        0-based block indices, negative ones from the end."""
+        self._check_contact_arch()
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tok.ndim != 2:
+            raise ValueError("forward_contacts takes tokens [B, T]")
+        B, T = tok.shape
+        if T < 3:
+            raise ValueError("forward_contacts: T = %d: a contact map needs <cls>, at least one position and <eos>" % T)
+        n = self.cfg["n_layers"]
+        want = []
+        for layer in attn_layers:
+            if int(layer) != layer or not -n <= layer < n:
+                raise ValueError("attention layer %r is outside -%d .. %d of this %d-layer model" % (layer, n, n - 1, n))
+            want.append(int(layer) % n)
+        if len(set(want)) != len(want):
+            raise ValueError("attention layers %r name a layer twice" % (list(attn_layers),))
+        if (contacts or logits) and self._contact_head is None:
+            raise RuntimeError("no contact head set on this model (set_contact_head)")
+        order = sorted(range(len(want)), key=want.__getitem__)
+        asc = np.asarray([want[i] for i in order], dtype=np.int32)
+        W, H = T - 2, self.cfg["n_heads"]
+        con = np.empty((B, W, W), dtype=np.float32) if contacts else None
+        lg = np.empty((B, W, W), dtype=np.float32) if logits else None
+        att = np.empty((len(asc), B, H, T, T), dtype=np.float32) if len(asc) else None
+        self._call("forward_contacts", tok, _lib.ptr(con) if contacts else None, _lib.ptr(lg) if logits else None,
+                   _lib.ptr(asc) if len(asc) else None, len(asc), _lib.ptr(att) if len(asc) else None)
+        return con, lg, (att[np.argsort(order)] if len(asc) else None)
+
+    def predict_contacts(self, tokens):
+        """fair-esm's model.predict_contacts(tokens): contact probabilities float32 [B, T-2, T-2]."""
+        return self.forward_contacts(tokens)[0]
+
+    def forward_attentions(self, tokens, layers):
+        """The attention probabilities of blocks `layers` (0-based, negative from the end): float32 [len(layers), B, n_heads, T, T],
+        columns at <pad> keys zero.  Needs no contact head."""
+        layers = list(layers)
+        if not layers:
+            raise ValueError("no attention layer requested")
+        return self.forward_contacts(tokens, contacts=False, logits=False, attn_layers=layers)[2]
 
     def normalise_layers(self, layers):
         """Layer numbers 0 .. n_layers from fair-esm's repr_layers: a negative number counts from the end (-1 is n_layers).

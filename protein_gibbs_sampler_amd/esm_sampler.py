@@ -346,22 +346,70 @@ class ESM_sampler():
     def _embed_group(self, lm, seqs, members, layers, kinds, per_tok, start, batch_size, done):
         """embed_batch on one group of equally long sequences: done[i] = the result of sequence i for every member i."""
         L = len(seqs[members[0]])
+        ranges = {"mean": (start, L), "bos": (0, 1)}
+        for tok, first in self._group_chunks(lm, seqs, members, batch_size):
+            pools = np.asarray([[ranges[kind]] * len(tok) for kind in kinds], dtype=np.int32) if kinds else None
+            rows, means = lm.forward_representations(tok, layers, pools, per_token=per_tok)
+            for b in range(len(tok)):
+                out = {kind: {layer: means[k, p, b].copy() for k, layer in enumerate(layers)} for p, kind in enumerate(kinds)}
+                if per_tok:
+                    out["per_tok"] = {layer: rows[k, b, start:start + L].copy() for k, layer in enumerate(layers)}
+                done[members[first + b]] = out
+
+    def _group_chunks(self, lm, seqs, members, batch_size, max_items=None):
+        """The grouping of embed_batch and predict_contacts_batch: the equally long sequences `members` as one token batch (no <pad>
+        reaches the model), yielded as (tokens of a chunk, index of its first member) in chunks of batch_size (None: the whole group),
+        cut further to max_items sequences when given.  Every chunk is a shard of the group's job (set_job_items while the generator
+        runs), so a sequence's result does not depend on the chunking."""
         _, _, tokens = self.model.batch_converter([(str(i), seqs[i]) for i in members])
         tokens = tokens.numpy()
-        ranges = {"mean": (start, L), "bos": (0, 1)}
+        size = len(members) if batch_size is None else batch_size
+        if max_items is not None:
+            size = max(1, min(size, max_items))
         lm.set_job_items(len(members))
         try:
-            for sl, first in _gibbs.chunks(len(members), len(members) if batch_size is None else batch_size):
-                tok = tokens[sl]
-                pools = np.asarray([[ranges[kind]] * len(tok) for kind in kinds], dtype=np.int32) if kinds else None
-                rows, means = lm.forward_representations(tok, layers, pools, per_token=per_tok)
-                for b in range(len(tok)):
-                    out = {kind: {layer: means[k, p, b].copy() for k, layer in enumerate(layers)} for p, kind in enumerate(kinds)}
-                    if per_tok:
-                        out["per_tok"] = {layer: rows[k, b, start:start + L].copy() for k, layer in enumerate(layers)}
-                    done[members[first + b]] = out
+            for sl, first in _gibbs.chunks(len(members), size):
+                yield tokens[sl], first
         finally:
             lm.set_job_items(0)
+
+    # ---- contact prediction (fair-esm's predict_contacts) ----------------------------------------------------
+    CONTACT_MAP_BYTES = 1 << 30      # default cap on one call's staged attention maps (B * n_heads * T * T fp32)
+
+    def predict_contacts(self, seq):
+        """Contact probabilities of one sequence: float32 [L, L] over its residues -- see predict_contacts_batch."""
+        return next(self.predict_contacts_batch([seq]))
+
+    def predict_contacts_batch(self, seq_list, batch_size=None, max_map_bytes=None):
+        """For every sequence, in order, yields its contact probabilities float32 [L, L] (residues only).  The grouping is
+        embed_batch's (_group_chunks); a chunk is also cut so that the one layer of attention maps the engine stages for it,
+        B * n_heads * T * T * 4 bytes, stays under max_map_bytes (default CONTACT_MAP_BYTES = 1 GiB; one sequence always runs).
+        The result does not depend on batch_size or the cap."""
+        self._require_gpu("predict_contacts_batch")
+        lm = self.model.model
+        if not isinstance(lm, NativeMaskedLM):
+            raise TypeError("predict_contacts_batch needs the HIP engine (NativeMaskedLM)")
+        predict = getattr(self.model, "predict_contacts", None) or lm.predict_contacts      # the holder's refusals (models.py) first
+        cap = self.CONTACT_MAP_BYTES if max_map_bytes is None else int(max_map_bytes)
+        if cap < 1:
+            raise ValueError("max_map_bytes must be positive, got %r" % (max_map_bytes,))
+        seqs = [self.clean_seed_seq(seq) for seq in seq_list]
+        if any(len(seq) < 1 for seq in seqs):
+            raise ValueError("predict_contacts_batch: an empty sequence has no contact map")
+        groups = {}
+        for i, seq in enumerate(seqs):
+            groups.setdefault(len(seq), []).append(i)
+        done = {}
+        for i, seq in enumerate(seqs):
+            if i not in done:
+                members = groups[len(seq)]
+                T = len(seq) + 2
+                per_seq = lm.cfg["n_heads"] * T * T * 4
+                for tok, first in self._group_chunks(lm, seqs, members, batch_size, max_items=max(1, cap // per_seq)):
+                    maps = predict(tok)
+                    for b in range(len(tok)):
+                        done[members[first + b]] = maps[b].copy()
+            yield done.pop(i)
 
     def score_mutations(self, seq, mutations, **kwargs):
         """Masked-marginal scores of point mutations such as "A24G" (wild type, 1-based position, mutant):

@@ -37,6 +37,40 @@ class _Wrapper:
         self.alphabet = alphabet
         self.batch_converter = alphabet.get_batch_converter(msa=msa)
         self.model = NativeMaskedLM(cfg, sd, precision)
+        self._contact_source = None      # the files a contact regression was looked for in (none: weights handed in as a state dict)
+        if self.has_contacts:
+            self._load_contact_head(state_dict, checkpoint, filename, seed, synthetic)
+
+    # ESM-1b, ESM-1v and every ESM-2 come with a contact regression; ESM-1 (bias key) and the MSA Transformer are not covered
+    has_contacts = True
+
+    def _load_contact_head(self, state_dict, checkpoint, filename, seed, synthetic):
+        if state_dict is not None:
+            return
+        path = checkpoint or _w.find_cached_checkpoint(filename)
+        if path:
+            self._contact_source = "%s or %s" % (path, _w.contact_regression_path(path))
+            # a regression that is not this model's (contact_head.* has always been ignored on load) must not keep the model from
+            # sampling: it is left out, and predict_contacts says why
+            try:
+                head = _w.contact_head_from_checkpoint(path, self.cfg)
+            except ValueError as e:
+                head = None
+                self._contact_source += "; refused: %s" % e
+        else:
+            head = _w.synthetic_contact_head(self.cfg, seed) if synthetic else None
+        if head is not None:
+            self.model.set_contact_head(*head)
+
+    def predict_contacts(self, tokens):
+        """fair-esm's model.predict_contacts(tokens): float32 [B, T-2, T-2].  NotImplementedError for the models without a contact
+        entry, RuntimeError naming the files looked in when the checkpoint came without a regression."""
+        if not self.has_contacts:
+            raise NotImplementedError("%s has no contact prediction in this package (ESM-1b, ESM-1v and ESM-2 only)" % type(self).__name__)
+        if not self.model.has_contact_head:
+            raise RuntimeError("%s: no contact regression loaded (looked in %s): pass one with .model.set_contact_head(weight, bias)"
+                               % (type(self).__name__, self._contact_source or "nothing: the weights were handed in as a state dict"))
+        return self.model.predict_contacts(tokens)
 
 
 class ESM1b(_Wrapper):
@@ -134,6 +168,7 @@ ESM2_MODELS = {cli: globals()[row["wrapper"]] for cli, row in _w.ESM2_SIZES.item
 
 class ESM_MSA1(_Wrapper):
     """esm_msa1b_t12_100M_UR50S (models.py:84-88) with the reference's patched MSA batch converter."""
+    has_contacts = False      # row-attention contacts are not built
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.MSA1B_CONFIG), Alphabet(True, False), True, state_dict, checkpoint,
@@ -143,6 +178,7 @@ class ESM_MSA1(_Wrapper):
 class _ESM1(_Wrapper):
     """ESM-1 family (models.py:69-82): the 35-token "ESM-1" alphabet, <cls> prepended, no <eos>."""
     _cfg, _file = None, None
+    has_contacts = False      # the bias key changes the softmax and the map shape
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(self._cfg), Alphabet(True, False, arch="ESM-1"), False, state_dict, checkpoint,

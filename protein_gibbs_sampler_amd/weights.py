@@ -509,3 +509,58 @@ def to_fair_esm_checkpoint_v2(sd, cfg, namespace=True):
 def find_cached_checkpoint(filename):
     p = os.path.join(os.path.expanduser("~/.cache/torch/hub/checkpoints"), filename)
     return p if os.path.exists(p) else None
+
+
+# ---- the contact regression head (fair-esm's ContactPredictionHead: one logistic regression over n_layers * n_heads channels) ----
+_CONTACT_KEYS = ("contact_head.regression.weight", "contact_head.regression.bias")
+
+
+def contact_regression_path(path):
+    """Where fair-esm keeps the contact regression of the ESM-1b / ESM-1v / ESM-2 checkpoint `path`: the sibling
+    `<stem>-contact-regression.pt` ({"model": {"contact_head.regression.weight", "contact_head.regression.bias"}})."""
+    stem, ext = os.path.splitext(path)
+    return stem + "-contact-regression" + (ext or ".pt")
+
+
+def _contact_head_of(sd, cfg, where):
+    """(weight float32 [n_layers * n_heads], bias) from a state dict's contact_head.regression.{weight, bias} under any of fair-esm's
+    prefixes, None when it holds neither.  A shape that is not the model's raises, naming both."""
+    found = {}
+    for k, v in sd.items():
+        name = _strip_fair_esm_prefixes(k)
+        if name in _CONTACT_KEYS:
+            found[name] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+    if not found:
+        return None
+    if len(found) != 2:
+        raise ValueError("%s holds %s without %s" % (where, *[k for k in _CONTACT_KEYS if k in found], *[k for k in _CONTACT_KEYS if k not in found]))
+    w, b = found[_CONTACT_KEYS[0]], found[_CONTACT_KEYS[1]]
+    n = cfg["n_layers"] * cfg["n_heads"]
+    if w.shape not in ((1, n), (n,)):
+        raise ValueError("%s: contact_head.regression.weight has shape %r, the model of %d layers x %d heads needs %r"
+                         % (where, tuple(w.shape), cfg["n_layers"], cfg["n_heads"], (1, n)))
+    if b.size != 1:
+        raise ValueError("%s: contact_head.regression.bias has shape %r, not %r" % (where, tuple(b.shape), (1,)))
+    return np.ascontiguousarray(w.reshape(-1)), float(b.reshape(-1)[0])
+
+
+def contact_head_from_checkpoint(path, cfg):
+    """The contact regression that goes with the fair-esm checkpoint `path` of a model `cfg`: (weight float32 [n_layers * n_heads]
+    in channel order l * n_heads + h, bias), taken from the file itself when it carries contact_head.regression.* and otherwise from
+    its sibling contact_regression_path(path); None when neither has one.  load_fair_esm_checkpoint does not look at these keys."""
+    import torch
+    for p in (path, contact_regression_path(path)):
+        if not os.path.exists(p):
+            continue
+        blob = torch.load(p, map_location="cpu", weights_only=False)
+        sd = blob["model"] if isinstance(blob, dict) and "model" in blob else blob
+        head = _contact_head_of(sd, cfg, p)
+        if head is not None:
+            return head
+    return None
+
+
+def synthetic_contact_head(cfg, seed=0, std=1.0, bias=-1.0):
+    """A seeded contact regression for a model `cfg`: weight N(0, std^2) float32 [n_layers * n_heads], and the bias."""
+    rng = np.random.default_rng([seed, 0xC0])
+    return (std * rng.standard_normal(cfg["n_layers"] * cfg["n_heads"])).astype(np.float32), float(bias)
