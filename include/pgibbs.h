@@ -277,7 +277,8 @@ PG_API int pg_repr_dbg_rows(int device, const float* x, int64_t M, int d, int d_
 /* ---- contact prediction --------------------------------------------------------------------------
  * fair-esm's model.predict_contacts(tokens) / return_contacts=True and need_head_weights=True, HuggingFace's predict_contacts and
  * output_attentions=True, for PG_ARCH_ESM1B and PG_ARCH_ESM2 engines (embedded models included: channel l * n_heads + h with the
- * model's own head count).  PG_ARCH_ESM1 (its bias key changes the softmax and the map shape) and the MSA engine are refused.
+ * model's own head count).  PG_ARCH_ESM1 (its bias key changes the softmax and the map shape) is refused; the MSA engine has an entry
+ * of its own, pg_msa_forward_contacts (below), and is refused by pg_esm_forward_contacts.
  * With A[b][l][h][i][j] = block l's softmax probability of query i over key j (<pad> keys masked, as in the forward):
  *   live[b][t]  = tokens[b][t] != eos_idx && tokens[b][t] != pad_idx; A is zeroed wherever i or j is not live, then the first and the
  *                 last row and column are cut off: the window t = 1 .. T-2 of W = T - 2 positions;
@@ -291,7 +292,8 @@ PG_API int pg_repr_dbg_rows(int device, const float* x, int64_t M, int d, int d_
  * masks, fp32 softmax; deterministic, and a sequence's result does not depend on the other sequences of the call.
  *
  * pg_engine_set_contact_head: weight[n_weights] with n_weights == n_layers * n_heads, uploaded once; weight NULL clears the head.
- * PG_ERR_INVALID: null engine; an MSA or ESM-1 engine (the message names the architecture); a wrong count; a non-finite value.
+ * PG_ERR_INVALID: null engine; an ESM-1 engine (the message names the architecture); a wrong count; a non-finite value.  An MSA engine
+ * takes a head too: it is the one pg_msa_forward_contacts folds (below).
  *
  * pg_esm_forward_contacts:
  *   contacts_out / logits_out   [B][T-2][T-2] or NULL
@@ -316,6 +318,42 @@ PG_API int pg_contact_dbg_probs(int device, int precision, const float* qkv, int
                                 int pad_idx, float* probs_out, char* plan, int plan_bytes);
 PG_API int pg_contact_dbg_accumulate(int device, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
                                      int first, int last, float* logits_inout, float* contacts_out, int B, int T, int H);
+
+/* ---- MSA Transformer contacts (fair-esm's return_contacts=True on esm_msa1b_t12_100M_UR50S) ------------
+ * tokens[B][R][C], row 0 the query sequence, column 0 <cls>; the MSA alphabet appends no <eos>.  Per block l and head h the TIED row
+ * attention map
+ *   S[b][h][i][j] = (64^-0.5 / sqrt(R)) * sum_r sum_d q[b,r,i,h,d] k[b,r,j,h,d],   P = softmax_j S        [B][n_heads][C][C]
+ * with the forward's semantics for a batch that holds <pad>: q zeroed at <pad> positions of any row, the scores of key columns that are
+ * <pad> in ROW 0 set to -10000 (finite, as in fair-esm), R the padded depth.  The head is the one above with prepend_bos = True,
+ * append_eos = False: only the <cls> row and column are cut (window t = 1 .. C-1, W = C - 1), nothing is masked for <eos>, channel
+ * c = l * n_heads + h, "live" = row 0's token at that column is not <pad>; same fp32 arithmetic, order and conventions (a12 == 0
+ * contributes 0; a not-live row or column gets logit = bias exactly).  Column-attention maps and MSA representations are not offered.
+ * The maps come from launches of their own into staging of their own (csrc/msa_contact.hip; one block's S and P at a time): an MSA's
+ * result does not depend on the other MSAs of the call nor on how the forward splits its row loop.
+ *
+ * pg_engine_set_contact_head takes PG_ARCH_MSA1B engines too (n_layers * n_heads weights).
+ * pg_msa_forward_contacts:
+ *   contacts_out / logits_out   [B][C-1][C-1] or NULL
+ *   attn_layers[n_attn]         0-based block indices, strictly ascending; may be NULL / 0
+ *   row_attn_out                [B][n_attn][n_heads][C][C] or NULL; given exactly when layers are; needs no head
+ * PG_ERR_INVALID, before a device is touched and in this order: null tokens; all three outputs NULL; row_attn_out without layers or
+ * layers without row_attn_out; a negative layer or layers not strictly ascending; C < 2; a null engine; an engine that is not MSA-1b;
+ * contacts or logits wanted with no head set; the call check of the other MSA entries; a layer >= n_layers; one block's maps beyond
+ * 2^31 - 1 values; tokens outside the vocabulary.  What the forward refuses the call refuses with the forward's message
+ * (PG_ERR_UNSUPPORTED: PG_PREC_F16 with <pad> or with C > 576).  PG_ERR_RANGE when a copied-back value is not finite.
+ *
+ * Kernel-level entries: pg_msa_contact_dbg_probs -- probs_out[B][H][C][C] from qkv[B * R * C][3 * H * 64] fp32 (rows [q | k | v]; rounded
+ * to the 16-bit type of `precision`, or kept fp32 for PG_PREC_FP32: the strict scores kernel), scores scaled by `scale`, tok[B][R][C]
+ * optional (the ragged semantics with pad_idx); plan: the scores launcher's plan text, with probs_out NULL only that, without a device.
+ * pg_contact_dbg_accumulate_window -- pg_contact_dbg_accumulate with a window of W = T - 1 - tail positions (tail 0 or 1) and the
+ * tokens of item b at tokens + b * tok_stride (>= T); logits_inout / contacts_out [B][W][W]. */
+PG_API int pg_msa_forward_contacts(pg_engine*, const int32_t* tokens, int B, int R, int C, float* contacts_out, float* logits_out,
+                                   const int32_t* attn_layers, int n_attn, float* row_attn_out);
+PG_API int pg_msa_contact_dbg_probs(int device, int precision, const float* qkv, int B, int R, int C, int H, float scale, const int32_t* tok,
+                                    int pad_idx, float* probs_out, char* plan, int plan_bytes);
+PG_API int pg_contact_dbg_accumulate_window(int device, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w,
+                                            float bias, int first, int last, float* logits_inout, float* contacts_out, int B, int T, int H,
+                                            int tail, int64_t tok_stride);
 
 /* ---- ESM-MSA-1b ---------------------------------------------------------------------------
  * tokens[B][R][C] (C = L + 1: <cls> then L columns, no <eos>).
@@ -483,7 +521,8 @@ PG_API int pg_dbg_gather_plan(int rank, int world, int64_t rows, int width, cons
  * class names: "gemm", "attention", "layernorm", "embed", "head", "sample", and "rope": ESM-2's rotation of q and k, timed under
  * its own class (not under "attention"; no launch of the other architectures falls into it); "repr_rows" and "repr_pool": the two
  * kernels of pg_esm_forward_representations (no other call has a launch in them); "attn_probs" and "contact": the attention
- * probabilities and the APC / regression fold of pg_esm_forward_contacts (likewise).  */
+ * probabilities and the APC / regression fold of pg_esm_forward_contacts and pg_msa_forward_contacts (likewise; for the latter the
+ * tied row scores and their softmax are "attn_probs").  */
 PG_API int pg_prof_enable(pg_engine*, int on);
 PG_API int pg_prof_reset(pg_engine*);
 PG_API int pg_prof_get(pg_engine*, const char* kernel_class, double* total_ms, int64_t* launches);

@@ -140,6 +140,12 @@ SIGNATURES = [
     ("pg_contact_dbg_probs", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_char_p, c_int]),
     ("pg_contact_dbg_accumulate", c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p,
                                           c_int, c_int, c_int]),
+    # the MSA Transformer's contacts: the engine entry, the kernel-level entry of its scores and softmax launchers, the fold's window form
+    ("pg_msa_forward_contacts", c_int, [EngineHandle, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    ("pg_msa_contact_dbg_probs", c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_char_p,
+                                         c_int]),
+    ("pg_contact_dbg_accumulate_window", c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p,
+                                                 c_void_p, c_int, c_int, c_int, c_int, c_int64]),
     ("pg_comm_unique_id", c_int, [c_void_p]),
     ("pg_comm_create", c_int, [c_int, c_int, c_void_p, c_int, POINTER(c_void_p)]),
     ("pg_comm_destroy", None, [c_void_p]),

@@ -179,10 +179,14 @@ struct ContactScope {
 const char* arch_name(int arch) {
   return arch == PG_ARCH_MSA1B ? "MSA-1b" : arch == PG_ARCH_ESM1 ? "ESM-1" : arch == PG_ARCH_ESM2 ? "ESM-2" : "ESM-1b";
 }
-// the architectures with a contacts entry: ESM-1b and ESM-2 (<cls> ... <eos>, no bias key); 0 = fine
-int contact_arch_check(const char* who, const Engine& e) {
-  if (e.cfg.arch == PG_ARCH_MSA1B || e.cfg.arch == PG_ARCH_ESM1)
-    return fail(PG_ERR_INVALID, std::string(who) + ": the " + arch_name(e.cfg.arch) + " architecture has no contact head in this engine (ESM-1b and ESM-2 only)");
+// the architectures with a contacts entry: ESM-1b and ESM-2 (<cls> ... <eos>, no bias key) through pg_esm_forward_contacts, MSA-1b
+// (row-attention maps) through pg_msa_forward_contacts; msa_ok: the caller serves the MSA engine too (the head setter).  0 = fine
+int contact_arch_check(const char* who, const Engine& e, bool msa_ok = false) {
+  if (e.cfg.arch == PG_ARCH_MSA1B && !msa_ok)
+    return fail(PG_ERR_INVALID, std::string(who) + ": the MSA-1b architecture has no contact head behind this entry (ESM-1b and ESM-2 only; "
+                                                   "row-attention contacts: pg_msa_forward_contacts)");
+  if (e.cfg.arch == PG_ARCH_ESM1)
+    return fail(PG_ERR_INVALID, std::string(who) + ": the ESM-1 architecture has no contact head in this engine (ESM-1b, ESM-2 and MSA-1b only)");
   return PG_OK;
 }
 
@@ -247,6 +251,80 @@ int forward_contacts(pg_engine* h, const int32_t* tokens, int B, int T, float* c
   if (contacts_out && (rc = check_finite(e, contacts_out, n_win))) return rc;
   if (logits_out && (rc = check_finite(e, logits_out, n_win))) return rc;
   return n_attn ? check_finite(e, attn_out, n_map * n_attn) : PG_OK;
+}
+
+// tokens[B][R][C] in; contact probabilities and / or logits [B][C-1][C-1] and / or the tied row-attention maps [B][n_attn][H][C][C] of
+// the listed blocks out: forward_contacts' shape on the MSA trunk (Engine::tap_row_attention).  Everything in the argument list is
+// refused before a device is touched, in the order pgibbs.h states
+int msa_forward_contacts(pg_engine* h, const int32_t* tokens, int B, int R, int C, float* contacts_out, float* logits_out,
+                         const int32_t* attn_layers, int n_attn, float* row_attn_out) {
+  const std::string who = "pg_msa_forward_contacts";
+  if (!tokens) return fail(PG_ERR_INVALID, who + ": null tokens");
+  if (!contacts_out && !logits_out && !row_attn_out) return fail(PG_ERR_INVALID, who + ": no output requested");
+  const bool want_layers = attn_layers && n_attn > 0;
+  if (n_attn < 0 || (row_attn_out != nullptr) != want_layers || (!attn_layers && n_attn > 0))
+    return fail(PG_ERR_INVALID, who + ": attention layers and row_attn_out come together or not at all");
+  for (int i = 0; i < n_attn; ++i) {
+    if (attn_layers[i] < 0) return fail(PG_ERR_INVALID, who + ": attention layer " + std::to_string(attn_layers[i]) + " is negative");
+    if (i && attn_layers[i] <= attn_layers[i - 1]) return fail(PG_ERR_INVALID, who + ": attention layers must be strictly ascending");
+  }
+  if (C < 2) return fail(PG_ERR_INVALID, who + ": C = " + std::to_string(C) + ": a contact map needs <cls> and at least one position");
+  if (!h) return fail(PG_ERR_INVALID, who + ": null engine");
+  Engine& e = h->e;
+  int rc;
+  if (e.cfg.arch != PG_ARCH_MSA1B)
+    return fail(PG_ERR_INVALID, who + ": the " + arch_name(e.cfg.arch) + " architecture has no row attention (MSA-1b only; pg_esm_forward_contacts)");
+  const bool fold = contacts_out || logits_out;
+  if (fold && !e.contact_w) return fail(PG_ERR_INVALID, who + ": no contact head set (pg_engine_set_contact_head); attention maps alone need none");
+  if ((rc = e.check_call(true, B, R, C))) return rc;
+  if (n_attn && attn_layers[n_attn - 1] >= e.cfg.n_layers)
+    return fail(PG_ERR_INVALID, who + ": attention layer " + std::to_string(attn_layers[n_attn - 1]) + " is outside 0 .. " + std::to_string(e.cfg.n_layers - 1));
+  if (B == 0) return PG_OK;
+  const int64_t M = (int64_t)B * R * C;
+  const int W = C - 1, H = e.cfg.n_heads;
+  if ((double)B * H * C * msa_row_scores_ld(C) > 2147483647.0)
+    return fail(PG_ERR_INVALID, who + ": the row-attention maps of one block exceed 2^31 - 1 values: use smaller batches");
+  bool has_pad;
+  if ((rc = scan_tokens(e, who.c_str(), tokens, (size_t)M, &has_pad))) return rc;
+  DeviceGuard g(e.device);
+  const size_t n_map = (size_t)B * H * C * C, n_win = (size_t)B * W * W;
+  if ((rc = e.d_tokens.ensure((size_t)M * 4, e.stream)) || (rc = e.contact_P.ensure(n_map * 4, e.stream)) ||
+      (rc = e.contact_S.ensure((size_t)B * H * C * msa_row_scores_ld(C) * 4, e.stream))) return rc;
+  if (n_attn && (rc = e.contact_attn.ensure(n_map * n_attn * 4, e.stream))) return rc;
+  if (fold && ((rc = e.contact_logits.ensure(n_win * 4, e.stream)) || (rc = e.contact_probs.ensure(n_win * 4, e.stream)) ||
+               (rc = e.contact_sums.ensure(contact_window_sums_floats(B, H, C, 0) * 4, e.stream)))) return rc;
+  PG_HIP(hipMemcpyAsync(e.d_tokens.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, e.stream));
+  ContactTap tap;
+  tap.d_tok = e.d_tokens.as<int32_t>();
+  tap.B = B;
+  tap.R = R;
+  tap.T = C;
+  tap.fold = fold;
+  tap.logits = fold ? e.contact_logits.as<float>() : nullptr;
+  tap.contacts = contacts_out ? e.contact_probs.as<float>() : nullptr;
+  if (n_attn) tap.attn_layers.assign(attn_layers, attn_layers + n_attn);
+  tap.attn_out = n_attn ? e.contact_attn.as<float>() : nullptr;
+  {
+    PadFlag pad(e, has_pad);
+    ContactScope scope(e, &tap);
+    rc = e.trunk(e.d_tokens.as<int32_t>(), B, R, C);
+  }
+  if (rc) return rc;
+  if (tap.folded != e.cfg.n_layers || tap.next_attn != tap.attn_layers.size())
+    return fail(PG_ERR_HIP, who + ": the forward did not show every layer's row attention");
+  // the engine stages the requested maps as [n_attn][B][H][C][C]; the caller's layout is [B][n_attn][H][C][C]
+  if (contacts_out) PG_HIP(hipMemcpyAsync(contacts_out, e.contact_probs.p, n_win * 4, hipMemcpyDeviceToHost, e.stream));
+  if (logits_out) PG_HIP(hipMemcpyAsync(logits_out, e.contact_logits.p, n_win * 4, hipMemcpyDeviceToHost, e.stream));
+  const size_t one = (size_t)H * C * C;
+  for (int i = 0; i < n_attn; ++i)
+    for (int b = 0; b < B; ++b)
+      PG_HIP(hipMemcpyAsync(row_attn_out + ((size_t)b * n_attn + i) * one, e.contact_attn.as<float>() + ((size_t)i * B + b) * one, one * 4,
+                            hipMemcpyDeviceToHost, e.stream));
+  PG_HIP(hipStreamSynchronize(e.stream));
+  if ((rc = e.chain_check())) return rc;
+  if (contacts_out && (rc = check_finite(e, contacts_out, n_win))) return rc;
+  if (logits_out && (rc = check_finite(e, logits_out, n_win))) return rc;
+  return n_attn ? check_finite(e, row_attn_out, n_map * n_attn) : PG_OK;
 }
 
 // A Gibbs call on host buffers: tokens and the index table go to the device, run(d_tokens, d_idx, d_sampled_logits, d_sampled_tokens)
@@ -470,11 +548,16 @@ int pg_esm_forward_contacts(pg_engine* h, const int32_t* tokens, int B, int T, f
   PG_RETRY_WITHOUT_CHAIN_TRUNK(h, forward_contacts(h, tokens, B, T, contacts_out, logits_out, attn_layers, n_attn, attn_out));
 }
 
+int pg_msa_forward_contacts(pg_engine* h, const int32_t* tokens, int B, int R, int C, float* contacts_out, float* logits_out,
+                            const int32_t* attn_layers, int n_attn, float* row_attn_out) {
+  return msa_forward_contacts(h, tokens, B, R, C, contacts_out, logits_out, attn_layers, n_attn, row_attn_out);
+}
+
 int pg_engine_set_contact_head(pg_engine* h, const float* weight, int n_weights, float bias) {
   const char* who = "pg_engine_set_contact_head";
   if (!h) return fail(PG_ERR_INVALID, std::string(who) + ": null engine");
   Engine& e = h->e;
-  if (int rc = contact_arch_check(who, e)) return rc;
+  if (int rc = contact_arch_check(who, e, true)) return rc;
   if (weight) {
     const int want = e.cfg.n_layers * e.cfg.n_heads;
     if (n_weights != want)

@@ -949,6 +949,80 @@ int pg_contact_dbg_accumulate(int device, const float* P, const int32_t* tokens,
   return contacts_out && last ? s.down(contacts_out, dcon, n_win) : PG_OK;
 }
 
+/* pg_contact_dbg_accumulate_window: the window form (launch_contact_accumulate_window).  The window is W = T - 1 - tail positions (tail 0 or
+ * 1) and the tokens of item b are tokens[b * tok_stride .. + T - 1] of tokens[(B - 1) * tok_stride + T]; logits_inout / contacts_out
+ * [B][W][W].  tail 1 with tok_stride T is pg_contact_dbg_accumulate. */
+int pg_contact_dbg_accumulate_window(int device, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
+                                     int first, int last, float* logits_inout, float* contacts_out, int B, int T, int H, int tail,
+                                     int64_t tok_stride) {
+  const char* who = "pg_contact_dbg_accumulate_window";
+  if (!P || !tokens || !w || !logits_inout || B < 1 || H < 1) return fail(PG_ERR_INVALID, std::string(who) + ": bad argument");
+  if (tail != 0 && tail != 1) return fail(PG_ERR_INVALID, std::string(who) + ": tail must be 0 or 1");
+  if (T < 2 + tail) return fail(PG_ERR_INVALID, std::string(who) + ": T must be at least " + std::to_string(2 + tail));
+  if (tok_stride < T) return fail(PG_ERR_INVALID, std::string(who) + ": tok_stride must be at least T");
+  if ((double)B * H * T * T > 2147483647.0 || (double)B * tok_stride > 2147483647.0)
+    return fail(PG_ERR_INVALID, std::string(who) + ": more than 2^31 - 1 values");
+  Dbg s;
+  int rc;
+  if ((rc = s.open(device))) return rc;
+  const int W = T - 1 - tail;
+  const size_t n_win = (size_t)B * W * W;
+  const float* dP = s.up(P, (size_t)B * H * T * T);
+  const int32_t* dtok = s.up(tokens, (size_t)(B - 1) * tok_stride + T);
+  const float* dw = s.up(w, (size_t)H);
+  float* dlog = s.up(logits_inout, n_win);
+  float* dcon = contacts_out ? s.alloc<float>(n_win) : nullptr;
+  float* dsum = s.alloc<float>(contact_window_sums_floats(B, H, T, tail));
+  if ((rc = s.check())) return rc;
+  if ((rc = launch_contact_accumulate_window(nullptr, dP, dtok, eos_idx, pad_idx, dw, bias, first != 0, last != 0, dsum, dlog, dcon, B, T, H, tail,
+                                             (size_t)tok_stride))) return rc;
+  if ((rc = s.down(logits_inout, dlog, n_win))) return rc;
+  return contacts_out && last ? s.down(contacts_out, dcon, n_win) : PG_OK;
+}
+
+/* The two launchers of msa_contact.hip alone, on host buffers: probs_out[B][H][C][C] = launch_row_softmax_probs of launch_msa_row_scores
+ * (precision bf16 / fp16: qkv rounded to that type first) or launch_msa_row_scores_f32 (PG_PREC_FP32: the fp32 values) of
+ * qkv[B * R * C][3 H 64], read as Engine::msa_trunk hands a block's row qkv over (ld = 3 d, k at d), scores scaled by `scale`.  tok
+ * (optional) [B][R][C] with pad_idx: the ragged semantics.  plan (may be NULL): the scores launcher's plan text; with probs_out NULL the
+ * plan alone, without a device.  Everything is refused on the host before a device is looked for. */
+int pg_msa_contact_dbg_probs(int device, int precision, const float* qkv, int B, int R, int C, int H, float scale, const int32_t* tok,
+                             int pad_idx, float* probs_out, char* plan, int plan_bytes) {
+  const char* who = "pg_msa_contact_dbg_probs";
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  int rc = dbg_precision(who, precision, true);
+  if (rc) return rc;
+  if (B < 1 || R < 1 || C < 1 || H < 1 || (plan && plan_bytes < 1) || (!probs_out && !plan) || (probs_out && !qkv))
+    return fail(PG_ERR_INVALID, std::string(who) + ": bad argument");
+  const bool strict = precision == PG_PREC_FP32;
+  if (!probs_out) {
+    std::string text;
+    if (strict) msa_row_scores_f32_plan_text(B, R, C, H, tok != nullptr, &text);
+    else OPS(msa_row_scores_plan_text, B, R, C, H, tok != nullptr, &text);
+    snprintf(plan, (size_t)plan_bytes, "%s", text.c_str());
+    return PG_OK;
+  }
+  const int ldS = msa_row_scores_ld(C);
+  if ((double)B * R * C * 3 * H * 64 > 2147483647.0 || (double)B * H * C * ldS > 2147483647.0)
+    return fail(PG_ERR_INVALID, std::string(who) + ": more than 2^31 - 1 values");
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const int d = H * 64;
+  const int64_t M = (int64_t)B * R * C;
+  const size_t n_map = (size_t)B * H * C * C;
+  const float* dq = s.up(qkv, (size_t)M * 3 * d);
+  const int32_t* dtok = s.up(tok, (size_t)M);
+  bf16_t* bq = strict ? nullptr : s.alloc<bf16_t>((size_t)M * 3 * d);
+  float* dS = s.alloc<float>((size_t)B * H * C * ldS);
+  float* dP = s.alloc<float>(n_map);
+  if ((rc = s.check())) return rc;
+  clear_noted_kernels();
+  if (strict) rc = launch_msa_row_scores_f32(nullptr, dq, dS, B, R, C, H, 3 * d, d, scale, dtok, pad_idx);
+  else if (!(rc = to16(precision, dq, bq, M * 3 * d))) rc = OPS(launch_msa_row_scores, nullptr, bq, dS, B, R, C, H, 3 * d, d, scale, dtok, pad_idx);
+  if (rc || (rc = launch_row_softmax_probs(nullptr, dS, dP, (int64_t)B * H * C, C, ldS))) return rc;
+  dbg_noted_text(plan, plan_bytes);
+  return s.down(probs_out, dP, n_map);
+}
+
 /* ---- embedded models: the host side of pg_engine_create_embedded, no device ---- */
 int pg_embedded_image(const char* name, const float* src, int64_t numel, int n_heads, int head_width, int head_slot, int d_ffn, int vocab,
                       float* image, int64_t image_numel) {

@@ -402,6 +402,18 @@ static std::string plan_text(const StrictRowPlan& p) {
 // <pad> tokens change what the kernels compute, not the plan
 void msa_row_f32_plan_text(int B, int R, int C, int H, std::string* text) { *text = plan_text(plan_msa_row_f32(B, R, C, H)); }
 
+// step 1 of the plan: launch_msa_row_attention_f32's first launch, and launch_msa_row_scores_f32's only one
+static void launch_row_scores_split(hipStream_t s, const StrictRowPlan& p, const float* qkv, float* scores, int R, int C, int H, int ld_qkv,
+                                    int k_off, float scale, const int32_t* tok, int pad_idx) {
+  const int ldS = msa_row_scores_ld(C);
+  auto go = [&](auto kb) {
+    hipLaunchKernelGGL(msa_row_scores_split_kernel<decltype(kb)::value>, dim3(p.grid_scores), dim3(256), 0, s, qkv, scores, R, C, H, ld_qkv,
+                       k_off, scale, p.n_chunk, p.n_ktile, ldS, tok, pad_idx);
+  };
+  if (p.kb == 4) go(std::integral_constant<int, 4>{});
+  else go(std::integral_constant<int, 10>{});
+}
+
 int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores, bf16_t* ctx, int split_d, int B, int R,
                                  int C, int H, int ld_qkv, int ld_ctx, int k_off, int v_off, float scale, const int32_t* tok,
                                  int pad_idx) {
@@ -409,15 +421,35 @@ int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores,
   if (!p.grid_apply) return 0;
   note_kernel(plan_text(p).c_str());
   const int ldS = msa_row_scores_ld(C);         // `scores` holds B*H*C rows of ldS floats
-  auto split = [&](auto kb) {
+  launch_row_scores_split(s, p, qkv, scores, R, C, H, ld_qkv, k_off, scale, tok, pad_idx);
+  auto apply = [&](auto kb) {
     constexpr int KB = decltype(kb)::value;
-    hipLaunchKernelGGL(msa_row_scores_split_kernel<KB>, dim3(p.grid_scores), dim3(256), 0, s, qkv, scores, R, C, H, ld_qkv, k_off,
-                       scale, p.n_chunk, p.n_ktile, ldS, tok, pad_idx);
     hipLaunchKernelGGL(msa_row_apply_split_kernel<KB>, dim3(p.grid_apply), dim3(256), 0, s, qkv, scores, ctx, split_d, R, C, H,
                        ld_qkv, ld_ctx, v_off, p.n_chunk, ldS);
   };
-  if (p.kb == 4) split(std::integral_constant<int, 4>{});
-  else split(std::integral_constant<int, 10>{});
+  if (p.kb == 4) apply(std::integral_constant<int, 4>{});
+  else apply(std::integral_constant<int, 10>{});
+  PG_HIP(hipGetLastError());
+  return 0;
+}
+
+// The scores launch alone (the contacts tap): the same kernel, grid and arguments as the first launch above
+void msa_row_scores_f32_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text) {
+  const StrictRowPlan p = plan_msa_row_f32(B, R, C, H);
+  *text = !p.grid_scores ? "nothing"
+                         : "row-scores-f32 kb" + std::to_string(p.kb) + " kt" + std::to_string(p.n_ktile) + (has_pad ? " pad " : " ") +
+                               std::to_string(p.grid_scores) + "wg";
+}
+int launch_msa_row_scores_f32(hipStream_t s, const float* qkv, float* scores, int B, int R, int C, int H, int ld_qkv, int k_off, float scale,
+                              const int32_t* tok, int pad_idx) {
+  if (B < 0 || R < 0 || C <= 0 || H < 1) return fail(1, "row scores: bad shape");
+  if ((int64_t)B * H * ((C + 63) / 64) * ((C + 159) / 160) > 0x7fffffff) return fail(1, "row scores: too many alignments");
+  const StrictRowPlan p = plan_msa_row_f32(B, R, C, H);
+  if (!p.grid_scores) return 0;
+  std::string text;
+  msa_row_scores_f32_plan_text(B, R, C, H, tok != nullptr, &text);
+  note_kernel(text.c_str());
+  launch_row_scores_split(s, p, qkv, scores, R, C, H, ld_qkv, k_off, scale, tok, pad_idx);
   PG_HIP(hipGetLastError());
   return 0;
 }

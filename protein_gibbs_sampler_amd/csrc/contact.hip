@@ -8,6 +8,8 @@
 //                              qkv, every operand split into a bf16 (hi, lo) pair, kl.qh + kh.ql per 32 d and then kh.qh, fp32
 //                              accumulation, small terms first (attention_f32.hip's scheme) -- bf16 flavour only.
 //   launch_contact_accumulate  logits[B][W][W] (W = T - 2) (+)= sum_h w[h] . APC(symmetrised, live-masked P[b][h]) -- one flavour.
+//                              launch_contact_accumulate_window: the same with W = T - 1 - tail and a token-row stride (the MSA
+//                              Transformer's maps: tail 0, row 0 of tokens[B][R][C], eos_idx = -1; the kernels say how).
 //
 // launch_attn_probs: how a row of any length is held.  One workgroup = (sequence, head, 64 queries), wave w its queries 16 w .. +15;
 // the keys go through the LDS in tiles of 64 and are swept TWICE at every T: sweep 1 keeps the row's running maximum m and sum l
@@ -302,13 +304,16 @@ __device__ __forceinline__ float contact_wave_tree(float acc) {
   return acc;
 }
 
+// The window form: the window is token positions 1 .. T - 1 - tail (W = T - 1 - tail: tail = 1 cuts a trailing <eos> position -- the
+// ESM family --, tail = 0 none -- the MSA Transformer, whose alphabet appends no <eos>), and the tokens of batch item b start at
+// tokens + b * tok_stride (T for a [B][T] batch; R * C for tokens[B][R][C], so that row 0 of each MSA is what is read).
 // One workgroup of 4 waves per (b, h): wave w sums the window rows i = w, w + 4, ... (a1), then wave 0 sums a1 (a12)
 __global__ __launch_bounds__(256) void contact_sums_kernel(const float* __restrict__ P, const int32_t* __restrict__ tokens, int eos_idx,
-                                                          int pad_idx, float* __restrict__ a1, float* __restrict__ a12, int H, int T) {
-  const int W = T - 2;
+                                                          int pad_idx, float* __restrict__ a1, float* __restrict__ a12, int H, int T, int W,
+                                                          size_t tok_stride) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t bh = blockIdx.x;
-  const int32_t* tok = tokens + (bh / H) * (size_t)T;
+  const int32_t* tok = tokens + (bh / H) * tok_stride;
   const float* A = P + bh * (size_t)T * T;
   float* a1o = a1 + bh * (size_t)W;
   for (int i = wave; i < W; i += 4) {
@@ -335,12 +340,12 @@ __global__ __launch_bounds__(256) void contact_sums_kernel(const float* __restri
 __global__ __launch_bounds__(256) void contact_fold_kernel(const float* __restrict__ P, const int32_t* __restrict__ tokens, int eos_idx,
                                                           int pad_idx, const float* __restrict__ a1, const float* __restrict__ a12,
                                                           const float* __restrict__ w, float bias, int first, int last,
-                                                          float* __restrict__ logits, float* __restrict__ contacts, int H, int T) {
-  const int W = T - 2;
+                                                          float* __restrict__ logits, float* __restrict__ contacts, int H, int T, int W,
+                                                          size_t tok_stride) {
   const int j = blockIdx.x * 16 + (threadIdx.x & 15), i = blockIdx.y * 16 + (threadIdx.x >> 4);
   const size_t b = blockIdx.z;
   if (i >= W || j >= W) return;
-  const int32_t* tok = tokens + b * (size_t)T;
+  const int32_t* tok = tokens + b * tok_stride;
   const bool on = contact_live(tok[i + 1], eos_idx, pad_idx) && contact_live(tok[j + 1], eos_idx, pad_idx);
   const size_t o = (b * W + i) * (size_t)W + j;
   float logit = first ? 0.f : logits[o];
@@ -359,21 +364,32 @@ __global__ __launch_bounds__(256) void contact_fold_kernel(const float* __restri
   if (last && contacts) contacts[o] = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-logit)));
 }
 
-size_t contact_sums_floats(int B, int H, int T) { return (size_t)B * H * (T - 2) + (size_t)B * H; }
+size_t contact_window_sums_floats(int B, int H, int T, int tail) { return (size_t)B * H * (T - 1 - tail) + (size_t)B * H; }
+size_t contact_sums_floats(int B, int H, int T) { return contact_window_sums_floats(B, H, T, 1); }
 
-int launch_contact_accumulate(hipStream_t s, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
-                              bool first, bool last, float* sums, float* logits, float* contacts, int B, int T, int H) {
-  if (B < 0 || T < 3 || H < 1) return fail(1, "contact_accumulate: bad shape (T >= 3: <cls>, at least one position, <eos>)");
+int launch_contact_accumulate_window(hipStream_t s, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
+                                     bool first, bool last, float* sums, float* logits, float* contacts, int B, int T, int H, int tail,
+                                     size_t tok_stride) {
+  if (tail != 0 && tail != 1) return fail(1, "contact_accumulate: tail must be 0 or 1");
+  if (B < 0 || T < 2 + tail || H < 1)
+    return fail(1, tail ? "contact_accumulate: bad shape (T >= 3: <cls>, at least one position, <eos>)"
+                        : "contact_accumulate: bad shape (T >= 2: <cls> and at least one position)");
+  if (tok_stride < (size_t)T) return fail(1, "contact_accumulate: token rows overlap");
   if (B == 0) return 0;
-  const int W = T - 2;
+  const int W = T - 1 - tail;
   if ((int64_t)B * H > 0x7fffffff || B > 65535 || (W + 15) / 16 > 65535) return fail(1, "contact_accumulate: too many sequences");
   float* a1 = sums;
   float* a12 = sums + (size_t)B * H * W;
-  hipLaunchKernelGGL(contact_sums_kernel, dim3((unsigned)(B * H)), dim3(256), 0, s, P, tokens, eos_idx, pad_idx, a1, a12, H, T);
+  hipLaunchKernelGGL(contact_sums_kernel, dim3((unsigned)(B * H)), dim3(256), 0, s, P, tokens, eos_idx, pad_idx, a1, a12, H, T, W, tok_stride);
   hipLaunchKernelGGL(contact_fold_kernel, dim3((W + 15) / 16, (W + 15) / 16, B), dim3(256), 0, s, P, tokens, eos_idx, pad_idx, a1, a12, w, bias,
-                     first ? 1 : 0, last ? 1 : 0, logits, contacts, H, T);
+                     first ? 1 : 0, last ? 1 : 0, logits, contacts, H, T, W, tok_stride);
   PG_HIP(hipGetLastError());
   return 0;
+}
+
+int launch_contact_accumulate(hipStream_t s, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
+                              bool first, bool last, float* sums, float* logits, float* contacts, int B, int T, int H) {
+  return launch_contact_accumulate_window(s, P, tokens, eos_idx, pad_idx, w, bias, first, last, sums, logits, contacts, B, T, H, 1, (size_t)T);
 }
 
 }  // namespace pg

@@ -100,9 +100,13 @@ struct ReprTap {
 // qkv buffer -- after the rotary kernel, next to the fused attention launch, which does not modify it -- to tap_attention.  The
 // probabilities of ONE layer are staged at a time (contact_P: B H T T fp32, so memory does not grow with depth) and folded into the
 // contact logits; a layer whose map the caller asked for is written to its slot of attn_out instead and folded from there
+// pg_msa_forward_contacts: msa_trunk hands every block's ROW qkv buffer to tap_row_attention, which runs its own scores launch into
+// tap-owned staging (contact_S: one layer's B H C rows of scaled fp32 scores) and the softmax over it; T is the column count C, the
+// window cuts <cls> only ([B][C-1][C-1]) and the live mask is row 0 of each MSA
 struct ContactTap {
-  const int32_t* d_tok = nullptr;    // the call's tokens [B][T]
+  const int32_t* d_tok = nullptr;    // the call's tokens [B][T] ([B][R][T] for the MSA engine)
   int B = 0, T = 0;
+  int R = 1;                         // alignment depth (MSA engine)
   bool fold = false;                 // contacts or logits wanted: the engine's head is folded over every layer into `logits`
   float* logits = nullptr;           // [B][T-2][T-2]
   float* contacts = nullptr;         // the same shape, or null
@@ -173,6 +177,10 @@ struct Engine {
   // carries no selection and never takes the persistent single-chain launch, which hides the per-layer qkv
   ContactTap* ctap = nullptr;
   int tap_attention(int l, const void* qkv_rows);      // block l's qkv (the engine's 16-bit type; fp32 in strict mode) is ready
+  // the MSA trunk's form (pg_msa_forward_contacts): block l's row qkv is ready, right before its row-attention launch.  The maps come
+  // from the tap's own scores launch, never from the forward's scratch: they do not depend on the batch or on the split-R decision
+  int tap_row_attention(int l, const void* qkv_rows);
+  DevBuf contact_S;                                    // one layer's scaled row scores [B*H*C][msa_row_scores_ld(C)]
   // the regression head (pg_engine_set_contact_head): n_layers * n_heads weights on the device (channel l * n_heads + h), null = none
   float* contact_w = nullptr;
   float contact_bias = 0.f;

@@ -111,7 +111,7 @@ Engine::~Engine() {
   DevBuf* bufs[] = {&x, &h, &qkv, &ctx, &ffn, &sel_h, &sel_g, &logits, &d_tokens, &d_idx, &d_samp_tok, &d_samp_logits,
                     &d_rowmap, &scratch, &d_iter, &tmp_idx, &tmp_out, &x_sel, &ctx_sel, &h_sel, &ffn_sel, &ffn_f32, &scores, &splitk,
                     &chain_sync, &chain_part, &chain_snap, &repr_rows, &repr_pooled, &repr_ranges,
-                    &contact_P, &contact_sums, &contact_logits, &contact_probs, &contact_attn};
+                    &contact_P, &contact_sums, &contact_logits, &contact_probs, &contact_attn, &contact_S};
   for (DevBuf* b : bufs) b->release();
   if (chain_err) (void)hipHostFree(chain_err);
   if (range_err) (void)hipHostFree(range_err);
@@ -767,6 +767,33 @@ int Engine::tap_attention(int l, const void* qkv_rows) {
   });
 }
 
+// The MSA trunk's contacts tap (engine.h): block l's row qkv is ready.  The tap's own scores launch (the 16-bit MFMA kernel of
+// msa_contact.hip, or the strict scores kernel) fills contact_S, the softmax writes the dense maps to the one-layer staging buffer or to
+// the caller's slot, and the head folds them over the window 1 .. C - 1 of row 0 (no <eos> in the MSA alphabet: eos_idx -1, tail 0)
+int Engine::tap_row_attention(int l, const void* qkv_rows) {
+  if (!ctap) return PG_OK;
+  ContactTap& t = *ctap;
+  const int d = cfg.d_model, H = cfg.n_heads, C = t.T;
+  const size_t map = (size_t)t.B * H * C * C;
+  float* Pl = contact_P.as<float>();
+  if (t.next_attn < t.attn_layers.size() && t.attn_layers[t.next_attn] == l) Pl = t.attn_out + map * t.next_attn++;
+  float* S = contact_S.as<float>();
+  const float row_scale = 0.125f / sqrtf((float)t.R);
+  const int32_t* pad_tok = esm_pad_in_batch ? t.d_tok : nullptr;
+  int rc = timed(PC_ATTN_PROBS, [&] {
+    int r = strict() ? launch_msa_row_scores_f32(stream, (const float*)qkv_rows, S, t.B, t.R, C, H, 3 * d, d, row_scale, pad_tok, cfg.pad_idx)
+                     : OPS(launch_msa_row_scores, stream, (const bf16_t*)qkv_rows, S, t.B, t.R, C, H, 3 * d, d, row_scale, pad_tok, cfg.pad_idx);
+    return r ? r : launch_row_softmax_probs(stream, S, Pl, (int64_t)t.B * H * C, C, msa_row_scores_ld(C));
+  });
+  ++t.folded;
+  if (rc || !t.fold) return rc;
+  return timed(PC_CONTACT, [&] {
+    return launch_contact_accumulate_window(stream, Pl, t.d_tok, -1, cfg.pad_idx, contact_w + (size_t)l * H, contact_bias, l == 0,
+                                            l == cfg.n_layers - 1, contact_sums.as<float>(), t.logits, t.contacts, t.B, C, H, 0,
+                                            (size_t)t.R * C);
+  });
+}
+
 int Engine::set_contact_head(const float* weight, int n_weights, float bias) {
   if (contact_w) {
     PG_HIP(hipStreamSynchronize(stream));
@@ -1024,8 +1051,10 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
     float* QKVf = qkv.as<float>();
     if ((rc = embed_rows(d_tok, M, C, R, nullptr))) return rc;
     const SeqLayout colS = {C, R * C, 1, C};
-    for (const MsaLayer& L : msa_layers) {
+    for (int l = 0; l < cfg.n_layers; ++l) {
+      const MsaLayer& L = msa_layers[l];
       rc = strict_attention(L.ln_row, L.row_qkv, L.row_out, Mi, M, [&](int split_d) {
+        if (int r = tap_row_attention(l, QKVf)) return r;
         return timed(PC_ATTN, [&] { return launch_msa_row_attention_f32(stream, QKVf, scores.as<float>(), CTX, split_d, B, R, C, H, 3 * d, 3 * d, d, 2 * d, row_scale, pad_tok, cfg.pad_idx); });
       });
       if (rc) return rc;
@@ -1056,6 +1085,7 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
         if ((rc = scores.ensure(need, stream))) return rc;           // the allocator's own error (out of memory)
         part = scores.as<float>();
       }
+      if ((rc = tap_row_attention(l, QKV))) return rc;
       if ((rc = timed(PC_ATTN, [&] { return OPS(launch_msa_row_attention_bf16, stream, QKV, CTX, B, R, C, H, 3 * d, d, d, 2 * d, row_scale, part, part ? scores.bytes : 0, (int)(job_batch(B) * H)); }))) return rc;
     } else {
       // alignments wider than the MFMA row-attention kernel's register budget: fp32 scores through a scratch buffer
@@ -1063,6 +1093,7 @@ int Engine::msa_trunk(const int32_t* d_tok, int B, int R, int C, const int32_t* 
         return fail(PG_ERR_UNSUPPORTED, "fp16 precision mode: alignments wider than 576 columns take the split-bf16 row attention, "
                                         "which exists for bf16 operands only -- use precision bf16 or fp32");
       if ((rc = scratch.ensure((size_t)Mp * 3 * d * 4, stream)) || (rc = scores.ensure((size_t)B * H * C * msa_row_scores_ld(C) * 4, stream))) return rc;
+      if ((rc = tap_row_attention(l, QKV))) return rc;
       rc = timed(PC_ATTN, [&] {
         int r2 = launch_bf16_to_f32(stream, QKV, scratch.as<float>(), (int64_t)M * 3 * d);
         if (r2) return r2;

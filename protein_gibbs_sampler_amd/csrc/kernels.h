@@ -111,5 +111,16 @@ int repr_pools_check(const char* who, const int32_t* pools, int n_pools, int B, 
 size_t contact_sums_floats(int B, int H, int T);
 int launch_contact_accumulate(hipStream_t s, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
                               bool first, bool last, float* sums, float* logits, float* contacts, int B, int T, int H);
+// The window form: W = T - 1 - tail positions 1 .. T - 1 - tail (tail 1: the form above; tail 0: no trailing position is cut -- the MSA
+// Transformer), the tokens of item b at tokens + b * tok_stride (R * C: row 0 of tokens[B][R][C]).  logits / contacts [B][W][W], sums of
+// contact_window_sums_floats floats.  The same kernels and arithmetic
+size_t contact_window_sums_floats(int B, int H, int T, int tail);
+int launch_contact_accumulate_window(hipStream_t s, const float* P, const int32_t* tokens, int eos_idx, int pad_idx, const float* w, float bias,
+                                     bool first, bool last, float* sums, float* logits, float* contacts, int B, int T, int H, int tail,
+                                     size_t tok_stride);
+
+// ---- MSA Transformer contacts (msa_contact.hip): P[n_rows][C] fp32 dense = softmax over the first C of each S row of ldS floats
+// (launch_msa_row_scores[_f32]); one wave per row.  A row with a non-finite score is written as NaN
+int launch_row_softmax_probs(hipStream_t s, const float* S, float* P, int64_t n_rows, int C, int ldS);
 
 }  // namespace pg

@@ -152,6 +152,14 @@ static inline int msa_row_scores_ld(int C) { return (C + 3) & ~3; }
 int launch_msa_row_attention_f32(hipStream_t s, const float* qkv, float* scores, bf16_t* ctx, int split_d, int B, int R,
                                  int C, int H, int ld_qkv, int ld_ctx, int k_off, int v_off, float scale,
                                  const int32_t* tok = nullptr, int pad_idx = -1);
+// Its first launch alone (msa_row_scores_split_kernel): the scaled fp32 scores S[B*H*C][msa_row_scores_ld(C)] of the strict mode, for
+// the contacts tap.  launch_msa_row_scores (msa_contact.hip) writes the same buffer from 16-bit q and k.  *_plan_text: no HIP call
+int launch_msa_row_scores_f32(hipStream_t s, const float* qkv, float* scores, int B, int R, int C, int H, int ld_qkv, int k_off, float scale,
+                              const int32_t* tok = nullptr, int pad_idx = -1);
+int launch_msa_row_scores(hipStream_t s, const bf16_t* qkv, float* scores, int B, int R, int C, int H, int ld_qkv, int k_off, float scale,
+                          const int32_t* tok = nullptr, int pad_idx = -1);
+void msa_row_scores_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text);
+void msa_row_scores_f32_plan_text(int B, int R, int C, int H, bool has_pad, std::string* text);
 // d_iter (optional): device-side iteration counter; idx is then the base of a [n_iters][...] table (hipGraph replay)
 int launch_gather_rows(hipStream_t s, const void* src, void* dst, const int32_t* idx, const int32_t* row_map, int P, int width,
                        int64_t n_sel, int row_bytes, const int32_t* d_iter = nullptr);

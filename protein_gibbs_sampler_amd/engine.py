@@ -288,14 +288,20 @@ class NativeMaskedLM:
 
     # ---- contact prediction ---------------------------------------------------------------------
     def _check_contact_arch(self):
-        if self.is_msa or self.cfg["arch"] == _lib.PG_ARCH_ESM1:
-            raise ValueError("the %s engine has no contact head (ESM-1b and ESM-2 only)" % ("MSA" if self.is_msa else "ESM-1"))
+        if self.is_msa:
+            raise ValueError("the MSA engine has no contact head over [B, T] attention maps (ESM-1b and ESM-2 only): its regression "
+                             "over the tied row-attention maps is set_row_contact_head / forward_row_contacts")
+        if self.cfg["arch"] == _lib.PG_ARCH_ESM1:
+            raise ValueError("the ESM-1 engine has no contact head (ESM-1b and ESM-2 only)")
 
     def set_contact_head(self, weight, bias):
         """The contact regression (fair-esm's contact_head.regression): weight [n_layers * n_heads] in channel order l * n_heads + h,
         and its bias; weight None clears it.  Kept on this object and set on every engine handle it builds from now on (the
         resident one, the bf16 twin of precision="auto", a rebuilt one after the fp16 probe or a later .to())."""
         self._check_contact_arch()
+        self._set_head(weight, bias)
+
+    def _set_head(self, weight, bias):
         if weight is None:
             self._contact_head = None
         else:
@@ -313,7 +319,7 @@ class NativeMaskedLM:
 
     @property
     def has_contact_head(self):
-        return self._contact_head is not None
+        return not self.is_msa and self._contact_head is not None
 
     def forward_contacts(self, tokens, contacts=True, logits=False, attn_layers=()):
         """C ABI pg_esm_forward_contacts for tokens int32 [B, T]: (contacts float32 [B, T-2, T-2] or None, logits of the same shape or
@@ -357,6 +363,70 @@ class NativeMaskedLM:
         if not layers:
             raise ValueError("no attention layer requested")
         return self.forward_contacts(tokens, contacts=False, logits=False, attn_layers=layers)[2]
+
+    # ---- MSA Transformer: contacts from the tied row-attention maps ------------------------------
+    def _check_row_contact_arch(self):
+        if not self.is_msa:
+            raise ValueError("row-attention contacts are the MSA engine's: this model takes set_contact_head / forward_contacts")
+
+    def set_row_contact_head(self, weight, bias):
+        """The MSA Transformer's contact regression over its n_layers * n_heads tied row-attention maps (channel l * n_heads + h) and
+        its bias; weight None clears it.  Kept and applied to every handle exactly as set_contact_head's is."""
+        self._check_row_contact_arch()
+        self._set_head(weight, bias)
+
+    @property
+    def has_row_contact_head(self):
+        return self.is_msa and self._contact_head is not None
+
+    def _block_layers(self, attn_layers):
+        """0-based block indices (negative from the end) -> (ascending int32 array, the caller's order as an index into it)"""
+        n = self.cfg["n_layers"]
+        want = []
+        for layer in attn_layers:
+            if int(layer) != layer or not -n <= layer < n:
+                raise ValueError("attention layer %r is outside -%d .. %d of this %d-layer model" % (layer, n, n - 1, n))
+            want.append(int(layer) % n)
+        if len(set(want)) != len(want):
+            raise ValueError("attention layers %r name a layer twice" % (list(attn_layers),))
+        order = sorted(range(len(want)), key=want.__getitem__)
+        return np.asarray([want[i] for i in order], dtype=np.int32), np.argsort(order)
+
+    def forward_row_contacts(self, tokens, contacts=True, logits=False, attn_layers=()):
+        """C ABI pg_msa_forward_contacts for tokens int32 [B, R, C]: (contacts float32 [B, C-1, C-1] or None, logits of the same shape
+        or None, row attentions float32 [B, len(attn_layers), n_heads, C, C] in the order the layers were given, or None).
+        attn_layers: 0-based block indices, negative ones from the end."""
+        self._check_row_contact_arch()
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tok.ndim != 3:
+            raise ValueError("forward_row_contacts takes tokens [B, R, C]")
+        B, R, C = tok.shape
+        if C < 2:
+            raise ValueError("forward_row_contacts: C = %d: a contact map needs <cls> and at least one position" % C)
+        asc, back = self._block_layers(attn_layers)
+        if (contacts or logits) and self._contact_head is None:
+            raise RuntimeError("no contact head set on this model (set_row_contact_head)")
+        if not (contacts or logits or len(asc)):
+            raise ValueError("forward_row_contacts: no output requested")
+        W, H = C - 1, self.cfg["n_heads"]
+        con = np.empty((B, W, W), dtype=np.float32) if contacts else None
+        lg = np.empty((B, W, W), dtype=np.float32) if logits else None
+        att = np.empty((B, len(asc), H, C, C), dtype=np.float32) if len(asc) else None
+        self._call("forward_contacts", tok, _lib.ptr(con) if contacts else None, _lib.ptr(lg) if logits else None,
+                   _lib.ptr(asc) if len(asc) else None, len(asc), _lib.ptr(att) if len(asc) else None)
+        return con, lg, (att[:, back] if len(asc) else None)
+
+    def predict_row_contacts(self, tokens):
+        """fair-esm's MSATransformer.predict_contacts(tokens): contact probabilities float32 [B, C-1, C-1]."""
+        return self.forward_row_contacts(tokens)[0]
+
+    def forward_row_attentions(self, tokens, layers=None):
+        """The tied row-attention probabilities of blocks `layers` (0-based, negative from the end; None: every block), fair-esm's
+        row_attentions: float32 [B, len(layers), n_heads, C, C].  Needs no contact head."""
+        layers = list(range(self.cfg["n_layers"])) if layers is None else list(layers)
+        if not layers:
+            raise ValueError("no attention layer requested")
+        return self.forward_row_contacts(tokens, contacts=False, logits=False, attn_layers=layers)[2]
 
     def normalise_layers(self, layers):
         """Layer numbers 0 .. n_layers from fair-esm's repr_layers: a negative number counts from the end (-1 is n_layers).

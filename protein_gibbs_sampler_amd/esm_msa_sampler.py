@@ -362,6 +362,57 @@ class ESM_MSA_sampler():
                 calls.append((copies[sl], row_of, idx[sl], tgt[sl]))
             yield dict(calls=calls, items=[dict(denom=denom, rows=rows, start=range_start)])
 
+    # ---- contact prediction (fair-esm's MSATransformer.predict_contacts) ---------------------------------
+    CONTACT_MAP_BYTES = 1 << 30      # default cap on one call's staged row-attention maps (B * n_heads * C * C fp32)
+
+    def predict_contacts(self, msa):
+        """Contact probabilities of one alignment's query sequence (row 0): float32 [L, L] -- see predict_contacts_batch."""
+        return next(self.predict_contacts_batch([msa]))
+
+    def predict_contacts_batch(self, msa_list, batch_size=None, max_map_bytes=None):
+        """For every MSA (a list of aligned rows, as log_likelihood_batch takes them; row 0 is the query), in order, yields the
+        contact probabilities float32 [L, L] over its L columns, from the tied row-attention maps.  MSAs of equal depth and width are
+        run together, batch_size at a time (None: the whole group); an MSA is NEVER padded to another's shape -- <pad> rows and
+        columns change the tied map and its 1/sqrt(R) --, so a contact map is each alignment's own.  A chunk is also cut so that the
+        one block of maps the engine stages for it, B * n_heads * C * C * 4 bytes, stays under max_map_bytes (default
+        CONTACT_MAP_BYTES = 1 GiB; one MSA always runs).  The result does not depend on batch_size or the cap."""
+        self._require_gpu("predict_contacts_batch")
+        lm = self.model.model
+        if not isinstance(lm, NativeMaskedLM):
+            raise TypeError("predict_contacts_batch needs the HIP engine (NativeMaskedLM)")
+        predict = getattr(self.model, "predict_row_contacts", None) or lm.predict_row_contacts      # the holder's refusals (models.py) first
+        cap = self.CONTACT_MAP_BYTES if max_map_bytes is None else int(max_map_bytes)
+        if cap < 1:
+            raise ValueError("max_map_bytes must be positive, got %r" % (max_map_bytes,))
+        rows = [[(str(r), self.clean_seed_seq(seq)) for r, seq in enumerate(msa)] for msa in msa_list]
+        for i, msa in enumerate(rows):
+            if not msa or len(msa[0][1]) < 1:
+                raise ValueError("predict_contacts_batch: alignment %d is empty: it has no contact map" % i)
+            if any(len(seq) != len(msa[0][1]) for _, seq in msa):
+                raise ValueError("predict_contacts_batch: the rows of alignment %d are not equally long" % i)
+        groups = {}
+        for i, msa in enumerate(rows):
+            groups.setdefault((len(msa), len(msa[0][1])), []).append(i)
+        done = {}
+        for i, msa in enumerate(rows):
+            if i not in done:
+                members = groups[len(msa), len(msa[0][1])]
+                C = len(msa[0][1]) + 1
+                size = max(1, cap // (lm.cfg["n_heads"] * C * C * 4))
+                if batch_size is not None:
+                    size = max(1, min(size, batch_size))
+                _, _, tokens = self.model.batch_converter([rows[m] for m in members])      # [n, R, C]: one shape, no <pad>
+                tokens = tokens.numpy()
+                lm.set_job_items(len(members))      # every chunk is a shard of the group's job: its maps do not depend on the chunking
+                try:
+                    for sl, first in _gibbs.chunks(len(members), size):
+                        maps = predict(tokens[sl])
+                        for b in range(len(maps)):
+                            done[members[first + b]] = maps[b].copy()
+                finally:
+                    lm.set_job_items(0)
+            yield done.pop(i)
+
     # ---- masked-marginal substitution tables ------------------------------------------------------------
     def masked_marginals_batch(self, msa_list, target_index=0, with_masking=True, count_gaps=False, mask_distance=float("inf"),
                                batch_size=1, normalise="vocab"):

@@ -38,11 +38,13 @@ class _Wrapper:
         self.batch_converter = alphabet.get_batch_converter(msa=msa)
         self.model = NativeMaskedLM(cfg, sd, precision)
         self._contact_source = None      # the files a contact regression was looked for in (none: weights handed in as a state dict)
-        if self.has_contacts:
+        if self.has_contacts or self.has_row_contacts:
             self._load_contact_head(state_dict, checkpoint, filename, seed, synthetic)
 
-    # ESM-1b, ESM-1v and every ESM-2 come with a contact regression; ESM-1 (bias key) and the MSA Transformer are not covered
+    # ESM-1b, ESM-1v and every ESM-2 come with a contact regression over their attention maps (predict_contacts); the MSA Transformer's
+    # is over its tied row-attention maps and has names of its own (has_row_contacts, predict_row_contacts); ESM-1 (bias key) has none
     has_contacts = True
+    has_row_contacts = False
 
     def _load_contact_head(self, state_dict, checkpoint, filename, seed, synthetic):
         if state_dict is not None:
@@ -60,13 +62,14 @@ class _Wrapper:
         else:
             head = _w.synthetic_contact_head(self.cfg, seed) if synthetic else None
         if head is not None:
-            self.model.set_contact_head(*head)
+            (self.model.set_row_contact_head if self.has_row_contacts else self.model.set_contact_head)(*head)
 
     def predict_contacts(self, tokens):
         """fair-esm's model.predict_contacts(tokens): float32 [B, T-2, T-2].  NotImplementedError for the models without a contact
         entry, RuntimeError naming the files looked in when the checkpoint came without a regression."""
         if not self.has_contacts:
-            raise NotImplementedError("%s has no contact prediction in this package (ESM-1b, ESM-1v and ESM-2 only)" % type(self).__name__)
+            raise NotImplementedError("%s has no contact prediction in this package (ESM-1b, ESM-1v and ESM-2 only%s)"
+                                      % (type(self).__name__, "; the MSA Transformer's is predict_row_contacts" if self.has_row_contacts else ""))
         if not self.model.has_contact_head:
             raise RuntimeError("%s: no contact regression loaded (looked in %s): pass one with .model.set_contact_head(weight, bias)"
                                % (type(self).__name__, self._contact_source or "nothing: the weights were handed in as a state dict"))
@@ -168,11 +171,21 @@ ESM2_MODELS = {cli: globals()[row["wrapper"]] for cli, row in _w.ESM2_SIZES.item
 
 class ESM_MSA1(_Wrapper):
     """esm_msa1b_t12_100M_UR50S (models.py:84-88) with the reference's patched MSA batch converter."""
-    has_contacts = False      # row-attention contacts are not built
+    has_contacts = False      # no [B, T] contacts entry: the maps are the tied row attention's, over tokens [B, R, C]
+    has_row_contacts = True   # fair-esm's return_contacts=True: the regression over the n_layers x n_heads row-attention maps
 
     def __init__(self, state_dict=None, checkpoint=None, seed=0, precision="auto", config=None, synthetic=False):
         super().__init__(config or dict(_w.MSA1B_CONFIG), Alphabet(True, False), True, state_dict, checkpoint,
                          "esm_msa1b_t12_100M_UR50S.pt", seed, precision, synthetic, config is not None)
+
+    def predict_row_contacts(self, tokens):
+        """fair-esm's MSATransformer.predict_contacts(tokens) for tokens [B, R, C]: float32 [B, C-1, C-1], the contact probabilities of
+        the query sequence's residues (row 0; only <cls> is cut).  RuntimeError naming the files looked in when the checkpoint came
+        without a regression."""
+        if not self.model.has_row_contact_head:
+            raise RuntimeError("%s: no contact regression loaded (looked in %s): pass one with .model.set_row_contact_head(weight, bias)"
+                               % (type(self).__name__, self._contact_source or "nothing: the weights were handed in as a state dict"))
+        return self.model.predict_row_contacts(tokens)
 
 
 class _ESM1(_Wrapper):
