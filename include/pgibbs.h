@@ -582,6 +582,21 @@ PG_API int pg_dbg_attention_plan(int kind, int precision, int64_t n_seq_or_B, in
  * projection-attention kernel of the MSA column block, one head per 256 x 192 tile) against the two launches of the ESM-1b path;
  * ms[0] fused, ms[1] projection, ms[2] attention (HIP events, `iters` launches each); max_diff = max |fused - unfused| context */
 PG_API int pg_dbg_qkv_attention_bench(int device, int B, int T, int H, int iters, double* ms, double* max_diff);
+/* The fused column QKV + attention kernel of the MSA column block (csrc/gemm_colattn.hip) in one launch of its own, or the two launches
+ * it replaces, on the same operands: x[B*R*C][d] fp32 in token order (row (b*R + r)*C + c), d = H*64; w[3 d][d] with the q rows first
+ * and bias[3 d] (the engine's col_qkv); R in {32, 64, 128, 256}; precision PG_PREC_BF16 or PG_PREC_F16 (the strict mode never runs
+ * this kernel).  x and w are rounded to the 16-bit type on the device.
+ *   fused 1: the operand rows are permuted on the host to column-major order (row (b*C + c)*R + r) into round_up(B*C*R, 256) rows,
+ *            the rows behind the live ones holding pad_fill (finite) in every feature; launch_headmajor_qkv regroups weights and bias
+ *            per head; launch_gemm_colattn.  PGIBBS_MSA_COLFUSE=0 is answered with the launcher's error, never with the other path;
+ *   fused 0: launch_gemm_bf16 (bf16 q, k, v rows) on the token-order rows padded to 256, then launch_attention_seq_bf16 over the
+ *            B*C strided sequences of R tokens -- the engine's unfused branch.
+ * ctx_inout[ctx_rows][d], ctx_rows >= B*R*C: the caller's pattern is uploaded in the 16-bit type, the launch writes its context rows
+ * (token order) into it, and all ctx_rows rows come back widened -- what the kernel does not write keeps the pattern.  plan (NULL: not
+ * wanted): the text the launches recorded.  All refusals (null pointer; B, C, H < 1; R; fused; pad_fill; ctx_rows; more than
+ * 2^31 - 1 values; precision) are PG_ERR_INVALID with their own message and precede the device lookup. */
+PG_API int pg_dbg_colattn(int device, int precision, const float* x, const float* w, const float* bias, float* ctx_inout, int64_t ctx_rows,
+                   int B, int R, int C, int H, int fused, float pad_fill, char* plan, int plan_bytes);
 /* y = LayerNorm(x[M][d]) * gamma + beta */
 PG_API int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float* beta, float* y, int M, int d,
                      float eps);

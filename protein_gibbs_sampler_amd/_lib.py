@@ -167,6 +167,8 @@ SIGNATURES = [
     ("pg_dbg_gemm_plan", c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),
     ("pg_dbg_attention_plan", c_int, [c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_char_p, c_int]),
     ("pg_dbg_qkv_attention_bench", c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
+    ("pg_dbg_colattn", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float,
+                               c_char_p, c_int]),
     ("pg_dbg_layernorm", c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),
     ("pg_dbg_layernorm_operand", c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),
     ("pg_dbg_attention", c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int]),

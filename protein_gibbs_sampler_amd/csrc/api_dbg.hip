@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "engine.h"
@@ -363,6 +364,64 @@ int pg_dbg_qkv_attention_bench(int device, int B, int T, int H, int iters, doubl
     *max_diff = worst;
   }
   return PG_OK;
+}
+
+/* gemm_colattn_kernel alone (fused 1), or the two launches of the engine's unfused column block on the same 16-bit operands
+ * (fused 0): x[B*R*C][d] in token order, w[3 d][d] (q rows first) and bias[3 d] -> context rows in token order.  The fused launch
+ * gets what the engine gives it: the operand rows permuted on the host to column-major order (row (b*C + c)*R + r) in a buffer of
+ * round_up(B*C*R, 256) rows whose rows behind the live ones hold pad_fill, and head-major weights from launch_headmajor_qkv.
+ * ctx_inout[ctx_rows][d] goes up as the caller's pattern in the 16-bit type and comes back whole, widened.  Everything is refused on
+ * the host before a device is looked for; the kernel switched off (PGIBBS_MSA_COLFUSE=0) is the launcher's own error. */
+int pg_dbg_colattn(int device, int precision, const float* x, const float* w, const float* bias, float* ctx_inout, int64_t ctx_rows, int B,
+                   int R, int C, int H, int fused, float pad_fill, char* plan, int plan_bytes) {
+  if (plan && plan_bytes > 0) plan[0] = 0;
+  int rc = dbg_precision("pg_dbg_colattn", precision, false);
+  if (rc) return rc;
+  if (!x || !w || !bias || !ctx_inout) return fail(PG_ERR_INVALID, "pg_dbg_colattn: null argument");
+  if (B < 1 || C < 1 || H < 1) return fail(PG_ERR_INVALID, "pg_dbg_colattn: B, C and H must be at least 1");
+  if (!(R == 32 || R == 64 || R == 128 || R == 256)) return fail(PG_ERR_INVALID, "pg_dbg_colattn: R must be 32, 64, 128 or 256");
+  if (fused < 0 || fused > 1 || (plan && plan_bytes < 1)) return fail(PG_ERR_INVALID, "pg_dbg_colattn: fused is 0 or 1, and a plan buffer has room");
+  if (!std::isfinite(pad_fill)) return fail(PG_ERR_INVALID, "pg_dbg_colattn: pad_fill must be finite");
+  const double m_live = (double)B * R * C;
+  if ((double)ctx_rows < m_live) return fail(PG_ERR_INVALID, "pg_dbg_colattn: ctx_rows must be at least B*R*C");
+  if ((m_live + 255.0) * 3 * H * 64 > 2147483647.0 || (double)ctx_rows * H * 64 > 2147483647.0 || 3.0 * H * 64 * H * 64 > 2147483647.0)
+    return fail(PG_ERR_INVALID, "pg_dbg_colattn: more than 2^31 - 1 values");
+  Dbg s;
+  if ((rc = s.open(device))) return rc;
+  const int d = H * 64;
+  const int64_t M = (int64_t)B * R * C, Mp = round_up64(M, kRowPad);
+  // the operand rows as the launch reads them: column-major for the fused kernel, token order otherwise; pad_fill behind them
+  std::vector<float> hx((size_t)Mp * d, pad_fill);
+  for (int64_t t = 0; t < M; ++t) {
+    const int64_t b = t / ((int64_t)R * C), r = t / C % R, c = t % C;
+    const int64_t row = fused ? (b * C + c) * R + r : t;
+    memcpy(&hx[(size_t)row * d], x + (size_t)t * d, (size_t)d * 4);
+  }
+  const float* dx = s.up(hx.data(), hx.size());
+  const float* dw = s.up(w, (size_t)3 * d * d);
+  const float* db = s.up(bias, (size_t)3 * d);
+  float* dctx = s.up(ctx_inout, (size_t)ctx_rows * d);      // the caller's pattern, fp32 on the way in and on the way out
+  bf16_t* bx = s.alloc<bf16_t>((size_t)Mp * d);
+  bf16_t* bw = s.alloc<bf16_t>((size_t)3 * d * d);
+  bf16_t* c16 = s.alloc<bf16_t>((size_t)ctx_rows * d);
+  bf16_t* bwh = fused ? s.alloc<bf16_t>((size_t)3 * d * d) : nullptr;
+  float* dbh = fused ? s.alloc<float>((size_t)3 * d) : nullptr;
+  bf16_t* qkv = fused ? nullptr : s.alloc<bf16_t>((size_t)Mp * 3 * d);
+  if ((rc = s.check("hipMalloc / copy failed"))) return rc;
+  if ((rc = to16(precision, dx, bx, Mp * d))) return rc;
+  if ((rc = to16(precision, dw, bw, (int64_t)3 * d * d))) return rc;
+  if ((rc = to16(precision, dctx, c16, ctx_rows * d))) return rc;
+  clear_noted_kernels();
+  if (fused) {
+    if ((rc = OPS(launch_headmajor_qkv, nullptr, bw, db, bwh, dbh, H, d))) return rc;
+    if ((rc = OPS(launch_gemm_colattn, nullptr, bx, bwh, dbh, c16, B, R, C, H, d, d))) return rc;
+  } else {
+    const SeqLayout col = {C, R * C, 1, C};
+    if ((rc = OPS(launch_gemm_bf16, nullptr, bx, bw, db, qkv, (int)Mp, 3 * d, d, d, d, 3 * d, EPI_BF16))) return rc;
+    if ((rc = OPS(launch_attention_seq_bf16, nullptr, qkv, c16, (int64_t)B * C, R, H, 3 * d, d, d, 2 * d, col))) return rc;
+  }
+  dbg_noted_text(plan, plan_bytes);
+  return down16(s, precision, c16, dctx, ctx_inout, ctx_rows * d);
 }
 
 int pg_dbg_layernorm(int device, const float* x, const float* gamma, const float* beta, float* y, int M, int d, float eps) {

@@ -45,6 +45,9 @@ def _cases():
                            "pg_dbg_gemm_ln: bad argument"),
         "pg_dbg_gemm_bench": ([0, 16, 64, 64, 0, 1, 1, _dbl(1)], 7, "pg_dbg_gemm_bench: bad argument"),
         "pg_dbg_qkv_attention_bench": ([0, 1, 32, 1, 1, _dbl(3), _dbl(1)], 5, "pg_dbg_qkv_attention_bench: T must be 32, 64, 128 or 256"),
+        # B = 1, R = 32, C = 1, H = 1, the fused launch, 32 context rows (tests/test_colattn_reference_cpu.py has every refusal)
+        "pg_dbg_colattn": ([0, BF16, _z(32, 64), _z(192, 64), _z(192), _z(32, 64), 32, 1, 32, 1, 1, 1, 0.0, None, 0], 3,
+                           "pg_dbg_colattn: null argument"),
         "pg_dbg_layernorm": ([0, x, g, g, _z(4, 64), 4, 64, 1e-5], 1, "pg_dbg_layernorm: bad argument"),
         "pg_dbg_layernorm_operand": ([0, BF16, x, g, g, _z(4, 64), 4, 64, 1e-5], 2, "pg_dbg_layernorm_operand: bad argument"),
         "pg_dbg_attention": ([0, BF16, qkv, ctx, 1, 16, 1], 2, "pg_dbg_attention: bad argument"),
